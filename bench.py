@@ -11,8 +11,13 @@ images sharded per rank, no data-path collective (weak scaling).
 
 Prints ONE json line (rank 0).  See DESIGN.md §measurement for the roofline terms.
 
-The line is self-certifying (N = 1): besides the timed default mode (split-bf16 reverse walk: hi*hi' + hi*lo' + lo*hi' in
-every layer, 16 mantissa bits on both operands — parity independent of the weight statistics) the same invocation
+A plain run sets up, warms up, times --steps steps and prints the headline (`value`, `ms_per_step`, `dtype`, ...).
+--dump-outputs DIR writes what the last timed step computed: a fixed sample of its heat-maps, DIR/heatmaps.npy
+(float32, at most DUMP_MAPS maps of 224x224x3).  The inputs are seeded, so two builds can be compared output for output.
+
+With --full the line is self-certifying (N = 1): besides the timed default mode (split-bf16 reverse walk: hi*hi' + hi*lo' +
+lo*hi' in every layer, 16 mantissa bits on both operands — parity independent of the weight statistics) the same invocation
+  * times 3 more steps with per-launch events on handle 0    -> "roofline" (also at N > 1)
   * times the exact-fp32 mode on the same batch              -> "fp32_mode"  {value, ms_per_step, roofline}
   * times the opt-in two-MFMA fp16 walk on the same batch    -> "fast_mode"  {value, ms_per_step, parity}
   * times the opt-in 2:4-sparse pooled boundaries            -> "sparse_pool_mode" {value, ms_per_step, distance from the default path}
@@ -83,6 +88,17 @@ def cpu_baseline(w, V, T, sample_tokens):
 
 
 PARITY_SAMPLES = [(0, 1), (0, 10), (31, 10), (13, 5)]        # (image, t) of the timed batch checked against the oracle
+DUMP_MAPS = 64                                               # heat-maps --dump-outputs keeps: 64 x 602 KB = 38.5 MB
+
+
+def dump_outputs(d, out):
+    """DIR/heatmaps.npy: the heat-maps of rows sorted(RandomState(0).choice(n, DUMP_MAPS)) of the (n, 224, 224, 3) result
+    (row = image * T + t - 1); the rows depend on n only."""
+    n = out.shape[0]
+    rows = np.sort(np.random.RandomState(0).choice(n, min(n, DUMP_MAPS), replace=False))
+    import torch
+    os.makedirs(d, exist_ok=True)
+    np.save(os.path.join(d, "heatmaps.npy"), out[torch.as_tensor(rows, device=out.device)].cpu().numpy())
 
 
 def algorithmic_bytes_per_walk(n_tokens, n_images, dataflow="as_built"):
@@ -341,15 +357,23 @@ def main():
     ap.add_argument("--sustained-seconds", type=float, default=5.0,
                     help="length of the `sustained` block: the same steps back to back for at least this long (0 = skip)")
     ap.add_argument("--no-configs", action="store_true", help="skip the config4 / config5 sub-blocks (BASELINE configs[3], [4])")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline, live PMC traffic, sustained, power, "
+                         "fp32 / fast / sparse modes, latency, config4 / config5, oracle parity, CPU baseline (the --no-* "
+                         "options above pick among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a fixed sample of the last timed step's heat-maps as "
+                                                          "DIR/heatmaps.npy (float32)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)    # one plain step under rocprofv3 (live_pmc_traffic)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d (launch with torch.distributed.run)" % (args.gpus, world))
-    extras = world == 1 and not args.child                  # the self-certifying blocks: rank 0 of a one-GPU run only
+    extras = args.full and world == 1 and not args.child    # the self-certifying blocks: rank 0 of a one-GPU run only
     live_traffic, live_src = (None, None)
     live32, live32_src = (None, None)
     if extras and not args.no_pmc:
@@ -495,8 +519,11 @@ def main():
     dt = timed_run(args.warmup, args.steps)
     if args.child:
         return
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs[(pipe.next_slot - 1) % len(outs)])     # the slot of the last timed step
     per_rank_ms = [round(t / args.steps * 1e3, 3) for t in per_rank]
-    n_launch, ms, flop = dominant_kernel()
+    if args.full:
+        n_launch, ms, flop = dominant_kernel()
     got = {args.precision: sampled(args.precision)} if extras and not args.no_parity else {}
 
     # ---- the rate the board HOLDS: the same steps for >= 5 s, power and clock sampled over that window
@@ -606,7 +633,7 @@ def main():
 
     if live_traffic:
         traffic, traffic_src = live_traffic["bytes"], live_src
-    else:
+    elif args.full:
         traffic, traffic_src = pmc_traffic_per_launch(args.precision)
         if traffic_src and live_src:
             traffic_src += " (%s)" % live_src
@@ -625,8 +652,9 @@ def main():
                        "schedule": "consecutive steps alternate between the handles, each on its own HIP stream (one batch's "
                                    "decoder / encode phases run under the previous batch's reverse walk)"
                                    if len(pipe.engines) > 1 else "one step after the other on one stream"},
-            "roofline": roofline_block(args.precision, n_launch, ms, flop, traffic, traffic_src),
         }
+        if args.full:
+            res["roofline"] = roofline_block(args.precision, n_launch, ms, flop, traffic, traffic_src)
         if live_traffic:
             res["roofline"]["traffic_detail"] = live_traffic
         if fp32_block:
@@ -668,7 +696,7 @@ def main():
             res["parity"] = par
             if fast_block and "f16x2" in par:
                 fast_block["parity"] = par["f16x2"]
-        if not args.no_cpu_baseline and args.cpu_sample_tokens > 0:
+        if args.full and not args.no_cpu_baseline and args.cpu_sample_tokens > 0:
             if world == 1:                                       # (rank 0 at N = 1 only: the other ranks would idle behind it)
                 res["cpu_baseline"] = cpu_baseline(w_host, V, T, args.cpu_sample_tokens)
             else:

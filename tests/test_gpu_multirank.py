@@ -39,7 +39,7 @@ def _torchrun(script_args, extra_env=None, timeout=900, nproc=2):
 
 
 def test_bench_two_ranks_one_gpu_gloo():
-    out = _torchrun(["bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+    out = _torchrun(["bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"])
     lines = [ln for ln in out.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out[-2000:]                       # rank 0 prints ONE line
     d = json.loads(lines[0])
