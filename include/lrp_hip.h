@@ -76,7 +76,7 @@ typedef struct lrp_config {
   int32_t conv_cout[LRP_MAX_CONV];
   int32_t conv_pool_after[LRP_MAX_CONV];
   char    conv_name[LRP_MAX_CONV][32];
-  int32_t L, D, H, E, V;        /* 196, 512, 512, 512, vocab  (config.py:14-15,36-40)   */
+  int32_t L, D, H, E, V;        /* 196, 512, 512, 512, vocab  (config.py:14-15,36-40);  D, H multiples of 8 */
   int32_t max_images;           /* capacity of the per-image caches                     */
   int32_t max_tokens;           /* capacity of one explain call (heat-maps)             */
   int32_t max_caption_len;      /* longest caption incl. EOS (config.py:34 -> 20+1)     */
@@ -96,7 +96,8 @@ typedef struct lrp_config {
 typedef struct lrp_handle lrp_handle;
 
 /* ExplainImgCaptioningAttentionModel.__init__ (E:24-40): build the engine for a
- * model geometry; allocates all device workspace. */
+ * model geometry; allocates all device workspace.  LRP_ERR_UNSUPPORTED when D or
+ * H is not a multiple of 8, or 2E+2H > 2048. */
 int lrp_create(const lrp_config* cfg, lrp_handle** out);
 int lrp_destroy(lrp_handle* h);
 

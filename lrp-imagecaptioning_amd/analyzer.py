@@ -65,8 +65,8 @@ class LRPSequentialPresetA(object):
         self._neuron_selection_mode = neuron_selection_mode
         self._model = model
         h, w, c = model.output_shape()
-        # the decoder half of the handle is idle here: minimal dims
-        self._engine = LRPEngine(decoder="adaptive", cnn_cfg=model.cnn_cfg, img_hw=model.img_hw, L=h * w, D=c, H=4, E=4,
+        # the decoder half of the handle is idle here: minimal dims (lrp_create: H a multiple of 8)
+        self._engine = LRPEngine(decoder="adaptive", cnn_cfg=model.cnn_cfg, img_hw=model.img_hw, L=h * w, D=c, H=8, E=8,
                                  V=4, max_images=max_batch, max_tokens=max_batch, max_caption_len=2, device=device,
                                  resnet=model.resnet)
         self._engine.set_weights(model.weights)

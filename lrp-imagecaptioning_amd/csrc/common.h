@@ -31,7 +31,6 @@ std::string& last_error_ref();
 struct Switches {
   int conv_halo = 1;        // LRP_CONV_HALO  0 never / 1 when a tile shape fills >= 90 % of the M tile / 2 always (ragged shapes: tests)
   int conv_breg = 1;        // LRP_CONV_BREG=0     N <= 64 backward convs without the weights-in-registers kernel
-  int conv_tile = 0;        // LRP_CONV_TILE  0 auto / 1 never the 8-wave tiles / 128 cap them at 256 x 128
   int conv_small = 1;       // LRP_CONV_SMALL=0    small grids keep the 128-row tiles (no 64 x 64 tiles)
   int conv_mid = 1;         // LRP_CONV_MID=0      no 128 x 64 tiles for the grids just above the small ones
   int epi_fast = 1;         // LRP_EPI_FAST=0      MUL / MUL_UP2 epilogues always through the general pass loop
@@ -44,18 +43,16 @@ struct Switches {
   int up2_gc = 1;           // LRP_UP2_GC=0        that interface with the full-resolution pool gate
   int up2_breg_pairs = 1;   // LRP_UP2_BREG_PAIRS=0  block2_conv1 writes its plain fp32 product instead of pairs
   int img_fold = 1;         // LRP_IMG_FOLD=0      image layer as its own launch
-  int dec_batched = 1;      // LRP_DEC_BATCHED=0   decoder LRP: one workgroup per unit instead of the step-synchronous scan
-  int dec_mfma_fwd = 1;     // LRP_DEC_MFMA_FWD=0  decoder forward: VALU skinny GEMMs
   int pool_fused = 1;       // LRP_POOL_FUSED=0    forward: max-pool + gate + pooled pairs as a pass of their own behind the conv
   int sparse_pool = 0;      // LRP_SPARSE_POOL=1   pooled boundaries with >= 256 output columns on the 2:4-sparse matrix cores (conv_sparse.h); read by encode and explain
   void load() {
     *this = Switches();
     auto rd = [](const char* name, int& v) { if (const char* e = getenv(name)) v = atoi(e); };
-    rd("LRP_CONV_HALO", conv_halo); rd("LRP_CONV_BREG", conv_breg); rd("LRP_CONV_TILE", conv_tile); rd("LRP_CONV_SMALL", conv_small);
+    rd("LRP_CONV_HALO", conv_halo); rd("LRP_CONV_BREG", conv_breg); rd("LRP_CONV_SMALL", conv_small);
     rd("LRP_CONV_MID", conv_mid); rd("LRP_EPI_FAST", epi_fast); rd("LRP_UP2_PW", up2_pw); rd("LRP_TILE_ORDER", tile_order);
     rd("LRP_FWD_EMIT", fwd_emit); rd("LRP_FWD_IL", fwd_il); rd("LRP_IMG_FUSED", img_fused); rd("LRP_UP2_COMPACT", up2_compact);
-    rd("LRP_UP2_GC", up2_gc); rd("LRP_UP2_BREG_PAIRS", up2_breg_pairs); rd("LRP_IMG_FOLD", img_fold); rd("LRP_DEC_BATCHED", dec_batched);
-    rd("LRP_DEC_MFMA_FWD", dec_mfma_fwd); rd("LRP_SPARSE_POOL", sparse_pool); rd("LRP_POOL_FUSED", pool_fused);
+    rd("LRP_UP2_GC", up2_gc); rd("LRP_UP2_BREG_PAIRS", up2_breg_pairs); rd("LRP_IMG_FOLD", img_fold);
+    rd("LRP_SPARSE_POOL", sparse_pool); rd("LRP_POOL_FUSED", pool_fused);
   }
 };
 inline Switches& sw() {

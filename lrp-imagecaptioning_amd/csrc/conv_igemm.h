@@ -1813,9 +1813,8 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
 //   n64   : 2,2,2,1 -> 128 x  64   (N == 64 layers)           48 KB LDS, 3 blocks/CU
 //   n32   : 4,1,1,1 -> 128 x  32   (N <= 32: tiny test nets)  40 KB LDS
 //   w256  : 2,4,4,2 -> 256 x 256   8 waves, 128 KB LDS, 1 block/CU   [bf16x3, N % 256 == 0]
-//   w128  : 4,2,2,2 -> 256 x 128   8 waves,  96 KB LDS, 1 block/CU   [bf16x3, N % 128 == 0]
 // bf16x3 spends 5.3x fewer matrix cycles per byte staged, so its limiter is the L2 -> LDS path
-// (~43 GB/s per CU at 128 x 128): the 8-wave tiles stage 25 % / 50 % fewer bytes per FLOP.
+// (~43 GB/s per CU at 128 x 128): the 8-wave tile stages 50 % fewer bytes per FLOP.
 struct ConvTile { int BM, BN; };
 inline ConvTile conv_pick_tile(int N) {
   if (N > 64) return {128, 128};
@@ -1824,9 +1823,6 @@ inline ConvTile conv_pick_tile(int N) {
 }
 inline int conv_npad(int N) { ConvTile t = conv_pick_tile(N); return (N + t.BN - 1) / t.BN * t.BN; }
 inline int conv_cinp(int Cin) { return (Cin + 31) / 32 * 32; }
-
-// switch LRP_CONV_TILE: 0 = auto, 1 = never use the 8-wave tiles, 128 = cap them at 256 x 128
-inline int conv_tile_override() { return sw().conv_tile; }
 
 // small grids take 64 x 64 tiles (conv_launch_epi): LRP_CONV_SMALL=0 disables; they are used up to a 128-row grid of 128 tiles
 // (4x as many 64 x 64 workgroups = the 512 that are resident at once; beyond that a second round of small tiles costs more
@@ -1877,16 +1873,12 @@ inline bool conv_takes_breg(int n_out, int H, int W, bool have_frag) {
   return conv_halo_geom(128, H, W, tw, th, hrows) >= 0.9f;
 }
 
-// The 8-wave tile width of a split-format reverse-walk launch: 256 (256 x 256 tile), 128 (256 x 128, LRP_CONV_TILE=128 only) or 0.
+// The 8-wave tile width of a split-format reverse-walk launch: 256 (256 x 256 tile) or 0.
 // ONE rule for conv_launch_epi and conv_takes_pw.
 inline int conv_wide_tile(int n_out, long mrows) {
-  if (n_out < 128 || (n_out % 128) != 0) return 0;
-  int wide = (n_out % 256) == 0 ? 256 : 0;               // measured: 256 x 128 loses to two 128 x 128 blocks per CU
-  if (conv_tile_override() == 128) wide = 128;
-  if (conv_tile_override() == 1) wide = 0;
+  if (n_out < 256 || (n_out % 256) != 0) return 0;      // measured: a 256 x 128 tile loses to two 128 x 128 blocks per CU
   // one 8-wave block per CU: only worth it when the grid still fills the chip ~1.5 times over
-  if (wide && ((mrows + 255) / 256) * (n_out / wide) < 400) wide = 0;
-  return wide;
+  return ((mrows + 255) / 256) * (n_out / 256) < 400 ? 0 : 256;
 }
 
 // Can the interleaved dual forward of a layer with `cout` channels on NB images of H x W pool in its epilogue
@@ -1906,9 +1898,7 @@ inline bool conv_takes_pw(int n_out, int NB, int H, int W) {
   if (!sw().up2_pw || conv_halo_mode() <= 0 || conv_pick_tile(n_out).BN != 128 || (H & 1) || (W & 1)) return false;
   const long mrows = (long)NB * H * W;
   int BM = 128, threads = 256;
-  const int wide = conv_wide_tile(n_out, mrows);
-  if (wide == 128) return false;                          // (LRP_CONV_TILE=128: the 256 x 128 tile has no resident-image variant)
-  if (wide == 256) { BM = 256; threads = 512; }
+  if (conv_wide_tile(n_out, mrows) == 256) { BM = 256; threads = 512; }
   if (BM == 128 && conv_small_tile_on() && ((mrows + 127) / 128) * ((n_out + 127) / 128) <= conv_small_tile_blocks()) return false;
   int tw, th, hrows;
   if (conv_halo_geom(BM, H, W, tw, th, hrows) < 0.9f) return false;
@@ -2098,7 +2088,7 @@ inline hipError_t conv_launch_epi(ConvArgs a, hipStream_t st) {
       hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 1, 1, EPI, PREC, false, false, TERMS, CONV_SMALL_NS>), dim3(a.m_tiles * a.n_tiles), dim3(256), 0, st, a);
       return hipGetLastError();
     }
-    if (a.taps == 9 && mode > 0 && (t.BN >= 128 || (mode == 2 && t.BN >= 64)) && wide != 128) {
+    if (a.taps == 9 && mode > 0 && (t.BN >= 128 || (mode == 2 && t.BN >= 64))) {
       const float u = conv_halo_geom(t.BM, a.H, a.W, a.tw, a.th, a.hrows);
       if (u >= 0.9f || (mode == 2 && u > 0.f)) {
         a.nyh = a.NB * a.H;
@@ -2116,8 +2106,8 @@ inline hipError_t conv_launch_epi(ConvArgs a, hipStream_t st) {
       }
     }
   }
-  // Only the resident-image kernels above read the compact pool interface.  A launch that carries it and got here (tile
-  // override, halo geometry below 0.9 for the tile actually chosen, fp32 operands) would run a kernel that ignores up2_src and
+  // Only the resident-image kernels above read the compact pool interface.  A launch that carries it and got here (halo
+  // switch off, halo geometry below 0.9 for the tile actually chosen, fp32 operands) would run a kernel that ignores up2_src and
   // reads a.in as a dense tensor: refuse instead of producing wrong heat-maps silently.
   if (a.up2_src || a.pool_gc) return hipErrorInvalidValue;
   if (small_tile) {
@@ -2130,10 +2120,6 @@ inline hipError_t conv_launch_epi(ConvArgs a, hipStream_t st) {
   if constexpr (PREC != PREC_FP32) {
     if (wide == 256) {
       hipLaunchKernelGGL((conv_igemm_kernel<2, 4, 4, 2, EPI, PREC, false, false, TERMS>), grid, dim3(512), 0, st, a);
-      return hipGetLastError();
-    }
-    if (wide == 128) {
-      hipLaunchKernelGGL((conv_igemm_kernel<4, 2, 2, 2, EPI, PREC, false, false, TERMS>), grid, dim3(512), 0, st, a);
       return hipGetLastError();
     }
   }

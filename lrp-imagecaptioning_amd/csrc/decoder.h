@@ -34,11 +34,11 @@ struct Decoder {
   std::map<std::string, DevBuf> raw_dev;
   bool finalized = false;
   // packed device weights
-  DevBuf w_if_dual, w_v, zero_bias, b_if, Wcat, bcat, Wg, Ws, vvec, Wglob, bglob, Wout, bout, emb, WgT, WglobT, WifT;
+  DevBuf w_if_dual, w_v, zero_bias, b_if, Wcat, bcat, Wg, Ws, vvec, Wglob, bglob, Wout, bout, emb, WglobT;
   // per-image static part
   DevBuf vfeat, if_pre, ipre, stat, avg, glob_pre;
   // per-step scratch
-  DevBuf xh, zgate, hproj, sproj, u, att_pre;
+  DevBuf xh, u, att_pre;
   // cached state (what the reference leaves on `self`)
   DevBuf state_arena;              // declared before its views (destroyed after them)
   std::map<std::string, StateBuf> state;
@@ -55,10 +55,9 @@ struct Decoder {
   int B_cur = 0;
   bool have_forward = false;
   // explain scratch
-  DevBuf rctx, ravg, tailA, w_ifT_pk, w_ifT_pks;
-  int prec = PREC_BF16X3;   // arithmetic of the tail GEMM (follows lrp_set_precision)
+  DevBuf rctx, ravg, tailA, w_ifT_pk;
   // grid-TD only
-  DevBuf Wcat2, bcat2, Wg2T, xh1d, xh2d, zg1d, zg2d, hprojd, sprojd, h2u, rho;
+  DevBuf Wcat2, bcat2, xh1d, xh2d, zg1d, zg2d, hprojd, sprojd, h2u, rho;
   // step-synchronous LRP scan (decoder_batched_kernels.h; allocated and packed on first use)
   bool bx_ready = false;
   DevBuf bxWg1, bxWg2, bx_rc, bx_rh, bx_rglob, bx_q32, bx_acc32;
@@ -71,9 +70,8 @@ struct Decoder {
     kind = c.decoder; L = c.L; D = c.D; H = c.H; E = c.E; V = c.V; Tm = c.max_caption_len;
     B_max = c.max_images; NT_max = c.max_tokens; sos = c.sos_id; eos = c.eos_id;
     if (L < 1 || D < 4 || H < 4 || E < 4 || V < 2) return fail(LRP_ERR_INVALID, "bad decoder dims");
-    if (D % 4 || H % 4) return fail(LRP_ERR_UNSUPPORTED, "D and H must be multiples of 4");
-    if (2 * E + H > SCAN_MAXR * 256 || H + 2 * E + H > SCAN_MAXR * 256)
-      return fail(LRP_ERR_UNSUPPORTED, "2E+H too large for the scan kernel");
+    if (D % 8 || H % 8) return fail(LRP_ERR_UNSUPPORTED, "D and H must be multiples of 8");
+    if (2 * E + 2 * H > 2048) return fail(LRP_ERR_UNSUPPORTED, "2E+2H too large for the LRP scan (bx_* / gbx_* kernels)");
     const size_t B = B_max, S = Tm + 1;
     // every array prepare_static has to zero lives in ONE arena (state_arena): one memset per forward instead of one per
     // array [MI355X, single image: 14 fills of ~4.8 us each on the critical path].  Two passes: sizes, then the views.
@@ -117,9 +115,6 @@ struct Decoder {
     LRP_TRY(avg.alloc(B * D * 4, total));
     LRP_TRY(glob_pre.alloc(B * E * 4, total));
     LRP_TRY(xh.alloc(B * (2 * E + 2 * H) * 4, total));
-    LRP_TRY(zgate.alloc(B * 5 * H * 4 * KS_GATE, total));
-    LRP_TRY(hproj.alloc(B * H * 4 * KS_PROJ, total));
-    LRP_TRY(sproj.alloc(B * H * 4 * KS_PROJ, total));
     LRP_TRY(att_pre.alloc(B * (L + 1) * 4, total));
     LRP_TRY(st("#u", B * Tm * H, 8));
     {
@@ -140,7 +135,7 @@ struct Decoder {
     }
     LRP_TRY(cap_dev.alloc(B * Tm * sizeof(int), total));
     LRP_TRY(rctx.alloc((size_t)NT_max * H * 8, total));
-    if ((H & 7) == 0) LRP_TRY(tailA.alloc((size_t)NT_max * L * H * 4, total));
+    LRP_TRY(tailA.alloc((size_t)NT_max * L * H * 4, total));
     LRP_TRY(ravg.alloc((size_t)NT_max * D * 8, total));
     cap_host.assign(B * Tm, eos);
     len_host.assign(B, 0);
@@ -216,7 +211,7 @@ struct Decoder {
     return LRP_OK;
   }
   // every derived operand copy (those that exist: the scan / gradient packs only once prepared) from Keras-layout DEVICE
-  // matrices: strided D2D copies, tiled transposes, the split kernel.  Buffers must exist with zeroed padding.
+  // matrices: strided D2D copies and tiled transposes.  Buffers must exist with zeroed padding.
   int repack_device(const std::function<const float*(const char*)>& Wd, hipStream_t st) {
     const bool td = kind == LRP_DEC_GRIDTD;
     const float *Wif = Wd("image_features_W"), *Wgl = Wd("global_W");
@@ -225,10 +220,7 @@ struct Decoder {
     tr2d(st, Wif, H, D, H, w_if_dual.as<float>() + (size_t)H * KD, KD);
     tr2d(st, Wd(td ? "W_va" : "Wv"), H, H, H, w_v.as<float>(), KH);
     tr2d(st, Wgl, E, D, E, WglobT.as<float>(), D);
-    tr2d(st, Wif, H, D, H, WifT.as<float>(), D);
     LRP_HIP_CHECK(cp2d(st, Wif, H, D, H, w_ifT_pk.as<float>(), KH));                     // [d][j] = W_if[d][j], K padded
-    hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(w_ifT_pk.bytes / 32)), dim3(256), 0, st, w_ifT_pk.as<float>(),
-                       w_ifT_pks.as<float>(), w_ifT_pk.bytes / 32);
     auto copy = [&](DevBuf& d, const char* nm, size_t n) {
       return hipMemcpyAsync(d.p, Wd(nm), n * 4, hipMemcpyDeviceToDevice, st);
     };
@@ -237,12 +229,12 @@ struct Decoder {
     LRP_HIP_CHECK(copy(bout, "output_b", V)); LRP_HIP_CHECK(copy(emb, "embedding", (size_t)V * E));
     LRP_HIP_CHECK(copy(Wg, td ? "W_ha" : "Wg", (size_t)H * H)); LRP_HIP_CHECK(copy(Ws, td ? "W_s" : "Ws", (size_t)H * H));
     LRP_HIP_CHECK(copy(vvec, td ? "W_a" : "V", H));
-    // one LSTM: Wcat (Kd x N) = [[Wi | Wsx]; [Wh | Wsh]] (N = 5H with a sentinel, else 4H), bias row, transposed gate-g
-    // block WgT (H x Kd), the scan's GEMM operand (rows of the gate-g block, K padded) and the gradient path's pack_rows
+    // one LSTM: Wcat (Kd x N) = [[Wi | Wsx]; [Wh | Wsh]] (N = 5H with a sentinel, else 4H), bias row, the scan's GEMM
+    // operand (rows of the gate-g block, K padded) and the gradient path's pack_rows
     auto lstm = [&](const char* wi, const char* wh, const char* wsx, const char* wsh, const char* bias, int Kx, DevBuf& Wc,
-                    DevBuf& bc, DevBuf& WgT_, DevBuf* bxW, DevBuf* gW) -> int {
+                    DevBuf& bc, DevBuf* bxW, DevBuf* gW) -> int {
       const float *Wi = Wd(wi), *Wh = Wd(wh);
-      const int Kd = Kx + H, Nn = wsx ? 5 * H : 4 * H;
+      const int Nn = wsx ? 5 * H : 4 * H;
       float* wc = Wc.as<float>();
       LRP_HIP_CHECK(cp2d(st, Wi, 4 * H, Kx, 4 * H, wc, Nn));
       LRP_HIP_CHECK(cp2d(st, Wh, 4 * H, H, 4 * H, wc + (size_t)Kx * Nn, Nn));
@@ -251,8 +243,6 @@ struct Decoder {
         LRP_HIP_CHECK(cp2d(st, Wd(wsh), H, H, H, wc + (size_t)Kx * Nn + 4 * H, Nn));
       }
       LRP_HIP_CHECK(hipMemcpyAsync(bc.p, Wd(bias), (size_t)4 * H * 4, hipMemcpyDeviceToDevice, st));
-      tr2d(st, Wi + 2 * H, 4 * H, Kx, H, WgT_.as<float>(), Kd);
-      tr2d(st, Wh + 2 * H, 4 * H, H, H, WgT_.as<float>() + Kx, Kd);
       if (bxW) {
         LRP_HIP_CHECK(cp2d(st, Wi + 2 * H, 4 * H, Kx, H, bxW->as<float>(), KH));
         LRP_HIP_CHECK(cp2d(st, Wh + 2 * H, 4 * H, H, H, bxW->as<float>() + (size_t)Kx * KH, KH));
@@ -264,12 +254,12 @@ struct Decoder {
       return LRP_OK;
     };
     if (td) {
-      LRP_TRY(lstm("td_Wi", "td_Wh", "W_x", "W_h", "td_b", H + 2 * E, Wcat, bcat, WgT, bx_ready ? &bxWg1 : nullptr,
+      LRP_TRY(lstm("td_Wi", "td_Wh", "W_x", "W_h", "td_b", H + 2 * E, Wcat, bcat, bx_ready ? &bxWg1 : nullptr,
                    grad_ready ? &gW1 : nullptr));
-      LRP_TRY(lstm("lang_Wi", "lang_Wh", nullptr, nullptr, "lang_b", 2 * H, Wcat2, bcat2, Wg2T, bx_ready ? &bxWg2 : nullptr,
+      LRP_TRY(lstm("lang_Wi", "lang_Wh", nullptr, nullptr, "lang_b", 2 * H, Wcat2, bcat2, bx_ready ? &bxWg2 : nullptr,
                    grad_ready ? &gW2 : nullptr));
     } else {
-      LRP_TRY(lstm("lstm_Wi", "lstm_Wh", "Wx", "Wh", "lstm_b", 2 * E, Wcat, bcat, WgT, bx_ready ? &bxWg1 : nullptr,
+      LRP_TRY(lstm("lstm_Wi", "lstm_Wh", "Wx", "Wh", "lstm_b", 2 * E, Wcat, bcat, bx_ready ? &bxWg1 : nullptr,
                    grad_ready ? &gW1 : nullptr));
     }
     if (grad_ready) {
@@ -333,25 +323,21 @@ struct Decoder {
     for (int d = 0; d < D; ++d)
       for (int e = 0; e < E; ++e) pk[(size_t)e * D + d] = Wgl[(size_t)d * E + e];
     LRP_TRY(upload(WglobT, pk, total));
-    pk.assign((size_t)H * D, 0.f);
-    for (int d = 0; d < D; ++d)
-      for (int j = 0; j < H; ++j) pk[(size_t)j * D + d] = Wif[(size_t)d * H + j];
-    LRP_TRY(upload(WifT, pk, total));
-    {  // the same matrix as the B operand of the MFMA tail GEMM: out[m][d] = sum_j A[m][j] * W_if[d][j]
+    {  // W_if as the B operand of the MFMA tail GEMM: out[m][d] = sum_j A[m][j] * W_if[d][j]
+      pk.assign((size_t)H * D, 0.f);
+      for (int d = 0; d < D; ++d)
+        for (int j = 0; j < H; ++j) pk[(size_t)j * D + d] = Wif[(size_t)d * H + j];
       const int Np = conv_npad(D), K = conv_cinp(H);
-      std::vector<float> g((size_t)Np * K, 0.f), gs((size_t)Np * K);
-      pack_conv_fwd(pk.data(), 1, H, D, 0, Np, g.data());          // pk = WifT [j][d] == "w[ci=j][co=d]"
-      pack_split8(g.data(), g.size(), gs.data());
+      std::vector<float> g((size_t)Np * K, 0.f);
+      pack_conv_fwd(pk.data(), 1, H, D, 0, Np, g.data());          // pk [j][d] == "w[ci=j][co=d]"
       LRP_TRY(upload(w_ifT_pk, g, total));
-      LRP_TRY(upload(w_ifT_pks, gs, total));
     }
     return LRP_OK;
   }
 
-  // [x | h] . [[Wi | Wsent_x] ; [Wh | Wsent_h]] packed (Kx+H) x (4H [+H]) and the transposed gate-g block
+  // [x | h] . [[Wi | Wsent_x] ; [Wh | Wsent_h]] packed (Kx+H) x (4H [+H])
   int pack_lstm(const std::vector<float>& Wi, const std::vector<float>& Wh, const std::vector<float>* Wsx,
-                const std::vector<float>* Wsh, const std::vector<float>& bias, int Kx, DevBuf& Wc, DevBuf& bc, DevBuf& WgT_,
-                int64_t* total) {
+                const std::vector<float>* Wsh, const std::vector<float>& bias, int Kx, DevBuf& Wc, DevBuf& bc, int64_t* total) {
     const int Kd = Kx + H, Nn = Wsx ? 5 * H : 4 * H;
     std::vector<float> pk((size_t)Kd * Nn, 0.f);
     for (int k = 0; k < Kd; ++k)
@@ -365,11 +351,6 @@ struct Decoder {
     std::vector<float> bcv(Nn, 0.f);
     std::copy(bias.begin(), bias.end(), bcv.begin());
     LRP_TRY(upload(bc, bcv, total));
-    pk.assign((size_t)H * Kd, 0.f);                                  // WgT[j][d] = [Wi;Wh][d][2H+j]
-    for (int d = 0; d < Kd; ++d)
-      for (int j = 0; j < H; ++j)
-        pk[(size_t)j * Kd + d] = d < Kx ? Wi[(size_t)d * 4 * H + 2 * H + j] : Wh[(size_t)(d - Kx) * 4 * H + 2 * H + j];
-    LRP_TRY(upload(WgT_, pk, total));
     return LRP_OK;
   }
 
@@ -380,8 +361,8 @@ struct Decoder {
     LRP_TRY(need("lang_Wi", {2 * H, 4 * H})); LRP_TRY(need("lang_Wh", {H, 4 * H})); LRP_TRY(need("lang_b", {4 * H}));
     LRP_TRY(need("W_ha", {H, H})); LRP_TRY(need("W_a", {H})); LRP_TRY(need("W_x", {K1, H}));
     LRP_TRY(need("W_h", {H, H})); LRP_TRY(need("W_s", {H, H}));
-    LRP_TRY(pack_lstm(raw["td_Wi"], raw["td_Wh"], &raw["W_x"], &raw["W_h"], raw["td_b"], K1, Wcat, bcat, WgT, total));
-    LRP_TRY(pack_lstm(raw["lang_Wi"], raw["lang_Wh"], nullptr, nullptr, raw["lang_b"], 2 * H, Wcat2, bcat2, Wg2T, total));
+    LRP_TRY(pack_lstm(raw["td_Wi"], raw["td_Wh"], &raw["W_x"], &raw["W_h"], raw["td_b"], K1, Wcat, bcat, total));
+    LRP_TRY(pack_lstm(raw["lang_Wi"], raw["lang_Wh"], nullptr, nullptr, raw["lang_b"], 2 * H, Wcat2, bcat2, total));
     LRP_TRY(upload(Wg, raw["W_ha"], total));
     LRP_TRY(upload(Ws, raw["W_s"], total));
     LRP_TRY(upload(vvec, raw["W_a"], total));
@@ -426,13 +407,10 @@ struct Decoder {
     LRP_TRY(zalloc(zero_bias, (size_t)std::max(H, E), total, st));
     LRP_TRY(zalloc(b_if, H, total, st)); LRP_TRY(zalloc(Wglob, (size_t)D * E, total, st)); LRP_TRY(zalloc(bglob, E, total, st));
     LRP_TRY(zalloc(Wout, (size_t)H * V, total, st)); LRP_TRY(zalloc(bout, V, total, st)); LRP_TRY(zalloc(emb, (size_t)V * E, total, st));
-    LRP_TRY(zalloc(WglobT, (size_t)E * D, total, st)); LRP_TRY(zalloc(WifT, (size_t)H * D, total, st));
-    LRP_TRY(zalloc(w_ifT_pk, (size_t)conv_npad(D) * KH, total, st)); LRP_TRY(zalloc(w_ifT_pks, (size_t)conv_npad(D) * KH, total, st));
+    LRP_TRY(zalloc(WglobT, (size_t)E * D, total, st)); LRP_TRY(zalloc(w_ifT_pk, (size_t)conv_npad(D) * KH, total, st));
     LRP_TRY(zalloc(Wcat, (size_t)(K1 + H) * 5 * H, total, st)); LRP_TRY(zalloc(bcat, (size_t)5 * H, total, st));
-    LRP_TRY(zalloc(WgT, (size_t)H * (K1 + H), total, st));
     if (td) {
       LRP_TRY(zalloc(Wcat2, (size_t)3 * H * 4 * H, total, st)); LRP_TRY(zalloc(bcat2, (size_t)4 * H, total, st));
-      LRP_TRY(zalloc(Wg2T, (size_t)H * 3 * H, total, st));
     }
     LRP_TRY(zalloc(Wg, (size_t)H * H, total, st)); LRP_TRY(zalloc(Ws, (size_t)H * H, total, st)); LRP_TRY(zalloc(vvec, H, total, st));
     finalized = true;
@@ -451,9 +429,8 @@ struct Decoder {
     LRP_TRY(need("lstm_Wi", {2 * E, 4 * H})); LRP_TRY(need("lstm_Wh", {H, 4 * H})); LRP_TRY(need("lstm_b", {4 * H}));
     LRP_TRY(need("Wg", {H, H})); LRP_TRY(need("V", {H}));
     LRP_TRY(need("Wx", {2 * E, H})); LRP_TRY(need("Wh", {H, H})); LRP_TRY(need("Ws", {H, H}));
-    // [x | h_prev] . [[Wi | Wx] ; [Wh | Wh_sentinel]] -> 4H gate pre-activations + H sentinel gate;
-    // transposed gate-g block for the LRP scan (E:556-558)
-    LRP_TRY(pack_lstm(raw["lstm_Wi"], raw["lstm_Wh"], &raw["Wx"], &raw["Wh"], raw["lstm_b"], 2 * E, Wcat, bcat, WgT, total));
+    // [x | h_prev] . [[Wi | Wx] ; [Wh | Wh_sentinel]] -> 4H gate pre-activations + H sentinel gate
+    LRP_TRY(pack_lstm(raw["lstm_Wi"], raw["lstm_Wh"], &raw["Wx"], &raw["Wh"], raw["lstm_b"], 2 * E, Wcat, bcat, total));
     LRP_TRY(upload(Wg, raw["Wg"], total));
     LRP_TRY(upload(Ws, raw["Ws"], total));
     LRP_TRY(upload(vvec, raw["V"], total));
@@ -545,18 +522,13 @@ struct Decoder {
     }
     hipLaunchKernelGGL(mean_rows_kernel, dim3(B, (D + 63) / 64), dim3(64), 0, st, feat_dev, avg.as<float>(), L, D);
     LRP_HIP_CHECK(hipGetLastError());
-    if (mfma_forward()) {
-      // on the fp32 matrix cores like the products of a step (K split over the chip, slices reduced in index order): the
-      // VALU GEMV walks K = D alone in 8 workgroups [MI355X, one image: 70 us]
-      LRP_TRY(need_sg_ws());
-      SgemmArgs a{};
-      a.A = avg.as<float>(); a.lda = D; a.B = Wglob.as<float>(); a.ldb = E; a.C = glob_pre.as<float>(); a.ldc = E;
-      a.M = B; a.N = E; a.K = D; a.bias = bglob.as<float>();
-      LRP_HIP_CHECK(sgemm(a, sg_ws.as<float>(), SG_WS_FLOATS, st));
-    } else {
-      LRP_HIP_CHECK((skinny<float, float, float>(avg.as<float>(), D, Wglob.as<float>(), E, bglob.as<float>(),
-                                                 glob_pre.as<float>(), E, B, D, E, 0, st)));
-    }
+    // on the fp32 matrix cores like the products of a step (K split over the chip, slices reduced in index order): a VALU
+    // GEMV walks K = D alone in 8 workgroups [MI355X, one image: 70 us]
+    LRP_TRY(need_sg_ws());
+    SgemmArgs a{};
+    a.A = avg.as<float>(); a.lda = D; a.B = Wglob.as<float>(); a.ldb = E; a.C = glob_pre.as<float>(); a.ldc = E;
+    a.M = B; a.N = E; a.K = D; a.bias = bglob.as<float>();
+    LRP_HIP_CHECK(sgemm(a, sg_ws.as<float>(), SG_WS_FLOATS, st));
     return LRP_OK;
   }
 
@@ -569,48 +541,33 @@ struct Decoder {
       hipLaunchKernelGGL(dec_prep_x_kernel, dim3(B), dim3(256), 0, st, emb.as<float>(), glob_pre.as<float>(), ht,
                          cap_dev.as<int>(), xh.as<float>(), S_<float>("xt"), i, Tm, E, H, V, sos);
       LRP_HIP_CHECK(hipGetLastError());
-      const size_t zslab = (size_t)B_max * 5 * H, pslab = (size_t)B_max * H;
       // the three products of a step on the fp32 matrix cores (train_gemm.h: 64 x 128 tiles, K split over ~240
-      // workgroups, slices reduced in index order) — LRP_DEC_MFMA_FWD=0: the VALU skinny GEMM with consumer-side slabs
-      const bool mf = mfma_forward();
-      int ksg = KS_GATE, ksp = KS_PROJ;
-      size_t zsl = zslab, psl = pslab;
-      const float *zsrc = zgate.as<float>(), *zbias = nullptr, *hsrc = hproj.as<float>(), *ssrc = sproj.as<float>();
-      // MFMA path: the K-split slices stay in the workspace and the CONSUMER kernel adds them up (index order, then the bias
-      // — the arithmetic of sgemm_reduce_kernel, so the results do not change): three launches fewer per step.  Regions of
-      // the workspace: gates [0, 3/4), h projection [3/4, 7/8), sentinel projection [7/8, 1).
+      // workgroups).  The K-split slices stay in the workspace and the CONSUMER kernel adds them up (index order, then the
+      // bias — the arithmetic of sgemm_reduce_kernel, so the results do not change): three launches fewer per step.  Regions
+      // of the workspace: gates [0, 3/4), h projection [3/4, 7/8), sentinel projection [7/8, 1).
       constexpr size_t WS_G = SG_WS_FLOATS / 4 * 3, WS_P = SG_WS_FLOATS / 8;
-      if (mf) {
-        LRP_TRY(need_sg_ws());
+      LRP_TRY(need_sg_ws());
+      float *zsrc = sg_ws.as<float>(), *hsrc = zsrc + WS_G, *ssrc = hsrc + WS_P;
+      int ksg = 0, ksp = 0;
+      {
         SgemmArgs a{};
         a.A = xh.as<float>(); a.lda = Kd; a.B = Wcat.as<float>(); a.ldb = 5 * H; a.M = B; a.N = 5 * H; a.K = Kd;
-        LRP_HIP_CHECK(sgemm(a, sg_ws.as<float>(), WS_G, st, &ksg));
-        zsrc = sg_ws.as<float>(); zsl = (size_t)B * 5 * H; zbias = bcat.as<float>();
-      } else {
-        LRP_HIP_CHECK((skinny<float, float, float>(xh.as<float>(), Kd, Wcat.as<float>(), 5 * H, bcat.as<float>(),
-                                                   zgate.as<float>(), 5 * H, B, Kd, 5 * H, 0, st, KS_GATE, zslab)));
+        LRP_HIP_CHECK(sgemm(a, zsrc, WS_G, st, &ksg));
       }
-      hipLaunchKernelGGL(dec_pointwise_kernel, dim3(B, (H + 63) / 64), dim3(64), 0, st, zsrc, ksg, zsl, zbias, ht,
-                         S_<float>("ct"), S_<float>("gt"), S_<float>("it_act"), S_<float>("ft_act"), stt,
+      hipLaunchKernelGGL(dec_pointwise_kernel, dim3(B, (H + 63) / 64), dim3(64), 0, st, zsrc, ksg, (size_t)B * 5 * H,
+                         bcat.as<float>(), ht, S_<float>("ct"), S_<float>("gt"), S_<float>("it_act"), S_<float>("ft_act"), stt,
                          S_<float>("ot_act"), i, Tm, H);
       LRP_HIP_CHECK(hipGetLastError());
-      if (mf) {
+      {
         SgemmArgs a{};
         a.lda = (long)S * H; a.ldb = H; a.M = B; a.N = H; a.K = H;
         // h . Wg and s . Ws: same shape, ONE launch (the upper half of the grid's z takes the second pair)
         a.A = ht + (size_t)(i + 1) * H; a.B = Wg.as<float>();
-        a.A2 = stt + (size_t)(i + 1) * H; a.B2 = Ws.as<float>(); a.ws2 = sg_ws.as<float>() + WS_G + WS_P;
-        LRP_HIP_CHECK(sgemm(a, sg_ws.as<float>() + WS_G, WS_P, st, &ksp));
-        psl = (size_t)B * H;
-        hsrc = sg_ws.as<float>() + WS_G; ssrc = sg_ws.as<float>() + WS_G + WS_P;
-      } else {
-        LRP_HIP_CHECK((skinny<float, float, float>(ht + (size_t)(i + 1) * H, S * H, Wg.as<float>(), H, nullptr,
-                                                   hproj.as<float>(), H, B, H, H, 0, st, KS_PROJ, pslab)));
-        LRP_HIP_CHECK((skinny<float, float, float>(stt + (size_t)(i + 1) * H, S * H, Ws.as<float>(), H, nullptr,
-                                                   sproj.as<float>(), H, B, H, H, 0, st, KS_PROJ, pslab)));
+        a.A2 = stt + (size_t)(i + 1) * H; a.B2 = Ws.as<float>(); a.ws2 = ssrc;
+        LRP_HIP_CHECK(sgemm(a, hsrc, WS_P, st, &ksp));
       }
       hipLaunchKernelGGL(dec_att_scores_kernel, dim3(B, (L + 1 + ATT_ROWS - 1) / ATT_ROWS), dim3(256),
-                         (size_t)2 * H * sizeof(float), st, hsrc, ssrc, ksp, psl,
+                         (size_t)2 * H * sizeof(float), st, hsrc, ssrc, ksp, (size_t)B * H,
                          stat.as<float>(), vvec.as<float>(), att_pre.as<float>(), L, H);
       LRP_HIP_CHECK(hipGetLastError());
       hipLaunchKernelGGL(dec_att_finish_kernel, dim3(B, (H + 63) / 64), dim3(64), (size_t)(L + 8) * sizeof(float), st,
@@ -734,75 +691,42 @@ struct Decoder {
 
   int explain_gridtd(int n, const int* img_dev, const int* t_dev, const int32_t* t_host, const float* feat_dev,
                      float* R_feat_dev, float* att_dev, double* rwords_dev, hipStream_t st) {
-    GtdExplainArgs a{};
-    a.img_idx = img_dev; a.tpos = t_dev; a.cap = cap_dev.as<int>();
-    a.h1t = S_<double>("h1t"); a.c1t = S_<double>("c1t"); a.g1t = S_<double>("g1t"); a.i1t = S_<double>("i1t_act");
-    a.f1t = S_<double>("f1t_act"); a.h2t = S_<double>("h2t"); a.c2t = S_<double>("c2t"); a.g2t = S_<double>("g2t");
-    a.i2t = S_<double>("i2t_act"); a.f2t = S_<double>("f2t_act"); a.x1t = S_<double>("x1t"); a.x2t = S_<double>("x2t");
-    a.ctx = S_<double>("context"); a.st = S_<double>("st"); a.chat = S_<double>("context_hat"); a.beta = S_<double>("beta");
-    a.att = S_<double>("attention"); a.preds = S_<double>("caption_preds");
-    a.Wout = Wout.as<float>(); a.Wg1T = WgT.as<float>(); a.Wg2T = Wg2T.as<float>(); a.WglobT = WglobT.as<float>();
-    a.avg = avg.as<float>(); a.glob_pre = glob_pre.as<float>();
-    a.rho = rho.as<double>(); a.ravg = ravg.as<double>();
-    a.att_out = att_dev; a.rwords_out = rwords_dev;
-    a.Tm = Tm; a.L = L; a.D = D; a.H = H; a.E = E; a.V = V;
-    if (batched_scan() && (H & 3) == 0 && t_host) {
-      int64_t dummy = 0;
-      LRP_TRY(bx_prepare(&dummy, st));
-      int t_max = 0;
-      for (int i = 0; i < n; ++i) t_max = std::max(t_max, (int)t_host[i]);
-      GbxArgs x{};
-      x.img_idx = img_dev; x.tpos = t_dev; x.cap = a.cap;
-      x.h1t = a.h1t; x.c1t = a.c1t; x.g1t = a.g1t; x.i1t = a.i1t; x.f1t = a.f1t; x.h2t = a.h2t; x.c2t = a.c2t; x.g2t = a.g2t;
-      x.i2t = a.i2t; x.f2t = a.f2t; x.x1t = a.x1t; x.x2t = a.x2t; x.ctx = a.ctx; x.st = a.st; x.chat = a.chat; x.beta = a.beta;
-      x.att = a.att; x.preds = a.preds; x.Wout = a.Wout; x.WglobT = a.WglobT; x.avg = a.avg; x.glob_pre = a.glob_pre;
-      x.rc1 = bx_g[0].as<double>(); x.rc2 = bx_g[1].as<double>(); x.rh1 = bx_g[2].as<double>(); x.rh2 = bx_g[3].as<double>();
-      x.rchat = bx_g[4].as<double>(); x.nh1 = bx_g[5].as<double>(); x.nh2 = bx_g[6].as<double>();
-      x.rglob = bx_rglob.as<double>(); x.q32 = bx_q32.as<float>(); x.acc32 = bx_acc32.as<float>();
-      x.rho = a.rho; x.ravg = a.ravg; x.att_out = att_dev; x.rwords_out = rwords_dev;
-      x.Tm = Tm; x.L = L; x.D = D; x.H = H; x.E = E; x.V = V;
-      hipLaunchKernelGGL(gbx_head_kernel, dim3(n), dim3(256), 0, st, x);
-      LRP_HIP_CHECK(hipGetLastError());
-      for (int s = 0; s < t_max; ++s) {
-        hipLaunchKernelGGL(gbx_pre2_kernel, dim3(n), dim3(256), 0, st, x, s);
-        LRP_HIP_CHECK(hipGetLastError());
-        LRP_TRY(gemm_nt(bx_q32.as<float>(), n, H, bxWg2, 3 * H, bx_acc32.as<float>(), st));
-        hipLaunchKernelGGL(gbx_mid_kernel, dim3(n), dim3(256), 0, st, x, s);
-        LRP_HIP_CHECK(hipGetLastError());
-        LRP_TRY(gemm_nt(bx_q32.as<float>(), n, H, bxWg1, 2 * H + 2 * E, bx_acc32.as<float>(), st));
-        hipLaunchKernelGGL(gbx_post_kernel, dim3(n), dim3(256), 0, st, x, s);
-        LRP_HIP_CHECK(hipGetLastError());
-      }
-      hipLaunchKernelGGL(gbx_tail_kernel, dim3(n, (D + 63) / 64), dim3(64), (size_t)E * sizeof(double), st, x);
-      LRP_HIP_CHECK(hipGetLastError());
-    } else {
-      const size_t lds = (size_t)(7 * H + std::max(H, E) + E + 8) * sizeof(double);
-      hipLaunchKernelGGL(gtd_explain_kernel, dim3(n), dim3(256), lds, st, a);
-      LRP_HIP_CHECK(hipGetLastError());
-    }
-    if (tailA.p && (D & 7) == 0) {
-      // tail on the matrix cores, as for the adaptive decoder
-      const bool split = prec == PREC_BF16X3 && tail_split();
-      hipLaunchKernelGGL(gtd_tail_a_kernel, dim3((L * (H / 8) + 255) / 256, n), dim3(256), 0, st, img_dev, t_dev,
-                         if_pre.as<float>(), a.att, a.rho, tailA.as<float>(), Tm, L, H, split ? 1 : 0);
-      LRP_HIP_CHECK(hipGetLastError());
-      ConvArgs cg{};
-      cg.in = tailA.as<float>(); cg.NB = n; cg.H = L; cg.W = 1; cg.Cin = H; cg.CinP = conv_cinp(H); cg.taps = 1;
-      cg.wpk = split ? w_ifT_pks.as<float>() : w_ifT_pk.as<float>(); cg.N = D; cg.aux = feat_dev; cg.row2img = img_dev;
-      cg.out = R_feat_dev; cg.out_plain = 1;
-      LRP_HIP_CHECK(conv_launch(EPI_MUL, cg, st, split ? PREC_BF16X3 : PREC_FP32));
-      hipLaunchKernelGGL(tail_finish_kernel, dim3((L * D + 255) / 256 > 64 ? 64 : (L * D + 255) / 256, n), dim3(256), 0, st,
-                         img_dev, feat_dev, a.avg, a.ravg, R_feat_dev, L, D);
-      LRP_HIP_CHECK(hipGetLastError());
-      return LRP_OK;
-    }
-    GtdTailArgs ta{};
-    ta.img_idx = img_dev; ta.tpos = t_dev; ta.F = feat_dev; ta.if_pre = if_pre.as<float>(); ta.att = a.att;
-    ta.avg = a.avg; ta.WifT = WifT.as<float>(); ta.rho = a.rho; ta.ravg = a.ravg; ta.R_feat = R_feat_dev;
-    ta.Tm = Tm; ta.L = L; ta.D = D; ta.H = H;
-    hipLaunchKernelGGL(gtd_tail_kernel, dim3(n, (L + 63) / 64, (D + 63) / 64), dim3(256), 0, st, ta);
+    int64_t dummy = 0;
+    LRP_TRY(bx_prepare(&dummy, st));
+    int t_max = 0;
+    for (int i = 0; i < n; ++i) t_max = std::max(t_max, (int)t_host[i]);
+    GbxArgs x{};
+    x.img_idx = img_dev; x.tpos = t_dev; x.cap = cap_dev.as<int>();
+    x.h1t = S_<double>("h1t"); x.c1t = S_<double>("c1t"); x.g1t = S_<double>("g1t"); x.i1t = S_<double>("i1t_act");
+    x.f1t = S_<double>("f1t_act"); x.h2t = S_<double>("h2t"); x.c2t = S_<double>("c2t"); x.g2t = S_<double>("g2t");
+    x.i2t = S_<double>("i2t_act"); x.f2t = S_<double>("f2t_act"); x.x1t = S_<double>("x1t"); x.x2t = S_<double>("x2t");
+    x.ctx = S_<double>("context"); x.st = S_<double>("st"); x.chat = S_<double>("context_hat"); x.beta = S_<double>("beta");
+    x.att = S_<double>("attention"); x.preds = S_<double>("caption_preds");
+    x.Wout = Wout.as<float>(); x.WglobT = WglobT.as<float>(); x.avg = avg.as<float>(); x.glob_pre = glob_pre.as<float>();
+    x.rc1 = bx_g[0].as<double>(); x.rc2 = bx_g[1].as<double>(); x.rh1 = bx_g[2].as<double>(); x.rh2 = bx_g[3].as<double>();
+    x.rchat = bx_g[4].as<double>(); x.nh1 = bx_g[5].as<double>(); x.nh2 = bx_g[6].as<double>();
+    x.rglob = bx_rglob.as<double>(); x.q32 = bx_q32.as<float>(); x.acc32 = bx_acc32.as<float>();
+    x.rho = rho.as<double>(); x.ravg = ravg.as<double>(); x.att_out = att_dev; x.rwords_out = rwords_dev;
+    x.Tm = Tm; x.L = L; x.D = D; x.H = H; x.E = E; x.V = V;
+    hipLaunchKernelGGL(gbx_head_kernel, dim3(n), dim3(256), 0, st, x);
     LRP_HIP_CHECK(hipGetLastError());
-    return LRP_OK;
+    for (int s = 0; s < t_max; ++s) {
+      hipLaunchKernelGGL(gbx_pre2_kernel, dim3(n), dim3(256), 0, st, x, s);
+      LRP_HIP_CHECK(hipGetLastError());
+      LRP_TRY(gemm_nt(bx_q32.as<float>(), n, H, bxWg2, 3 * H, bx_acc32.as<float>(), st));
+      hipLaunchKernelGGL(gbx_mid_kernel, dim3(n), dim3(256), 0, st, x, s);
+      LRP_HIP_CHECK(hipGetLastError());
+      LRP_TRY(gemm_nt(bx_q32.as<float>(), n, H, bxWg1, 2 * H + 2 * E, bx_acc32.as<float>(), st));
+      hipLaunchKernelGGL(gbx_post_kernel, dim3(n), dim3(256), 0, st, x, s);
+      LRP_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(gbx_tail_kernel, dim3(n, (D + 63) / 64), dim3(64), (size_t)E * sizeof(double), st, x);
+    LRP_HIP_CHECK(hipGetLastError());
+    // tail on the matrix cores, as for the adaptive decoder
+    hipLaunchKernelGGL(gtd_tail_a_kernel, dim3((L * (H / 8) + 255) / 256, n), dim3(256), 0, st, img_dev, t_dev,
+                       if_pre.as<float>(), x.att, x.rho, tailA.as<float>(), Tm, L, H);
+    LRP_HIP_CHECK(hipGetLastError());
+    return tail_gemm(n, img_dev, feat_dev, R_feat_dev, st);
   }
 
   // ---- gradient baselines: _lstm_decoder_backward (E:780-832 adaptive, E:1452-1532 grid-TD), see gradient_kernels.h
@@ -957,18 +881,12 @@ struct Decoder {
         g[(size_t)d * H + j] = d < Kx ? Wi[(size_t)d * 4 * H + 2 * H + j] : Wh[(size_t)(d - Kx) * 4 * H + 2 * H + j];
     return g;
   }
-  // tail GEMM of the decoder LRP (R at the image_features layer back to the CNN features): exact fp32 MFMA — its split-bf16 form
-  // saved 0.2 ms of a 40 ms step and cost the decoder half 5x of its parity margin (R_feat 3-10e-6 instead of 0.4-1.2e-6 vs
-  // the float64 oracle); it was kept behind LRP_DEC_TAIL_SPLIT until round 4.
-  static constexpr bool tail_split() { return false; }
   DevBuf sg_ws;                                        // K-split partials of the forward's matrix-core products
   static constexpr size_t SG_WS_FLOATS = (size_t)4 << 20;
   int need_sg_ws() {
     if (!sg_ws.p) { int64_t dummy = 0; LRP_TRY(sg_ws.alloc(SG_WS_FLOATS * sizeof(float), &dummy)); }
     return LRP_OK;
   }
-  static bool mfma_forward() { return sw().dec_mfma_fwd != 0; }   // LRP_DEC_MFMA_FWD=0: VALU skinny GEMMs in the forward
-  static bool batched_scan() { return sw().dec_batched != 0; }    // LRP_DEC_BATCHED=0: one workgroup per unit (dec_explain_adaptive_kernel)
   int bx_prepare(int64_t* total, hipStream_t st = nullptr) {
     if (bx_ready) return LRP_OK;
     const size_t NT = NT_max;
@@ -997,6 +915,21 @@ struct Decoder {
     return LRP_OK;
   }
 
+  // tail GEMM of the decoder LRP (R at the image_features layer back to the CNN features), A operand in tailA: 1-tap
+  // conv_igemm in exact fp32 with the F-multiply as its gate -> mean-pool share.  (Its split-bf16 form saved 0.2 ms of a
+  // 40 ms step and cost the decoder half 5x of its parity margin: R_feat 3-10e-6 instead of 0.4-1.2e-6 vs the float64 oracle.)
+  int tail_gemm(int n, const int* img_dev, const float* feat_dev, float* R_feat_dev, hipStream_t st) {
+    ConvArgs cg{};
+    cg.in = tailA.as<float>(); cg.NB = n; cg.H = L; cg.W = 1; cg.Cin = H; cg.CinP = conv_cinp(H); cg.taps = 1;
+    cg.wpk = w_ifT_pk.as<float>(); cg.N = D; cg.aux = feat_dev; cg.row2img = img_dev;
+    cg.out = R_feat_dev; cg.out_plain = 1;
+    LRP_HIP_CHECK(conv_launch(EPI_MUL, cg, st, PREC_FP32));
+    hipLaunchKernelGGL(tail_finish_kernel, dim3((L * D + 255) / 256 > 64 ? 64 : (L * D + 255) / 256, n), dim3(256), 0, st,
+                       img_dev, feat_dev, avg.as<float>(), ravg.as<double>(), R_feat_dev, L, D);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  }
+
   int explain(int n, const int* img_dev, const int* t_dev, const int32_t*, const int32_t* t_host, int variant,
               const float* feat_dev, float* R_feat_dev, float* att_dev, double* rwords_dev, hipStream_t st) {
     if (variant != LRP_EXPLAIN_SEQUENCE && variant != LRP_EXPLAIN_SINGLE_STEP) return fail(LRP_ERR_INVALID, "bad variant");
@@ -1005,73 +938,40 @@ struct Decoder {
         return fail(LRP_ERR_UNSUPPORTED, "the grid-TD decoder has no single-step variant");
       return explain_gridtd(n, img_dev, t_dev, t_host, feat_dev, R_feat_dev, att_dev, rwords_dev, st);
     }
-    ExplainArgs a{};
-    a.img_idx = img_dev; a.tpos = t_dev; a.cap = cap_dev.as<int>();
-    a.ht = S_<float>("ht"); a.ct = S_<float>("ct"); a.gt = S_<float>("gt"); a.it = S_<float>("it_act");
-    a.ft = S_<float>("ft_act"); a.st = S_<float>("st"); a.beta = S_<float>("beta"); a.att = S_<float>("attention");
-    a.xt = S_<float>("xt"); a.ctx = S_<double>("context"); a.chat = S_<double>("c_hat");
-    a.preds = S_<double>("caption_preds");
-    a.Wout = Wout.as<float>(); a.WgT = WgT.as<float>(); a.WglobT = WglobT.as<float>();
-    a.avg = avg.as<float>(); a.glob_pre = glob_pre.as<float>();
-    a.rctx = rctx.as<double>(); a.ravg = ravg.as<double>();
-    a.att_out = att_dev; a.rwords_out = rwords_dev;
-    a.Tm = Tm; a.L = L; a.D = D; a.H = H; a.E = E; a.V = V; a.single_step = variant == LRP_EXPLAIN_SINGLE_STEP;
-    if (batched_scan() && (H & 3) == 0 && t_host) {
-      // step-synchronous scan: per step one pointwise kernel, ONE GEMM over all units, one routing kernel
-      int64_t dummy = 0;
-      LRP_TRY(bx_prepare(&dummy, st));
-      int t_max = 0;
-      for (int i = 0; i < n; ++i) t_max = std::max(t_max, (int)t_host[i]);
-      BxArgs x{};
-      x.img_idx = img_dev; x.tpos = t_dev; x.cap = a.cap; x.ht = a.ht; x.ct = a.ct; x.gt = a.gt; x.it = a.it; x.ft = a.ft;
-      x.st = a.st; x.beta = a.beta; x.att = a.att; x.xt = a.xt; x.ctx = a.ctx; x.chat = a.chat; x.preds = a.preds;
-      x.Wout = a.Wout; x.WglobT = a.WglobT; x.avg = a.avg; x.glob_pre = a.glob_pre;
-      x.rc = bx_rc.as<double>(); x.rh = bx_rh.as<double>(); x.rglob = bx_rglob.as<double>(); x.q32 = bx_q32.as<float>();
-      x.acc32 = bx_acc32.as<float>(); x.rctx = a.rctx; x.ravg = a.ravg; x.att_out = att_dev; x.rwords_out = rwords_dev;
-      x.Tm = Tm; x.L = L; x.D = D; x.H = H; x.E = E; x.V = V; x.single_step = a.single_step;
-      hipLaunchKernelGGL(bx_head_kernel, dim3(n), dim3(256), 0, st, x);
-      LRP_HIP_CHECK(hipGetLastError());
-      const int steps = a.single_step ? 1 : t_max;
-      hipLaunchKernelGGL(bx_pre_kernel, dim3(n), dim3(256), 0, st, x, 0);
-      LRP_HIP_CHECK(hipGetLastError());
-      for (int s = 0; s < steps; ++s) {
-        LRP_TRY(gemm_nt(bx_q32.as<float>(), n, H, bxWg1, 2 * E + H, bx_acc32.as<float>(), st));
-        hipLaunchKernelGGL(bx_post_kernel, dim3(n), dim3(256), 0, st, x, s, s + 1 < steps ? 1 : 0);   // post(s) + pre(s + 1): one launch
-        LRP_HIP_CHECK(hipGetLastError());
-      }
-      hipLaunchKernelGGL(bx_tail_kernel, dim3(n, (D + 63) / 64), dim3(64), (size_t)E * sizeof(double), st, x);
-      LRP_HIP_CHECK(hipGetLastError());
-    } else {
-      const size_t lds = (size_t)(2 * H + std::max(H, E) + E + 8) * sizeof(double);
-      hipLaunchKernelGGL(dec_explain_adaptive_kernel, dim3(n), dim3(256), lds, st, a);
-      LRP_HIP_CHECK(hipGetLastError());
-    }
-    if (tailA.p && (D & 7) == 0) {
-      // tail on the matrix cores: A operand -> 1-tap conv_igemm with the F-multiply as its gate -> mean-pool share
-      const bool split = prec == PREC_BF16X3 && tail_split();
-      TailAArgs aa{};
-      aa.img_idx = img_dev; aa.tpos = t_dev; aa.vfeat = vfeat.as<float>(); aa.ipre = ipre.as<double>(); aa.att = a.att;
-      aa.rho = a.rctx; aa.A = tailA.as<float>(); aa.Tm = Tm; aa.L = L; aa.H = H; aa.split = split;
-      hipLaunchKernelGGL(tail_a_kernel, dim3((L * (H / 8) + 255) / 256, n), dim3(256), 0, st, aa);
-      LRP_HIP_CHECK(hipGetLastError());
-      ConvArgs cg{};
-      cg.in = tailA.as<float>(); cg.NB = n; cg.H = L; cg.W = 1; cg.Cin = H; cg.CinP = conv_cinp(H); cg.taps = 1;
-      cg.wpk = split ? w_ifT_pks.as<float>() : w_ifT_pk.as<float>(); cg.N = D; cg.aux = feat_dev; cg.row2img = img_dev;
-      cg.out = R_feat_dev; cg.out_plain = 1;
-      LRP_HIP_CHECK(conv_launch(EPI_MUL, cg, st, split ? PREC_BF16X3 : PREC_FP32));
-      hipLaunchKernelGGL(tail_finish_kernel, dim3((L * D + 255) / 256 > 64 ? 64 : (L * D + 255) / 256, n), dim3(256), 0, st,
-                         img_dev, feat_dev, a.avg, a.ravg, R_feat_dev, L, D);
-      LRP_HIP_CHECK(hipGetLastError());
-      return LRP_OK;
-    }
-    TailArgs ta{};
-    ta.img_idx = img_dev; ta.tpos = t_dev; ta.F = feat_dev; ta.vfeat = vfeat.as<float>(); ta.ipre = ipre.as<double>();
-    ta.att = a.att;
-    ta.avg = a.avg; ta.WifT = WifT.as<float>(); ta.rctx = a.rctx; ta.ravg = a.ravg; ta.R_feat = R_feat_dev;
-    ta.Tm = Tm; ta.L = L; ta.D = D; ta.H = H;
-    hipLaunchKernelGGL(dec_tail_kernel, dim3(n, (L + 63) / 64, (D + 63) / 64), dim3(256), 0, st, ta);
+    // step-synchronous scan: per step one pointwise kernel, ONE GEMM over all units, one routing kernel
+    int64_t dummy = 0;
+    LRP_TRY(bx_prepare(&dummy, st));
+    int t_max = 0;
+    for (int i = 0; i < n; ++i) t_max = std::max(t_max, (int)t_host[i]);
+    BxArgs x{};
+    x.img_idx = img_dev; x.tpos = t_dev; x.cap = cap_dev.as<int>();
+    x.ht = S_<float>("ht"); x.ct = S_<float>("ct"); x.gt = S_<float>("gt"); x.it = S_<float>("it_act");
+    x.ft = S_<float>("ft_act"); x.st = S_<float>("st"); x.beta = S_<float>("beta"); x.att = S_<float>("attention");
+    x.xt = S_<float>("xt"); x.ctx = S_<double>("context"); x.chat = S_<double>("c_hat"); x.preds = S_<double>("caption_preds");
+    x.Wout = Wout.as<float>(); x.WglobT = WglobT.as<float>(); x.avg = avg.as<float>(); x.glob_pre = glob_pre.as<float>();
+    x.rc = bx_rc.as<double>(); x.rh = bx_rh.as<double>(); x.rglob = bx_rglob.as<double>(); x.q32 = bx_q32.as<float>();
+    x.acc32 = bx_acc32.as<float>(); x.rctx = rctx.as<double>(); x.ravg = ravg.as<double>(); x.att_out = att_dev;
+    x.rwords_out = rwords_dev;
+    x.Tm = Tm; x.L = L; x.D = D; x.H = H; x.E = E; x.V = V; x.single_step = variant == LRP_EXPLAIN_SINGLE_STEP;
+    hipLaunchKernelGGL(bx_head_kernel, dim3(n), dim3(256), 0, st, x);
     LRP_HIP_CHECK(hipGetLastError());
-    return LRP_OK;
+    const int steps = x.single_step ? 1 : t_max;
+    hipLaunchKernelGGL(bx_pre_kernel, dim3(n), dim3(256), 0, st, x, 0);
+    LRP_HIP_CHECK(hipGetLastError());
+    for (int s = 0; s < steps; ++s) {
+      LRP_TRY(gemm_nt(bx_q32.as<float>(), n, H, bxWg1, 2 * E + H, bx_acc32.as<float>(), st));
+      hipLaunchKernelGGL(bx_post_kernel, dim3(n), dim3(256), 0, st, x, s, s + 1 < steps ? 1 : 0);   // post(s) + pre(s + 1): one launch
+      LRP_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(bx_tail_kernel, dim3(n, (D + 63) / 64), dim3(64), (size_t)E * sizeof(double), st, x);
+    LRP_HIP_CHECK(hipGetLastError());
+    // tail: A operand -> 1-tap conv_igemm with the F-multiply as its gate -> mean-pool share
+    TailAArgs aa{};
+    aa.img_idx = img_dev; aa.tpos = t_dev; aa.vfeat = vfeat.as<float>(); aa.ipre = ipre.as<double>(); aa.att = x.att;
+    aa.rho = x.rctx; aa.A = tailA.as<float>(); aa.Tm = Tm; aa.L = L; aa.H = H;
+    hipLaunchKernelGGL(tail_a_kernel, dim3((L * (H / 8) + 255) / 256, n), dim3(256), 0, st, aa);
+    LRP_HIP_CHECK(hipGetLastError());
+    return tail_gemm(n, img_dev, feat_dev, R_feat_dev, st);
   }
 
   int read_state(const char* name, void* out_dev, size_t out_bytes, hipStream_t st) {

@@ -1,10 +1,12 @@
-// decoder_batched_kernels.h — the per-token decoder LRP (E:537-666, E:1180-1321) run STEP-SYNCHRONOUSLY over all
-// (image, token) units of a call: at scan step s every unit handles its LSTM step i = t-1-s, so the gate-g rule's
-// product with the (2E+H) x H weight block is ONE (n x H).(H x Nd) GEMM on the matrix cores per step (conv_igemm,
-// 1 tap, exact fp32) instead of one GEMV per unit that re-reads 3 MB of weights from L2 (dec_explain_adaptive_kernel /
-// gtd_explain_kernel: one workgroup per unit, kept as the fallback for H % 4 != 0).  The element-wise rule arithmetic
-// stays in float64 exactly as in those kernels; only the GEMM operand q = r_g / stab(g) and its result pass through
-// float32 (6e-8 relative, bar 1e-4).
+// decoder_batched_kernels.h — the per-token decoder LRP (E:537-666, E:1180-1321; closed form in SURVEY.md Appendix B)
+// run STEP-SYNCHRONOUSLY over all (image, token) units of a call.  The identity-weight rule calls collapse to
+// element-wise shares  part / stab(whole) * R  (float64, one workgroup per unit); the gate-g rule is a product with the
+// (2E+H) x H weight block.  At scan step s every unit handles its LSTM step i = t-1-s, so that product is ONE
+// (n x H).(H x Nd) GEMM on the matrix cores per step (conv_igemm, 1 tap, exact fp32) instead of one GEMV per unit that
+// re-reads 3 MB of weights from L2.  Only the GEMM operand q = r_g / stab(g) and its result pass through float32
+// (6e-8 relative, bar 1e-4).  Outputs per token: rho = r_ctx / stab(ctx) (adaptive: rctx [n][H]; grid-TD: rho
+// [n][Tm][H], one row per step for the attention-sum rule of the tail), ravg [n][D], r_words — consumed by the tail
+// kernels of decoder_kernels.h / decoder_gridtd_kernels.h.
 #pragma once
 #include "decoder_kernels.h"
 
@@ -23,7 +25,7 @@ struct BxArgs {                                    // adaptive
   int Tm, L, D, H, E, V, single_step;
 };
 
-// head (E:552-602), identical arithmetic to dec_explain_adaptive_kernel
+// head (E:552-602): output layer, h / c_hat split, context / sentinel split
 __global__ __launch_bounds__(256) void bx_head_kernel(BxArgs a) {
   const int H = a.H, E = a.E, Tm = a.Tm, S = Tm + 1;
   const int n = blockIdx.x, tid = threadIdx.x;
@@ -149,8 +151,7 @@ __global__ __launch_bounds__(256) void bx_tail_kernel(BxArgs a) {
 
 // ------------------------------------------------------------------------------------------------------------
 // grid-TD (E:1180-1321): the same step-synchronous scan with two LSTMs per step — language cell -> GEMM (3H columns)
-// -> routing + c_hat split + top-down cell -> GEMM (H+2E+H columns) -> routing.  Arithmetic transcribed from
-// gtd_explain_kernel (decoder_gridtd_kernels.h), state in float64 per unit instead of LDS.
+// -> routing + c_hat split + top-down cell -> GEMM (H+2E+H columns) -> routing.  Scan state in float64 per unit.
 // ------------------------------------------------------------------------------------------------------------
 struct GbxArgs {
   const int* img_idx; const int* tpos; const int* cap;

@@ -356,31 +356,7 @@ __global__ __launch_bounds__(256) void dec_att_finish_kernel(const float* __rest
   }
 }
 
-// ------------------------------------------------------------------------------------------
-// Per-token LRP through the decoder, one workgroup per (image, t) pair.  Closed form of
-// E:537-666: identity-weight rule calls collapse to element-wise
-// shares  part / stab(whole) * R ; the gate-g rule is a (2E+H) x H GEMV per scan step.
-// WgT[j][d] = [Wi;Wh][d][2H+j] (transposed gate-g block), WglobT[e][d] = W_glob[d][e].
-// Outputs per token: rctx (H) , ravg (D)  -> consumed by dec_tail_kernel; r_words.
-// dynamic LDS (doubles): rc[H] rh[H] q[max(H,E)] rglob[E] red[4]
-// ------------------------------------------------------------------------------------------
-constexpr int SCAN_MAXR = 8;         // (2E+H) <= 8*256
-
-struct ExplainArgs {
-  const int* img_idx; const int* tpos;            // [n]
-  const int* cap;                                 // [B][Tm]
-  const float *ht, *ct, *gt, *it, *ft, *st, *beta, *att, *xt;
-  const double *ctx, *chat, *preds;
-  const float* Wout;                              // [H][V]
-  const float* WgT;                               // [H][2E+H]
-  const float* WglobT;                            // [E][D]
-  const float *avg, *glob_pre;
-  double *rctx, *ravg;                            // rho = r_ctx/stab(ctx) [n][H], r_avg [n][D]
-  float* att_out;                                 // [n][L] or null
-  double* rwords_out;                             // [n][Tm] or null
-  int Tm, L, D, H, E, V, single_step;
-};
-
+// sum of v over a 256-thread block (red: 4 doubles of LDS); its barriers also order the block's earlier writes
 __device__ __forceinline__ double block_sum_d(double v, double* red) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   v = wave_sum_d(v);
@@ -392,228 +368,22 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {
   return r;
 }
 
-__global__ __launch_bounds__(256) void dec_explain_adaptive_kernel(ExplainArgs a) {
-  extern __shared__ double dsm[];
-  const int H = a.H, E = a.E, D = a.D, Tm = a.Tm, S = Tm + 1;
-  double* rc = dsm;
-  double* rh = rc + H;
-  double* q = rh + H;
-  double* rglob = q + (H > E ? H : E);
-  double* red = rglob + E;
-  const int n = blockIdx.x, tid = threadIdx.x;
-  const int b = a.img_idx[n], t = a.tpos[n];
-  const int Nd = 2 * E + H;
-  const size_t rowt = (size_t)b * S + t;
-
-  // ---- output layer, h / c_hat split, context / sentinel split   (E:552-602)
-  const int k = a.cap[b * Tm + t - 1] - 1;
-  const double zk = a.preds[((size_t)b * Tm + (t - 1)) * a.V + k];
-  const double bt32_1m = (double)(1.f - a.beta[rowt]);
-  const float btf = a.beta[rowt];
-  for (int j = tid; j < H; j += 256) {
-    const double h = (double)a.ht[rowt * H + j], ch = a.chat[rowt * H + j];
-    const double u = h + ch;
-    const double r_u = ((double)a.Wout[(size_t)j * a.V + k] * u) / stab(zk) * zk;
-    const double su = stab(u);
-    const double r_h = h / su * r_u;
-    const double r_ch = ch / su * r_u;
-    const double sch = stab(ch);
-    const double r_ctx = (bt32_1m * a.ctx[rowt * H + j]) / sch * r_ch;
-    const double r_s = (double)(btf * a.st[rowt * H + j]) / sch * r_ch;
-    a.rctx[(size_t)n * H + j] = r_ctx / stab(a.ctx[rowt * H + j]);      // rho_j, consumed by dec_tail_kernel
-    rc[j] = r_s;                                  // r_ct[t] = r_st            (E:602)
-    rh[j] = r_h;
-  }
-  for (int e = tid; e < E; e += 256) rglob[e] = 0.0;
-  if (a.att_out)
-    for (int l = tid; l < a.L; l += 256) a.att_out[(size_t)n * a.L + l] = a.att[rowt * a.L + l];
-  if (a.rwords_out)
-    for (int i = tid; i < Tm; i += 256) a.rwords_out[(size_t)n * Tm + i] = 0.0;
-  __syncthreads();
-
-  // ---- reverse scan over the LSTM steps   (E:604-632)
-  const int i_stop = a.single_step ? t - 1 : 0;
-  for (int i = t - 1; i >= i_stop; --i) {
-    const size_t r1 = ((size_t)b * S + i + 1) * H, r0 = ((size_t)b * S + i) * H;
-    for (int j = tid; j < H; j += 256) {
-      const double rcj = rc[j] + rh[j];                                   // r_ct[i+1] += r_ht[i+1]
-      const double sc = stab((double)a.ct[r1 + j]);
-      const float pg = a.it[r1 + j] * tanhf(a.gt[r1 + j]);                // float32 product, as in numpy
-      const float pc = a.ft[r1 + j] * a.ct[r0 + j];
-      const double r_g = (double)pg / sc * rcj;
-      rc[j] = (double)pc / sc * rcj;                                      // r_ct[i]
-      q[j] = r_g / stab((double)a.gt[r1 + j]);
-    }
-    __syncthreads();
-    // GEMV acc[d] = sum_j WgT[j][d] * q[j].  Column indices are clamped (not branched) so the
-    // loads of 4 consecutive j are independent and all in flight together; lanes run along d
-    // (coalesced 256 B per wave-load).
-    double acc[SCAN_MAXR];
-    int dcl[SCAN_MAXR];
-#pragma unroll
-    for (int r = 0; r < SCAN_MAXR; ++r) { acc[r] = 0.0; const int d = tid + 256 * r; dcl[r] = d < Nd ? d : Nd - 1; }
-    const int nr = (Nd + 255) >> 8;                       // live accumulators (uniform)
-    int j = 0;
-    for (; j + 4 <= H; j += 4) {
-      float wv[4][SCAN_MAXR];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int r = 0; r < SCAN_MAXR; ++r)
-          if (r < nr) wv[u][r] = a.WgT[(size_t)(j + u) * Nd + dcl[r]];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const double qj = q[j + u];
-#pragma unroll
-        for (int r = 0; r < SCAN_MAXR; ++r)
-          if (r < nr) acc[r] += (double)wv[u][r] * qj;
-      }
-    }
-    for (; j < H; ++j) {
-      const double qj = q[j];
-#pragma unroll
-      for (int r = 0; r < SCAN_MAXR; ++r)
-        if (r < nr) acc[r] += (double)a.WgT[(size_t)j * Nd + dcl[r]] * qj;
-    }
-    double wsum = 0.0;
-#pragma unroll
-    for (int r = 0; r < SCAN_MAXR; ++r) {
-      const int d = tid + 256 * r;
-      if (d < Nd) {
-        const float x = d < 2 * E ? a.xt[((size_t)b * Tm + i) * 2 * E + d] : a.ht[r0 + d - 2 * E];
-        const double rx = (double)x * acc[r];
-        if (d < E) wsum += rx;                                            // r_wording_embedding[i]
-        else if (d < 2 * E) rglob[d - E] += rx;                           // r_global_img_feature +=
-        else rh[d - 2 * E] = rx;                                          // r_ht[i] =   ('=' E:627)
-      }
-    }
-    const double ws = block_sum_d(wsum, red);                             // includes the barriers the next step needs
-    if (tid == 0 && a.rwords_out) a.rwords_out[(size_t)n * Tm + i] = ws;
-  }
-  __syncthreads();
-
-  // ---- global-feature rule  (E:634-639):  r_avg = avg * ( W_glob . (r_glob / stab(glob_pre)) )
-  for (int e = tid; e < E; e += 256) q[e] = rglob[e] / stab((double)a.glob_pre[(size_t)b * E + e]);
-  __syncthreads();
-  for (int d = tid; d < D; d += 256) {
-    double s = 0.0;
-    for (int e = 0; e < E; ++e) s += (double)a.WglobT[(size_t)e * D + d] * q[e];
-    a.ravg[(size_t)n * D + d] = (double)a.avg[(size_t)b * D + d] * s;
-  }
-
-  // ---- r_words post-processing (adaptive): [0] = 0, / max|.|, drop first   (E:660-665)
-  if (a.rwords_out && !a.single_step) {
-    __syncthreads();
-    if (tid == 0) {
-      double* rw = a.rwords_out + (size_t)n * Tm;
-      rw[0] = 0.0;
-      double m = 0.0;
-      for (int i = 0; i < t; ++i) m = fmax(m, fabs(rw[i]));
-      for (int i = 0; i + 1 < t; ++i) rw[i] = m != 0.0 ? rw[i + 1] / m : rw[i + 1];
-      rw[t - 1] = 0.0;
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // Tail of the per-token LRP (E:641-659): for every location l and feature d
 //   r_V[l][j]   = float32( relu(if_pre[l][j]) * alpha_l / stab(ctx[j]) * r_ctx[j] )          (E:648-653)
 //   R_feat[l][d]= float32( F[l][d]/L / stab(avg[d]) * r_avg[d] )                             (E:642-647)
 //               + F[l][d] * sum_j W_if[d][j] * r_V[l][j] / stab(if_pre[l][j])                (E:654-659)
-// = an (L x H) . (H x D) float64 GEMM per token whose A operand is generated on the fly.
-// grid (n, ceil(L/64), ceil(D/64)); 256 threads, 4x4 outputs each; WifT[j][d] = W_if[d][j].
-// ------------------------------------------------------------------------------------------
-struct TailArgs {
-  const int* img_idx; const int* tpos;
-  const float* F;          // [B][L][D]
-  const float* vfeat;      // [B][L][H]   relu(if_pre)
-  const double* ipre;      // [B][L][H]   1 / stab(if_pre)   (per image, so the tail has no divides)
-  const float* att;        // [B][S][L]
-  const float* avg;        // [B][D]
-  const float* WifT;       // [H][D]
-  const double *rctx, *ravg;   // rctx holds rho = r_ctx / stab(ctx)
-  float* R_feat;           // [n][L][D]
-  int Tm, L, D, H;
-};
-
-__global__ __launch_bounds__(256) void dec_tail_kernel(TailArgs a) {
-  __shared__ double As[16][65];
-  __shared__ double Bs[16][65];
-  __shared__ double rho[16];     // r_ctx / stab(ctx) is applied per j: keep both factors exact instead
-  const int n = blockIdx.x, l0 = blockIdx.y * 64, d0 = blockIdx.z * 64;
-  const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-  const int b = a.img_idx[n], t = a.tpos[n], S = a.Tm + 1;
-  const int L = a.L, D = a.D, H = a.H;
-  const size_t rowt = (size_t)b * S + t;
-  (void)rho;
-  double acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-  for (int j0 = 0; j0 < H; j0 += 16) {
-    // A tile: 64 locations x 16 j  (1024 elements, 4 per thread)
-    for (int e = tid; e < 1024; e += 256) {
-      const int jj = e & 15, ll = e >> 4;
-      const int l = l0 + ll, j = j0 + jj;
-      double v = 0.0;
-      if (l < L && j < H) {
-        const size_t o = ((size_t)b * L + l) * H + j;
-        const double vf = (double)a.vfeat[o] * (double)a.att[rowt * L + l];
-        const float rV = (float)(vf * a.rctx[(size_t)n * H + j]);           // float32 store into r_V (E:554, :648)
-        v = (double)rV * a.ipre[o];
-      }
-      As[jj][ll] = v;
-    }
-    for (int e = tid; e < 1024; e += 256) {
-      const int dd = e & 63, jj = e >> 6;
-      const int d = d0 + dd, j = j0 + jj;
-      Bs[jj][dd] = (d < D && j < H) ? (double)a.WifT[(size_t)j * D + d] : 0.0;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int jj = 0; jj < 16; ++jj) {
-      double av[4], bv[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) av[i] = As[jj][ty * 4 + i];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) bv[j] = Bs[jj][tx * 4 + j];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] += av[i] * bv[j];
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int l = l0 + ty * 4 + i;
-    if (l >= L) continue;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int d = d0 + tx * 4 + j;
-      if (d >= D) continue;
-      const float f = a.F[((size_t)b * L + l) * D + d];
-      const float fl = f / (float)L;                                   // float32 division, as numpy does
-      const float first = (float)((double)fl / stab((double)a.avg[(size_t)b * D + d]) * a.ravg[(size_t)n * D + d]);
-      a.R_feat[((size_t)n * L + l) * D + d] = (float)((double)first + (double)f * acc[i][j]);
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------
-// Tail on the matrix cores (replaces dec_tail_kernel's float64 VALU GEMM): the (L x H).(H x D) product per
-// token runs on conv_igemm (1-tap mode) with the A operand materialised once by tail_a_kernel and the
-// F-multiply fused as the EPI_MUL gate; tail_finish_kernel adds the mean-pool share.  The reference rounds
-// r_V and R_feat to float32 anyway (E:554-555); the GEMM itself now rounds at fp32 / split-bf16 level
-// (~1e-6 relative on R_feat, bar 1e-4).
+// = an (L x H) . (H x D) GEMM per token.  It runs on the matrix cores: conv_igemm (1-tap mode, exact fp32)
+// with the A operand materialised once by tail_a_kernel and the F-multiply fused as the EPI_MUL gate;
+// tail_finish_kernel adds the mean-pool share.  The reference rounds r_V and R_feat to float32 anyway
+// (E:554-555); the GEMM itself rounds at fp32 level (~1e-6 relative on R_feat, bar 1e-4).
 //   A[n][l][j] = float32( float32( relu(if_pre[l][j]) * alpha_l * rho_j ) / stab(if_pre[l][j]) )
 // ------------------------------------------------------------------------------------------
 struct TailAArgs {
   const int* img_idx; const int* tpos;
   const float* vfeat; const double* ipre; const float* att; const double* rho;
-  float* A;                 // [n][L][H] fp32, or split8 when `split`
-  int Tm, L, H, split;
+  float* A;                 // [n][L][H] fp32
+  int Tm, L, H;
 };
 
 __global__ __launch_bounds__(256) void tail_a_kernel(TailAArgs a) {
@@ -632,12 +402,8 @@ __global__ __launch_bounds__(256) void tail_a_kernel(TailAArgs a) {
       v[q] = (float)((double)rV * a.ipre[o + q]);
     }
     float* dst = a.A + ((size_t)n * a.L + l) * a.H + j0;
-    if (a.split) {
-      split8_store(v, dst);
-    } else {
-      *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(v);
-      *reinterpret_cast<f32x4*>(dst + 4) = *reinterpret_cast<const f32x4*>(v + 4);
-    }
+    *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(v);
+    *reinterpret_cast<f32x4*>(dst + 4) = *reinterpret_cast<const f32x4*>(v + 4);
   }
 }
 

@@ -386,7 +386,6 @@ int lrp_set_precision(lrp_handle* h, int32_t mode) {
     h->enc.fwd_fast = fast;
     h->enc.walk_f16 = f16;                            // (forward, decoder and the ResNet encoder stay as in LRP_PREC_BF16X3)
     h->rn.prec = km;
-    h->dec.prec = km;
     return LRP_OK;
   });
 }

@@ -404,6 +404,19 @@ def test_explicit_device_and_allocation_failure_are_statuses():
 
 
 @pytest.mark.parametrize("kind", ["adaptive", "gridtd"])
+def test_decoder_dims_not_multiple_of_8_are_unsupported(kind):
+    """lrp_create refuses D or H that is not a multiple of 8 (the LRP tail's A operand is written in groups of 8 channels):
+    LRP_ERR_UNSUPPORTED -> NotImplementedError, also for widths that are multiples of 4."""
+    from lrp_imagecaptioning_amd.engine import LRPEngine
+    kw = dict(decoder=kind, img_hw=(4, 4), L=16, V=V, max_images=1, max_tokens=2, max_caption_len=4)
+    LRPEngine(cnn_cfg=[("c1", 3, 16, False)], D=16, H=32, E=32, **kw)           # the same geometry with D, H % 8 == 0 builds
+    with pytest.raises(NotImplementedError, match="multiples of 8"):
+        LRPEngine(cnn_cfg=[("c1", 3, 16, False)], D=16, H=36, E=36, **kw)
+    with pytest.raises(NotImplementedError, match="multiples of 8"):
+        LRPEngine(cnn_cfg=[("c1", 3, 20, False)], D=20, H=32, E=32, **kw)
+
+
+@pytest.mark.parametrize("kind", ["adaptive", "gridtd"])
 def test_weights_set_from_device_match_host_set(kind):
     """lrp_set_weight_dev (the multi-GPU start-up path: the bundle arrives in HBM over RCCL and is packed by device
     kernels, no host round trip) must leave the handle in exactly the state lrp_set_weight does: heat-maps, decoder

@@ -2,8 +2,9 @@
 
 VERDICT r3: "~40 LRP_* switches, six swept once, none under a committed test — each untested switch is a dead or wrong code
 path waiting for a user."  Round 4 deleted 21 of them (their code paths with them where nothing else reaches those) and
-keeps 17 as measurement knobs / fall-backs (+ round 4's LRP_POOL_FUSED and the opt-in LRP_SPARSE_POOL); this file runs each of the kept ones — alone, at the setting that leaves the
-default path — through the engine at a size where the kernels of the benchmark configuration engage and compares every
+kept 17 as measurement knobs / fall-backs (+ round 4's LRP_POOL_FUSED and the opt-in LRP_SPARSE_POOL); three more went later
+(LRP_CONV_TILE, LRP_DEC_BATCHED, LRP_DEC_MFMA_FWD: their alternatives were code nothing else reached), which leaves 15 + the
+opt-in.  This file runs each of the kept ones — alone, at the setting that leaves the default path — through the engine at a size where the kernels of the benchmark configuration engage and compares every
 heat-map with the default run:
 
   * VGG16 at full size, 8 images x 9 words = 72 heat-maps per call: block1 takes the weights-in-registers kernel with the
@@ -31,8 +32,6 @@ B, T, V = 8, 9, 1000
 CASES = [
     ("LRP_CONV_HALO", 0, 1e-6, 1e-6),
     ("LRP_CONV_BREG", 0, 1e-6, 1e-6),
-    ("LRP_CONV_TILE", 1, 1e-6, 0.0),
-    ("LRP_CONV_TILE", 128, 1e-6, 0.0),
     ("LRP_CONV_SMALL", 0, 0.0, 0.0),
     ("LRP_CONV_MID", 0, 0.0, 0.0),
     ("LRP_EPI_FAST", 0, 0.0, 0.0),
@@ -45,8 +44,6 @@ CASES = [
     ("LRP_IMG_FUSED", 0, 1e-6, 1e-6),
     ("LRP_FWD_EMIT", 0, 2e-5, 2e-5),
     ("LRP_FWD_IL", 0, 2e-5, 2e-5),
-    ("LRP_DEC_BATCHED", 0, 2e-5, 2e-5),
-    ("LRP_DEC_MFMA_FWD", 0, 2e-5, 2e-5),
     ("LRP_POOL_FUSED", 0, 0.0, 0.0),        # max-pool / gate / pooled pairs as a pass behind the conv: the same arithmetic, bit for bit
     ("LRP_SPARSE_POOL", 1, 1e-6, 1e-6),    # opt-in: block4_conv3 / block3_conv3 on the 2:4-sparse matrix cores (other summation order)
 ]
