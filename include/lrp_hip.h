@@ -207,7 +207,13 @@ int lrp_decoder_gradient(lrp_handle* h, int32_t n, const int32_t* img_idx_host, 
 /* lrp_cnn_walk == <Analyzer>(image_model, neuron_selection_mode="replace").analyze([X, head]) for
  * Gradient / InputTimesGradient / GuidedBackprop (innvestigate/analyzer/gradient_based.py:101-265;
  * explainers.py:672, :884, :928) — and LRPSequentialPresetA for LRP_WALK_LRP (same as lrp_cnn_explain).
- * head_dev (n, L, D) -> out_dev (n, img_h, img_w, 3).  VGG-style encoders only for the gradient walks. */
+ * head_dev (n, L, D) -> out_dev (n, img_h, img_w, 3).  Both encoders.  VGG-style encoders: every precision mode (the
+ * gradient walks are exact fp32 in each).  ResNet encoder: the gradient walks run in LRP_PREC_FP32 only — its ReLU
+ * decisions are recorded by the fp32-mode forward of lrp_encode_images, the other modes' forward keeps the inner
+ * activations as fp16 pairs only — and return LRP_ERR_UNSUPPORTED in the other modes (set LRP_PREC_FP32 with
+ * lrp_set_precision and call lrp_encode_images again); LRP_WALK_LRP runs in every mode.  The first gradient walk on a
+ * ResNet handle after its weights changed packs a BN-scaled copy of the conv weights (counted in lrp_workspace_bytes,
+ * like the ReLU masks the first fp32-mode encode allocates). */
 enum { LRP_WALK_LRP = 0, LRP_WALK_GRADIENT = 1, LRP_WALK_INPUT_X_GRADIENT = 2, LRP_WALK_GUIDED_BACKPROP = 3 };
 int lrp_cnn_walk(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const float* head_dev, float* out_dev,
                  int32_t walk, void* stream);

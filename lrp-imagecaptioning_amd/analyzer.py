@@ -7,7 +7,17 @@
 `image_model` is an `ImageModelSpec` (layer list + weights) instead of a Keras model: the
 symbolic graph reversal of the reference (utils/keras/graph.py:704-942) is not reproduced,
 only its semantics — Conv -> Alpha1Beta0Rule, MaxPooling -> gradient routing, fused ReLU ->
-pass-through, head relevance := second input — executed by the HIP encoder path."""
+pass-through, head relevance := second input — executed by the HIP encoder path.
+
+The gradient baselines beside it (innvestigate/analyzer/gradient_based.py:101-265), same surface:
+
+    Gradient(image_model, postprocess=None | "abs" | "square", neuron_selection_mode='replace')
+    InputTimesGradient(image_model, ...)          # gradient (post-processed) x X
+    GuidedBackprop(image_model, ...)              # every ReLU clamps what arrives at 0 before its own gradient
+    analyzer.analyze([X, head])                   # -> (N,H,W,3)
+
+on lrp_cnn_walk in exact fp32 (LRP_PREC_FP32: a ReLU decision taken in another arithmetic switches whole gradient paths),
+for a VGG-style or a ResNet `ImageModelSpec`."""
 import numpy as np
 
 from .engine import LRPEngine
@@ -76,3 +86,88 @@ class LRPSequentialPresetA(object):
         if neuron_selection is not None:
             raise ValueError("Only neuron_selection_mode 'index' expects the neuron_selection parameter.")  # base.py:489-492
         return self._impl.analyze(X)
+
+
+def _check_selection_mode(neuron_selection_mode):
+    if neuron_selection_mode not in ["max_activation", "index", "all", "replace"]:
+        raise ValueError("neuron_selection parameter is not valid.")             # base.py:332-333
+    if neuron_selection_mode != "replace":
+        raise NotImplementedError("only neuron_selection_mode='replace' is on the captioning hot path")
+
+
+class _GradientWalkAnalyzer(object):
+    """`analyze([X, head])` of a gradient_based analyzer on the engine's encoder walk (lrp_cnn_walk)."""
+    _walk = "gradient"
+
+    def __init__(self, model, neuron_selection_mode="replace", max_batch=8, device=None):
+        _check_selection_mode(neuron_selection_mode)
+        self._neuron_selection_mode = neuron_selection_mode
+        self._model = model
+        h, w, c = model.output_shape()
+        self._engine = LRPEngine(decoder="adaptive", cnn_cfg=model.cnn_cfg, img_hw=model.img_hw, L=h * w, D=c, H=8, E=8,
+                                 V=4, max_images=max_batch, max_tokens=max_batch, max_caption_len=2, device=device,
+                                 resnet=model.resnet)
+        self._engine.set_weights(model.weights)
+        self._engine.set_precision("fp32")
+
+    def _walk_of_call(self):
+        return self._walk
+
+    def _finish(self, g, img):
+        return g
+
+    def analyze(self, X, neuron_selection=None):
+        if neuron_selection is not None:
+            raise ValueError("Only neuron_selection_mode 'index' expects the neuron_selection parameter.")  # base.py:489-492
+        X = list(X) if isinstance(X, (list, tuple)) else [X]
+        if len(X) != 2:
+            raise ValueError("neuron_selection_mode 'replace' expects [X, head]")
+        img, R = np.asarray(X[0], dtype=np.float32), np.asarray(X[1], dtype=np.float32)
+        n = img.shape[0]
+        if R.shape[0] != n:
+            raise ValueError("X and head must have the same batch size")
+        e = self._engine
+        out = np.empty_like(img)
+        for lo in range(0, n, e.max_images):
+            hi = min(n, lo + e.max_images, lo + e.max_tokens)
+            e.encode_images(img[lo:hi])
+            g = e.cnn_walk(list(range(hi - lo)), R[lo:hi].reshape(hi - lo, e.L, e.D), self._walk_of_call()).cpu().numpy()
+            out[lo:hi] = self._finish(g, img[lo:hi])
+        return out
+
+
+class Gradient(_GradientWalkAnalyzer):
+    """gradient_based.py:101-151: the gradient of the head-weighted output w.r.t. the input, optionally |.| or squared."""
+
+    def __init__(self, model, postprocess=None, **kwargs):
+        if postprocess not in [None, "abs", "square"]:
+            raise ValueError("Parameter 'postprocess' must be either None, 'abs', or 'square'.")   # :110-112
+        self._postprocess = postprocess
+        super(Gradient, self).__init__(model, **kwargs)
+
+    def _post(self, g):
+        if self._postprocess == "abs":
+            return np.abs(g)
+        if self._postprocess == "square":
+            return np.square(g)
+        return g
+
+    def _finish(self, g, img):
+        return self._post(g)
+
+
+class InputTimesGradient(Gradient):
+    """gradient_based.py:154-176: X times the (post-processed) gradient.  Without a post-processing step the product is taken
+    on the device (the walk's Input x Gradient stem); with one, the gradient is post-processed first, as in the reference."""
+    _walk = "input_x_gradient"
+
+    def _walk_of_call(self):
+        return "input_x_gradient" if self._postprocess is None else "gradient"
+
+    def _finish(self, g, img):
+        return g if self._postprocess is None else img * self._post(g)
+
+
+class GuidedBackprop(_GradientWalkAnalyzer):
+    """gradient_based.py:228-265: every layer with a ReLU first clamps the arriving value at 0, then applies its gradient."""
+    _walk = "guided_backprop"

@@ -288,7 +288,11 @@ constexpr int conv_halo_rows(int BM) { return BM == 256 ? 352 : 192; }   // x 12
 // small-grid launches (6 MFMAs per wave and iteration) then run at one L2 / HBM round trip per k-step [MI355X, one image:
 // 0.65 us per k-step, 95 us for a K = 4608 launch].  With NS stages NS-1 chunks are in flight and the barrier waits with a
 // COUNTED s_waitcnt vmcnt((NS-2) x DMA instructions per chunk) for the oldest only.
-template <int WM, int WN, int TM, int TN, int EPI, int PREC, bool HALO = false, bool BREG = false, int TERMS = 7, int NS = 2>
+// GMASK (EPI_MUL, PREC_FP32 only: the ResNet encoder's gradient walks, resnet_encoder.h explain_grad): `aux` and `join_gate` are
+// BYTE masks [images][H][W][N] (1 = the ReLU behind this tensor was active) instead of fp32 gates.  A template axis of its own, so
+// that no other instantiation carries its loads (a runtime flag in the shared epilogue costs the VGG walk registers).
+template <int WM, int WN, int TM, int TN, int EPI, int PREC, bool HALO = false, bool BREG = false, int TERMS = 7, int NS = 2,
+          bool GMASK = false>
 __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_waves(WM * WN, TM, TN, HALO)) void conv_igemm_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (the buffer-resource builtins are device-only)
   constexpr int NW = WM * WN, NT = 64 * NW;           // waves / threads per block (4 or 8 waves)
@@ -1591,7 +1595,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
           // Rows are located twice (at issue and at use: a few VALU ops) instead of keeping six arrays of NP entries alive.
           if constexpr (PREC != PREC_F16X2) {
             const bool tail_ = EPI == EPI_MUL && a.join != nullptr, head2_ = EPI == EPI_MUL && a.out2s != nullptr;
-            if (!(EPI == EPI_MUL && a.gate_none) && !tail_ && !head2_ && !a.gate_binary && !a.relu_out && !a.epi_generic) {
+            if (!GMASK && !(EPI == EPI_MUL && a.gate_none) && !tail_ && !head2_ && !a.gate_binary && !a.relu_out && !a.epi_generic) {
               constexpr int NPf = RH / RPP;
               constexpr int UPf = EPI == EPI_MUL_UP2 ? 4 : 1;
               constexpr int RING = (UPf == 1 ? 4 : 2) < NPf ? (UPf == 1 ? 4 : 2) : NPf;
@@ -1689,6 +1693,23 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
           };
           auto load_gates = [&](Gates& G, int ps) {
             const f32x4 one4 = {1.f, 1.f, 1.f, 1.f};
+            if constexpr (GMASK) {
+              static_assert(EPI == EPI_MUL && PREC == PREC_FP32 && CW == 4, "byte-mask gates: exact fp32 EPI_MUL only");
+              auto m4 = [](const float* base, size_t e) {
+                const unsigned m = *reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(base) + e);
+                f32x4 g;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) g[q] = ((m >> (8 * q)) & 0xFFu) ? 1.f : 0.f;
+                return g;
+              };
+              const size_t go = ((size_t)imgv[ps] * HW + hv[ps] * a.W + wv[ps]) * a.N + col;
+              G.g[0][0] = m4(a.aux, go);
+              if (tail) {
+                G.jn[0] = *reinterpret_cast<const f32x4*>(a.join + (size_t)rowv[ps] * a.N + col);
+                G.jg[0] = m4(a.join_gate, go);
+              }
+              return;
+            }
 #pragma unroll
             for (int q = 0; q < UPN; ++q)
 #pragma unroll
@@ -1984,8 +2005,10 @@ inline hipError_t conv_launch_img(ConvArgs a, hipStream_t st) {
   return hipGetLastError();
 }
 
-template <int EPI, int PREC, int TERMS = 7>
+template <int EPI, int PREC, int TERMS = 7, bool GMASK = false>
 inline hipError_t conv_launch_epi(ConvArgs a, hipStream_t st) {
+  static_assert(!GMASK || (EPI == EPI_MUL && PREC == PREC_FP32), "byte-mask gates: exact fp32 EPI_MUL only");
+  if (GMASK && (a.out2s || a.gate_none || a.up2_src || a.img_part || a.pool_gc)) return hipErrorInvalidValue;
   constexpr int need = PREC != PREC_FP32 ? 7 : 3;                                     // 16 B (fp32) / 32 B (split8) epilogue
   if (PREC == PREC_F16X2 && (EPI == EPI_MUL || EPI == EPI_MUL_UP2) && (!a.tok_fac || !a.tok_max_out || a.out_plain)) return hipErrorInvalidValue;
   if (PREC == PREC_F16X2 && (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_FWD_DUAL) && !a.in_unscale) return hipErrorInvalidValue;
@@ -2113,7 +2136,7 @@ inline hipError_t conv_launch_epi(ConvArgs a, hipStream_t st) {
   if (small_tile) {
     a.m_tiles = (a.M + 63) / 64;
     a.n_tiles = (a.N + 63) / 64;
-    hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 1, 1, EPI, PREC, false, false, TERMS, CONV_SMALL_NS>), dim3(a.m_tiles * a.n_tiles), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 1, 1, EPI, PREC, false, false, TERMS, CONV_SMALL_NS, GMASK>), dim3(a.m_tiles * a.n_tiles), dim3(256), 0, st, a);
     return hipGetLastError();
   }
   const dim3 grid(a.m_tiles * a.n_tiles);
@@ -2125,11 +2148,11 @@ inline hipError_t conv_launch_epi(ConvArgs a, hipStream_t st) {
   }
   const dim3 block(256);
   if (t.BN == 128)
-    hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, false, false, TERMS>), grid, block, 0, st, a);
+    hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, false, false, TERMS, 2, GMASK>), grid, block, 0, st, a);
   else if (t.BN == 64)
-    hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 1, EPI, PREC, false, false, TERMS>), grid, block, 0, st, a);
+    hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 1, EPI, PREC, false, false, TERMS, 2, GMASK>), grid, block, 0, st, a);
   else
-    hipLaunchKernelGGL((conv_igemm_kernel<4, 1, 1, 1, EPI, PREC, false, false, TERMS>), grid, block, 0, st, a);
+    hipLaunchKernelGGL((conv_igemm_kernel<4, 1, 1, 1, EPI, PREC, false, false, TERMS, 2, GMASK>), grid, block, 0, st, a);
   return hipGetLastError();
 }
 
@@ -2179,6 +2202,11 @@ inline hipError_t conv_launch(int epi, const ConvArgs& a, hipStream_t st, int pr
     case EPI_IMG_STENCIL: return conv_launch_img<PREC_FP32>(a, st);
   }
   return hipErrorInvalidValue;
+}
+
+// the ResNet gradient walks' transposed convs: exact fp32, `aux` / `join_gate` are byte masks (conv_igemm_kernel GMASK)
+inline hipError_t conv_launch_grad_mask(const ConvArgs& a, hipStream_t st) {
+  return conv_launch_epi<EPI_MUL, PREC_FP32, 7, true>(a, st);
 }
 
 // ---- host-side weight packing (one-off at lrp_set_weight time)

@@ -359,9 +359,11 @@ int lrp_cnn_walk(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const fl
     if (!h || !img_idx_host || !head_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
     if (walk < LRP_WALK_LRP || walk > LRP_WALK_GUIDED_BACKPROP) return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
     if (h->encoded() < 1 || h->features_only()) return fail(LRP_ERR_STATE, "lrp_encode_images must run before lrp_cnn_walk");
-    if (h->resnet && walk != LRP_WALK_LRP) return fail(LRP_ERR_UNSUPPORTED, "gradient walks exist for the conv-list (VGG) encoder only");
+    if (h->resnet && walk != LRP_WALK_LRP && h->rn.prec != PREC_FP32)   // (checked before any staging: nothing runs)
+      return fail(LRP_ERR_UNSUPPORTED, "gradient walks on a ResNet encoder run in LRP_PREC_FP32 only: set it with lrp_set_precision "
+                                       "and call lrp_encode_images again");
     LRP_TRY(stage_indices(h, n, img_idx_host, nullptr, false, S(stream)));
-    if (h->resnet) return h->rn.explain(n, h->idx_dev.as<int>(), head_dev, out_dev, S(stream));
+    if (h->resnet) return h->rn.explain(n, h->idx_dev.as<int>(), head_dev, out_dev, S(stream), walk);
     h->enc.row2img_host = h->idx_pinned;
     return h->enc.explain(n, h->idx_dev.as<int>(), head_dev, out_dev, S(stream), walk);
   });

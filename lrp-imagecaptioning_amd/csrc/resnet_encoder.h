@@ -5,6 +5,9 @@
 //   explain(): one reverse walk per TOKEN: three (four) convs per bottleneck block on conv_igemm + streaming kernels
 // The algorithm is oracle/resnet_lrp_ref.analyze_cached, which equals the literal iNNvestigate walk to 1e-10.
 // This path runs in exact fp32 (PREC_FP32) throughout.
+//   explain_grad(): the gradient baselines (Gradient / InputTimesGradient / GuidedBackprop) in LRP_PREC_FP32 mode: the same
+//              convT launches with BN-scaled full-sign weights (w_g, packed on the first such walk) and the ReLU decisions
+//              the fp32 forward recorded as byte masks (RnUnit::mask, RnBlock::omask).
 #pragma once
 #include <algorithm>
 #include <string>
@@ -30,6 +33,11 @@ struct RnUnit {            // conv + BN
   DevBuf w_dual_h, wds;    // w_dual as fp16 pairs scaled by a power of two + its scale record (f16_operand.h)
   bool dual_il = false;    // ... with its rows interleaved per 32 channels ([w | w+] side by side): BN + gate in the conv's epilogue
   DevBuf gate;             // [B][Hout][Wout][cout]: act*Q (relu units) or Q (pre-Add units)
+  // gradient walks: [B][Hout][Wout][cout] bytes, y > 0 (relu units behind the stem; written by the LRP_PREC_FP32 forward), and the
+  // backward matrix of conv + BN (w_b's layout, full sign, W * gamma / sqrt(var + eps)), packed on the first gradient walk after a
+  // weight of the unit changed (grad_ok)
+  DevBuf mask, w_g;
+  bool grad_ok = false;
   size_t out_elems() const { return (size_t)Hout * Wout * cout; }
   size_t in_elems() const { return (size_t)Hin * Win * cin; }
 };
@@ -40,6 +48,7 @@ struct RnBlock {
   DevBuf t_in;             // [B][Hin][Win][cin] block input (what relevance is multiplied with at the fork)
   DevBuf t_sub;            // [B][H][W][cin] stride-2 gather of t_in (first block of stacks 3..5)
   DevBuf GA, GS;           // [B][H][W][4f]: fA*Q3 and fS (identity) / fS*Q0 (projection)
+  DevBuf omask;            // [B][H][W][4f] bytes: block output > 0 (LRP_PREC_FP32 forward; the gradient walks)
 };
 
 struct ResNetEncoder {
@@ -62,6 +71,8 @@ struct ResNetEncoder {
   bool features_only = false;
   bool profile = false;
   int prec = PREC_BF16X3;  // arithmetic of the reverse walk's conv chains (lrp_set_precision); forward stays exact fp32
+  bool masks_ok = false;   // the ReLU masks belong to the current encode (an LRP_PREC_FP32 forward)
+  int64_t* ws_total = nullptr;   // the handle's workspace counter (lazy allocations of the gradient walks)
   std::vector<ProfileRec> prof;
 
   int add_unit(const std::string& nm, int k, int cin, int cout, int stride, int Hin, int Win, bool relu) {
@@ -74,6 +85,7 @@ struct ResNetEncoder {
 
   int init(const lrp_config& c, int64_t* total) {
     img_h = c.img_h; img_w = c.img_w; max_images = c.max_images; max_tokens = c.max_tokens; stem_c = c.resnet_stem;
+    ws_total = total;
     if (c.resnet_n_stacks < 1 || c.resnet_n_stacks > 8) return fail(LRP_ERR_INVALID, "resnet_n_stacks out of range");
     if ((img_h % 4) || (img_w % 4) || stem_c % 4) return fail(LRP_ERR_UNSUPPORTED, "image size and stem width must be multiples of 4");
     add_unit("conv1", 7, 3, stem_c, 2, img_h, img_w, true);
@@ -170,6 +182,7 @@ struct ResNetEncoder {
         LRP_TRY(up(*dst[s], std::vector<float>(data, data + u.cout), total));
       }
       u.have[s] = true;
+      u.grad_ok = false;
       norms_ready = false;
       return LRP_OK;
     }
@@ -208,6 +221,7 @@ struct ResNetEncoder {
         LRP_HIP_CHECK(hipMemcpyAsync(dst[s]->p, data_dev, (size_t)u.cout * 4, hipMemcpyDeviceToDevice, st));
       }
       u.have[s] = true;
+      u.grad_ok = false;
       norms_ready = false;
       encoded = 0;                                       // caches belong to the old weights
       return LRP_OK;
@@ -352,7 +366,7 @@ struct ResNetEncoder {
   // slots_in: maxima of x (fp16-pair forward: the power of two x is scaled by); slots_out: where max|act| is collected
   // (nullptr: nobody convolves this output)
   int unit_forward(RnUnit& u, const float* x, int B, float* act, hipStream_t st, const unsigned* slots_in = nullptr,
-                   unsigned* slots_out = nullptr) {
+                   unsigned* slots_out = nullptr, unsigned char* mask = nullptr) {
     const float* xin = x;
     if (u.k == 1 && u.stride == 2) {
       const size_t n = (size_t)B * u.Hout * u.Wout * u.cin;
@@ -398,7 +412,7 @@ struct ResNetEncoder {
     const size_t n = (size_t)B * u.out_elems();
     hipLaunchKernelGGL(rn_bn_unit_kernel, dim3(stream_grid(n)), dim3(256), 0, st, fc.as<float>(), fz.as<float>(),
                        u.gamma.as<float>(), u.beta.as<float>(), u.mean.as<float>(), u.var.as<float>(), RN_BN_EPS, act,
-                       u.gate.as<float>(), (float*)nullptr, n, u.cout, u.relu ? 1 : 0, slots_out);
+                       u.gate.as<float>(), (float*)nullptr, n, u.cout, u.relu ? 1 : 0, slots_out, mask);
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   }
@@ -529,9 +543,21 @@ struct ResNetEncoder {
     return LRP_OK;
   }
 
+  // the ReLU masks of the gradient walks (allocated by the first LRP_PREC_FP32 encode: other modes never pay for them)
+  int alloc_masks() {
+    const size_t B = max_images;
+    for (RnBlock& b : blocks) {
+      for (int ui : {b.u1, b.u2})
+        if (!units[ui].mask.p) LRP_TRY(units[ui].mask.alloc(B * units[ui].out_elems(), ws_total));
+      if (!b.omask.p) LRP_TRY(b.omask.alloc(B * (size_t)b.H * b.W * 4 * b.f, ws_total));
+    }
+    return LRP_OK;
+  }
+
   int encode(const float* images_dev, int B, hipStream_t st) {
     if (B < 1 || B > max_images) return fail(LRP_ERR_INVALID, "B=%d outside [1,%d]", B, max_images);
     LRP_TRY(check_ready());
+    masks_ok = false;
     if (emit_ok()) {
       LRP_HIP_CHECK(hipMemcpyAsync(images.p, images_dev, (size_t)B * img_h * img_w * 3 * 4, hipMemcpyDeviceToDevice, st));
       LRP_TRY(encode_emit(B, st));
@@ -541,6 +567,9 @@ struct ResNetEncoder {
     }
     LRP_HIP_CHECK(hipMemcpyAsync(images.p, images_dev, (size_t)B * img_h * img_w * 3 * 4, hipMemcpyDeviceToDevice, st));
     LRP_HIP_CHECK(hipMemsetAsync(act_max.p, 0, act_max.bytes, st));
+    const bool rec = prec == PREC_FP32;                  // record the ReLU masks (the gradient walks exist in this mode only)
+    if (rec) LRP_TRY(alloc_masks());
+    auto mask_of = [&](RnUnit& u) { return rec ? u.mask.as<unsigned char>() : (unsigned char*)nullptr; };
     RnUnit& s = units[0];
     {  // stem: im2col -> two 1-tap GEMMs (c exact / Z with both sign branches) -> BN + relu + gate
       const size_t tot = (size_t)B * s.Hout * s.Wout * 2 * RN_STEM_K;
@@ -558,7 +587,7 @@ struct ResNetEncoder {
       const size_t n = (size_t)B * s.out_elems();
       hipLaunchKernelGGL(rn_bn_unit_kernel, dim3(stream_grid(n)), dim3(256), 0, st, fc.as<float>(), fz.as<float>(),
                          s.gamma.as<float>(), s.beta.as<float>(), s.mean.as<float>(), s.var.as<float>(), RN_BN_EPS,
-                         a0.as<float>(), s.gate.as<float>(), q_stem.as<float>(), n, s.cout, 1, unit_slots(0));
+                         a0.as<float>(), s.gate.as<float>(), q_stem.as<float>(), n, s.cout, 1, unit_slots(0), (unsigned char*)nullptr);
       LRP_HIP_CHECK(hipGetLastError());
       const size_t np = (size_t)B * (s.Hout / 2) * (s.Wout / 2) * s.cout;
       hipLaunchKernelGGL(rn_pool3_kernel, dim3(stream_grid(np)), dim3(256), 0, st, a0.as<float>(), blocks[0].t_in.as<float>(),
@@ -577,8 +606,8 @@ struct ResNetEncoder {
         LRP_HIP_CHECK(hipGetLastError());
       }
       // main path: fa <- a1, fb <- a2, fa <- y3 ; shortcut: fsc2 (= r0 scratch is per-token; use GS buffer as temp) ...
-      LRP_TRY(unit_forward(units[b.u1], t, B, fa.as<float>(), st, ts, unit_slots(b.u1)));
-      LRP_TRY(unit_forward(units[b.u2], fa.as<float>(), B, fb.as<float>(), st, unit_slots(b.u1), unit_slots(b.u2)));
+      LRP_TRY(unit_forward(units[b.u1], t, B, fa.as<float>(), st, ts, unit_slots(b.u1), mask_of(units[b.u1])));
+      LRP_TRY(unit_forward(units[b.u2], fa.as<float>(), B, fb.as<float>(), st, unit_slots(b.u1), unit_slots(b.u2), mask_of(units[b.u2])));
       LRP_TRY(unit_forward(units[b.u3], fb.as<float>(), B, fa.as<float>(), st, unit_slots(b.u2)));        // fa = y3
       const float* sc = t;
       if (b.u0 >= 0) {
@@ -590,11 +619,13 @@ struct ResNetEncoder {
       const size_t n = (size_t)B * b.H * b.W * 4 * b.f;
       hipLaunchKernelGGL(rn_block_out_kernel, dim3(stream_grid(n / 4)), dim3(256), 0, st, sc, fa.as<float>(),
                          units[b.u3].gate.as<float>(), b.u0 >= 0 ? units[b.u0].gate.as<float>() : (const float*)nullptr, o,
-                         b.GA.as<float>(), b.GS.as<float>(), n, last ? (unsigned*)nullptr : block_slots(bi));
+                         b.GA.as<float>(), b.GS.as<float>(), n, last ? (unsigned*)nullptr : block_slots(bi),
+                         rec ? b.omask.as<unsigned char>() : (unsigned char*)nullptr);
       LRP_HIP_CHECK(hipGetLastError());
     }
     encoded = B;
     features_only = false;
+    masks_ok = rec;
     return LRP_OK;
   }
 
@@ -622,9 +653,10 @@ struct ResNetEncoder {
     return LRP_OK;
   }
 
-  int explain(int n, const int* row2img, const float* R_feat_dev, float* R_img_dev, hipStream_t st) {
+  int explain(int n, const int* row2img, const float* R_feat_dev, float* R_img_dev, hipStream_t st, int walk = LRP_WALK_LRP) {
     if (n < 1 || n > max_tokens) return fail(LRP_ERR_INVALID, "n=%d outside [1,%d]", n, max_tokens);
     if (encoded < 1 || features_only) return fail(LRP_ERR_STATE, "lrp_encode_images must run before the CNN explain");
+    if (walk != LRP_WALK_LRP) return explain_grad(n, row2img, R_feat_dev, R_img_dev, st, walk);
     const float* Ro = R_feat_dev;          // relevance at the current block's output
     float* cur = r0.as<float>();           // where the next R_t is written (ping-pong r0 / r4)
     float* other = r4.as<float>();
@@ -757,11 +789,139 @@ struct ResNetEncoder {
     ca.in = r1.as<float>(); ca.NB = n * s.Hout * s.Wout; ca.H = 1; ca.W = 1; ca.Cin = s.cout; ca.CinP = conv_cinp(s.cout);
     ca.taps = 1; ca.wpk = ssplit ? s.w_bs.as<float>() : s.w_b.as<float>(); ca.N = RN_STEM_TCOLS; ca.out = r2.as<float>();
     LRP_HIP_CHECK(conv_launch(EPI_STORE, ca, st, ssplit ? PREC_BF16X3 : PREC_FP32));
-    hipLaunchKernelGGL(rn_stem_stencil_kernel, dim3(stream_grid((size_t)n * img_h * img_w)), dim3(256), 0, st, r2.as<float>(),
+    hipLaunchKernelGGL(rn_stem_stencil_kernel<0>, dim3(stream_grid((size_t)n * img_h * img_w)), dim3(256), 0, st, r2.as<float>(),
                        images.as<float>(), row2img, R_img_dev, n, img_h, img_w);
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   }
+
+  // ---- gradient walks (lrp_cnn_walk: LRP_WALK_GRADIENT / _INPUT_X_GRADIENT / _GUIDED_BACKPROP) -------------------------------
+  // w_g of every unit whose weights changed since its last packing, from the device-resident forward matrix w_a and the BN
+  // vectors (no host copy of the weights is kept; LRP-only users never allocate or pack these)
+  int ensure_grad_weights(hipStream_t st) {
+    for (RnUnit& u : units) {
+      if (u.grad_ok) continue;
+      if (u.k == 7) {
+        const int Npb = conv_npad(RN_STEM_TCOLS), Kb = conv_cinp(u.cout);
+        const size_t nb = (size_t)Npb * Kb;
+        if (!u.w_g.p) LRP_TRY(u.w_g.alloc(nb * 4, ws_total));
+        hipLaunchKernelGGL(rn_pack_stem_grad_kernel, dim3(stream_grid(nb)), dim3(256), 0, st, u.w_a.as<float>(), u.gamma.as<float>(),
+                           u.var.as<float>(), RN_BN_EPS, u.w_g.as<float>(), u.cout, Npb, Kb);
+      } else {
+        const int taps = u.k * u.k, CPi = conv_cinp(u.cin), CPo = conv_cinp(u.cout), rows = conv_npad(u.cin);
+        const size_t nb = (size_t)rows * taps * CPo;
+        if (!u.w_g.p) LRP_TRY(u.w_g.alloc(nb * 4, ws_total));
+        hipLaunchKernelGGL(rn_pack_grad_kernel, dim3(stream_grid(nb)), dim3(256), 0, st, u.w_a.as<float>(), u.gamma.as<float>(),
+                           u.var.as<float>(), RN_BN_EPS, u.w_g.as<float>(), taps, u.cin, u.cout, CPi, CPo, rows);
+      }
+      LRP_HIP_CHECK(hipGetLastError());
+      u.grad_ok = true;
+    }
+    return LRP_OK;
+  }
+  // one unit's gradient step: out = convT(S, W s) on the unit's output grid, then (mask != nullptr) the ReLU in front of it —
+  // GUIDED: clamp at 0 — and (tail != nullptr) the residual join out = rho(acc + tail) [mask], all in the conv's epilogue
+  int grad_backward(const RnUnit& u, int n, const int* row2img, const float* S, const unsigned char* mask, float* out, bool guided,
+                    hipStream_t st, const float* tail = nullptr) {
+    ConvArgs ca{};
+    ca.in = S; ca.wpk = u.w_g.as<float>(); ca.row2img = row2img; ca.out = out; ca.N = u.cin; ca.out_plain = 1;
+    ca.Cin = u.cout; ca.CinP = conv_cinp(u.cout); ca.NB = n; ca.H = u.Hout; ca.W = u.Wout; ca.taps = u.k == 3 ? 9 : 1;
+    if (!mask) {
+      ca.gate_none = 1;
+      LRP_HIP_CHECK(conv_launch(EPI_MUL, ca, st, PREC_FP32));
+      return LRP_OK;
+    }
+    ca.aux = reinterpret_cast<const float*>(mask);       // (byte masks: conv_igemm_kernel GMASK)
+    ca.relu_out = guided ? 1 : 0;
+    if (tail) { ca.join = tail; ca.join_gate = reinterpret_cast<const float*>(mask); }
+    LRP_HIP_CHECK(conv_launch_grad_mask(ca, st));
+    return LRP_OK;
+  }
+  // The walk (oracle: tests/resnet_grad_ref.py).  One tensor per block boundary: G = the gradient at the block's pre-ReLU sum,
+  // which is both the head of the block's chain and its shortcut's term of the join below.
+  //   identity block:   G' = [t_in > 0] rho( convT1([a1 > 0] rho(convT2([a2 > 0] rho(convT3(G))))) + G )
+  //   projection block: the same main chain and convT0(G) on the coarse grid, summed (scattered to the even positions behind a
+  //                     stride 2) BEFORE the block input's ReLU; the first block's input is the stem pool's output: no ReLU
+  //   stem:             pool routing summed over the overlapping windows, rho, [a0 > 0], convT of the 7x7/2 conv, crop
+  // rho = relu for GUIDED_BACKPROP (every ReLU clamps what arrives first), identity otherwise.
+  int explain_grad(int n, const int* row2img, const float* head, float* R_img_dev, hipStream_t st, int walk) {
+    if (walk != LRP_WALK_GRADIENT && walk != LRP_WALK_INPUT_X_GRADIENT && walk != LRP_WALK_GUIDED_BACKPROP)
+      return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
+    if (prec != PREC_FP32)
+      return fail(LRP_ERR_UNSUPPORTED, "gradient walks on a ResNet encoder run in LRP_PREC_FP32 only: set it with lrp_set_precision "
+                                       "and call lrp_encode_images again");
+    if (!masks_ok) return fail(LRP_ERR_STATE, "lrp_encode_images must run in LRP_PREC_FP32 mode before a ResNet gradient walk");
+    const bool guided = walk == LRP_WALK_GUIDED_BACKPROP;
+    LRP_TRY(ensure_grad_weights(st));
+    float* G = r0.as<float>();
+    float* other = r4.as<float>();
+    {
+      const RnBlock& t = blocks.back();
+      const size_t per = (size_t)t.H * t.W * 4 * t.f;
+      hipLaunchKernelGGL(rn_grad_head_kernel, dim3(stream_grid((size_t)n * per / 4)), dim3(256), 0, st, head,
+                         t.omask.as<unsigned char>(), row2img, G, n, per, guided ? 1 : 0);
+      LRP_HIP_CHECK(hipGetLastError());
+    }
+    for (int bi = (int)blocks.size() - 1; bi >= 0; --bi) {
+      const RnBlock& b = blocks[bi];
+      const RnUnit &u1 = units[b.u1], &u2 = units[b.u2], &u3 = units[b.u3];
+      LRP_TRY(grad_backward(u3, n, row2img, G, u2.mask.as<unsigned char>(), r2.as<float>(), guided, st));
+      LRP_TRY(grad_backward(u2, n, row2img, r2.as<float>(), u1.mask.as<unsigned char>(), r3.as<float>(), guided, st));
+      const unsigned char* in_mask = bi > 0 ? blocks[bi - 1].omask.as<unsigned char>() : (const unsigned char*)nullptr;
+      if (b.u0 < 0) {
+        // identity block (never the first): the join and the block input's ReLU in unit 1's epilogue
+        LRP_TRY(grad_backward(u1, n, row2img, r3.as<float>(), in_mask, other, guided, st, G));
+      } else {
+        LRP_TRY(grad_backward(u1, n, row2img, r3.as<float>(), nullptr, r1.as<float>(), guided, st));
+        LRP_TRY(grad_backward(units[b.u0], n, row2img, G, nullptr, r5.as<float>(), guided, st));
+        const size_t tot = (size_t)n * b.Hin * b.Win * b.cin / 4;
+        if (b.stride == 2)
+          hipLaunchKernelGGL(rn_grad_join_kernel<true>, dim3(stream_grid(tot)), dim3(256), 0, st, r1.as<float>(), r5.as<float>(), in_mask,
+                             row2img, other, n, b.Hin, b.Win, b.cin, guided ? 1 : 0);
+        else
+          hipLaunchKernelGGL(rn_grad_join_kernel<false>, dim3(stream_grid(tot)), dim3(256), 0, st, r1.as<float>(), r5.as<float>(), in_mask,
+                             row2img, other, n, b.Hin, b.Win, b.cin, guided ? 1 : 0);
+        LRP_HIP_CHECK(hipGetLastError());
+      }
+      std::swap(G, other);
+    }
+    // stem: G is the gradient at the pool's output
+    const RnUnit& s = units[0];
+    const size_t tot = (size_t)n * s.Hout * s.Wout * s.cout / 4;
+    hipLaunchKernelGGL(rn_grad_pool_route_kernel, dim3(stream_grid(tot)), dim3(256), 0, st, G, pool_win.as<unsigned char>(),
+                       a0.as<float>(), row2img, r1.as<float>(), n, s.Hout, s.Wout, s.cout, guided ? 1 : 0);
+    LRP_HIP_CHECK(hipGetLastError());
+    const bool ixg = walk == LRP_WALK_INPUT_X_GRADIENT;
+    if (sw().img_fused != 0 && s.cout == 64 && conv_npad(RN_STEM_TCOLS) >= 5 * 60 + 4 && conv_cinp(s.cout) == 64) {
+      const int txs = (s.Wout + RN_ST - 1) / RN_ST, tys = (s.Hout + RN_ST - 1) / RN_ST;
+      if (!stem_grad_attr_set) {
+        LRP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rn_stem_reverse_kernel<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, RN_STEM_LDS));
+        LRP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rn_stem_reverse_kernel<false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, RN_STEM_LDS));
+        stem_grad_attr_set = true;
+      }
+      if (ixg)
+        hipLaunchKernelGGL((rn_stem_reverse_kernel<false, 2>), dim3((unsigned)(n * txs * tys)), dim3(512), RN_STEM_LDS, st, r1.as<float>(),
+                           s.w_g.as<float>(), images.as<float>(), row2img, R_img_dev, s.Hout, s.Wout, txs, tys);
+      else
+        hipLaunchKernelGGL((rn_stem_reverse_kernel<false, 1>), dim3((unsigned)(n * txs * tys)), dim3(512), RN_STEM_LDS, st, r1.as<float>(),
+                           s.w_g.as<float>(), images.as<float>(), row2img, R_img_dev, s.Hout, s.Wout, txs, tys);
+      LRP_HIP_CHECK(hipGetLastError());
+      return LRP_OK;
+    }
+    ConvArgs ca{};
+    ca.in = r1.as<float>(); ca.NB = n * s.Hout * s.Wout; ca.H = 1; ca.W = 1; ca.Cin = s.cout; ca.CinP = conv_cinp(s.cout);
+    ca.taps = 1; ca.wpk = s.w_g.as<float>(); ca.N = RN_STEM_TCOLS; ca.out = r2.as<float>();
+    LRP_HIP_CHECK(conv_launch(EPI_STORE, ca, st, PREC_FP32));
+    if (ixg)
+      hipLaunchKernelGGL(rn_stem_stencil_kernel<2>, dim3(stream_grid((size_t)n * img_h * img_w)), dim3(256), 0, st, r2.as<float>(),
+                         images.as<float>(), row2img, R_img_dev, n, img_h, img_w);
+    else
+      hipLaunchKernelGGL(rn_stem_stencil_kernel<1>, dim3(stream_grid((size_t)n * img_h * img_w)), dim3(256), 0, st, r2.as<float>(),
+                         images.as<float>(), row2img, R_img_dev, n, img_h, img_w);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  }
+  bool stem_grad_attr_set = false;
 
   // the stem's routing needs Q alone: what arrives at a0 = relu(y) through the pool is already a relevance
   // (t * C1 of the first block), so multiplying by the relu-unit gate a0*Q would count a0 twice

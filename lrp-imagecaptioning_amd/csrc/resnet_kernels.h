@@ -24,12 +24,13 @@ __device__ __forceinline__ void rn_flush_max(float m, unsigned* __restrict__ slo
 //   y = BN(c);  Q = c (y - beta) / stab((c - mu) y) / safe(Z)     [BN reverse o conv denominator]
 //   relu != 0: act = relu(y), gate = act * Q  (what the NEXT conv's relevance is multiplied with)
 //   relu == 0: act = y (pre-Add tensor), gate = Q
+//   mask (optional, relu units of the LRP_PREC_FP32 forward): mask = y > 0, the ReLU's own decision (the gradient walks)
 __global__ __launch_bounds__(256) void rn_bn_unit_kernel(const float* __restrict__ c, const float* __restrict__ Z,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
                                                          const float* __restrict__ mean, const float* __restrict__ var,
                                                          float bn_eps, float* __restrict__ act, float* __restrict__ gate,
                                                          float* __restrict__ qonly, size_t n, int C, int relu,
-                                                         unsigned* __restrict__ max_slots) {
+                                                         unsigned* __restrict__ max_slots, unsigned char* __restrict__ mask) {
   float m = 0.f;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     const int ch = (int)(i % C);
@@ -41,6 +42,7 @@ __global__ __launch_bounds__(256) void rn_bn_unit_kernel(const float* __restrict
     m = fmaxf(m, fabsf(av));
     gate[i] = relu ? av * q : q;
     if (qonly) qonly[i] = q;
+    if (mask) mask[i] = y > 0.f ? 1 : 0;
   }
   if (max_slots) rn_flush_max(m, max_slots);
 }
@@ -50,7 +52,7 @@ __global__ __launch_bounds__(256) void rn_block_out_kernel(const float* __restri
                                                            const float* __restrict__ Q3, const float* __restrict__ Q0,
                                                            float* __restrict__ o, float* __restrict__ GA,
                                                            float* __restrict__ GS, size_t n,
-                                                           unsigned* __restrict__ max_slots) {
+                                                           unsigned* __restrict__ max_slots, unsigned char* __restrict__ mask) {
   // 16 B per lane and tensor (n is a multiple of 4: channel counts are)
   float m = 0.f;
   const size_t n4 = n / 4;
@@ -71,6 +73,9 @@ __global__ __launch_bounds__(256) void rn_block_out_kernel(const float* __restri
     reinterpret_cast<f32x4*>(o)[i] = ov;
     reinterpret_cast<f32x4*>(GA)[i] = ga;
     reinterpret_cast<f32x4*>(GS)[i] = gs;
+    if (mask)                                            // (optional) o > 0 as bytes: the block-output ReLU of the gradient walks
+      reinterpret_cast<unsigned*>(mask)[i] = (ov[0] > 0.f ? 1u : 0u) | (ov[1] > 0.f ? 1u << 8 : 0u) | (ov[2] > 0.f ? 1u << 16 : 0u) |
+                                             (ov[3] > 0.f ? 1u << 24 : 0u);
   }
   if (max_slots) rn_flush_max(m, max_slots);
 }
@@ -541,7 +546,9 @@ constexpr int RN_SP = 16, RN_ST = 13, RN_SO = 2 * RN_ST;      // patch edge, pat
 constexpr int RN_SROW = 68;                                   // LDS row pitch of the W tile in floats (64 + 4: conflict-free 16 B reads)
 constexpr int RN_STS = 61;                                    // ... of the T tile (60 columns used; odd: the stencil's column reads spread over the banks)
 constexpr int RN_STEM_LDS = (64 * RN_SROW + 256 * RN_STS) * 4;   // 79.9 KB: two workgroups per CU
-template <bool SPLIT>
+// MODE (the image end, like the VGG image layer's img_mode): 0 = LRP, x+ . T+ + x- . T-;  1 = T+ (a gradient: the weights are
+// packed W s into both halves, rn_pack_stem_grad_kernel);  2 = x . T+ (Input x Gradient)
+template <bool SPLIT, int MODE = 0>
 __global__ __launch_bounds__(512, 2) void rn_stem_reverse_kernel(const float* __restrict__ S, const float* __restrict__ Wb,
                                                                  const float* __restrict__ ximg, const int* __restrict__ row2img,
                                                                  float* __restrict__ out, int Ho, int Wo, int tiles_x, int tiles_y) {
@@ -666,10 +673,15 @@ __global__ __launch_bounds__(512, 2) void rn_stem_reverse_kernel(const float* __
     const float* xv = ximg + ((size_t)img * H2 * W2 + pix) * 3;
     float* ov = out + ((size_t)pn * H2 * W2 + pix) * 3;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) ov[c] = xv[c] >= 0.f ? xv[c] * pos[q][c] : xv[c] * neg[q][c];
+    for (int c = 0; c < 3; ++c) {
+      if constexpr (MODE == 1) ov[c] = pos[q][c];
+      else if constexpr (MODE == 2) ov[c] = xv[c] * pos[q][c];
+      else ov[c] = xv[c] >= 0.f ? xv[c] * pos[q][c] : xv[c] * neg[q][c];
+    }
   }
 }
 
+template <int MODE>                                       // as rn_stem_reverse_kernel
 __global__ __launch_bounds__(256) void rn_stem_stencil_kernel(const float* __restrict__ T, const float* __restrict__ ximg,
                                                               const int* __restrict__ row2img, float* __restrict__ out,
                                                               int ntok, int H, int W) {
@@ -695,7 +707,137 @@ __global__ __launch_bounds__(256) void rn_stem_stencil_kernel(const float* __res
     const float* x = ximg + ((size_t)img * HW + pix) * 3;
     float* o = out + idx * 3;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) o[c] = x[c] >= 0.f ? x[c] * pos[c] : x[c] * neg[c];
+    for (int c = 0; c < 3; ++c) {
+      if constexpr (MODE == 1) o[c] = pos[c];
+      else if constexpr (MODE == 2) o[c] = x[c] * pos[c];
+      else o[c] = x[c] >= 0.f ? x[c] * pos[c] : x[c] * neg[c];
+    }
+  }
+}
+
+// ---- gradient walks (Gradient / InputTimesGradient / GuidedBackprop, LRP_PREC_FP32 only; resnet_encoder.h explain_grad) --------
+// A conv + BN unit's backward is convT with the weights scaled per output channel by s = gamma / sqrt(var + eps); a ReLU passes
+// the gradient where its forward output was > 0 (byte masks of the fp32 forward); GUIDED: every ReLU first clamps at 0.
+
+// Backward matrix of a conv + BN unit in the layout of w_b (pack_conv_bwd), full sign and BN-scaled, from the forward matrix
+// w_a [rows >= cout][taps * CPi]:  wg[ci][t * CPo + co] = w_a[co][t' * CPi + ci] * s[co],  t' = taps - 1 - t
+__global__ __launch_bounds__(256) void rn_pack_grad_kernel(const float* __restrict__ wa, const float* __restrict__ gamma,
+                                                           const float* __restrict__ var, float bn_eps, float* __restrict__ wg,
+                                                           int taps, int cin, int cout, int CPi, int CPo, int rows) {
+  const int K = taps * CPo;
+  const size_t total = (size_t)rows * K;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int ci = (int)(i / K), k = (int)(i % K), t = k / CPo, co = k % CPo;
+    float v = 0.f;
+    if (ci < cin && co < cout)
+      v = wa[(size_t)co * taps * CPi + (size_t)(taps - 1 - t) * CPi + ci] * (gamma[co] / sqrtf(var[co] + bn_eps));
+    wg[i] = v;
+  }
+}
+// The stem's tap matrix [Npb][Kb] (layout of its w_b) with W s in BOTH the w+ and the w- rows: row t*6 + c and t*6 + 3 + c =
+// W[t][c][:] * s.  From the stem's forward matrix w_a [Np][2 * RN_STEM_K] (w_a[co][t*3 + c] = W[t][c][co]).
+__global__ __launch_bounds__(256) void rn_pack_stem_grad_kernel(const float* __restrict__ wa, const float* __restrict__ gamma,
+                                                                const float* __restrict__ var, float bn_eps, float* __restrict__ wg,
+                                                                int cout, int Npb, int Kb) {
+  const size_t total = (size_t)Npb * Kb;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int row = (int)(i / Kb), co = (int)(i % Kb), t = row / 6, c = (row % 6) % 3;
+    float v = 0.f;
+    if (t < 49 && co < cout) v = wa[(size_t)co * 2 * RN_STEM_K + t * 3 + c] * (gamma[co] / sqrtf(var[co] + bn_eps));
+    wg[i] = v;
+  }
+}
+
+// head of the walk: out[t][e] = [mask[img(t)][e]] * (GUIDED ? relu(R[t][e]) : R[t][e])   (the last block's output ReLU)
+__global__ __launch_bounds__(256) void rn_grad_head_kernel(const float* __restrict__ R, const unsigned char* __restrict__ mask,
+                                                           const int* __restrict__ row2img, float* __restrict__ out, int ntok,
+                                                           size_t per_img, int guided) {
+  const size_t per4 = per_img / 4, total = (size_t)ntok * per4;      // (per_img % 4 == 0: channel counts are)
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int t = (int)(i / per4);
+    const size_t e = i - (size_t)t * per4;
+    const int img = row2img ? row2img[t] : t;
+    const unsigned m = reinterpret_cast<const unsigned*>(mask)[(size_t)img * per4 + e];
+    f32x4 v = reinterpret_cast<const f32x4*>(R)[i];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float g = guided ? fmaxf(v[q], 0.f) : v[q];
+      v[q] = ((m >> (8 * q)) & 0xFFu) ? g : 0.f;
+    }
+    reinterpret_cast<f32x4*>(out)[i] = v;
+  }
+}
+
+// join of a projection block: fine = a + b (SCATTER: at the even positions of the stride-2 grid, zeros elsewhere), the
+// completed fan-out sum; then the block input's ReLU (mask != nullptr: GUIDED clamp, then [t_in > 0]).  mask == nullptr: the
+// first block, whose input is the stem's pool output (no ReLU there: the clamp waits for the pool routing's sum)
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void rn_grad_join_kernel(const float* __restrict__ a, const float* __restrict__ b,
+                                                           const unsigned char* __restrict__ mask, const int* __restrict__ row2img,
+                                                           float* __restrict__ fine, int NB, int H, int W, int C, int guided) {
+  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2, C4 = C / 4;
+  const size_t total = (size_t)NB * H * W * C4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int c = (int)(i % C4) * 4;
+    size_t r = i / C4;
+    const int w = (int)(r % W);
+    r /= W;
+    const int h = (int)(r % H);
+    const int n = (int)(r / H);
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (!SCATTER || (!(h & 1) && !(w & 1))) {
+      const size_t j = SCATTER ? (((size_t)n * Ho + (h >> 1)) * Wo + (w >> 1)) * C + c : i * 4;
+      v = *reinterpret_cast<const f32x4*>(a + j) + *reinterpret_cast<const f32x4*>(b + j);
+      if (mask) {
+        const int img = row2img ? row2img[n] : n;
+        const unsigned m = *reinterpret_cast<const unsigned*>(mask + (((size_t)img * H + h) * W + w) * C + c);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float g = guided ? fmaxf(v[q], 0.f) : v[q];
+          v[q] = ((m >> (8 * q)) & 0xFFu) ? g : 0.f;
+        }
+      }
+    }
+    reinterpret_cast<f32x4*>(fine)[i] = v;
+  }
+}
+
+// gradient through the stem's overlapping 3x3/2 max-pool (first arg-max of every window, pool_win) and the stem ReLU:
+// S[n][i][j][c] = [a0[img][i][j][c] > 0] * rho(sum_{windows whose winner is (i,j)} R[n][oh][ow][c]),  rho = relu when GUIDED
+// (the clamp acts on the completed sum over the overlapping windows), identity otherwise.  Four channels per thread.
+__global__ __launch_bounds__(256) void rn_grad_pool_route_kernel(const float* __restrict__ R, const unsigned char* __restrict__ win,
+                                                                 const float* __restrict__ a0, const int* __restrict__ row2img,
+                                                                 float* __restrict__ S, int ntok, int H, int W, int C, int guided) {
+  const int Ho = H / 2, Wo = W / 2, CG = C / 4;
+  const size_t total = (size_t)ntok * H * W * CG;
+  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+    const int c = (int)(idx % CG) * 4;
+    size_t r = idx / CG;
+    const int j = (int)(r % W);
+    r /= W;
+    const int i = (int)(r % H);
+    const int t = (int)(r / H);
+    const int img = row2img ? row2img[t] : t;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int oh = i / 2; oh <= (i + 1) / 2; ++oh) {
+      if (oh >= Ho || 2 * oh - 1 > i || 2 * oh + 1 < i) continue;
+      for (int ow = j / 2; ow <= (j + 1) / 2; ++ow) {
+        if (ow >= Wo || 2 * ow - 1 > j || 2 * ow + 1 < j) continue;
+        const unsigned mine = (unsigned)((i - 2 * oh + 1) * 3 + (j - 2 * ow + 1));
+        const unsigned w4 = *reinterpret_cast<const unsigned*>(win + (((size_t)img * Ho + oh) * Wo + ow) * C + c);
+        const f32x4 rv = *reinterpret_cast<const f32x4*>(R + (((size_t)t * Ho + oh) * Wo + ow) * C + c);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          if (((w4 >> (8 * q)) & 0xFFu) == mine) acc[q] += rv[q];
+      }
+    }
+    const f32x4 av = *reinterpret_cast<const f32x4*>(a0 + (((size_t)img * H + i) * W + j) * C + c);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float g = guided ? fmaxf(acc[q], 0.f) : acc[q];
+      acc[q] = av[q] > 0.f ? g : 0.f;
+    }
+    *reinterpret_cast<f32x4*>(S + idx * 4) = acc;
   }
 }
 

@@ -338,7 +338,8 @@ class _GradientMixin(object):
         # accuracy (LRP does not: such a unit carries ~ 0 relevance).  The comparison baselines therefore run the engine
         # with the forward that takes the fewest of those decisions differently from float64 — the exact fp32 MFMA
         # (their walks are exact fp32 in every mode): VGG16-size gradient maps 7e-7 from float64 instead of ~1e-3
-        # (tests/test_gpu_gradient.py).  `self._engine.set_precision("bf16x3")` restores the faster default forward.
+        # (tests/test_gpu_gradient.py).  `self._engine.set_precision("bf16x3")` restores the faster default forward on a VGG
+        # encoder; a ResNet encoder's gradient walks exist in this mode only (include/lrp_hip.h, lrp_cnn_walk).
         self._engine.set_precision("fp32")
 
     def _lstm_decoder_backward(self, t):
