@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define LRP_ABI_VERSION 6
+#define LRP_ABI_VERSION 7
 
 enum {
   LRP_OK = 0,
@@ -330,6 +330,30 @@ int lrp_preprocess_images(const uint8_t* rgb_dev, float* out_dev, int32_t NB, in
  * R_img_dev (n, npix, C) float32, scores_dev (n) float64. */
 int lrp_heatmap_scores(const float* R_img_dev, double* scores_dev, int32_t n, int32_t npix, int32_t C, int32_t mode,
                        void* stream);
+
+/* ABI v7.  Bounding-box correctness evaluation (evaluate_bbox.py:59-86, :191-272, EvaluationBboxCOCO /
+ * EvaluationBboxCOCOBaseline): handle-free operators, device pointers, no synchronisation.  Per workgroup fixed-order
+ * reductions, so a map's or an entry's results do not depend on what else shares the launch.
+ * lrp_eval_relevance_maps: R_img_dev (n, npix, C) float32 (fp64 = 0) or float64 (fp64 = 1) relevance -> maps_dev (n, npix)
+ *   in the same dtype, bit-identical to the reference's numpy chain: BGR -> RGB flip, multiply by `sign` (+1 / -1; the
+ *   shipped script uses -1), max(., 0), channel mean, x / absmax (all zeros when absmax == 0).
+ * lrp_eval_expand_matrix: host only, no GPU.  M_host (g * upscale, g) float64 with pyramid_expand(A, upscale, sigma) =
+ *   M A M^T (skimage.transform.pyramid_expand: bilinear resize with mirrored edges, then a Gaussian blur of radius
+ *   int(4 sigma + 0.5) with scipy's 'reflect' boundary).  g <= 16, g * upscale <= 448.
+ * lrp_eval_attention_maps: att_dev (n, g * g) float32, M_dev = that matrix on the device -> maps_dev (n, S, S) float64,
+ *   S = g * upscale: M A M^T followed by project() (x / absmax, then (x + 1) / 2 if any value is negative).
+ * lrp_eval_box_scores: maps_dev (n, h, w) float32 / float64, boxes_dev (nb, 5) int32 = (map, y0, y1, x0, x1) with
+ *   0 <= y0 <= y1 <= h, 0 <= x0 <= x1 <= w (rows [y0, y1), columns [x0, x1)), thr_dev (nb, K) float64 with K <= 16 ->
+ *   scores_dev (nb, K) float64 = sum over the box of v [v > thr] / sum over the map of v [v > thr], 0 when the
+ *   denominator is 0, capped at 1.  An entry outside these bounds is not read and scores NaN.  The reference's threshold
+ *   carry-over between the boxes of one word is the caller's: it goes into the per-entry thresholds. */
+int lrp_eval_relevance_maps(const void* R_img_dev, void* maps_dev, int32_t fp64, int32_t n, int32_t npix, int32_t C,
+                            int32_t sign, void* stream);
+int lrp_eval_expand_matrix(int32_t g, int32_t upscale, double sigma, double* M_host);
+int lrp_eval_attention_maps(const float* att_dev, const double* M_dev, double* maps_dev, int32_t n, int32_t g,
+                            int32_t upscale, void* stream);
+int lrp_eval_box_scores(const void* maps_dev, int32_t fp64, int32_t n, int32_t h, int32_t w, const int32_t* boxes_dev,
+                        const double* thr_dev, int32_t nb, int32_t K, double* scores_dev, void* stream);
 
 /* Operator-level entries of the fine-tune step's dense products (unit tests at real layer sizes; csrc/train_gemm.h).
  * lrp_op_sgemm: C (+)= op(A) op(B) on the fp32 matrix cores, row-major with leading dimensions;

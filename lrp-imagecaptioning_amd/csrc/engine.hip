@@ -3,6 +3,7 @@
 // encoder (CNN half) and decoder (LSTM/attention half) orchestration.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <exception>
 #include <map>
@@ -15,6 +16,7 @@
 #include "conv_sparse.h"
 #include "decoder.h"
 #include "encoder.h"
+#include "eval_kernels.h"
 #include "resnet_encoder.h"
 #include "rules_kernels.h"
 #include "score_kernels.h"
@@ -760,6 +762,108 @@ int lrp_op_log_softmax_topk(const double* logits_dev, int32_t rows, int32_t V, i
     if (!logits_dev || !ids_dev || !logp_dev) return fail(LRP_ERR_INVALID, "null argument");
     if (rows < 1 || V < 1 || k < 1 || k > V || k > TOPK_MAX) return fail(LRP_ERR_INVALID, "need rows >= 1 and 1 <= k <= min(V, %d)", TOPK_MAX);
     hipLaunchKernelGGL(log_softmax_topk_kernel, dim3(rows), dim3(256), 0, S(stream), logits_dev, V, k, ids_dev, logp_dev);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+// ---- bounding-box correctness evaluation (csrc/eval_kernels.h; evaluate_bbox.py)
+static int eval_expand_matrix(int g, int up, double sigma, double* M) {
+  // pyramid_expand(A, upscale, sigma) = G R A R^T G^T: R (S x g) the bilinear resize of skimage's `resize` (output centre o
+  // samples (o + 0.5) g / S - 0.5, out-of-range neighbours mirrored about the edge samples), G (S x S) scipy's
+  // gaussian_filter1d (taps exp(-0.5 / sigma^2 x^2) normalised, radius int(4 sigma + 0.5), mode 'reflect').  M = G R.
+  const int S = g * up;
+  std::vector<double> Rm((size_t)S * g, 0.0);
+  auto mirror = [g](int j) {
+    if (g == 1) return 0;
+    const int per = 2 * (g - 1);
+    j %= per;
+    if (j < 0) j += per;
+    return j >= g ? per - j : j;
+  };
+  for (int o = 0; o < S; ++o) {
+    const double c = ((double)o + 0.5) * ((double)g / (double)S) - 0.5;
+    const double f = std::floor(c), w1 = c - f;
+    const int j0 = (int)f;
+    Rm[(size_t)o * g + mirror(j0)] += 1.0 - w1;
+    Rm[(size_t)o * g + mirror(j0 + 1)] += w1;
+  }
+  const int rad = (int)(4.0 * sigma + 0.5);
+  std::vector<double> tap(2 * rad + 1);
+  double tsum = 0.0;
+  for (int x = -rad; x <= rad; ++x) tsum += tap[x + rad] = std::exp(-0.5 / (sigma * sigma) * (double)(x * x));
+  for (auto& t : tap) t /= tsum;
+  auto reflect = [S](int j) {
+    const int per = 2 * S;
+    j %= per;
+    if (j < 0) j += per;
+    return j >= S ? per - 1 - j : j;
+  };
+  for (int y = 0; y < S; ++y)
+    for (int j = 0; j < g; ++j) {
+      double s = 0.0;
+      for (int k = -rad; k <= rad; ++k) s += tap[k + rad] * Rm[(size_t)reflect(y + k) * g + j];
+      M[(size_t)y * g + j] = s;
+    }
+  return LRP_OK;
+}
+
+int lrp_eval_expand_matrix(int32_t g, int32_t upscale, double sigma, double* M_host) {
+  return guarded([&]() -> int {
+    if (!M_host) return fail(LRP_ERR_INVALID, "null argument");
+    if (g < 1 || g > EVAL_MAX_G || upscale < 1 || g * upscale > EVAL_MAX_S)
+      return fail(LRP_ERR_INVALID, "need 1 <= g <= %d and 1 <= g * upscale <= %d", EVAL_MAX_G, EVAL_MAX_S);
+    if (!(sigma > 0.0) || sigma > 1e4) return fail(LRP_ERR_INVALID, "sigma must be in (0, 1e4]");
+    return eval_expand_matrix(g, upscale, sigma, M_host);
+  });
+}
+
+int lrp_eval_relevance_maps(const void* R_img_dev, void* maps_dev, int32_t fp64, int32_t n, int32_t npix, int32_t C,
+                            int32_t sign, void* stream) {
+  return guarded([&]() -> int {
+    if (!R_img_dev || !maps_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n < 1 || npix < 1 || C < 1) return fail(LRP_ERR_INVALID, "n, npix, C must be positive");
+    if (sign != 1 && sign != -1) return fail(LRP_ERR_INVALID, "sign must be +1 or -1");
+    if (fp64 != 0 && fp64 != 1) return fail(LRP_ERR_INVALID, "fp64 must be 0 or 1");
+    if (fp64)
+      hipLaunchKernelGGL(eval_relevance_map_kernel<double>, dim3(n), dim3(256), 0, S(stream), (const double*)R_img_dev,
+                         (double*)maps_dev, npix, C, (double)sign);
+    else
+      hipLaunchKernelGGL(eval_relevance_map_kernel<float>, dim3(n), dim3(256), 0, S(stream), (const float*)R_img_dev,
+                         (float*)maps_dev, npix, C, (float)sign);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_eval_attention_maps(const float* att_dev, const double* M_dev, double* maps_dev, int32_t n, int32_t g, int32_t upscale,
+                            void* stream) {
+  return guarded([&]() -> int {
+    if (!att_dev || !M_dev || !maps_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n < 1) return fail(LRP_ERR_INVALID, "n must be positive");
+    if (g < 1 || g > EVAL_MAX_G || upscale < 1 || g * upscale > EVAL_MAX_S)
+      return fail(LRP_ERR_INVALID, "need 1 <= g <= %d and 1 <= g * upscale <= %d", EVAL_MAX_G, EVAL_MAX_S);
+    const int Sd = g * upscale;
+    const size_t lds = (size_t)(g * g + g * Sd) * sizeof(double);
+    hipLaunchKernelGGL(eval_attention_map_kernel, dim3(n), dim3(256), lds, S(stream), att_dev, M_dev, maps_dev, g, Sd);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_eval_box_scores(const void* maps_dev, int32_t fp64, int32_t n, int32_t h, int32_t w, const int32_t* boxes_dev,
+                        const double* thr_dev, int32_t nb, int32_t K, double* scores_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (!maps_dev || !boxes_dev || !thr_dev || !scores_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n < 1 || h < 1 || w < 1 || nb < 1) return fail(LRP_ERR_INVALID, "n, h, w, nb must be positive");
+    if (K < 1 || K > EVAL_MAX_K) return fail(LRP_ERR_INVALID, "need 1 <= K <= %d thresholds", EVAL_MAX_K);
+    if (fp64 != 0 && fp64 != 1) return fail(LRP_ERR_INVALID, "fp64 must be 0 or 1");
+    if (fp64)
+      hipLaunchKernelGGL(eval_box_score_kernel<double>, dim3(nb), dim3(256), 0, S(stream), (const double*)maps_dev, n, h, w,
+                         boxes_dev, thr_dev, K, scores_dev);
+    else
+      hipLaunchKernelGGL(eval_box_score_kernel<float>, dim3(nb), dim3(256), 0, S(stream), (const float*)maps_dev, n, h, w,
+                         boxes_dev, thr_dev, K, scores_dev);
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   });

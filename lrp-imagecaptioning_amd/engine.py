@@ -654,3 +654,66 @@ def heatmap_scores(R_img, mode):
     _capi.check(lib.lrp_heatmap_scores(C.c_void_p(R.data_ptr()), C.c_void_p(out.data_ptr()), n, R[0].numel() // C_, C_, m,
                                        _cur_stream(R.device)))
     return out
+
+
+# ---- bounding-box correctness evaluation (evaluate_bbox.py; csrc/eval_kernels.h, lrp_eval_*)
+def eval_relevance_maps(R_img, sign=-1):
+    """`project(mean(max(sign * postprocess(R, 'BGRtoRGB'), 0), -1))` of the evaluator (evaluate_bbox.py:59-86) on the
+    device: R_img (n, H, W, C) float32 or float64 tensor -> (n, H, W) maps of the same dtype, bit-identical to numpy."""
+    lib = _capi.load()
+    R = R_img.contiguous()
+    if R.dtype not in (torch.float32, torch.float64) or R.dim() != 4:
+        raise ValueError("expected an (n, H, W, C) float32 or float64 tensor")
+    n, Hh, Ww, Cc = R.shape
+    out = torch.empty((n, Hh, Ww), dtype=R.dtype, device=R.device)
+    _capi.check(lib.lrp_eval_relevance_maps(C.c_void_p(R.data_ptr()), C.c_void_p(out.data_ptr()), int(R.dtype == torch.float64),
+                                            n, Hh * Ww, Cc, int(sign), _cur_stream(R.device)))
+    return out
+
+
+def eval_expand_matrix(g, upscale, sigma=20.0):
+    """(g * upscale, g) float64 M with pyramid_expand(A, upscale, sigma) = M A M^T (host only)."""
+    lib = _capi.load()
+    M = np.empty((g * upscale, g), dtype=np.float64)
+    _capi.check(lib.lrp_eval_expand_matrix(int(g), int(upscale), float(sigma), M.ctypes.data_as(C.c_void_p)))
+    return M
+
+
+_EXPAND_CACHE = {}
+
+
+def eval_attention_maps(att, g, upscale, sigma=20.0):
+    """`project(pyramid_expand(att.reshape(g, g), upscale, sigma))` (evaluate_bbox.py:75-84) on the device:
+    att (n, g * g) float32 tensor -> (n, S, S) float64, S = g * upscale."""
+    lib = _capi.load()
+    a = att.contiguous()
+    if a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != g * g:
+        raise ValueError("expected an (n, g * g) float32 tensor")
+    key = (str(a.device), int(g), int(upscale), float(sigma))
+    if key not in _EXPAND_CACHE:
+        _EXPAND_CACHE[key] = torch.as_tensor(eval_expand_matrix(g, upscale, sigma)).to(a.device)
+    S = g * upscale
+    out = torch.empty((a.shape[0], S, S), dtype=torch.float64, device=a.device)
+    _capi.check(lib.lrp_eval_attention_maps(C.c_void_p(a.data_ptr()), C.c_void_p(_EXPAND_CACHE[key].data_ptr()),
+                                            C.c_void_p(out.data_ptr()), a.shape[0], int(g), int(upscale), _cur_stream(a.device)))
+    return out
+
+
+def eval_box_scores(maps, boxes, thr):
+    """Box scores of evaluate_bbox.py:191-208 on the device: maps (n, h, w) float32 / float64 tensor, boxes (nb, 5) int32
+    (map, y0, y1, x0, x1), thr (nb, K) float64 (numpy or tensors) -> (nb, K) float64 tensor."""
+    lib = _capi.load()
+    m = maps.contiguous()
+    if m.dtype not in (torch.float32, torch.float64) or m.dim() != 3:
+        raise ValueError("expected an (n, h, w) float32 or float64 tensor")
+    b = torch.as_tensor(np.asarray(boxes, dtype=np.int32) if not torch.is_tensor(boxes) else boxes).to(m.device).contiguous()
+    t = torch.as_tensor(np.asarray(thr, dtype=np.float64) if not torch.is_tensor(thr) else thr).to(m.device).contiguous()
+    if b.dtype != torch.int32 or b.dim() != 2 or b.shape[1] != 5 or t.dtype != torch.float64 or t.dim() != 2 \
+            or t.shape[0] != b.shape[0]:
+        raise ValueError("boxes must be (nb, 5) int32 and thr (nb, K) float64")
+    nb, K = t.shape
+    out = torch.empty((nb, K), dtype=torch.float64, device=m.device)
+    _capi.check(lib.lrp_eval_box_scores(C.c_void_p(m.data_ptr()), int(m.dtype == torch.float64), m.shape[0], m.shape[1],
+                                        m.shape[2], C.c_void_p(b.data_ptr()), C.c_void_p(t.data_ptr()), nb, K,
+                                        C.c_void_p(out.data_ptr()), _cur_stream(m.device)))
+    return out
