@@ -293,7 +293,8 @@ __global__ __launch_bounds__(256) void dual_interleave_rows_kernel(const float* 
 // scaled by scale[image]) in ONE pass over (a_l, Z+_l): replaces maxpool2_kernel + pool_gate_kernel + split_h_scaled_kernel.
 // 8 channels per thread; a may alias g; xnext (fp32 pooled activations: the fine-tune step's kept input) may be null.
 // gc / gpos (may be null): the same gate in COMPACT form — per window and channel its one non-zero value and that value's
-// position p = 2 dy + dx — for the consumer of the compact pool interface (conv_igemm.h ConvArgs::up2_gc).
+// position p = 2 dy + dx — for the compact pool interface (conv_igemm.h ConvArgs::up2_src: its producer multiplies with gc,
+// its consumer reads gpos).
 __global__ __launch_bounds__(256) void pool_gate_split_kernel(const float* a, const float* __restrict__ z, float* g,
                                                               float* __restrict__ pairs, float* __restrict__ xnext,
                                                               const float* __restrict__ scale, int NB, int H, int W, int C,

@@ -39,9 +39,7 @@ struct Switches {
   int fwd_emit = 1;         // LRP_FWD_EMIT=0      forward: split / absmax / pool passes between the convs
   int fwd_il = 1;           // LRP_FWD_IL=0        dual forward matrix with stacked rows: separate gate pass (decided when lrp_set_weight packs)
   int img_fused = 1;        // LRP_IMG_FUSED=0     image layer as T GEMM + separate stencil kernel (VGG16 and the ResNet stem)
-  int up2_compact = 1;      // LRP_UP2_COMPACT=0   expanded pool interface between block2_conv1 and block1_conv2
-  int up2_gc = 1;           // LRP_UP2_GC=0        that interface with the full-resolution pool gate
-  int up2_breg_pairs = 1;   // LRP_UP2_BREG_PAIRS=0  block2_conv1 writes its plain fp32 product instead of pairs
+  int up2_compact = 1;      // LRP_UP2_COMPACT=0   every pooled boundary through the expanded tensor
   int img_fold = 1;         // LRP_IMG_FOLD=0      image layer as its own launch
   int pool_fused = 1;       // LRP_POOL_FUSED=0    forward: max-pool + gate + pooled pairs as a pass of their own behind the conv
   int sparse_pool = 0;      // LRP_SPARSE_POOL=1   pooled boundaries with >= 256 output columns on the 2:4-sparse matrix cores (conv_sparse.h); read by encode and explain
@@ -51,8 +49,7 @@ struct Switches {
     rd("LRP_CONV_HALO", conv_halo); rd("LRP_CONV_BREG", conv_breg); rd("LRP_CONV_SMALL", conv_small);
     rd("LRP_CONV_MID", conv_mid); rd("LRP_EPI_FAST", epi_fast); rd("LRP_UP2_PW", up2_pw); rd("LRP_TILE_ORDER", tile_order);
     rd("LRP_FWD_EMIT", fwd_emit); rd("LRP_FWD_IL", fwd_il); rd("LRP_IMG_FUSED", img_fused); rd("LRP_UP2_COMPACT", up2_compact);
-    rd("LRP_UP2_GC", up2_gc); rd("LRP_UP2_BREG_PAIRS", up2_breg_pairs); rd("LRP_IMG_FOLD", img_fold);
-    rd("LRP_SPARSE_POOL", sparse_pool); rd("LRP_POOL_FUSED", pool_fused);
+    rd("LRP_IMG_FOLD", img_fold); rd("LRP_SPARSE_POOL", sparse_pool); rd("LRP_POOL_FUSED", pool_fused);
   }
 };
 inline Switches& sw() {

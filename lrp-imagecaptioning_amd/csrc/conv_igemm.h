@@ -1,7 +1,7 @@
 // conv_igemm.h — MFMA implicit-GEMM 3x3/1x1 convolution for gfx950 with the LRP epilogues fused.  This one kernel
 // family carries >95 % of the FLOPs of the hot path:
-//   * encoder forward: activation chain (EPI_BIAS / EPI_BIAS_RELU, three-way split operands, TERMS 15 + 3) and
-//     denominators Z+ (EPI_BIAS, TERMS 7); exact-fp32 variants (EPI_FWD_DUAL)             — per image, cached
+//   * encoder forward: the dual conv a_l | Z+_l (EPI_FWD_DUAL: fp16 pairs, TERMS 7 / 23, or exact fp32), the activation
+//     chain (EPI_BIAS_RELU) and denominators Z+ (EPI_BIAS) in split-bf16 (TERMS 7)          — per image, cached
 //   * conv-LRP alpha1beta0 backward (EPI_MUL / EPI_MUL_UP2 / EPI_IMG_STENCIL)              — per token
 //     RR:274-322 restructured: S_{l-1} = up2?(convT(S_l, w_l+)) * G_{l-1}
 //   * every dense product of the decoder LRP / gradient paths (taps = 1, EPI_STORE / EPI_MUL)
@@ -202,24 +202,17 @@ struct ConvArgs {
   // from that image, so a scale per image is as legal as one per call, and the result for an image no longer depends on
   // which other images share its batch.
   int scale_per_img, img_rows, n_imgs;
-  // Compact pool interface (PREC_BF16X3; first form: the weights-in-registers kernel, Cin <= 64, fields up2_src / up2_gate /
-  // up2_gc; general form: every halo kernel through up2_pairs below): the relevance entering this layer came
-  // through a 2x2 max-pool, i.e. S_in[n][y][x][c] = P[n][y/2][x/2][c] * G_up[img(n)][y][x][c] with exactly one non-zero per
-  // window and channel.  Instead of reading that 4x-expanded, 75 %-zero tensor (which its producer would have had to write),
-  // the tile's resident image is BUILT from P (fp32, pooled resolution, written by the producer with gate_none) and the
-  // pool gate of this layer's output (fp32 per image, shared by an image's tokens in L2): `in` is then unused.
-  const float* up2_src;        // P  [NB][H/2][W/2][Cin] fp32
-  const float* up2_gate;       // G_up [images][H][W][Cin] fp32
-  int gate_none;               // EPI_MUL: out = acc (no gate: the consumer applies it, see up2_src)
-  // The pool gate in compact form as well (per-token tiles, ConvArgs::tpt > 0): gc [images][H/2][W/2][Cin] = the window's one
-  // non-zero gate value, gpos (same shape, bytes) = its position 2 dy + dx.  The prologue then walks WINDOWS instead of pixels:
-  // P, gc and gpos once per window and channel group (a quarter of the loads of the full-resolution gate, which every pixel
-  // item fetched together with the same P again) and writes the product to the one position that has it, zeros to the others.
-  const float* up2_gc;
-  const unsigned char* up2_gpos;
-  // up2_pairs = 1 (pipelined halo kernels): up2_src holds S_c = acc x compact gate at pooled resolution as bf16 pairs (its
-  // producer ran EPI_MUL with the COMPACT gate as its gate): the consumer needs only the position bytes
-  int up2_pairs;
+  // Compact pool interface (PREC_BF16X3, EPI_MUL / EPI_MUL_UP2 on the halo kernels: the folded weights-in-registers launch and
+  // the pipelined 128 x 128 / 256 x 256 tiles): the relevance entering this layer came through a 2x2 max-pool, i.e.
+  // S_in[n][y][x][c] = S_c[n][y/2][x/2][c] at the window's arg-max position and 0 at the three others.  Instead of reading that
+  // 4x-expanded, 75 %-zero tensor (which its producer would have had to write), the producer runs EPI_MUL with this layer's
+  // COMPACT pool gate and writes S_c = acc x gate at pooled resolution as bf16 pairs, and the tile builds its resident image
+  // from S_c and the position bytes (2 dy + dx per window and channel, per image: shared by an image's tokens in L2): the
+  // value where the position matches, zeros elsewhere.  `in` is then unused.
+  const float* up2_src;        // S_c [NB][H/2][W/2][Cin] split8 bf16 pairs
+  int gate_none;               // EPI_MUL: out = acc, no gate (ResNet gradient walk: a unit without a ReLU mask in front)
+  const unsigned char* up2_gpos;   // [images][H/2][W/2][Cin] bytes
+  int up2_pairs;               // must be 1 with up2_src: pairs are the only form the loaders read (conv_launch_epi refuses others)
   // Image layer folded into the epilogue of the layer above it (weights-in-registers kernel, PREC_BF16X3, N = 64, EPI_MUL):
   // S_1 = acc x gate never goes to memory.  The tile turns it into bf16 pairs in LDS, multiplies it with the tap-expanded
   // 64 -> 54 matrix `img_w` (the image layer's T = S_1 . W, cnn_kernels.h) and applies the 9-tap shift-and-add for the
@@ -277,12 +270,10 @@ constexpr int conv_halo_rows(int BM) { return BM == 256 ? 352 : 192; }   // x 12
 // (tap, chunk) are 4 coalesced 16 B loads per lane from a fragment-major copy of the packed weights (wpk_frag,
 // L1/L2 resident: 8 KB per tap), prefetched one tap ahead in registers.  The main loop then has NO barrier per tap —
 // only one per channel group — which is what the 12-MFMA-per-tap waves of the N = 64 tiles could not amortise.
-// TERMS (bf16x3 operand format only): which of the four partial products of (ah + al)(bh + bl) are issued —
-// bit 0: al*bh, bit 1: ah*bl, bit 2: ah*bh, bit 3: al*bl.  7 = the split-bf16 product of the reverse walk.  The
-// exact forward uses two passes over THREE-way split operands x = h + m + l (24 mantissa bits):
-//   pass A  (h|m) x (h|m), TERMS 15: hh + hm + mh + mm      pass B  (h|l) x (h|l), TERMS 3: hl + lh
-// = every partial product down to 2^-16 of the leading one, i.e. an fp32-grade product in 6 bf16 MFMAs of 32 cycles
-// per 16 k (192) instead of 8 fp32 MFMAs of 64 (512).
+// TERMS (split operands): which partial products of (ah + al)(bh + bl) are issued — bit 0: al*bh, bit 1: ah*bl, bit 2: ah*bh
+// (al*bl never).  7 = all three: every split launch but the PREC_F16X2 forms below.  PREC_F16X2 only: 5 = bit 1 off, the
+// weights' lo half is not read (two MFMAs); bit 4 (23 = 7 | 16, interleaved dual forward) = the same for the odd column
+// tiles only (Z+).  conv_launch instantiates 7 for PREC_BF16X3 and 7, 5, 23 for PREC_F16X2.
 // NS (plain staging only: !HALO, !BREG): LDS stages of the k pipeline.  2 = chunk kc+2 is launched at the barrier of iteration kc
 // and must have landed one iteration later — fine when an iteration holds 24-48 MFMAs per wave, but the 64 x 64 tiles of the
 // small-grid launches (6 MFMAs per wave and iteration) then run at one L2 / HBM round trip per k-step [MI355X, one image:
@@ -509,12 +500,9 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
   // chunks (256 k) the running block is folded into `tot` and restarted: chains of 256 + K/256.
   // (bf16x3: one MFMA already folds 16 k internally and the chain is K/16 long — no second level.)
   constexpr int FLUSH = 8;
-  // (the four-term pass of the exact forward product rounds its accumulator 4 x K/16 times: blocked as well — measured
-  //  feature error of VGG16 2.3e-6 without)
-  // (and the fp16-pair forward, whose three-term product is fp32-grade: without the second level its accumulator's
-  //  3 x K/16 roundings would be the largest error left)
-  constexpr bool BLOCKED = PREC == PREC_FP32 || TERMS == 15 ||
-                           (PREC == PREC_F16X2 && (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_FWD_DUAL));
+  // (the fp16-pair forward, whose three-term product is fp32-grade, is blocked as well: without the second level its
+  //  accumulator's 3 x K/16 roundings would be the largest error left)
+  constexpr bool BLOCKED = PREC == PREC_FP32 || (PREC == PREC_F16X2 && (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_FWD_DUAL));
   f32x16 acc[TM][TN], tot[BLOCKED ? TM : 1][BLOCKED ? TN : 1];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -606,9 +594,9 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
   };
   [[maybe_unused]] PwItem pwi{};
   if constexpr (BREG) {
-    if (PREC == PREC_BF16X3 && a.up2_src && (a.up2_gc || a.up2_pairs) && a.up2_gpos && a.tpt > 0) {
-      // compact pool interface, compact gate: item = (window of the resident image, 8-channel group)
-      const bool pairs = a.up2_pairs != 0;
+    if (PREC == PREC_BF16X3 && a.up2_src) {
+      // compact pool interface (pairs of S_c, per-token tiles: the launcher checks): item = (window of the resident image,
+      // 8-channel group)
       const int Hp = a.H >> 1, Wp = a.W >> 1;
       const int h0 = Y0 - img0 * a.H;                      // the tile's first image row (tiles are per token)
       const int wy0 = (h0 - 1) >> 1, wx0 = (x0 - 1) >> 1;  // (arithmetic shifts: -1 >> 1 = -1, the window row / column outside the image)
@@ -617,10 +605,10 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
       const int ntok = img0 < a.NB ? img0 : a.NB - 1;
       const int img = a.row2img ? a.row2img[ntok] : ntok;
       const float inv_nwx = 1.0f / (float)nwx;
-      constexpr int UW = 2;                                // items in flight per thread (4 x 16 B + 8 B of loads each)
+      constexpr int UW = 2;                                // items in flight per thread (2 x 16 B + 8 B of loads each)
       typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
       for (int it0 = tid; it0 < items; it0 += NT * UW) {
-        f32x4 pv[UW][2], gv[UW][2] = {};
+        f32x4 pv[UW][2];
         u32x2_ qv[UW];
         int wyv[UW], wxv[UW], cgv[UW];
         bool okv[UW];
@@ -639,33 +627,14 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
           const size_t wo = ((size_t)wyc * Wp + wxc) * a.Cin + cgc * 8;
           const float* pp = a.up2_src + (size_t)ntok * Hp * Wp * a.Cin + wo;
           pv[u][0] = *reinterpret_cast<const f32x4*>(pp); pv[u][1] = *reinterpret_cast<const f32x4*>(pp + 4);
-          if (!pairs) {                                   // (block-uniform; pairs mode: up2_src already holds P x gate as [hi8 | lo8])
-            const float* gp = a.up2_gc + (size_t)img * Hp * Wp * a.Cin + wo;
-            gv[u][0] = *reinterpret_cast<const f32x4*>(gp); gv[u][1] = *reinterpret_cast<const f32x4*>(gp + 4);
-          }
           qv[u] = *reinterpret_cast<const u32x2_*>(a.up2_gpos + (size_t)img * Hp * Wp * a.Cin + wo);
         }
 #pragma unroll
         for (int u = 0; u < UW; ++u) {
           if (it0 + u * NT >= items) continue;
-          u32x4 hiw, low;
-          if (pairs) {
-            const u32x4 z4u = {0u, 0u, 0u, 0u};
-            hiw = okv[u] ? __builtin_bit_cast(u32x4, pv[u][0]) : z4u;
-            low = okv[u] ? __builtin_bit_cast(u32x4, pv[u][1]) : z4u;
-          } else {
-            float r[8];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { r[e] = pv[u][0][e] * gv[u][0][e]; r[4 + e] = pv[u][1][e] * gv[u][1][e]; }
-            bf16x8 hi, lo;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-              const float rq = okv[u] ? r[q] : 0.f;
-              hi[q] = (__bf16)rq;
-              lo[q] = (__bf16)(rq - (float)hi[q]);
-            }
-            hiw = __builtin_bit_cast(u32x4, hi); low = __builtin_bit_cast(u32x4, lo);
-          }
+          const u32x4 z4u = {0u, 0u, 0u, 0u};
+          const u32x4 hiw = okv[u] ? __builtin_bit_cast(u32x4, pv[u][0]) : z4u;   // S_c as [hi8 | lo8]
+          const u32x4 low = okv[u] ? __builtin_bit_cast(u32x4, pv[u][1]) : z4u;
 #pragma unroll
           for (int j = 0; j < 4; ++j) {                    // the window's four pixels: position j = 2 dy + dx
             const int hy = 2 * wyv[u] + (j >> 1) - (h0 - 1), hx = 2 * wxv[u] + (j & 1) - (x0 - 1);
@@ -685,58 +654,6 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
             *reinterpret_cast<u32x4*>(smem + dst) = mh;
             *reinterpret_cast<u32x4*>(smem + (dst ^ 4)) = ml;
           }
-        }
-      }
-    } else if (PREC == PREC_BF16X3 && a.up2_src) {
-      // compact pool interface: resident image = P (pooled resolution) x pool gate, built here through registers.
-      // item = (LDS row, 8-channel group of the 64 channels); chunk cc = group / 4 goes to LDS buffer cc.
-      const int Hp = a.H >> 1, Wp = a.W >> 1;
-      const int items = a.hrows * HALO_PITCH * 8;
-      const int ri0 = a.row2img ? a.row2img[img0 < a.NB ? img0 : a.NB - 1] : img0;
-      const int ri1 = a.row2img ? a.row2img[img0 + 1 < a.NB ? img0 + 1 : a.NB - 1] : img0 + 1;
-      constexpr int UB = 6;                              // items in flight per thread (4 x 16 B loads each): one round for the 128-row tile
-      for (int it0 = tid; it0 < items; it0 += NT * UB) {
-        f32x4 pv[UB][2], gv[UB][2];
-        int dst[UB];
-        bool okv[UB];
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-          const int item = it0 + u * NT;
-          const int row = item >> 3, cg = item & 7, hy = row / HALO_PITCH, hx = row - hy * HALO_PITCH;
-          const int E = Y0 + img0 - 1 + hy;
-          int n, h;
-          divmod(E < 0 ? 0 : E, a.H + 1, inv_H1, n, h);
-          const int x = x0 - 1 + hx;
-          okv[u] = item < items && E >= 0 && h < a.H && n < a.NB && hx < a.tw + 2 && x >= 0 && x < a.W && cg * 8 < a.Cin;
-          const int swzu = ((hy * a.tw + hx - 1) >> 1) & 7;
-          // hi chunk of group g = cg & 3 is logical chunk 2g, lo chunk 2g + 1; physical = logical ^ swizzle (see set_tap)
-          dst[u] = (cg >> 2) * STAGE + row * LDS_STRIDE + (((2 * (cg & 3)) ^ swzu) << 2);
-          const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
-          pv[u][0] = pv[u][1] = gv[u][0] = gv[u][1] = z4;
-          if (okv[u]) {
-            const int rel = n - img0;
-            const int img = rel == 0 ? ri0 : rel == 1 ? ri1 : (a.row2img ? a.row2img[n] : n);
-            const float* pp = a.up2_src + (((size_t)n * Hp + (h >> 1)) * Wp + (x >> 1)) * a.Cin + cg * 8;
-            const float* gp = a.up2_gate + (((size_t)img * a.H + h) * a.W + x) * a.Cin + cg * 8;
-            pv[u][0] = *reinterpret_cast<const f32x4*>(pp); pv[u][1] = *reinterpret_cast<const f32x4*>(pp + 4);
-            gv[u][0] = *reinterpret_cast<const f32x4*>(gp); gv[u][1] = *reinterpret_cast<const f32x4*>(gp + 4);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < UB; ++u) {
-          if (it0 + u * NT >= items) continue;
-          float r[8];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { r[e] = pv[u][0][e] * gv[u][0][e]; r[4 + e] = pv[u][1][e] * gv[u][1][e]; }
-          bf16x8 hi, lo;
-#pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            hi[q] = (__bf16)r[q];
-            lo[q] = (__bf16)(r[q] - (float)hi[q]);
-          }
-          // lo sits in the logical chunk next to hi: physical index differs in bit 0 only (the swizzle XORs whole indices)
-          *reinterpret_cast<u32x4*>(smem + dst[u]) = __builtin_bit_cast(u32x4, hi);
-          *reinterpret_cast<u32x4*>(smem + (dst[u] ^ 4)) = __builtin_bit_cast(u32x4, lo);
         }
       }
     } else
@@ -880,7 +797,6 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
         for (int j = 0; j < TN; ++j) {
           const bf16x8 ah = __builtin_bit_cast(bf16x8, f.a[2 * i]), al = __builtin_bit_cast(bf16x8, f.a[2 * i + 1]);
           const bf16x8 bh = __builtin_bit_cast(bf16x8, f.b[2 * j]), bl = __builtin_bit_cast(bf16x8, f.b[2 * j + 1]);
-          if constexpr ((TERMS & 8) != 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bl, acc[i][j], 0, 0, 0);
           if constexpr ((TERMS & 1) != 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i][j], 0, 0, 0);    // small terms first
           if constexpr ((TERMS & 2) != 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i][j], 0, 0, 0);
           if constexpr ((TERMS & 4) != 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i][j], 0, 0, 0);
@@ -2091,8 +2007,9 @@ inline hipError_t conv_launch_epi(ConvArgs a, hipStream_t st) {
             a.m_tiles = a.NB * a.tpt * a.cols_t;
           }
           a.tile_map = conv_tile_order(a, st);
-          if (a.up2_src && (PREC != PREC_BF16X3 || a.CinP > 64 || (!a.up2_gate && !a.up2_pairs) || (a.H & 1) || (a.W & 1))) return hipErrorInvalidValue;
-          if (a.up2_pairs && (!a.up2_gpos || !a.img_part)) return hipErrorInvalidValue;   // (pairs need the window loader: per-token tiles = the folded launch)
+          // (the compact pool interface needs the window loader: per-token tiles = the folded launch)
+          if (a.up2_src && (PREC != PREC_BF16X3 || a.CinP > 64 || !a.up2_pairs || !a.up2_gpos || !a.img_part || (a.H & 1) || (a.W & 1)))
+            return hipErrorInvalidValue;
           hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 1, EPI, PREC, true, true, TERMS>), dim3(a.m_tiles), dim3(256), 0, st, a);
           return hipGetLastError();
         }

@@ -847,8 +847,8 @@ struct Encoder {
   //   used as the ReLU/arg-max mask, exact fp32.
   // layer_hook (fine-tune step): called with (li, dZ_li) — the gradient at the pre-activation of conv li, n x H x W x cout —
   // before that layer's backward-data conv is launched; the image layer itself is then skipped (R_img_dev may be null).
-  // The walks that read a pooled layer's gate at full resolution (EPI_MUL_UP2 / up2_gate: the gradient baselines, the fp32 and
-  // fast modes, LRP_UP2_COMPACT=0) after an encode whose fused pool epilogue left the compact form only
+  // The walks that read a pooled layer's gate at full resolution (EPI_MUL_UP2: the gradient baselines, the fp32 and fast modes,
+  // pooled boundaries without a pairs consumer, LRP_UP2_COMPACT=0) after an encode whose fused pool epilogue left the compact form only
   int full_gate(int li, hipStream_t st) {
     ConvLayer& L = layers[li];
     if (!L.pool_after || L.gfull_epoch == encode_epoch) return LRP_OK;
@@ -920,14 +920,15 @@ struct Encoder {
                          reinterpret_cast<f32x4*>(S), n, per4);
       LRP_HIP_CHECK(hipGetLastError());
     }
-    // Compact pool interface (conv_igemm.h ConvArgs::up2_src): where the consumer of a pooled boundary runs on the
-    // weights-in-registers kernel (VGG16: block2_conv1 -> pool -> block1_conv2, the 4.1 GB interface), the producer writes
-    // its plain fp32 product at POOLED resolution and the consumer builds S = P x gate itself: the 4x-expanded, 75 %-zero
-    // tensor is neither written nor read [MI355X, same box: block2_conv1 2.19 -> 1.48 ms (its store stream shrinks 4x, no gate
-    // loads), block1_conv2 3.87 -> 4.14 ms (its prologue now multiplies and splits in registers instead of a plain LDS-DMA),
-    // walk 26.3 -> 25.7-25.9 ms; heat-map parity unchanged].  LRP_UP2_COMPACT=0 disables.
+    // Compact pool interface (conv_igemm.h ConvArgs::up2_src): the producer of a pooled boundary (layer li, its consumer li - 1)
+    // multiplies with the consumer's COMPACT gate (one value per window and channel, at the producer's resolution) and writes
+    // S_c as bf16 pairs at POOLED resolution; the consumer builds its resident image from the pairs and the position bytes:
+    // the 4x-expanded, 75 %-zero tensor is neither written nor read.  Only two consumers can: the folded weights-in-registers
+    // launch (VGG16 block1_conv2: per-token tiles, its window loader) and the pipelined halo kernels (conv_takes_pw); both
+    // need a compact gate from this encode.  Every other pooled boundary takes EPI_MUL_UP2 (the expanded tensor; same fp32
+    // product, same pairs).  LRP_UP2_COMPACT=0 disables.
     const bool up2_on = sw().up2_compact != 0;
-    int compact_in = 0;                                  // S (the current layer's input) is in a compact form: 1 fp32 P (BREG consumer), 2 pairs of S_c (pipelined consumer)
+    bool pairs_in = false;                               // S (the current layer's input) is S_c as pairs at pooled resolution
     int fold_tw = 0, fold_th = 0;
     // Image layer folded into the epilogue of the layer above it (ConvArgs::img_part): S_1 — 4.1 GB written, 4.5 GB read at
     // the bench configuration — never goes to memory; per tile 160 positions x 6 partial sums do, and a streaming pass
@@ -936,6 +937,16 @@ struct Encoder {
     // batch invariance bit-exact].
     // LRP_IMG_FOLD=0 disables.
     const bool fold_on = sw().img_fold != 0;
+    // does the launch of layer li write pairs for its consumer li - 1 (see above)?
+    auto writes_pairs = [&](int li) {
+      const ConvLayer& P = layers[li - 1];
+      if (!P.pool_after || !up2_on || !split || f16 || walk != 0 || layer_hook || li < 2 || (P.cout & 7) || !P.Gc.p ||
+          P.gc_epoch != encode_epoch)
+        return false;
+      const bool cons_fold = li == 2 && fold_on && img_fused() && !layers[0].pool_after && P.cin == 64 && conv_cinp(P.cout) <= 64 &&
+                             layers[0].w_bwd_s.p != nullptr && conv_takes_breg(P.cin, P.H, P.W, P.w_bwd_frag.p != nullptr);
+      return cons_fold || conv_takes_pw(P.cin, n, P.H, P.W);
+    };
     for (int li = (int)layers.size() - 1; li >= 0; --li) {
       const ConvLayer& L = layers[li];
       if (layer_hook) {
@@ -985,7 +996,7 @@ struct Encoder {
           (void)conv_halo_geom(128, L.H, L.W, fold_tw, fold_th, hr_);
           ca.img_w = P.w_bwd_s.as<float>(); ca.img_part = Snext; ca.out = nullptr;
         }
-        if (compact_in == 2 && sw().sparse_pool && L.w_sp.p && L.idx_epoch == encode_epoch && !P.pool_after && split && !f16 && walk == 0 &&
+        if (pairs_in && sw().sparse_pool && L.w_sp.p && L.idx_epoch == encode_epoch && !P.pool_after && split && !f16 && walk == 0 &&
             !layer_hook && sp_scp.p) {
           // the pooled boundary on the 2:4-sparse matrix cores (conv_sparse.h): S_c re-laid chunk-major, then one launch per class
           const int Hp = L.H / 2, Wp = L.W / 2;
@@ -1003,41 +1014,17 @@ struct Encoder {
             pr.flop = 2.0 * (double)n * L.H * L.W * 9.0 * L.cout * L.cin;
             prof.push_back(pr);
           }
-          compact_in = 0;
+          pairs_in = false;
           float* t = S; S = Snext; Snext = t;
           continue;
         }
-        if (compact_in == 2 || compact_in == 3) {         // pairs of S_c at pooled resolution (pipelined kernels' loader / the folded BREG launch)
+        if (pairs_in) {                                   // (ca.in = S stays a valid pointer; it is not read)
           ca.up2_src = S; ca.up2_pairs = 1; ca.up2_gpos = L.Gpos.as<unsigned char>();
-          compact_in = 0;
-        } else if (compact_in) {                          // this layer reads the compact form its producer left
-          ca.up2_src = S; ca.up2_gate = L.G.as<float>();     // (ca.in = S stays a valid pointer; it is not read)
-          const bool gc_on = sw().up2_gc != 0;
-          if (gc_on && L.Gc.p && L.gc_epoch == encode_epoch) {   // ... with the gate in compact form too (per-token tiles only)
-            ca.up2_gc = L.Gc.as<float>(); ca.up2_gpos = L.Gpos.as<unsigned char>();
-          }
-          compact_in = 0;
+          pairs_in = false;
         }
-        // does THIS launch write the compact form?  Its consumer is layer li - 1 (N = P.cin, at 2x this resolution)
-        if (P.pool_after && up2_on && split && !f16 && walk == 0 && !layer_hook && li >= 2 && P.cin <= 64 && conv_cinp(P.cout) <= 64 &&
-            !(P.cout & 7) && conv_takes_breg(P.cin, P.H, P.W, P.w_bwd_frag.p != nullptr)) {
-          // pairs mode as below when the consumer will run the folded launch (per-token tiles: its window loader) and this
-          // encode left a compact gate; else the plain fp32 product and the consumer multiplies
-          const bool gc_on3 = sw().up2_gc != 0 && sw().up2_breg_pairs != 0;
-          const bool cons_fold = li == 2 && fold_on && img_fused() && !layers[0].pool_after && P.cin == 64 && layers[0].w_bwd_s.p != nullptr;
-          if (gc_on3 && cons_fold && P.Gc.p && P.gc_epoch == encode_epoch) {
-            epi = EPI_MUL; ca.aux = P.Gc.as<float>();
-            compact_in = 3;
-          } else {
-            epi = EPI_MUL; ca.gate_none = 1; ca.out_plain = 1;
-            compact_in = 1;
-          }
-        } else if (P.pool_after && up2_on && split && !f16 && walk == 0 && !layer_hook && li >= 2 && !(P.cout & 7) && P.Gc.p &&
-                   P.gc_epoch == encode_epoch && conv_takes_pw(P.cin, n, P.H, P.W)) {
-          // ... or by a pipelined halo kernel (ConvArgs::up2_pairs): this launch multiplies with the consumer's COMPACT gate
-          // (one value per window and channel, at this layer's resolution) and writes S_c as pairs at pooled resolution
+        if (writes_pairs(li)) {                            // THIS launch writes S_c for layer li - 1 (N = P.cin, at 2x this resolution)
           epi = EPI_MUL; ca.aux = P.Gc.as<float>();
-          compact_in = 2;
+          pairs_in = true;
         }
       }
       ProfileRec pr{};
@@ -1054,7 +1041,6 @@ struct Encoder {
       // overrides both.
       const int terms = f16 && two_term(li) ? 5 : 7;
       if (epi == EPI_MUL_UP2) LRP_TRY(full_gate(li - 1, st));
-      if (ca.up2_gate) LRP_TRY(full_gate(li, st));
       LRP_HIP_CHECK(conv_launch(epi, ca, st, run_prec, terms));
       if (profile) {
         (void)hipEventRecord(pr.e1, st);

@@ -3,8 +3,8 @@
 VERDICT r3: "~40 LRP_* switches, six swept once, none under a committed test — each untested switch is a dead or wrong code
 path waiting for a user."  Round 4 deleted 21 of them (their code paths with them where nothing else reaches those) and
 kept 17 as measurement knobs / fall-backs (+ round 4's LRP_POOL_FUSED and the opt-in LRP_SPARSE_POOL); three more went later
-(LRP_CONV_TILE, LRP_DEC_BATCHED, LRP_DEC_MFMA_FWD: their alternatives were code nothing else reached), which leaves 15 + the
-opt-in.  This file runs each of the kept ones — alone, at the setting that leaves the default path — through the engine at a size where the kernels of the benchmark configuration engage and compares every
+(LRP_CONV_TILE, LRP_DEC_BATCHED, LRP_DEC_MFMA_FWD: their alternatives were code nothing else reached), then the two that
+selected the fp32 forms of the compact pool interface, which leaves 13 + the opt-in.  This file runs each of the kept ones — alone, at the setting that leaves the default path — through the engine at a size where the kernels of the benchmark configuration engage and compares every
 heat-map with the default run:
 
   * VGG16 at full size, 8 images x 9 words = 72 heat-maps per call: block1 takes the weights-in-registers kernel with the
@@ -38,8 +38,6 @@ CASES = [
     ("LRP_UP2_PW", 0, 0.0, 0.0),
     ("LRP_TILE_ORDER", 0, 0.0, 0.0),
     ("LRP_UP2_COMPACT", 0, 0.0, 0.0),
-    ("LRP_UP2_GC", 0, 1e-6, 1e-6),          # (the consumer multiplies P x gate itself: one more rounding than acc x gate -> pairs)
-    ("LRP_UP2_BREG_PAIRS", 0, 0.0, 0.0),
     ("LRP_IMG_FOLD", 0, 1e-6, 1e-6),
     ("LRP_IMG_FUSED", 0, 1e-6, 1e-6),
     ("LRP_FWD_EMIT", 0, 2e-5, 2e-5),
