@@ -76,7 +76,11 @@ typedef struct lrp_config {
   int32_t conv_cout[LRP_MAX_CONV];
   int32_t conv_pool_after[LRP_MAX_CONV];
   char    conv_name[LRP_MAX_CONV][32];
-  int32_t L, D, H, E, V;        /* 196, 512, 512, 512, vocab  (config.py:14-15,36-40);  D, H multiples of 8 */
+  int32_t L, D, H, E, V;        /* 196, 512, 512, 512, vocab  (config.py:14-15,36-40);  D, H multiples of 8;
+                                   E >= 4, any width with 2E + 2H <= 2048, E != H included (LRP, forward replay and
+                                   caption generation read every 2E-strided row with scalar loads).  E == H is needed
+                                   by lrp_train_begin and by the ADAPTIVE lrp_decoder_gradient, E % 4 == 0 (and
+                                   D, H % 4) by every lrp_decoder_gradient */
   int32_t max_images;           /* capacity of the per-image caches                     */
   int32_t max_tokens;           /* capacity of one explain call (heat-maps)             */
   int32_t max_caption_len;      /* longest caption incl. EOS (config.py:34 -> 20+1)     */
@@ -201,7 +205,11 @@ int lrp_op_log_softmax_topk(const double* logits_dev, int32_t rows, int32_t V, i
  * (models/explainers.py:780-832, :1452-1532) for n (image, t) units at once: d_feat_dev (n, L, D) float32 =
  * the reference's hand-written BPTT of logit[caption[t-1]-1] w.r.t. the CNN features (its simplifications
  * included); r_words_dev (n, max_caption_len) float64 or NULL, columns >= t untouched zeros.
- * Errors as lrp_decoder_explain. */
+ * Errors as lrp_decoder_explain, and LRP_ERR_UNSUPPORTED (before anything is allocated or launched) when
+ *   - the decoder is LRP_DEC_ADAPTIVE and E != H: the reference's adaptive gradient class cannot run there
+ *     (explainers.py:798 sizes d_xt E + H wide, :823 stores a 2E-wide row into it: ValueError), so no reference
+ *     defines the result.  The grid-TD class runs at any E % 4 == 0 (goldens gridtd_grad_small_e16 / _e56 / _e20);
+ *   - H, E or D is not a multiple of 4. */
 int lrp_decoder_gradient(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const int32_t* t_host,
                          float* d_feat_dev, double* r_words_dev, void* stream);
 /* lrp_cnn_walk == <Analyzer>(image_model, neuron_selection_mode="replace").analyze([X, head]) for

@@ -347,6 +347,12 @@ int lrp_decoder_gradient(lrp_handle* h, int32_t n, const int32_t* img_idx_host, 
                          double* r_words_dev, void* stream) {
   return with_handle(h, [&]() -> int {
     if (!h || !img_idx_host || !t_host || !d_feat_dev) return fail(LRP_ERR_INVALID, "null argument");
+    // (checked before any staging, allocation or launch: nothing runs)
+    if (h->cfg.decoder == LRP_DEC_ADAPTIVE && h->cfg.E != h->cfg.H)
+      return fail(LRP_ERR_UNSUPPORTED, "the adaptive gradient baseline needs E == H (E=%d, H=%d): the reference's class cannot run there "
+                                       "(explainers.py:798 sizes d_xt E + H wide, :823 stores a 2E-wide row into it and raises), so "
+                                       "no reference defines the result",
+                  h->cfg.E, h->cfg.H);
     LRP_TRY(stage_indices(h, n, img_idx_host, t_host, true, S(stream)));
     int t_max = 0;
     for (int i = 0; i < n; ++i) t_max = t_host[i] > t_max ? t_host[i] : t_max;

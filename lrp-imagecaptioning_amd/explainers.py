@@ -343,7 +343,9 @@ class _GradientMixin(object):
         self._engine.set_precision("fp32")
 
     def _lstm_decoder_backward(self, t):
-        """E:780-832 / E:1452-1532 -> d_img_feature (1, sqrtL, sqrtL, D) float32; sets self.r_words (t,)."""
+        """E:780-832 / E:1452-1532 -> d_img_feature (1, sqrtL, sqrtL, D) float32; sets self.r_words (t,).
+        Adaptive decoder with embedding_dim != hidden_dim: NotImplementedError (the reference's class raises there,
+        E:798 / E:823; lrp_decoder_gradient returns LRP_ERR_UNSUPPORTED).  The grid-TD classes run at any E % 4 == 0."""
         self._check_t(t)
         d, rw = self._engine.decoder_gradient([0], [t])
         g = int(np.sqrt(self.L))

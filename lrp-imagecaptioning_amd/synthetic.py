@@ -19,7 +19,6 @@ def _n(rs, *shape, fan_in=None):
 
 def adaptive_weights(rs, L, D, H, E, V):
     """Adaptive-attention decoder (model.py:415-604)."""
-    assert E == H
     w = {}
     w["image_features_W"] = _n(rs, D, H, fan_in=D)
     w["image_features_b"] = _n(rs, H) * 0.1
@@ -75,10 +74,10 @@ def decoder_inputs(rs, L, D, V, T):
     return feat, cap
 
 
-def decoder_case(kind, seed, L, D, H, V, T):
-    """Everything a golden decoder case is built from, in fixture draw order."""
+def decoder_case(kind, seed, L, D, H, V, T, E=None):
+    """Everything a golden decoder case is built from, in fixture draw order (E=None: embedding width = H)."""
     rs = np.random.RandomState(seed)
-    w = (adaptive_weights if kind == "adaptive" else gridtd_weights)(rs, L, D, H, H, V)
+    w = (adaptive_weights if kind == "adaptive" else gridtd_weights)(rs, L, D, H, H if E is None else E, V)
     feat, cap = decoder_inputs(rs, L, D, V, T)
     return w, feat, cap
 

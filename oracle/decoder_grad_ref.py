@@ -54,6 +54,10 @@ class AdaptiveGradOracle(AdaptiveOracle):
     def backward(self, t):
         """E:780-832 -> (d_img_feature (1, sqrtL, sqrtL, D) float32; self.r_words (t,))."""
         w, H, E, L, D = self.w, self.H, self.E, self.L, self.D
+        if E != H:
+            # E:798 sizes d_xt (t, E + H) although a row of it is 2E wide: the store at E:823 raises for E != H, so the
+            # reference defines no adaptive gradient there (tests/golden/make_golden.py re-checks that it raises)
+            raise ValueError("could not broadcast input array from shape (%d,) into shape (%d,)" % (2 * E, E + H))
         k = self.caption[t - 1] - 1
         f32 = lambda *s: np.zeros(s, dtype="float32")
         d_ht, d_ct = f32(t + 1, H), f32(t + 1, H)

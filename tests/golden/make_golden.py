@@ -149,9 +149,9 @@ GRIDTD_STATE = ["h1t", "c1t", "g1t", "i1t_act", "f1t_act", "h2t", "c2t", "g2t", 
                 "_global_image_feature_before_act_bm", "_image_features_proj_bm"]
 
 
-def run_case(E, kind, seed, L, D, H, V, T, store_weights=True, tokens=None, single_word=False):
-    E_ = H
-    w, feat, cap = decoder_case(kind, seed, L, D, H, V, T)
+def run_case(E, kind, seed, L, D, H, V, T, store_weights=True, tokens=None, single_word=False, E_=None):
+    E_ = H if E_ is None else E_
+    w, feat, cap = decoder_case(kind, seed, L, D, H, V, T, E=E_)
     o = (build_adaptive if kind == "adaptive" else build_gridtd)(E, w, feat, L, D, H, E_)
     o._forward_beam_search((None, None), cap)
     out = {"kind": kind, "seed": seed, "dims": np.array([L, D, H, E_, V, T]),
@@ -187,11 +187,11 @@ def run_case(E, kind, seed, L, D, H, V, T, store_weights=True, tokens=None, sing
     return out
 
 
-def run_gradient_case(E, kind, seed, L, D, H, V, T, store_weights=True, tokens=None):
+def run_gradient_case(E, kind, seed, L, D, H, V, T, store_weights=True, tokens=None, E_=None):
     """The hand-written BPTT of the gradient baselines (E:780-832 adaptive, E:1452-1532 grid-TD) on the same
     seeded inputs: d(logit_k)/d(image features) per token and the per-word sums r_words."""
-    E_ = H
-    w, feat, cap = decoder_case(kind, seed, L, D, H, V, T)
+    E_ = H if E_ is None else E_
+    w, feat, cap = decoder_case(kind, seed, L, D, H, V, T, E=E_)
     if kind == "adaptive":
         o = build_adaptive(E, w, feat, L, D, H, E_)
         o.__class__ = E.ExplainImgCaptioningAdaptiveAttentionGradient
@@ -218,6 +218,31 @@ def run_gradient_case(E, kind, seed, L, D, H, V, T, store_weights=True, tokens=N
         rel = o._explain_sentence()                   # E:834-839 / E:1534-1539
         assert all(np.array_equal(a, b) for a, b in zip(rel, gs))
     return out
+
+
+# Embedding width != LSTM width: (L, D, H, E, V, T) and the seed per decoder kind.  The seeds are the first ones the
+# conditioning check of tests/test_gpu_decoder_geometry.py (`admit`) lets through.
+E_NE_H = {"e16": (9, 24, 32, 16, 23, 4), "e56": (25, 40, 24, 56, 31, 5), "e20": (49, 72, 40, 20, 17, 3)}
+E_NE_H_SEED = {("adaptive", "e16"): 0, ("adaptive", "e56"): 1, ("adaptive", "e20"): 0,
+               ("gridtd", "e16"): 0, ("gridtd", "e56"): 0, ("gridtd", "e20"): 0}
+
+
+def check_adaptive_gradient_refuses(E):
+    """The reference's ADAPTIVE gradient class cannot run at E != H: E:798 sizes d_xt (t, E + H) while a row of
+    lstm_Wi^T products is 2E wide, so E:823 raises `ValueError: could not broadcast input array`.  Tried here for
+    every E != H geometry so that the statement stays checked whenever the goldens are regenerated; there is
+    therefore no adaptive_grad_small_e*.npz, and the engine and the oracle refuse the case as well."""
+    for tag, (L, D, H, E_, V, T) in sorted(E_NE_H.items()):
+        w, feat, cap = decoder_case("adaptive", E_NE_H_SEED[("adaptive", tag)], L, D, H, V, T, E=E_)
+        o = build_adaptive(E, w, feat, L, D, H, E_)
+        o.__class__ = E.ExplainImgCaptioningAdaptiveAttentionGradient
+        o._forward_beam_search((None, None), cap)
+        try:
+            o._lstm_decoder_backward(1)
+        except ValueError as e:
+            print("adaptive gradient at %s (E=%d, H=%d): reference raises ValueError: %s" % (tag, E_, H, e))
+        else:
+            raise AssertionError("the reference's adaptive gradient ran at E=%d, H=%d" % (E_, H))
 
 
 def run_beam_case(E, seed, V, n_images, beam, max_len):
@@ -275,6 +300,9 @@ def main():
             ("adaptive_grad_full_s0", "adaptive", 0, 196, 512, 512, 2000, 10, dict(store_weights=False, tokens=[1, 10])),
             ("gridtd_grad_full_s0", "gridtd", 0, 196, 512, 512, 2000, 10, dict(store_weights=False, tokens=[1, 10])),
         ]
+        for tag, (L, D, H, E_, V, T) in sorted(E_NE_H.items()):
+            gcases.append(("gridtd_grad_small_" + tag, "gridtd", E_NE_H_SEED[("gridtd", tag)], L, D, H, V, T, dict(E_=E_)))
+        check_adaptive_gradient_refuses(E)
         for name, kind, seed, L, D, H, V, T, kw in gcases:
             out = run_gradient_case(E, kind, seed, L, D, H, V, T, **kw)
             if name.endswith("full_s0"):
@@ -304,6 +332,10 @@ def main():
         ("gridtd_full_s0", "gridtd", 0, 196, 512, 512, 2000, 10,
          dict(store_weights=False, tokens=[1, 10])),
     ]
+    for tag, (L, D, H, E_, V, T) in sorted(E_NE_H.items()):
+        cases.append(("adaptive_small_" + tag, "adaptive", E_NE_H_SEED[("adaptive", tag)], L, D, H, V, T,
+                      dict(single_word=True, E_=E_)))
+        cases.append(("gridtd_small_" + tag, "gridtd", E_NE_H_SEED[("gridtd", tag)], L, D, H, V, T, dict(E_=E_)))
     for name, kind, seed, L, D, H, V, T, kw in cases:
         out = run_case(E, kind, seed, L, D, H, V, T, **kw)
         if name.endswith("full_s0"):

@@ -10,7 +10,10 @@ from lrp_imagecaptioning_amd.synthetic import decoder_case
 from oracle.decoder_ref import AdaptiveOracle, GridTDOracle, linear_lrp, stabilize
 
 SMALL = ["adaptive_small_s0", "adaptive_small_s1", "adaptive_small_s2",
-         "gridtd_small_s0", "gridtd_small_s1", "gridtd_small_s2"]
+         "gridtd_small_s0", "gridtd_small_s1", "gridtd_small_s2",
+         # embedding width != LSTM width (E = 16 / 56 / 20 against H = 32 / 24 / 40): the reference's own code again
+         "adaptive_small_e16", "adaptive_small_e56", "adaptive_small_e20",
+         "gridtd_small_e16", "gridtd_small_e56", "gridtd_small_e20"]
 
 STATE_MAP_ADAPTIVE = {"ht": "ht", "ct": "ct", "gt": "gt", "it_act": "it_act", "ft_act": "ft_act",
                       "context": "context", "attention": "attention", "st": "st", "beta": "beta",
@@ -71,7 +74,8 @@ def test_explain_matches_reference(name):
     np.testing.assert_allclose(att, g["sentence_attention"], rtol=1e-6)
 
 
-@pytest.mark.parametrize("name", ["adaptive_small_s0", "adaptive_small_s1"])
+@pytest.mark.parametrize("name", ["adaptive_small_s0", "adaptive_small_s1", "adaptive_small_e16", "adaptive_small_e56",
+                                  "adaptive_small_e20"])
 def test_single_step_variant(name):
     g = load(name)
     _, o = build(g)
