@@ -107,7 +107,11 @@ int lrp_destroy(lrp_handle* h);
 
 /* Weight extraction (E:264-278, E:1000-1019; conv kernels = the image_model's
  * layers, E:29-30).  `data_host` is float32 in the Keras layout; the library
- * splits conv weights into w+ / w- (RR:256-260), packs and uploads them.
+ * copies the array into HBM and builds every operand copy there (conv weights
+ * split into w+ / w-, RR:256-260) with the packers of lrp_set_weight_dev —
+ * there is one packing route.  Synchronous: on return the array has been read
+ * and may be reused or freed.  An encoder weight invalidates the encode caches
+ * (lrp_encode_images must run again before an explain call).
  * Names: "<conv>_W","<conv>_b", "image_features_W/_b", "global_W/_b",
  * "embedding", "output_W/_b"; adaptive: "lstm_Wi","lstm_Wh","lstm_b","Wv","Wg",
  * "V","Wx","Wh","Ws"; grid-TD: "td_Wi","td_Wh","td_b","lang_Wi","lang_Wh",

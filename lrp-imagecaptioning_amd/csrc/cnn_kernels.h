@@ -124,8 +124,9 @@ __global__ __launch_bounds__(256) void split_copy_kernel(const float* __restrict
   }
 }
 
-// Device twins of the host weight packers (conv_igemm.h pack_conv_fwd / pack_conv_bwd / pack_frag64) for the fine-tune
-// step, whose weights change on the device every iteration.  dst [rows_total][taps * CP], zero padded.
+// The weight packers: HWIO kernel w[tap][ci][co] in HBM -> the B operand of conv_igemm.h, dst [rows_total][taps * CP], zero
+// padded.  Every route packs here: lrp_set_weight[_dev], the operator entries and the fine-tune step (whose weights change on
+// the device every iteration).
 //   bwd = 0: row = output channel, k = tap * CP + ci       (dual: rows [Cout, 2 Cout) hold w+ of row - Cout)
 //   bwd = 1: row = input channel,  k = tap' * CP + co with the taps flipped (transposed conv as a conv)
 __global__ __launch_bounds__(256) void pack_conv_dev_kernel(const float* __restrict__ w, float* __restrict__ dst, int bwd, int Cin,
@@ -471,7 +472,7 @@ __global__ __launch_bounds__(256) void top_divide_f16_kernel(const float* __rest
   }
 }
 
-// Device twin of the image-layer packers of Encoder::set_conv_weight (li == 0): w (3,3,3,cout) HWIO ->
+// The image layer's packer (Encoder::repack_conv_weight_from_device, li == 0): w (3,3,3,cout) HWIO ->
 //   fwd  [.][64]  rows [0,cout): w against both halves of the im2col row (x+ patch | x- patch) = a_1;
 //                 rows [cout,2cout): w+ | w- = Z_1 (RR:256-260)
 //   bwd  [.][Kb]  row t*6+c = w+[t][c][:], row t*6+3+c = w-[t][c][:]   (tap-expanded channel reduction, conv_igemm.h)
@@ -491,7 +492,8 @@ __global__ __launch_bounds__(256) void pack_image_layer_dev_kernel(const float* 
   bwd[(size_t)(t * 6 + 3 + c) * Kb + co] = vn;
   full[(size_t)(t * 6 + c) * Kb + co] = v;
 }
-// split8-packed [64][K] -> fragment-major copy for the weights-in-registers kernel (pack_frag64)
+// BREG operand: split8-packed weights [64 rows][K = 9 * CP] -> fragment-major copy for the weights-in-registers kernel,
+// [kc = chunk*9 + tap][step q][hi|lo][64 rows][4 dwords] (chunk c = 4 (q >> 1) + 2 hh + (q & 1) of the 128 B tap-chunk row)
 __global__ __launch_bounds__(256) void pack_frag64_dev_kernel(const float* __restrict__ src, float* __restrict__ dst, int CP) {
   const int K = 9 * CP, cpt = CP / 32;
   const size_t total = (size_t)cpt * 9 * 4 * 2 * 64;

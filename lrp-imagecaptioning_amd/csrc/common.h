@@ -115,7 +115,7 @@ struct DevBuf {
     if (e != hipSuccess) {
       p = nullptr;
       (void)hipGetLastError();                         // clear the sticky error: the next launch check must not report this one
-      return fail(LRP_ERR_NOMEM, "hipMalloc(%zu bytes) failed: %s", n, hipGetErrorString(e));
+      return fail(LRP_ERR_NOMEM, "device memory: hipMalloc(%zu bytes) failed: %s", n, hipGetErrorString(e));
     }
     bytes = n;
     if (total) *total += (int64_t)n;

@@ -2126,67 +2126,6 @@ inline hipError_t conv_launch_grad_mask(const ConvArgs& a, hipStream_t st) {
   return conv_launch_epi<EPI_MUL, PREC_FP32, 7, true>(a, st);
 }
 
-// ---- host-side weight packing (one-off at lrp_set_weight time)
-// forward:  wpk[n = co][k = tap*CinP + ci] = w[kh][kw][ci][co]
-inline void pack_conv_fwd(const float* w_hwio, int taps, int Cin, int Cout, int col0, int Npad, float* wpk) {
-  const int CinP = conv_cinp(Cin), K = taps * CinP;
-  (void)Npad;
-  for (int t = 0; t < taps; ++t)
-    for (int ci = 0; ci < Cin; ++ci)
-      for (int co = 0; co < Cout; ++co)
-        wpk[(size_t)(col0 + co) * K + t * CinP + ci] = w_hwio[((size_t)t * Cin + ci) * Cout + co];
-}
-// backward (transposed conv as a forward conv over S with flipped taps):
-//   wpk[n = ci][k = tap'*CoutP + co] = w[2-kh'][2-kw'][ci][co]
-inline void pack_conv_bwd(const float* w_hwio, int taps, int Cin, int Cout, int col0, float* wpk) {
-  const int CoutP = conv_cinp(Cout), K = taps * CoutP;
-  for (int t = 0; t < taps; ++t) {
-    const int tf = (taps == 9) ? 8 - t : 0;            // (2-kh')*3 + (2-kw') = 8 - t
-    for (int ci = 0; ci < Cin; ++ci)
-      for (int co = 0; co < Cout; ++co)
-        wpk[(size_t)(col0 + ci) * K + t * CoutP + co] = w_hwio[((size_t)tf * Cin + ci) * Cout + co];
-  }
-}
-
-// fp32 packed matrix [rows][K] (K % 8 == 0) -> split8 in place-compatible layout: per 8 k, 32 B = [hi8 | lo8]
-inline unsigned short f32_to_bf16_rne(float f) {
-  unsigned u;
-  memcpy(&u, &f, 4);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
-inline float bf16_to_f32(unsigned short h) {
-  unsigned u = (unsigned)h << 16;
-  float f;
-  memcpy(&f, &u, 4);
-  return f;
-}
-// BREG operand: split8-packed weights [64 rows][K = taps*CP] -> fragment-major [kc = chunk*9 + tap][step][hi|lo][lane half][64][4 dwords]
-inline void pack_frag64(const float* split8_pk, int taps, int CP, float* dst) {
-  const int K = taps * CP, cpt = CP / 32;
-  for (int cc = 0; cc < cpt; ++cc)
-    for (int t = 0; t < taps; ++t) {
-      const int kc = cc * taps + t;
-      for (int q = 0; q < 4; ++q)
-        for (int hh = 0; hh < 2; ++hh)
-          for (int n = 0; n < 64; ++n) {
-            const int c = 4 * (q >> 1) + 2 * hh + (q & 1);          // 16 B chunk of the 128 B tap-chunk row
-            memcpy(dst + ((((size_t)kc * 4 + q) * 2 + hh) * 64 + n) * 4, split8_pk + (size_t)n * K + t * CP + cc * 32 + c * 4, 16);
-          }
-    }
-}
-
-inline void pack_split8(const float* src, size_t n_floats, float* dst_as_float) {
-  unsigned short* d = reinterpret_cast<unsigned short*>(dst_as_float);
-  for (size_t g = 0; g < n_floats / 8; ++g)
-    for (int q = 0; q < 8; ++q) {
-      const float x = src[g * 8 + q];
-      const unsigned short hi = f32_to_bf16_rne(x);
-      d[g * 16 + q] = hi;
-      d[g * 16 + 8 + q] = f32_to_bf16_rne(x - bf16_to_f32(hi));
-    }
-}
-
 #endif  // LRP_CONV_KERNEL_ONLY
 
 }  // namespace lrp

@@ -27,10 +27,9 @@ struct StateBuf {
 
 struct Decoder {
   int kind = 0, L = 0, D = 0, H = 0, E = 0, V = 0, Tm = 0, B_max = 0, NT_max = 0, sos = 2, eos = 1;
-  std::map<std::string, std::vector<float>> raw;            // Keras-layout weights until finalize()
   std::map<std::string, std::vector<int64_t>> raw_shape;
-  // lrp_set_weight_dev: the Keras-layout matrices stay on the device (no host copy exists); once any weight arrived this
-  // way finalize() builds every operand copy with the device packers (repack_device) and uploads host-set stragglers
+  // the Keras-layout matrices as set, in HBM (lrp_set_weight copies the caller's host array there, lrp_set_weight_dev the
+  // caller's device array); finalize() builds every operand copy from them with the device packers (repack_device)
   std::map<std::string, DevBuf> raw_dev;
   bool finalized = false;
   // packed device weights
@@ -173,26 +172,19 @@ struct Decoder {
     *n_out = n;
     return LRP_OK;
   }
-  int set_weight(const std::string& nm, const float* data, int ndim, const int64_t* shape, int64_t*) {
-    size_t n = 0;
-    LRP_TRY(weight_set_common(nm, ndim, shape, &n));
-    raw[nm].assign(data, data + n);
-    raw_dev.erase(nm);                                 // (a device copy of the old value, if any, is stale)
-    return LRP_OK;
-  }
-  int set_weight_dev(const std::string& nm, const float* data_dev, int ndim, const int64_t* shape, int64_t* total, hipStream_t st) {
+  // `data`: host or device memory, as `kind` says
+  int set_weight(const std::string& nm, const float* data, hipMemcpyKind kind, int ndim, const int64_t* shape, int64_t* total,
+                 hipStream_t st) {
     size_t n = 0;
     LRP_TRY(weight_set_common(nm, ndim, shape, &n));
     DevBuf& d = raw_dev[nm];
     if (d.bytes != n * sizeof(float)) LRP_TRY(d.alloc(n * sizeof(float), total));
-    LRP_HIP_CHECK(hipMemcpyAsync(d.p, data_dev, n * sizeof(float), hipMemcpyDeviceToDevice, st));
-    raw.erase(nm);
+    LRP_HIP_CHECK(hipMemcpyAsync(d.p, data, n * sizeof(float), kind, st));
     return LRP_OK;
   }
 
   // ---- fine-tune step: the derived operand copies rebuilt in place from device weights (adaptive decoder; every
-  // buffer below was sized by a previous finalize(); padding stays zero).  Wd(name) = device pointer of the Keras-layout
-  // matrix.  Returns 1 when there is nothing to rebuild in place yet (the caller then takes the host path).
+  // buffer below was sized by finalize(); padding stays zero).  Wd(name) = device pointer of the Keras-layout matrix.
   static void tr2d(hipStream_t st, const float* src, int lds, int rows, int cols, float* dst, int ldd) {   // dst[c][r] = src[r][c]
     hipLaunchKernelGGL(dec_transpose_kernel, dim3((cols + 31) / 32, (rows + 31) / 32), dim3(32, 8), 0, st, src, lds, rows, cols, dst, ldd);
   }
@@ -200,9 +192,9 @@ struct Decoder {
     return hipMemcpy2DAsync(dst, (size_t)ldd * 4, src, (size_t)lds * 4, (size_t)cols * 4, rows, hipMemcpyDeviceToDevice, st);
   }
   int refresh_from_device(const std::function<const float*(const char*)>& Wd, hipStream_t st) {
-    if (!finalized) return 1;
+    int64_t dummy = 0;
+    LRP_TRY(finalize(&dummy, st));                     // (no forward has run yet: the buffers are made from the weights as set)
     if (!raw_stale) {                                  // last moment the set weights are current: build every lazily made pack
-      int64_t dummy = 0;
       LRP_TRY(bx_prepare(&dummy, st));
       if (!((H | E | D) & 3)) LRP_TRY(grad_prepare(&dummy, st));
     }
@@ -230,7 +222,7 @@ struct Decoder {
     LRP_HIP_CHECK(copy(Wg, td ? "W_ha" : "Wg", (size_t)H * H)); LRP_HIP_CHECK(copy(Ws, td ? "W_s" : "Ws", (size_t)H * H));
     LRP_HIP_CHECK(copy(vvec, td ? "W_a" : "V", H));
     // one LSTM: Wcat (Kd x N) = [[Wi | Wsx]; [Wh | Wsh]] (N = 5H with a sentinel, else 4H), bias row, the scan's GEMM
-    // operand (rows of the gate-g block, K padded) and the gradient path's pack_rows
+    // operand (rows of the gate-g block [Wi;Wh][:, 2H:3H], E:556-558, K padded) and the gradient path's row pack
     auto lstm = [&](const char* wi, const char* wh, const char* wsx, const char* wsh, const char* bias, int Kx, DevBuf& Wc,
                     DevBuf& bc, DevBuf* bxW, DevBuf* gW) -> int {
       const float *Wi = Wd(wi), *Wh = Wd(wh);
@@ -269,7 +261,7 @@ struct Decoder {
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   }
-  bool raw_stale = false;                                // host copies in `raw` are older than the device operands
+  bool raw_stale = false;                                // the copies in `raw_dev` are older than the operands (fine-tune step)
 
   int need(const char* nm, std::initializer_list<int64_t> shp) const {
     auto it = raw_shape.find(nm);
@@ -283,94 +275,6 @@ struct Decoder {
     return LRP_OK;
   }
 
-  static int upload(DevBuf& d, const std::vector<float>& v, int64_t* total) {
-    LRP_TRY(d.alloc(v.size() * sizeof(float), total));
-    LRP_HIP_CHECK(hipMemcpy(d.p, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-    return LRP_OK;
-  }
-
-  // weights shared by both decoders: image_features (dual 1-tap conv), attention projection of the
-  // features (Wv / W_va), global feature, embedding, output layer, transposed copies for the LRP tail
-  int finalize_common(const char* proj_name, int64_t* total) {
-    LRP_TRY(need("image_features_W", {D, H})); LRP_TRY(need("image_features_b", {H}));
-    LRP_TRY(need("global_W", {D, E})); LRP_TRY(need("global_b", {E}));
-    LRP_TRY(need("embedding", {V, E}));
-    LRP_TRY(need(proj_name, {H, H}));
-    LRP_TRY(need("output_W", {H, V})); LRP_TRY(need("output_b", {V}));
-    const std::vector<float>&Wif = raw["image_features_W"], &Wgl = raw["global_W"];
-    std::vector<float> pk;
-    {
-      const int Np = conv_npad(2 * H), K = conv_cinp(D);
-      pk.assign((size_t)Np * K, 0.f);
-      pack_conv_fwd(Wif.data(), 1, D, H, 0, Np, pk.data());
-      pack_conv_fwd(Wif.data(), 1, D, H, H, Np, pk.data());
-      LRP_TRY(upload(w_if_dual, pk, total));
-    }
-    {
-      const int Np = conv_npad(H), K = conv_cinp(H);
-      pk.assign((size_t)Np * K, 0.f);
-      pack_conv_fwd(raw[proj_name].data(), 1, H, H, 0, Np, pk.data());
-      LRP_TRY(upload(w_v, pk, total));
-    }
-    LRP_TRY(upload(zero_bias, std::vector<float>(std::max(H, E), 0.f), total));
-    LRP_TRY(upload(b_if, raw["image_features_b"], total));
-    LRP_TRY(upload(Wglob, Wgl, total));
-    LRP_TRY(upload(bglob, raw["global_b"], total));
-    LRP_TRY(upload(Wout, raw["output_W"], total));
-    LRP_TRY(upload(bout, raw["output_b"], total));
-    LRP_TRY(upload(emb, raw["embedding"], total));
-    pk.assign((size_t)E * D, 0.f);
-    for (int d = 0; d < D; ++d)
-      for (int e = 0; e < E; ++e) pk[(size_t)e * D + d] = Wgl[(size_t)d * E + e];
-    LRP_TRY(upload(WglobT, pk, total));
-    {  // W_if as the B operand of the MFMA tail GEMM: out[m][d] = sum_j A[m][j] * W_if[d][j]
-      pk.assign((size_t)H * D, 0.f);
-      for (int d = 0; d < D; ++d)
-        for (int j = 0; j < H; ++j) pk[(size_t)j * D + d] = Wif[(size_t)d * H + j];
-      const int Np = conv_npad(D), K = conv_cinp(H);
-      std::vector<float> g((size_t)Np * K, 0.f);
-      pack_conv_fwd(pk.data(), 1, H, D, 0, Np, g.data());          // pk [j][d] == "w[ci=j][co=d]"
-      LRP_TRY(upload(w_ifT_pk, g, total));
-    }
-    return LRP_OK;
-  }
-
-  // [x | h] . [[Wi | Wsent_x] ; [Wh | Wsent_h]] packed (Kx+H) x (4H [+H])
-  int pack_lstm(const std::vector<float>& Wi, const std::vector<float>& Wh, const std::vector<float>* Wsx,
-                const std::vector<float>* Wsh, const std::vector<float>& bias, int Kx, DevBuf& Wc, DevBuf& bc, int64_t* total) {
-    const int Kd = Kx + H, Nn = Wsx ? 5 * H : 4 * H;
-    std::vector<float> pk((size_t)Kd * Nn, 0.f);
-    for (int k = 0; k < Kd; ++k)
-      for (int n = 0; n < Nn; ++n) {
-        float v;
-        if (k < Kx) v = n < 4 * H ? Wi[(size_t)k * 4 * H + n] : (*Wsx)[(size_t)k * H + n - 4 * H];
-        else v = n < 4 * H ? Wh[(size_t)(k - Kx) * 4 * H + n] : (*Wsh)[(size_t)(k - Kx) * H + n - 4 * H];
-        pk[(size_t)k * Nn + n] = v;
-      }
-    LRP_TRY(upload(Wc, pk, total));
-    std::vector<float> bcv(Nn, 0.f);
-    std::copy(bias.begin(), bias.end(), bcv.begin());
-    LRP_TRY(upload(bc, bcv, total));
-    return LRP_OK;
-  }
-
-  int finalize_gridtd(int64_t* total) {
-    LRP_TRY(finalize_common("W_va", total));
-    const int K1 = H + 2 * E;
-    LRP_TRY(need("td_Wi", {K1, 4 * H})); LRP_TRY(need("td_Wh", {H, 4 * H})); LRP_TRY(need("td_b", {4 * H}));
-    LRP_TRY(need("lang_Wi", {2 * H, 4 * H})); LRP_TRY(need("lang_Wh", {H, 4 * H})); LRP_TRY(need("lang_b", {4 * H}));
-    LRP_TRY(need("W_ha", {H, H})); LRP_TRY(need("W_a", {H})); LRP_TRY(need("W_x", {K1, H}));
-    LRP_TRY(need("W_h", {H, H})); LRP_TRY(need("W_s", {H, H}));
-    LRP_TRY(pack_lstm(raw["td_Wi"], raw["td_Wh"], &raw["W_x"], &raw["W_h"], raw["td_b"], K1, Wcat, bcat, total));
-    LRP_TRY(pack_lstm(raw["lang_Wi"], raw["lang_Wh"], nullptr, nullptr, raw["lang_b"], 2 * H, Wcat2, bcat2, total));
-    LRP_TRY(upload(Wg, raw["W_ha"], total));
-    LRP_TRY(upload(Ws, raw["W_s"], total));
-    LRP_TRY(upload(vvec, raw["W_a"], total));
-    finalized = true;
-    return LRP_OK;
-  }
-
-  // lrp_set_weight_dev path: shapes checked like the host path, operand buffers allocated zeroed, then repack_device
   std::function<const float*(const char*)> raw_dev_lookup() {
     return [this](const char* nm) -> const float* { return raw_dev.at(nm).as<float>(); };
   }
@@ -379,7 +283,12 @@ struct Decoder {
     LRP_HIP_CHECK(hipMemsetAsync(d.p, 0, d.bytes, st));
     return LRP_OK;
   }
-  int finalize_device(int64_t* total, hipStream_t st) {
+  // shapes checked, operand buffers allocated zeroed, then repack_device fills them.  Shared by both decoders:
+  // image_features (dual 1-tap conv), attention projection of the features (Wv / W_va), global feature, embedding, output
+  // layer, transposed copies for the LRP tail; then the LSTM(s): [x | h_prev] . [[Wi | Wx] ; [Wh | Wh_sentinel]] -> 4H gate
+  // pre-activations + H sentinel gate
+  int finalize(int64_t* total, hipStream_t st = nullptr) {
+    if (finalized) return LRP_OK;
     const bool td = kind == LRP_DEC_GRIDTD;
     const int K1 = td ? H + 2 * E : 2 * E;              // input width of the (first) LSTM
     LRP_TRY(need("image_features_W", {D, H})); LRP_TRY(need("image_features_b", {H}));
@@ -394,12 +303,6 @@ struct Decoder {
       LRP_TRY(need("lstm_Wi", {K1, 4 * H})); LRP_TRY(need("lstm_Wh", {H, 4 * H})); LRP_TRY(need("lstm_b", {4 * H}));
       LRP_TRY(need("Wv", {H, H})); LRP_TRY(need("Wg", {H, H})); LRP_TRY(need("V", {H}));
       LRP_TRY(need("Wx", {K1, H})); LRP_TRY(need("Wh", {H, H})); LRP_TRY(need("Ws", {H, H}));
-    }
-    for (auto& kv : raw) {                             // weights that were set from the host: one upload each
-      if (raw_dev.count(kv.first)) continue;
-      DevBuf& d = raw_dev[kv.first];
-      LRP_TRY(d.alloc(kv.second.size() * sizeof(float), total));
-      LRP_HIP_CHECK(hipMemcpyAsync(d.p, kv.second.data(), kv.second.size() * sizeof(float), hipMemcpyHostToDevice, st));
     }
     const size_t KD = conv_cinp(D), KH = conv_cinp(H);
     LRP_TRY(zalloc(w_if_dual, (size_t)conv_npad(2 * H) * KD, total, st));
@@ -416,26 +319,9 @@ struct Decoder {
     finalized = true;
     return repack_device(raw_dev_lookup(), st);
   }
-  // (the scan / gradient-path packs in device mode: allocate zeroed, mark ready, let repack_device fill everything)
+  // (the scan / gradient-path packs: allocate zeroed, mark ready, let repack_device fill everything)
   int pack_alloc_device(DevBuf& d, int rows, int K, int64_t* total, hipStream_t st) {
     return zalloc(d, (size_t)conv_npad(rows) * conv_cinp(K), total, st);
-  }
-
-  int finalize(int64_t* total, hipStream_t st = nullptr) {
-    if (finalized) return LRP_OK;
-    if (!raw_dev.empty()) return finalize_device(total, st);
-    if (kind == LRP_DEC_GRIDTD) return finalize_gridtd(total);
-    LRP_TRY(finalize_common("Wv", total));
-    LRP_TRY(need("lstm_Wi", {2 * E, 4 * H})); LRP_TRY(need("lstm_Wh", {H, 4 * H})); LRP_TRY(need("lstm_b", {4 * H}));
-    LRP_TRY(need("Wg", {H, H})); LRP_TRY(need("V", {H}));
-    LRP_TRY(need("Wx", {2 * E, H})); LRP_TRY(need("Wh", {H, H})); LRP_TRY(need("Ws", {H, H}));
-    // [x | h_prev] . [[Wi | Wx] ; [Wh | Wh_sentinel]] -> 4H gate pre-activations + H sentinel gate
-    LRP_TRY(pack_lstm(raw["lstm_Wi"], raw["lstm_Wh"], &raw["Wx"], &raw["Wh"], raw["lstm_b"], 2 * E, Wcat, bcat, total));
-    LRP_TRY(upload(Wg, raw["Wg"], total));
-    LRP_TRY(upload(Ws, raw["Ws"], total));
-    LRP_TRY(upload(vvec, raw["V"], total));
-    finalized = true;
-    return LRP_OK;
   }
 
   // ks > 1: split-K into `ks` slabs of `slab` elements each (the consumer sums them)
@@ -731,49 +617,23 @@ struct Decoder {
 
   // ---- gradient baselines: _lstm_decoder_backward (E:780-832 adaptive, E:1452-1532 grid-TD), see gradient_kernels.h
   // B operand of a transposed-weight product on conv_igemm: rows = the Keras kernels (in_dim, K) stacked, K padded to 32
-  int pack_rows(const std::vector<std::pair<const char*, int>>& blocks, int K, DevBuf& dst, int64_t* total) {
-    int N = 0;
-    for (auto& b : blocks) N += b.second;
-    const int Kp = conv_cinp(K);
-    std::vector<float> pk((size_t)conv_npad(N) * Kp, 0.f);
-    int r0 = 0;
-    for (auto& b : blocks) {
-      const std::vector<float>& w = raw.at(b.first);
-      if (w.size() != (size_t)b.second * K) return fail(LRP_ERR_INVALID, "weight '%s' has the wrong size for the gradient path", b.first);
-      for (int r = 0; r < b.second; ++r) memcpy(&pk[(size_t)(r0 + r) * Kp], &w[(size_t)r * K], (size_t)K * sizeof(float));
-      r0 += b.second;
-    }
-    return upload(dst, pk, total);
-  }
   int grad_prepare(int64_t* total, hipStream_t st = nullptr) {
     if (grad_ready) return LRP_OK;
     if ((H & 3) || (E & 3) || (D & 3)) return fail(LRP_ERR_UNSUPPORTED, "gradient path: H, E, D must be multiples of 4");
     const size_t NT = NT_max;
-    const bool dev = !raw_dev.empty();                 // weights live on the device: allocate here, repack_device fills
-    if (kind == LRP_DEC_ADAPTIVE) {
-      if (dev) LRP_TRY(pack_alloc_device(gW1, H + 2 * E, 4 * H, total, st));
-      else LRP_TRY(pack_rows({{"lstm_Wh", H}, {"lstm_Wi", 2 * E}}, 4 * H, gW1, total));
+    if (kind == LRP_DEC_ADAPTIVE) {                    // (allocated here, repack_device fills)
+      LRP_TRY(pack_alloc_device(gW1, H + 2 * E, 4 * H, total, st));                  // rows [lstm_Wh ; lstm_Wi]
       LRP_TRY(g_out1.alloc(NT * (H + 2 * E) * 4, total));
     } else {
-      if (dev) {
-        LRP_TRY(pack_alloc_device(gW1, 2 * H + 2 * E, 4 * H, total, st));
-        LRP_TRY(pack_alloc_device(gW2, 3 * H, 4 * H, total, st));
-      } else {
-        LRP_TRY(pack_rows({{"td_Wh", H}, {"td_Wi", H + 2 * E}}, 4 * H, gW1, total));
-        LRP_TRY(pack_rows({{"lang_Wh", H}, {"lang_Wi", 2 * H}}, 4 * H, gW2, total));
-      }
+      LRP_TRY(pack_alloc_device(gW1, 2 * H + 2 * E, 4 * H, total, st));              // rows [td_Wh ; td_Wi]
+      LRP_TRY(pack_alloc_device(gW2, 3 * H, 4 * H, total, st));                      // rows [lang_Wh ; lang_Wi]
       LRP_TRY(g_out1.alloc(NT * (2 * H + 2 * E) * 4, total));
       LRP_TRY(g_out2.alloc(NT * 3 * H * 4, total));
       LRP_TRY(g_dc2.alloc(NT * H * 4, total));
       LRP_TRY(g_dctx.alloc(NT * Tm * H * 4, total));
     }
-    if (dev) {
-      LRP_TRY(pack_alloc_device(gWglob, D, E, total, st));
-      LRP_TRY(pack_alloc_device(gWif, D, H, total, st));
-    } else {
-      LRP_TRY(pack_rows({{"global_W", D}}, E, gWglob, total));
-      LRP_TRY(pack_rows({{"image_features_W", D}}, H, gWif, total));
-    }
+    LRP_TRY(pack_alloc_device(gWglob, D, E, total, st));
+    LRP_TRY(pack_alloc_device(gWif, D, H, total, st));
     LRP_TRY(g_seed.alloc(NT * H * 4, total));
     LRP_TRY(g_dc1.alloc(NT * H * 4, total));
     LRP_TRY(g_dg.alloc(NT * 4 * H * 4, total));
@@ -782,10 +642,10 @@ struct Decoder {
     LRP_TRY(g_davg.alloc(NT * D * 4, total));
     LRP_TRY(g_tailA.alloc(NT * L * H * 4, total));
     grad_ready = true;
-    if (dev && finalized) LRP_TRY(repack_device(raw_dev_lookup(), st));
+    if (finalized) LRP_TRY(repack_device(raw_dev_lookup(), st));
     return LRP_OK;
   }
-  // out[M][N] = in[M][K] . W^T   (W packed by pack_rows)
+  // out[M][N] = in[M][K] . W^T   (W: a row pack of grad_prepare)
   static int gemm_nt(const float* in, int M, int K, const DevBuf& W, int N, float* out, hipStream_t st) {
     ConvArgs c{};
     c.in = in; c.NB = M; c.H = 1; c.W = 1; c.Cin = K; c.CinP = conv_cinp(K); c.taps = 1; c.N = N;
@@ -864,23 +724,6 @@ struct Decoder {
     return LRP_OK;
   }
 
-  // B operand [rows][K] (fp32, padded like pack_rows) from a host matrix
-  int pack_matrix(const std::vector<float>& m, int N, int K, DevBuf& dst, int64_t* total) {
-    const int Kp = conv_cinp(K);
-    std::vector<float> pk((size_t)conv_npad(N) * Kp, 0.f);
-    for (int r = 0; r < N; ++r) memcpy(&pk[(size_t)r * Kp], &m[(size_t)r * K], (size_t)K * sizeof(float));
-    return upload(dst, pk, total);
-  }
-  // gate-g block of an LSTM, [Wi;Wh][:, 2H:3H] (E:556-558), as (Kx + H) rows x H
-  std::vector<float> gate_g_block(const char* wi, const char* wh, int Kx) const {
-    const std::vector<float>& Wi = raw.at(wi);
-    const std::vector<float>& Wh = raw.at(wh);
-    std::vector<float> g((size_t)(Kx + H) * H);
-    for (int d = 0; d < Kx + H; ++d)
-      for (int j = 0; j < H; ++j)
-        g[(size_t)d * H + j] = d < Kx ? Wi[(size_t)d * 4 * H + 2 * H + j] : Wh[(size_t)(d - Kx) * 4 * H + 2 * H + j];
-    return g;
-  }
   DevBuf sg_ws;                                        // K-split partials of the forward's matrix-core products
   static constexpr size_t SG_WS_FLOATS = (size_t)4 << 20;
   int need_sg_ws() {
@@ -890,19 +733,12 @@ struct Decoder {
   int bx_prepare(int64_t* total, hipStream_t st = nullptr) {
     if (bx_ready) return LRP_OK;
     const size_t NT = NT_max;
-    const bool dev = !raw_dev.empty();
-    if (kind == LRP_DEC_ADAPTIVE) {
-      if (dev) LRP_TRY(pack_alloc_device(bxWg1, 2 * E + H, H, total, st));
-      else LRP_TRY(pack_matrix(gate_g_block("lstm_Wi", "lstm_Wh", 2 * E), 2 * E + H, H, bxWg1, total));
+    if (kind == LRP_DEC_ADAPTIVE) {                    // gate-g blocks of the LSTMs: allocated here, repack_device fills
+      LRP_TRY(pack_alloc_device(bxWg1, 2 * E + H, H, total, st));
       LRP_TRY(bx_acc32.alloc(NT * (2 * E + H) * 4, total));
     } else {
-      if (dev) {
-        LRP_TRY(pack_alloc_device(bxWg1, 2 * H + 2 * E, H, total, st));
-        LRP_TRY(pack_alloc_device(bxWg2, 3 * H, H, total, st));
-      } else {
-        LRP_TRY(pack_matrix(gate_g_block("td_Wi", "td_Wh", H + 2 * E), 2 * H + 2 * E, H, bxWg1, total));
-        LRP_TRY(pack_matrix(gate_g_block("lang_Wi", "lang_Wh", 2 * H), 3 * H, H, bxWg2, total));
-      }
+      LRP_TRY(pack_alloc_device(bxWg1, 2 * H + 2 * E, H, total, st));
+      LRP_TRY(pack_alloc_device(bxWg2, 3 * H, H, total, st));
       LRP_TRY(bx_acc32.alloc(NT * (size_t)std::max(2 * H + 2 * E, 3 * H) * 4, total));
       for (DevBuf& d : bx_g) LRP_TRY(d.alloc(NT * H * 8, total));
     }
@@ -911,7 +747,7 @@ struct Decoder {
     LRP_TRY(bx_rglob.alloc(NT * E * 8, total));
     LRP_TRY(bx_q32.alloc(NT * H * 4, total));
     bx_ready = true;
-    if (dev && finalized) LRP_TRY(repack_device(raw_dev_lookup(), st));
+    if (finalized) LRP_TRY(repack_device(raw_dev_lookup(), st));
     return LRP_OK;
   }
 

@@ -5,7 +5,6 @@
 // sub-model input_1 -> block5_conv3 (E:29-32); rules RR:274-322, RA:470-480.
 #pragma once
 #include <algorithm>
-#include <cstring>
 #include <functional>
 #include <memory>
 #include <string>
@@ -55,8 +54,7 @@ struct ConvLayer {
   DevBuf w_sp, idxp;
   long idx_epoch = -1;
   bool sparse_ok() const { return pool_after && conv_sparse_supports(cin, cout, H / 2, W / 2) && !(H & 1) && !(W & 1); }
-  std::vector<float> raw_w, raw_b;   // host copies as set (HWIO / (cout,)): the fine-tune step's master weights start here
-  DevBuf raw_w_dev, raw_b_dev;       // the same when the weights arrived through lrp_set_weight_dev (no host copy exists then)
+  DevBuf raw_w_dev, raw_b_dev;       // the arrays as set (HWIO / (cout,)): the fine-tune step's master weights start here
   DevBuf fnorm;    // {largest absolute row sum of w, max|b|}: bound behind the scale of the pairs this layer emits (fwd_scale_kernel)
   bool norm_dirty = true;
   DevBuf Akeep;    // fine-tune step only: a_l of the layers whose output is the next conv's input (no pool after); the
@@ -239,154 +237,13 @@ struct Encoder {
     return -1;
   }
 
-  // "<name>_W": HWIO (3,3,cin,cout) -> split by sign (RR:256-260), pack, upload.
-  int set_conv_weight(int li, const float* w, int64_t* total) {
-    ConvLayer& L = layers[li];
-    const size_t nW = (size_t)9 * L.cin * L.cout;
-    if (w != L.raw_w.data()) L.raw_w.assign(w, w + nW);
-    L.raw_w_dev.release();
-    std::vector<float> wp(nW), wn(nW);
-    for (size_t i = 0; i < nW; ++i) { wp[i] = w[i] >= 0.f ? w[i] : 0.f; wn[i] = w[i] < 0.f ? w[i] : 0.f; }
-    std::vector<float> pk;
-    if (li == 0) {
-      // forward: 1-tap GEMM over the im2col matrix A1[m][64]; rows = [a_1 (cout) | Z_1 (cout)]
-      const int Np = conv_npad(2 * L.cout), K = 64;
-      pk.assign((size_t)Np * K, 0.f);
-      for (int k = 0; k < 27; ++k)
-        for (int co = 0; co < L.cout; ++co) {
-          const float v = w[(size_t)k * L.cout + co];
-          pk[(size_t)co * K + k] = v;                       // a_1 = (x+ + x-) . w
-          pk[(size_t)co * K + 32 + k] = v;
-          pk[(size_t)(L.cout + co) * K + k] = wp[(size_t)k * L.cout + co];        // Z_1 = x+.w+ + x-.w-
-          pk[(size_t)(L.cout + co) * K + 32 + k] = wn[(size_t)k * L.cout + co];
-        }
-      LRP_TRY(L.w_fwd.alloc(pk.size() * sizeof(float), total));
-      LRP_HIP_CHECK(hipMemcpy(L.w_fwd.p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-      if (!image_layer_interleaved(L)) L.w_fwd_il.release();   // (the layout of a layer's copies is decided HERE; encode() asks which copies exist)
-      if (image_layer_interleaved(L)) {
-        LRP_TRY(L.w_fwd_il.alloc(pk.size() * sizeof(float), total));
-        hipLaunchKernelGGL(dual_interleave_rows_kernel, dim3(stream_grid((size_t)2 * L.cout * K)), dim3(256), 0, nullptr, L.w_fwd.as<float>(),
-                           L.w_fwd_il.as<float>(), L.cout, K);
-        LRP_HIP_CHECK(hipGetLastError());
-        LRP_HIP_CHECK(hipStreamSynchronize(nullptr));
-        LRP_TRY(L.w_fwd_h.alloc(pk.size() * sizeof(float), total));
-        LRP_TRY(make_f16_operand(L.w_fwd_il.as<float>(), pk.size(), 0, 0, L.w_fwd_h, L.wds, total, nullptr));
-      }
-      // backward at the image: tap-expanded channel reduction, 54 = 9 taps x (3 with w+ | 3 with w-)
-      // columns, K = cout; the 3x3 shift-and-add happens in img_stencil_kernel.
-      const int Npb = conv_npad(IMG_T_COLS), Kb = conv_cinp(L.cout);
-      pk.assign((size_t)Npb * Kb, 0.f);
-      for (int t = 0; t < 9; ++t)
-        for (int c = 0; c < 3; ++c)
-          for (int co = 0; co < L.cout; ++co) {
-            pk[(size_t)(t * 6 + c) * Kb + co] = wp[((size_t)t * 3 + c) * L.cout + co];
-            pk[(size_t)(t * 6 + 3 + c) * Kb + co] = wn[((size_t)t * 3 + c) * L.cout + co];
-          }
-      LRP_TRY(L.w_bwd.alloc(pk.size() * sizeof(float), total));
-      LRP_HIP_CHECK(hipMemcpy(L.w_bwd.p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-      {
-        std::vector<float> sp(pk.size());
-        pack_split8(pk.data(), pk.size(), sp.data());
-        LRP_TRY(L.w_bwd_s.alloc(sp.size() * sizeof(float), total));
-        LRP_HIP_CHECK(hipMemcpy(L.w_bwd_s.p, sp.data(), sp.size() * sizeof(float), hipMemcpyHostToDevice));
-        LRP_TRY(L.w_bwd_h.alloc(sp.size() * sizeof(float), total));
-        LRP_TRY(make_f16_operand(L.w_bwd.as<float>(), sp.size(), 0, 0, L.w_bwd_h, L.wbs, total, nullptr));
-      }
-      // gradient baselines: the same tap expansion with the whole w in the "+" columns
-      pk.assign((size_t)Npb * Kb, 0.f);
-      for (int t = 0; t < 9; ++t)
-        for (int c = 0; c < 3; ++c)
-          for (int co = 0; co < L.cout; ++co) pk[(size_t)(t * 6 + c) * Kb + co] = w[((size_t)t * 3 + c) * L.cout + co];
-      LRP_TRY(L.w_bwd_full.alloc(pk.size() * sizeof(float), total));
-      LRP_HIP_CHECK(hipMemcpy(L.w_bwd_full.p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-    } else {
-      const int Np = conv_npad(2 * L.cout), K = 9 * conv_cinp(L.cin);
-      pk.assign((size_t)Np * K, 0.f);
-      pack_conv_fwd(w, 9, L.cin, L.cout, 0, Np, pk.data());
-      pack_conv_fwd(wp.data(), 9, L.cin, L.cout, L.cout, Np, pk.data());    // input >= 0: Z = x.w+ + b
-      LRP_TRY(L.w_fwd.alloc(pk.size() * sizeof(float), total));
-      LRP_HIP_CHECK(hipMemcpy(L.w_fwd.p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-      LRP_TRY(L.w_fwd_h.alloc(pk.size() * sizeof(float), total));
-      if (dual_interleaved(L)) {
-        std::vector<float> il(pk.size(), 0.f);            // rows in blocks of 32: [w | w+] of the same 32 channels
-        for (int c = 0; c < L.cout; ++c)
-          for (int half = 0; half < 2; ++half)
-            memcpy(&il[(size_t)(64 * (c / 32) + 32 * half + (c & 31)) * K], &pk[(size_t)(half * L.cout + c) * K], (size_t)K * sizeof(float));
-        LRP_TRY(L.w_fwd_il.alloc(il.size() * sizeof(float), total));
-        LRP_HIP_CHECK(hipMemcpy(L.w_fwd_il.p, il.data(), il.size() * sizeof(float), hipMemcpyHostToDevice));
-      } else {
-        L.w_fwd_il.release();
-      }
-      LRP_TRY(make_f16_operand(L.w_fwd_il.p ? L.w_fwd_il.as<float>() : L.w_fwd.as<float>(), pk.size(), 0, 0, L.w_fwd_h, L.wds,
-                               total, nullptr));
-      {  // mixed-precision forward: w (fp32) and w+ (split8) as separate N = cout matrices
-        const int Npa = conv_npad(L.cout);
-        std::vector<float> pa((size_t)Npa * K, 0.f), pz((size_t)Npa * K, 0.f), pzs((size_t)Npa * K);
-        pack_conv_fwd(w, 9, L.cin, L.cout, 0, Npa, pa.data());
-        pack_conv_fwd(wp.data(), 9, L.cin, L.cout, 0, Npa, pz.data());
-        pack_split8(pz.data(), pz.size(), pzs.data());
-        LRP_TRY(L.w_fwd_a.alloc(pa.size() * sizeof(float), total));
-        LRP_HIP_CHECK(hipMemcpy(L.w_fwd_a.p, pa.data(), pa.size() * sizeof(float), hipMemcpyHostToDevice));
-        LRP_TRY(L.w_fwd_zs.alloc(pzs.size() * sizeof(float), total));
-        LRP_HIP_CHECK(hipMemcpy(L.w_fwd_zs.p, pzs.data(), pzs.size() * sizeof(float), hipMemcpyHostToDevice));
-        pack_split8(pa.data(), pa.size(), pzs.data());
-        LRP_TRY(L.w_fwd_as.alloc(pzs.size() * sizeof(float), total));
-        LRP_HIP_CHECK(hipMemcpy(L.w_fwd_as.p, pzs.data(), pzs.size() * sizeof(float), hipMemcpyHostToDevice));
-      }
-      const int Npb = conv_npad(L.cin), Kb = 9 * conv_cinp(L.cout);
-      pk.assign((size_t)Npb * Kb, 0.f);
-      pack_conv_bwd(wp.data(), 9, L.cin, L.cout, 0, pk.data());
-      LRP_TRY(L.w_bwd.alloc(pk.size() * sizeof(float), total));
-      LRP_HIP_CHECK(hipMemcpy(L.w_bwd.p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-      {
-        std::vector<float> sp(pk.size());
-        pack_split8(pk.data(), pk.size(), sp.data());
-        LRP_TRY(L.w_bwd_s.alloc(sp.size() * sizeof(float), total));
-        LRP_HIP_CHECK(hipMemcpy(L.w_bwd_s.p, sp.data(), sp.size() * sizeof(float), hipMemcpyHostToDevice));
-        if (L.sparse_ok() && L.idxp.p) {
-          LRP_TRY(L.w_sp.alloc(conv_sparse_weight_floats(L.cin, L.cout) * sizeof(float), total));
-          LRP_HIP_CHECK(conv_sparse_pack(L.w_bwd.as<float>(), L.w_sp.as<float>(), L.cin, L.cout, nullptr));
-        }
-        if (Npb == 64) {
-          std::vector<float> fr((size_t)64 * Kb);
-          pack_frag64(sp.data(), 9, conv_cinp(L.cout), fr.data());
-          LRP_TRY(L.w_bwd_frag.alloc(fr.size() * sizeof(float), total));
-          LRP_HIP_CHECK(hipMemcpy(L.w_bwd_frag.p, fr.data(), fr.size() * sizeof(float), hipMemcpyHostToDevice));
-        }
-        // fp16 copies (PREC_F16X2), their scale and norm: derived on the device from the fp32 matrix just uploaded
-        LRP_TRY(L.w_bwd_h.alloc(sp.size() * sizeof(float), total));
-        if (Npb == 64) LRP_TRY(L.w_bwd_frag_h.alloc((size_t)64 * Kb * sizeof(float), total));
-        LRP_TRY(make_f16_operand(L.w_bwd.as<float>(), sp.size(), Npb, Kb, L.w_bwd_h, L.wbs, total, nullptr));
-        if (Npb == 64) {
-          hipLaunchKernelGGL(pack_frag64_dev_kernel, dim3(stream_grid((size_t)conv_cinp(L.cout) / 32 * 9 * 512)), dim3(256), 0, nullptr,
-                             L.w_bwd_h.as<float>(), L.w_bwd_frag_h.as<float>(), conv_cinp(L.cout));
-          LRP_HIP_CHECK(hipGetLastError());
-          LRP_HIP_CHECK(hipStreamSynchronize(nullptr));
-        }
-      }
-      pk.assign((size_t)Npb * Kb, 0.f);
-      pack_conv_bwd(w, 9, L.cin, L.cout, 0, pk.data());
-      LRP_TRY(L.w_bwd_full.alloc(pk.size() * sizeof(float), total));
-      LRP_HIP_CHECK(hipMemcpy(L.w_bwd_full.p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-      {
-        std::vector<float> sp(pk.size());
-        pack_split8(pk.data(), pk.size(), sp.data());
-        LRP_TRY(L.w_bwd_full_s.alloc(sp.size() * sizeof(float), total));
-        LRP_HIP_CHECK(hipMemcpy(L.w_bwd_full_s.p, sp.data(), sp.size() * sizeof(float), hipMemcpyHostToDevice));
-      }
-    }
-    L.have_w = true;
-    L.norm_dirty = true;
-    return LRP_OK;
-  }
-
-  // ---- operand copies built ON THE DEVICE from device weights: lrp_set_weight_dev (the multi-GPU start-up path: the
-  // bundle arrives over RCCL/xGMI and never visits the host) and the fine-tune step (weights change every iteration).
+  // ---- every operand copy is built ON THE DEVICE from the HWIO array in HBM: lrp_set_weight (the caller's host array is
+  // copied there first), lrp_set_weight_dev (the multi-GPU start-up path: the bundle arrives over RCCL/xGMI and never
+  // visits the host) and the fine-tune step (weights change every iteration).  "<name>_W" is split by sign (RR:256-260).
   DevBuf pack_tmp;                                     // scratch of the device packers (largest forward matrix)
   DevBuf f16_slots;                                    // ACT_MAX_SLOTS maxima while a weight matrix' fp16 copy is made
-  int make_f16_operand(const float* src, size_t n_floats, int rows, int K, DevBuf& dst, DevBuf& wsc, int64_t* total, hipStream_t st,
-                       bool sync = true) {
-    return lrp::make_f16_operand(f16_slots, src, n_floats, rows, K, dst, wsc, total, st, sync);      // f16_operand.h
+  int make_f16_operand(const float* src, size_t n_floats, int rows, int K, DevBuf& dst, DevBuf& wsc, int64_t* total, hipStream_t st) {
+    return lrp::make_f16_operand(f16_slots, src, n_floats, rows, K, dst, wsc, total, st);      // f16_operand.h
   }
   int alloc_conv_operands(int li, int64_t* total, hipStream_t st) {
     ConvLayer& L = layers[li];
@@ -421,7 +278,7 @@ struct Encoder {
     if (pack_tmp.bytes < nf * sizeof(float)) LRP_TRY(pack_tmp.alloc(nf * sizeof(float), total));
     return LRP_OK;
   }
-  // every operand copy of layer li from w_dev (HWIO, device); the buffers exist (set_conv_weight or alloc_conv_operands)
+  // every operand copy of layer li from w_dev (HWIO, device); the buffers exist (alloc_conv_operands)
   int repack_conv_weight_from_device(int li, const float* w_dev, float* tmp, hipStream_t st) {
     ConvLayer& L = layers[li];
     if (li == 0) {
@@ -432,10 +289,10 @@ struct Encoder {
       if (L.w_fwd_il.p) {
         hipLaunchKernelGGL(dual_interleave_rows_kernel, dim3(stream_grid((size_t)2 * L.cout * 64)), dim3(256), 0, st, L.w_fwd.as<float>(),
                            L.w_fwd_il.as<float>(), L.cout, 64);
-        LRP_TRY(make_f16_operand(L.w_fwd_il.as<float>(), (size_t)conv_npad(2 * L.cout) * 64, 0, 0, L.w_fwd_h, L.wds, nullptr, st, false));
+        LRP_TRY(make_f16_operand(L.w_fwd_il.as<float>(), (size_t)conv_npad(2 * L.cout) * 64, 0, 0, L.w_fwd_h, L.wds, nullptr, st));
       }
       hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(nb / 8)), dim3(256), 0, st, L.w_bwd.as<float>(), L.w_bwd_s.as<float>(), nb / 8);
-      LRP_TRY(make_f16_operand(L.w_bwd.as<float>(), nb, 0, 0, L.w_bwd_h, L.wbs, nullptr, st, false));
+      LRP_TRY(make_f16_operand(L.w_bwd.as<float>(), nb, 0, 0, L.w_bwd_h, L.wbs, nullptr, st));
       LRP_HIP_CHECK(hipGetLastError());
       return LRP_OK;
     }
@@ -453,7 +310,7 @@ struct Encoder {
     pack(L.w_fwd.as<float>(), 0, Np2, 1, 0);
     if (L.w_fwd_il.p) pack(L.w_fwd_il.as<float>(), 0, Np2, 2, 0);
     LRP_TRY(make_f16_operand(L.w_fwd_il.p ? L.w_fwd_il.as<float>() : L.w_fwd.as<float>(), (size_t)Np2 * 9 * CPi, 0, 0, L.w_fwd_h,
-                             L.wds, nullptr, st, false));
+                             L.wds, nullptr, st));
     pack(L.w_fwd_a.as<float>(), 0, Npa, 0, 0);
     pack(tmp, 0, Npa, 0, 1);
     split(tmp, L.w_fwd_zs.as<float>(), nf);
@@ -464,7 +321,7 @@ struct Encoder {
     if (L.w_bwd_frag.p)
       hipLaunchKernelGGL(pack_frag64_dev_kernel, dim3(stream_grid((size_t)CPo / 32 * 9 * 512)), dim3(256), 0, st, L.w_bwd_s.as<float>(),
                          L.w_bwd_frag.as<float>(), CPo);
-    LRP_TRY(make_f16_operand(L.w_bwd.as<float>(), nb, Npb, 9 * CPo, L.w_bwd_h, L.wbs, nullptr, st, false));
+    LRP_TRY(make_f16_operand(L.w_bwd.as<float>(), nb, Npb, 9 * CPo, L.w_bwd_h, L.wbs, nullptr, st));
     if (L.w_bwd_frag_h.p)
       hipLaunchKernelGGL(pack_frag64_dev_kernel, dim3(stream_grid((size_t)CPo / 32 * 9 * 512)), dim3(256), 0, st, L.w_bwd_h.as<float>(),
                          L.w_bwd_frag_h.as<float>(), CPo);
@@ -480,12 +337,12 @@ struct Encoder {
     LRP_TRY(repack_conv_weight_from_device(li, w_dev, tmp, st));
     L.norm_dirty = true;
     LRP_HIP_CHECK(hipMemcpyAsync(L.bias.p, b_dev, (size_t)L.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
-    L.raw_w.clear(); L.raw_b.clear();               // stale from here on (the trainer's master buffer is the truth)
-    L.raw_w_dev.release(); L.raw_b_dev.release();
+    L.raw_w_dev.release(); L.raw_b_dev.release();   // stale from here on (the trainer's master buffer is the truth)
     return LRP_OK;
   }
-  // lrp_set_weight_dev: "<name>_W" / "<name>_b" from device memory — D2D copy, then the device packers; no host round trip
-  int set_conv_weight_dev(int li, const float* w_dev, int64_t* total, hipStream_t st) {
+  // lrp_set_weight / lrp_set_weight_dev: "<name>_W" / "<name>_b" from host or device memory (`kind`) — one copy into
+  // HBM, then the device packers; nothing here waits for the stream
+  int set_conv_weight_dev(int li, const float* w, hipMemcpyKind kind, int64_t* total, hipStream_t st) {
     ConvLayer& L = layers[li];
     const size_t nW = (size_t)9 * L.cin * L.cout;
     if (gates_pending) {                               // the side stream may still read the operand copies we replace
@@ -493,8 +350,7 @@ struct Encoder {
       gates_pending = false;
     }
     if (!L.raw_w_dev.p) LRP_TRY(L.raw_w_dev.alloc(nW * sizeof(float), total));
-    LRP_HIP_CHECK(hipMemcpyAsync(L.raw_w_dev.p, w_dev, nW * sizeof(float), hipMemcpyDeviceToDevice, st));
-    L.raw_w.clear();
+    LRP_HIP_CHECK(hipMemcpyAsync(L.raw_w_dev.p, w, nW * sizeof(float), kind, st));
     LRP_TRY(alloc_conv_operands(li, total, st));
     LRP_TRY(repack_conv_weight_from_device(li, L.raw_w_dev.as<float>(), pack_tmp.as<float>(), st));
     L.have_w = true;
@@ -502,27 +358,15 @@ struct Encoder {
     encoded = 0;                                       // caches belong to the old weights
     return LRP_OK;
   }
-  int set_conv_bias_dev(int li, const float* b_dev, int64_t* total, hipStream_t st) {
+  int set_conv_bias_dev(int li, const float* b, hipMemcpyKind kind, int64_t* total, hipStream_t st) {
     ConvLayer& L = layers[li];
     if (!L.raw_b_dev.p) LRP_TRY(L.raw_b_dev.alloc((size_t)L.cout * sizeof(float), total));
     if (!L.bias.p) LRP_TRY(L.bias.alloc((size_t)L.cout * sizeof(float), total));
-    LRP_HIP_CHECK(hipMemcpyAsync(L.raw_b_dev.p, b_dev, (size_t)L.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
-    LRP_HIP_CHECK(hipMemcpyAsync(L.bias.p, b_dev, (size_t)L.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
-    L.raw_b.clear();
+    LRP_HIP_CHECK(hipMemcpyAsync(L.raw_b_dev.p, b, (size_t)L.cout * sizeof(float), kind, st));
+    LRP_HIP_CHECK(hipMemcpyAsync(L.bias.p, L.raw_b_dev.p, (size_t)L.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
     L.have_b = true;
     L.norm_dirty = true;
     encoded = 0;
-    return LRP_OK;
-  }
-
-  int set_conv_bias(int li, const float* b, int64_t* total) {
-    ConvLayer& L = layers[li];
-    if (b != L.raw_b.data()) L.raw_b.assign(b, b + L.cout);
-    L.raw_b_dev.release();
-    LRP_TRY(L.bias.alloc((size_t)L.cout * sizeof(float), total));
-    LRP_HIP_CHECK(hipMemcpy(L.bias.p, b, (size_t)L.cout * sizeof(float), hipMemcpyHostToDevice));
-    L.have_b = true;
-    L.norm_dirty = true;
     return LRP_OK;
   }
 

@@ -56,8 +56,8 @@ static hipStream_t S(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // ---- the two invariants of the boundary (include/lrp_hip.h:10-20), enforced in ONE place for every entry point:
 //  (1) no C++ exception crosses the C ABI: bodies run inside guarded(), which maps std::bad_alloc -> LRP_ERR_NOMEM and
-//      anything else -> LRP_ERR_INVALID (std::vector / std::string / std::map in the weight setters and the operator
-//      entries can throw; `new lrp_handle` too);
+//      anything else -> LRP_ERR_INVALID (std::vector / std::string / std::map in the weight setters, the decoder and
+//      the evaluation entries can throw; `new lrp_handle` too);
 //  (2) a handle's work runs on the handle's device: with_handle() makes cfg.device current for the duration of the call
 //      and restores the caller's device on return (lazy allocations — Decoder::finalize, the scan / gradient packs, the
 //      trainer's buffers — and every kernel launch would otherwise land on whatever device the calling thread had
@@ -157,14 +157,19 @@ int lrp_destroy(lrp_handle* h) {
 
 int64_t lrp_workspace_bytes(const lrp_handle* h) { return h ? h->ws_bytes : 0; }
 
-static int set_weight_host(lrp_handle* h, const char* name, const float* data, int32_t ndim, const int64_t* shape) {
-  if (!h || !name || !data || !shape || ndim < 1 || ndim > 4) return fail(LRP_ERR_INVALID, "bad lrp_set_weight arguments");
+// One body for both weight setters: name routing, shape checks, then the array is copied into HBM (`kind`: from the
+// caller's host or device memory) and every operand copy is built there by the device packers (cnn_kernels.h pack_*_dev,
+// resnet_encoder.h pack_unit_dev, Decoder::repack_device).  Everything is enqueued on `st`; nothing waits for it.
+static int set_weight(lrp_handle* h, const char* name, const float* data, hipMemcpyKind kind, int32_t ndim, const int64_t* shape,
+                      hipStream_t st) {
+  if (!name || !data || !shape || ndim < 1 || ndim > 4) return fail(LRP_ERR_INVALID, "bad lrp_set_weight arguments");
   LRP_TRY(h->trainer.drop_early_forward(nullptr));   // an lrp_train_forward of the old weights is stale
   const std::string nm(name);
   if (h->resnet) {
-    const int rc = h->rn.set_weight(nm, data, ndim, shape, &h->ws_bytes);
-    if (rc != 1) return rc;                       // 1 = not an encoder weight
-    return h->dec.set_weight(nm, data, ndim, shape, &h->ws_bytes);
+    if (h->dec.known_weight(nm)) return h->dec.set_weight(nm, data, kind, ndim, shape, &h->ws_bytes, st);
+    const int rc = h->rn.set_weight(nm, data, kind, ndim, shape, &h->ws_bytes, st);
+    if (rc != 1) return rc;                         // 1 = not an encoder weight
+    return fail(LRP_ERR_INVALID, "unknown weight '%s'", name);
   }
   if (nm.size() > 2 && (nm.compare(nm.size() - 2, 2, "_W") == 0 || nm.compare(nm.size() - 2, 2, "_b") == 0)) {
     const int li = h->enc.find_layer(nm.substr(0, nm.size() - 2));
@@ -173,52 +178,34 @@ static int set_weight_host(lrp_handle* h, const char* name, const float* data, i
       if (nm.back() == 'W') {
         if (ndim != 4 || shape[0] != 3 || shape[1] != 3 || shape[2] != L.cin || shape[3] != L.cout)
           return fail(LRP_ERR_INVALID, "%s: expected HWIO (3,3,%d,%d)", name, L.cin, L.cout);
-        return h->enc.set_conv_weight(li, data, &h->ws_bytes);
+        return h->enc.set_conv_weight_dev(li, data, kind, &h->ws_bytes, st);
       }
       if (ndim != 1 || shape[0] != L.cout) return fail(LRP_ERR_INVALID, "%s: expected (%d,)", name, L.cout);
-      return h->enc.set_conv_bias(li, data, &h->ws_bytes);
+      return h->enc.set_conv_bias_dev(li, data, kind, &h->ws_bytes, st);
     }
   }
-  return h->dec.set_weight(nm, data, ndim, shape, &h->ws_bytes);
+  return h->dec.set_weight(nm, data, kind, ndim, shape, &h->ws_bytes, st);
 }
 
+// Synchronous: on return the caller's array has been read (it may be reused or freed) and errors of the copy have surfaced.
 int lrp_set_weight(lrp_handle* h, const char* name, const float* data_host, int32_t ndim, const int64_t* shape) {
   return with_handle(h, [&]() -> int {
-    return set_weight_host(h, name, data_host, ndim, shape);
+    const int rc = set_weight(h, name, data_host, hipMemcpyHostToDevice, ndim, shape, nullptr);
+    if (rc != LRP_OK) {
+      (void)hipStreamSynchronize(nullptr);               // (a copy out of the caller's array may already be in flight)
+      return rc;
+    }
+    LRP_HIP_CHECK(hipStreamSynchronize(nullptr));
+    return LRP_OK;
   });
 }
 
+// The multi-GPU start-up path: the bundle arrives in HBM over RCCL/xGMI and stays there.  No device-to-host copy, no
+// stream synchronisation.
 int lrp_set_weight_dev(lrp_handle* h, const char* name, const float* data_dev, int32_t ndim, const int64_t* shape,
                        void* stream) {
   return with_handle(h, [&]() -> int {
-    if (!h || !name || !data_dev || !shape || ndim < 1 || ndim > 4) return fail(LRP_ERR_INVALID, "bad lrp_set_weight_dev arguments");
-    LRP_TRY(h->trainer.drop_early_forward(nullptr));
-    const std::string nm(name);
-    hipStream_t st = S(stream);
-    // The multi-GPU start-up path: the bundle arrives in HBM over RCCL/xGMI and stays there — D2D copy of the Keras-layout
-    // array, then the device packers (cnn_kernels.h pack_*_dev, Decoder::repack_device) build every operand copy.  No
-    // device-to-host copy, no stream synchronisation.
-    if (!h->resnet) {
-      if (nm.size() > 2 && (nm.compare(nm.size() - 2, 2, "_W") == 0 || nm.compare(nm.size() - 2, 2, "_b") == 0)) {
-        const int li = h->enc.find_layer(nm.substr(0, nm.size() - 2));
-        if (li >= 0) {
-          const ConvLayer& L = h->enc.layers[li];
-          if (nm.back() == 'W') {
-            if (ndim != 4 || shape[0] != 3 || shape[1] != 3 || shape[2] != L.cin || shape[3] != L.cout)
-              return fail(LRP_ERR_INVALID, "%s: expected HWIO (3,3,%d,%d)", name, L.cin, L.cout);
-            return h->enc.set_conv_weight_dev(li, data_dev, &h->ws_bytes, st);
-          }
-          if (ndim != 1 || shape[0] != L.cout) return fail(LRP_ERR_INVALID, "%s: expected (%d,)", name, L.cout);
-          return h->enc.set_conv_bias_dev(li, data_dev, &h->ws_bytes, st);
-        }
-      }
-      return h->dec.set_weight_dev(nm, data_dev, ndim, shape, &h->ws_bytes, st);
-    }
-    if (h->dec.known_weight(nm)) return h->dec.set_weight_dev(nm, data_dev, ndim, shape, &h->ws_bytes, st);
-    // ResNet encoder units: packed on the device as well (resnet_encoder.h pack_unit_dev)
-    const int rc = h->rn.set_weight_dev(nm, data_dev, ndim, shape, &h->ws_bytes, st);
-    if (rc != 1) return rc;
-    return fail(LRP_ERR_INVALID, "unknown weight '%s'", name);
+    return set_weight(h, name, data_dev, hipMemcpyDeviceToDevice, ndim, shape, S(stream));
   });
 }
 
@@ -438,6 +425,23 @@ int lrp_profile_records(lrp_handle* h, int32_t cap, double* ms_out, double* flop
   });
 }
 
+// Operator entries: the caller's HWIO array (taps, Cin, Cout) goes to HBM as it is (`raw`, uploaded once) and is packed there
+// by the packer the handles use (cnn_kernels.h pack_conv_dev_kernel): forward [Cout rows][taps * CinP], or — bwd — the
+// transposed conv's [Cin rows][taps * CoutP] with flipped taps; zero padded.
+static int op_pack_weight(const float* w_host, int taps, int Cin, int Cout, int bwd, DevBuf& raw, DevBuf& pk, hipStream_t st) {
+  if (!raw.p) {
+    LRP_TRY(raw.alloc((size_t)taps * Cin * Cout * sizeof(float), nullptr));
+    LRP_HIP_CHECK(hipMemcpy(raw.p, w_host, raw.bytes, hipMemcpyHostToDevice));
+  }
+  const int rows = conv_npad(bwd ? Cin : Cout), CP = conv_cinp(bwd ? Cout : Cin);
+  const size_t tot = (size_t)rows * taps * CP;
+  LRP_TRY(pk.alloc(tot * sizeof(float), nullptr));
+  hipLaunchKernelGGL(pack_conv_dev_kernel, dim3(stream_grid(tot)), dim3(256), 0, st, raw.as<float>(), pk.as<float>(), bwd, Cin, Cout, CP,
+                     rows, 0, 0, taps);
+  LRP_HIP_CHECK(hipGetLastError());
+  return LRP_OK;
+}
+
 int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias_host, const float* aux_dev, float* out_dev,
                 int32_t NB, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t taps, int32_t mode, void* stream) {
   return guarded([&]() -> int {
@@ -452,34 +456,30 @@ int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias
     // forward: in has Cin channels, out Cout.  backward: in has Cout channels (S), out Cin (relevance of the input)
     const int inC = bwd ? Cout : Cin, outC = bwd ? Cin : Cout;
     if (inC % 4 != 0) return fail(LRP_ERR_UNSUPPORTED, "input channels must be a multiple of 4");
+    if (split && ((inC & 7) || (bwd && (outC & 7)))) return fail(LRP_ERR_UNSUPPORTED, "split-bf16 path: channels must be multiples of 8");
     const int Np = conv_npad(outC), K = taps * conv_cinp(inC);
-    std::vector<float> pk((size_t)Np * K, 0.f);
-    if (bwd) pack_conv_bwd(w_hwio_host, taps, Cin, Cout, 0, pk.data());
-    else pack_conv_fwd(w_hwio_host, taps, Cin, Cout, 0, Np, pk.data());
-    DevBuf wdev, bdev, insplit, wfrag;
+    hipStream_t st = S(stream);
+    DevBuf wraw, wdev, wsplit, bdev, insplit, wfrag;
+    LRP_TRY(op_pack_weight(w_hwio_host, taps, Cin, Cout, bwd, wraw, wdev, st));
     if (split) {
-      if ((inC & 7) || (bwd && (outC & 7))) return fail(LRP_ERR_UNSUPPORTED, "split-bf16 path: channels must be multiples of 8");
-      std::vector<float> sp(pk.size());
-      pack_split8(pk.data(), pk.size(), sp.data());
-      pk.swap(sp);
+      const size_t nw8 = (size_t)Np * K / 8;
+      LRP_TRY(wsplit.alloc(wdev.bytes, nullptr));
+      hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(nw8)), dim3(256), 0, st, wdev.as<float>(), wsplit.as<float>(), nw8);
       if (bwd && taps == 9 && Np == 64) {                  // weights-in-registers variant of the N <= 64 backward convs
-        std::vector<float> fr((size_t)64 * K);
-        pack_frag64(pk.data(), 9, conv_cinp(inC), fr.data());
-        LRP_TRY(wfrag.alloc(fr.size() * sizeof(float), nullptr));
-        LRP_HIP_CHECK(hipMemcpy(wfrag.p, fr.data(), fr.size() * sizeof(float), hipMemcpyHostToDevice));
+        LRP_TRY(wfrag.alloc((size_t)64 * K * sizeof(float), nullptr));
+        hipLaunchKernelGGL(pack_frag64_dev_kernel, dim3(stream_grid((size_t)conv_cinp(inC) / 32 * 9 * 512)), dim3(256), 0, st,
+                           wsplit.as<float>(), wfrag.as<float>(), conv_cinp(inC));
       }
       const size_t n8 = (size_t)NB * H * W * inC / 8;
       LRP_TRY(insplit.alloc(n8 * 32, nullptr));
-      hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n8)), dim3(256), 0, S(stream), in_dev, insplit.as<float>(), n8);
+      hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n8)), dim3(256), 0, st, in_dev, insplit.as<float>(), n8);
       LRP_HIP_CHECK(hipGetLastError());
       in_dev = insplit.as<float>();
     }
-    LRP_TRY(wdev.alloc(pk.size() * sizeof(float), nullptr));
-    LRP_HIP_CHECK(hipMemcpy(wdev.p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
     ConvArgs ca{};
     ca.out_plain = 1;
     ca.wpk_frag = wfrag.as<float>();
-    ca.in = in_dev; ca.wpk = wdev.as<float>(); ca.NB = NB; ca.H = H; ca.W = W; ca.Cin = inC; ca.CinP = conv_cinp(inC);
+    ca.in = in_dev; ca.wpk = split ? wsplit.as<float>() : wdev.as<float>(); ca.NB = NB; ca.H = H; ca.W = W; ca.Cin = inC; ca.CinP = conv_cinp(inC);
     ca.N = outC; ca.taps = taps; ca.out = out_dev; ca.aux = aux_dev;
     if (!bwd) {
       if (!bias_host) return fail(LRP_ERR_INVALID, "bias required for forward modes");
@@ -490,8 +490,8 @@ int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias
       return fail(LRP_ERR_INVALID, "aux (gate) required for backward modes");
     }
     static const int epi_of_mode[4] = {EPI_BIAS_RELU, EPI_BIAS, EPI_MUL, EPI_MUL_UP2};
-    LRP_HIP_CHECK(conv_launch(epi_of_mode[mode], ca, S(stream), split ? PREC_BF16X3 : PREC_FP32));
-    LRP_HIP_CHECK(hipStreamSynchronize(S(stream)));      // weights are freed on return
+    LRP_HIP_CHECK(conv_launch(epi_of_mode[mode], ca, st, split ? PREC_BF16X3 : PREC_FP32));
+    LRP_HIP_CHECK(hipStreamSynchronize(st));             // weights are freed on return
     return LRP_OK;
   });
 }
@@ -504,12 +504,8 @@ int lrp_op_conv_pool_sparse(const float* sc_dev, const unsigned char* pos_dev, c
     if (!conv_sparse_supports(Cin, Cout, Hp, Wp))
       return fail(LRP_ERR_UNSUPPORTED, "the sparse consumer needs Cin %% 256 == 0 (output columns) and Cout %% 16 == 0");
     hipStream_t st = S(stream);
-    const int Npb = conv_npad(Cin), Kb = 9 * conv_cinp(Cout);
-    std::vector<float> pk((size_t)Npb * Kb, 0.f);
-    pack_conv_bwd(w_hwio_host, 9, Cin, Cout, 0, pk.data());
-    DevBuf wb, wsp, pairs;
-    LRP_TRY(wb.alloc(pk.size() * sizeof(float), nullptr));
-    LRP_HIP_CHECK(hipMemcpy(wb.p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
+    DevBuf wraw, wb, wsp, pairs;
+    LRP_TRY(op_pack_weight(w_hwio_host, 9, Cin, Cout, 1, wraw, wb, st));
     LRP_TRY(wsp.alloc(conv_sparse_weight_floats(Cin, Cout) * sizeof(float), nullptr));
     LRP_HIP_CHECK(conv_sparse_pack(wb.as<float>(), wsp.as<float>(), Cin, Cout, st));
     const size_t n8 = (size_t)NB * Hp * Wp * Cout / 8;
@@ -536,17 +532,12 @@ int lrp_op_epsilon_dense(const float* x_dev, const float* W_host, const float* R
     if (N < 1 || (Din & 3) || (Dout & 3) || !(epsilon > 0.f)) return fail(LRP_ERR_INVALID, "need N>=1, Din%%4==0, Dout%%4==0, epsilon>0");
     hipStream_t st = S(stream);
     // Z = x.W  (1-tap GEMM, B operand packed [Dout][Din]);  C = S.W^T  (packed [Din][Dout])
-    const int Np = conv_npad(Dout), K = conv_cinp(Din), Npb = conv_npad(Din), Kb = conv_cinp(Dout);
-    std::vector<float> pk((size_t)Np * K, 0.f), pkb((size_t)Npb * Kb, 0.f);
-    pack_conv_fwd(W_host, 1, Din, Dout, 0, Np, pk.data());
-    pack_conv_bwd(W_host, 1, Din, Dout, 0, pkb.data());
-    DevBuf wf, wb, Z, Sb;
-    LRP_TRY(wf.alloc(pk.size() * sizeof(float), nullptr));
-    LRP_TRY(wb.alloc(pkb.size() * sizeof(float), nullptr));
+    const int K = conv_cinp(Din), Kb = conv_cinp(Dout);
+    DevBuf wraw, wf, wb, Z, Sb;
+    LRP_TRY(op_pack_weight(W_host, 1, Din, Dout, 0, wraw, wf, st));
+    LRP_TRY(op_pack_weight(W_host, 1, Din, Dout, 1, wraw, wb, st));
     LRP_TRY(Z.alloc((size_t)N * Dout * sizeof(float), nullptr));
     LRP_TRY(Sb.alloc((size_t)N * Dout * sizeof(float), nullptr));
-    LRP_HIP_CHECK(hipMemcpy(wf.p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
-    LRP_HIP_CHECK(hipMemcpy(wb.p, pkb.data(), pkb.size() * sizeof(float), hipMemcpyHostToDevice));
     ConvArgs cz{};
     cz.in = x_dev; cz.wpk = wf.as<float>(); cz.NB = N; cz.H = 1; cz.W = 1; cz.Cin = Din; cz.CinP = K; cz.N = Dout; cz.taps = 1;
     cz.out = Z.as<float>();
@@ -737,7 +728,7 @@ int lrp_train_drop_forward(lrp_handle* h, void* stream) {
 int lrp_train_apply(lrp_handle* h, const float* grads_dev, void* stream) {
   return with_handle(h, [&]() -> int {
     if (!h || !grads_dev) return fail(LRP_ERR_INVALID, "null argument");
-    return h->trainer.apply(h->enc, h->dec, grads_dev, nullptr, S(stream));
+    return h->trainer.apply(h->enc, h->dec, grads_dev, S(stream));
   });
 }
 

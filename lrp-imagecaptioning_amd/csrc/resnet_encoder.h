@@ -137,7 +137,7 @@ struct ResNetEncoder {
       LRP_TRY(b.GA.alloc(B * (size_t)b.H * b.W * 4 * b.f * 4, total));
       LRP_TRY(b.GS.alloc(B * (size_t)b.H * b.W * 4 * b.f * 4, total));
     }
-    // staging of lrp_set_weight_dev (allocated here: that entry point promises no allocation / stream synchronisation)
+    // staging of the weight setters (allocated here: lrp_set_weight_dev promises no allocation / stream synchronisation)
     size_t mx = 0, mxd = 0;
     for (const RnUnit& q : units) {
       mx = std::max(mx, (size_t)q.k * q.k * q.cin * q.cout);
@@ -157,46 +157,17 @@ struct ResNetEncoder {
     return -1;
   }
 
-  static int up(DevBuf& d, const std::vector<float>& v, int64_t* total) {
-    LRP_TRY(d.alloc(v.size() * 4, total));
-    LRP_HIP_CHECK(hipMemcpy(d.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-    return LRP_OK;
-  }
-
-  // name = "<unit>_conv_W" | "_conv_b" | "_bn_gamma" | "_bn_beta" | "_bn_mean" | "_bn_var"; returns 1 if not ours
-  int set_weight(const std::string& nm, const float* data, int ndim, const int64_t* shape, int64_t* total) {
-    static const char* suf[6] = {"_conv_W", "_conv_b", "_bn_gamma", "_bn_beta", "_bn_mean", "_bn_var"};
-    for (int s = 0; s < 6; ++s) {
-      const std::string sf(suf[s]);
-      if (nm.size() <= sf.size() || nm.compare(nm.size() - sf.size(), sf.size(), sf) != 0) continue;
-      const int ui = find_unit(nm.substr(0, nm.size() - sf.size()));
-      if (ui < 0) return 1;
-      RnUnit& u = units[ui];
-      if (s == 0) {
-        if (ndim != 4 || shape[0] != u.k || shape[1] != u.k || shape[2] != u.cin || shape[3] != u.cout)
-          return fail(LRP_ERR_INVALID, "%s: expected HWIO (%d,%d,%d,%d)", nm.c_str(), u.k, u.k, u.cin, u.cout);
-        LRP_TRY(pack_unit(u, data, total));
-      } else {
-        if (ndim != 1 || shape[0] != u.cout) return fail(LRP_ERR_INVALID, "%s: expected (%d,)", nm.c_str(), u.cout);
-        DevBuf* dst[6] = {nullptr, &u.bias, &u.gamma, &u.beta, &u.mean, &u.var};
-        LRP_TRY(up(*dst[s], std::vector<float>(data, data + u.cout), total));
-      }
-      u.have[s] = true;
-      u.grad_ok = false;
-      norms_ready = false;
-      return LRP_OK;
-    }
-    return 1;
-  }
-
-  // lrp_set_weight_dev for the encoder units: the array is already in HBM (RCCL broadcast); vectors are D2D copies, kernels
-  // are packed by device kernels — no device-to-host copy, no stream synchronisation.  Returns 1 if the name is not ours.
+  // name = "<unit>_conv_W" | "_conv_b" | "_bn_gamma" | "_bn_beta" | "_bn_mean" | "_bn_var"; returns 1 if not ours.
+  // `data` is a host array (lrp_set_weight) or already in HBM (lrp_set_weight_dev: RCCL broadcast), `kind` says which:
+  // vectors are one copy, kernels are copied into the staging buffer and packed by device kernels — no device-to-host
+  // copy, no allocation after a unit's first set, no stream synchronisation.
   // ONE staging pair for every unit (largest interleaved dual matrix / largest HWIO kernel): a call's packers read it
   // asynchronously on that call's stream, so the NEXT call — possibly on another stream: an RCCL stream, then a compute
   // stream — first makes its stream wait for `ev_pack`, recorded behind the previous call's last reader.
   DevBuf pack_tmp, raw_tmp;
   hipEvent_t ev_pack = nullptr;
-  int set_weight_dev(const std::string& nm, const float* data_dev, int ndim, const int64_t* shape, int64_t* total, hipStream_t st) {
+  int set_weight(const std::string& nm, const float* data, hipMemcpyKind kind, int ndim, const int64_t* shape, int64_t* total,
+                 hipStream_t st) {
     static const char* suf[6] = {"_conv_W", "_conv_b", "_bn_gamma", "_bn_beta", "_bn_mean", "_bn_var"};
     for (int s = 0; s < 6; ++s) {
       const std::string sf(suf[s]);
@@ -211,14 +182,14 @@ struct ResNetEncoder {
         const size_t nW = (size_t)u.k * u.k * u.cin * u.cout;
         if (!ev_pack) LRP_HIP_CHECK(hipEventCreateWithFlags(&ev_pack, hipEventDisableTiming));
         else LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_pack, 0));          // the previous unit's packers still read the staging pair
-        LRP_HIP_CHECK(hipMemcpyAsync(raw_tmp.p, data_dev, nW * 4, hipMemcpyDeviceToDevice, st));
+        LRP_HIP_CHECK(hipMemcpyAsync(raw_tmp.p, data, nW * 4, kind, st));
         LRP_TRY(pack_unit_dev(u, raw_tmp.as<float>(), total, st));
         LRP_HIP_CHECK(hipEventRecord(ev_pack, st));
       } else {
         if (ndim != 1 || shape[0] != u.cout) return fail(LRP_ERR_INVALID, "%s: expected (%d,)", nm.c_str(), u.cout);
         DevBuf* dst[6] = {nullptr, &u.bias, &u.gamma, &u.beta, &u.mean, &u.var};
         if (!dst[s]->p || dst[s]->bytes != (size_t)u.cout * 4) LRP_TRY(dst[s]->alloc((size_t)u.cout * 4, total));
-        LRP_HIP_CHECK(hipMemcpyAsync(dst[s]->p, data_dev, (size_t)u.cout * 4, hipMemcpyDeviceToDevice, st));
+        LRP_HIP_CHECK(hipMemcpyAsync(dst[s]->p, data, (size_t)u.cout * 4, kind, st));
       }
       u.have[s] = true;
       u.grad_ok = false;
@@ -271,7 +242,7 @@ struct ResNetEncoder {
           pack(pack_tmp.as<float>(), 0, Nd, 2, 0);
           src = pack_tmp.as<float>();
         }
-        LRP_TRY(make_f16_operand(f16_slots, src, nd, 0, 0, u.w_dual_h, u.wds, total, st, false));
+        LRP_TRY(make_f16_operand(f16_slots, src, nd, 0, 0, u.w_dual_h, u.wds, total, st));
       }
     }
     LRP_TRY(mk(u.w_b, nb)); LRP_TRY(mk(u.w_bs, nb));
@@ -279,77 +250,6 @@ struct ResNetEncoder {
     split(u.w_b.as<float>(), u.w_bs.as<float>(), nb);
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
-  }
-
-  int pack_unit(RnUnit& u, const float* w, int64_t* total) {
-    const size_t nW = (size_t)u.k * u.k * u.cin * u.cout;
-    std::vector<float> wp(nW), wn(nW), pk;
-    for (size_t i = 0; i < nW; ++i) { wp[i] = w[i] >= 0.f ? w[i] : 0.f; wn[i] = w[i] < 0.f ? w[i] : 0.f; }
-    if (u.k == 7) {
-      // stem forward: 1-tap GEMM over the im2col matrix [x+ patch | x- patch] (K = 2 * 160)
-      const int Np = conv_npad(u.cout), K = 2 * RN_STEM_K;
-      std::vector<float> a((size_t)Np * K, 0.f), z((size_t)Np * K, 0.f);
-      for (int kk = 0; kk < 147; ++kk)
-        for (int co = 0; co < u.cout; ++co) {
-          const size_t s = (size_t)kk * u.cout + co;
-          a[(size_t)co * K + kk] = w[s]; a[(size_t)co * K + RN_STEM_K + kk] = w[s];
-          z[(size_t)co * K + kk] = wp[s]; z[(size_t)co * K + RN_STEM_K + kk] = wn[s];
-        }
-      LRP_TRY(up(u.w_a, a, total));
-      LRP_TRY(up(u.w_z, z, total));
-      // reverse at the image: T[q][tap*6 + c] (c<3: w+, c>=3: w-), K = cout
-      const int Npb = conv_npad(RN_STEM_TCOLS), Kb = conv_cinp(u.cout);
-      pk.assign((size_t)Npb * Kb, 0.f);
-      for (int t = 0; t < 49; ++t)
-        for (int c = 0; c < 3; ++c)
-          for (int co = 0; co < u.cout; ++co) {
-            pk[(size_t)(t * 6 + c) * Kb + co] = wp[((size_t)t * 3 + c) * u.cout + co];
-            pk[(size_t)(t * 6 + 3 + c) * Kb + co] = wn[((size_t)t * 3 + c) * u.cout + co];
-          }
-      LRP_TRY(up(u.w_b, pk, total));
-      if (!(u.cout & 7)) {                               // split-bf16 copy: the tap GEMM of the walk as bf16x3
-        std::vector<float> sp(pk.size());
-        pack_split8(pk.data(), pk.size(), sp.data());
-        LRP_TRY(up(u.w_bs, sp, total));
-      }
-      return LRP_OK;
-    }
-    const int taps = u.k * u.k;
-    const int Np = conv_npad(u.cout), K = taps * conv_cinp(u.cin);
-    pk.assign((size_t)Np * K, 0.f);
-    pack_conv_fwd(w, taps, u.cin, u.cout, 0, Np, pk.data());
-    LRP_TRY(up(u.w_a, pk, total));
-    pk.assign((size_t)Np * K, 0.f);
-    pack_conv_fwd(wp.data(), taps, u.cin, u.cout, 0, Np, pk.data());           // inputs are post-ReLU: Z = conv(x, w+) + b
-    LRP_TRY(up(u.w_z, pk, total));
-    if (!(u.cout & 3)) {
-      const int Nd = conv_npad(2 * u.cout);
-      pk.assign((size_t)Nd * K, 0.f);
-      pack_conv_fwd(w, taps, u.cin, u.cout, 0, Nd, pk.data());
-      pack_conv_fwd(wp.data(), taps, u.cin, u.cout, u.cout, Nd, pk.data());
-      LRP_TRY(up(u.w_dual, pk, total));
-      if (!(u.cin & 7)) {
-        u.dual_il = !(u.cout & 31) && Nd == 2 * u.cout;
-        if (u.dual_il) {                                  // rows in blocks of 32: [w | w+] of the same 32 channels
-          std::vector<float> il(pk.size(), 0.f);
-          for (int c = 0; c < u.cout; ++c)
-            for (int half = 0; half < 2; ++half)
-              memcpy(&il[(size_t)(64 * (c / 32) + 32 * half + (c & 31)) * K], &pk[(size_t)(half * u.cout + c) * K], (size_t)K * sizeof(float));
-          DevBuf tmp;
-          LRP_TRY(up(tmp, il, nullptr));
-          LRP_TRY(make_f16_operand(f16_slots, tmp.as<float>(), pk.size(), 0, 0, u.w_dual_h, u.wds, total, nullptr));
-        } else {
-          LRP_TRY(make_f16_operand(f16_slots, u.w_dual.as<float>(), pk.size(), 0, 0, u.w_dual_h, u.wds, total, nullptr));
-        }
-      }
-    }
-    const int Npb = conv_npad(u.cin), Kb = taps * conv_cinp(u.cout);
-    pk.assign((size_t)Npb * Kb, 0.f);
-    pack_conv_bwd(wp.data(), taps, u.cin, u.cout, 0, pk.data());
-    LRP_TRY(up(u.w_b, pk, total));
-    std::vector<float> sp(pk.size());
-    pack_split8(pk.data(), pk.size(), sp.data());
-    return up(u.w_bs, sp, total);
   }
 
   int check_ready() const {

@@ -502,7 +502,7 @@ __global__ __launch_bounds__(256) void rn_stem_im2col_kernel(const float* __rest
 // R_img[p][c] = x+[p][c] * sum_{tap} T+[q(p,tap)][tap][c] + x-[p][c] * sum T-[...],  q = ((i+3-kh)/2, (j+3-kw)/2) when integral
 constexpr int RN_STEM_TCOLS = 294;
 
-// Device twin of RnEncoder::pack_unit's stem branch (lrp_set_weight_dev: the weights arrive in HBM and stay there).
+// The 7x7 stem's packer (ResNetEncoder::pack_unit_dev; the other units take cnn_kernels.h pack_conv_dev_kernel):
 // w: HWIO (7,7,3,cout).  wa / wz [Np][2 * RN_STEM_K]: a rows hold w against the x+ and the x- patch, z rows w+ / w-;
 // wb [Npb][Kb]: row t*6 + c = w+[t][c][:], row t*6 + 3 + c = w-[t][c][:] (the tap GEMM of the walk).  All zero padded.
 __global__ __launch_bounds__(256) void rn_pack_stem_dev_kernel(const float* __restrict__ w, float* __restrict__ wa, float* __restrict__ wz,
@@ -719,7 +719,7 @@ __global__ __launch_bounds__(256) void rn_stem_stencil_kernel(const float* __res
 // A conv + BN unit's backward is convT with the weights scaled per output channel by s = gamma / sqrt(var + eps); a ReLU passes
 // the gradient where its forward output was > 0 (byte masks of the fp32 forward); GUIDED: every ReLU first clamps at 0.
 
-// Backward matrix of a conv + BN unit in the layout of w_b (pack_conv_bwd), full sign and BN-scaled, from the forward matrix
+// Backward matrix of a conv + BN unit in the layout of w_b (cnn_kernels.h pack_conv_dev_kernel, bwd = 1), full sign and BN-scaled, from the forward matrix
 // w_a [rows >= cout][taps * CPi]:  wg[ci][t * CPo + co] = w_a[co][t' * CPi + ci] * s[co],  t' = taps - 1 - t
 __global__ __launch_bounds__(256) void rn_pack_grad_kernel(const float* __restrict__ wa, const float* __restrict__ gamma,
                                                            const float* __restrict__ var, float bn_eps, float* __restrict__ wg,

@@ -45,10 +45,7 @@ struct Trainer {
   std::vector<TrainParam> params;
   size_t n_total = 0;
   DevBuf master, mom, vel;
-  std::vector<float> host;                     // staging of the initial weights
-  float* host_pinned = nullptr;                // pinned mirror of the slices that are re-packed on the host
   ~Trainer() {
-    if (host_pinned) (void)hipHostFree(host_pinned);
     if (ev_fwd) (void)hipEventDestroy(ev_fwd);
   }
   float lr = 0.f, clip = 0.f, b1 = 0.9f, b2 = 0.999f, eps = 1e-7f;
@@ -106,34 +103,25 @@ struct Trainer {
       add("Wv", {H, H}); add("Wg", {H, H}); add("V", {H, 1}); add("Wx", {2 * E, H}); add("Wh", {H, H}); add("Ws", {H, H});
     }
     add("output_W", {H, V}); add("output_b", {V});
-    host.assign(n_total, 0.f);
-    // initial master weights: the host copies of lrp_set_weight, or — for weights that arrived through
-    // lrp_set_weight_dev — a device-to-device copy after the upload below
-    std::vector<std::pair<size_t, const DevBuf*>> from_dev;
-    auto take = [&](size_t pi, const std::vector<float>& hostv, const DevBuf* devv, const char* what) -> int {
-      if (hostv.size() == params[pi].n) std::copy(hostv.begin(), hostv.end(), host.begin() + params[pi].off);
-      else if (devv && devv->p && devv->bytes == params[pi].n * 4) from_dev.push_back({pi, devv});
-      else return fail(LRP_ERR_STATE, "weight '%s' is not set (or has the wrong size)", what);
+    LRP_TRY(master.alloc(n_total * 4, total)); LRP_TRY(mom.alloc(n_total * 4, total)); LRP_TRY(vel.alloc(n_total * 4, total));
+    // initial master weights: the arrays as set, device to device (the padding between the slices stays zero)
+    LRP_HIP_CHECK(hipMemset(master.p, 0, n_total * 4));
+    auto take = [&](size_t pi, const DevBuf* set) -> int {
+      if (!set || !set->p || set->bytes != params[pi].n * 4)
+        return fail(LRP_ERR_STATE, "weight '%s' is not set (or has the wrong size)", params[pi].name.c_str());
+      LRP_HIP_CHECK(hipMemcpy(master.as<float>() + params[pi].off, set->p, params[pi].n * 4, hipMemcpyDeviceToDevice));
       return LRP_OK;
     };
     size_t pi = 0;
     for (const ConvLayer& Ly : enc.layers) {
-      LRP_TRY(take(pi, Ly.raw_w, &Ly.raw_w_dev, params[pi].name.c_str()));
-      LRP_TRY(take(pi + 1, Ly.raw_b, &Ly.raw_b_dev, params[pi + 1].name.c_str()));
+      LRP_TRY(take(pi, &Ly.raw_w_dev));
+      LRP_TRY(take(pi + 1, &Ly.raw_b_dev));
       pi += 2;
     }
-    static const std::vector<float> none;
     for (; pi < params.size(); ++pi) {
-      auto it = dec.raw.find(params[pi].name);
-      auto jt = dec.raw_dev.find(params[pi].name);
-      LRP_TRY(take(pi, it != dec.raw.end() ? it->second : none, jt != dec.raw_dev.end() ? &jt->second : nullptr, params[pi].name.c_str()));
+      auto it = dec.raw_dev.find(params[pi].name);
+      LRP_TRY(take(pi, it != dec.raw_dev.end() ? &it->second : nullptr));
     }
-    if (host_pinned) { (void)hipHostFree(host_pinned); host_pinned = nullptr; }
-    if (hipHostMalloc(reinterpret_cast<void**>(&host_pinned), n_total * 4) != hipSuccess) return fail(LRP_ERR_NOMEM, "hipHostMalloc failed");
-    LRP_TRY(master.alloc(n_total * 4, total)); LRP_TRY(mom.alloc(n_total * 4, total)); LRP_TRY(vel.alloc(n_total * 4, total));
-    LRP_HIP_CHECK(hipMemcpy(master.p, host.data(), n_total * 4, hipMemcpyHostToDevice));
-    for (auto& fd : from_dev)
-      LRP_HIP_CHECK(hipMemcpy(master.as<float>() + params[fd.first].off, fd.second->p, params[fd.first].n * 4, hipMemcpyDeviceToDevice));
     LRP_HIP_CHECK(hipMemset(mom.p, 0, n_total * 4));
     LRP_HIP_CHECK(hipMemset(vel.p, 0, n_total * 4));
     lr = lr_; clip = clip_; b1 = b1_; b2 = b2_; eps = eps_; iter = 0;
@@ -627,7 +615,7 @@ struct Trainer {
   }
 
   // keras Adam(lr, clipvalue) on the master weights, then the engine's operand copies are rebuilt from them
-  int apply(Encoder& enc, Decoder& dec, const float* grads, int64_t* total, hipStream_t st) {
+  int apply(Encoder& enc, Decoder& dec, const float* grads, hipStream_t st) {
     if (!ready) return fail(LRP_ERR_STATE, "lrp_train_begin must run first");
     fwd_valid = false;                             // (a forward of the old weights, if any, is stale)
     ++iter;
@@ -635,13 +623,12 @@ struct Trainer {
     hipLaunchKernelGGL(tr_adam_kernel, dim3(grid_for(n_total)), dim3(256), 0, st, master.as<float>(), grads, mom.as<float>(),
                        vel.as<float>(), n_total, (float)lr_t, clip, b1, b2, eps);
     LRP_HIP_CHECK(hipGetLastError());
-    return sync_engine(enc, dec, total, st);
+    return sync_engine(enc, dec, st);
   }
 
   // Operand copies are rebuilt on the device: the encoder's by cnn_kernels.h pack_*_dev (image layer included), the
-  // decoder's by Decoder::refresh_from_device.  Only a decoder that no forward has finalised yet (refresh returns 1)
-  // is handed its weights through the host, once.
-  int sync_engine(Encoder& enc, Decoder& dec, int64_t* total, hipStream_t st) {
+  // decoder's by Decoder::refresh_from_device (which first builds them if no forward has done so yet).
+  int sync_engine(Encoder& enc, Decoder& dec, hipStream_t st) {
     if (enc.gates_pending) {                       // the side stream may still read the operand copies we replace
       LRP_HIP_CHECK(hipStreamWaitEvent(st, enc.ev_gates, 0));
       enc.gates_pending = false;
@@ -649,16 +636,8 @@ struct Trainer {
     for (size_t li = 0; li < enc.layers.size(); ++li)
       LRP_TRY(enc.repack_conv_from_device((int)li, master.as<float>() + params[2 * li].off, master.as<float>() + params[2 * li + 1].off,
                                           ws.as<float>(), st));
-    const size_t dec0 = params[2 * enc.layers.size()].off;                         // [dec0, n): decoder
     std::function<const float*(const char*)> Wd = [&](const char* nm) -> const float* { return W(nm); };
-    const int drc = dec.refresh_from_device(Wd, st);   // 1: the decoder has not built its operand copies yet
-    if (drc != LRP_OK && drc != 1) return drc;
-    if (drc == 1) {                                // no forward has finalised the decoder yet: hand it the weights once
-      LRP_HIP_CHECK(hipMemcpyAsync(host_pinned + dec0, master.as<float>() + dec0, (n_total - dec0) * 4, hipMemcpyDeviceToHost, st));
-      LRP_HIP_CHECK(hipStreamSynchronize(st));
-      for (size_t pi = 2 * enc.layers.size(); pi < params.size(); ++pi)
-        LRP_TRY(dec.set_weight(params[pi].name, host_pinned + params[pi].off, (int)params[pi].shape.size(), params[pi].shape.data(), total));
-    }
+    LRP_TRY(dec.refresh_from_device(Wd, st));
     enc.encoded = 0;                               // caches belong to the old weights
     return LRP_OK;
   }

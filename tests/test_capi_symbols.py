@@ -61,9 +61,10 @@ def test_missing_library_fails_loudly(monkeypatch, tmp_path):
 
 def test_no_exception_crosses_the_abi():
     """include/lrp_hip.h: 'return value: 0 = LRP_OK, negative = error' — a C++ exception must never unwind through an
-    extern "C" entry into ctypes.  lrp_op_conv packs its weights into a std::vector sized from the caller's channel
-    counts BEFORE any HIP call; 2^27 x 2^27 channels make that allocation (~650 PB) throw std::bad_alloc, which has to
-    come back as LRP_ERR_NOMEM with a message (every entry point runs inside the same guard, csrc/engine.hip)."""
+    extern "C" entry into ctypes.  lrp_op_conv sizes its first allocation from the caller's channel counts; 2^27 x 2^27
+    channels (~650 PB) cannot be had and have to come back as LRP_ERR_NOMEM with a message (every entry point runs
+    inside the same guard, csrc/engine.hip).  The weights are packed on the device, so that allocation is the device
+    copy of the array — without a GPU the allocator fails just the same."""
     import numpy as np
     from lrp_imagecaptioning_amd import _capi
     lib = _capi.load()

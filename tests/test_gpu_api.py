@@ -421,7 +421,8 @@ def test_weights_set_from_device_match_host_set(kind):
     """lrp_set_weight_dev (the multi-GPU start-up path: the bundle arrives in HBM over RCCL and is packed by device
     kernels, no host round trip) must leave the handle in exactly the state lrp_set_weight does: heat-maps, decoder
     LRP, gradient baselines and the fine-tune step's first gradients bit for bit — also when some weights come from the
-    host and some from the device."""
+    host and some from the device.  Both setters pack with the same device kernels: a host-set handle holds what a
+    device-set one holds (equal lrp_workspace_bytes), and lrp_set_weight has read the caller's array when it returns."""
     import torch
     from lrp_imagecaptioning_amd.engine import LRPEngine
     from lrp_imagecaptioning_amd.synthetic import gridtd_weights
@@ -443,12 +444,23 @@ def test_weights_set_from_device_match_host_set(kind):
 
     host = LRPEngine(**kw)
     host.set_weights(w)
+    ws_host = host.workspace_bytes
     want = run(host)
     wd = {k: torch.as_tensor(v).cuda() for k, v in w.items()}
     dev = LRPEngine(**kw)
     dev.set_weights_from_device(wd)
+    assert dev.workspace_bytes == ws_host
     got = run(dev)
     for a, b in zip(got, want):
+        assert torch.equal(a, b)
+    assert dev.workspace_bytes == host.workspace_bytes
+    # lrp_set_weight is synchronous: the caller's array may be overwritten as soon as the call returns
+    reuse = LRPEngine(**kw)
+    for k, v in w.items():
+        a = np.ascontiguousarray(v.copy(), dtype=np.float32)       # (set_weights hands this very buffer to the library)
+        reuse.set_weights({k: a})
+        a.fill(np.nan)
+    for a, b in zip(run(reuse), want):
         assert torch.equal(a, b)
     # mixed: decoder from the host, encoder from the device, one weight overwritten by the other route afterwards
     mix = LRPEngine(**kw)

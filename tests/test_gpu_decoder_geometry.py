@@ -344,7 +344,7 @@ def test_gridtd_gradient(gid):
 @pytest.mark.parametrize("gid", ROUTE_GEOS)
 def test_device_route_equals_host_route(gid, kind):
     """lrp_set_weight_dev (repack_device: strided copies and transposes with E- and H-wide leading dimensions) leaves the
-    handle in exactly the state lrp_set_weight (pack_lstm, gate_g_block, pack_rows on the host) does: forward state, R_feat
+    handle in exactly the state lrp_set_weight (a copy of the host array into HBM, then the same packer) does: forward state, R_feat
     and the grid-TD gradient bit for bit — also after the first LSTM's input kernel and global_W are set again with other
     values through each route after the first explain.  (Any lrp_set_weight[_dev] drops the derived packs, so the re-set
     goes through finalize / bx_prepare / grad_prepare again like the first set; repack_device into packs that already

@@ -281,8 +281,8 @@ def test_reference_surface_with_resnet():
 
 
 def test_resnet_handle_takes_weights_from_device():
-    """lrp_set_weight_dev on a ResNet handle: the decoder's weights are packed on the device, the encoder units (conv + BN
-    folding is a host packer) are staged once through the host — the handle must end up in the host-set state exactly."""
+    """lrp_set_weight_dev on a ResNet handle: the decoder's weights and the encoder units (conv kernels, BatchNorm vectors)
+    are packed on the device, none of them visits the host — the handle must end up in the host-set state exactly."""
     import torch
     stacks, stem, hw, H, V = ((4, 2), (8, 2)), 8, 32, 32, 50
     rs = np.random.RandomState(19)
