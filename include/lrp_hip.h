@@ -297,7 +297,8 @@ int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias
  * S[n][y+dy][x+dx][co] w+[..], with S given in COMPACT form — sc_dev (NB, Hp, Wp, Cout) fp32 = the value of each window's
  * non-zero, pos_dev (same shape, bytes) = its position 2 dy + dx.  w_hwio_host (3, 3, Cin, Cout) like lrp_op_conv's backward
  * modes; gate_dev / out_dev (NB, 2 Hp, 2 Wp, Cin) fp32.  Split-bf16 arithmetic (three matrix instructions per product).
- * Needs Cin % 256 == 0, Cout % 16 == 0.  reps >= 1 repeats the launch (profiling).  Same values as lrp_op_conv mode 2 with
+ * Needs Cin % 256 == 0, Cout % 16 == 0.  reps in 1 ... 255 repeats the launch (profiling); the bits above are not part
+ * of this interface (the project's own measurement variants, SparseArgs::diag).  Same values as lrp_op_conv mode 2 with
  * LRP_CONV_SPLIT_BF16 on the expanded tensor up to the summation order (tests/test_gpu_conv_sparse.py). */
 int lrp_op_conv_pool_sparse(const float* sc_dev, const unsigned char* pos_dev, const float* w_hwio_host, const float* gate_dev,
                             float* out_dev, int32_t NB, int32_t Hp, int32_t Wp, int32_t Cin, int32_t Cout, int32_t reps, void* stream);

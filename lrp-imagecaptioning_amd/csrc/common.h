@@ -34,15 +34,16 @@ struct Switches {
   int conv_small = 1;       // LRP_CONV_SMALL=0    small grids keep the 128-row tiles (no 64 x 64 tiles)
   int conv_mid = 1;         // LRP_CONV_MID=0      no 128 x 64 tiles for the grids just above the small ones
   int epi_fast = 1;         // LRP_EPI_FAST=0      MUL / MUL_UP2 epilogues always through the general pass loop
-  int up2_pw = 1;           // LRP_UP2_PW=0        pooled boundaries of the pipelined halo kernels through the expanded tensor
+  int up2_pw = 1;           // LRP_UP2_PW=0        pooled boundaries of the pipelined halo kernels through the expanded tensor (dense consumers only:
+                            //                     a boundary with a sparse consumer, LRP_SPARSE_POOL, always gets the compact S_c)
   int tile_order = 1;       // LRP_TILE_ORDER=0    reverse-walk launches in stack order
   int fwd_emit = 1;         // LRP_FWD_EMIT=0      forward: split / absmax / pool passes between the convs
   int fwd_il = 1;           // LRP_FWD_IL=0        dual forward matrix with stacked rows: separate gate pass (decided when lrp_set_weight packs)
   int img_fused = 1;        // LRP_IMG_FUSED=0     image layer as T GEMM + separate stencil kernel (VGG16 and the ResNet stem)
-  int up2_compact = 1;      // LRP_UP2_COMPACT=0   every pooled boundary through the expanded tensor
+  int up2_compact = 1;      // LRP_UP2_COMPACT=0   every pooled boundary with a dense consumer through the expanded tensor
   int img_fold = 1;         // LRP_IMG_FOLD=0      image layer as its own launch
   int pool_fused = 1;       // LRP_POOL_FUSED=0    forward: max-pool + gate + pooled pairs as a pass of their own behind the conv
-  int sparse_pool = 0;      // LRP_SPARSE_POOL=1   pooled boundaries with >= 256 output columns on the 2:4-sparse matrix cores (conv_sparse.h); read by encode and explain
+  int sparse_pool = 1;      // LRP_SPARSE_POOL=0   pooled boundaries with N % 256 == 0 output columns through the dense kernels, not the 2:4-sparse matrix cores (conv_sparse.h); read by encode and explain
   void load() {
     *this = Switches();
     auto rd = [](const char* name, int& v) { if (const char* e = getenv(name)) v = atoi(e); };

@@ -19,10 +19,18 @@
 // ONE class (rows = windows), four weight arrangements exist (4/3 of the dense bytes each), and the grid walks class by class
 // so that the workgroups resident on an XCD share one arrangement in its L2.
 //
-// Tile 256 windows x 256 output channels, 8 waves of 128 x 64 (as the dense 8-wave tile); per 8-channel set three k-steps
-// (own | h + d | v) of 24 smfmacs per wave, two k-steps per barrier.  B: LDS-DMA, four 32 KB stages (two super-steps).
-// A: the tile's windows + a one-window ring, 96 B per window and chunk (pairs in lane order + four planes of index words, the
-// latter precomputed once per image by conv_sparse_index_kernel), copied through registers a step ahead, double-buffered.
+// Tile (large form) 256 windows x 256 output channels, 8 waves of 128 x 64 (as the dense 8-wave tile); per 8-channel set three
+// k-steps (own | h + d | v) of 24 smfmacs per wave, two k-steps per barrier.  B: LDS-DMA, four 32 KB stages (two super-steps).
+// A: the tile's windows + a one-window ring, 96 B per window and chunk (pairs + four planes of index words, the latter
+// precomputed once per image by conv_sparse_index_kernel), by 16 B-per-lane LDS-DMA from chunk-major sources, double-buffered
+// per 8-channel set.  162 016 B of LDS, 225 VGPRs, no spills: one workgroup per CU.
+//
+// Small form (SparseTileSmall; small grids, conv_sparse_small_grid): 64 windows (4 window rows x 14) x 128 columns, 4 waves of
+// 32 x 64, the same loop with 16 KB B stages: 74 976 B of LDS, 98 VGPRs, no spills: two workgroups per CU.  An output element
+// sees the same chain of smfmacs in both forms, so they agree to the bit — and the walk takes these kernels for every token and
+// image count (Encoder::explain chooses by layer shape only), which keeps a picture's heat-map independent of its batch.
+// Default path of the walk for the pooled boundaries with N % 256 == 0 (VGG16: block4_conv3, block3_conv3); LRP_SPARSE_POOL=0
+// returns them to the dense kernels.
 #pragma once
 #include "cnn_kernels.h"
 #include "conv_igemm.h"
@@ -44,21 +52,45 @@ struct SparseArgs {
   int NB, Hp, Wp, C, N;
   int cols_t, m_tiles, n_tiles;
   int out_plain;
-  int diag;                   // measurement only (profiles/sparse_ab.py): bit 0 no epilogue stores
+  int diag;                   // measurement only (profiles/sparse_ab.py): bit 0 no epilogue stores, bit 1 / bit 2 the large / small tile form whatever the grid
 };
 
-constexpr int SP_TW = 14, SP_TH = 18, SP_PITCH = SP_TW + 2;      // tile = 18 stack window rows x 14 window columns = 252 rows
-constexpr int SP_NENT = (SP_TH + 2) * SP_PITCH;                  // resident windows (tile + ring); entry SP_NENT = all-zero
-constexpr int SP_PENT = SP_NENT + 1;                             // entries of a sub-plane (the last one is the all-zero entry)
-constexpr int SP_SUB = SP_PENT * 16;                             // bytes of a sub-plane: 16 B per resident window = [lane half 0: 8 B | half 1: 8 B]
-constexpr int SP_ABUF = 3 * SP_SUB;                              // one 8-channel set: [pairs hi | pairs lo | index words]
-constexpr int SP_SUBPIECES = (SP_PENT + 63) / 64;                // 1 KiB DMA pieces per sub-plane (the last one overlaps the one before)
-constexpr int SP_APIECES = 3 * SP_SUBPIECES;
-constexpr int SP_ASLOTS = (SP_APIECES + 7) / 8;                  // pieces per wave and set
-constexpr int SP_BSTAGE = 32768, SP_NSTAGE = 4;
-constexpr int SP_LDS = SP_NSTAGE * SP_BSTAGE + 2 * SP_ABUF + 128;      // (+ the window row -> image table)
-static_assert(SP_LDS <= 160 * 1024, "LDS");
-static_assert(SP_PENT >= 64, "a DMA piece is 64 windows");
+constexpr int SP_TW = 14, SP_PITCH = SP_TW + 2;                   // window columns of a tile (both forms); pitch of the resident windows
+constexpr int SP_BPACK = 32768, SP_NSTAGE = 4;                    // bytes of one k-step of a 256-column weight tile as packed; LDS stages of B
+
+// A tile form: WMW x WNW waves of MI x NJ 32 x 32 fragments, TH stack window rows x SP_TW window columns (<= BM rows).
+//   large  2 x 4 waves of 4 x 2: 256 windows x 256 columns, 18 x 14 = 252 rows used   (the grids of the batch engine)
+//   small  2 x 2 waves of 1 x 2:  64 windows x 128 columns,  4 x 14 =  56 rows used   (small grids: conv_sparse_small_grid)
+// Both walk the SAME packed weights (a small tile takes its 128 of the 256 columns of every plane of a k-step) and the same A
+// layout, and an output element sees the same chain in both — chunk-major, six k-steps per 16 channels, lo x hi, hi x lo, hi x hi
+// on one accumulator, then gate multiply and split — so the two forms agree to the bit (tests/test_gpu_sparse_default.py).
+template <int WMW_, int WNW_, int MI_, int NJ_, int TH_>
+struct SparseTile {
+  static constexpr int WMW = WMW_, WNW = WNW_, MI = MI_, NJ = NJ_, TH = TH_;
+  static constexpr int NW = WMW * WNW, NT = 64 * NW;               // waves, threads
+  static constexpr int BM = WMW * MI * 32, BN = WNW * NJ * 32;
+  static constexpr int NENT = (TH + 2) * SP_PITCH;                 // resident windows (tile + ring); entry NENT = all-zero
+  static constexpr int PENT = NENT + 1;                            // entries of a sub-plane (the last one is the all-zero entry)
+  static constexpr int SUB = PENT * 16;                            // bytes of a sub-plane: 16 B per resident window = [lane half 0: 8 B | half 1: 8 B]
+  static constexpr int ABUF = 3 * SUB;                             // one 8-channel set: [pairs hi | pairs lo | index words]
+  static constexpr int SUBPIECES = (PENT + 63) / 64;               // 1 KiB DMA pieces per sub-plane (the last one overlaps the one before)
+  static constexpr int APIECES = 3 * SUBPIECES;
+  static constexpr int ASLOTS = (APIECES + NW - 1) / NW;           // pieces per wave and set
+  static constexpr int PLANE = BN * 16;                            // bytes of one of the eight [hi|lo][half][part] planes of a k-step
+  static constexpr int BSTAGE = 8 * PLANE;
+  static constexpr int BPIECES = BSTAGE / 1024 / NW;               // 1 KiB DMA pieces per wave and k-step
+  static constexpr int NSLAB = BM / 64;                            // epilogue slabs of 64 rows
+  static constexpr int EPI_P = 64 * (BN / 8) / NT;                 // epilogue items (row, 8 columns) per thread and slab
+  static constexpr int LDS = SP_NSTAGE * BSTAGE + 2 * ABUF + 128;  // (+ the window row -> image table)
+  static_assert(TH * SP_TW <= BM && BM % 64 == 0 && 256 % BN == 0, "tile");
+  static_assert(BPIECES * NW * 1024 == BSTAGE && EPI_P * NT == 64 * (BN / 8), "pieces");
+  static_assert(SP_NSTAGE * BSTAGE >= 64 * BN * 4, "the epilogue's C slab lies in the B stages");
+  static_assert((TH + 2) * 4 <= 128, "image table");
+  static_assert(LDS <= 160 * 1024, "LDS");
+  static_assert(PENT >= 64, "a DMA piece is 64 windows");
+};
+typedef SparseTile<2, 4, 4, 2, 18> SparseTileLarge;
+typedef SparseTile<2, 2, 1, 2, 4> SparseTileSmall;
 
 // B operand of class q: slot -> tap of the backward conv (the matrix conv_igemm's launch multiplies with: row = output channel
 // ci, k = tap * CPo + co, tap = 3 (dy + 1) + (dx + 1) reads S[y + dy][x + dx]); -1 = dump slot (zero row).
@@ -177,27 +209,31 @@ __global__ __launch_bounds__(256) void conv_sparse_pack_kernel(const float* __re
       lo[e] = (__bf16)(v - (float)hi[e]);
     }
     // element offset (in 16 B units) inside the step's 32 KB: [hl][half][part][col]
-    const size_t sbase = ((((size_t)q * n_tiles + nt) * (C / 16) + chunk) * 6 + step) * (SP_BSTAGE / 16);
+    const size_t sbase = ((((size_t)q * n_tiles + nt) * (C / 16) + chunk) * 6 + step) * (SP_BPACK / 16);
     u32x4* dst = reinterpret_cast<u32x4*>(wsp);
     dst[sbase + ((0 * 2 + half) * 2 + part) * 256 + col] = __builtin_bit_cast(u32x4, hi);
     dst[sbase + ((1 * 2 + half) * 2 + part) * 256 + col] = __builtin_bit_cast(u32x4, lo);
   }
 }
 
-__global__ __launch_bounds__(512, 2) void conv_sparse_kernel(SparseArgs a) {
+template <class TL>
+__global__ __launch_bounds__(TL::NT, 2) void conv_sparse_kernel(SparseArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
-  __shared__ __attribute__((aligned(16))) unsigned char lds[SP_LDS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 2, wn = wave & 3;
+  constexpr int MI = TL::MI, NJ = TL::NJ, NW = TL::NW, NT = TL::NT, BN = TL::BN, TH = TL::TH;
+  constexpr int NENT = TL::NENT, PENT = TL::PENT, SUB = TL::SUB, ABUF = TL::ABUF, BSTAGE = TL::BSTAGE, PLANE = TL::PLANE;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[TL::LDS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / TL::WNW, wn = wave % TL::WNW;
   const int l31 = lane & 31, half = lane >> 5;
   const int per_class = a.m_tiles * a.n_tiles;
   const int q = blockIdx.x / per_class, rem = blockIdx.x - q * per_class;
   const int nt = rem / a.m_tiles, mt = rem - nt * a.m_tiles;
   const int qy = q >> 1, qx = q & 1, sy = qy ? 1 : -1, sx = qx ? 1 : -1;
   const int tyt = mt / a.cols_t, txt = mt - tyt * a.cols_t;
-  const int Y0 = tyt * SP_TH, x0 = txt * SP_TW;            // first stack window row / window column of the tile
+  const int Y0 = tyt * TH, x0 = txt * SP_TW;               // first stack window row / window column of the tile
   const int Hp = a.Hp, Wp = a.Wp, C = a.C, N = a.N, H = 2 * Hp, W = 2 * Wp;
   const int nys = a.NB * Hp;                                // window rows of the stack
-  const int n0 = nt * 256;
+  const int n0 = nt * BN;
+  const int nt256 = n0 >> 8, ncol0 = n0 & 255;             // the packed 256-column weight tile of this tile's columns, its first column in it
   const float inv_Hp = 1.0f / (float)Hp;
   auto divmod = [](int x, int d, float inv, int& qq, int& r) {
     qq = (int)(((float)x + 0.5f) * inv);
@@ -205,7 +241,7 @@ __global__ __launch_bounds__(512, 2) void conv_sparse_kernel(SparseArgs a) {
     if (r < 0) { --qq; r += d; } else if (r >= d) { ++qq; r -= d; }
   };
   unsigned char* Bs = lds;
-  unsigned char* As = lds + SP_NSTAGE * SP_BSTAGE;
+  unsigned char* As = lds + SP_NSTAGE * BSTAGE;
 
   // ---- A in LDS: six sub-planes per buffer — pairs hi, pairs lo, index words, each for set 0 and set 1 — of 16 B per resident
   // window: [lane half 0: 8 B | lane half 1: 8 B].  The 16 lanes LDS serves per cycle of a ds_read_b64 read 16 (nearly) consecutive
@@ -213,35 +249,39 @@ __global__ __launch_bounds__(512, 2) void conv_sparse_kernel(SparseArgs a) {
   // lies in global memory.  Per A fragment: the sub-plane offsets of the four windows its row reads — own, horizontal, vertical,
   // diagonal neighbour; a neighbour outside the image, or in another token, is the all-zero entry.  Fixed for the whole K loop.
   auto chunk0 = [&](int e) { return e * 16 + half * 8; };
-  int e_own[4], e_h[4], e_v[4], e_d[4];
+  int e_own[MI], e_h[MI], e_v[MI], e_d[MI];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int r = (wm * 4 + i) * 32 + l31;
+  for (int i = 0; i < MI; ++i) {
+    const int r = (wm * MI + i) * 32 + l31;
     const int ty = r / SP_TW, tx = r - ty * SP_TW;
     const int Ys = Y0 + ty, wx = x0 + tx;
     int n_, wy;
     divmod(Ys, Hp, inv_Hp, n_, wy);
-    const bool ok = r < SP_TH * SP_TW && Ys < nys && wx < Wp;
+    const bool ok = r < TH * SP_TW && Ys < nys && wx < Wp;
     const bool okh = ok && wx + sx >= 0 && wx + sx < Wp, okv = ok && wy + sy >= 0 && wy + sy < Hp;
     const int e = (ty + 1) * SP_PITCH + tx + 1;
-    e_own[i] = chunk0(ok ? e : SP_NENT);
-    e_h[i] = chunk0(okh ? e + sx : SP_NENT);
-    e_v[i] = chunk0(okv ? e + sy * SP_PITCH : SP_NENT);
-    e_d[i] = chunk0(okh && okv ? e + sy * SP_PITCH + sx : SP_NENT);
+    e_own[i] = chunk0(ok ? e : NENT);
+    e_h[i] = chunk0(okh ? e + sx : NENT);
+    e_v[i] = chunk0(okv ? e + sy * SP_PITCH : NENT);
+    e_d[i] = chunk0(okh && okv ? e + sy * SP_PITCH + sx : NENT);
   }
 
-  // ---- B: LDS-DMA, 4 x 1 KiB per wave and step
+  // ---- B: LDS-DMA, BPIECES x 1 KiB per wave and step.  A stage holds the tile's BN columns of the step's eight planes
+  // [hi|lo][half][part][BN cols] x 16 B; a piece is 64 columns of one plane, contiguous in the packed 256-column tile.
   typedef __attribute__((address_space(3))) void* lptr_t;
   constexpr int RSRC_FLAGS = 0x00020000;
   const int nchunks = C >> 4, nsteps = nchunks * 6;
   const __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(reinterpret_cast<const unsigned char*>(a.wsp) + ((size_t)q * a.n_tiles + nt) * (size_t)nsteps * SP_BSTAGE), 0, nsteps * SP_BSTAGE, RSRC_FLAGS);
+      (void*)(reinterpret_cast<const unsigned char*>(a.wsp) + ((size_t)q * (N >> 8) + nt256) * (size_t)nsteps * SP_BPACK), 0, nsteps * SP_BPACK, RSRC_FLAGS);
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);
   auto fire_b = [&](int step, int stage) {
 #pragma unroll
-    for (int p = 0; p < 4; ++p)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lptr_t)(Bs + stage * SP_BSTAGE + (wave_s * 4 + p) * 1024), 16, lane * 16,
-                                               step * SP_BSTAGE + (wave_s * 4 + p) * 1024, 0, 0);
+    for (int p = 0; p < TL::BPIECES; ++p) {
+      const int pc = wave_s * TL::BPIECES + p;
+      const int plane = pc / (BN / 64), sub = pc - plane * (BN / 64);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lptr_t)(Bs + stage * BSTAGE + pc * 1024), 16, lane * 16,
+                                               step * SP_BPACK + plane * 4096 + (ncol0 + sub * 64) * 16, 0, 0);
+    }
   };
 
   // ---- A staging: by LDS-DMA as well, 16 B per lane: a sub-plane entry IS 16 contiguous bytes of global memory — the hi (or lo)
@@ -250,9 +290,9 @@ __global__ __launch_bounds__(512, 2) void conv_sparse_kernel(SparseArgs a) {
   // block4_conv3, 2.5 ms launch]: through registers, +0.4 ms — hipcc waits vmcnt(0) for a register load that has LDS-DMA behind it
   // on the counter, and a load that misses L2 stalls the step it was issued in, also when only half of the waves stage; one DWORD
   // per lane into a swizzled 32 B-per-window image, +0.9 ms — 123 DMA instructions per chunk.)  A piece = 64 windows of one
-  // sub-plane; wave w moves pieces w, w + 8, ...; windows outside the image and the all-zero entry are out-of-range offsets = zeros.
-  int* imgtab = reinterpret_cast<int*>(As + 2 * SP_ABUF);       // resident window row hy -> image of its token
-  if (tid < SP_TH + 2) {
+  // sub-plane; wave w moves pieces w, w + NW, ...; windows outside the image and the all-zero entry are out-of-range offsets = zeros.
+  int* imgtab = reinterpret_cast<int*>(As + 2 * ABUF);          // resident window row hy -> image of its token
+  if (tid < TH + 2) {
     const int Ys = Y0 - 1 + tid;
     int n_, wy;
     divmod(Ys >= 0 && Ys < nys ? Ys : 0, Hp, inv_Hp, n_, wy);
@@ -266,14 +306,14 @@ __global__ __launch_bounds__(512, 2) void conv_sparse_kernel(SparseArgs a) {
     //  alive across the K loop; recomputed per call it is ~25 VALU instructions)
     int wv = wave_s, ln = lane;
     asm volatile("" : "+s"(wv), "+v"(ln));
-    int pj = wv + 8 * slot;
-    if (pj >= SP_APIECES) pj = SP_APIECES - 1;               // (spare slots repeat the last piece: idempotent)
-    const int pl = pj / SP_SUBPIECES, jp = pj - pl * SP_SUBPIECES;         // sub-plane (hi, lo, index words), piece of it (wave-uniform)
-    const int first = jp * 64 < SP_PENT - 64 ? jp * 64 : SP_PENT - 64;     // (the last piece overlaps its predecessor)
+    int pj = wv + NW * slot;
+    if (pj >= TL::APIECES) pj = TL::APIECES - 1;             // (spare slots repeat the last piece: idempotent)
+    const int pl = pj / TL::SUBPIECES, jp = pj - pl * TL::SUBPIECES;       // sub-plane (hi, lo, index words), piece of it (wave-uniform)
+    const int first = jp * 64 < PENT - 64 ? jp * 64 : PENT - 64;           // (the last piece overlaps its predecessor)
     const int e = first + ln;
     const int hy = e >> 4, hx = e & 15;
     const int Ys = Y0 - 1 + hy, wx = x0 - 1 + hx;
-    const bool ok = e < SP_NENT && Ys >= 0 && Ys < nys && wx >= 0 && wx < Wp;
+    const bool ok = e < NENT && Ys >= 0 && Ys < nys && wx >= 0 && wx < Wp;
     int n_, wy;
     divmod(ok ? Ys : 0, Hp, inv_Hp, n_, wy);
     const int chunk = set8 >> 1, s = set8 & 1;
@@ -284,18 +324,19 @@ __global__ __launch_bounds__(512, 2) void conv_sparse_kernel(SparseArgs a) {
       const int img = imgtab[ok ? hy : 0];
       vo = (((((img * 4 + q) * (C >> 4) + chunk) * Hp + wy) * Wp + wx) << 5) + s * 16;
     }
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(pl < 2 ? rsS : rsI, (lptr_t)(As + abuf * SP_ABUF + pl * SP_SUB + first * 16), 16, ok ? vo : OOB,
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(pl < 2 ? rsS : rsI, (lptr_t)(As + abuf * ABUF + pl * SUB + first * 16), 16, ok ? vo : OOB,
                                              0, 0, 0);
   };
   auto fire_set = [&](int set8, int abuf) {
 #pragma unroll
-    for (int sl = 0; sl < SP_ASLOTS; ++sl) fire_a(sl, set8, abuf);
+    for (int sl = 0; sl < TL::ASLOTS; ++sl) fire_a(sl, set8, abuf);
   };
 
   // ---- K loop.  A set = 8 channels = three k-steps (own | h + d | v); the sources are 16-channel chunks = two sets = six steps,
-  // walked as three SUPER-STEPS of two k-steps with ONE barrier each (48 smfmacs per wave between barriers, like the dense tile):
+  // walked as three SUPER-STEPS of two k-steps with ONE barrier each (48 smfmacs per wave between barriers in the large form, like
+  // the dense tile; 12 in the small one):
   //     super-step 0: (set 0 own, set 0 h+d)    1: (set 0 v, set 1 own)    2: (set 1 h+d, set 1 v)
-  // B: four 32 KB stages = two super-steps; at the top of a super-step the two stages of the NEXT one are requested (into the
+  // B: four stages = two super-steps; at the top of a super-step the two stages of the NEXT one are requested (into the
   // stages the previous one just released).  A: one buffer per set parity; set 0 of the next chunk is requested at the top of
   // super-step 2 (its buffer was last read in super-step 1), set 1 at the top of the next chunk's super-step 0.  Everything
   // requested at the top of a super-step has landed by its end: one s_waitcnt vmcnt(0) per barrier, nothing to count.
@@ -310,15 +351,15 @@ __global__ __launch_bounds__(512, 2) void conv_sparse_kernel(SparseArgs a) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
-  f32x16 acc[4][2];
+  f32x16 acc[MI][NJ];
 #pragma unroll
-  for (int i = 0; i < 4; ++i)
+  for (int i = 0; i < MI; ++i)
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < NJ; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  const int bcol = (wn * 64 + l31) * 16 + half * 8192;
+  const int bcol = (wn * (NJ * 32) + l31) * 16 + half * (2 * PLANE);
   auto expand = [](u32x2 x) -> bf16x8 {                     // [a|b], [c|d] -> (a, 0), (b, 0), (c, 0), (d, 0)
     const u32x4 r = {x[0] & 0xFFFFu, x[0] >> 16, x[1] & 0xFFFFu, x[1] >> 16};
     return __builtin_bit_cast(bf16x8, r);
@@ -330,13 +371,13 @@ __global__ __launch_bounds__(512, 2) void conv_sparse_kernel(SparseArgs a) {
   };
   auto ld8 = [](const unsigned char* p) { return *reinterpret_cast<const u32x2*>(p); };
   auto ld2 = [](const unsigned char* p) { return (unsigned)*reinterpret_cast<const unsigned short*>(p); };
-  struct BF { bf16x16 h[2], l[2]; };
+  struct BF { bf16x16 h[NJ], l[NJ]; };
   auto load_b = [&](BF& b, const unsigned char* Bb) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
+    for (int j = 0; j < NJ; ++j) {
       const unsigned char* bp = Bb + j * 512;                               // [hi|lo][half][part][col] x 16 B
-      const bf16x8 h0 = *reinterpret_cast<const bf16x8*>(bp), h1 = *reinterpret_cast<const bf16x8*>(bp + 4096);
-      const bf16x8 l0 = *reinterpret_cast<const bf16x8*>(bp + 16384), l1 = *reinterpret_cast<const bf16x8*>(bp + 16384 + 4096);
+      const bf16x8 h0 = *reinterpret_cast<const bf16x8*>(bp), h1 = *reinterpret_cast<const bf16x8*>(bp + PLANE);
+      const bf16x8 l0 = *reinterpret_cast<const bf16x8*>(bp + 4 * PLANE), l1 = *reinterpret_cast<const bf16x8*>(bp + 4 * PLANE + PLANE);
       b.h[j] = __builtin_shufflevector(h0, h1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
       b.l[j] = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
     }
@@ -344,10 +385,10 @@ __global__ __launch_bounds__(512, 2) void conv_sparse_kernel(SparseArgs a) {
   // one k-step: group grp (0 own, 1 h + d, 2 v) of the set in buffer Ab against the B fragments b
   auto kstep = [&](const unsigned char* Ab, int grp, const BF& b) {
     const unsigned char* Ah = Ab;
-    const unsigned char* Al = Ab + SP_SUB;
-    const unsigned char* Ai = Ab + 2 * SP_SUB;
+    const unsigned char* Al = Ab + SUB;
+    const unsigned char* Ai = Ab + 2 * SUB;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < MI; ++i) {
       bf16x8 vh, vl;
       int ix;
       if (grp == 1) {
@@ -362,7 +403,7 @@ __global__ __launch_bounds__(512, 2) void conv_sparse_kernel(SparseArgs a) {
         ix = (int)ld2(Ai + oo + (grp == 0 ? 0 : 6));
       }
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
+      for (int j = 0; j < NJ; ++j) {
         acc[i][j] = __builtin_amdgcn_smfmac_f32_32x32x32_bf16(vl, b.h[j], acc[i][j], ix, 0, 0);     // small terms first
         acc[i][j] = __builtin_amdgcn_smfmac_f32_32x32x32_bf16(vh, b.l[j], acc[i][j], ix, 0, 0);
         acc[i][j] = __builtin_amdgcn_smfmac_f32_32x32x32_bf16(vh, b.h[j], acc[i][j], ix, 0, 0);
@@ -386,10 +427,10 @@ __global__ __launch_bounds__(512, 2) void conv_sparse_kernel(SparseArgs a) {
       if (ss == 0 && chunk > 0) fire_set(2 * chunk + 1, 1);
       // (2) the two k-steps; the second one's B fragments are read while the first one's smfmacs run
       BF b0, b1;
-      load_b(b0, Bs + (st0 & 3) * SP_BSTAGE + bcol);
-      load_b(b1, Bs + ((st0 + 1) & 3) * SP_BSTAGE + bcol);
-      kstep(As + (t0 / 3) * SP_ABUF, t0 % 3, b0);
-      kstep(As + (t1 / 3) * SP_ABUF, t1 % 3, b1);
+      load_b(b0, Bs + (st0 & 3) * BSTAGE + bcol);
+      load_b(b1, Bs + ((st0 + 1) & 3) * BSTAGE + bcol);
+      kstep(As + (t0 / 3) * ABUF, t0 % 3, b0);
+      kstep(As + (t1 / 3) * ABUF, t1 % 3, b1);
       // (3) everything requested at the top has landed; everyone is done with this super-step's stages and (ss 1, 2) A buffer.
       // (A bare s_barrier: __syncthreads() adds hipcc's workgroup fence.)
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -397,23 +438,23 @@ __global__ __launch_bounds__(512, 2) void conv_sparse_kernel(SparseArgs a) {
   }
 
   // ---- epilogue: out = acc x gate at the class-q pixel of every window, 64 rows of the tile at a time through LDS
-  float* Cs = reinterpret_cast<float*>(lds);               // 64 x 256 fp32 = 64 KB (the B stages)
+  float* Cs = reinterpret_cast<float*>(lds);               // 64 x BN fp32 (in the B stages)
 #pragma unroll
-  for (int sl = 0; sl < 4; ++sl) {
+  for (int sl = 0; sl < TL::NSLAB; ++sl) {
     // the slab's gate rows first: their latency runs under the C tile's trip through LDS
-    f32x4 g[4][2];
-    bool ok4[4];
-    size_t off4[4];
+    f32x4 g[TL::EPI_P][2];
+    bool ok4[TL::EPI_P];
+    size_t off4[TL::EPI_P];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
-      const int item = tid + p * 512, row = item >> 5, cg = item & 31;
+    for (int p = 0; p < TL::EPI_P; ++p) {
+      const int item = tid + p * NT, row = item / (BN / 8), cg = item % (BN / 8);
       const int R = sl * 64 + row;
       const int ty = R / SP_TW, tx = R - ty * SP_TW;
       const int Ys = Y0 + ty, wx = x0 + tx;
       int n_, wy;
       divmod(Ys < nys ? Ys : 0, Hp, inv_Hp, n_, wy);
       const int col = n0 + cg * 8;
-      ok4[p] = R < SP_TH * SP_TW && Ys < nys && wx < Wp && col < N && !((a.diag & 1) && (row | cg | sl));
+      ok4[p] = R < TH * SP_TW && Ys < nys && wx < Wp && col < N && !((a.diag & 1) && (row | cg | sl));
       const int y = 2 * wy + qy, x = 2 * (wx < Wp ? wx : 0) + qx;
       const int img = a.row2img ? a.row2img[n_] : n_;
       const size_t goff = (((size_t)img * H + y) * W + x) * N + (col < N ? col : 0);
@@ -422,21 +463,24 @@ __global__ __launch_bounds__(512, 2) void conv_sparse_kernel(SparseArgs a) {
       g[p][1] = *reinterpret_cast<const f32x4*>(a.gate + goff + 4);
     }
     if (sl) __syncthreads();
-    if (wm == (sl >> 1)) {
-      float* cw = Cs + (4 * half) * 256 + wn * 64 + l31;
+    // the slab's two 32-row fragments: fragment f of the tile is fragment f % MI of the waves wm = f / MI
+    float* cw = Cs + (4 * half) * BN + wn * (NJ * 32) + l31;
 #pragma unroll
-      for (int ii = 0; ii < 2; ++ii)
+    for (int ii = 0; ii < 2; ++ii) {
+      const int f = 2 * sl + ii;
+      if (wm == f / MI) {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) cw[(ii * 32 + (r & 3) + 8 * (r >> 2)) * 256 + j * 32] = acc[2 * (sl & 1) + ii][j][r];
+          for (int j = 0; j < NJ; ++j) cw[(ii * 32 + (r & 3) + 8 * (r >> 2)) * BN + j * 32] = acc[f % MI][j][r];
+      }
     }
     __syncthreads();
 #pragma unroll
-    for (int p = 0; p < 4; ++p) {
+    for (int p = 0; p < TL::EPI_P; ++p) {
       if (!ok4[p]) continue;
-      const int item = tid + p * 512, row = item >> 5, cg = item & 31;
-      const f32x4 c0 = *reinterpret_cast<const f32x4*>(Cs + row * 256 + cg * 8), c1 = *reinterpret_cast<const f32x4*>(Cs + row * 256 + cg * 8 + 4);
+      const int item = tid + p * NT, row = item / (BN / 8), cg = item % (BN / 8);
+      const f32x4 c0 = *reinterpret_cast<const f32x4*>(Cs + row * BN + cg * 8), c1 = *reinterpret_cast<const f32x4*>(Cs + row * BN + cg * 8 + 4);
       float r[8];
 #pragma unroll
       for (int e = 0; e < 4; ++e) { r[e] = c0[e] * g[p][0][e]; r[4 + e] = c1[e] * g[p][1][e]; }
@@ -453,7 +497,7 @@ __global__ __launch_bounds__(512, 2) void conv_sparse_kernel(SparseArgs a) {
 }
 
 // floats of the packed weights of a layer (all four classes)
-inline size_t conv_sparse_weight_floats(int N, int C) { return (size_t)4 * ((N + 255) / 256) * (C / 16) * 6 * (SP_BSTAGE / 4); }
+inline size_t conv_sparse_weight_floats(int N, int C) { return (size_t)4 * ((N + 255) / 256) * (C / 16) * 6 * (SP_BPACK / 4); }
 inline bool conv_sparse_supports(int N, int C, int Hp, int Wp) { return N % 256 == 0 && C % 16 == 0 && Hp >= 1 && Wp >= 1; }
 
 inline hipError_t conv_sparse_pack(const float* wb_dev, float* wsp_dev, int N, int C, hipStream_t st) {
@@ -477,14 +521,36 @@ inline hipError_t conv_sparse_pairs(const float* sc_dev, float* scp_dev, int NB,
   return hipGetLastError();
 }
 
+// Small grids take the small form (LRP_CONV_SMALL=0 disables, as for the dense tiles): up to CONV_SPARSE_SMALL_BLOCKS
+// workgroups of the LARGE form.  Measured per launch at the operator level (profiles/sparse_forms.py, figures in
+// profiles/r05_sparse_default_ab.txt), large / small form in us by workgroups of the large form:
+//   block4_conv3 (14 x 14, 512):  32: 234 / 104    64: 237 / 179    96: 238 / 208   128: 237 / 272   256: 280 / 483
+//   block3_conv3 (28 x 28, 256):  40: 125 /  59    64: 126 /  94   128: 127 / 143   192: 133 / 200   256: 156 / 255
+// The large form stays flat up to one round of the 256 CUs; the small form grows with its four-fold workgroup count and
+// crosses it between 96 and 128 workgroups on both layers.
+constexpr long CONV_SPARSE_SMALL_BLOCKS = 96L;
+inline long conv_sparse_large_blocks(int NB, int Hp, int Wp, int N) {
+  return 4L * ((NB * Hp + SparseTileLarge::TH - 1) / SparseTileLarge::TH) * ((Wp + SP_TW - 1) / SP_TW) * (N / SparseTileLarge::BN);
+}
+inline bool conv_sparse_small_grid(int NB, int Hp, int Wp, int N) {
+  return conv_small_tile_on() && conv_sparse_large_blocks(NB, Hp, Wp, N) <= CONV_SPARSE_SMALL_BLOCKS;
+}
+
+template <class TL>
+inline hipError_t conv_sparse_launch_tile(SparseArgs a, hipStream_t st) {
+  a.cols_t = (a.Wp + SP_TW - 1) / SP_TW;
+  a.n_tiles = a.N / TL::BN;
+  a.m_tiles = ((a.NB * a.Hp + TL::TH - 1) / TL::TH) * a.cols_t;
+  hipLaunchKernelGGL(conv_sparse_kernel<TL>, dim3(4 * a.m_tiles * a.n_tiles), dim3(TL::NT), 0, st, a);
+  return hipGetLastError();
+}
+
 inline hipError_t conv_sparse_launch(SparseArgs a, hipStream_t st) {
   if (!conv_sparse_supports(a.N, a.C, a.Hp, a.Wp) || !a.sc || !a.idxp || !a.wsp || !a.gate || !a.out) return hipErrorInvalidValue;
   if (a.NB <= 0) return hipSuccess;
-  a.cols_t = (a.Wp + SP_TW - 1) / SP_TW;
-  a.n_tiles = a.N / 256;
-  a.m_tiles = ((a.NB * a.Hp + SP_TH - 1) / SP_TH) * a.cols_t;
-  hipLaunchKernelGGL(conv_sparse_kernel, dim3(4 * a.m_tiles * a.n_tiles), dim3(512), 0, st, a);
-  return hipGetLastError();
+  // (diag bits 1 / 2, measurement only: the large / the small form whatever the grid)
+  const bool small = (a.diag & 4) ? true : (a.diag & 2) ? false : conv_sparse_small_grid(a.NB, a.Hp, a.Wp, a.N);
+  return small ? conv_sparse_launch_tile<SparseTileSmall>(a, st) : conv_sparse_launch_tile<SparseTileLarge>(a, st);
 }
 
 }  // namespace lrp

@@ -781,12 +781,24 @@ struct Encoder {
     // batch invariance bit-exact].
     // LRP_IMG_FOLD=0 disables.
     const bool fold_on = sw().img_fold != 0;
-    // does the launch of layer li write pairs for its consumer li - 1 (see above)?
+    // Does layer lc's launch run on the 2:4-sparse matrix cores (conv_sparse.h)?  Decided by the layer's shape, the precision
+    // and what this encode left — never by the token or image count: sparse and dense sum in different orders, and a picture's
+    // heat-map must not depend on the batch it is explained in.  LRP_SPARSE_POOL=0 disables.
+    auto sparse_consumer = [&](int lc) {
+      if (lc < 1) return false;
+      const ConvLayer& Lc = layers[lc];
+      return sw().sparse_pool && Lc.w_sp.p && Lc.idxp.p && Lc.idx_epoch == encode_epoch && !layers[lc - 1].pool_after && split && !f16 &&
+             walk == 0 && !layer_hook && sp_scp.p != nullptr;
+    };
+    // does the launch of layer li write pairs for its consumer li - 1 (see above)?  A sparse consumer reads nothing else, so its
+    // producer writes them whatever LRP_UP2_COMPACT / LRP_UP2_PW say and whatever tile the producer takes (a plain EPI_MUL
+    // epilogue with the compact gate); those two switches govern the boundaries whose consumer is dense.
     auto writes_pairs = [&](int li) {
       const ConvLayer& P = layers[li - 1];
-      if (!P.pool_after || !up2_on || !split || f16 || walk != 0 || layer_hook || li < 2 || (P.cout & 7) || !P.Gc.p ||
-          P.gc_epoch != encode_epoch)
+      if (!P.pool_after || !split || f16 || walk != 0 || layer_hook || li < 2 || (P.cout & 7) || !P.Gc.p || P.gc_epoch != encode_epoch)
         return false;
+      if (sparse_consumer(li - 1)) return true;
+      if (!up2_on) return false;
       const bool cons_fold = li == 2 && fold_on && img_fused() && !layers[0].pool_after && P.cin == 64 && conv_cinp(P.cout) <= 64 &&
                              layers[0].w_bwd_s.p != nullptr && conv_takes_breg(P.cin, P.H, P.W, P.w_bwd_frag.p != nullptr);
       return cons_fold || conv_takes_pw(P.cin, n, P.H, P.W);
@@ -840,8 +852,7 @@ struct Encoder {
           (void)conv_halo_geom(128, L.H, L.W, fold_tw, fold_th, hr_);
           ca.img_w = P.w_bwd_s.as<float>(); ca.img_part = Snext; ca.out = nullptr;
         }
-        if (pairs_in && sw().sparse_pool && L.w_sp.p && L.idx_epoch == encode_epoch && !P.pool_after && split && !f16 && walk == 0 &&
-            !layer_hook && sp_scp.p) {
+        if (pairs_in && sparse_consumer(li)) {
           // the pooled boundary on the 2:4-sparse matrix cores (conv_sparse.h): S_c re-laid chunk-major, then one launch per class
           const int Hp = L.H / 2, Wp = L.W / 2;
           const size_t n_sets = (size_t)n * Hp * Wp * (L.cout / 8);

@@ -517,7 +517,7 @@ int lrp_op_conv_pool_sparse(const float* sc_dev, const unsigned char* pos_dev, c
     SparseArgs sa{};
     sa.sc = pairs.as<float>(); sa.idxp = idxp.as<unsigned>(); sa.wsp = wsp.as<float>(); sa.gate = gate_dev; sa.out = out_dev;
     sa.NB = NB; sa.Hp = Hp; sa.Wp = Wp; sa.C = Cout; sa.N = Cin; sa.out_plain = 1;
-    sa.diag = reps >> 8;                                   // (measurement variants, profiles/sparse_ab.py; results are then not meaningful)
+    sa.diag = reps >> 8;                                   // (measurement variants, profiles/sparse_ab.py: bit 0 leaves the results meaningless; bits 1 / 2 force a tile form)
     reps &= 255;
     for (int r = 0; r < reps; ++r) LRP_HIP_CHECK(conv_sparse_launch(sa, st));
     LRP_HIP_CHECK(hipStreamSynchronize(st));               // the operand copies are freed on return
