@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define LRP_ABI_VERSION 7
+#define LRP_ABI_VERSION 8
 
 enum {
   LRP_OK = 0,
@@ -450,6 +450,27 @@ int64_t lrp_launch_count(void);
  * thread is inside the library.  A switch that changes how lrp_encode_images lays out its caches takes effect at the next
  * lrp_encode_images.  The reference has no counterpart. */
 int lrp_reload_switches(void);
+
+/* ABI v8.  Which form of the implicit-GEMM convolution kernel a launch would take (csrc/conv_igemm.h conv_plan: the one
+ * function the launcher executes and every caller inside the library asks) — pure host arithmetic on the current switches:
+ * it touches no device, so the tile rules can be tested on a machine without a GPU (tests/test_conv_plan.py).
+ *   epi    LRP_EPI_*: the epilogue;  prec  LRP_OPND_*: the operand format;  terms  7, or 5 / 23 (two-MFMA forms of LRP_OPND_F16X2)
+ *   NB, H, W   the image stack (a 1-tap GEMM: NB rows, H = W = 1);  N output columns from Cin channels;  taps 9 or 1
+ *   split  LRP_EPI_FWD_DUAL: the columns of the first half
+ *   flags  LRP_PLAN_FRAG ... GMASK: facts about the operands;  LRP_PLAN_UP2_SRC / IMG_PART / POOL_GC: what the caller wants the
+ *          launch to carry (compact pool interface, folded image layer, pool fused into the dual forward) — only some forms can
+ *   out11  ok, form (LRP_FORM_*), BM, BN, threads, tw, th, hrows, tpt, m_tiles, n_tiles;  ok = 0: the launch would be refused
+ * A request is carried by a resident-image form or refused, never dropped: IMG_PART with fp32 operands is refused (no kernel
+ * of that format reads it), and under LRP_CONV_HALO=2 a launch with a request is still decided at the default fill of 0.9.
+ * The reference has no counterpart. */
+enum { LRP_EPI_BIAS_RELU = 0, LRP_EPI_BIAS = 1, LRP_EPI_MUL = 2, LRP_EPI_MUL_UP2 = 3, LRP_EPI_FWD_DUAL = 4, LRP_EPI_STORE = 5,
+       LRP_EPI_IMG_STENCIL = 6 };
+enum { LRP_OPND_FP32 = 0, LRP_OPND_BF16X3 = 1, LRP_OPND_F16X2 = 2 };
+enum { LRP_FORM_PLAIN = 0, LRP_FORM_SMALL = 1, LRP_FORM_HALO = 2, LRP_FORM_BREG = 3, LRP_FORM_POOL = 4, LRP_FORM_IMG = 5 };
+enum { LRP_PLAN_FRAG = 1, LRP_PLAN_JOIN = 2, LRP_PLAN_DUAL_IL = 4, LRP_PLAN_GMASK = 8,
+       LRP_PLAN_UP2_SRC = 16, LRP_PLAN_IMG_PART = 32, LRP_PLAN_POOL_GC = 64 };
+int lrp_conv_plan(int32_t epi, int32_t prec, int32_t terms, int32_t NB, int32_t H, int32_t W, int32_t N, int32_t Cin, int32_t taps,
+                  int32_t split, uint32_t flags, int32_t* out11);
 
 const char* lrp_last_error(void);
 int lrp_abi_version(void);

@@ -7,7 +7,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "liblrp_hip.so")
 
-LRP_ABI_VERSION = 7
+LRP_ABI_VERSION = 8
 LRP_OK, LRP_ERR_INVALID, LRP_ERR_STATE, LRP_ERR_HIP, LRP_ERR_NOMEM, LRP_ERR_RANGE, LRP_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 LRP_DEC_ADAPTIVE, LRP_DEC_GRIDTD = 0, 1
 LRP_ENC_VGG, LRP_ENC_RESNET = 0, 1
@@ -15,6 +15,11 @@ LRP_EXPLAIN_SEQUENCE, LRP_EXPLAIN_SINGLE_STEP = 0, 1
 LRP_PREC_FP32, LRP_PREC_BF16X3, LRP_PREC_BF16X3_FAST, LRP_PREC_F16X2 = 0, 1, 2, 3
 LRP_MAX_CONV = 32
 LRP_TRAIN_FP32, LRP_TRAIN_BF16 = 0, 1
+# lrp_conv_plan: epilogues, operand formats, forms, flags
+LRP_EPI_BIAS_RELU, LRP_EPI_BIAS, LRP_EPI_MUL, LRP_EPI_MUL_UP2, LRP_EPI_FWD_DUAL, LRP_EPI_STORE, LRP_EPI_IMG_STENCIL = range(7)
+LRP_OPND_FP32, LRP_OPND_BF16X3, LRP_OPND_F16X2 = 0, 1, 2
+LRP_FORM_PLAIN, LRP_FORM_SMALL, LRP_FORM_HALO, LRP_FORM_BREG, LRP_FORM_POOL, LRP_FORM_IMG = range(6)
+LRP_PLAN_FRAG, LRP_PLAN_JOIN, LRP_PLAN_DUAL_IL, LRP_PLAN_GMASK, LRP_PLAN_UP2_SRC, LRP_PLAN_IMG_PART, LRP_PLAN_POOL_GC = 1, 2, 4, 8, 16, 32, 64
 
 
 class LrpConfig(C.Structure):
@@ -88,6 +93,7 @@ SYMBOLS = {
     "lrp_last_error": (C.c_char_p, []),
     "lrp_abi_version": (C.c_int, []),
     "lrp_launch_count": (C.c_int64, []),
+    "lrp_conv_plan": (C.c_int, [C.c_int32] * 10 + [C.c_uint32, C.POINTER(C.c_int32)]),
 }
 
 _lib = None

@@ -1761,25 +1761,53 @@ inline ConvTile conv_pick_tile(int N) {
 inline int conv_npad(int N) { ConvTile t = conv_pick_tile(N); return (N + t.BN - 1) / t.BN * t.BN; }
 inline int conv_cinp(int Cin) { return (Cin + 31) / 32 * 32; }
 
-// small grids take 64 x 64 tiles (conv_launch_epi): LRP_CONV_SMALL=0 disables; they are used up to a 128-row grid of 128 tiles
-// (4x as many 64 x 64 workgroups = the 512 that are resident at once; beyond that a second round of small tiles costs more
-// than the large tiles' idle CUs [MI355X, one image, 252 large tiles: 115 -> 145 us])
+// ---- the launch plan: ONE host function decides which form of conv_igemm_kernel a convolution runs on ----
+// conv_launch_epi executes the plan; a caller that has to know what a launch will do BEFORE it launches (Encoder::explain:
+// may the producer write the compact pool interface, may the image layer ride on this launch; Encoder::encode: may the pool be
+// fused) asks conv_plan about that launch with its request set and reads `ok`.  lrp_conv_plan (include/lrp_hip.h) exposes it.
+enum ConvForm {
+  FORM_PLAIN = 0,   // A and B staged per k-step, 128 x 128 / 128 x 64 / 128 x 32 / 8-wave 256 x 256
+  FORM_SMALL = 1,   // small grids: 64 x 64 tiles, CONV_SMALL_NS-stage k pipeline
+  FORM_HALO = 2,    // resident image (3x3, split operands), 128 x 128 / 128 x 64 / 8-wave 256 x 256
+  FORM_BREG = 3,    // resident image + weights in registers (N <= 64), 128 x 64
+  FORM_POOL = 4,    // FORM_HALO 128 x 128 with tiles of even height and width: the 2x2 max-pool in the dual forward's epilogue
+  FORM_IMG = 5      // EPI_IMG_STENCIL: 16 x 16 pixel patches
+};
+// one launch, as far as the decision depends on it.  The three requests are what the caller wants this launch to CARRY
+// (ConvArgs::up2_src, img_part, pool_gc): only some forms can, and a request never changes the tile — it is refused instead.
+struct ConvAsk {
+  int epi = EPI_MUL, prec = PREC_FP32, terms = 7;
+  bool gmask = false;
+  int NB = 0, H = 0, W = 0, N = 0, Cin = 0, taps = 9;
+  bool frag = false;         // a fragment-major copy of the weights exists (ConvArgs::wpk_frag)
+  bool join = false;         // ConvArgs::join
+  bool dual_il = false;
+  int split = 0;
+  bool up2_src = false, img_part = false, pool_gc = false;
+};
+struct ConvPlan {
+  bool ok;                   // false: conv_launch refuses this launch (hipErrorInvalidValue)
+  int form, BM, BN, threads;
+  int M, m_tiles, n_tiles, tw, th, hrows, cols_t, nyh, tpt, epi_generic;   // what the launcher writes into ConvArgs
+};
+
 constexpr int CONV_SMALL_NS = 4;                       // LDS stages of the 64 x 64 tile's k pipeline (4 x 16 KB: two workgroups per CU... see NS)
-inline bool conv_small_tile_on() { return sw().conv_small != 0; }
-constexpr long conv_small_tile_blocks() { return 128L; }
+// Small grids take 64 x 64 tiles up to a 128-row grid of 128 tiles (4x as many 64 x 64 workgroups = the 512 that are resident
+// at once; beyond that a second round of small tiles costs more than the large tiles' idle CUs [MI355X, one image, 252 large
+// tiles: 115 -> 145 us]); up to twice that, 128 x 64 tiles.
+constexpr long CONV_SMALL_BLOCKS = 128;
 
-// halo-resident variant: switch LRP_CONV_HALO = 0 never, 1 (default) when a tile shape fills >= 90 % of the M tile,
-// 2 always (tests: ragged tile shapes)
-inline int conv_halo_mode() { return sw().conv_halo; }
-// best (tw, th, pitch) for a BM-row tile on an H x W image stack; returns the fraction of MFMA rows doing real work
-inline float conv_halo_geom(int BM, int H, int W, int& tw, int& th, int& hrows) {
+// best (tw, th, pitch) for a BM-row tile on an H x W image stack; returns the fraction of MFMA rows doing real work.
+// even: an even number of rows and columns (ConvArgs::pool_gc: 2x2 windows never straddle two tiles)
+inline float conv_halo_geom(int BM, int H, int W, bool even, int& tw, int& th, int& hrows) {
   const int avail = conv_halo_rows(BM) / HALO_PITCH;   // resident image rows that fit
+  const int step = even ? 2 : 1;
   float best = 0.f;
-  for (int c = 1; c <= HALO_PITCH - 2 && c <= W; ++c) {
+  for (int c = step; c <= HALO_PITCH - 2 && c <= W; c += step) {
     // th stack rows cross at most ceil((th-1)/H) image boundaries, each costing one separator row
-    int t = BM / c;
-    while (t > 0 && t + 2 + (t - 1 + H - 1) / H > avail) --t;
-    if (t < 1) continue;
+    int t = even ? (BM / c) & ~1 : BM / c;
+    while (t > 0 && t + 2 + (t - 1 + H - 1) / H > avail) t -= step;
+    if (t < step) continue;
     const int cols = (W + c - 1) / c;
     const float u = (float)(t * c) / (float)BM * (float)W / (float)(cols * c);
     if (u > best + 1e-6f) { best = u; tw = c; th = t; hrows = t + 2 + (t - 1 + H - 1) / H; }
@@ -1787,59 +1815,137 @@ inline float conv_halo_geom(int BM, int H, int W, int& tw, int& th, int& hrows) 
   return best;
 }
 
-// ... with an even number of rows and columns (ConvArgs::pool_gc: 2x2 windows never straddle two tiles)
-inline float conv_halo_geom_even(int BM, int H, int W, int& tw, int& th, int& hrows) {
-  const int avail = conv_halo_rows(BM) / HALO_PITCH;
-  float best = 0.f;
-  for (int c = 2; c <= HALO_PITCH - 2 && c <= W; c += 2) {
-    int t = (BM / c) & ~1;
-    while (t > 0 && t + 2 + (t - 1 + H - 1) / H > avail) t -= 2;
-    if (t < 2) continue;
-    const int cols = (W + c - 1) / c;
-    const float u = (float)(t * c) / (float)BM * (float)W / (float)(cols * c);
-    if (u > best + 1e-6f) { best = u; tw = c; th = t; hrows = t + 2 + (t - 1 + H - 1) / H; }
+// Can a reverse launch through a layer (N output columns from Cin channels at H x W) read the compact pool interface at SOME
+// token count?  The part of conv_plan's answer to an up2_src request that depends on neither the grid nor a switch:
+// Encoder::init sizes the compact gates by it.  (N <= 32 never reaches a kernel that reads them; those are the tiny test nets.)
+inline bool conv_compact_shape(int N, int Cin, int H, int W) {
+  if ((Cin & 7) || (H & 1) || (W & 1)) return false;
+  return conv_pick_tile(N).BN == 128 /* pipelined halo tiles */ || (N <= 64 && conv_cinp(Cin) <= 64) /* weights in registers */;
+}
+
+inline ConvPlan conv_plan(const ConvAsk& q, const Switches& s = sw()) {
+  const ConvPlan refused{};
+  ConvPlan p{};
+  const int epi = q.epi, prec = q.prec;
+  const bool mul = epi == EPI_MUL || epi == EPI_MUL_UP2, fwd = epi == EPI_BIAS || epi == EPI_BIAS_RELU || epi == EPI_FWD_DUAL;
+  const bool asked = q.up2_src || q.img_part || q.pool_gc;
+  // the (epilogue, operand format, terms) that exist: prec = PREC_BF16X3 for the reverse-walk epilogues (MUL, MUL_UP2, STORE,
+  // the image stencil) and the forward Z+ / late activation convs (BIAS, BIAS_RELU), always three-term; PREC_F16X2 see TERMS.
+  // This is the list; conv_launch below holds one instantiation per combination accepted here (a template needs its case
+  // written out) and refuses whatever has none: a new combination is stated here and gets its case there.
+  if (epi < EPI_BIAS_RELU || epi > EPI_IMG_STENCIL || prec < PREC_FP32 || prec > PREC_F16X2) return refused;
+  if (prec == PREC_BF16X3 && (q.terms != 7 || epi == EPI_FWD_DUAL)) return refused;
+  if (prec == PREC_F16X2 && (q.terms == 23 ? !(epi == EPI_FWD_DUAL && q.dual_il) : q.terms == 5 ? !mul : epi == EPI_STORE)) return refused;
+  if (q.gmask && (epi != EPI_MUL || prec != PREC_FP32 || asked)) return refused;         // byte-mask gates: exact fp32 EPI_MUL only
+  if (prec != PREC_FP32 && (q.Cin & 7)) return refused;
+  p.M = q.NB * q.H * q.W;
+  p.epi_generic = s.epi_fast ? 0 : 1;
+  if (epi == EPI_IMG_STENCIL) {
+    if (q.taps != 1 || q.N > 64 || (q.Cin & 3) || asked) return refused;
+    p.ok = true; p.form = FORM_IMG; p.BM = 256; p.BN = 64; p.threads = 256;
+    p.n_tiles = 1;
+    p.m_tiles = q.NB * ((q.W + IMG_TILE - 1) / IMG_TILE) * ((q.H + IMG_TILE - 1) / IMG_TILE);
+    return p;
   }
-  return best;
-}
+  if (mul && (q.N & (prec != PREC_FP32 ? 7 : 3))) return refused;                         // 16 B (fp32) / 32 B (split8) epilogue
+  if ((epi == EPI_BIAS || epi == EPI_BIAS_RELU) && (q.N & 3)) return refused;
+  if (epi == EPI_FWD_DUAL && ((q.split & 3) || (q.dual_il && ((q.split & 31) || q.N != 2 * q.split)))) return refused;
 
-// Would a 3x3 MUL launch with N = n_out, input H x W, take the weights-in-registers kernel?  (Encoder::explain asks before it
-// chooses the compact pool interface, which only that kernel reads.)
-inline bool conv_takes_breg(int n_out, int H, int W, bool have_frag) {
-  if (!sw().conv_breg || !have_frag || conv_halo_mode() <= 0 || n_out > 64 || n_out <= 32) return false;
-  int tw, th, hrows;
-  return conv_halo_geom(128, H, W, tw, th, hrows) >= 0.9f;
-}
+  // ---- the tile ----
+  const long rows = (long)q.NB * q.H * q.W;
+  ConvTile t = conv_pick_tile(q.N);
+  // fp32, few M rows (the per-image forward at batch 32): 128 x 128 tiles leave CUs idle; halve the tile
+  // [MI355X] encode of 32 images 14.06 -> 13.54 ms with the threshold at 2200 blocks (~4 waves of 512 slots)
+  if (prec == PREC_FP32 && t.BN == 128 && (q.N % 64) == 0 && ((rows + 127) / 128) * ((q.N + 127) / 128) < 2200) t = {128, 64};
+  // split operands: the 8-wave 256 x 256 tile (blocked accumulation — the fp16-pair forward — does not fit it).  Measured: a
+  // 256 x 128 tile loses to two 128 x 128 blocks per CU, and one 8-wave block per CU is only worth it when the grid still
+  // fills the chip ~1.5 times over.  The tail of a ResNet identity block (1 tap, K = f channels, three full-width streams
+  // per output element in the epilogue) is bound by those streams, not by staging: two 128 x 128 workgroups per CU overlap
+  // one's epilogue with the other's K loop  [MI355X, ResNet-101 conv4_x: 354 -> 316 us per launch; config 4 -0.9 ms per walk]
+  if (prec != PREC_FP32 && (q.terms == 7 || prec == PREC_F16X2) && !(prec == PREC_F16X2 && fwd) && q.N >= 256 && (q.N % 256) == 0 &&
+      !(epi == EPI_MUL && q.taps == 1 && q.join) && ((rows + 255) / 256) * (q.N / 256) >= 400)
+    t = {256, 256};
+  p.m_tiles = (p.M + t.BM - 1) / t.BM;
+  p.n_tiles = (q.N + t.BN - 1) / t.BN;
+  if (p.M <= 0 || q.N <= 0) {                            // nothing to launch
+    p.ok = true; p.form = FORM_PLAIN; p.BM = t.BM; p.BN = t.BN; p.threads = t.BM == 256 ? 512 : 256;
+    return p;
+  }
+  const long grid = (long)p.m_tiles * p.n_tiles;
+  // the resident-image kernels exist for the split formats' 3x3 MUL and forward epilogues.  LRP_CONV_HALO=2 puts ragged tile
+  // shapes on them (tests); a launch that carries a request is decided at the default fill
+  const int mode = prec != PREC_FP32 && (mul || fwd) && q.taps == 9 ? s.conv_halo : 0;
+  auto resident = [&](bool even, float fill) {
+    int tw = 0, th = 0, hrows = 0;
+    const float u = conv_halo_geom(t.BM, q.H, q.W, even, tw, th, hrows);
+    if (!(u >= fill || (mode == 2 && !asked && u > 0.f))) return false;
+    p.tw = tw; p.th = th; p.hrows = hrows;
+    p.nyh = q.NB * q.H;
+    p.cols_t = (q.W + tw - 1) / tw;
+    p.m_tiles = ((p.nyh + th - 1) / th) * p.cols_t;
+    return true;
+  };
+  auto done = [&](int form) {
+    p.ok = true; p.form = form; p.BM = t.BM; p.BN = t.BN; p.threads = t.BM == 256 ? 512 : 256;
+    return p;
+  };
 
-// The 8-wave tile width of a split-format reverse-walk launch: 256 (256 x 256 tile) or 0.
-// ONE rule for conv_launch_epi and conv_takes_pw.
-inline int conv_wide_tile(int n_out, long mrows) {
-  if (n_out < 256 || (n_out % 256) != 0) return 0;      // measured: a 256 x 128 tile loses to two 128 x 128 blocks per CU
-  // one 8-wave block per CU: only worth it when the grid still fills the chip ~1.5 times over
-  return ((mrows + 255) / 256) * (n_out / 256) < 400 ? 0 : 256;
-}
-
-// Can the interleaved dual forward of a layer with `cout` channels on NB images of H x W pool in its epilogue
-// (ConvArgs::pool_gc)?  The launch must reach the 128 x 128 resident-image kernel: mirrors conv_launch_epi; LRP_POOL_FUSED=0 disables.
-inline bool conv_takes_pool_fused(int cout, int NB, int H, int W) {
-  if (!sw().pool_fused || conv_halo_mode() <= 0 || (H & 1) || (W & 1) || (cout & 31) || conv_pick_tile(2 * cout).BN != 128) return false;
-  const long blocks = (((long)NB * H * W + 127) / 128) * ((2 * cout + 127) / 128);
-  if (conv_small_tile_on() && blocks <= 2 * conv_small_tile_blocks()) return false;      // (small / mid-size grids: other tiles)
-  int tw, th, hrows;
-  return conv_halo_geom_even(128, H, W, tw, th, hrows) >= 0.8f;
-}
-
-// Would a split-bf16 3x3 MUL launch (N = n_out columns, NB x H x W rows) take a pipelined halo kernel — 128 x 128 or the 8-wave
-// 256 x 256 — and fit its loader of the compact pool interface (two items per thread and channel chunk)?  Mirrors the tile
-// choice of conv_launch_epi; LRP_UP2_PW=0 disables.
-inline bool conv_takes_pw(int n_out, int NB, int H, int W) {
-  if (!sw().up2_pw || conv_halo_mode() <= 0 || conv_pick_tile(n_out).BN != 128 || (H & 1) || (W & 1)) return false;
-  const long mrows = (long)NB * H * W;
-  int BM = 128, threads = 256;
-  if (conv_wide_tile(n_out, mrows) == 256) { BM = 256; threads = 512; }
-  if (BM == 128 && conv_small_tile_on() && ((mrows + 127) / 128) * ((n_out + 127) / 128) <= conv_small_tile_blocks()) return false;
-  int tw, th, hrows;
-  if (conv_halo_geom(BM, H, W, tw, th, hrows) < 0.9f) return false;
-  return hrows * ((tw + 2) / 2 + 1) * 4 <= 2 * threads;
+  if (q.pool_gc) {
+    // pool fused into the dual forward's epilogue: 128 x 128 resident-image tiles of even height and width or nothing (a grid
+    // small enough for the small / mid-size tiles keeps its pool pass); LRP_POOL_FUSED=0 disables
+    if (epi != EPI_FWD_DUAL || prec != PREC_F16X2 || !q.dual_il || q.up2_src || q.img_part || !s.pool_fused || mode <= 0 ||
+        (q.H & 1) || (q.W & 1) || t.BM != 128 || t.BN != 128 || (s.conv_small && grid <= 2 * CONV_SMALL_BLOCKS) || !resident(true, 0.8f))
+      return refused;
+    return done(FORM_POOL);
+  }
+  // N <= 64: resident image + weights in registers, no barrier per tap (LRP_CONV_BREG=0 disables).  128-row tiles, whatever
+  // the grid: 256-row tiles, 8 waves, one block per CU, halve the weight traffic per pixel but lose more to the single block
+  // per CU  [MI355X: block1_conv2 bwd 4.19 ms vs 3.83 ms with these 128-row tiles, 3 blocks per CU]
+  if (mul && mode > 0 && s.conv_breg && t.BN == 64 && q.frag && resident(false, 0.9f)) {
+    if (q.img_part) {                                    // image layer folded in: tiles laid out per token (none straddles two tokens)
+      if (prec != PREC_BF16X3 || epi != EPI_MUL || q.N != 64) return refused;
+      p.tpt = (q.H + p.th - 1) / p.th;
+      p.hrows = p.th + 2;                                // (no separator row inside a tile's own rows)
+      p.m_tiles = q.NB * p.tpt * p.cols_t;
+    }
+    // (the compact pool interface needs the window loader: per-token tiles = the folded launch)
+    if (q.up2_src && (!q.img_part || !conv_compact_shape(q.N, q.Cin, q.H, q.W))) return refused;
+    return done(FORM_BREG);
+  }
+  if (q.img_part) return refused;                        // the folded image layer exists for the weights-in-registers kernel only
+  // Small grids (one image, a handful of words: explain_image.py's own call): with 128-row tiles the 14 x 14 / 28 x 28
+  // layers are 16-250 workgroups, each walking K = 2304-4608 alone — the launch takes as long as ONE tile's K loop
+  // [MI355X, B = 1, T = 10: 115-119 us per block4 / block5 launch, forward and backward].  64 x 64 tiles (4 waves of
+  // 32 x 32) put 4x the workgroups on the chip and a k-step costs a quarter of the MFMAs.  Every output element still sees
+  // the same chain of MFMAs in the same k order, so the results are bit-identical to the large tiles (batch invariance).
+  // LRP_CONV_SMALL=0 disables.
+  const bool small = s.conv_small && t.BM == 128 && t.BN >= 64 && grid <= CONV_SMALL_BLOCKS;
+  if (q.up2_src) {
+    // compact pool interface into a pipelined halo kernel (128 x 128 or 8-wave; LRP_UP2_PW=0 disables): the grid must be
+    // one that takes such a kernel without the request, and the loader must fit (below)
+    if (!mul || prec != PREC_BF16X3 || !s.up2_pw || mode <= 0 || t.BN < 128 || small || !conv_compact_shape(q.N, q.Cin, q.H, q.W))
+      return refused;
+  } else if (small) {
+    t = {64, 64};
+    p.m_tiles = (p.M + 63) / 64;
+    p.n_tiles = (q.N + 63) / 64;
+    return done(FORM_SMALL);
+  } else if (s.conv_mid && s.conv_small && t.BM == 128 && t.BN == 128 && (q.N % 64) == 0 && grid <= 2 * CONV_SMALL_BLOCKS) {
+    // In between (at most one large tile per CU, but too many for the 64 x 64 tiles to stay resident): 128 x 64 tiles put two
+    // workgroups on a CU and halve a k-step — same chains, same bits [MI355X, one image, ten words: block4's walk launches
+    // (252 large tiles) 115 -> ~80 us, explain 1.62 -> 1.51 ms].  LRP_CONV_MID=0 disables.
+    t = {128, 64};
+    p.n_tiles = (q.N + 63) / 64;
+  }
+  // N = 64 tiles (TM x TN = 2 x 1 per wave) lose with the resident image: 2 instead of 3 blocks per CU and the
+  // per-tap address work is spread over half as many MFMAs  [MI355X: block1_conv2 bwd 4.5 ms vs 5.2 ms]
+  if (mode > 0 && (t.BN >= 128 || (mode == 2 && t.BN >= 64)) && resident(false, 0.9f)) {
+    // the loader of the compact pool interface handles two items per thread and channel chunk
+    if (q.up2_src && p.hrows * ((p.tw + 2) / 2 + 1) * 4 > 2 * (t.BM == 256 ? 512 : 256)) return refused;
+    return done(FORM_HALO);
+  }
+  if (asked) return refused;                             // only the resident-image kernels read the compact pool interface
+  return done(FORM_PLAIN);
 }
 
 // device table of a.order for this call's token -> image map (see TileOrder); nullptr when the stack order is as good
@@ -1906,174 +2012,91 @@ inline const int* conv_tile_order(const ConvArgs& a, hipStream_t st) {
   return o.dev;
 }
 
+// the question conv_plan is asked about the launch of `a`
+inline ConvAsk conv_ask(int epi, int prec, int terms, bool gmask, const ConvArgs& a) {
+  ConvAsk q;
+  q.epi = epi; q.prec = prec; q.terms = terms; q.gmask = gmask;
+  q.NB = a.NB; q.H = a.H; q.W = a.W; q.N = a.N; q.Cin = a.Cin; q.taps = a.taps;
+  q.frag = a.wpk_frag != nullptr; q.join = a.join != nullptr; q.dual_il = a.dual_il != 0; q.split = a.split;
+  q.up2_src = a.up2_src != nullptr; q.img_part = a.img_part != nullptr; q.pool_gc = a.pool_gc != nullptr;
+  return q;
+}
+inline void conv_apply_plan(const ConvPlan& p, ConvArgs& a) {
+  a.M = p.M; a.m_tiles = p.m_tiles; a.n_tiles = p.n_tiles;
+  a.tw = p.tw; a.th = p.th; a.hrows = p.hrows; a.cols_t = p.cols_t; a.nyh = p.nyh; a.tpt = p.tpt;
+  a.epi_generic = p.epi_generic;
+}
+
 // EPI_IMG_STENCIL: NB = image slots (tokens), H x W = the image; in = S_1 (NB, H, W, Cin); N = 54 <= 64
 template <int PREC>
 inline hipError_t conv_launch_img(ConvArgs a, hipStream_t st) {
-  if (a.taps != 1 || a.N > 64 || !a.ximg || (a.Cin & (PREC != PREC_FP32 ? 7 : 3))) return hipErrorInvalidValue;
-  if (PREC == PREC_F16X2 && !a.tok_fac) return hipErrorInvalidValue;
+  if (!a.ximg || (PREC == PREC_F16X2 && !a.tok_fac)) return hipErrorInvalidValue;
+  const ConvPlan p = conv_plan(conv_ask(EPI_IMG_STENCIL, PREC, 7, false, a));
+  if (!p.ok) return hipErrorInvalidValue;
   if (a.NB <= 0) return hipSuccess;
-  a.M = a.NB * a.H * a.W;
+  conv_apply_plan(p, a);
   a.tiles_x = (a.W + IMG_TILE - 1) / IMG_TILE;
   a.tiles_y = (a.H + IMG_TILE - 1) / IMG_TILE;
-  a.n_tiles = 1;
-  a.m_tiles = a.NB * a.tiles_x * a.tiles_y;
-  hipLaunchKernelGGL((conv_igemm_kernel<4, 1, 2, 2, EPI_IMG_STENCIL, PREC>), dim3(a.m_tiles), dim3(256), 0, st, a);
+  hipLaunchKernelGGL((conv_igemm_kernel<4, 1, 2, 2, EPI_IMG_STENCIL, PREC>), dim3(a.m_tiles), dim3(p.threads), 0, st, a);
   return hipGetLastError();
 }
 
 template <int EPI, int PREC, int TERMS = 7, bool GMASK = false>
 inline hipError_t conv_launch_epi(ConvArgs a, hipStream_t st) {
   static_assert(!GMASK || (EPI == EPI_MUL && PREC == PREC_FP32), "byte-mask gates: exact fp32 EPI_MUL only");
-  if (GMASK && (a.out2s || a.gate_none || a.up2_src || a.img_part || a.pool_gc)) return hipErrorInvalidValue;
-  constexpr int need = PREC != PREC_FP32 ? 7 : 3;                                     // 16 B (fp32) / 32 B (split8) epilogue
-  if (PREC == PREC_F16X2 && (EPI == EPI_MUL || EPI == EPI_MUL_UP2) && (!a.tok_fac || !a.tok_max_out || a.out_plain)) return hipErrorInvalidValue;
-  if (PREC == PREC_F16X2 && (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_FWD_DUAL) && !a.in_unscale) return hipErrorInvalidValue;
-  if ((EPI == EPI_MUL || EPI == EPI_MUL_UP2) && (a.N & need)) return hipErrorInvalidValue;
-  if ((EPI == EPI_BIAS || EPI == EPI_BIAS_RELU) && (a.N & 3)) return hipErrorInvalidValue;
-  if (PREC != PREC_FP32 && (a.Cin & 7)) return hipErrorInvalidValue;
-  if (EPI == EPI_FWD_DUAL && (a.split & 3)) return hipErrorInvalidValue;
-  if (EPI == EPI_FWD_DUAL && a.dual_il && ((a.split & 31) || a.N != 2 * a.split)) return hipErrorInvalidValue;
-  ConvTile t = conv_pick_tile(a.N);
-  if (PREC == PREC_FP32 && t.BN == 128 && (a.N % 64) == 0) {
-    // few M rows (the per-image forward at batch 32): 128 x 128 tiles leave CUs idle; halve the tile
-    // [MI355X] encode of 32 images 14.06 -> 13.54 ms with the threshold at 2200 blocks (~4 waves of 512 slots)
-    constexpr int thr = 2200;
-    const long blocks = (((long)a.NB * a.H * a.W + 127) / 128) * ((a.N + 127) / 128);
-    if (blocks < thr) t = {128, 64};
-  }
-  int wide = 0;
-  if (PREC != PREC_FP32 && (TERMS == 7 || PREC == PREC_F16X2) &&
-      !(PREC == PREC_F16X2 && (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_FWD_DUAL)) &&
-      a.N >= 128 && (a.N % 128) == 0) {   // (blocked accumulation does not fit the 8-wave tile)
-    wide = conv_wide_tile(a.N, (long)a.NB * a.H * a.W);
-    // the tail of a ResNet identity block (1 tap, K = f channels, three full-width streams per output element in the
-    // epilogue) is bound by those streams, not by staging: two 128 x 128 workgroups per CU overlap one's epilogue with the
-    // other's K loop  [MI355X, ResNet-101 conv4_x: 354 -> 316 us per launch; config 4 -0.9 ms per walk]
-    if (EPI == EPI_MUL && a.taps == 1 && a.join) wide = 0;
-    if (wide) t = {256, wide};
-  }
-  a.M = a.NB * a.H * a.W;
-  a.m_tiles = (a.M + t.BM - 1) / t.BM;
-  a.n_tiles = (a.N + t.BN - 1) / t.BN;
-  if (a.M <= 0 || a.N <= 0) return hipSuccess;
-  a.epi_generic = sw().epi_fast ? 0 : 1;
-  // Small grids (one image, a handful of words: explain_image.py's own call): with 128-row tiles the 14 x 14 / 28 x 28
-  // layers are 16-250 workgroups, each walking K = 2304-4608 alone — the launch takes as long as ONE tile's K loop
-  // [MI355X, B = 1, T = 10: 115-119 us per block4 / block5 launch, forward and backward].  64 x 64 tiles (4 waves of
-  // 32 x 32) put 4x the workgroups on the chip and a k-step costs a quarter of the MFMAs.  Every output element still sees
-  // the same chain of MFMAs in the same k order, so the results are bit-identical to the large tiles (batch invariance).
-  const bool small_tile = conv_small_tile_on() && t.BM == 128 && t.BN >= 64 && (long)a.m_tiles * a.n_tiles <= conv_small_tile_blocks() &&
-                          !a.up2_src && !a.img_part;
-  // In between (at most one large tile per CU, but too many for the 64 x 64 tiles to stay resident): 128 x 64 tiles put two
-  // workgroups on a CU and halve a k-step — same chains, same bits [MI355X, one image, ten words: block4's walk launches
-  // (252 large tiles) 115 -> ~80 us, explain 1.62 -> 1.51 ms].  LRP_CONV_MID=0 disables.
-  const bool mid_on = sw().conv_mid != 0;
-  if (mid_on && !small_tile && conv_small_tile_on() && t.BM == 128 && t.BN == 128 && (a.N % 64) == 0 && !a.up2_src && !a.img_part &&
-      (long)a.m_tiles * a.n_tiles <= 2 * conv_small_tile_blocks()) {
-    t = {128, 64};
-    a.n_tiles = (a.N + 63) / 64;
-  }
-
-  if constexpr (PREC != PREC_FP32 && (EPI == EPI_MUL || EPI == EPI_MUL_UP2 || EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_FWD_DUAL)) {
-    const int mode = conv_halo_mode();
-    if (a.pool_gc) {
-      // pool fused into the dual forward's epilogue: 128 x 128 resident-image tiles of even height and width or nothing
-      if (!(EPI == EPI_FWD_DUAL && PREC == PREC_F16X2) || !a.dual_il || !a.pairs_out || !a.pool_pos || a.taps != 9 || small_tile ||
-          t.BM != 128 || t.BN != 128 || !conv_takes_pool_fused(a.split, a.NB, a.H, a.W))
-        return hipErrorInvalidValue;
-      (void)conv_halo_geom_even(128, a.H, a.W, a.tw, a.th, a.hrows);
-      a.nyh = a.NB * a.H;
-      a.cols_t = (a.W + a.tw - 1) / a.tw;
-      a.m_tiles = ((a.nyh + a.th - 1) / a.th) * a.cols_t;
-      hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, true, false, TERMS>), dim3(a.m_tiles * a.n_tiles), dim3(256), 0, st, a);
-      return hipGetLastError();
-    }
-    // N = 64 tiles (TM x TN = 2 x 1 per wave) lose with the resident image: 2 instead of 3 blocks per CU and the
-    // per-tap address work is spread over half as many MFMAs  [MI355X: block1_conv2 bwd 4.5 ms vs 5.2 ms]
-    if constexpr (EPI == EPI_MUL || EPI == EPI_MUL_UP2) {
-      // N <= 64: resident image + weights in registers, no barrier per tap (LRP_CONV_BREG=0 disables)
-      if (a.taps == 9 && mode > 0 && sw().conv_breg && t.BN == 64 && a.n_tiles == 1 && a.wpk_frag) {
-        // (256-row tiles, 8 waves, one block per CU, halve the weight traffic per pixel but lose more to the single
-        // block per CU  [MI355X: block1_conv2 bwd 4.19 ms vs 3.83 ms with these 128-row tiles, 3 blocks per CU])
-        const float u = conv_halo_geom(t.BM, a.H, a.W, a.tw, a.th, a.hrows);
-        if (u >= 0.9f || (mode == 2 && u > 0.f)) {
-          a.nyh = a.NB * a.H;
-          a.cols_t = (a.W + a.tw - 1) / a.tw;
-          a.m_tiles = ((a.nyh + a.th - 1) / a.th) * a.cols_t;
-          if (a.img_part) {                              // image layer folded in: tiles laid out per token (none straddles two tokens)
-            if (PREC != PREC_BF16X3 || EPI != EPI_MUL || a.N != 64 || !a.img_w) return hipErrorInvalidValue;
-            a.tpt = (a.H + a.th - 1) / a.th;
-            a.hrows = a.th + 2;                          // (no separator row inside a tile's own rows)
-            a.m_tiles = a.NB * a.tpt * a.cols_t;
-          }
-          a.tile_map = conv_tile_order(a, st);
-          // (the compact pool interface needs the window loader: per-token tiles = the folded launch)
-          if (a.up2_src && (PREC != PREC_BF16X3 || a.CinP > 64 || !a.up2_pairs || !a.up2_gpos || !a.img_part || (a.H & 1) || (a.W & 1)))
-            return hipErrorInvalidValue;
-          hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 1, EPI, PREC, true, true, TERMS>), dim3(a.m_tiles), dim3(256), 0, st, a);
+  constexpr bool MUL = EPI == EPI_MUL || EPI == EPI_MUL_UP2, FWD = EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_FWD_DUAL;
+  // 1. what only the pointers tell
+  if (GMASK && (a.out2s || a.gate_none)) return hipErrorInvalidValue;
+  if (PREC == PREC_F16X2 && MUL && (!a.tok_fac || !a.tok_max_out || a.out_plain)) return hipErrorInvalidValue;
+  if (PREC == PREC_F16X2 && FWD && !a.in_unscale) return hipErrorInvalidValue;
+  // 2. the plan
+  const ConvPlan p = conv_plan(conv_ask(EPI, PREC, TERMS, GMASK, a));
+  if (!p.ok) return hipErrorInvalidValue;
+  if (p.M <= 0 || a.N <= 0) return hipSuccess;
+  // (what a request needs besides the form: only a launch that does something is held to it)
+  if (a.pool_gc && (!a.pairs_out || !a.pool_pos)) return hipErrorInvalidValue;
+  if (a.img_part && !a.img_w) return hipErrorInvalidValue;
+  if (a.up2_src && (!a.up2_pairs || !a.up2_gpos)) return hipErrorInvalidValue;
+  conv_apply_plan(p, a);
+  // 3. its kernel
+  const dim3 grid(p.m_tiles * p.n_tiles), block(p.threads);
+  if constexpr (PREC != PREC_FP32 && (MUL || FWD)) {
+    if (p.form == FORM_BREG || p.form == FORM_HALO || p.form == FORM_POOL) {
+      if constexpr (MUL) {
+        a.tile_map = conv_tile_order(a, st);
+        if (p.form == FORM_BREG) {
+          hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 1, EPI, PREC, true, true, TERMS>), grid, block, 0, st, a);
           return hipGetLastError();
         }
       }
-    }
-    if (a.img_part) return hipErrorInvalidValue;     // the folded image layer exists for the weights-in-registers kernel only
-    if (a.up2_src) {
-      // compact pool interface into a pipelined halo kernel (ConvArgs::up2_pairs): the launch must reach one (conv_takes_pw)
-      if (!((EPI == EPI_MUL || EPI == EPI_MUL_UP2) && PREC == PREC_BF16X3 && TERMS == 7) || !a.up2_pairs || !a.up2_gpos || a.taps != 9 ||
-          !conv_takes_pw(a.N, a.NB, a.H, a.W))
-        return hipErrorInvalidValue;
-    }
-    if (small_tile) {
-      a.m_tiles = (a.M + 63) / 64;
-      a.n_tiles = (a.N + 63) / 64;
-      hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 1, 1, EPI, PREC, false, false, TERMS, CONV_SMALL_NS>), dim3(a.m_tiles * a.n_tiles), dim3(256), 0, st, a);
+      if (p.BM == 256)
+        hipLaunchKernelGGL((conv_igemm_kernel<2, 4, 4, 2, EPI, PREC, true, false, TERMS>), grid, block, 0, st, a);
+      else if (p.BN == 128)
+        hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, true, false, TERMS>), grid, block, 0, st, a);
+      else
+        hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 1, EPI, PREC, true, false, TERMS>), grid, block, 0, st, a);
       return hipGetLastError();
     }
-    if (a.taps == 9 && mode > 0 && (t.BN >= 128 || (mode == 2 && t.BN >= 64))) {
-      const float u = conv_halo_geom(t.BM, a.H, a.W, a.tw, a.th, a.hrows);
-      if (u >= 0.9f || (mode == 2 && u > 0.f)) {
-        a.nyh = a.NB * a.H;
-        a.cols_t = (a.W + a.tw - 1) / a.tw;
-        a.m_tiles = ((a.nyh + a.th - 1) / a.th) * a.cols_t;
-        if constexpr (EPI == EPI_MUL || EPI == EPI_MUL_UP2) a.tile_map = conv_tile_order(a, st);
-        const dim3 hgrid(a.m_tiles * a.n_tiles);
-        if (wide == 256)
-          hipLaunchKernelGGL((conv_igemm_kernel<2, 4, 4, 2, EPI, PREC, true, false, TERMS>), hgrid, dim3(512), 0, st, a);
-        else if (t.BN == 128)
-          hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, true, false, TERMS>), hgrid, dim3(256), 0, st, a);
-        else
-          hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 1, EPI, PREC, true, false, TERMS>), hgrid, dim3(256), 0, st, a);
-        return hipGetLastError();
-      }
-    }
   }
-  // Only the resident-image kernels above read the compact pool interface.  A launch that carries it and got here (halo
-  // switch off, halo geometry below 0.9 for the tile actually chosen, fp32 operands) would run a kernel that ignores up2_src and
-  // reads a.in as a dense tensor: refuse instead of producing wrong heat-maps silently.
-  if (a.up2_src || a.pool_gc) return hipErrorInvalidValue;
-  if (small_tile) {
-    a.m_tiles = (a.M + 63) / 64;
-    a.n_tiles = (a.N + 63) / 64;
-    hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 1, 1, EPI, PREC, false, false, TERMS, CONV_SMALL_NS, GMASK>), dim3(a.m_tiles * a.n_tiles), dim3(256), 0, st, a);
-    return hipGetLastError();
-  }
-  const dim3 grid(a.m_tiles * a.n_tiles);
   if constexpr (PREC != PREC_FP32) {
-    if (wide == 256) {
-      hipLaunchKernelGGL((conv_igemm_kernel<2, 4, 4, 2, EPI, PREC, false, false, TERMS>), grid, dim3(512), 0, st, a);
+    if (p.BM == 256) {
+      hipLaunchKernelGGL((conv_igemm_kernel<2, 4, 4, 2, EPI, PREC, false, false, TERMS>), grid, block, 0, st, a);
       return hipGetLastError();
     }
   }
-  const dim3 block(256);
-  if (t.BN == 128)
+  if (p.form == FORM_SMALL)
+    hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 1, 1, EPI, PREC, false, false, TERMS, CONV_SMALL_NS, GMASK>), grid, block, 0, st, a);
+  else if (p.BN == 128)
     hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, false, false, TERMS, 2, GMASK>), grid, block, 0, st, a);
-  else if (t.BN == 64)
+  else if (p.BN == 64)
     hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 1, EPI, PREC, false, false, TERMS, 2, GMASK>), grid, block, 0, st, a);
   else
     hipLaunchKernelGGL((conv_igemm_kernel<4, 1, 1, 1, EPI, PREC, false, false, TERMS, 2, GMASK>), grid, block, 0, st, a);
   return hipGetLastError();
 }
 
-// prec = PREC_BF16X3 exists for the reverse-walk epilogues (MUL, MUL_UP2, STORE) and the forward Z+ conv (BIAS)
+// The instantiation table: one case per (epilogue, operand format, terms) that conv_plan accepts — which combinations exist and
+// why is stated there, at the head of conv_plan — and hipErrorInvalidValue for everything else.
 inline hipError_t conv_launch(int epi, const ConvArgs& a, hipStream_t st, int prec = PREC_FP32, int terms = 7) {
   if (prec == PREC_BF16X3 && terms != 7) return hipErrorInvalidValue;   // (the two-pass three-way split forward product of rounds 1-2 is gone)
   if (prec == PREC_F16X2) {                            // reverse walk of the VGG encoder only

@@ -533,7 +533,7 @@ inline long conv_sparse_large_blocks(int NB, int Hp, int Wp, int N) {
   return 4L * ((NB * Hp + SparseTileLarge::TH - 1) / SparseTileLarge::TH) * ((Wp + SP_TW - 1) / SP_TW) * (N / SparseTileLarge::BN);
 }
 inline bool conv_sparse_small_grid(int NB, int Hp, int Wp, int N) {
-  return conv_small_tile_on() && conv_sparse_large_blocks(NB, Hp, Wp, N) <= CONV_SPARSE_SMALL_BLOCKS;
+  return sw().conv_small != 0 && conv_sparse_large_blocks(NB, Hp, Wp, N) <= CONV_SPARSE_SMALL_BLOCKS;
 }
 
 template <class TL>

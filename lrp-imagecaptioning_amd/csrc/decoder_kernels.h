@@ -1,7 +1,7 @@
 // decoder_kernels.h — HIP kernels of the decoder half (adaptive attention):
 //   forward replay   _forward_beam_search            E:370-436   (E: = models/explainers.py)
 //   per-token LRP    _explain_lstm_single_word_sequence  E:537-666, rule E:156-165
-// Precision mirrors the reference: float32 LSTM / attention chain, float64 from
+// Precision follows the reference: float32 LSTM / attention chain, float64 from
 // `context` on and for every LRP accumulator, float32 stores into r_V / R_feat.
 // These kernels are HBM/L2- or latency-bound (GEMV-like); the design rules that
 // matter are coalesced weight streams (weights pre-transposed so that lanes run

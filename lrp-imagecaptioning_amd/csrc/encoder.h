@@ -177,9 +177,8 @@ struct Encoder {
     LRP_TRY(s1.alloc(NT * max_tok_act * sizeof(float), total));
     for (size_t i = 0; i + 1 < layers.size(); ++i) LRP_TRY(layers[i].G.alloc(B * layers[i].act_elems() * sizeof(float), total));
     for (size_t i = 0; i + 1 < layers.size(); ++i) {
-      ConvLayer& Lc = layers[i];                         // (the condition of Encoder::explain for the compact interface, weights aside)
-      if (Lc.pool_after && !(Lc.cout & 7) && !(Lc.H & 1) && !(Lc.W & 1) &&
-          ((Lc.cin <= 64 && conv_cinp(Lc.cout) <= 64) || conv_pick_tile(Lc.cin).BN == 128)) {
+      ConvLayer& Lc = layers[i];                         // compact gate: where the layer's reverse launch can read it at some token count
+      if (Lc.pool_after && conv_compact_shape(Lc.cin, Lc.cout, Lc.H, Lc.W)) {
         LRP_TRY(Lc.Gc.alloc(B * Lc.act_elems() / 4 * sizeof(float), total));
         LRP_TRY(Lc.Gpos.alloc(B * Lc.act_elems() / 4, total));
       }
@@ -485,13 +484,6 @@ struct Encoder {
             LRP_HIP_CHECK(hipGetLastError());
           }
           if (emit_conv) { cd.pairs_out = pout; cd.pairs_scale = oscale_of(li); cd.skip_out = keep_acts ? 0 : 1; }
-          // pooled layer: max-pool, arg-max gate (compact form) and the pooled pairs in THIS conv's epilogue — a_l and Z+_l at
-          // full resolution are neither written nor read back (round 4; the pass it replaces: pool_gate_split_kernel below)
-          const bool pool_fused = emit_pool && !keep_acts && cd.dual_il && L.Gc.p && L.Gpos.p && conv_takes_pool_fused(L.cout, B, L.H, L.W);
-          if (pool_fused) {
-            cd.pool_gc = L.Gc.as<float>(); cd.pool_pos = L.Gpos.as<unsigned char>(); cd.pairs_out = pout; cd.pairs_scale = oscale_of(li);
-            cd.out = nullptr; cd.out2 = nullptr;
-          }
           // The denominators Z+_l of the layers whose reverse launch is two-term (explain(): up to the last pool, >= 576
           // products) are computed two-term as well — with the SAME rounded weights hi(w+) the walk multiplies with.
           // [MI355X: parity at the bench configuration 5.5e-6 -> 4.4e-6, 6 seeds median 4.2e-6 -> 3.3e-6: gate and
@@ -499,6 +491,16 @@ struct Encoder {
           // two-term Z+ in EVERY layer: 1.0e-4, the top block again.]
           int fterms = 7;
           if (cd.dual_il && walk_f16 && two_term((int)li)) fterms = 23;
+          // pooled layer: max-pool, arg-max gate (compact form) and the pooled pairs in THIS conv's epilogue — a_l and Z+_l at
+          // full resolution are neither written nor read back (round 4; the pass it replaces: pool_gate_split_kernel below) —
+          // where the launch takes the form that can (conv_plan)
+          ConvAsk ask = conv_ask(EPI_FWD_DUAL, PREC_F16X2, fterms, false, cd);
+          ask.pool_gc = true;
+          const bool pool_fused = emit_pool && !keep_acts && L.Gc.p && L.Gpos.p && conv_plan(ask).ok;
+          if (pool_fused) {
+            cd.pool_gc = L.Gc.as<float>(); cd.pool_pos = L.Gpos.as<unsigned char>(); cd.pairs_out = pout; cd.pairs_scale = oscale_of(li);
+            cd.out = nullptr; cd.out2 = nullptr;
+          }
           LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, cd, st, PREC_F16X2, fterms));
           if (top) break;
           in_pairs = emit_conv || emit_pool;
@@ -768,19 +770,30 @@ struct Encoder {
     // multiplies with the consumer's COMPACT gate (one value per window and channel, at the producer's resolution) and writes
     // S_c as bf16 pairs at POOLED resolution; the consumer builds its resident image from the pairs and the position bytes:
     // the 4x-expanded, 75 %-zero tensor is neither written nor read.  Only two consumers can: the folded weights-in-registers
-    // launch (VGG16 block1_conv2: per-token tiles, its window loader) and the pipelined halo kernels (conv_takes_pw); both
-    // need a compact gate from this encode.  Every other pooled boundary takes EPI_MUL_UP2 (the expanded tensor; same fp32
+    // launch (VGG16 block1_conv2: per-token tiles, its window loader) and the pipelined halo kernels; conv_plan says whether the
+    // consumer's launch is one of them, and both need a compact gate from this encode.  Every other pooled boundary takes EPI_MUL_UP2 (the expanded tensor; same fp32
     // product, same pairs).  LRP_UP2_COMPACT=0 disables.
     const bool up2_on = sw().up2_compact != 0;
     bool pairs_in = false;                               // S (the current layer's input) is S_c as pairs at pooled resolution
-    int fold_tw = 0, fold_th = 0;
     // Image layer folded into the epilogue of the layer above it (ConvArgs::img_part): S_1 — 4.1 GB written, 4.5 GB read at
     // the bench configuration — never goes to memory; per tile 160 positions x 6 partial sums do, and a streaming pass
     // adds them up in a fixed order [MI355X, same box: block1_conv2 4.25 -> 4.57 ms (it now also runs the tap GEMM and the
     // in-tile stencil), image layer 1.29 -> 0.18 ms, walk 26.1-26.3 -> 25.3 ms; heat-maps unchanged to fp32 round-off,
     // batch invariance bit-exact].
     // LRP_IMG_FOLD=0 disables.
-    const bool fold_on = sw().img_fold != 0;
+    const bool fold_on = sw().img_fold != 0 && split && !f16 && walk == 0 && !layer_hook && img_fused() && layers.size() > 1 &&
+                         !layers[0].pool_after && layers[1].cin == 64 && layers[0].w_bwd_s.p != nullptr;
+    // conv_plan's answer for the dense launch through layer lc (lc >= 1) of this walk: with the folded image layer on it where
+    // that is wanted, and reading the compact pool interface or not
+    auto walk_plan = [&](int lc, bool up2) {
+      const ConvLayer& Lc = layers[lc];
+      ConvAsk q;
+      q.epi = layers[lc - 1].pool_after ? EPI_MUL_UP2 : EPI_MUL; q.prec = run_prec;      // (asked for the split-bf16 walk only)
+      q.NB = n; q.H = Lc.H; q.W = Lc.W; q.N = Lc.cin; q.Cin = Lc.cout; q.taps = 9;
+      q.frag = split && walk == 0 && Lc.w_bwd_frag.p != nullptr;
+      q.up2_src = up2; q.img_part = lc == 1 && fold_on;
+      return conv_plan(q);
+    };
     // Does layer lc's launch run on the 2:4-sparse matrix cores (conv_sparse.h)?  Decided by the layer's shape, the precision
     // and what this encode left — never by the token or image count: sparse and dense sum in different orders, and a picture's
     // heat-map must not depend on the batch it is explained in.  LRP_SPARSE_POOL=0 disables.
@@ -798,10 +811,7 @@ struct Encoder {
       if (!P.pool_after || !split || f16 || walk != 0 || layer_hook || li < 2 || (P.cout & 7) || !P.Gc.p || P.gc_epoch != encode_epoch)
         return false;
       if (sparse_consumer(li - 1)) return true;
-      if (!up2_on) return false;
-      const bool cons_fold = li == 2 && fold_on && img_fused() && !layers[0].pool_after && P.cin == 64 && conv_cinp(P.cout) <= 64 &&
-                             layers[0].w_bwd_s.p != nullptr && conv_takes_breg(P.cin, P.H, P.W, P.w_bwd_frag.p != nullptr);
-      return cons_fold || conv_takes_pw(P.cin, n, P.H, P.W);
+      return up2_on && walk_plan(li - 1, true).ok;
     };
     for (int li = (int)layers.size() - 1; li >= 0; --li) {
       const ConvLayer& L = layers[li];
@@ -810,6 +820,7 @@ struct Encoder {
         if (li == 0) return LRP_OK;
       }
       ConvArgs ca{};
+      ConvPlan fold{};                                   // (li == 1: the plan of the launch that carries the image layer)
       ca.in = S; ca.NB = n; ca.H = L.H; ca.W = L.W; ca.Cin = L.cout; ca.CinP = conv_cinp(L.cout); ca.taps = 9;
       if (hook_split) {
         const size_t n8 = (size_t)n * L.act_elems() / 8;
@@ -846,10 +857,7 @@ struct Encoder {
         ca.N = L.cin; ca.aux = P.G.as<float>(); ca.out = Snext;
         epi = P.pool_after ? EPI_MUL_UP2 : EPI_MUL;
         // the image layer rides on this launch's epilogue?
-        if (li == 1 && fold_on && split && !f16 && walk == 0 && !layer_hook && img_fused() && !P.pool_after && L.cin == 64 &&
-            P.w_bwd_s.p && conv_takes_breg(L.cin, L.H, L.W, L.w_bwd_frag.p != nullptr)) {
-          int hr_ = 0;
-          (void)conv_halo_geom(128, L.H, L.W, fold_tw, fold_th, hr_);
+        if (li == 1 && fold_on && (fold = walk_plan(1, pairs_in)).ok) {
           ca.img_w = P.w_bwd_s.as<float>(); ca.img_part = Snext; ca.out = nullptr;
         }
         if (pairs_in && sparse_consumer(li)) {
@@ -911,7 +919,7 @@ struct Encoder {
           (void)hipEventRecord(p2.e0, st);
         }
         hipLaunchKernelGGL(img_partial_sum_kernel, dim3(stream_grid((size_t)n * L0.H * L0.W)), dim3(256), 0, st, ca.img_part, images.as<float>(),
-                           row2img_dev, R_img_dev, n, L0.H, L0.W, fold_th, fold_tw, (L0.W + fold_tw - 1) / fold_tw, 0);
+                           row2img_dev, R_img_dev, n, L0.H, L0.W, fold.th, fold.tw, fold.cols_t, 0);
         LRP_HIP_CHECK(hipGetLastError());
         if (profile) {
           (void)hipEventRecord(p2.e1, st);

@@ -110,6 +110,27 @@ int lrp_reload_switches(void) {
   return guarded([&]() -> int { lrp::sw().load(); return LRP_OK; });
 }
 
+int lrp_conv_plan(int32_t epi, int32_t prec, int32_t terms, int32_t NB, int32_t H, int32_t W, int32_t N, int32_t Cin, int32_t taps,
+                  int32_t split, uint32_t flags, int32_t* out11) {
+  return guarded([&]() -> int {
+    static_assert(LRP_EPI_BIAS_RELU == lrp::EPI_BIAS_RELU && LRP_EPI_BIAS == lrp::EPI_BIAS && LRP_EPI_MUL == lrp::EPI_MUL &&
+                  LRP_EPI_MUL_UP2 == lrp::EPI_MUL_UP2 && LRP_EPI_FWD_DUAL == lrp::EPI_FWD_DUAL && LRP_EPI_STORE == lrp::EPI_STORE &&
+                  LRP_EPI_IMG_STENCIL == lrp::EPI_IMG_STENCIL, "lrp_hip.h LRP_EPI_*");
+    static_assert(LRP_OPND_FP32 == lrp::PREC_FP32 && LRP_OPND_BF16X3 == lrp::PREC_BF16X3 && LRP_OPND_F16X2 == lrp::PREC_F16X2, "lrp_hip.h LRP_OPND_*");
+    static_assert(LRP_FORM_PLAIN == lrp::FORM_PLAIN && LRP_FORM_SMALL == lrp::FORM_SMALL && LRP_FORM_HALO == lrp::FORM_HALO &&
+                  LRP_FORM_BREG == lrp::FORM_BREG && LRP_FORM_POOL == lrp::FORM_POOL && LRP_FORM_IMG == lrp::FORM_IMG, "lrp_hip.h LRP_FORM_*");
+    if (!out11) return fail(LRP_ERR_INVALID, "null argument");
+    lrp::ConvAsk q;
+    q.epi = epi; q.prec = prec; q.terms = terms; q.NB = NB; q.H = H; q.W = W; q.N = N; q.Cin = Cin; q.taps = taps; q.split = split;
+    q.frag = flags & LRP_PLAN_FRAG; q.join = flags & LRP_PLAN_JOIN; q.dual_il = flags & LRP_PLAN_DUAL_IL; q.gmask = flags & LRP_PLAN_GMASK;
+    q.up2_src = flags & LRP_PLAN_UP2_SRC; q.img_part = flags & LRP_PLAN_IMG_PART; q.pool_gc = flags & LRP_PLAN_POOL_GC;
+    const lrp::ConvPlan p = lrp::conv_plan(q);
+    const int v[11] = {p.ok ? 1 : 0, p.form, p.BM, p.BN, p.threads, p.tw, p.th, p.hrows, p.tpt, p.m_tiles, p.n_tiles};
+    for (int i = 0; i < 11; ++i) out11[i] = v[i];
+    return LRP_OK;
+  });
+}
+
 int64_t lrp_launch_count(void) { return (int64_t)lrp::g_launch_count.load(std::memory_order_relaxed); }
 const char* lrp_last_error(void) { return last_error_ref().c_str(); }
 

@@ -628,6 +628,17 @@ class switches(object):
         return False
 
 
+PLAN_FIELDS = ("ok", "form", "BM", "BN", "threads", "tw", "th", "hrows", "tpt", "m_tiles", "n_tiles")
+
+
+def conv_plan(epi, prec, NB, H, W, N, Cin, taps=9, terms=7, split=0, flags=0):
+    """lrp_conv_plan (ABI v8): the form of the implicit-GEMM convolution kernel this launch would take under the current
+    switches, as a dict of PLAN_FIELDS.  Host arithmetic only: works without a GPU."""
+    out = (C.c_int32 * len(PLAN_FIELDS))()
+    _capi.check(_capi.load().lrp_conv_plan(epi, prec, terms, NB, H, W, N, Cin, taps, split, flags, out))
+    return dict(zip(PLAN_FIELDS, out))
+
+
 def preprocess_images(rgb_u8, size=(224, 224)):
     """models/preprocessors.py:38-53 on the device: (NB, H0, W0, 3) uint8 RGB tensor -> (NB, H, W, 3) float32 BGR,
     mean-subtracted, nearest-neighbour resized like keras `load_img(target_size=size)`."""

@@ -2,16 +2,18 @@
 
 VERDICT r3: "~40 LRP_* switches, six swept once, none under a committed test — each untested switch is a dead or wrong code
 path waiting for a user."  Round 4 deleted 21 of them (their code paths with them where nothing else reaches those) and
-kept 17 as measurement knobs / fall-backs (+ round 4's LRP_POOL_FUSED and the opt-in LRP_SPARSE_POOL); three more went later
+kept 17 as measurement knobs / fall-backs (+ round 4's LRP_POOL_FUSED and LRP_SPARSE_POOL, opt-in then, the default now); three more went later
 (LRP_CONV_TILE, LRP_DEC_BATCHED, LRP_DEC_MFMA_FWD: their alternatives were code nothing else reached), then the two that
-selected the fp32 forms of the compact pool interface, which leaves 13 + the opt-in.  This file runs each of the kept ones — alone, at the setting that leaves the default path — through the engine at a size where the kernels of the benchmark configuration engage and compares every
+selected the fp32 forms of the compact pool interface, which leaves 14.  This file runs each of the kept ones — alone, at the setting that leaves the default path — through the engine at a size where the kernels of the benchmark configuration engage and compares every
 heat-map with the default run:
 
   * VGG16 at full size, 8 images x 9 words = 72 heat-maps per call: block1 takes the weights-in-registers kernel with the
     folded image layer and the compact pool interface, block2 the 128 x 128 halo tiles with the in-loop window loader,
-    block3 / block4 the 8-wave 256 x 256 tiles (>= 400 workgroups), block5 128 x 128 tiles; the tile-order table is built
+    block3 / block4 the 8-wave 256 x 256 tiles (>= 400 workgroups) except their first convs (half as many output columns:
+    128 x 128), block5 128 x 128 tiles, block4_conv3 / block3_conv3 the 2:4-sparse kernels; the tile-order table is built
     for 9 tokens per image;
   * the same network on ONE image x 3 words (a B = 1 handle): the small-grid 64 x 64 / 128 x 64 tiles.
+Which dense form each of these launches takes is asserted, without a GPU, by tests/test_conv_plan.py.
 
 Expectation per switch: `0.0` = bit-identical (the alternative computes every element through the same chain of operations:
 DESIGN 4.1 says so for the tile shapes, the tile order, the compact pool interfaces and the epilogue pass loop), otherwise a
@@ -43,7 +45,7 @@ CASES = [
     ("LRP_FWD_EMIT", 0, 2e-5, 2e-5),
     ("LRP_FWD_IL", 0, 2e-5, 2e-5),
     ("LRP_POOL_FUSED", 0, 0.0, 0.0),        # max-pool / gate / pooled pairs as a pass behind the conv: the same arithmetic, bit for bit
-    ("LRP_SPARSE_POOL", 1, 1e-6, 1e-6),    # opt-in: block4_conv3 / block3_conv3 on the 2:4-sparse matrix cores (other summation order)
+    ("LRP_SPARSE_POOL", 0, 1e-6, 1e-6),    # block4_conv3 / block3_conv3 on the dense kernels, not the 2:4-sparse matrix cores (other summation order)
 ]
 
 
