@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define LRP_ABI_VERSION 8
+#define LRP_ABI_VERSION 9
 
 enum {
   LRP_OK = 0,
@@ -367,6 +367,27 @@ int lrp_eval_attention_maps(const float* att_dev, const double* M_dev, double* m
                             int32_t upscale, void* stream);
 int lrp_eval_box_scores(const void* maps_dev, int32_t fp64, int32_t n, int32_t h, int32_t w, const int32_t* boxes_dev,
                         const double* thr_dev, int32_t nb, int32_t K, double* scores_dev, void* stream);
+
+/* ABI v9.  Grad-CAM on the device and the word examination (explainers.py:939-949 / :1643-1653 with the product of :934;
+ * exaimin_word.py:95-102, :131-160, :488-489): handle-free operators like lrp_eval_*, device pointers, no synchronisation,
+ * one workgroup per unit with fixed-order fp64 reductions.
+ * lrp_op_gradcam: n (image, word) units.  feat_dev (B, L, D) float32 (what lrp_get_features returns), img_idx_dev (n) int32
+ *   on the device, grads_dev (n, L, D) float32 (lrp_decoder_gradient), M_dev (S, g) float64 (lrp_eval_expand_matrix on the
+ *   device), L = g * g, S = g * upscale.  Per unit in fp64: w_c = mean_l grads[l][c], A[l] = sum_c feat[img][l][c] w_c,
+ *   cam = max(M A M^T, 0), cam /= max|cam| + 1e-6 -> cam_dev (n, S, S) float64 (a cam that is nowhere positive: exact zeros).
+ *   gb_dev (n, S * S, C) float32 (lrp_cnn_walk with LRP_WALK_GUIDED_BACKPROP) and out_dev (n, S * S, C) float64 =
+ *   (double)gb * cam, or NULL for both: the cam only.  g <= 16, S <= 448, D a multiple of 8 up to 4096, C <= 64.  A unit whose
+ *   image index is outside [0, B) reads nothing and comes out as NaN.
+ * lrp_exam_maps: R_img_dev (n, H, W, C) float32 (fp64 = 0) or float64 (fp64 = 1) -> per pixel the channel mean in flipped
+ *   channel order in the input dtype (no sign, no rectification), pool = 0 none / 1 max / 2 ave over k x k blocks (k divides H
+ *   and W; max exact, ave accumulated in fp64), x / absmax (zeros when absmax == 0; no (x + 1) / 2 branch), |x| if absval.
+ *   maps_dev: (n, H, W) in the input dtype, or (n, H/k, W/k) float64 when pooled; means_dev (n) float64, the fixed-order
+ *   fp64 mean of that map.  Either output may be NULL, not both. */
+int lrp_op_gradcam(const float* feat_dev, const int32_t* img_idx_dev, const float* grads_dev, const double* M_dev,
+                   const float* gb_dev, double* cam_dev, double* out_dev, int32_t n, int32_t B, int32_t g, int32_t upscale,
+                   int32_t D, int32_t C, void* stream);
+int lrp_exam_maps(const void* R_img_dev, int32_t fp64, int32_t n, int32_t H, int32_t W, int32_t C, int32_t pool, int32_t k,
+                  int32_t absval, void* maps_dev, double* means_dev, void* stream);
 
 /* Operator-level entries of the fine-tune step's dense products (unit tests at real layer sizes; csrc/train_gemm.h).
  * lrp_op_sgemm: C (+)= op(A) op(B) on the fp32 matrix cores, row-major with leading dimensions;

@@ -17,6 +17,7 @@
 #include "decoder.h"
 #include "encoder.h"
 #include "eval_kernels.h"
+#include "gradcam_kernels.h"
 #include "resnet_encoder.h"
 #include "rules_kernels.h"
 #include "score_kernels.h"
@@ -882,6 +883,51 @@ int lrp_eval_box_scores(const void* maps_dev, int32_t fp64, int32_t n, int32_t h
     else
       hipLaunchKernelGGL(eval_box_score_kernel<float>, dim3(nb), dim3(256), 0, S(stream), (const float*)maps_dev, n, h, w,
                          boxes_dev, thr_dev, K, scores_dev);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+// ---- Grad-CAM and the word examination (csrc/gradcam_kernels.h; explainers.py:939-949, exaimin_word.py)
+int lrp_op_gradcam(const float* feat_dev, const int32_t* img_idx_dev, const float* grads_dev, const double* M_dev,
+                   const float* gb_dev, double* cam_dev, double* out_dev, int32_t n, int32_t B, int32_t g, int32_t upscale,
+                   int32_t D, int32_t C, void* stream) {
+  return guarded([&]() -> int {
+    if (!feat_dev || !img_idx_dev || !grads_dev || !M_dev || !cam_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if ((gb_dev == nullptr) != (out_dev == nullptr)) return fail(LRP_ERR_INVALID, "gb_dev and out_dev go together: both or neither may be null");
+    if (n < 1 || B < 1) return fail(LRP_ERR_INVALID, "n and B must be positive");
+    if (g < 1 || g > EVAL_MAX_G || upscale < 1 || g * upscale > EVAL_MAX_S)
+      return fail(LRP_ERR_INVALID, "need 1 <= g <= %d and 1 <= g * upscale <= %d", EVAL_MAX_G, EVAL_MAX_S);
+    if (D < 8 || D % 8 != 0 || D > GRADCAM_MAX_D) return fail(LRP_ERR_INVALID, "D must be a multiple of 8 in [8, %d]", GRADCAM_MAX_D);
+    if (gb_dev && (C < 1 || C > 64)) return fail(LRP_ERR_INVALID, "need 1 <= C <= 64 channels of the gated map");
+    const int Sd = g * upscale;
+    const size_t lds = (size_t)(g * g + (D > g * Sd ? D : g * Sd)) * sizeof(double);
+    hipLaunchKernelGGL(gradcam_kernel, dim3(n), dim3(256), lds, S(stream), feat_dev, img_idx_dev, grads_dev, M_dev, gb_dev,
+                       cam_dev, out_dev, B, g, Sd, D, C);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_exam_maps(const void* R_img_dev, int32_t fp64, int32_t n, int32_t H, int32_t W, int32_t C, int32_t pool, int32_t k,
+                  int32_t absval, void* maps_dev, double* means_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (!R_img_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (!maps_dev && !means_dev) return fail(LRP_ERR_INVALID, "null argument: at least one of maps_dev and means_dev is needed");
+    if (n < 1 || H < 1 || W < 1 || C < 1) return fail(LRP_ERR_INVALID, "n, H, W, C must be positive");
+    if ((int64_t)H * W * C > INT32_MAX) return fail(LRP_ERR_INVALID, "one map must hold fewer than 2^31 values");
+    if (fp64 != 0 && fp64 != 1) return fail(LRP_ERR_INVALID, "fp64 must be 0 or 1");
+    if (absval != 0 && absval != 1) return fail(LRP_ERR_INVALID, "absval must be 0 or 1");
+    if (pool != EXAM_POOL_NONE && pool != EXAM_POOL_MAX && pool != EXAM_POOL_AVE)
+      return fail(LRP_ERR_INVALID, "pool must be 0 (none), 1 (max) or 2 (ave)");
+    if (pool != EXAM_POOL_NONE && (k < 1 || H % k != 0 || W % k != 0))
+      return fail(LRP_ERR_INVALID, "the pool block k must be positive and divide H and W");
+    if (fp64)
+      hipLaunchKernelGGL(exam_map_kernel<double>, dim3(n), dim3(256), 0, S(stream), (const double*)R_img_dev, H, W, C, pool, k,
+                         absval, maps_dev, means_dev);
+    else
+      hipLaunchKernelGGL(exam_map_kernel<float>, dim3(n), dim3(256), 0, S(stream), (const float*)R_img_dev, H, W, C, pool, k,
+                         absval, maps_dev, means_dev);
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   });

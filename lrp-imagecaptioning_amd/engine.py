@@ -377,6 +377,21 @@ class LRPEngine(object):
                                            self.WALKS[walk], self._stream()))
         return out
 
+    def guided_gradcam(self, img_idx, t, want_cam=False):
+        """Guided Grad-CAM (explainers.py:930-949 / :1634-1653) for n <= max_tokens (image, t) units in one chain on the
+        cached forward: decoder_gradient -> cnn_walk('guided_backprop') -> op_gradcam on get_features().  Returns the
+        (n, H, W, 3) float64 tensor `guided backprop * cam` (and the (n, H, W) float64 cams); nothing leaves the device."""
+        g = int(round(np.sqrt(self.L)))
+        up = self.img_hw[0] // max(g, 1)
+        if g * g != self.L or g * up != self.img_hw[0] or self.img_hw[0] != self.img_hw[1]:
+            raise ValueError("guided_gradcam needs a square image whose side is a multiple of sqrt(L)")
+        if len(img_idx) != len(t) or not 1 <= len(img_idx) <= self.max_tokens:
+            raise ValueError("need between 1 and max_tokens=%d (image, t) units" % self.max_tokens)
+        d, _ = self.decoder_gradient(img_idx, t, want_r_words=False)
+        gb = self.cnn_walk(img_idx, d, "guided_backprop")
+        out, cam = op_gradcam(self.get_features(), img_idx, d, g, up, gb=gb)
+        return (out, cam) if want_cam else out
+
     def explain_tokens(self, img_idx, t, variant="sequence", out=None, want_R_feat=False, want_attention=False,
                        want_r_words=False):
         """Fused decoder-LRP -> CNN-LRP for n (image, t) pairs: (n,H,W,3) heat-map relevances."""
@@ -728,3 +743,67 @@ def eval_box_scores(maps, boxes, thr):
                                         m.shape[2], C.c_void_p(b.data_ptr()), C.c_void_p(t.data_ptr()), nb, K,
                                         C.c_void_p(out.data_ptr()), _cur_stream(m.device)))
     return out
+
+
+# ---- Grad-CAM and the word examination (exaimin_word.py; csrc/gradcam_kernels.h, lrp_op_gradcam / lrp_exam_maps)
+def _expand_matrix_dev(device, g, upscale, sigma):
+    key = (str(device), int(g), int(upscale), float(sigma))
+    if key not in _EXPAND_CACHE:
+        _EXPAND_CACHE[key] = torch.as_tensor(eval_expand_matrix(g, upscale, sigma)).to(device)
+    return _EXPAND_CACHE[key]
+
+
+def op_gradcam(feat, img_idx, grads, g, upscale, gb=None, sigma=20.0):
+    """`grad_cam` (explainers.py:939-949) for n (image, word) units in fp64 on the device: feat (B, L, D) float32 tensor,
+    img_idx n image indices, grads (n, L, D) float32 tensor, L = g * g -> cam (n, S, S) float64, S = g * upscale.
+    With gb (n, S, S, C) float32 (the guided-backprop map) -> (gb * cam (n, S, S, C) float64, cam)."""
+    lib = _capi.load()
+    f, d = feat.contiguous(), grads.contiguous()
+    if f.dtype != torch.float32 or d.dtype != torch.float32 or f.dim() != 3 or d.dim() != 3 or f.shape[1:] != d.shape[1:] \
+            or f.shape[1] != g * g:
+        raise ValueError("expected feat (B, g * g, D) and grads (n, g * g, D) float32 tensors")
+    n, B, D, S = d.shape[0], f.shape[0], f.shape[2], g * upscale
+    ii = np.asarray(img_idx.cpu() if torch.is_tensor(img_idx) else img_idx, dtype=np.int64).reshape(-1)
+    if len(ii) != n or (n and (ii.min() < 0 or ii.max() >= B)):
+        raise ValueError("img_idx must hold n indices in [0, %d)" % B)
+    idx = torch.as_tensor(ii.astype(np.int32)).to(f.device)
+    out = None
+    if gb is not None:
+        gb = gb.contiguous()
+        if gb.dtype != torch.float32 or gb.dim() != 4 or tuple(gb.shape[:3]) != (n, S, S):
+            raise ValueError("gb must be an (n, S, S, C) float32 tensor")
+        out = torch.empty(gb.shape, dtype=torch.float64, device=f.device)
+    M = _expand_matrix_dev(f.device, g, upscale, sigma)      # validates g, upscale and sigma
+    cam = torch.empty((n, S, S), dtype=torch.float64, device=f.device)
+    p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
+    _capi.check(lib.lrp_op_gradcam(p(f), p(idx), p(d), p(M), p(gb), p(cam), p(out), n, B, int(g), int(upscale), D,
+                                   gb.shape[3] if gb is not None else 0, _cur_stream(f.device)))
+    return cam if gb is None else (out, cam)
+
+
+_EXAM_POOL = {None: 0, "max": 1, "ave": 2}
+
+
+def exam_maps(R_img, pool=None, k=None, absval=False, want_maps=True):
+    """The map and statistic of the word examination (exaimin_word.py:95-102, :131-160, :488-489) on the device: R_img
+    (n, H, W, C) float32 or float64 tensor -> channel mean (flipped channel order, input dtype), pool None / 'max' / 'ave'
+    over k x k blocks, x / absmax, |x| if absval.  Returns (maps, means): maps (n, H, W) in the input dtype, or
+    (n, H / k, W / k) float64 when pooled (None unless want_maps); means (n,) float64, the mean of each map."""
+    lib = _capi.load()
+    if pool not in _EXAM_POOL:
+        raise ValueError("pool must be None, 'max' or 'ave'")
+    R = R_img.contiguous()
+    if R.dtype not in (torch.float32, torch.float64) or R.dim() != 4:
+        raise ValueError("expected an (n, H, W, C) float32 or float64 tensor")
+    n, Hh, Ww, Cc = R.shape
+    k = int(k) if pool is not None else 1
+    if pool is not None and (k < 1 or Hh % k or Ww % k):
+        raise ValueError("the pool block k must divide H and W")
+    maps = None
+    if want_maps:
+        maps = torch.empty((n, Hh // k, Ww // k), dtype=R.dtype if pool is None else torch.float64, device=R.device)
+    means = torch.empty((n,), dtype=torch.float64, device=R.device)
+    _capi.check(lib.lrp_exam_maps(C.c_void_p(R.data_ptr()), int(R.dtype == torch.float64), n, Hh, Ww, Cc, _EXAM_POOL[pool], k,
+                                  int(bool(absval)), C.c_void_p(maps.data_ptr()) if maps is not None else None,
+                                  C.c_void_p(means.data_ptr()), _cur_stream(R.device)))
+    return maps, means

@@ -8,7 +8,8 @@ annotated object, the share of the word's heat-map (and attention map) inside th
 `evaluate(X, data)` keeps the reference's surface and return values.  `evaluate_batch` explains every object word of a
 batch in one launch chain; the maps stay on the device (lrp_eval_relevance_maps / _attention_maps / _box_scores) and only
 the (boxes x thresholds) scores come back.  Explainers whose `_explain_CNN` is host-side (the Guided Grad-CAM classes)
-take the per-word path; their float64 maps are uploaded and scored in float64.
+take the per-word path; their float64 maps are uploaded and scored in float64 — unless EvaluationBboxCOCOBaseline is
+built with device_gradcam=True, which computes their Grad-CAM factor on the device and batches them like the others.
 
 The category synonym table and the word filter list are constructor keywords (the reference's CATEGORY_EXTENSION and
 FILTER, EB:11-21, are the caller's to pass).
@@ -166,7 +167,7 @@ class EvaluationBboxCOCO(object):
         ex = self._explainer
         eng = ex._engine
         out = [[None] * len(p[2]) for p in plans]
-        batched = getattr(ex, "_batched_cnn", True)
+        batched = self._batched(ex)
         step = eng.max_images if batched else 1
         for lo in range(0, len(images), step):
             hi = min(len(images), lo + step)
@@ -197,6 +198,9 @@ class EvaluationBboxCOCO(object):
                     out[b][e] = r
         return out
 
+    def _batched(self, ex):
+        return getattr(ex, "_batched_cnn", True)
+
     def _maps_of(self, units, images, batched):
         ex = self._explainer
         eng = ex._engine
@@ -217,13 +221,29 @@ class EvaluationBboxCOCO(object):
 
 class EvaluationBboxCOCOBaseline(EvaluationBboxCOCO):
     """EB:273-358: the gradient baselines (decoder gradient -> CNN walk); no attention map.
-    evaluate / evaluate_batch return (gradient_score, category_key) per image."""
+    evaluate / evaluate_batch return (gradient_score, category_key) per image.
+
+    device_gradcam=True (opt-in): a Guided Grad-CAM explainer takes the batched branch too — `max_images` images and
+    `max_tokens` words per chain through LRPEngine.guided_gradcam (Grad-CAM in fp64 on the device, lrp_op_gradcam); its
+    float64 maps are scored in float64 and only the scores come back.  The default keeps the per-word host path."""
     _maps = ("gradient",)
+
+    def __init__(self, *args, **kwargs):
+        self.device_gradcam = bool(kwargs.pop("device_gradcam", False))
+        super(EvaluationBboxCOCOBaseline, self).__init__(*args, **kwargs)
+
+    def _on_device_gradcam(self, ex):
+        return self.device_gradcam and hasattr(ex, "grad_cam_device")
+
+    def _batched(self, ex):
+        return self._on_device_gradcam(ex) or getattr(ex, "_batched_cnn", True)
 
     def _maps_of(self, units, images, batched):
         ex = self._explainer
         eng = ex._engine
         ii, ts = [u[0] for u in units], [u[1] for u in units]
+        if batched and self._on_device_gradcam(ex):
+            return [_eng.eval_relevance_maps(eng.guided_gradcam(ii, ts), self.sign)]
         if batched:
             d, _ = eng.decoder_gradient(ii, ts, want_r_words=False)
             return [_eng.eval_relevance_maps(eng.cnn_walk(ii, d, ex._walk), self.sign)]

@@ -400,6 +400,29 @@ class _GuidedGradcamMixin(_GradientMixin):
         cam = self.grad_cam(feat, R[0])
         return (gb[0] * cam[..., np.newaxis])[np.newaxis, :]
 
+    # -------------------------------------------------------------- batched forms on the device (new; lrp_op_gradcam)
+    def grad_cam_device(self, grads):
+        """`grad_cam` of n gradient rows of the cached image at once, in fp64 on the device: grads (n, L, D) or
+        (n, g, g, D) -> (n, S, S) float64 tensor."""
+        from .engine import op_gradcam
+        g = int(np.sqrt(self.L))
+        d = self._engine._dev(grads).reshape(-1, self.L, self.D)
+        return op_gradcam(self._engine.get_features()[:1], [0] * d.shape[0], d, g, self._model.img_hw[0] // g)
+
+    def explain_words(self, ts, want_cam=False):
+        """`_explain_CNN(X, _lstm_decoder_backward(t))` for every t of `ts` in one chain on the cached caption:
+        (len(ts), H, W, 3) float64 tensor on the device (and the cams on request)."""
+        ts = [int(t) for t in ts]
+        for t in ts:
+            self._check_t(t)
+        return self._engine.guided_gradcam([0] * len(ts), ts, want_cam=want_cam)
+
+    def explain_sentence_cnn(self):
+        """Every word of the cached caption: explain_words(1 .. len(caption) - 1)."""
+        if self.caption is None:
+            raise RuntimeError("_forward_beam_search must run first")
+        return self.explain_words(range(1, len(self.caption)))
+
 
 class ExplainImgCaptioningAdaptiveAttentionGradient(_GradientMixin, ExplainImgCaptioningAdaptiveAttention):
     """E:667-879."""
