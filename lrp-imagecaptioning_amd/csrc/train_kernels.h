@@ -242,6 +242,7 @@ __global__ __launch_bounds__(256) void tr_att_mix_kernel(const float* __restrict
 // Two-headed loss (M:95-103, :1364-1373) of one (t, b) row, in place: Z row (logits before the bias) -> d loss / d logits.
 // part[row] = (CE head 1, CE head 2, hit head 1, hit head 2, labelled) — hit = the label is the arg-max (M:105-124).
 // Rows of the last time step and rows without a label give zero.
+// A hit is z_y >= max where tf.argmax takes the first maximal index: the two differ only on an exact tie at the maximum.
 // ml: Dropout on the logits (grid-TD model, M:1303-1304), (B, T, V) or null.
 __global__ __launch_bounds__(256) void tr_loss_kernel(float* __restrict__ Z, const float* __restrict__ bout, const float* __restrict__ lw,
                                                       const float* __restrict__ ml, const int* __restrict__ y_idx,

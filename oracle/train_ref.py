@@ -175,8 +175,26 @@ def two_head_loss(logits, lrp_weight, y_idx):
     return 0.5 * l1 + 0.5 * l2, l1, l2
 
 
+def two_head_accuracy(logits, lrp_weight, y_idx, counts=False):
+    """categorical_accuracy_with_variable_timestep (M:105-123) of both heads: the last step is dropped, all-zero label
+    rows (y_idx < 0) are dropped, the mean of (arg-max == label) runs over the remaining rows; head 1 takes its arg-max
+    on the logits, head 2 on logits * lrp_weight, both with tf.argmax's first-index rule.  The logits are the
+    training-mode ones `loss_and_grads` returns (for grid-TD they carry their Dropout mask).
+    -> (acc1, acc2), 0 without a labelled row; counts=True -> (hits1, hits2, rows)."""
+    z = np.asarray(logits, np.float64)[:, :-1]
+    z2 = z * np.asarray(lrp_weight, np.float64)[:, :-1]
+    y = np.asarray(y_idx)[:, :-1]
+    keep = y >= 0
+    h1 = int(((np.argmax(z, axis=-1) == y) & keep).sum())                 # np.argmax: first maximal index, like tf.argmax
+    h2 = int(((np.argmax(z2, axis=-1) == y) & keep).sum())
+    n = int(keep.sum())
+    if counts:
+        return h1, h2, n
+    return (h1 / n, h2 / n) if n else (0.0, 0.0)
+
+
 def loss_and_grads(weights, cnn_cfg, images, cap_in, y_idx, lrp_weight, masks=None, kind="adaptive"):
-    """-> (total, l1, l2, {name: grad ndarray}) for every parameter of the training model."""
+    """-> (total, l1, l2, {name: grad ndarray}, training-mode logits (B, T, V)) for every parameter of the training model."""
     w = {k: _t(v).requires_grad_(True) for k, v in weights.items() if k in set(param_names(cnn_cfg, kind))}
     mk = {k: _t(v) for k, v in (masks or {}).items() if v is not None}
     feat = cnn_features(w, cnn_cfg, _t(images))

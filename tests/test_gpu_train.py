@@ -68,6 +68,7 @@ def test_gradients_match_oracle(with_masks, precision):
 
 
 def test_adam_step_matches_oracle_and_engine_follows():
+    """Adam's first step and the engine following the masters; steps beyond the first: tests/test_gpu_train_optimizer.py."""
     from oracle import train_ref as T
     w, X, cap_in, y, lw, masks = _case(3)
     eng = _engine(w, len(X))

@@ -1,11 +1,14 @@
 """oracle/train_ref.py: pinned against the decoder oracle (itself pinned by reference outputs) and by finite differences."""
 import numpy as np
+import pytest
 import torch
 
 from lrp_imagecaptioning_amd.synthetic import adaptive_weights, vgg_weights
 from oracle import cnn_lrp_ref as C
 from oracle import train_ref as T
 from oracle.decoder_ref import AdaptiveOracle
+
+import train_util as U
 
 CFG = [("c1", 3, 8, True), ("c2", 8, 16, True), ("c3", 16, 16, False)]
 HW, L, D, H, V = 16, 16, 16, 16, 24
@@ -91,3 +94,90 @@ def test_gridtd_hidden_states_match_decoder_oracle():
     want = (o.h2t[1:] + o.context_hat[1:]) @ w["output_W"] + w["output_b"]
     np.testing.assert_allclose(logits[0], want, rtol=2e-4, atol=2e-5)
     assert set(g) == set(T.param_names(CFG, "gridtd")) and all(np.isfinite(v).all() for v in g.values())
+
+
+def test_two_head_accuracy_hand_example():
+    """B = 2, T = 3, V = 4; the last step is dropped, so rows (b, t) with t in {0, 1} count.
+      (0, 0) logits [1, 3, 2, 0], lw [1, 1, 2, 1] -> head 2 sees [1, 3, 4, 0]; label 1: head 1 hit, head 2 miss
+      (0, 1) logits [2, 2, 1, 0] (tie: the FIRST index, 0), lw 1;               label 1: miss, miss
+      (1, 0) logits [-1, -2, -3, -4], lw [2, 1, 1, 1] -> [-2, -2, -3, -4] (tie -> 0); label 0: hit, hit
+      (1, 1) no label (-1): dropped although its arg-max is defined
+      (0, 2), (1, 2): last step, dropped although (0, 2) would be a hit for both heads
+    -> 3 rows; head 1: 2 hits = 2/3; head 2: 1 hit = 1/3."""
+    logits = np.array([[[1, 3, 2, 0], [2, 2, 1, 0], [9, 0, 0, 0]],
+                       [[-1, -2, -3, -4], [0, 5, 0, 0], [0, 0, 0, 0]]], np.float64)
+    lw = np.ones((2, 3, 4))
+    lw[0, 0, 2] = 2
+    lw[1, 0, 0] = 2
+    y = np.array([[1, 1, 0], [0, -1, 2]])
+    assert T.two_head_accuracy(logits, lw, y, counts=True) == (2, 1, 3)
+    a1, a2 = T.two_head_accuracy(logits, lw, y)
+    assert a1 == 2 / 3 and a2 == 1 / 3
+    assert T.two_head_accuracy(logits, lw, np.full_like(y, -1)) == (0.0, 0.0)          # no labelled row
+    y2 = y.copy()
+    y2[0, 1] = 0                                                                       # the first index of the tie: a hit
+    assert T.two_head_accuracy(logits, lw, y2, counts=True) == (3, 2, 3)
+
+
+ADAM_WRONG = ("no_clip", "step_minus_1", "step_plus_1", "no_bias_correction", "eps_in_root", "eps_on_vhat")
+
+
+@pytest.mark.parametrize("name", list(U.ADAM_CONFIGS))
+def test_adam_bound_holds_for_fp32_and_excludes_wrong_optimizers(name):
+    """The bound tests/test_gpu_train_optimizer.py applies to the device, on the very gradients it uses: (a) tr_adam_kernel's
+    operation order in np.float32 stays within HALF of it at every step, so fp32 rounding cannot fail the device test;
+    (b) every wrong variant of the float64 oracle leaves it by more than 100x on at least 5 % of the elements at the last
+    step, so each of those mistakes in the kernel or in the host's lr_t would."""
+    kind, size, steps, lr, clip, b1, b2, eps = U.ADAM_CONFIGS[name]
+    w, cfg, kind = U.adam_weights(name)
+    layout, total = U.flat_layout(w, cfg, kind)
+    if size == "big":
+        assert total > U.GRID_LIMIT + 1
+    p0 = U.flatten(w, layout, total)
+    G = U.adam_gradients(layout, total, steps)
+    assert G.dtype == np.float32 and G.shape == (steps, total)
+    real = np.zeros(total, bool)
+    for off, n in layout.values():
+        real[off:off + n] = True
+    assert not G[:, ~real].any()                                                        # padding gets zeros
+    assert 0.05 < (G[:, real] == 0).mean() and (np.abs(G) > 0.1).any() and ((np.abs(G) < 1e-8) & (G != 0)).any()
+    ref = U.adam_reference(p0, G, lr, clip, b1, b2, eps)
+    emu = U.adam_fp32_emulation(p0, G, lr, clip, b1, b2, eps)
+    for k in range(steps):
+        ratio = np.abs(emu[k] - ref[k]) / U.adam_bound(k + 1, ref[k], U.f32c(lr))
+        assert ratio.max() <= 0.5, (name, k + 1, float(ratio.max()))
+    bound = U.adam_bound(steps, ref[-1], U.f32c(lr))
+    for variant in ADAM_WRONG:
+        if variant == "no_clip" and not clip:
+            continue
+        wrong = U.adam_reference(p0, G, lr, clip, b1, b2, eps, variant=variant)[-1]
+        outside = ~(np.abs(wrong - ref[-1]) <= 100 * bound)                             # (a NaN is outside)
+        assert outside.mean() >= 0.05, (name, variant, float(outside.mean()))
+    if size == "big":                                 # the elements the device test names have moved far more than the bound
+        for i in (U.GRID_LIMIT - 1, U.GRID_LIMIT, U.GRID_LIMIT + 1):
+            assert real[i] and abs(ref[-1][i] - p0[i]) > 100 * bound[i]
+        off, n = layout["output_b"]
+        assert off + n == total and (np.abs(ref[-1] - p0)[off:off + n] > 100 * bound[off:off + n]).mean() > 0.5
+
+
+def test_device_constants_are_not_the_decimal_ones():
+    """float32(0.999): 1 - b2 differs from 1e-3 by 1.3e-5 relative — the oracle must get the constants the device has."""
+    assert abs((1 - U.f32c(0.999)) / 1e-3 - 1) > 1e-5
+
+
+@pytest.mark.parametrize("kind", ["adaptive", "gridtd"])
+@pytest.mark.parametrize("with_masks", [False, True])
+def test_accuracy_case_conditions(kind, with_masks):
+    """The inputs of the device's accuracy test decide something: the two expected accuracies differ from each other and
+    from 0 and 1, and in every labelled row both heads' top-1 to top-2 margin exceeds 1e-3 max|logit| (a hundred times the
+    forward's fp32 error: no decision depends on rounding, no exact tie at the maximum)."""
+    w, X, cap_in, y, lw, masks, logits, (h1, h2, n) = U.accuracy_case(kind, with_masks)
+    assert cap_in.shape == (4, 6) and (masks is not None) == with_masks
+    assert (y[1, -2:] == -1).all() and n == 19                                          # the padded tail of _case is kept
+    assert 0 < h1 < n and 0 < h2 < n and h1 != h2
+    if kind == "gridtd" and with_masks:
+        assert (logits == 0).mean() > 0.3                                               # the logits carry their Dropout mask
+    keep = y[:, :-1] >= 0
+    for z in (logits[:, :-1], logits[:, :-1] * lw[:, :-1].astype(np.float64)):
+        s = np.sort(z, axis=-1)
+        assert ((s[..., -1] - s[..., -2])[keep]).min() > 1e-3 * np.abs(z).max()
