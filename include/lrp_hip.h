@@ -70,7 +70,11 @@ typedef struct lrp_config {
   int32_t abi_version;          /* = LRP_ABI_VERSION                                    */
   int32_t device;               /* HIP device ordinal                                   */
   int32_t decoder;              /* LRP_DEC_*                                            */
-  int32_t img_h, img_w;         /* 224, 224                                             */
+  int32_t img_h, img_w;         /* 224, 224.  img_h != img_w is supported by both encoders, every walk and the
+                                   fine-tune step (tests/test_gpu_nonsquare.py).  lrp_create refuses with
+                                   LRP_ERR_UNSUPPORTED: VGG-style, an odd resolution in front of a 2x2 pool; ResNet,
+                                   sides that are not multiples of 4 or an odd resolution in front of a stride-2
+                                   block.  L = (top rows) x (top columns), row-major.                            */
   int32_t n_conv;
   int32_t conv_cin[LRP_MAX_CONV];
   int32_t conv_cout[LRP_MAX_CONV];

@@ -2,9 +2,10 @@
 (oracle/resnet_lrp_ref.py) — BASELINE config 4's CNN half (rows c3, c5, c6 of SURVEY §8a)."""
 import numpy as np
 import pytest
+import torch
 
 from conftest import rel_l1
-from gpu_util import report
+from gpu_util import band_bar, band_rel_l1, report
 from lrp_imagecaptioning_amd.synthetic import RESNET101_STACKS, gridtd_weights, resnet_weights
 from oracle import resnet_lrp_ref as RN
 from oracle.decoder_ref import GridTDOracle
@@ -45,9 +46,14 @@ def test_small_resnets_match_oracle(name, stacks, stem, hw, B, prec):
     out = eng.cnn_explain(idx, R).cpu().numpy()
     ref = RN.analyze(w, spec, X[idx], R)
     errs = [rel_l1(out[i], ref[i]) for i in range(2 * B)]
-    report("resnet_" + name, prec=prec, feat_rel_l1=rel_l1(feat, feat_ref), max_rel_l1=max(errs))
+    # the worst single image row / column as well (gpu_util.band_rel_l1), held to 10 x the float32 oracle's own figure
+    bar, band32 = band_bar(RN.analyze(w, spec, X[idx], R, dtype=torch.float32), ref)
+    band = max(band_rel_l1(out[i], ref[i], where=True) for i in range(2 * B))
+    report("resnet_" + name, prec=prec, feat_rel_l1=rel_l1(feat, feat_ref), max_rel_l1=max(errs), worst_band=band[0],
+           worst_band_at=band[1], f32_restatement_band=band32, band_bar=bar)
     assert np.isfinite(out).all()
     assert max(errs) < TOL, errs
+    assert band[0] < bar, (band, bar)
 
 
 @pytest.mark.parametrize("prec", ["bf16x3", "fp32"])
@@ -81,7 +87,6 @@ def test_pair_emitting_forward_matches_oracle_is_batch_invariant_and_has_a_fallb
     features and heat-maps vs the float64 oracle; an image alone == the same image inside the batch, bit for bit (what the
     per-call scales of round 3 could not give); LRP_FWD_EMIT=0 (split passes between the convs) agrees to the forward's rounding;
     the walk's projection-block path (S3 from the previous epilogue, join + next head in one pass) is the same arithmetic."""
-    import torch
     from lrp_imagecaptioning_amd.engine import switches
     stacks, stem, hw, B = ((32, 3), (64, 2)), 32, 64, 3
     rs = np.random.RandomState(12)
@@ -111,10 +116,17 @@ def test_pair_emitting_forward_matches_oracle_is_batch_invariant_and_has_a_fallb
         feat0, out0 = run(eng, X, idx, R)
     e_fb = float((feat0.double() - feat.double()).abs().sum() / feat.double().abs().sum())
     e_fb_hm = max(rel_l1(out0[i].cpu().numpy(), out[i].cpu().numpy()) for i in range(2 * B))
-    report("resnet_emit", feat_rel_l1=e_feat, max_rel_l1=max(errs), fallback_feat=e_fb, fallback_heatmaps=e_fb_hm)
+    # the worst single image row / column of both comparisons (gpu_util.band_rel_l1)
+    bar, band32 = band_bar(RN.analyze(w, spec, X[idx], R, dtype=torch.float32), ref)
+    band = max(band_rel_l1(out[i].cpu().numpy(), ref[i], where=True) for i in range(2 * B))
+    band_fb = max(band_rel_l1(out0[i].cpu().numpy(), out[i].cpu().numpy(), where=True) for i in range(2 * B))
+    report("resnet_emit", feat_rel_l1=e_feat, max_rel_l1=max(errs), fallback_feat=e_fb, fallback_heatmaps=e_fb_hm,
+           worst_band=band[0], worst_band_at=band[1], fallback_worst_band=band_fb[0], fallback_worst_band_at=band_fb[1],
+           f32_restatement_band=band32, band_bar=bar)
     assert e_feat < 1e-5
     assert max(errs) < TOL, errs
     assert e_fb < 1e-5 and e_fb_hm < 2e-5
+    assert band[0] < bar and band_fb[0] < bar, (band, band_fb, bar)
 
 
 def _stem_pool_windows(w, Xh, dtype):

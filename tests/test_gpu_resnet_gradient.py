@@ -7,7 +7,7 @@ import torch
 
 import resnet_grad_ref as RG
 from conftest import rel_l1
-from gpu_util import report
+from gpu_util import band_bar, band_rel_l1, report
 from lrp_imagecaptioning_amd.synthetic import RESNET101_STACKS, resnet_weights
 
 pytestmark = pytest.mark.gpu
@@ -50,15 +50,22 @@ def test_small_resnets_gradient_walks_match_oracle(name):
         out = eng.cnn_walk(idx, head, walk).cpu().numpy()
         ref = RG.gradient_analyze(w, spec, X[idx], head, walk)
         errs = [rel_l1(out[i], ref[i]) for i in range(4)]
-        report("resnet_grad_" + name, walk=walk, max_rel_l1=max(errs))
+        # the worst single image row / column as well (gpu_util.band_rel_l1), held to 10 x the float32 oracle's own figure
+        bar, band32 = band_bar(RG.gradient_analyze(w, spec, X[idx], head, walk, dtype=torch.float32), ref)
+        band = max(band_rel_l1(out[i], ref[i], where=True) for i in range(4))
+        report("resnet_grad_" + name, walk=walk, max_rel_l1=max(errs), worst_band=band[0], worst_band_at=band[1],
+               f32_restatement_band=band32, band_bar=bar)
         assert np.isfinite(out).all()
         assert max(errs) < TOL, (walk, errs)
+        assert band[0] < bar, (walk, band, bar)
         if name == "stem64":                               # the two-kernel stem (GEMM + stencil) as well
             with switches(LRP_IMG_FUSED="0"):
                 out2 = eng.cnn_walk(idx, head, walk).cpu().numpy()
             errs2 = [rel_l1(out2[i], ref[i]) for i in range(4)]
-            report("resnet_grad_stem64_two_kernel", walk=walk, max_rel_l1=max(errs2))
+            band2 = max(band_rel_l1(out2[i], ref[i], where=True) for i in range(4))
+            report("resnet_grad_stem64_two_kernel", walk=walk, max_rel_l1=max(errs2), worst_band=band2[0], worst_band_at=band2[1])
             assert max(errs2) < TOL, (walk, errs2)
+            assert band2[0] < bar, (walk, band2, bar)
 
 
 def test_resnet101_full_size_gradient_walks():

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from conftest import rel_l1
+from gpu_util import NONSQUARE_RESNETS, transpose_spatial
 from lrp_imagecaptioning_amd.synthetic import resnet_conv_list, resnet_weights
 from oracle import resnet_lrp_ref as RN
 
@@ -60,3 +61,27 @@ def test_float32_close_to_float64():
     feat = RN.forward(w, spec, X)
     R = (rs.standard_normal(feat.shape) * feat).astype(np.float32)
     assert rel_l1(RN.analyze(w, spec, X, R, torch.float32), RN.analyze(w, spec, X, R)) < 1e-4
+
+
+@pytest.mark.parametrize("name", ["stem64", "mid", "tiny"])
+def test_transposition_equivariance_at_h_ne_w(name):
+    """The oracle at H != W: with every kernel transposed in its two spatial axes, the image and the relevance transposed,
+    forward and analyze return the transposed result (to summation order: 1e-12) — an H / W mix-up anywhere in it, the
+    7 x 7 / 2 stem's padding, the overlapping pool or the stride-2 blocks included, would break this.  Continuous random inputs:
+    no pool ties.  Transposing the stem kernel alone moves the map by more than its own mass: the inputs are not
+    accidentally symmetric."""
+    stacks, stem, (H, W) = NONSQUARE_RESNETS[name]
+    rs = np.random.RandomState(3)
+    w = resnet_weights(rs, stacks, stem=stem, bias_std=0.2)
+    spec = RN.resnet_spec(stacks, stem=stem)
+    X = rs.uniform(-120, 130, size=(2, H, W, 3))
+    feat = RN.forward(w, spec, X)
+    assert feat.shape[1:3] == (H // 4 // 2 ** (len(stacks) - 1), W // 4 // 2 ** (len(stacks) - 1))
+    R = rs.standard_normal(feat.shape) * feat
+    ref = RN.analyze(w, spec, X, R)
+    wt, Xt, Rt = transpose_spatial(w), np.swapaxes(X, 1, 2), np.swapaxes(R, 1, 2)
+    assert rel_l1(np.swapaxes(RN.forward(wt, spec, Xt), 1, 2), feat) < 1e-12
+    assert rel_l1(np.swapaxes(RN.analyze(wt, spec, Xt, Rt), 1, 2), ref) < 1e-12
+    assert rel_l1(np.swapaxes(RN.analyze_cached(wt, spec, Xt, Rt), 1, 2), ref) < 1e-10
+    only_stem = dict(w, conv1_conv_W=wt["conv1_conv_W"])
+    assert rel_l1(RN.analyze(only_stem, spec, X, R), ref) > 1.0

@@ -8,6 +8,7 @@ import torch.nn.functional as F
 
 import resnet_grad_ref as RG
 from conftest import rel_l1
+from gpu_util import NONSQUARE_RESNETS, transpose_spatial
 from lrp_imagecaptioning_amd.synthetic import resnet_weights
 from oracle import resnet_lrp_ref as RN
 
@@ -171,3 +172,26 @@ def test_analyzer_argument_validation():
     del w2["conv2_block1_2_bn_var"]
     with pytest.raises(A.NotAnalyzeableModelException):
         A.ImageModelSpec(w2, img_hw=(32, 32), resnet={"stem": 8, "stacks": TINY})
+
+
+@pytest.mark.parametrize("name", ["stem64", "mid", "tiny"])
+def test_gradient_walks_are_transposition_equivariant_at_h_ne_w(name):
+    """The gradient oracle at H != W: kernels, image and head transposed in their spatial axes -> the transposed map, for
+    all three walks (1e-12: only the summation order differs); with the stem kernel alone transposed the map moves by more
+    than half its own mass (symmetric inputs would give 1e-12; guided backprop's maps, rectified at every layer, stay
+    correlated and land just under 1, the other two walks above it)."""
+    stacks, stem, (H, W) = NONSQUARE_RESNETS[name]
+    rs = np.random.RandomState(3)
+    w = resnet_weights(rs, stacks, stem=stem, bias_std=0.2)
+    spec = RN.resnet_spec(stacks, stem=stem)
+    X = rs.uniform(-120, 130, size=(2, H, W, 3))
+    feat = RG.forward(w, spec, X)
+    head = rs.standard_normal(feat.shape)
+    wt, Xt, ht = transpose_spatial(w), np.swapaxes(X, 1, 2), np.swapaxes(head, 1, 2)
+    assert rel_l1(np.swapaxes(RG.forward(wt, spec, Xt), 1, 2), feat) < 1e-12
+    only_stem = dict(w, conv1_conv_W=wt["conv1_conv_W"])
+    for walk in ("gradient", "input_x_gradient", "guided_backprop"):
+        ref = RG.gradient_analyze(w, spec, X, head, walk)
+        assert np.abs(ref).sum() > 0
+        assert rel_l1(np.swapaxes(RG.gradient_analyze(wt, spec, Xt, ht, walk), 1, 2), ref) < 1e-12, walk
+        assert rel_l1(RG.gradient_analyze(only_stem, spec, X, head, walk), ref) > 0.5, walk
