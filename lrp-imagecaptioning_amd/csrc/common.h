@@ -126,4 +126,46 @@ struct DevBuf {
   T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// Per-launch timing of the reverse walks (lrp_profile_enable / _query / _records): a pair of events around a launch and the
+// algorithmic flops booked on it.  Off: begin / end do nothing and the list stays empty.
+struct ProfileRec {
+  hipEvent_t e0, e1;
+  double flop;
+};
+struct Profiler {
+  bool on = false;
+  ProfileRec cur{};                                    // between begin and end
+  std::vector<ProfileRec> recs;
+  void begin(hipStream_t st) {
+    if (on) { (void)hipEventCreate(&cur.e0); (void)hipEventCreate(&cur.e1); (void)hipEventRecord(cur.e0, st); }
+  }
+  void end(hipStream_t st, double flop) {
+    if (on) { (void)hipEventRecord(cur.e1, st); cur.flop = flop; recs.push_back(cur); }
+  }
+  // waits for every record, hands (ms, flop) of those that finished to `each`, and empties the list
+  template <typename F>
+  void drain(F each) {
+    for (ProfileRec& p : recs) {
+      float t = 0.f;
+      if (hipEventSynchronize(p.e1) == hipSuccess && hipEventElapsedTime(&t, p.e0, p.e1) == hipSuccess) each((double)t, p.flop);
+      (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1);
+    }
+    recs.clear();
+  }
+  int records(int cap, double* ms_out, double* flop_out, int* n_out) {
+    int k = 0;
+    drain([&](double ms, double flop) { if (k < cap) { ms_out[k] = ms; flop_out[k] = flop; ++k; } });
+    *n_out = k;
+    return LRP_OK;
+  }
+  int query(int64_t* launches, double* ms, double* flop) {
+    int64_t nl = 0; double tm = 0, fl = 0;
+    drain([&](double t, double f) { tm += t; fl += f; ++nl; });
+    if (launches) *launches = nl;
+    if (ms) *ms = tm;
+    if (flop) *flop = fl;
+    return LRP_OK;
+  }
+};
+
 }  // namespace lrp

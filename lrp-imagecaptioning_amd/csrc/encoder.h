@@ -15,6 +15,7 @@
 #include "conv_igemm.h"
 #include "conv_sparse.h"
 #include "f16_operand.h"
+#include "fwd_mode.h"
 
 namespace lrp {
 
@@ -62,11 +63,6 @@ struct ConvLayer {
   size_t act_elems() const { return (size_t)H * W * cout; }
 };
 
-struct ProfileRec {
-  hipEvent_t e0, e1;
-  double flop;
-};
-
 struct Encoder {
   int img_h = 0, img_w = 0, max_images = 0, max_tokens = 0;
   int top_h = 0, top_w = 0, top_c = 0;
@@ -81,7 +77,6 @@ struct Encoder {
   DevBuf s0, s1;           // reverse-walk ping-pong [max_tokens][biggest layer]
   int encoded = 0;         // images currently cached
   bool features_only = false;
-  bool profile = false;
   int prec = PREC_BF16X3;  // arithmetic of the per-token reverse walk (lrp_set_precision); falls back to fp32 for widths % 8 != 0
   const int* row2img_host = nullptr;   // host copy of the NEXT explain call's token -> image map (one-shot; lets the launcher
                                        // order the tiles so that an image's gates are fetched once, conv_igemm.h TileOrder)
@@ -103,9 +98,9 @@ struct Encoder {
   DevBuf sp_scp;                      // sparse consumers: S_c of the call as chunk-major pairs (conv_sparse.h)
   DevBuf act_max, act_unscale;        // fp16-pair forward: per layer ACT_MAX_SLOTS maxima of its output / 2^-k of its input
   DevBuf out_scale;                   // ... and 2^k of the pairs a layer emits for its consumer (no split pass in between)
-  static bool fwd_emit() { return sw().fwd_emit != 0; }   // LRP_FWD_EMIT=0: split passes between the convs as in round 2
+  static bool fwd_emit() { return sw().fwd_emit != 0; }   // LRP_FWD_EMIT=0: absmax / split / gate passes between the convs (forward_pairs_split)
   DevBuf tok_exp, tok_max, tok_fac;   // its per-token scale exponents / measured maxima [layers + 1][max_tokens], factors [max_tokens]
-  std::vector<ProfileRec> prof;
+  Profiler prof;                      // one record per layer of a reverse walk (common.h)
   // Overlapped encode (mixed-precision mode): the caller's stream runs only the activation chain a_1..a_top (what
   // the decoder needs); the denominators Z+_l and the gates G_l — needed by explain() only — run on `side` behind
   // it, i.e. concurrently with the latency-bound decoder replay the caller enqueues next.
@@ -124,13 +119,11 @@ struct Encoder {
   // its whole relevance to a neighbour pixel: measured on VGG16, relative L1 of the heat-maps 5e-6 ... 3.6e-5 instead
   // of 5.6e-6.  Default: none (splitting only the layers behind the last pool is flip-free but makes the features the
   // decoder consumes 10x less exact, 7.4e-7 -> 7.8e-6, for 0.5 ms); lrp_set_precision(LRP_PREC_BF16X3_FAST): every layer
-  // but the image layer (-5 ms, heat-map parity <= 4e-5).
+  // but the image layer (-5 ms, heat-map parity <= 4e-5): forward_fast.
   bool fwd_fast = false;
-  int fwd_split_from() const { return fwd_fast ? 1 : 1000; }
   // Activation chain and denominators in ONE pass on the fp16 MFMA: operands as fp16 pairs hi + lo (22 mantissa bits, x scaled by
   // a power of two per layer and image), product hi*hi' + hi*lo' + lo*hi' in three MFMAs with blocked fp32 accumulation,
-  // weights (w | w+) stacked along N.  (Rounds 1-2 kept the earlier arrangements — two-pass three-way bf16 split, single
-  // activation conv + side-stream Z+ chain — behind LRP_FWD_F16 / LRP_FWD_DUAL / LRP_FWD_X6; removed in round 4: untested.)
+  // weights (w | w+) stacked along N.
   // fp16-pair dual forward with interleaved weight rows: a_l and the gate G_l = a_l / safe(Z+_l) leave the conv's epilogue
   // together where no pool follows (conv_igemm.h ConvArgs::dual_il) — no Z+ tensor, no gate pass.  LRP_FWD_IL=0: stacked rows.
   static bool fwd_il() { return sw().fwd_il != 0; }
@@ -381,7 +374,7 @@ struct Encoder {
     if (B < 1 || B > max_images) return fail(LRP_ERR_INVALID, "B=%d outside [1,%d]", B, max_images);
     LRP_TRY(check_ready());
     ++encode_epoch;
-    for (ConvLayer& L : layers) L.gfull_epoch = encode_epoch;     // (every path writes the full-resolution gates, except the fused pool below)
+    for (ConvLayer& L : layers) L.gfull_epoch = encode_epoch;     // (every path writes the full-resolution gates, except the fused pool: after_pool_gate)
     const size_t img_elems = (size_t)img_h * img_w * 3;
     if (gates_pending) {                               // the previous encode's side work still owns G / bufZ / bufXs
       LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_gates, 0));
@@ -389,310 +382,325 @@ struct Encoder {
     }
     LRP_HIP_CHECK(hipMemsetAsync(act_max.p, 0, act_max.bytes, st));
     LRP_HIP_CHECK(hipMemcpyAsync(images.p, images_dev, B * img_elems * sizeof(float), hipMemcpyDeviceToDevice, st));
-    auto im2col_fp32 = [&]() -> int {
-      const size_t total = (size_t)B * img_h * img_w * 8;
-      hipLaunchKernelGGL(im2col_image_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                         images.as<float>(), a1.as<float>(), B, img_h, img_w);
-      LRP_HIP_CHECK(hipGetLastError());
-      return LRP_OK;
-    };
-    float* x = bufX.as<float>();
-    float* a = bufA.as<float>();
-    float* z = bufZ.as<float>();
-    bool mixed = prec == PREC_BF16X3;
-    for (const ConvLayer& L : layers)
-      if (L.cout & 7) mixed = false;
-    const bool overlap = mixed && side && layers.size() > 1;
-    std::vector<const float*> xin(layers.size() + 1, nullptr);   // overlapped path: input of every conv
-    bool dual = overlap && !fwd_fast;                    // (LRP_PREC_BF16X3_FAST: split-bf16 activation convs + side-stream Z+ chain)
-    for (size_t li = 1; li < layers.size(); ++li)
-      if (((layers[li].cin | layers[li].cout) & 7) || !layers[li].w_fwd_h.p) dual = false;
-    // dual path: the producer hands its consumer the fp16 pairs directly (conv epilogue where no pool follows, the fused
-    // pool kernel where one does) — `in_pairs`: pin already holds the operand of the conv about to run
-    bool in_pairs = false;
-    float *pin = bufXs.as<float>(), *pout = bufXl.as<float>();
-    // ... which needs every layer on the interleaved dual matrix (the pairs and the gate leave one epilogue); scales, maxima
-    // and unscale records are then kept per IMAGE, so an image's result does not depend on the rest of its batch
-    bool emit = dual && fwd_emit() && layers.size() > 1 && layers[0].w_fwd_il.p && !layers[0].pool_after && !(img_elems & 3);
-    for (size_t li = 1; li < layers.size(); ++li)
-      if (!layers[li].w_fwd_il.p) emit = false;          // (interleaved rows: decided when the weights were packed)
-    const size_t per = emit ? (size_t)max_images : 1;    // records per layer
-    auto slots_of = [&](size_t lev) { return act_max.as<unsigned>() + lev * per * ACT_MAX_SLOTS; };
-    auto unscale_of = [&](size_t li) { return act_unscale.as<float>() + li * per; };
-    auto oscale_of = [&](size_t li) { return out_scale.as<float>() + li * per; };
-    if (emit)
-      for (size_t li = 0; li < layers.size(); ++li) {
-        ConvLayer& L = layers[li];
-        if (!L.norm_dirty) continue;
-        LRP_HIP_CHECK(hipMemsetAsync(L.fnorm.p, 0, 2 * sizeof(float), st));
-        // (image layer: the a rows of its 64-wide im2col matrix hold w twice, against x+ and x-: the row sum is 2x the bound)
-        hipLaunchKernelGGL(conv_norm_kernel, dim3(L.cout + 1), dim3(256), 0, st, li == 0 ? L.w_fwd.as<float>() : L.w_fwd_a.as<float>(), L.cout,
-                           li == 0 ? 64 : 9 * conv_cinp(L.cin), L.bias.as<float>(), L.cout, L.fnorm.as<float>());
-        LRP_HIP_CHECK(hipGetLastError());
-        L.norm_dirty = false;
-      }
-    int gate_due = -1;                                 // dual path: layer whose gate waits for the next layer's split (it reads a_l)
-    auto launch_gate = [&](int gl) {
-      ConvLayer& Lg = layers[gl];
-      const size_t ng = (size_t)B * Lg.act_elems();
-      hipLaunchKernelGGL(gate_kernel, dim3(stream_grid(ng / 4)), dim3(256), 0, st,
-                         reinterpret_cast<const f32x4*>(keep_acts ? Lg.Akeep.as<float>() : Lg.G.as<float>()),
-                         reinterpret_cast<const f32x4*>(bufZ.as<float>()), Lg.G.as<f32x4>(), ng / 4);
-    };
-    for (size_t li = 0; li < layers.size(); ++li) {
-      ConvLayer& L = layers[li];
-      const bool top = li + 1 == layers.size();
-      ConvArgs ca{};
-      if (overlap && li > 0) {
-        // activation chain only: a_l = relu(conv(x_l) + b) exact fp32, parked in the storage of its future gate
-        ca.in = xin[li]; ca.NB = B; ca.H = L.H; ca.W = L.W; ca.Cin = L.cin; ca.CinP = conv_cinp(L.cin); ca.taps = 9;
-        ca.bias = L.bias.as<float>(); ca.wpk = L.w_fwd_a.as<float>(); ca.N = L.cout;
-        float* a_out = top ? feat.as<float>() : (keep_acts && !L.pool_after) ? L.Akeep.as<float>() : L.G.as<float>();
-        ca.out = a_out;
-        if (dual) {
-          const size_t n8 = (size_t)B * L.H * L.W * L.cin / 8;
-          unsigned* slots_in = slots_of(li - 1);
-          if (!in_pairs) {
-            if (li == 1)
-              hipLaunchKernelGGL(absmax_slots_kernel, dim3(stream_grid(n8 * 2)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(xin[li]),
-                                 n8 * 2, slots_in);
-            hipLaunchKernelGGL(split_h_scaled_kernel, dim3(stream_grid(n8)), dim3(256), 0, st, xin[li], pin, n8, slots_in,
-                               unscale_of(li), L.wds.as<float>());
-          }
-          if (gate_due >= 0) { launch_gate(gate_due); gate_due = -1; }       // a_{l-1} has been read: it may become G_{l-1} now
-          LRP_HIP_CHECK(hipGetLastError());
-          ConvArgs cd = ca;
-          cd.in = pin; cd.wpk = L.w_fwd_h.as<float>(); cd.N = 2 * L.cout; cd.split = L.cout;
-          cd.out = a_out; cd.out2 = top ? ztop.as<float>() : bufZ.as<float>();
-          cd.in_unscale = unscale_of(li);
-          cd.act_max_out = slots_of(li);
-          cd.scale_per_img = emit ? 1 : 0; cd.img_rows = L.H * L.W; cd.n_imgs = B;
-          cd.dual_il = L.w_fwd_il.p ? 1 : 0;
-          const bool fused_gate = cd.dual_il && !top && !L.pool_after;
-          if (fused_gate) {
-            // a_l and G_l leave the epilogue together: a_l into a ping-pong buffer its consumer (the next layer's split)
-            // reads once (or where the fine-tune step looks for it), the gate straight into its cache
-            if (!keep_acts) a_out = xin[li] == bufA.as<float>() ? bufX.as<float>() : bufA.as<float>();
-            cd.out = a_out; cd.out2 = L.G.as<float>(); cd.dual_gate = 1;
-          }
-          // pairs for the next conv from THIS layer's epilogue (no pool behind it) or from the fused pool kernel below;
-          // their scale comes from a bound that is known now (fwd_scale_kernel), the consumer's unscale with it
-          const bool emit_conv = emit && fused_gate, emit_pool = emit && !top && L.pool_after;
-          if (emit_conv || emit_pool) {
-            hipLaunchKernelGGL(fwd_scale_kernel, dim3(B), dim3(64), 0, st, slots_in, L.fnorm.as<float>(), layers[li + 1].wds.as<float>(),
-                               oscale_of(li), unscale_of(li + 1));
-            LRP_HIP_CHECK(hipGetLastError());
-          }
-          if (emit_conv) { cd.pairs_out = pout; cd.pairs_scale = oscale_of(li); cd.skip_out = keep_acts ? 0 : 1; }
-          // The denominators Z+_l of the layers whose reverse launch is two-term (explain(): up to the last pool, >= 576
-          // products) are computed two-term as well — with the SAME rounded weights hi(w+) the walk multiplies with.
-          // [MI355X: parity at the bench configuration 5.5e-6 -> 4.4e-6, 6 seeds median 4.2e-6 -> 3.3e-6: gate and
-          // transposed conv now belong to one (slightly perturbed) network and the rounding largely cancels in R / Z+;
-          // two-term Z+ in EVERY layer: 1.0e-4, the top block again.]
-          int fterms = 7;
-          if (cd.dual_il && walk_f16 && two_term((int)li)) fterms = 23;
-          // pooled layer: max-pool, arg-max gate (compact form) and the pooled pairs in THIS conv's epilogue — a_l and Z+_l at
-          // full resolution are neither written nor read back (round 4; the pass it replaces: pool_gate_split_kernel below) —
-          // where the launch takes the form that can (conv_plan)
-          ConvAsk ask = conv_ask(EPI_FWD_DUAL, PREC_F16X2, fterms, false, cd);
-          ask.pool_gc = true;
-          const bool pool_fused = emit_pool && !keep_acts && L.Gc.p && L.Gpos.p && conv_plan(ask).ok;
-          if (pool_fused) {
-            cd.pool_gc = L.Gc.as<float>(); cd.pool_pos = L.Gpos.as<unsigned char>(); cd.pairs_out = pout; cd.pairs_scale = oscale_of(li);
-            cd.out = nullptr; cd.out2 = nullptr;
-          }
-          LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, cd, st, PREC_F16X2, fterms));
-          if (top) break;
-          in_pairs = emit_conv || emit_pool;
-          if (in_pairs) { float* t = pin; pin = pout; pout = t; }
-          if (fused_gate) { xin[li + 1] = a_out; continue; }
-          if (L.pool_after && pool_fused) {
-            layers[li].gc_epoch = encode_epoch;
-            layers[li].gfull_epoch = -1;                 // G itself was not written: expanded on demand (full_gate)
-            if (L.idxp.p && L.w_sp.p && sw().sparse_pool) {
-              LRP_HIP_CHECK(conv_sparse_index(L.Gpos.as<unsigned char>(), L.idxp.as<unsigned>(), B, L.H / 2, L.W / 2, L.cout, st));
-              layers[li].idx_epoch = encode_epoch;
-            }
-            xin[li + 1] = L.P.as<float>();               // (not read: the next conv takes the pairs)
-            continue;
-          }
-          if (L.pool_after) {
-            const size_t n = (size_t)B * L.act_elems();
-            if (emit_pool) {
-              // pooled activations as pairs (and fp32 only where the fine-tune step looks for them), arg-max gate: one pass
-              hipLaunchKernelGGL(pool_gate_split_kernel, dim3(stream_grid(n / 32)), dim3(256), 0, st, L.G.as<float>(), bufZ.as<float>(),
-                                 L.G.as<float>(), pin, keep_acts ? L.P.as<float>() : (float*)nullptr, oscale_of(li), B, L.H, L.W, L.cout,
-                                 L.Gc.as<float>(), L.Gpos.as<unsigned char>());
-              if (L.Gc.p) layers[li].gc_epoch = encode_epoch;
-              if (L.idxp.p && L.w_sp.p && sw().sparse_pool) {          // the sparse consumer's index words, once per image
-                LRP_HIP_CHECK(conv_sparse_index(L.Gpos.as<unsigned char>(), L.idxp.as<unsigned>(), B, L.H / 2, L.W / 2, L.cout, st));
-                layers[li].idx_epoch = encode_epoch;
-              }
-            } else {
-              hipLaunchKernelGGL(maxpool2_kernel, dim3(stream_grid(n / 16)), dim3(256), 0, st, a_out, L.P.as<float>(), B, L.H, L.W, L.cout);
-              hipLaunchKernelGGL(pool_gate_kernel, dim3(stream_grid(n / 16)), dim3(256), 0, st, L.G.as<float>(), bufZ.as<float>(),
-                                 (float*)nullptr, L.G.as<float>(), B, L.H, L.W, L.cout);
-            }
-            LRP_HIP_CHECK(hipGetLastError());
-            xin[li + 1] = L.P.as<float>();
-          } else {
-            xin[li + 1] = a_out;
-            gate_due = (int)li;
-          }
-          continue;
-        }
-        if ((int)li >= fwd_split_from()) {
-          // late layers: activation conv in split-bf16 as well (its error passes through few further layers)
-          const size_t n8 = (size_t)B * L.H * L.W * L.cin / 8;
-          hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n8)), dim3(256), 0, st, xin[li], bufXs.as<float>(), n8);
-          LRP_HIP_CHECK(hipGetLastError());
-          ca.in = bufXs.as<float>(); ca.wpk = L.w_fwd_as.as<float>();
-          LRP_HIP_CHECK(conv_launch(EPI_BIAS_RELU, ca, st, PREC_BF16X3));
-        } else {
-          LRP_HIP_CHECK(conv_launch(EPI_BIAS_RELU, ca, st));
-        }
-        if (top) break;
-        if (L.pool_after) {
-          const size_t n = (size_t)B * L.act_elems();
-          hipLaunchKernelGGL(maxpool2_kernel, dim3(stream_grid(n / 16)), dim3(256), 0, st, a_out, L.P.as<float>(), B, L.H, L.W, L.cout);
-          LRP_HIP_CHECK(hipGetLastError());
-          xin[li + 1] = L.P.as<float>();
-        } else {
-          xin[li + 1] = a_out;
-        }
-        continue;
-      }
-      if (li == 0 && emit) {
-        // image layer of the dual forward: the fp32 GEMM over the im2col matrix with interleaved (w | w+-) rows — its epilogue
-        // writes the gate G_1, a_1 as the next conv's fp16 pairs (scale from the images' measured maximum) and raises max|a_1|:
-        // no gate / absmax / split pass, a_1 itself only where the fine-tune step looks for it
-        unsigned* img_slots = slots_of(layers.size());
-        hipLaunchKernelGGL(absmax_img_slots_kernel, dim3(64, B), dim3(256), 0, st, images.as<f32x4>(), img_elems / 4, img_slots);
-        hipLaunchKernelGGL(fwd_scale_kernel, dim3(B), dim3(64), 0, st, img_slots, L.fnorm.as<float>(), layers[1].wds.as<float>(), oscale_of(0),
-                           unscale_of(1));
-        // the im2col matrix as fp16 pairs (scaled per image by its own maximum) and the GEMM on the f16 MFMA — unless the
-        // fine-tune step is on: its weight gradient of this layer is a product over the fp32 im2col matrix (trainer.h)
-        // (the image layer stays on the exact fp32 MFMA: as fp16 pairs it is 0.2-0.4 ms faster per encode and puts the features of
-        //  ill-conditioned nets at 1.0e-5 instead of 6.3e-6 — first-layer errors are inherited by every later layer; round 3 kept
-        //  that variant behind LRP_FWD_L0_F16, round 4 removed it)
-        LRP_TRY(im2col_fp32());
-        LRP_HIP_CHECK(hipGetLastError());
-        ConvArgs c0{};
-        c0.in = a1.as<float>(); c0.NB = B * L.H * L.W; c0.H = 1; c0.W = 1; c0.Cin = 64; c0.CinP = 64; c0.taps = 1;
-        c0.bias = L.bias.as<float>(); c0.wpk = L.w_fwd_il.as<float>(); c0.N = 2 * L.cout; c0.split = L.cout;
-        c0.in_unscale = unscale_of(0);
-        c0.dual_il = 1; c0.dual_gate = 1;
-        c0.out = keep_acts ? L.Akeep.as<float>() : nullptr; c0.skip_out = keep_acts ? 0 : 1;
-        c0.out2 = L.G.as<float>();
-        c0.pairs_out = pin; c0.pairs_scale = oscale_of(0);
-        c0.act_max_out = slots_of(0);
-        c0.scale_per_img = 1; c0.img_rows = L.H * L.W; c0.n_imgs = B;
-        LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, c0, st));
-        in_pairs = true;
-        xin[1] = keep_acts ? L.Akeep.as<float>() : nullptr;
-        continue;
-      }
-      if (li == 0) {
-        LRP_TRY(im2col_fp32());
-        ca.in = a1.as<float>(); ca.NB = B * L.H * L.W; ca.H = 1; ca.W = 1; ca.Cin = 64; ca.CinP = 64; ca.taps = 1;
-      } else {
-        ca.in = x; ca.NB = B; ca.H = L.H; ca.W = L.W; ca.Cin = L.cin; ca.CinP = conv_cinp(L.cin); ca.taps = 9;
-      }
-      ca.bias = L.bias.as<float>();
-      float* a_out = top ? feat.as<float>() : a;
-      float* z_out = top ? ztop.as<float>() : z;
-      if (li > 0 && mixed) {
-        // a_l exact (it feeds the next layer), Z+_l in bf16x3 (its error stays inside gate G_l):
-        // measured on CPU emulation 4e-6 vs 3e-6 relative L1 for the all-fp32 forward.
-        ConvArgs cz = ca;
-        ca.wpk = L.w_fwd_a.as<float>(); ca.N = L.cout; ca.out = a_out;
-        LRP_HIP_CHECK(conv_launch(EPI_BIAS_RELU, ca, st));
-        cz.in = bufXs.as<float>(); cz.wpk = L.w_fwd_zs.as<float>(); cz.N = L.cout; cz.out = z_out;
-        LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, st, PREC_BF16X3));
-      } else {
-        ca.wpk = L.w_fwd.as<float>();
-        ca.N = 2 * L.cout; ca.split = L.cout;
-        ca.out = a_out; ca.out2 = z_out;
-        LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, ca, st));
-      }
-      if (top) break;
-      const size_t n = (size_t)B * L.act_elems();
-      if (L.pool_after) {
-        hipLaunchKernelGGL(pool_gate_kernel, dim3(stream_grid(n / 16)), dim3(256), 0, st, a, z, x, L.G.as<float>(), B, L.H,
-                           L.W, L.cout);
-        LRP_HIP_CHECK(hipGetLastError());
-        // x now holds pool(a): input of the next conv
-      } else {
-        hipLaunchKernelGGL(gate_kernel, dim3(stream_grid(n / 4)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(a),
-                           reinterpret_cast<const f32x4*>(z), L.G.as<f32x4>(), n / 4);
-        LRP_HIP_CHECK(hipGetLastError());
-        float* t = x; x = a; a = t;                   // next input = a_l
-      }
-      xin[li + 1] = x;
-      if (keep_acts) {
-        // layers that run through the ping-pong buffers (the image layer always; every layer of the exact-fp32 / not
-        // overlapped forward): park the next conv's input where layer_input() looks for it
-        const size_t bytes = (size_t)B * L.act_elems() * sizeof(float) / (L.pool_after ? 4 : 1);
-        LRP_HIP_CHECK(hipMemcpyAsync(L.pool_after ? L.P.p : L.Akeep.p, x, bytes, hipMemcpyDeviceToDevice, st));
-      }
-      if (mixed && !overlap) {                        // split8 copy of the next conv's input
-        const size_t n8 = (size_t)B * layers[li + 1].H * layers[li + 1].W * layers[li + 1].cin / 8;
-        hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n8)), dim3(256), 0, st, x, bufXs.as<float>(), n8);
-        LRP_HIP_CHECK(hipGetLastError());
-      }
+    // emitting needs every layer on the interleaved dual matrix (the pairs and the gate leave one epilogue: decided when the
+    // weights were packed)
+    std::vector<int> widths;
+    bool emit_ready = fwd_emit() && !(img_elems & 3);
+    for (const ConvLayer& L : layers) {
+      widths.push_back(L.cout);
+      if (!L.w_fwd_il.p) emit_ready = false;
     }
-    if (dual) {
-      if (gate_due >= 0) launch_gate(gate_due);         // (cannot happen for a net that ends in conv layers feeding the top: kept for safety)
-      LRP_HIP_CHECK(hipGetLastError());
-    } else if (overlap) {
-      // side stream, top layer first: layer l's input x_l = a_{l-1} lives in the gate storage of layer l-1, which
-      // is turned into G_{l-1} only after layer l is done with it
-      LRP_HIP_CHECK(hipEventRecord(ev_fwd, st));
-      LRP_HIP_CHECK(hipStreamWaitEvent(side, ev_fwd, 0));
-      for (size_t li = layers.size() - 1; li >= 1; --li) {
-        ConvLayer& L = layers[li];
-        const bool top = li + 1 == layers.size();
-        const size_t n8 = (size_t)B * L.H * L.W * L.cin / 8;
-        hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n8)), dim3(256), 0, side, xin[li], bufXs.as<float>(), n8);
-        LRP_HIP_CHECK(hipGetLastError());
-        ConvArgs cz{};
-        cz.in = bufXs.as<float>(); cz.NB = B; cz.H = L.H; cz.W = L.W; cz.Cin = L.cin; cz.CinP = conv_cinp(L.cin); cz.taps = 9;
-        cz.bias = L.bias.as<float>(); cz.wpk = L.w_fwd_zs.as<float>(); cz.N = L.cout;
-        cz.out = top ? ztop.as<float>() : bufZ.as<float>();
-        if (!top && !L.pool_after) {
-          // no pool behind this layer: G_l = a_l / safe(Z+_l) in the conv's epilogue, Z+_l never written
-          cz.gate_src = keep_acts ? L.Akeep.as<float>() : L.G.as<float>();
-          cz.out = L.G.as<float>();
-          LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, side, PREC_BF16X3));
-          continue;
-        }
-        LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, side, PREC_BF16X3));
-        if (top) continue;
-        const size_t n = (size_t)B * L.act_elems();
-        if (L.pool_after)
-          hipLaunchKernelGGL(pool_gate_kernel, dim3(stream_grid(n / 16)), dim3(256), 0, side, L.G.as<float>(), bufZ.as<float>(),
-                             (float*)nullptr, L.G.as<float>(), B, L.H, L.W, L.cout);
-        else
-          hipLaunchKernelGGL(gate_kernel, dim3(stream_grid(n / 4)), dim3(256), 0, side,
-                             reinterpret_cast<const f32x4*>(keep_acts ? L.Akeep.as<float>() : L.G.as<float>()),
-                             reinterpret_cast<const f32x4*>(bufZ.as<float>()), L.G.as<f32x4>(), n / 4);
-        LRP_HIP_CHECK(hipGetLastError());
-      }
-      LRP_HIP_CHECK(hipEventRecord(ev_gates, side));
-      gates_pending = true;
-    }
+    const FwdPlan fp = forward_mode(prec == PREC_BF16X3, fwd_fast, widths.data(), widths.size(), layers[0].pool_after, emit_ready);
+    LRP_TRY(fp.mode == FWD_EXACT ? forward_exact(B, st) : fp.mode == FWD_FAST ? forward_fast(B, st)
+            : fp.emit ? forward_pairs_emit(B, st) : forward_pairs_split(B, st));
     encoded = B;
     features_only = false;
     return LRP_OK;
   }
 
+  // ---- launch helpers of the forwards ----
+  static int launched() { LRP_HIP_CHECK(hipGetLastError()); return LRP_OK; }
+  // geometry of the 3x3 conv through layer L over NB images (or relevance maps) reading `in`, C channels wide
+  static ConvArgs conv3x3_args(const ConvLayer& L, int NB, const float* in, int C) {
+    ConvArgs ca{};
+    ca.in = in; ca.NB = NB; ca.H = L.H; ca.W = L.W; ca.Cin = C; ca.CinP = conv_cinp(C); ca.taps = 9;
+    return ca;
+  }
+  static ConvArgs fwd_conv_args(const ConvLayer& L, int B, const float* in) {
+    ConvArgs ca = conv3x3_args(L, B, in, L.cin);
+    ca.bias = L.bias.as<float>();
+    return ca;
+  }
+  // the image layer as a GEMM over its im2col matrix a1 (one row per pixel, 64 columns: 27 x+ | 27 x- | padding)
+  int im2col_gemm_args(int B, hipStream_t st, ConvArgs& ca) {
+    const ConvLayer& L = layers[0];
+    const size_t total = (size_t)B * img_h * img_w * 8;
+    hipLaunchKernelGGL(im2col_image_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                       images.as<float>(), a1.as<float>(), B, img_h, img_w);
+    LRP_HIP_CHECK(hipGetLastError());
+    ca = ConvArgs{};
+    ca.in = a1.as<float>(); ca.NB = B * L.H * L.W; ca.H = 1; ca.W = 1; ca.Cin = 64; ca.CinP = 64; ca.taps = 1;
+    ca.bias = L.bias.as<float>();
+    return LRP_OK;
+  }
+  // G_l = a_l / safe(Z+_l); may run in place (G == a)
+  int gate_pass(ConvLayer& L, int B, const float* a, const float* z, hipStream_t st) {
+    const size_t n = (size_t)B * L.act_elems();
+    hipLaunchKernelGGL(gate_kernel, dim3(stream_grid(n / 4)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(a),
+                       reinterpret_cast<const f32x4*>(z), L.G.as<f32x4>(), n / 4);
+    return launched();
+  }
+  // a_l where the gate pass of a layer finds it when the conv parked it in the gate's own storage
+  const float* parked_act(const ConvLayer& L) const { return keep_acts ? L.Akeep.as<float>() : L.G.as<float>(); }
+  // arg-max gate of a pooled layer at full resolution; pooled != nullptr: pool(a_l) as well
+  int pool_gate_pass(ConvLayer& L, int B, const float* a, const float* z, float* pooled, hipStream_t st) {
+    const size_t n = (size_t)B * L.act_elems();
+    hipLaunchKernelGGL(pool_gate_kernel, dim3(stream_grid(n / 16)), dim3(256), 0, st, a, z, pooled, L.G.as<float>(), B, L.H, L.W, L.cout);
+    return launched();
+  }
+  int maxpool_pass(ConvLayer& L, int B, const float* a, hipStream_t st) {
+    const size_t n = (size_t)B * L.act_elems();
+    hipLaunchKernelGGL(maxpool2_kernel, dim3(stream_grid(n / 16)), dim3(256), 0, st, a, L.P.as<float>(), B, L.H, L.W, L.cout);
+    return launched();
+  }
+  int split_copy(const float* src, size_t n8, hipStream_t st) {      // split8 (bf16 hi | lo) copy of a conv input into bufXs
+    hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n8)), dim3(256), 0, st, src, bufXs.as<float>(), n8);
+    return launched();
+  }
+  // where a layer's activation conv of the overlapped forwards writes a_l: the features, where the fine-tune step looks for
+  // it, or parked in the storage of its future gate
+  float* act_out(ConvLayer& L, bool top) { return top ? feat.as<float>() : (keep_acts && !L.pool_after) ? L.Akeep.as<float>() : L.G.as<float>(); }
+
+  // One layer of the exact forward, and the image layer of every forward that does not emit: dual fp32 GEMM (a_l | Z+_l), gate
+  // or pool-gate pass, x / a ping-pong.  On return x holds the next conv's input.
+  int dual_fp32_layer(size_t li, int B, hipStream_t st, float*& x, float*& a, float* z) {
+    ConvLayer& L = layers[li];
+    const bool top = li + 1 == layers.size();
+    ConvArgs ca;
+    if (li == 0) LRP_TRY(im2col_gemm_args(B, st, ca));
+    else ca = fwd_conv_args(L, B, x);
+    ca.wpk = L.w_fwd.as<float>(); ca.N = 2 * L.cout; ca.split = L.cout;
+    ca.out = top ? feat.as<float>() : a; ca.out2 = top ? ztop.as<float>() : z;
+    LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, ca, st));
+    if (top) return LRP_OK;
+    if (L.pool_after) {
+      LRP_TRY(pool_gate_pass(L, B, a, z, x, st));      // x now holds pool(a): input of the next conv
+    } else {
+      LRP_TRY(gate_pass(L, B, a, z, st));
+      std::swap(x, a);                                 // next input = a_l
+    }
+    if (keep_acts) {
+      // these layers run through the ping-pong buffers: park the next conv's input where layer_input() looks for it
+      const size_t bytes = (size_t)B * L.act_elems() * sizeof(float) / (L.pool_after ? 4 : 1);
+      LRP_HIP_CHECK(hipMemcpyAsync(L.pool_after ? L.P.p : L.Akeep.p, x, bytes, hipMemcpyDeviceToDevice, st));
+    }
+    return LRP_OK;
+  }
+
+  // LRP_PREC_FP32, a width % 8 != 0 or a one-layer net (fwd_mode.h): everything on the caller's stream, exact fp32
+  int forward_exact(int B, hipStream_t st) {
+    float *x = bufX.as<float>(), *a = bufA.as<float>();
+    for (size_t li = 0; li < layers.size(); ++li) LRP_TRY(dual_fp32_layer(li, B, st, x, a, bufZ.as<float>()));
+    return LRP_OK;
+  }
+
+  // LRP_PREC_BF16X3_FAST: the caller's stream runs the activation chain a_1..a_top alone, split-bf16 behind the image layer (its
+  // error passes through few further layers); the denominators and the gates follow on the side stream.
+  int forward_fast(int B, hipStream_t st) {
+    std::vector<const float*> xin(layers.size() + 1, nullptr);   // input of every conv
+    float *x = bufX.as<float>(), *a = bufA.as<float>();
+    LRP_TRY(dual_fp32_layer(0, B, st, x, a, bufZ.as<float>()));
+    xin[1] = x;
+    for (size_t li = 1; li < layers.size(); ++li) {
+      ConvLayer& L = layers[li];
+      const bool top = li + 1 == layers.size();
+      LRP_TRY(split_copy(xin[li], (size_t)B * L.H * L.W * L.cin / 8, st));
+      ConvArgs ca = fwd_conv_args(L, B, bufXs.as<float>());
+      ca.wpk = L.w_fwd_as.as<float>(); ca.N = L.cout; ca.out = act_out(L, top);
+      LRP_HIP_CHECK(conv_launch(EPI_BIAS_RELU, ca, st, PREC_BF16X3));
+      if (top) break;
+      if (L.pool_after) LRP_TRY(maxpool_pass(L, B, ca.out, st));
+      xin[li + 1] = L.pool_after ? L.P.as<float>() : ca.out;
+    }
+    // side stream, top layer first: layer l's input x_l = a_{l-1} lives in the gate storage of layer l-1, which
+    // is turned into G_{l-1} only after layer l is done with it
+    LRP_HIP_CHECK(hipEventRecord(ev_fwd, st));
+    LRP_HIP_CHECK(hipStreamWaitEvent(side, ev_fwd, 0));
+    for (size_t li = layers.size() - 1; li >= 1; --li) {
+      ConvLayer& L = layers[li];
+      const bool top = li + 1 == layers.size();
+      LRP_TRY(split_copy(xin[li], (size_t)B * L.H * L.W * L.cin / 8, side));
+      ConvArgs cz = fwd_conv_args(L, B, bufXs.as<float>());
+      cz.wpk = L.w_fwd_zs.as<float>(); cz.N = L.cout; cz.out = top ? ztop.as<float>() : bufZ.as<float>();
+      if (!top && !L.pool_after) {
+        // no pool behind this layer: G_l = a_l / safe(Z+_l) in the conv's epilogue, Z+_l never written
+        cz.gate_src = parked_act(L); cz.out = L.G.as<float>();
+      }
+      LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, side, PREC_BF16X3));
+      if (!top && L.pool_after) LRP_TRY(pool_gate_pass(L, B, L.G.as<float>(), bufZ.as<float>(), nullptr, side));
+    }
+    LRP_HIP_CHECK(hipEventRecord(ev_gates, side));
+    gates_pending = true;
+    return LRP_OK;
+  }
+
+  // ---- fp16-pair dual forward (the default) ----
+  // Scale records of layer / level `lev`: ACT_MAX_SLOTS maxima of its output, 2^-k of its input, 2^k of the pairs it emits.
+  // `per` of each per layer: one for the whole batch, or — emitting — one per image, so that an image's result does not depend
+  // on the rest of its batch.
+  struct ScaleRecs {
+    unsigned* max; float *unscale, *oscale; size_t per;
+    unsigned* slots_of(size_t lev) const { return max + lev * per * ACT_MAX_SLOTS; }
+    float* unscale_of(size_t li) const { return unscale + li * per; }
+    float* oscale_of(size_t li) const { return oscale + li * per; }
+  };
+  ScaleRecs scale_recs(size_t per) const { return {act_max.as<unsigned>(), act_unscale.as<float>(), out_scale.as<float>(), per}; }
+  // the dual conv a_l | Z+_l of layer li >= 1 over the pairs in `pin`; a_l goes to act_out, Z+_l to ztop / bufZ
+  ConvArgs dual_pairs_args(size_t li, int B, const float* pin, const ScaleRecs& r, bool per_img) {
+    ConvLayer& L = layers[li];
+    const bool top = li + 1 == layers.size();
+    ConvArgs cd = fwd_conv_args(L, B, pin);
+    cd.wpk = L.w_fwd_h.as<float>(); cd.N = 2 * L.cout; cd.split = L.cout;
+    cd.out = act_out(L, top); cd.out2 = top ? ztop.as<float>() : bufZ.as<float>();
+    cd.in_unscale = r.unscale_of(li);
+    cd.act_max_out = r.slots_of(li);
+    cd.scale_per_img = per_img ? 1 : 0; cd.img_rows = L.H * L.W; cd.n_imgs = B;
+    cd.dual_il = L.w_fwd_il.p ? 1 : 0;
+    return cd;
+  }
+  // no pool behind an interleaved layer: a_l and G_l leave the epilogue together — a_l into the ping-pong buffer its consumer
+  // does not read from (or where the fine-tune step looks for it), the gate straight into its cache
+  void fuse_gate(ConvLayer& L, ConvArgs& cd, const float* x_in) {
+    if (!keep_acts) cd.out = x_in == bufA.as<float>() ? bufX.as<float>() : bufA.as<float>();
+    cd.out2 = L.G.as<float>(); cd.dual_gate = 1;
+  }
+  // The denominators Z+_l of the layers whose reverse launch is two-term (explain(): up to the last pool, >= 576
+  // products) are computed two-term as well — with the SAME rounded weights hi(w+) the walk multiplies with.
+  // [MI355X: parity at the bench configuration 5.5e-6 -> 4.4e-6, 6 seeds median 4.2e-6 -> 3.3e-6: gate and
+  // transposed conv now belong to one (slightly perturbed) network and the rounding largely cancels in R / Z+;
+  // two-term Z+ in EVERY layer: 1.0e-4, the top block again.]
+  int fwd_terms(size_t li, const ConvArgs& cd) const { return cd.dual_il && walk_f16 && two_term((int)li) ? 23 : 7; }
+  // behind the pool gate of layer li, fused into the conv or a pass of its own: what this encode left for the walks
+  int after_pool_gate(size_t li, int B, hipStream_t st, bool full_written) {
+    ConvLayer& L = layers[li];
+    if (L.Gc.p) L.gc_epoch = encode_epoch;
+    if (!full_written) L.gfull_epoch = -1;             // G itself was not written: expanded on demand (full_gate)
+    if (L.idxp.p && L.w_sp.p && sw().sparse_pool) {    // the sparse consumer's index words, once per image
+      LRP_HIP_CHECK(conv_sparse_index(L.Gpos.as<unsigned char>(), L.idxp.as<unsigned>(), B, L.H / 2, L.W / 2, L.cout, st));
+      L.idx_epoch = encode_epoch;
+    }
+    return LRP_OK;
+  }
+
+  // LRP_FWD_EMIT=0, or a layer without interleaved rows: one scale per batch; absmax (first conv), split, and — where the rows
+  // are stacked — gate passes between the convs
+  int forward_pairs_split(int B, hipStream_t st) {
+    const ScaleRecs r = scale_recs(1);
+    float* pin = bufXs.as<float>();
+    float *x = bufX.as<float>(), *a = bufA.as<float>();
+    LRP_TRY(dual_fp32_layer(0, B, st, x, a, bufZ.as<float>()));
+    const float* x_in = x;                             // fp32 input of the conv about to run
+    int gate_due = -1;                                 // layer whose gate waits for the next layer's split (it reads a_l)
+    for (size_t li = 1; li < layers.size(); ++li) {
+      ConvLayer& L = layers[li];
+      const bool top = li + 1 == layers.size();
+      const size_t n8 = (size_t)B * L.H * L.W * L.cin / 8;
+      if (li == 1)
+        hipLaunchKernelGGL(absmax_slots_kernel, dim3(stream_grid(n8 * 2)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(x_in),
+                           n8 * 2, r.slots_of(0));
+      hipLaunchKernelGGL(split_h_scaled_kernel, dim3(stream_grid(n8)), dim3(256), 0, st, x_in, pin, n8, r.slots_of(li - 1),
+                         r.unscale_of(li), L.wds.as<float>());
+      LRP_HIP_CHECK(hipGetLastError());
+      if (gate_due >= 0) {                             // a_{l-1} has been read: it may become G_{l-1} now
+        LRP_TRY(gate_pass(layers[gate_due], B, parked_act(layers[gate_due]), bufZ.as<float>(), st));
+        gate_due = -1;
+      }
+      ConvArgs cd = dual_pairs_args(li, B, pin, r, false);
+      const bool fused_gate = cd.dual_il && !top && !L.pool_after;
+      if (fused_gate) fuse_gate(L, cd, x_in);
+      LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, cd, st, PREC_F16X2, fwd_terms(li, cd)));
+      if (top) break;
+      x_in = cd.out;
+      if (L.pool_after) {
+        LRP_TRY(maxpool_pass(L, B, cd.out, st));
+        LRP_TRY(pool_gate_pass(L, B, L.G.as<float>(), bufZ.as<float>(), nullptr, st));
+        x_in = L.P.as<float>();
+      } else if (!fused_gate) {
+        gate_due = (int)li;
+      }
+    }
+    return LRP_OK;
+  }
+
+  // The default: the producer hands its consumer the fp16 pairs directly — the conv's epilogue where no pool follows, the fused
+  // pool (or the pool pass) where one does; their scale comes from a bound that is known before the conv runs (fwd_scale_kernel:
+  // the input's measured maximum times the layer's norm), the consumer's unscale with it.  No absmax, split or gate pass.
+  int forward_pairs_emit(int B, hipStream_t st) {
+    const ScaleRecs r = scale_recs((size_t)max_images);
+    for (ConvLayer& L : layers) {
+      if (!L.norm_dirty) continue;
+      LRP_HIP_CHECK(hipMemsetAsync(L.fnorm.p, 0, 2 * sizeof(float), st));
+      // (image layer: the a rows of its 64-wide im2col matrix hold w twice, against x+ and x-: the row sum is 2x the bound)
+      const bool img = &L == &layers[0];
+      hipLaunchKernelGGL(conv_norm_kernel, dim3(L.cout + 1), dim3(256), 0, st, img ? L.w_fwd.as<float>() : L.w_fwd_a.as<float>(), L.cout,
+                         img ? 64 : 9 * conv_cinp(L.cin), L.bias.as<float>(), L.cout, L.fnorm.as<float>());
+      LRP_HIP_CHECK(hipGetLastError());
+      L.norm_dirty = false;
+    }
+    float *pin = bufXs.as<float>(), *pout = bufXl.as<float>();   // pin: the operand of the conv about to run
+    LRP_TRY(image_layer_emit(B, st, r, pin));
+    const float* x_in = keep_acts ? layers[0].Akeep.as<float>() : nullptr;   // where a_{l-1} went as fp32 (not read here)
+    for (size_t li = 1; li < layers.size(); ++li) {
+      ConvLayer& L = layers[li];
+      const bool top = li + 1 == layers.size();
+      ConvArgs cd = dual_pairs_args(li, B, pin, r, true);
+      if (!top) {
+        hipLaunchKernelGGL(fwd_scale_kernel, dim3(B), dim3(64), 0, st, r.slots_of(li - 1), L.fnorm.as<float>(), layers[li + 1].wds.as<float>(),
+                           r.oscale_of(li), r.unscale_of(li + 1));
+        LRP_HIP_CHECK(hipGetLastError());
+      }
+      bool pool_fused = false;
+      if (!top && !L.pool_after) {
+        fuse_gate(L, cd, x_in);
+        cd.pairs_out = pout; cd.pairs_scale = r.oscale_of(li); cd.skip_out = keep_acts ? 0 : 1;
+      }
+      const int fterms = fwd_terms(li, cd);
+      if (!top && L.pool_after) {
+        // max-pool, arg-max gate (compact form) and the pooled pairs in THIS conv's epilogue — a_l and Z+_l at full resolution
+        // are neither written nor read back — where the launch takes the form that can (conv_plan)
+        ConvAsk ask = conv_ask(EPI_FWD_DUAL, PREC_F16X2, fterms, false, cd);
+        ask.pool_gc = true;
+        pool_fused = !keep_acts && L.Gc.p && L.Gpos.p && conv_plan(ask).ok;
+        if (pool_fused) {
+          cd.pool_gc = L.Gc.as<float>(); cd.pool_pos = L.Gpos.as<unsigned char>(); cd.pairs_out = pout; cd.pairs_scale = r.oscale_of(li);
+          cd.out = nullptr; cd.out2 = nullptr;
+        }
+      }
+      LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, cd, st, PREC_F16X2, fterms));
+      if (top) break;
+      std::swap(pin, pout);
+      x_in = L.pool_after ? L.P.as<float>() : cd.out;
+      if (!L.pool_after) continue;
+      if (!pool_fused) {
+        // LRP_POOL_FUSED=0, the fine-tune step, or a launch that cannot pool: pooled activations as pairs (and fp32 only where
+        // the fine-tune step looks for them) and the arg-max gate in one pass behind the conv
+        const size_t n = (size_t)B * L.act_elems();
+        hipLaunchKernelGGL(pool_gate_split_kernel, dim3(stream_grid(n / 32)), dim3(256), 0, st, L.G.as<float>(), bufZ.as<float>(),
+                           L.G.as<float>(), pin, keep_acts ? L.P.as<float>() : (float*)nullptr, r.oscale_of(li), B, L.H, L.W, L.cout,
+                           L.Gc.as<float>(), L.Gpos.as<unsigned char>());
+        LRP_HIP_CHECK(hipGetLastError());
+      }
+      LRP_TRY(after_pool_gate(li, B, st, !pool_fused));
+    }
+    return LRP_OK;
+  }
+
+  // Image layer of the emitting forward: the fp32 GEMM over the im2col matrix with interleaved (w | w+-) rows — its epilogue
+  // writes the gate G_1, a_1 as the next conv's fp16 pairs (scale from the images' measured maximum) and raises max|a_1|:
+  // no gate / absmax / split pass, a_1 itself only where the fine-tune step looks for it.
+  // (It stays on the exact fp32 MFMA: as fp16 pairs it is 0.2-0.4 ms faster per encode and puts the features of
+  //  ill-conditioned nets at 1.0e-5 instead of 6.3e-6 — first-layer errors are inherited by every later layer.)
+  int image_layer_emit(int B, hipStream_t st, const ScaleRecs& r, float* pairs_out) {
+    ConvLayer& L = layers[0];
+    unsigned* img_slots = r.slots_of(layers.size());
+    hipLaunchKernelGGL(absmax_img_slots_kernel, dim3(64, B), dim3(256), 0, st, images.as<f32x4>(), (size_t)img_h * img_w * 3 / 4, img_slots);
+    hipLaunchKernelGGL(fwd_scale_kernel, dim3(B), dim3(64), 0, st, img_slots, L.fnorm.as<float>(), layers[1].wds.as<float>(), r.oscale_of(0),
+                       r.unscale_of(1));
+    ConvArgs c0;
+    LRP_TRY(im2col_gemm_args(B, st, c0));
+    c0.wpk = L.w_fwd_il.as<float>(); c0.N = 2 * L.cout; c0.split = L.cout;
+    c0.in_unscale = r.unscale_of(0);
+    c0.dual_il = 1; c0.dual_gate = 1;
+    c0.out = keep_acts ? L.Akeep.as<float>() : nullptr; c0.skip_out = keep_acts ? 0 : 1;
+    c0.out2 = L.G.as<float>();
+    c0.pairs_out = pairs_out; c0.pairs_scale = r.oscale_of(0);
+    c0.act_max_out = r.slots_of(0);
+    c0.scale_per_img = 1; c0.img_rows = L.H * L.W; c0.n_imgs = B;
+    LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, c0, st));
+    return LRP_OK;
+  }
+
   // ---- reverse walk, n relevance maps at once ---------------------------------------------
-  // R_feat_dev (n, top_h*top_w, top_c) -> R_img_dev (n, img_h, img_w, 3); row2img_dev: device int[n]
-  // walk: 0 = LRP (LRPSequentialPresetA); gradient baselines (gradient_based.py:101-265) on the same caches:
-  //   1 = Gradient, 2 = InputTimesGradient, 3 = GuidedBackprop — backward-data convs with the full w, the LRP gate
-  //   used as the ReLU/arg-max mask, exact fp32.
-  // layer_hook (fine-tune step): called with (li, dZ_li) — the gradient at the pre-activation of conv li, n x H x W x cout —
-  // before that layer's backward-data conv is launched; the image layer itself is then skipped (R_img_dev may be null).
   // The walks that read a pooled layer's gate at full resolution (EPI_MUL_UP2: the gradient baselines, the fp32 and fast modes,
   // pooled boundaries without a pairs consumer, LRP_UP2_COMPACT=0) after an encode whose fused pool epilogue left the compact form only
   int full_gate(int li, hipStream_t st) {
@@ -707,6 +715,137 @@ struct Encoder {
     return LRP_OK;
   }
 
+  // What one explain call runs, decided once at its top (walk_mode)
+  struct WalkMode {
+    int n = 0, walk = 0, run_prec = PREC_FP32;
+    bool hook = false;                                 // fine-tune step: the layer hook is called, the image layer skipped
+    bool split = false, hook_split = false, f16 = false, fold_on = false;
+    // the default walk: what the compact pool interface, the sparse consumers and the folded image layer belong to
+    bool lrp_split() const { return split && !f16 && walk == 0 && !hook; }
+  };
+  WalkMode walk_mode(int n, int walk, bool hook) const {
+    WalkMode m;
+    m.n = n; m.walk = walk; m.hook = hook;
+    m.split = prec == PREC_BF16X3 && walk == 0;        // the LRP walk on split-bf16 operands
+    // Fine-tune step (hook, walk = 1) in the default arithmetic: the backward-data convs run split-bf16 too —
+    // bf16 operands (hi + lo), three MFMAs per product, fp32 accumulate; the hook still sees plain fp32 dZ (the weight
+    // gradient reads it), so every layer's dZ is written fp32 and re-split by one streaming pass in front of its conv.
+    m.hook_split = prec == PREC_BF16X3 && walk == 1 && hook;
+    for (const ConvLayer& L : layers)
+      if (L.cout & 7) m.split = m.hook_split = false;   // split8 groups need widths % 8 == 0: exact fp32 otherwise
+    for (size_t li = 1; li < layers.size(); ++li)
+      if (!layers[li].w_bwd_full_s.p) m.hook_split = false;
+    // LRP_PREC_F16X2: fp16 pairs for S, one fp16 per weight, per-token power-of-two scales (conv_igemm.h PREC_F16X2);
+    // needs the fused image layer (the chain's scale is undone in its epilogue)
+    m.f16 = m.split && walk_f16 && img_fused();
+    m.run_prec = m.f16 ? PREC_F16X2 : (m.split || m.hook_split) ? PREC_BF16X3 : PREC_FP32;
+    // Image layer folded into the epilogue of the layer above it (ConvArgs::img_part): S_1 — 4.1 GB written, 4.5 GB read at
+    // the bench configuration — never goes to memory; per tile 160 positions x 6 partial sums do, and a streaming pass
+    // adds them up in a fixed order [MI355X, same box: block1_conv2 4.25 -> 4.57 ms (it now also runs the tap GEMM and the
+    // in-tile stencil), image layer 1.29 -> 0.18 ms, walk 26.1-26.3 -> 25.3 ms; heat-maps unchanged to fp32 round-off,
+    // batch invariance bit-exact].  LRP_IMG_FOLD=0 disables.
+    m.fold_on = sw().img_fold != 0 && m.lrp_split() && img_fused() && layers.size() > 1 && !layers[0].pool_after &&
+                layers[1].cin == 64 && layers[0].w_bwd_s.p != nullptr;
+    return m;
+  }
+  // conv_plan's answer for the dense launch through layer lc (lc >= 1) of this walk: with the folded image layer on it where
+  // that is wanted, and reading the compact pool interface or not
+  ConvPlan walk_plan(const WalkMode& m, int lc, bool up2) const {
+    const ConvLayer& Lc = layers[lc];
+    ConvAsk q;
+    q.epi = layers[lc - 1].pool_after ? EPI_MUL_UP2 : EPI_MUL; q.prec = m.run_prec;      // (asked for the split-bf16 walk only)
+    q.NB = m.n; q.H = Lc.H; q.W = Lc.W; q.N = Lc.cin; q.Cin = Lc.cout; q.taps = 9;
+    q.frag = m.split && m.walk == 0 && Lc.w_bwd_frag.p != nullptr;
+    q.up2_src = up2; q.img_part = lc == 1 && m.fold_on;
+    return conv_plan(q);
+  }
+  // Does layer lc's launch run on the 2:4-sparse matrix cores (conv_sparse.h)?  Decided by the layer's shape, the precision
+  // and what this encode left — never by the token or image count: sparse and dense sum in different orders, and a picture's
+  // heat-map must not depend on the batch it is explained in.  LRP_SPARSE_POOL=0 disables.
+  bool sparse_consumer(const WalkMode& m, int lc) const {
+    if (lc < 1) return false;
+    const ConvLayer& Lc = layers[lc];
+    return sw().sparse_pool && Lc.w_sp.p && Lc.idxp.p && Lc.idx_epoch == encode_epoch && !layers[lc - 1].pool_after && m.lrp_split() &&
+           sp_scp.p != nullptr;
+  }
+  // Compact pool interface (conv_igemm.h ConvArgs::up2_src): the producer of a pooled boundary (layer li, its consumer li - 1)
+  // multiplies with the consumer's COMPACT gate (one value per window and channel, at the producer's resolution) and writes
+  // S_c as bf16 pairs at POOLED resolution; the consumer builds its resident image from the pairs and the position bytes:
+  // the 4x-expanded, 75 %-zero tensor is neither written nor read.  Only two dense consumers can: the folded weights-in-registers
+  // launch (VGG16 block1_conv2: per-token tiles, its window loader) and the pipelined halo kernels; conv_plan says whether the
+  // consumer's launch is one of them, and both need a compact gate from this encode.  Every other pooled boundary takes
+  // EPI_MUL_UP2 (the expanded tensor; same fp32 product, same pairs).  LRP_UP2_COMPACT=0 disables.
+  // Does the launch of layer li write those pairs for its consumer li - 1?  A sparse consumer reads nothing else, so its
+  // producer writes them whatever LRP_UP2_COMPACT / LRP_UP2_PW say and whatever tile the producer takes (a plain EPI_MUL
+  // epilogue with the compact gate); those two switches govern the boundaries whose consumer is dense.
+  bool writes_pairs(const WalkMode& m, int li) const {
+    const ConvLayer& P = layers[li - 1];
+    if (!P.pool_after || !m.lrp_split() || li < 2 || (P.cout & 7) || !P.Gc.p || P.gc_epoch != encode_epoch) return false;
+    if (sparse_consumer(m, li - 1)) return true;
+    return sw().up2_compact != 0 && walk_plan(m, li - 1, true).ok;
+  }
+  int* lev_exp(int lev) const { return tok_exp.as<int>() + (size_t)lev * max_tokens; }          // PREC_F16X2: per-token scale
+  unsigned* lev_max(int lev) const { return tok_max.as<unsigned>() + (size_t)lev * max_tokens; }   // exponents / maxima of level lev
+  // algorithmic flops of the reverse launch through layer li (the image layer: 6 sums per pixel and tap)
+  double layer_flop(int n, int li) const { return 2.0 * (double)n * layers[li].H * layers[li].W * 9.0 * layers[li].cout * (li == 0 ? 6 : layers[li].cin); }
+
+  // top of the chain: S_top = R / safe(Z+_top) in the form the walk's first launch reads (gradient walks: the head's gradient
+  // through the top ReLU)
+  int top_relevance(const WalkMode& m, const int* row2img_dev, const float* R_feat_dev, float* S, hipStream_t st) {
+    const ConvLayer& T = layers.back();
+    const size_t per4 = T.act_elems() / 4, per8 = T.act_elems() / 8;
+    const int n = m.n;
+    if (m.walk != 0) {
+      hipLaunchKernelGGL(grad_top_kernel, dim3(stream_grid((size_t)n * per4)), dim3(256), 0, st,
+                         reinterpret_cast<const f32x4*>(R_feat_dev), feat.as<f32x4>(), row2img_dev,
+                         reinterpret_cast<f32x4*>(S), n, per4, m.walk == 3 ? 1 : 0);
+    } else if (m.f16) {
+      const int top = (int)layers.size() - 1;
+      hipLaunchKernelGGL(top_divide_f16_kernel, dim3(n), dim3(256), 0, st, R_feat_dev, ztop.as<float>(), row2img_dev, S,
+                         per8, lev_exp(top), lev_max(top));
+    } else if (m.split) {
+      hipLaunchKernelGGL(top_divide_split_kernel, dim3(stream_grid((size_t)n * per8)), dim3(256), 0, st, R_feat_dev,
+                         ztop.as<float>(), row2img_dev, S, n, per8);
+    } else {
+      hipLaunchKernelGGL(top_divide_kernel, dim3(stream_grid((size_t)n * per4)), dim3(256), 0, st,
+                         reinterpret_cast<const f32x4*>(R_feat_dev), ztop.as<f32x4>(), row2img_dev,
+                         reinterpret_cast<f32x4*>(S), n, per4);
+    }
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  }
+  // the pooled boundary below layer li on the 2:4-sparse matrix cores (conv_sparse.h): S_c re-laid chunk-major, then one launch per class
+  int sparse_boundary(int li, int n, const int* row2img_dev, const float* S, float* out, hipStream_t st) {
+    const ConvLayer& L = layers[li];
+    const int Hp = L.H / 2, Wp = L.W / 2;
+    const size_t n_sets = (size_t)n * Hp * Wp * (L.cout / 8);
+    prof.begin(st);
+    hipLaunchKernelGGL(conv_sparse_relayout_kernel, dim3(stream_grid(n_sets)), dim3(256), 0, st, S, sp_scp.as<float>(), n_sets, Hp * Wp, L.cout);
+    LRP_HIP_CHECK(hipGetLastError());
+    SparseArgs sa{};
+    sa.sc = sp_scp.as<float>(); sa.idxp = L.idxp.as<unsigned>(); sa.wsp = L.w_sp.as<float>(); sa.gate = layers[li - 1].G.as<float>(); sa.out = out;
+    sa.row2img = row2img_dev; sa.NB = n; sa.Hp = Hp; sa.Wp = Wp; sa.C = L.cout; sa.N = L.cin;
+    LRP_HIP_CHECK(conv_sparse_launch(sa, st));
+    prof.end(st, layer_flop(n, li));
+    return LRP_OK;
+  }
+  // the folded image layer's second half: the tiles' partial sums -> R_img (its algorithmic flops are booked on this record)
+  int fold_image_sum(int n, const ConvPlan& fold, const float* part, const int* row2img_dev, float* R_img_dev, hipStream_t st) {
+    const ConvLayer& L0 = layers[0];
+    prof.begin(st);
+    hipLaunchKernelGGL(img_partial_sum_kernel, dim3(stream_grid((size_t)n * L0.H * L0.W)), dim3(256), 0, st, part, images.as<float>(),
+                       row2img_dev, R_img_dev, n, L0.H, L0.W, fold.th, fold.tw, fold.cols_t, 0);
+    LRP_HIP_CHECK(hipGetLastError());
+    prof.end(st, layer_flop(n, 0));
+    return LRP_OK;
+  }
+
+  // R_feat_dev (n, top_h*top_w, top_c) -> R_img_dev (n, img_h, img_w, 3); row2img_dev: device int[n]
+  // walk: 0 = LRP (LRPSequentialPresetA); gradient baselines (gradient_based.py:101-265) on the same caches:
+  //   1 = Gradient, 2 = InputTimesGradient, 3 = GuidedBackprop — backward-data convs with the full w, the LRP gate
+  //   used as the ReLU/arg-max mask, exact fp32.
+  // layer_hook (fine-tune step): called with (li, dZ_li) — the gradient at the pre-activation of conv li, n x H x W x cout —
+  // before that layer's backward-data conv is launched; the image layer itself is then skipped (R_img_dev may be null).
   int explain(int n, const int* row2img_dev, const float* R_feat_dev, float* R_img_dev, hipStream_t st, int walk = 0,
               const std::function<int(int, const float*)>* layer_hook = nullptr) {
     const int* r2i_host = row2img_host;
@@ -715,22 +854,9 @@ struct Encoder {
     if (walk < 0 || walk > 3) return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
     if (encoded < 1 || features_only) return fail(LRP_ERR_STATE, "lrp_encode_images must run before the CNN explain");
     if (gates_pending) LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_gates, 0));   // gates / Z_top come from the side stream
-    const ConvLayer& T = layers.back();
-    float* S = s0.as<float>();
-    float* Snext = s1.as<float>();
-    bool split = prec == PREC_BF16X3 && walk == 0;
-    // Fine-tune step (layer_hook, walk = 1) in the default arithmetic: the backward-data convs run split-bf16 too —
-    // bf16 operands (hi + lo), three MFMAs per product, fp32 accumulate; the hook still sees plain fp32 dZ (the weight
-    // gradient reads it), so every layer's dZ is written fp32 and re-split by one streaming pass in front of its conv.
-    bool hook_split = prec == PREC_BF16X3 && walk == 1 && layer_hook != nullptr;
-    for (const ConvLayer& L : layers)
-      if (L.cout & 7) split = hook_split = false;       // split8 groups need widths % 8 == 0: exact fp32 otherwise
-    for (size_t li = 1; li < layers.size(); ++li)
-      if (!layers[li].w_bwd_full_s.p) hook_split = false;
-    // LRP_PREC_F16X2: fp16 pairs for S, one fp16 per weight, per-token power-of-two scales (conv_igemm.h PREC_F16X2);
-    // needs the fused image layer (the chain's scale is undone in its epilogue)
-    const bool f16 = split && walk_f16 && img_fused();
-    if (f16) {
+    const WalkMode m = walk_mode(n, walk, layer_hook != nullptr);
+    float *S = s0.as<float>(), *Snext = s1.as<float>();
+    if (m.f16) {
       const size_t cnt = (layers.size() + 1) * (size_t)max_tokens;
       if (!tok_exp.p) {
         int64_t dummy = 0;
@@ -740,99 +866,30 @@ struct Encoder {
       }
       LRP_HIP_CHECK(hipMemsetAsync(tok_max.p, 0, cnt * sizeof(unsigned), st));
     }
-    auto lev_exp = [&](int lev) { return tok_exp.as<int>() + (size_t)lev * max_tokens; };
-    auto lev_max = [&](int lev) { return tok_max.as<unsigned>() + (size_t)lev * max_tokens; };
-    const int run_prec = f16 ? PREC_F16X2 : (split || hook_split) ? PREC_BF16X3 : PREC_FP32;
-    if (walk != 0) {
-      const size_t per4 = T.act_elems() / 4;
-      hipLaunchKernelGGL(grad_top_kernel, dim3(stream_grid((size_t)n * per4)), dim3(256), 0, st,
-                         reinterpret_cast<const f32x4*>(R_feat_dev), feat.as<f32x4>(), row2img_dev,
-                         reinterpret_cast<f32x4*>(S), n, per4, walk == 3 ? 1 : 0);
-      LRP_HIP_CHECK(hipGetLastError());
-    } else if (f16) {
-      const int top = (int)layers.size() - 1;
-      hipLaunchKernelGGL(top_divide_f16_kernel, dim3(n), dim3(256), 0, st, R_feat_dev, ztop.as<float>(), row2img_dev, S,
-                         T.act_elems() / 8, lev_exp(top), lev_max(top));
-      LRP_HIP_CHECK(hipGetLastError());
-    } else if (split) {
-      const size_t per8 = T.act_elems() / 8;
-      hipLaunchKernelGGL(top_divide_split_kernel, dim3(stream_grid((size_t)n * per8)), dim3(256), 0, st, R_feat_dev,
-                         ztop.as<float>(), row2img_dev, S, n, per8);
-      LRP_HIP_CHECK(hipGetLastError());
-    } else {
-      const size_t per4 = T.act_elems() / 4;
-      hipLaunchKernelGGL(top_divide_kernel, dim3(stream_grid((size_t)n * per4)), dim3(256), 0, st,
-                         reinterpret_cast<const f32x4*>(R_feat_dev), ztop.as<f32x4>(), row2img_dev,
-                         reinterpret_cast<f32x4*>(S), n, per4);
-      LRP_HIP_CHECK(hipGetLastError());
-    }
-    // Compact pool interface (conv_igemm.h ConvArgs::up2_src): the producer of a pooled boundary (layer li, its consumer li - 1)
-    // multiplies with the consumer's COMPACT gate (one value per window and channel, at the producer's resolution) and writes
-    // S_c as bf16 pairs at POOLED resolution; the consumer builds its resident image from the pairs and the position bytes:
-    // the 4x-expanded, 75 %-zero tensor is neither written nor read.  Only two consumers can: the folded weights-in-registers
-    // launch (VGG16 block1_conv2: per-token tiles, its window loader) and the pipelined halo kernels; conv_plan says whether the
-    // consumer's launch is one of them, and both need a compact gate from this encode.  Every other pooled boundary takes EPI_MUL_UP2 (the expanded tensor; same fp32
-    // product, same pairs).  LRP_UP2_COMPACT=0 disables.
-    const bool up2_on = sw().up2_compact != 0;
+    LRP_TRY(top_relevance(m, row2img_dev, R_feat_dev, S, st));
     bool pairs_in = false;                               // S (the current layer's input) is S_c as pairs at pooled resolution
-    // Image layer folded into the epilogue of the layer above it (ConvArgs::img_part): S_1 — 4.1 GB written, 4.5 GB read at
-    // the bench configuration — never goes to memory; per tile 160 positions x 6 partial sums do, and a streaming pass
-    // adds them up in a fixed order [MI355X, same box: block1_conv2 4.25 -> 4.57 ms (it now also runs the tap GEMM and the
-    // in-tile stencil), image layer 1.29 -> 0.18 ms, walk 26.1-26.3 -> 25.3 ms; heat-maps unchanged to fp32 round-off,
-    // batch invariance bit-exact].
-    // LRP_IMG_FOLD=0 disables.
-    const bool fold_on = sw().img_fold != 0 && split && !f16 && walk == 0 && !layer_hook && img_fused() && layers.size() > 1 &&
-                         !layers[0].pool_after && layers[1].cin == 64 && layers[0].w_bwd_s.p != nullptr;
-    // conv_plan's answer for the dense launch through layer lc (lc >= 1) of this walk: with the folded image layer on it where
-    // that is wanted, and reading the compact pool interface or not
-    auto walk_plan = [&](int lc, bool up2) {
-      const ConvLayer& Lc = layers[lc];
-      ConvAsk q;
-      q.epi = layers[lc - 1].pool_after ? EPI_MUL_UP2 : EPI_MUL; q.prec = run_prec;      // (asked for the split-bf16 walk only)
-      q.NB = n; q.H = Lc.H; q.W = Lc.W; q.N = Lc.cin; q.Cin = Lc.cout; q.taps = 9;
-      q.frag = split && walk == 0 && Lc.w_bwd_frag.p != nullptr;
-      q.up2_src = up2; q.img_part = lc == 1 && fold_on;
-      return conv_plan(q);
-    };
-    // Does layer lc's launch run on the 2:4-sparse matrix cores (conv_sparse.h)?  Decided by the layer's shape, the precision
-    // and what this encode left — never by the token or image count: sparse and dense sum in different orders, and a picture's
-    // heat-map must not depend on the batch it is explained in.  LRP_SPARSE_POOL=0 disables.
-    auto sparse_consumer = [&](int lc) {
-      if (lc < 1) return false;
-      const ConvLayer& Lc = layers[lc];
-      return sw().sparse_pool && Lc.w_sp.p && Lc.idxp.p && Lc.idx_epoch == encode_epoch && !layers[lc - 1].pool_after && split && !f16 &&
-             walk == 0 && !layer_hook && sp_scp.p != nullptr;
-    };
-    // does the launch of layer li write pairs for its consumer li - 1 (see above)?  A sparse consumer reads nothing else, so its
-    // producer writes them whatever LRP_UP2_COMPACT / LRP_UP2_PW say and whatever tile the producer takes (a plain EPI_MUL
-    // epilogue with the compact gate); those two switches govern the boundaries whose consumer is dense.
-    auto writes_pairs = [&](int li) {
-      const ConvLayer& P = layers[li - 1];
-      if (!P.pool_after || !split || f16 || walk != 0 || layer_hook || li < 2 || (P.cout & 7) || !P.Gc.p || P.gc_epoch != encode_epoch)
-        return false;
-      if (sparse_consumer(li - 1)) return true;
-      return up2_on && walk_plan(li - 1, true).ok;
-    };
     for (int li = (int)layers.size() - 1; li >= 0; --li) {
       const ConvLayer& L = layers[li];
       if (layer_hook) {
         LRP_TRY((*layer_hook)(li, S));
         if (li == 0) return LRP_OK;
       }
-      ConvArgs ca{};
-      ConvPlan fold{};                                   // (li == 1: the plan of the launch that carries the image layer)
-      ca.in = S; ca.NB = n; ca.H = L.H; ca.W = L.W; ca.Cin = L.cout; ca.CinP = conv_cinp(L.cout); ca.taps = 9;
-      if (hook_split) {
-        const size_t n8 = (size_t)n * L.act_elems() / 8;
-        hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n8)), dim3(256), 0, st, S, bufXs.as<float>(), n8);
-        LRP_HIP_CHECK(hipGetLastError());
-        ca.in = bufXs.as<float>();
-        ca.out_plain = 1;
+      if (pairs_in && sparse_consumer(m, li)) {
+        LRP_TRY(sparse_boundary(li, n, row2img_dev, S, Snext, st));
+        pairs_in = false;
+        std::swap(S, Snext);
+        continue;
       }
-      ca.wpk = hook_split ? L.w_bwd_full_s.as<float>() : walk != 0 ? L.w_bwd_full.as<float>() : f16 ? L.w_bwd_h.as<float>()
-               : split ? L.w_bwd_s.as<float>() : L.w_bwd.as<float>();
-      ca.wpk_frag = f16 ? L.w_bwd_frag_h.as<float>() : (split && walk == 0) ? L.w_bwd_frag.as<float>() : nullptr;
-      if (f16) {                                        // S_li (level li) -> S_{li-1} (level li - 1); the image layer ends the chain
+      ConvArgs ca = conv3x3_args(L, n, S, L.cout);
+      ConvPlan fold{};                                   // (li == 1: the plan of the launch that carries the image layer)
+      if (m.hook_split) {
+        LRP_TRY(split_copy(S, (size_t)n * L.act_elems() / 8, st));
+        ca.in = bufXs.as<float>(); ca.out_plain = 1;
+      }
+      ca.wpk = m.hook_split ? L.w_bwd_full_s.as<float>() : walk != 0 ? L.w_bwd_full.as<float>() : m.f16 ? L.w_bwd_h.as<float>()
+               : m.split ? L.w_bwd_s.as<float>() : L.w_bwd.as<float>();
+      ca.wpk_frag = m.f16 ? L.w_bwd_frag_h.as<float>() : (m.split && walk == 0) ? L.w_bwd_frag.as<float>() : nullptr;
+      if (m.f16) {                                        // S_li (level li) -> S_{li-1} (level li - 1); the image layer ends the chain
         hipLaunchKernelGGL(tok_scale_kernel, dim3((n + 255) / 256), dim3(256), 0, st, lev_max(li), lev_exp(li),
                            L.wbs.as<float>(), tok_fac.as<float>(), li > 0 ? lev_exp(li - 1) : (int*)nullptr,
                            n, li == 0 ? 1 : 0);
@@ -840,8 +897,7 @@ struct Encoder {
         ca.tok_fac = tok_fac.as<float>();
         if (li > 0) ca.tok_max_out = lev_max(li - 1);
       }
-      ca.row2img = row2img_dev;
-      ca.order = L.order.get(); ca.row2img_host = r2i_host;
+      ca.row2img = row2img_dev; ca.order = L.order.get(); ca.row2img_host = r2i_host;
       ca.gate_binary = walk != 0; ca.relu_out = walk == 3;
       int epi;
       if (li == 0 && img_fused()) {
@@ -857,43 +913,17 @@ struct Encoder {
         ca.N = L.cin; ca.aux = P.G.as<float>(); ca.out = Snext;
         epi = P.pool_after ? EPI_MUL_UP2 : EPI_MUL;
         // the image layer rides on this launch's epilogue?
-        if (li == 1 && fold_on && (fold = walk_plan(1, pairs_in)).ok) {
+        if (li == 1 && m.fold_on && (fold = walk_plan(m, 1, pairs_in)).ok) {
           ca.img_w = P.w_bwd_s.as<float>(); ca.img_part = Snext; ca.out = nullptr;
-        }
-        if (pairs_in && sparse_consumer(li)) {
-          // the pooled boundary on the 2:4-sparse matrix cores (conv_sparse.h): S_c re-laid chunk-major, then one launch per class
-          const int Hp = L.H / 2, Wp = L.W / 2;
-          const size_t n_sets = (size_t)n * Hp * Wp * (L.cout / 8);
-          ProfileRec pr{};
-          if (profile) { (void)hipEventCreate(&pr.e0); (void)hipEventCreate(&pr.e1); (void)hipEventRecord(pr.e0, st); }
-          hipLaunchKernelGGL(conv_sparse_relayout_kernel, dim3(stream_grid(n_sets)), dim3(256), 0, st, S, sp_scp.as<float>(), n_sets, Hp * Wp, L.cout);
-          LRP_HIP_CHECK(hipGetLastError());
-          SparseArgs sa{};
-          sa.sc = sp_scp.as<float>(); sa.idxp = L.idxp.as<unsigned>(); sa.wsp = L.w_sp.as<float>(); sa.gate = P.G.as<float>(); sa.out = Snext;
-          sa.row2img = row2img_dev; sa.NB = n; sa.Hp = Hp; sa.Wp = Wp; sa.C = L.cout; sa.N = L.cin;
-          LRP_HIP_CHECK(conv_sparse_launch(sa, st));
-          if (profile) {
-            (void)hipEventRecord(pr.e1, st);
-            pr.flop = 2.0 * (double)n * L.H * L.W * 9.0 * L.cout * L.cin;
-            prof.push_back(pr);
-          }
-          pairs_in = false;
-          float* t = S; S = Snext; Snext = t;
-          continue;
         }
         if (pairs_in) {                                   // (ca.in = S stays a valid pointer; it is not read)
           ca.up2_src = S; ca.up2_pairs = 1; ca.up2_gpos = L.Gpos.as<unsigned char>();
           pairs_in = false;
         }
-        if (writes_pairs(li)) {                            // THIS launch writes S_c for layer li - 1 (N = P.cin, at 2x this resolution)
+        if (writes_pairs(m, li)) {                         // THIS launch writes S_c for layer li - 1 (N = P.cin, at 2x this resolution)
           epi = EPI_MUL; ca.aux = P.Gc.as<float>();
           pairs_in = true;
         }
-      }
-      ProfileRec pr{};
-      if (profile) {
-        (void)hipEventCreate(&pr.e0); (void)hipEventCreate(&pr.e1);
-        (void)hipEventRecord(pr.e0, st);
       }
       // PREC_F16X2: two MFMAs per product (the weights as ONE fp16, 11 bits) below the top block where a sum has at
       // least 576 products (64 channels), three (fp16 pairs on both sides) in the layers after the last pool.  [MI355X, bench configuration, relative L1 vs the float64 graph:
@@ -902,33 +932,13 @@ struct Encoder {
       // weight rounding, the same for every token, no longer averages out; profiles/r02_f16_terms_sweep.txt]
       // Encoder::two_term is that rule; lrp_set_fast_layers replaces it by a per-model mask, LRP_F16_T2MASK (experiments)
       // overrides both.
-      const int terms = f16 && two_term(li) ? 5 : 7;
+      const int terms = m.f16 && two_term(li) ? 5 : 7;
       if (epi == EPI_MUL_UP2) LRP_TRY(full_gate(li - 1, st));
-      LRP_HIP_CHECK(conv_launch(epi, ca, st, run_prec, terms));
-      if (profile) {
-        (void)hipEventRecord(pr.e1, st);
-        pr.flop = 2.0 * (double)n * L.H * L.W * 9.0 * L.cout * (li == 0 ? 6 : L.cin);
-        prof.push_back(pr);
-      }
-      if (ca.img_part) {
-        // the tiles' partial sums -> R_img (the image layer's second half; its algorithmic flops are booked on this record)
-        const ConvLayer& L0 = layers[0];
-        ProfileRec p2{};
-        if (profile) {
-          (void)hipEventCreate(&p2.e0); (void)hipEventCreate(&p2.e1);
-          (void)hipEventRecord(p2.e0, st);
-        }
-        hipLaunchKernelGGL(img_partial_sum_kernel, dim3(stream_grid((size_t)n * L0.H * L0.W)), dim3(256), 0, st, ca.img_part, images.as<float>(),
-                           row2img_dev, R_img_dev, n, L0.H, L0.W, fold.th, fold.tw, fold.cols_t, 0);
-        LRP_HIP_CHECK(hipGetLastError());
-        if (profile) {
-          (void)hipEventRecord(p2.e1, st);
-          p2.flop = 2.0 * (double)n * L0.H * L0.W * 9.0 * L0.cout * 6;
-          prof.push_back(p2);
-        }
-        return LRP_OK;
-      }
-      float* t = S; S = Snext; Snext = t;
+      prof.begin(st);
+      LRP_HIP_CHECK(conv_launch(epi, ca, st, m.run_prec, terms));
+      prof.end(st, layer_flop(n, li));
+      if (ca.img_part) return fold_image_sum(n, fold, ca.img_part, row2img_dev, R_img_dev, st);
+      std::swap(S, Snext);
     }
     if (!img_fused()) {  // S now holds T (n, H, W, 54): 9-tap shift-and-add and the x+/x- selection
       const ConvLayer& L0 = layers[0];
@@ -936,33 +946,6 @@ struct Encoder {
                          images.as<float>(), row2img_dev, R_img_dev, n, L0.H, L0.W, walk == 0 ? 0 : walk == 2 ? 2 : 1);
       LRP_HIP_CHECK(hipGetLastError());
     }
-    return LRP_OK;
-  }
-
-  int profile_records(int cap, double* ms_out, double* flop_out, int* n_out) {
-    int k = 0;
-    for (ProfileRec& p : prof) {
-      float t = 0.f;
-      const bool ok = hipEventSynchronize(p.e1) == hipSuccess && hipEventElapsedTime(&t, p.e0, p.e1) == hipSuccess;
-      if (ok && k < cap) { ms_out[k] = t; flop_out[k] = p.flop; ++k; }
-      (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1);
-    }
-    prof.clear();
-    *n_out = k;
-    return LRP_OK;
-  }
-
-  int profile_query(int64_t* launches, double* ms, double* flop) {
-    int64_t nl = 0; double tm = 0, fl = 0;
-    for (ProfileRec& p : prof) {
-      float t = 0.f;
-      if (hipEventSynchronize(p.e1) == hipSuccess && hipEventElapsedTime(&t, p.e0, p.e1) == hipSuccess) { tm += t; fl += p.flop; ++nl; }
-      (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1);
-    }
-    prof.clear();
-    if (launches) *launches = nl;
-    if (ms) *ms = tm;
-    if (flop) *flop = fl;
     return LRP_OK;
   }
 };

@@ -427,8 +427,8 @@ int lrp_set_fast_layers(lrp_handle* h, int64_t mask) {
 int lrp_profile_enable(lrp_handle* h, int32_t on) {
   return with_handle(h, [&]() -> int {
     if (!h) return fail(LRP_ERR_INVALID, "null handle");
-    h->enc.profile = on != 0;
-    h->rn.profile = on != 0;
+    h->enc.prof.on = on != 0;
+    h->rn.prof.on = on != 0;
     return LRP_OK;
   });
 }
@@ -436,14 +436,14 @@ int lrp_profile_enable(lrp_handle* h, int32_t on) {
 int lrp_profile_query(lrp_handle* h, int64_t* n_launches, double* total_ms, double* total_flop) {
   return with_handle(h, [&]() -> int {
     if (!h) return fail(LRP_ERR_INVALID, "null handle");
-    return h->enc.profile_query(n_launches, total_ms, total_flop);
+    return (h->resnet ? h->rn.prof : h->enc.prof).query(n_launches, total_ms, total_flop);
   });
 }
 
 int lrp_profile_records(lrp_handle* h, int32_t cap, double* ms_out, double* flop_out, int32_t* n_out) {
   return with_handle(h, [&]() -> int {
     if (!h || !ms_out || !flop_out || !n_out || cap < 0) return fail(LRP_ERR_INVALID, "bad lrp_profile_records arguments");
-    return h->resnet ? h->rn.profile_records(cap, ms_out, flop_out, n_out) : h->enc.profile_records(cap, ms_out, flop_out, n_out);
+    return (h->resnet ? h->rn.prof : h->enc.prof).records(cap, ms_out, flop_out, n_out);
   });
 }
 

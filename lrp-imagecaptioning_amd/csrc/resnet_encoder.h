@@ -69,11 +69,10 @@ struct ResNetEncoder {
   DevBuf r0, r1, r2, r3, r4, r5;   // reverse scratch (per token)
   int encoded = 0;
   bool features_only = false;
-  bool profile = false;
   int prec = PREC_BF16X3;  // arithmetic of the reverse walk's conv chains (lrp_set_precision); forward stays exact fp32
   bool masks_ok = false;   // the ReLU masks belong to the current encode (an LRP_PREC_FP32 forward)
   int64_t* ws_total = nullptr;   // the handle's workspace counter (lazy allocations of the gradient walks)
-  std::vector<ProfileRec> prof;
+  Profiler prof;           // one record per unit_backward launch (common.h)
 
   int add_unit(const std::string& nm, int k, int cin, int cout, int stride, int Hin, int Win, bool relu) {
     RnUnit u;
@@ -542,14 +541,9 @@ struct ResNetEncoder {
     ca.in = S; ca.wpk = split ? u.w_bs.as<float>() : u.w_b.as<float>(); ca.row2img = row2img; ca.aux = aux; ca.out = out;
     ca.N = u.cin; ca.out_plain = plain_out ? 1 : 0;
     ca.Cin = u.cout; ca.CinP = conv_cinp(u.cout); ca.NB = n; ca.H = u.Hout; ca.W = u.Wout; ca.taps = u.k == 3 ? 9 : 1;
-    ProfileRec pr{};
-    if (profile) { (void)hipEventCreate(&pr.e0); (void)hipEventCreate(&pr.e1); (void)hipEventRecord(pr.e0, st); }
+    prof.begin(st);
     LRP_HIP_CHECK(conv_launch(EPI_MUL, ca, st, split ? PREC_BF16X3 : PREC_FP32));
-    if (profile) {
-      (void)hipEventRecord(pr.e1, st);
-      pr.flop = 2.0 * n * u.Hout * u.Wout * (double)(u.k == 3 ? 9 : 1) * u.cout * u.cin;
-      prof.push_back(pr);
-    }
+    prof.end(st, 2.0 * n * u.Hout * u.Wout * (double)(u.k == 3 ? 9 : 1) * u.cout * u.cin);
     return LRP_OK;
   }
 
@@ -828,19 +822,6 @@ struct ResNetEncoder {
   DevBuf q_stem;
   DevBuf pool_win;
   bool stem_attr_set = false;
-
-  int profile_records(int cap, double* ms_out, double* flop_out, int* n_out) {
-    int k = 0;
-    for (ProfileRec& p : prof) {
-      float t = 0.f;
-      const bool ok = hipEventSynchronize(p.e1) == hipSuccess && hipEventElapsedTime(&t, p.e0, p.e1) == hipSuccess;
-      if (ok && k < cap) { ms_out[k] = t; flop_out[k] = p.flop; ++k; }
-      (void)hipEventDestroy(p.e0); (void)hipEventDestroy(p.e1);
-    }
-    prof.clear();
-    *n_out = k;
-    return LRP_OK;
-  }
 };
 
 }  // namespace lrp
