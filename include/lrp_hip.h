@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define LRP_ABI_VERSION 9
+#define LRP_ABI_VERSION 10
 
 enum {
   LRP_OK = 0,
@@ -392,6 +392,42 @@ int lrp_op_gradcam(const float* feat_dev, const int32_t* img_idx_dev, const floa
                    int32_t D, int32_t C, void* stream);
 int lrp_exam_maps(const void* R_img_dev, int32_t fp64, int32_t n, int32_t H, int32_t W, int32_t C, int32_t pool, int32_t k,
                   int32_t absval, void* maps_dev, double* means_dev, void* stream);
+
+/* ABI v10.  Perturbation ("pixel-flipping") analysis on the device (PT: = innvestigate/tools/perturbate.py): rank the regions
+ * of a heat-map, replace the top-k regions of the image, read the explained word's score off the next forward.  Operators like
+ * lrp_eval_* / lrp_exam_maps: device pointers, no synchronisation, one workgroup per unit with fixed-order fp64 reductions, so
+ * a unit's result does not depend on what else shares the launch.  (csrc/perturb_kernels.h)
+ * Geometry (PT:105-116, PT:170), shared by the first two entries: a map of H x W is cut into regions of rh x rw.  If rh divides
+ *   H and rw divides W nothing is padded; if neither divides, each axis is padded by r - dim % r, floor(pad / 2) before and the
+ *   rest after, in np.pad's 'reflect' mode (the edge sample is not repeated) — by index arithmetic, nothing padded is stored.
+ *   If exactly one axis is divisible the reference pads it by a whole region and fails its assert at PT:107: LRP_ERR_INVALID.
+ *   nreg = Hr * Wr regions in row-major order; more than 4096 regions, or a region side below 1: LRP_ERR_RANGE.
+ * lrp_perturb_ranks (PT:167, PT:125-128, PT:79-84): R_img_dev (n, H, W, C) float32 (fp64 = 0) or float64 (fp64 = 1);
+ *   reduce over the channels and aggregate over a region, each 0 = mean or 1 = max (np.mean / np.max).  Everything is
+ *   accumulated in fp64 from the input dtype in one fixed order: a pixel is ((c0 + c1) + ...) / C, a region the sum of its
+ *   pixels in raster order / (rh * rw); negate = 1 negates the score (least relevant first).  ranks_dev (n, nreg) int32:
+ *   rank[i] = #{j : s_j > s_i or (s_j == s_i and j < i)}, 0 = the highest score; exact ties go to the lower region index (the
+ *   reference sorts with quicksort and leaves their order open), NaN scores rank last.  scores_dev (n, nreg) float64 or NULL.
+ * lrp_perturb_apply (PT:74-76, PT:130-148, PT:182-185): out_dev (n, H, W, C) float32: unit u is image img_idx_dev[u] of
+ *   x_dev (B, H, W, C) float32 with every region of rank <= k_dev[u] - 1 replaced (k float64, as PT:385 adds a float
+ *   regions_per_step).  mode 0 zeros, 1 mean (the fp64 raster-order mean of the padded region, reflected pixels included,
+ *   per channel, rounded once to float32), 2 invert (-x), 3 noise (copies noise_dev (n, H, W, C) inside the perturbed regions:
+ *   'gaussian' with the draw left to the caller; noise_dev is NULL for every other mode).  all_channels = 0 perturbs channel 0
+ *   only, as the reference does (its mask has a channel axis of length 1 and PT:135-139 index x with that channel); 1 perturbs
+ *   every channel.  has_range: np.clip to [lo, hi] (PT:142-146) of the whole unit, every channel, iff k >= 1 (one region is
+ *   perturbed); the reference clips inside its loop, so what it perturbs afterwards is the clipped tensor: the unit is clipped,
+ *   perturbed, and clipped again.  A unit whose image index is outside [0, B) reads nothing and comes out as NaN.
+ * lrp_perturb_word_scores: the score of the explained word on the handle's cached forward (lrp_decoder_forward), read in
+ *   place.  slot_dev, t_dev, k_dev (n) int32 on the device: image slot, position t >= 1, model column (token id - 1) ->
+ *   logit_dev, logp_dev (n) float64: l[k] and l[k] - (max + log sum exp(l - max)) over row t - 1 of caption_preds.  A unit
+ *   outside the cached logits reads nothing and comes out as NaN.  LRP_ERR_STATE without a forward. */
+int lrp_perturb_ranks(const void* R_img_dev, int32_t fp64, int32_t n, int32_t H, int32_t W, int32_t C, int32_t rh, int32_t rw,
+                      int32_t reduce, int32_t aggregate, int32_t negate, int32_t* ranks_dev, double* scores_dev, void* stream);
+int lrp_perturb_apply(const float* x_dev, const int32_t* img_idx_dev, const int32_t* ranks_dev, const double* k_dev,
+                      const float* noise_dev, float* out_dev, int32_t n, int32_t B, int32_t H, int32_t W, int32_t C, int32_t rh,
+                      int32_t rw, int32_t mode, int32_t all_channels, int32_t has_range, float lo, float hi, void* stream);
+int lrp_perturb_word_scores(lrp_handle* h, const int32_t* slot_dev, const int32_t* t_dev, const int32_t* k_dev, int32_t n,
+                            double* logit_dev, double* logp_dev, void* stream);
 
 /* Operator-level entries of the fine-tune step's dense products (unit tests at real layer sizes; csrc/train_gemm.h).
  * lrp_op_sgemm: C (+)= op(A) op(B) on the fp32 matrix cores, row-major with leading dimensions;

@@ -7,7 +7,7 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "liblrp_hip.so")
 
-LRP_ABI_VERSION = 9
+LRP_ABI_VERSION = 10
 LRP_OK, LRP_ERR_INVALID, LRP_ERR_STATE, LRP_ERR_HIP, LRP_ERR_NOMEM, LRP_ERR_RANGE, LRP_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 LRP_DEC_ADAPTIVE, LRP_DEC_GRIDTD = 0, 1
 LRP_ENC_VGG, LRP_ENC_RESNET = 0, 1
@@ -92,6 +92,9 @@ SYMBOLS = {
     "lrp_eval_box_scores": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     "lrp_op_gradcam": (C.c_int, [_P] * 7 + [C.c_int32] * 6 + [_P]),
     "lrp_exam_maps": (C.c_int, [_P] + [C.c_int32] * 8 + [_P, _P, _P]),
+    "lrp_perturb_ranks": (C.c_int, [_P] + [C.c_int32] * 10 + [_P, _P, _P]),
+    "lrp_perturb_apply": (C.c_int, [_P] * 6 + [C.c_int32] * 10 + [C.c_float, C.c_float, _P]),
+    "lrp_perturb_word_scores": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, _P]),
     "lrp_last_error": (C.c_char_p, []),
     "lrp_abi_version": (C.c_int, []),
     "lrp_launch_count": (C.c_int64, []),

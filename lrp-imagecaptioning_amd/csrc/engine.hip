@@ -18,6 +18,7 @@
 #include "encoder.h"
 #include "eval_kernels.h"
 #include "gradcam_kernels.h"
+#include "perturb_kernels.h"
 #include "resnet_encoder.h"
 #include "rules_kernels.h"
 #include "score_kernels.h"
@@ -928,6 +929,83 @@ int lrp_exam_maps(const void* R_img_dev, int32_t fp64, int32_t n, int32_t H, int
     else
       hipLaunchKernelGGL(exam_map_kernel<float>, dim3(n), dim3(256), 0, S(stream), (const float*)R_img_dev, H, W, C, pool, k,
                          absval, maps_dev, means_dev);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+// ---- perturbation analysis (csrc/perturb_kernels.h; innvestigate/tools/perturbate.py)
+// The geometry of PT:105-116 / PT:170: no padding when the region divides both axes, r - dim % r per axis (floor(pad / 2)
+// before) when it divides neither; one divisible axis is the reference's assert at PT:107.
+static int perturb_geometry(int32_t H, int32_t W, int32_t C, int32_t rh, int32_t rw, PerturbGeom* g) {
+  if (H < 1 || W < 1 || C < 1) return fail(LRP_ERR_INVALID, "H, W, C must be positive");
+  if ((int64_t)H * W * C > INT32_MAX) return fail(LRP_ERR_INVALID, "one map must hold fewer than 2^31 values");
+  if (rh < 1 || rw < 1) return fail(LRP_ERR_RANGE, "the region shape must be at least 1 x 1");
+  if (rh > (1 << 15) || rw > (1 << 15)) return fail(LRP_ERR_RANGE, "a region side may not exceed 32768");
+  const bool dh = H % rh == 0, dw = W % rw == 0;
+  if (dh != dw)
+    return fail(LRP_ERR_INVALID, "region (%d, %d) divides one axis of (%d, %d) and not the other: the reference pads the "
+                "divisible axis by a whole region and fails its assert (perturbate.py:107)", rh, rw, H, W);
+  const int ph = dh ? 0 : rh - H % rh, pw = dw ? 0 : rw - W % rw;
+  const int64_t nreg = (int64_t)((H + ph) / rh) * ((W + pw) / rw);
+  if (nreg > PERTURB_MAX_REGIONS) return fail(LRP_ERR_RANGE, "%lld regions: at most %d are ranked", (long long)nreg, PERTURB_MAX_REGIONS);
+  *g = PerturbGeom{H, W, C, rh, rw, (H + ph) / rh, (W + pw) / rw, ph / 2, pw / 2};
+  return LRP_OK;
+}
+
+int lrp_perturb_ranks(const void* R_img_dev, int32_t fp64, int32_t n, int32_t H, int32_t W, int32_t C, int32_t rh, int32_t rw,
+                      int32_t reduce, int32_t aggregate, int32_t negate, int32_t* ranks_dev, double* scores_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (!R_img_dev || !ranks_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n < 1) return fail(LRP_ERR_INVALID, "n must be positive");
+    if (fp64 != 0 && fp64 != 1) return fail(LRP_ERR_INVALID, "fp64 must be 0 or 1");
+    if (negate != 0 && negate != 1) return fail(LRP_ERR_INVALID, "negate must be 0 or 1");
+    if ((reduce != PERTURB_FN_MEAN && reduce != PERTURB_FN_MAX) || (aggregate != PERTURB_FN_MEAN && aggregate != PERTURB_FN_MAX))
+      return fail(LRP_ERR_INVALID, "reduce and aggregate must be 0 (mean) or 1 (max)");
+    PerturbGeom g;
+    LRP_TRY(perturb_geometry(H, W, C, rh, rw, &g));
+    const size_t lds = (size_t)g.Hr * g.Wr * sizeof(double);
+    const double sign = negate ? -1.0 : 1.0;
+    if (fp64)
+      hipLaunchKernelGGL(perturb_rank_kernel<double>, dim3(n), dim3(256), lds, S(stream), (const double*)R_img_dev, g, reduce,
+                         aggregate, sign, ranks_dev, scores_dev);
+    else
+      hipLaunchKernelGGL(perturb_rank_kernel<float>, dim3(n), dim3(256), lds, S(stream), (const float*)R_img_dev, g, reduce,
+                         aggregate, sign, ranks_dev, scores_dev);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_perturb_apply(const float* x_dev, const int32_t* img_idx_dev, const int32_t* ranks_dev, const double* k_dev,
+                      const float* noise_dev, float* out_dev, int32_t n, int32_t B, int32_t H, int32_t W, int32_t C, int32_t rh,
+                      int32_t rw, int32_t mode, int32_t all_channels, int32_t has_range, float lo, float hi, void* stream) {
+  return guarded([&]() -> int {
+    if (!x_dev || !img_idx_dev || !ranks_dev || !k_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n < 1 || B < 1) return fail(LRP_ERR_INVALID, "n and B must be positive");
+    if (mode != PERTURB_ZEROS && mode != PERTURB_MEAN && mode != PERTURB_INVERT && mode != PERTURB_NOISE)
+      return fail(LRP_ERR_INVALID, "mode must be 0 (zeros), 1 (mean), 2 (invert) or 3 (noise)");
+    if ((mode == PERTURB_NOISE) != (noise_dev != nullptr)) return fail(LRP_ERR_INVALID, "noise_dev goes with mode 3 (noise) and with no other");
+    if ((all_channels != 0 && all_channels != 1) || (has_range != 0 && has_range != 1))
+      return fail(LRP_ERR_INVALID, "all_channels and has_range must be 0 or 1");
+    if (has_range && !(lo <= hi)) return fail(LRP_ERR_INVALID, "the value range needs lo <= hi");
+    PerturbGeom g;
+    LRP_TRY(perturb_geometry(H, W, C, rh, rw, &g));
+    hipLaunchKernelGGL(perturb_apply_kernel, dim3(n), dim3(256), 0, S(stream), x_dev, img_idx_dev, ranks_dev, k_dev, noise_dev,
+                       out_dev, B, g, mode, all_channels, has_range, lo, hi);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_perturb_word_scores(lrp_handle* h, const int32_t* slot_dev, const int32_t* t_dev, const int32_t* k_dev, int32_t n,
+                            double* logit_dev, double* logp_dev, void* stream) {
+  return with_handle(h, [&]() -> int {
+    if (!h || !slot_dev || !t_dev || !k_dev || !logit_dev || !logp_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n < 1) return fail(LRP_ERR_INVALID, "n must be positive");
+    if (!h->dec.have_forward) return fail(LRP_ERR_STATE, "lrp_decoder_forward must run before lrp_perturb_word_scores");
+    hipLaunchKernelGGL(perturb_word_score_kernel, dim3(n), dim3(256), 0, S(stream), h->dec.S_<double>("caption_preds"), slot_dev,
+                       t_dev, k_dev, h->dec.B_cur, h->dec.Tm, h->dec.V, logit_dev, logp_dev);
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   });

@@ -807,3 +807,107 @@ def exam_maps(R_img, pool=None, k=None, absval=False, want_maps=True):
                                   int(bool(absval)), C.c_void_p(maps.data_ptr()) if maps is not None else None,
                                   C.c_void_p(means.data_ptr()), _cur_stream(R.device)))
     return maps, means
+
+
+# ---- perturbation analysis (innvestigate/tools/perturbate.py, PT:; csrc/perturb_kernels.h, lrp_perturb_*)
+PERTURB_MAX_REGIONS = 4096
+_PERTURB_FN = {"mean": 0, "max": 1}
+_PERTURB_MODE = {"zeros": 0, "mean": 1, "invert": 2, "noise": 3}
+
+
+def perturb_geometry(H, W, region_shape):
+    """The region grid of PT:105-116 / PT:170 (host arithmetic): (Hr, Wr, rows padded before, columns padded before).
+    ValueError when the region divides exactly one axis (the reference's assert, PT:107); NotImplementedError for a region
+    side below 1 or more than PERTURB_MAX_REGIONS regions."""
+    rh, rw = int(region_shape[0]), int(region_shape[1])
+    if rh < 1 or rw < 1:
+        raise NotImplementedError("the region shape must be at least 1 x 1")
+    dh, dw = H % rh == 0, W % rw == 0
+    if dh != dw:
+        raise ValueError("region (%d, %d) divides one axis of (%d, %d) and not the other: the reference pads the divisible "
+                         "axis by a whole region and fails its assert (perturbate.py:107)" % (rh, rw, H, W))
+    ph, pw = (0 if dh else rh - H % rh), (0 if dw else rw - W % rw)
+    Hr, Wr = (H + ph) // rh, (W + pw) // rw
+    if Hr * Wr > PERTURB_MAX_REGIONS:
+        raise NotImplementedError("%d regions: at most %d are ranked" % (Hr * Wr, PERTURB_MAX_REGIONS))
+    return Hr, Wr, ph // 2, pw // 2
+
+
+def perturb_ranks(R_img, region_shape, reduce="mean", aggregate="mean", want_scores=False, negate=False):
+    """Region ranks of PT:79-84 on the device: R_img (n, H, W, C) float32 or float64 tensor -> ranks (n, nreg) int32, 0 = the
+    most relevant region, exact ties to the lower region index, NaN last; with want_scores also the (n, nreg) float64 region
+    scores (channel `reduce`, region `aggregate`, each 'mean' or 'max'; negated if `negate`: least relevant first)."""
+    lib = _capi.load()
+    if reduce not in _PERTURB_FN or aggregate not in _PERTURB_FN:
+        raise ValueError("reduce and aggregate must be 'mean' or 'max'")
+    R = R_img.contiguous()
+    if R.dtype not in (torch.float32, torch.float64) or R.dim() != 4:
+        raise ValueError("expected an (n, H, W, C) float32 or float64 tensor")
+    n, Hh, Ww, Cc = R.shape
+    Hr, Wr, _, _ = perturb_geometry(Hh, Ww, region_shape)
+    ranks = torch.empty((n, Hr * Wr), dtype=torch.int32, device=R.device)
+    scores = torch.empty((n, Hr * Wr), dtype=torch.float64, device=R.device) if want_scores else None
+    _capi.check(lib.lrp_perturb_ranks(C.c_void_p(R.data_ptr()), int(R.dtype == torch.float64), n, Hh, Ww, Cc,
+                                      int(region_shape[0]), int(region_shape[1]), _PERTURB_FN[reduce], _PERTURB_FN[aggregate],
+                                      int(bool(negate)), C.c_void_p(ranks.data_ptr()),
+                                      C.c_void_p(scores.data_ptr()) if scores is not None else None, _cur_stream(R.device)))
+    return (ranks, scores) if want_scores else ranks
+
+
+def perturb_apply(x, img_idx, ranks, k, region_shape, mode="zeros", noise=None, all_channels=False, value_range=None):
+    """PT:130-148 on the device: x (B, H, W, C) float32 tensor, img_idx (n) image index per unit, ranks (n, nreg) int32 tensor,
+    k (n) or a scalar: the regions of rank <= k - 1 are replaced -> (n, H, W, C) float32 tensor.  mode 'zeros' | 'mean' |
+    'invert' | 'noise' (copies `noise` (n, H, W, C) inside the perturbed regions); channel 0 only unless all_channels;
+    value_range (lo, hi): a unit with k >= 1 is clipped, perturbed and clipped again.  A unit whose image index is outside
+    [0, B) comes out as NaN."""
+    lib = _capi.load()
+    if mode not in _PERTURB_MODE:
+        raise ValueError("mode must be 'zeros', 'mean', 'invert' or 'noise'")
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise ValueError("expected a (B, H, W, C) float32 tensor")
+    x = x.contiguous()
+    B, Hh, Ww, Cc = x.shape
+    Hr, Wr, _, _ = perturb_geometry(Hh, Ww, region_shape)
+    dev = x.device
+    if ranks.dtype != torch.int32 or ranks.dim() != 2 or ranks.shape[1] != Hr * Wr or ranks.device != dev:
+        raise ValueError("ranks must be an (n, %d) int32 tensor on the device of x" % (Hr * Wr))
+    ranks = ranks.contiguous()
+    n = ranks.shape[0]
+    idx = img_idx if torch.is_tensor(img_idx) else torch.as_tensor(np.asarray(img_idx, dtype=np.int32).reshape(-1))
+    idx = idx.to(device=dev, dtype=torch.int32).contiguous()
+    kk = k if torch.is_tensor(k) else torch.as_tensor(np.broadcast_to(np.asarray(k, dtype=np.float64), (n,)).copy())
+    kk = kk.to(device=dev, dtype=torch.float64).contiguous()
+    if tuple(idx.shape) != (n,) or tuple(kk.shape) != (n,):
+        raise ValueError("img_idx and k must hold one entry per row of ranks")
+    if (mode == "noise") != (noise is not None):
+        raise ValueError("`noise` goes with mode 'noise' and with no other")
+    if noise is not None:
+        if noise.dtype != torch.float32 or tuple(noise.shape) != (n, Hh, Ww, Cc) or noise.device != dev:
+            raise ValueError("noise must be an (n, H, W, C) float32 tensor on the device of x")
+        noise = noise.contiguous()
+    lo, hi = (0.0, 0.0) if value_range is None else (float(value_range[0]), float(value_range[1]))
+    out = torch.empty((n, Hh, Ww, Cc), dtype=torch.float32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    _capi.check(lib.lrp_perturb_apply(p(x), p(idx), p(ranks), p(kk), p(noise), p(out), n, B, Hh, Ww, Cc, int(region_shape[0]),
+                                      int(region_shape[1]), _PERTURB_MODE[mode], int(bool(all_channels)),
+                                      int(value_range is not None), C.c_float(lo), C.c_float(hi), _cur_stream(dev)))
+    return out
+
+
+def perturb_word_scores(engine, slot, t, col):
+    """The score of n words on the cached forward of `engine` (an LRPEngine after decoder_forward), read in place: slot, t,
+    col (n) ints (lists or device tensors): image slot, position t >= 1, model column (token id - 1) -> (logit, logp), (n,)
+    float64 device tensors: l[col] and log_softmax(l)[col] of row t - 1 of caption_preds.  A unit outside the cached logits
+    comes out as NaN."""
+    def dev(a):
+        a = a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a, dtype=np.int32).reshape(-1))
+        return a.to(device=engine.device, dtype=torch.int32).contiguous()
+    s, tt, kk = dev(slot), dev(t), dev(col)
+    n = s.shape[0]
+    if n < 1 or tuple(tt.shape) != (n,) or tuple(kk.shape) != (n,):
+        raise ValueError("slot, t and col must hold the same number (>= 1) of entries")
+    logit = torch.empty((n,), dtype=torch.float64, device=engine.device)
+    logp = torch.empty((n,), dtype=torch.float64, device=engine.device)
+    p = lambda x: C.c_void_p(x.data_ptr())
+    _capi.check(engine._lib.lrp_perturb_word_scores(engine._h, p(s), p(tt), p(kk), n, p(logit), p(logp), engine._stream()))
+    return logit, logp
