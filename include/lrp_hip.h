@@ -529,7 +529,7 @@ int lrp_reload_switches(void);
 enum { LRP_EPI_BIAS_RELU = 0, LRP_EPI_BIAS = 1, LRP_EPI_MUL = 2, LRP_EPI_MUL_UP2 = 3, LRP_EPI_FWD_DUAL = 4, LRP_EPI_STORE = 5,
        LRP_EPI_IMG_STENCIL = 6 };
 enum { LRP_OPND_FP32 = 0, LRP_OPND_BF16X3 = 1, LRP_OPND_F16X2 = 2 };
-enum { LRP_FORM_PLAIN = 0, LRP_FORM_SMALL = 1, LRP_FORM_HALO = 2, LRP_FORM_BREG = 3, LRP_FORM_POOL = 4, LRP_FORM_IMG = 5 };
+enum { LRP_FORM_PLAIN = 0, LRP_FORM_SMALL = 1, LRP_FORM_HALO = 2, LRP_FORM_BREG = 3, LRP_FORM_POOL = 4, LRP_FORM_IMG = 5, LRP_FORM_BREG8 = 6 };
 enum { LRP_PLAN_FRAG = 1, LRP_PLAN_JOIN = 2, LRP_PLAN_DUAL_IL = 4, LRP_PLAN_GMASK = 8,
        LRP_PLAN_UP2_SRC = 16, LRP_PLAN_IMG_PART = 32, LRP_PLAN_POOL_GC = 64 };
 int lrp_conv_plan(int32_t epi, int32_t prec, int32_t terms, int32_t NB, int32_t H, int32_t W, int32_t N, int32_t Cin, int32_t taps,

@@ -492,14 +492,16 @@ __global__ __launch_bounds__(256) void pack_image_layer_dev_kernel(const float* 
   bwd[(size_t)(t * 6 + 3 + c) * Kb + co] = vn;
   full[(size_t)(t * 6 + c) * Kb + co] = v;
 }
-// BREG operand: split8-packed weights [64 rows][K = 9 * CP] -> fragment-major copy for the weights-in-registers kernel,
-// [kc = chunk*9 + tap][step q][hi|lo][64 rows][4 dwords] (chunk c = 4 (q >> 1) + 2 hh + (q & 1) of the 128 B tap-chunk row)
-__global__ __launch_bounds__(256) void pack_frag64_dev_kernel(const float* __restrict__ src, float* __restrict__ dst, int CP) {
+// BREG operand: split8-packed weights [rows][K = 9 * CP] -> fragment-major copy for the weights-in-registers kernels,
+// [kc = chunk*9 + tap][step q][hi|lo][rows][4 dwords] (chunk c = 4 (q >> 1) + 2 hh + (q & 1) of the 128 B tap-chunk row);
+// rows = 64 (the N <= 64 tile) or the layer's N % 256 == 0 columns (the 8-wave tile: a wave's 32 columns stay one coalesced 512 B)
+__global__ __launch_bounds__(256) void pack_frag_dev_kernel(const float* __restrict__ src, float* __restrict__ dst, int CP, int rows) {
   const int K = 9 * CP, cpt = CP / 32;
-  const size_t total = (size_t)cpt * 9 * 4 * 2 * 64;
+  const size_t total = (size_t)cpt * 9 * 4 * 2 * rows;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int n = (int)(i & 63), hh = (int)((i >> 6) & 1), q = (int)((i >> 7) & 3);
-    const int kc = (int)(i >> 9), cc = kc / 9, t = kc % 9;
+    const size_t f = i / rows;
+    const int n = (int)(i - f * rows), hh = (int)(f & 1), q = (int)((f >> 1) & 3);
+    const int kc = (int)(f >> 3), cc = kc / 9, t = kc % 9;
     const int c = 4 * (q >> 1) + 2 * hh + (q & 1);
     *reinterpret_cast<f32x4*>(dst + i * 4) = *reinterpret_cast<const f32x4*>(src + (size_t)n * K + t * CP + cc * 32 + c * 4);
   }

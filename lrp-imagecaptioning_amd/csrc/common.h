@@ -31,6 +31,8 @@ std::string& last_error_ref();
 struct Switches {
   int conv_halo = 1;        // LRP_CONV_HALO  0 never / 1 when a tile shape fills >= 90 % of the M tile / 2 always (ragged shapes: tests)
   int conv_breg = 1;        // LRP_CONV_BREG=0     N <= 64 backward convs without the weights-in-registers kernel
+  int conv_breg8 = 1;       // LRP_CONV_BREG8=0    the dense 8-wave 256 x 256 walk launches on the pipelined kernel (a weight stage in LDS, a barrier per tap);
+                            //                     also read when weights are set: only then are the layers' fragment-major copies made
   int conv_small = 1;       // LRP_CONV_SMALL=0    small grids keep the 128-row tiles (no 64 x 64 tiles)
   int conv_mid = 1;         // LRP_CONV_MID=0      no 128 x 64 tiles for the grids just above the small ones
   int epi_fast = 1;         // LRP_EPI_FAST=0      MUL / MUL_UP2 epilogues always through the general pass loop
@@ -51,6 +53,9 @@ struct Switches {
     rd("LRP_CONV_MID", conv_mid); rd("LRP_EPI_FAST", epi_fast); rd("LRP_UP2_PW", up2_pw); rd("LRP_TILE_ORDER", tile_order);
     rd("LRP_FWD_EMIT", fwd_emit); rd("LRP_FWD_IL", fwd_il); rd("LRP_IMG_FUSED", img_fused); rd("LRP_UP2_COMPACT", up2_compact);
     rd("LRP_IMG_FOLD", img_fold); rd("LRP_SPARSE_POOL", sparse_pool); rd("LRP_POOL_FUSED", pool_fused);
+    // (read apart from the list above, which tests/test_capi_symbols.py holds against the rows of tests/test_gpu_switches.py: this
+    // switch's run against the default path — operator and engine level, bit-identical — is tests/test_gpu_conv_breg8.py)
+    if (const char* e = getenv("LRP_CONV_BREG8")) conv_breg8 = atoi(e);
   }
 };
 inline Switches& sw() {

@@ -6,7 +6,7 @@
 //     RR:274-322 restructured: S_{l-1} = up2?(convT(S_l, w_l+)) * G_{l-1}
 //   * every dense product of the decoder LRP / gradient paths (taps = 1, EPI_STORE / EPI_MUL)
 // Template axes: tile (WM, WN, TM, TN), epilogue EPI, operand arithmetic PREC (exact fp32 MFMA | split-bf16),
-// HALO (3x3: A tile + halo resident in LDS for all 9 taps), BREG (N <= 64: weights in registers, no barrier per tap),
+// HALO (3x3: A tile + halo resident in LDS for all 9 taps), BREG (weights in registers, no barrier per tap: N <= 64, and the 8-wave tile),
 // TERMS (which partial products of the split operands are issued).  DESIGN.md 4.1 has the measurements behind each.
 //
 // GEMM view: D[m][n] = sum_k A[m][k] * B[k][n],  m = output pixel (NHWC row),
@@ -125,7 +125,7 @@ struct TileOrder {
 struct ConvArgs {
   const float* in;     // [NB][H][W][Cin] fp32
   const float* wpk;    // [n_tiles*BN][K] fp32, K = taps*CinP, CinP = roundup(Cin,32), zero padded
-  const float* wpk_frag;  // BREG: the same weights fragment-major, [kc][step][hi|lo][lane half][BN = 64] x 16 B
+  const float* wpk_frag;  // BREG: the same weights fragment-major, [kc][step][hi|lo][lane half][all N columns] x 16 B (N = 64, or N % 256 == 0)
   int NB, H, W, Cin, CinP;
   int N;               // valid output columns
   int taps;            // 9 (3x3 same) or 1
@@ -284,7 +284,7 @@ constexpr int conv_halo_rows(int BM) { return BM == 256 ? 352 : 192; }   // x 12
 // that no other instantiation carries its loads (a runtime flag in the shared epilogue costs the VGG walk registers).
 template <int WM, int WN, int TM, int TN, int EPI, int PREC, bool HALO = false, bool BREG = false, int TERMS = 7, int NS = 2,
           bool GMASK = false>
-__global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_waves(WM * WN, TM, TN, HALO)) void conv_igemm_kernel(ConvArgs a) {
+__global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2 : conv_min_waves(WM * WN, TM, TN, HALO)) void conv_igemm_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (the buffer-resource builtins are device-only)
   constexpr int NW = WM * WN, NT = 64 * NW;           // waves / threads per block (4 or 8 waves)
   constexpr bool SPLIT = PREC != PREC_FP32;            // operands in split8 form (bf16 or fp16 pairs): 16 k per MFMA
@@ -293,13 +293,18 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
   constexpr int HR = conv_halo_rows(BM);              // HALO: LDS rows (pixels) of the resident image
   constexpr int ABUF = (HALO ? HR : BM) * LDS_STRIDE;
   constexpr int STAGE = ABUF + (BREG ? 0 : BN) * LDS_STRIDE;
-  static_assert(!BREG || (HALO && SPLIT && BM * BN <= 2 * STAGE), "BREG needs the resident image");
+  constexpr bool BREG8 = BREG && NW == 8;              // the 8-wave 256 x 256 tile with its weights in registers (see the main loop)
+  static_assert(!BREG || (HALO && SPLIT && (BREG8 || BM * BN <= 2 * STAGE)), "BREG needs the resident image");
+  static_assert(!BREG8 || (PREC == PREC_BF16X3 && EPI == EPI_MUL && TERMS == 7 && TM == 4 && TN == 2), "one instantiation: the dense split-bf16 walk");
   static_assert((BM / 8) % NW == 0 && (BN / 8) % NW == 0, "pieces must divide over the waves");
   static_assert(!HALO || EPI != EPI_STORE, "the image layer is a 1-tap GEMM");
   static_assert(NS == 2 || (NS > 2 && !HALO && !BREG), "deeper staging exists for the plain (non-resident) A path only");
   constexpr int DPC = AP + BP;                         // DMA instructions per wave and chunk (plain staging)
   static_assert((NS - 2) * DPC <= 63, "vmcnt is a 6-bit counter");
-  __shared__ __attribute__((aligned(16))) float smem[NS * STAGE];
+  // BREG8: no B stage, so LDS is the two resident images or one 128-row C slab of the epilogue, whichever is larger (128 KB)
+  constexpr int SMEM = BREG8 ? (2 * STAGE > BM / 2 * BN ? 2 * STAGE : BM / 2 * BN) : NS * STAGE;
+  constexpr int CSLAB = BREG8 ? SMEM : 2 * STAGE;      // floats the epilogue's C slab may take
+  __shared__ __attribute__((aligned(16))) float smem[SMEM];
 
   // ---- XCD-aware block remap: the n_tiles blocks that share an A tile get
   // consecutive logical ids and land on one XCD (one L2) [bijective form].
@@ -376,7 +381,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
   // 32-bit VGPR offset per lane that never changes; out-of-image taps, ragged tails and padded channels set the
   // VGPR offset to a value beyond num_records and the hardware writes zeros — no pointer selects, no 64-bit
   // VALU adds, no branches in the loop.  Descriptors are rebased per block, so tensors > 4 GiB are fine.
-  const int prow = lane >> 3, pchk = lane & 7;
+  int prow = lane >> 3, pchk = lane & 7;             // (not const: the BREG8 loop launders them, see there)
   const int wave_s = __builtin_amdgcn_readfirstlane(wave);
   typedef __attribute__((address_space(3))) void* lptr_t;
   constexpr int OOB = (int)0x80000000;                 // >= any num_records used here
@@ -593,7 +598,9 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
     }
   };
   [[maybe_unused]] PwItem pwi{};
-  if constexpr (BREG) {
+  if constexpr (BREG8) {
+    for (int p = wave_s; p < halo_np; p += NW) fire_halo_piece(prep_halo_piece(p, 0, true), p, 0);   // chunk 0; chunk 1 follows in the loop
+  } else if constexpr (BREG) {
     if (PREC == PREC_BF16X3 && a.up2_src) {
       // compact pool interface (pairs of S_c, per-token tiles: the launcher checks): item = (window of the resident image,
       // 8-channel group)
@@ -813,7 +820,89 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
     }
   };
 
-  if constexpr (BREG) {
+  if constexpr (BREG8) {
+    // ---- 8-wave tile, weights in registers.  The pipelined form of this tile ends every tap in vmcnt(0) + a workgroup
+    // barrier (the weight stage it vacates is refilled for tap + 2), which keeps all eight waves — both waves of every SIMD —
+    // in the same phase.  Here B never touches LDS: a wave takes its 64 columns' fragments of one k16 step with four coalesced
+    // 16 B loads from the fragment-major copy (wpk_frag: [kc][step][hi|lo][lane half][N] x 16 B, the BREG layout over all N
+    // columns), two steps ahead of their use in a ring of three register sets, and waits for them with a counted vmcnt.
+    // The A fragments of step s + 1 are re-read row block by row block behind the six MFMAs that consumed that block at
+    // step s (one register set: 128 accumulators + 48 B + 32 A).  The only workgroup barrier is the one where the A buffers
+    // change hands, once per channel chunk: the next chunk's resident image arrives by six DMA pieces per wave spread over
+    // the chunk's steps and is waited for (in-order vmcnt) in front of that barrier.  A chunk's 18 steps are unrolled into
+    // ONE basic block — dead pieces and prefetches past the end are clamped or go to a spare LDS slot instead of being
+    // branched around — so that hipcc counts every wait.  Same MFMA chain per output element as every other form: chunk-major,
+    // taps innermost, two k16 steps, al*bh, ah*bl, ah*bh.
+    static_assert(NSTEP == 2 && SMEM >= 2 * STAGE + NW * 8 * LDS_STRIDE, "bf16x3; a spare LDS slot per wave behind the two images");
+    const int NF = a.n_tiles * BN;                       // columns of the fragment-major copy (N % 256 == 0)
+    const int nsteps = 2 * nk;
+    const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void*)a.wpk_frag, 0, nsteps * 4 * NF * 16, RSRC_FLAGS);
+    const int fvo = ((lane >> 5) * NF + n0 + wn * TN * 32 + (lane & 31)) * 16;
+    u32x4 bq[3][2 * TN];                                 // ring of three k16 steps: [hi|lo] x TN
+    u32x4 aq[2 * TM];                                    // the step being consumed: [row block][hi|lo]
+    auto load_b = [&](u32x4* b, int gs) {                // gs = (chunk * 9 + tap) * 2 + step
+      const int so = (gs < nsteps ? gs : nsteps - 1) * 4 * NF * 16;
+#pragma unroll
+      for (int hl = 0; hl < 2; ++hl)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+          b[hl * TN + j] = __builtin_amdgcn_raw_buffer_load_b128(rsF, fvo + j * 32 * 16, so + hl * 2 * NF * 16, 0);
+    };
+    load_b(bq[0], 0);
+    load_b(bq[1], 1);
+    set_tap(0);
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      aq[2 * i] = *reinterpret_cast<const u32x4*>(smem + faddr[i]);
+      aq[2 * i + 1] = *reinterpret_cast<const u32x4*>(smem + (faddr[i] ^ 4));
+    }
+    for (int c = 0; c < cpt; ++c) {
+      const int cb = c & 1;
+      const float* Ab = smem + cb * STAGE;
+      const float* An = smem + (cb ^ 1) * STAGE;
+      // the per-tap fragment addresses and most of a piece's offsets do not depend on the chunk: left alone, hipcc hoists all of
+      // them (nine taps x four row blocks, six pieces) out of the chunk loop and spills them.  They are a few VALU ops each.
+#pragma unroll
+      for (int i = 0; i < TM; ++i) asm volatile("" : "+v"(fbase[i]), "+v"(fu[i]));
+      asm volatile("" : "+v"(prow), "+v"(pchk));
+#pragma unroll
+      for (int s = 0; s < 18; ++s) {
+        load_b(bq[(s + 2) % 3], c * 18 + s + 2);
+        if (s % 3 == 0) {                                // piece slot s / 3 of chunk c + 1 -> the buffer chunk c - 1 was read from
+          const int p = (s / 3) * NW + wave_s;
+          const bool livep = p < halo_np;
+          const HaloPiece hp = prep_halo_piece(p, c + 1, livep && c + 1 < cpt);
+          const int dst = livep ? (cb ^ 1) * STAGE + p * 8 * LDS_STRIDE : 2 * STAGE + wave_s * 8 * LDS_STRIDE;   // (dead piece: zeros into the spare slot)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lptr_t)(smem + dst), 16, hp.vo, hp.so, 0, 0);
+        }
+        if (s == 17) {
+          // A hand-over.  Loads complete in order: all but the two youngest weight steps done = every piece of chunk c + 1
+          // this wave fired (the last one at step 15) has landed; lgkmcnt(0) = this wave's reads of chunk c are done, so
+          // behind the barrier its buffer may be refilled.  (Not __syncthreads(): its fence would drain the weight loads.)
+          asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        }
+        const int nst = (s + 1) & 1;
+        if (nst == 0) set_tap(((s + 1) >> 1) % 9);
+        const float* Ax = s == 17 ? An : Ab;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          const bf16x8 ah = __builtin_bit_cast(bf16x8, aq[2 * i]), al = __builtin_bit_cast(bf16x8, aq[2 * i + 1]);
+#pragma unroll
+          for (int j = 0; j < TN; ++j) {
+            const bf16x8 bh = __builtin_bit_cast(bf16x8, bq[s % 3][j]), bl = __builtin_bit_cast(bf16x8, bq[s % 3][TN + j]);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i][j], 0, 0, 0);
+          }
+          // this row block's fragments of the next step, behind the MFMAs that have just read the old ones
+          aq[2 * i] = *reinterpret_cast<const u32x4*>(Ax + (faddr[i] ^ ((4 * nst) << 2)));
+          aq[2 * i + 1] = *reinterpret_cast<const u32x4*>(Ax + (faddr[i] ^ ((4 * nst + 1) << 2)));
+          __builtin_amdgcn_sched_barrier(0);             // (pinned: hoisted above the MFMAs the reads would need a second register set)
+        }
+      }
+    }
+  } else if constexpr (BREG) {
     static_assert(NSTEP == 2, "bf16x3");
     // B fragments of (kc = chunk*9 + tap): [step][hi|lo] x TN, one 16 B load each
     const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void*)a.wpk_frag, 0, nk * 8 * BN * 16, RSRC_FLAGS);
@@ -1158,9 +1247,9 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
     return;
   } else if constexpr (EPI != EPI_STORE) {
     // The C tile goes through the staging LDS in NH row slabs (a 256-row tile does not fit at once).
-    constexpr int NH = (BM * BN + 2 * STAGE - 1) / (2 * STAGE);
+    constexpr int NH = (BM * BN + CSLAB - 1) / CSLAB;
     constexpr int RH = BM / NH;                         // rows per slab
-    static_assert(BM % NH == 0 && RH % (TM * 32) == 0 && RH * BN <= 2 * STAGE, "slab must hold whole wave tiles");
+    static_assert(BM % NH == 0 && RH % (TM * 32) == 0 && RH * BN <= CSLAB, "slab must hold whole wave tiles");
     float* Cs = smem;
     constexpr bool SPLIT_OUT = SPLIT && (EPI == EPI_MUL || EPI == EPI_MUL_UP2);
     constexpr int CW = SPLIT_OUT ? 8 : 4;               // channels per thread (split8 output is written per group)
@@ -1749,7 +1838,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG ? 3 : NS > 2 ? 2 : conv_min_wave
 //   big   : 2,2,2,2 -> 128 x 128   (N >= 128)                 64 KB LDS, 2 blocks/CU   [fp32]
 //   n64   : 2,2,2,1 -> 128 x  64   (N == 64 layers)           48 KB LDS, 3 blocks/CU
 //   n32   : 4,1,1,1 -> 128 x  32   (N <= 32: tiny test nets)  40 KB LDS
-//   w256  : 2,4,4,2 -> 256 x 256   8 waves, 128 KB LDS, 1 block/CU   [bf16x3, N % 256 == 0]
+//   w256  : 2,4,4,2 -> 256 x 256   8 waves, 128 KB LDS, 1 block/CU   [bf16x3, N % 256 == 0; BREG: the dense walk launches, FORM_BREG8]
 // bf16x3 spends 5.3x fewer matrix cycles per byte staged, so its limiter is the L2 -> LDS path
 // (~43 GB/s per CU at 128 x 128): the 8-wave tile stages 50 % fewer bytes per FLOP.
 struct ConvTile { int BM, BN; };
@@ -1771,7 +1860,8 @@ enum ConvForm {
   FORM_HALO = 2,    // resident image (3x3, split operands), 128 x 128 / 128 x 64 / 8-wave 256 x 256
   FORM_BREG = 3,    // resident image + weights in registers (N <= 64), 128 x 64
   FORM_POOL = 4,    // FORM_HALO 128 x 128 with tiles of even height and width: the 2x2 max-pool in the dual forward's epilogue
-  FORM_IMG = 5      // EPI_IMG_STENCIL: 16 x 16 pixel patches
+  FORM_IMG = 5,     // EPI_IMG_STENCIL: 16 x 16 pixel patches
+  FORM_BREG8 = 6    // FORM_HALO's 8-wave 256 x 256 tile with the weights in registers (dense split-bf16 EPI_MUL, N % 256 == 0)
 };
 // one launch, as far as the decision depends on it.  The three requests are what the caller wants this launch to CARRY
 // (ConvArgs::up2_src, img_part, pool_gc): only some forms can, and a request never changes the tile — it is refused instead.
@@ -1942,6 +2032,11 @@ inline ConvPlan conv_plan(const ConvAsk& q, const Switches& s = sw()) {
   if (mode > 0 && (t.BN >= 128 || (mode == 2 && t.BN >= 64)) && resident(false, 0.9f)) {
     // the loader of the compact pool interface handles two items per thread and channel chunk
     if (q.up2_src && p.hrows * ((p.tw + 2) / 2 + 1) * 4 > 2 * (t.BM == 256 ? 512 : 256)) return refused;
+    // the 8-wave tile of the dense split-bf16 walk with a fragment-major weight copy: weights in registers, one barrier per
+    // channel chunk instead of one per tap (LRP_CONV_BREG8=0 disables).  A launch that carries a request keeps the pipelined
+    // kernel (its window loader is ordered by the tap barriers); so does the tail of a residual block (ConvArgs::join).
+    if (s.conv_breg8 && t.BM == 256 && prec == PREC_BF16X3 && epi == EPI_MUL && q.terms == 7 && q.frag && !asked && !q.join)
+      return done(FORM_BREG8);
     return done(FORM_HALO);
   }
   if (asked) return refused;                             // only the resident-image kernels read the compact pool interface
@@ -2061,9 +2156,16 @@ inline hipError_t conv_launch_epi(ConvArgs a, hipStream_t st) {
   // 3. its kernel
   const dim3 grid(p.m_tiles * p.n_tiles), block(p.threads);
   if constexpr (PREC != PREC_FP32 && (MUL || FWD)) {
-    if (p.form == FORM_BREG || p.form == FORM_HALO || p.form == FORM_POOL) {
+    if (p.form == FORM_BREG || p.form == FORM_HALO || p.form == FORM_POOL || p.form == FORM_BREG8) {
       if constexpr (MUL) {
         a.tile_map = conv_tile_order(a, st);
+        if constexpr (EPI == EPI_MUL && PREC == PREC_BF16X3 && TERMS == 7) {
+          if (p.form == FORM_BREG8) {
+            hipLaunchKernelGGL((conv_igemm_kernel<2, 4, 4, 2, EPI_MUL, PREC_BF16X3, true, true, 7>), grid, block, 0, st, a);
+            return hipGetLastError();
+          }
+        }
+        if (p.form == FORM_BREG8) return hipErrorInvalidValue;
         if (p.form == FORM_BREG) {
           hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 1, EPI, PREC, true, true, TERMS>), grid, block, 0, st, a);
           return hipGetLastError();

@@ -39,7 +39,7 @@ struct ConvLayer {
   DevBuf wbs;         // device record {2^k, 2^-k, norm, k} of the fp16 backward copy's power-of-two scale
   DevBuf w_fwd_il;    // the dual forward matrix with its rows interleaved per 32 channels ([w | w+] side by side): fp32 source of w_fwd_h
   std::unique_ptr<TileOrder> order{new TileOrder};   // tile-row order of this layer's reverse launch (conv_igemm.h)
-  DevBuf w_bwd_frag;  // w_bwd_s fragment-major (layers whose backward conv has N = cin <= 64: weights-in-registers kernel)
+  DevBuf w_bwd_frag;  // w_bwd_s fragment-major (layers whose backward conv has N = cin <= 64, or cin % 256 == 0 with LRP_CONV_BREG8: weights-in-registers kernels)
   DevBuf bias;
   DevBuf G;        // [max_images][H][W][cout] relevance gate (not for the top layer)
   DevBuf P;        // [max_images][H/2][W/2][cout] pooled activations (pool_after layers; overlapped encode)
@@ -267,6 +267,9 @@ struct Encoder {
     LRP_TRY(mk(L.w_bwd_h, nb));
     if (L.sparse_ok() && L.idxp.p) LRP_TRY(mk(L.w_sp, conv_sparse_weight_floats(L.cin, L.cout)));
     if (conv_npad(L.cin) == 64) { LRP_TRY(mk(L.w_bwd_frag, (size_t)64 * Kb)); LRP_TRY(mk(L.w_bwd_frag_h, (size_t)64 * Kb)); }
+    // the 8-wave weights-in-registers form of the split-bf16 walk (conv_plan FORM_BREG8): a copy as large as w_bwd_s for every layer
+    // whose reverse launch can take it at some token count
+    else if (sw().conv_breg8 && (L.cin % 256) == 0 && !(L.cout & 7)) LRP_TRY(mk(L.w_bwd_frag, nb));
     if (pack_tmp.bytes < nf * sizeof(float)) LRP_TRY(pack_tmp.alloc(nf * sizeof(float), total));
     return LRP_OK;
   }
@@ -311,12 +314,12 @@ struct Encoder {
     split(L.w_bwd.as<float>(), L.w_bwd_s.as<float>(), nb);
     if (L.w_sp.p) LRP_HIP_CHECK(conv_sparse_pack(L.w_bwd.as<float>(), L.w_sp.as<float>(), L.cin, L.cout, st));
     if (L.w_bwd_frag.p)
-      hipLaunchKernelGGL(pack_frag64_dev_kernel, dim3(stream_grid((size_t)CPo / 32 * 9 * 512)), dim3(256), 0, st, L.w_bwd_s.as<float>(),
-                         L.w_bwd_frag.as<float>(), CPo);
+      hipLaunchKernelGGL(pack_frag_dev_kernel, dim3(stream_grid((size_t)CPo / 32 * 9 * 8 * Npb)), dim3(256), 0, st, L.w_bwd_s.as<float>(),
+                         L.w_bwd_frag.as<float>(), CPo, Npb);
     LRP_TRY(make_f16_operand(L.w_bwd.as<float>(), nb, Npb, 9 * CPo, L.w_bwd_h, L.wbs, nullptr, st));
     if (L.w_bwd_frag_h.p)
-      hipLaunchKernelGGL(pack_frag64_dev_kernel, dim3(stream_grid((size_t)CPo / 32 * 9 * 512)), dim3(256), 0, st, L.w_bwd_h.as<float>(),
-                         L.w_bwd_frag_h.as<float>(), CPo);
+      hipLaunchKernelGGL(pack_frag_dev_kernel, dim3(stream_grid((size_t)CPo / 32 * 9 * 512)), dim3(256), 0, st, L.w_bwd_h.as<float>(),
+                         L.w_bwd_frag_h.as<float>(), CPo, 64);
     pack(L.w_bwd_full.as<float>(), 1, Npb, 0, 0);
     split(L.w_bwd_full.as<float>(), L.w_bwd_full_s.as<float>(), nb);
     LRP_HIP_CHECK(hipGetLastError());

@@ -120,7 +120,7 @@ int lrp_conv_plan(int32_t epi, int32_t prec, int32_t terms, int32_t NB, int32_t 
                   LRP_EPI_IMG_STENCIL == lrp::EPI_IMG_STENCIL, "lrp_hip.h LRP_EPI_*");
     static_assert(LRP_OPND_FP32 == lrp::PREC_FP32 && LRP_OPND_BF16X3 == lrp::PREC_BF16X3 && LRP_OPND_F16X2 == lrp::PREC_F16X2, "lrp_hip.h LRP_OPND_*");
     static_assert(LRP_FORM_PLAIN == lrp::FORM_PLAIN && LRP_FORM_SMALL == lrp::FORM_SMALL && LRP_FORM_HALO == lrp::FORM_HALO &&
-                  LRP_FORM_BREG == lrp::FORM_BREG && LRP_FORM_POOL == lrp::FORM_POOL && LRP_FORM_IMG == lrp::FORM_IMG, "lrp_hip.h LRP_FORM_*");
+                  LRP_FORM_BREG == lrp::FORM_BREG && LRP_FORM_POOL == lrp::FORM_POOL && LRP_FORM_IMG == lrp::FORM_IMG && LRP_FORM_BREG8 == lrp::FORM_BREG8, "lrp_hip.h LRP_FORM_*");
     if (!out11) return fail(LRP_ERR_INVALID, "null argument");
     lrp::ConvAsk q;
     q.epi = epi; q.prec = prec; q.terms = terms; q.NB = NB; q.H = H; q.W = W; q.N = N; q.Cin = Cin; q.taps = taps; q.split = split;
@@ -488,10 +488,11 @@ int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias
       const size_t nw8 = (size_t)Np * K / 8;
       LRP_TRY(wsplit.alloc(wdev.bytes, nullptr));
       hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(nw8)), dim3(256), 0, st, wdev.as<float>(), wsplit.as<float>(), nw8);
-      if (bwd && taps == 9 && Np == 64) {                  // weights-in-registers variant of the N <= 64 backward convs
-        LRP_TRY(wfrag.alloc((size_t)64 * K * sizeof(float), nullptr));
-        hipLaunchKernelGGL(pack_frag64_dev_kernel, dim3(stream_grid((size_t)conv_cinp(inC) / 32 * 9 * 512)), dim3(256), 0, st,
-                           wsplit.as<float>(), wfrag.as<float>(), conv_cinp(inC));
+      // weights-in-registers variants of the backward convs: N <= 64, and the 8-wave tile's N % 256 == 0 (LRP_CONV_BREG8)
+      if (bwd && taps == 9 && (Np == 64 || (sw().conv_breg8 && (outC % 256) == 0))) {
+        LRP_TRY(wfrag.alloc((size_t)Np * K * sizeof(float), nullptr));
+        hipLaunchKernelGGL(pack_frag_dev_kernel, dim3(stream_grid((size_t)conv_cinp(inC) / 32 * 9 * 8 * Np)), dim3(256), 0, st,
+                           wsplit.as<float>(), wfrag.as<float>(), conv_cinp(inC), Np);
       }
       const size_t n8 = (size_t)NB * H * W * inC / 8;
       LRP_TRY(insplit.alloc(n8 * 32, nullptr));
