@@ -51,6 +51,36 @@ def band_bar(ref32, ref, floor=1e-4, factor=10.0):
     return max(floor, factor * e32), e32
 
 
+def elem_ratio(out, ref, mag):
+    """max |out - ref| / mag over the elements of one operator result, in float64: `mag` is the mass each element was summed
+    from (|gate| x (|in| conv |w|), plus |bias|), so the ratio is an error per unit of what went into THAT element, and one wrong
+    pixel among millions scores what it would score alone — the whole-tensor rel_l1 divides it by the tensor.  An element without
+    mass must be exactly zero: the result is inf if one is not.  numpy arrays or torch tensors (of one device)."""
+    if hasattr(out, "detach"):
+        import torch
+        d, m = (out.double() - ref.double()).abs(), mag.double()
+        if tuple(d.shape) != tuple(m.shape):
+            raise ValueError("elem_ratio takes three arrays of one shape")
+        if bool(((m <= 0) & (d > 0)).any()):
+            return float("inf")
+        return float((d / torch.where(m > 0, m, torch.ones_like(m))).max()) if d.numel() else 0.0
+    d = np.abs(np.asarray(out, dtype=np.float64) - np.asarray(ref, dtype=np.float64))
+    m = np.asarray(mag, dtype=np.float64)
+    if d.shape != m.shape:
+        raise ValueError("elem_ratio takes three arrays of one shape")
+    if ((m <= 0) & (d > 0)).any():
+        return float("inf")
+    return float((d / np.where(m > 0, m, 1.0)).max()) if d.size else 0.0
+
+
+def elem_bar(r32, split):
+    """The bound of elem_ratio for an operator result, from the reference alone: `r32` is elem_ratio of torch's float32
+    evaluation of the same graph.  fp32 operator: max(2^-22, 10 r32) — 10 for a float32 sum in another order (as band_bar),
+    2^-22 = four ulp for the epilogue's roundings when K is tiny.  Split-bf16 operator: 2^-16 more, the worst case per product
+    of the three-term split (csrc/conv_igemm.h header)."""
+    return (2.0 ** -16 if split else 0.0) + max(2.0 ** -22, 10.0 * r32)
+
+
 def transpose_spatial(w):
     """A weight dict with every 4-d (kh, kw, cin, cout) kernel transposed in its two spatial axes: the network that maps the
     transposed image to the transposed result."""

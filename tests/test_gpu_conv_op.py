@@ -1,16 +1,23 @@
-"""-m gpu: the fp32-MFMA implicit-GEMM conv kernel (lrp_op_conv through the C ABI)
-against float64 torch-CPU convolutions.  Covers every tile configuration
-(N>64, N==64, N<=32), ragged M tails, Cin not a multiple of 32, 1x1 mode and
-both LRP epilogues (gate multiply, gate multiply through a 2x2 pool)."""
+"""-m gpu: the implicit-GEMM conv kernel (lrp_op_conv through the C ABI) against float64 torch-CPU convolutions under a
+whole-tensor relative L1: ragged M tails, Cin not a multiple of 32, 1x1 mode and both LRP epilogues (gate multiply, gate multiply
+through a 2x2 pool).  These stacks of a few small images are small grids: under default switches the launch plan puts most of them
+on the 64 x 64 tiles (the form each case takes is noted beside it and written into its report line).  Every form of the kernel,
+one launch at a time and per output element, is tests/test_gpu_conv_forms.py over the table of tests/conv_cases.py."""
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_cases
 from conftest import rel_l1
 from gpu_util import report
 
 pytestmark = pytest.mark.gpu
+
+
+def _planned(case, taps, mode, split):
+    """the form lrp_op_conv takes for this launch under the switches in force, e.g. 'SMALL 64x64' (conv_cases.op_plan)"""
+    return conv_cases.plan_name(conv_cases.op_plan(conv_cases.Case(*case[:5], taps, mode, split, {}, "", (), "")))
 
 
 def _ref_conv(x, w, b, taps, relu):
@@ -30,13 +37,13 @@ def _ref_convT(s, w, taps):
 
 
 FWD_CASES = [  # NB, H, W, Cin, Cout, taps
-    (2, 8, 8, 32, 128, 9),      # big tile, exact
-    (1, 14, 14, 64, 256, 9),    # big tile, two N tiles, ragged M (196)
-    (3, 7, 5, 8, 64, 9),        # n64 tile, Cin < 32, odd sizes
-    (2, 6, 6, 16, 16, 9),       # n32 tile, tiny
-    (1, 9, 9, 36, 40, 9),       # Cin, Cout not multiples of 32
-    (1, 1, 300, 64, 96, 1),     # 1x1 mode (dense layer), ragged M
-    (2, 16, 16, 128, 192, 9),   # N=192: one full + one half big tile
+    (2, 8, 8, 32, 128, 9),      # SMALL 64x64: two M tiles, two N tiles, exact
+    (1, 14, 14, 64, 256, 9),    # SMALL 64x64: four N tiles, ragged M (196)
+    (3, 7, 5, 8, 64, 9),        # SMALL 64x64: Cin < 32, odd sizes
+    (2, 6, 6, 16, 16, 9),       # PLAIN 128x32, tiny
+    (1, 9, 9, 36, 40, 9),       # SMALL 64x64: Cin, Cout not multiples of 32
+    (1, 1, 300, 64, 96, 1),     # SMALL 64x64: 1x1 mode (dense layer), ragged M
+    (2, 16, 16, 128, 192, 9),   # SMALL 64x64: N = 192, three N tiles
 ]
 
 
@@ -53,7 +60,7 @@ def test_conv_forward(case, mode):
     out = op_conv(torch.as_tensor(x).cuda(), w, b, None, mode, taps).cpu().numpy()
     ref = _ref_conv(x, w, b, taps, relu=(mode == 0))
     err = rel_l1(out, ref)
-    report("conv_fwd", case=list(case), mode=mode, rel_l1=err)
+    report("conv_fwd", case=list(case), mode=mode, plan=_planned(case, taps, mode, False), rel_l1=err)
     assert out.shape == ref.shape
     assert err < 2e-6, err
 
@@ -84,7 +91,7 @@ def test_conv_lrp_backward(case, mode):
         c = c.repeat(2, axis=1).repeat(2, axis=2)
     ref = c * gate
     err = rel_l1(out, ref)
-    report("conv_bwd", case=list(case), mode=mode, rel_l1=err)
+    report("conv_bwd", case=list(case), mode=mode, plan=_planned(case, 9, mode, False), rel_l1=err)
     assert out.shape == ref.shape
     assert err < 2e-6, err
 
@@ -103,16 +110,19 @@ def test_identity_weight_asymmetric():
     np.testing.assert_allclose(out, ref, rtol=1e-6, atol=1e-6)
 
 
-# ---- split-bf16 path, incl. the halo-resident 3x3 variant (LRP_CONV_HALO: 0 never, 1 auto, 2 always)
+# ---- split-bf16 path (LRP_CONV_HALO: 0 never, 1 auto, 2 always the resident-image kernels).  Forward, all but two of these
+# small grids take SMALL 64x64 at every setting; backward they take BREG 128x64 (N = 40 ... 64 output columns; SMALL under
+# LRP_CONV_HALO=0), SMALL (N = 72) or PLAIN 128x32 (N <= 32).  The resident-image geometries that the shapes were once chosen for — tiles that span images, W = 33,
+# widths below 14, the power-of-two pitch — are the cases of tests/conv_cases.py with the small-grid rules switched off.
 SPLIT_CASES = [  # NB, H, W, Cin, Cout   (forward: Cin -> Cout; backward: S has Cout channels, out has Cin)
-    (3, 14, 14, 64, 128),     # tw = 14: tiles span image boundaries in the stack
-    (2, 28, 28, 40, 64),      # tw = 14 on W = 28 (BM = 128), Cin not a multiple of 32
-    (1, 56, 56, 8, 128),      # two column tiles per row
-    (2, 7, 5, 72, 64),        # W < every candidate: ragged columns, tiny image
-    (1, 9, 33, 16, 128),      # W = 33 = 3 x 11
-    (2, 16, 16, 64, 64),      # power-of-two width (the halo pitch equals tw + 2 only for 14 / 30)
-    (33, 56, 56, 8, 256),     # 8-wave 256 x 256 tile (>= 400 blocks), tw = 28
-    (140, 14, 14, 16, 256),   # 8-wave tile on 14 x 14 images: 18 stack rows per tile, ~1.3 images
+    (3, 14, 14, 64, 128),     # fwd SMALL; bwd BREG 128x64 tw 14 th 9: tiles span image boundaries in the stack
+    (2, 28, 28, 40, 64),      # fwd SMALL; bwd BREG: N = 40 < 64, two column tiles
+    (1, 56, 56, 8, 128),      # fwd SMALL; bwd PLAIN 128x32 (N = 8)
+    (2, 7, 5, 72, 64),        # fwd SMALL; bwd SMALL (N = 72)
+    (1, 9, 33, 16, 128),      # fwd SMALL; bwd PLAIN 128x32 (N = 16)
+    (2, 16, 16, 64, 64),      # fwd SMALL; bwd BREG tw 8 under LRP_CONV_HALO=2, SMALL otherwise
+    (33, 56, 56, 8, 256),     # fwd HALO 256x256, the 8-wave tile (>= 400 blocks), tw 14 th 18; bwd PLAIN 128x32
+    (140, 14, 14, 16, 256),   # fwd HALO 128x128 tw 14 th 9 (218 x 2 tiles: below the 8-wave tile's 400 blocks); bwd PLAIN 128x32
     (3, 28, 28, 64, 64),      # backward: N = 64, two channel chunks -> weights-in-registers kernel (one group)
     (2, 14, 28, 64, 128),     # backward: N = 64, four chunks = two groups of the resident image
     (2, 14, 14, 56, 96),      # backward: N = 56 (< 64), three chunks: the last group holds one chunk
@@ -136,7 +146,7 @@ def test_split_bf16_forward(case, halo_mode):
     b = rs.standard_normal(Cout).astype(np.float32)
     out = op_conv(torch.as_tensor(x).cuda(), w, b, None, 1, 9, split_bf16=True).cpu().numpy()
     err = rel_l1(out, _ref_conv(x, w, b, 9, relu=False))
-    report("conv_split_fwd", case=list(case), halo=halo_mode, rel_l1=err)
+    report("conv_split_fwd", case=list(case), halo=halo_mode, plan=_planned(case, 9, 1, True), rel_l1=err)
     assert err < 2e-5, err
 
 
@@ -157,7 +167,7 @@ def test_split_bf16_lrp_backward(case, mode, halo_mode):
     if mode == 3:
         c = c.repeat(2, axis=1).repeat(2, axis=2)
     err = rel_l1(out, c * gate)
-    report("conv_split_bwd", case=list(case), mode=mode, halo=halo_mode, rel_l1=err)
+    report("conv_split_bwd", case=list(case), mode=mode, halo=halo_mode, plan=_planned((NB,) + tuple(case[1:]), 9, mode, True), rel_l1=err)
     assert err < 2e-5, err
 
 
@@ -169,7 +179,8 @@ SMALL_CASES = [  # NB, H, W, Cin, Cout
     (10, 14, 14, 256, 128),   # ten words: 16 x 1 large tiles
     (1, 28, 28, 72, 64),      # N = 64 tile family, Cin not a multiple of 32
     (2, 7, 5, 40, 192),       # ragged M, N = 192
-    (10, 28, 28, 256, 256),   # 62 x 2 large tiles (forward) / 62 x 2 (backward): between 128 and 256 -> the 128 x 64 tiles
+    (10, 28, 28, 256, 256),   # split: 62 x 2 large tiles = 124 <= 128, still the 64 x 64 tiles; fp32: PLAIN 128x64 (62 x 4, the halved
+                              # fp32 tile) under either setting.  The 128 x 64 tiles of the grids in between: tests/conv_cases.py
 ]
 
 
