@@ -289,8 +289,11 @@ int64_t lrp_workspace_bytes(const lrp_handle* h);
  * mode 2: out = convT(in, w) * aux   (LRP backward with gate `aux`, shape of out)
  * mode 3: like 2 with 2x nearest up-sampling of the conv result (pool routing).
  * mode | LRP_CONV_SPLIT_BF16 (modes 1..3, channels % 8 == 0): the same operator on the split-bf16
- * MFMA path the engine uses by default (three bf16 MFMAs per fp32 product); in/out stay float32. */
-enum { LRP_CONV_SPLIT_BF16 = 0x100 };
+ * MFMA path the engine uses by default (three bf16 MFMAs per fp32 product); in/out stay float32.
+ * mode | LRP_CONV_SPLIT_BF16 | LRP_CONV_WREG (mode 2, taps = 9, Cin % 128 == 0, otherwise LRP_ERR_UNSUPPORTED): the entry also makes
+ * the fragment-major copy of the weights, so that a launch on the 128 x 128 resident-image tile takes the weights-in-registers
+ * loop (LRP_FORM_BREG4).  Without the bit such a launch keeps the pipelined kernel. */
+enum { LRP_CONV_SPLIT_BF16 = 0x100, LRP_CONV_WREG = 0x200 };
 int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias_host,
                 const float* aux_dev, float* out_dev, int32_t NB, int32_t H, int32_t W,
                 int32_t Cin, int32_t Cout, int32_t taps, int32_t mode, void* stream);
@@ -525,11 +528,16 @@ int lrp_reload_switches(void);
  *   out11  ok, form (LRP_FORM_*), BM, BN, threads, tw, th, hrows, tpt, m_tiles, n_tiles;  ok = 0: the launch would be refused
  * A request is carried by a resident-image form or refused, never dropped: IMG_PART with fp32 operands is refused (no kernel
  * of that format reads it), and under LRP_CONV_HALO=2 a launch with a request is still decided at the default fill of 0.9.
+ * LRP_FORM_BREG4 / LRP_FORM_BREG4_POOL: the 128 x 128 tile and geometry of LRP_FORM_HALO / LRP_FORM_POOL on the loop that takes its
+ * weights from registers (one workgroup barrier per channel chunk) — with LRP_PLAN_FRAG and N % 128 == 0, for the dense split-bf16
+ * LRP_EPI_MUL launch (no JOIN, no request) and the interleaved fp16-pair LRP_EPI_FWD_DUAL (terms 7 | 23; POOL_GC gives the _POOL
+ * form).  LRP_CONV_BREG4=0 gives the pipelined forms back.
  * The reference has no counterpart. */
 enum { LRP_EPI_BIAS_RELU = 0, LRP_EPI_BIAS = 1, LRP_EPI_MUL = 2, LRP_EPI_MUL_UP2 = 3, LRP_EPI_FWD_DUAL = 4, LRP_EPI_STORE = 5,
        LRP_EPI_IMG_STENCIL = 6 };
 enum { LRP_OPND_FP32 = 0, LRP_OPND_BF16X3 = 1, LRP_OPND_F16X2 = 2 };
-enum { LRP_FORM_PLAIN = 0, LRP_FORM_SMALL = 1, LRP_FORM_HALO = 2, LRP_FORM_BREG = 3, LRP_FORM_POOL = 4, LRP_FORM_IMG = 5, LRP_FORM_BREG8 = 6 };
+enum { LRP_FORM_PLAIN = 0, LRP_FORM_SMALL = 1, LRP_FORM_HALO = 2, LRP_FORM_BREG = 3, LRP_FORM_POOL = 4, LRP_FORM_IMG = 5, LRP_FORM_BREG8 = 6,
+       LRP_FORM_BREG4 = 7, LRP_FORM_BREG4_POOL = 8 };
 enum { LRP_PLAN_FRAG = 1, LRP_PLAN_JOIN = 2, LRP_PLAN_DUAL_IL = 4, LRP_PLAN_GMASK = 8,
        LRP_PLAN_UP2_SRC = 16, LRP_PLAN_IMG_PART = 32, LRP_PLAN_POOL_GC = 64 };
 int lrp_conv_plan(int32_t epi, int32_t prec, int32_t terms, int32_t NB, int32_t H, int32_t W, int32_t N, int32_t Cin, int32_t taps,

@@ -19,6 +19,7 @@ LRP_TRAIN_FP32, LRP_TRAIN_BF16 = 0, 1
 LRP_EPI_BIAS_RELU, LRP_EPI_BIAS, LRP_EPI_MUL, LRP_EPI_MUL_UP2, LRP_EPI_FWD_DUAL, LRP_EPI_STORE, LRP_EPI_IMG_STENCIL = range(7)
 LRP_OPND_FP32, LRP_OPND_BF16X3, LRP_OPND_F16X2 = 0, 1, 2
 LRP_FORM_PLAIN, LRP_FORM_SMALL, LRP_FORM_HALO, LRP_FORM_BREG, LRP_FORM_POOL, LRP_FORM_IMG, LRP_FORM_BREG8 = range(7)
+LRP_FORM_BREG4, LRP_FORM_BREG4_POOL = 7, 8
 LRP_PLAN_FRAG, LRP_PLAN_JOIN, LRP_PLAN_DUAL_IL, LRP_PLAN_GMASK, LRP_PLAN_UP2_SRC, LRP_PLAN_IMG_PART, LRP_PLAN_POOL_GC = 1, 2, 4, 8, 16, 32, 64
 
 

@@ -33,6 +33,8 @@ struct Switches {
   int conv_breg = 1;        // LRP_CONV_BREG=0     N <= 64 backward convs without the weights-in-registers kernel
   int conv_breg8 = 1;       // LRP_CONV_BREG8=0    the dense 8-wave 256 x 256 walk launches on the pipelined kernel (a weight stage in LDS, a barrier per tap);
                             //                     also read when weights are set: only then are the layers' fragment-major copies made
+  int conv_breg4 = 1;       // LRP_CONV_BREG4=0    the 128 x 128 resident-image launches with N % 128 == 0 (dense split-bf16 walk, interleaved dual forward) on the
+                            //                     pipelined kernel; also read when weights are set: only then are the fragment-major copies made
   int conv_small = 1;       // LRP_CONV_SMALL=0    small grids keep the 128-row tiles (no 64 x 64 tiles)
   int conv_mid = 1;         // LRP_CONV_MID=0      no 128 x 64 tiles for the grids just above the small ones
   int epi_fast = 1;         // LRP_EPI_FAST=0      MUL / MUL_UP2 epilogues always through the general pass loop
@@ -56,6 +58,7 @@ struct Switches {
     // (read apart from the list above, which tests/test_capi_symbols.py holds against the rows of tests/test_gpu_switches.py: this
     // switch's run against the default path — operator and engine level, bit-identical — is tests/test_gpu_conv_breg8.py)
     if (const char* e = getenv("LRP_CONV_BREG8")) conv_breg8 = atoi(e);
+    if (const char* e = getenv("LRP_CONV_BREG4")) conv_breg4 = atoi(e);   // (likewise: tests/test_gpu_conv_breg4.py)
   }
 };
 inline Switches& sw() {

@@ -125,7 +125,7 @@ struct TileOrder {
 struct ConvArgs {
   const float* in;     // [NB][H][W][Cin] fp32
   const float* wpk;    // [n_tiles*BN][K] fp32, K = taps*CinP, CinP = roundup(Cin,32), zero padded
-  const float* wpk_frag;  // BREG: the same weights fragment-major, [kc][step][hi|lo][lane half][all N columns] x 16 B (N = 64, or N % 256 == 0)
+  const float* wpk_frag;  // BREG: the same weights fragment-major, [kc][step][hi|lo][lane half][all N columns] x 16 B (N = 64, or N % 128 == 0)
   int NB, H, W, Cin, CinP;
   int N;               // valid output columns
   int taps;            // 9 (3x3 same) or 1
@@ -272,8 +272,8 @@ constexpr int conv_halo_rows(int BM) { return BM == 256 ? 352 : 192; }   // x 12
 // only one per channel group — which is what the 12-MFMA-per-tap waves of the N = 64 tiles could not amortise.
 // TERMS (split operands): which partial products of (ah + al)(bh + bl) are issued — bit 0: al*bh, bit 1: ah*bl, bit 2: ah*bh
 // (al*bl never).  7 = all three: every split launch but the PREC_F16X2 forms below.  PREC_F16X2 only: 5 = bit 1 off, the
-// weights' lo half is not read (two MFMAs); bit 4 (23 = 7 | 16, interleaved dual forward) = the same for the odd column
-// tiles only (Z+).  conv_launch instantiates 7 for PREC_BF16X3 and 7, 5, 23 for PREC_F16X2.
+// weights' lo half is not read (two MFMAs); bit 4 (23 = 7 | 16, interleaved dual forward) = the same for the odd 32-column
+// blocks of the matrix only (Z+: z_tile in the kernel).  conv_launch instantiates 7 for PREC_BF16X3 and 7, 5, 23 for PREC_F16X2.
 // NS (plain staging only: !HALO, !BREG): LDS stages of the k pipeline.  2 = chunk kc+2 is launched at the barrier of iteration kc
 // and must have landed one iteration later — fine when an iteration holds 24-48 MFMAs per wave, but the 64 x 64 tiles of the
 // small-grid launches (6 MFMAs per wave and iteration) then run at one L2 / HBM round trip per k-step [MI355X, one image:
@@ -282,9 +282,12 @@ constexpr int conv_halo_rows(int BM) { return BM == 256 ? 352 : 192; }   // x 12
 // GMASK (EPI_MUL, PREC_FP32 only: the ResNet encoder's gradient walks, resnet_encoder.h explain_grad): `aux` and `join_gate` are
 // BYTE masks [images][H][W][N] (1 = the ReLU behind this tensor was active) instead of fp32 gates.  A template axis of its own, so
 // that no other instantiation carries its loads (a runtime flag in the shared epilogue costs the VGG walk registers).
+// PW (the 128 x 128 weights-in-registers loop only): the launch reads the compact pool interface (ConvArgs::up2_src).  The
+// pipelined kernels decide that at run time; in the unrolled chunk of this loop the loader's registers would be carried through the
+// dense launch's loop as well, and every reuse of one of them waited for the weight loads in flight [ISA: vmcnt(1) three times a chunk].
 template <int WM, int WN, int TM, int TN, int EPI, int PREC, bool HALO = false, bool BREG = false, int TERMS = 7, int NS = 2,
-          bool GMASK = false>
-__global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2 : conv_min_waves(WM * WN, TM, TN, HALO)) void conv_igemm_kernel(ConvArgs a) {
+          bool GMASK = false, bool PW = false>
+__global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 : NS > 2 ? 2 : conv_min_waves(WM * WN, TM, TN, HALO)) void conv_igemm_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (the buffer-resource builtins are device-only)
   constexpr int NW = WM * WN, NT = 64 * NW;           // waves / threads per block (4 or 8 waves)
   constexpr bool SPLIT = PREC != PREC_FP32;            // operands in split8 form (bf16 or fp16 pairs): 16 k per MFMA
@@ -294,16 +297,24 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2
   constexpr int ABUF = (HALO ? HR : BM) * LDS_STRIDE;
   constexpr int STAGE = ABUF + (BREG ? 0 : BN) * LDS_STRIDE;
   constexpr bool BREG8 = BREG && NW == 8;              // the 8-wave 256 x 256 tile with its weights in registers (see the main loop)
-  static_assert(!BREG || (HALO && SPLIT && (BREG8 || BM * BN <= 2 * STAGE)), "BREG needs the resident image");
+  constexpr bool BREG4 = BREG && NW == 4 && TN == 2;   // the same loop on the 4-wave 128 x 128 tile (FORM_BREG4: walk and dual forward)
+  constexpr bool BREGC = BREG8 || BREG4;               // weights in registers, one barrier per channel CHUNK
+  static_assert(!BREG || (HALO && SPLIT && (BREGC || BM * BN <= 2 * STAGE)), "BREG needs the resident image");
   static_assert(!BREG8 || (PREC == PREC_BF16X3 && EPI == EPI_MUL && TERMS == 7 && TM == 4 && TN == 2), "one instantiation: the dense split-bf16 walk");
+  static_assert(!BREG4 || (TM == 2 && ((PREC == PREC_BF16X3 && EPI == EPI_MUL && TERMS == 7) || (PREC == PREC_F16X2 && EPI == EPI_FWD_DUAL && (TERMS == 7 || TERMS == 23)))),
+                "two uses: the dense split-bf16 walk and the interleaved fp16-pair dual forward");
+  static_assert(!PW || (BREG4 && PREC == PREC_BF16X3), "PW: the split-bf16 walk on the 128 x 128 weights-in-registers loop");
   static_assert((BM / 8) % NW == 0 && (BN / 8) % NW == 0, "pieces must divide over the waves");
   static_assert(!HALO || EPI != EPI_STORE, "the image layer is a 1-tap GEMM");
   static_assert(NS == 2 || (NS > 2 && !HALO && !BREG), "deeper staging exists for the plain (non-resident) A path only");
   constexpr int DPC = AP + BP;                         // DMA instructions per wave and chunk (plain staging)
   static_assert((NS - 2) * DPC <= 63, "vmcnt is a 6-bit counter");
   // BREG8: no B stage, so LDS is the two resident images or one 128-row C slab of the epilogue, whichever is larger (128 KB)
-  constexpr int SMEM = BREG8 ? (2 * STAGE > BM / 2 * BN ? 2 * STAGE : BM / 2 * BN) : NS * STAGE;
-  constexpr int CSLAB = BREG8 ? SMEM : 2 * STAGE;      // floats the epilogue's C slab may take
+  // BREG4: the two resident images + a spare slot per wave (52 KB) or the epilogue's whole 128 x 128 C tile (64 KB; 80 KB pipelined)
+  constexpr int SMEM = BREG8   ? (2 * STAGE > BM / 2 * BN ? 2 * STAGE : BM / 2 * BN)
+                       : BREG4 ? (2 * STAGE + NW * 8 * LDS_STRIDE > BM * BN ? 2 * STAGE + NW * 8 * LDS_STRIDE : BM * BN)
+                               : NS * STAGE;
+  constexpr int CSLAB = BREGC ? SMEM : 2 * STAGE;      // floats the epilogue's C slab may take
   __shared__ __attribute__((aligned(16))) float smem[SMEM];
 
   // ---- XCD-aware block remap: the n_tiles blocks that share an A tile get
@@ -534,10 +545,11 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2
   // barriers ahead of the chunk's first read, into the A buffer last read a chunk ago.  Works on stack tiles and per-token tiles.
   typedef unsigned u32x2w __attribute__((ext_vector_type(2)));
   struct PwItem { u32x4 hi, lo; u32x2w q; };
-  [[maybe_unused]] const bool pw = HALO && !BREG && PREC == PREC_BF16X3 && a.up2_src != nullptr;
+  // (BREG4: the same items, sequenced by the chunk's steps instead — see its loop)
+  [[maybe_unused]] const bool pw = BREG4 ? PW : HALO && !BREG && PREC == PREC_BF16X3 && a.up2_src != nullptr;
   [[maybe_unused]] int pw_wx0 = 0, pw_nwx = 1, pw_items = 0, pw_ri0 = 0, pw_ri1 = 0;
   [[maybe_unused]] float pw_inv_nwx = 1.f;
-  if constexpr (HALO && !BREG && PREC == PREC_BF16X3) {
+  if constexpr (HALO && (!BREG || PW) && PREC == PREC_BF16X3) {
     if (pw) {
       pw_wx0 = (x0 - 1) >> 1;                           // (arithmetic shift: the window column outside the image for x0 = 0)
       pw_nwx = ((x0 + a.tw) >> 1) - pw_wx0 + 1;
@@ -563,7 +575,9 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2
     // unconditional loads from a clamped (always valid) place; an invalid item's values are zeroed at the store
     const int nc = r.valid ? n : 0, wyc = r.valid ? (h >> 1) : 0, wxc = r.valid ? r.wx : 0, co = r.valid ? (chunk << 5) + r.g * 8 : 0;
     const int rel = nc - img0;
-    const int img = rel == 0 ? pw_ri0 : rel == 1 ? pw_ri1 : (a.row2img ? a.row2img[nc] : nc);
+    // (PW: a resident image spans two images at most — conv_plan takes the form for hrows <= H only — and a look-up here would drain
+    //  the weight loads in flight; an item that is not valid loads from a clamped place of image pw_ri0)
+    const int img = PW ? (rel == 1 ? pw_ri1 : pw_ri0) : rel == 0 ? pw_ri0 : rel == 1 ? pw_ri1 : (a.row2img ? a.row2img[nc] : nc);
     r.sp = a.up2_src + (((size_t)nc * Hp + wyc) * Wp + wxc) * a.Cin + co;
     r.qp = a.up2_gpos + (((size_t)img * Hp + wyc) * Wp + wxc) * a.Cin + co;
     return r;
@@ -598,7 +612,11 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2
     }
   };
   [[maybe_unused]] PwItem pwi{};
-  if constexpr (BREG8) {
+  if constexpr (BREGC) {
+    if constexpr (PW) {
+      pw_load(pwi, tid, 0); pw_store(pwi, tid, 0, 0);
+      if (tid + NT < pw_items) { pw_load(pwi, tid + NT, 0); pw_store(pwi, tid + NT, 0, 0); }
+    } else
     for (int p = wave_s; p < halo_np; p += NW) fire_halo_piece(prep_halo_piece(p, 0, true), p, 0);   // chunk 0; chunk 1 follows in the loop
   } else if constexpr (BREG) {
     if (PREC == PREC_BF16X3 && a.up2_src) {
@@ -748,6 +766,12 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2
   for (int q = 0; q < 4; ++q)
     koff[q] = SPLIT ? (((4 * (q >> 1) + 2 * hh + (q & 1)) ^ swz) << 2)     // q = 2*step + {hi,lo}
                                   : (((2 * q + hh) ^ swz) << 2);
+  // TERMS bit 4: is column tile j of this wave an ODD 32-column block of the matrix (interleaved rows: Z+)?  By the block's place
+  // in the MATRIX, not in the wave: with one column tile per wave (the 64 x 64, 128 x 64 and 128 x 32 tiles) the wave's own index
+  // is always 0, and those tiles computed Z+ with all three terms — the denominators, and with them an image's heat-map in the
+  // fp16-pair walk, depended on which tile the batch size picked.  Two column tiles per wave: j & 1, known at compile time.
+  const int ztile0 = TN % 2 == 0 ? 0 : ((n0 >> 5) + (wave_s % WN) * TN) & 1;
+  auto z_tile = [&](int j) { return ((ztile0 + j) & 1) != 0; };
   struct Frag { u32x4 a[SPLIT ? 2 * TM : TM], b[SPLIT ? 2 * TN : TN]; };
   // HALO: A addresses come from faddr[] (set_tap); chunk c ^ swizzle = (c0 ^ swizzle) ^ (c - c0) for disjoint bits
   auto read_frag = [&](Frag& f, const float* Ab, const float* Bb, int st) {
@@ -775,7 +799,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         f.b[2 * j] = *reinterpret_cast<const u32x4*>(Bb + j * 32 * LDS_STRIDE + koff[2 * st]);
-        if (PREC != PREC_F16X2 || ((TERMS & 2) != 0 && !((TERMS & 16) != 0 && (j & 1))))   // (two-term form: the lo chunk is never read)
+        if (PREC != PREC_F16X2 || ((TERMS & 2) != 0 && !((TERMS & 16) != 0 && TN % 2 == 0 && (j & 1))))   // (two-term form: the lo chunk is never read)
           f.b[2 * j + 1] = *reinterpret_cast<const u32x4*>(Bb + j * 32 * LDS_STRIDE + koff[2 * st + 1]);
       }
     } else {
@@ -793,7 +817,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2
           const f16x8 bh = __builtin_bit_cast(f16x8, f.b[2 * j]);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[i][j], 0, 0, 0);    // small terms first
           // TERMS 7: the weights' lo half too.  TERMS bit 4 (interleaved dual forward): not for the odd column tiles = Z+
-          if ((TERMS & 2) != 0 && !((TERMS & 16) != 0 && (j & 1)))          // (folds once the j loop is unrolled)
+          if ((TERMS & 2) != 0 && !((TERMS & 16) != 0 && z_tile(j)))        // (TN even: folds once the j loop is unrolled; else wave-uniform)
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, __builtin_bit_cast(f16x8, f.b[2 * j + 1]), acc[i][j], 0, 0, 0);
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[i][j], 0, 0, 0);
         }
@@ -820,8 +844,8 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2
     }
   };
 
-  if constexpr (BREG8) {
-    // ---- 8-wave tile, weights in registers.  The pipelined form of this tile ends every tap in vmcnt(0) + a workgroup
+  if constexpr (BREGC) {
+    // ---- 8-wave tile (and, BREG4, the 4-wave 128 x 128 tile), weights in registers.  The pipelined form of this tile ends every tap in vmcnt(0) + a workgroup
     // barrier (the weight stage it vacates is refilled for tap + 2), which keeps all eight waves — both waves of every SIMD —
     // in the same phase.  Here B never touches LDS: a wave takes its 64 columns' fragments of one k16 step with four coalesced
     // 16 B loads from the fragment-major copy (wpk_frag: [kc][step][hi|lo][lane half][N] x 16 B, the BREG layout over all N
@@ -833,8 +857,17 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2
     // ONE basic block — dead pieces and prefetches past the end are clamped or go to a spare LDS slot instead of being
     // branched around — so that hipcc counts every wait.  Same MFMA chain per output element as every other form: chunk-major,
     // taps innermost, two k16 steps, al*bh, ah*bl, ah*bh.
-    static_assert(NSTEP == 2 && SMEM >= 2 * STAGE + NW * 8 * LDS_STRIDE, "bf16x3; a spare LDS slot per wave behind the two images");
-    const int NF = a.n_tiles * BN;                       // columns of the fragment-major copy (N % 256 == 0)
+    // BREG4 (TM x TN = 2 x 2): a 12-row resident image is 24 pieces = six per wave as well, and two outstanding weight steps
+    // are again 2 x 2 TN = 8 loads.  The fp16-pair dual forward rides on the same loop: TERMS 23 leaves out the lo half of the
+    // odd column tiles (Z+; three loads per step, six outstanding), and the blocked accumulation folds acc into tot behind the
+    // same taps as the pipelined loop — kc = 9 chunk + tap, (kc & 7) == 7 <=> ((chunk + tap) & 7) == 7 — under a wave-uniform
+    // branch that holds VALU work only, so the weight waits stay counted.
+    static_assert(NSTEP == 2 && SMEM >= 2 * STAGE + NW * 8 * LDS_STRIDE, "split operands; a spare LDS slot per wave behind the two images");
+    static_assert(6 * NW * 8 >= HR, "six piece slots per wave cover the resident image");
+    // does column tile j read the weights' lo half (mfma_frag's rule)
+    auto uses_lo = [](int j) { return PREC != PREC_F16X2 || ((TERMS & 2) != 0 && !((TERMS & 16) != 0 && (j & 1))); };
+    constexpr int LPS = PREC == PREC_F16X2 && (TERMS & 16) != 0 ? 2 * TN - TN / 2 : 2 * TN;   // weight loads per k16 step
+    const int NF = a.n_tiles * BN;                       // columns of the fragment-major copy (N % BN == 0)
     const int nsteps = 2 * nk;
     const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void*)a.wpk_frag, 0, nsteps * 4 * NF * 16, RSRC_FLAGS);
     const int fvo = ((lane >> 5) * NF + n0 + wn * TN * 32 + (lane & 31)) * 16;
@@ -846,7 +879,8 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2
       for (int hl = 0; hl < 2; ++hl)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-          b[hl * TN + j] = __builtin_amdgcn_raw_buffer_load_b128(rsF, fvo + j * 32 * 16, so + hl * 2 * NF * 16, 0);
+          if (hl == 0 || uses_lo(j))
+            b[hl * TN + j] = __builtin_amdgcn_raw_buffer_load_b128(rsF, fvo + j * 32 * 16, so + hl * 2 * NF * 16, 0);
     };
     load_b(bq[0], 0);
     load_b(bq[1], 1);
@@ -868,7 +902,15 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2
 #pragma unroll
       for (int s = 0; s < 18; ++s) {
         load_b(bq[(s + 2) % 3], c * 18 + s + 2);
-        if (s % 3 == 0) {                                // piece slot s / 3 of chunk c + 1 -> the buffer chunk c - 1 was read from
+        if constexpr (PW) {
+          // compact pool interface: behind the hand-over barrier of chunk c - 1 the other buffer is free for all of chunk c.  The two
+          // items of a thread go through the same ten registers one after the other: loaded early, written mid-chunk; the
+          // lgkmcnt(0) in front of the next hand-over covers the writes.  (Unconditional: a dead item loads from a clamped
+          // address and writes nothing or zeros, a chunk past the end zeros — like the dead pieces below.)
+          if (s == 0) pw_load(pwi, tid, c + 1);
+          if (s == 6) { pw_store(pwi, tid, c + 1, cb ^ 1); pw_load(pwi, tid + NT, c + 1); }
+          if (s == 12) pw_store(pwi, tid + NT, c + 1, cb ^ 1);
+        } else if (s % 3 == 0) {                         // piece slot s / 3 of chunk c + 1 -> the buffer chunk c - 1 was read from
           const int p = (s / 3) * NW + wave_s;
           const bool livep = p < halo_np;
           const HaloPiece hp = prep_halo_piece(p, c + 1, livep && c + 1 < cpt);
@@ -879,7 +921,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2
           // A hand-over.  Loads complete in order: all but the two youngest weight steps done = every piece of chunk c + 1
           // this wave fired (the last one at step 15) has landed; lgkmcnt(0) = this wave's reads of chunk c are done, so
           // behind the barrier its buffer may be refilled.  (Not __syncthreads(): its fence would drain the weight loads.)
-          asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+          asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(2 * LPS) : "memory");
         }
         const int nst = (s + 1) & 1;
         if (nst == 0) set_tap(((s + 1) >> 1) % 9);
@@ -887,18 +929,41 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
-          const bf16x8 ah = __builtin_bit_cast(bf16x8, aq[2 * i]), al = __builtin_bit_cast(bf16x8, aq[2 * i + 1]);
+          if constexpr (PREC == PREC_F16X2) {
+            const f16x8 ah = __builtin_bit_cast(f16x8, aq[2 * i]), al = __builtin_bit_cast(f16x8, aq[2 * i + 1]);
 #pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            const bf16x8 bh = __builtin_bit_cast(bf16x8, bq[s % 3][j]), bl = __builtin_bit_cast(bf16x8, bq[s % 3][TN + j]);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i][j], 0, 0, 0);
+            for (int j = 0; j < TN; ++j) {
+              const f16x8 bh = __builtin_bit_cast(f16x8, bq[s % 3][j]);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[i][j], 0, 0, 0);
+              if (uses_lo(j)) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, __builtin_bit_cast(f16x8, bq[s % 3][TN + j]), acc[i][j], 0, 0, 0);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[i][j], 0, 0, 0);
+            }
+          } else {
+            const bf16x8 ah = __builtin_bit_cast(bf16x8, aq[2 * i]), al = __builtin_bit_cast(bf16x8, aq[2 * i + 1]);
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+              const bf16x8 bh = __builtin_bit_cast(bf16x8, bq[s % 3][j]), bl = __builtin_bit_cast(bf16x8, bq[s % 3][TN + j]);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i][j], 0, 0, 0);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i][j], 0, 0, 0);
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i][j], 0, 0, 0);
+            }
           }
           // this row block's fragments of the next step, behind the MFMAs that have just read the old ones
           aq[2 * i] = *reinterpret_cast<const u32x4*>(Ax + (faddr[i] ^ ((4 * nst) << 2)));
           aq[2 * i + 1] = *reinterpret_cast<const u32x4*>(Ax + (faddr[i] ^ ((4 * nst + 1) << 2)));
           __builtin_amdgcn_sched_barrier(0);             // (pinned: hoisted above the MFMAs the reads would need a second register set)
+        }
+        if constexpr (BLOCKED) {
+          if ((s & 1) && ((c + (s >> 1)) & (FLUSH - 1)) == FLUSH - 1) {   // behind tap s >> 1: where the pipelined loop flushes
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+              for (int j = 0; j < TN; ++j) {
+                tot[i][j] += acc[i][j];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+              }
+          }
         }
       }
     }
@@ -1838,6 +1903,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 ? 3 : NS > 2 ? 2
 //   big   : 2,2,2,2 -> 128 x 128   (N >= 128)                 64 KB LDS, 2 blocks/CU   [fp32]
 //   n64   : 2,2,2,1 -> 128 x  64   (N == 64 layers)           48 KB LDS, 3 blocks/CU
 //   n32   : 4,1,1,1 -> 128 x  32   (N <= 32: tiny test nets)  40 KB LDS
+//   big, BREG (FORM_BREG4): weights in registers, 64 KB LDS, 2 blocks/CU   [dense bf16x3 walk, interleaved f16x2 dual forward; N % 128 == 0]
 //   w256  : 2,4,4,2 -> 256 x 256   8 waves, 128 KB LDS, 1 block/CU   [bf16x3, N % 256 == 0; BREG: the dense walk launches, FORM_BREG8]
 // bf16x3 spends 5.3x fewer matrix cycles per byte staged, so its limiter is the L2 -> LDS path
 // (~43 GB/s per CU at 128 x 128): the 8-wave tile stages 50 % fewer bytes per FLOP.
@@ -1861,7 +1927,9 @@ enum ConvForm {
   FORM_BREG = 3,    // resident image + weights in registers (N <= 64), 128 x 64
   FORM_POOL = 4,    // FORM_HALO 128 x 128 with tiles of even height and width: the 2x2 max-pool in the dual forward's epilogue
   FORM_IMG = 5,     // EPI_IMG_STENCIL: 16 x 16 pixel patches
-  FORM_BREG8 = 6    // FORM_HALO's 8-wave 256 x 256 tile with the weights in registers (dense split-bf16 EPI_MUL, N % 256 == 0)
+  FORM_BREG8 = 6,   // FORM_HALO's 8-wave 256 x 256 tile with the weights in registers (dense split-bf16 EPI_MUL, N % 256 == 0)
+  FORM_BREG4 = 7,   // FORM_HALO's 128 x 128 tile with the weights in registers (N % 128 == 0: dense split-bf16 EPI_MUL, interleaved fp16-pair dual forward)
+  FORM_BREG4_POOL = 8   // FORM_POOL's even tiles on the FORM_BREG4 loop
 };
 // one launch, as far as the decision depends on it.  The three requests are what the caller wants this launch to CARRY
 // (ConvArgs::up2_src, img_part, pool_gc): only some forms can, and a request never changes the tile — it is refused instead.
@@ -1986,6 +2054,7 @@ inline ConvPlan conv_plan(const ConvAsk& q, const Switches& s = sw()) {
     if (epi != EPI_FWD_DUAL || prec != PREC_F16X2 || !q.dual_il || q.up2_src || q.img_part || !s.pool_fused || mode <= 0 ||
         (q.H & 1) || (q.W & 1) || t.BM != 128 || t.BN != 128 || (s.conv_small && grid <= 2 * CONV_SMALL_BLOCKS) || !resident(true, 0.8f))
       return refused;
+    if (s.conv_breg4 && q.frag && (q.N % 128) == 0 && (q.terms == 7 || q.terms == 23)) return done(FORM_BREG4_POOL);   // (see FORM_BREG4 below)
     return done(FORM_POOL);
   }
   // N <= 64: resident image + weights in registers, no barrier per tap (LRP_CONV_BREG=0 disables).  128-row tiles, whatever
@@ -2037,6 +2106,13 @@ inline ConvPlan conv_plan(const ConvAsk& q, const Switches& s = sw()) {
     // kernel (its window loader is ordered by the tap barriers); so does the tail of a residual block (ConvArgs::join).
     if (s.conv_breg8 && t.BM == 256 && prec == PREC_BF16X3 && epi == EPI_MUL && q.terms == 7 && q.frag && !asked && !q.join)
       return done(FORM_BREG8);
+    // the same loop on the 128 x 128 tile (LRP_CONV_BREG4=0 disables): the dense split-bf16 walk launches and the interleaved
+    // fp16-pair dual forward, N a multiple of the tile.  The walk launch may read the compact pool interface (its window loader
+    // is sequenced by the chunk's steps there, for resident images that span two images at most); img_part and pool_gc never get here.
+    if (s.conv_breg4 && t.BM == 128 && t.BN == 128 && q.frag && (q.N % 128) == 0 && !q.join && !(q.up2_src && p.hrows > q.H) &&
+        ((prec == PREC_BF16X3 && epi == EPI_MUL && q.terms == 7) ||
+         (prec == PREC_F16X2 && epi == EPI_FWD_DUAL && q.dual_il && (q.terms == 7 || q.terms == 23))))
+      return done(FORM_BREG4);
     return done(FORM_HALO);
   }
   if (asked) return refused;                             // only the resident-image kernels read the compact pool interface
@@ -2156,6 +2232,20 @@ inline hipError_t conv_launch_epi(ConvArgs a, hipStream_t st) {
   // 3. its kernel
   const dim3 grid(p.m_tiles * p.n_tiles), block(p.threads);
   if constexpr (PREC != PREC_FP32 && (MUL || FWD)) {
+    if (p.form == FORM_BREG4 || p.form == FORM_BREG4_POOL) {
+      if constexpr ((EPI == EPI_MUL && PREC == PREC_BF16X3 && TERMS == 7) || (EPI == EPI_FWD_DUAL && PREC == PREC_F16X2 && (TERMS == 7 || TERMS == 23))) {
+        if constexpr (MUL) {
+          a.tile_map = conv_tile_order(a, st);
+          if (a.up2_src) {
+            hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, true, true, TERMS, 2, false, true>), grid, block, 0, st, a);
+            return hipGetLastError();
+          }
+        }
+        hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, true, true, TERMS>), grid, block, 0, st, a);
+        return hipGetLastError();
+      }
+      return hipErrorInvalidValue;
+    }
     if (p.form == FORM_BREG || p.form == FORM_HALO || p.form == FORM_POOL || p.form == FORM_BREG8) {
       if constexpr (MUL) {
         a.tile_map = conv_tile_order(a, st);

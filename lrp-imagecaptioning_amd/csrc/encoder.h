@@ -39,7 +39,9 @@ struct ConvLayer {
   DevBuf wbs;         // device record {2^k, 2^-k, norm, k} of the fp16 backward copy's power-of-two scale
   DevBuf w_fwd_il;    // the dual forward matrix with its rows interleaved per 32 channels ([w | w+] side by side): fp32 source of w_fwd_h
   std::unique_ptr<TileOrder> order{new TileOrder};   // tile-row order of this layer's reverse launch (conv_igemm.h)
-  DevBuf w_bwd_frag;  // w_bwd_s fragment-major (layers whose backward conv has N = cin <= 64, or cin % 256 == 0 with LRP_CONV_BREG8: weights-in-registers kernels)
+  DevBuf w_bwd_frag;  // w_bwd_s fragment-major (layers whose backward conv has N = cin <= 64, or cin % 256 == 0 with LRP_CONV_BREG8, or cin % 128 == 0 with
+                      // LRP_CONV_BREG4: weights-in-registers kernels)
+  DevBuf w_fwd_frag;  // w_fwd_h fragment-major (interleaved layers with 2 cout % 128 == 0, LRP_CONV_BREG4: the dual forward's weights-in-registers loop)
   DevBuf bias;
   DevBuf G;        // [max_images][H][W][cout] relevance gate (not for the top layer)
   DevBuf P;        // [max_images][H/2][W/2][cout] pooled activations (pool_after layers; overlapped encode)
@@ -269,7 +271,12 @@ struct Encoder {
     if (conv_npad(L.cin) == 64) { LRP_TRY(mk(L.w_bwd_frag, (size_t)64 * Kb)); LRP_TRY(mk(L.w_bwd_frag_h, (size_t)64 * Kb)); }
     // the 8-wave weights-in-registers form of the split-bf16 walk (conv_plan FORM_BREG8): a copy as large as w_bwd_s for every layer
     // whose reverse launch can take it at some token count
-    else if (sw().conv_breg8 && (L.cin % 256) == 0 && !(L.cout & 7)) LRP_TRY(mk(L.w_bwd_frag, nb));
+    // (and FORM_BREG4: the 128 x 128 tile's, for N = cin % 128 == 0)
+    else if (((sw().conv_breg8 && (L.cin % 256) == 0) || (sw().conv_breg4 && (L.cin % 128) == 0)) && !(L.cout & 7)) LRP_TRY(mk(L.w_bwd_frag, nb));
+    else L.w_bwd_frag.release();
+    // the dual forward on the same loop: w_fwd_h fragment-major, as large as w_fwd_h (VGG16: 118 MB per handle)
+    if (sw().conv_breg4 && dual_interleaved(L) && (2 * L.cout) % 128 == 0) LRP_TRY(mk(L.w_fwd_frag, (size_t)conv_npad(2 * L.cout) * Kf));
+    else L.w_fwd_frag.release();
     if (pack_tmp.bytes < nf * sizeof(float)) LRP_TRY(pack_tmp.alloc(nf * sizeof(float), total));
     return LRP_OK;
   }
@@ -306,6 +313,9 @@ struct Encoder {
     if (L.w_fwd_il.p) pack(L.w_fwd_il.as<float>(), 0, Np2, 2, 0);
     LRP_TRY(make_f16_operand(L.w_fwd_il.p ? L.w_fwd_il.as<float>() : L.w_fwd.as<float>(), (size_t)Np2 * 9 * CPi, 0, 0, L.w_fwd_h,
                              L.wds, nullptr, st));
+    if (L.w_fwd_frag.p)
+      hipLaunchKernelGGL(pack_frag_dev_kernel, dim3(stream_grid((size_t)CPi / 32 * 9 * 8 * Np2)), dim3(256), 0, st, L.w_fwd_h.as<float>(),
+                         L.w_fwd_frag.as<float>(), CPi, Np2);
     pack(L.w_fwd_a.as<float>(), 0, Npa, 0, 0);
     pack(tmp, 0, Npa, 0, 1);
     split(tmp, L.w_fwd_zs.as<float>(), nf);
@@ -549,6 +559,7 @@ struct Encoder {
     cd.act_max_out = r.slots_of(li);
     cd.scale_per_img = per_img ? 1 : 0; cd.img_rows = L.H * L.W; cd.n_imgs = B;
     cd.dual_il = L.w_fwd_il.p ? 1 : 0;
+    cd.wpk_frag = cd.dual_il ? L.w_fwd_frag.as<float>() : nullptr;
     return cd;
   }
   // no pool behind an interleaved layer: a_l and G_l leave the epilogue together — a_l into the ping-pong buffer its consumer

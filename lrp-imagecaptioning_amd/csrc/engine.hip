@@ -120,7 +120,8 @@ int lrp_conv_plan(int32_t epi, int32_t prec, int32_t terms, int32_t NB, int32_t 
                   LRP_EPI_IMG_STENCIL == lrp::EPI_IMG_STENCIL, "lrp_hip.h LRP_EPI_*");
     static_assert(LRP_OPND_FP32 == lrp::PREC_FP32 && LRP_OPND_BF16X3 == lrp::PREC_BF16X3 && LRP_OPND_F16X2 == lrp::PREC_F16X2, "lrp_hip.h LRP_OPND_*");
     static_assert(LRP_FORM_PLAIN == lrp::FORM_PLAIN && LRP_FORM_SMALL == lrp::FORM_SMALL && LRP_FORM_HALO == lrp::FORM_HALO &&
-                  LRP_FORM_BREG == lrp::FORM_BREG && LRP_FORM_POOL == lrp::FORM_POOL && LRP_FORM_IMG == lrp::FORM_IMG && LRP_FORM_BREG8 == lrp::FORM_BREG8, "lrp_hip.h LRP_FORM_*");
+                  LRP_FORM_BREG == lrp::FORM_BREG && LRP_FORM_POOL == lrp::FORM_POOL && LRP_FORM_IMG == lrp::FORM_IMG && LRP_FORM_BREG8 == lrp::FORM_BREG8 &&
+                  LRP_FORM_BREG4 == lrp::FORM_BREG4 && LRP_FORM_BREG4_POOL == lrp::FORM_BREG4_POOL, "lrp_hip.h LRP_FORM_*");
     if (!out11) return fail(LRP_ERR_INVALID, "null argument");
     lrp::ConvAsk q;
     q.epi = epi; q.prec = prec; q.terms = terms; q.NB = NB; q.H = H; q.W = W; q.N = N; q.Cin = Cin; q.taps = taps; q.split = split;
@@ -472,7 +473,10 @@ int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias
     if (taps != 1 && taps != 9) return fail(LRP_ERR_INVALID, "taps must be 1 or 9");
     if (Cin % 4 != 0) return fail(LRP_ERR_UNSUPPORTED, "Cin must be a multiple of 4");
     const bool split = (mode & LRP_CONV_SPLIT_BF16) != 0;   // same op on the split-bf16 MFMA path (fp32 in, fp32 out)
-    mode &= ~LRP_CONV_SPLIT_BF16;
+    const bool wreg = (mode & LRP_CONV_WREG) != 0;          // ... with the fragment-major weight copy of the 128 x 128 weights-in-registers loop
+    mode &= ~(LRP_CONV_SPLIT_BF16 | LRP_CONV_WREG);
+    if (wreg && !(split && mode == 2 && taps == 9 && (Cin % 128) == 0))
+      return fail(LRP_ERR_UNSUPPORTED, "LRP_CONV_WREG needs LRP_CONV_SPLIT_BF16, mode 2, 9 taps and Cin %% 128 == 0");
     if (mode < 0 || mode > 3) return fail(LRP_ERR_INVALID, "mode must be 0..3");
     if (split && mode == 0) return fail(LRP_ERR_UNSUPPORTED, "the split-bf16 path has no relu epilogue (modes 1..3)");
     const bool bwd = mode >= 2;
@@ -489,7 +493,7 @@ int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias
       LRP_TRY(wsplit.alloc(wdev.bytes, nullptr));
       hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(nw8)), dim3(256), 0, st, wdev.as<float>(), wsplit.as<float>(), nw8);
       // weights-in-registers variants of the backward convs: N <= 64, and the 8-wave tile's N % 256 == 0 (LRP_CONV_BREG8)
-      if (bwd && taps == 9 && (Np == 64 || (sw().conv_breg8 && (outC % 256) == 0))) {
+      if (bwd && taps == 9 && (Np == 64 || (sw().conv_breg8 && (outC % 256) == 0) || wreg)) {
         LRP_TRY(wfrag.alloc((size_t)Np * K * sizeof(float), nullptr));
         hipLaunchKernelGGL(pack_frag_dev_kernel, dim3(stream_grid((size_t)conv_cinp(inC) / 32 * 9 * 8 * Np)), dim3(256), 0, st,
                            wsplit.as<float>(), wfrag.as<float>(), conv_cinp(inC), Np);
@@ -514,6 +518,10 @@ int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias
       return fail(LRP_ERR_INVALID, "aux (gate) required for backward modes");
     }
     static const int epi_of_mode[4] = {EPI_BIAS_RELU, EPI_BIAS, EPI_MUL, EPI_MUL_UP2};
+    if (split && !wreg && ca.wpk_frag) {                   // without the bit a 128 x 128 launch keeps the pipelined kernel
+      const ConvPlan p = conv_plan(conv_ask(epi_of_mode[mode], PREC_BF16X3, 7, false, ca));
+      if (p.ok && p.form == FORM_BREG4) ca.wpk_frag = nullptr;
+    }
     LRP_HIP_CHECK(conv_launch(epi_of_mode[mode], ca, st, split ? PREC_BF16X3 : PREC_FP32));
     LRP_HIP_CHECK(hipStreamSynchronize(st));             // weights are freed on return
     return LRP_OK;

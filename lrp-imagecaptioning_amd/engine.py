@@ -460,11 +460,12 @@ LRPEngine.profile_records = _profile_records
 
 
 CONV_SPLIT_BF16 = 0x100
+CONV_WREG = 0x200
 
 
-def op_conv(x, w_hwio, bias, aux, mode, taps=9, split_bf16=False):
+def op_conv(x, w_hwio, bias, aux, mode, taps=9, split_bf16=False, wreg=False):
     """Operator-level entry for unit tests of the MFMA conv kernel (see lrp_op_conv); split_bf16 runs the
-    same operator on the split-bf16 path (LRP_CONV_SPLIT_BF16)."""
+    same operator on the split-bf16 path (LRP_CONV_SPLIT_BF16), wreg with the fragment-major weight copy (LRP_CONV_WREG)."""
     lib = _capi.load()
     dev = x.device
     w = np.ascontiguousarray(w_hwio, dtype=np.float32)
@@ -482,7 +483,7 @@ def op_conv(x, w_hwio, bias, aux, mode, taps=9, split_bf16=False):
                                 b.ctypes.data_as(C.c_void_p) if b is not None else None,
                                 C.c_void_p(aux.data_ptr()) if aux is not None else None,
                                 C.c_void_p(out.data_ptr()), NB, H, W, Cin, Cout, taps,
-                                mode | (CONV_SPLIT_BF16 if split_bf16 else 0),
+                                mode | (CONV_SPLIT_BF16 if split_bf16 else 0) | (CONV_WREG if wreg else 0),
                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return out
 
