@@ -20,13 +20,18 @@
 // so that the workgroups resident on an XCD share one arrangement in its L2.
 //
 // Tile (large form) 256 windows x 256 output channels, 8 waves of 128 x 64 (as the dense 8-wave tile); per 8-channel set three
-// k-steps (own | h + d | v) of 24 smfmacs per wave, two k-steps per barrier.  B: LDS-DMA, four 32 KB stages (two super-steps).
-// A: the tile's windows + a one-window ring, 96 B per window and chunk (pairs + four planes of index words, the latter
-// precomputed once per image by conv_sparse_index_kernel), by 16 B-per-lane LDS-DMA from chunk-major sources, double-buffered
-// per 8-channel set.  162 016 B of LDS, 225 VGPRs, no spills: one workgroup per CU.
+// k-steps (own | h + d | v) of 24 smfmacs per wave.  A: the tile's windows + a one-window ring, 96 B per window and chunk (pairs +
+// four planes of index words, the latter precomputed once per image by conv_sparse_index_kernel), by 16 B-per-lane LDS-DMA from
+// chunk-major sources.  Two K loops (template axis WREG, LRP_CONV_SPARSE_WREG, profiles/sparse_wreg_ab.txt):
+//   weights in registers (the default)  B by eight 16 B register loads per wave and k-step straight from the packed layout, a ring
+//     of three column-fragment sets refilled behind their last use, counted vmcnt; A double-buffered per 16-channel chunk, ONE
+//     workgroup barrier per chunk (the hand-over).  65 536 B of LDS, 249 VGPRs, no scratch, no spills.
+//   LDS stages (=0, the tested fall-back)  B by LDS-DMA through four 32 KB stages (two super-steps), two k-steps per barrier; A
+//     double-buffered per 8-channel set.  162 016 B of LDS, 225 VGPRs, no spills.
+// One workgroup per CU either way.
 //
 // Small form (SparseTileSmall; small grids, conv_sparse_small_grid): 64 windows (4 window rows x 14) x 128 columns, 4 waves of
-// 32 x 64, the same loop with 16 KB B stages: 74 976 B of LDS, 98 VGPRs, no spills: two workgroups per CU.  An output element
+// 32 x 64, the LDS-stage loop with 16 KB B stages: 74 976 B of LDS, 98 VGPRs, no spills: two workgroups per CU.  An output element
 // sees the same chain of smfmacs in both forms, so they agree to the bit — and the walk takes these kernels for every token and
 // image count (Encoder::explain chooses by layer shape only), which keeps a picture's heat-map independent of its batch.
 // Default path of the walk for the pooled boundaries with N % 256 == 0 (VGG16: block4_conv3, block3_conv3); LRP_SPARSE_POOL=0
@@ -82,11 +87,17 @@ struct SparseTile {
   static constexpr int NSLAB = BM / 64;                            // epilogue slabs of 64 rows
   static constexpr int EPI_P = 64 * (BN / 8) / NT;                 // epilogue items (row, 8 columns) per thread and slab
   static constexpr int LDS = SP_NSTAGE * BSTAGE + 2 * ABUF + 128;  // (+ the window row -> image table)
+  // weights in registers (WREG): no B stage; two buffers of a whole 16-channel chunk (set 0 | set 1), or the epilogue's C slab
+  static constexpr int CBUF = 2 * ABUF;
+  static constexpr int CSLOTS = 6;                                 // DMA pieces per wave and chunk: one of each sub-plane of the two sets
+  static constexpr int LDS_WREG = 2 * CBUF + 128 > 64 * BN * 4 ? 2 * CBUF + 128 : 64 * BN * 4;
   static_assert(TH * SP_TW <= BM && BM % 64 == 0 && 256 % BN == 0, "tile");
   static_assert(BPIECES * NW * 1024 == BSTAGE && EPI_P * NT == 64 * (BN / 8), "pieces");
   static_assert(SP_NSTAGE * BSTAGE >= 64 * BN * 4, "the epilogue's C slab lies in the B stages");
   static_assert((TH + 2) * 4 <= 128, "image table");
   static_assert(LDS <= 160 * 1024, "LDS");
+  static_assert(2 * CBUF <= 65536, "WREG: every A address is an immediate offset of a ds_read");
+  static_assert(SUBPIECES <= NW, "WREG: a wave moves one piece of every sub-plane");
   static_assert(PENT >= 64, "a DMA piece is 64 windows");
 };
 typedef SparseTile<2, 4, 4, 2, 18> SparseTileLarge;
@@ -216,12 +227,13 @@ __global__ __launch_bounds__(256) void conv_sparse_pack_kernel(const float* __re
   }
 }
 
-template <class TL>
+template <class TL, bool WREG>
 __global__ __launch_bounds__(TL::NT, 2) void conv_sparse_kernel(SparseArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
   constexpr int MI = TL::MI, NJ = TL::NJ, NW = TL::NW, NT = TL::NT, BN = TL::BN, TH = TL::TH;
   constexpr int NENT = TL::NENT, PENT = TL::PENT, SUB = TL::SUB, ABUF = TL::ABUF, BSTAGE = TL::BSTAGE, PLANE = TL::PLANE;
-  __shared__ __attribute__((aligned(16))) unsigned char lds[TL::LDS];
+  constexpr int CBUF = TL::CBUF;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[WREG ? TL::LDS_WREG : TL::LDS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / TL::WNW, wn = wave % TL::WNW;
   const int l31 = lane & 31, half = lane >> 5;
   const int per_class = a.m_tiles * a.n_tiles;
@@ -234,14 +246,19 @@ __global__ __launch_bounds__(TL::NT, 2) void conv_sparse_kernel(SparseArgs a) {
   const int nys = a.NB * Hp;                                // window rows of the stack
   const int n0 = nt * BN;
   const int nt256 = n0 >> 8, ncol0 = n0 & 255;             // the packed 256-column weight tile of this tile's columns, its first column in it
-  const float inv_Hp = 1.0f / (float)Hp;
+  float inv_Hp = 1.0f / (float)Hp;
+  if constexpr (WREG) {                                    // (a scalar register: no VGPR lives through the K loop for it)
+    float sc_;
+    asm volatile("v_readfirstlane_b32 %0, %1" : "=s"(sc_) : "v"(inv_Hp));
+    inv_Hp = sc_;
+  }
   auto divmod = [](int x, int d, float inv, int& qq, int& r) {
     qq = (int)(((float)x + 0.5f) * inv);
     r = x - qq * d;
     if (r < 0) { --qq; r += d; } else if (r >= d) { ++qq; r -= d; }
   };
-  unsigned char* Bs = lds;
-  unsigned char* As = lds + SP_NSTAGE * BSTAGE;
+  [[maybe_unused]] unsigned char* Bs = lds;
+  unsigned char* As = WREG ? lds : lds + SP_NSTAGE * BSTAGE;      // (WREG: no B stages)
 
   // ---- A in LDS: six sub-planes per buffer — pairs hi, pairs lo, index words, each for set 0 and set 1 — of 16 B per resident
   // window: [lane half 0: 8 B | lane half 1: 8 B].  The 16 lanes LDS serves per cycle of a ds_read_b64 read 16 (nearly) consecutive
@@ -291,7 +308,7 @@ __global__ __launch_bounds__(TL::NT, 2) void conv_sparse_kernel(SparseArgs a) {
   // on the counter, and a load that misses L2 stalls the step it was issued in, also when only half of the waves stage; one DWORD
   // per lane into a swizzled 32 B-per-window image, +0.9 ms — 123 DMA instructions per chunk.)  A piece = 64 windows of one
   // sub-plane; wave w moves pieces w, w + NW, ...; windows outside the image and the all-zero entry are out-of-range offsets = zeros.
-  int* imgtab = reinterpret_cast<int*>(As + 2 * ABUF);          // resident window row hy -> image of its token
+  int* imgtab = reinterpret_cast<int*>(As + (WREG ? 2 * CBUF : 2 * ABUF));   // resident window row hy -> image of its token
   if (tid < TH + 2) {
     const int Ys = Y0 - 1 + tid;
     int n_, wy;
@@ -301,19 +318,14 @@ __global__ __launch_bounds__(TL::NT, 2) void conv_sparse_kernel(SparseArgs a) {
   const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc((void*)a.sc, 0, 0x7FFFFFFF, RSRC_FLAGS);
   const __amdgpu_buffer_rsrc_t rsI = __builtin_amdgcn_make_buffer_rsrc((void*)a.idxp, 0, 0x7FFFFFFF, RSRC_FLAGS);
   constexpr int OOB = (int)0x80000000;
-  auto fire_a = [&](int slot, int set8, int abuf) {           // set8 = 8-channel set of the layer (two per 16-channel chunk of the sources)
-    // (opaque copies: the address math of a slot does not depend on the set, and hipcc otherwise keeps every slot's worth of it
-    //  alive across the K loop; recomputed per call it is ~25 VALU instructions)
-    int wv = wave_s, ln = lane;
-    asm volatile("" : "+s"(wv), "+v"(ln));
-    int pj = wv + NW * slot;
-    if (pj >= TL::APIECES) pj = TL::APIECES - 1;             // (spare slots repeat the last piece: idempotent)
-    const int pl = pj / TL::SUBPIECES, jp = pj - pl * TL::SUBPIECES;       // sub-plane (hi, lo, index words), piece of it (wave-uniform)
+  // one piece of 8-channel set set8 (two per 16-channel chunk of the sources) -> the set's sub-planes at dst;
+  // !live: zeros
+  auto fire_piece = [&](int pl, int jp, int ln, int set8, unsigned char* dst, bool live) {   // sub-plane (hi, lo, index words), piece of it (wave-uniform)
     const int first = jp * 64 < PENT - 64 ? jp * 64 : PENT - 64;           // (the last piece overlaps its predecessor)
     const int e = first + ln;
     const int hy = e >> 4, hx = e & 15;
     const int Ys = Y0 - 1 + hy, wx = x0 - 1 + hx;
-    const bool ok = e < NENT && Ys >= 0 && Ys < nys && wx >= 0 && wx < Wp;
+    const bool ok = live && e < NENT && Ys >= 0 && Ys < nys && wx >= 0 && wx < Wp;
     int n_, wy;
     divmod(ok ? Ys : 0, Hp, inv_Hp, n_, wy);
     const int chunk = set8 >> 1, s = set8 & 1;
@@ -324,8 +336,17 @@ __global__ __launch_bounds__(TL::NT, 2) void conv_sparse_kernel(SparseArgs a) {
       const int img = imgtab[ok ? hy : 0];
       vo = (((((img * 4 + q) * (C >> 4) + chunk) * Hp + wy) * Wp + wx) << 5) + s * 16;
     }
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(pl < 2 ? rsS : rsI, (lptr_t)(As + abuf * ABUF + pl * SUB + first * 16), 16, ok ? vo : OOB,
-                                             0, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(pl < 2 ? rsS : rsI, (lptr_t)(dst + pl * SUB + first * 16), 16, ok ? vo : OOB, 0, 0, 0);
+  };
+  auto fire_a = [&](int slot, int set8, int abuf) {
+    // (opaque copies: the address math of a slot does not depend on the set, and hipcc otherwise keeps every slot's worth of it
+    //  alive across the K loop; recomputed per call it is ~25 VALU instructions)
+    int wv = wave_s, ln = lane;
+    asm volatile("" : "+s"(wv), "+v"(ln));
+    int pj = wv + NW * slot;
+    if (pj >= TL::APIECES) pj = TL::APIECES - 1;             // (spare slots repeat the last piece: idempotent)
+    const int pl = pj / TL::SUBPIECES;
+    fire_piece(pl, pj - pl * TL::SUBPIECES, ln, set8, As + abuf * ABUF, true);
   };
   auto fire_set = [&](int set8, int abuf) {
 #pragma unroll
@@ -343,11 +364,26 @@ __global__ __launch_bounds__(TL::NT, 2) void conv_sparse_kernel(SparseArgs a) {
   const int nsteps2 = nchunks * 6;
   // global step index t -> where its 32 KB of B lie: chunk16 * 6 + 2 * group + set  (the pack kernel's order)
   auto bsrc = [&](int chunk, int t6) { return chunk * 6 + 2 * (t6 % 3) + t6 / 3; };
+  // WREG: piece slot sl of a wave = sub-plane sl % 3 of set sl / 3 of the chunk (known at compile time: nothing to branch on), of
+  // which wave w moves piece w (the waves past SUBPIECES repeat the last one: idempotent) -> chunk buffer cbuf
+  auto fire_chunk_piece = [&](int slot, int chunk, int cbuf, bool live) {
+    int wv = wave_s;                                         // (opaque copy: as in fire_a; the lane is counted anew, no register lives
+    asm volatile("" : "+s"(wv));                             //  through the loop for it)
+    int ln;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=&v"(ln));
+    const int s2 = slot / 3;
+    fire_piece(slot % 3, wv < TL::SUBPIECES ? wv : TL::SUBPIECES - 1, ln, 2 * chunk + s2, As + cbuf * CBUF + s2 * ABUF, live);
+  };
   __syncthreads();                                         // (imgtab)
-  fire_set(0, 0);
-  if (nchunks * 2 > 1) fire_set(1, 1);
-  fire_b(bsrc(0, 0), 0);
-  fire_b(bsrc(0, 1), 1);
+  if constexpr (WREG) {
+#pragma unroll
+    for (int sl = 0; sl < TL::CSLOTS; ++sl) fire_chunk_piece(sl, 0, 0, true);
+  } else {
+    fire_set(0, 0);
+    if (nchunks * 2 > 1) fire_set(1, 1);
+    fire_b(bsrc(0, 0), 0);
+    fire_b(bsrc(0, 1), 1);
+  }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
@@ -382,32 +418,156 @@ __global__ __launch_bounds__(TL::NT, 2) void conv_sparse_kernel(SparseArgs a) {
       b.l[j] = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
     }
   };
-  // one k-step: group grp (0 own, 1 h + d, 2 v) of the set in buffer Ab against the B fragments b
-  auto kstep = [&](const unsigned char* Ab, int grp, const BF& b) {
+  // the sub-plane offset of row block i's own (0), horizontal (1), vertical (2), diagonal (3) window.  WREG keeps them as 16-bit pairs
+  // and unpacks at every use (volatile, so that hipcc neither hoists nor shares the unpacked values: sixteen registers become eight)
+  [[maybe_unused]] int e_oh[MI], e_vd[MI];
+  if constexpr (WREG) {
+    static_assert(PENT * 16 < 65536, "offsets fit 16 bits");
+#pragma unroll
+    for (int i = 0; i < MI; ++i) { e_oh[i] = e_own[i] | (e_h[i] << 16); e_vd[i] = e_v[i] | (e_d[i] << 16); }
+  }
+  auto eoff = [&](int i, int which) -> int {
+    if constexpr (WREG) {
+      int o;
+      const int pk = which < 2 ? e_oh[i] : e_vd[i];
+      if (which & 1) asm volatile("v_lshrrev_b32 %0, 16, %1" : "=v"(o) : "v"(pk));
+      else asm volatile("v_and_b32 %0, 0xffff, %1" : "=v"(o) : "v"(pk));
+      return o;
+    } else {
+      return which == 0 ? e_own[i] : which == 1 ? e_h[i] : which == 2 ? e_v[i] : e_d[i];
+    }
+  };
+  // row block i's compressed operand of group grp (0 own, 1 h + d, 2 v) of the set in buffer Ab: pairs hi, pairs lo, index word
+  struct AF { bf16x8 vh, vl; int ix; };
+  struct AR { u32x2 h0, h1, l0, l1; unsigned i0, i1; };    // as read from LDS (h1, l1, i1: the diagonal window's, group 1 only)
+  auto read_raw = [&](int i, const unsigned char* Ab, int grp) -> AR {
     const unsigned char* Ah = Ab;
     const unsigned char* Al = Ab + SUB;
     const unsigned char* Ai = Ab + 2 * SUB;
+    AR r{};
+    if (grp == 1) {
+      const int oh = eoff(i, 1), od = eoff(i, 3);
+      r.h0 = ld8(Ah + oh); r.h1 = ld8(Ah + od);
+      r.l0 = ld8(Al + oh); r.l1 = ld8(Al + od);
+      r.i0 = ld2(Ai + oh + 2); r.i1 = ld2(Ai + od + 4);
+    } else {
+      const int oo = eoff(i, grp == 0 ? 0 : 2);
+      r.h0 = ld8(Ah + oo);
+      r.l0 = ld8(Al + oo);
+      r.i0 = ld2(Ai + oo + (grp == 0 ? 0 : 6));
+    }
+    return r;
+  };
+  auto finish_a = [&](const AR& r, int grp) -> AF {
+    AF f;
+    if (grp == 1) {
+      f.vh = pairup(r.h0, r.h1);
+      f.vl = pairup(r.l0, r.l1);
+      f.ix = (int)(r.i0 | r.i1);
+    } else {
+      f.vh = expand(r.h0);
+      f.vl = expand(r.l0);
+      f.ix = (int)r.i0;
+    }
+    return f;
+  };
+  auto read_a = [&](int i, const unsigned char* Ab, int grp) -> AF { return finish_a(read_raw(i, Ab, grp), grp); };
+  // the three products of one accumulator and k-step, small terms first
+  auto mma3 = [&](f32x16& c, const AF& f, bf16x16 bh, bf16x16 bl) {
+    c = __builtin_amdgcn_smfmac_f32_32x32x32_bf16(f.vl, bh, c, f.ix, 0, 0);
+    c = __builtin_amdgcn_smfmac_f32_32x32x32_bf16(f.vh, bl, c, f.ix, 0, 0);
+    c = __builtin_amdgcn_smfmac_f32_32x32x32_bf16(f.vh, bh, c, f.ix, 0, 0);
+  };
+
+  if constexpr (WREG) {
+    // ---- weights in registers (the loop of conv_igemm.h's 8-wave tile, FORM_BREG8, on the sparse operands).  B never touches LDS: a
+    // wave takes a k-step's fragments of its 64 columns with eight coalesced 16 B loads — NJ x [hi|lo] x part 0 / 1, lanes 0-31 at
+    // col * 16 of a plane and lanes 32-63 two planes further: the packed layout as it is.  A step runs column-outer (column
+    // fragment 0 against the MI row blocks, then fragment 1), the fragments live in a ring of three register sets (one and a
+    // half steps: two whole steps next to 128 accumulators and the A set do not fit 256 registers), and a set is refilled right
+    // behind its last use with the fragment three further on: a load has a whole step to land, waited for by a counted vmcnt.  The A
+    // fragments of the step (one register set) are re-read row block by row block for step s + 1 behind the second smfmac triple
+    // that consumed them.  A in LDS: two buffers of a whole 16-channel chunk (both sets), the next chunk arriving by CSLOTS DMA
+    // pieces per wave fired in the steps 0 .. 3, so the only workgroup barrier is the hand-over at the top of step 5,
+    // once per chunk, after 6 x 6 MI smfmacs per wave.  A chunk's six steps are ONE basic block: prefetches past the last step are
+    // clamped, the pieces of a chunk past the end write zeros — nothing is branched around, so hipcc counts every wait.  Per
+    // accumulator the chain of smfmacs is the one of the LDS-stage loop below: bit-identical results.
+    struct BW { u32x4 h[2], l[2]; };                        // one column fragment of a k-step: [part]
+    BW bq[3];                                                // ring: column fragment f = 2 step + j of the chunk lies in slot f % 3
+    static_assert(NJ == 2, "two column fragments per step: a chunk is twelve, a multiple of the ring");
+    const int bvo = (ncol0 + wn * (NJ * 32) + l31) * 16 + half * (2 * 4096);   // (planes of the packed 256-column tile: 4 KB)
+    auto load_bw = [&](BW& b, int chunk, int f) {           // f may run past the chunk's twelve
+      int st = bsrc(chunk + f / 12, (f % 12) >> 1);
+      st = st < nsteps2 ? st : nsteps2 - 1;                  // (past the end: a clamped re-load)
+      const int so = st * SP_BPACK, vo = bvo + (f & 1) * 512;
+#pragma unroll
+      for (int part = 0; part < 2; ++part) {
+        b.h[part] = __builtin_amdgcn_raw_buffer_load_b128(rsB, vo, so + part * 4096, 0);
+        b.l[part] = __builtin_amdgcn_raw_buffer_load_b128(rsB, vo, so + (4 + part) * 4096, 0);
+      }
+    };
+    auto whole = [](u32x4 p0, u32x4 p1) -> bf16x16 {
+      return __builtin_shufflevector(__builtin_bit_cast(bf16x8, p0), __builtin_bit_cast(bf16x8, p1), 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12,
+                                     13, 14, 15);
+    };
+#pragma unroll
+    for (int f = 0; f < 3; ++f) load_bw(bq[f], 0, f);
+    AF aq[MI];
+    AR raw;
+#pragma unroll
+    for (int i = 0; i < MI; ++i) aq[i] = read_a(i, As, 0);
+    for (int chunk = 0; chunk < nchunks; ++chunk) {
+      const unsigned char* Ac = As + (chunk & 1) * CBUF;
+      const unsigned char* An = As + ((chunk & 1) ^ 1) * CBUF;
+      const bool next_chunk = chunk + 1 < nchunks;
+#pragma unroll
+      for (int s = 0; s < 6; ++s) {
+        if (s == 5) {
+          // A hand-over.  Loads complete in order, and this wave's last piece of chunk + 1 went out in the middle of step 3, with four
+          // fragment refills = 16 weight loads behind it: all but the 16 youngest done = every piece has landed.  lgkmcnt(0) = this
+          // wave has read its last A fragments of this chunk, so behind the barrier the buffer may be refilled.
+          // (A bare s_barrier: the fence of __syncthreads() would drain the weight loads.)
+          asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        }
+        const int ns = (s + 1) % 6;                          // the step A is re-read for
+        const unsigned char* Ax = (s == 5 ? An : Ac) + (ns / 3) * ABUF;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+          const int f = 2 * s + j;
+          BW& b = bq[f % 3];
+          const bf16x16 bh = whole(b.h[0], b.h[1]), bl = whole(b.l[0], b.l[1]);
+#pragma unroll
+          for (int i = 0; i < MI; ++i) {
+            mma3(acc[i][j], aq[i], bh, bl);
+            if (j == NJ - 1) {
+              // this row block's operand of the next step, behind the smfmacs that have just read the old one — and the VALU part
+              // (expand / pair up) of the row block before, whose LDS reads have had three smfmacs to come back
+              if (i > 0) aq[i - 1] = finish_a(raw, ns % 3);
+              raw = read_raw(i, Ax, ns % 3);
+              __builtin_amdgcn_sched_barrier(0);             // (pinned: hoisted above the smfmacs the reads would need a second register set)
+            }
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          if (j == 0 && s < 4) {                             // (here: the address math of a piece finds the fragment's registers free)
+#pragma unroll
+            for (int sl = s; sl < TL::CSLOTS; sl += 4) fire_chunk_piece(sl, chunk + 1, (chunk & 1) ^ 1, next_chunk);
+          }
+          load_bw(b, chunk, f + 3);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        aq[MI - 1] = finish_a(raw, ns % 3);
+      }
+    }
+    __syncthreads();                                       // the epilogue's C slab lies over the A buffers
+  } else {
+  // one k-step: group grp (0 own, 1 h + d, 2 v) of the set in buffer Ab against the B fragments b
+  auto kstep = [&](const unsigned char* Ab, int grp, const BF& b) {
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
-      bf16x8 vh, vl;
-      int ix;
-      if (grp == 1) {
-        const int oh = e_h[i], od = e_d[i];
-        vh = pairup(ld8(Ah + oh), ld8(Ah + od));
-        vl = pairup(ld8(Al + oh), ld8(Al + od));
-        ix = (int)(ld2(Ai + oh + 2) | ld2(Ai + od + 4));
-      } else {
-        const int oo = grp == 0 ? e_own[i] : e_v[i];
-        vh = expand(ld8(Ah + oo));
-        vl = expand(ld8(Al + oo));
-        ix = (int)ld2(Ai + oo + (grp == 0 ? 0 : 6));
-      }
+      const AF f = read_a(i, Ab, grp);
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        acc[i][j] = __builtin_amdgcn_smfmac_f32_32x32x32_bf16(vl, b.h[j], acc[i][j], ix, 0, 0);     // small terms first
-        acc[i][j] = __builtin_amdgcn_smfmac_f32_32x32x32_bf16(vh, b.l[j], acc[i][j], ix, 0, 0);
-        acc[i][j] = __builtin_amdgcn_smfmac_f32_32x32x32_bf16(vh, b.h[j], acc[i][j], ix, 0, 0);
-      }
+      for (int j = 0; j < NJ; ++j) mma3(acc[i][j], f, b.h[j], b.l[j]);
     }
   };
 
@@ -435,6 +595,7 @@ __global__ __launch_bounds__(TL::NT, 2) void conv_sparse_kernel(SparseArgs a) {
       // (A bare s_barrier: __syncthreads() adds hipcc's workgroup fence.)
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
+  }
   }
 
   // ---- epilogue: out = acc x gate at the class-q pixel of every window, 64 rows of the tile at a time through LDS
@@ -536,12 +697,12 @@ inline bool conv_sparse_small_grid(int NB, int Hp, int Wp, int N) {
   return sw().conv_small != 0 && conv_sparse_large_blocks(NB, Hp, Wp, N) <= CONV_SPARSE_SMALL_BLOCKS;
 }
 
-template <class TL>
+template <class TL, bool WREG>
 inline hipError_t conv_sparse_launch_tile(SparseArgs a, hipStream_t st) {
   a.cols_t = (a.Wp + SP_TW - 1) / SP_TW;
   a.n_tiles = a.N / TL::BN;
   a.m_tiles = ((a.NB * a.Hp + TL::TH - 1) / TL::TH) * a.cols_t;
-  hipLaunchKernelGGL(conv_sparse_kernel<TL>, dim3(4 * a.m_tiles * a.n_tiles), dim3(TL::NT), 0, st, a);
+  hipLaunchKernelGGL((conv_sparse_kernel<TL, WREG>), dim3(4 * a.m_tiles * a.n_tiles), dim3(TL::NT), 0, st, a);
   return hipGetLastError();
 }
 
@@ -550,7 +711,8 @@ inline hipError_t conv_sparse_launch(SparseArgs a, hipStream_t st) {
   if (a.NB <= 0) return hipSuccess;
   // (diag bits 1 / 2, measurement only: the large / the small form whatever the grid)
   const bool small = (a.diag & 4) ? true : (a.diag & 2) ? false : conv_sparse_small_grid(a.NB, a.Hp, a.Wp, a.N);
-  return small ? conv_sparse_launch_tile<SparseTileSmall>(a, st) : conv_sparse_launch_tile<SparseTileLarge>(a, st);
+  if (small) return conv_sparse_launch_tile<SparseTileSmall, false>(a, st);
+  return sw().conv_sparse_wreg ? conv_sparse_launch_tile<SparseTileLarge, true>(a, st) : conv_sparse_launch_tile<SparseTileLarge, false>(a, st);
 }
 
 }  // namespace lrp
