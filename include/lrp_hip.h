@@ -270,6 +270,23 @@ int lrp_set_precision(lrp_handle* h, int32_t mode);
  * LRP_PREC_F16X2 mode (LRP_ERR_STATE from explain calls until lrp_encode_images ran again). */
 int lrp_set_fast_layers(lrp_handle* h, int64_t mask);
 
+/* ABI v10 (added without a version bump: purely additive).  The conv rule of the VGG-style encoder's LRP walk: AlphaBetaRule (relevance_rule.py:216-322, bias = True) with
+ * alpha >= 1, beta >= 0, alpha - beta == 1 (relevance_based/utils.py:72-129; anything else LRP_ERR_INVALID).  The two floats are
+ * the caller's numbers rounded one by one, so the difference is checked to that rounding (|alpha - beta - 1| <= 6e-8 (alpha + beta):
+ * (1.3f, 0.3f) is accepted, (2, 0.5) is not) and the walk uses beta = alpha - 1 in float.  Default (1, 0):
+ * LRPSequentialPresetA / LRPAlpha1Beta0, the walk every handle has always run — that path is unchanged to the bit.
+ * beta > 0 (LRPAlpha2Beta1 / LRPSequentialPresetB at (2, 1)): R_in = alpha act - beta inh with a second denominator
+ * Z_inh = conv(x+, w-) + conv(x-, w+) + b per layer.  lrp_encode_images then also computes the inhibitor gates (one more
+ * denominator conv per layer, in the handle's arithmetic: exact fp32 or three-term split-bf16), and the walk carries two
+ * relevance chains through ONE GEMM per layer over the concatenated matrix [alpha w+ ; -beta w-] with a dual-gate epilogue
+ * (DESIGN.md 4.15).  Max-pools route by gradient as before.  Followed by lrp_cnn_explain, lrp_explain_tokens,
+ * lrp_cnn_walk(LRP_WALK_LRP) and everything built on them; the gradient walks ignore it.
+ * A CHANGE drops the encode caches like lrp_set_precision: explain calls return LRP_ERR_STATE until lrp_encode_images ran
+ * again.  The first beta > 0 allocates the second gates, the two-chain buffers, the kept layer inputs and the packed matrices
+ * (counted in lrp_workspace_bytes; idle again at beta = 0); a handle that never sets a beta > 0 allocates nothing.
+ * LRP_ERR_UNSUPPORTED: beta > 0 on a ResNet handle; and from the explain calls with beta > 0 in LRP_PREC_F16X2. */
+int lrp_set_cnn_rule(lrp_handle* h, float alpha, float beta);
+
 /* Dominant-kernel timing for bench.py's roofline block: when enabled, HIP
  * events bracket every conv-LRP launch on the caller's stream; query returns
  * launches and summed milliseconds since the last reset (syncs the events). */
@@ -297,6 +314,16 @@ enum { LRP_CONV_SPLIT_BF16 = 0x100, LRP_CONV_WREG = 0x200 };
 int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias_host,
                 const float* aux_dev, float* out_dev, int32_t NB, int32_t H, int32_t W,
                 int32_t Cin, int32_t Cout, int32_t taps, int32_t mode, void* stream);
+
+/* ABI v10 (added without a version bump: purely additive).  Operator-level entry of the two-chain launch of the alpha-beta walk (lrp_set_cnn_rule, beta > 0), all tensors plain
+ * fp32 NHWC:  c = convT(sp, alpha w+) + convT(sn, -beta w-)  (3x3 'same', ONE GEMM with K = 2 x 9 x Cout),
+ *   outp = c x gp,  outn = c x gn       with c repeated 2 x 2 (nearest) when pool != 0.
+ * sp_dev, sn_dev (NB, H, W, Cout); w_hwio_host (3, 3, Cin, Cout); gp_dev, gn_dev, outp_dev, outn_dev (NB, H u, W u, Cin), u = 2
+ * with pool.  split != 0: on the split-bf16 path (channels % 8 == 0), fp32 otherwise (channels % 4 == 0).  The launch takes the
+ * form lrp_conv_plan answers for LRP_PLAN_DUAL_MUL with Cin(plan) = 2 Cout, N(plan) = Cin. */
+int lrp_op_conv_ab(const float* sp_dev, const float* sn_dev, const float* w_hwio_host, float alpha, float beta, const float* gp_dev,
+                   const float* gn_dev, float* outp_dev, float* outn_dev, int32_t NB, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                   int32_t pool, int32_t split, void* stream);
 
 /* ABI v6.  The conv-LRP launch BEHIND a 2x2 max-pool (AlphaBetaRule RR:274-322 for a conv whose output feeds MaxPooling2D: the
  * relevance arrives through the pool's gradient routing, RA:470-480 -> IL:138-157, i.e. one non-zero per window and channel)
@@ -532,6 +559,10 @@ int lrp_reload_switches(void);
  * weights from registers (one workgroup barrier per channel chunk) — with LRP_PLAN_FRAG and N % 128 == 0, for the dense split-bf16
  * LRP_EPI_MUL launch (no JOIN, no request) and the interleaved fp16-pair LRP_EPI_FWD_DUAL (terms 7 | 23; POOL_GC gives the _POOL
  * form).  LRP_CONV_BREG4=0 gives the pipelined forms back.
+ * LRP_PLAN_DUAL_MUL (added later in ABI v10): the dual-gate epilogue of the alpha-beta walk (two gates on one accumulator, two outputs; Cin counts both
+ * chains).  LRP_EPI_MUL / LRP_EPI_MUL_UP2 with LRP_OPND_FP32 or LRP_OPND_BF16X3 on LRP_FORM_PLAIN, LRP_FORM_SMALL and the 128 x 128
+ * LRP_FORM_HALO; never the 8-wave tile or a weights-in-registers form; refused with FRAG, JOIN, GMASK, any request, LRP_OPND_F16X2,
+ * or chains that are not whole 16 B (fp32) / 32 B (split) groups.
  * The reference has no counterpart. */
 enum { LRP_EPI_BIAS_RELU = 0, LRP_EPI_BIAS = 1, LRP_EPI_MUL = 2, LRP_EPI_MUL_UP2 = 3, LRP_EPI_FWD_DUAL = 4, LRP_EPI_STORE = 5,
        LRP_EPI_IMG_STENCIL = 6 };
@@ -539,7 +570,7 @@ enum { LRP_OPND_FP32 = 0, LRP_OPND_BF16X3 = 1, LRP_OPND_F16X2 = 2 };
 enum { LRP_FORM_PLAIN = 0, LRP_FORM_SMALL = 1, LRP_FORM_HALO = 2, LRP_FORM_BREG = 3, LRP_FORM_POOL = 4, LRP_FORM_IMG = 5, LRP_FORM_BREG8 = 6,
        LRP_FORM_BREG4 = 7, LRP_FORM_BREG4_POOL = 8 };
 enum { LRP_PLAN_FRAG = 1, LRP_PLAN_JOIN = 2, LRP_PLAN_DUAL_IL = 4, LRP_PLAN_GMASK = 8,
-       LRP_PLAN_UP2_SRC = 16, LRP_PLAN_IMG_PART = 32, LRP_PLAN_POOL_GC = 64 };
+       LRP_PLAN_UP2_SRC = 16, LRP_PLAN_IMG_PART = 32, LRP_PLAN_POOL_GC = 64, LRP_PLAN_DUAL_MUL = 128 };
 int lrp_conv_plan(int32_t epi, int32_t prec, int32_t terms, int32_t NB, int32_t H, int32_t W, int32_t N, int32_t Cin, int32_t taps,
                   int32_t split, uint32_t flags, int32_t* out11);
 

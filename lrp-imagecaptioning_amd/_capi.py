@@ -21,6 +21,7 @@ LRP_OPND_FP32, LRP_OPND_BF16X3, LRP_OPND_F16X2 = 0, 1, 2
 LRP_FORM_PLAIN, LRP_FORM_SMALL, LRP_FORM_HALO, LRP_FORM_BREG, LRP_FORM_POOL, LRP_FORM_IMG, LRP_FORM_BREG8 = range(7)
 LRP_FORM_BREG4, LRP_FORM_BREG4_POOL = 7, 8
 LRP_PLAN_FRAG, LRP_PLAN_JOIN, LRP_PLAN_DUAL_IL, LRP_PLAN_GMASK, LRP_PLAN_UP2_SRC, LRP_PLAN_IMG_PART, LRP_PLAN_POOL_GC = 1, 2, 4, 8, 16, 32, 64
+LRP_PLAN_DUAL_MUL = 128
 
 
 class LrpConfig(C.Structure):
@@ -54,6 +55,7 @@ SYMBOLS = {
     "lrp_explain_tokens": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, _P, _P, _P, _P, _P]),
     "lrp_set_precision": (C.c_int, [_P, C.c_int32]),
     "lrp_set_fast_layers": (C.c_int, [_P, C.c_int64]),
+    "lrp_set_cnn_rule": (C.c_int, [_P, C.c_float, C.c_float]),
     "lrp_profile_enable": (C.c_int, [_P, C.c_int32]),
     "lrp_profile_query": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "lrp_profile_records": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
@@ -81,6 +83,7 @@ SYMBOLS = {
     "lrp_train_forward": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "lrp_train_drop_forward": (C.c_int, [_P, _P]),
     "lrp_reload_switches": (C.c_int, []),
+    "lrp_op_conv_ab": (C.c_int, [_P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P] + [C.c_int32] * 7 + [_P]),
     "lrp_op_conv_pool_sparse": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "lrp_train_apply": (C.c_int, [_P, _P, _P]),
     "lrp_train_get_master": (C.c_int, [_P, _P, _P]),

@@ -88,6 +88,67 @@ class LRPSequentialPresetA(object):
         return self._impl.analyze(X)
 
 
+def infer_alpha_beta(alpha, beta, caller):
+    """(alpha, beta) of an alpha-beta rule under the reference's conditions (relevance_based/utils.py:72-129): alpha >= 1,
+    beta >= 0, alpha - beta == 1; either one may be None and follows from the other.  `caller`: the class name the reference
+    puts in front of its message.  The messages are the reference's."""
+    head = "Constructor call to {} : ".format(caller)
+    if alpha is None and beta is None:
+        raise ValueError(head + "Neither alpha or beta were given")
+    if alpha is not None and alpha < 1:
+        raise ValueError(head + "Passed parameter alpha invalid. Expecting alpha >= 1 but was {}".format(alpha))
+    if beta is not None and beta < 0:
+        raise ValueError(head + "Passed parameter beta invalid. Expecting beta >= 0 but was {}".format(beta))
+    if alpha is None:
+        alpha = beta + 1
+        if alpha < 1:
+            raise ValueError(head + "Inferring alpha from given beta {} s.t. alpha - beta = 1, with condition alpha >= 1 not possible.".format(beta))
+    if beta is None:
+        beta = alpha - 1
+        if beta < 0:
+            raise ValueError(head + "Inferring beta from given alpha {} s.t. alpha - beta = 1, with condition beta >= 0 not possible.".format(alpha))
+    if alpha - beta != 1:
+        raise ValueError(head + "Condition alpha - beta = 1 not fulfilled. alpha={} ; beta={} -> alpha - beta = {}".format(alpha, beta, alpha - beta))
+    return alpha, beta
+
+
+class LRPAlphaBeta(LRPSequentialPresetA):
+    """relevance_analyzer.py:578-620: every conv under AlphaBetaRule(alpha, beta, bias=True) (relevance_rule.py:216-322), max-pools
+    by gradient routing — the same `analyze([X, R])` surface as LRPSequentialPresetA, on the engine's walk under
+    lrp_set_cnn_rule(alpha, beta).  (1, 0) is LRPSequentialPresetA's walk to the bit; beta > 0 runs the two-chain walk
+    (VGG-style encoders).  The IgnoreBias variants (bias=False) are not built."""
+
+    def __init__(self, model, alpha=None, beta=None, bias=True, neuron_selection_mode="replace", **kwargs):
+        alpha, beta = infer_alpha_beta(alpha, beta, self.__class__.__name__)
+        if not bias:
+            raise NotImplementedError("the IgnoreBias variants (bias=False) are not built")
+        self._alpha, self._beta, self._bias = alpha, beta, bias
+        super(LRPAlphaBeta, self).__init__(model, neuron_selection_mode=neuron_selection_mode, **kwargs)
+        self._engine.set_cnn_rule(alpha, beta)
+
+
+class LRPAlpha2Beta1(LRPAlphaBeta):
+    """relevance_analyzer.py:635-642."""
+
+    def __init__(self, model, **kwargs):
+        super(LRPAlpha2Beta1, self).__init__(model, alpha=2, beta=1, bias=True, **kwargs)
+
+
+class LRPAlpha1Beta0(LRPAlphaBeta):
+    """relevance_analyzer.py:655-662."""
+
+    def __init__(self, model, **kwargs):
+        super(LRPAlpha1Beta0, self).__init__(model, alpha=1, beta=0, bias=True, **kwargs)
+
+
+class LRPSequentialPresetB(LRPAlphaBeta):
+    """relevance_analyzer.py:724-748: Dense -> EpsilonRule(epsilon), Conv -> Alpha2Beta1Rule.  The truncated encoders have no
+    Dense layer, so epsilon is validated and stored as LRPSequentialPresetA does."""
+
+    def __init__(self, model, epsilon=0.1, **kwargs):
+        super(LRPSequentialPresetB, self).__init__(model, alpha=2, beta=1, bias=True, epsilon=epsilon, **kwargs)
+
+
 def _check_selection_mode(neuron_selection_mode):
     if neuron_selection_mode not in ["max_activation", "index", "all", "replace"]:
         raise ValueError("neuron_selection parameter is not valid.")             # base.py:332-333

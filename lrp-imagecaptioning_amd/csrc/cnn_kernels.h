@@ -542,6 +542,106 @@ __global__ __launch_bounds__(256) void top_divide_split_kernel(const float* __re
   }
 }
 
+// ---- alpha-beta LRP with beta > 0 (RR:274-322, Encoder::explain_ab): the operands of the two-chain walk ----
+// Packers, HWIO kernel w[tap][ci][co] in HBM -> B operands of conv_igemm.h, zero padded (the buffers were zeroed at allocation:
+// only rows < the layer's own are written, every k of them).
+//   mode 0: forward [Cout rows][9 * CP], CP = cinp(Cin): w- — the inhibitor denominator conv Z_inh = conv(x+, w-) + b
+//   mode 1: backward [Cin rows][9 * CP], CP = cinp(2 Cout), taps flipped: k = tap' * CP + c, c < Cout: alpha w+[co = c],
+//           Cout <= c < 2 Cout: -beta w-[co = c - Cout] — both chains' transposed conv as ONE GEMM over [S+ | S-]
+__global__ __launch_bounds__(256) void pack_conv_ab_dev_kernel(const float* __restrict__ w, float* __restrict__ dst, int mode, int Cin,
+                                                               int Cout, int CP, int rows, float alpha, float beta) {
+  const int K = 9 * CP;
+  const size_t total = (size_t)rows * K;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int row = (int)(i / K), k = (int)(i % K), t = k / CP, c = k % CP;
+    float v = 0.f;
+    if (mode == 0) {
+      if (c < Cin) { const float x = w[((size_t)t * Cin + c) * Cout + row]; v = x < 0.f ? x : 0.f; }
+    } else if (c < Cout) {
+      const float x = w[((size_t)(8 - t) * Cin + row) * Cout + c];
+      v = x >= 0.f ? alpha * x : 0.f;
+    } else if (c < 2 * Cout) {
+      const float x = w[((size_t)(8 - t) * Cin + row) * Cout + c - Cout];
+      v = x < 0.f ? -beta * x : 0.f;
+    }
+    dst[i] = v;
+  }
+}
+// The image layer's: w (3,3,3,cout) ->
+//   fwd_n [cout][64]   w- | w+ against the im2col row (x+ patch | x- patch): Z_inh,1 = conv(x+, w-) + conv(x-, w+) (+ b in the epilogue)
+//   bwd   [54][Kb2]    Kb2 = cinp(2 cout), k = [S+ channels | S- channels]:
+//                      row t*6+c   (times x+): alpha w+ | -beta w-      row t*6+3+c (times x-): alpha w- | -beta w+
+__global__ __launch_bounds__(256) void pack_image_layer_ab_dev_kernel(const float* __restrict__ w, float* __restrict__ fwd_n,
+                                                                      float* __restrict__ bwd, int cout, int Kb2, float alpha, float beta) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 27 * cout) return;
+  const int k = i / cout, co = i - k * cout, t = k / 3, c = k - 3 * t;
+  const float v = w[i], vp = v >= 0.f ? v : 0.f, vn = v < 0.f ? v : 0.f;
+  fwd_n[(size_t)co * 64 + k] = vn;
+  fwd_n[(size_t)co * 64 + 32 + k] = vp;
+  bwd[(size_t)(t * 6 + c) * Kb2 + co] = alpha * vp;
+  bwd[(size_t)(t * 6 + c) * Kb2 + cout + co] = -beta * vn;
+  bwd[(size_t)(t * 6 + 3 + c) * Kb2 + co] = alpha * vn;
+  bwd[(size_t)(t * 6 + 3 + c) * Kb2 + cout + co] = -beta * vp;
+}
+// Two tensors [pixels][C] -> the walk's two-chain form [pixels][S+ (C) | S- (C)], fp32 or split8 (G = 4 / 8 channels per thread).
+// Z == nullptr: a plain join (the operator entry).  Otherwise the head of the walk (KG:898-900 per chain):
+//   S+ = R / safe(Z_act,top[img]),  S- = R / safe(Z_inh,top[img])      (sp = sn = R; per = pixels per map)
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void chain_join_kernel(const float* __restrict__ sp, const float* __restrict__ sn, const float* __restrict__ za,
+                                                         const float* __restrict__ zi, const int* __restrict__ row2img,
+                                                         float* __restrict__ dst, size_t pixels, int per, int C) {
+  constexpr int G = SPLIT ? 8 : 4;
+  const int cg = C / G;
+  const size_t total = pixels * cg;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t pix = i / cg;
+    const int e = (int)(i - pix * cg) * G;
+    float a[G], b[G];
+#pragma unroll
+    for (int q = 0; q < G; q += 4) {
+      *reinterpret_cast<f32x4*>(a + q) = *reinterpret_cast<const f32x4*>(sp + pix * C + e + q);
+      *reinterpret_cast<f32x4*>(b + q) = *reinterpret_cast<const f32x4*>(sn + pix * C + e + q);
+    }
+    if (za) {
+      const int t = (int)(pix / per);
+      const int img = row2img ? row2img[t] : t;
+      const size_t zo = ((size_t)img * per + (pix - (size_t)t * per)) * C + e;
+#pragma unroll
+      for (int q = 0; q < G; ++q) { a[q] = a[q] / safe_den(za[zo + q]); b[q] = b[q] / safe_den(zi[zo + q]); }
+    }
+    float* d = dst + pix * 2 * C + e;
+    if constexpr (SPLIT) {
+      split8_store(a, d);
+      split8_store(b, d + C);
+    } else {
+      *reinterpret_cast<f32x4*>(d) = *reinterpret_cast<const f32x4*>(a);
+      *reinterpret_cast<f32x4*>(d + C) = *reinterpret_cast<const f32x4*>(b);
+    }
+  }
+}
+// Inhibitor gate of a pooled layer at full resolution: the arg-max mask is the activator gate's (G+ != 0 exactly where the
+// window's first maximum sits and is positive; a zero maximum gates to zero in both), the value the pooled activation:
+//   G- = [G+ != 0] * pool(a)[window] / safe(Z_inh)
+__global__ __launch_bounds__(256) void pool_gate_inh_kernel(const f32x4* __restrict__ gp, const float* __restrict__ pooled,
+                                                            const f32x4* __restrict__ zinh, f32x4* __restrict__ gn, int NB, int H, int W, int C) {
+  const int C4 = C >> 2;
+  const size_t total = (size_t)NB * H * W * C4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int c4 = (int)(i % C4);
+    size_t r = i / C4;
+    const int w = (int)(r % W);
+    r /= W;
+    const int h = (int)(r % H), n = (int)(r / H);
+    const f32x4 g = gp[i], z = zinh[i];
+    const f32x4 pv = *reinterpret_cast<const f32x4*>(pooled + ((((size_t)n * (H >> 1) + (h >> 1)) * (W >> 1) + (w >> 1)) * C) + 4 * c4);
+    f32x4 o;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) o[c] = g[c] != 0.f ? pv[c] / safe_den(z[c]) : 0.f;
+    gn[i] = o;
+  }
+}
+
 // Image layer of the reverse walk (RR:306-312 with both sign branches live):
 //   R_img[p][c] = x+[p][c] * convT(S_1, w+)[p][c] + x-[p][c] * convT(S_1, w-)[p][c]
 // computed as a channel reduction FIRST (one K = C_1 GEMM on the MFMA kernel):

@@ -4,6 +4,8 @@
 //     chain (EPI_BIAS_RELU) and denominators Z+ (EPI_BIAS) in split-bf16 (TERMS 7)          — per image, cached
 //   * conv-LRP alpha1beta0 backward (EPI_MUL / EPI_MUL_UP2 / EPI_IMG_STENCIL)              — per token
 //     RR:274-322 restructured: S_{l-1} = up2?(convT(S_l, w_l+)) * G_{l-1}
+//     alpha-beta with beta > 0: both chains [S+ | S-] through one GEMM against [alpha w+ ; -beta w-], two gates on one
+//     accumulator (template DG, ConvArgs::aux_b)                                          — per token, lrp_set_cnn_rule
 //   * every dense product of the decoder LRP / gradient paths (taps = 1, EPI_STORE / EPI_MUL)
 // Template axes: tile (WM, WN, TM, TN), epilogue EPI, operand arithmetic PREC (exact fp32 MFMA | split-bf16),
 // HALO (3x3: A tile + halo resident in LDS for all 9 taps), BREG (weights in registers, no barrier per tap: N <= 64, and the 8-wave tile),
@@ -240,6 +242,15 @@ struct ConvArgs {
   float* pool_gc;
   unsigned char* pool_pos;
   float* pool_x;
+  // Dual-gate MUL epilogues (template DG; alpha-beta LRP with beta > 0, Encoder::explain_ab): the two relevance chains
+  // S+ = R / safe(Z_act) and S- = R / safe(Z_inh) travel as ONE tensor, channels [S+ (C) | S- (C)] per pixel, so that the
+  // launch against the concatenated matrix [alpha w+ ; -beta w-] (K = taps x 2C) is the ordinary implicit GEMM with
+  // Cin = 2C and its accumulator c = convT(S+, alpha w+) + convT(S-, -beta w-) is shared by both chains:
+  //   out = c x aux[img],  out_b = c x aux_b[img]      (aux = G+ = a / safe(Z_act), aux_b = G- = a / safe(Z_inh): N wide each)
+  // out / out_b have ostride floats per pixel (2N with out_b = out + N: the next launch's input; N for two plain tensors).
+  const float* aux_b;
+  float* out_b;
+  int ostride;
 };
 constexpr int ACT_MAX_SLOTS = 64;
 
@@ -285,8 +296,10 @@ constexpr int conv_halo_rows(int BM) { return BM == 256 ? 352 : 192; }   // x 12
 // PW (the 128 x 128 weights-in-registers loop only): the launch reads the compact pool interface (ConvArgs::up2_src).  The
 // pipelined kernels decide that at run time; in the unrolled chunk of this loop the loader's registers would be carried through the
 // dense launch's loop as well, and every reuse of one of them waited for the weight loads in flight [ISA: vmcnt(1) three times a chunk].
+// DG (EPI_MUL / EPI_MUL_UP2, PREC_FP32 and PREC_BF16X3, staged and pipelined resident-image tiles): the dual-gate epilogue
+// (ConvArgs::aux_b).  An axis of its own for GMASK's reason: the single-gate instantiations compile to what they were.
 template <int WM, int WN, int TM, int TN, int EPI, int PREC, bool HALO = false, bool BREG = false, int TERMS = 7, int NS = 2,
-          bool GMASK = false, bool PW = false>
+          bool GMASK = false, bool PW = false, bool DG = false>
 __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 : NS > 2 ? 2 : conv_min_waves(WM * WN, TM, TN, HALO)) void conv_igemm_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (the buffer-resource builtins are device-only)
   constexpr int NW = WM * WN, NT = 64 * NW;           // waves / threads per block (4 or 8 waves)
@@ -304,6 +317,8 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
   static_assert(!BREG4 || (TM == 2 && ((PREC == PREC_BF16X3 && EPI == EPI_MUL && TERMS == 7) || (PREC == PREC_F16X2 && EPI == EPI_FWD_DUAL && (TERMS == 7 || TERMS == 23)))),
                 "two uses: the dense split-bf16 walk and the interleaved fp16-pair dual forward");
   static_assert(!PW || (BREG4 && PREC == PREC_BF16X3), "PW: the split-bf16 walk on the 128 x 128 weights-in-registers loop");
+  static_assert(!DG || ((EPI == EPI_MUL || EPI == EPI_MUL_UP2) && PREC != PREC_F16X2 && !BREG && !GMASK && !PW && TERMS == 7 && WM * WN == 4),
+                "dual gate: the MUL epilogues of the 4-wave staged / pipelined tiles, exact fp32 or split-bf16");
   static_assert((BM / 8) % NW == 0 && (BN / 8) % NW == 0, "pieces must divide over the waves");
   static_assert(!HALO || EPI != EPI_STORE, "the image layer is a 1-tap GEMM");
   static_assert(NS == 2 || (NS > 2 && !HALO && !BREG), "deeper staging exists for the plain (non-resident) A path only");
@@ -1655,6 +1670,78 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
         // gate rows one pass AHEAD of the arithmetic (written as explicit phases — left as load/multiply/store per
         // pass, the possible aliasing of `out` and `aux` made hipcc serialise a full memory round trip per pass, which
         // the short K = 576 layers could not hide).
+        if constexpr (DG) {
+          // ---- dual gate (ConvArgs::aux_b): one accumulator, two gates, two outputs.  The fast form below with a second gate
+          // row per pass; the ring is shorter (two gate sets per entry).
+          if (col < a.N) {
+            constexpr int NPd = RH / RPP;
+            constexpr int UPd = EPI == EPI_MUL_UP2 ? 4 : 1;
+            constexpr int RINGd = UPd == 1 ? (2 < NPd ? 2 : NPd) : 1;
+            const int W2d = 2 * a.W, H2d = 2 * a.H;
+            int imgd[NPd];
+#pragma unroll
+            for (int ps = 0; ps < NPd; ++ps) {
+              int row, n_, h_, w_;
+              if (!locate(hf * RH + rin + ps * RPP, row, n_, h_, w_)) n_ = 0;
+              imgd[ps] = a.row2img ? a.row2img[n_] : n_;
+            }
+            f32x4 gd[RINGd][UPd][2][CW / 4];
+            auto issue = [&](int ps) {
+              int row, n_, h_, w_;
+              if (!locate(hf * RH + rin + ps * RPP, row, n_, h_, w_)) { h_ = 0; w_ = 0; }
+#pragma unroll
+              for (int q = 0; q < UPd; ++q) {
+                const size_t go = EPI == EPI_MUL ? ((size_t)imgd[ps] * HW + h_ * a.W + w_) * a.N + col
+                                                 : (((size_t)imgd[ps] * H2d + 2 * h_ + (q >> 1)) * W2d + 2 * w_ + (q & 1)) * a.N + col;
+#pragma unroll
+                for (int q4 = 0; q4 < CW / 4; ++q4) {
+                  gd[ps % RINGd][q][0][q4] = *reinterpret_cast<const f32x4*>(a.aux + go + 4 * q4);
+                  gd[ps % RINGd][q][1][q4] = *reinterpret_cast<const f32x4*>(a.aux_b + go + 4 * q4);
+                }
+              }
+            };
+#pragma unroll
+            for (int ps = 0; ps < RINGd - 1; ++ps) issue(ps);
+            const bool plain = SPLIT_OUT && a.out_plain;
+#pragma unroll
+            for (int ps = 0; ps < NPd; ++ps) {
+              if (ps + RINGd - 1 < NPd) issue(ps + RINGd - 1);
+              int row, n_, h_, w_;
+              if (locate(hf * RH + rin + ps * RPP, row, n_, h_, w_)) {
+                const int ll = rin + ps * RPP;
+                float v[CW];
+#pragma unroll
+                for (int q4 = 0; q4 < CW / 4; ++q4)
+                  *reinterpret_cast<f32x4*>(v + 4 * q4) = *reinterpret_cast<const f32x4*>(Cs + ll * BN + c4 * CW + 4 * q4);
+#pragma unroll
+                for (int q = 0; q < UPd; ++q) {
+                  const size_t po = EPI == EPI_MUL ? (size_t)row * a.ostride + col
+                                                   : (((size_t)n_ * H2d + 2 * h_ + (q >> 1)) * W2d + 2 * w_ + (q & 1)) * a.ostride + col;
+#pragma unroll
+                  for (int b = 0; b < 2; ++b) {
+                    float r[CW];
+#pragma unroll
+                    for (int q4 = 0; q4 < CW / 4; ++q4)
+#pragma unroll
+                      for (int e = 0; e < 4; ++e) r[4 * q4 + e] = v[4 * q4 + e] * gd[ps % RINGd][q][b][q4][e];
+                    float* dst = (b ? a.out_b : a.out) + po;
+                    if constexpr (SPLIT_OUT) {
+                      if (plain) {
+                        *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(r);
+                        *reinterpret_cast<f32x4*>(dst + 4) = *reinterpret_cast<const f32x4*>(r + 4);
+                      } else {
+                        split8_store(r, dst);
+                      }
+                    } else {
+                      *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(r);
+                    }
+                  }
+                }
+              }
+            }
+          }
+          continue;                                     // next slab
+        } else
         if (col < a.N) {
           // ---- the walk's common case (plain gate, no residual join, no second head, no gradient-walk switches): the same
           // arithmetic with nothing to decide inside the passes.  In the general form below every runtime switch sits next to
@@ -1942,6 +2029,7 @@ struct ConvAsk {
   bool dual_il = false;
   int split = 0;
   bool up2_src = false, img_part = false, pool_gc = false;
+  bool dual_mul = false;     // the dual-gate MUL epilogue (ConvArgs::aux_b; Cin = both chains)
 };
 struct ConvPlan {
   bool ok;                   // false: conv_launch refuses this launch (hipErrorInvalidValue)
@@ -1996,6 +2084,13 @@ inline ConvPlan conv_plan(const ConvAsk& q, const Switches& s = sw()) {
   if (prec == PREC_F16X2 && (q.terms == 23 ? !(epi == EPI_FWD_DUAL && q.dual_il) : q.terms == 5 ? !mul : epi == EPI_STORE)) return refused;
   if (q.gmask && (epi != EPI_MUL || prec != PREC_FP32 || asked)) return refused;         // byte-mask gates: exact fp32 EPI_MUL only
   if (prec != PREC_FP32 && (q.Cin & 7)) return refused;
+  // dual gate (alpha-beta LRP, beta > 0): the dense 3x3 / 1x1 MUL epilogues in exact fp32 and split-bf16, on the staged tiles
+  // (FORM_PLAIN 128 x 128 / 128 x 64 / 128 x 32, FORM_SMALL) and the pipelined 128 x 128 resident-image tile (FORM_HALO).
+  // Not built: the 8-wave tile, the weights-in-registers forms (a fragment-major copy of the concatenated matrix is refused, not
+  // ignored), the compact pool interface, the folded image layer, a residual join, byte-mask gates, fp16 pairs.  Each chain
+  // is half of Cin and must be made of whole 16 B (fp32) / 32 B (split8) groups.
+  if (q.dual_mul && (!mul || prec == PREC_F16X2 || q.terms != 7 || q.gmask || asked || q.frag || q.join || (q.Cin & (prec != PREC_FP32 ? 15 : 7))))
+    return refused;
   p.M = q.NB * q.H * q.W;
   p.epi_generic = s.epi_fast ? 0 : 1;
   if (epi == EPI_IMG_STENCIL) {
@@ -2021,7 +2116,7 @@ inline ConvPlan conv_plan(const ConvAsk& q, const Switches& s = sw()) {
   // per output element in the epilogue) is bound by those streams, not by staging: two 128 x 128 workgroups per CU overlap
   // one's epilogue with the other's K loop  [MI355X, ResNet-101 conv4_x: 354 -> 316 us per launch; config 4 -0.9 ms per walk]
   if (prec != PREC_FP32 && (q.terms == 7 || prec == PREC_F16X2) && !(prec == PREC_F16X2 && fwd) && q.N >= 256 && (q.N % 256) == 0 &&
-      !(epi == EPI_MUL && q.taps == 1 && q.join) && ((rows + 255) / 256) * (q.N / 256) >= 400)
+      !(epi == EPI_MUL && q.taps == 1 && q.join) && !q.dual_mul && ((rows + 255) / 256) * (q.N / 256) >= 400)
     t = {256, 256};
   p.m_tiles = (p.M + t.BM - 1) / t.BM;
   p.n_tiles = (q.N + t.BN - 1) / t.BN;
@@ -2060,7 +2155,7 @@ inline ConvPlan conv_plan(const ConvAsk& q, const Switches& s = sw()) {
   // N <= 64: resident image + weights in registers, no barrier per tap (LRP_CONV_BREG=0 disables).  128-row tiles, whatever
   // the grid: 256-row tiles, 8 waves, one block per CU, halve the weight traffic per pixel but lose more to the single block
   // per CU  [MI355X: block1_conv2 bwd 4.19 ms vs 3.83 ms with these 128-row tiles, 3 blocks per CU]
-  if (mul && mode > 0 && s.conv_breg && t.BN == 64 && q.frag && resident(false, 0.9f)) {
+  if (mul && mode > 0 && s.conv_breg && t.BN == 64 && q.frag && !q.dual_mul && resident(false, 0.9f)) {
     if (q.img_part) {                                    // image layer folded in: tiles laid out per token (none straddles two tokens)
       if (prec != PREC_BF16X3 || epi != EPI_MUL || q.N != 64) return refused;
       p.tpt = (q.H + p.th - 1) / p.th;
@@ -2098,7 +2193,7 @@ inline ConvPlan conv_plan(const ConvAsk& q, const Switches& s = sw()) {
   }
   // N = 64 tiles (TM x TN = 2 x 1 per wave) lose with the resident image: 2 instead of 3 blocks per CU and the
   // per-tap address work is spread over half as many MFMAs  [MI355X: block1_conv2 bwd 4.5 ms vs 5.2 ms]
-  if (mode > 0 && (t.BN >= 128 || (mode == 2 && t.BN >= 64)) && resident(false, 0.9f)) {
+  if (mode > 0 && (t.BN >= 128 || (mode == 2 && t.BN >= 64 && !q.dual_mul)) && resident(false, 0.9f)) {
     // the loader of the compact pool interface handles two items per thread and channel chunk
     if (q.up2_src && p.hrows * ((p.tw + 2) / 2 + 1) * 4 > 2 * (t.BM == 256 ? 512 : 256)) return refused;
     // the 8-wave tile of the dense split-bf16 walk with a fragment-major weight copy: weights in registers, one barrier per
@@ -2190,6 +2285,7 @@ inline ConvAsk conv_ask(int epi, int prec, int terms, bool gmask, const ConvArgs
   q.NB = a.NB; q.H = a.H; q.W = a.W; q.N = a.N; q.Cin = a.Cin; q.taps = a.taps;
   q.frag = a.wpk_frag != nullptr; q.join = a.join != nullptr; q.dual_il = a.dual_il != 0; q.split = a.split;
   q.up2_src = a.up2_src != nullptr; q.img_part = a.img_part != nullptr; q.pool_gc = a.pool_gc != nullptr;
+  q.dual_mul = a.out_b != nullptr;
   return q;
 }
 inline void conv_apply_plan(const ConvPlan& p, ConvArgs& a) {
@@ -2212,11 +2308,16 @@ inline hipError_t conv_launch_img(ConvArgs a, hipStream_t st) {
   return hipGetLastError();
 }
 
-template <int EPI, int PREC, int TERMS = 7, bool GMASK = false>
+template <int EPI, int PREC, int TERMS = 7, bool GMASK = false, bool DG = false>
 inline hipError_t conv_launch_epi(ConvArgs a, hipStream_t st) {
   static_assert(!GMASK || (EPI == EPI_MUL && PREC == PREC_FP32), "byte-mask gates: exact fp32 EPI_MUL only");
   constexpr bool MUL = EPI == EPI_MUL || EPI == EPI_MUL_UP2, FWD = EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_FWD_DUAL;
+  static_assert(!DG || (MUL && PREC != PREC_F16X2 && TERMS == 7 && !GMASK), "dual gate: MUL epilogues, exact fp32 or split-bf16");
   // 1. what only the pointers tell
+  if (DG != (a.out_b != nullptr)) return hipErrorInvalidValue;
+  if (DG && (!a.aux || !a.aux_b || !a.out || a.ostride < a.N || (a.ostride & (PREC != PREC_FP32 ? 7 : 3)) || a.out2s || a.gate_none ||
+             a.gate_binary || a.relu_out))
+    return hipErrorInvalidValue;
   if (GMASK && (a.out2s || a.gate_none)) return hipErrorInvalidValue;
   if (PREC == PREC_F16X2 && MUL && (!a.tok_fac || !a.tok_max_out || a.out_plain)) return hipErrorInvalidValue;
   if (PREC == PREC_F16X2 && FWD && !a.in_unscale) return hipErrorInvalidValue;
@@ -2231,6 +2332,28 @@ inline hipError_t conv_launch_epi(ConvArgs a, hipStream_t st) {
   conv_apply_plan(p, a);
   // 3. its kernel
   const dim3 grid(p.m_tiles * p.n_tiles), block(p.threads);
+  if constexpr (DG) {                                  // the forms conv_plan answers for ConvAsk::dual_mul, nothing else
+    if (p.form == FORM_HALO) {
+      if constexpr (PREC == PREC_BF16X3) {
+        if (p.BM != 128 || p.BN != 128) return hipErrorInvalidValue;
+        a.tile_map = conv_tile_order(a, st);
+        hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, true, false, 7, 2, false, false, true>), grid, block, 0, st, a);
+        return hipGetLastError();
+      }
+      return hipErrorInvalidValue;
+    }
+    if (p.form == FORM_SMALL)
+      hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 1, 1, EPI, PREC, false, false, 7, CONV_SMALL_NS, false, false, true>), grid, block, 0, st, a);
+    else if (p.form != FORM_PLAIN || p.BM != 128)
+      return hipErrorInvalidValue;
+    else if (p.BN == 128)
+      hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, false, false, 7, 2, false, false, true>), grid, block, 0, st, a);
+    else if (p.BN == 64)
+      hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 1, EPI, PREC, false, false, 7, 2, false, false, true>), grid, block, 0, st, a);
+    else
+      hipLaunchKernelGGL((conv_igemm_kernel<4, 1, 1, 1, EPI, PREC, false, false, 7, 2, false, false, true>), grid, block, 0, st, a);
+    return hipGetLastError();
+  }
   if constexpr (PREC != PREC_FP32 && (MUL || FWD)) {
     if (p.form == FORM_BREG4 || p.form == FORM_BREG4_POOL) {
       if constexpr ((EPI == EPI_MUL && PREC == PREC_BF16X3 && TERMS == 7) || (EPI == EPI_FWD_DUAL && PREC == PREC_F16X2 && (TERMS == 7 || TERMS == 23))) {
@@ -2291,6 +2414,17 @@ inline hipError_t conv_launch_epi(ConvArgs a, hipStream_t st) {
 // why is stated there, at the head of conv_plan — and hipErrorInvalidValue for everything else.
 inline hipError_t conv_launch(int epi, const ConvArgs& a, hipStream_t st, int prec = PREC_FP32, int terms = 7) {
   if (prec == PREC_BF16X3 && terms != 7) return hipErrorInvalidValue;   // (the two-pass three-way split forward product of rounds 1-2 is gone)
+  if (a.out_b) {                                       // dual gate (ConvArgs::aux_b): two epilogues x two operand formats
+    if (terms != 7) return hipErrorInvalidValue;
+    if (prec == PREC_BF16X3) {
+      if (epi == EPI_MUL) return conv_launch_epi<EPI_MUL, PREC_BF16X3, 7, false, true>(a, st);
+      if (epi == EPI_MUL_UP2) return conv_launch_epi<EPI_MUL_UP2, PREC_BF16X3, 7, false, true>(a, st);
+    } else if (prec == PREC_FP32) {
+      if (epi == EPI_MUL) return conv_launch_epi<EPI_MUL, PREC_FP32, 7, false, true>(a, st);
+      if (epi == EPI_MUL_UP2) return conv_launch_epi<EPI_MUL_UP2, PREC_FP32, 7, false, true>(a, st);
+    }
+    return hipErrorInvalidValue;
+  }
   if (prec == PREC_F16X2) {                            // reverse walk of the VGG encoder only
     // terms 7: S(hi + lo) x w(hi + lo) without lo*lo — three MFMAs; terms 5: the weights' lo half dropped — two.  Which
     // layers take which is the caller's rule (Encoder::explain: two-term up to the last pool, measured there).

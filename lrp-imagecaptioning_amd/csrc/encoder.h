@@ -62,6 +62,11 @@ struct ConvLayer {
   bool norm_dirty = true;
   DevBuf Akeep;    // fine-tune step only: a_l of the layers whose output is the next conv's input (no pool after); the
                    // LRP path turns that storage into the gate in place
+  // alpha-beta rule with beta > 0 (Encoder::set_rule): the inhibitor gate G- = a / safe(Z_inh) next to G (same mask), the
+  // forward matrix w- of its denominator conv (fp32, split8) and the two-chain backward matrix [alpha w+ ; -beta w-]
+  // (cnn_kernels.h pack_conv_ab_dev_kernel; the image layer: pack_image_layer_ab_dev_kernel).  Allocated on the first beta > 0.
+  DevBuf Gn, w_fwd_n, w_fwd_ns, w_bwd_ab, w_bwd_ab_s;
+  bool ab_packed = false;
   size_t act_elems() const { return (size_t)H * W * cout; }
 };
 
@@ -207,14 +212,144 @@ struct Encoder {
     return LRP_OK;
   }
 
+  // ---- alpha-beta rule (lrp_set_cnn_rule; RR:274-322 with beta > 0) ----
+  // R_in = alpha act - beta inh with two denominators per layer, Z_act (the Z+ of alpha1beta0) and Z_inh = conv(x+, w-) + b
+  // (behind a ReLU or a pool x- = 0: the second conv of each branch contributes its bias only).  The walk carries two chains
+  // S+ = R / safe(Z_act), S- = R / safe(Z_inh) as one tensor [S+ | S-] and every launch is ONE GEMM over both:
+  //   c = convT(S+, alpha w+) + convT(S-, -beta w-);  S+' = G+ c,  S-' = G- c        (conv_igemm.h ConvArgs::aux_b)
+  // beta = 0 (the default) is the alpha1beta0 walk: nothing here is allocated, launched or read.
+  float ab_alpha = 1.f, ab_beta = 0.f;
+  bool ab_on() const { return ab_beta > 0.f; }
+  DevBuf zntop, s0ab, s1ab;                            // Z_inh of the top layer; the two-chain ping-pong
+  size_t max_act_elems() const {
+    size_t m = 0;
+    for (const ConvLayer& L : layers) m = std::max(m, L.act_elems());
+    return m;
+  }
+  int set_rule(float alpha, float beta, int64_t* total) {
+    if (alpha == ab_alpha && beta == ab_beta) return LRP_OK;
+    const bool was_on = ab_on();
+    if (beta > 0.f) {
+      auto mk = [&](DevBuf& d, size_t floats) -> int {
+        if (d.p) return LRP_OK;
+        LRP_TRY(d.alloc(floats * sizeof(float), total));
+        LRP_HIP_CHECK(hipMemset(d.p, 0, d.bytes));       // padding rows / columns stay zero
+        return LRP_OK;
+      };
+      const size_t B = (size_t)max_images, NT = (size_t)max_tokens;
+      for (size_t i = 0; i < layers.size(); ++i) {
+        ConvLayer& L = layers[i];
+        if (i + 1 < layers.size()) LRP_TRY(mk(L.Gn, B * L.act_elems()));
+        if (i == 0) {
+          LRP_TRY(mk(L.w_fwd_n, (size_t)conv_npad(L.cout) * 64));
+          const size_t nb = (size_t)conv_npad(IMG_T_COLS) * conv_cinp(2 * L.cout);
+          LRP_TRY(mk(L.w_bwd_ab, nb)); LRP_TRY(mk(L.w_bwd_ab_s, nb));
+        } else {
+          const size_t nf = (size_t)conv_npad(L.cout) * 9 * conv_cinp(L.cin), nb = (size_t)conv_npad(L.cin) * 9 * conv_cinp(2 * L.cout);
+          LRP_TRY(mk(L.w_fwd_n, nf)); LRP_TRY(mk(L.w_fwd_ns, nf));
+          LRP_TRY(mk(L.w_bwd_ab, nb)); LRP_TRY(mk(L.w_bwd_ab_s, nb));
+        }
+      }
+      LRP_TRY(mk(zntop, B * layers.back().act_elems()));
+      const size_t tok = std::max(2 * max_act_elems(), (size_t)img_h * img_w * IMG_T_COLS);
+      LRP_TRY(mk(s0ab, NT * tok)); LRP_TRY(mk(s1ab, NT * tok));
+      LRP_TRY(enable_keep_acts(total, true));            // the denominator convs read the layer inputs after the forward
+    } else {
+      keep_for_rule = false;                             // (the buffers stay, idle; the fine-tune step's own request stands)
+      keep_acts = keep_for_train;
+    }
+    ab_alpha = alpha; ab_beta = beta;
+    for (ConvLayer& L : layers) L.ab_packed = false;
+    encoded = 0;                                         // the caches belong to the old rule
+    return LRP_OK;
+  }
+  // the rule's operand copies of layer li from w_dev (HWIO, device)
+  int pack_ab_layer(int li, const float* w_dev, hipStream_t st) {
+    ConvLayer& L = layers[li];
+    auto split = [&](const float* src, float* dst, size_t n) {
+      hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n / 8)), dim3(256), 0, st, src, dst, n / 8);
+    };
+    if (li == 0) {
+      const int Kb2 = conv_cinp(2 * L.cout);
+      hipLaunchKernelGGL(pack_image_layer_ab_dev_kernel, dim3((27 * L.cout + 255) / 256), dim3(256), 0, st, w_dev, L.w_fwd_n.as<float>(),
+                         L.w_bwd_ab.as<float>(), L.cout, Kb2, ab_alpha, ab_beta);
+      split(L.w_bwd_ab.as<float>(), L.w_bwd_ab_s.as<float>(), (size_t)conv_npad(IMG_T_COLS) * Kb2);
+    } else {
+      const int CPi = conv_cinp(L.cin), CP2 = conv_cinp(2 * L.cout);
+      const size_t nf = (size_t)conv_npad(L.cout) * 9 * CPi, nb = (size_t)conv_npad(L.cin) * 9 * CP2;
+      hipLaunchKernelGGL(pack_conv_ab_dev_kernel, dim3(stream_grid((size_t)L.cout * 9 * CPi)), dim3(256), 0, st, w_dev, L.w_fwd_n.as<float>(), 0,
+                         L.cin, L.cout, CPi, L.cout, ab_alpha, ab_beta);
+      hipLaunchKernelGGL(pack_conv_ab_dev_kernel, dim3(stream_grid((size_t)L.cin * 9 * CP2)), dim3(256), 0, st, w_dev, L.w_bwd_ab.as<float>(), 1,
+                         L.cin, L.cout, CP2, L.cin, ab_alpha, ab_beta);
+      split(L.w_fwd_n.as<float>(), L.w_fwd_ns.as<float>(), nf);
+      split(L.w_bwd_ab.as<float>(), L.w_bwd_ab_s.as<float>(), nb);
+    }
+    LRP_HIP_CHECK(hipGetLastError());
+    L.ab_packed = true;
+    return LRP_OK;
+  }
+  bool ab_split() const {                                // the rule's arithmetic follows the handle's mode (as walk_mode's split)
+    if (prec != PREC_BF16X3) return false;
+    for (const ConvLayer& L : layers)
+      if (L.cout & 7) return false;
+    return true;
+  }
+  // Behind the forward (keep_acts: every conv's input is still there): per layer one more denominator conv with w- and the full
+  // bias, G- with the mask of G+; Z_inh of the top layer next to ztop.  Exact fp32 in LRP_PREC_FP32, three-term split-bf16 like
+  // the Z+ convs of the mixed modes otherwise; the image layer's GEMM stays fp32 as in every forward.
+  int inhibitor_pass(int B, hipStream_t st) {
+    if (gates_pending) {                                 // G+, bufZ and bufXs belong to the side stream until its gates are done
+      LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_gates, 0));
+      gates_pending = false;
+    }
+    const bool split = ab_split();
+    for (size_t li = 0; li < layers.size(); ++li) {
+      ConvLayer& L = layers[li];
+      if (!L.ab_packed) {
+        if (!L.raw_w_dev.p) return fail(LRP_ERR_STATE, "layer '%s': set its weights again after a change of the CNN rule", L.name.c_str());
+        LRP_TRY(pack_ab_layer((int)li, L.raw_w_dev.as<float>(), st));
+      }
+      const bool top = li + 1 == layers.size();
+      ConvArgs cz;
+      int zprec = PREC_FP32;
+      if (li == 0) {
+        LRP_TRY(im2col_gemm_args(B, st, cz));
+        cz.wpk = L.w_fwd_n.as<float>();
+      } else {
+        const float* x = layer_input((int)li);
+        if (split) {
+          LRP_TRY(split_copy(x, (size_t)B * L.H * L.W * L.cin / 8, st));
+          x = bufXs.as<float>();
+          zprec = PREC_BF16X3;
+        }
+        cz = fwd_conv_args(L, B, x);
+        cz.wpk = split ? L.w_fwd_ns.as<float>() : L.w_fwd_n.as<float>();
+      }
+      cz.N = L.cout;
+      cz.out = top ? zntop.as<float>() : bufZ.as<float>();
+      if (!top && !L.pool_after) { cz.gate_src = L.Akeep.as<float>(); cz.out = L.Gn.as<float>(); }
+      LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, st, zprec));
+      if (!top && L.pool_after) {
+        LRP_TRY(full_gate((int)li, st));
+        const size_t n4 = (size_t)B * L.act_elems() / 4;
+        hipLaunchKernelGGL(pool_gate_inh_kernel, dim3(stream_grid(n4)), dim3(256), 0, st, L.G.as<f32x4>(), L.P.as<float>(), bufZ.as<f32x4>(),
+                           L.Gn.as<f32x4>(), B, L.H, L.W, L.cout);
+        LRP_HIP_CHECK(hipGetLastError());
+      }
+    }
+    return LRP_OK;
+  }
+
   // Fine-tune step: the weight gradient of layer l needs a_{l-1}; keep what the LRP caches drop.
-  bool keep_acts = false;
-  int enable_keep_acts(int64_t* total) {
-    if (keep_acts) return LRP_OK;
+  // Two users: the fine-tune step (for the life of the handle once lrp_train_begin ran) and a beta > 0 rule (while it is set).
+  // keep_acts = either; each asks and releases for itself, so neither can switch the other's activations off.
+  bool keep_acts = false, keep_for_train = false, keep_for_rule = false;
+  int enable_keep_acts(int64_t* total, bool for_rule = false) {
     for (size_t li = 0; li + 1 < layers.size(); ++li) {
       ConvLayer& L = layers[li];
-      if (!L.pool_after) LRP_TRY(L.Akeep.alloc((size_t)max_images * L.act_elems() * sizeof(float), total));
+      if (!L.pool_after && !L.Akeep.p) LRP_TRY(L.Akeep.alloc((size_t)max_images * L.act_elems() * sizeof(float), total));   // (kept across a rule round trip)
     }
+    (for_rule ? keep_for_rule : keep_for_train) = true;
     keep_acts = true;
     return LRP_OK;
   }
@@ -340,6 +475,8 @@ struct Encoder {
     ConvLayer& L = layers[li];
     if (!L.have_w || !L.have_b) return fail(LRP_ERR_STATE, "layer %d has no operand copies to rebuild", li);
     LRP_TRY(repack_conv_weight_from_device(li, w_dev, tmp, st));
+    L.ab_packed = false;
+    if (ab_on()) LRP_TRY(pack_ab_layer(li, w_dev, st));
     L.norm_dirty = true;
     LRP_HIP_CHECK(hipMemcpyAsync(L.bias.p, b_dev, (size_t)L.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
     L.raw_w_dev.release(); L.raw_b_dev.release();   // stale from here on (the trainer's master buffer is the truth)
@@ -360,6 +497,7 @@ struct Encoder {
     LRP_TRY(repack_conv_weight_from_device(li, L.raw_w_dev.as<float>(), pack_tmp.as<float>(), st));
     L.have_w = true;
     L.norm_dirty = true;
+    L.ab_packed = false;                               // (repacked by the next encode under a beta > 0 rule)
     encoded = 0;                                       // caches belong to the old weights
     return LRP_OK;
   }
@@ -407,6 +545,10 @@ struct Encoder {
     LRP_TRY(fp.mode == FWD_EXACT ? forward_exact(B, st) : fp.mode == FWD_FAST ? forward_fast(B, st)
             : fp.emit ? forward_pairs_emit(B, st) : forward_pairs_split(B, st));
     encoded = B;
+    if (ab_on()) {
+      const int rc = inhibitor_pass(B, st);
+      if (rc != LRP_OK) { encoded = 0; return rc; }
+    }
     features_only = false;
     return LRP_OK;
   }
@@ -854,6 +996,56 @@ struct Encoder {
     return LRP_OK;
   }
 
+  // The two-chain walk of the alpha-beta rule with beta > 0 (see set_rule): the dense dual-gate launches conv_plan answers for
+  // ConvAsk::dual_mul; the image layer is the same tap-expanded GEMM + stencil over K = [S+ | S-].
+  int explain_ab(int n, const int* row2img_dev, const float* R_feat_dev, float* R_img_dev, hipStream_t st) {
+    const bool split = ab_split();
+    const int rp = split ? PREC_BF16X3 : PREC_FP32;
+    float *S = s0ab.as<float>(), *Snext = s1ab.as<float>();
+    {
+      const ConvLayer& T = layers.back();
+      const size_t pixels = (size_t)n * T.H * T.W, items = pixels * (T.cout / (split ? 8 : 4));
+      if (split)
+        hipLaunchKernelGGL(chain_join_kernel<true>, dim3(stream_grid(items)), dim3(256), 0, st, R_feat_dev, R_feat_dev, ztop.as<float>(),
+                           zntop.as<float>(), row2img_dev, S, pixels, T.H * T.W, T.cout);
+      else
+        hipLaunchKernelGGL(chain_join_kernel<false>, dim3(stream_grid(items)), dim3(256), 0, st, R_feat_dev, R_feat_dev, ztop.as<float>(),
+                           zntop.as<float>(), row2img_dev, S, pixels, T.H * T.W, T.cout);
+      LRP_HIP_CHECK(hipGetLastError());
+    }
+    for (int li = (int)layers.size() - 1; li >= 0; --li) {
+      const ConvLayer& L = layers[li];
+      ConvArgs ca = conv3x3_args(L, n, S, 2 * L.cout);
+      ca.wpk = split ? L.w_bwd_ab_s.as<float>() : L.w_bwd_ab.as<float>();
+      ca.row2img = row2img_dev;
+      int epi;
+      if (li == 0 && img_fused()) {
+        ca.taps = 1; ca.N = IMG_T_COLS; ca.out = R_img_dev; ca.ximg = images.as<float>(); ca.img_mode = 0;
+        epi = EPI_IMG_STENCIL;
+      } else if (li == 0) {
+        ca.NB = n * L.H * L.W; ca.H = 1; ca.W = 1; ca.taps = 1;
+        ca.N = IMG_T_COLS; ca.out = Snext; epi = EPI_STORE;
+      } else {
+        const ConvLayer& P = layers[li - 1];
+        ca.N = L.cin; ca.aux = P.G.as<float>(); ca.aux_b = P.Gn.as<float>();
+        ca.out = Snext; ca.out_b = Snext + L.cin; ca.ostride = 2 * L.cin;
+        epi = P.pool_after ? EPI_MUL_UP2 : EPI_MUL;
+        if (P.pool_after) LRP_TRY(full_gate(li - 1, st));
+      }
+      prof.begin(st);
+      LRP_HIP_CHECK(conv_launch(epi, ca, st, rp));
+      prof.end(st, 2.0 * layer_flop(n, li));
+      std::swap(S, Snext);
+    }
+    if (!img_fused()) {
+      const ConvLayer& L0 = layers[0];
+      hipLaunchKernelGGL(img_stencil_kernel, dim3(stream_grid((size_t)n * L0.H * L0.W)), dim3(256), 0, st, S, images.as<float>(), row2img_dev,
+                         R_img_dev, n, L0.H, L0.W, 0);
+      LRP_HIP_CHECK(hipGetLastError());
+    }
+    return LRP_OK;
+  }
+
   // R_feat_dev (n, top_h*top_w, top_c) -> R_img_dev (n, img_h, img_w, 3); row2img_dev: device int[n]
   // walk: 0 = LRP (LRPSequentialPresetA); gradient baselines (gradient_based.py:101-265) on the same caches:
   //   1 = Gradient, 2 = InputTimesGradient, 3 = GuidedBackprop — backward-data convs with the full w, the LRP gate
@@ -868,6 +1060,10 @@ struct Encoder {
     if (walk < 0 || walk > 3) return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
     if (encoded < 1 || features_only) return fail(LRP_ERR_STATE, "lrp_encode_images must run before the CNN explain");
     if (gates_pending) LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_gates, 0));   // gates / Z_top come from the side stream
+    if (ab_on() && walk == 0 && !layer_hook) {           // (the gradient walks and the fine-tune step ignore the rule)
+      if (walk_f16) return fail(LRP_ERR_UNSUPPORTED, "LRP_PREC_F16X2 has no alpha-beta walk with beta > 0 (its per-token scaling is per chain)");
+      return explain_ab(n, row2img_dev, R_feat_dev, R_img_dev, st);
+    }
     const WalkMode m = walk_mode(n, walk, layer_hook != nullptr);
     float *S = s0.as<float>(), *Snext = s1.as<float>();
     if (m.f16) {

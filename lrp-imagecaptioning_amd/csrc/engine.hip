@@ -127,6 +127,7 @@ int lrp_conv_plan(int32_t epi, int32_t prec, int32_t terms, int32_t NB, int32_t 
     q.epi = epi; q.prec = prec; q.terms = terms; q.NB = NB; q.H = H; q.W = W; q.N = N; q.Cin = Cin; q.taps = taps; q.split = split;
     q.frag = flags & LRP_PLAN_FRAG; q.join = flags & LRP_PLAN_JOIN; q.dual_il = flags & LRP_PLAN_DUAL_IL; q.gmask = flags & LRP_PLAN_GMASK;
     q.up2_src = flags & LRP_PLAN_UP2_SRC; q.img_part = flags & LRP_PLAN_IMG_PART; q.pool_gc = flags & LRP_PLAN_POOL_GC;
+    q.dual_mul = flags & LRP_PLAN_DUAL_MUL;
     const lrp::ConvPlan p = lrp::conv_plan(q);
     const int v[11] = {p.ok ? 1 : 0, p.form, p.BM, p.BN, p.threads, p.tw, p.th, p.hrows, p.tpt, p.m_tiles, p.n_tiles};
     for (int i = 0; i < 11; ++i) out11[i] = v[i];
@@ -411,6 +412,36 @@ int lrp_set_precision(lrp_handle* h, int32_t mode) {
   });
 }
 
+int lrp_set_cnn_rule(lrp_handle* h, float alpha, float beta) {
+  return with_handle(h, [&]() -> int {
+    if (!h) return fail(LRP_ERR_INVALID, "null handle");
+    // relevance_based/utils.py:72-129 (the caller's binding infers an omitted parameter and words the errors as the reference does)
+    if (!(alpha >= 1.f)) return fail(LRP_ERR_INVALID, "alpha should be >= 1 (alpha=%g)", (double)alpha);
+    if (!(beta >= 0.f)) return fail(LRP_ERR_INVALID, "beta should be >= 0 (beta=%g)", (double)beta);
+    // alpha - beta == 1 holds for the caller's numbers, which reach this entry rounded to float each (1.3f - 0.3f = 1 - 2^-24): the
+    // pair is accepted when it is 1 to that rounding (half an ulp of each operand), and the walk's beta is then alpha - 1, which
+    // is exact in float for alpha in [1, 2] and the nearest float beyond — so the relevance the rule conserves is conserved
+    if (!(fabs((double)alpha - (double)beta - 1.0) <= 6e-8 * ((double)alpha + (double)beta)))
+      return fail(LRP_ERR_INVALID, "alpha - beta should be 1 (alpha=%g, beta=%g)", (double)alpha, (double)beta);
+    beta = alpha - 1.f;
+    if (h->resnet) {
+      if (beta > 0.f) return fail(LRP_ERR_UNSUPPORTED, "the ResNet encoder's walk is alpha1beta0 only");
+      return LRP_OK;
+    }
+    if (alpha == h->enc.ab_alpha && beta == h->enc.ab_beta) return LRP_OK;
+    LRP_TRY(h->trainer.drop_early_forward(nullptr));
+    LRP_TRY(h->enc.set_rule(alpha, beta, &h->ws_bytes));
+    if (h->enc.ab_on() && h->trainer.ready) {
+      // the fine-tune step owns the weights (the layers' own HWIO copies are gone after its first update): the rule's matrices
+      // come from its master buffer, here, once per rule change
+      for (size_t li = 0; li < h->enc.layers.size(); ++li)
+        LRP_TRY(h->enc.pack_ab_layer((int)li, h->trainer.master.as<float>() + h->trainer.params[2 * li].off, nullptr));
+      LRP_HIP_CHECK(hipStreamSynchronize(nullptr));
+    }
+    return LRP_OK;
+  });
+}
+
 int lrp_set_fast_layers(lrp_handle* h, int64_t mask) {
   return with_handle(h, [&]() -> int {
     if (!h) return fail(LRP_ERR_INVALID, "null handle");
@@ -524,6 +555,48 @@ int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias
     }
     LRP_HIP_CHECK(conv_launch(epi_of_mode[mode], ca, st, split ? PREC_BF16X3 : PREC_FP32));
     LRP_HIP_CHECK(hipStreamSynchronize(st));             // weights are freed on return
+    return LRP_OK;
+  });
+}
+
+int lrp_op_conv_ab(const float* sp_dev, const float* sn_dev, const float* w_hwio_host, float alpha, float beta, const float* gp_dev,
+                   const float* gn_dev, float* outp_dev, float* outn_dev, int32_t NB, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                   int32_t pool, int32_t split, void* stream) {
+  return guarded([&]() -> int {
+    if (!sp_dev || !sn_dev || !w_hwio_host || !gp_dev || !gn_dev || !outp_dev || !outn_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (NB < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return fail(LRP_ERR_INVALID, "NB, H, W, Cin, Cout must be >= 1");
+    const int g = split ? 7 : 3;
+    if ((Cin & g) || (Cout & g)) return fail(LRP_ERR_UNSUPPORTED, "channels must be multiples of %d", g + 1);
+    if ((int64_t)NB * H * W * 2 * Cout >= ((int64_t)1 << 31) || (int64_t)9 * Cin * Cout >= ((int64_t)1 << 31))
+      return fail(LRP_ERR_UNSUPPORTED, "operator entry: tensor too large");
+    hipStream_t st = S(stream);
+    const int CP2 = conv_cinp(2 * Cout), Np = conv_npad(Cin);
+    DevBuf wraw, wab, wabs, sj;
+    LRP_TRY(wraw.alloc((size_t)9 * Cin * Cout * sizeof(float), nullptr));
+    LRP_HIP_CHECK(hipMemcpy(wraw.p, w_hwio_host, wraw.bytes, hipMemcpyHostToDevice));
+    const size_t nb = (size_t)Np * 9 * CP2;
+    LRP_TRY(wab.alloc(nb * sizeof(float), nullptr));
+    LRP_HIP_CHECK(hipMemsetAsync(wab.p, 0, wab.bytes, st));
+    hipLaunchKernelGGL(pack_conv_ab_dev_kernel, dim3(stream_grid((size_t)Cin * 9 * CP2)), dim3(256), 0, st, wraw.as<float>(), wab.as<float>(), 1,
+                       Cin, Cout, CP2, Cin, alpha, beta);
+    const size_t pixels = (size_t)NB * H * W;
+    LRP_TRY(sj.alloc(pixels * 2 * Cout * sizeof(float), nullptr));
+    if (split) {
+      LRP_TRY(wabs.alloc(nb * sizeof(float), nullptr));
+      hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(nb / 8)), dim3(256), 0, st, wab.as<float>(), wabs.as<float>(), nb / 8);
+      hipLaunchKernelGGL(chain_join_kernel<true>, dim3(stream_grid(pixels * (Cout / 8))), dim3(256), 0, st, sp_dev, sn_dev, (const float*)nullptr,
+                         (const float*)nullptr, (const int*)nullptr, sj.as<float>(), pixels, 1, Cout);
+    } else {
+      hipLaunchKernelGGL(chain_join_kernel<false>, dim3(stream_grid(pixels * (Cout / 4))), dim3(256), 0, st, sp_dev, sn_dev, (const float*)nullptr,
+                         (const float*)nullptr, (const int*)nullptr, sj.as<float>(), pixels, 1, Cout);
+    }
+    LRP_HIP_CHECK(hipGetLastError());
+    ConvArgs ca{};
+    ca.in = sj.as<float>(); ca.wpk = split ? wabs.as<float>() : wab.as<float>();
+    ca.NB = NB; ca.H = H; ca.W = W; ca.Cin = 2 * Cout; ca.CinP = CP2; ca.N = Cin; ca.taps = 9;
+    ca.aux = gp_dev; ca.aux_b = gn_dev; ca.out = outp_dev; ca.out_b = outn_dev; ca.ostride = Cin; ca.out_plain = 1;
+    LRP_HIP_CHECK(conv_launch(pool ? EPI_MUL_UP2 : EPI_MUL, ca, st, split ? PREC_BF16X3 : PREC_FP32));
+    LRP_HIP_CHECK(hipStreamSynchronize(st));             // the operand copies are freed on return
     return LRP_OK;
   });
 }

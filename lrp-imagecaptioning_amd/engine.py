@@ -65,6 +65,7 @@ class LRPEngine(object):
         self.captions = None
         self.n_images = 0
         self.precision = "bf16x3"                       # library default for the reverse walk (set_precision)
+        self.cnn_rule = (1, 0)                          # ... and for its conv rule (set_cnn_rule)
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -424,6 +425,20 @@ class LRPEngine(object):
             self.captions = None
         self.precision = mode
 
+    def set_cnn_rule(self, alpha=None, beta=None):
+        """The conv rule of the VGG-style encoder's LRP walk (lrp_set_cnn_rule): AlphaBetaRule with alpha >= 1, beta >= 0,
+        alpha - beta == 1; one of the two may be omitted and is inferred.  (1, 0), the default, is LRPSequentialPresetA's
+        alpha1beta0; (2, 1) is LRPAlpha2Beta1 / LRPSequentialPresetB.  A change drops the encode caches: call encode_images
+        again.  beta > 0 is not built for the ResNet encoder (NotImplementedError) nor for the 'f16x2' walk (the explain
+        calls raise NotImplementedError there)."""
+        from .analyzer import infer_alpha_beta
+        alpha, beta = infer_alpha_beta(alpha, beta, "LRPEngine.set_cnn_rule")
+        _capi.check(self._lib.lrp_set_cnn_rule(self._h, float(alpha), float(beta)))
+        if (alpha, beta) != self.cnn_rule:
+            self.n_images = 0                            # the library dropped the caches of the other rule
+            self.captions = None
+        self.cnn_rule = (alpha, beta)
+
     def set_fast_layers(self, mask):
         """Which conv layers take the two-MFMA form in 'f16x2' mode (lrp_set_fast_layers): bit li of `mask`, an iterable of
         layer indices, or None / -1 for the built-in rule.  0 = fp16 pairs with three MFMAs in every layer.  A change drops
@@ -486,6 +501,26 @@ def op_conv(x, w_hwio, bias, aux, mode, taps=9, split_bf16=False, wreg=False):
                                 mode | (CONV_SPLIT_BF16 if split_bf16 else 0) | (CONV_WREG if wreg else 0),
                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return out
+
+
+def op_conv_ab(sp, sn, w_hwio, alpha, beta, gp, gn, pool=False, split_bf16=False):
+    """The two-chain launch of the alpha-beta walk (lrp_op_conv_ab): c = convT(sp, alpha w+) + convT(sn, -beta w-) in one GEMM,
+    outputs (c x gp, c x gn), c repeated 2 x 2 with pool.  sp, sn (NB, H, W, Cout) float32 device tensors, w_hwio (3, 3, Cin,
+    Cout) numpy, gp, gn (NB, H u, W u, Cin)."""
+    lib = _capi.load()
+    w = np.ascontiguousarray(w_hwio, dtype=np.float32)
+    Cin, Cout = w.shape[2], w.shape[3]
+    NB, H, W, _ = sp.shape
+    u = 2 if pool else 1
+    assert tuple(sn.shape) == (NB, H, W, Cout) == tuple(sp.shape)
+    assert tuple(gp.shape) == tuple(gn.shape) == (NB, u * H, u * W, Cin)
+    sp, sn, gp, gn = sp.contiguous(), sn.contiguous(), gp.contiguous(), gn.contiguous()
+    outp = torch.empty((NB, u * H, u * W, Cin), dtype=torch.float32, device=sp.device)
+    outn = torch.empty_like(outp)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    _capi.check(lib.lrp_op_conv_ab(p(sp), p(sn), w.ctypes.data_as(C.c_void_p), float(alpha), float(beta), p(gp), p(gn), p(outp), p(outn),
+                                   NB, H, W, Cin, Cout, int(bool(pool)), int(bool(split_bf16)), _cur_stream(sp.device)))
+    return outp, outn
 
 
 def op_conv_pool_sparse(sc, pos, w_hwio, gate, reps=1):

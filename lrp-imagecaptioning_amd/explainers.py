@@ -45,8 +45,12 @@ class CaptionModelSpec(object):
     """What the reference reads off `model` (E:26-39): encoder kind, dims, and the weights."""
 
     def __init__(self, weights, img_encoder="vgg16", hidden_dim=512, embedding_dim=512, L=196, D=512,
-                 vocab_size=None, cnn_cfg=None, img_hw=(224, 224), resnet=None):
-        """img_encoder 'vgg16' (config.py:36-40: block5_conv3, 196 x 512), 'vgg19' (config.py:37: block5_conv4) or
+                 vocab_size=None, cnn_cfg=None, img_hw=(224, 224), resnet=None, cnn_rule=(1, 0)):
+        """cnn_rule: the (alpha, beta) of the encoder's conv rule (LRPEngine.set_cnn_rule), or 'alpha1beta0' (the default:
+        LRPSequentialPresetA, E:32) / 'alpha2beta1' (LRPSequentialPresetB's conv rule); every explainer built on the spec
+        whose CNN half is the LRP walk applies it to its engine; the gradient-baseline classes do not (their walks ignore the
+        rule, and setting it would cost them its encode pass and buffers for nothing).
+        img_encoder 'vgg16' (config.py:36-40: block5_conv3, 196 x 512), 'vgg19' (config.py:37: block5_conv4) or
         'resnet101' (config.py:41-45: conv5_block3_out, 49 x 2048; `resnet` = dict(stem, stacks), default ResNet-101).
         cnn_cfg: the conv list of a VGG-style encoder (default: the full-size one of `img_encoder`)."""
         if img_encoder not in ("vgg16", "vgg19", "resnet101"):
@@ -65,10 +69,17 @@ class CaptionModelSpec(object):
         self.vocab_size = vocab_size if vocab_size is not None else int(self.weights["output_W"].shape[1])
         self.cnn_cfg = list(cnn_cfg)
         self.img_hw = tuple(img_hw)
+        if isinstance(cnn_rule, str):
+            if cnn_rule not in ("alpha1beta0", "alpha2beta1"):
+                raise ValueError("cnn_rule must be (alpha, beta), 'alpha1beta0' or 'alpha2beta1'")
+            cnn_rule = (1, 0) if cnn_rule == "alpha1beta0" else (2, 1)
+        from .analyzer import infer_alpha_beta
+        self.cnn_rule = infer_alpha_beta(cnn_rule[0], cnn_rule[1], "CaptionModelSpec")
 
 
 class ExplainImgCaptioningAttentionModel(object):
     _decoder_kind = None
+    _applies_cnn_rule = True     # the CNN half is the LRP walk (False: the gradient baselines, whose walks ignore the rule)
 
     def __init__(self, model, weight_path=None, dataset_provider=None, max_caption_length=20, max_images=1,
                  device=None):
@@ -91,6 +102,8 @@ class ExplainImgCaptioningAttentionModel(object):
                                  eos_id=self._preprocessor.EOS_TOKEN_LABEL_ENCODED, device=device,
                                  resnet=getattr(model, "resnet", None))
         self._engine.set_weights(model.weights)
+        if self._applies_cnn_rule and tuple(getattr(model, "cnn_rule", (1, 0))) != (1, 0):
+            self._engine.set_cnn_rule(*model.cnn_rule)
         self._CNN_explainer = _EngineAnalyzer(self._engine)      # LRPSequentialPresetA(image_model, EPS, 'replace'), E:32
         self._state_cache = {}
         self.caption = None
@@ -331,6 +344,7 @@ class ExplainImgCaptioningGridTDModel(ExplainImgCaptioningAttentionModel):
 # ---------------------------------------------------------------------------------------------------------------
 class _GradientMixin(object):
     _walk = "gradient"
+    _applies_cnn_rule = False
 
     def __init__(self, *args, **kwargs):
         super(_GradientMixin, self).__init__(*args, **kwargs)
