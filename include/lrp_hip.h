@@ -544,7 +544,7 @@ int64_t lrp_launch_count(void);
  * lrp_encode_images.  The reference has no counterpart. */
 int lrp_reload_switches(void);
 
-/* ABI v8.  Which form of the implicit-GEMM convolution kernel a launch would take (csrc/conv_igemm.h conv_plan: the one
+/* ABI v8.  Which form of the implicit-GEMM convolution kernel a launch would take (csrc/conv_plan.h conv_plan: the one
  * function the launcher executes and every caller inside the library asks) — pure host arithmetic on the current switches:
  * it touches no device, so the tile rules can be tested on a machine without a GPU (tests/test_conv_plan.py).
  *   epi    LRP_EPI_*: the epilogue;  prec  LRP_OPND_*: the operand format;  terms  7, or 5 / 23 (two-MFMA forms of LRP_OPND_F16X2)

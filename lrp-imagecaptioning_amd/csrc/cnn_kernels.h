@@ -2,7 +2,7 @@
 // not a convolution).  All are pure streaming kernels: 16 B per lane, coalesced.
 #pragma once
 #include <hip/hip_runtime.h>
-#include "conv_igemm.h"
+#include "conv_args.h"
 
 namespace lrp {
 
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void pack_conv_dev_kernel(const float* __restr
     dst[i] = (pos && !(v >= 0.f)) ? 0.f : v;
   }
 }
-// ---- fp16-pair operands (conv_igemm.h PREC_F16X2).  A weight matrix is stored scaled by a power of two, 2^k with
+// ---- fp16-pair operands (conv_args.h PREC_F16X2).  A weight matrix is stored scaled by a power of two, 2^k with
 // k = floor(log2(16384 / max|w|)): unscaled, the lo halves of VGG-sized weights (|w| ~ 1e-3, lo ~ 5e-7) fall into fp16's
 // subnormals and the pair keeps 15 bits instead of 21 [MI355X: feature error of the forward 2.4e-6 -> see DESIGN 4.1].
 // Per matrix a device record wsc[4] = { 2^k, 2^-k, max row sum of |hi| (scaled), k } that the consumers read.
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(256) void dual_interleave_rows_kernel(const float* 
 // scaled by scale[image]) in ONE pass over (a_l, Z+_l): replaces maxpool2_kernel + pool_gate_kernel + split_h_scaled_kernel.
 // 8 channels per thread; a may alias g; xnext (fp32 pooled activations: the fine-tune step's kept input) may be null.
 // gc / gpos (may be null): the same gate in COMPACT form — per window and channel its one non-zero value and that value's
-// position p = 2 dy + dx — for the compact pool interface (conv_igemm.h ConvArgs::up2_src: its producer multiplies with gc,
+// position p = 2 dy + dx — for the compact pool interface (conv_args.h ConvArgs::up2_src: its producer multiplies with gc,
 // its consumer reads gpos).
 __global__ __launch_bounds__(256) void pool_gate_split_kernel(const float* a, const float* __restrict__ z, float* g,
                                                               float* __restrict__ pairs, float* __restrict__ xnext,
@@ -367,7 +367,7 @@ __global__ __launch_bounds__(256) void pool_gate_split_kernel(const float* a, co
   }
 }
 // the full-resolution pool gate from its compact form (one value per window and channel + its position byte): what the fused
-// pool epilogue of the forward conv (conv_igemm.h ConvArgs::pool_gc) leaves for the walks that read the expanded interface —
+// pool epilogue of the forward conv (conv_args.h ConvArgs::pool_gc) leaves for the walks that read the expanded interface —
 // the gradient baselines, the fp32 / fast modes, LRP_UP2_COMPACT=0 — built on their first use after an encode.  8 channels per thread.
 __global__ __launch_bounds__(256) void pool_gate_expand_kernel(const float* __restrict__ gc, const unsigned char* __restrict__ gpos,
                                                                float* __restrict__ g, int NB, int H, int W, int C) {
@@ -683,7 +683,7 @@ __global__ __launch_bounds__(256) void img_stencil_kernel(const float* __restric
   }
 }
 
-// Second half of the image layer when it is folded into the epilogue of the layer above it (conv_igemm.h ConvArgs::img_part):
+// Second half of the image layer when it is folded into the epilogue of the layer above it (conv_args.h ConvArgs::img_part):
 // every tile of that launch left, for its (th + 2) x (tw + 2) ring-inclusive output positions, the six partial sums
 // (3 x "+", 3 x "-") over the source pixels it owns.  An output pixel adds the partials of the up to four tiles whose ring
 // covers it — in a FIXED order (tile row, then tile column), the same for every token and every batch — and applies

@@ -10,6 +10,8 @@
 // Template axes: tile (WM, WN, TM, TN), epilogue EPI, operand arithmetic PREC (exact fp32 MFMA | split-bf16),
 // HALO (3x3: A tile + halo resident in LDS for all 9 taps), BREG (weights in registers, no barrier per tap: N <= 64, and the 8-wave tile),
 // TERMS (which partial products of the split operands are issued).  DESIGN.md 4.1 has the measurements behind each.
+// This file is the kernel alone: its arguments are conv_args.h, which instantiations exist and which one a launch takes is
+// conv_plan.h, the launchers are conv_launch.h.  A translation unit that wants ONE instantiation (ISA inspection) includes this file.
 //
 // GEMM view: D[m][n] = sum_k A[m][k] * B[k][n],  m = output pixel (NHWC row),
 // n = output channel, k = (tap, input channel).  A is gathered on the fly
@@ -25,236 +27,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-#include <algorithm>
-#include <vector>
 
-#include "common.h"
+#include "conv_args.h"
+#include "conv_plan.h"
 
 namespace lrp {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// PREC_FP32 : operands fp32, v_mfma_f32_32x32x2_f32 (exact fp32 fma chain).  The walk and the forward of LRP_PREC_FP32; the image
-//   layer's forward GEMM and the decoder's products in every mode.
-// PREC_BF16X3: operands stored as "split8" — per 8 consecutive channels 32 B = [8 x bf16 hi | 8 x bf16 lo] with
-//   x ~= hi + lo (16 mantissa bits), same bytes as fp32.  Each product is hi*hi' + hi*lo' + lo*hi' on
-//   v_mfma_f32_32x32x16_bf16 with fp32 accumulation: 3 MFMAs of 32 cycles per 16 k instead of 8 of 64
-//   (5.3x fewer matrix-pipe cycles).  The per-token reverse walk of the DEFAULT mode (lrp_create: LRP_PREC_BF16X3): worst case
-//   2^-16 per product whatever the weights [MI355X: 2-3.5e-6 relative L1 vs the float64 graph on He-normal kernels,
-//   6e-6 ... 1.6e-5 on trained-like ones, DESIGN 4.2].
-// PREC_F16X2 : both operands as fp16 pairs hi + lo (22 mantissa bits) in the same split8 layout, carried scaled by powers
-//   of two taken from MEASURED maxima (fp16 has 5 exponent bits): per token for the relevance S of the reverse walk
-//   (ConvArgs::tok_*; Encoder::explain), per image for the forward's activations, per matrix for the weights.
-//   TERMS 7: hi*hi' + hi*lo' + lo*hi', three v_mfma_f32_32x32x16_f16 per 16 k — fp32-grade.  This is the encoder FORWARD of every
-//   mode but LRP_PREC_FP32 (the interleaved dual conv a_l | Z+_l, blocked accumulation: features 7e-7 from float64) and the top
-//   block of the opt-in fast walk.
-//   TERMS 5: the weights' lo half is not read: lo*w + hi*w, TWO MFMAs — the layers of the OPT-IN fast walk (LRP_PREC_F16X2) that
-//   lrp_set_fast_layers / calibration.py selected; TERMS bit 4 computes the matching two-term denominators Z+ in the forward.
-//   One fp16 per weight is 2^-12 per product: fine on dense Gaussian kernels (the rounding averages out), above the 1e-4 bar on
-//   sparse heavy-tailed ones — which is why this is not the default (tests/test_gpu_stress_parity.py).
-enum ConvPrec { PREC_FP32 = 0, PREC_BF16X3 = 1, PREC_F16X2 = 2 };
-
-__device__ __forceinline__ void split8h_store(const float* r, float* dst) {  // 8 fp32 -> 32 B [fp16 hi8 | fp16 lo8]
-  f16x8 hi, lo;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    hi[q] = (_Float16)r[q];
-    lo[q] = (_Float16)(r[q] - (float)hi[q]);
-  }
-  u32x4* d = reinterpret_cast<u32x4*>(dst);
-  d[0] = __builtin_bit_cast(u32x4, hi);
-  d[1] = __builtin_bit_cast(u32x4, lo);
-}
-__device__ __forceinline__ void split8_store(const float* r, float* dst) {   // 8 fp32 -> 32 B [hi8 | lo8]
-  bf16x8 hi, lo;
-#pragma unroll
-  for (int q = 0; q < 8; ++q) {
-    hi[q] = (__bf16)r[q];
-    lo[q] = (__bf16)(r[q] - (float)hi[q]);
-  }
-  u32x4* d = reinterpret_cast<u32x4*>(dst);
-  d[0] = __builtin_bit_cast(u32x4, hi);
-  d[1] = __builtin_bit_cast(u32x4, lo);
-}
-
-enum ConvEpi {
-  EPI_BIAS_RELU = 0,  // out = relu(acc + bias)
-  EPI_BIAS = 1,       // out = acc + bias
-  EPI_MUL = 2,        // out = acc * aux[img(row)]               (conv-LRP, no pool)
-  EPI_MUL_UP2 = 3,    // out(2x res) = acc * aux[img(row)](2x)   (conv-LRP through a 2x2 max-pool)
-  EPI_FWD_DUAL = 4,   // cols [0,split): out = relu(acc+bias); cols [split,2split): out2 = acc+bias  (a_l and Z+_l)
-  EPI_STORE = 5,      // out = acc (row stride = N)   (image layer: tap-expanded channel reduction, see img_stencil_kernel)
-  // Image layer in ONE launch: the rows of a tile are a 16 x 16 pixel PATCH (14 x 14 output pixels + 1 halo), the
-  // tile computes T = S_1 . W (54 tap-expanded columns, see cnn_kernels.h) for the patch, keeps it in LDS and applies
-  // the 9-tap shift-and-add for its 14 x 14 interior: S_1 is read once (x 1.31 halo) and only R_img is written,
-  // instead of writing and re-reading the 3.5 GB T tensor.  BM = 256, BN = 64, 1 tap.
-  EPI_IMG_STENCIL = 6
-};
-constexpr int IMG_PATCH = 16, IMG_TILE = 14;
-
-// Halo-resident launches walk the image STACK (all tokens on top of each other) tile row by tile row.  The gate a tile is
-// multiplied with belongs to the token's IMAGE, and with several tokens per image (10 words per caption) the same gate rows
-// were fetched once per token — the stack order puts 25 tile rows of other traffic between two uses, far more than an
-// XCD's 4 MB of L2 [MI355X, block1_conv2: FETCH_SIZE 8.2 GB = S_in 4.1 + 10 x 0.41 of gates].  TileOrder is a per-layer
-// host cache of a permutation of the tiles — ordered by (image, column strip, row band, token) — so that the tiles of an
-// image's tokens at the same place run back to back on one XCD (they share the gate rows in its L2) and a strip's next
-// row band follows within a few dozen tiles (the vertical halo rows of S are still there); built from the call's
-// token -> image map, rebuilt only when that map changes.  Tiles are independent, so the order changes no result bit.
-struct TileOrder {
-  std::vector<int> sig;                                 // token -> image map the table was built for
-  int H = 0, th = 0, nyh = 0, cols_t = 0, tpt = 0;
-  bool identity = true;
-  int* dev = nullptr;
-  int* pinned = nullptr;
-  size_t cap = 0;
-  hipEvent_t ev = nullptr;                              // the last upload
-  TileOrder() = default;
-  TileOrder(const TileOrder&) = delete;
-  TileOrder& operator=(const TileOrder&) = delete;
-  ~TileOrder() {
-    if (dev) (void)hipFree(dev);
-    if (pinned) (void)hipHostFree(pinned);
-    if (ev) (void)hipEventDestroy(ev);
-  }
-};
-
-struct ConvArgs {
-  const float* in;     // [NB][H][W][Cin] fp32
-  const float* wpk;    // [n_tiles*BN][K] fp32, K = taps*CinP, CinP = roundup(Cin,32), zero padded
-  const float* wpk_frag;  // BREG: the same weights fragment-major, [kc][step][hi|lo][lane half][all N columns] x 16 B (N = 64, or N % 128 == 0)
-  int NB, H, W, Cin, CinP;
-  int N;               // valid output columns
-  int taps;            // 9 (3x3 same) or 1
-  int M;               // NB*H*W
-  int m_tiles, n_tiles;
-  const float* bias;
-  float* out;
-  float* out2;
-  const float* aux;
-  const int* row2img;  // per input image-slot n -> cache slot (nullptr = identity)
-  int split;
-  int out_plain;       // bf16x3 MUL epilogues: 1 = write fp32 instead of re-splitting (last GEMM of a chain)
-  // EPI_IMG_STENCIL: tiles per image row / column, ximg = the images (x of the image layer), mode 0 LRP | 1 sum | 2 x*sum
-  int tiles_x, tiles_y, img_mode;
-  const float* ximg;
-  const float* addend; // BIAS / BIAS_RELU epilogues: out = [relu](acc + bias + addend)  (bias may be null)
-  // EPI_BIAS only: out = gate_src / SafeDivide-denominator(acc + bias) — the relevance gate G_l = a_l / safe(Z+_l)
-  // (IL:456-458) straight from the denominator conv, Z+_l itself never goes to memory.  gate_src may alias out (the
-  // overlapped encode parks a_l in the gate's storage): an element is read and written by the same thread.
-  const float* gate_src;
-  // EPI_MUL only — tail of a residual block in one epilogue (ResNet walk):
-  //   r    = acc * aux[img] + join[row] * join_gate[img]     (the shortcut's share joins the main branch, KG:799-803)
-  //   out  = r                                               (fp32 / split8 as usual)
-  //   out2 = r * gate2[img]                                  (head of the NEXT block's conv chain; split8 in bf16x3 mode)
-  const float* join;
-  const float* join_gate;
-  const float* gate2;
-  float* out2s;
-  // gradient baselines on the MUL epilogues: the cached LRP gate is used as a MASK (gate != 0 <=> the unit's ReLU was
-  // active and it won its pool window), and guided backprop also clamps the propagated value at 0
-  int gate_binary, relu_out;
-  int dual_norelu;     // EPI_FWD_DUAL: first half without the relu (a conv + BatchNorm unit: c and Z+ in one pass)
-  // EPI_FWD_DUAL, interleaved weights (dual_il): the stacked matrix has its rows in blocks of 32 — [w of channels 32g..32g+31 |
-  // w+ of the SAME channels] — so a tile holds c and Z+ of a channel side by side and the epilogue can finish the pair:
-  // dual_gate = 1: out = a_l = relu(c), out2 = the relevance gate G_l = a_l / safe(Z+_l) (IL:456-458); Z+_l never goes to
-  // memory and no gate pass follows.  dual_gate = 0: out2 = Z+_l as in the stacked form.  Needs split % 32 == 0.
-  int dual_il, dual_gate;
-  // dual_gate = 2 (a conv + BatchNorm unit of the ResNet encoder, RA:197-257 folded with alpha1beta0; resnet_kernels.h
-  // rn_bn_unit_kernel is the unfused form): with c = conv + b, Z = the alpha1beta0 denominator,
-  //   y = gamma (c - mean) / sqrt(var + eps) + beta,  Q = c (y - beta) / stab((c - mean) y) / safe(Z)
-  //   bn_relu: out = relu(y), out2 = relu(y) Q      else: out = y, out2 = Q
-  const float* bn_gamma; const float* bn_beta; const float* bn_mean; const float* bn_var;
-  float bn_eps; int bn_relu;
-  // halo-resident 3x3 variant (template HALO): a tile is th rows x tw (<= 14) columns of the image stack
-  // (all NB images on top of each other: Y = n*H + h), cols_t tiles per image row; hrows = rows of the
-  // resident image (th + 2 + separator rows), each HALO_PITCH pixels wide
-  int tw, th, hrows, cols_t, nyh;
-  const int* tile_map;        // device: launch position -> tile of the stack (nullptr = stack order); filled by the launcher from:
-  TileOrder* order;           // host: the layer's cache (nullptr = never reorder)
-  const int* row2img_host;    // host copy of row2img for this call (nullptr = identity: one token per image)
-  // PREC_F16X2: per-token power-of-two scaling of the fp16 relevance tensors (indexed by the token slot n of a row).
-  //   stored input = true * 2^e_in[n], |stored input| <= max_in[n] (measured by the producer).  tok_scale_kernel
-  //   (cnn_kernels.h) picks k[n] = floor(log2(30000 / (max_in[n] * wnorm))) — wnorm = max row sum of |w| of the layer's
-  //   backward matrix, the gate is <= 1, so |acc * gate| * 2^k stays below fp16's 65504 — and hands this launch
-  //   tok_fac[n] = 2^k[n]; the epilogue stores acc * gate * tok_fac[n] and raises tok_max_out[n] (float bits) to the
-  //   largest |stored output|.  EPI_IMG_STENCIL ends the chain: tok_fac[n] = 2^-e_in[n].
-  const float* tok_fac;
-  unsigned* tok_max_out;
-  // PREC_F16X2 forward (EPI_BIAS / EPI_BIAS_RELU, TERMS 7 = fp16 pairs on BOTH operands, 22 mantissa bits: an fp32-grade
-  // product in three MFMAs): the input tensor is stored scaled by a power of two; *in_unscale (device scalar) = its
-  // inverse, applied to the accumulator in front of the bias.  act_max_out: ACT_MAX_SLOTS float-bit slots raised to the
-  // largest |out| (slot = block id mod slots: spreads the atomics; the consumer takes the maximum over the slots).
-  const float* in_unscale;
-  unsigned* act_max_out;
-  // EPI_FWD_DUAL, interleaved rows, PREC_F16X2: the epilogue also writes a_l as the NEXT conv's operand — fp16 pairs
-  // [hi8 | lo8] of a_l * *pairs_scale (a power of two chosen BEFORE the launch from a bound on |a_l|: the measured maximum
-  // of this conv's input x its weights' largest absolute row sum + max|b|; cnn_kernels.h fwd_scale_kernel) — so no split
-  // pass runs between two convs.  skip_out: a_l itself (fp32) is not written (nobody else reads it).
-  float* pairs_out;
-  const float* pairs_scale;
-  int skip_out;
-  // scale_per_img (interleaved dual forward): in_unscale, pairs_scale and act_max_out are arrays indexed by the IMAGE of a row
-  // (row / img_rows; act_max_out[image][ACT_MAX_SLOTS]) instead of one record for the call — an image's rows only ever gather
-  // from that image, so a scale per image is as legal as one per call, and the result for an image no longer depends on
-  // which other images share its batch.
-  int scale_per_img, img_rows, n_imgs;
-  // Compact pool interface (PREC_BF16X3, EPI_MUL / EPI_MUL_UP2 on the halo kernels: the folded weights-in-registers launch and
-  // the pipelined 128 x 128 / 256 x 256 tiles): the relevance entering this layer came through a 2x2 max-pool, i.e.
-  // S_in[n][y][x][c] = S_c[n][y/2][x/2][c] at the window's arg-max position and 0 at the three others.  Instead of reading that
-  // 4x-expanded, 75 %-zero tensor (which its producer would have had to write), the producer runs EPI_MUL with this layer's
-  // COMPACT pool gate and writes S_c = acc x gate at pooled resolution as bf16 pairs, and the tile builds its resident image
-  // from S_c and the position bytes (2 dy + dx per window and channel, per image: shared by an image's tokens in L2): the
-  // value where the position matches, zeros elsewhere.  `in` is then unused.
-  const float* up2_src;        // S_c [NB][H/2][W/2][Cin] split8 bf16 pairs
-  int gate_none;               // EPI_MUL: out = acc, no gate (ResNet gradient walk: a unit without a ReLU mask in front)
-  const unsigned char* up2_gpos;   // [images][H/2][W/2][Cin] bytes
-  int up2_pairs;               // must be 1 with up2_src: pairs are the only form the loaders read (conv_launch_epi refuses others)
-  // Image layer folded into the epilogue of the layer above it (weights-in-registers kernel, PREC_BF16X3, N = 64, EPI_MUL):
-  // S_1 = acc x gate never goes to memory.  The tile turns it into bf16 pairs in LDS, multiplies it with the tap-expanded
-  // 64 -> 54 matrix `img_w` (the image layer's T = S_1 . W, cnn_kernels.h) and applies the 9-tap shift-and-add for the
-  // SOURCE pixels it owns: per tile (th + 2) x (tw + 2) output positions (its pixels and the one-pixel ring around them)
-  // x 6 partial sums go to img_part[tile of the stack][position][6]; img_partial_sum_kernel adds the up to four tiles'
-  // partials of a pixel in a fixed order and applies x+ / x-.  Tiles are laid out per token (tpt below: none straddles two
-  // tokens, so the grouping of a pixel's nine taps into partials is the same for every token and every batch: results stay
-  // batch-invariant bit for bit).
-  const float* img_w;          // [64][64] split8 bf16 pairs (layer 0's backward matrix)
-  float* img_part;
-  // tpt > 0 (folded launch): tiles are laid out PER TOKEN — tpt tile rows of th stack rows per token, the last one possibly
-  // short — instead of over the whole stack, so that no tile straddles two tokens and the tile boundaries fall at the same
-  // image rows for every token.  Tile row R of the launch covers token R / tpt, image rows (R % tpt) * th ...
-  int tpt;
-  int epi_generic;             // MUL / MUL_UP2 epilogues: 1 = always the general pass loop (A/B switch LRP_EPI_FAST=0; filled by the launcher)
-  // 2x2 max-pool fused into the interleaved dual forward's epilogue (PREC_F16X2, 128 x 128 resident-image tile: the whole C
-  // tile is in LDS; tiles of an EVEN number of rows and columns starting at even positions, so a window never straddles two
-  // tiles): per window and channel the epilogue takes the first maximum in scan order, and writes — instead of a_l and Z+_l
-  // at full resolution, which a streaming pass then read back (cnn_kernels.h pool_gate_split_kernel: the same arithmetic) —
-  //   pool_gc   [images][H/2][W/2][C]   the gate a_l / safe(Z+_l) at the winning position (IL:456-458 through the pool)
-  //   pool_pos  same shape, bytes        that position, 2 dy + dx
-  //   pairs_out [images][H/2][W/2][C]   the pooled activation as the next conv's fp16 pairs (x pairs_scale[image])
-  //   pool_x    (optional) the pooled activation in fp32
-  // and raises act_max_out from the pooled values.  The full-resolution gate is rebuilt from (pool_gc, pool_pos) on demand.
-  float* pool_gc;
-  unsigned char* pool_pos;
-  float* pool_x;
-  // Dual-gate MUL epilogues (template DG; alpha-beta LRP with beta > 0, Encoder::explain_ab): the two relevance chains
-  // S+ = R / safe(Z_act) and S- = R / safe(Z_inh) travel as ONE tensor, channels [S+ (C) | S- (C)] per pixel, so that the
-  // launch against the concatenated matrix [alpha w+ ; -beta w-] (K = taps x 2C) is the ordinary implicit GEMM with
-  // Cin = 2C and its accumulator c = convT(S+, alpha w+) + convT(S-, -beta w-) is shared by both chains:
-  //   out = c x aux[img],  out_b = c x aux_b[img]      (aux = G+ = a / safe(Z_act), aux_b = G- = a / safe(Z_inh): N wide each)
-  // out / out_b have ostride floats per pixel (2N with out_b = out + N: the next launch's input; N for two plain tensors).
-  const float* aux_b;
-  float* out_b;
-  int ostride;
-};
-constexpr int ACT_MAX_SLOTS = 64;
-
-constexpr int LDS_STRIDE = 32;   // floats per staged row (128 B, no padding; swizzled chunks)
 
 // Out-of-image taps / ragged tails read this instead of branching around the load: the
 // select is two v_cndmask on the address, the load itself stays unconditional and the
@@ -265,17 +42,6 @@ __device__ __attribute__((aligned(16))) float lrp_zero_page[4] = {0.f, 0.f, 0.f,
 // floor(160 KB / LDS per block) blocks of NW waves
 constexpr int conv_min_waves(int NW, int TM, int TN, bool halo = false) { return NW == 8 || halo ? 2 : (TM * TN >= 4 ? 2 : 3); }
 
-// HALO (3x3 only): instead of re-staging the A tile for each of the 9 taps (9 x BM rows per 32-channel
-// chunk, 8 of them L2 hits but still L2->LDS traffic, the limiter of the bf16x3 mode), the tile's pixels
-// PLUS their one-pixel halo are staged once per channel chunk and the taps read shifted rows of that
-// resident image.  A traffic per chunk: 9 x 256 rows -> 352 rows.
-// The resident image is a window of the EXTENDED stack: every image contributes its H rows plus one all-zero
-// separator row (extended row E = n*(H+1) + h, h == H is the separator), and columns x0-1 .. x0+tw with zeros
-// outside [0, W).  A pixel's 3x3 neighbourhood is then always at fixed offsets (dy*HALO_PITCH + dx) from it,
-// borders included: no per-lane tap masks in the main loop.  See DESIGN.md 4.1.
-constexpr int HALO_PITCH = 16, HALO_PL = 4;
-constexpr int conv_halo_rows(int BM) { return BM == 256 ? 352 : 192; }   // x 128 B; 22 / 12 image rows
-
 // BREG (HALO, bf16x3, N <= 64 layers): the weights never touch LDS.  With K <= 2 x 32 channels per group the whole A
 // operand of a group is resident (both LDS buffers hold one 32-channel chunk each), and the B fragments of a
 // (tap, chunk) are 4 coalesced 16 B loads per lane from a fragment-major copy of the packed weights (wpk_frag,
@@ -284,7 +50,7 @@ constexpr int conv_halo_rows(int BM) { return BM == 256 ? 352 : 192; }   // x 12
 // TERMS (split operands): which partial products of (ah + al)(bh + bl) are issued — bit 0: al*bh, bit 1: ah*bl, bit 2: ah*bh
 // (al*bl never).  7 = all three: every split launch but the PREC_F16X2 forms below.  PREC_F16X2 only: 5 = bit 1 off, the
 // weights' lo half is not read (two MFMAs); bit 4 (23 = 7 | 16, interleaved dual forward) = the same for the odd 32-column
-// blocks of the matrix only (Z+: z_tile in the kernel).  conv_launch instantiates 7 for PREC_BF16X3 and 7, 5, 23 for PREC_F16X2.
+// blocks of the matrix only (Z+: z_tile in the kernel).  Which values exist for which format and epilogue: conv_plan.h conv_epi_exists.
 // NS (plain staging only: !HALO, !BREG): LDS stages of the k pipeline.  2 = chunk kc+2 is launched at the barrier of iteration kc
 // and must have landed one iteration later — fine when an iteration holds 24-48 MFMAs per wave, but the 64 x 64 tiles of the
 // small-grid launches (6 MFMAs per wave and iteration) then run at one L2 / HBM round trip per k-step [MI355X, one image:
@@ -313,12 +79,9 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
   constexpr bool BREG4 = BREG && NW == 4 && TN == 2;   // the same loop on the 4-wave 128 x 128 tile (FORM_BREG4: walk and dual forward)
   constexpr bool BREGC = BREG8 || BREG4;               // weights in registers, one barrier per channel CHUNK
   static_assert(!BREG || (HALO && SPLIT && (BREGC || BM * BN <= 2 * STAGE)), "BREG needs the resident image");
-  static_assert(!BREG8 || (PREC == PREC_BF16X3 && EPI == EPI_MUL && TERMS == 7 && TM == 4 && TN == 2), "one instantiation: the dense split-bf16 walk");
-  static_assert(!BREG4 || (TM == 2 && ((PREC == PREC_BF16X3 && EPI == EPI_MUL && TERMS == 7) || (PREC == PREC_F16X2 && EPI == EPI_FWD_DUAL && (TERMS == 7 || TERMS == 23)))),
-                "two uses: the dense split-bf16 walk and the interleaved fp16-pair dual forward");
-  static_assert(!PW || (BREG4 && PREC == PREC_BF16X3), "PW: the split-bf16 walk on the 128 x 128 weights-in-registers loop");
-  static_assert(!DG || ((EPI == EPI_MUL || EPI == EPI_MUL_UP2) && PREC != PREC_F16X2 && !BREG && !GMASK && !PW && TERMS == 7 && WM * WN == 4),
-                "dual gate: the MUL epilogues of the 4-wave staged / pipelined tiles, exact fp32 or split-bf16");
+  // which tiles, forms and epilogues go together — BREG8 / BREG4: the dense split-bf16 walk (and, BREG4, the fp16-pair dual forward);
+  // PW: that walk on the BREG4 loop; DG: the MUL epilogues of the 4-wave staged / pipelined tiles — is conv_plan.h's table
+  static_assert(conv_kernel_instantiated(WM, WN, TM, TN, HALO, BREG, NS, PW, EPI, PREC, TERMS, GMASK, DG), "no such instantiation: conv_plan.h conv_kernel_exists");
   static_assert((BM / 8) % NW == 0 && (BN / 8) % NW == 0, "pieces must divide over the waves");
   static_assert(!HALO || EPI != EPI_STORE, "the image layer is a 1-tap GEMM");
   static_assert(NS == 2 || (NS > 2 && !HALO && !BREG), "deeper staging exists for the plain (non-resident) A path only");
@@ -1670,78 +1433,6 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
         // gate rows one pass AHEAD of the arithmetic (written as explicit phases — left as load/multiply/store per
         // pass, the possible aliasing of `out` and `aux` made hipcc serialise a full memory round trip per pass, which
         // the short K = 576 layers could not hide).
-        if constexpr (DG) {
-          // ---- dual gate (ConvArgs::aux_b): one accumulator, two gates, two outputs.  The fast form below with a second gate
-          // row per pass; the ring is shorter (two gate sets per entry).
-          if (col < a.N) {
-            constexpr int NPd = RH / RPP;
-            constexpr int UPd = EPI == EPI_MUL_UP2 ? 4 : 1;
-            constexpr int RINGd = UPd == 1 ? (2 < NPd ? 2 : NPd) : 1;
-            const int W2d = 2 * a.W, H2d = 2 * a.H;
-            int imgd[NPd];
-#pragma unroll
-            for (int ps = 0; ps < NPd; ++ps) {
-              int row, n_, h_, w_;
-              if (!locate(hf * RH + rin + ps * RPP, row, n_, h_, w_)) n_ = 0;
-              imgd[ps] = a.row2img ? a.row2img[n_] : n_;
-            }
-            f32x4 gd[RINGd][UPd][2][CW / 4];
-            auto issue = [&](int ps) {
-              int row, n_, h_, w_;
-              if (!locate(hf * RH + rin + ps * RPP, row, n_, h_, w_)) { h_ = 0; w_ = 0; }
-#pragma unroll
-              for (int q = 0; q < UPd; ++q) {
-                const size_t go = EPI == EPI_MUL ? ((size_t)imgd[ps] * HW + h_ * a.W + w_) * a.N + col
-                                                 : (((size_t)imgd[ps] * H2d + 2 * h_ + (q >> 1)) * W2d + 2 * w_ + (q & 1)) * a.N + col;
-#pragma unroll
-                for (int q4 = 0; q4 < CW / 4; ++q4) {
-                  gd[ps % RINGd][q][0][q4] = *reinterpret_cast<const f32x4*>(a.aux + go + 4 * q4);
-                  gd[ps % RINGd][q][1][q4] = *reinterpret_cast<const f32x4*>(a.aux_b + go + 4 * q4);
-                }
-              }
-            };
-#pragma unroll
-            for (int ps = 0; ps < RINGd - 1; ++ps) issue(ps);
-            const bool plain = SPLIT_OUT && a.out_plain;
-#pragma unroll
-            for (int ps = 0; ps < NPd; ++ps) {
-              if (ps + RINGd - 1 < NPd) issue(ps + RINGd - 1);
-              int row, n_, h_, w_;
-              if (locate(hf * RH + rin + ps * RPP, row, n_, h_, w_)) {
-                const int ll = rin + ps * RPP;
-                float v[CW];
-#pragma unroll
-                for (int q4 = 0; q4 < CW / 4; ++q4)
-                  *reinterpret_cast<f32x4*>(v + 4 * q4) = *reinterpret_cast<const f32x4*>(Cs + ll * BN + c4 * CW + 4 * q4);
-#pragma unroll
-                for (int q = 0; q < UPd; ++q) {
-                  const size_t po = EPI == EPI_MUL ? (size_t)row * a.ostride + col
-                                                   : (((size_t)n_ * H2d + 2 * h_ + (q >> 1)) * W2d + 2 * w_ + (q & 1)) * a.ostride + col;
-#pragma unroll
-                  for (int b = 0; b < 2; ++b) {
-                    float r[CW];
-#pragma unroll
-                    for (int q4 = 0; q4 < CW / 4; ++q4)
-#pragma unroll
-                      for (int e = 0; e < 4; ++e) r[4 * q4 + e] = v[4 * q4 + e] * gd[ps % RINGd][q][b][q4][e];
-                    float* dst = (b ? a.out_b : a.out) + po;
-                    if constexpr (SPLIT_OUT) {
-                      if (plain) {
-                        *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(r);
-                        *reinterpret_cast<f32x4*>(dst + 4) = *reinterpret_cast<const f32x4*>(r + 4);
-                      } else {
-                        split8_store(r, dst);
-                      }
-                    } else {
-                      *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(r);
-                    }
-                  }
-                }
-              }
-            }
-          }
-          continue;                                     // next slab
-        } else
         if (col < a.N) {
           // ---- the walk's common case (plain gate, no residual join, no second head, no gradient-walk switches): the same
           // arithmetic with nothing to decide inside the passes.  In the general form below every runtime switch sits next to
@@ -1750,12 +1441,16 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
           // tile's epilogue ran as 16 dependent L2 round trips with the matrix pipe idle.  Here the gate loads of RING passes
           // are in flight, unconditionally (padding rows read row 0 of image 0), and each pass waits with a counted vmcnt.
           // Rows are located twice (at issue and at use: a few VALU ops) instead of keeping six arrays of NP entries alive.
+          // Dual gate (DG, ConvArgs::aux_b): always this form, with a second gate row per pass — one accumulator, two gates, two
+          // outputs of ostride floats per pixel — and a shorter ring (two gate sets per entry).
           if constexpr (PREC != PREC_F16X2) {
             const bool tail_ = EPI == EPI_MUL && a.join != nullptr, head2_ = EPI == EPI_MUL && a.out2s != nullptr;
-            if (!GMASK && !(EPI == EPI_MUL && a.gate_none) && !tail_ && !head2_ && !a.gate_binary && !a.relu_out && !a.epi_generic) {
+            if (DG || (!GMASK && !(EPI == EPI_MUL && a.gate_none) && !tail_ && !head2_ && !a.gate_binary && !a.relu_out && !a.epi_generic)) {
               constexpr int NPf = RH / RPP;
               constexpr int UPf = EPI == EPI_MUL_UP2 ? 4 : 1;
-              constexpr int RING = (UPf == 1 ? 4 : 2) < NPf ? (UPf == 1 ? 4 : 2) : NPf;
+              constexpr int NG = DG ? 2 : 1;              // gates per pass; gate b of ring slot s lies in gq[b * RING + s]
+              constexpr int DEPTH = DG ? (UPf == 1 ? 2 : 1) : (UPf == 1 ? 4 : 2);
+              constexpr int RING = DEPTH < NPf ? DEPTH : NPf;
               const int W2f = 2 * a.W, H2f = 2 * a.H;
               int imgf[NPf];
 #pragma unroll
@@ -1764,7 +1459,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
                 if (!locate(hf * RH + rin + ps * RPP, row, n_, h_, w_)) n_ = 0;
                 imgf[ps] = a.row2img ? a.row2img[n_] : n_;
               }
-              f32x4 gq[RING][UPf][CW / 4];
+              f32x4 gq[NG * RING][UPf][CW / 4];
               auto issue = [&](int ps) {
                 int row, n_, h_, w_;
                 if (!locate(hf * RH + rin + ps * RPP, row, n_, h_, w_)) { h_ = 0; w_ = 0; }
@@ -1774,6 +1469,10 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
                                                    : a.aux + (((size_t)imgf[ps] * H2f + 2 * h_ + (q >> 1)) * W2f + 2 * w_ + (q & 1)) * a.N + col;
 #pragma unroll
                   for (int q4 = 0; q4 < CW / 4; ++q4) gq[ps % RING][q][q4] = *reinterpret_cast<const f32x4*>(gp + 4 * q4);
+                  if constexpr (DG) {
+#pragma unroll
+                    for (int q4 = 0; q4 < CW / 4; ++q4) gq[RING + ps % RING][q][q4] = *reinterpret_cast<const f32x4*>(a.aux_b + (gp - a.aux) + 4 * q4);
+                  }
                 }
               };
 #pragma unroll
@@ -1799,6 +1498,8 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
                     float* dst = EPI == EPI_MUL
                                      ? a.out + (size_t)row * a.N + col
                                      : a.out + (((size_t)n_ * H2f + 2 * h_ + (q >> 1)) * W2f + 2 * w_ + (q & 1)) * a.N + col;
+                    if constexpr (DG)                     // out / out_b: ostride floats per pixel
+                      dst = a.out + (EPI == EPI_MUL ? (size_t)row : ((size_t)n_ * H2f + 2 * h_ + (q >> 1)) * W2f + 2 * w_ + (q & 1)) * a.ostride + col;
                     if constexpr (SPLIT_OUT) {
                       if (plain) {
                         *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(r);
@@ -1808,6 +1509,23 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
                       }
                     } else {
                       *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(r);
+                    }
+                    if constexpr (DG) {                   // the same accumulator under the second gate
+#pragma unroll
+                      for (int q4 = 0; q4 < CW / 4; ++q4)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) r[4 * q4 + e] = v[4 * q4 + e] * gq[RING + ps % RING][q][q4][e];
+                      float* dstb = a.out_b + (dst - a.out);
+                      if constexpr (SPLIT_OUT) {
+                        if (plain) {
+                          *reinterpret_cast<f32x4*>(dstb) = *reinterpret_cast<const f32x4*>(r);
+                          *reinterpret_cast<f32x4*>(dstb + 4) = *reinterpret_cast<const f32x4*>(r + 4);
+                        } else {
+                          split8_store(r, dstb);
+                        }
+                      } else {
+                        *reinterpret_cast<f32x4*>(dstb) = *reinterpret_cast<const f32x4*>(r);
+                      }
                     }
                   }
                 }
@@ -1819,141 +1537,143 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
             //  [MI355X, same box: 24.55 -> 25.15 ms, WRITE_SIZE +11 %: the register allocator spilled], so it was taken out
             //  again; those launches are bound by their three full-width streams either way)
           }
-          constexpr int NP = RH / RPP;
-          constexpr int UPN = EPI == EPI_MUL_UP2 ? 4 : 1;
-          const int W2 = 2 * a.W, H2 = 2 * a.H;
-          int rowv[NP], nv[NP], hv[NP], wv[NP], imgv[NP];
-          bool okv[NP];
+          if constexpr (!DG) {                           // the general pass loop: one gate
+            constexpr int NP = RH / RPP;
+            constexpr int UPN = EPI == EPI_MUL_UP2 ? 4 : 1;
+            const int W2 = 2 * a.W, H2 = 2 * a.H;
+            int rowv[NP], nv[NP], hv[NP], wv[NP], imgv[NP];
+            bool okv[NP];
 #pragma unroll
-          for (int ps = 0; ps < NP; ++ps) {
-            okv[ps] = locate(hf * RH + rin + ps * RPP, rowv[ps], nv[ps], hv[ps], wv[ps]);
-            if (!okv[ps]) { rowv[ps] = 0; nv[ps] = 0; hv[ps] = 0; wv[ps] = 0; }
-            imgv[ps] = a.row2img ? a.row2img[nv[ps]] : nv[ps];
-          }
-          // PREC_F16X2: running maximum of |stored output| for the token of the rows this thread has seen so far
-          unsigned lmax = 0u;
-          int ltok = -1;
-          auto flush_max = [&](int t, unsigned m) {
-            if (m) {
-              const int rel = t - tok_first;
-              if (TMAX_LDS && rel >= 0 && rel < 16) atomicMax(tmax_s + rel, m);
-              else atomicMax(a.tok_max_out + t, m);
+            for (int ps = 0; ps < NP; ++ps) {
+              okv[ps] = locate(hf * RH + rin + ps * RPP, rowv[ps], nv[ps], hv[ps], wv[ps]);
+              if (!okv[ps]) { rowv[ps] = 0; nv[ps] = 0; hv[ps] = 0; wv[ps] = 0; }
+              imgv[ps] = a.row2img ? a.row2img[nv[ps]] : nv[ps];
             }
-          };
-          const bool tail = EPI == EPI_MUL && a.join != nullptr, head2 = EPI == EPI_MUL && a.out2s != nullptr;
-          struct Gates { f32x4 g[UPN][CW / 4]; f32x4 jn[CW / 4], jg[CW / 4], g2[CW / 4]; };
-          auto gate_ptr = [&](int ps, int q) -> const float* {
-            if constexpr (EPI == EPI_MUL)
-              return a.aux + ((size_t)imgv[ps] * HW + hv[ps] * a.W + wv[ps]) * a.N + col;
-            else
-              return a.aux + (((size_t)imgv[ps] * H2 + 2 * hv[ps] + (q >> 1)) * W2 + 2 * wv[ps] + (q & 1)) * a.N + col;
-          };
-          auto load_gates = [&](Gates& G, int ps) {
-            const f32x4 one4 = {1.f, 1.f, 1.f, 1.f};
-            if constexpr (GMASK) {
-              static_assert(EPI == EPI_MUL && PREC == PREC_FP32 && CW == 4, "byte-mask gates: exact fp32 EPI_MUL only");
-              auto m4 = [](const float* base, size_t e) {
-                const unsigned m = *reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(base) + e);
-                f32x4 g;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) g[q] = ((m >> (8 * q)) & 0xFFu) ? 1.f : 0.f;
-                return g;
-              };
-              const size_t go = ((size_t)imgv[ps] * HW + hv[ps] * a.W + wv[ps]) * a.N + col;
-              G.g[0][0] = m4(a.aux, go);
-              if (tail) {
-                G.jn[0] = *reinterpret_cast<const f32x4*>(a.join + (size_t)rowv[ps] * a.N + col);
-                G.jg[0] = m4(a.join_gate, go);
+            // PREC_F16X2: running maximum of |stored output| for the token of the rows this thread has seen so far
+            unsigned lmax = 0u;
+            int ltok = -1;
+            auto flush_max = [&](int t, unsigned m) {
+              if (m) {
+                const int rel = t - tok_first;
+                if (TMAX_LDS && rel >= 0 && rel < 16) atomicMax(tmax_s + rel, m);
+                else atomicMax(a.tok_max_out + t, m);
               }
-              return;
-            }
+            };
+            const bool tail = EPI == EPI_MUL && a.join != nullptr, head2 = EPI == EPI_MUL && a.out2s != nullptr;
+            struct Gates { f32x4 g[UPN][CW / 4]; f32x4 jn[CW / 4], jg[CW / 4], g2[CW / 4]; };
+            auto gate_ptr = [&](int ps, int q) -> const float* {
+              if constexpr (EPI == EPI_MUL)
+                return a.aux + ((size_t)imgv[ps] * HW + hv[ps] * a.W + wv[ps]) * a.N + col;
+              else
+                return a.aux + (((size_t)imgv[ps] * H2 + 2 * hv[ps] + (q >> 1)) * W2 + 2 * wv[ps] + (q & 1)) * a.N + col;
+            };
+            auto load_gates = [&](Gates& G, int ps) {
+              const f32x4 one4 = {1.f, 1.f, 1.f, 1.f};
+              if constexpr (GMASK) {
+                static_assert(EPI == EPI_MUL && PREC == PREC_FP32 && CW == 4, "byte-mask gates: exact fp32 EPI_MUL only");
+                auto m4 = [](const float* base, size_t e) {
+                  const unsigned m = *reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(base) + e);
+                  f32x4 g;
 #pragma unroll
-            for (int q = 0; q < UPN; ++q)
-#pragma unroll
-              for (int q4 = 0; q4 < CW / 4; ++q4)
-                G.g[q][q4] = (EPI == EPI_MUL && a.gate_none) ? one4 : *reinterpret_cast<const f32x4*>(gate_ptr(ps, q) + 4 * q4);
-            if constexpr (EPI == EPI_MUL) {
-              const size_t go = ((size_t)imgv[ps] * HW + hv[ps] * a.W + wv[ps]) * a.N + col;
-#pragma unroll
-              for (int q4 = 0; q4 < CW / 4; ++q4) {
+                  for (int q = 0; q < 4; ++q) g[q] = ((m >> (8 * q)) & 0xFFu) ? 1.f : 0.f;
+                  return g;
+                };
+                const size_t go = ((size_t)imgv[ps] * HW + hv[ps] * a.W + wv[ps]) * a.N + col;
+                G.g[0][0] = m4(a.aux, go);
                 if (tail) {
-                  G.jn[q4] = *reinterpret_cast<const f32x4*>(a.join + (size_t)rowv[ps] * a.N + col + 4 * q4);
-                  G.jg[q4] = *reinterpret_cast<const f32x4*>(a.join_gate + go + 4 * q4);
+                  G.jn[0] = *reinterpret_cast<const f32x4*>(a.join + (size_t)rowv[ps] * a.N + col);
+                  G.jg[0] = m4(a.join_gate, go);
                 }
-                if (head2) G.g2[q4] = *reinterpret_cast<const f32x4*>(a.gate2 + go + 4 * q4);
+                return;
               }
-            }
-          };
-          Gates cur, nxt;
-          load_gates(cur, 0);
 #pragma unroll
-          for (int ps = 0; ps < NP; ++ps) {
-            if (ps + 1 < NP) load_gates(nxt, ps + 1);
-            float fac16 = 1.f;                            // PREC_F16X2: the power of two this launch adds to the token's scale
-            if constexpr (PREC == PREC_F16X2) {
-              fac16 = a.tok_fac[nv[ps]];
-              if (okv[ps] && nv[ps] != ltok) { flush_max(ltok, lmax); ltok = nv[ps]; lmax = 0u; }
-            }
-            if (okv[ps]) {
-              const int ll = rin + ps * RPP;
-              float v[CW];
+              for (int q = 0; q < UPN; ++q)
 #pragma unroll
-              for (int q4 = 0; q4 < CW / 4; ++q4)
-                *reinterpret_cast<f32x4*>(v + 4 * q4) = *reinterpret_cast<const f32x4*>(Cs + ll * BN + c4 * CW + 4 * q4);
-#pragma unroll
-              for (int q = 0; q < UPN; ++q) {
-                float r[CW];
+                for (int q4 = 0; q4 < CW / 4; ++q4)
+                  G.g[q][q4] = (EPI == EPI_MUL && a.gate_none) ? one4 : *reinterpret_cast<const f32x4*>(gate_ptr(ps, q) + 4 * q4);
+              if constexpr (EPI == EPI_MUL) {
+                const size_t go = ((size_t)imgv[ps] * HW + hv[ps] * a.W + wv[ps]) * a.N + col;
 #pragma unroll
                 for (int q4 = 0; q4 < CW / 4; ++q4) {
-                  f32x4 g = cur.g[q][q4];
-                  if (a.gate_binary) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) g[e] = g[e] != 0.f ? 1.f : 0.f;
+                  if (tail) {
+                    G.jn[q4] = *reinterpret_cast<const f32x4*>(a.join + (size_t)rowv[ps] * a.N + col + 4 * q4);
+                    G.jg[q4] = *reinterpret_cast<const f32x4*>(a.join_gate + go + 4 * q4);
                   }
+                  if (head2) G.g2[q4] = *reinterpret_cast<const f32x4*>(a.gate2 + go + 4 * q4);
+                }
+              }
+            };
+            Gates cur, nxt;
+            load_gates(cur, 0);
 #pragma unroll
-                  for (int e = 0; e < 4; ++e) {
-                    float pr = v[4 * q4 + e] * g[e];
-                    if (tail) pr += cur.jn[q4][e] * cur.jg[q4][e];
-                    if constexpr (PREC == PREC_F16X2) {
-                      pr *= fac16;
-                      lmax = max(lmax, __float_as_uint(fabsf(pr)));               // (non-negative floats order like their bits)
+            for (int ps = 0; ps < NP; ++ps) {
+              if (ps + 1 < NP) load_gates(nxt, ps + 1);
+              float fac16 = 1.f;                            // PREC_F16X2: the power of two this launch adds to the token's scale
+              if constexpr (PREC == PREC_F16X2) {
+                fac16 = a.tok_fac[nv[ps]];
+                if (okv[ps] && nv[ps] != ltok) { flush_max(ltok, lmax); ltok = nv[ps]; lmax = 0u; }
+              }
+              if (okv[ps]) {
+                const int ll = rin + ps * RPP;
+                float v[CW];
+#pragma unroll
+                for (int q4 = 0; q4 < CW / 4; ++q4)
+                  *reinterpret_cast<f32x4*>(v + 4 * q4) = *reinterpret_cast<const f32x4*>(Cs + ll * BN + c4 * CW + 4 * q4);
+#pragma unroll
+                for (int q = 0; q < UPN; ++q) {
+                  float r[CW];
+#pragma unroll
+                  for (int q4 = 0; q4 < CW / 4; ++q4) {
+                    f32x4 g = cur.g[q][q4];
+                    if (a.gate_binary) {
+#pragma unroll
+                      for (int e = 0; e < 4; ++e) g[e] = g[e] != 0.f ? 1.f : 0.f;
                     }
-                    r[4 * q4 + e] = a.relu_out ? fmaxf(pr, 0.f) : pr;
-                  }
-                }
-                float* dst = EPI == EPI_MUL
-                                 ? a.out + (size_t)rowv[ps] * a.N + col
-                                 : a.out + (((size_t)nv[ps] * H2 + 2 * hv[ps] + (q >> 1)) * W2 + 2 * wv[ps] + (q & 1)) * a.N + col;
-                if constexpr (SPLIT_OUT) {
-                  if (a.out_plain) {
-                    *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(r);
-                    *reinterpret_cast<f32x4*>(dst + 4) = *reinterpret_cast<const f32x4*>(r + 4);
-                  } else if constexpr (PREC == PREC_F16X2) {
-                    split8h_store(r, dst);
-                  } else {
-                    split8_store(r, dst);
-                  }
-                } else {
-                  *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(r);
-                }
-                if (head2) {
-                  float r2[CW];
 #pragma unroll
-                  for (int q4 = 0; q4 < CW / 4; ++q4)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) r2[4 * q4 + e] = r[4 * q4 + e] * cur.g2[q4][e];
-                  float* d2 = a.out2s + (size_t)rowv[ps] * a.N + col;
+                    for (int e = 0; e < 4; ++e) {
+                      float pr = v[4 * q4 + e] * g[e];
+                      if (tail) pr += cur.jn[q4][e] * cur.jg[q4][e];
+                      if constexpr (PREC == PREC_F16X2) {
+                        pr *= fac16;
+                        lmax = max(lmax, __float_as_uint(fabsf(pr)));               // (non-negative floats order like their bits)
+                      }
+                      r[4 * q4 + e] = a.relu_out ? fmaxf(pr, 0.f) : pr;
+                    }
+                  }
+                  float* dst = EPI == EPI_MUL
+                                   ? a.out + (size_t)rowv[ps] * a.N + col
+                                   : a.out + (((size_t)nv[ps] * H2 + 2 * hv[ps] + (q >> 1)) * W2 + 2 * wv[ps] + (q & 1)) * a.N + col;
                   if constexpr (SPLIT_OUT) {
-                    split8_store(r2, d2);
+                    if (a.out_plain) {
+                      *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(r);
+                      *reinterpret_cast<f32x4*>(dst + 4) = *reinterpret_cast<const f32x4*>(r + 4);
+                    } else if constexpr (PREC == PREC_F16X2) {
+                      split8h_store(r, dst);
+                    } else {
+                      split8_store(r, dst);
+                    }
                   } else {
-                    *reinterpret_cast<f32x4*>(d2) = *reinterpret_cast<const f32x4*>(r2);
+                    *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(r);
+                  }
+                  if (head2) {
+                    float r2[CW];
+#pragma unroll
+                    for (int q4 = 0; q4 < CW / 4; ++q4)
+#pragma unroll
+                      for (int e = 0; e < 4; ++e) r2[4 * q4 + e] = r[4 * q4 + e] * cur.g2[q4][e];
+                    float* d2 = a.out2s + (size_t)rowv[ps] * a.N + col;
+                    if constexpr (SPLIT_OUT) {
+                      split8_store(r2, d2);
+                    } else {
+                      *reinterpret_cast<f32x4*>(d2) = *reinterpret_cast<const f32x4*>(r2);
+                    }
                   }
                 }
               }
+              cur = nxt;
             }
-            cur = nxt;
+            if constexpr (PREC == PREC_F16X2) flush_max(ltok, lmax);
           }
-          if constexpr (PREC == PREC_F16X2) flush_max(ltok, lmax);
         }
       }
     }
@@ -1984,497 +1704,5 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
   }
 #endif
 }
-
-#ifndef LRP_CONV_KERNEL_ONLY   // (a translation unit that wants ONE instantiation for ISA inspection defines this and skips the launchers)
-// tile configurations: (WM,WN,TM,TN) -> BM x BN
-//   big   : 2,2,2,2 -> 128 x 128   (N >= 128)                 64 KB LDS, 2 blocks/CU   [fp32]
-//   n64   : 2,2,2,1 -> 128 x  64   (N == 64 layers)           48 KB LDS, 3 blocks/CU
-//   n32   : 4,1,1,1 -> 128 x  32   (N <= 32: tiny test nets)  40 KB LDS
-//   big, BREG (FORM_BREG4): weights in registers, 64 KB LDS, 2 blocks/CU   [dense bf16x3 walk, interleaved f16x2 dual forward; N % 128 == 0]
-//   w256  : 2,4,4,2 -> 256 x 256   8 waves, 128 KB LDS, 1 block/CU   [bf16x3, N % 256 == 0; BREG: the dense walk launches, FORM_BREG8]
-// bf16x3 spends 5.3x fewer matrix cycles per byte staged, so its limiter is the L2 -> LDS path
-// (~43 GB/s per CU at 128 x 128): the 8-wave tile stages 50 % fewer bytes per FLOP.
-struct ConvTile { int BM, BN; };
-inline ConvTile conv_pick_tile(int N) {
-  if (N > 64) return {128, 128};
-  if (N > 32) return {128, 64};
-  return {128, 32};
-}
-inline int conv_npad(int N) { ConvTile t = conv_pick_tile(N); return (N + t.BN - 1) / t.BN * t.BN; }
-inline int conv_cinp(int Cin) { return (Cin + 31) / 32 * 32; }
-
-// ---- the launch plan: ONE host function decides which form of conv_igemm_kernel a convolution runs on ----
-// conv_launch_epi executes the plan; a caller that has to know what a launch will do BEFORE it launches (Encoder::explain:
-// may the producer write the compact pool interface, may the image layer ride on this launch; Encoder::encode: may the pool be
-// fused) asks conv_plan about that launch with its request set and reads `ok`.  lrp_conv_plan (include/lrp_hip.h) exposes it.
-enum ConvForm {
-  FORM_PLAIN = 0,   // A and B staged per k-step, 128 x 128 / 128 x 64 / 128 x 32 / 8-wave 256 x 256
-  FORM_SMALL = 1,   // small grids: 64 x 64 tiles, CONV_SMALL_NS-stage k pipeline
-  FORM_HALO = 2,    // resident image (3x3, split operands), 128 x 128 / 128 x 64 / 8-wave 256 x 256
-  FORM_BREG = 3,    // resident image + weights in registers (N <= 64), 128 x 64
-  FORM_POOL = 4,    // FORM_HALO 128 x 128 with tiles of even height and width: the 2x2 max-pool in the dual forward's epilogue
-  FORM_IMG = 5,     // EPI_IMG_STENCIL: 16 x 16 pixel patches
-  FORM_BREG8 = 6,   // FORM_HALO's 8-wave 256 x 256 tile with the weights in registers (dense split-bf16 EPI_MUL, N % 256 == 0)
-  FORM_BREG4 = 7,   // FORM_HALO's 128 x 128 tile with the weights in registers (N % 128 == 0: dense split-bf16 EPI_MUL, interleaved fp16-pair dual forward)
-  FORM_BREG4_POOL = 8   // FORM_POOL's even tiles on the FORM_BREG4 loop
-};
-// one launch, as far as the decision depends on it.  The three requests are what the caller wants this launch to CARRY
-// (ConvArgs::up2_src, img_part, pool_gc): only some forms can, and a request never changes the tile — it is refused instead.
-struct ConvAsk {
-  int epi = EPI_MUL, prec = PREC_FP32, terms = 7;
-  bool gmask = false;
-  int NB = 0, H = 0, W = 0, N = 0, Cin = 0, taps = 9;
-  bool frag = false;         // a fragment-major copy of the weights exists (ConvArgs::wpk_frag)
-  bool join = false;         // ConvArgs::join
-  bool dual_il = false;
-  int split = 0;
-  bool up2_src = false, img_part = false, pool_gc = false;
-  bool dual_mul = false;     // the dual-gate MUL epilogue (ConvArgs::aux_b; Cin = both chains)
-};
-struct ConvPlan {
-  bool ok;                   // false: conv_launch refuses this launch (hipErrorInvalidValue)
-  int form, BM, BN, threads;
-  int M, m_tiles, n_tiles, tw, th, hrows, cols_t, nyh, tpt, epi_generic;   // what the launcher writes into ConvArgs
-};
-
-constexpr int CONV_SMALL_NS = 4;                       // LDS stages of the 64 x 64 tile's k pipeline (4 x 16 KB: two workgroups per CU... see NS)
-// Small grids take 64 x 64 tiles up to a 128-row grid of 128 tiles (4x as many 64 x 64 workgroups = the 512 that are resident
-// at once; beyond that a second round of small tiles costs more than the large tiles' idle CUs [MI355X, one image, 252 large
-// tiles: 115 -> 145 us]); up to twice that, 128 x 64 tiles.
-constexpr long CONV_SMALL_BLOCKS = 128;
-
-// best (tw, th, pitch) for a BM-row tile on an H x W image stack; returns the fraction of MFMA rows doing real work.
-// even: an even number of rows and columns (ConvArgs::pool_gc: 2x2 windows never straddle two tiles)
-inline float conv_halo_geom(int BM, int H, int W, bool even, int& tw, int& th, int& hrows) {
-  const int avail = conv_halo_rows(BM) / HALO_PITCH;   // resident image rows that fit
-  const int step = even ? 2 : 1;
-  float best = 0.f;
-  for (int c = step; c <= HALO_PITCH - 2 && c <= W; c += step) {
-    // th stack rows cross at most ceil((th-1)/H) image boundaries, each costing one separator row
-    int t = even ? (BM / c) & ~1 : BM / c;
-    while (t > 0 && t + 2 + (t - 1 + H - 1) / H > avail) t -= step;
-    if (t < step) continue;
-    const int cols = (W + c - 1) / c;
-    const float u = (float)(t * c) / (float)BM * (float)W / (float)(cols * c);
-    if (u > best + 1e-6f) { best = u; tw = c; th = t; hrows = t + 2 + (t - 1 + H - 1) / H; }
-  }
-  return best;
-}
-
-// Can a reverse launch through a layer (N output columns from Cin channels at H x W) read the compact pool interface at SOME
-// token count?  The part of conv_plan's answer to an up2_src request that depends on neither the grid nor a switch:
-// Encoder::init sizes the compact gates by it.  (N <= 32 never reaches a kernel that reads them; those are the tiny test nets.)
-inline bool conv_compact_shape(int N, int Cin, int H, int W) {
-  if ((Cin & 7) || (H & 1) || (W & 1)) return false;
-  return conv_pick_tile(N).BN == 128 /* pipelined halo tiles */ || (N <= 64 && conv_cinp(Cin) <= 64) /* weights in registers */;
-}
-
-inline ConvPlan conv_plan(const ConvAsk& q, const Switches& s = sw()) {
-  const ConvPlan refused{};
-  ConvPlan p{};
-  const int epi = q.epi, prec = q.prec;
-  const bool mul = epi == EPI_MUL || epi == EPI_MUL_UP2, fwd = epi == EPI_BIAS || epi == EPI_BIAS_RELU || epi == EPI_FWD_DUAL;
-  const bool asked = q.up2_src || q.img_part || q.pool_gc;
-  // the (epilogue, operand format, terms) that exist: prec = PREC_BF16X3 for the reverse-walk epilogues (MUL, MUL_UP2, STORE,
-  // the image stencil) and the forward Z+ / late activation convs (BIAS, BIAS_RELU), always three-term; PREC_F16X2 see TERMS.
-  // This is the list; conv_launch below holds one instantiation per combination accepted here (a template needs its case
-  // written out) and refuses whatever has none: a new combination is stated here and gets its case there.
-  if (epi < EPI_BIAS_RELU || epi > EPI_IMG_STENCIL || prec < PREC_FP32 || prec > PREC_F16X2) return refused;
-  if (prec == PREC_BF16X3 && (q.terms != 7 || epi == EPI_FWD_DUAL)) return refused;
-  if (prec == PREC_F16X2 && (q.terms == 23 ? !(epi == EPI_FWD_DUAL && q.dual_il) : q.terms == 5 ? !mul : epi == EPI_STORE)) return refused;
-  if (q.gmask && (epi != EPI_MUL || prec != PREC_FP32 || asked)) return refused;         // byte-mask gates: exact fp32 EPI_MUL only
-  if (prec != PREC_FP32 && (q.Cin & 7)) return refused;
-  // dual gate (alpha-beta LRP, beta > 0): the dense 3x3 / 1x1 MUL epilogues in exact fp32 and split-bf16, on the staged tiles
-  // (FORM_PLAIN 128 x 128 / 128 x 64 / 128 x 32, FORM_SMALL) and the pipelined 128 x 128 resident-image tile (FORM_HALO).
-  // Not built: the 8-wave tile, the weights-in-registers forms (a fragment-major copy of the concatenated matrix is refused, not
-  // ignored), the compact pool interface, the folded image layer, a residual join, byte-mask gates, fp16 pairs.  Each chain
-  // is half of Cin and must be made of whole 16 B (fp32) / 32 B (split8) groups.
-  if (q.dual_mul && (!mul || prec == PREC_F16X2 || q.terms != 7 || q.gmask || asked || q.frag || q.join || (q.Cin & (prec != PREC_FP32 ? 15 : 7))))
-    return refused;
-  p.M = q.NB * q.H * q.W;
-  p.epi_generic = s.epi_fast ? 0 : 1;
-  if (epi == EPI_IMG_STENCIL) {
-    if (q.taps != 1 || q.N > 64 || (q.Cin & 3) || asked) return refused;
-    p.ok = true; p.form = FORM_IMG; p.BM = 256; p.BN = 64; p.threads = 256;
-    p.n_tiles = 1;
-    p.m_tiles = q.NB * ((q.W + IMG_TILE - 1) / IMG_TILE) * ((q.H + IMG_TILE - 1) / IMG_TILE);
-    return p;
-  }
-  if (mul && (q.N & (prec != PREC_FP32 ? 7 : 3))) return refused;                         // 16 B (fp32) / 32 B (split8) epilogue
-  if ((epi == EPI_BIAS || epi == EPI_BIAS_RELU) && (q.N & 3)) return refused;
-  if (epi == EPI_FWD_DUAL && ((q.split & 3) || (q.dual_il && ((q.split & 31) || q.N != 2 * q.split)))) return refused;
-
-  // ---- the tile ----
-  const long rows = (long)q.NB * q.H * q.W;
-  ConvTile t = conv_pick_tile(q.N);
-  // fp32, few M rows (the per-image forward at batch 32): 128 x 128 tiles leave CUs idle; halve the tile
-  // [MI355X] encode of 32 images 14.06 -> 13.54 ms with the threshold at 2200 blocks (~4 waves of 512 slots)
-  if (prec == PREC_FP32 && t.BN == 128 && (q.N % 64) == 0 && ((rows + 127) / 128) * ((q.N + 127) / 128) < 2200) t = {128, 64};
-  // split operands: the 8-wave 256 x 256 tile (blocked accumulation — the fp16-pair forward — does not fit it).  Measured: a
-  // 256 x 128 tile loses to two 128 x 128 blocks per CU, and one 8-wave block per CU is only worth it when the grid still
-  // fills the chip ~1.5 times over.  The tail of a ResNet identity block (1 tap, K = f channels, three full-width streams
-  // per output element in the epilogue) is bound by those streams, not by staging: two 128 x 128 workgroups per CU overlap
-  // one's epilogue with the other's K loop  [MI355X, ResNet-101 conv4_x: 354 -> 316 us per launch; config 4 -0.9 ms per walk]
-  if (prec != PREC_FP32 && (q.terms == 7 || prec == PREC_F16X2) && !(prec == PREC_F16X2 && fwd) && q.N >= 256 && (q.N % 256) == 0 &&
-      !(epi == EPI_MUL && q.taps == 1 && q.join) && !q.dual_mul && ((rows + 255) / 256) * (q.N / 256) >= 400)
-    t = {256, 256};
-  p.m_tiles = (p.M + t.BM - 1) / t.BM;
-  p.n_tiles = (q.N + t.BN - 1) / t.BN;
-  if (p.M <= 0 || q.N <= 0) {                            // nothing to launch
-    p.ok = true; p.form = FORM_PLAIN; p.BM = t.BM; p.BN = t.BN; p.threads = t.BM == 256 ? 512 : 256;
-    return p;
-  }
-  const long grid = (long)p.m_tiles * p.n_tiles;
-  // the resident-image kernels exist for the split formats' 3x3 MUL and forward epilogues.  LRP_CONV_HALO=2 puts ragged tile
-  // shapes on them (tests); a launch that carries a request is decided at the default fill
-  const int mode = prec != PREC_FP32 && (mul || fwd) && q.taps == 9 ? s.conv_halo : 0;
-  auto resident = [&](bool even, float fill) {
-    int tw = 0, th = 0, hrows = 0;
-    const float u = conv_halo_geom(t.BM, q.H, q.W, even, tw, th, hrows);
-    if (!(u >= fill || (mode == 2 && !asked && u > 0.f))) return false;
-    p.tw = tw; p.th = th; p.hrows = hrows;
-    p.nyh = q.NB * q.H;
-    p.cols_t = (q.W + tw - 1) / tw;
-    p.m_tiles = ((p.nyh + th - 1) / th) * p.cols_t;
-    return true;
-  };
-  auto done = [&](int form) {
-    p.ok = true; p.form = form; p.BM = t.BM; p.BN = t.BN; p.threads = t.BM == 256 ? 512 : 256;
-    return p;
-  };
-
-  if (q.pool_gc) {
-    // pool fused into the dual forward's epilogue: 128 x 128 resident-image tiles of even height and width or nothing (a grid
-    // small enough for the small / mid-size tiles keeps its pool pass); LRP_POOL_FUSED=0 disables
-    if (epi != EPI_FWD_DUAL || prec != PREC_F16X2 || !q.dual_il || q.up2_src || q.img_part || !s.pool_fused || mode <= 0 ||
-        (q.H & 1) || (q.W & 1) || t.BM != 128 || t.BN != 128 || (s.conv_small && grid <= 2 * CONV_SMALL_BLOCKS) || !resident(true, 0.8f))
-      return refused;
-    if (s.conv_breg4 && q.frag && (q.N % 128) == 0 && (q.terms == 7 || q.terms == 23)) return done(FORM_BREG4_POOL);   // (see FORM_BREG4 below)
-    return done(FORM_POOL);
-  }
-  // N <= 64: resident image + weights in registers, no barrier per tap (LRP_CONV_BREG=0 disables).  128-row tiles, whatever
-  // the grid: 256-row tiles, 8 waves, one block per CU, halve the weight traffic per pixel but lose more to the single block
-  // per CU  [MI355X: block1_conv2 bwd 4.19 ms vs 3.83 ms with these 128-row tiles, 3 blocks per CU]
-  if (mul && mode > 0 && s.conv_breg && t.BN == 64 && q.frag && !q.dual_mul && resident(false, 0.9f)) {
-    if (q.img_part) {                                    // image layer folded in: tiles laid out per token (none straddles two tokens)
-      if (prec != PREC_BF16X3 || epi != EPI_MUL || q.N != 64) return refused;
-      p.tpt = (q.H + p.th - 1) / p.th;
-      p.hrows = p.th + 2;                                // (no separator row inside a tile's own rows)
-      p.m_tiles = q.NB * p.tpt * p.cols_t;
-    }
-    // (the compact pool interface needs the window loader: per-token tiles = the folded launch)
-    if (q.up2_src && (!q.img_part || !conv_compact_shape(q.N, q.Cin, q.H, q.W))) return refused;
-    return done(FORM_BREG);
-  }
-  if (q.img_part) return refused;                        // the folded image layer exists for the weights-in-registers kernel only
-  // Small grids (one image, a handful of words: explain_image.py's own call): with 128-row tiles the 14 x 14 / 28 x 28
-  // layers are 16-250 workgroups, each walking K = 2304-4608 alone — the launch takes as long as ONE tile's K loop
-  // [MI355X, B = 1, T = 10: 115-119 us per block4 / block5 launch, forward and backward].  64 x 64 tiles (4 waves of
-  // 32 x 32) put 4x the workgroups on the chip and a k-step costs a quarter of the MFMAs.  Every output element still sees
-  // the same chain of MFMAs in the same k order, so the results are bit-identical to the large tiles (batch invariance).
-  // LRP_CONV_SMALL=0 disables.
-  const bool small = s.conv_small && t.BM == 128 && t.BN >= 64 && grid <= CONV_SMALL_BLOCKS;
-  if (q.up2_src) {
-    // compact pool interface into a pipelined halo kernel (128 x 128 or 8-wave; LRP_UP2_PW=0 disables): the grid must be
-    // one that takes such a kernel without the request, and the loader must fit (below)
-    if (!mul || prec != PREC_BF16X3 || !s.up2_pw || mode <= 0 || t.BN < 128 || small || !conv_compact_shape(q.N, q.Cin, q.H, q.W))
-      return refused;
-  } else if (small) {
-    t = {64, 64};
-    p.m_tiles = (p.M + 63) / 64;
-    p.n_tiles = (q.N + 63) / 64;
-    return done(FORM_SMALL);
-  } else if (s.conv_mid && s.conv_small && t.BM == 128 && t.BN == 128 && (q.N % 64) == 0 && grid <= 2 * CONV_SMALL_BLOCKS) {
-    // In between (at most one large tile per CU, but too many for the 64 x 64 tiles to stay resident): 128 x 64 tiles put two
-    // workgroups on a CU and halve a k-step — same chains, same bits [MI355X, one image, ten words: block4's walk launches
-    // (252 large tiles) 115 -> ~80 us, explain 1.62 -> 1.51 ms].  LRP_CONV_MID=0 disables.
-    t = {128, 64};
-    p.n_tiles = (q.N + 63) / 64;
-  }
-  // N = 64 tiles (TM x TN = 2 x 1 per wave) lose with the resident image: 2 instead of 3 blocks per CU and the
-  // per-tap address work is spread over half as many MFMAs  [MI355X: block1_conv2 bwd 4.5 ms vs 5.2 ms]
-  if (mode > 0 && (t.BN >= 128 || (mode == 2 && t.BN >= 64 && !q.dual_mul)) && resident(false, 0.9f)) {
-    // the loader of the compact pool interface handles two items per thread and channel chunk
-    if (q.up2_src && p.hrows * ((p.tw + 2) / 2 + 1) * 4 > 2 * (t.BM == 256 ? 512 : 256)) return refused;
-    // the 8-wave tile of the dense split-bf16 walk with a fragment-major weight copy: weights in registers, one barrier per
-    // channel chunk instead of one per tap (LRP_CONV_BREG8=0 disables).  A launch that carries a request keeps the pipelined
-    // kernel (its window loader is ordered by the tap barriers); so does the tail of a residual block (ConvArgs::join).
-    if (s.conv_breg8 && t.BM == 256 && prec == PREC_BF16X3 && epi == EPI_MUL && q.terms == 7 && q.frag && !asked && !q.join)
-      return done(FORM_BREG8);
-    // the same loop on the 128 x 128 tile (LRP_CONV_BREG4=0 disables): the dense split-bf16 walk launches and the interleaved
-    // fp16-pair dual forward, N a multiple of the tile.  The walk launch may read the compact pool interface (its window loader
-    // is sequenced by the chunk's steps there, for resident images that span two images at most); img_part and pool_gc never get here.
-    if (s.conv_breg4 && t.BM == 128 && t.BN == 128 && q.frag && (q.N % 128) == 0 && !q.join && !(q.up2_src && p.hrows > q.H) &&
-        ((prec == PREC_BF16X3 && epi == EPI_MUL && q.terms == 7) ||
-         (prec == PREC_F16X2 && epi == EPI_FWD_DUAL && q.dual_il && (q.terms == 7 || q.terms == 23))))
-      return done(FORM_BREG4);
-    return done(FORM_HALO);
-  }
-  if (asked) return refused;                             // only the resident-image kernels read the compact pool interface
-  return done(FORM_PLAIN);
-}
-
-// device table of a.order for this call's token -> image map (see TileOrder); nullptr when the stack order is as good
-inline const int* conv_tile_order(const ConvArgs& a, hipStream_t st) {
-  if (!sw().tile_order || !a.order || !a.row2img_host || a.NB < 2 || a.th < 1) return nullptr;
-  TileOrder& o = *a.order;
-  const int tiles_y = a.tpt > 0 ? a.NB * a.tpt : (a.nyh + a.th - 1) / a.th;
-  const bool same = o.H == a.H && o.th == a.th && o.nyh == a.nyh && o.cols_t == a.cols_t && o.tpt == a.tpt && (int)o.sig.size() == a.NB &&
-                    memcmp(o.sig.data(), a.row2img_host, (size_t)a.NB * sizeof(int)) == 0;
-  if (same) return o.identity ? nullptr : o.dev;
-  o.sig.assign(a.row2img_host, a.row2img_host + a.NB);
-  o.H = a.H; o.th = a.th; o.nyh = a.nyh; o.cols_t = a.cols_t; o.tpt = a.tpt;
-  constexpr int band = 1, strip = 2;                   // row band of `band` tile rows per token; column tiles per strip (measured, round 2)
-  std::vector<long long> key((size_t)tiles_y);
-  for (int ty = 0; ty < tiles_y; ++ty) {
-    int Ym = a.tpt > 0 ? (ty / a.tpt) * a.H + (ty % a.tpt) * a.th + a.th / 2 : ty * a.th + a.th / 2;
-    if (a.tpt > 0 && Ym > (ty / a.tpt + 1) * a.H - 1) Ym = (ty / a.tpt + 1) * a.H - 1;
-    if (Ym > a.nyh - 1) Ym = a.nyh - 1;
-    const int t = Ym / a.H, hpos = Ym - t * a.H;
-    key[ty] = ((long long)o.sig[t] << 42) | ((long long)(hpos / (a.th * band)) << 21) | (long long)t;
-  }
-  std::vector<int> rows((size_t)tiles_y);
-  for (int i = 0; i < tiles_y; ++i) rows[i] = i;
-  std::stable_sort(rows.begin(), rows.end(), [&](int x, int y) { return key[x] < key[y]; });
-  // rows are now (image, band, token); within an image, walk the column strips outermost
-  const int sw = strip > 0 && strip < a.cols_t ? strip : a.cols_t;
-  const size_t m_tiles = (size_t)tiles_y * a.cols_t;
-  std::vector<int> map;
-  map.reserve(m_tiles);
-  for (int r0 = 0; r0 < tiles_y;) {
-    int r1 = r0;
-    while (r1 < tiles_y && (key[rows[r1]] >> 42) == (key[rows[r0]] >> 42)) ++r1;
-    for (int c0 = 0; c0 < a.cols_t; c0 += sw)
-      for (int r = r0; r < r1; ++r)
-        for (int c = c0; c < c0 + sw && c < a.cols_t; ++c) map.push_back(rows[r] * a.cols_t + c);
-    r0 = r1;
-  }
-  o.identity = true;
-  for (size_t i = 0; i < m_tiles; ++i)
-    if (map[i] != (int)i) { o.identity = false; break; }
-  if (o.identity) return nullptr;
-  if (o.ev) (void)hipEventSynchronize(o.ev);            // the staging buffer may still feed the previous upload
-  if (o.cap < m_tiles) {
-    if (o.dev) (void)hipFree(o.dev);
-    if (o.pinned) (void)hipHostFree(o.pinned);
-    o.dev = o.pinned = nullptr;
-    o.cap = 0;
-    if (hipMalloc((void**)&o.dev, m_tiles * sizeof(int)) != hipSuccess ||
-        hipHostMalloc((void**)&o.pinned, m_tiles * sizeof(int), hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      o.sig.clear();                                    // (try again next call; this one runs in stack order)
-      return nullptr;
-    }
-    o.cap = m_tiles;
-  }
-  memcpy(o.pinned, map.data(), m_tiles * sizeof(int));
-  if (!o.ev) (void)hipEventCreateWithFlags(&o.ev, hipEventDisableTiming);
-  if (hipMemcpyAsync(o.dev, o.pinned, m_tiles * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) {
-    (void)hipGetLastError();
-    o.sig.clear();
-    return nullptr;
-  }
-  (void)hipEventRecord(o.ev, st);
-  return o.dev;
-}
-
-// the question conv_plan is asked about the launch of `a`
-inline ConvAsk conv_ask(int epi, int prec, int terms, bool gmask, const ConvArgs& a) {
-  ConvAsk q;
-  q.epi = epi; q.prec = prec; q.terms = terms; q.gmask = gmask;
-  q.NB = a.NB; q.H = a.H; q.W = a.W; q.N = a.N; q.Cin = a.Cin; q.taps = a.taps;
-  q.frag = a.wpk_frag != nullptr; q.join = a.join != nullptr; q.dual_il = a.dual_il != 0; q.split = a.split;
-  q.up2_src = a.up2_src != nullptr; q.img_part = a.img_part != nullptr; q.pool_gc = a.pool_gc != nullptr;
-  q.dual_mul = a.out_b != nullptr;
-  return q;
-}
-inline void conv_apply_plan(const ConvPlan& p, ConvArgs& a) {
-  a.M = p.M; a.m_tiles = p.m_tiles; a.n_tiles = p.n_tiles;
-  a.tw = p.tw; a.th = p.th; a.hrows = p.hrows; a.cols_t = p.cols_t; a.nyh = p.nyh; a.tpt = p.tpt;
-  a.epi_generic = p.epi_generic;
-}
-
-// EPI_IMG_STENCIL: NB = image slots (tokens), H x W = the image; in = S_1 (NB, H, W, Cin); N = 54 <= 64
-template <int PREC>
-inline hipError_t conv_launch_img(ConvArgs a, hipStream_t st) {
-  if (!a.ximg || (PREC == PREC_F16X2 && !a.tok_fac)) return hipErrorInvalidValue;
-  const ConvPlan p = conv_plan(conv_ask(EPI_IMG_STENCIL, PREC, 7, false, a));
-  if (!p.ok) return hipErrorInvalidValue;
-  if (a.NB <= 0) return hipSuccess;
-  conv_apply_plan(p, a);
-  a.tiles_x = (a.W + IMG_TILE - 1) / IMG_TILE;
-  a.tiles_y = (a.H + IMG_TILE - 1) / IMG_TILE;
-  hipLaunchKernelGGL((conv_igemm_kernel<4, 1, 2, 2, EPI_IMG_STENCIL, PREC>), dim3(a.m_tiles), dim3(p.threads), 0, st, a);
-  return hipGetLastError();
-}
-
-template <int EPI, int PREC, int TERMS = 7, bool GMASK = false, bool DG = false>
-inline hipError_t conv_launch_epi(ConvArgs a, hipStream_t st) {
-  static_assert(!GMASK || (EPI == EPI_MUL && PREC == PREC_FP32), "byte-mask gates: exact fp32 EPI_MUL only");
-  constexpr bool MUL = EPI == EPI_MUL || EPI == EPI_MUL_UP2, FWD = EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_FWD_DUAL;
-  static_assert(!DG || (MUL && PREC != PREC_F16X2 && TERMS == 7 && !GMASK), "dual gate: MUL epilogues, exact fp32 or split-bf16");
-  // 1. what only the pointers tell
-  if (DG != (a.out_b != nullptr)) return hipErrorInvalidValue;
-  if (DG && (!a.aux || !a.aux_b || !a.out || a.ostride < a.N || (a.ostride & (PREC != PREC_FP32 ? 7 : 3)) || a.out2s || a.gate_none ||
-             a.gate_binary || a.relu_out))
-    return hipErrorInvalidValue;
-  if (GMASK && (a.out2s || a.gate_none)) return hipErrorInvalidValue;
-  if (PREC == PREC_F16X2 && MUL && (!a.tok_fac || !a.tok_max_out || a.out_plain)) return hipErrorInvalidValue;
-  if (PREC == PREC_F16X2 && FWD && !a.in_unscale) return hipErrorInvalidValue;
-  // 2. the plan
-  const ConvPlan p = conv_plan(conv_ask(EPI, PREC, TERMS, GMASK, a));
-  if (!p.ok) return hipErrorInvalidValue;
-  if (p.M <= 0 || a.N <= 0) return hipSuccess;
-  // (what a request needs besides the form: only a launch that does something is held to it)
-  if (a.pool_gc && (!a.pairs_out || !a.pool_pos)) return hipErrorInvalidValue;
-  if (a.img_part && !a.img_w) return hipErrorInvalidValue;
-  if (a.up2_src && (!a.up2_pairs || !a.up2_gpos)) return hipErrorInvalidValue;
-  conv_apply_plan(p, a);
-  // 3. its kernel
-  const dim3 grid(p.m_tiles * p.n_tiles), block(p.threads);
-  if constexpr (DG) {                                  // the forms conv_plan answers for ConvAsk::dual_mul, nothing else
-    if (p.form == FORM_HALO) {
-      if constexpr (PREC == PREC_BF16X3) {
-        if (p.BM != 128 || p.BN != 128) return hipErrorInvalidValue;
-        a.tile_map = conv_tile_order(a, st);
-        hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, true, false, 7, 2, false, false, true>), grid, block, 0, st, a);
-        return hipGetLastError();
-      }
-      return hipErrorInvalidValue;
-    }
-    if (p.form == FORM_SMALL)
-      hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 1, 1, EPI, PREC, false, false, 7, CONV_SMALL_NS, false, false, true>), grid, block, 0, st, a);
-    else if (p.form != FORM_PLAIN || p.BM != 128)
-      return hipErrorInvalidValue;
-    else if (p.BN == 128)
-      hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, false, false, 7, 2, false, false, true>), grid, block, 0, st, a);
-    else if (p.BN == 64)
-      hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 1, EPI, PREC, false, false, 7, 2, false, false, true>), grid, block, 0, st, a);
-    else
-      hipLaunchKernelGGL((conv_igemm_kernel<4, 1, 1, 1, EPI, PREC, false, false, 7, 2, false, false, true>), grid, block, 0, st, a);
-    return hipGetLastError();
-  }
-  if constexpr (PREC != PREC_FP32 && (MUL || FWD)) {
-    if (p.form == FORM_BREG4 || p.form == FORM_BREG4_POOL) {
-      if constexpr ((EPI == EPI_MUL && PREC == PREC_BF16X3 && TERMS == 7) || (EPI == EPI_FWD_DUAL && PREC == PREC_F16X2 && (TERMS == 7 || TERMS == 23))) {
-        if constexpr (MUL) {
-          a.tile_map = conv_tile_order(a, st);
-          if (a.up2_src) {
-            hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, true, true, TERMS, 2, false, true>), grid, block, 0, st, a);
-            return hipGetLastError();
-          }
-        }
-        hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, true, true, TERMS>), grid, block, 0, st, a);
-        return hipGetLastError();
-      }
-      return hipErrorInvalidValue;
-    }
-    if (p.form == FORM_BREG || p.form == FORM_HALO || p.form == FORM_POOL || p.form == FORM_BREG8) {
-      if constexpr (MUL) {
-        a.tile_map = conv_tile_order(a, st);
-        if constexpr (EPI == EPI_MUL && PREC == PREC_BF16X3 && TERMS == 7) {
-          if (p.form == FORM_BREG8) {
-            hipLaunchKernelGGL((conv_igemm_kernel<2, 4, 4, 2, EPI_MUL, PREC_BF16X3, true, true, 7>), grid, block, 0, st, a);
-            return hipGetLastError();
-          }
-        }
-        if (p.form == FORM_BREG8) return hipErrorInvalidValue;
-        if (p.form == FORM_BREG) {
-          hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 1, EPI, PREC, true, true, TERMS>), grid, block, 0, st, a);
-          return hipGetLastError();
-        }
-      }
-      if (p.BM == 256)
-        hipLaunchKernelGGL((conv_igemm_kernel<2, 4, 4, 2, EPI, PREC, true, false, TERMS>), grid, block, 0, st, a);
-      else if (p.BN == 128)
-        hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, true, false, TERMS>), grid, block, 0, st, a);
-      else
-        hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 1, EPI, PREC, true, false, TERMS>), grid, block, 0, st, a);
-      return hipGetLastError();
-    }
-  }
-  if constexpr (PREC != PREC_FP32) {
-    if (p.BM == 256) {
-      hipLaunchKernelGGL((conv_igemm_kernel<2, 4, 4, 2, EPI, PREC, false, false, TERMS>), grid, block, 0, st, a);
-      return hipGetLastError();
-    }
-  }
-  if (p.form == FORM_SMALL)
-    hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 1, 1, EPI, PREC, false, false, TERMS, CONV_SMALL_NS, GMASK>), grid, block, 0, st, a);
-  else if (p.BN == 128)
-    hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 2, EPI, PREC, false, false, TERMS, 2, GMASK>), grid, block, 0, st, a);
-  else if (p.BN == 64)
-    hipLaunchKernelGGL((conv_igemm_kernel<2, 2, 2, 1, EPI, PREC, false, false, TERMS, 2, GMASK>), grid, block, 0, st, a);
-  else
-    hipLaunchKernelGGL((conv_igemm_kernel<4, 1, 1, 1, EPI, PREC, false, false, TERMS, 2, GMASK>), grid, block, 0, st, a);
-  return hipGetLastError();
-}
-
-// The instantiation table: one case per (epilogue, operand format, terms) that conv_plan accepts — which combinations exist and
-// why is stated there, at the head of conv_plan — and hipErrorInvalidValue for everything else.
-inline hipError_t conv_launch(int epi, const ConvArgs& a, hipStream_t st, int prec = PREC_FP32, int terms = 7) {
-  if (prec == PREC_BF16X3 && terms != 7) return hipErrorInvalidValue;   // (the two-pass three-way split forward product of rounds 1-2 is gone)
-  if (a.out_b) {                                       // dual gate (ConvArgs::aux_b): two epilogues x two operand formats
-    if (terms != 7) return hipErrorInvalidValue;
-    if (prec == PREC_BF16X3) {
-      if (epi == EPI_MUL) return conv_launch_epi<EPI_MUL, PREC_BF16X3, 7, false, true>(a, st);
-      if (epi == EPI_MUL_UP2) return conv_launch_epi<EPI_MUL_UP2, PREC_BF16X3, 7, false, true>(a, st);
-    } else if (prec == PREC_FP32) {
-      if (epi == EPI_MUL) return conv_launch_epi<EPI_MUL, PREC_FP32, 7, false, true>(a, st);
-      if (epi == EPI_MUL_UP2) return conv_launch_epi<EPI_MUL_UP2, PREC_FP32, 7, false, true>(a, st);
-    }
-    return hipErrorInvalidValue;
-  }
-  if (prec == PREC_F16X2) {                            // reverse walk of the VGG encoder only
-    // terms 7: S(hi + lo) x w(hi + lo) without lo*lo — three MFMAs; terms 5: the weights' lo half dropped — two.  Which
-    // layers take which is the caller's rule (Encoder::explain: two-term up to the last pool, measured there).
-    if (terms == 23) {                                 // interleaved dual forward, Z+ column tiles two-term
-      if (epi == EPI_FWD_DUAL && a.dual_il) return conv_launch_epi<EPI_FWD_DUAL, PREC_F16X2, 23>(a, st);
-      return hipErrorInvalidValue;
-    }
-    if (terms == 5) {
-      if (epi == EPI_MUL) return conv_launch_epi<EPI_MUL, PREC_F16X2, 5>(a, st);
-      if (epi == EPI_MUL_UP2) return conv_launch_epi<EPI_MUL_UP2, PREC_F16X2, 5>(a, st);
-      return hipErrorInvalidValue;
-    }
-    switch (epi) {
-      case EPI_MUL: return conv_launch_epi<EPI_MUL, PREC_F16X2>(a, st);
-      case EPI_MUL_UP2: return conv_launch_epi<EPI_MUL_UP2, PREC_F16X2>(a, st);
-      case EPI_IMG_STENCIL: return conv_launch_img<PREC_F16X2>(a, st);
-      case EPI_BIAS_RELU: return conv_launch_epi<EPI_BIAS_RELU, PREC_F16X2>(a, st);   // forward activation conv, fp16 pairs x fp16 pairs
-      case EPI_BIAS: return conv_launch_epi<EPI_BIAS, PREC_F16X2>(a, st);
-      case EPI_FWD_DUAL: return conv_launch_epi<EPI_FWD_DUAL, PREC_F16X2>(a, st);       // a_l and Z+_l from one pass over x_l
-    }
-    return hipErrorInvalidValue;
-  }
-  if (prec == PREC_BF16X3) {
-    switch (epi) {
-      case EPI_MUL: return conv_launch_epi<EPI_MUL, PREC_BF16X3>(a, st);
-      case EPI_MUL_UP2: return conv_launch_epi<EPI_MUL_UP2, PREC_BF16X3>(a, st);
-      case EPI_STORE: return conv_launch_epi<EPI_STORE, PREC_BF16X3>(a, st);
-      case EPI_IMG_STENCIL: return conv_launch_img<PREC_BF16X3>(a, st);
-      case EPI_BIAS: return conv_launch_epi<EPI_BIAS, PREC_BF16X3>(a, st);     // forward Z+ conv (fp32 out)
-      case EPI_BIAS_RELU: return conv_launch_epi<EPI_BIAS_RELU, PREC_BF16X3>(a, st);   // forward a conv of the late layers
-    }
-    return hipErrorInvalidValue;
-  }
-  switch (epi) {
-    case EPI_BIAS_RELU: return conv_launch_epi<EPI_BIAS_RELU, PREC_FP32>(a, st);
-    case EPI_BIAS: return conv_launch_epi<EPI_BIAS, PREC_FP32>(a, st);
-    case EPI_MUL: return conv_launch_epi<EPI_MUL, PREC_FP32>(a, st);
-    case EPI_MUL_UP2: return conv_launch_epi<EPI_MUL_UP2, PREC_FP32>(a, st);
-    case EPI_FWD_DUAL: return conv_launch_epi<EPI_FWD_DUAL, PREC_FP32>(a, st);
-    case EPI_STORE: return conv_launch_epi<EPI_STORE, PREC_FP32>(a, st);
-    case EPI_IMG_STENCIL: return conv_launch_img<PREC_FP32>(a, st);
-  }
-  return hipErrorInvalidValue;
-}
-
-// the ResNet gradient walks' transposed convs: exact fp32, `aux` / `join_gate` are byte masks (conv_igemm_kernel GMASK)
-inline hipError_t conv_launch_grad_mask(const ConvArgs& a, hipStream_t st) {
-  return conv_launch_epi<EPI_MUL, PREC_FP32, 7, true>(a, st);
-}
-
-#endif  // LRP_CONV_KERNEL_ONLY
 
 }  // namespace lrp

@@ -38,7 +38,9 @@
 // returns them to the dense kernels.
 #pragma once
 #include "cnn_kernels.h"
-#include "conv_igemm.h"
+#include "common.h"
+#include "conv_args.h"
+#include "conv_plan.h"
 
 namespace lrp {
 

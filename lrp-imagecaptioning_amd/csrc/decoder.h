@@ -11,7 +11,7 @@
 
 #include "cnn_kernels.h"
 #include "common.h"
-#include "conv_igemm.h"
+#include "conv_launch.h"
 #include "decoder_gridtd_kernels.h"
 #include "decoder_batched_kernels.h"
 #include "decoder_kernels.h"

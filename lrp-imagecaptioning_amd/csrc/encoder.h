@@ -12,7 +12,8 @@
 
 #include "cnn_kernels.h"
 #include "common.h"
-#include "conv_igemm.h"
+#include "conv_launch.h"
+#include "conv_plan.h"
 #include "conv_sparse.h"
 #include "f16_operand.h"
 #include "fwd_mode.h"
@@ -38,10 +39,9 @@ struct ConvLayer {
   DevBuf w_bwd_frag_h;   // ... fragment-major for the weights-in-registers kernel
   DevBuf wbs;         // device record {2^k, 2^-k, norm, k} of the fp16 backward copy's power-of-two scale
   DevBuf w_fwd_il;    // the dual forward matrix with its rows interleaved per 32 channels ([w | w+] side by side): fp32 source of w_fwd_h
-  std::unique_ptr<TileOrder> order{new TileOrder};   // tile-row order of this layer's reverse launch (conv_igemm.h)
-  DevBuf w_bwd_frag;  // w_bwd_s fragment-major (layers whose backward conv has N = cin <= 64, or cin % 256 == 0 with LRP_CONV_BREG8, or cin % 128 == 0 with
-                      // LRP_CONV_BREG4: weights-in-registers kernels)
-  DevBuf w_fwd_frag;  // w_fwd_h fragment-major (interleaved layers with 2 cout % 128 == 0, LRP_CONV_BREG4: the dual forward's weights-in-registers loop)
+  std::unique_ptr<TileOrder> order{new TileOrder};   // tile-row order of this layer's reverse launch (conv_args.h)
+  DevBuf w_bwd_frag;  // w_bwd_s fragment-major: layers whose backward conv can take a weights-in-registers kernel (conv_plan.h conv_frag_forms)
+  DevBuf w_fwd_frag;  // w_fwd_h fragment-major: interleaved layers whose dual forward can (the same function)
   DevBuf bias;
   DevBuf G;        // [max_images][H][W][cout] relevance gate (not for the top layer)
   DevBuf P;        // [max_images][H/2][W/2][cout] pooled activations (pool_after layers; overlapped encode)
@@ -86,7 +86,7 @@ struct Encoder {
   bool features_only = false;
   int prec = PREC_BF16X3;  // arithmetic of the per-token reverse walk (lrp_set_precision); falls back to fp32 for widths % 8 != 0
   const int* row2img_host = nullptr;   // host copy of the NEXT explain call's token -> image map (one-shot; lets the launcher
-                                       // order the tiles so that an image's gates are fetched once, conv_igemm.h TileOrder)
+                                       // order the tiles so that an image's gates are fetched once, conv_args.h TileOrder)
   bool walk_f16 = false;   // LRP_PREC_F16X2 (opt-in): the LRP reverse walk on fp16 pairs, 2 MFMAs per product below the top block.
   // Which layers take the two-MFMA form in that mode (reverse launch through layer li AND its forward denominators Z+_li: the
   // two always go together).  -1 = the built-in rule (every layer up to the last pool whose sums have >= 576 products);
@@ -132,7 +132,7 @@ struct Encoder {
   // a power of two per layer and image), product hi*hi' + hi*lo' + lo*hi' in three MFMAs with blocked fp32 accumulation,
   // weights (w | w+) stacked along N.
   // fp16-pair dual forward with interleaved weight rows: a_l and the gate G_l = a_l / safe(Z+_l) leave the conv's epilogue
-  // together where no pool follows (conv_igemm.h ConvArgs::dual_il) — no Z+ tensor, no gate pass.  LRP_FWD_IL=0: stacked rows.
+  // together where no pool follows (conv_args.h ConvArgs::dual_il) — no Z+ tensor, no gate pass.  LRP_FWD_IL=0: stacked rows.
   static bool fwd_il() { return sw().fwd_il != 0; }
   // the image layer's fp32 dual GEMM with interleaved rows: gate, pairs and maximum leave its epilogue (no gate / absmax / split pass)
   static bool image_layer_interleaved(const ConvLayer& L) { return fwd_il() && !(L.cout & 31) && conv_npad(2 * L.cout) == 2 * L.cout && !L.pool_after; }
@@ -216,7 +216,7 @@ struct Encoder {
   // R_in = alpha act - beta inh with two denominators per layer, Z_act (the Z+ of alpha1beta0) and Z_inh = conv(x+, w-) + b
   // (behind a ReLU or a pool x- = 0: the second conv of each branch contributes its bias only).  The walk carries two chains
   // S+ = R / safe(Z_act), S- = R / safe(Z_inh) as one tensor [S+ | S-] and every launch is ONE GEMM over both:
-  //   c = convT(S+, alpha w+) + convT(S-, -beta w-);  S+' = G+ c,  S-' = G- c        (conv_igemm.h ConvArgs::aux_b)
+  //   c = convT(S+, alpha w+) + convT(S-, -beta w-);  S+' = G+ c,  S-' = G- c        (conv_args.h ConvArgs::aux_b)
   // beta = 0 (the default) is the alpha1beta0 walk: nothing here is allocated, launched or read.
   float ab_alpha = 1.f, ab_beta = 0.f;
   bool ab_on() const { return ab_beta > 0.f; }
@@ -403,14 +403,12 @@ struct Encoder {
     LRP_TRY(mk(L.w_bwd, nb)); LRP_TRY(mk(L.w_bwd_s, nb)); LRP_TRY(mk(L.w_bwd_full, nb)); LRP_TRY(mk(L.w_bwd_full_s, nb));
     LRP_TRY(mk(L.w_bwd_h, nb));
     if (L.sparse_ok() && L.idxp.p) LRP_TRY(mk(L.w_sp, conv_sparse_weight_floats(L.cin, L.cout)));
-    if (conv_npad(L.cin) == 64) { LRP_TRY(mk(L.w_bwd_frag, (size_t)64 * Kb)); LRP_TRY(mk(L.w_bwd_frag_h, (size_t)64 * Kb)); }
-    // the 8-wave weights-in-registers form of the split-bf16 walk (conv_plan FORM_BREG8): a copy as large as w_bwd_s for every layer
-    // whose reverse launch can take it at some token count
-    // (and FORM_BREG4: the 128 x 128 tile's, for N = cin % 128 == 0)
-    else if (((sw().conv_breg8 && (L.cin % 256) == 0) || (sw().conv_breg4 && (L.cin % 128) == 0)) && !(L.cout & 7)) LRP_TRY(mk(L.w_bwd_frag, nb));
+    // fragment-major copies, as large as the matrices they copy (VGG16's w_fwd_frag: 118 MB per handle), for every layer whose
+    // launch can take a weights-in-registers form at some token / image count (conv_plan.h conv_frag_forms)
+    if (conv_frag_forms(EPI_MUL, PREC_BF16X3, 7, L.cin, L.cout, 9)) LRP_TRY(mk(L.w_bwd_frag, nb));
     else L.w_bwd_frag.release();
-    // the dual forward on the same loop: w_fwd_h fragment-major, as large as w_fwd_h (VGG16: 118 MB per handle)
-    if (sw().conv_breg4 && dual_interleaved(L) && (2 * L.cout) % 128 == 0) LRP_TRY(mk(L.w_fwd_frag, (size_t)conv_npad(2 * L.cout) * Kf));
+    if (conv_frag_forms(EPI_MUL, PREC_F16X2, 7, L.cin, L.cout, 9)) LRP_TRY(mk(L.w_bwd_frag_h, nb));
+    if (dual_interleaved(L) && conv_frag_forms(EPI_FWD_DUAL, PREC_F16X2, 7, 2 * L.cout, L.cin, 9)) LRP_TRY(mk(L.w_fwd_frag, (size_t)conv_npad(2 * L.cout) * Kf));
     else L.w_fwd_frag.release();
     if (pack_tmp.bytes < nf * sizeof(float)) LRP_TRY(pack_tmp.alloc(nf * sizeof(float), total));
     return LRP_OK;
@@ -891,7 +889,7 @@ struct Encoder {
       if (L.cout & 7) m.split = m.hook_split = false;   // split8 groups need widths % 8 == 0: exact fp32 otherwise
     for (size_t li = 1; li < layers.size(); ++li)
       if (!layers[li].w_bwd_full_s.p) m.hook_split = false;
-    // LRP_PREC_F16X2: fp16 pairs for S, one fp16 per weight, per-token power-of-two scales (conv_igemm.h PREC_F16X2);
+    // LRP_PREC_F16X2: fp16 pairs for S, one fp16 per weight, per-token power-of-two scales (conv_args.h PREC_F16X2);
     // needs the fused image layer (the chain's scale is undone in its epilogue)
     m.f16 = m.split && walk_f16 && img_fused();
     m.run_prec = m.f16 ? PREC_F16X2 : (m.split || m.hook_split) ? PREC_BF16X3 : PREC_FP32;
@@ -924,7 +922,7 @@ struct Encoder {
     return sw().sparse_pool && Lc.w_sp.p && Lc.idxp.p && Lc.idx_epoch == encode_epoch && !layers[lc - 1].pool_after && m.lrp_split() &&
            sp_scp.p != nullptr;
   }
-  // Compact pool interface (conv_igemm.h ConvArgs::up2_src): the producer of a pooled boundary (layer li, its consumer li - 1)
+  // Compact pool interface (conv_args.h ConvArgs::up2_src): the producer of a pooled boundary (layer li, its consumer li - 1)
   // multiplies with the consumer's COMPACT gate (one value per window and channel, at the producer's resolution) and writes
   // S_c as bf16 pairs at POOLED resolution; the consumer builds its resident image from the pairs and the position bytes:
   // the 4x-expanded, 75 %-zero tensor is neither written nor read.  Only two dense consumers can: the folded weights-in-registers

@@ -12,7 +12,8 @@
 #include <vector>
 
 #include "common.h"
-#include "conv_igemm.h"
+#include "conv_launch.h"
+#include "conv_plan.h"
 #include "conv_sparse.h"
 #include "decoder.h"
 #include "encoder.h"
@@ -506,13 +507,15 @@ int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias
     const bool split = (mode & LRP_CONV_SPLIT_BF16) != 0;   // same op on the split-bf16 MFMA path (fp32 in, fp32 out)
     const bool wreg = (mode & LRP_CONV_WREG) != 0;          // ... with the fragment-major weight copy of the 128 x 128 weights-in-registers loop
     mode &= ~(LRP_CONV_SPLIT_BF16 | LRP_CONV_WREG);
-    if (wreg && !(split && mode == 2 && taps == 9 && (Cin % 128) == 0))
-      return fail(LRP_ERR_UNSUPPORTED, "LRP_CONV_WREG needs LRP_CONV_SPLIT_BF16, mode 2, 9 taps and Cin %% 128 == 0");
     if (mode < 0 || mode > 3) return fail(LRP_ERR_INVALID, "mode must be 0..3");
     if (split && mode == 0) return fail(LRP_ERR_UNSUPPORTED, "the split-bf16 path has no relu epilogue (modes 1..3)");
     const bool bwd = mode >= 2;
     // forward: in has Cin channels, out Cout.  backward: in has Cout channels (S), out Cin (relevance of the input)
     const int inC = bwd ? Cout : Cin, outC = bwd ? Cin : Cout;
+    static const int epi_of_mode[4] = {EPI_BIAS_RELU, EPI_BIAS, EPI_MUL, EPI_MUL_UP2};
+    // (the bit asks for what the default switches would make: LRP_CONV_BREG4=0 then puts the same copy on the pipelined kernel)
+    if (wreg && !(split && (conv_frag_forms(epi_of_mode[mode], PREC_BF16X3, 7, outC, inC, taps, Switches()) & (1u << FORM_BREG4))))
+      return fail(LRP_ERR_UNSUPPORTED, "LRP_CONV_WREG needs LRP_CONV_SPLIT_BF16, mode 2, 9 taps and Cin %% 128 == 0");
     if (inC % 4 != 0) return fail(LRP_ERR_UNSUPPORTED, "input channels must be a multiple of 4");
     if (split && ((inC & 7) || (bwd && (outC & 7)))) return fail(LRP_ERR_UNSUPPORTED, "split-bf16 path: channels must be multiples of 8");
     const int Np = conv_npad(outC), K = taps * conv_cinp(inC);
@@ -523,8 +526,8 @@ int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias
       const size_t nw8 = (size_t)Np * K / 8;
       LRP_TRY(wsplit.alloc(wdev.bytes, nullptr));
       hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(nw8)), dim3(256), 0, st, wdev.as<float>(), wsplit.as<float>(), nw8);
-      // weights-in-registers variants of the backward convs: N <= 64, and the 8-wave tile's N % 256 == 0 (LRP_CONV_BREG8)
-      if (bwd && taps == 9 && (Np == 64 || (sw().conv_breg8 && (outC % 256) == 0) || wreg)) {
+      // weights-in-registers variants of the backward convs
+      if (wreg || conv_frag_forms(epi_of_mode[mode], PREC_BF16X3, 7, outC, inC, taps)) {
         LRP_TRY(wfrag.alloc((size_t)Np * K * sizeof(float), nullptr));
         hipLaunchKernelGGL(pack_frag_dev_kernel, dim3(stream_grid((size_t)conv_cinp(inC) / 32 * 9 * 8 * Np)), dim3(256), 0, st,
                            wsplit.as<float>(), wfrag.as<float>(), conv_cinp(inC), Np);
@@ -548,7 +551,6 @@ int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias
     } else if (!aux_dev) {
       return fail(LRP_ERR_INVALID, "aux (gate) required for backward modes");
     }
-    static const int epi_of_mode[4] = {EPI_BIAS_RELU, EPI_BIAS, EPI_MUL, EPI_MUL_UP2};
     if (split && !wreg && ca.wpk_frag) {                   // without the bit a 128 x 128 launch keeps the pipelined kernel
       const ConvPlan p = conv_plan(conv_ask(epi_of_mode[mode], PREC_BF16X3, 7, false, ca));
       if (p.ok && p.form == FORM_BREG4) ca.wpk_frag = nullptr;

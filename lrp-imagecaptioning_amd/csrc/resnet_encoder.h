@@ -14,7 +14,8 @@
 #include <vector>
 
 #include "common.h"
-#include "conv_igemm.h"
+#include "conv_launch.h"
+#include "conv_plan.h"
 #include "f16_operand.h"
 #include "resnet_kernels.h"
 
@@ -281,7 +282,7 @@ struct ResNetEncoder {
     const int ui = (int)(&u - units.data());
     if (u.w_dual_h.p && slots_in && prec == PREC_BF16X3) {
       // the same single pass on the fp16 MFMA: x and (w | w+) as fp16 pairs, the product in three MFMAs with blocked
-      // fp32 accumulation (conv_igemm.h PREC_F16X2) — fp32-grade, ~2.5x the fp32 matrix rate
+      // fp32 accumulation (conv_args.h PREC_F16X2) — fp32-grade, ~2.5x the fp32 matrix rate
       const size_t n8 = (size_t)B * u.Hout * u.Wout * u.cin / 8;
       hipLaunchKernelGGL(split_h_scaled_kernel, dim3(stream_grid(n8)), dim3(256), 0, st, xin, fxs.as<float>(), n8, slots_in,
                          act_unscale.as<float>() + ui, u.wds.as<float>());
@@ -289,7 +290,7 @@ struct ResNetEncoder {
       ca.in = fxs.as<float>(); ca.wpk = u.w_dual_h.as<float>(); ca.N = 2 * u.cout; ca.split = u.cout; ca.dual_norelu = 1;
       ca.out = fc.as<float>(); ca.out2 = fz.as<float>(); ca.in_unscale = act_unscale.as<float>() + ui;
       if (u.dual_il) {
-        // BatchNorm, ReLU and the unit's gate in the conv's epilogue: c and Z+ never go to memory (conv_igemm.h dual_gate = 2)
+        // BatchNorm, ReLU and the unit's gate in the conv's epilogue: c and Z+ never go to memory (conv_args.h ConvArgs::dual_gate = 2)
         ca.dual_il = 1; ca.dual_gate = 2; ca.bn_gamma = u.gamma.as<float>(); ca.bn_beta = u.beta.as<float>();
         ca.bn_mean = u.mean.as<float>(); ca.bn_var = u.var.as<float>(); ca.bn_eps = RN_BN_EPS; ca.bn_relu = u.relu ? 1 : 0;
         ca.out = act; ca.out2 = u.gate.as<float>(); ca.act_max_out = slots_out;

@@ -16,7 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "conv_igemm.h"
+#include "conv_args.h"
 #include "train_gemm.h"
 
 namespace lrp {

@@ -4,7 +4,7 @@ take) and tests/test_gpu_conv_forms.py (GPU: every case against a float64 convol
 
 A case is (NB, H, W, Cin, Cout, taps, mode, split) as lrp_op_conv takes them — mode 0 bias + relu, 1 bias, 2 gate multiply of the
 transposed conv, 3 the same through a 2x2 pool; the backward modes map Cout channels of S to Cin output columns — plus the
-switches it runs under and the form and tile conv_plan (csrc/conv_igemm.h) must answer under them."""
+switches it runs under and the form and tile conv_plan (csrc/conv_plan.h) must answer under them."""
 from collections import namedtuple
 
 from lrp_imagecaptioning_amd import _capi as K
@@ -82,7 +82,7 @@ def case_id(c):
 
 
 def conv_npad(n):
-    """csrc/conv_igemm.h conv_npad: the output columns padded to the tile width their count picks"""
+    """csrc/conv_plan.h conv_npad: the output columns padded to the tile width their count picks"""
     bn = 128 if n > 64 else 64 if n > 32 else 32
     return -(-n // bn) * bn
 

@@ -1,4 +1,4 @@
-"""The operator cases of tests/conv_cases.py against the launch plan (csrc/conv_igemm.h conv_plan, through lrp_conv_plan): every
+"""The operator cases of tests/conv_cases.py against the launch plan (csrc/conv_plan.h conv_plan, through lrp_conv_plan): every
 case takes the form and tile it states under its switches, and together the cases reach every (operand format, epilogue, form,
 tile) that lrp_op_conv can take — so a change of the plan that moves a case onto another kernel, or a case that is dropped,
 shows here and not as a silent loss of what tests/test_gpu_conv_forms.py compares with float64.  Host arithmetic only — no GPU."""

@@ -1,4 +1,4 @@
-"""The launch plan of the implicit-GEMM convolution (csrc/conv_igemm.h conv_plan, through lrp_conv_plan, ABI v8): which form and
+"""The launch plan of the implicit-GEMM convolution (csrc/conv_plan.h conv_plan, through lrp_conv_plan, ABI v8): which form and
 tile a launch takes, and which launches may carry the compact pool interface, the folded image layer or the fused pool.
 Host arithmetic only — no GPU.  The launcher executes this plan and Encoder::explain / Encoder::encode ask the same function,
 so what is asserted here is what runs."""

@@ -1,4 +1,4 @@
-"""The launch plan of the dual-gate epilogue (csrc/conv_igemm.h conv_plan with ConvAsk::dual_mul, through lrp_conv_plan and
+"""The launch plan of the dual-gate epilogue (csrc/conv_plan.h conv_plan with ConvAsk::dual_mul, through lrp_conv_plan and
 LRP_PLAN_DUAL_MUL): which form and tile every reverse launch of the alpha-beta walk (beta > 0) takes, what the plan refuses for
 it, and that the operator table tests/conv_ab_cases.py reaches every form it can answer.  Pure host arithmetic: no GPU."""
 import pytest

@@ -1,4 +1,4 @@
-"""The launch plan's FORM_BREG4 / FORM_BREG4_POOL (csrc/conv_igemm.h conv_plan, through lrp_conv_plan): the launches on the 4-wave
+"""The launch plan's FORM_BREG4 / FORM_BREG4_POOL (csrc/conv_plan.h conv_plan, through lrp_conv_plan): the launches on the 4-wave
 128 x 128 resident-image tile whose N is a multiple of the tile — the dense split-bf16 EPI_MUL launches of the reverse walk and
 the interleaved fp16-pair dual forward — take their weights from registers when a fragment-major copy of the weights exists.
 Tile and geometry stay those of FORM_HALO / FORM_POOL.  Host arithmetic only — no GPU."""

@@ -1,4 +1,4 @@
-"""The launch plan's FORM_BREG8 (csrc/conv_igemm.h conv_plan, through lrp_conv_plan): the dense split-bf16 EPI_MUL launches of the
+"""The launch plan's FORM_BREG8 (csrc/conv_plan.h conv_plan, through lrp_conv_plan): the dense split-bf16 EPI_MUL launches of the
 reverse walk that take the 8-wave 256 x 256 tile run it with the weights in registers when a fragment-major copy of the weights
 exists.  Host arithmetic only — no GPU."""
 import pytest
