@@ -90,7 +90,12 @@ __device__ __forceinline__ void split8_store(const float* r, float* dst) {   // 
   d[0] = __builtin_bit_cast(u32x4, hi);
   d[1] = __builtin_bit_cast(u32x4, lo);
 }
-
+// exact small-integer division (operands < 2^22): float estimate + one fix-up step
+__device__ __forceinline__ void conv_divmod(int x, int d, float inv, int& q, int& r) {
+  q = (int)(((float)x + 0.5f) * inv);
+  r = x - q * d;
+  if (r < 0) { --q; r += d; } else if (r >= d) { ++q; r -= d; }
+}
 
 // Halo-resident launches walk the image STACK (all tokens on top of each other) tile row by tile row.  The gate a tile is
 // multiplied with belongs to the token's IMAGE, and with several tokens per image (10 words per caption) the same gate rows

@@ -10,8 +10,9 @@
 // Template axes: tile (WM, WN, TM, TN), epilogue EPI, operand arithmetic PREC (exact fp32 MFMA | split-bf16),
 // HALO (3x3: A tile + halo resident in LDS for all 9 taps), BREG (weights in registers, no barrier per tap: N <= 64, and the 8-wave tile),
 // TERMS (which partial products of the split operands are issued).  DESIGN.md 4.1 has the measurements behind each.
-// This file is the kernel alone: its arguments are conv_args.h, which instantiations exist and which one a launch takes is
-// conv_plan.h, the launchers are conv_launch.h.  A translation unit that wants ONE instantiation (ISA inspection) includes this file.
+// This file is the kernel alone: its arguments are conv_args.h, its tile constants (ConvKernelTraits) and the pieces of its body
+// that stand on their own conv_tile.h, which instantiations exist and which one a launch takes is conv_plan.h, the launchers are
+// conv_launch.h.  A translation unit that wants ONE instantiation (ISA inspection) includes this file.
 //
 // GEMM view: D[m][n] = sum_k A[m][k] * B[k][n],  m = output pixel (NHWC row),
 // n = output channel, k = (tap, input channel).  A is gathered on the fly
@@ -30,6 +31,7 @@
 
 #include "conv_args.h"
 #include "conv_plan.h"
+#include "conv_tile.h"
 
 namespace lrp {
 
@@ -40,7 +42,6 @@ __device__ __attribute__((aligned(16))) float lrp_zero_page[4] = {0.f, 0.f, 0.f,
 
 // waves per SIMD the register allocator must leave room for: LDS already limits a CU to
 // floor(160 KB / LDS per block) blocks of NW waves
-constexpr int conv_min_waves(int NW, int TM, int TN, bool halo = false) { return NW == 8 || halo ? 2 : (TM * TN >= 4 ? 2 : 3); }
 
 // BREG (HALO, bf16x3, N <= 64 layers): the weights never touch LDS.  With K <= 2 x 32 channels per group the whole A
 // operand of a group is resident (both LDS buffers hold one 32-channel chunk each), and the B fragments of a
@@ -68,32 +69,10 @@ template <int WM, int WN, int TM, int TN, int EPI, int PREC, bool HALO = false, 
           bool GMASK = false, bool PW = false, bool DG = false>
 __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 : NS > 2 ? 2 : conv_min_waves(WM * WN, TM, TN, HALO)) void conv_igemm_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (the buffer-resource builtins are device-only)
-  constexpr int NW = WM * WN, NT = 64 * NW;           // waves / threads per block (4 or 8 waves)
-  constexpr bool SPLIT = PREC != PREC_FP32;            // operands in split8 form (bf16 or fp16 pairs): 16 k per MFMA
-  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-  constexpr int AP = BM / 8 / NW, BP = BN / 8 / NW;   // 1 KiB (8-row) DMA pieces per wave and chunk
-  constexpr int HR = conv_halo_rows(BM);              // HALO: LDS rows (pixels) of the resident image
-  constexpr int ABUF = (HALO ? HR : BM) * LDS_STRIDE;
-  constexpr int STAGE = ABUF + (BREG ? 0 : BN) * LDS_STRIDE;
-  constexpr bool BREG8 = BREG && NW == 8;              // the 8-wave 256 x 256 tile with its weights in registers (see the main loop)
-  constexpr bool BREG4 = BREG && NW == 4 && TN == 2;   // the same loop on the 4-wave 128 x 128 tile (FORM_BREG4: walk and dual forward)
-  constexpr bool BREGC = BREG8 || BREG4;               // weights in registers, one barrier per channel CHUNK
-  static_assert(!BREG || (HALO && SPLIT && (BREGC || BM * BN <= 2 * STAGE)), "BREG needs the resident image");
-  // which tiles, forms and epilogues go together — BREG8 / BREG4: the dense split-bf16 walk (and, BREG4, the fp16-pair dual forward);
-  // PW: that walk on the BREG4 loop; DG: the MUL epilogues of the 4-wave staged / pipelined tiles — is conv_plan.h's table
-  static_assert(conv_kernel_instantiated(WM, WN, TM, TN, HALO, BREG, NS, PW, EPI, PREC, TERMS, GMASK, DG), "no such instantiation: conv_plan.h conv_kernel_exists");
-  static_assert((BM / 8) % NW == 0 && (BN / 8) % NW == 0, "pieces must divide over the waves");
-  static_assert(!HALO || EPI != EPI_STORE, "the image layer is a 1-tap GEMM");
-  static_assert(NS == 2 || (NS > 2 && !HALO && !BREG), "deeper staging exists for the plain (non-resident) A path only");
-  constexpr int DPC = AP + BP;                         // DMA instructions per wave and chunk (plain staging)
-  static_assert((NS - 2) * DPC <= 63, "vmcnt is a 6-bit counter");
+  using T = ConvKernelTraits<WM, WN, TM, TN, EPI, PREC, HALO, BREG, TERMS, NS, GMASK, PW, DG>;
   // BREG8: no B stage, so LDS is the two resident images or one 128-row C slab of the epilogue, whichever is larger (128 KB)
   // BREG4: the two resident images + a spare slot per wave (52 KB) or the epilogue's whole 128 x 128 C tile (64 KB; 80 KB pipelined)
-  constexpr int SMEM = BREG8   ? (2 * STAGE > BM / 2 * BN ? 2 * STAGE : BM / 2 * BN)
-                       : BREG4 ? (2 * STAGE + NW * 8 * LDS_STRIDE > BM * BN ? 2 * STAGE + NW * 8 * LDS_STRIDE : BM * BN)
-                               : NS * STAGE;
-  constexpr int CSLAB = BREGC ? SMEM : 2 * STAGE;      // floats the epilogue's C slab may take
-  __shared__ __attribute__((aligned(16))) float smem[SMEM];
+  __shared__ __attribute__((aligned(16))) float smem[T::SMEM];
 
   // ---- XCD-aware block remap: the n_tiles blocks that share an A tile get
   // consecutive logical ids and land on one XCD (one L2) [bijective form].
@@ -104,7 +83,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
   }
   const int mt = logical / a.n_tiles, nt = logical - mt * a.n_tiles;
-  const int m0 = mt * BM, n0 = nt * BN;
+  const int m0 = mt * T::BM, n0 = nt * T::BN;
   int pn = 0, py0 = 0, px0 = 0;                        // EPI_IMG_STENCIL: image slot and first OUTPUT pixel of the patch
   if constexpr (EPI == EPI_IMG_STENCIL) {
     const int tpi = a.tiles_x * a.tiles_y;
@@ -126,12 +105,6 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
       img0 = Y0 / a.H;
     }
   }
-  // exact small-integer division (operands < 2^22): float estimate + one fix-up step
-  auto divmod = [](int x, int d, float inv, int& q, int& r) {
-    q = (int)(((float)x + 0.5f) * inv);
-    r = x - q * d;
-    if (r < 0) { --q; r += d; } else if (r >= d) { ++q; r -= d; }
-  };
   // first stack row that is NOT this tile's any more: the end of the stack, or of the tile's token when tiles are per token
   const int yend = HALO ? (a.tpt > 0 && (img0 + 1) * a.H < a.nyh ? (img0 + 1) * a.H : a.nyh) : 0;
   const float inv_tw = HALO ? 1.0f / (float)a.tw : 0.f, inv_H = HALO ? 1.0f / (float)a.H : 0.f;
@@ -176,11 +149,11 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
   constexpr int OOB = (int)0x80000000;                 // >= any num_records used here
   constexpr int RSRC_FLAGS = 0x00020000;               // raw buffer, DATA_FORMAT_32 (gfx9 V# dword 3)
   const __amdgpu_buffer_rsrc_t rsB =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(a.wpk + (size_t)n0 * K), 0, BN * K * 4, RSRC_FLAGS);
-  int bvo[BP];
+      __builtin_amdgcn_make_buffer_rsrc((void*)(a.wpk + (size_t)n0 * K), 0, T::BN * K * 4, RSRC_FLAGS);
+  int bvo[T::BP];
 #pragma unroll
-  for (int p = 0; p < BP; ++p) {
-    const int r = (wave_s * BP + p) * 8 + prow;
+  for (int p = 0; p < T::BP; ++p) {
+    const int r = (wave_s * T::BP + p) * 8 + prow;
     bvo[p] = (r * K + ((pchk ^ ((r >> 1) & 7)) << 2)) * 4;
   }
   // A, non-HALO: descriptor base = pixel (m0 - W - 1), so that every tap offset is >= 0
@@ -188,16 +161,16 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
                        : EPI == EPI_IMG_STENCIL ? a.in + (size_t)pn * HW * a.Cin
                             : a.in + ((long)m0 - (a.taps == 1 ? 0 : a.W + 1)) * (long)a.Cin;
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)abase, 0, 0x7FFFFFFF, RSRC_FLAGS);
-  int avo[HALO ? 1 : AP];
-  unsigned amask[HALO ? 1 : AP];
-  int acf[HALO ? 1 : AP];                              // first channel (within a 32-chunk) of this lane's 16 B
+  int avo[HALO ? 1 : T::AP];
+  unsigned amask[HALO ? 1 : T::AP];
+  int acf[HALO ? 1 : T::AP];                              // first channel (within a 32-chunk) of this lane's 16 B
   if constexpr (!HALO) {
-    const int rfirst = wave_s * AP * 8 + prow;         // tile row of piece p = 0
+    const int rfirst = wave_s * T::AP * 8 + prow;         // tile row of piece p = 0
     const int mfirst = m0 + rfirst;
     int rem = mfirst % HW;
     int h = rem / a.W, w = rem - h * a.W;
 #pragma unroll
-    for (int p = 0; p < AP; ++p) {
+    for (int p = 0; p < T::AP; ++p) {
       const int r = rfirst + 8 * p, m = m0 + r;
       unsigned mask = 0;
       if constexpr (EPI == EPI_IMG_STENCIL) {
@@ -206,7 +179,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
         const bool ok = y >= 0 && y < a.H && x >= 0 && x < a.W;
         amask[p] = ok ? 1u : 0u;
         const int lc = (pchk ^ ((r >> 1) & 7)) << 2;
-        acf[p] = SPLIT ? ((lc >> 3) << 3) : lc;
+        acf[p] = T::SPLIT ? ((lc >> 3) << 3) : lc;
         avo[p] = ok ? ((y * a.W + x) * a.Cin + lc) * 4 : 0;
         continue;
       }
@@ -221,7 +194,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
       }
       amask[p] = mask;
       const int lc = (pchk ^ ((r >> 1) & 7)) << 2;
-      acf[p] = SPLIT ? ((lc >> 3) << 3) : lc;   // 4*chunk (fp32) or 8*(chunk/2) (split8 group)
+      acf[p] = T::SPLIT ? ((lc >> 3) << 3) : lc;   // 4*chunk (fp32) or 8*(chunk/2) (split8 group)
       avo[p] = (r * a.Cin + lc) * 4;
       if (a.taps != 1) {                                  // next piece: 8 pixels further
         w += 8;
@@ -240,10 +213,10 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     const int hy = p >> 1, hx = (p & 1) * 8 + prow;
     const int E = Y0 + img0 - 1 + hy;
     int n, h;
-    divmod(E < 0 ? 0 : E, a.H + 1, inv_H1, n, h);
+    conv_divmod(E < 0 ? 0 : E, a.H + 1, inv_H1, n, h);
     const int x = x0 - 1 + hx;
     const int lc = (pchk ^ (((hy * a.tw + hx - 1) >> 1) & 7)) << 2;   // halo swizzle, see set_tap
-    const int cfirst = SPLIT ? ((lc >> 3) << 3) : lc;
+    const int cfirst = T::SPLIT ? ((lc >> 3) << 3) : lc;
     const bool ok = live && E >= 0 && h < a.H && n < a.NB && hx < a.tw + 2 && x >= 0 && x < a.W && (chunk << 5) + cfirst < a.Cin;
     HaloPiece r;
     r.vo = ok ? (x * a.Cin + lc) * 4 : OOB;
@@ -253,17 +226,17 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     return r;
   };
   auto fire_halo_piece = [&](const HaloPiece& hp, int p, int abuf) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lptr_t)(smem + abuf * STAGE + p * 8 * LDS_STRIDE), 16, hp.vo, hp.so, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lptr_t)(smem + abuf * T::STAGE + p * 8 * LDS_STRIDE), 16, hp.vo, hp.so, 0, 0);
   };
   // prep: per-lane offsets of the chunk at (tap, cc) (cheap VALU, placed BEFORE the barrier where it overlaps the
   // MFMAs still in flight); fire: the DMA instructions themselves, right after the barrier.
-  struct ChunkPrep { int avo[HALO ? 1 : AP]; int aso, bso; };
+  struct ChunkPrep { int avo[HALO ? 1 : T::AP]; int aso, bso; };
   auto prep_chunk = [&](bool live) {
     ChunkPrep c;
     const int c0 = cc << 5;
     if constexpr (!HALO) {
 #pragma unroll
-      for (int p = 0; p < AP; ++p) {
+      for (int p = 0; p < T::AP; ++p) {
         const bool ok = live && ((amask[p] >> tap) & 1u) && (c0 + acf[p] < a.Cin);
         c.avo[p] = ok ? avo[p] : OOB;
       }
@@ -277,27 +250,25 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     return c;
   };
   auto fire_chunk = [&](const ChunkPrep& c, int buf) {
-    float* As = smem + buf * STAGE;
-    float* Bs = As + ABUF;
+    float* As = smem + buf * T::STAGE;
+    float* Bs = As + T::ABUF;
     if constexpr (!HALO) {
 #pragma unroll
-      for (int p = 0; p < AP; ++p)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lptr_t)(As + (wave_s * AP + p) * 8 * LDS_STRIDE), 16, c.avo[p], c.aso, 0, 0);
+      for (int p = 0; p < T::AP; ++p)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lptr_t)(As + (wave_s * T::AP + p) * 8 * LDS_STRIDE), 16, c.avo[p], c.aso, 0, 0);
     }
 #pragma unroll
-    for (int p = 0; p < BP; ++p)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lptr_t)(Bs + (wave_s * BP + p) * 8 * LDS_STRIDE), 16, bvo[p], c.bso, 0, 0);
+    for (int p = 0; p < T::BP; ++p)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB, (lptr_t)(Bs + (wave_s * T::BP + p) * 8 * LDS_STRIDE), 16, bvo[p], c.bso, 0, 0);
   };
 
   // Two-level (blocked) summation: the MFMA is a strictly k-ordered fp32 fma chain, so a
   // K = 4608 reduction in ONE accumulator carries ~sqrt(K) ulp of round-off.  Every FLUSH
   // chunks (256 k) the running block is folded into `tot` and restarted: chains of 256 + K/256.
   // (bf16x3: one MFMA already folds 16 k internally and the chain is K/16 long — no second level.)
-  constexpr int FLUSH = 8;
   // (the fp16-pair forward, whose three-term product is fp32-grade, is blocked as well: without the second level its
   //  accumulator's 3 x K/16 roundings would be the largest error left)
-  constexpr bool BLOCKED = PREC == PREC_FP32 || (PREC == PREC_F16X2 && (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU || EPI == EPI_FWD_DUAL));
-  f32x16 acc[TM][TN], tot[BLOCKED ? TM : 1][BLOCKED ? TN : 1];
+  f32x16 acc[TM][TN], tot[T::BLOCKED ? TM : 1][T::BLOCKED ? TN : 1];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -305,7 +276,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         acc[i][j][r] = 0.f;
-        if constexpr (BLOCKED) tot[i][j][r] = 0.f;
+        if constexpr (T::BLOCKED) tot[i][j][r] = 0.f;
       }
 
   // DMA schedule: chunk kc+2 is launched right AFTER the barrier of iteration kc (the barrier proves every wave
@@ -324,7 +295,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
   typedef unsigned u32x2w __attribute__((ext_vector_type(2)));
   struct PwItem { u32x4 hi, lo; u32x2w q; };
   // (BREG4: the same items, sequenced by the chunk's steps instead — see its loop)
-  [[maybe_unused]] const bool pw = BREG4 ? PW : HALO && !BREG && PREC == PREC_BF16X3 && a.up2_src != nullptr;
+  [[maybe_unused]] const bool pw = T::BREG4 ? PW : HALO && !BREG && PREC == PREC_BF16X3 && a.up2_src != nullptr;
   [[maybe_unused]] int pw_wx0 = 0, pw_nwx = 1, pw_items = 0, pw_ri0 = 0, pw_ri1 = 0;
   [[maybe_unused]] float pw_inv_nwx = 1.f;
   if constexpr (HALO && (!BREG || PW) && PREC == PREC_BF16X3) {
@@ -342,12 +313,12 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     PwPos r;
     r.g = it & 3;
     int wxi;
-    divmod(it >> 2, pw_nwx, pw_inv_nwx, r.hy, wxi);
+    conv_divmod(it >> 2, pw_nwx, pw_inv_nwx, r.hy, wxi);
     r.wx = pw_wx0 + wxi;
     const int Hp = a.H >> 1, Wp = a.W >> 1;
     const int E = Y0 + img0 - 1 + r.hy;
     int n, h;
-    divmod(E < 0 ? 0 : E, a.H + 1, inv_H1, n, h);
+    conv_divmod(E < 0 ? 0 : E, a.H + 1, inv_H1, n, h);
     r.valid = it < pw_items && E >= 0 && h < a.H && n < a.NB && r.wx >= 0 && r.wx < Wp && (chunk << 5) + r.g * 8 < a.Cin;
     r.dy = h & 1;
     // unconditional loads from a clamped (always valid) place; an invalid item's values are zeroed at the store
@@ -384,18 +355,18 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
       }
       const int row = r.hy * HALO_PITCH + hx;
       const int swzu = ((r.hy * a.tw + hx - 1) >> 1) & 7;
-      const int dst = abuf * STAGE + row * LDS_STRIDE + (((2 * r.g) ^ swzu) << 2);
+      const int dst = abuf * T::STAGE + row * LDS_STRIDE + (((2 * r.g) ^ swzu) << 2);
       *reinterpret_cast<u32x4*>(smem + dst) = mh;
       *reinterpret_cast<u32x4*>(smem + (dst ^ 4)) = ml;
     }
   };
   [[maybe_unused]] PwItem pwi{};
-  if constexpr (BREGC) {
+  if constexpr (T::BREGC) {
     if constexpr (PW) {
       pw_load(pwi, tid, 0); pw_store(pwi, tid, 0, 0);
-      if (tid + NT < pw_items) { pw_load(pwi, tid + NT, 0); pw_store(pwi, tid + NT, 0, 0); }
+      if (tid + T::NT < pw_items) { pw_load(pwi, tid + T::NT, 0); pw_store(pwi, tid + T::NT, 0, 0); }
     } else
-    for (int p = wave_s; p < halo_np; p += NW) fire_halo_piece(prep_halo_piece(p, 0, true), p, 0);   // chunk 0; chunk 1 follows in the loop
+    for (int p = wave_s; p < halo_np; p += T::NW) fire_halo_piece(prep_halo_piece(p, 0, true), p, 0);   // chunk 0; chunk 1 follows in the loop
   } else if constexpr (BREG) {
     if (PREC == PREC_BF16X3 && a.up2_src) {
       // compact pool interface (pairs of S_c, per-token tiles: the launcher checks): item = (window of the resident image,
@@ -410,17 +381,17 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
       const float inv_nwx = 1.0f / (float)nwx;
       constexpr int UW = 2;                                // items in flight per thread (2 x 16 B + 8 B of loads each)
       typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
-      for (int it0 = tid; it0 < items; it0 += NT * UW) {
+      for (int it0 = tid; it0 < items; it0 += T::NT * UW) {
         f32x4 pv[UW][2];
         u32x2_ qv[UW];
         int wyv[UW], wxv[UW], cgv[UW];
         bool okv[UW];
 #pragma unroll
         for (int u = 0; u < UW; ++u) {
-          const int item = it0 + u * NT;
+          const int item = it0 + u * T::NT;
           const int cg = item & 7, wdx = item >> 3;
           int wr, wc;
-          divmod(wdx, nwx, inv_nwx, wr, wc);
+          conv_divmod(wdx, nwx, inv_nwx, wr, wc);
           const int wy = wy0 + wr, wx = wx0 + wc;
           cgv[u] = cg; wyv[u] = wy; wxv[u] = wx;
           okv[u] = item < items && wy >= 0 && wy < Hp && wx >= 0 && wx < Wp && cg * 8 < a.Cin;
@@ -434,7 +405,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
         }
 #pragma unroll
         for (int u = 0; u < UW; ++u) {
-          if (it0 + u * NT >= items) continue;
+          if (it0 + u * T::NT >= items) continue;
           const u32x4 z4u = {0u, 0u, 0u, 0u};
           const u32x4 hiw = okv[u] ? __builtin_bit_cast(u32x4, pv[u][0]) : z4u;   // S_c as [hi8 | lo8]
           const u32x4 low = okv[u] ? __builtin_bit_cast(u32x4, pv[u][1]) : z4u;
@@ -453,14 +424,14 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
             }
             const int row = hy * HALO_PITCH + hx;
             const int swzu = ((hy * a.tw + hx - 1) >> 1) & 7;
-            const int dst = (cgv[u] >> 2) * STAGE + row * LDS_STRIDE + (((2 * (cgv[u] & 3)) ^ swzu) << 2);
+            const int dst = (cgv[u] >> 2) * T::STAGE + row * LDS_STRIDE + (((2 * (cgv[u] & 3)) ^ swzu) << 2);
             *reinterpret_cast<u32x4*>(smem + dst) = mh;
             *reinterpret_cast<u32x4*>(smem + (dst ^ 4)) = ml;
           }
         }
       }
     } else
-    for (int p = wave_s; p < halo_np; p += NW) {         // channel chunks 0 and 1 -> LDS buffers 0 and 1
+    for (int p = wave_s; p < halo_np; p += T::NW) {         // channel chunks 0 and 1 -> LDS buffers 0 and 1
       fire_halo_piece(prep_halo_piece(p, 0, true), p, 0);
       fire_halo_piece(prep_halo_piece(p, 1, cpt > 1), p, 1);
     }
@@ -468,9 +439,9 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     if constexpr (HALO) {
       if (pw) {
         pw_load(pwi, tid, 0); pw_store(pwi, tid, 0, 0);
-        if (tid + NT < pw_items) { pw_load(pwi, tid + NT, 0); pw_store(pwi, tid + NT, 0, 0); }
+        if (tid + T::NT < pw_items) { pw_load(pwi, tid + T::NT, 0); pw_store(pwi, tid + T::NT, 0, 0); }
       } else {
-        for (int p = wave_s; p < halo_np; p += NW) fire_halo_piece(prep_halo_piece(p, 0, true), p, 0);
+        for (int p = wave_s; p < halo_np; p += T::NW) fire_halo_piece(prep_halo_piece(p, 0, true), p, 0);
         if (wave_s < halo_np) fire_halo_piece(prep_halo_piece(wave_s, 1, cpt > 1), wave_s, 1);   // slot 0 of chunk 1 (see the loop)
       }
     }
@@ -479,25 +450,10 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
 #pragma unroll
     for (int s_ = 2; s_ < NS; ++s_) fire_chunk(prep_chunk(nk > s_), s_);
   }
-  // hipcc gives __syncthreads() an lgkmcnt(0) only; the LDS-DMA completes on vmcnt, so the wait is explicit
-  auto dma_landed_barrier = [] {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  };
-  // NS > 2: the oldest chunk in flight has landed (the NS - 2 younger ones may still be on their way)
-  auto dma_oldest_landed_barrier = [] {
-    if constexpr (NS > 2) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 2) * ((WM * TM * 32 + WN * TN * 32) / 8 / (WM * WN))) : "memory");   // (NS - 2) x DPC
-      __syncthreads();
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
-  };
-  dma_oldest_landed_barrier();
+  conv_dma_oldest_landed_barrier<T>();
 
   const int a_off = HALO ? 0 : (wm * TM * 32 + (lane & 31)) * LDS_STRIDE;
-  const int b_off = ABUF + (wn * TN * 32 + (lane & 31)) * LDS_STRIDE;
+  const int b_off = T::ABUF + (wn * TN * 32 + (lane & 31)) * LDS_STRIDE;
   // HALO: per A fragment row, the LDS row of its pixel in the resident image (padding rows of the tile read
   // pixel (1,1): their C rows are never stored), and per tap the float offset of its first 16 B chunk
   int fbase[HALO ? TM : 1], fu[HALO ? TM : 1], faddr[HALO ? TM : 1];
@@ -507,9 +463,9 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     for (int i = 0; i < TM; ++i) {
       const int r = (wm * TM + i) * 32 + (lane & 31);
       int ty, tx, n_, h_;
-      divmod(r, a.tw, inv_tw, ty, tx);
+      conv_divmod(r, a.tw, inv_tw, ty, tx);
       const int Y = Y0 + ty;
-      divmod(Y, a.H, inv_H, n_, h_);
+      conv_divmod(Y, a.H, inv_H, n_, h_);
       const bool ok = r < a.th * a.tw && Y < yend && x0 + tx < a.W;
       const int hy = ok ? ty + 1 + n_ - img0 : 1, hx = ok ? tx + 1 : 1;
       fbase[i] = hy * HALO_PITCH + hx;
@@ -528,7 +484,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
 #pragma unroll
     for (int i = 0; i < (HALO ? TM : 0); ++i) {
       const int row = fbase[i] + tsh, u = fu[i] + ush;
-      faddr[i] = row * LDS_STRIDE + ((((SPLIT ? 2 : 1) * hh_) ^ ((u >> 1) & 7)) << 2);
+      faddr[i] = row * LDS_STRIDE + ((((T::SPLIT ? 2 : 1) * hh_) ^ ((u >> 1) & 7)) << 2);
     }
   };
   // Fragment registers are double-buffered one step ahead, and the first fragments of the NEXT
@@ -537,12 +493,11 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
   // before the barrier => the DMA of the following iteration cannot race them.)
   // fp32 : 4 steps of 8 k per chunk; lane-half h consumes k = 4h+s -> logical chunk 2kk+h.
   // bf16x3: 2 steps of 16 k; lane-half h consumes k = 8h+j -> split8 group 2s+h = chunks 4s+2h (hi), 4s+2h+1 (lo).
-  constexpr int NSTEP = SPLIT ? 2 : 4;
   const int swz = (lane >> 1) & 7, hh = lane >> 5;
   int koff[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q)
-    koff[q] = SPLIT ? (((4 * (q >> 1) + 2 * hh + (q & 1)) ^ swz) << 2)     // q = 2*step + {hi,lo}
+    koff[q] = T::SPLIT ? (((4 * (q >> 1) + 2 * hh + (q & 1)) ^ swz) << 2)     // q = 2*step + {hi,lo}
                                   : (((2 * q + hh) ^ swz) << 2);
   // TERMS bit 4: is column tile j of this wave an ODD 32-column block of the matrix (interleaved rows: Z+)?  By the block's place
   // in the MATRIX, not in the wave: with one column tile per wave (the 64 x 64, 128 x 64 and 128 x 32 tiles) the wave's own index
@@ -550,20 +505,20 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
   // fp16-pair walk, depended on which tile the batch size picked.  Two column tiles per wave: j & 1, known at compile time.
   const int ztile0 = TN % 2 == 0 ? 0 : ((n0 >> 5) + (wave_s % WN) * TN) & 1;
   auto z_tile = [&](int j) { return ((ztile0 + j) & 1) != 0; };
-  struct Frag { u32x4 a[SPLIT ? 2 * TM : TM], b[SPLIT ? 2 * TN : TN]; };
+  struct Frag { u32x4 a[T::SPLIT ? 2 * TM : TM], b[T::SPLIT ? 2 * TN : TN]; };
   // HALO: A addresses come from faddr[] (set_tap); chunk c ^ swizzle = (c0 ^ swizzle) ^ (c - c0) for disjoint bits
   auto read_frag = [&](Frag& f, const float* Ab, const float* Bb, int st) {
     if constexpr (HALO) {
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
-        if constexpr (SPLIT) {
+        if constexpr (T::SPLIT) {
           f.a[2 * i] = *reinterpret_cast<const u32x4*>(Ab + (faddr[i] ^ ((4 * st) << 2)));
           f.a[2 * i + 1] = *reinterpret_cast<const u32x4*>(Ab + (faddr[i] ^ ((4 * st + 1) << 2)));
         } else {
           f.a[i] = *reinterpret_cast<const u32x4*>(Ab + (faddr[i] ^ ((2 * st) << 2)));
         }
       }
-    } else if constexpr (SPLIT) {
+    } else if constexpr (T::SPLIT) {
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         f.a[2 * i] = *reinterpret_cast<const u32x4*>(Ab + i * 32 * LDS_STRIDE + koff[2 * st]);
@@ -573,7 +528,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
 #pragma unroll
       for (int i = 0; i < TM; ++i) f.a[i] = *reinterpret_cast<const u32x4*>(Ab + i * 32 * LDS_STRIDE + koff[st]);
     }
-    if constexpr (SPLIT) {
+    if constexpr (T::SPLIT) {
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         f.b[2 * j] = *reinterpret_cast<const u32x4*>(Bb + j * 32 * LDS_STRIDE + koff[2 * st]);
@@ -622,7 +577,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     }
   };
 
-  if constexpr (BREGC) {
+  if constexpr (T::BREGC) {
     // ---- 8-wave tile (and, BREG4, the 4-wave 128 x 128 tile), weights in registers.  The pipelined form of this tile ends every tap in vmcnt(0) + a workgroup
     // barrier (the weight stage it vacates is refilled for tap + 2), which keeps all eight waves — both waves of every SIMD —
     // in the same phase.  Here B never touches LDS: a wave takes its 64 columns' fragments of one k16 step with four coalesced
@@ -640,12 +595,10 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     // odd column tiles (Z+; three loads per step, six outstanding), and the blocked accumulation folds acc into tot behind the
     // same taps as the pipelined loop — kc = 9 chunk + tap, (kc & 7) == 7 <=> ((chunk + tap) & 7) == 7 — under a wave-uniform
     // branch that holds VALU work only, so the weight waits stay counted.
-    static_assert(NSTEP == 2 && SMEM >= 2 * STAGE + NW * 8 * LDS_STRIDE, "split operands; a spare LDS slot per wave behind the two images");
-    static_assert(6 * NW * 8 >= HR, "six piece slots per wave cover the resident image");
     // does column tile j read the weights' lo half (mfma_frag's rule)
     auto uses_lo = [](int j) { return PREC != PREC_F16X2 || ((TERMS & 2) != 0 && !((TERMS & 16) != 0 && (j & 1))); };
     constexpr int LPS = PREC == PREC_F16X2 && (TERMS & 16) != 0 ? 2 * TN - TN / 2 : 2 * TN;   // weight loads per k16 step
-    const int NF = a.n_tiles * BN;                       // columns of the fragment-major copy (N % BN == 0)
+    const int NF = a.n_tiles * T::BN;                       // columns of the fragment-major copy (N % BN == 0)
     const int nsteps = 2 * nk;
     const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void*)a.wpk_frag, 0, nsteps * 4 * NF * 16, RSRC_FLAGS);
     const int fvo = ((lane >> 5) * NF + n0 + wn * TN * 32 + (lane & 31)) * 16;
@@ -670,8 +623,8 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     }
     for (int c = 0; c < cpt; ++c) {
       const int cb = c & 1;
-      const float* Ab = smem + cb * STAGE;
-      const float* An = smem + (cb ^ 1) * STAGE;
+      const float* Ab = smem + cb * T::STAGE;
+      const float* An = smem + (cb ^ 1) * T::STAGE;
       // the per-tap fragment addresses and most of a piece's offsets do not depend on the chunk: left alone, hipcc hoists all of
       // them (nine taps x four row blocks, six pieces) out of the chunk loop and spills them.  They are a few VALU ops each.
 #pragma unroll
@@ -686,13 +639,13 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
           // lgkmcnt(0) in front of the next hand-over covers the writes.  (Unconditional: a dead item loads from a clamped
           // address and writes nothing or zeros, a chunk past the end zeros — like the dead pieces below.)
           if (s == 0) pw_load(pwi, tid, c + 1);
-          if (s == 6) { pw_store(pwi, tid, c + 1, cb ^ 1); pw_load(pwi, tid + NT, c + 1); }
-          if (s == 12) pw_store(pwi, tid + NT, c + 1, cb ^ 1);
+          if (s == 6) { pw_store(pwi, tid, c + 1, cb ^ 1); pw_load(pwi, tid + T::NT, c + 1); }
+          if (s == 12) pw_store(pwi, tid + T::NT, c + 1, cb ^ 1);
         } else if (s % 3 == 0) {                         // piece slot s / 3 of chunk c + 1 -> the buffer chunk c - 1 was read from
-          const int p = (s / 3) * NW + wave_s;
+          const int p = (s / 3) * T::NW + wave_s;
           const bool livep = p < halo_np;
           const HaloPiece hp = prep_halo_piece(p, c + 1, livep && c + 1 < cpt);
-          const int dst = livep ? (cb ^ 1) * STAGE + p * 8 * LDS_STRIDE : 2 * STAGE + wave_s * 8 * LDS_STRIDE;   // (dead piece: zeros into the spare slot)
+          const int dst = livep ? (cb ^ 1) * T::STAGE + p * 8 * LDS_STRIDE : 2 * T::STAGE + wave_s * 8 * LDS_STRIDE;   // (dead piece: zeros into the spare slot)
           __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lptr_t)(smem + dst), 16, hp.vo, hp.so, 0, 0);
         }
         if (s == 17) {
@@ -731,8 +684,8 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
           aq[2 * i + 1] = *reinterpret_cast<const u32x4*>(Ax + (faddr[i] ^ ((4 * nst + 1) << 2)));
           __builtin_amdgcn_sched_barrier(0);             // (pinned: hoisted above the MFMAs the reads would need a second register set)
         }
-        if constexpr (BLOCKED) {
-          if ((s & 1) && ((c + (s >> 1)) & (FLUSH - 1)) == FLUSH - 1) {   // behind tap s >> 1: where the pipelined loop flushes
+        if constexpr (T::BLOCKED) {
+          if ((s & 1) && ((c + (s >> 1)) & (T::FLUSH - 1)) == T::FLUSH - 1) {   // behind tap s >> 1: where the pipelined loop flushes
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -746,17 +699,16 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
       }
     }
   } else if constexpr (BREG) {
-    static_assert(NSTEP == 2, "bf16x3");
     // B fragments of (kc = chunk*9 + tap): [step][hi|lo] x TN, one 16 B load each
-    const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void*)a.wpk_frag, 0, nk * 8 * BN * 16, RSRC_FLAGS);
-    const int fvo = ((lane >> 5) * BN + wn * TN * 32 + (lane & 31)) * 16;
+    const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void*)a.wpk_frag, 0, nk * 8 * T::BN * 16, RSRC_FLAGS);
+    const int fvo = ((lane >> 5) * T::BN + wn * TN * 32 + (lane & 31)) * 16;
     struct BFrag { u32x4 v[4 * TN]; };
     auto load_b = [&](BFrag& b, int kc) {
 #pragma unroll
       for (int q = 0; q < 4; q += ((PREC == PREC_F16X2 && !(TERMS & 2)) ? 2 : 1))    // q = 2*step + (0 hi | 1 lo); two-term fp16: hi only
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-          b.v[q * TN + j] = __builtin_amdgcn_raw_buffer_load_b128(rsF, fvo + j * 32 * 16, ((kc * 4 + q) * 2) * BN * 16, 0);
+          b.v[q * TN + j] = __builtin_amdgcn_raw_buffer_load_b128(rsF, fvo + j * 32 * 16, ((kc * 4 + q) * 2) * T::BN * 16, 0);
     };
     struct AFrag { u32x4 v[4 * TM]; };                   // [step][hi|lo] x TM
     auto load_a = [&](AFrag& f, const float* Ab) {
@@ -795,11 +747,11 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     for (int g = 0; g < cpt; g += 2) {                   // groups of two channel chunks = the two LDS buffers
       if (g > 0) {
         __syncthreads();                                 // everyone is done with the previous group's image
-        for (int p = wave_s; p < halo_np; p += NW) {
+        for (int p = wave_s; p < halo_np; p += T::NW) {
           fire_halo_piece(prep_halo_piece(p, g, true), p, 0);
           fire_halo_piece(prep_halo_piece(p, g + 1, g + 1 < cpt), p, 1);
         }
-        dma_landed_barrier();
+        conv_dma_landed_barrier();
       }
       const int ng = (g + 2 <= cpt ? 2 : 1) * 9;         // (tap, chunk) pairs of this group
       set_tap(0);
@@ -813,14 +765,14 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
         if (++nt == 9) { nt = 0; ++nc; }
         load_b(b1, kc + 1 < nk ? kc + 1 : nk - 1);
         set_tap(nt);
-        load_a(a1, smem + (nc > 1 ? 1 : nc) * STAGE);
+        load_a(a1, smem + (nc > 1 ? 1 : nc) * T::STAGE);
         __builtin_amdgcn_sched_barrier(0);               // keep the prefetches ABOVE the 12 MFMAs they hide behind
         mma(a0, b0);
         __builtin_amdgcn_sched_barrier(0);
         if (++nt == 9) { nt = 0; ++nc; }
         load_b(b0, kc + 2 < nk ? kc + 2 : nk - 1);
         set_tap(nt);
-        load_a(a0, smem + (nc > 1 ? 1 : nc) * STAGE);
+        load_a(a0, smem + (nc > 1 ? 1 : nc) * T::STAGE);
         __builtin_amdgcn_sched_barrier(0);
         if (q + 1 < ng) mma(a1, b1);
         __builtin_amdgcn_sched_barrier(0);
@@ -838,9 +790,9 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     const bool more = (kc + 1) < nk;
     const int nbuf = buf + 1 == NS ? 0 : buf + 1;      // stage of chunk kc + 1
     const int abuf = HALO ? (ccc & 1) : buf;
-    const float* Ab = smem + abuf * STAGE + a_off;
-    const float* Bb = smem + buf * STAGE + b_off;
-    if constexpr (NSTEP == 4) {
+    const float* Ab = smem + abuf * T::STAGE + a_off;
+    const float* Bb = smem + buf * T::STAGE + b_off;
+    if constexpr (T::NSTEP == 4) {
       read_frag(f1, Ab, Bb, 1);
       mfma_frag(f0);                                   // step 0
       read_frag(f0, Ab, Bb, 2);
@@ -862,21 +814,21 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
         hpp = -1;
         if (ccc + 1 < cpt) {
           if (ctap == 5) pw_store(pwi, tid, ccc + 1, (ccc & 1) ^ 1);
-          else if (ctap == 7) pw_store(pwi, tid + NT, ccc + 1, (ccc & 1) ^ 1);
+          else if (ctap == 7) pw_store(pwi, tid + T::NT, ccc + 1, (ccc & 1) ^ 1);
         }
       } else {
-        hpp = ctap * NW + wave_s;
+        hpp = ctap * T::NW + wave_s;
         if (hpp >= halo_np) hpp = -1;
         hp = prep_halo_piece(hpp < 0 ? 0 : hpp, ccc + 1, more && ccc + 1 < cpt);
       }
     }
-    dma_oldest_landed_barrier();                       // reads of `buf` done everywhere; DMA of chunk kc+1 landed
+    conv_dma_oldest_landed_barrier<T>();                       // reads of `buf` done everywhere; DMA of chunk kc+1 landed
     fire_chunk(cp, buf);
     if constexpr (HALO) {
       if (pw) {
         if (ccc + 1 < cpt) {
           if (ctap == 3) pw_load(pwi, tid, ccc + 1);
-          else if (ctap == 5 && tid + NT < pw_items) pw_load(pwi, tid + NT, ccc + 1);
+          else if (ctap == 5 && tid + T::NT < pw_items) pw_load(pwi, tid + T::NT, ccc + 1);
         }
       } else if (hpp >= 0 && more && ccc + 1 < cpt) fire_halo_piece(hp, hpp, (ccc & 1) ^ 1);
     }
@@ -889,13 +841,13 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     // (on the last iteration this reads a stale buffer into registers nobody uses)
     if constexpr (HALO) {
       set_tap(ctap);
-      read_frag(f0, smem + (ccc & 1) * STAGE, smem + nbuf * STAGE + b_off, 0);
+      read_frag(f0, smem + (ccc & 1) * T::STAGE, smem + nbuf * T::STAGE + b_off, 0);
     } else {
-      read_frag(f0, smem + nbuf * STAGE + a_off, smem + nbuf * STAGE + b_off, 0);
+      read_frag(f0, smem + nbuf * T::STAGE + a_off, smem + nbuf * T::STAGE + b_off, 0);
     }
     mfma_frag(f1);                                     // last step
-    if constexpr (BLOCKED) {
-      if ((kc & (FLUSH - 1)) == FLUSH - 1) {
+    if constexpr (T::BLOCKED) {
+      if ((kc & (T::FLUSH - 1)) == T::FLUSH - 1) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -908,8 +860,8 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     }
     buf = nbuf;
   }
-  dma_landed_barrier();                                // LDS is reused by the epilogue (and the tail DMAs of zeros are in)
-  if constexpr (BLOCKED) {
+  conv_dma_landed_barrier();                                // LDS is reused by the epilogue (and the tail DMAs of zeros are in)
+  if constexpr (T::BLOCKED) {
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -919,7 +871,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
   // ---- image layer folded into this layer's epilogue (ConvArgs::img_part)
   if constexpr (BREG && EPI == EPI_MUL && PREC == PREC_BF16X3 && TM == 2 && TN == 1 && WM == 2 && WN == 2) {
     if (a.img_part) {
-      static_assert(2 * STAGE >= 128 * 64, "the C tile (then S_1 as pairs, in place; then T) inside the staging LDS");
+      static_assert(2 * T::STAGE >= 128 * 64, "the C tile (then S_1 as pairs, in place; then T) inside the staging LDS");
       constexpr int TS2 = 57;                             // T row stride (54 used; odd: conflict-free column reads)
       float* Cs = smem;                                   // [128 rows][64] fp32 — rewritten IN PLACE as S_1's bf16 pairs:
       // row r keeps its 256 B = [chunk 0 | chunk 1] x 128 B, 16 B slots XOR-swizzled with (r >> 1) & 7 like an A tile.  The eight
@@ -932,15 +884,15 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
       f32x4 gq[4][2];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const int item = tid + k * NT, row = item >> 3, g = item & 7;
+        const int item = tid + k * T::NT, row = item >> 3, g = item & 7;
         int ty, tx;
-        divmod(row, a.tw, inv_tw2, ty, tx);
+        conv_divmod(row, a.tw, inv_tw2, ty, tx);
         const int Y = Y0 + ty, w = x0 + tx;
         const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
         gq[k][0] = gq[k][1] = z4;                         // (gate = 0 for padding rows / pixels outside the image)
         if (row < a.th * a.tw && Y < yend && w < a.W) {
           int n, h;
-          divmod(Y, a.H, inv_H, n, h);
+          conv_divmod(Y, a.H, inv_H, n, h);
           const int img = a.row2img ? a.row2img[n] : n;
           const float* gp = a.aux + ((size_t)img * HW + h * a.W + w) * a.N + g * 8;
           gq[k][0] = *reinterpret_cast<const f32x4*>(gp); gq[k][1] = *reinterpret_cast<const f32x4*>(gp + 4);
@@ -967,7 +919,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
       __syncthreads();
 #pragma unroll
       for (int k = 0; k < 4; ++k) {                       // 128 rows x 8 channel groups = 1024 items over 256 threads
-        const int item = tid + k * NT, row = item >> 3, g = item & 7;
+        const int item = tid + k * T::NT, row = item >> 3, g = item & 7;
         float* rp = Cs + row * 64 + (g >> 2) * 32;
         const f32x4 c0 = *reinterpret_cast<const f32x4*>(rp + (g & 3) * 8), c1 = *reinterpret_cast<const f32x4*>(rp + (g & 3) * 8 + 4);
         float v[8];
@@ -1023,7 +975,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
       // sum over taps of T[source = (oy - (kh - 1), ox - (kw - 1))][tap] for the sources this tile owns
       const int RW = a.tw + 2, npos = (a.th + 2) * RW;
       const int mtp_ = a.tile_map ? a.tile_map[mt] : mt;
-      for (int p = tid; p < npos; p += NT) {
+      for (int p = tid; p < npos; p += T::NT) {
         const int ry = p / RW, rx = p - ry * RW, oy = ry - 1, ox = rx - 1;
         float pos[3] = {0.f, 0.f, 0.f}, neg[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -1048,8 +1000,8 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
   if constexpr (EPI == EPI_IMG_STENCIL) {
     // row stride 65 floats: with 64 (= 256 B = one sweep of the banks) the stencil's reads of one column across the
     // 64 pixels of a wave all hit the same bank  [MI355X: SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.75]
-    constexpr int TS = BN + 1;
-    static_assert(BM == IMG_PATCH * IMG_PATCH && BN == 64 && BM * TS <= 2 * STAGE, "patch tile is 256 x 64");
+    constexpr int TS = T::BN + 1;
+    static_assert(T::BM == IMG_PATCH * IMG_PATCH && T::BN == 64 && T::BM * TS <= 2 * T::STAGE, "patch tile is 256 x 64");
     float* Ts = smem;                                   // T of the patch: [256 patch pixels][64 columns (54 used)]
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -1061,7 +1013,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
       }
     __syncthreads();
     // R_img[p] = sum_tap T[p - d(tap)][tap], d = (kh - 1, kw - 1): patch pixel (oy + 2 - kh, ox + 2 - kw)
-    for (int o = tid; o < IMG_TILE * IMG_TILE; o += NT) {
+    for (int o = tid; o < IMG_TILE * IMG_TILE; o += T::NT) {
       const int oy = o / IMG_TILE, ox = o - oy * IMG_TILE;
       const int y = py0 + oy, x = px0 + ox;
       if (y >= a.H || x >= a.W) continue;
@@ -1090,26 +1042,20 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     return;
   } else if constexpr (EPI != EPI_STORE) {
     // The C tile goes through the staging LDS in NH row slabs (a 256-row tile does not fit at once).
-    constexpr int NH = (BM * BN + CSLAB - 1) / CSLAB;
-    constexpr int RH = BM / NH;                         // rows per slab
-    static_assert(BM % NH == 0 && RH % (TM * 32) == 0 && RH * BN <= CSLAB, "slab must hold whole wave tiles");
     float* Cs = smem;
-    constexpr bool SPLIT_OUT = SPLIT && (EPI == EPI_MUL || EPI == EPI_MUL_UP2);
-    constexpr int CW = SPLIT_OUT ? 8 : 4;               // channels per thread (split8 output is written per group)
-    constexpr int C4 = BN / CW, RPP = NT / C4;
-    const int c4 = tid % C4, rin = tid / C4;
-    const int col = n0 + c4 * CW;
+    const int c4 = tid % T::C4, rin = tid / T::C4;
+    const int col = n0 + c4 * T::CW;
     const int tn0 = m0 / HW, tp0 = m0 - tn0 * HW;
     const float invw = 1.0f / (float)a.W;
     // tile row lr -> linear NHWC row / image slot n / pixel (h, w); false = padding row
     auto locate = [&](int lr, int& row, int& n, int& h, int& w) -> bool {
       if constexpr (HALO) {
         int ty, tx;
-        divmod(lr, a.tw, inv_tw, ty, tx);
+        conv_divmod(lr, a.tw, inv_tw, ty, tx);
         const int Y = Y0 + ty;
         w = x0 + tx;
         if (lr >= a.th * a.tw || Y >= yend || w >= a.W) return false;
-        divmod(Y, a.H, inv_H, n, h);
+        conv_divmod(Y, a.H, inv_H, n, h);
         row = Y * a.W + w;
         return true;
       } else {
@@ -1131,26 +1077,25 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     // (the slots live in the staging LDS behind the C slab where the tile shape leaves room — every tile does except the
     // non-halo 128 x 128 / 256 x 256 ones, which fall back to the per-wave global atomic; LDS is sized to the byte:
     // two 128 x 128 halo blocks fill the CU's 160 KB exactly)
-    constexpr bool TMAX_LDS = PREC == PREC_F16X2 && RH * BN + 16 <= 2 * STAGE;
-    unsigned* tmax_s = reinterpret_cast<unsigned*>(smem + RH * BN);
+    unsigned* tmax_s = reinterpret_cast<unsigned*>(smem + T::RH * T::BN);
     const int tok_first = HALO ? img0 : tn0;
-    if constexpr (TMAX_LDS) {
+    if constexpr (T::TMAX_LDS) {
       if (tid < 16) tmax_s[tid] = 0u;                   // (ordered before its first use by the barrier that publishes the C slab)
     }
 #pragma unroll 1
-    for (int hf = 0; hf < NH; ++hf) {
+    for (int hf = 0; hf < T::NH; ++hf) {
       if (hf) __syncthreads();                          // previous slab fully consumed
-      if ((wm * TM * 32) / RH == hf) {
+      if ((wm * TM * 32) / T::RH == hf) {
         // a wave's TM x 32 rows lie inside ONE slab (static_assert above), so their position in the slab does not depend on hf:
         // one base address + compile-time offsets (written with `- hf * RH` hipcc kept sixteen addresses per wave alive across
         // the main loop of the 8-wave tile, spilled them, and reloaded each behind its own s_waitcnt vmcnt(0))
-        float* cw = Cs + (((wm * TM * 32) % RH) + 4 * (lane >> 5)) * BN + wn * TN * 32 + (lane & 31);
+        float* cw = Cs + (((wm * TM * 32) % T::RH) + 4 * (lane >> 5)) * T::BN + wn * TN * 32 + (lane & 31);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int r = 0; r < 16; ++r)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) cw[(i * 32 + (r & 3) + 8 * (r >> 2)) * BN + j * 32] = acc[i][j][r];
+            for (int j = 0; j < TN; ++j) cw[(i * 32 + (r & 3) + 8 * (r >> 2)) * T::BN + j * 32] = acc[i][j][r];
       }
       __syncthreads();
       if constexpr (EPI == EPI_BIAS || EPI == EPI_BIAS_RELU) {
@@ -1161,11 +1106,11 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
           float omax = 0.f;
           if constexpr (PREC == PREC_F16X2) unscale = *a.in_unscale;
 #pragma unroll 4
-          for (int ps = 0; ps < RH / RPP; ++ps) {
-            const int ll = rin + ps * RPP;
+          for (int ps = 0; ps < T::RH / T::RPP; ++ps) {
+            const int ll = rin + ps * T::RPP;
             int row, n_, h_, w_;
-            if (!locate(hf * RH + ll, row, n_, h_, w_)) continue;
-            f32x4 v = *reinterpret_cast<const f32x4*>(Cs + ll * BN + c4 * 4);
+            if (!locate(hf * T::RH + ll, row, n_, h_, w_)) continue;
+            f32x4 v = *reinterpret_cast<const f32x4*>(Cs + ll * T::BN + c4 * 4);
             if constexpr (PREC == PREC_F16X2) v *= unscale;
             v += bv;
             if (a.addend) v += *reinterpret_cast<const f32x4*>(a.addend + (size_t)row * a.N + col);   // second pass of a product
@@ -1198,18 +1143,18 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
           const int p = c4 * 4, half = (p >> 5) & 1;
           const int ch = (n0 >> 1) + (p >> 6) * 32 + (p & 31);
           bool pooled = false;
-          if constexpr (HALO && NH == 1 && PREC == PREC_F16X2) {
+          if constexpr (HALO && T::NH == 1 && PREC == PREC_F16X2) {
             if (a.pool_gc) {
               // ---- fused 2x2 max-pool (ConvArgs::pool_gc): item = (window of the tile, channel quad)
               pooled = true;
-              const int wpr = a.tw >> 1, nq = BN / 8;     // windows per tile row; channel quads of the tile's c columns
+              const int wpr = a.tw >> 1, nq = T::BN / 8;     // windows per tile row; channel quads of the tile's c columns
               const int nitems = (a.th >> 1) * wpr * nq;
               const float inv_wpr = 1.0f / (float)wpr;
               float pmax0 = 0.f, pmax1 = 0.f;
-              for (int it = tid; it < nitems; it += NT) {
+              for (int it = tid; it < nitems; it += T::NT) {
                 const int q = it % nq, win = it / nq;
                 int wy, wx;
-                divmod(win, wpr, inv_wpr, wy, wx);
+                conv_divmod(win, wpr, inv_wpr, wy, wx);
                 const int cq = 4 * q, chp = (n0 >> 1) + cq, pcp = (cq >> 5) * 64 + (cq & 31);
                 const int r00 = (2 * wy) * a.tw + 2 * wx;
                 int row = 0, n_ = 0, h_ = 0, w_ = 0;
@@ -1223,7 +1168,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
                 unsigned posw = 0u;
 #pragma unroll
                 for (int pp = 0; pp < 4; ++pp) {
-                  const float* cr = Cs + (r00 + (pp >> 1) * a.tw + (pp & 1)) * BN + pcp;
+                  const float* cr = Cs + (r00 + (pp >> 1) * a.tw + (pp & 1)) * T::BN + pcp;
                   f32x4 vc = *reinterpret_cast<const f32x4*>(cr), vz = *reinterpret_cast<const f32x4*>(cr + 32);
                   vc *= unscale; vz *= unscale;
                   vc += bvp; vz += bvp;
@@ -1296,16 +1241,16 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
             // took 250 us instead of 36 [MI355X])
             float omax0 = 0.f, omax1 = 0.f, omax2 = 0.f, omax3 = 0.f;
             auto max_slot = [&](int img) { return a.act_max_out + (size_t)img * ACT_MAX_SLOTS + ((blockIdx.x + wave) & (ACT_MAX_SLOTS - 1)); };
-            static_assert((RH / RPP) % 4 == 0, "constant, even trip count: the loop holds lane shuffles (no remainder loop)");
+            static_assert((T::RH / T::RPP) % 4 == 0, "constant, even trip count: the loop holds lane shuffles (no remainder loop)");
 #pragma unroll 2
-            for (int pi = 0; pi < RH / RPP / 2; ++pi) {
-              const int ll = rin + (half + 2 * pi) * RPP;
+            for (int pi = 0; pi < T::RH / T::RPP / 2; ++pi) {
+              const int ll = rin + (half + 2 * pi) * T::RPP;
               int row, n_, h_, w_;
-              if (!locate(hf * RH + ll, row, n_, h_, w_)) continue;
+              if (!locate(hf * T::RH + ll, row, n_, h_, w_)) continue;
               int rimg = 0;                                // image of the row (1-tap launches over a pixel list: rows / image is
               if (a.scale_per_img) {                       //  not a power of two — float estimate + fix-up, not an integer division)
                 if constexpr (HALO) rimg = n_;
-                else { int rr; divmod(row, a.img_rows, inv_img_rows, rimg, rr); }
+                else { int rr; conv_divmod(row, a.img_rows, inv_img_rows, rimg, rr); }
               }
               const int rel = rimg - simg0;
               float unscale = rel == 0 ? us0 : us1, pscale = rel == 0 ? ps0 : ps1;
@@ -1313,8 +1258,8 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
                 if constexpr (PREC == PREC_F16X2) unscale = a.in_unscale[simg0 + rel];
                 if (a.pairs_out) pscale = a.pairs_scale[simg0 + rel];
               }
-              f32x4 vc = *reinterpret_cast<const f32x4*>(Cs + ll * BN + pc);
-              f32x4 vz = *reinterpret_cast<const f32x4*>(Cs + ll * BN + pc + 32);
+              f32x4 vc = *reinterpret_cast<const f32x4*>(Cs + ll * T::BN + pc);
+              f32x4 vz = *reinterpret_cast<const f32x4*>(Cs + ll * T::BN + pc + 32);
               if constexpr (PREC == PREC_F16X2) { vc *= unscale; vz *= unscale; }
               vc += bv; vz += bv;
               if (!a.dual_norelu) {
@@ -1402,11 +1347,11 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
           float unscale = 1.f, omax = 0.f;                // PREC_F16X2: as in the BIAS epilogues (max of the a half only)
           if constexpr (PREC == PREC_F16X2) unscale = *a.in_unscale;
 #pragma unroll 4
-          for (int ps = 0; ps < RH / RPP; ++ps) {
-            const int ll = rin + ps * RPP;
+          for (int ps = 0; ps < T::RH / T::RPP; ++ps) {
+            const int ll = rin + ps * T::RPP;
             int row, n_, h_, w_;
-            if (!locate(hf * RH + ll, row, n_, h_, w_)) continue;
-            f32x4 v = *reinterpret_cast<const f32x4*>(Cs + ll * BN + c4 * 4);
+            if (!locate(hf * T::RH + ll, row, n_, h_, w_)) continue;
+            f32x4 v = *reinterpret_cast<const f32x4*>(Cs + ll * T::BN + c4 * 4);
             if constexpr (PREC == PREC_F16X2) v *= unscale;
             v += bv;
             if (!isz && !a.dual_norelu) {
@@ -1446,7 +1391,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
           if constexpr (PREC != PREC_F16X2) {
             const bool tail_ = EPI == EPI_MUL && a.join != nullptr, head2_ = EPI == EPI_MUL && a.out2s != nullptr;
             if (DG || (!GMASK && !(EPI == EPI_MUL && a.gate_none) && !tail_ && !head2_ && !a.gate_binary && !a.relu_out && !a.epi_generic)) {
-              constexpr int NPf = RH / RPP;
+              constexpr int NPf = T::RH / T::RPP;
               constexpr int UPf = EPI == EPI_MUL_UP2 ? 4 : 1;
               constexpr int NG = DG ? 2 : 1;              // gates per pass; gate b of ring slot s lies in gq[b * RING + s]
               constexpr int DEPTH = DG ? (UPf == 1 ? 2 : 1) : (UPf == 1 ? 4 : 2);
@@ -1456,43 +1401,43 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
 #pragma unroll
               for (int ps = 0; ps < NPf; ++ps) {
                 int row, n_, h_, w_;
-                if (!locate(hf * RH + rin + ps * RPP, row, n_, h_, w_)) n_ = 0;
+                if (!locate(hf * T::RH + rin + ps * T::RPP, row, n_, h_, w_)) n_ = 0;
                 imgf[ps] = a.row2img ? a.row2img[n_] : n_;
               }
-              f32x4 gq[NG * RING][UPf][CW / 4];
+              f32x4 gq[NG * RING][UPf][T::CW / 4];
               auto issue = [&](int ps) {
                 int row, n_, h_, w_;
-                if (!locate(hf * RH + rin + ps * RPP, row, n_, h_, w_)) { h_ = 0; w_ = 0; }
+                if (!locate(hf * T::RH + rin + ps * T::RPP, row, n_, h_, w_)) { h_ = 0; w_ = 0; }
 #pragma unroll
                 for (int q = 0; q < UPf; ++q) {
                   const float* gp = EPI == EPI_MUL ? a.aux + ((size_t)imgf[ps] * HW + h_ * a.W + w_) * a.N + col
                                                    : a.aux + (((size_t)imgf[ps] * H2f + 2 * h_ + (q >> 1)) * W2f + 2 * w_ + (q & 1)) * a.N + col;
 #pragma unroll
-                  for (int q4 = 0; q4 < CW / 4; ++q4) gq[ps % RING][q][q4] = *reinterpret_cast<const f32x4*>(gp + 4 * q4);
+                  for (int q4 = 0; q4 < T::CW / 4; ++q4) gq[ps % RING][q][q4] = *reinterpret_cast<const f32x4*>(gp + 4 * q4);
                   if constexpr (DG) {
 #pragma unroll
-                    for (int q4 = 0; q4 < CW / 4; ++q4) gq[RING + ps % RING][q][q4] = *reinterpret_cast<const f32x4*>(a.aux_b + (gp - a.aux) + 4 * q4);
+                    for (int q4 = 0; q4 < T::CW / 4; ++q4) gq[RING + ps % RING][q][q4] = *reinterpret_cast<const f32x4*>(a.aux_b + (gp - a.aux) + 4 * q4);
                   }
                 }
               };
 #pragma unroll
               for (int ps = 0; ps < RING - 1; ++ps) issue(ps);
-              const bool plain = SPLIT_OUT && a.out_plain;
+              const bool plain = T::SPLIT_OUT && a.out_plain;
 #pragma unroll
               for (int ps = 0; ps < NPf; ++ps) {
                 if (ps + RING - 1 < NPf) issue(ps + RING - 1);
                 int row, n_, h_, w_;
-                if (locate(hf * RH + rin + ps * RPP, row, n_, h_, w_)) {
-                  const int ll = rin + ps * RPP;
-                  float v[CW];
+                if (locate(hf * T::RH + rin + ps * T::RPP, row, n_, h_, w_)) {
+                  const int ll = rin + ps * T::RPP;
+                  float v[T::CW];
 #pragma unroll
-                  for (int q4 = 0; q4 < CW / 4; ++q4)
-                    *reinterpret_cast<f32x4*>(v + 4 * q4) = *reinterpret_cast<const f32x4*>(Cs + ll * BN + c4 * CW + 4 * q4);
+                  for (int q4 = 0; q4 < T::CW / 4; ++q4)
+                    *reinterpret_cast<f32x4*>(v + 4 * q4) = *reinterpret_cast<const f32x4*>(Cs + ll * T::BN + c4 * T::CW + 4 * q4);
 #pragma unroll
                   for (int q = 0; q < UPf; ++q) {
-                    float r[CW];
+                    float r[T::CW];
 #pragma unroll
-                    for (int q4 = 0; q4 < CW / 4; ++q4)
+                    for (int q4 = 0; q4 < T::CW / 4; ++q4)
 #pragma unroll
                       for (int e = 0; e < 4; ++e) r[4 * q4 + e] = v[4 * q4 + e] * gq[ps % RING][q][q4][e];
                     float* dst = EPI == EPI_MUL
@@ -1500,7 +1445,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
                                      : a.out + (((size_t)n_ * H2f + 2 * h_ + (q >> 1)) * W2f + 2 * w_ + (q & 1)) * a.N + col;
                     if constexpr (DG)                     // out / out_b: ostride floats per pixel
                       dst = a.out + (EPI == EPI_MUL ? (size_t)row : ((size_t)n_ * H2f + 2 * h_ + (q >> 1)) * W2f + 2 * w_ + (q & 1)) * a.ostride + col;
-                    if constexpr (SPLIT_OUT) {
+                    if constexpr (T::SPLIT_OUT) {
                       if (plain) {
                         *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(r);
                         *reinterpret_cast<f32x4*>(dst + 4) = *reinterpret_cast<const f32x4*>(r + 4);
@@ -1512,11 +1457,11 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
                     }
                     if constexpr (DG) {                   // the same accumulator under the second gate
 #pragma unroll
-                      for (int q4 = 0; q4 < CW / 4; ++q4)
+                      for (int q4 = 0; q4 < T::CW / 4; ++q4)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) r[4 * q4 + e] = v[4 * q4 + e] * gq[RING + ps % RING][q][q4][e];
                       float* dstb = a.out_b + (dst - a.out);
-                      if constexpr (SPLIT_OUT) {
+                      if constexpr (T::SPLIT_OUT) {
                         if (plain) {
                           *reinterpret_cast<f32x4*>(dstb) = *reinterpret_cast<const f32x4*>(r);
                           *reinterpret_cast<f32x4*>(dstb + 4) = *reinterpret_cast<const f32x4*>(r + 4);
@@ -1538,14 +1483,14 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
             //  again; those launches are bound by their three full-width streams either way)
           }
           if constexpr (!DG) {                           // the general pass loop: one gate
-            constexpr int NP = RH / RPP;
+            constexpr int NP = T::RH / T::RPP;
             constexpr int UPN = EPI == EPI_MUL_UP2 ? 4 : 1;
             const int W2 = 2 * a.W, H2 = 2 * a.H;
             int rowv[NP], nv[NP], hv[NP], wv[NP], imgv[NP];
             bool okv[NP];
 #pragma unroll
             for (int ps = 0; ps < NP; ++ps) {
-              okv[ps] = locate(hf * RH + rin + ps * RPP, rowv[ps], nv[ps], hv[ps], wv[ps]);
+              okv[ps] = locate(hf * T::RH + rin + ps * T::RPP, rowv[ps], nv[ps], hv[ps], wv[ps]);
               if (!okv[ps]) { rowv[ps] = 0; nv[ps] = 0; hv[ps] = 0; wv[ps] = 0; }
               imgv[ps] = a.row2img ? a.row2img[nv[ps]] : nv[ps];
             }
@@ -1555,12 +1500,12 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
             auto flush_max = [&](int t, unsigned m) {
               if (m) {
                 const int rel = t - tok_first;
-                if (TMAX_LDS && rel >= 0 && rel < 16) atomicMax(tmax_s + rel, m);
+                if (T::TMAX_LDS && rel >= 0 && rel < 16) atomicMax(tmax_s + rel, m);
                 else atomicMax(a.tok_max_out + t, m);
               }
             };
             const bool tail = EPI == EPI_MUL && a.join != nullptr, head2 = EPI == EPI_MUL && a.out2s != nullptr;
-            struct Gates { f32x4 g[UPN][CW / 4]; f32x4 jn[CW / 4], jg[CW / 4], g2[CW / 4]; };
+            struct Gates { f32x4 g[UPN][T::CW / 4]; f32x4 jn[T::CW / 4], jg[T::CW / 4], g2[T::CW / 4]; };
             auto gate_ptr = [&](int ps, int q) -> const float* {
               if constexpr (EPI == EPI_MUL)
                 return a.aux + ((size_t)imgv[ps] * HW + hv[ps] * a.W + wv[ps]) * a.N + col;
@@ -1570,7 +1515,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
             auto load_gates = [&](Gates& G, int ps) {
               const f32x4 one4 = {1.f, 1.f, 1.f, 1.f};
               if constexpr (GMASK) {
-                static_assert(EPI == EPI_MUL && PREC == PREC_FP32 && CW == 4, "byte-mask gates: exact fp32 EPI_MUL only");
+                static_assert(EPI == EPI_MUL && PREC == PREC_FP32 && T::CW == 4, "byte-mask gates: exact fp32 EPI_MUL only");
                 auto m4 = [](const float* base, size_t e) {
                   const unsigned m = *reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(base) + e);
                   f32x4 g;
@@ -1589,12 +1534,12 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
 #pragma unroll
               for (int q = 0; q < UPN; ++q)
 #pragma unroll
-                for (int q4 = 0; q4 < CW / 4; ++q4)
+                for (int q4 = 0; q4 < T::CW / 4; ++q4)
                   G.g[q][q4] = (EPI == EPI_MUL && a.gate_none) ? one4 : *reinterpret_cast<const f32x4*>(gate_ptr(ps, q) + 4 * q4);
               if constexpr (EPI == EPI_MUL) {
                 const size_t go = ((size_t)imgv[ps] * HW + hv[ps] * a.W + wv[ps]) * a.N + col;
 #pragma unroll
-                for (int q4 = 0; q4 < CW / 4; ++q4) {
+                for (int q4 = 0; q4 < T::CW / 4; ++q4) {
                   if (tail) {
                     G.jn[q4] = *reinterpret_cast<const f32x4*>(a.join + (size_t)rowv[ps] * a.N + col + 4 * q4);
                     G.jg[q4] = *reinterpret_cast<const f32x4*>(a.join_gate + go + 4 * q4);
@@ -1614,16 +1559,16 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
                 if (okv[ps] && nv[ps] != ltok) { flush_max(ltok, lmax); ltok = nv[ps]; lmax = 0u; }
               }
               if (okv[ps]) {
-                const int ll = rin + ps * RPP;
-                float v[CW];
+                const int ll = rin + ps * T::RPP;
+                float v[T::CW];
 #pragma unroll
-                for (int q4 = 0; q4 < CW / 4; ++q4)
-                  *reinterpret_cast<f32x4*>(v + 4 * q4) = *reinterpret_cast<const f32x4*>(Cs + ll * BN + c4 * CW + 4 * q4);
+                for (int q4 = 0; q4 < T::CW / 4; ++q4)
+                  *reinterpret_cast<f32x4*>(v + 4 * q4) = *reinterpret_cast<const f32x4*>(Cs + ll * T::BN + c4 * T::CW + 4 * q4);
 #pragma unroll
                 for (int q = 0; q < UPN; ++q) {
-                  float r[CW];
+                  float r[T::CW];
 #pragma unroll
-                  for (int q4 = 0; q4 < CW / 4; ++q4) {
+                  for (int q4 = 0; q4 < T::CW / 4; ++q4) {
                     f32x4 g = cur.g[q][q4];
                     if (a.gate_binary) {
 #pragma unroll
@@ -1643,7 +1588,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
                   float* dst = EPI == EPI_MUL
                                    ? a.out + (size_t)rowv[ps] * a.N + col
                                    : a.out + (((size_t)nv[ps] * H2 + 2 * hv[ps] + (q >> 1)) * W2 + 2 * wv[ps] + (q & 1)) * a.N + col;
-                  if constexpr (SPLIT_OUT) {
+                  if constexpr (T::SPLIT_OUT) {
                     if (a.out_plain) {
                       *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(r);
                       *reinterpret_cast<f32x4*>(dst + 4) = *reinterpret_cast<const f32x4*>(r + 4);
@@ -1656,13 +1601,13 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
                     *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(r);
                   }
                   if (head2) {
-                    float r2[CW];
+                    float r2[T::CW];
 #pragma unroll
-                    for (int q4 = 0; q4 < CW / 4; ++q4)
+                    for (int q4 = 0; q4 < T::CW / 4; ++q4)
 #pragma unroll
                       for (int e = 0; e < 4; ++e) r2[4 * q4 + e] = r[4 * q4 + e] * cur.g2[q4][e];
                     float* d2 = a.out2s + (size_t)rowv[ps] * a.N + col;
-                    if constexpr (SPLIT_OUT) {
+                    if constexpr (T::SPLIT_OUT) {
                       split8_store(r2, d2);
                     } else {
                       *reinterpret_cast<f32x4*>(d2) = *reinterpret_cast<const f32x4*>(r2);
@@ -1677,7 +1622,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
         }
       }
     }
-    if constexpr (TMAX_LDS && (EPI == EPI_MUL || EPI == EPI_MUL_UP2)) {
+    if constexpr (T::TMAX_LDS && (EPI == EPI_MUL || EPI == EPI_MUL_UP2)) {
       __syncthreads();
       if (tid < 16 && tmax_s[tid]) atomicMax(a.tok_max_out + tok_first + tid, tmax_s[tid]);
     }

@@ -254,11 +254,6 @@ __global__ __launch_bounds__(TL::NT, 2) void conv_sparse_kernel(SparseArgs a) {
     asm volatile("v_readfirstlane_b32 %0, %1" : "=s"(sc_) : "v"(inv_Hp));
     inv_Hp = sc_;
   }
-  auto divmod = [](int x, int d, float inv, int& qq, int& r) {
-    qq = (int)(((float)x + 0.5f) * inv);
-    r = x - qq * d;
-    if (r < 0) { --qq; r += d; } else if (r >= d) { ++qq; r -= d; }
-  };
   [[maybe_unused]] unsigned char* Bs = lds;
   unsigned char* As = WREG ? lds : lds + SP_NSTAGE * BSTAGE;      // (WREG: no B stages)
 
@@ -275,7 +270,7 @@ __global__ __launch_bounds__(TL::NT, 2) void conv_sparse_kernel(SparseArgs a) {
     const int ty = r / SP_TW, tx = r - ty * SP_TW;
     const int Ys = Y0 + ty, wx = x0 + tx;
     int n_, wy;
-    divmod(Ys, Hp, inv_Hp, n_, wy);
+    conv_divmod(Ys, Hp, inv_Hp, n_, wy);
     const bool ok = r < TH * SP_TW && Ys < nys && wx < Wp;
     const bool okh = ok && wx + sx >= 0 && wx + sx < Wp, okv = ok && wy + sy >= 0 && wy + sy < Hp;
     const int e = (ty + 1) * SP_PITCH + tx + 1;
@@ -314,7 +309,7 @@ __global__ __launch_bounds__(TL::NT, 2) void conv_sparse_kernel(SparseArgs a) {
   if (tid < TH + 2) {
     const int Ys = Y0 - 1 + tid;
     int n_, wy;
-    divmod(Ys >= 0 && Ys < nys ? Ys : 0, Hp, inv_Hp, n_, wy);
+    conv_divmod(Ys >= 0 && Ys < nys ? Ys : 0, Hp, inv_Hp, n_, wy);
     imgtab[tid] = a.row2img ? a.row2img[n_] : n_;
   }
   const __amdgpu_buffer_rsrc_t rsS = __builtin_amdgcn_make_buffer_rsrc((void*)a.sc, 0, 0x7FFFFFFF, RSRC_FLAGS);
@@ -329,7 +324,7 @@ __global__ __launch_bounds__(TL::NT, 2) void conv_sparse_kernel(SparseArgs a) {
     const int Ys = Y0 - 1 + hy, wx = x0 - 1 + hx;
     const bool ok = live && e < NENT && Ys >= 0 && Ys < nys && wx >= 0 && wx < Wp;
     int n_, wy;
-    divmod(ok ? Ys : 0, Hp, inv_Hp, n_, wy);
+    conv_divmod(ok ? Ys : 0, Hp, inv_Hp, n_, wy);
     const int chunk = set8 >> 1, s = set8 & 1;
     int vo;
     if (pl < 2) {
@@ -615,7 +610,7 @@ __global__ __launch_bounds__(TL::NT, 2) void conv_sparse_kernel(SparseArgs a) {
       const int ty = R / SP_TW, tx = R - ty * SP_TW;
       const int Ys = Y0 + ty, wx = x0 + tx;
       int n_, wy;
-      divmod(Ys < nys ? Ys : 0, Hp, inv_Hp, n_, wy);
+      conv_divmod(Ys < nys ? Ys : 0, Hp, inv_Hp, n_, wy);
       const int col = n0 + cg * 8;
       ok4[p] = R < TH * SP_TW && Ys < nys && wx < Wp && col < N && !((a.diag & 1) && (row | cg | sl));
       const int y = 2 * wy + qy, x = 2 * (wx < Wp ? wx : 0) + qx;
