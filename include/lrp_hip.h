@@ -287,6 +287,40 @@ int lrp_set_fast_layers(lrp_handle* h, int64_t mask);
  * LRP_ERR_UNSUPPORTED: beta > 0 on a ResNet handle; and from the explain calls with beta > 0 in LRP_PREC_F16X2. */
 int lrp_set_cnn_rule(lrp_handle* h, float alpha, float beta);
 
+/* Added without a version bump (purely additive).  A rule per conv for the VGG-style encoder's LRP walk: the
+ * relevance-rule half of LRP(model, rule=..., input_layer_rule=...), relevance_analyzer.py:343-415.  `rules` holds one record per
+ * configured conv, input layer first; n_rules must equal the handle's number of convs.
+ *   LRP_RULE_ALPHA_BETA  alpha, beta as lrp_set_cnn_rule checks them; bias 1 = AlphaBetaRule, 0 = AlphaBetaIgnoreBiasRule
+ *                        (both denominators without the bias).  Any layer.
+ *   LRP_RULE_EPSILON     eps >= 0; eps = 0 is ZRule (SafeDivide, no stabiliser), eps > 0 EpsilonRule: Z + (2 [Z >= 0] - 1) eps and a
+ *                        plain divide; bias 1 / 0 = with / IgnoreBias.  Any layer; LRP_PREC_FP32 only.
+ *   LRP_RULE_FLAT, LRP_RULE_WSQUARE   FlatRule / WSquareRule: Z = conv(1, 1) resp. conv(1, w^2) with 'same' padding (so it varies at
+ *                        the border), no bias, R_in = convT(R / Z, 1 resp. w^2).  Layer 0 only.
+ *   LRP_RULE_BOUNDED     BoundedRule with the scalars low < high.  Layer 0 only.
+ * Fields a kind does not use are ignored.  LRP_ERR_INVALID: a wrong count, an unknown kind, bias outside {0, 1}, flat / w-square /
+ * bounded above layer 0, eps < 0, low >= high, alpha / beta outside lrp_set_cnn_rule's check.  LRP_ERR_UNSUPPORTED: a ResNet handle;
+ * an input-layer kind on a one-conv encoder.
+ * A table that is the same alpha-beta record with bias on every layer IS lrp_set_cnn_rule(alpha, beta): it takes that entry's path,
+ * to the bit ((1, 0) everywhere is the default walk), and lrp_set_cnn_rule in turn replaces any table.  Every other table runs the
+ * dense table walk: layer l reads one or two relevance chains (two for alpha-beta with beta > 0) against one matrix and applies
+ * layer l-1's one or two gates; lrp_encode_images adds the denominator passes the rules need behind the unchanged forward.
+ * Alpha-beta kinds and the three input-layer kinds run in exact fp32 and in three-term split-bf16 with the handle; with an epsilon
+ * kind in the table the explain calls return LRP_ERR_UNSUPPORTED outside LRP_PREC_FP32, and in LRP_PREC_F16X2 for every table.
+ * LRP_ERR_UNSUPPORTED from the explain calls as well for a table with a launch lrp_conv_plan refuses: a one-chain layer on a
+ * two-chain layer takes LRP_PLAN_DUAL_MUL with Cin(plan) = its width, a multiple of 16 (split-bf16) / 8 (fp32).  A CHANGE drops the encode caches (LRP_ERR_STATE from explain calls until lrp_encode_images ran
+ * again).  Buffers appear with the first table that needs them, sized by that table's chain counts (a table that reads one chain
+ * everywhere walks on the default walk's buffers), are counted in lrp_workspace_bytes and idle afterwards; a handle that never sets
+ * a table allocates nothing. */
+enum { LRP_RULE_ALPHA_BETA = 0, LRP_RULE_EPSILON = 1, LRP_RULE_FLAT = 2, LRP_RULE_WSQUARE = 3, LRP_RULE_BOUNDED = 4 };
+typedef struct lrp_conv_rule {
+  int32_t kind;        /* LRP_RULE_* */
+  int32_t bias;        /* alpha-beta and epsilon kinds: 1 = the bias is a constant input, 0 = IgnoreBias */
+  float alpha, beta;   /* LRP_RULE_ALPHA_BETA */
+  float eps;           /* LRP_RULE_EPSILON */
+  float low, high;     /* LRP_RULE_BOUNDED */
+} lrp_conv_rule;
+int lrp_set_cnn_rules(lrp_handle* h, const lrp_conv_rule* rules, int32_t n_rules);
+
 /* Dominant-kernel timing for bench.py's roofline block: when enabled, HIP
  * events bracket every conv-LRP launch on the caller's stream; query returns
  * launches and summed milliseconds since the last reset (syncs the events). */
@@ -324,6 +358,17 @@ int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias
 int lrp_op_conv_ab(const float* sp_dev, const float* sn_dev, const float* w_hwio_host, float alpha, float beta, const float* gp_dev,
                    const float* gn_dev, float* outp_dev, float* outn_dev, int32_t NB, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
                    int32_t pool, int32_t split, void* stream);
+
+/* Added without a version bump (purely additive).  lrp_op_conv_ab for chains_in, gates_out in {1, 2} (the launches of the rule
+ * table's walk, lrp_set_cnn_rules): chain j is multiplied with p_j w+ + q_j w-,
+ *   c = sum_j convT(s_j, p_j w+ + q_j w-)   (3x3 'same', ONE GEMM with K = chains_in x 9 x Cout),   out_i = c x g_i,
+ * c repeated 2 x 2 (nearest) when pool != 0.  s0_dev, s1_dev (NB, H, W, Cout); g_i / out_i (NB, H u, W u, Cin); s1_dev is not read
+ * with one chain, g1_dev / out1_dev not with one gate.  split as in lrp_op_conv_ab.  Two gates take the form lrp_conv_plan answers
+ * for LRP_PLAN_DUAL_MUL with Cin(plan) = chains_in x Cout, one gate the plain MUL epilogues' with the same Cin(plan); what the plan
+ * refuses is LRP_ERR_UNSUPPORTED (one chain into two gates: Cout % 16 == 0 split, % 8 fp32). */
+int lrp_op_conv_rule(const float* s0_dev, const float* s1_dev, const float* w_hwio_host, int32_t chains_in, int32_t gates_out, float p0,
+                     float q0, float p1, float q1, const float* g0_dev, const float* g1_dev, float* out0_dev, float* out1_dev, int32_t NB,
+                     int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t pool, int32_t split, void* stream);
 
 /* ABI v6.  The conv-LRP launch BEHIND a 2x2 max-pool (AlphaBetaRule RR:274-322 for a conv whose output feeds MaxPooling2D: the
  * relevance arrives through the pool's gradient routing, RA:470-480 -> IL:138-157, i.e. one non-zero per window and channel)

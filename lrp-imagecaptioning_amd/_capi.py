@@ -38,6 +38,15 @@ class LrpConfig(C.Structure):
     ]
 
 
+# lrp_set_cnn_rules: one record per conv
+LRP_RULE_ALPHA_BETA, LRP_RULE_EPSILON, LRP_RULE_FLAT, LRP_RULE_WSQUARE, LRP_RULE_BOUNDED = range(5)
+
+
+class LrpConvRule(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("bias", C.c_int32), ("alpha", C.c_float), ("beta", C.c_float), ("eps", C.c_float),
+                ("low", C.c_float), ("high", C.c_float)]
+
+
 # every symbol include/lrp_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = {
@@ -56,6 +65,7 @@ SYMBOLS = {
     "lrp_set_precision": (C.c_int, [_P, C.c_int32]),
     "lrp_set_fast_layers": (C.c_int, [_P, C.c_int64]),
     "lrp_set_cnn_rule": (C.c_int, [_P, C.c_float, C.c_float]),
+    "lrp_set_cnn_rules": (C.c_int, [_P, _P, C.c_int32]),
     "lrp_profile_enable": (C.c_int, [_P, C.c_int32]),
     "lrp_profile_query": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "lrp_profile_records": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
@@ -84,6 +94,7 @@ SYMBOLS = {
     "lrp_train_drop_forward": (C.c_int, [_P, _P]),
     "lrp_reload_switches": (C.c_int, []),
     "lrp_op_conv_ab": (C.c_int, [_P, _P, _P, C.c_float, C.c_float, _P, _P, _P, _P] + [C.c_int32] * 7 + [_P]),
+    "lrp_op_conv_rule": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32] + [C.c_float] * 4 + [_P] * 4 + [C.c_int32] * 7 + [_P]),
     "lrp_op_conv_pool_sparse": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     "lrp_train_apply": (C.c_int, [_P, _P, _P]),
     "lrp_train_get_master": (C.c_int, [_P, _P, _P]),

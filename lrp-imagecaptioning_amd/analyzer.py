@@ -116,12 +116,13 @@ class LRPAlphaBeta(LRPSequentialPresetA):
     """relevance_analyzer.py:578-620: every conv under AlphaBetaRule(alpha, beta, bias=True) (relevance_rule.py:216-322), max-pools
     by gradient routing — the same `analyze([X, R])` surface as LRPSequentialPresetA, on the engine's walk under
     lrp_set_cnn_rule(alpha, beta).  (1, 0) is LRPSequentialPresetA's walk to the bit; beta > 0 runs the two-chain walk
-    (VGG-style encoders).  The IgnoreBias variants (bias=False) are not built."""
+    (VGG-style encoders).  bias=False is refused here: the IgnoreBias rules run on the rule table (LRPAlpha2Beta1IgnoreBias,
+    LRPAlpha1Beta0IgnoreBias, or LRP(model, rule=("alphabeta", alpha, beta, False)))."""
 
     def __init__(self, model, alpha=None, beta=None, bias=True, neuron_selection_mode="replace", **kwargs):
         alpha, beta = infer_alpha_beta(alpha, beta, self.__class__.__name__)
         if not bias:
-            raise NotImplementedError("the IgnoreBias variants (bias=False) are not built")
+            raise NotImplementedError("bias=False: use LRPAlpha2Beta1IgnoreBias / LRPAlpha1Beta0IgnoreBias or LRP(model, rule=('alphabeta', alpha, beta, False))")
         self._alpha, self._beta, self._bias = alpha, beta, bias
         super(LRPAlphaBeta, self).__init__(model, neuron_selection_mode=neuron_selection_mode, **kwargs)
         self._engine.set_cnn_rule(alpha, beta)
@@ -147,6 +148,240 @@ class LRPSequentialPresetB(LRPAlphaBeta):
 
     def __init__(self, model, epsilon=0.1, **kwargs):
         super(LRPSequentialPresetB, self).__init__(model, alpha=2, beta=1, bias=True, epsilon=epsilon, **kwargs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Rule table: LRP(model, rule=..., input_layer_rule=...) (relevance_analyzer.py:300-415) on lrp_set_cnn_rules
+# ---------------------------------------------------------------------------------------------------------------------
+class _Rule(object):
+    """A conv rule of relevance_rule.py as data: subclass and override the class attributes to pass parameters, as the
+    reference's proxy classes do (relevance_analyzer.py:538-548)."""
+    _kind = None
+    alpha, beta, bias, epsilon, low, high = None, None, True, 1e-7, -1, 1
+
+    @classmethod
+    def spec(cls):
+        if cls._kind == "alphabeta":
+            a, b = infer_alpha_beta(cls.alpha, cls.beta, cls.__name__)
+            return ("alphabeta", a, b, bool(cls.bias))
+        if cls._kind == "epsilon":
+            return ("epsilon", check_epsilon(cls.epsilon, cls.__name__), bool(cls.bias))
+        if cls._kind == "z":
+            return ("epsilon", 0.0, bool(cls.bias))
+        if cls._kind == "bounded":
+            return ("bounded", cls.low, cls.high)
+        if cls._kind in ("flat", "wsquare"):
+            return (cls._kind,)
+        raise NotImplementedError("%s: %s" % (cls.__name__, cls.__doc__))
+
+
+def check_epsilon(epsilon, caller):
+    """relevance_based/utils.py:52-69."""
+    if epsilon <= 0:
+        raise ValueError("Constructor call to {} : Parameter epsilon must be > 0 but was {}".format(caller, epsilon))
+    return epsilon
+
+
+class ZRule(_Rule): _kind = "z"                                                         # RR:74-98
+class ZIgnoreBiasRule(ZRule): bias = False                                              # RR:102-109
+class EpsilonRule(_Rule): _kind = "epsilon"                                             # RR:113-144
+class EpsilonIgnoreBiasRule(EpsilonRule): bias = False                                  # RR:148-152
+class WSquareRule(_Rule): _kind = "wsquare"                                             # RR:156-187
+class FlatRule(_Rule): _kind = "flat"                                                   # RR:192-211
+class AlphaBetaRule(_Rule): _kind = "alphabeta"                                         # RR:216-322
+class AlphaBetaIgnoreBiasRule(AlphaBetaRule): bias = False                              # RR:327-331
+class Alpha2Beta1Rule(AlphaBetaRule): alpha, beta = 2, 1                                # RR:335-341
+class Alpha2Beta1IgnoreBiasRule(Alpha2Beta1Rule): bias = False                          # RR:344-350
+class Alpha1Beta0Rule(AlphaBetaRule): alpha, beta = 1, 0                                # RR:353-359
+class Alpha1Beta0IgnoreBiasRule(Alpha1Beta0Rule): bias = False                          # RR:362-368
+class BoundedRule(_Rule): _kind = "bounded"                                             # RR:372-441
+class ZPlusRule(Alpha1Beta0IgnoreBiasRule): pass                                        # RR:445-456
+
+
+class ZPlusFastRule(_Rule):
+    """not built: its one-conv form assumes x >= 0, which the image layer's mean-subtracted input is not; use ZPlus"""
+
+
+LRP_RULES = {"Z": ZRule, "ZIgnoreBias": ZIgnoreBiasRule, "Epsilon": EpsilonRule, "EpsilonIgnoreBias": EpsilonIgnoreBiasRule,
+             "WSquare": WSquareRule, "Flat": FlatRule, "AlphaBeta": AlphaBetaRule, "AlphaBetaIgnoreBias": AlphaBetaIgnoreBiasRule,
+             "Alpha2Beta1": Alpha2Beta1Rule, "Alpha2Beta1IgnoreBias": Alpha2Beta1IgnoreBiasRule, "Alpha1Beta0": Alpha1Beta0Rule,
+             "Alpha1Beta0IgnoreBias": Alpha1Beta0IgnoreBiasRule, "ZPlus": ZPlusRule, "ZPlusFast": ZPlusFastRule,
+             "Bounded": BoundedRule}                                                     # relevance_analyzer.py:173-194
+
+_INPUT_ONLY = ("flat", "wsquare", "bounded")
+
+
+def normalize_rule(rule):
+    """One conv's rule -> the record LRPEngine.set_cnn_rules takes: a name of LRP_RULES, one of the rule classes above, or the
+    record itself — ("alphabeta", alpha, beta, bias), ("epsilon", eps, bias) with eps = 0 for ZRule, ("flat",), ("wsquare",),
+    ("bounded", low, high)."""
+    if isinstance(rule, str):
+        if rule not in LRP_RULES:
+            raise ValueError("unknown LRP rule %r: one of %s" % (rule, sorted(LRP_RULES)))
+        rule = LRP_RULES[rule]
+    if isinstance(rule, type) and issubclass(rule, _Rule):
+        return rule.spec()
+    if not isinstance(rule, (tuple, list)) or not rule or not isinstance(rule[0], str):
+        raise ValueError("not an LRP rule: %r" % (rule,))
+    kind, args = rule[0], tuple(rule[1:])
+    if kind == "alphabeta" and len(args) in (2, 3):
+        a, b = infer_alpha_beta(args[0], args[1], "AlphaBetaRule")
+        return ("alphabeta", a, b, bool(args[2]) if len(args) == 3 else True)
+    if kind == "epsilon" and len(args) in (1, 2):
+        if not args[0] >= 0:
+            raise ValueError("epsilon must be >= 0 but was {}".format(args[0]))
+        return ("epsilon", float(args[0]), bool(args[1]) if len(args) == 2 else True)
+    if kind == "bounded" and len(args) == 2:
+        if not args[0] < args[1]:
+            raise ValueError("BoundedRule needs low < high but got ({}, {})".format(*args))
+        return ("bounded", float(args[0]), float(args[1]))
+    if kind in ("flat", "wsquare") and not args:
+        return (kind,)
+    raise ValueError("not an LRP rule: %r" % (rule,))
+
+
+def rule_table(rule, input_layer_rule, n_conv):
+    """The per-conv table of LRP(model, rule=..., input_layer_rule=...), input layer first (relevance_analyzer.py:343-415).
+    rule: one rule for every conv, or a list with one per conv in the reference's order — create_rule_mapping pops from the END
+    while the graph is walked in reverse, so the list reads input layer first, and with an input_layer_rule (inserted at index
+    0, RA:395) it holds the convs above the image layer only.  input_layer_rule: a rule, or (low, high) for BoundedRule."""
+    if rule is None:
+        raise ValueError("Need LRP rule(s).")                                              # RA:345-346
+    if input_layer_rule is not None:
+        if isinstance(input_layer_rule, tuple) and len(input_layer_rule) == 2 and not isinstance(input_layer_rule[0], str):
+            input_layer_rule = ("bounded",) + tuple(input_layer_rule)                      # RA:379-386
+        input_layer_rule = normalize_rule(input_layer_rule)
+    if isinstance(rule, list):
+        if rule and isinstance(rule[0], tuple) and len(rule[0]) == 2 and callable(rule[0][0]):
+            raise NotImplementedError("conditional rule lists need the Keras graph; give one rule per conv")
+        table = [normalize_rule(r) for r in rule]
+        if input_layer_rule is not None:
+            table.insert(0, input_layer_rule)
+        if len(table) != n_conv:
+            raise ValueError("%d rules for %d layers with a kernel" % (len(table), n_conv))
+    else:
+        table = [normalize_rule(rule)] * n_conv
+        if input_layer_rule is not None:
+            table[0] = input_layer_rule
+    for i, r in enumerate(table):
+        if r[0] in _INPUT_ONLY and i > 0:
+            raise NotImplementedError("%s above the input layer is not built: it sends relevance to units whose ReLU is off, "
+                                      "which the cached gates a / Z cannot carry" % r[0])
+    return tuple(table)
+
+
+class LRP(LRPSequentialPresetA):
+    """relevance_analyzer.py:300-500 for the truncated VGG-style encoders: `rule` for every conv (a name of LRP_RULES, a rule
+    class, a record of normalize_rule, or a list per conv), `input_layer_rule` for the image layer (a rule, or (low, high) for
+    BoundedRule); max-pools by gradient routing.  Same analyze([X, R]) surface; the engine runs the table walk of
+    lrp_set_cnn_rules.  Epsilon and Z rules switch the engine to exact fp32, as the gradient analyzers do."""
+
+    def __init__(self, model, rule=None, input_layer_rule=None, neuron_selection_mode="replace", **kwargs):
+        if rule is None:
+            raise ValueError("Need LRP rule(s).")                                          # RA:345-346
+        if getattr(model, "resnet", None) is not None:
+            raise NotImplementedError("the ResNet encoder's walk is alpha1beta0 only")
+        table = rule_table(rule, input_layer_rule, len(model.cnn_cfg))
+        self._rule, self._input_layer_rule, self._table = rule, input_layer_rule, table
+        super(LRP, self).__init__(model, neuron_selection_mode=neuron_selection_mode, **kwargs)
+        if any(r[0] == "epsilon" for r in table):
+            self._engine.set_precision("fp32")
+        self._engine.set_cnn_rules(table)
+
+
+class LRPZ(LRP):
+    """relevance_analyzer.py:517-520."""
+
+    def __init__(self, model, **kwargs):
+        super(LRPZ, self).__init__(model, rule="Z", **kwargs)
+
+
+class LRPZIgnoreBias(LRP):
+    """relevance_analyzer.py:523-527."""
+
+    def __init__(self, model, **kwargs):
+        super(LRPZIgnoreBias, self).__init__(model, rule="ZIgnoreBias", **kwargs)
+
+
+class LRPEpsilon(LRP):
+    """relevance_analyzer.py:531-552."""
+
+    def __init__(self, model, epsilon=1e-7, bias=True, **kwargs):
+        self._epsilon_rule = check_epsilon(epsilon, self.__class__.__name__)
+        super(LRPEpsilon, self).__init__(model, rule=("epsilon", epsilon, bias), **kwargs)
+
+
+class LRPEpsilonIgnoreBias(LRPEpsilon):
+    """relevance_analyzer.py:555-561."""
+
+    def __init__(self, model, epsilon=1e-7, **kwargs):
+        super(LRPEpsilonIgnoreBias, self).__init__(model, epsilon=epsilon, bias=False, **kwargs)
+
+
+class LRPAlpha2Beta1IgnoreBias(LRP):
+    """relevance_analyzer.py:649-656."""
+
+    def __init__(self, model, **kwargs):
+        super(LRPAlpha2Beta1IgnoreBias, self).__init__(model, rule="Alpha2Beta1IgnoreBias", **kwargs)
+
+
+class LRPAlpha1Beta0IgnoreBias(LRP):
+    """relevance_analyzer.py:669-676."""
+
+    def __init__(self, model, **kwargs):
+        super(LRPAlpha1Beta0IgnoreBias, self).__init__(model, rule="Alpha1Beta0IgnoreBias", **kwargs)
+
+
+class LRPZPlus(LRPAlpha1Beta0IgnoreBias):
+    """relevance_analyzer.py:678-681."""
+
+
+class LRPSequentialPresetAFlat(LRP):
+    """relevance_analyzer.py:755-760: LRPSequentialPresetA with FlatRule at the image layer."""
+
+    def __init__(self, model, epsilon=0.1, **kwargs):
+        super(LRPSequentialPresetAFlat, self).__init__(model, rule="Alpha1Beta0", input_layer_rule=FlatRule, epsilon=epsilon, **kwargs)
+
+
+class LRPSequentialPresetBFlat(LRP):
+    """relevance_analyzer.py:765-770: LRPSequentialPresetB with FlatRule at the image layer."""
+
+    def __init__(self, model, epsilon=0.1, **kwargs):
+        super(LRPSequentialPresetBFlat, self).__init__(model, rule="Alpha2Beta1", input_layer_rule="Flat", epsilon=epsilon, **kwargs)
+
+
+class _NotBuilt(object):
+    _why = ""
+
+    def __init__(self, model=None, *args, **kwargs):
+        raise NotImplementedError("%s: %s" % (self.__class__.__name__, self._why))
+
+
+class LRPFlat(_NotBuilt):
+    """relevance_analyzer.py:571-575."""
+    _why = "FlatRule above the input layer needs relevance at units whose ReLU is off; use input_layer_rule='Flat'"
+
+
+class LRPWSquare(_NotBuilt):
+    """relevance_analyzer.py:564-568."""
+    _why = "WSquareRule above the input layer needs relevance at units whose ReLU is off; use input_layer_rule='WSquare'"
+
+
+class LRPZPlusFast(_NotBuilt):
+    """relevance_analyzer.py:684-692."""
+    _why = "its one-conv form assumes x >= 0, which the mean-subtracted image is not; LRPZPlus is the same rule without that assumption"
+
+
+class BaselineLRPZ(_NotBuilt):
+    """relevance_analyzer.py:57-100."""
+    _why = "input x gradient of the whole model; InputTimesGradient is that walk, and LRPZ the rule-based one"
+
+
+PRESETS = {  # CaptionModelSpec(cnn_rule=<name>): (rule, input_layer_rule)
+    "presetA": ("Alpha1Beta0", None), "presetB": ("Alpha2Beta1", None), "presetAflat": ("Alpha1Beta0", "Flat"),
+    "presetBflat": ("Alpha2Beta1", "Flat"), "alpha2beta1ignorebias": ("Alpha2Beta1IgnoreBias", None),
+    "alpha1beta0ignorebias": ("Alpha1Beta0IgnoreBias", None), "zplus": ("ZPlus", None), "z": ("Z", None),
+    "zignorebias": ("ZIgnoreBias", None)}
 
 
 def _check_selection_mode(neuron_selection_mode):

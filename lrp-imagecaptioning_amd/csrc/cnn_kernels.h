@@ -642,6 +642,144 @@ __global__ __launch_bounds__(256) void pool_gate_inh_kernel(const f32x4* __restr
   }
 }
 
+// ---- rule table of the VGG walk (lrp_set_cnn_rules, Encoder::explain_table): operands and gates per conv ----
+// The packer of a conv above the image layer, per-chain coefficients on the sign halves: chain j holds p_j w+ + q_j w-
+//   bwd = 0: forward [Cout rows][9 * CP], CP = cinp(Cin), chain 0 only (a denominator conv: w+ (1,0), w- (0,1), w (1,1))
+//   bwd = 1: backward [Cin rows][9 * CP], CP = cinp(chains * Cout), taps flipped, k = tap' * CP + j * Cout + co: the transposed conv
+//            of every chain as ONE GEMM over [S_0 | S_1]  ([alpha w+ ; -beta w-] = (alpha, 0), (0, -beta))
+// Every k of the rows < `rows` is written (zeros included); rows beyond stay as the buffer was cleared.
+__global__ __launch_bounds__(256) void pack_conv_rule_dev_kernel(const float* __restrict__ w, float* __restrict__ dst, int bwd, int Cin, int Cout,
+                                                                 int CP, int rows, int chains, float p0, float q0, float p1, float q1) {
+  const int K = 9 * CP;
+  const size_t total = (size_t)rows * K;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int row = (int)(i / K), k = (int)(i % K), t = k / CP, c = k % CP;
+    float v = 0.f;
+    if (!bwd) {
+      if (c < Cin) { const float x = w[((size_t)t * Cin + c) * Cout + row]; v = x >= 0.f ? p0 * x : q0 * x; }
+    } else if (c < chains * Cout) {
+      const int j = c >= Cout ? 1 : 0;
+      const float x = w[((size_t)(8 - t) * Cin + row) * Cout + c - j * Cout];
+      v = x >= 0.f ? (j ? p1 : p0) * x : (j ? q1 : q0) * x;
+    }
+    dst[i] = v;
+  }
+}
+// The image layer's, by rule kind (include/lrp_hip.h LRP_RULE_*): w (3,3,3,cout) ->
+//   fwd_a [cout][64]  activator denominator against the im2col row (first patch | second patch): w+ | w-   (alpha-beta without the
+//                     bias: x+ | x-; bounded: x - low | x - high)                                       — nullptr: not wanted
+//   fwd_n [cout][64]  inhibitor denominator w- | w+                                                     — nullptr: not wanted
+//   bwd   [54][Kb]    tap-expanded channel reduction, row t*6+c the "+" column and t*6+3+c the "-" column of the stencil:
+//     alpha-beta   chains 1: w+ ; w-      chains 2 (k = [S+ | S-]): alpha w+ | -beta w- ; alpha w- | -beta w+
+//     epsilon      w ; 0        flat  1 ; 0        w-square  w^2 ; 0        bounded  w+ ; w-
+__global__ __launch_bounds__(256) void pack_image_layer_rule_dev_kernel(const float* __restrict__ w, float* __restrict__ fwd_a,
+                                                                        float* __restrict__ fwd_n, float* __restrict__ bwd, int cout, int Kb,
+                                                                        int kind, int chains, float alpha, float beta) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 27 * cout) return;
+  const int k = i / cout, co = i - k * cout, t = k / 3, c = k - 3 * t;
+  const float v = w[i], vp = v >= 0.f ? v : 0.f, vn = v < 0.f ? v : 0.f;
+  if (fwd_a) { fwd_a[(size_t)co * 64 + k] = vp; fwd_a[(size_t)co * 64 + 32 + k] = vn; }
+  if (fwd_n) { fwd_n[(size_t)co * 64 + k] = vn; fwd_n[(size_t)co * 64 + 32 + k] = vp; }
+  float* rp = bwd + (size_t)(t * 6 + c) * Kb;
+  float* rn = bwd + (size_t)(t * 6 + 3 + c) * Kb;
+  if (kind == 0 && chains == 2) {
+    rp[co] = alpha * vp; rp[cout + co] = -beta * vn;
+    rn[co] = alpha * vn; rn[cout + co] = -beta * vp;
+  } else if (kind == 0 || kind == 4) {
+    rp[co] = vp; rn[co] = vn;
+  } else {
+    rp[co] = kind == 1 ? v : kind == 2 ? 1.f : v * v;
+    rn[co] = 0.f;
+  }
+}
+// im2col of the image layer for BoundedRule (RR:411-441): A1[m][64] = [ (x - low) patch | (x - high) patch ], both zero padded
+// outside the image — conv(x, w) - conv(low, w+) - conv(high, w-) = conv(x - low, w+) + conv(x - high, w-)
+__global__ __launch_bounds__(256) void im2col_image_bounded_kernel(const float* __restrict__ img, float* __restrict__ A1, int NB, int H,
+                                                                   int W, float low, float high) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t total = (size_t)NB * H * W * 8;
+  if (idx >= total) return;
+  const int g = (int)(idx & 7);
+  const size_t m = idx >> 3;
+  const int HW = H * W;
+  const int n = (int)(m / HW), rem = (int)(m - (size_t)n * HW);
+  const int h = rem / W, w = rem - h * W;
+  const float sub = g >= 4 ? high : low;
+  float v[8];
+#pragma unroll
+  for (int q = 0; q < 8; ++q) {
+    const int kk = 8 * (g & 3) + q;
+    float x = 0.f;
+    if (kk < 27) {
+      const int t = kk / 3, c = kk - 3 * t;
+      const int hh = h + t / 3 - 1, ww = w + t % 3 - 1;
+      if (hh >= 0 && hh < H && ww >= 0 && ww < W) x = img[(((size_t)n * H + hh) * W + ww) * 3 + c] - sub;
+    }
+    v[q] = x;
+  }
+  *reinterpret_cast<f32x4*>(A1 + idx * 8) = *reinterpret_cast<const f32x4*>(v);
+  *reinterpret_cast<f32x4*>(A1 + idx * 8 + 4) = *reinterpret_cast<const f32x4*>(v + 4);
+}
+// EpsilonRule's denominator (RR:131): z + (2 [z >= 0] - 1) eps; eps = 0 is ZRule's SafeDivide
+__device__ __forceinline__ float stab_eps(float z, float eps) { return eps > 0.f ? z + (z >= 0.f ? eps : -eps) : safe_den(z); }
+// WSquareRule's denominator of the image layer (RR:177-181: conv(1, w^2), 'same' padding): one value per output channel and
+// border class cls = [h == 0] | [h == H-1] << 1 | [w == 0] << 2 | [w == W-1] << 3 (the taps that fall outside are missing)
+__global__ __launch_bounds__(256) void wsquare_class_kernel(const float* __restrict__ w, float* __restrict__ zc, int cout) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 16 * cout) return;
+  const int cls = i / cout, co = i - cls * cout;
+  float s = 0.f;
+  for (int t = 0; t < 9; ++t) {
+    const int kh = t / 3, kw = t % 3;
+    if ((kh == 0 && (cls & 1)) || (kh == 2 && (cls & 2)) || (kw == 0 && (cls & 4)) || (kw == 2 && (cls & 8))) continue;
+    for (int c = 0; c < 3; ++c) { const float v = w[(size_t)(t * 3 + c) * cout + co]; s += v * v; }
+  }
+  zc[i] = s;
+}
+// The gate of a table rule whose denominator is not the forward's Z+:  G = v / den, with v = a_l (no pool behind the layer;
+// gmask == nullptr) or the pooled activation at the window's arg-max — where the activator gate `gmask` of the forward is
+// non-zero — and an exact zero elsewhere.  den by zmode:
+//   0 safe(z)   1 stab_eps(z)   2 stab_eps(v) (EpsilonRule with bias behind a ReLU: Z = a wherever relevance arrives)
+//   3 FlatRule at the image: 3 x the taps inside the image   4 WSquareRule at the image: zc[border class][channel]
+__global__ __launch_bounds__(256) void rule_gate_kernel(const float* __restrict__ a, const float* __restrict__ gmask, const float* __restrict__ pooled,
+                                                        const float* __restrict__ z, const float* __restrict__ zc, float* __restrict__ out, int NB,
+                                                        int H, int W, int C, int zmode, float eps) {
+  const int C4 = C >> 2;
+  const size_t total = (size_t)NB * H * W * C4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int c4 = (int)(i % C4);
+    size_t r = i / C4;
+    const int w = (int)(r % W);
+    r /= W;
+    const int h = (int)(r % H), n = (int)(r / H);
+    f32x4 v, m;
+    if (gmask) {
+      m = *reinterpret_cast<const f32x4*>(gmask + i * 4);
+      v = *reinterpret_cast<const f32x4*>(pooled + ((((size_t)n * (H >> 1) + (h >> 1)) * (W >> 1) + (w >> 1)) * C) + 4 * c4);
+    } else {
+      v = *reinterpret_cast<const f32x4*>(a + i * 4);
+      m = v;
+    }
+    f32x4 zv = v;
+    if (zmode <= 1) zv = *reinterpret_cast<const f32x4*>(z + i * 4);
+    const int cls = (h == 0 ? 1 : 0) | (h == H - 1 ? 2 : 0) | (w == 0 ? 4 : 0) | (w == W - 1 ? 8 : 0);
+    if (zmode == 4) zv = *reinterpret_cast<const f32x4*>(zc + (size_t)cls * C + 4 * c4);
+    const float flat = 3.f * (float)((3 - (cls & 1) - ((cls >> 1) & 1)) * (3 - ((cls >> 2) & 1) - ((cls >> 3) & 1)));
+    f32x4 o;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const float den = zmode == 0 || zmode == 4 ? safe_den(zv[c]) : zmode == 3 ? flat : stab_eps(zv[c], eps);
+      o[c] = m[c] != 0.f ? v[c] / den : 0.f;
+    }
+    *reinterpret_cast<f32x4*>(out + i * 4) = o;
+  }
+}
+// z -> stab_eps(z) in place (the top layer's denominator under EpsilonRule; the head then divides by it)
+__global__ __launch_bounds__(256) void stab_eps_kernel(float* __restrict__ z, size_t n, float eps) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) z[i] = stab_eps(z[i], eps);
+}
+
 // Image layer of the reverse walk (RR:306-312 with both sign branches live):
 //   R_img[p][c] = x+[p][c] * convT(S_1, w+)[p][c] + x-[p][c] * convT(S_1, w-)[p][c]
 // computed as a channel reduction FIRST (one K = C_1 GEMM on the MFMA kernel):
@@ -652,7 +790,7 @@ __global__ __launch_bounds__(256) void pool_gate_inh_kernel(const f32x4* __restr
 constexpr int IMG_T_COLS = 54;
 __global__ __launch_bounds__(256) void img_stencil_kernel(const float* __restrict__ T, const float* __restrict__ ximg,
                                                           const int* __restrict__ row2img, float* __restrict__ out,
-                                                          int n, int H, int W, int mode) {
+                                                          int n, int H, int W, int mode, float lo, float hi) {
   const size_t total = (size_t)n * H * W;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int HW = H * W;
@@ -678,7 +816,8 @@ __global__ __launch_bounds__(256) void img_stencil_kernel(const float* __restric
     for (int c = 0; c < 3; ++c) {
       if (mode == 0) o[c] = x[c] >= 0.f ? x[c] * pos[c] : x[c] * neg[c];   // LRP alpha1beta0 at the image
       else if (mode == 1) o[c] = pos[c] + neg[c];                          // plain gradient (w sits in the + columns)
-      else o[c] = x[c] * (pos[c] + neg[c]);                                // input x gradient
+      else if (mode == 2) o[c] = x[c] * (pos[c] + neg[c]);                 // input x gradient
+      else o[c] = (x[c] - lo) * pos[c] + (x[c] - hi) * neg[c];             // BoundedRule (RR:430-439)
     }
   }
 }

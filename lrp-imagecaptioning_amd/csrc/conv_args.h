@@ -139,7 +139,8 @@ struct ConvArgs {
   const int* row2img;  // per input image-slot n -> cache slot (nullptr = identity)
   int split;
   int out_plain;       // bf16x3 MUL epilogues: 1 = write fp32 instead of re-splitting (last GEMM of a chain)
-  // EPI_IMG_STENCIL: tiles per image row / column, ximg = the images (x of the image layer), mode 0 LRP | 1 sum | 2 x*sum
+  // EPI_IMG_STENCIL: tiles per image row / column, ximg = the images (x of the image layer), mode 0 LRP | 1 sum | 2 x*sum |
+  // 3 bounded: (x - img_lo) * sum+ + (x - img_hi) * sum-  (the two bounds are the struct's last members)
   int tiles_x, tiles_y, img_mode;
   const float* ximg;
   const float* addend; // BIAS / BIAS_RELU epilogues: out = [relu](acc + bias + addend)  (bias may be null)
@@ -250,6 +251,7 @@ struct ConvArgs {
   const float* aux_b;
   float* out_b;
   int ostride;
+  float img_lo, img_hi;        // EPI_IMG_STENCIL, img_mode 3 (BoundedRule at the image layer): the bounds (low, high)
 };
 
 }  // namespace lrp

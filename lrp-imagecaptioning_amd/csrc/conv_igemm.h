@@ -1036,7 +1036,8 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
       for (int c = 0; c < 3; ++c) {
         if (a.img_mode == 0) ov[c] = xv[c] >= 0.f ? xv[c] * pos[c] : xv[c] * neg[c];   // LRP alpha1beta0 at the image
         else if (a.img_mode == 1) ov[c] = pos[c] + neg[c];                                // plain gradient
-        else ov[c] = xv[c] * (pos[c] + neg[c]);                                           // input x gradient
+        else if (a.img_mode == 2) ov[c] = xv[c] * (pos[c] + neg[c]);                      // input x gradient
+        else ov[c] = (xv[c] - a.img_lo) * pos[c] + (xv[c] - a.img_hi) * neg[c];           // BoundedRule (RR:430-439)
       }
     }
     return;

@@ -67,6 +67,11 @@ struct ConvLayer {
   // (cnn_kernels.h pack_conv_ab_dev_kernel; the image layer: pack_image_layer_ab_dev_kernel).  Allocated on the first beta > 0.
   DevBuf Gn, w_fwd_n, w_fwd_ns, w_bwd_ab, w_bwd_ab_s;
   bool ab_packed = false;
+  // rule table (Encoder::set_table): the activator gate of a rule whose denominator is not the forward's Z+, the forward matrix of
+  // that denominator (fp32, split8) and the layer's backward matrix over its one or two chains (cnn_kernels.h
+  // pack_conv_rule_dev_kernel / pack_image_layer_rule_dev_kernel).  Allocated by the first table that needs them.
+  DevBuf Gt, w_fwd_t, w_fwd_ts, w_bwd_t, w_bwd_t_s;
+  bool t_packed = false;
   size_t act_elems() const { return (size_t)H * W * cout; }
 };
 
@@ -475,6 +480,8 @@ struct Encoder {
     LRP_TRY(repack_conv_weight_from_device(li, w_dev, tmp, st));
     L.ab_packed = false;
     if (ab_on()) LRP_TRY(pack_ab_layer(li, w_dev, st));
+    L.t_packed = false;
+    if (table_on()) LRP_TRY(pack_table_layer(li, w_dev, st));
     L.norm_dirty = true;
     LRP_HIP_CHECK(hipMemcpyAsync(L.bias.p, b_dev, (size_t)L.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
     L.raw_w_dev.release(); L.raw_b_dev.release();   // stale from here on (the trainer's master buffer is the truth)
@@ -496,6 +503,7 @@ struct Encoder {
     L.have_w = true;
     L.norm_dirty = true;
     L.ab_packed = false;                               // (repacked by the next encode under a beta > 0 rule)
+    L.t_packed = false;                                // (... or under a rule table)
     encoded = 0;                                       // caches belong to the old weights
     return LRP_OK;
   }
@@ -545,6 +553,10 @@ struct Encoder {
     encoded = B;
     if (ab_on()) {
       const int rc = inhibitor_pass(B, st);
+      if (rc != LRP_OK) { encoded = 0; return rc; }
+    }
+    if (table_on() && table_runs()) {
+      const int rc = table_pass(B, st);
       if (rc != LRP_OK) { encoded = 0; return rc; }
     }
     features_only = false;
@@ -1038,7 +1050,319 @@ struct Encoder {
     if (!img_fused()) {
       const ConvLayer& L0 = layers[0];
       hipLaunchKernelGGL(img_stencil_kernel, dim3(stream_grid((size_t)n * L0.H * L0.W)), dim3(256), 0, st, S, images.as<float>(), row2img_dev,
-                         R_img_dev, n, L0.H, L0.W, 0);
+                         R_img_dev, n, L0.H, L0.W, 0, 0.f, 0.f);
+      LRP_HIP_CHECK(hipGetLastError());
+    }
+    return LRP_OK;
+  }
+
+
+  // ---- rule table (lrp_set_cnn_rules): one rule per conv ----
+  // Layer l reads k_l relevance chains S_l = R_l / den_l — two for alpha-beta with beta > 0, one otherwise — as one tensor against one
+  // tap-flipped matrix ([alpha w+ ; -beta w-], w+ or w) and applies the k_{l-1} gates of layer l-1's rule in its epilogue: the
+  // launches of explain_ab, plus "two chains in, one gate" (the ordinary MUL epilogue over Cin = 2 Cout) and "one chain in, two
+  // gates" (the dual-gate epilogue over Cin = Cout).  The gates that are not the forward's come from table_pass at encode.
+  // Dense launches only: no compact pool interface, no folded image layer, no sparse or weights-in-registers forms.
+  struct ConvRule {
+    int kind = LRP_RULE_ALPHA_BETA, bias = 1;
+    float alpha = 1.f, beta = 0.f, eps = 0.f, low = 0.f, high = 0.f;
+    int chains() const { return kind == LRP_RULE_ALPHA_BETA && beta > 0.f ? 2 : 1; }
+    bool own_gate() const { return kind != LRP_RULE_ALPHA_BETA || !bias; }       // activator gate not the forward's a / safe(Z+)
+    bool input_only() const { return kind == LRP_RULE_FLAT || kind == LRP_RULE_WSQUARE || kind == LRP_RULE_BOUNDED; }
+  };
+  std::vector<ConvRule> table;                         // empty: no table (the default walk or set_rule's)
+  DevBuf zt_top, wsq_zc;                               // the top layer's activator denominator where it is not ztop; w-square's border classes
+  DevBuf a1b;                                          // BoundedRule: im2col of the image layer over (x - low | x - high) — a1 stays the forward's (the fine-tune step reads it)
+  bool table_on() const { return !table.empty(); }
+  bool table_has_eps() const {
+    for (const ConvRule& r : table)
+      if (r.kind == LRP_RULE_EPSILON) return true;
+    return false;
+  }
+  // epsilon kinds are exact-fp32 only (their gate a / (a + eps) is a step in a for small eps: a ReLU decision the fp16-pair forward
+  // takes differently moves the map by O(1)); fp16 pairs have no table walk at all
+  bool table_runs() const { return !walk_f16 && (!table_has_eps() || prec == PREC_FP32); }
+  bool table_split() const { return ab_split() && !table_has_eps(); }
+  void clear_table() {
+    if (!table_on()) return;
+    table.clear();
+    keep_for_rule = ab_on();
+    keep_acts = keep_for_train || keep_for_rule;
+    encoded = 0;
+  }
+  // `rules` is validated (engine.hip) and is not the same alpha-beta-with-bias record on every layer
+  // does layer li of `rules` walk on the default walk's own backward matrix (w+ tap-flipped; the image layer: w+ ; w-)?
+  static bool rule_on_default_matrix(const ConvRule& r) { return r.kind == LRP_RULE_ALPHA_BETA && r.bias && r.chains() == 1; }
+  static int table_chains(const std::vector<ConvRule>& rules) {
+    int k = 1;
+    for (const ConvRule& r : rules) k = std::max(k, r.chains());
+    return k;
+  }
+  int set_table(const std::vector<ConvRule>& rules, int64_t* total) {
+    // a buffer appears, or grows, with the first table that needs it at that size: everything is sized by THIS table's chain counts
+    auto mk = [&](DevBuf& d, size_t floats) -> int {
+      if (d.p && d.bytes >= floats * sizeof(float)) return LRP_OK;
+      if (d.p && total) *total -= (int64_t)d.bytes;
+      LRP_TRY(d.alloc(floats * sizeof(float), total));
+      LRP_HIP_CHECK(hipMemset(d.p, 0, d.bytes));
+      return LRP_OK;
+    };
+    const size_t B = (size_t)max_images, NT = (size_t)max_tokens, nl = layers.size();
+    for (size_t i = 0; i < nl; ++i) {
+      ConvLayer& L = layers[i];
+      const ConvRule& r = rules[i];
+      const bool top = i + 1 == nl;
+      const int k = r.chains();
+      if (!top && r.own_gate()) LRP_TRY(mk(L.Gt, B * L.act_elems()));
+      if (!top && k == 2) LRP_TRY(mk(L.Gn, B * L.act_elems()));
+      const bool fwd_a = (r.kind == LRP_RULE_ALPHA_BETA && !r.bias) || r.kind == LRP_RULE_BOUNDED;
+      const size_t nf = i == 0 ? (size_t)conv_npad(L.cout) * 64 : (size_t)conv_npad(L.cout) * 9 * conv_cinp(L.cin);
+      const size_t nb = i == 0 ? (size_t)conv_npad(IMG_T_COLS) * conv_cinp(k * L.cout) : (size_t)conv_npad(L.cin) * 9 * conv_cinp(k * L.cout);
+      if (fwd_a) { LRP_TRY(mk(L.w_fwd_t, nf)); if (i) LRP_TRY(mk(L.w_fwd_ts, nf)); }
+      if (k == 2) { LRP_TRY(mk(L.w_fwd_n, nf)); if (i) LRP_TRY(mk(L.w_fwd_ns, nf)); }
+      if (!rule_on_default_matrix(r)) { LRP_TRY(mk(L.w_bwd_t, nb)); LRP_TRY(mk(L.w_bwd_t_s, nb)); }
+      L.t_packed = false;
+    }
+    if (rules.back().own_gate()) LRP_TRY(mk(zt_top, B * layers.back().act_elems()));
+    if (rules.back().chains() == 2) LRP_TRY(mk(zntop, B * layers.back().act_elems()));
+    if (rules[0].kind == LRP_RULE_WSQUARE) LRP_TRY(mk(wsq_zc, (size_t)16 * layers[0].cout));
+    if (rules[0].kind == LRP_RULE_BOUNDED) LRP_TRY(mk(a1b, B * img_h * img_w * 64));
+    if (table_chains(rules) == 2) {                      // (one chain everywhere: the default walk's ping-pong s0 / s1)
+      const size_t tok = std::max(2 * max_act_elems(), (size_t)img_h * img_w * IMG_T_COLS);
+      LRP_TRY(mk(s0ab, NT * tok)); LRP_TRY(mk(s1ab, NT * tok));
+    }
+    LRP_TRY(enable_keep_acts(total, true));
+    table = rules;
+    encoded = 0;
+    return LRP_OK;
+  }
+  // the table's operand copies of layer li from w_dev (HWIO, device)
+  int pack_table_layer(int li, const float* w_dev, hipStream_t st) {
+    ConvLayer& L = layers[li];
+    const ConvRule& r = table[li];
+    const int k = r.chains();
+    auto split = [&](const float* src, float* dst, size_t n) {
+      hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n / 8)), dim3(256), 0, st, src, dst, n / 8);
+    };
+    const bool fwd_a = (r.kind == LRP_RULE_ALPHA_BETA && !r.bias) || r.kind == LRP_RULE_BOUNDED;
+    const bool own_bwd = !rule_on_default_matrix(r);
+    if (own_bwd) {                                       // the last table's layout may have been another: cleared in stream order
+      LRP_HIP_CHECK(hipMemsetAsync(L.w_bwd_t.p, 0, L.w_bwd_t.bytes, st));
+      LRP_HIP_CHECK(hipMemsetAsync(L.w_bwd_t_s.p, 0, L.w_bwd_t_s.bytes, st));
+    }
+    if (li == 0) {
+      const int Kb = conv_cinp(k * L.cout);
+      if (!own_bwd) { L.t_packed = true; return LRP_OK; }   // (alpha-beta (1, 0) with bias needs nothing of its own)
+      hipLaunchKernelGGL(pack_image_layer_rule_dev_kernel, dim3((27 * L.cout + 255) / 256), dim3(256), 0, st, w_dev,
+                         fwd_a ? L.w_fwd_t.as<float>() : (float*)nullptr, k == 2 ? L.w_fwd_n.as<float>() : (float*)nullptr, L.w_bwd_t.as<float>(),
+                         L.cout, Kb, r.kind, k, r.alpha, r.beta);
+      split(L.w_bwd_t.as<float>(), L.w_bwd_t_s.as<float>(), (size_t)conv_npad(IMG_T_COLS) * Kb);
+      if (r.kind == LRP_RULE_WSQUARE)
+        hipLaunchKernelGGL(wsquare_class_kernel, dim3((16 * L.cout + 255) / 256), dim3(256), 0, st, w_dev, wsq_zc.as<float>(), L.cout);
+    } else {
+      const int CPi = conv_cinp(L.cin), CPk = conv_cinp(k * L.cout);
+      const size_t nf = (size_t)conv_npad(L.cout) * 9 * CPi, nb = (size_t)conv_npad(L.cin) * 9 * CPk;
+      auto pack = [&](float* dst, int bwd, int chains, float p0, float q0, float p1, float q1) {
+        const int rows = bwd ? L.cin : L.cout, CP = bwd ? CPk : CPi;
+        hipLaunchKernelGGL(pack_conv_rule_dev_kernel, dim3(stream_grid((size_t)rows * 9 * CP)), dim3(256), 0, st, w_dev, dst, bwd, L.cin, L.cout, CP,
+                           rows, chains, p0, q0, p1, q1);
+      };
+      if (fwd_a) { pack(L.w_fwd_t.as<float>(), 0, 1, 1.f, 0.f, 0.f, 0.f); split(L.w_fwd_t.as<float>(), L.w_fwd_ts.as<float>(), nf); }
+      if (k == 2) { pack(L.w_fwd_n.as<float>(), 0, 1, 0.f, 1.f, 0.f, 0.f); split(L.w_fwd_n.as<float>(), L.w_fwd_ns.as<float>(), nf); }
+      if (own_bwd) {
+        if (r.kind == LRP_RULE_EPSILON) pack(L.w_bwd_t.as<float>(), 1, 1, 1.f, 1.f, 0.f, 0.f);
+        else if (k == 2) pack(L.w_bwd_t.as<float>(), 1, 2, r.alpha, 0.f, 0.f, -r.beta);
+        else pack(L.w_bwd_t.as<float>(), 1, 1, 1.f, 0.f, 0.f, 0.f);          // (alpha-beta (1, 0) without the bias: w+)
+        split(L.w_bwd_t.as<float>(), L.w_bwd_t_s.as<float>(), nb);
+      }
+    }
+    LRP_HIP_CHECK(hipGetLastError());
+    L.t_packed = true;
+    L.ab_packed = false;                                 // (w_fwd_n is shared with set_rule's matrices: that path packs again)
+    return LRP_OK;
+  }
+  const float* table_gate(int li) const { return table[li].own_gate() ? layers[li].Gt.as<float>() : layers[li].G.as<float>(); }
+  // Behind the forward, like inhibitor_pass: per layer the denominators its rule needs beyond the forward's Z+ — over the kept layer
+  // inputs, exact fp32 or three-term split-bf16 with the handle (epsilon tables: fp32) — and the gates from them.  A pooled layer's
+  // gates take the arg-max mask from G+.
+  int table_pass(int B, hipStream_t st) {
+    if (gates_pending) {
+      LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_gates, 0));
+      gates_pending = false;
+    }
+    const bool split = table_split();
+    for (size_t li = 0; li < layers.size(); ++li) {
+      ConvLayer& L = layers[li];
+      const ConvRule& r = table[li];
+      if (!L.t_packed) {
+        if (!L.raw_w_dev.p) return fail(LRP_ERR_STATE, "layer '%s': set its weights again after a change of the CNN rule", L.name.c_str());
+        LRP_TRY(pack_table_layer((int)li, L.raw_w_dev.as<float>(), st));
+      }
+      const bool top = li + 1 == layers.size();
+      if (!top && L.pool_after) LRP_TRY(full_gate((int)li, st));
+      // one denominator conv: matrix (fp32, split8 or nullptr), bias or none, into `dst`
+      auto den_conv = [&](const float* w32, const float* ws, bool bias, bool bounded, float* dst) -> int {
+        ConvArgs cz;
+        int zprec = PREC_FP32;
+        if (li == 0 && bounded) {                        // its own im2col matrix: a1 stays what the forward built
+          const size_t tot = (size_t)B * img_h * img_w * 8;
+          hipLaunchKernelGGL(im2col_image_bounded_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st, images.as<float>(),
+                             a1b.as<float>(), B, img_h, img_w, r.low, r.high);
+          LRP_HIP_CHECK(hipGetLastError());
+          cz = ConvArgs{};
+          cz.in = a1b.as<float>(); cz.NB = B * L.H * L.W; cz.H = 1; cz.W = 1; cz.Cin = 64; cz.CinP = 64; cz.taps = 1;
+          cz.wpk = w32;
+        } else if (li == 0) {
+          LRP_TRY(im2col_gemm_args(B, st, cz));
+          cz.wpk = w32;
+        } else {
+          const float* x = layer_input((int)li);
+          if (split && ws) {
+            LRP_TRY(split_copy(x, (size_t)B * L.H * L.W * L.cin / 8, st));
+            x = bufXs.as<float>();
+            zprec = PREC_BF16X3;
+          }
+          cz = fwd_conv_args(L, B, x);
+          cz.wpk = zprec == PREC_BF16X3 ? ws : w32;
+        }
+        if (!bias) cz.bias = nullptr;
+        cz.N = L.cout;
+        cz.out = dst;
+        LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, st, zprec));
+        return LRP_OK;
+      };
+      // gate from (value, denominator): a_l where no pool follows, the pooled activation under G+'s mask otherwise
+      auto gate = [&](const float* z, int zmode, float* out) -> int {
+        const size_t n4 = (size_t)B * L.act_elems() / 4;
+        hipLaunchKernelGGL(rule_gate_kernel, dim3(stream_grid(n4)), dim3(256), 0, st, L.pool_after ? (const float*)nullptr : L.Akeep.as<float>(),
+                           L.pool_after ? L.G.as<float>() : (const float*)nullptr, L.pool_after ? L.P.as<float>() : (const float*)nullptr, z,
+                           wsq_zc.as<float>(), out, B, L.H, L.W, L.cout, zmode, r.eps);
+        LRP_HIP_CHECK(hipGetLastError());
+        return LRP_OK;
+      };
+      float* zbuf = bufZ.as<float>();
+      if (r.own_gate()) {                                // the activator chain
+        float* zdst = top ? zt_top.as<float>() : zbuf;
+        switch (r.kind) {
+          case LRP_RULE_ALPHA_BETA:                      // without the bias: conv(x+, w+) + conv(x-, w-)
+            LRP_TRY(den_conv(L.w_fwd_t.as<float>(), L.w_fwd_ts.as<float>(), false, false, zdst));
+            if (!top) LRP_TRY(gate(zbuf, 0, L.Gt.as<float>()));
+            break;
+          case LRP_RULE_BOUNDED:
+            LRP_TRY(den_conv(L.w_fwd_t.as<float>(), nullptr, false, true, zdst));
+            if (!top) LRP_TRY(gate(zbuf, 0, L.Gt.as<float>()));
+            break;
+          case LRP_RULE_EPSILON:
+            // behind a ReLU relevance arrives only where a > 0, and there Z = a with the bias: no conv.  The top layer's relevance
+            // is the caller's, and without the bias Z is another sum: one conv with the full w (the exact activation conv's matrix;
+            // the image layer: the w rows of its dual matrix)
+            if (top || !r.bias) {
+              LRP_TRY(den_conv(li == 0 ? L.w_fwd.as<float>() : L.w_fwd_a.as<float>(), nullptr, r.bias != 0, false, zdst));
+              if (top) {
+                const size_t nz = (size_t)B * L.act_elems();
+                hipLaunchKernelGGL(stab_eps_kernel, dim3(stream_grid(nz)), dim3(256), 0, st, zdst, nz, r.eps);
+                LRP_HIP_CHECK(hipGetLastError());
+              } else {
+                LRP_TRY(gate(zbuf, 1, L.Gt.as<float>()));
+              }
+            } else {
+              LRP_TRY(gate(nullptr, 2, L.Gt.as<float>()));
+            }
+            break;
+          case LRP_RULE_FLAT: LRP_TRY(gate(nullptr, 3, L.Gt.as<float>())); break;
+          case LRP_RULE_WSQUARE: LRP_TRY(gate(nullptr, 4, L.Gt.as<float>())); break;
+        }
+      }
+      if (r.chains() == 2) {                             // the inhibitor chain: conv(x+, w-) + conv(x-, w+), with the bias or without
+        if (top) {
+          LRP_TRY(den_conv(L.w_fwd_n.as<float>(), L.w_fwd_ns.as<float>(), r.bias != 0, false, zntop.as<float>()));
+        } else {
+          LRP_TRY(den_conv(L.w_fwd_n.as<float>(), L.w_fwd_ns.as<float>(), r.bias != 0, false, zbuf));
+          const size_t n4 = (size_t)B * L.act_elems() / 4;
+          if (L.pool_after) {
+            hipLaunchKernelGGL(pool_gate_inh_kernel, dim3(stream_grid(n4)), dim3(256), 0, st, L.G.as<f32x4>(), L.P.as<float>(),
+                               reinterpret_cast<const f32x4*>(zbuf), L.Gn.as<f32x4>(), B, L.H, L.W, L.cout);
+            LRP_HIP_CHECK(hipGetLastError());
+          } else {
+            LRP_TRY(gate(zbuf, 0, L.Gn.as<float>()));
+          }
+        }
+      }
+    }
+    return LRP_OK;
+  }
+  // the table's walk
+  int explain_table(int n, const int* row2img_dev, const float* R_feat_dev, float* R_img_dev, hipStream_t st) {
+    if (walk_f16) return fail(LRP_ERR_UNSUPPORTED, "LRP_PREC_F16X2 has no rule-table walk");
+    if (!table_runs()) return fail(LRP_ERR_UNSUPPORTED, "epsilon rules run in LRP_PREC_FP32 only");
+    const bool split = table_split();
+    const int rp = split ? PREC_BF16X3 : PREC_FP32;
+    for (size_t li = 1; li < layers.size(); ++li) {      // every launch is one conv_plan answers: asked before the first one runs
+      const ConvLayer& L = layers[li];
+      ConvAsk q;
+      q.epi = layers[li - 1].pool_after ? EPI_MUL_UP2 : EPI_MUL; q.prec = rp;
+      q.NB = n; q.H = L.H; q.W = L.W; q.N = L.cin; q.Cin = table[li].chains() * L.cout; q.taps = 9;
+      q.dual_mul = table[li - 1].chains() == 2;
+      if (!conv_plan(q).ok)
+        return fail(LRP_ERR_UNSUPPORTED, "conv %d: no launch reads %d chain(s) of %d channels into %d gate(s)", (int)li, table[li].chains(), L.cout,
+                    table[li - 1].chains());
+    }
+    const bool two = table_chains(table) == 2;
+    float *S = two ? s0ab.as<float>() : s0.as<float>(), *Snext = two ? s1ab.as<float>() : s1.as<float>();
+    {
+      const ConvLayer& T = layers.back();
+      const ConvRule& r = table.back();
+      const float* za = r.own_gate() ? zt_top.as<float>() : ztop.as<float>();
+      const size_t pixels = (size_t)n * T.H * T.W, per = T.act_elems();
+      if (r.chains() == 2) {
+        const size_t items = pixels * (T.cout / (split ? 8 : 4));
+        if (split)
+          hipLaunchKernelGGL(chain_join_kernel<true>, dim3(stream_grid(items)), dim3(256), 0, st, R_feat_dev, R_feat_dev, za, zntop.as<float>(),
+                             row2img_dev, S, pixels, T.H * T.W, T.cout);
+        else
+          hipLaunchKernelGGL(chain_join_kernel<false>, dim3(stream_grid(items)), dim3(256), 0, st, R_feat_dev, R_feat_dev, za, zntop.as<float>(),
+                             row2img_dev, S, pixels, T.H * T.W, T.cout);
+      } else if (split) {
+        hipLaunchKernelGGL(top_divide_split_kernel, dim3(stream_grid((size_t)n * per / 8)), dim3(256), 0, st, R_feat_dev, za, row2img_dev, S, n, per / 8);
+      } else {
+        hipLaunchKernelGGL(top_divide_kernel, dim3(stream_grid((size_t)n * per / 4)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(R_feat_dev),
+                           reinterpret_cast<const f32x4*>(za), row2img_dev, reinterpret_cast<f32x4*>(S), n, per / 4);
+      }
+      LRP_HIP_CHECK(hipGetLastError());
+    }
+    const ConvRule& r0 = table[0];
+    const int img_mode = r0.kind == LRP_RULE_ALPHA_BETA ? 0 : r0.kind == LRP_RULE_EPSILON ? 2 : r0.kind == LRP_RULE_BOUNDED ? 3 : 1;
+    for (int li = (int)layers.size() - 1; li >= 0; --li) {
+      const ConvLayer& L = layers[li];
+      const int k = table[li].chains();
+      ConvArgs ca = conv3x3_args(L, n, S, k * L.cout);
+      if (rule_on_default_matrix(table[li])) ca.wpk = split ? L.w_bwd_s.as<float>() : L.w_bwd.as<float>();
+      else ca.wpk = split ? L.w_bwd_t_s.as<float>() : L.w_bwd_t.as<float>();
+      ca.row2img = row2img_dev;
+      int epi;
+      if (li == 0 && img_fused()) {
+        ca.taps = 1; ca.N = IMG_T_COLS; ca.out = R_img_dev; ca.ximg = images.as<float>(); ca.img_mode = img_mode;
+        ca.img_lo = r0.low; ca.img_hi = r0.high;
+        epi = EPI_IMG_STENCIL;
+      } else if (li == 0) {
+        ca.NB = n * L.H * L.W; ca.H = 1; ca.W = 1; ca.taps = 1;
+        ca.N = IMG_T_COLS; ca.out = Snext; epi = EPI_STORE;
+      } else {
+        const ConvLayer& P = layers[li - 1];
+        if (P.pool_after) LRP_TRY(full_gate(li - 1, st));
+        ca.N = L.cin; ca.aux = table_gate(li - 1); ca.out = Snext;
+        if (table[li - 1].chains() == 2) { ca.aux_b = P.Gn.as<float>(); ca.out_b = Snext + L.cin; ca.ostride = 2 * L.cin; }
+        epi = P.pool_after ? EPI_MUL_UP2 : EPI_MUL;
+      }
+      prof.begin(st);
+      LRP_HIP_CHECK(conv_launch(epi, ca, st, rp));
+      prof.end(st, (double)k * layer_flop(n, li));
+      std::swap(S, Snext);
+    }
+    if (!img_fused()) {
+      const ConvLayer& L0 = layers[0];
+      hipLaunchKernelGGL(img_stencil_kernel, dim3(stream_grid((size_t)n * L0.H * L0.W)), dim3(256), 0, st, S, images.as<float>(), row2img_dev,
+                         R_img_dev, n, L0.H, L0.W, img_mode, r0.low, r0.high);
       LRP_HIP_CHECK(hipGetLastError());
     }
     return LRP_OK;
@@ -1058,6 +1382,7 @@ struct Encoder {
     if (walk < 0 || walk > 3) return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
     if (encoded < 1 || features_only) return fail(LRP_ERR_STATE, "lrp_encode_images must run before the CNN explain");
     if (gates_pending) LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_gates, 0));   // gates / Z_top come from the side stream
+    if (table_on() && walk == 0 && !layer_hook) return explain_table(n, row2img_dev, R_feat_dev, R_img_dev, st);
     if (ab_on() && walk == 0 && !layer_hook) {           // (the gradient walks and the fine-tune step ignore the rule)
       if (walk_f16) return fail(LRP_ERR_UNSUPPORTED, "LRP_PREC_F16X2 has no alpha-beta walk with beta > 0 (its per-token scaling is per chain)");
       return explain_ab(n, row2img_dev, R_feat_dev, R_img_dev, st);
@@ -1151,7 +1476,7 @@ struct Encoder {
     if (!img_fused()) {  // S now holds T (n, H, W, 54): 9-tap shift-and-add and the x+/x- selection
       const ConvLayer& L0 = layers[0];
       hipLaunchKernelGGL(img_stencil_kernel, dim3(stream_grid((size_t)n * L0.H * L0.W)), dim3(256), 0, st, S,
-                         images.as<float>(), row2img_dev, R_img_dev, n, L0.H, L0.W, walk == 0 ? 0 : walk == 2 ? 2 : 1);
+                         images.as<float>(), row2img_dev, R_img_dev, n, L0.H, L0.W, walk == 0 ? 0 : walk == 2 ? 2 : 1, 0.f, 0.f);
       LRP_HIP_CHECK(hipGetLastError());
     }
     return LRP_OK;

@@ -429,6 +429,10 @@ int lrp_set_cnn_rule(lrp_handle* h, float alpha, float beta) {
       if (beta > 0.f) return fail(LRP_ERR_UNSUPPORTED, "the ResNet encoder's walk is alpha1beta0 only");
       return LRP_OK;
     }
+    if (h->enc.table_on()) {                             // the one rule replaces a table (lrp_set_cnn_rules)
+      LRP_TRY(h->trainer.drop_early_forward(nullptr));
+      h->enc.clear_table();
+    }
     if (alpha == h->enc.ab_alpha && beta == h->enc.ab_beta) return LRP_OK;
     LRP_TRY(h->trainer.drop_early_forward(nullptr));
     LRP_TRY(h->enc.set_rule(alpha, beta, &h->ws_bytes));
@@ -441,6 +445,67 @@ int lrp_set_cnn_rule(lrp_handle* h, float alpha, float beta) {
     }
     return LRP_OK;
   });
+}
+
+int lrp_set_cnn_rules(lrp_handle* h, const lrp_conv_rule* rules, int32_t n_rules) {
+  std::vector<Encoder::ConvRule> t;
+  bool uniform = true;
+  const int rc = with_handle(h, [&]() -> int {
+    if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "the ResNet encoder's walk has no rule table");
+    if (!rules || n_rules != (int)h->enc.layers.size())
+      return fail(LRP_ERR_INVALID, "one rule per conv: %d given, %d convs", rules ? n_rules : 0, (int)h->enc.layers.size());
+    t.resize((size_t)n_rules);
+    for (int i = 0; i < n_rules; ++i) {
+      const lrp_conv_rule& r = rules[i];
+      Encoder::ConvRule& o = t[(size_t)i];
+      if (r.kind < LRP_RULE_ALPHA_BETA || r.kind > LRP_RULE_BOUNDED) return fail(LRP_ERR_INVALID, "conv %d: unknown rule kind %d", i, r.kind);
+      o.kind = r.kind;
+      if (o.input_only() && i > 0)
+        return fail(LRP_ERR_INVALID, "conv %d: flat, w-square and bounded are input-layer rules (above it they need relevance at dead units)", i);
+      o.bias = 0;
+      if (r.kind == LRP_RULE_ALPHA_BETA || r.kind == LRP_RULE_EPSILON) {
+        if (r.bias != 0 && r.bias != 1) return fail(LRP_ERR_INVALID, "conv %d: bias must be 0 or 1", i);
+        o.bias = r.bias;
+      }
+      if (r.kind == LRP_RULE_ALPHA_BETA) {               // lrp_set_cnn_rule's check
+        if (!(r.alpha >= 1.f)) return fail(LRP_ERR_INVALID, "conv %d: alpha should be >= 1 (alpha=%g)", i, (double)r.alpha);
+        if (!(r.beta >= 0.f)) return fail(LRP_ERR_INVALID, "conv %d: beta should be >= 0 (beta=%g)", i, (double)r.beta);
+        if (!(fabs((double)r.alpha - (double)r.beta - 1.0) <= 6e-8 * ((double)r.alpha + (double)r.beta)))
+          return fail(LRP_ERR_INVALID, "conv %d: alpha - beta should be 1 (alpha=%g, beta=%g)", i, (double)r.alpha, (double)r.beta);
+        o.alpha = r.alpha; o.beta = r.alpha - 1.f;
+      } else if (r.kind == LRP_RULE_EPSILON) {
+        if (!(r.eps >= 0.f) || !(r.eps < 3.0e38f)) return fail(LRP_ERR_INVALID, "conv %d: epsilon should be >= 0 (eps=%g)", i, (double)r.eps);
+        o.eps = r.eps;
+      } else if (r.kind == LRP_RULE_BOUNDED) {
+        if (!(r.low < r.high) || !(fabsf(r.low) < 3.0e38f) || !(fabsf(r.high) < 3.0e38f))
+          return fail(LRP_ERR_INVALID, "bounded rule: low < high (low=%g, high=%g)", (double)r.low, (double)r.high);
+        o.low = r.low; o.high = r.high;
+      }
+      if (o.kind != LRP_RULE_ALPHA_BETA || !o.bias || o.alpha != t[0].alpha) uniform = false;
+    }
+    if (uniform) return LRP_OK;                          // (lrp_set_cnn_rule below)
+    if (t[0].input_only() && n_rules < 2) return fail(LRP_ERR_UNSUPPORTED, "an input-layer rule needs a conv above the image layer");
+    Encoder& e = h->enc;
+    if (e.table_on()) {                                  // the same table again changes nothing
+      bool same = true;
+      for (size_t i = 0; i < t.size(); ++i) {
+        const Encoder::ConvRule &a = e.table[i], &b = t[i];
+        if (a.kind != b.kind || a.bias != b.bias || a.alpha != b.alpha || a.eps != b.eps || a.low != b.low || a.high != b.high) same = false;
+      }
+      if (same) return LRP_OK;
+    }
+    LRP_TRY(h->trainer.drop_early_forward(nullptr));
+    LRP_TRY(e.set_rule(1.f, 0.f, &h->ws_bytes));         // (the one-rule walk's buffers stay, idle)
+    LRP_TRY(e.set_table(t, &h->ws_bytes));
+    if (h->trainer.ready) {                              // the fine-tune step owns the weights: see lrp_set_cnn_rule
+      for (size_t li = 0; li < e.layers.size(); ++li)
+        LRP_TRY(e.pack_table_layer((int)li, h->trainer.master.as<float>() + h->trainer.params[2 * li].off, nullptr));
+      LRP_HIP_CHECK(hipStreamSynchronize(nullptr));
+    }
+    return LRP_OK;
+  });
+  // the same alpha-beta record with bias on every layer IS the one-rule entry: its path, to the bit
+  return rc == LRP_OK && uniform ? lrp_set_cnn_rule(h, t[0].alpha, t[0].beta) : rc;
 }
 
 int lrp_set_fast_layers(lrp_handle* h, int64_t mask) {
@@ -597,6 +662,65 @@ int lrp_op_conv_ab(const float* sp_dev, const float* sn_dev, const float* w_hwio
     ca.in = sj.as<float>(); ca.wpk = split ? wabs.as<float>() : wab.as<float>();
     ca.NB = NB; ca.H = H; ca.W = W; ca.Cin = 2 * Cout; ca.CinP = CP2; ca.N = Cin; ca.taps = 9;
     ca.aux = gp_dev; ca.aux_b = gn_dev; ca.out = outp_dev; ca.out_b = outn_dev; ca.ostride = Cin; ca.out_plain = 1;
+    LRP_HIP_CHECK(conv_launch(pool ? EPI_MUL_UP2 : EPI_MUL, ca, st, split ? PREC_BF16X3 : PREC_FP32));
+    LRP_HIP_CHECK(hipStreamSynchronize(st));             // the operand copies are freed on return
+    return LRP_OK;
+  });
+}
+
+int lrp_op_conv_rule(const float* s0_dev, const float* s1_dev, const float* w_hwio_host, int32_t chains_in, int32_t gates_out, float p0,
+                     float q0, float p1, float q1, const float* g0_dev, const float* g1_dev, float* out0_dev, float* out1_dev, int32_t NB,
+                     int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t pool, int32_t split, void* stream) {
+  return guarded([&]() -> int {
+    if ((chains_in != 1 && chains_in != 2) || (gates_out != 1 && gates_out != 2)) return fail(LRP_ERR_INVALID, "chains_in and gates_out are 1 or 2");
+    if (!s0_dev || !w_hwio_host || !g0_dev || !out0_dev || (chains_in == 2 && !s1_dev) || (gates_out == 2 && (!g1_dev || !out1_dev)))
+      return fail(LRP_ERR_INVALID, "null argument");
+    if (NB < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return fail(LRP_ERR_INVALID, "NB, H, W, Cin, Cout must be >= 1");
+    const int g = split ? 7 : 3;
+    if ((Cin & g) || (Cout & g)) return fail(LRP_ERR_UNSUPPORTED, "channels must be multiples of %d", g + 1);
+    {
+      ConvAsk q;                                         // the launch below, as conv_launch will ask for it
+      q.epi = pool ? EPI_MUL_UP2 : EPI_MUL; q.prec = split ? PREC_BF16X3 : PREC_FP32;
+      q.NB = NB; q.H = H; q.W = W; q.N = Cin; q.Cin = chains_in * Cout; q.taps = 9; q.dual_mul = gates_out == 2;
+      if (!conv_plan(q).ok)
+        return fail(LRP_ERR_UNSUPPORTED, "no launch reads %d chain(s) of %d channels into %d gate(s) of %d", chains_in, Cout, gates_out, Cin);
+    }
+    const int64_t up = pool ? 4 : 1, lim = (int64_t)1 << 31;
+    if ((int64_t)NB * H * W * 2 * Cout >= lim || (int64_t)9 * Cin * Cout >= lim || (int64_t)NB * H * W * up * Cin * gates_out >= lim)
+      return fail(LRP_ERR_UNSUPPORTED, "operator entry: tensor too large");
+    hipStream_t st = S(stream);
+    const int CPk = conv_cinp(chains_in * Cout), Np = conv_npad(Cin);
+    DevBuf wraw, wk, wks, sj;
+    LRP_TRY(wraw.alloc((size_t)9 * Cin * Cout * sizeof(float), nullptr));
+    LRP_HIP_CHECK(hipMemcpy(wraw.p, w_hwio_host, wraw.bytes, hipMemcpyHostToDevice));
+    const size_t nb = (size_t)Np * 9 * CPk;
+    LRP_TRY(wk.alloc(nb * sizeof(float), nullptr));
+    LRP_HIP_CHECK(hipMemsetAsync(wk.p, 0, wk.bytes, st));
+    hipLaunchKernelGGL(pack_conv_rule_dev_kernel, dim3(stream_grid((size_t)Cin * 9 * CPk)), dim3(256), 0, st, wraw.as<float>(), wk.as<float>(), 1,
+                       Cin, Cout, CPk, Cin, chains_in, p0, q0, p1, q1);
+    const size_t pixels = (size_t)NB * H * W;
+    const float* in = s0_dev;
+    if (chains_in == 2 || split) LRP_TRY(sj.alloc(pixels * chains_in * Cout * sizeof(float), nullptr));
+    if (split) {
+      LRP_TRY(wks.alloc(nb * sizeof(float), nullptr));
+      hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(nb / 8)), dim3(256), 0, st, wk.as<float>(), wks.as<float>(), nb / 8);
+      if (chains_in == 2)
+        hipLaunchKernelGGL(chain_join_kernel<true>, dim3(stream_grid(pixels * (Cout / 8))), dim3(256), 0, st, s0_dev, s1_dev, (const float*)nullptr,
+                           (const float*)nullptr, (const int*)nullptr, sj.as<float>(), pixels, 1, Cout);
+      else
+        hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(pixels * Cout / 8)), dim3(256), 0, st, s0_dev, sj.as<float>(), pixels * Cout / 8);
+      in = sj.as<float>();
+    } else if (chains_in == 2) {
+      hipLaunchKernelGGL(chain_join_kernel<false>, dim3(stream_grid(pixels * (Cout / 4))), dim3(256), 0, st, s0_dev, s1_dev, (const float*)nullptr,
+                         (const float*)nullptr, (const int*)nullptr, sj.as<float>(), pixels, 1, Cout);
+      in = sj.as<float>();
+    }
+    LRP_HIP_CHECK(hipGetLastError());
+    ConvArgs ca{};
+    ca.in = in; ca.wpk = split ? wks.as<float>() : wk.as<float>();
+    ca.NB = NB; ca.H = H; ca.W = W; ca.Cin = chains_in * Cout; ca.CinP = CPk; ca.N = Cin; ca.taps = 9;
+    ca.aux = g0_dev; ca.out = out0_dev; ca.out_plain = 1;
+    if (gates_out == 2) { ca.aux_b = g1_dev; ca.out_b = out1_dev; ca.ostride = Cin; }
     LRP_HIP_CHECK(conv_launch(pool ? EPI_MUL_UP2 : EPI_MUL, ca, st, split ? PREC_BF16X3 : PREC_FP32));
     LRP_HIP_CHECK(hipStreamSynchronize(st));             // the operand copies are freed on return
     return LRP_OK;

@@ -66,6 +66,7 @@ class LRPEngine(object):
         self.n_images = 0
         self.precision = "bf16x3"                       # library default for the reverse walk (set_precision)
         self.cnn_rule = (1, 0)                          # ... and for its conv rule (set_cnn_rule)
+        self.cnn_rules = None                           # ... or the table in its place (set_cnn_rules)
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -438,6 +439,33 @@ class LRPEngine(object):
             self.n_images = 0                            # the library dropped the caches of the other rule
             self.captions = None
         self.cnn_rule = (alpha, beta)
+        self.cnn_rules = None                           # (the one rule replaces a table: set_cnn_rules)
+
+    def set_cnn_rules(self, table):
+        """One rule per conv of the VGG-style encoder's LRP walk (lrp_set_cnn_rules), input layer first.  `table`: a list with one
+        entry per conv — ("alphabeta", alpha, beta, bias), ("epsilon", eps, bias), ("flat",), ("wsquare",), ("bounded", low, high)
+        (the last three at the input layer only) — or anything analyzer.rule_table() accepts with this engine's conv count.
+        The same alpha-beta rule with bias on every conv is set_cnn_rule(alpha, beta).  A change drops the encode caches: call
+        encode_images again.  Epsilon kinds need set_precision('fp32') (the explain calls raise NotImplementedError otherwise)."""
+        from .analyzer import normalize_rule
+        table = tuple(normalize_rule(r) for r in table)
+        arr = (_capi.LrpConvRule * max(1, len(table)))()
+        for rec, r in zip(arr, table):
+            if r[0] == "alphabeta":
+                rec.kind, rec.alpha, rec.beta, rec.bias = _capi.LRP_RULE_ALPHA_BETA, r[1], r[2], int(r[3])
+            elif r[0] == "epsilon":
+                rec.kind, rec.eps, rec.bias = _capi.LRP_RULE_EPSILON, r[1], int(r[2])
+            elif r[0] == "bounded":
+                rec.kind, rec.low, rec.high = _capi.LRP_RULE_BOUNDED, r[1], r[2]
+            else:
+                rec.kind = _capi.LRP_RULE_FLAT if r[0] == "flat" else _capi.LRP_RULE_WSQUARE
+        _capi.check(self._lib.lrp_set_cnn_rules(self._h, C.cast(arr, C.c_void_p), len(table)))
+        uniform = table[0][0] == "alphabeta" and table[0][3] and all(r == table[0] for r in table)
+        new_rule, new_table = ((table[0][1], table[0][2]), None) if uniform else (None, table)
+        if (new_rule, new_table) != (self.cnn_rule, getattr(self, "cnn_rules", None)):
+            self.n_images = 0                            # the library dropped the caches of the other rules
+            self.captions = None
+        self.cnn_rule, self.cnn_rules = new_rule, new_table
 
     def set_fast_layers(self, mask):
         """Which conv layers take the two-MFMA form in 'f16x2' mode (lrp_set_fast_layers): bit li of `mask`, an iterable of
@@ -521,6 +549,29 @@ def op_conv_ab(sp, sn, w_hwio, alpha, beta, gp, gn, pool=False, split_bf16=False
     _capi.check(lib.lrp_op_conv_ab(p(sp), p(sn), w.ctypes.data_as(C.c_void_p), float(alpha), float(beta), p(gp), p(gn), p(outp), p(outn),
                                    NB, H, W, Cin, Cout, int(bool(pool)), int(bool(split_bf16)), _cur_stream(sp.device)))
     return outp, outn
+
+
+def op_conv_rule(chains, w_hwio, coef, gates, pool=False, split_bf16=False):
+    """A launch of the rule table's walk (lrp_op_conv_rule): c = sum_j convT(chains[j], p_j w+ + q_j w-) in one GEMM, outputs
+    [c x g for g in gates], c repeated 2 x 2 with pool.  chains: one or two (NB, H, W, Cout) float32 device tensors, coef: a
+    (p, q) per chain, gates: one or two (NB, H u, W u, Cin) tensors; w_hwio (3, 3, Cin, Cout) numpy."""
+    lib = _capi.load()
+    w = np.ascontiguousarray(w_hwio, dtype=np.float32)
+    Cin, Cout = w.shape[2], w.shape[3]
+    chains = [t.contiguous() for t in chains]
+    gates = [t.contiguous() for t in gates]
+    NB, H, W, _ = chains[0].shape
+    u = 2 if pool else 1
+    assert len(chains) in (1, 2) and len(gates) in (1, 2) and len(coef) == len(chains)
+    assert all(tuple(t.shape) == (NB, H, W, Cout) for t in chains) and all(tuple(t.shape) == (NB, u * H, u * W, Cin) for t in gates)
+    outs = [torch.empty((NB, u * H, u * W, Cin), dtype=torch.float32, device=chains[0].device) for _ in gates]
+    p = lambda t: C.c_void_p(t.data_ptr())
+    opt = lambda ts, i: p(ts[i]) if len(ts) > i else None
+    pq = [float(v) for c in coef for v in c] + [0.0, 0.0]
+    _capi.check(lib.lrp_op_conv_rule(p(chains[0]), opt(chains, 1), w.ctypes.data_as(C.c_void_p), len(chains), len(gates), pq[0], pq[1],
+                                     pq[2], pq[3], p(gates[0]), opt(gates, 1), p(outs[0]), opt(outs, 1), NB, H, W, Cin, Cout,
+                                     int(bool(pool)), int(bool(split_bf16)), _cur_stream(chains[0].device)))
+    return outs
 
 
 def op_conv_pool_sparse(sc, pos, w_hwio, gate, reps=1):

@@ -47,7 +47,9 @@ class CaptionModelSpec(object):
     def __init__(self, weights, img_encoder="vgg16", hidden_dim=512, embedding_dim=512, L=196, D=512,
                  vocab_size=None, cnn_cfg=None, img_hw=(224, 224), resnet=None, cnn_rule=(1, 0)):
         """cnn_rule: the (alpha, beta) of the encoder's conv rule (LRPEngine.set_cnn_rule), or 'alpha1beta0' (the default:
-        LRPSequentialPresetA, E:32) / 'alpha2beta1' (LRPSequentialPresetB's conv rule); every explainer built on the spec
+        LRPSequentialPresetA, E:32) / 'alpha2beta1' (LRPSequentialPresetB's conv rule), or — VGG-style encoders — a preset name
+        of analyzer.PRESETS ('presetAflat', 'presetBflat', 'zplus', ...) or a list with one rule per conv, input layer first
+        (analyzer.normalize_rule; LRPEngine.set_cnn_rules: self.cnn_rules holds the table, self.cnn_rule is then None); every explainer built on the spec
         whose CNN half is the LRP walk applies it to its engine; the gradient-baseline classes do not (their walks ignore the
         rule, and setting it would cost them its encode pass and buffers for nothing).
         img_encoder 'vgg16' (config.py:36-40: block5_conv3, 196 x 512), 'vgg19' (config.py:37: block5_conv4) or
@@ -69,12 +71,32 @@ class CaptionModelSpec(object):
         self.vocab_size = vocab_size if vocab_size is not None else int(self.weights["output_W"].shape[1])
         self.cnn_cfg = list(cnn_cfg)
         self.img_hw = tuple(img_hw)
+        from .analyzer import PRESETS, infer_alpha_beta, rule_table
+        self.cnn_rule, self.cnn_rules = self._conv_rule(cnn_rule, PRESETS, infer_alpha_beta, rule_table)
+
+    def _conv_rule(self, cnn_rule, presets, infer_alpha_beta, rule_table):
+        """-> (cnn_rule, cnn_rules): the (alpha, beta) of the one-rule entry and None, or None and a per-conv table
+        (LRPEngine.set_cnn_rules); a table that is one alpha-beta rule with bias on every conv is that one rule"""
+        names = ("alpha1beta0", "alpha2beta1")
+        table = None
+        if isinstance(cnn_rule, str) and cnn_rule not in names:
+            if cnn_rule not in presets:
+                raise ValueError("cnn_rule must be (alpha, beta), 'alpha1beta0', 'alpha2beta1', one of %s or a list with a rule per conv"
+                                 % sorted(presets))
+            table = presets[cnn_rule]
+        elif isinstance(cnn_rule, list):
+            table = (cnn_rule, None)
+        if table is not None:
+            if self.resnet is not None:
+                raise NotImplementedError("the ResNet encoder's walk is alpha1beta0 only: no rule table, no preset %r" % (cnn_rule,))
+            table = rule_table(table[0], table[1], len(self.cnn_cfg))
+            r0 = table[0]
+            if r0[0] == "alphabeta" and r0[3] and all(r == r0 for r in table):
+                return (r0[1], r0[2]), None
+            return None, table
         if isinstance(cnn_rule, str):
-            if cnn_rule not in ("alpha1beta0", "alpha2beta1"):
-                raise ValueError("cnn_rule must be (alpha, beta), 'alpha1beta0' or 'alpha2beta1'")
             cnn_rule = (1, 0) if cnn_rule == "alpha1beta0" else (2, 1)
-        from .analyzer import infer_alpha_beta
-        self.cnn_rule = infer_alpha_beta(cnn_rule[0], cnn_rule[1], "CaptionModelSpec")
+        return infer_alpha_beta(cnn_rule[0], cnn_rule[1], "CaptionModelSpec"), None
 
 
 class ExplainImgCaptioningAttentionModel(object):
@@ -102,7 +124,11 @@ class ExplainImgCaptioningAttentionModel(object):
                                  eos_id=self._preprocessor.EOS_TOKEN_LABEL_ENCODED, device=device,
                                  resnet=getattr(model, "resnet", None))
         self._engine.set_weights(model.weights)
-        if self._applies_cnn_rule and tuple(getattr(model, "cnn_rule", (1, 0))) != (1, 0):
+        if self._applies_cnn_rule and getattr(model, "cnn_rules", None) is not None:
+            if any(r[0] == "epsilon" for r in model.cnn_rules):
+                self._engine.set_precision("fp32")      # (epsilon kinds run in exact fp32 only)
+            self._engine.set_cnn_rules(model.cnn_rules)
+        elif self._applies_cnn_rule and tuple(getattr(model, "cnn_rule", None) or (1, 0)) != (1, 0):
             self._engine.set_cnn_rule(*model.cnn_rule)
         self._CNN_explainer = _EngineAnalyzer(self._engine)      # LRPSequentialPresetA(image_model, EPS, 'replace'), E:32
         self._state_cache = {}
