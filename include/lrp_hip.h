@@ -270,7 +270,7 @@ int lrp_set_precision(lrp_handle* h, int32_t mode);
  * LRP_PREC_F16X2 mode (LRP_ERR_STATE from explain calls until lrp_encode_images ran again). */
 int lrp_set_fast_layers(lrp_handle* h, int64_t mask);
 
-/* ABI v10 (added without a version bump: purely additive).  The conv rule of the VGG-style encoder's LRP walk: AlphaBetaRule (relevance_rule.py:216-322, bias = True) with
+/* ABI v10 (added without a version bump: purely additive).  The conv rule of the encoder's LRP walk: AlphaBetaRule (relevance_rule.py:216-322, bias = True) with
  * alpha >= 1, beta >= 0, alpha - beta == 1 (relevance_based/utils.py:72-129; anything else LRP_ERR_INVALID).  The two floats are
  * the caller's numbers rounded one by one, so the difference is checked to that rounding (|alpha - beta - 1| <= 6e-8 (alpha + beta):
  * (1.3f, 0.3f) is accepted, (2, 0.5) is not) and the walk uses beta = alpha - 1 in float.  Default (1, 0):
@@ -284,7 +284,12 @@ int lrp_set_fast_layers(lrp_handle* h, int64_t mask);
  * A CHANGE drops the encode caches like lrp_set_precision: explain calls return LRP_ERR_STATE until lrp_encode_images ran
  * again.  The first beta > 0 allocates the second gates, the two-chain buffers, the kept layer inputs and the packed matrices
  * (counted in lrp_workspace_bytes; idle again at beta = 0); a handle that never sets a beta > 0 allocates nothing.
- * LRP_ERR_UNSUPPORTED: beta > 0 on a ResNet handle; and from the explain calls with beta > 0 in LRP_PREC_F16X2. */
+ * A ResNet handle takes the rule as well: per conv + BN unit a second gate with Z_inh = conv(x, w-) + b, computed by
+ * lrp_encode_images behind the unchanged forward (the pair-emitting path: the unit's own launch again against [w | w-]), the walk
+ * with units 3 and 2 of a bottleneck block as dual-gate launches and unit 1 / the projection as one-gate launches over both chains;
+ * LRP_PREC_BF16X3 and LRP_PREC_FP32.  It needs a stem width and stack widths that are multiples of 8 (the dual gate's granularity).
+ * LRP_ERR_UNSUPPORTED: beta > 0 on a ResNet handle with another width (at this call); from the explain calls with beta > 0 in
+ * LRP_PREC_F16X2 (VGG-style encoders) or for a launch lrp_conv_plan refuses. */
 int lrp_set_cnn_rule(lrp_handle* h, float alpha, float beta);
 
 /* Added without a version bump (purely additive).  A rule per conv for the VGG-style encoder's LRP walk: the

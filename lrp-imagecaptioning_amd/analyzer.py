@@ -116,7 +116,7 @@ class LRPAlphaBeta(LRPSequentialPresetA):
     """relevance_analyzer.py:578-620: every conv under AlphaBetaRule(alpha, beta, bias=True) (relevance_rule.py:216-322), max-pools
     by gradient routing — the same `analyze([X, R])` surface as LRPSequentialPresetA, on the engine's walk under
     lrp_set_cnn_rule(alpha, beta).  (1, 0) is LRPSequentialPresetA's walk to the bit; beta > 0 runs the two-chain walk
-    (VGG-style encoders).  bias=False is refused here: the IgnoreBias rules run on the rule table (LRPAlpha2Beta1IgnoreBias,
+    (VGG-style encoders, and a ResNet `ImageModelSpec` whose widths are multiples of 8).  bias=False is refused here: the IgnoreBias rules run on the rule table (LRPAlpha2Beta1IgnoreBias,
     LRPAlpha1Beta0IgnoreBias, or LRP(model, rule=("alphabeta", alpha, beta, False)))."""
 
     def __init__(self, model, alpha=None, beta=None, bias=True, neuron_selection_mode="replace", **kwargs):
@@ -280,7 +280,8 @@ class LRP(LRPSequentialPresetA):
         if rule is None:
             raise ValueError("Need LRP rule(s).")                                          # RA:345-346
         if getattr(model, "resnet", None) is not None:
-            raise NotImplementedError("the ResNet encoder's walk is alpha1beta0 only")
+            raise NotImplementedError("the ResNet encoder's walk has no rule table: LRPAlphaBeta / LRPAlpha2Beta1 / LRPSequentialPresetB "
+                                      "run one alpha-beta rule on it")
         table = rule_table(rule, input_layer_rule, len(model.cnn_cfg))
         self._rule, self._input_layer_rule, self._table = rule, input_layer_rule, table
         super(LRP, self).__init__(model, neuron_selection_mode=neuron_selection_mode, **kwargs)

@@ -425,10 +425,7 @@ int lrp_set_cnn_rule(lrp_handle* h, float alpha, float beta) {
     if (!(fabs((double)alpha - (double)beta - 1.0) <= 6e-8 * ((double)alpha + (double)beta)))
       return fail(LRP_ERR_INVALID, "alpha - beta should be 1 (alpha=%g, beta=%g)", (double)alpha, (double)beta);
     beta = alpha - 1.f;
-    if (h->resnet) {
-      if (beta > 0.f) return fail(LRP_ERR_UNSUPPORTED, "the ResNet encoder's walk is alpha1beta0 only");
-      return LRP_OK;
-    }
+    if (h->resnet) return h->rn.set_rule(alpha, beta);    // (refuses beta > 0 on widths that are no multiples of 8)
     if (h->enc.table_on()) {                             // the one rule replaces a table (lrp_set_cnn_rules)
       LRP_TRY(h->trainer.drop_early_forward(nullptr));
       h->enc.clear_table();

@@ -5,6 +5,8 @@
 //   explain(): one reverse walk per TOKEN: three (four) convs per bottleneck block on conv_igemm + streaming kernels
 // The algorithm is oracle/resnet_lrp_ref.analyze_cached, which equals the literal iNNvestigate walk to 1e-10.
 // This path runs in exact fp32 (PREC_FP32) throughout.
+//   explain_ab(): the same walk under the alpha-beta rule with beta > 0 (set_rule): two relevance chains per tensor, the second
+//              gate of every unit and block made at encode time behind the unchanged forward (oracle: tests/resnet_ab_ref.py).
 //   explain_grad(): the gradient baselines (Gradient / InputTimesGradient / GuidedBackprop) in LRP_PREC_FP32 mode: the same
 //              convT launches with BN-scaled full-sign weights (w_g, packed on the first such walk) and the ReLU decisions
 //              the fp32 forward recorded as byte masks (RnUnit::mask, RnBlock::omask).
@@ -39,6 +41,11 @@ struct RnUnit {            // conv + BN
   // weight of the unit changed (grad_ok)
   DevBuf mask, w_g;
   bool grad_ok = false;
+  // alpha-beta rule with beta > 0 (ResNetEncoder::set_rule; none of these exists before the first such rule): the inhibitor gate
+  // (gate's form with Zi = conv(x, w-) + b), the forward matrix of Zi (w_n: w- in w_a's layout; the stem: the swapped-slot matrix;
+  // w_dualn_h: interleaved [w | w-] fp16 pairs of a dual_il unit) and the backward matrix [alpha w+ ; -beta w-], plain and split8
+  DevBuf gate_i, w_n, w_dualn_h, w_ab, w_abs;
+  bool ab_packed = false;
   size_t out_elems() const { return (size_t)Hout * Wout * cout; }
   size_t in_elems() const { return (size_t)Hin * Win * cin; }
 };
@@ -50,6 +57,7 @@ struct RnBlock {
   DevBuf t_sub;            // [B][H][W][cin] stride-2 gather of t_in (first block of stacks 3..5)
   DevBuf GA, GS;           // [B][H][W][4f]: fA*Q3 and fS (identity) / fS*Q0 (projection)
   DevBuf omask;            // [B][H][W][4f] bytes: block output > 0 (LRP_PREC_FP32 forward; the gradient walks)
+  DevBuf GA_i, GS_i;       // fA*Q3i and (projection blocks) fS*Q0i: the inhibitor chain's GA / GS (beta > 0)
 };
 
 struct ResNetEncoder {
@@ -193,6 +201,7 @@ struct ResNetEncoder {
       }
       u.have[s] = true;
       u.grad_ok = false;
+      u.ab_packed = false;
       norms_ready = false;
       encoded = 0;                                       // caches belong to the old weights
       return LRP_OK;
@@ -252,6 +261,119 @@ struct ResNetEncoder {
     return LRP_OK;
   }
 
+  // ---- alpha-beta rule (lrp_set_cnn_rule; RR:274-322 with beta > 0) ----
+  // Per conv + BN unit two denominators, Za = conv(x, w+) + b (the forward's Z) and Zi = conv(x, w-) + b, both with the full
+  // bias, hence two gates Bn / safe(Za) and Bn / safe(Zi); the walk carries [S_a | S_i] as one tensor and every transposed conv is
+  // ONE GEMM over both chains against [alpha w+ ; -beta w-] (explain_ab).  beta = 0 (the default) is the alpha1beta0 walk:
+  // nothing here is allocated, launched or read, and what the (1, 0) walk reads is written by the same launches either way.
+  float ab_alpha = 1.f, ab_beta = 0.f;
+  bool ab_on() const { return ab_beta > 0.f; }
+  DevBuf q_stem_i;
+  // the dual-gate epilogue works on whole split8 groups of either chain (conv_plan: Cin % 16 == 0 over both chains)
+  bool ab_supported() const {
+    if (stem_c & 7) return false;
+    for (const RnBlock& b : blocks)
+      if (b.f & 7) return false;
+    return true;
+  }
+  int set_rule(float alpha, float beta) {
+    if (alpha == ab_alpha && beta == ab_beta) return LRP_OK;
+    if (beta > 0.f) {
+      if (!ab_supported())
+        return fail(LRP_ERR_UNSUPPORTED, "alpha-beta with beta > 0 on a ResNet encoder needs a stem width and stack widths that are multiples of 8");
+      auto mk = [&](DevBuf& d, size_t floats) -> int {   // appears, or grows, with the first rule that needs it
+        if (d.p && d.bytes >= floats * sizeof(float)) return LRP_OK;
+        if (d.p && ws_total) *ws_total -= (int64_t)d.bytes;
+        return d.alloc(floats * sizeof(float), ws_total);
+      };
+      const size_t B = max_images, NT = max_tokens;
+      for (RnUnit& u : units) {
+        if (u.k == 7) {                                  // (the stem's second gate is q_stem_i)
+          LRP_TRY(mk(u.w_n, (size_t)conv_npad(u.cout) * 2 * RN_STEM_K));
+          const size_t nb = (size_t)conv_npad(RN_STEM_TCOLS) * conv_cinp(2 * u.cout);
+          LRP_TRY(mk(u.w_ab, nb)); LRP_TRY(mk(u.w_abs, nb));
+          continue;
+        }
+        const int taps = u.k * u.k;
+        LRP_TRY(mk(u.gate_i, B * u.out_elems()));
+        LRP_TRY(mk(u.w_n, (size_t)conv_npad(u.cout) * taps * conv_cinp(u.cin)));
+        if (u.dual_il && u.w_dual_h.p) LRP_TRY(mk(u.w_dualn_h, (size_t)conv_npad(2 * u.cout) * taps * conv_cinp(u.cin)));
+        const size_t nb = (size_t)conv_npad(u.cin) * taps * conv_cinp(2 * u.cout);
+        LRP_TRY(mk(u.w_ab, nb)); LRP_TRY(mk(u.w_abs, nb));
+      }
+      for (RnBlock& b : blocks) {
+        const size_t ne = B * (size_t)b.H * b.W * 4 * b.f;
+        LRP_TRY(mk(b.GA_i, ne));
+        if (b.u0 >= 0) LRP_TRY(mk(b.GS_i, ne));
+      }
+      const size_t stem_hw = (size_t)(img_h / 2) * (img_w / 2);
+      LRP_TRY(mk(q_stem_i, B * stem_hw * stem_c));
+      // the per-token scratch of the tensors that carry two chains (S3 / S0, S2, S1, the pool routing's output)
+      size_t max_act = stem_hw * stem_c;
+      for (const RnUnit& u : units) max_act = std::max(max_act, std::max(u.out_elems(), u.in_elems()));
+      const size_t tok2 = std::max(2 * max_act, stem_hw * (size_t)RN_STEM_TCOLS);
+      for (DevBuf* d : {&r1, &r2, &r3, &r5}) LRP_TRY(mk(*d, NT * tok2));
+    }
+    // (beta = 0 again: the buffers stay, idle)
+    ab_alpha = alpha; ab_beta = beta;
+    for (RnUnit& u : units) u.ab_packed = false;
+    encoded = 0;                                         // the caches belong to the old rule
+    return LRP_OK;
+  }
+  // the rule's matrices of every unit whose weights or rule changed since its last packing, from the resident forward matrix w_a
+  int ensure_ab_weights(hipStream_t st) {
+    auto split = [&](const float* src, float* dst, size_t n) {
+      hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n / 8)), dim3(256), 0, st, src, dst, n / 8);
+    };
+    for (RnUnit& u : units) {
+      if (u.ab_packed) continue;
+      // a weight set after the rule may have changed which forward path the unit takes
+      if (u.k != 7 && u.dual_il && u.w_dual_h.p && !u.w_dualn_h.p)
+        LRP_TRY(u.w_dualn_h.alloc((size_t)conv_npad(2 * u.cout) * u.k * u.k * conv_cinp(u.cin) * 4, ws_total));
+      if (u.k == 7) {
+        const int Np = conv_npad(u.cout), Npb = conv_npad(RN_STEM_TCOLS), Kb2 = conv_cinp(2 * u.cout);
+        const size_t nf = (size_t)Np * 2 * RN_STEM_K, nb = (size_t)Npb * Kb2;
+        hipLaunchKernelGGL(rn_pack_stem_ab_kernel, dim3(stream_grid(nf + nb)), dim3(256), 0, st, u.w_a.as<float>(), u.w_n.as<float>(),
+                           u.w_ab.as<float>(), u.cout, Np, Npb, Kb2, ab_alpha, ab_beta);
+        split(u.w_ab.as<float>(), u.w_abs.as<float>(), nb);
+      } else {
+        const int taps = u.k * u.k, CPi = conv_cinp(u.cin), CP2 = conv_cinp(2 * u.cout), rows = conv_npad(u.cin);
+        const size_t nf = (size_t)conv_npad(u.cout) * taps * CPi, nb = (size_t)rows * taps * CP2;
+        hipLaunchKernelGGL(rn_pack_neg_kernel, dim3(stream_grid(nf)), dim3(256), 0, st, u.w_a.as<float>(), u.w_n.as<float>(), nf);
+        if (u.w_dualn_h.p) {
+          const int Nd = conv_npad(2 * u.cout);
+          hipLaunchKernelGGL(rn_pack_dual_neg_h_kernel, dim3(stream_grid((size_t)Nd * taps * CPi / 8)), dim3(256), 0, st, u.w_a.as<float>(),
+                             u.w_dualn_h.as<float>(), taps * CPi, Nd, u.wds.as<float>());
+        }
+        hipLaunchKernelGGL(rn_pack_ab_kernel, dim3(stream_grid(nb)), dim3(256), 0, st, u.w_a.as<float>(), u.w_ab.as<float>(), taps, u.cin,
+                           u.cout, CPi, CP2, rows, ab_alpha, ab_beta);
+        split(u.w_ab.as<float>(), u.w_abs.as<float>(), nb);
+      }
+      LRP_HIP_CHECK(hipGetLastError());
+      u.ab_packed = true;
+    }
+    return LRP_OK;
+  }
+  // the inhibitor gate of a unit from c (what the forward's conv left in `c`) and one more conv for Zi (`cz`: the unit's forward
+  // launch on fp32 operands); Zi goes through fz
+  int unit_gate_inh(RnUnit& u, ConvArgs cz, const float* c, float* gate, int B, int relu, hipStream_t st) {
+    cz.wpk = u.w_n.as<float>(); cz.out = fz.as<float>();
+    LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, st));
+    const size_t n = (size_t)B * u.out_elems();
+    hipLaunchKernelGGL(rn_gate_inh_kernel, dim3(stream_grid(n / 4)), dim3(256), 0, st, c, fz.as<float>(), u.gamma.as<float>(),
+                       u.beta.as<float>(), u.mean.as<float>(), u.var.as<float>(), RN_BN_EPS, gate, n, u.cout, relu);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  }
+  int block_gates_inh(RnBlock& b, const float* sc, const float* y3, int B, hipStream_t st) {
+    const size_t n = (size_t)B * b.H * b.W * 4 * b.f;
+    hipLaunchKernelGGL(rn_block_gates_inh_kernel, dim3(stream_grid(n / 4)), dim3(256), 0, st, sc, y3, units[b.u3].gate_i.as<float>(),
+                       b.u0 >= 0 ? units[b.u0].gate_i.as<float>() : (const float*)nullptr, b.GA_i.as<float>(),
+                       b.u0 >= 0 ? b.GS_i.as<float>() : (float*)nullptr, n);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  }
+
   int check_ready() const {
     for (const RnUnit& u : units)
       for (int s = 0; s < 6; ++s)
@@ -295,6 +417,10 @@ struct ResNetEncoder {
         ca.bn_mean = u.mean.as<float>(); ca.bn_var = u.var.as<float>(); ca.bn_eps = RN_BN_EPS; ca.bn_relu = u.relu ? 1 : 0;
         ca.out = act; ca.out2 = u.gate.as<float>(); ca.act_max_out = slots_out;
         LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, ca, st, PREC_F16X2));
+        if (ab_on()) {                                   // the same launch against [w | w-]: the inhibitor gate, nothing else written
+          ca.wpk = u.w_dualn_h.as<float>(); ca.out2 = u.gate_i.as<float>(); ca.skip_out = 1; ca.act_max_out = nullptr;
+          LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, ca, st, PREC_F16X2));
+        }
         return LRP_OK;
       }
       LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, ca, st, PREC_F16X2));
@@ -314,6 +440,7 @@ struct ResNetEncoder {
                        u.gamma.as<float>(), u.beta.as<float>(), u.mean.as<float>(), u.var.as<float>(), RN_BN_EPS, act,
                        u.gate.as<float>(), (float*)nullptr, n, u.cout, u.relu ? 1 : 0, slots_out, mask);
     LRP_HIP_CHECK(hipGetLastError());
+    if (ab_on()) LRP_TRY(unit_gate_inh(u, cz, fc.as<float>(), u.gate_i.as<float>(), B, u.relu ? 1 : 0, st));
     return LRP_OK;
   }
 
@@ -365,6 +492,12 @@ struct ResNetEncoder {
     ca.scale_per_img = 1; ca.img_rows = u.Hout * u.Wout; ca.n_imgs = B;
     if (pairs_out) { ca.pairs_out = pairs_out; ca.pairs_scale = eoscale_unit(ui); ca.skip_out = 1; }
     LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, ca, st, PREC_F16X2));
+    if (ab_on()) {
+      // the unit's own launch again, [w | w-] in place of [w | w+]: same operands, scales and epilogue, the gate only
+      ca.wpk = u.w_dualn_h.as<float>(); ca.out2 = u.gate_i.as<float>(); ca.skip_out = 1;
+      ca.pairs_out = nullptr; ca.pairs_scale = nullptr; ca.act_max_out = nullptr;
+      LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, ca, st, PREC_F16X2));
+    }
     return LRP_OK;
   }
   int encode_emit(int B, hipStream_t st) {
@@ -404,6 +537,7 @@ struct ResNetEncoder {
       hipLaunchKernelGGL(rn_pool3_pairs_kernel, img_grid(per / 4 / 8, B), dim3(256), 0, st, a0.as<float>(), blocks[0].t_in.as<float>(),
                          pool_win.as<unsigned char>(), tp, eslots_unit(0), scales_of(blocks[0]), s.Hout, s.Wout, s.cout);
       LRP_HIP_CHECK(hipGetLastError());
+      if (ab_on()) LRP_TRY(unit_gate_inh(s, cz, fa.as<float>(), q_stem_i.as<float>(), B, 0, st));
     }
     for (size_t bi = 0; bi < blocks.size(); ++bi) {
       RnBlock& b = blocks[bi];
@@ -438,6 +572,7 @@ struct ResNetEncoder {
                          last ? (unsigned*)nullptr : eslots_block(bi), last ? (float*)nullptr : tp_other, eslots_unit(b.u3), sc_slots,
                          last ? RnBlockScales{} : scales_of(blocks[bi + 1]));
       LRP_HIP_CHECK(hipGetLastError());
+      if (ab_on()) LRP_TRY(block_gates_inh(b, sc, fa.as<float>(), B, st));
       std::swap(tp, tp_other);
     }
     return LRP_OK;
@@ -457,6 +592,7 @@ struct ResNetEncoder {
   int encode(const float* images_dev, int B, hipStream_t st) {
     if (B < 1 || B > max_images) return fail(LRP_ERR_INVALID, "B=%d outside [1,%d]", B, max_images);
     LRP_TRY(check_ready());
+    if (ab_on()) LRP_TRY(ensure_ab_weights(st));
     masks_ok = false;
     if (emit_ok()) {
       LRP_HIP_CHECK(hipMemcpyAsync(images.p, images_dev, (size_t)B * img_h * img_w * 3 * 4, hipMemcpyDeviceToDevice, st));
@@ -493,6 +629,7 @@ struct ResNetEncoder {
       hipLaunchKernelGGL(rn_pool3_kernel, dim3(stream_grid(np)), dim3(256), 0, st, a0.as<float>(), blocks[0].t_in.as<float>(),
                          pool_win.as<unsigned char>(), B, s.Hout, s.Wout, s.cout);
       LRP_HIP_CHECK(hipGetLastError());
+      if (ab_on()) LRP_TRY(unit_gate_inh(s, cz, fc.as<float>(), q_stem_i.as<float>(), B, 0, st));
     }
     for (size_t bi = 0; bi < blocks.size(); ++bi) {
       RnBlock& b = blocks[bi];
@@ -522,6 +659,7 @@ struct ResNetEncoder {
                          b.GA.as<float>(), b.GS.as<float>(), n, last ? (unsigned*)nullptr : block_slots(bi),
                          rec ? b.omask.as<unsigned char>() : (unsigned char*)nullptr);
       LRP_HIP_CHECK(hipGetLastError());
+      if (ab_on()) LRP_TRY(block_gates_inh(b, sc, fa.as<float>(), B, st));
     }
     encoded = B;
     features_only = false;
@@ -552,6 +690,10 @@ struct ResNetEncoder {
     if (n < 1 || n > max_tokens) return fail(LRP_ERR_INVALID, "n=%d outside [1,%d]", n, max_tokens);
     if (encoded < 1 || features_only) return fail(LRP_ERR_STATE, "lrp_encode_images must run before the CNN explain");
     if (walk != LRP_WALK_LRP) return explain_grad(n, row2img, R_feat_dev, R_img_dev, st, walk);
+    if (ab_on()) {                                       // every launch is asked about before the first runs
+      LRP_TRY(explain_ab(n, row2img, R_feat_dev, R_img_dev, st, true));
+      return explain_ab(n, row2img, R_feat_dev, R_img_dev, st, false);
+    }
     const float* Ro = R_feat_dev;          // relevance at the current block's output
     float* cur = r0.as<float>();           // where the next R_t is written (ping-pong r0 / r4)
     float* other = r4.as<float>();
@@ -684,6 +826,118 @@ struct ResNetEncoder {
     ca.in = r1.as<float>(); ca.NB = n * s.Hout * s.Wout; ca.H = 1; ca.W = 1; ca.Cin = s.cout; ca.CinP = conv_cinp(s.cout);
     ca.taps = 1; ca.wpk = ssplit ? s.w_bs.as<float>() : s.w_b.as<float>(); ca.N = RN_STEM_TCOLS; ca.out = r2.as<float>();
     LRP_HIP_CHECK(conv_launch(EPI_STORE, ca, st, ssplit ? PREC_BF16X3 : PREC_FP32));
+    hipLaunchKernelGGL(rn_stem_stencil_kernel<0>, dim3(stream_grid((size_t)n * img_h * img_w)), dim3(256), 0, st, r2.as<float>(),
+                       images.as<float>(), row2img, R_img_dev, n, img_h, img_w);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  }
+
+  // ---- the two-chain walk of the alpha-beta rule with beta > 0 (set_rule) ----
+  // explain()'s walk with [S_a | S_i] tensors.  Per block: head S3 = R_o [GA | GA_i]; units 3 and 2 as dual-gate launches (one
+  // accumulator c = convT(S_a, alpha w+) + convT(S_i, -beta w-), two gates, two outputs side by side); unit 1 and the projection
+  // as ordinary one-gate launches over Cin = 2 cout whose output t * c is a relevance again.  The identity tail keeps the fused
+  // join (R_o * GS: the shortcut has no conv, both chains share it); the next block's head is a pass of its own (two gates), or
+  // rides on the projection join (rn_join2_kernel).  The stem: two-gate pool routing, the tap GEMM over K = 2 stem_c, the stencil.
+  // dry: nothing is launched — conv_plan is asked about every conv launch of the walk, LRP_ERR_UNSUPPORTED for what it refuses.
+  int explain_ab(int n, const int* row2img, const float* R_feat_dev, float* R_img_dev, hipStream_t st, bool dry) {
+    const bool sp = prec == PREC_BF16X3;                 // (set_rule: every width is a multiple of 8)
+    const int rp = sp ? PREC_BF16X3 : PREC_FP32;
+    // one transposed conv through unit u over both chains; aux_b != nullptr: dual gate, the output carries two chains
+    auto conv = [&](const RnUnit& u, const float* S, const float* aux, const float* aux_b, float* out, const BlockTail* tail) -> int {
+      ConvArgs ca{};
+      if (tail) { ca.join = tail->join; ca.join_gate = tail->join_gate; }
+      ca.in = S; ca.wpk = sp ? u.w_abs.as<float>() : u.w_ab.as<float>(); ca.row2img = row2img; ca.aux = aux; ca.out = out;
+      ca.N = u.cin; ca.Cin = 2 * u.cout; ca.CinP = conv_cinp(2 * u.cout); ca.NB = n; ca.H = u.Hout; ca.W = u.Wout;
+      ca.taps = u.k == 3 ? 9 : 1;
+      if (aux_b) { ca.aux_b = aux_b; ca.out_b = out + u.cin; ca.ostride = 2 * u.cin; }
+      else ca.out_plain = 1;                             // a relevance: feeds the join
+      if (dry) {
+        if (!conv_plan(conv_ask(EPI_MUL, rp, 7, false, ca)).ok)
+          return fail(LRP_ERR_UNSUPPORTED, "alpha-beta walk: no conv kernel for '%s' (N=%d, Cin=%d, %s)", u.name.c_str(), ca.N, ca.Cin,
+                      aux_b ? "dual gate" : "one gate");
+        return LRP_OK;
+      }
+      prof.begin(st);
+      LRP_HIP_CHECK(conv_launch(EPI_MUL, ca, st, rp));
+      prof.end(st, 4.0 * n * u.Hout * u.Wout * (double)(u.k == 3 ? 9 : 1) * u.cout * u.cin);
+      return LRP_OK;
+    };
+    auto head = [&](const RnBlock& bb, const float* Ro, const float* Ga, const float* Gi, float* dst) -> int {
+      if (dry) return LRP_OK;
+      const size_t per_o = (size_t)bb.H * bb.W * 4 * bb.f;
+      if (sp)
+        hipLaunchKernelGGL(rn_mul_gate2_kernel<true>, dim3(stream_grid((size_t)n * per_o / 8)), dim3(256), 0, st, Ro, Ga, Gi, row2img, dst, n,
+                           per_o, 4 * bb.f);
+      else
+        hipLaunchKernelGGL(rn_mul_gate2_kernel<false>, dim3(stream_grid((size_t)n * per_o / 4)), dim3(256), 0, st, Ro, Ga, Gi, row2img, dst, n,
+                           per_o, 4 * bb.f);
+      LRP_HIP_CHECK(hipGetLastError());
+      return LRP_OK;
+    };
+    const float* Ro = R_feat_dev;
+    float *cur = r0.as<float>(), *other = r4.as<float>();
+    float *s3 = r1.as<float>(), *s3_other = r5.as<float>();
+    bool have_s3 = false;
+    for (int bi = (int)blocks.size() - 1; bi >= 0; --bi) {
+      const RnBlock& b = blocks[bi];
+      const RnUnit &u1 = units[b.u1], &u2 = units[b.u2], &u3 = units[b.u3];
+      if (!have_s3) LRP_TRY(head(b, Ro, b.GA.as<float>(), b.GA_i.as<float>(), s3));
+      have_s3 = false;
+      LRP_TRY(conv(u3, s3, u2.gate.as<float>(), u2.gate_i.as<float>(), r2.as<float>(), nullptr));                       // S2
+      if (b.u0 < 0) {
+        LRP_TRY(conv(u2, r2.as<float>(), u1.gate.as<float>(), u1.gate_i.as<float>(), r3.as<float>(), nullptr));         // S1
+        BlockTail tl;
+        tl.join = Ro; tl.join_gate = b.GS.as<float>();
+        LRP_TRY(conv(u1, r3.as<float>(), b.t_in.as<float>(), nullptr, cur, &tl));                                       // R_t = t*C1 + R_o*GS
+      } else {
+        const RnUnit& u0 = units[b.u0];
+        LRP_TRY(conv(u2, r2.as<float>(), u1.gate.as<float>(), u1.gate_i.as<float>(), s3_other, nullptr));               // S1
+        const float* taux = b.stride == 2 ? b.t_sub.as<float>() : b.t_in.as<float>();
+        LRP_TRY(conv(u1, s3_other, taux, nullptr, r2.as<float>(), nullptr));                                            // t*C1 (coarse)
+        LRP_TRY(head(b, Ro, b.GS.as<float>(), b.GS_i.as<float>(), s3_other));                                           // S0
+        LRP_TRY(conv(u0, s3_other, taux, nullptr, r3.as<float>(), nullptr));                                            // t*C0
+        // join (scattered to the even positions behind a stride-2 block) and, in the same pass, the head of the block walked next
+        const bool fuse_next = bi > 0;
+        if (!dry) {
+          const float* ga = fuse_next ? blocks[bi - 1].GA.as<float>() : (const float*)nullptr;
+          const float* gi = fuse_next ? blocks[bi - 1].GA_i.as<float>() : (const float*)nullptr;
+          float* o2 = fuse_next ? s3 : (float*)nullptr;
+          const size_t tot = (size_t)n * b.Hin * b.Win * b.cin / (sp ? 8 : 4);
+          const dim3 g(stream_grid(tot));
+          const float *pa = r2.as<float>(), *pb = r3.as<float>();
+          if (b.stride == 2 && sp)
+            hipLaunchKernelGGL((rn_join2_kernel<true, true>), g, dim3(256), 0, st, pa, pb, cur, ga, gi, row2img, o2, n, b.Hin, b.Win, b.cin);
+          else if (b.stride == 2)
+            hipLaunchKernelGGL((rn_join2_kernel<true, false>), g, dim3(256), 0, st, pa, pb, cur, ga, gi, row2img, o2, n, b.Hin, b.Win, b.cin);
+          else if (sp)
+            hipLaunchKernelGGL((rn_join2_kernel<false, true>), g, dim3(256), 0, st, pa, pb, cur, ga, gi, row2img, o2, n, b.Hin, b.Win, b.cin);
+          else
+            hipLaunchKernelGGL((rn_join2_kernel<false, false>), g, dim3(256), 0, st, pa, pb, cur, ga, gi, row2img, o2, n, b.Hin, b.Win, b.cin);
+          LRP_HIP_CHECK(hipGetLastError());
+        }
+        have_s3 = fuse_next;                              // (written into s3: S3 of this block has been consumed)
+      }
+      Ro = cur;
+      std::swap(cur, other);
+    }
+    // stem: two-gate pool routing -> T = [S_a | S_i] . [alpha (w+ | w-) ; -beta (w- | w+)] (K = 2 stem_c, N = 294) -> 7x7/2 stencil
+    const RnUnit& s = units[0];
+    ConvArgs ca{};
+    ca.in = r1.as<float>(); ca.NB = n * s.Hout * s.Wout; ca.H = 1; ca.W = 1; ca.Cin = 2 * s.cout; ca.CinP = conv_cinp(2 * s.cout);
+    ca.taps = 1; ca.wpk = sp ? s.w_abs.as<float>() : s.w_ab.as<float>(); ca.N = RN_STEM_TCOLS; ca.out = r2.as<float>();
+    if (dry) {
+      if (!conv_plan(conv_ask(EPI_STORE, rp, 7, false, ca)).ok) return fail(LRP_ERR_UNSUPPORTED, "alpha-beta walk: no conv kernel for the stem's tap GEMM");
+      return LRP_OK;
+    }
+    const size_t tot = (size_t)n * s.Hout * s.Wout * s.cout;
+    if (sp)
+      hipLaunchKernelGGL(rn_pool3_route2_kernel<true>, dim3(stream_grid(tot / 8)), dim3(256), 0, st, Ro, pool_win.as<unsigned char>(),
+                         q_stem.as<float>(), q_stem_i.as<float>(), row2img, r1.as<float>(), n, s.Hout, s.Wout, s.cout);
+    else
+      hipLaunchKernelGGL(rn_pool3_route2_kernel<false>, dim3(stream_grid(tot / 4)), dim3(256), 0, st, Ro, pool_win.as<unsigned char>(),
+                         q_stem.as<float>(), q_stem_i.as<float>(), row2img, r1.as<float>(), n, s.Hout, s.Wout, s.cout);
+    LRP_HIP_CHECK(hipGetLastError());
+    LRP_HIP_CHECK(conv_launch(EPI_STORE, ca, st, rp));
     hipLaunchKernelGGL(rn_stem_stencil_kernel<0>, dim3(stream_grid((size_t)n * img_h * img_w)), dim3(256), 0, st, r2.as<float>(),
                        images.as<float>(), row2img, R_img_dev, n, img_h, img_w);
     LRP_HIP_CHECK(hipGetLastError());

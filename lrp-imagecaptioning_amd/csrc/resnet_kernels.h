@@ -841,4 +841,251 @@ __global__ __launch_bounds__(256) void rn_grad_pool_route_kernel(const float* __
   }
 }
 
+// ---- alpha-beta rule with beta > 0 (ResNetEncoder::explain_ab) ---------------------------------------------------
+// RR:274-322 with two denominators per conv + BN unit: Za = conv(x, w+) + b (the Z of alpha1beta0) and Zi = conv(x, w-) + b
+// (x >= 0 behind the stem: the second conv of either branch contributes its bias only, so both carry the FULL bias).  The walk
+// carries two chains per tensor, [S_a | S_i] = R Bn [1 / safe(Za) | 1 / safe(Zi)], 2 C floats per pixel, and every transposed conv
+// is ONE GEMM over both against [alpha w+ ; -beta w-].  The kernels below make the second gate of every cache the one-chain walk
+// keeps, the two-chain operands and the two-chain forms of the walk's element-wise steps.
+
+// Inhibitor gate of a conv + BN unit from c = conv(x, w) + b (what the forward left) and Zi: rn_bn_unit_kernel's Q with Zi in
+// place of Z;  relu != 0: gate = relu(y) Qi, relu == 0: gate = Qi (pre-Add units; the stem's q-only cache).  4 channels per thread.
+__global__ __launch_bounds__(256) void rn_gate_inh_kernel(const float* __restrict__ c, const float* __restrict__ Zi,
+                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                          const float* __restrict__ mean, const float* __restrict__ var, float bn_eps,
+                                                          float* __restrict__ gate, size_t n, int C, int relu) {
+  const size_t n4 = n / 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const int ch = (int)((i * 4) % C);
+    const f32x4 cv = reinterpret_cast<const f32x4*>(c)[i], zv = reinterpret_cast<const f32x4*>(Zi)[i];
+    const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + ch), be = *reinterpret_cast<const f32x4*>(beta + ch);
+    const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + ch), va = *reinterpret_cast<const f32x4*>(var + ch);
+    f32x4 g;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float y = ga[q] * (cv[q] - mu[q]) / sqrtf(va[q] + bn_eps) + be[q];
+      const float qq = (cv[q] * (y - be[q])) / safe_den(stab_sign((cv[q] - mu[q]) * y)) / safe_den(zv[q]);
+      g[q] = relu ? fmaxf(y, 0.f) * qq : qq;
+    }
+    reinterpret_cast<f32x4*>(gate)[i] = g;
+  }
+}
+
+// Block end, inhibitor chain: GAi = y3 / safe(sc + y3) * Q3i;  GSi = sc / safe(sc + y3) * Q0i (projection shortcut; an identity
+// shortcut has no conv: both chains share GS).  rn_block_out_kernel's factors, 4 channels per thread.
+__global__ __launch_bounds__(256) void rn_block_gates_inh_kernel(const float* __restrict__ sc, const float* __restrict__ y3,
+                                                                 const float* __restrict__ Q3i, const float* __restrict__ Q0i,
+                                                                 float* __restrict__ GAi, float* __restrict__ GSi, size_t n) {
+  const size_t n4 = n / 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const f32x4 s = reinterpret_cast<const f32x4*>(sc)[i], y = reinterpret_cast<const f32x4*>(y3)[i];
+    const f32x4 q3 = reinterpret_cast<const f32x4*>(Q3i)[i];
+    f32x4 q0 = {1.f, 1.f, 1.f, 1.f};
+    if (Q0i) q0 = reinterpret_cast<const f32x4*>(Q0i)[i];
+    f32x4 ga, gs;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float den = safe_den(s[q] + y[q]);
+      ga[q] = y[q] / den * q3[q];
+      gs[q] = s[q] / den * q0[q];
+    }
+    reinterpret_cast<f32x4*>(GAi)[i] = ga;
+    if (Q0i) reinterpret_cast<f32x4*>(GSi)[i] = gs;
+  }
+}
+
+// one pixel's CW channels of both chains: dst[0 .. C) = v ga, dst[C .. 2C) = v gi at channel offset c  (split8 or plain fp32)
+template <bool SPLIT, int CW>
+__device__ __forceinline__ void rn_store_two_chains(const float* v, const float* __restrict__ ga, const float* __restrict__ gi,
+                                                    float* __restrict__ dst, int C) {
+  float a[CW], b[CW];
+#pragma unroll
+  for (int g = 0; g < CW / 4; ++g) {
+    const f32x4 x = *reinterpret_cast<const f32x4*>(ga + 4 * g), y = *reinterpret_cast<const f32x4*>(gi + 4 * g);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { a[4 * g + q] = v[4 * g + q] * x[q]; b[4 * g + q] = v[4 * g + q] * y[q]; }
+  }
+  if constexpr (SPLIT) {
+    split8_store(a, dst);
+    split8_store(b, dst + C);
+  } else {
+    *reinterpret_cast<f32x4*>(dst) = *reinterpret_cast<const f32x4*>(a);
+    *reinterpret_cast<f32x4*>(dst + C) = *reinterpret_cast<const f32x4*>(b);
+  }
+}
+
+// Head of a two-chain conv chain: out[t][p][2C] = [R[t][p] Ga[img][p] | R[t][p] Gi[img][p]]   (rn_mul_gate[_split]_kernel twice,
+// R read once).  SPLIT: 8 channels per thread, split8 operand; otherwise 4, plain fp32.  per_img = pixels x C of one image.
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void rn_mul_gate2_kernel(const float* __restrict__ R, const float* __restrict__ Ga,
+                                                           const float* __restrict__ Gi, const int* __restrict__ row2img,
+                                                           float* __restrict__ out, int ntok, size_t per_img, int C) {
+  constexpr int CW = SPLIT ? 8 : 4;
+  const size_t per = per_img / CW, total = (size_t)ntok * per;
+  const int CG = C / CW;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int t = (int)(i / per);
+    const size_t e = i - (size_t)t * per;
+    const int img = row2img ? row2img[t] : t;
+    const size_t pix = i / CG;                            // pixel of the token stack
+    const int c = (int)(i - pix * CG) * CW;
+    float v[CW];
+#pragma unroll
+    for (int g = 0; g < CW / 4; ++g) *reinterpret_cast<f32x4*>(v + 4 * g) = *reinterpret_cast<const f32x4*>(R + i * CW + 4 * g);
+    const size_t go = (size_t)img * per_img + e * CW;
+    rn_store_two_chains<SPLIT, CW>(v, Ga + go, Gi + go, out + pix * 2 * C + c, C);
+  }
+}
+
+// End of a projection block's two-chain walk in one pass: rn_join_split_kernel with both gates of the block walked next,
+//   fine = a + b (SCATTER: at the even positions of the stride-2 grid, zeros elsewhere)
+//   out2[t][p][2C] = [fine G2a[img] | fine G2i[img]]   (optional)
+template <bool SCATTER, bool SPLIT>
+__global__ __launch_bounds__(256) void rn_join2_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ fine,
+                                                       const float* __restrict__ G2a, const float* __restrict__ G2i,
+                                                       const int* __restrict__ row2img, float* __restrict__ out2, int NB, int H, int W,
+                                                       int C) {
+  constexpr int CW = SPLIT ? 8 : 4;
+  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2, CG = C / CW;
+  const size_t total = (size_t)NB * H * W * CG;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int c = (int)(i % CG) * CW;
+    const size_t pix = i / CG;
+    size_t r = pix;
+    const int w = (int)(r % W);
+    r /= W;
+    const int h = (int)(r % H);
+    const int n = (int)(r / H);
+    float v[CW];
+#pragma unroll
+    for (int q = 0; q < CW; ++q) v[q] = 0.f;
+    if (!SCATTER || (!(h & 1) && !(w & 1))) {
+      const size_t j = SCATTER ? (((size_t)n * Ho + (h >> 1)) * Wo + (w >> 1)) * C + c : i * CW;
+#pragma unroll
+      for (int g = 0; g < CW / 4; ++g)
+        *reinterpret_cast<f32x4*>(v + 4 * g) = *reinterpret_cast<const f32x4*>(a + j + 4 * g) + *reinterpret_cast<const f32x4*>(b + j + 4 * g);
+    }
+#pragma unroll
+    for (int g = 0; g < CW / 4; ++g) *reinterpret_cast<f32x4*>(fine + i * CW + 4 * g) = *reinterpret_cast<const f32x4*>(v + 4 * g);
+    if (out2) {
+      const int img = row2img ? row2img[n] : n;
+      const size_t go = (((size_t)img * H + h) * W + w) * C + c;
+      rn_store_two_chains<SPLIT, CW>(v, G2a + go, G2i + go, out2 + pix * 2 * C + c, C);
+    }
+  }
+}
+
+// rn_pool3_route_kernel with both stem gates: S[t][i][j][2C] = [sum Qa | sum Qi], sum = the relevance of the windows whose first
+// arg-max is (i, j)
+template <bool SPLIT>
+__global__ __launch_bounds__(256) void rn_pool3_route2_kernel(const float* __restrict__ R, const unsigned char* __restrict__ win,
+                                                              const float* __restrict__ Qa, const float* __restrict__ Qi,
+                                                              const int* __restrict__ row2img, float* __restrict__ S, int ntok, int H,
+                                                              int W, int C) {
+  constexpr int CW = SPLIT ? 8 : 4;
+  const int Ho = H / 2, Wo = W / 2, CG = C / CW;
+  const size_t total = (size_t)ntok * H * W * CG;
+  for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+    const int c = (int)(idx % CG) * CW;
+    const size_t pix = idx / CG;
+    size_t r = pix;
+    const int j = (int)(r % W);
+    r /= W;
+    const int i = (int)(r % H);
+    const int t = (int)(r / H);
+    const int img = row2img ? row2img[t] : t;
+    float acc[CW];
+#pragma unroll
+    for (int q = 0; q < CW; ++q) acc[q] = 0.f;
+    for (int oh = i / 2; oh <= (i + 1) / 2; ++oh) {
+      if (oh >= Ho || 2 * oh - 1 > i || 2 * oh + 1 < i) continue;
+      for (int ow = j / 2; ow <= (j + 1) / 2; ++ow) {
+        if (ow >= Wo || 2 * ow - 1 > j || 2 * ow + 1 < j) continue;
+        const unsigned mine = (unsigned)((i - 2 * oh + 1) * 3 + (j - 2 * ow + 1));
+        const size_t wo = (((size_t)img * Ho + oh) * Wo + ow) * C + c, ro = (((size_t)t * Ho + oh) * Wo + ow) * C + c;
+#pragma unroll
+        for (int g = 0; g < CW / 4; ++g) {
+          const unsigned w4 = *reinterpret_cast<const unsigned*>(win + wo + 4 * g);
+          const f32x4 rv = *reinterpret_cast<const f32x4*>(R + ro + 4 * g);
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (((w4 >> (8 * q)) & 0xFFu) == mine) acc[4 * g + q] += rv[q];
+        }
+      }
+    }
+    const size_t qo = (((size_t)img * H + i) * W + j) * C + c;
+    rn_store_two_chains<SPLIT, CW>(acc, Qa + qo, Qi + qo, S + pix * 2 * C + c, C);
+  }
+}
+
+// The rule's operands, from the unit's resident forward matrix w_a [rows >= cout][taps * CPi] (full sign, zero padded):
+//   backward [rows >= cin][taps * CP2], CP2 = cinp(2 cout), taps flipped: k = t * CP2 + j * cout + co,
+//   chain j = 0: alpha w+, j = 1: -beta w-          (both chains' transposed conv as one GEMM; every element is written)
+__global__ __launch_bounds__(256) void rn_pack_ab_kernel(const float* __restrict__ wa, float* __restrict__ wab, int taps, int cin, int cout,
+                                                         int CPi, int CP2, int rows, float alpha, float beta) {
+  const int K = taps * CP2;
+  const size_t total = (size_t)rows * K;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int ci = (int)(i / K), k = (int)(i % K), t = k / CP2, c = k % CP2;
+    float v = 0.f;
+    if (ci < cin && c < 2 * cout) {
+      const int j = c >= cout ? 1 : 0;
+      const float x = wa[(size_t)(c - j * cout) * taps * CPi + (size_t)(taps - 1 - t) * CPi + ci];
+      v = j ? (x < 0.f ? -beta * x : 0.f) : (x >= 0.f ? alpha * x : 0.f);
+    }
+    wab[i] = v;
+  }
+}
+//   forward, the inhibitor denominator conv: wn = w- in w_a's layout
+__global__ __launch_bounds__(256) void rn_pack_neg_kernel(const float* __restrict__ wa, float* __restrict__ wn, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    const float x = wa[i];
+    wn[i] = x < 0.f ? x : 0.f;
+  }
+}
+//   forward, interleaved dual rows [w | w-] per 32 channels (pack_conv_dev_kernel dual = 2 with w- in the second block) as fp16
+//   pairs under the scale record of the unit's [w | w+] matrix (both hold all of w: the same max|w|, the same power of two)
+__global__ __launch_bounds__(256) void rn_pack_dual_neg_h_kernel(const float* __restrict__ wa, float* __restrict__ dst, int K, int rows,
+                                                                 const float* __restrict__ wsc) {
+  const float sc = wsc[0];
+  const int K8 = K / 8;
+  const size_t total = (size_t)rows * K8;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int row = (int)(i / K8), k = (int)(i % K8) * 8, blk = row >> 5;
+    const float* src = wa + (size_t)((blk >> 1) * 32 + (row & 31)) * K + k;
+    float v[8];
+    *reinterpret_cast<f32x4*>(v) = *reinterpret_cast<const f32x4*>(src);
+    *reinterpret_cast<f32x4*>(v + 4) = *reinterpret_cast<const f32x4*>(src + 4);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = ((blk & 1) && !(v[q] < 0.f)) ? 0.f : v[q] * sc;
+    split8h_store(v, dst + i * 8);
+  }
+}
+//   the stem, from its w_a [Np][2 * RN_STEM_K]: wzn = the swapped-slot matrix (w- against the x+ patch, w+ against the x- patch:
+//   Zi = conv(x+, w-) + conv(x-, w+) + b);  wb [Npb][Kb2], Kb2 = cinp(2 cout), k = [S_a channels | S_i channels]:
+//   row t*6 + c (times x+): alpha w+ | -beta w-      row t*6 + 3 + c (times x-): alpha w- | -beta w+
+__global__ __launch_bounds__(256) void rn_pack_stem_ab_kernel(const float* __restrict__ wa, float* __restrict__ wzn, float* __restrict__ wb,
+                                                              int cout, int Np, int Npb, int Kb2, float alpha, float beta) {
+  const int K = 2 * RN_STEM_K;
+  const size_t nf = (size_t)Np * K, nb = (size_t)Npb * Kb2;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nf + nb; i += (size_t)gridDim.x * 256) {
+    if (i < nf) {
+      const int neg = (int)(i % K) / RN_STEM_K;
+      const float v = wa[i];
+      wzn[i] = neg ? (v >= 0.f ? v : 0.f) : (v < 0.f ? v : 0.f);
+    } else {
+      const size_t q = i - nf;
+      const int row = (int)(q / Kb2), c = (int)(q % Kb2), t = row / 6, c6 = row % 6, ch = c6 % 3;
+      float v = 0.f;
+      if (t < 49 && c < 2 * cout) {
+        const int j = c >= cout ? 1 : 0;
+        const float x = wa[(size_t)(c - j * cout) * K + t * 3 + ch];
+        const float xp = x >= 0.f ? x : 0.f, xn = x < 0.f ? x : 0.f;
+        v = c6 < 3 ? (j ? -beta * xn : alpha * xp) : (j ? -beta * xp : alpha * xn);
+      }
+      wb[q] = v;
+    }
+  }
+}
+
 }  // namespace lrp

@@ -427,11 +427,12 @@ class LRPEngine(object):
         self.precision = mode
 
     def set_cnn_rule(self, alpha=None, beta=None):
-        """The conv rule of the VGG-style encoder's LRP walk (lrp_set_cnn_rule): AlphaBetaRule with alpha >= 1, beta >= 0,
-        alpha - beta == 1; one of the two may be omitted and is inferred.  (1, 0), the default, is LRPSequentialPresetA's
+        """The conv rule of the encoder's LRP walk (lrp_set_cnn_rule), VGG-style or ResNet: AlphaBetaRule with alpha >= 1,
+        beta >= 0, alpha - beta == 1; one of the two may be omitted and is inferred.  (1, 0), the default, is LRPSequentialPresetA's
         alpha1beta0; (2, 1) is LRPAlpha2Beta1 / LRPSequentialPresetB.  A change drops the encode caches: call encode_images
-        again.  beta > 0 is not built for the ResNet encoder (NotImplementedError) nor for the 'f16x2' walk (the explain
-        calls raise NotImplementedError there)."""
+        again.  beta > 0 on a ResNet encoder needs a stem width and stack widths that are multiples of 8 (ResNet-50/101/152 are;
+        NotImplementedError otherwise) and runs in 'bf16x3' and 'fp32'; it is not built for the 'f16x2' walk of the VGG-style
+        encoder (the explain calls raise NotImplementedError there)."""
         from .analyzer import infer_alpha_beta
         alpha, beta = infer_alpha_beta(alpha, beta, "LRPEngine.set_cnn_rule")
         _capi.check(self._lib.lrp_set_cnn_rule(self._h, float(alpha), float(beta)))

@@ -47,8 +47,9 @@ class CaptionModelSpec(object):
     def __init__(self, weights, img_encoder="vgg16", hidden_dim=512, embedding_dim=512, L=196, D=512,
                  vocab_size=None, cnn_cfg=None, img_hw=(224, 224), resnet=None, cnn_rule=(1, 0)):
         """cnn_rule: the (alpha, beta) of the encoder's conv rule (LRPEngine.set_cnn_rule), or 'alpha1beta0' (the default:
-        LRPSequentialPresetA, E:32) / 'alpha2beta1' (LRPSequentialPresetB's conv rule), or — VGG-style encoders — a preset name
-        of analyzer.PRESETS ('presetAflat', 'presetBflat', 'zplus', ...) or a list with one rule per conv, input layer first
+        LRPSequentialPresetA, E:32) / 'alpha2beta1' (LRPSequentialPresetB's conv rule), or a preset name of analyzer.PRESETS
+        ('presetB', and — VGG-style encoders — 'presetAflat', 'presetBflat', 'zplus', ...) or a list with one rule per conv, input
+        layer first; a ResNet encoder takes what amounts to ONE alpha-beta rule with bias on every conv (NotImplementedError otherwise)
         (analyzer.normalize_rule; LRPEngine.set_cnn_rules: self.cnn_rules holds the table, self.cnn_rule is then None); every explainer built on the spec
         whose CNN half is the LRP walk applies it to its engine; the gradient-baseline classes do not (their walks ignore the
         rule, and setting it would cost them its encode pass and buffers for nothing).
@@ -87,9 +88,17 @@ class CaptionModelSpec(object):
         elif isinstance(cnn_rule, list):
             table = (cnn_rule, None)
         if table is not None:
+            n_conv = len(self.cnn_cfg)
             if self.resnet is not None:
-                raise NotImplementedError("the ResNet encoder's walk is alpha1beta0 only: no rule table, no preset %r" % (cnn_rule,))
-            table = rule_table(table[0], table[1], len(self.cnn_cfg))
+                if isinstance(cnn_rule, list):
+                    raise NotImplementedError("the ResNet encoder's walk has no rule table: no list with a rule per conv")
+                from .synthetic import resnet_conv_list
+                n_conv = len(resnet_conv_list(self.resnet["stacks"], self.resnet.get("stem", 64)))
+            table = rule_table(table[0], table[1], n_conv)
+            r0 = table[0]
+            if self.resnet is not None and not (r0[0] == "alphabeta" and r0[3] and all(r == r0 for r in table)):
+                raise NotImplementedError("the ResNet encoder's walk is one alpha-beta rule with bias on every conv: no rule table, "
+                                          "no preset %r" % (cnn_rule,))
             r0 = table[0]
             if r0[0] == "alphabeta" and r0[3] and all(r == r0 for r in table):
                 return (r0[1], r0[2]), None
