@@ -229,8 +229,16 @@ int lrp_decoder_gradient(lrp_handle* h, int32_t n, const int32_t* img_idx_host, 
  * activations as fp16 pairs only — and return LRP_ERR_UNSUPPORTED in the other modes (set LRP_PREC_FP32 with
  * lrp_set_precision and call lrp_encode_images again); LRP_WALK_LRP runs in every mode.  The first gradient walk on a
  * ResNet handle after its weights changed packs a BN-scaled copy of the conv weights (counted in lrp_workspace_bytes,
- * like the ReLU masks the first fp32-mode encode allocates). */
-enum { LRP_WALK_LRP = 0, LRP_WALK_GRADIENT = 1, LRP_WALK_INPUT_X_GRADIENT = 2, LRP_WALK_GUIDED_BACKPROP = 3 };
+ * like the ReLU masks the first fp32-mode encode allocates).
+ * LRP_WALK_DECONVNET (gradient_based.py:180-225, DeconvnetReverseReLULayer): a layer with a ReLU clamps what arrives at 0 and
+ * applies the gradient of the layer WITHOUT its activation; pools, BatchNorm, Add and padding take the plain gradient, pools
+ * routing to the forward's arg-max (first in scan order on ties — an all-zero window included, whose share lands on its first
+ * cell; in the ResNet stem that may be a padding cell, and the share is cropped away).  No forward ReLU decision is read, so
+ * the walk runs in every precision mode on both encoders, in exact fp32.  Its first call after an encode builds a 0/1
+ * position gate per pooled layer of a VGG-style encoder (max_images x that layer's activations, float32, allocated by the
+ * first call and counted in lrp_workspace_bytes); the ResNet form allocates the BN-scaled matrices of the other gradient
+ * walks and nothing else. */
+enum { LRP_WALK_LRP = 0, LRP_WALK_GRADIENT = 1, LRP_WALK_INPUT_X_GRADIENT = 2, LRP_WALK_GUIDED_BACKPROP = 3, LRP_WALK_DECONVNET = 4 };
 int lrp_cnn_walk(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const float* head_dev, float* out_dev,
                  int32_t walk, void* stream);
 
@@ -472,6 +480,37 @@ int lrp_op_gradcam(const float* feat_dev, const int32_t* img_idx_dev, const floa
                    int32_t D, int32_t C, void* stream);
 int lrp_exam_maps(const void* R_img_dev, int32_t fp64, int32_t n, int32_t H, int32_t W, int32_t C, int32_t pool, int32_t k,
                   int32_t absval, void* maps_dev, double* means_dev, void* stream);
+
+/* Augment and reduce of the reference's wrappers (innvestigate/analyzer/wrapper.py:78-345: GaussianSmoother behind SmoothGrad,
+ * PathIntegrator behind IntegratedGradients).  Handle-free operators like lrp_op_gradcam: device pointers, the caller's stream, no
+ * synchronisation; additive to the ABI.  (csrc/augment_kernels.h)
+ * The sample matrix is (B * n, per_image) in np.repeat order (wrapper.py:169): row r = b * n + s is sample s of image b.  Every
+ * entry works on the rows [r0, r0 + count) of it: out_dev / maps_dev hold those count rows only (row r0 first), x_dev is the
+ * (B, per_image) float32 input.  A row's values are a pure function of (r, i) and the arguments, so any cut into chunks gives
+ * the same bits.  B * n < 2^31, per_image >= 1 (any value: a tail group writes fewer than four values).
+ * lrp_op_augment_gaussian: out[r][i] = x[b][i] + sigma * N(seed, r, i) (two float32 roundings).  N is Philox4x32-10
+ *   (multipliers 0xD2511F53 and 0xCD9E8D57, Weyl key increments 0x9E3779B9 and 0xBB67AE85; the Random123 known answers are in
+ *   tests/test_gradient_family_ref.py) with key = (seed & 0xFFFFFFFF, seed >> 32) and counter = (g & 0xFFFFFFFF, g >> 32, r, 0),
+ *   g = i / 4.  Its outputs x0..x3 become two Box-Muller pairs with u = ((x >> 8) + 0.5) 2^-24:
+ *   z0 = sqrt(-2 ln u0) cos(2 pi u1), z1 = sqrt(-2 ln u0) sin(2 pi u1), (z2, z3) alike from (u2, u3); element i takes z[i % 4];
+ *   |z| <= 5.89.  float32 with the precise logf / log1pf / sincospif on exactly representable arguments, no fast-math intrinsic.
+ * lrp_op_augment_path: mode 0: out[r][i] = x + (s / n) (x - ref) — literally what the reference computes (wrapper.py:268-288,
+ *   :317-337 with layers.py:513-522: it starts at x and moves AWAY from the reference; s / n excludes 1); mode 1: the published
+ *   path ref + (s / n) (x - ref).  ref_dev (B, per_image) float32, or NULL for the scalar ref_scalar.  Each of s / n, x - ref,
+ *   the product and the sum is rounded to float32 on its own, as numpy does.
+ * lrp_op_reduce_mean, phase 0 (accumulate): acc_dev (B, per_image) float64 += sum over the chunk's rows of each image, in
+ *   ascending s, of post(maps[r][i]); post 0 none, 1 |.|, 2 square (gradient_based.py:110-137 post-processes a sample, then the
+ *   mean is taken).  One thread per element, no atomics; launches accumulate in stream order, so the sum does not depend on the
+ *   chunking.  The caller zeroes acc_dev first.  out_dev, x_dev, ref_dev, ref_scalar, has_factor are not read.
+ *   phase 1 (finish): out_dev (B, per_image) float32 = float(acc / n) or, has_factor = 1, float(acc / n * (x - ref)) with the
+ *   product in float64 (wrapper.py:290-296, :339-345), rounded once.  maps_dev, r0, count, post are not read. */
+int lrp_op_augment_gaussian(const float* x_dev, float* out_dev, int32_t B, int32_t n, int64_t per_image, int32_t r0, int32_t count,
+                            float sigma, uint64_t seed, void* stream);
+int lrp_op_augment_path(const float* x_dev, const float* ref_dev, float ref_scalar, float* out_dev, int32_t B, int32_t n,
+                        int64_t per_image, int32_t r0, int32_t count, int32_t mode, void* stream);
+int lrp_op_reduce_mean(int32_t phase, const float* maps_dev, double* acc_dev, int32_t B, int32_t n, int64_t per_image, int32_t r0,
+                       int32_t count, int32_t post, float* out_dev, const float* x_dev, const float* ref_dev, float ref_scalar,
+                       int32_t has_factor, void* stream);
 
 /* ABI v10.  Perturbation ("pixel-flipping") analysis on the device (PT: = innvestigate/tools/perturbate.py): rank the regions
  * of a heat-map, replace the top-k regions of the image, read the explained word's score off the next forward.  Operators like

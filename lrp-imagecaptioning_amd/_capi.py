@@ -107,6 +107,10 @@ SYMBOLS = {
     "lrp_eval_box_scores": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P, _P]),
     "lrp_op_gradcam": (C.c_int, [_P] * 7 + [C.c_int32] * 6 + [_P]),
     "lrp_exam_maps": (C.c_int, [_P] + [C.c_int32] * 8 + [_P, _P, _P]),
+    "lrp_op_augment_gaussian": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_float, C.c_uint64, _P]),
+    "lrp_op_augment_path": (C.c_int, [_P, _P, C.c_float, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "lrp_op_reduce_mean": (C.c_int, [C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                     C.c_float, C.c_int32, _P]),
     "lrp_perturb_ranks": (C.c_int, [_P] + [C.c_int32] * 10 + [_P, _P, _P]),
     "lrp_perturb_apply": (C.c_int, [_P] * 6 + [C.c_int32] * 10 + [C.c_float, C.c_float, _P]),
     "lrp_perturb_word_scores": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, _P]),

@@ -17,7 +17,17 @@ The gradient baselines beside it (innvestigate/analyzer/gradient_based.py:101-26
     analyzer.analyze([X, head])                   # -> (N,H,W,3)
 
 on lrp_cnn_walk in exact fp32 (LRP_PREC_FP32: a ReLU decision taken in another arithmetic switches whole gradient paths),
-for a VGG-style or a ResNet `ImageModelSpec`."""
+for a VGG-style or a ResNet `ImageModelSpec`.
+
+And the rest of the gradient-based entries that need no trained side data (gradient_based.py:180-225, :273-319; wrapper.py:214-345):
+
+    Deconvnet(image_model)                        # every ReLU clamps what arrives at 0 and passes it on: no forward decision is read
+    GaussianSmoother(subanalyzer, augment_by_n=2, noise_scale=1, seed=0)
+    PathIntegrator(subanalyzer, steps=16, reference_inputs=0, path="reference" | "standard")
+    SmoothGrad(image_model, augment_by_n=64, postprocess=None, ...)       # GaussianSmoother over Gradient
+    IntegratedGradients(image_model, steps=64, postprocess=None, ...)     # PathIntegrator over Gradient
+
+with samples, walks and the mean on the device (LRPEngine.cnn_walk_augmented); `analyzers` maps the reference's names to what is built."""
 import numpy as np
 
 from .engine import LRPEngine
@@ -468,3 +478,169 @@ class InputTimesGradient(Gradient):
 class GuidedBackprop(_GradientWalkAnalyzer):
     """gradient_based.py:228-265: every layer with a ReLU first clamps the arriving value at 0, then applies its gradient."""
     _walk = "guided_backprop"
+
+
+class Deconvnet(_GradientWalkAnalyzer):
+    """gradient_based.py:180-225: every layer with a ReLU clamps the arriving value at 0 and applies the gradient of the layer
+    WITHOUT its activation — no forward ReLU decision is read; max-pools route to the forward's arg-max."""
+    _walk = "deconvnet"
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# AugmentReduceBase wrappers (wrapper.py:78-345) on LRPEngine.cnn_walk_augmented
+# ---------------------------------------------------------------------------------------------------------------------
+def _engine_walk(subanalyzer):
+    """(walk, postprocess) of an analyzer of this module that runs on an engine walk: the four gradient-walk classes and the
+    LRP classes (the 'lrp' walk under the subanalyzer's own rule and precision)."""
+    if isinstance(subanalyzer, _GradientWalkAnalyzer):
+        post = getattr(subanalyzer, "_postprocess", None)
+        if isinstance(subanalyzer, InputTimesGradient) and post is not None:
+            raise NotImplementedError("InputTimesGradient with a postprocess under a wrapper: the product with the sample "
+                                      "follows the post-processing; wrap Gradient(postprocess=...) instead")
+        return subanalyzer._walk, post
+    if isinstance(subanalyzer, LRPSequentialPresetA):
+        return "lrp", None
+    raise TypeError("the wrappers take an analyzer of this module that runs on an engine walk (Gradient, InputTimesGradient, "
+                    "GuidedBackprop, Deconvnet or an LRP class), not %r" % (type(subanalyzer).__name__,))
+
+
+class AugmentReduceBase(object):
+    """wrapper.py:78-206 with `analyze([X, head])`: every input is augmented to augment_by_n samples, each sample explained by the
+    subanalyzer's engine walk, and the maps reduced to their mean — all on the device (LRPEngine.cnn_walk_augmented); only the
+    (N, H, W, 3) result comes back.  One deviation from the reference: its wrappers silently switch the subanalyzer to
+    neuron_selection_mode 'index' (wrapper.py:84-86) and so cannot run with a replaced head at all; here the mode stays
+    'replace' and the head stays the caller's, repeated for each of its image's samples."""
+    _kind = None
+
+    @staticmethod
+    def _check_n(augment_by_n):
+        if isinstance(augment_by_n, bool) or int(augment_by_n) != augment_by_n or augment_by_n < 1:
+            raise ValueError("augment_by_n must be a positive integer but was {}".format(augment_by_n))
+
+    def __init__(self, subanalyzer, augment_by_n=2, max_batch=None):
+        self._check_n(augment_by_n)
+        self._walk, self._post = _engine_walk(subanalyzer)
+        self._augment_by_n = int(augment_by_n)
+        self._subanalyzer = subanalyzer
+        self._neuron_selection_mode = subanalyzer._neuron_selection_mode
+        self._max_batch = max_batch
+
+    def _augment_args(self):
+        return {}
+
+    def analyze(self, X, neuron_selection=None):
+        if neuron_selection is not None:
+            raise ValueError("Only neuron_selection_mode 'index' expects the neuron_selection parameter.")  # base.py:489-492
+        X = list(X) if isinstance(X, (list, tuple)) else [X]
+        if len(X) != 2:
+            raise ValueError("neuron_selection_mode 'replace' expects [X, head]")
+        img, R = np.asarray(X[0], dtype=np.float32), np.asarray(X[1], dtype=np.float32)
+        if R.shape[0] != img.shape[0]:
+            raise ValueError("X and head must have the same batch size")
+        e = self._subanalyzer._engine
+        out = e.cnn_walk_augmented(img, R.reshape(img.shape[0], e.L, e.D), self._walk, self._kind, self._augment_by_n,
+                                   postprocess=self._post, max_batch=self._max_batch, **self._augment_args())
+        return out.cpu().numpy()
+
+
+class GaussianSmoother(AugmentReduceBase):
+    """wrapper.py:214-242: sample = x + N(0, noise_scale).  The draw is the device generator of lrp_op_augment_gaussian
+    (Philox4x32-10 + Box-Muller, a pure function of (seed, sample row, element)), not numpy's / TensorFlow's."""
+    _kind = "gaussian"
+
+    @staticmethod
+    def _check_noise(noise_scale, seed):
+        if not noise_scale >= 0:
+            raise ValueError("noise_scale must be >= 0 but was {}".format(noise_scale))
+        if isinstance(seed, bool) or int(seed) != seed or not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be an integer in [0, 2^64)")
+
+    def __init__(self, subanalyzer, augment_by_n=2, noise_scale=1, seed=0, **kwargs):
+        self._check_noise(noise_scale, seed)
+        super(GaussianSmoother, self).__init__(subanalyzer, augment_by_n=augment_by_n, **kwargs)
+        self._noise_scale, self._seed = float(noise_scale), int(seed)
+
+    def _augment_args(self):
+        return {"noise_scale": self._noise_scale, "seed": self._seed}
+
+
+class PathIntegrator(AugmentReduceBase):
+    """wrapper.py:250-345: the mean of the subanalyzer's maps over `steps` points of a path, times (x - reference_inputs).
+    path='reference' is literally what the reference computes — x + (s / steps) (x - reference), s = 0 .. steps - 1: it starts
+    at x and moves AWAY from the reference (wrapper.py:268-288, :317-337) — and path='standard' the published straight path
+    reference + (s / steps) (x - reference).  reference_inputs: a scalar, or an array that broadcasts to X."""
+    _kind = "path"
+
+    @staticmethod
+    def _check_path(reference_inputs, path):
+        if path not in ("reference", "standard"):
+            raise ValueError("path must be 'reference' or 'standard'")
+        if isinstance(reference_inputs, (str, bytes)):
+            raise ValueError("reference_inputs must be a number or an array")
+        return reference_inputs if np.isscalar(reference_inputs) else np.asarray(reference_inputs, dtype=np.float32)
+
+    def __init__(self, subanalyzer, steps=16, reference_inputs=0, path="reference", **kwargs):
+        reference_inputs = self._check_path(reference_inputs, path)
+        super(PathIntegrator, self).__init__(subanalyzer, augment_by_n=steps, **kwargs)
+        self._reference_inputs, self._path = reference_inputs, path
+
+    def _augment_args(self):
+        return {"reference": self._reference_inputs, "path": self._path}
+
+
+def _check_wrapped_gradient(postprocess, neuron_selection_mode):
+    """what Gradient(model, ...) refuses, asked before the wrapper's own checks so that nothing is created on a bad argument"""
+    _check_selection_mode(neuron_selection_mode)
+    if postprocess not in [None, "abs", "square"]:
+        raise ValueError("Parameter 'postprocess' must be either None, 'abs', or 'square'.")   # gradient_based.py:110-112
+
+
+class SmoothGrad(GaussianSmoother):
+    """gradient_based.py:300-319: GaussianSmoother over Gradient(model, postprocess)."""
+
+    def __init__(self, model, augment_by_n=64, postprocess=None, neuron_selection_mode="replace", noise_scale=1, seed=0,
+                 max_batch=8, device=None):
+        _check_wrapped_gradient(postprocess, neuron_selection_mode)
+        self._check_n(augment_by_n)
+        self._check_noise(noise_scale, seed)
+        sub = Gradient(model, postprocess=postprocess, neuron_selection_mode=neuron_selection_mode, max_batch=max_batch, device=device)
+        super(SmoothGrad, self).__init__(sub, augment_by_n=augment_by_n, noise_scale=noise_scale, seed=seed)
+
+
+class IntegratedGradients(PathIntegrator):
+    """gradient_based.py:273-292: PathIntegrator over Gradient(model, postprocess)."""
+
+    def __init__(self, model, steps=64, postprocess=None, neuron_selection_mode="replace", reference_inputs=0, path="reference",
+                 max_batch=8, device=None):
+        _check_wrapped_gradient(postprocess, neuron_selection_mode)
+        self._check_n(steps)
+        self._check_path(reference_inputs, path)
+        sub = Gradient(model, postprocess=postprocess, neuron_selection_mode=neuron_selection_mode, max_batch=max_batch, device=device)
+        super(IntegratedGradients, self).__init__(sub, steps=steps, reference_inputs=reference_inputs, path=path)
+
+
+# innvestigate/analyzer/__init__.py:35-85, the entries this module builds under the reference's keys (deep_taylor*, deep_lift*,
+# pattern.*, gradient.baseline, input and random are not built and stay absent)
+analyzers = {
+    "gradient": Gradient,
+    "input_t_gradient": InputTimesGradient,
+    "deconvnet": Deconvnet,
+    "guided_backprop": GuidedBackprop,
+    "integrated_gradients": IntegratedGradients,
+    "smoothgrad": SmoothGrad,
+    "lrp": LRP,
+    "lrp.z": LRPZ,
+    "lrp.z_IB": LRPZIgnoreBias,
+    "lrp.epsilon": LRPEpsilon,
+    "lrp.epsilon_IB": LRPEpsilonIgnoreBias,
+    "lrp.alpha_beta": LRPAlphaBeta,
+    "lrp.alpha_2_beta_1": LRPAlpha2Beta1,
+    "lrp.alpha_2_beta_1_IB": LRPAlpha2Beta1IgnoreBias,
+    "lrp.alpha_1_beta_0": LRPAlpha1Beta0,
+    "lrp.alpha_1_beta_0_IB": LRPAlpha1Beta0IgnoreBias,
+    "lrp.z_plus": LRPZPlus,
+    "lrp.sequential_preset_a": LRPSequentialPresetA,
+    "lrp.sequential_preset_b": LRPSequentialPresetB,
+    "lrp.sequential_preset_a_flat": LRPSequentialPresetAFlat,
+    "lrp.sequential_preset_b_flat": LRPSequentialPresetBFlat,
+}

@@ -861,8 +861,44 @@ __global__ __launch_bounds__(256) void img_partial_sum_kernel(const float* __res
   }
 }
 
+// Deconvnet: the routing of a 2x2/2 max-pool alone, as a 0/1 gate at full resolution, from the layer's gate G = [first arg-max]
+// a / safe(Z+).  a > 0 implies Z+ >= a > 0, so the window's arg-max is its one cell with G != 0; a window without one is all
+// zero behind its ReLU, a four-way tie, and the first cell in scan order takes what is routed into it (tf.gradients' rule).
+// Four channels per thread.
+__global__ __launch_bounds__(256) void pool_pos_gate_kernel(const float* __restrict__ g, float* __restrict__ d, int NB, int H, int W,
+                                                            int C) {
+  const int C4 = C >> 2, Ho = H >> 1, Wo = W >> 1;
+  const size_t total = (size_t)NB * Ho * Wo * C4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int c4 = (int)(i % C4);
+    size_t r = i / C4;
+    const int wo = (int)(r % Wo);
+    r /= Wo;
+    const int ho = (int)(r % Ho);
+    const int n = (int)(r / Ho);
+    size_t off[4];
+    int arg[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int p = 3; p >= 0; --p) {
+      off[p] = ((((size_t)n * H + 2 * ho + (p >> 1)) * W + 2 * wo + (p & 1)) * C) + 4 * c4;
+      const f32x4 gv = *reinterpret_cast<const f32x4*>(g + off[p]);
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (gv[c] != 0.f) arg[c] = p;
+    }
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+      f32x4 o;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) o[c] = arg[c] == p ? 1.f : 0.f;
+      *reinterpret_cast<f32x4*>(d + off[p]) = o;
+    }
+  }
+}
+
 // Head of the gradient walks: the cut is AFTER block5_conv3's ReLU, so the head tensor first passes that ReLU's
-// backward: S_top = R * [feat > 0]  (guided backprop: max(R, 0) * [feat > 0], gradient_based.py:228-234)
+// backward: S_top = R * [feat > 0]  (guided backprop: max(R, 0) * [feat > 0], gradient_based.py:228-234;
+// guided = 2, Deconvnet: max(R, 0), the forward is not read, gradient_based.py:180-196)
 __global__ __launch_bounds__(256) void grad_top_kernel(const f32x4* __restrict__ R, const f32x4* __restrict__ feat,
                                                        const int* __restrict__ row2img, f32x4* __restrict__ S, int n,
                                                        size_t per4, int guided) {
@@ -870,8 +906,15 @@ __global__ __launch_bounds__(256) void grad_top_kernel(const f32x4* __restrict__
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const size_t t = i / per4, r = i - t * per4;
     const int img = row2img ? row2img[t] : (int)t;
-    const f32x4 rv = R[i], fv = feat[(size_t)img * per4 + r];
+    const f32x4 rv = R[i];
     f32x4 o;
+    if (guided == 2) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) o[c] = fmaxf(rv[c], 0.f);
+      S[i] = o;
+      continue;
+    }
+    const f32x4 fv = feat[(size_t)img * per4 + r];
 #pragma unroll
     for (int c = 0; c < 4; ++c) o[c] = fv[c] > 0.f ? (guided ? fmaxf(rv[c], 0.f) : rv[c]) : 0.f;
     S[i] = o;

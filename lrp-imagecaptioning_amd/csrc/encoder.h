@@ -52,6 +52,11 @@ struct ConvLayer {
   // the full-resolution gate G of a pooled layer is current for the encode whose number this holds: the fused pool epilogue
   // writes the compact form only, Encoder::full_gate() expands it for the walks that read G (cnn_kernels.h pool_gate_expand_kernel)
   long gfull_epoch = -1;
+  // Deconvnet walk (LRP_WALK_DECONVNET): the pool's routing alone as a 0/1 gate at full resolution — 1 at the forward's arg-max
+  // cell of every window, the FIRST cell in scan order where the whole window is zero (G is zero there and cannot say) —
+  // built from G on the first Deconvnet walk after an encode (cnn_kernels.h pool_pos_gate_kernel); allocated by that walk
+  DevBuf Dg;
+  long dg_epoch = -1;
   // 2:4-sparse consumer of the pooled boundary behind this layer (conv_sparse.h; layers with cin % 256 == 0 whose output is pooled:
   // VGG16 block3_conv3, block4_conv3): the four class arrangements of w+ and, per encode, the index planes of the pool's positions
   DevBuf w_sp, idxp;
@@ -142,7 +147,9 @@ struct Encoder {
   // the image layer's fp32 dual GEMM with interleaved rows: gate, pairs and maximum leave its epilogue (no gate / absmax / split pass)
   static bool image_layer_interleaved(const ConvLayer& L) { return fwd_il() && !(L.cout & 31) && conv_npad(2 * L.cout) == 2 * L.cout && !L.pool_after; }
   static bool dual_interleaved(const ConvLayer& L) { return fwd_il() && !(L.cout & 31) && conv_npad(2 * L.cout) == 2 * L.cout; }
+  int64_t* ws_total = nullptr;   // the handle's workspace counter (what a walk allocates on its first use is counted too)
   int init(const lrp_config& c, int64_t* total) {
+    ws_total = total;
     img_h = c.img_h; img_w = c.img_w; max_images = c.max_images; max_tokens = c.max_tokens;
     if (c.n_conv < 1 || c.n_conv > LRP_MAX_CONV) return fail(LRP_ERR_INVALID, "n_conv=%d out of range", c.n_conv);
     if (c.conv_cin[0] != 3) return fail(LRP_ERR_UNSUPPORTED, "first conv must read a 3-channel image");
@@ -881,6 +888,20 @@ struct Encoder {
     return LRP_OK;
   }
 
+  // Deconvnet: the 0/1 position gate of pooled layer li (ConvLayer::Dg) for this encode
+  int position_gate(int li, hipStream_t st) {
+    ConvLayer& L = layers[li];
+    if (L.dg_epoch == encode_epoch) return LRP_OK;
+    LRP_TRY(full_gate(li, st));
+    if (!L.Dg.p) LRP_TRY(L.Dg.alloc((size_t)max_images * L.act_elems() * sizeof(float), ws_total));
+    const size_t n4 = (size_t)encoded * (L.H / 2) * (L.W / 2) * (L.cout / 4);
+    hipLaunchKernelGGL(pool_pos_gate_kernel, dim3(stream_grid(n4)), dim3(256), 0, st, L.G.as<float>(), L.Dg.as<float>(), encoded, L.H,
+                       L.W, L.cout);
+    LRP_HIP_CHECK(hipGetLastError());
+    L.dg_epoch = encode_epoch;
+    return LRP_OK;
+  }
+
   // What one explain call runs, decided once at its top (walk_mode)
   struct WalkMode {
     int n = 0, walk = 0, run_prec = PREC_FP32;
@@ -964,7 +985,7 @@ struct Encoder {
     if (m.walk != 0) {
       hipLaunchKernelGGL(grad_top_kernel, dim3(stream_grid((size_t)n * per4)), dim3(256), 0, st,
                          reinterpret_cast<const f32x4*>(R_feat_dev), feat.as<f32x4>(), row2img_dev,
-                         reinterpret_cast<f32x4*>(S), n, per4, m.walk == 3 ? 1 : 0);
+                         reinterpret_cast<f32x4*>(S), n, per4, m.walk == 4 ? 2 : m.walk == 3 ? 1 : 0);
     } else if (m.f16) {
       const int top = (int)layers.size() - 1;
       hipLaunchKernelGGL(top_divide_f16_kernel, dim3(n), dim3(256), 0, st, R_feat_dev, ztop.as<float>(), row2img_dev, S,
@@ -1372,6 +1393,8 @@ struct Encoder {
   // walk: 0 = LRP (LRPSequentialPresetA); gradient baselines (gradient_based.py:101-265) on the same caches:
   //   1 = Gradient, 2 = InputTimesGradient, 3 = GuidedBackprop — backward-data convs with the full w, the LRP gate
   //   used as the ReLU/arg-max mask, exact fp32.
+  //   4 = Deconvnet (gradient_based.py:180-225): every ReLU clamps what arrives at 0 and passes it on — no forward ReLU decision
+  //   is read; the pools route to the forward's arg-max (position_gate), non-pooled boundaries take no gate at all.
   // layer_hook (fine-tune step): called with (li, dZ_li) — the gradient at the pre-activation of conv li, n x H x W x cout —
   // before that layer's backward-data conv is launched; the image layer itself is then skipped (R_img_dev may be null).
   int explain(int n, const int* row2img_dev, const float* R_feat_dev, float* R_img_dev, hipStream_t st, int walk = 0,
@@ -1379,7 +1402,7 @@ struct Encoder {
     const int* r2i_host = row2img_host;
     row2img_host = nullptr;                              // one-shot
     if (n < 1 || n > max_tokens) return fail(LRP_ERR_INVALID, "n=%d outside [1,%d]", n, max_tokens);
-    if (walk < 0 || walk > 3) return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
+    if (walk < 0 || walk > 4) return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
     if (encoded < 1 || features_only) return fail(LRP_ERR_STATE, "lrp_encode_images must run before the CNN explain");
     if (gates_pending) LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_gates, 0));   // gates / Z_top come from the side stream
     if (table_on() && walk == 0 && !layer_hook) return explain_table(n, row2img_dev, R_feat_dev, R_img_dev, st);
@@ -1431,7 +1454,7 @@ struct Encoder {
         if (li > 0) ca.tok_max_out = lev_max(li - 1);
       }
       ca.row2img = row2img_dev; ca.order = L.order.get(); ca.row2img_host = r2i_host;
-      ca.gate_binary = walk != 0; ca.relu_out = walk == 3;
+      ca.gate_binary = walk != 0; ca.relu_out = walk == 3 || walk == 4;
       int epi;
       if (li == 0 && img_fused()) {
         // T GEMM + 9-tap stencil in one launch (patch tiles, T stays in LDS)
@@ -1445,6 +1468,14 @@ struct Encoder {
         const ConvLayer& P = layers[li - 1];
         ca.N = L.cin; ca.aux = P.G.as<float>(); ca.out = Snext;
         epi = P.pool_after ? EPI_MUL_UP2 : EPI_MUL;
+        if (walk == 4) {                                   // Deconvnet: the pool's routing, or nothing, in place of the ReLU gate
+          if (P.pool_after) {
+            LRP_TRY(position_gate(li - 1, st));
+            ca.aux = P.Dg.as<float>();
+          } else {
+            ca.gate_none = 1;
+          }
+        }
         // the image layer rides on this launch's epilogue?
         if (li == 1 && m.fold_on && (fold = walk_plan(m, 1, pairs_in)).ok) {
           ca.img_w = P.w_bwd_s.as<float>(); ca.img_part = Snext; ca.out = nullptr;

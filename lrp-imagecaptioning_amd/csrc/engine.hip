@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "augment_kernels.h"
 #include "common.h"
 #include "conv_launch.h"
 #include "conv_plan.h"
@@ -378,9 +379,10 @@ int lrp_cnn_walk(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const fl
                  void* stream) {
   return with_handle(h, [&]() -> int {
     if (!h || !img_idx_host || !head_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
-    if (walk < LRP_WALK_LRP || walk > LRP_WALK_GUIDED_BACKPROP) return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
+    if (walk < LRP_WALK_LRP || walk > LRP_WALK_DECONVNET) return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
     if (h->encoded() < 1 || h->features_only()) return fail(LRP_ERR_STATE, "lrp_encode_images must run before lrp_cnn_walk");
-    if (h->resnet && walk != LRP_WALK_LRP && h->rn.prec != PREC_FP32)   // (checked before any staging: nothing runs)
+    // (checked before any staging: nothing runs; Deconvnet reads no ReLU decision and runs in every mode)
+    if (h->resnet && walk != LRP_WALK_LRP && walk != LRP_WALK_DECONVNET && h->rn.prec != PREC_FP32)
       return fail(LRP_ERR_UNSUPPORTED, "gradient walks on a ResNet encoder run in LRP_PREC_FP32 only: set it with lrp_set_precision "
                                        "and call lrp_encode_images again");
     LRP_TRY(stage_indices(h, n, img_idx_host, nullptr, false, S(stream)));
@@ -1134,6 +1136,71 @@ int lrp_exam_maps(const void* R_img_dev, int32_t fp64, int32_t n, int32_t H, int
     else
       hipLaunchKernelGGL(exam_map_kernel<float>, dim3(n), dim3(256), 0, S(stream), (const float*)R_img_dev, H, W, C, pool, k,
                          absval, maps_dev, means_dev);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+// ---- augment and reduce of SmoothGrad / IntegratedGradients (csrc/augment_kernels.h; innvestigate/analyzer/wrapper.py:78-345)
+static int augment_rows(int32_t B, int32_t n, int64_t per_image, int32_t r0, int32_t count) {
+  if (B < 1 || n < 1 || per_image < 1) return fail(LRP_ERR_INVALID, "B, n and per_image must be positive");
+  if ((int64_t)B * n > INT32_MAX) return fail(LRP_ERR_INVALID, "B * n must be below 2^31");
+  if (r0 < 0 || count < 1 || (int64_t)r0 + count > (int64_t)B * n)
+    return fail(LRP_ERR_INVALID, "rows [%d, %lld) are not rows of the (%lld, per_image) sample matrix", r0, (long long)r0 + count,
+                (long long)B * n);
+  return LRP_OK;
+}
+
+int lrp_op_augment_gaussian(const float* x_dev, float* out_dev, int32_t B, int32_t n, int64_t per_image, int32_t r0, int32_t count,
+                            float sigma, uint64_t seed, void* stream) {
+  return guarded([&]() -> int {
+    if (!x_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
+    LRP_TRY(augment_rows(B, n, per_image, r0, count));
+    const size_t groups = ((size_t)per_image + 3) / 4;
+    hipLaunchKernelGGL(augment_gaussian_kernel, dim3(stream_grid((size_t)count * groups)), dim3(256), 0, S(stream), x_dev, out_dev, n,
+                       (size_t)per_image, r0, count, sigma, (unsigned)(seed & 0xFFFFFFFFull), (unsigned)(seed >> 32));
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_op_augment_path(const float* x_dev, const float* ref_dev, float ref_scalar, float* out_dev, int32_t B, int32_t n,
+                        int64_t per_image, int32_t r0, int32_t count, int32_t mode, void* stream) {
+  return guarded([&]() -> int {
+    if (!x_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (mode != 0 && mode != 1) return fail(LRP_ERR_INVALID, "mode must be 0 (the reference's x + a (x - ref)) or 1 (ref + a (x - ref))");
+    LRP_TRY(augment_rows(B, n, per_image, r0, count));
+    hipLaunchKernelGGL(augment_path_kernel, dim3(stream_grid((size_t)count * per_image)), dim3(256), 0, S(stream), x_dev, ref_dev,
+                       ref_scalar, out_dev, n, (size_t)per_image, r0, count, mode);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_op_reduce_mean(int32_t phase, const float* maps_dev, double* acc_dev, int32_t B, int32_t n, int64_t per_image, int32_t r0,
+                       int32_t count, int32_t post, float* out_dev, const float* x_dev, const float* ref_dev, float ref_scalar,
+                       int32_t has_factor, void* stream) {
+  return guarded([&]() -> int {
+    if (!acc_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (phase == 0) {
+      if (!maps_dev) return fail(LRP_ERR_INVALID, "null argument");
+      if (post != AUG_POST_NONE && post != AUG_POST_ABS && post != AUG_POST_SQUARE)
+        return fail(LRP_ERR_INVALID, "post must be 0 (none), 1 (abs) or 2 (square)");
+      LRP_TRY(augment_rows(B, n, per_image, r0, count));
+      const size_t imgs = (size_t)((r0 + count - 1) / n - r0 / n + 1);
+      hipLaunchKernelGGL(reduce_accum_kernel, dim3(stream_grid(imgs * per_image)), dim3(256), 0, S(stream), maps_dev, acc_dev, n,
+                         (size_t)per_image, r0, count, post);
+    } else if (phase == 1) {
+      if (!out_dev) return fail(LRP_ERR_INVALID, "null argument");
+      if (B < 1 || n < 1 || per_image < 1) return fail(LRP_ERR_INVALID, "B, n and per_image must be positive");
+      if (has_factor != 0 && has_factor != 1) return fail(LRP_ERR_INVALID, "has_factor must be 0 or 1");
+      if (has_factor && !x_dev) return fail(LRP_ERR_INVALID, "the factor x - ref needs x_dev");
+      const size_t total = (size_t)B * per_image;
+      hipLaunchKernelGGL(reduce_finish_kernel, dim3(stream_grid(total)), dim3(256), 0, S(stream), acc_dev, out_dev, n, total, has_factor,
+                         x_dev, ref_dev, ref_scalar);
+    } else {
+      return fail(LRP_ERR_INVALID, "phase must be 0 (accumulate) or 1 (finish)");
+    }
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   });

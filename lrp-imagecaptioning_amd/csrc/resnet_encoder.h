@@ -10,6 +10,8 @@
 //   explain_grad(): the gradient baselines (Gradient / InputTimesGradient / GuidedBackprop) in LRP_PREC_FP32 mode: the same
 //              convT launches with BN-scaled full-sign weights (w_g, packed on the first such walk) and the ReLU decisions
 //              the fp32 forward recorded as byte masks (RnUnit::mask, RnBlock::omask).
+//   explain_deconvnet(): Deconvnet, the guided-backprop walk without any mask (a clamp at every Activation, no ReLU decision
+//              read; the stem pool by pool_win): every precision mode.
 #pragma once
 #include <algorithm>
 #include <string>
@@ -971,12 +973,13 @@ struct ResNetEncoder {
   // one unit's gradient step: out = convT(S, W s) on the unit's output grid, then (mask != nullptr) the ReLU in front of it —
   // GUIDED: clamp at 0 — and (tail != nullptr) the residual join out = rho(acc + tail) [mask], all in the conv's epilogue
   int grad_backward(const RnUnit& u, int n, const int* row2img, const float* S, const unsigned char* mask, float* out, bool guided,
-                    hipStream_t st, const float* tail = nullptr) {
+                    hipStream_t st, const float* tail = nullptr, bool relu_nomask = false) {
     ConvArgs ca{};
     ca.in = S; ca.wpk = u.w_g.as<float>(); ca.row2img = row2img; ca.out = out; ca.N = u.cin; ca.out_plain = 1;
     ca.Cin = u.cout; ca.CinP = conv_cinp(u.cout); ca.NB = n; ca.H = u.Hout; ca.W = u.Wout; ca.taps = u.k == 3 ? 9 : 1;
     if (!mask) {
       ca.gate_none = 1;
+      ca.relu_out = relu_nomask ? 1 : 0;                 // Deconvnet: the ReLU in front clamps, and no mask follows
       LRP_HIP_CHECK(conv_launch(EPI_MUL, ca, st, PREC_FP32));
       return LRP_OK;
     }
@@ -993,9 +996,13 @@ struct ResNetEncoder {
   //                     stride 2) BEFORE the block input's ReLU; the first block's input is the stem pool's output: no ReLU
   //   stem:             pool routing summed over the overlapping windows, rho, [a0 > 0], convT of the 7x7/2 conv, crop
   // rho = relu for GUIDED_BACKPROP (every ReLU clamps what arrives first), identity otherwise.
+  // LRP_WALK_DECONVNET (gradient_based.py:180-225) is the GUIDED walk with every mask replaced by ones: rho at each Activation,
+  // the plain gradient through conv + BN, Add, pad and the stem pool.  It reads no ReLU decision — only pool_win, which every
+  // forward writes, and the BN-scaled matrices — so it runs in every precision mode (explain_deconvnet).
   int explain_grad(int n, const int* row2img, const float* head, float* R_img_dev, hipStream_t st, int walk) {
-    if (walk != LRP_WALK_GRADIENT && walk != LRP_WALK_INPUT_X_GRADIENT && walk != LRP_WALK_GUIDED_BACKPROP)
+    if (walk != LRP_WALK_GRADIENT && walk != LRP_WALK_INPUT_X_GRADIENT && walk != LRP_WALK_GUIDED_BACKPROP && walk != LRP_WALK_DECONVNET)
       return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
+    if (walk == LRP_WALK_DECONVNET) return explain_deconvnet(n, row2img, head, R_img_dev, st);
     if (prec != PREC_FP32)
       return fail(LRP_ERR_UNSUPPORTED, "gradient walks on a ResNet encoder run in LRP_PREC_FP32 only: set it with lrp_set_precision "
                                        "and call lrp_encode_images again");
@@ -1040,7 +1047,53 @@ struct ResNetEncoder {
     hipLaunchKernelGGL(rn_grad_pool_route_kernel, dim3(stream_grid(tot)), dim3(256), 0, st, G, pool_win.as<unsigned char>(),
                        a0.as<float>(), row2img, r1.as<float>(), n, s.Hout, s.Wout, s.cout, guided ? 1 : 0);
     LRP_HIP_CHECK(hipGetLastError());
-    const bool ixg = walk == LRP_WALK_INPUT_X_GRADIENT;
+    return grad_stem(n, row2img, R_img_dev, st, walk == LRP_WALK_INPUT_X_GRADIENT);
+  }
+  // the Deconvnet walk (see explain_grad): rho = relu at every Activation, no mask anywhere
+  int explain_deconvnet(int n, const int* row2img, const float* head, float* R_img_dev, hipStream_t st) {
+    LRP_TRY(ensure_grad_weights(st));
+    float* G = r0.as<float>();
+    float* other = r4.as<float>();
+    {
+      const RnBlock& t = blocks.back();
+      const size_t per = (size_t)t.H * t.W * 4 * t.f;
+      hipLaunchKernelGGL(rn_grad_head_kernel, dim3(stream_grid((size_t)n * per / 4)), dim3(256), 0, st, head, (const unsigned char*)nullptr,
+                         row2img, G, n, per, 1);
+      LRP_HIP_CHECK(hipGetLastError());
+    }
+    for (int bi = (int)blocks.size() - 1; bi >= 0; --bi) {
+      const RnBlock& b = blocks[bi];
+      const RnUnit &u1 = units[b.u1], &u2 = units[b.u2], &u3 = units[b.u3];
+      LRP_TRY(grad_backward(u3, n, row2img, G, nullptr, r2.as<float>(), false, st, nullptr, true));
+      LRP_TRY(grad_backward(u2, n, row2img, r2.as<float>(), nullptr, r3.as<float>(), false, st, nullptr, true));
+      LRP_TRY(grad_backward(u1, n, row2img, r3.as<float>(), nullptr, r1.as<float>(), false, st));
+      const float* sc = G;                               // the shortcut's term: G itself, or convT0(G) on the coarse grid
+      if (b.u0 >= 0) {
+        LRP_TRY(grad_backward(units[b.u0], n, row2img, G, nullptr, r5.as<float>(), false, st));
+        sc = r5.as<float>();
+      }
+      // the join, then the block input's Activation (the first block's input is the stem pool's output: no clamp there)
+      const size_t tot = (size_t)n * b.Hin * b.Win * b.cin / 4;
+      const int clamp = bi > 0 ? 2 : 0;
+      if (b.u0 >= 0 && b.stride == 2)
+        hipLaunchKernelGGL(rn_grad_join_kernel<true>, dim3(stream_grid(tot)), dim3(256), 0, st, r1.as<float>(), sc, (const unsigned char*)nullptr,
+                           row2img, other, n, b.Hin, b.Win, b.cin, clamp);
+      else
+        hipLaunchKernelGGL(rn_grad_join_kernel<false>, dim3(stream_grid(tot)), dim3(256), 0, st, r1.as<float>(), sc, (const unsigned char*)nullptr,
+                           row2img, other, n, b.Hin, b.Win, b.cin, clamp);
+      LRP_HIP_CHECK(hipGetLastError());
+      std::swap(G, other);
+    }
+    const RnUnit& s = units[0];
+    const size_t tot = (size_t)n * s.Hout * s.Wout * s.cout / 4;
+    hipLaunchKernelGGL(rn_grad_pool_route_kernel, dim3(stream_grid(tot)), dim3(256), 0, st, G, pool_win.as<unsigned char>(),
+                       (const float*)nullptr, row2img, r1.as<float>(), n, s.Hout, s.Wout, s.cout, 1);
+    LRP_HIP_CHECK(hipGetLastError());
+    return grad_stem(n, row2img, R_img_dev, st, false);
+  }
+  // the stem conv's backward on r1 (the gradient at its pre-activation): T GEMM + 7x7/2 stencil, ixg: times the image
+  int grad_stem(int n, const int* row2img, float* R_img_dev, hipStream_t st, bool ixg) {
+    const RnUnit& s = units[0];
     if (sw().img_fused != 0 && s.cout == 64 && conv_npad(RN_STEM_TCOLS) >= 5 * 60 + 4 && conv_cinp(s.cout) == 64) {
       const int txs = (s.Wout + RN_ST - 1) / RN_ST, tys = (s.Hout + RN_ST - 1) / RN_ST;
       if (!stem_grad_attr_set) {

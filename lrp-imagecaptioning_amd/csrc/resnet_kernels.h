@@ -749,6 +749,7 @@ __global__ __launch_bounds__(256) void rn_pack_stem_grad_kernel(const float* __r
 }
 
 // head of the walk: out[t][e] = [mask[img(t)][e]] * (GUIDED ? relu(R[t][e]) : R[t][e])   (the last block's output ReLU)
+// mask == nullptr (Deconvnet): no mask, the clamp alone
 __global__ __launch_bounds__(256) void rn_grad_head_kernel(const float* __restrict__ R, const unsigned char* __restrict__ mask,
                                                            const int* __restrict__ row2img, float* __restrict__ out, int ntok,
                                                            size_t per_img, int guided) {
@@ -757,7 +758,7 @@ __global__ __launch_bounds__(256) void rn_grad_head_kernel(const float* __restri
     const int t = (int)(i / per4);
     const size_t e = i - (size_t)t * per4;
     const int img = row2img ? row2img[t] : t;
-    const unsigned m = reinterpret_cast<const unsigned*>(mask)[(size_t)img * per4 + e];
+    const unsigned m = mask ? reinterpret_cast<const unsigned*>(mask)[(size_t)img * per4 + e] : 0x01010101u;
     f32x4 v = reinterpret_cast<const f32x4*>(R)[i];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -770,7 +771,9 @@ __global__ __launch_bounds__(256) void rn_grad_head_kernel(const float* __restri
 
 // join of a projection block: fine = a + b (SCATTER: at the even positions of the stride-2 grid, zeros elsewhere), the
 // completed fan-out sum; then the block input's ReLU (mask != nullptr: GUIDED clamp, then [t_in > 0]).  mask == nullptr: the
-// first block, whose input is the stem's pool output (no ReLU there: the clamp waits for the pool routing's sum)
+// first block, whose input is the stem's pool output (no ReLU there: the clamp waits for the pool routing's sum);
+// mask == nullptr and guided == 2 (Deconvnet): the clamp alone.  A SCATTER block is a projection block (b is its shortcut on the
+// coarse grid, like a); without SCATTER a and b share the fine grid (stride-1 projection, or an identity block's b = G).
 template <bool SCATTER>
 __global__ __launch_bounds__(256) void rn_grad_join_kernel(const float* __restrict__ a, const float* __restrict__ b,
                                                            const unsigned char* __restrict__ mask, const int* __restrict__ row2img,
@@ -796,6 +799,9 @@ __global__ __launch_bounds__(256) void rn_grad_join_kernel(const float* __restri
           const float g = guided ? fmaxf(v[q], 0.f) : v[q];
           v[q] = ((m >> (8 * q)) & 0xFFu) ? g : 0.f;
         }
+      } else if (guided == 2) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.f);
       }
     }
     reinterpret_cast<f32x4*>(fine)[i] = v;
@@ -805,6 +811,9 @@ __global__ __launch_bounds__(256) void rn_grad_join_kernel(const float* __restri
 // gradient through the stem's overlapping 3x3/2 max-pool (first arg-max of every window, pool_win) and the stem ReLU:
 // S[n][i][j][c] = [a0[img][i][j][c] > 0] * rho(sum_{windows whose winner is (i,j)} R[n][oh][ow][c]),  rho = relu when GUIDED
 // (the clamp acts on the completed sum over the overlapping windows), identity otherwise.  Four channels per thread.
+// a0 == nullptr (Deconvnet): no mask.  What is routed into a window whose nine cells are all zero goes to its first cell in scan
+// order — win holds 0 there, the scan starts at -inf — which is a zero-padding cell for the windows of the first row and column:
+// no map cell claims it and it is cropped away, as the gradient through ZeroPadding2D does.
 __global__ __launch_bounds__(256) void rn_grad_pool_route_kernel(const float* __restrict__ R, const unsigned char* __restrict__ win,
                                                                  const float* __restrict__ a0, const int* __restrict__ row2img,
                                                                  float* __restrict__ S, int ntok, int H, int W, int C, int guided) {
@@ -831,7 +840,8 @@ __global__ __launch_bounds__(256) void rn_grad_pool_route_kernel(const float* __
           if (((w4 >> (8 * q)) & 0xFFu) == mine) acc[q] += rv[q];
       }
     }
-    const f32x4 av = *reinterpret_cast<const f32x4*>(a0 + (((size_t)img * H + i) * W + j) * C + c);
+    f32x4 av = {1.f, 1.f, 1.f, 1.f};
+    if (a0) av = *reinterpret_cast<const f32x4*>(a0 + (((size_t)img * H + i) * W + j) * C + c);
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float g = guided ? fmaxf(acc[q], 0.f) : acc[q];

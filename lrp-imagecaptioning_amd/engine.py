@@ -353,7 +353,7 @@ class LRPEngine(object):
         return log_softmax_topk(logits, k)
 
     # ------------------------------------------------------------------ gradient baselines
-    WALKS = {"lrp": 0, "gradient": 1, "input_x_gradient": 2, "guided_backprop": 3}
+    WALKS = {"lrp": 0, "gradient": 1, "input_x_gradient": 2, "guided_backprop": 3, "deconvnet": 4}
 
     def decoder_gradient(self, img_idx, t, want_r_words=True):
         """_lstm_decoder_backward (explainers.py:780-832 / :1452-1532) for n (image, t) units: (n, L, D) float32
@@ -369,7 +369,8 @@ class LRPEngine(object):
 
     def cnn_walk(self, img_idx, head, walk="gradient", out=None):
         """Gradient / InputTimesGradient / GuidedBackprop `.analyze([X, head])` (gradient_based.py:101-265) on the
-        cached forward of `lrp_encode_images`; walk='lrp' is cnn_explain."""
+        cached forward of `lrp_encode_images`; walk='lrp' is cnn_explain; walk='deconvnet' (gradient_based.py:180-225) reads
+        no ReLU decision of the forward and runs in every precision mode on both encoders."""
         n = len(img_idx)
         ii, pi = _i32(img_idx)
         Hd = self._dev(head).reshape(n, self.L, self.D)
@@ -378,6 +379,60 @@ class LRPEngine(object):
         _capi.check(self._lib.lrp_cnn_walk(self._h, n, pi, C.c_void_p(Hd.data_ptr()), C.c_void_p(out.data_ptr()),
                                            self.WALKS[walk], self._stream()))
         return out
+
+    AUGMENT_KINDS = ("gaussian", "path")
+
+    def cnn_walk_augmented(self, images, head, walk, kind, n, noise_scale=1.0, seed=0, reference=0, path="reference",
+                           postprocess=None, max_batch=None):
+        """GaussianSmoother / PathIntegrator (wrapper.py:214-345) around an encoder walk, on the device: for the (B, H, W, 3)
+        images and their (B, L, D) heads, the B * n samples (kind 'gaussian': x + noise_scale * N(seed); 'path': the path of
+        op_augment_path) are explained in chunks of at most min(max_images, max_tokens, max_batch) samples — augment ->
+        encode_images(chunk) -> cnn_walk(chunk rows, the head of each row's image, walk) -> accumulate — and reduced to the
+        per-image mean of postprocess(map) (None / 'abs' / 'square'), for 'path' times (x - reference).  Chunks may cross
+        image boundaries; the result does not depend on the chunk size.  walk: any name of WALKS; under 'input_x_gradient'
+        the product is with the SAMPLE, as the reference's subanalyzer sees the augmented input.  Only the returned (B, H, W, 3)
+        float32 tensor is ever meant to leave the device.
+        The call overwrites the handle's encode caches with samples: afterwards they belong to no image (n_images = 0,
+        captions = None) and encode_images has to run again before anything else is explained."""
+        if walk not in self.WALKS:
+            raise ValueError("unknown walk %r: one of %s" % (walk, sorted(self.WALKS)))
+        if kind not in self.AUGMENT_KINDS:
+            raise ValueError("kind must be 'gaussian' or 'path'")
+        if postprocess not in _POST:
+            raise ValueError("Parameter 'postprocess' must be either None, 'abs', or 'square'.")
+        if path not in ("reference", "standard"):
+            raise ValueError("path must be 'reference' or 'standard'")
+        n = int(n)
+        if n < 1:
+            raise ValueError("the number of samples per image must be at least 1")
+        x = self._dev(images)
+        if x.dim() != 4 or tuple(x.shape[1:]) != (self.img_hw[0], self.img_hw[1], 3):
+            raise ValueError("images must be (B,%d,%d,3)" % self.img_hw)
+        B = int(x.shape[0])
+        Hd = self._dev(head).reshape(-1, self.L, self.D)
+        if Hd.shape[0] != B:
+            raise ValueError("X and head must have the same batch size")
+        chunk = min(self.max_images, self.max_tokens, int(max_batch) if max_batch else self.max_images)
+        if chunk < 1:
+            raise ValueError("max_batch must be at least 1")
+        acc = torch.zeros(x.shape, dtype=torch.float64, device=self.device)
+        samples = torch.empty((chunk,) + tuple(x.shape[1:]), dtype=torch.float32, device=self.device)
+        maps = torch.empty_like(samples)
+        try:
+            for r0 in range(0, B * n, chunk):
+                cnt = min(chunk, B * n - r0)
+                if kind == "gaussian":
+                    op_augment_gaussian(x, n, noise_scale, seed, r0, cnt, out=samples[:cnt])
+                else:
+                    op_augment_path(x, n, reference, path, r0, cnt, out=samples[:cnt])
+                self.encode_images(samples[:cnt])
+                rows = torch.arange(r0, r0 + cnt, device=self.device) // n
+                self.cnn_walk(list(range(cnt)), Hd.index_select(0, rows), walk, out=maps[:cnt])
+                op_reduce_accumulate(maps[:cnt], acc, n, r0, postprocess)
+        finally:
+            self.n_images = 0
+            self.captions = None
+        return op_reduce_finish(acc, n, x if kind == "path" else None, reference)
 
     def guided_gradcam(self, img_idx, t, want_cam=False):
         """Guided Grad-CAM (explainers.py:930-949 / :1634-1653) for n <= max_tokens (image, t) units in one chain on the
@@ -867,6 +922,103 @@ def op_gradcam(feat, img_idx, grads, g, upscale, gb=None, sigma=20.0):
     _capi.check(lib.lrp_op_gradcam(p(f), p(idx), p(d), p(M), p(gb), p(cam), p(out), n, B, int(g), int(upscale), D,
                                    gb.shape[3] if gb is not None else 0, _cur_stream(f.device)))
     return cam if gb is None else (out, cam)
+
+
+# ---- augment and reduce of SmoothGrad / IntegratedGradients (wrapper.py:78-345; csrc/augment_kernels.h)
+_POST = {None: 0, "abs": 1, "square": 2}
+_p = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None
+
+
+def _aug_input(x):
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() < 2 or not x.is_cuda:
+        raise ValueError("expected a (B, ...) float32 tensor on the device")
+    x = x.contiguous()
+    return x, int(x.shape[0]), int(x[0].numel())
+
+
+def _aug_rows(B, n, r0, count):
+    n, r0 = int(n), int(r0)
+    count = B * n - r0 if count is None else int(count)
+    if n < 1 or r0 < 0 or count < 1 or r0 + count > B * n:
+        raise ValueError("rows [%d, %d) are not rows of the (%d * %d, per_image) sample matrix" % (r0, r0 + count, B, n))
+    return n, r0, count
+
+
+def _aug_ref(x, ref):
+    """reference_inputs -> (tensor or None, scalar)"""
+    if np.isscalar(ref):
+        return None, float(ref)
+    r = ref if torch.is_tensor(ref) else torch.as_tensor(np.ascontiguousarray(ref, dtype=np.float32))
+    r = r.to(device=x.device, dtype=torch.float32)
+    try:
+        r = r.broadcast_to(x.shape).contiguous()
+    except RuntimeError:
+        raise ValueError("reference_inputs must be a scalar or broadcast to the input's shape %s" % (tuple(x.shape),))
+    return r, 0.0
+
+
+def op_augment_gaussian(x, n, sigma, seed=0, r0=0, count=None, out=None):
+    """Rows [r0, r0 + count) of GaussianSmoother's sample matrix (wrapper.py:221-225 in np.repeat order: row b * n + s is
+    x[b] + sigma * N(seed, row, element)) -> (count, ...) float32 tensor.  The noise is Philox4x32-10 + Box-Muller, a pure
+    function of (seed, row, element) (include/lrp_hip.h): any chunking gives the same bits."""
+    x, B, per = _aug_input(x)
+    n, r0, count = _aug_rows(B, n, r0, count)
+    if out is None:
+        out = torch.empty((count,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    _capi.check(_capi.load().lrp_op_augment_gaussian(_p(x), _p(out), B, n, per, r0, count, float(sigma),
+                                                     int(seed) & 0xFFFFFFFFFFFFFFFF, _cur_stream(x.device)))
+    return out
+
+
+def op_augment_path(x, n, reference=0, path="reference", r0=0, count=None, out=None):
+    """Rows [r0, r0 + count) of PathIntegrator's sample matrix: path='reference' is what the reference computes,
+    x + (s / n) (x - ref) (wrapper.py:268-288); path='standard' the published ref + (s / n) (x - ref)."""
+    if path not in ("reference", "standard"):
+        raise ValueError("path must be 'reference' or 'standard'")
+    x, B, per = _aug_input(x)
+    n, r0, count = _aug_rows(B, n, r0, count)
+    rt, rs = _aug_ref(x, reference)
+    if out is None:
+        out = torch.empty((count,) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    _capi.check(_capi.load().lrp_op_augment_path(_p(x), _p(rt), rs, _p(out), B, n, per, r0, count,
+                                                 0 if path == "reference" else 1, _cur_stream(x.device)))
+    return out
+
+
+def op_reduce_accumulate(maps, acc, n, r0=0, post=None):
+    """acc (B, ...) float64 += the rows of a chunk: maps (count, ...) float32 holds the maps of samples [r0, r0 + count);
+    post None / 'abs' / 'square' is applied per sample (gradient_based.py:110-137).  One thread per element, ascending
+    sample order, launches in stream order: the sum does not depend on the chunking."""
+    if post not in _POST:
+        raise ValueError("Parameter 'postprocess' must be either None, 'abs', or 'square'.")
+    if not torch.is_tensor(acc) or acc.dtype != torch.float64 or not acc.is_contiguous():
+        raise ValueError("acc must be a contiguous (B, ...) float64 tensor")
+    m, count, per = _aug_input(maps)
+    B = int(acc.shape[0])
+    if int(acc[0].numel()) != per:
+        raise ValueError("maps and acc differ in the size of a map")
+    n, r0, count = _aug_rows(B, n, r0, count)
+    _capi.check(_capi.load().lrp_op_reduce_mean(0, _p(m), _p(acc), B, n, per, r0, count, _POST[post], None, None, None, 0.0, 0,
+                                                _cur_stream(m.device)))
+    return acc
+
+
+def op_reduce_finish(acc, n, x=None, reference=0, out=None):
+    """float32(acc / n), or with x float32(acc / n * (x - reference)) (PathIntegrator, wrapper.py:290-296), rounded once."""
+    if not torch.is_tensor(acc) or acc.dtype != torch.float64 or not acc.is_contiguous():
+        raise ValueError("acc must be a contiguous (B, ...) float64 tensor")
+    B, per = int(acc.shape[0]), int(acc[0].numel())
+    rt, rs = None, 0.0
+    if x is not None:
+        x, Bx, perx = _aug_input(x)
+        if (Bx, perx) != (B, per):
+            raise ValueError("x and acc differ in shape")
+        rt, rs = _aug_ref(x, reference)
+    if out is None:
+        out = torch.empty(acc.shape, dtype=torch.float32, device=acc.device)
+    _capi.check(_capi.load().lrp_op_reduce_mean(1, None, _p(acc), B, int(n), per, 0, 0, 0, _p(out), _p(x), _p(rt), rs,
+                                                0 if x is None else 1, _cur_stream(acc.device)))
+    return out
 
 
 _EXAM_POOL = {None: 0, "max": 1, "ave": 2}

@@ -504,3 +504,75 @@ class ExplainImgCaptioningGridTDGuidedGradcam(_GuidedGradcamMixin, ExplainImgCap
 
     def guided_backproe(self, img_input, grads):
         return _GradientMixin._explain_CNN(self, img_input, grads)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Deconvnet, SmoothGrad and IntegratedGradients (innvestigate/analyzer/gradient_based.py:180-225, :273-319) as comparison engines
+# in the shape of the six above: decoder half = `_lstm_decoder_backward`, unchanged; CNN half = the analyzer named.  The reference
+# has no such classes (its wrappers cannot run with a replaced head, wrapper.py:84-86); the names follow its scheme.
+# ---------------------------------------------------------------------------------------------------------------
+class _DeconvnetMixin(_GradientMixin):
+    _walk = "deconvnet"
+
+
+class _AugmentedMixin(_GradientMixin):
+    """`_explain_CNN(X, R)` on an analyzer instance of its own, created on first use from an ImageModelSpec of the model's encoder
+    weights: a second, CNN-only handle, as every analyzer of analyzer.py has.  The explainer's own engine — its encode caches
+    and the decoder state of `_forward_beam_search` — is not touched by it."""
+    _analyzer_name = None
+    _batched_cnn = False     # one (image, head) per call: the samples of a word fill the analyzer's batch
+    _KW = ()
+
+    def __init__(self, *args, **kwargs):
+        self._analyzer_kwargs = {k: kwargs.pop(k) for k in self._KW + ("max_batch", "postprocess") if k in kwargs}
+        super(_AugmentedMixin, self).__init__(*args, **kwargs)
+        self._augmented = None
+
+    def _cnn_analyzer(self):
+        if self._augmented is None:
+            from . import analyzer as A
+            m = self._model
+            spec = A.ImageModelSpec(m.weights, cnn_cfg=m.cnn_cfg, img_hw=m.img_hw, resnet=getattr(m, "resnet", None))
+            self._augmented = getattr(A, self._analyzer_name)(spec, device=self._engine.device.index, **self._analyzer_kwargs)
+        return self._augmented
+
+    def _explain_CNN(self, X, relevance_value, as_tensor=False):
+        X = np.asarray(X, dtype=np.float32)
+        R = np.asarray(relevance_value, dtype=np.float32)
+        n = R.shape[0]
+        out = self._cnn_analyzer().analyze([np.repeat(X[:1], n, axis=0), R.reshape((n,) + tuple(R.shape[1:]))])
+        return torch.as_tensor(out).to(self._engine.device) if as_tensor else out
+
+
+class _SmoothGradMixin(_AugmentedMixin):
+    _analyzer_name = "SmoothGrad"
+    _KW = ("augment_by_n", "noise_scale", "seed")
+
+
+class _IntegratedGradientsMixin(_AugmentedMixin):
+    _analyzer_name = "IntegratedGradients"
+    _KW = ("steps", "reference_inputs", "path")
+
+
+class ExplainImgCaptioningAdaptiveAttentionDeconvnet(_DeconvnetMixin, ExplainImgCaptioningAdaptiveAttention):
+    _STATE_ATTRS = ExplainImgCaptioningAdaptiveAttention._STATE_ATTRS + ("ot_act",)
+
+
+class ExplainImgCaptioningAdaptiveAttentionSmoothGrad(_SmoothGradMixin, ExplainImgCaptioningAdaptiveAttention):
+    _STATE_ATTRS = ExplainImgCaptioningAdaptiveAttention._STATE_ATTRS + ("ot_act",)
+
+
+class ExplainImgCaptioningAdaptiveAttentionIntegratedGradients(_IntegratedGradientsMixin, ExplainImgCaptioningAdaptiveAttention):
+    _STATE_ATTRS = ExplainImgCaptioningAdaptiveAttention._STATE_ATTRS + ("ot_act",)
+
+
+class ExplainImgCaptioningGridTDDeconvnet(_DeconvnetMixin, ExplainImgCaptioningGridTDModel):
+    _STATE_ATTRS = ExplainImgCaptioningGridTDModel._STATE_ATTRS + ("o1t_act", "o2t_act")
+
+
+class ExplainImgCaptioningGridTDSmoothGrad(_SmoothGradMixin, ExplainImgCaptioningGridTDModel):
+    _STATE_ATTRS = ExplainImgCaptioningGridTDModel._STATE_ATTRS + ("o1t_act", "o2t_act")
+
+
+class ExplainImgCaptioningGridTDIntegratedGradients(_IntegratedGradientsMixin, ExplainImgCaptioningGridTDModel):
+    _STATE_ATTRS = ExplainImgCaptioningGridTDModel._STATE_ATTRS + ("o1t_act", "o2t_act")
