@@ -292,6 +292,8 @@ int lrp_set_fast_layers(lrp_handle* h, int64_t mask);
  * A CHANGE drops the encode caches like lrp_set_precision: explain calls return LRP_ERR_STATE until lrp_encode_images ran
  * again.  The first beta > 0 allocates the second gates, the two-chain buffers, the kept layer inputs and the packed matrices
  * (counted in lrp_workspace_bytes; idle again at beta = 0); a handle that never sets a beta > 0 allocates nothing.
+ * On a VGG-style handle the rule is the table of lrp_set_cnn_rules with this record, bias 1, on every conv: one rule state, and
+ * the buffers are the table's (a later table that needs the same ones finds them there).
  * A ResNet handle takes the rule as well: per conv + BN unit a second gate with Z_inh = conv(x, w-) + b, computed by
  * lrp_encode_images behind the unchanged forward (the pair-emitting path: the unit's own launch again against [w | w-]), the walk
  * with units 3 and 2 of a bottleneck block as dual-gate launches and unit 1 / the projection as one-gate launches over both chains;
@@ -313,8 +315,9 @@ int lrp_set_cnn_rule(lrp_handle* h, float alpha, float beta);
  * Fields a kind does not use are ignored.  LRP_ERR_INVALID: a wrong count, an unknown kind, bias outside {0, 1}, flat / w-square /
  * bounded above layer 0, eps < 0, low >= high, alpha / beta outside lrp_set_cnn_rule's check.  LRP_ERR_UNSUPPORTED: a ResNet handle;
  * an input-layer kind on a one-conv encoder.
- * A table that is the same alpha-beta record with bias on every layer IS lrp_set_cnn_rule(alpha, beta): it takes that entry's path,
- * to the bit ((1, 0) everywhere is the default walk), and lrp_set_cnn_rule in turn replaces any table.  Every other table runs the
+ * lrp_set_cnn_rule(alpha, beta) IS the table with the same alpha-beta record with bias on every layer: the two entries set one rule
+ * state and run the same code, to the bit ((1, 0) everywhere is the default walk, from either entry; the rule already set, from
+ * either entry, changes and drops nothing), and lrp_set_cnn_rule in turn replaces any table.  Every other table runs the
  * dense table walk: layer l reads one or two relevance chains (two for alpha-beta with beta > 0) against one matrix and applies
  * layer l-1's one or two gates; lrp_encode_images adds the denominator passes the rules need behind the unchanged forward.
  * Alpha-beta kinds and the three input-layer kinds run in exact fp32 and in three-term split-bf16 with the handle; with an epsilon
@@ -367,7 +370,8 @@ int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias
  *   outp = c x gp,  outn = c x gn       with c repeated 2 x 2 (nearest) when pool != 0.
  * sp_dev, sn_dev (NB, H, W, Cout); w_hwio_host (3, 3, Cin, Cout); gp_dev, gn_dev, outp_dev, outn_dev (NB, H u, W u, Cin), u = 2
  * with pool.  split != 0: on the split-bf16 path (channels % 8 == 0), fp32 otherwise (channels % 4 == 0).  The launch takes the
- * form lrp_conv_plan answers for LRP_PLAN_DUAL_MUL with Cin(plan) = 2 Cout, N(plan) = Cin. */
+ * form lrp_conv_plan answers for LRP_PLAN_DUAL_MUL with Cin(plan) = 2 Cout, N(plan) = Cin.  It is lrp_op_conv_rule with
+ * chains_in = gates_out = 2 and (p0, q0, p1, q1) = (alpha, 0, 0, -beta). */
 int lrp_op_conv_ab(const float* sp_dev, const float* sn_dev, const float* w_hwio_host, float alpha, float beta, const float* gp_dev,
                    const float* gn_dev, float* outp_dev, float* outn_dev, int32_t NB, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
                    int32_t pool, int32_t split, void* stream);

@@ -542,48 +542,8 @@ __global__ __launch_bounds__(256) void top_divide_split_kernel(const float* __re
   }
 }
 
-// ---- alpha-beta LRP with beta > 0 (RR:274-322, Encoder::explain_ab): the operands of the two-chain walk ----
-// Packers, HWIO kernel w[tap][ci][co] in HBM -> B operands of conv_igemm.h, zero padded (the buffers were zeroed at allocation:
-// only rows < the layer's own are written, every k of them).
-//   mode 0: forward [Cout rows][9 * CP], CP = cinp(Cin): w- — the inhibitor denominator conv Z_inh = conv(x+, w-) + b
-//   mode 1: backward [Cin rows][9 * CP], CP = cinp(2 Cout), taps flipped: k = tap' * CP + c, c < Cout: alpha w+[co = c],
-//           Cout <= c < 2 Cout: -beta w-[co = c - Cout] — both chains' transposed conv as ONE GEMM over [S+ | S-]
-__global__ __launch_bounds__(256) void pack_conv_ab_dev_kernel(const float* __restrict__ w, float* __restrict__ dst, int mode, int Cin,
-                                                               int Cout, int CP, int rows, float alpha, float beta) {
-  const int K = 9 * CP;
-  const size_t total = (size_t)rows * K;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int row = (int)(i / K), k = (int)(i % K), t = k / CP, c = k % CP;
-    float v = 0.f;
-    if (mode == 0) {
-      if (c < Cin) { const float x = w[((size_t)t * Cin + c) * Cout + row]; v = x < 0.f ? x : 0.f; }
-    } else if (c < Cout) {
-      const float x = w[((size_t)(8 - t) * Cin + row) * Cout + c];
-      v = x >= 0.f ? alpha * x : 0.f;
-    } else if (c < 2 * Cout) {
-      const float x = w[((size_t)(8 - t) * Cin + row) * Cout + c - Cout];
-      v = x < 0.f ? -beta * x : 0.f;
-    }
-    dst[i] = v;
-  }
-}
-// The image layer's: w (3,3,3,cout) ->
-//   fwd_n [cout][64]   w- | w+ against the im2col row (x+ patch | x- patch): Z_inh,1 = conv(x+, w-) + conv(x-, w+) (+ b in the epilogue)
-//   bwd   [54][Kb2]    Kb2 = cinp(2 cout), k = [S+ channels | S- channels]:
-//                      row t*6+c   (times x+): alpha w+ | -beta w-      row t*6+3+c (times x-): alpha w- | -beta w+
-__global__ __launch_bounds__(256) void pack_image_layer_ab_dev_kernel(const float* __restrict__ w, float* __restrict__ fwd_n,
-                                                                      float* __restrict__ bwd, int cout, int Kb2, float alpha, float beta) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= 27 * cout) return;
-  const int k = i / cout, co = i - k * cout, t = k / 3, c = k - 3 * t;
-  const float v = w[i], vp = v >= 0.f ? v : 0.f, vn = v < 0.f ? v : 0.f;
-  fwd_n[(size_t)co * 64 + k] = vn;
-  fwd_n[(size_t)co * 64 + 32 + k] = vp;
-  bwd[(size_t)(t * 6 + c) * Kb2 + co] = alpha * vp;
-  bwd[(size_t)(t * 6 + c) * Kb2 + cout + co] = -beta * vn;
-  bwd[(size_t)(t * 6 + 3 + c) * Kb2 + co] = alpha * vn;
-  bwd[(size_t)(t * 6 + 3 + c) * Kb2 + cout + co] = -beta * vp;
-}
+// ---- alpha-beta LRP with beta > 0 (RR:274-322): the chains and the inhibitor gate of the two-chain launches; their operands are
+// the rule packers' below ----
 // Two tensors [pixels][C] -> the walk's two-chain form [pixels][S+ (C) | S- (C)], fp32 or split8 (G = 4 / 8 channels per thread).
 // Z == nullptr: a plain join (the operator entry).  Otherwise the head of the walk (KG:898-900 per chain):
 //   S+ = R / safe(Z_act,top[img]),  S- = R / safe(Z_inh,top[img])      (sp = sn = R; per = pixels per map)
@@ -643,8 +603,10 @@ __global__ __launch_bounds__(256) void pool_gate_inh_kernel(const f32x4* __restr
 }
 
 // ---- rule table of the VGG walk (lrp_set_cnn_rules, Encoder::explain_table): operands and gates per conv ----
+// Packers, HWIO kernel w[tap][ci][co] in HBM -> B operands of conv_igemm.h, zero padded.
 // The packer of a conv above the image layer, per-chain coefficients on the sign halves: chain j holds p_j w+ + q_j w-
-//   bwd = 0: forward [Cout rows][9 * CP], CP = cinp(Cin), chain 0 only (a denominator conv: w+ (1,0), w- (0,1), w (1,1))
+//   bwd = 0: forward [Cout rows][9 * CP], CP = cinp(Cin), chain 0 only (a denominator conv: w+ (1,0), w (1,1), and w- (0,1) — the
+//            inhibitor's Z_inh = conv(x+, w-) + b)
 //   bwd = 1: backward [Cin rows][9 * CP], CP = cinp(chains * Cout), taps flipped, k = tap' * CP + j * Cout + co: the transposed conv
 //            of every chain as ONE GEMM over [S_0 | S_1]  ([alpha w+ ; -beta w-] = (alpha, 0), (0, -beta))
 // Every k of the rows < `rows` is written (zeros included); rows beyond stay as the buffer was cleared.
@@ -668,8 +630,9 @@ __global__ __launch_bounds__(256) void pack_conv_rule_dev_kernel(const float* __
 // The image layer's, by rule kind (include/lrp_hip.h LRP_RULE_*): w (3,3,3,cout) ->
 //   fwd_a [cout][64]  activator denominator against the im2col row (first patch | second patch): w+ | w-   (alpha-beta without the
 //                     bias: x+ | x-; bounded: x - low | x - high)                                       — nullptr: not wanted
-//   fwd_n [cout][64]  inhibitor denominator w- | w+                                                     — nullptr: not wanted
-//   bwd   [54][Kb]    tap-expanded channel reduction, row t*6+c the "+" column and t*6+3+c the "-" column of the stencil:
+//   fwd_n [cout][64]  inhibitor denominator w- | w+: Z_inh,1 = conv(x+, w-) + conv(x-, w+) (+ b in the epilogue) — nullptr: not wanted
+//   bwd   [54][Kb]    tap-expanded channel reduction, Kb = cinp(chains * cout), row t*6+c the "+" column (times x+) and t*6+3+c the
+//                     "-" column (times x-) of the stencil:
 //     alpha-beta   chains 1: w+ ; w-      chains 2 (k = [S+ | S-]): alpha w+ | -beta w- ; alpha w- | -beta w+
 //     epsilon      w ; 0        flat  1 ; 0        w-square  w^2 ; 0        bounded  w+ ; w-
 __global__ __launch_bounds__(256) void pack_image_layer_rule_dev_kernel(const float* __restrict__ w, float* __restrict__ fwd_a,

@@ -242,7 +242,7 @@ struct ConvArgs {
   float* pool_gc;
   unsigned char* pool_pos;
   float* pool_x;
-  // Dual-gate MUL epilogues (template DG; alpha-beta LRP with beta > 0, Encoder::explain_ab): the two relevance chains
+  // Dual-gate MUL epilogues (template DG; alpha-beta LRP with beta > 0, Encoder::explain_table): the two relevance chains
   // S+ = R / safe(Z_act) and S- = R / safe(Z_inh) travel as ONE tensor, channels [S+ (C) | S- (C)] per pixel, so that the
   // launch against the concatenated matrix [alpha w+ ; -beta w-] (K = taps x 2C) is the ordinary implicit GEMM with
   // Cin = 2C and its accumulator c = convT(S+, alpha w+) + convT(S-, -beta w-) is shared by both chains:

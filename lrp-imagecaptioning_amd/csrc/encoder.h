@@ -67,15 +67,13 @@ struct ConvLayer {
   bool norm_dirty = true;
   DevBuf Akeep;    // fine-tune step only: a_l of the layers whose output is the next conv's input (no pool after); the
                    // LRP path turns that storage into the gate in place
-  // alpha-beta rule with beta > 0 (Encoder::set_rule): the inhibitor gate G- = a / safe(Z_inh) next to G (same mask), the
-  // forward matrix w- of its denominator conv (fp32, split8) and the two-chain backward matrix [alpha w+ ; -beta w-]
-  // (cnn_kernels.h pack_conv_ab_dev_kernel; the image layer: pack_image_layer_ab_dev_kernel).  Allocated on the first beta > 0.
-  DevBuf Gn, w_fwd_n, w_fwd_ns, w_bwd_ab, w_bwd_ab_s;
-  bool ab_packed = false;
   // rule table (Encoder::set_table): the activator gate of a rule whose denominator is not the forward's Z+, the forward matrix of
   // that denominator (fp32, split8) and the layer's backward matrix over its one or two chains (cnn_kernels.h
-  // pack_conv_rule_dev_kernel / pack_image_layer_rule_dev_kernel).  Allocated by the first table that needs them.
+  // pack_conv_rule_dev_kernel / pack_image_layer_rule_dev_kernel); for alpha-beta with beta > 0 the inhibitor gate
+  // G- = a / safe(Z_inh) next to G (same mask) and the forward matrix w- of its denominator conv (fp32, split8).  Allocated by
+  // the first table that needs them.
   DevBuf Gt, w_fwd_t, w_fwd_ts, w_bwd_t, w_bwd_t_s;
+  DevBuf Gn, w_fwd_n, w_fwd_ns;
   bool t_packed = false;
   size_t act_elems() const { return (size_t)H * W * cout; }
 };
@@ -224,136 +222,14 @@ struct Encoder {
     return LRP_OK;
   }
 
-  // ---- alpha-beta rule (lrp_set_cnn_rule; RR:274-322 with beta > 0) ----
-  // R_in = alpha act - beta inh with two denominators per layer, Z_act (the Z+ of alpha1beta0) and Z_inh = conv(x+, w-) + b
-  // (behind a ReLU or a pool x- = 0: the second conv of each branch contributes its bias only).  The walk carries two chains
-  // S+ = R / safe(Z_act), S- = R / safe(Z_inh) as one tensor [S+ | S-] and every launch is ONE GEMM over both:
-  //   c = convT(S+, alpha w+) + convT(S-, -beta w-);  S+' = G+ c,  S-' = G- c        (conv_args.h ConvArgs::aux_b)
-  // beta = 0 (the default) is the alpha1beta0 walk: nothing here is allocated, launched or read.
-  float ab_alpha = 1.f, ab_beta = 0.f;
-  bool ab_on() const { return ab_beta > 0.f; }
-  DevBuf zntop, s0ab, s1ab;                            // Z_inh of the top layer; the two-chain ping-pong
   size_t max_act_elems() const {
     size_t m = 0;
     for (const ConvLayer& L : layers) m = std::max(m, L.act_elems());
     return m;
   }
-  int set_rule(float alpha, float beta, int64_t* total) {
-    if (alpha == ab_alpha && beta == ab_beta) return LRP_OK;
-    const bool was_on = ab_on();
-    if (beta > 0.f) {
-      auto mk = [&](DevBuf& d, size_t floats) -> int {
-        if (d.p) return LRP_OK;
-        LRP_TRY(d.alloc(floats * sizeof(float), total));
-        LRP_HIP_CHECK(hipMemset(d.p, 0, d.bytes));       // padding rows / columns stay zero
-        return LRP_OK;
-      };
-      const size_t B = (size_t)max_images, NT = (size_t)max_tokens;
-      for (size_t i = 0; i < layers.size(); ++i) {
-        ConvLayer& L = layers[i];
-        if (i + 1 < layers.size()) LRP_TRY(mk(L.Gn, B * L.act_elems()));
-        if (i == 0) {
-          LRP_TRY(mk(L.w_fwd_n, (size_t)conv_npad(L.cout) * 64));
-          const size_t nb = (size_t)conv_npad(IMG_T_COLS) * conv_cinp(2 * L.cout);
-          LRP_TRY(mk(L.w_bwd_ab, nb)); LRP_TRY(mk(L.w_bwd_ab_s, nb));
-        } else {
-          const size_t nf = (size_t)conv_npad(L.cout) * 9 * conv_cinp(L.cin), nb = (size_t)conv_npad(L.cin) * 9 * conv_cinp(2 * L.cout);
-          LRP_TRY(mk(L.w_fwd_n, nf)); LRP_TRY(mk(L.w_fwd_ns, nf));
-          LRP_TRY(mk(L.w_bwd_ab, nb)); LRP_TRY(mk(L.w_bwd_ab_s, nb));
-        }
-      }
-      LRP_TRY(mk(zntop, B * layers.back().act_elems()));
-      const size_t tok = std::max(2 * max_act_elems(), (size_t)img_h * img_w * IMG_T_COLS);
-      LRP_TRY(mk(s0ab, NT * tok)); LRP_TRY(mk(s1ab, NT * tok));
-      LRP_TRY(enable_keep_acts(total, true));            // the denominator convs read the layer inputs after the forward
-    } else {
-      keep_for_rule = false;                             // (the buffers stay, idle; the fine-tune step's own request stands)
-      keep_acts = keep_for_train;
-    }
-    ab_alpha = alpha; ab_beta = beta;
-    for (ConvLayer& L : layers) L.ab_packed = false;
-    encoded = 0;                                         // the caches belong to the old rule
-    return LRP_OK;
-  }
-  // the rule's operand copies of layer li from w_dev (HWIO, device)
-  int pack_ab_layer(int li, const float* w_dev, hipStream_t st) {
-    ConvLayer& L = layers[li];
-    auto split = [&](const float* src, float* dst, size_t n) {
-      hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n / 8)), dim3(256), 0, st, src, dst, n / 8);
-    };
-    if (li == 0) {
-      const int Kb2 = conv_cinp(2 * L.cout);
-      hipLaunchKernelGGL(pack_image_layer_ab_dev_kernel, dim3((27 * L.cout + 255) / 256), dim3(256), 0, st, w_dev, L.w_fwd_n.as<float>(),
-                         L.w_bwd_ab.as<float>(), L.cout, Kb2, ab_alpha, ab_beta);
-      split(L.w_bwd_ab.as<float>(), L.w_bwd_ab_s.as<float>(), (size_t)conv_npad(IMG_T_COLS) * Kb2);
-    } else {
-      const int CPi = conv_cinp(L.cin), CP2 = conv_cinp(2 * L.cout);
-      const size_t nf = (size_t)conv_npad(L.cout) * 9 * CPi, nb = (size_t)conv_npad(L.cin) * 9 * CP2;
-      hipLaunchKernelGGL(pack_conv_ab_dev_kernel, dim3(stream_grid((size_t)L.cout * 9 * CPi)), dim3(256), 0, st, w_dev, L.w_fwd_n.as<float>(), 0,
-                         L.cin, L.cout, CPi, L.cout, ab_alpha, ab_beta);
-      hipLaunchKernelGGL(pack_conv_ab_dev_kernel, dim3(stream_grid((size_t)L.cin * 9 * CP2)), dim3(256), 0, st, w_dev, L.w_bwd_ab.as<float>(), 1,
-                         L.cin, L.cout, CP2, L.cin, ab_alpha, ab_beta);
-      split(L.w_fwd_n.as<float>(), L.w_fwd_ns.as<float>(), nf);
-      split(L.w_bwd_ab.as<float>(), L.w_bwd_ab_s.as<float>(), nb);
-    }
-    LRP_HIP_CHECK(hipGetLastError());
-    L.ab_packed = true;
-    return LRP_OK;
-  }
-  bool ab_split() const {                                // the rule's arithmetic follows the handle's mode (as walk_mode's split)
-    if (prec != PREC_BF16X3) return false;
-    for (const ConvLayer& L : layers)
-      if (L.cout & 7) return false;
-    return true;
-  }
-  // Behind the forward (keep_acts: every conv's input is still there): per layer one more denominator conv with w- and the full
-  // bias, G- with the mask of G+; Z_inh of the top layer next to ztop.  Exact fp32 in LRP_PREC_FP32, three-term split-bf16 like
-  // the Z+ convs of the mixed modes otherwise; the image layer's GEMM stays fp32 as in every forward.
-  int inhibitor_pass(int B, hipStream_t st) {
-    if (gates_pending) {                                 // G+, bufZ and bufXs belong to the side stream until its gates are done
-      LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_gates, 0));
-      gates_pending = false;
-    }
-    const bool split = ab_split();
-    for (size_t li = 0; li < layers.size(); ++li) {
-      ConvLayer& L = layers[li];
-      if (!L.ab_packed) {
-        if (!L.raw_w_dev.p) return fail(LRP_ERR_STATE, "layer '%s': set its weights again after a change of the CNN rule", L.name.c_str());
-        LRP_TRY(pack_ab_layer((int)li, L.raw_w_dev.as<float>(), st));
-      }
-      const bool top = li + 1 == layers.size();
-      ConvArgs cz;
-      int zprec = PREC_FP32;
-      if (li == 0) {
-        LRP_TRY(im2col_gemm_args(B, st, cz));
-        cz.wpk = L.w_fwd_n.as<float>();
-      } else {
-        const float* x = layer_input((int)li);
-        if (split) {
-          LRP_TRY(split_copy(x, (size_t)B * L.H * L.W * L.cin / 8, st));
-          x = bufXs.as<float>();
-          zprec = PREC_BF16X3;
-        }
-        cz = fwd_conv_args(L, B, x);
-        cz.wpk = split ? L.w_fwd_ns.as<float>() : L.w_fwd_n.as<float>();
-      }
-      cz.N = L.cout;
-      cz.out = top ? zntop.as<float>() : bufZ.as<float>();
-      if (!top && !L.pool_after) { cz.gate_src = L.Akeep.as<float>(); cz.out = L.Gn.as<float>(); }
-      LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, st, zprec));
-      if (!top && L.pool_after) {
-        LRP_TRY(full_gate((int)li, st));
-        const size_t n4 = (size_t)B * L.act_elems() / 4;
-        hipLaunchKernelGGL(pool_gate_inh_kernel, dim3(stream_grid(n4)), dim3(256), 0, st, L.G.as<f32x4>(), L.P.as<float>(), bufZ.as<f32x4>(),
-                           L.Gn.as<f32x4>(), B, L.H, L.W, L.cout);
-        LRP_HIP_CHECK(hipGetLastError());
-      }
-    }
-    return LRP_OK;
-  }
 
   // Fine-tune step: the weight gradient of layer l needs a_{l-1}; keep what the LRP caches drop.
-  // Two users: the fine-tune step (for the life of the handle once lrp_train_begin ran) and a beta > 0 rule (while it is set).
+  // Two users: the fine-tune step (for the life of the handle once lrp_train_begin ran) and a rule table (while it is set).
   // keep_acts = either; each asks and releases for itself, so neither can switch the other's activations off.
   bool keep_acts = false, keep_for_train = false, keep_for_rule = false;
   int enable_keep_acts(int64_t* total, bool for_rule = false) {
@@ -485,8 +361,6 @@ struct Encoder {
     ConvLayer& L = layers[li];
     if (!L.have_w || !L.have_b) return fail(LRP_ERR_STATE, "layer %d has no operand copies to rebuild", li);
     LRP_TRY(repack_conv_weight_from_device(li, w_dev, tmp, st));
-    L.ab_packed = false;
-    if (ab_on()) LRP_TRY(pack_ab_layer(li, w_dev, st));
     L.t_packed = false;
     if (table_on()) LRP_TRY(pack_table_layer(li, w_dev, st));
     L.norm_dirty = true;
@@ -509,8 +383,7 @@ struct Encoder {
     LRP_TRY(repack_conv_weight_from_device(li, L.raw_w_dev.as<float>(), pack_tmp.as<float>(), st));
     L.have_w = true;
     L.norm_dirty = true;
-    L.ab_packed = false;                               // (repacked by the next encode under a beta > 0 rule)
-    L.t_packed = false;                                // (... or under a rule table)
+    L.t_packed = false;                                // (repacked by the next encode under a rule table)
     encoded = 0;                                       // caches belong to the old weights
     return LRP_OK;
   }
@@ -558,10 +431,6 @@ struct Encoder {
     LRP_TRY(fp.mode == FWD_EXACT ? forward_exact(B, st) : fp.mode == FWD_FAST ? forward_fast(B, st)
             : fp.emit ? forward_pairs_emit(B, st) : forward_pairs_split(B, st));
     encoded = B;
-    if (ab_on()) {
-      const int rc = inhibitor_pass(B, st);
-      if (rc != LRP_OK) { encoded = 0; return rc; }
-    }
     if (table_on() && table_runs()) {
       const int rc = table_pass(B, st);
       if (rc != LRP_OK) { encoded = 0; return rc; }
@@ -1027,73 +896,55 @@ struct Encoder {
     return LRP_OK;
   }
 
-  // The two-chain walk of the alpha-beta rule with beta > 0 (see set_rule): the dense dual-gate launches conv_plan answers for
-  // ConvAsk::dual_mul; the image layer is the same tap-expanded GEMM + stencil over K = [S+ | S-].
-  int explain_ab(int n, const int* row2img_dev, const float* R_feat_dev, float* R_img_dev, hipStream_t st) {
-    const bool split = ab_split();
-    const int rp = split ? PREC_BF16X3 : PREC_FP32;
-    float *S = s0ab.as<float>(), *Snext = s1ab.as<float>();
-    {
-      const ConvLayer& T = layers.back();
-      const size_t pixels = (size_t)n * T.H * T.W, items = pixels * (T.cout / (split ? 8 : 4));
-      if (split)
-        hipLaunchKernelGGL(chain_join_kernel<true>, dim3(stream_grid(items)), dim3(256), 0, st, R_feat_dev, R_feat_dev, ztop.as<float>(),
-                           zntop.as<float>(), row2img_dev, S, pixels, T.H * T.W, T.cout);
-      else
-        hipLaunchKernelGGL(chain_join_kernel<false>, dim3(stream_grid(items)), dim3(256), 0, st, R_feat_dev, R_feat_dev, ztop.as<float>(),
-                           zntop.as<float>(), row2img_dev, S, pixels, T.H * T.W, T.cout);
-      LRP_HIP_CHECK(hipGetLastError());
+  // The image layer's launch of a walk; `ca` holds the input, the matrix and row2img.  T GEMM + 9-tap stencil in one launch (patch
+  // tiles, T stays in LDS) into R_img_dev — or, with LRP_IMG_FUSED=0, the 1-tap GEMM over the pixels into T, which
+  // image_stencil_tail turns into R_img_dev.  Returns the epilogue.
+  int image_layer_args(ConvArgs& ca, int n, float* T, float* R_img_dev, int img_mode, float lo, float hi) const {
+    const ConvLayer& L = layers[0];
+    ca.taps = 1; ca.N = IMG_T_COLS;
+    if (img_fused()) {
+      ca.out = R_img_dev; ca.ximg = images.as<float>(); ca.img_mode = img_mode; ca.img_lo = lo; ca.img_hi = hi;
+      return EPI_IMG_STENCIL;
     }
-    for (int li = (int)layers.size() - 1; li >= 0; --li) {
-      const ConvLayer& L = layers[li];
-      ConvArgs ca = conv3x3_args(L, n, S, 2 * L.cout);
-      ca.wpk = split ? L.w_bwd_ab_s.as<float>() : L.w_bwd_ab.as<float>();
-      ca.row2img = row2img_dev;
-      int epi;
-      if (li == 0 && img_fused()) {
-        ca.taps = 1; ca.N = IMG_T_COLS; ca.out = R_img_dev; ca.ximg = images.as<float>(); ca.img_mode = 0;
-        epi = EPI_IMG_STENCIL;
-      } else if (li == 0) {
-        ca.NB = n * L.H * L.W; ca.H = 1; ca.W = 1; ca.taps = 1;
-        ca.N = IMG_T_COLS; ca.out = Snext; epi = EPI_STORE;
-      } else {
-        const ConvLayer& P = layers[li - 1];
-        ca.N = L.cin; ca.aux = P.G.as<float>(); ca.aux_b = P.Gn.as<float>();
-        ca.out = Snext; ca.out_b = Snext + L.cin; ca.ostride = 2 * L.cin;
-        epi = P.pool_after ? EPI_MUL_UP2 : EPI_MUL;
-        if (P.pool_after) LRP_TRY(full_gate(li - 1, st));
-      }
-      prof.begin(st);
-      LRP_HIP_CHECK(conv_launch(epi, ca, st, rp));
-      prof.end(st, 2.0 * layer_flop(n, li));
-      std::swap(S, Snext);
-    }
-    if (!img_fused()) {
-      const ConvLayer& L0 = layers[0];
-      hipLaunchKernelGGL(img_stencil_kernel, dim3(stream_grid((size_t)n * L0.H * L0.W)), dim3(256), 0, st, S, images.as<float>(), row2img_dev,
-                         R_img_dev, n, L0.H, L0.W, 0, 0.f, 0.f);
-      LRP_HIP_CHECK(hipGetLastError());
-    }
+    ca.NB = n * L.H * L.W; ca.H = 1; ca.W = 1; ca.out = T;
+    return EPI_STORE;
+  }
+  // LRP_IMG_FUSED=0: T (n, H, W, 54) -> R_img_dev, the 9-tap shift-and-add and the selection of x+ / x- (or what img_mode says)
+  int image_stencil_tail(int n, const float* T, const int* row2img_dev, float* R_img_dev, int img_mode, float lo, float hi, hipStream_t st) {
+    if (img_fused()) return LRP_OK;
+    const ConvLayer& L0 = layers[0];
+    hipLaunchKernelGGL(img_stencil_kernel, dim3(stream_grid((size_t)n * L0.H * L0.W)), dim3(256), 0, st, T, images.as<float>(), row2img_dev,
+                       R_img_dev, n, L0.H, L0.W, img_mode, lo, hi);
+    LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   }
 
-
-  // ---- rule table (lrp_set_cnn_rules): one rule per conv ----
+  // ---- rule table (lrp_set_cnn_rule, lrp_set_cnn_rules): one rule per conv ----
   // Layer l reads k_l relevance chains S_l = R_l / den_l — two for alpha-beta with beta > 0, one otherwise — as one tensor against one
-  // tap-flipped matrix ([alpha w+ ; -beta w-], w+ or w) and applies the k_{l-1} gates of layer l-1's rule in its epilogue: the
-  // launches of explain_ab, plus "two chains in, one gate" (the ordinary MUL epilogue over Cin = 2 Cout) and "one chain in, two
-  // gates" (the dual-gate epilogue over Cin = Cout).  The gates that are not the forward's come from table_pass at encode.
+  // tap-flipped matrix ([alpha w+ ; -beta w-], w+ or w) and applies the k_{l-1} gates of layer l-1's rule in its epilogue.
+  // Alpha-beta with beta > 0 (RR:274-322) is R_in = alpha act - beta inh with two denominators per layer, Z_act (the Z+ of
+  // alpha1beta0) and Z_inh = conv(x+, w-) + b (behind a ReLU or a pool x- = 0: the second conv of each branch contributes its bias
+  // only).  Its chains S+ = R / safe(Z_act), S- = R / safe(Z_inh) travel as one tensor [S+ | S-] and every launch is ONE GEMM over both:
+  //   c = convT(S+, alpha w+) + convT(S-, -beta w-);  S+' = G+ c,  S-' = G- c        (conv_args.h ConvArgs::aux_b)
+  // — the dense dual-gate launches conv_plan answers for ConvAsk::dual_mul; the image layer is the same tap-expanded
+  // GEMM + stencil over K = [S+ | S-].  Between rules of different chain counts: "two chains in, one gate" (the ordinary MUL epilogue
+  // over Cin = 2 Cout) and "one chain in, two gates" (the dual-gate epilogue over Cin = Cout).  The gates that are not the forward's
+  // come from table_pass at encode.
   // Dense launches only: no compact pool interface, no folded image layer, no sparse or weights-in-registers forms.
   struct ConvRule {
     int kind = LRP_RULE_ALPHA_BETA, bias = 1;
     float alpha = 1.f, beta = 0.f, eps = 0.f, low = 0.f, high = 0.f;
     int chains() const { return kind == LRP_RULE_ALPHA_BETA && beta > 0.f ? 2 : 1; }
     bool own_gate() const { return kind != LRP_RULE_ALPHA_BETA || !bias; }       // activator gate not the forward's a / safe(Z+)
+    bool fwd_a() const { return (kind == LRP_RULE_ALPHA_BETA && !bias) || kind == LRP_RULE_BOUNDED; }   // ... and its denominator a conv with w+ | w-
     bool input_only() const { return kind == LRP_RULE_FLAT || kind == LRP_RULE_WSQUARE || kind == LRP_RULE_BOUNDED; }
   };
-  std::vector<ConvRule> table;                         // empty: no table (the default walk or set_rule's)
+  // The handle's rule.  Empty: the default alpha1beta0 walk with all its fast forms — nothing below is allocated, launched or read.
+  // Anything else, the same (alpha, beta > 0, bias) record on every conv (the one-rule entry) included, is a table.
+  std::vector<ConvRule> table;
   DevBuf zt_top, wsq_zc;                               // the top layer's activator denominator where it is not ztop; w-square's border classes
   DevBuf a1b;                                          // BoundedRule: im2col of the image layer over (x - low | x - high) — a1 stays the forward's (the fine-tune step reads it)
+  DevBuf zntop, s0ab, s1ab;                            // two chains: Z_inh of the top layer; the two-chain ping-pong
   bool table_on() const { return !table.empty(); }
   bool table_has_eps() const {
     for (const ConvRule& r : table)
@@ -1103,15 +954,20 @@ struct Encoder {
   // epsilon kinds are exact-fp32 only (their gate a / (a + eps) is a step in a for small eps: a ReLU decision the fp16-pair forward
   // takes differently moves the map by O(1)); fp16 pairs have no table walk at all
   bool table_runs() const { return !walk_f16 && (!table_has_eps() || prec == PREC_FP32); }
-  bool table_split() const { return ab_split() && !table_has_eps(); }
+  bool rule_split() const {                              // the table's arithmetic follows the handle's mode (as walk_mode's split)
+    if (prec != PREC_BF16X3) return false;
+    for (const ConvLayer& L : layers)
+      if (L.cout & 7) return false;
+    return true;
+  }
+  bool table_split() const { return rule_split() && !table_has_eps(); }
   void clear_table() {
     if (!table_on()) return;
     table.clear();
-    keep_for_rule = ab_on();
-    keep_acts = keep_for_train || keep_for_rule;
-    encoded = 0;
+    keep_for_rule = false;                               // (the buffers stay, idle; the fine-tune step's own request stands)
+    keep_acts = keep_for_train;
+    encoded = 0;                                         // the caches belong to the old rule
   }
-  // `rules` is validated (engine.hip) and is not the same alpha-beta-with-bias record on every layer
   // does layer li of `rules` walk on the default walk's own backward matrix (w+ tap-flipped; the image layer: w+ ; w-)?
   static bool rule_on_default_matrix(const ConvRule& r) { return r.kind == LRP_RULE_ALPHA_BETA && r.bias && r.chains() == 1; }
   static int table_chains(const std::vector<ConvRule>& rules) {
@@ -1119,6 +975,7 @@ struct Encoder {
     for (const ConvRule& r : rules) k = std::max(k, r.chains());
     return k;
   }
+  // `rules` is validated (engine.hip) and not empty
   int set_table(const std::vector<ConvRule>& rules, int64_t* total) {
     // a buffer appears, or grows, with the first table that needs it at that size: everything is sized by THIS table's chain counts
     auto mk = [&](DevBuf& d, size_t floats) -> int {
@@ -1136,10 +993,9 @@ struct Encoder {
       const int k = r.chains();
       if (!top && r.own_gate()) LRP_TRY(mk(L.Gt, B * L.act_elems()));
       if (!top && k == 2) LRP_TRY(mk(L.Gn, B * L.act_elems()));
-      const bool fwd_a = (r.kind == LRP_RULE_ALPHA_BETA && !r.bias) || r.kind == LRP_RULE_BOUNDED;
       const size_t nf = i == 0 ? (size_t)conv_npad(L.cout) * 64 : (size_t)conv_npad(L.cout) * 9 * conv_cinp(L.cin);
       const size_t nb = i == 0 ? (size_t)conv_npad(IMG_T_COLS) * conv_cinp(k * L.cout) : (size_t)conv_npad(L.cin) * 9 * conv_cinp(k * L.cout);
-      if (fwd_a) { LRP_TRY(mk(L.w_fwd_t, nf)); if (i) LRP_TRY(mk(L.w_fwd_ts, nf)); }
+      if (r.fwd_a()) { LRP_TRY(mk(L.w_fwd_t, nf)); if (i) LRP_TRY(mk(L.w_fwd_ts, nf)); }
       if (k == 2) { LRP_TRY(mk(L.w_fwd_n, nf)); if (i) LRP_TRY(mk(L.w_fwd_ns, nf)); }
       if (!rule_on_default_matrix(r)) { LRP_TRY(mk(L.w_bwd_t, nb)); LRP_TRY(mk(L.w_bwd_t_s, nb)); }
       L.t_packed = false;
@@ -1165,7 +1021,7 @@ struct Encoder {
     auto split = [&](const float* src, float* dst, size_t n) {
       hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n / 8)), dim3(256), 0, st, src, dst, n / 8);
     };
-    const bool fwd_a = (r.kind == LRP_RULE_ALPHA_BETA && !r.bias) || r.kind == LRP_RULE_BOUNDED;
+    const bool fwd_a = r.fwd_a();
     const bool own_bwd = !rule_on_default_matrix(r);
     if (own_bwd) {                                       // the last table's layout may have been another: cleared in stream order
       LRP_HIP_CHECK(hipMemsetAsync(L.w_bwd_t.p, 0, L.w_bwd_t.bytes, st));
@@ -1199,13 +1055,13 @@ struct Encoder {
     }
     LRP_HIP_CHECK(hipGetLastError());
     L.t_packed = true;
-    L.ab_packed = false;                                 // (w_fwd_n is shared with set_rule's matrices: that path packs again)
     return LRP_OK;
   }
   const float* table_gate(int li) const { return table[li].own_gate() ? layers[li].Gt.as<float>() : layers[li].G.as<float>(); }
-  // Behind the forward, like inhibitor_pass: per layer the denominators its rule needs beyond the forward's Z+ — over the kept layer
-  // inputs, exact fp32 or three-term split-bf16 with the handle (epsilon tables: fp32) — and the gates from them.  A pooled layer's
-  // gates take the arg-max mask from G+.
+  // Behind the forward (keep_acts: every conv's input is still there): per layer the denominators its rule needs beyond the forward's
+  // Z+ — over the kept layer inputs, exact fp32 or three-term split-bf16 like the Z+ convs of the mixed modes with the handle
+  // (epsilon tables: fp32; the image layer's GEMM stays fp32 as in every forward) — and the gates from them.  A pooled layer's
+  // gates take the arg-max mask from G+; the top layer has no gate, its denominators stay next to ztop.
   int table_pass(int B, hipStream_t st) {
     if (gates_pending) {
       LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_gates, 0));
@@ -1221,8 +1077,11 @@ struct Encoder {
       }
       const bool top = li + 1 == layers.size();
       if (!top && L.pool_after) LRP_TRY(full_gate((int)li, st));
-      // one denominator conv: matrix (fp32, split8 or nullptr), bias or none, into `dst`
-      auto den_conv = [&](const float* w32, const float* ws, bool bias, bool bounded, float* dst) -> int {
+      // the gate a_l / safe(Z) of a layer with no pool behind it leaves the denominator conv's epilogue (ConvArgs::gate_src): Z
+      // never goes to memory.  rule_gate_kernel's zmode 0 gives the same numbers, up to the sign of a zero where a_l = 0 and Z < 0.
+      const bool fuse = !top && !L.pool_after;
+      // one denominator conv: matrix (fp32, split8 or nullptr), bias or none; Z, or with `gated` the fused gate, into `dst`
+      auto den_conv = [&](const float* w32, const float* ws, bool bias, bool bounded, float* dst, bool gated) -> int {
         ConvArgs cz;
         int zprec = PREC_FP32;
         if (li == 0 && bounded) {                        // its own im2col matrix: a1 stays what the forward built
@@ -1249,6 +1108,7 @@ struct Encoder {
         if (!bias) cz.bias = nullptr;
         cz.N = L.cout;
         cz.out = dst;
+        if (gated) cz.gate_src = L.Akeep.as<float>();
         LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, st, zprec));
         return LRP_OK;
       };
@@ -1264,21 +1124,22 @@ struct Encoder {
       float* zbuf = bufZ.as<float>();
       if (r.own_gate()) {                                // the activator chain
         float* zdst = top ? zt_top.as<float>() : zbuf;
+        float* gdst = fuse ? L.Gt.as<float>() : zdst;    // (a v / safe(z) gate)
         switch (r.kind) {
           case LRP_RULE_ALPHA_BETA:                      // without the bias: conv(x+, w+) + conv(x-, w-)
-            LRP_TRY(den_conv(L.w_fwd_t.as<float>(), L.w_fwd_ts.as<float>(), false, false, zdst));
-            if (!top) LRP_TRY(gate(zbuf, 0, L.Gt.as<float>()));
+            LRP_TRY(den_conv(L.w_fwd_t.as<float>(), L.w_fwd_ts.as<float>(), false, false, gdst, fuse));
+            if (!top && !fuse) LRP_TRY(gate(zbuf, 0, L.Gt.as<float>()));
             break;
           case LRP_RULE_BOUNDED:
-            LRP_TRY(den_conv(L.w_fwd_t.as<float>(), nullptr, false, true, zdst));
-            if (!top) LRP_TRY(gate(zbuf, 0, L.Gt.as<float>()));
+            LRP_TRY(den_conv(L.w_fwd_t.as<float>(), nullptr, false, true, gdst, fuse));
+            if (!top && !fuse) LRP_TRY(gate(zbuf, 0, L.Gt.as<float>()));
             break;
           case LRP_RULE_EPSILON:
             // behind a ReLU relevance arrives only where a > 0, and there Z = a with the bias: no conv.  The top layer's relevance
             // is the caller's, and without the bias Z is another sum: one conv with the full w (the exact activation conv's matrix;
             // the image layer: the w rows of its dual matrix)
             if (top || !r.bias) {
-              LRP_TRY(den_conv(li == 0 ? L.w_fwd.as<float>() : L.w_fwd_a.as<float>(), nullptr, r.bias != 0, false, zdst));
+              LRP_TRY(den_conv(li == 0 ? L.w_fwd.as<float>() : L.w_fwd_a.as<float>(), nullptr, r.bias != 0, false, zdst, false));
               if (top) {
                 const size_t nz = (size_t)B * L.act_elems();
                 hipLaunchKernelGGL(stab_eps_kernel, dim3(stream_grid(nz)), dim3(256), 0, st, zdst, nz, r.eps);
@@ -1295,18 +1156,13 @@ struct Encoder {
         }
       }
       if (r.chains() == 2) {                             // the inhibitor chain: conv(x+, w-) + conv(x-, w+), with the bias or without
-        if (top) {
-          LRP_TRY(den_conv(L.w_fwd_n.as<float>(), L.w_fwd_ns.as<float>(), r.bias != 0, false, zntop.as<float>()));
-        } else {
-          LRP_TRY(den_conv(L.w_fwd_n.as<float>(), L.w_fwd_ns.as<float>(), r.bias != 0, false, zbuf));
+        LRP_TRY(den_conv(L.w_fwd_n.as<float>(), L.w_fwd_ns.as<float>(), r.bias != 0, false,
+                         top ? zntop.as<float>() : fuse ? L.Gn.as<float>() : zbuf, fuse));
+        if (!top && L.pool_after) {
           const size_t n4 = (size_t)B * L.act_elems() / 4;
-          if (L.pool_after) {
-            hipLaunchKernelGGL(pool_gate_inh_kernel, dim3(stream_grid(n4)), dim3(256), 0, st, L.G.as<f32x4>(), L.P.as<float>(),
-                               reinterpret_cast<const f32x4*>(zbuf), L.Gn.as<f32x4>(), B, L.H, L.W, L.cout);
-            LRP_HIP_CHECK(hipGetLastError());
-          } else {
-            LRP_TRY(gate(zbuf, 0, L.Gn.as<float>()));
-          }
+          hipLaunchKernelGGL(pool_gate_inh_kernel, dim3(stream_grid(n4)), dim3(256), 0, st, L.G.as<f32x4>(), L.P.as<float>(),
+                             reinterpret_cast<const f32x4*>(zbuf), L.Gn.as<f32x4>(), B, L.H, L.W, L.cout);
+          LRP_HIP_CHECK(hipGetLastError());
         }
       }
     }
@@ -1314,7 +1170,7 @@ struct Encoder {
   }
   // the table's walk
   int explain_table(int n, const int* row2img_dev, const float* R_feat_dev, float* R_img_dev, hipStream_t st) {
-    if (walk_f16) return fail(LRP_ERR_UNSUPPORTED, "LRP_PREC_F16X2 has no rule-table walk");
+    if (walk_f16) return fail(LRP_ERR_UNSUPPORTED, "LRP_PREC_F16X2 has no rule-table walk (its per-token scaling is per chain)");
     if (!table_runs()) return fail(LRP_ERR_UNSUPPORTED, "epsilon rules run in LRP_PREC_FP32 only");
     const bool split = table_split();
     const int rp = split ? PREC_BF16X3 : PREC_FP32;
@@ -1361,13 +1217,8 @@ struct Encoder {
       else ca.wpk = split ? L.w_bwd_t_s.as<float>() : L.w_bwd_t.as<float>();
       ca.row2img = row2img_dev;
       int epi;
-      if (li == 0 && img_fused()) {
-        ca.taps = 1; ca.N = IMG_T_COLS; ca.out = R_img_dev; ca.ximg = images.as<float>(); ca.img_mode = img_mode;
-        ca.img_lo = r0.low; ca.img_hi = r0.high;
-        epi = EPI_IMG_STENCIL;
-      } else if (li == 0) {
-        ca.NB = n * L.H * L.W; ca.H = 1; ca.W = 1; ca.taps = 1;
-        ca.N = IMG_T_COLS; ca.out = Snext; epi = EPI_STORE;
+      if (li == 0) {
+        epi = image_layer_args(ca, n, Snext, R_img_dev, img_mode, r0.low, r0.high);
       } else {
         const ConvLayer& P = layers[li - 1];
         if (P.pool_after) LRP_TRY(full_gate(li - 1, st));
@@ -1380,13 +1231,7 @@ struct Encoder {
       prof.end(st, (double)k * layer_flop(n, li));
       std::swap(S, Snext);
     }
-    if (!img_fused()) {
-      const ConvLayer& L0 = layers[0];
-      hipLaunchKernelGGL(img_stencil_kernel, dim3(stream_grid((size_t)n * L0.H * L0.W)), dim3(256), 0, st, S, images.as<float>(), row2img_dev,
-                         R_img_dev, n, L0.H, L0.W, img_mode, r0.low, r0.high);
-      LRP_HIP_CHECK(hipGetLastError());
-    }
-    return LRP_OK;
+    return image_stencil_tail(n, S, row2img_dev, R_img_dev, img_mode, r0.low, r0.high, st);
   }
 
   // R_feat_dev (n, top_h*top_w, top_c) -> R_img_dev (n, img_h, img_w, 3); row2img_dev: device int[n]
@@ -1405,12 +1250,10 @@ struct Encoder {
     if (walk < 0 || walk > 4) return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
     if (encoded < 1 || features_only) return fail(LRP_ERR_STATE, "lrp_encode_images must run before the CNN explain");
     if (gates_pending) LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_gates, 0));   // gates / Z_top come from the side stream
+    // (the gradient walks and the fine-tune step ignore the rule)
     if (table_on() && walk == 0 && !layer_hook) return explain_table(n, row2img_dev, R_feat_dev, R_img_dev, st);
-    if (ab_on() && walk == 0 && !layer_hook) {           // (the gradient walks and the fine-tune step ignore the rule)
-      if (walk_f16) return fail(LRP_ERR_UNSUPPORTED, "LRP_PREC_F16X2 has no alpha-beta walk with beta > 0 (its per-token scaling is per chain)");
-      return explain_ab(n, row2img_dev, R_feat_dev, R_img_dev, st);
-    }
     const WalkMode m = walk_mode(n, walk, layer_hook != nullptr);
+    const int img_mode = walk == 0 ? 0 : walk == 2 ? 2 : 1;
     float *S = s0.as<float>(), *Snext = s1.as<float>();
     if (m.f16) {
       const size_t cnt = (layers.size() + 1) * (size_t)max_tokens;
@@ -1456,14 +1299,8 @@ struct Encoder {
       ca.row2img = row2img_dev; ca.order = L.order.get(); ca.row2img_host = r2i_host;
       ca.gate_binary = walk != 0; ca.relu_out = walk == 3 || walk == 4;
       int epi;
-      if (li == 0 && img_fused()) {
-        // T GEMM + 9-tap stencil in one launch (patch tiles, T stays in LDS)
-        ca.taps = 1; ca.N = IMG_T_COLS; ca.out = R_img_dev; ca.ximg = images.as<float>();
-        ca.img_mode = walk == 0 ? 0 : walk == 2 ? 2 : 1;
-        epi = EPI_IMG_STENCIL;
-      } else if (li == 0) {
-        ca.NB = n * L.H * L.W; ca.H = 1; ca.W = 1; ca.taps = 1;          // 1-tap GEMM over the pixels
-        ca.N = IMG_T_COLS; ca.out = Snext; epi = EPI_STORE;
+      if (li == 0) {
+        epi = image_layer_args(ca, n, Snext, R_img_dev, img_mode, 0.f, 0.f);
       } else {
         const ConvLayer& P = layers[li - 1];
         ca.N = L.cin; ca.aux = P.G.as<float>(); ca.out = Snext;
@@ -1504,13 +1341,7 @@ struct Encoder {
       if (ca.img_part) return fold_image_sum(n, fold, ca.img_part, row2img_dev, R_img_dev, st);
       std::swap(S, Snext);
     }
-    if (!img_fused()) {  // S now holds T (n, H, W, 54): 9-tap shift-and-add and the x+/x- selection
-      const ConvLayer& L0 = layers[0];
-      hipLaunchKernelGGL(img_stencil_kernel, dim3(stream_grid((size_t)n * L0.H * L0.W)), dim3(256), 0, st, S,
-                         images.as<float>(), row2img_dev, R_img_dev, n, L0.H, L0.W, walk == 0 ? 0 : walk == 2 ? 2 : 1, 0.f, 0.f);
-      LRP_HIP_CHECK(hipGetLastError());
-    }
-    return LRP_OK;
+    return image_stencil_tail(n, S, row2img_dev, R_img_dev, img_mode, 0.f, 0.f, st);   // (S now holds T)
   }
 };
 

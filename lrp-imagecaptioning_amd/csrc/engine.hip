@@ -415,6 +415,36 @@ int lrp_set_precision(lrp_handle* h, int32_t mode) {
   });
 }
 
+// The rule of a VGG handle, from either entry: `t` is validated, one record per conv.  Alpha-beta with the bias and beta == 0 on every
+// conv is the default walk, which is the empty table.
+static int set_vgg_table(lrp_handle* h, std::vector<Encoder::ConvRule> t) {
+  Encoder& e = h->enc;
+  bool is_default = true;
+  for (const Encoder::ConvRule& r : t)
+    if (r.kind != LRP_RULE_ALPHA_BETA || !r.bias || r.beta > 0.f) is_default = false;
+  if (is_default) t.clear();
+  bool same = t.size() == e.table.size();                // the same rule again changes nothing
+  for (size_t i = 0; same && i < t.size(); ++i) {
+    const Encoder::ConvRule &a = e.table[i], &b = t[i];
+    if (a.kind != b.kind || a.bias != b.bias || a.alpha != b.alpha || a.eps != b.eps || a.low != b.low || a.high != b.high) same = false;
+  }
+  if (same) return LRP_OK;
+  LRP_TRY(h->trainer.drop_early_forward(nullptr));
+  if (t.empty()) {
+    e.clear_table();
+    return LRP_OK;
+  }
+  LRP_TRY(e.set_table(t, &h->ws_bytes));
+  if (h->trainer.ready) {
+    // the fine-tune step owns the weights (the layers' own HWIO copies are gone after its first update): the table's matrices
+    // come from its master buffer, here, once per rule change
+    for (size_t li = 0; li < e.layers.size(); ++li)
+      LRP_TRY(e.pack_table_layer((int)li, h->trainer.master.as<float>() + h->trainer.params[2 * li].off, nullptr));
+    LRP_HIP_CHECK(hipStreamSynchronize(nullptr));
+  }
+  return LRP_OK;
+}
+
 int lrp_set_cnn_rule(lrp_handle* h, float alpha, float beta) {
   return with_handle(h, [&]() -> int {
     if (!h) return fail(LRP_ERR_INVALID, "null handle");
@@ -428,32 +458,18 @@ int lrp_set_cnn_rule(lrp_handle* h, float alpha, float beta) {
       return fail(LRP_ERR_INVALID, "alpha - beta should be 1 (alpha=%g, beta=%g)", (double)alpha, (double)beta);
     beta = alpha - 1.f;
     if (h->resnet) return h->rn.set_rule(alpha, beta);    // (refuses beta > 0 on widths that are no multiples of 8)
-    if (h->enc.table_on()) {                             // the one rule replaces a table (lrp_set_cnn_rules)
-      LRP_TRY(h->trainer.drop_early_forward(nullptr));
-      h->enc.clear_table();
-    }
-    if (alpha == h->enc.ab_alpha && beta == h->enc.ab_beta) return LRP_OK;
-    LRP_TRY(h->trainer.drop_early_forward(nullptr));
-    LRP_TRY(h->enc.set_rule(alpha, beta, &h->ws_bytes));
-    if (h->enc.ab_on() && h->trainer.ready) {
-      // the fine-tune step owns the weights (the layers' own HWIO copies are gone after its first update): the rule's matrices
-      // come from its master buffer, here, once per rule change
-      for (size_t li = 0; li < h->enc.layers.size(); ++li)
-        LRP_TRY(h->enc.pack_ab_layer((int)li, h->trainer.master.as<float>() + h->trainer.params[2 * li].off, nullptr));
-      LRP_HIP_CHECK(hipStreamSynchronize(nullptr));
-    }
-    return LRP_OK;
+    Encoder::ConvRule r;                                 // the one rule is a uniform table (with the bias, as RR:274-322 has it)
+    r.alpha = alpha; r.beta = beta;
+    return set_vgg_table(h, std::vector<Encoder::ConvRule>(h->enc.layers.size(), r));
   });
 }
 
 int lrp_set_cnn_rules(lrp_handle* h, const lrp_conv_rule* rules, int32_t n_rules) {
-  std::vector<Encoder::ConvRule> t;
-  bool uniform = true;
-  const int rc = with_handle(h, [&]() -> int {
+  return with_handle(h, [&]() -> int {
     if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "the ResNet encoder's walk has no rule table");
     if (!rules || n_rules != (int)h->enc.layers.size())
       return fail(LRP_ERR_INVALID, "one rule per conv: %d given, %d convs", rules ? n_rules : 0, (int)h->enc.layers.size());
-    t.resize((size_t)n_rules);
+    std::vector<Encoder::ConvRule> t((size_t)n_rules);
     for (int i = 0; i < n_rules; ++i) {
       const lrp_conv_rule& r = rules[i];
       Encoder::ConvRule& o = t[(size_t)i];
@@ -480,31 +496,10 @@ int lrp_set_cnn_rules(lrp_handle* h, const lrp_conv_rule* rules, int32_t n_rules
           return fail(LRP_ERR_INVALID, "bounded rule: low < high (low=%g, high=%g)", (double)r.low, (double)r.high);
         o.low = r.low; o.high = r.high;
       }
-      if (o.kind != LRP_RULE_ALPHA_BETA || !o.bias || o.alpha != t[0].alpha) uniform = false;
     }
-    if (uniform) return LRP_OK;                          // (lrp_set_cnn_rule below)
     if (t[0].input_only() && n_rules < 2) return fail(LRP_ERR_UNSUPPORTED, "an input-layer rule needs a conv above the image layer");
-    Encoder& e = h->enc;
-    if (e.table_on()) {                                  // the same table again changes nothing
-      bool same = true;
-      for (size_t i = 0; i < t.size(); ++i) {
-        const Encoder::ConvRule &a = e.table[i], &b = t[i];
-        if (a.kind != b.kind || a.bias != b.bias || a.alpha != b.alpha || a.eps != b.eps || a.low != b.low || a.high != b.high) same = false;
-      }
-      if (same) return LRP_OK;
-    }
-    LRP_TRY(h->trainer.drop_early_forward(nullptr));
-    LRP_TRY(e.set_rule(1.f, 0.f, &h->ws_bytes));         // (the one-rule walk's buffers stay, idle)
-    LRP_TRY(e.set_table(t, &h->ws_bytes));
-    if (h->trainer.ready) {                              // the fine-tune step owns the weights: see lrp_set_cnn_rule
-      for (size_t li = 0; li < e.layers.size(); ++li)
-        LRP_TRY(e.pack_table_layer((int)li, h->trainer.master.as<float>() + h->trainer.params[2 * li].off, nullptr));
-      LRP_HIP_CHECK(hipStreamSynchronize(nullptr));
-    }
-    return LRP_OK;
+    return set_vgg_table(h, std::move(t));
   });
-  // the same alpha-beta record with bias on every layer IS the one-rule entry: its path, to the bit
-  return rc == LRP_OK && uniform ? lrp_set_cnn_rule(h, t[0].alpha, t[0].beta) : rc;
 }
 
 int lrp_set_fast_layers(lrp_handle* h, int64_t mask) {
@@ -625,48 +620,6 @@ int lrp_op_conv(const float* in_dev, const float* w_hwio_host, const float* bias
   });
 }
 
-int lrp_op_conv_ab(const float* sp_dev, const float* sn_dev, const float* w_hwio_host, float alpha, float beta, const float* gp_dev,
-                   const float* gn_dev, float* outp_dev, float* outn_dev, int32_t NB, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
-                   int32_t pool, int32_t split, void* stream) {
-  return guarded([&]() -> int {
-    if (!sp_dev || !sn_dev || !w_hwio_host || !gp_dev || !gn_dev || !outp_dev || !outn_dev) return fail(LRP_ERR_INVALID, "null argument");
-    if (NB < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return fail(LRP_ERR_INVALID, "NB, H, W, Cin, Cout must be >= 1");
-    const int g = split ? 7 : 3;
-    if ((Cin & g) || (Cout & g)) return fail(LRP_ERR_UNSUPPORTED, "channels must be multiples of %d", g + 1);
-    if ((int64_t)NB * H * W * 2 * Cout >= ((int64_t)1 << 31) || (int64_t)9 * Cin * Cout >= ((int64_t)1 << 31))
-      return fail(LRP_ERR_UNSUPPORTED, "operator entry: tensor too large");
-    hipStream_t st = S(stream);
-    const int CP2 = conv_cinp(2 * Cout), Np = conv_npad(Cin);
-    DevBuf wraw, wab, wabs, sj;
-    LRP_TRY(wraw.alloc((size_t)9 * Cin * Cout * sizeof(float), nullptr));
-    LRP_HIP_CHECK(hipMemcpy(wraw.p, w_hwio_host, wraw.bytes, hipMemcpyHostToDevice));
-    const size_t nb = (size_t)Np * 9 * CP2;
-    LRP_TRY(wab.alloc(nb * sizeof(float), nullptr));
-    LRP_HIP_CHECK(hipMemsetAsync(wab.p, 0, wab.bytes, st));
-    hipLaunchKernelGGL(pack_conv_ab_dev_kernel, dim3(stream_grid((size_t)Cin * 9 * CP2)), dim3(256), 0, st, wraw.as<float>(), wab.as<float>(), 1,
-                       Cin, Cout, CP2, Cin, alpha, beta);
-    const size_t pixels = (size_t)NB * H * W;
-    LRP_TRY(sj.alloc(pixels * 2 * Cout * sizeof(float), nullptr));
-    if (split) {
-      LRP_TRY(wabs.alloc(nb * sizeof(float), nullptr));
-      hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(nb / 8)), dim3(256), 0, st, wab.as<float>(), wabs.as<float>(), nb / 8);
-      hipLaunchKernelGGL(chain_join_kernel<true>, dim3(stream_grid(pixels * (Cout / 8))), dim3(256), 0, st, sp_dev, sn_dev, (const float*)nullptr,
-                         (const float*)nullptr, (const int*)nullptr, sj.as<float>(), pixels, 1, Cout);
-    } else {
-      hipLaunchKernelGGL(chain_join_kernel<false>, dim3(stream_grid(pixels * (Cout / 4))), dim3(256), 0, st, sp_dev, sn_dev, (const float*)nullptr,
-                         (const float*)nullptr, (const int*)nullptr, sj.as<float>(), pixels, 1, Cout);
-    }
-    LRP_HIP_CHECK(hipGetLastError());
-    ConvArgs ca{};
-    ca.in = sj.as<float>(); ca.wpk = split ? wabs.as<float>() : wab.as<float>();
-    ca.NB = NB; ca.H = H; ca.W = W; ca.Cin = 2 * Cout; ca.CinP = CP2; ca.N = Cin; ca.taps = 9;
-    ca.aux = gp_dev; ca.aux_b = gn_dev; ca.out = outp_dev; ca.out_b = outn_dev; ca.ostride = Cin; ca.out_plain = 1;
-    LRP_HIP_CHECK(conv_launch(pool ? EPI_MUL_UP2 : EPI_MUL, ca, st, split ? PREC_BF16X3 : PREC_FP32));
-    LRP_HIP_CHECK(hipStreamSynchronize(st));             // the operand copies are freed on return
-    return LRP_OK;
-  });
-}
-
 int lrp_op_conv_rule(const float* s0_dev, const float* s1_dev, const float* w_hwio_host, int32_t chains_in, int32_t gates_out, float p0,
                      float q0, float p1, float q1, const float* g0_dev, const float* g1_dev, float* out0_dev, float* out1_dev, int32_t NB,
                      int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t pool, int32_t split, void* stream) {
@@ -724,6 +677,14 @@ int lrp_op_conv_rule(const float* s0_dev, const float* s1_dev, const float* w_hw
     LRP_HIP_CHECK(hipStreamSynchronize(st));             // the operand copies are freed on return
     return LRP_OK;
   });
+}
+
+// the two-chain launch of alpha-beta with beta > 0: both chains in, both gates out, [alpha w+ ; -beta w-]
+int lrp_op_conv_ab(const float* sp_dev, const float* sn_dev, const float* w_hwio_host, float alpha, float beta, const float* gp_dev,
+                   const float* gn_dev, float* outp_dev, float* outn_dev, int32_t NB, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                   int32_t pool, int32_t split, void* stream) {
+  return lrp_op_conv_rule(sp_dev, sn_dev, w_hwio_host, 2, 2, alpha, 0.f, 0.f, -beta, gp_dev, gn_dev, outp_dev, outn_dev, NB, H, W, Cin, Cout, pool,
+                          split, stream);
 }
 
 int lrp_op_conv_pool_sparse(const float* sc_dev, const unsigned char* pos_dev, const float* w_hwio_host, const float* gate_dev,

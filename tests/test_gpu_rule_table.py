@@ -138,7 +138,7 @@ def test_walk_with_the_unfused_image_layer_and_behind_the_fast_forward(name, pre
 
 
 # ---------------------------------------------------------------- exact properties
-def test_a_uniform_table_is_the_old_entry_bit_for_bit():
+def test_a_uniform_table_equals_the_one_rule_entry_bit_for_bit():
     w, X, idx, R, _ = K.net("mid")
     fresh = _engine(K.MID_CFG, 32, 2, 4, w)
     ws0 = fresh.workspace_bytes
@@ -156,6 +156,44 @@ def test_a_uniform_table_is_the_old_entry_bit_for_bit():
     assert eng.cnn_rule == (2, 1) and eng.workspace_bytes == old.workspace_bytes
     eng.encode_images(X)
     assert np.array_equal(eng.cnn_explain(list(idx), R).cpu().numpy(), out21)
+
+
+def test_the_two_entries_share_their_buffers():
+    # the one-rule entry is a uniform table: a table with two chains and the bias on every conv needs exactly its buffers
+    w, X, idx, R, layers = K.net("mid")
+    only = _engine(K.MID_CFG, 32, 2, 4, w)
+    only.set_cnn_rule(2, 1)
+    only.encode_images(X)
+    out21 = only.cnn_explain(list(idx), R).cpu().numpy()
+    eng = _engine(K.MID_CFG, 32, 2, 4, w)
+    eng.set_cnn_rule(2, 1)
+    wsA = eng.workspace_bytes
+    assert wsA == only.workspace_bytes
+    table = [("alphabeta", 1.5, 0.5, True)] * 4 + [AB21]
+    eng.set_cnn_rules(table)
+    assert eng.workspace_bytes == wsA
+    eng.encode_images(X)
+    out = eng.cnn_explain(list(idx), R).cpu().numpy()
+    assert np.isfinite(out).all() and not np.array_equal(out, out21)
+    want = RT.analyze(layers, X[list(idx)], R, table)
+    errs = [rel_l1(out[i], want[i]) for i in range(len(R))]
+    print("two-chain table on mid: rel_l1 per map %s" % " ".join("%.3e" % e for e in errs))
+    assert max(errs) < 1e-4, errs
+    eng.set_cnn_rule(2, 1)
+    assert eng.workspace_bytes == wsA
+    eng.encode_images(X)
+    assert np.array_equal(eng.cnn_explain(list(idx), R).cpu().numpy(), out21)
+
+
+def test_the_same_rule_again_drops_nothing_through_either_entry():
+    w, X, idx, R, _ = K.net("mid")
+    eng = _engine(K.MID_CFG, 32, 2, 4, w)
+    eng.set_cnn_rule(2, 1)
+    eng.encode_images(X)
+    before = eng.cnn_explain(list(idx), R).cpu().numpy()
+    eng.set_cnn_rule(2, 1)
+    eng.set_cnn_rules([AB21] * 5)
+    assert np.array_equal(eng.cnn_explain(list(idx), R).cpu().numpy(), before)          # (LRP_ERR_STATE had the caches been dropped)
 
 
 def test_round_trip_state_and_workspace():
