@@ -7,11 +7,18 @@
 // This path runs in exact fp32 (PREC_FP32) throughout.
 //   explain_ab(): the same walk under the alpha-beta rule with beta > 0 (set_rule): two relevance chains per tensor, the second
 //              gate of every unit and block made at encode time behind the unchanged forward (oracle: tests/resnet_ab_ref.py).
-//   explain_grad(): the gradient baselines (Gradient / InputTimesGradient / GuidedBackprop) in LRP_PREC_FP32 mode: the same
-//              convT launches with BN-scaled full-sign weights (w_g, packed on the first such walk) and the ReLU decisions
-//              the fp32 forward recorded as byte masks (RnUnit::mask, RnBlock::omask).
-//   explain_deconvnet(): Deconvnet, the guided-backprop walk without any mask (a clamp at every Activation, no ReLU decision
-//              read; the stem pool by pool_win): every precision mode.
+//   explain_grad(): the gradient family, one walk driven by a GradMode.  Gradient / InputTimesGradient / GuidedBackprop in
+//              LRP_PREC_FP32 mode: the same convT launches with BN-scaled full-sign weights (w_g, packed on the first such walk)
+//              and the ReLU decisions the fp32 forward recorded as byte masks (RnUnit::mask, RnBlock::omask).  Deconvnet: the
+//              guided walk without any mask (a clamp at every Activation, no ReLU decision read; the stem pool by pool_win),
+//              every precision mode.
+// What the paths share, each written once:
+//   encode() = the common part + encode_emit() (fp16 pairs between the convs) or encode_fp32_acts() (fp32 activations between
+//              them); both start with stem_forward() and build a unit's launch from fwd_args(), bn_epilogue() and
+//              launch_inh_dual()
+//   bwd_args(): the transposed conv through a unit over one or two chains (unit_backward, explain_ab, grad_backward)
+//   stem_reverse(): the tap GEMM + stencil, or the fused kernel where it applies, behind all three walks
+//   reserve() / split_copy(): the buffers and split8 copies of the packers (pack_unit_dev, set_rule, ensure_*_weights)
 #pragma once
 #include <algorithm>
 #include <string>
@@ -68,6 +75,11 @@ struct ResNetEncoder {
   std::vector<RnUnit> units;       // units[0] = stem
   std::vector<RnBlock> blocks;
   DevBuf images, stemA, a0;        // image copy, stem im2col, stem activation [B][H/2][W/2][stem]
+  // the stem's routing needs Q alone: what arrives at a0 = relu(y) through the pool is already a relevance
+  // (t * C1 of the first block), so multiplying by the relu-unit gate a0*Q would count a0 twice
+  DevBuf q_stem;
+  DevBuf pool_win;                 // winner of every 3x3/2 pool window (one byte)
+  const void* stem_attr_set[4] = {};   // the rn_stem_reverse_kernel instantiations whose LDS attribute is set (stem_lds_attr)
   DevBuf fa, fb, fc, fz, fsc;      // forward scratch
   DevBuf fxs;                      // a unit's input as scaled fp16 pairs (fp16-pair forward)
   DevBuf f16_slots;                // scratch maxima of make_f16_operand
@@ -129,7 +141,7 @@ struct ResNetEncoder {
     LRP_TRY(stemA.alloc(B * stem_hw * 2 * RN_STEM_K * 4, total));
     LRP_TRY(a0.alloc(B * stem_hw * stem_c * 4, total));
     LRP_TRY(q_stem.alloc(B * stem_hw * stem_c * 4, total));
-    LRP_TRY(pool_win.alloc(B * (stem_hw / 4) * stem_c, total));      // winner of every 3x3/2 pool window (one byte)
+    LRP_TRY(pool_win.alloc(B * (stem_hw / 4) * stem_c, total));
     for (DevBuf* d : {&fa, &fb, &fc, &fz, &fsc, &fxs}) LRP_TRY(d->alloc(B * max_act * 4, total));
     LRP_TRY(act_max.alloc((units.size() + blocks.size()) * ACT_MAX_SLOTS * sizeof(unsigned), total));
     LRP_TRY(act_unscale.alloc(units.size() * sizeof(float), total));
@@ -193,7 +205,7 @@ struct ResNetEncoder {
         if (!ev_pack) LRP_HIP_CHECK(hipEventCreateWithFlags(&ev_pack, hipEventDisableTiming));
         else LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_pack, 0));          // the previous unit's packers still read the staging pair
         LRP_HIP_CHECK(hipMemcpyAsync(raw_tmp.p, data, nW * 4, kind, st));
-        LRP_TRY(pack_unit_dev(u, raw_tmp.as<float>(), total, st));
+        LRP_TRY(pack_unit_dev(u, raw_tmp.as<float>(), st));
         LRP_HIP_CHECK(hipEventRecord(ev_pack, st));
       } else {
         if (ndim != 1 || shape[0] != u.cout) return fail(LRP_ERR_INVALID, "%s: expected (%d,)", nm.c_str(), u.cout);
@@ -210,22 +222,28 @@ struct ResNetEncoder {
     }
     return 1;
   }
-  int pack_unit_dev(RnUnit& u, const float* w_dev, int64_t* total, hipStream_t st) {
-    auto mk = [&](DevBuf& d, size_t floats) -> int {
-      if (d.p && d.bytes == floats * 4) return LRP_OK;
-      return d.alloc(floats * 4, total);
-    };
-    auto split = [&](const float* src, float* dst, size_t n) {
-      hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n / 8)), dim3(256), 0, st, src, dst, n / 8);
-    };
+  // `d` holds at least `floats` floats afterwards: allocated at its first use, grown (the handle's workspace counter corrected
+  // for the buffer that goes) where a later caller needs more — the walk's scratch under the first two-chain rule — and left
+  // alone otherwise.  A unit's matrices depend on its geometry alone, so for them "at least" and "exactly" are the same test:
+  // they are allocated once, and a weight set again finds them.
+  int reserve(DevBuf& d, size_t floats) {
+    if (d.p && d.bytes >= floats * sizeof(float)) return LRP_OK;
+    if (d.p && ws_total) *ws_total -= (int64_t)d.bytes;
+    return d.alloc(floats * sizeof(float), ws_total);
+  }
+  // dst = the split8 form (bf16x3 operand) of the n floats at src
+  void split_copy(const float* src, float* dst, size_t n, hipStream_t st) {
+    hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n / 8)), dim3(256), 0, st, src, dst, n / 8);
+  }
+  int pack_unit_dev(RnUnit& u, const float* w_dev, hipStream_t st) {
     if (u.k == 7) {
       const int Np = conv_npad(u.cout), K = 2 * RN_STEM_K, Npb = conv_npad(RN_STEM_TCOLS), Kb = conv_cinp(u.cout);
-      LRP_TRY(mk(u.w_a, (size_t)Np * K)); LRP_TRY(mk(u.w_z, (size_t)Np * K)); LRP_TRY(mk(u.w_b, (size_t)Npb * Kb));
+      LRP_TRY(reserve(u.w_a, (size_t)Np * K)); LRP_TRY(reserve(u.w_z, (size_t)Np * K)); LRP_TRY(reserve(u.w_b, (size_t)Npb * Kb));
       hipLaunchKernelGGL(rn_pack_stem_dev_kernel, dim3(stream_grid((size_t)Np * K + (size_t)Npb * Kb)), dim3(256), 0, st, w_dev,
                          u.w_a.as<float>(), u.w_z.as<float>(), u.w_b.as<float>(), u.cout, Np, Npb, Kb);
       if (!(u.cout & 7)) {
-        LRP_TRY(mk(u.w_bs, (size_t)Npb * Kb));
-        split(u.w_b.as<float>(), u.w_bs.as<float>(), (size_t)Npb * Kb);
+        LRP_TRY(reserve(u.w_bs, (size_t)Npb * Kb));
+        split_copy(u.w_b.as<float>(), u.w_bs.as<float>(), (size_t)Npb * Kb, st);
       }
       LRP_HIP_CHECK(hipGetLastError());
       return LRP_OK;
@@ -238,13 +256,13 @@ struct ResNetEncoder {
       hipLaunchKernelGGL(pack_conv_dev_kernel, dim3(stream_grid(tot)), dim3(256), 0, st, w_dev, dst, bwd, u.cin, u.cout, bwd ? CPo : CPi,
                          rows, dual, pos, taps);
     };
-    LRP_TRY(mk(u.w_a, nf)); LRP_TRY(mk(u.w_z, nf));
+    LRP_TRY(reserve(u.w_a, nf)); LRP_TRY(reserve(u.w_z, nf));
     pack(u.w_a.as<float>(), 0, Np, 0, 0);
     pack(u.w_z.as<float>(), 0, Np, 0, 1);                // inputs are post-ReLU: Z = conv(x, w+) + b
     if (!(u.cout & 3)) {
       const int Nd = conv_npad(2 * u.cout);
       const size_t nd = (size_t)Nd * taps * CPi;
-      LRP_TRY(mk(u.w_dual, nd));
+      LRP_TRY(reserve(u.w_dual, nd));
       pack(u.w_dual.as<float>(), 0, Nd, 1, 0);
       if (!(u.cin & 7)) {
         u.dual_il = !(u.cout & 31) && Nd == 2 * u.cout;
@@ -253,12 +271,12 @@ struct ResNetEncoder {
           pack(pack_tmp.as<float>(), 0, Nd, 2, 0);
           src = pack_tmp.as<float>();
         }
-        LRP_TRY(make_f16_operand(f16_slots, src, nd, 0, 0, u.w_dual_h, u.wds, total, st));
+        LRP_TRY(make_f16_operand(f16_slots, src, nd, 0, 0, u.w_dual_h, u.wds, ws_total, st));
       }
     }
-    LRP_TRY(mk(u.w_b, nb)); LRP_TRY(mk(u.w_bs, nb));
+    LRP_TRY(reserve(u.w_b, nb)); LRP_TRY(reserve(u.w_bs, nb));
     pack(u.w_b.as<float>(), 1, Npb, 0, 1);
-    split(u.w_b.as<float>(), u.w_bs.as<float>(), nb);
+    split_copy(u.w_b.as<float>(), u.w_bs.as<float>(), nb, st);
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   }
@@ -283,38 +301,33 @@ struct ResNetEncoder {
     if (beta > 0.f) {
       if (!ab_supported())
         return fail(LRP_ERR_UNSUPPORTED, "alpha-beta with beta > 0 on a ResNet encoder needs a stem width and stack widths that are multiples of 8");
-      auto mk = [&](DevBuf& d, size_t floats) -> int {   // appears, or grows, with the first rule that needs it
-        if (d.p && d.bytes >= floats * sizeof(float)) return LRP_OK;
-        if (d.p && ws_total) *ws_total -= (int64_t)d.bytes;
-        return d.alloc(floats * sizeof(float), ws_total);
-      };
-      const size_t B = max_images, NT = max_tokens;
+      const size_t B = max_images, NT = max_tokens;      // (every buffer below appears, or grows, with the first rule that needs it)
       for (RnUnit& u : units) {
         if (u.k == 7) {                                  // (the stem's second gate is q_stem_i)
-          LRP_TRY(mk(u.w_n, (size_t)conv_npad(u.cout) * 2 * RN_STEM_K));
+          LRP_TRY(reserve(u.w_n, (size_t)conv_npad(u.cout) * 2 * RN_STEM_K));
           const size_t nb = (size_t)conv_npad(RN_STEM_TCOLS) * conv_cinp(2 * u.cout);
-          LRP_TRY(mk(u.w_ab, nb)); LRP_TRY(mk(u.w_abs, nb));
+          LRP_TRY(reserve(u.w_ab, nb)); LRP_TRY(reserve(u.w_abs, nb));
           continue;
         }
         const int taps = u.k * u.k;
-        LRP_TRY(mk(u.gate_i, B * u.out_elems()));
-        LRP_TRY(mk(u.w_n, (size_t)conv_npad(u.cout) * taps * conv_cinp(u.cin)));
-        if (u.dual_il && u.w_dual_h.p) LRP_TRY(mk(u.w_dualn_h, (size_t)conv_npad(2 * u.cout) * taps * conv_cinp(u.cin)));
+        LRP_TRY(reserve(u.gate_i, B * u.out_elems()));
+        LRP_TRY(reserve(u.w_n, (size_t)conv_npad(u.cout) * taps * conv_cinp(u.cin)));
+        if (u.dual_il && u.w_dual_h.p) LRP_TRY(reserve(u.w_dualn_h, (size_t)conv_npad(2 * u.cout) * taps * conv_cinp(u.cin)));
         const size_t nb = (size_t)conv_npad(u.cin) * taps * conv_cinp(2 * u.cout);
-        LRP_TRY(mk(u.w_ab, nb)); LRP_TRY(mk(u.w_abs, nb));
+        LRP_TRY(reserve(u.w_ab, nb)); LRP_TRY(reserve(u.w_abs, nb));
       }
       for (RnBlock& b : blocks) {
         const size_t ne = B * (size_t)b.H * b.W * 4 * b.f;
-        LRP_TRY(mk(b.GA_i, ne));
-        if (b.u0 >= 0) LRP_TRY(mk(b.GS_i, ne));
+        LRP_TRY(reserve(b.GA_i, ne));
+        if (b.u0 >= 0) LRP_TRY(reserve(b.GS_i, ne));
       }
       const size_t stem_hw = (size_t)(img_h / 2) * (img_w / 2);
-      LRP_TRY(mk(q_stem_i, B * stem_hw * stem_c));
+      LRP_TRY(reserve(q_stem_i, B * stem_hw * stem_c));
       // the per-token scratch of the tensors that carry two chains (S3 / S0, S2, S1, the pool routing's output)
       size_t max_act = stem_hw * stem_c;
       for (const RnUnit& u : units) max_act = std::max(max_act, std::max(u.out_elems(), u.in_elems()));
       const size_t tok2 = std::max(2 * max_act, stem_hw * (size_t)RN_STEM_TCOLS);
-      for (DevBuf* d : {&r1, &r2, &r3, &r5}) LRP_TRY(mk(*d, NT * tok2));
+      for (DevBuf* d : {&r1, &r2, &r3, &r5}) LRP_TRY(reserve(*d, NT * tok2));
     }
     // (beta = 0 again: the buffers stay, idle)
     ab_alpha = alpha; ab_beta = beta;
@@ -324,20 +337,17 @@ struct ResNetEncoder {
   }
   // the rule's matrices of every unit whose weights or rule changed since its last packing, from the resident forward matrix w_a
   int ensure_ab_weights(hipStream_t st) {
-    auto split = [&](const float* src, float* dst, size_t n) {
-      hipLaunchKernelGGL(split_copy_kernel, dim3(stream_grid(n / 8)), dim3(256), 0, st, src, dst, n / 8);
-    };
     for (RnUnit& u : units) {
       if (u.ab_packed) continue;
       // a weight set after the rule may have changed which forward path the unit takes
-      if (u.k != 7 && u.dual_il && u.w_dual_h.p && !u.w_dualn_h.p)
-        LRP_TRY(u.w_dualn_h.alloc((size_t)conv_npad(2 * u.cout) * u.k * u.k * conv_cinp(u.cin) * 4, ws_total));
+      if (u.k != 7 && u.dual_il && u.w_dual_h.p)
+        LRP_TRY(reserve(u.w_dualn_h, (size_t)conv_npad(2 * u.cout) * u.k * u.k * conv_cinp(u.cin)));
       if (u.k == 7) {
         const int Np = conv_npad(u.cout), Npb = conv_npad(RN_STEM_TCOLS), Kb2 = conv_cinp(2 * u.cout);
         const size_t nf = (size_t)Np * 2 * RN_STEM_K, nb = (size_t)Npb * Kb2;
         hipLaunchKernelGGL(rn_pack_stem_ab_kernel, dim3(stream_grid(nf + nb)), dim3(256), 0, st, u.w_a.as<float>(), u.w_n.as<float>(),
                            u.w_ab.as<float>(), u.cout, Np, Npb, Kb2, ab_alpha, ab_beta);
-        split(u.w_ab.as<float>(), u.w_abs.as<float>(), nb);
+        split_copy(u.w_ab.as<float>(), u.w_abs.as<float>(), nb, st);
       } else {
         const int taps = u.k * u.k, CPi = conv_cinp(u.cin), CP2 = conv_cinp(2 * u.cout), rows = conv_npad(u.cin);
         const size_t nf = (size_t)conv_npad(u.cout) * taps * CPi, nb = (size_t)rows * taps * CP2;
@@ -349,7 +359,7 @@ struct ResNetEncoder {
         }
         hipLaunchKernelGGL(rn_pack_ab_kernel, dim3(stream_grid(nb)), dim3(256), 0, st, u.w_a.as<float>(), u.w_ab.as<float>(), taps, u.cin,
                            u.cout, CPi, CP2, rows, ab_alpha, ab_beta);
-        split(u.w_ab.as<float>(), u.w_abs.as<float>(), nb);
+        split_copy(u.w_ab.as<float>(), u.w_abs.as<float>(), nb, st);
       }
       LRP_HIP_CHECK(hipGetLastError());
       u.ab_packed = true;
@@ -386,6 +396,31 @@ struct ResNetEncoder {
   unsigned* unit_slots(int ui) { return act_max.as<unsigned>() + (size_t)ui * ACT_MAX_SLOTS; }
   unsigned* block_slots(size_t bi) { return act_max.as<unsigned>() + (units.size() + bi) * ACT_MAX_SLOTS; }
 
+  // a unit's forward conv over x on fp32 operands and the unit's own weights: geometry (3x3: the image grid; 1x1: one row per
+  // output pixel), bias, Cin / CinP.  The callers add the matrix, the outputs and what their operand format needs
+  ConvArgs fwd_args(const RnUnit& u, const float* x, int B) const {
+    ConvArgs ca{};
+    ca.in = x; ca.bias = u.bias.as<float>(); ca.N = u.cout; ca.Cin = u.cin; ca.CinP = conv_cinp(u.cin);
+    if (u.k == 3) { ca.NB = B; ca.H = u.Hout; ca.W = u.Wout; ca.taps = 9; }
+    else { ca.NB = B * u.Hout * u.Wout; ca.H = 1; ca.W = 1; ca.taps = 1; }
+    return ca;
+  }
+  // BatchNorm, ReLU and the unit's gate in the epilogue of a dual_il unit's conv: c and Z+ never go to memory (conv_args.h
+  // ConvArgs::dual_gate = 2); act = relu(BN) or BN (nullptr with skip_out), the gate into u.gate
+  static void bn_epilogue(ConvArgs& ca, const RnUnit& u, float* act) {
+    ca.dual_il = 1; ca.dual_gate = 2; ca.bn_gamma = u.gamma.as<float>(); ca.bn_beta = u.beta.as<float>();
+    ca.bn_mean = u.mean.as<float>(); ca.bn_var = u.var.as<float>(); ca.bn_eps = RN_BN_EPS; ca.bn_relu = u.relu ? 1 : 0;
+    ca.out = act; ca.out2 = u.gate.as<float>();
+  }
+  // the inhibitor gate of a dual_il unit (beta > 0): the launch `ca` has just made again, [w | w-] in place of [w | w+] — same
+  // operands, scales and epilogue — writing the gate alone: no activation, no pairs, no maxima
+  int launch_inh_dual(const RnUnit& u, ConvArgs& ca, hipStream_t st) {
+    ca.wpk = u.w_dualn_h.as<float>(); ca.out2 = u.gate_i.as<float>(); ca.skip_out = 1;
+    ca.pairs_out = nullptr; ca.pairs_scale = nullptr; ca.act_max_out = nullptr;
+    LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, ca, st, PREC_F16X2));
+    return LRP_OK;
+  }
+
   // conv + BN unit forward: x [B][Hin][Win][cin] -> act (relu(BN) or BN) and the unit's gate.
   // slots_in: maxima of x (fp16-pair forward: the power of two x is scaled by); slots_out: where max|act| is collected
   // (nullptr: nobody convolves this output)
@@ -398,11 +433,7 @@ struct ResNetEncoder {
       LRP_HIP_CHECK(hipGetLastError());
       xin = fsc.as<float>();
     }
-    ConvArgs ca{};
-    ca.in = xin; ca.bias = u.bias.as<float>(); ca.N = u.cout;
-    if (u.k == 3) { ca.NB = B; ca.H = u.Hout; ca.W = u.Wout; ca.Cin = u.cin; ca.CinP = conv_cinp(u.cin); ca.taps = 9; }
-    else { ca.NB = B * u.Hout * u.Wout; ca.H = 1; ca.W = 1; ca.Cin = u.cin; ca.CinP = conv_cinp(u.cin); ca.taps = 1; }
-    ConvArgs cz = ca;
+    ConvArgs ca = fwd_args(u, xin, B);
     const int ui = (int)(&u - units.data());
     if (u.w_dual_h.p && slots_in && prec == PREC_BF16X3) {
       // the same single pass on the fp16 MFMA: x and (w | w+) as fp16 pairs, the product in three MFMAs with blocked
@@ -414,15 +445,10 @@ struct ResNetEncoder {
       ca.in = fxs.as<float>(); ca.wpk = u.w_dual_h.as<float>(); ca.N = 2 * u.cout; ca.split = u.cout; ca.dual_norelu = 1;
       ca.out = fc.as<float>(); ca.out2 = fz.as<float>(); ca.in_unscale = act_unscale.as<float>() + ui;
       if (u.dual_il) {
-        // BatchNorm, ReLU and the unit's gate in the conv's epilogue: c and Z+ never go to memory (conv_args.h ConvArgs::dual_gate = 2)
-        ca.dual_il = 1; ca.dual_gate = 2; ca.bn_gamma = u.gamma.as<float>(); ca.bn_beta = u.beta.as<float>();
-        ca.bn_mean = u.mean.as<float>(); ca.bn_var = u.var.as<float>(); ca.bn_eps = RN_BN_EPS; ca.bn_relu = u.relu ? 1 : 0;
-        ca.out = act; ca.out2 = u.gate.as<float>(); ca.act_max_out = slots_out;
+        bn_epilogue(ca, u, act);
+        ca.act_max_out = slots_out;
         LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, ca, st, PREC_F16X2));
-        if (ab_on()) {                                   // the same launch against [w | w-]: the inhibitor gate, nothing else written
-          ca.wpk = u.w_dualn_h.as<float>(); ca.out2 = u.gate_i.as<float>(); ca.skip_out = 1; ca.act_max_out = nullptr;
-          LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, ca, st, PREC_F16X2));
-        }
+        if (ab_on()) LRP_TRY(launch_inh_dual(u, ca, st));
         return LRP_OK;
       }
       LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, ca, st, PREC_F16X2));
@@ -434,15 +460,15 @@ struct ResNetEncoder {
     } else {
       ca.wpk = u.w_a.as<float>(); ca.out = fc.as<float>();
       LRP_HIP_CHECK(conv_launch(EPI_BIAS, ca, st));
-      cz.wpk = u.w_z.as<float>(); cz.out = fz.as<float>();
-      LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, st));
+      ca.wpk = u.w_z.as<float>(); ca.out = fz.as<float>();
+      LRP_HIP_CHECK(conv_launch(EPI_BIAS, ca, st));
     }
     const size_t n = (size_t)B * u.out_elems();
     hipLaunchKernelGGL(rn_bn_unit_kernel, dim3(stream_grid(n)), dim3(256), 0, st, fc.as<float>(), fz.as<float>(),
                        u.gamma.as<float>(), u.beta.as<float>(), u.mean.as<float>(), u.var.as<float>(), RN_BN_EPS, act,
                        u.gate.as<float>(), (float*)nullptr, n, u.cout, u.relu ? 1 : 0, slots_out, mask);
     LRP_HIP_CHECK(hipGetLastError());
-    if (ab_on()) LRP_TRY(unit_gate_inh(u, cz, fc.as<float>(), u.gate_i.as<float>(), B, u.relu ? 1 : 0, st));
+    if (ab_on()) LRP_TRY(unit_gate_inh(u, fwd_args(u, xin, B), fc.as<float>(), u.gate_i.as<float>(), B, u.relu ? 1 : 0, st));
     return LRP_OK;
   }
 
@@ -480,26 +506,32 @@ struct ResNetEncoder {
   // (pairs_out: relu units inside a block; fp32 activation not written) OR the fp32 pre-Add tensor `act`
   int unit_forward_emit(RnUnit& u, const float* xpairs, int B, float* act, float* pairs_out, hipStream_t st) {
     const int ui = (int)(&u - units.data());
-    ConvArgs ca{};
-    ca.in = xpairs; ca.bias = u.bias.as<float>();
-    if (u.k == 3) { ca.NB = B; ca.H = u.Hout; ca.W = u.Wout; ca.taps = 9; }
-    else { ca.NB = B * u.Hout * u.Wout; ca.H = 1; ca.W = 1; ca.taps = 1; }
-    ca.Cin = u.cin; ca.CinP = conv_cinp(u.cin);
+    ConvArgs ca = fwd_args(u, xpairs, B);
     ca.wpk = u.w_dual_h.as<float>(); ca.N = 2 * u.cout; ca.split = u.cout; ca.dual_norelu = 1;
     ca.in_unscale = eunscale_unit(ui);
-    ca.dual_il = 1; ca.dual_gate = 2; ca.bn_gamma = u.gamma.as<float>(); ca.bn_beta = u.beta.as<float>();
-    ca.bn_mean = u.mean.as<float>(); ca.bn_var = u.var.as<float>(); ca.bn_eps = RN_BN_EPS; ca.bn_relu = u.relu ? 1 : 0;
-    ca.out = act; ca.out2 = u.gate.as<float>();
+    bn_epilogue(ca, u, act);
     ca.act_max_out = pairs_out ? (unsigned*)nullptr : eslots_unit(ui);      // measured maxima: the block end's two summands only
     ca.scale_per_img = 1; ca.img_rows = u.Hout * u.Wout; ca.n_imgs = B;
     if (pairs_out) { ca.pairs_out = pairs_out; ca.pairs_scale = eoscale_unit(ui); ca.skip_out = 1; }
     LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, ca, st, PREC_F16X2));
-    if (ab_on()) {
-      // the unit's own launch again, [w | w-] in place of [w | w+]: same operands, scales and epilogue, the gate only
-      ca.wpk = u.w_dualn_h.as<float>(); ca.out2 = u.gate_i.as<float>(); ca.skip_out = 1;
-      ca.pairs_out = nullptr; ca.pairs_scale = nullptr; ca.act_max_out = nullptr;
-      LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, ca, st, PREC_F16X2));
-    }
+    if (ab_on()) LRP_TRY(launch_inh_dual(u, ca, st));
+    return LRP_OK;
+  }
+  // the stem's forward up to its BatchNorm, for both paths: im2col -> two 1-tap GEMMs on the fp32 MFMA, c (exact) into fa and Z
+  // (both sign branches) into fz.  cz: the Z launch, which unit_gate_inh runs once more against w_n under beta > 0
+  int stem_forward(int B, ConvArgs& cz, hipStream_t st) {
+    const RnUnit& s = units[0];
+    const size_t tot = (size_t)B * s.Hout * s.Wout * 2 * RN_STEM_K;
+    hipLaunchKernelGGL(rn_stem_im2col_kernel, dim3(stream_grid(tot)), dim3(256), 0, st, images.as<float>(),
+                       stemA.as<float>(), B, img_h, img_w);
+    LRP_HIP_CHECK(hipGetLastError());
+    cz = ConvArgs{};
+    cz.in = stemA.as<float>(); cz.NB = B * s.Hout * s.Wout; cz.H = 1; cz.W = 1; cz.Cin = 2 * RN_STEM_K; cz.CinP = 2 * RN_STEM_K;
+    cz.taps = 1; cz.N = s.cout; cz.bias = s.bias.as<float>();
+    cz.wpk = s.w_a.as<float>(); cz.out = fa.as<float>();
+    LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, st));
+    cz.wpk = s.w_z.as<float>(); cz.out = fz.as<float>();
+    LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, st));
     return LRP_OK;
   }
   int encode_emit(int B, hipStream_t st) {
@@ -520,18 +552,8 @@ struct ResNetEncoder {
     float* tp = fc.as<float>();                          // the block input as pairs (fc / fsc alternate)
     float* tp_other = fsc.as<float>();
     {  // stem: im2col -> two 1-tap GEMMs (fp32 MFMA) -> BN + relu + gate -> pool (+ pairs of the first block's input)
-      const size_t tot = (size_t)B * s.Hout * s.Wout * 2 * RN_STEM_K;
-      hipLaunchKernelGGL(rn_stem_im2col_kernel, dim3(stream_grid(tot)), dim3(256), 0, st, images.as<float>(),
-                         stemA.as<float>(), B, img_h, img_w);
-      LRP_HIP_CHECK(hipGetLastError());
-      ConvArgs ca{};
-      ca.in = stemA.as<float>(); ca.NB = B * s.Hout * s.Wout; ca.H = 1; ca.W = 1; ca.Cin = 2 * RN_STEM_K; ca.CinP = 2 * RN_STEM_K;
-      ca.taps = 1; ca.N = s.cout; ca.bias = s.bias.as<float>();
-      ConvArgs cz = ca;
-      ca.wpk = s.w_a.as<float>(); ca.out = fa.as<float>();
-      LRP_HIP_CHECK(conv_launch(EPI_BIAS, ca, st));
-      cz.wpk = s.w_z.as<float>(); cz.out = fz.as<float>();
-      LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, st));
+      ConvArgs cz;
+      LRP_TRY(stem_forward(B, cz, st));
       const size_t per = s.out_elems();
       hipLaunchKernelGGL(rn_bn_unit_img_kernel, img_grid(per, B), dim3(256), 0, st, fa.as<float>(), fz.as<float>(),
                          s.gamma.as<float>(), s.beta.as<float>(), s.mean.as<float>(), s.var.as<float>(), RN_BN_EPS,
@@ -595,35 +617,27 @@ struct ResNetEncoder {
     if (B < 1 || B > max_images) return fail(LRP_ERR_INVALID, "B=%d outside [1,%d]", B, max_images);
     LRP_TRY(check_ready());
     if (ab_on()) LRP_TRY(ensure_ab_weights(st));
-    masks_ok = false;
-    if (emit_ok()) {
-      LRP_HIP_CHECK(hipMemcpyAsync(images.p, images_dev, (size_t)B * img_h * img_w * 3 * 4, hipMemcpyDeviceToDevice, st));
-      LRP_TRY(encode_emit(B, st));
-      encoded = B;
-      features_only = false;
-      return LRP_OK;
-    }
     LRP_HIP_CHECK(hipMemcpyAsync(images.p, images_dev, (size_t)B * img_h * img_w * 3 * 4, hipMemcpyDeviceToDevice, st));
+    masks_ok = false;
+    if (emit_ok()) LRP_TRY(encode_emit(B, st));
+    else LRP_TRY(encode_fp32_acts(B, st));               // (sets masks_ok in LRP_PREC_FP32 mode)
+    encoded = B;
+    features_only = false;
+    return LRP_OK;
+  }
+  // the forward with an fp32 activation between every two convs: exact fp32 (LRP_PREC_FP32, widths that are no multiples of 8)
+  // or fp16 pairs made per unit from that activation (bf16x3 with LRP_FWD_EMIT=0, or a unit that emit_ok refuses)
+  int encode_fp32_acts(int B, hipStream_t st) {
     LRP_HIP_CHECK(hipMemsetAsync(act_max.p, 0, act_max.bytes, st));
     const bool rec = prec == PREC_FP32;                  // record the ReLU masks (the gradient walks exist in this mode only)
     if (rec) LRP_TRY(alloc_masks());
     auto mask_of = [&](RnUnit& u) { return rec ? u.mask.as<unsigned char>() : (unsigned char*)nullptr; };
     RnUnit& s = units[0];
-    {  // stem: im2col -> two 1-tap GEMMs (c exact / Z with both sign branches) -> BN + relu + gate
-      const size_t tot = (size_t)B * s.Hout * s.Wout * 2 * RN_STEM_K;
-      hipLaunchKernelGGL(rn_stem_im2col_kernel, dim3(stream_grid(tot)), dim3(256), 0, st, images.as<float>(),
-                         stemA.as<float>(), B, img_h, img_w);
-      LRP_HIP_CHECK(hipGetLastError());
-      ConvArgs ca{};
-      ca.in = stemA.as<float>(); ca.NB = B * s.Hout * s.Wout; ca.H = 1; ca.W = 1; ca.Cin = 2 * RN_STEM_K; ca.CinP = 2 * RN_STEM_K;
-      ca.taps = 1; ca.N = s.cout; ca.bias = s.bias.as<float>();
-      ConvArgs cz = ca;
-      ca.wpk = s.w_a.as<float>(); ca.out = fc.as<float>();
-      LRP_HIP_CHECK(conv_launch(EPI_BIAS, ca, st));
-      cz.wpk = s.w_z.as<float>(); cz.out = fz.as<float>();
-      LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, st));
+    {  // stem: im2col -> two 1-tap GEMMs (c exact / Z with both sign branches) -> BN + relu + gate (fa is free until block 0's unit 1)
+      ConvArgs cz;
+      LRP_TRY(stem_forward(B, cz, st));
       const size_t n = (size_t)B * s.out_elems();
-      hipLaunchKernelGGL(rn_bn_unit_kernel, dim3(stream_grid(n)), dim3(256), 0, st, fc.as<float>(), fz.as<float>(),
+      hipLaunchKernelGGL(rn_bn_unit_kernel, dim3(stream_grid(n)), dim3(256), 0, st, fa.as<float>(), fz.as<float>(),
                          s.gamma.as<float>(), s.beta.as<float>(), s.mean.as<float>(), s.var.as<float>(), RN_BN_EPS,
                          a0.as<float>(), s.gate.as<float>(), q_stem.as<float>(), n, s.cout, 1, unit_slots(0), (unsigned char*)nullptr);
       LRP_HIP_CHECK(hipGetLastError());
@@ -631,7 +645,7 @@ struct ResNetEncoder {
       hipLaunchKernelGGL(rn_pool3_kernel, dim3(stream_grid(np)), dim3(256), 0, st, a0.as<float>(), blocks[0].t_in.as<float>(),
                          pool_win.as<unsigned char>(), B, s.Hout, s.Wout, s.cout);
       LRP_HIP_CHECK(hipGetLastError());
-      if (ab_on()) LRP_TRY(unit_gate_inh(s, cz, fc.as<float>(), q_stem_i.as<float>(), B, 0, st));
+      if (ab_on()) LRP_TRY(unit_gate_inh(s, cz, fa.as<float>(), q_stem_i.as<float>(), B, 0, st));
     }
     for (size_t bi = 0; bi < blocks.size(); ++bi) {
       RnBlock& b = blocks[bi];
@@ -663,11 +677,20 @@ struct ResNetEncoder {
       LRP_HIP_CHECK(hipGetLastError());
       if (ab_on()) LRP_TRY(block_gates_inh(b, sc, fa.as<float>(), B, st));
     }
-    encoded = B;
-    features_only = false;
     masks_ok = rec;
     return LRP_OK;
   }
+
+  // the transposed conv through unit u, every walk's: S [n][Hout][Wout][chains * cout] -> out [n][Hout][Wout][cin].  The callers
+  // add the matrix (w_b / w_bs, w_ab / w_abs over two chains, w_g), the gates and the epilogue
+  static ConvArgs bwd_args(const RnUnit& u, int n, const int* row2img, const float* S, float* out, int chains = 1) {
+    ConvArgs ca{};
+    ca.in = S; ca.row2img = row2img; ca.out = out; ca.N = u.cin;
+    ca.Cin = chains * u.cout; ca.CinP = conv_cinp(chains * u.cout); ca.NB = n; ca.H = u.Hout; ca.W = u.Wout; ca.taps = u.k == 3 ? 9 : 1;
+    return ca;
+  }
+  // what the profiler books on it per chain: 2 n H W k^2 cout cin
+  static double bwd_flop(const RnUnit& u, int n) { return 2.0 * n * u.Hout * u.Wout * (double)(u.k == 3 ? 9 : 1) * u.cout * u.cin; }
 
   // conv-LRP step through one unit: S [n][Hout][Wout][cout] -> out [n][Hout'][..][cin] = convT(S, w+) * aux[img]
   // split: S is in split8 form and the conv runs as bf16x3; plain_out: the result feeds an element-wise kernel (fp32)
@@ -677,14 +700,12 @@ struct ResNetEncoder {
   };
   int unit_backward(const RnUnit& u, int n, const int* row2img, const float* S, const float* aux, float* out, hipStream_t st,
                     bool split = false, bool plain_out = true, const BlockTail* tail = nullptr) {
-    ConvArgs ca{};
+    ConvArgs ca = bwd_args(u, n, row2img, S, out);
     if (tail) { ca.join = tail->join; ca.join_gate = tail->join_gate; ca.gate2 = tail->gate2; ca.out2s = tail->out2; }
-    ca.in = S; ca.wpk = split ? u.w_bs.as<float>() : u.w_b.as<float>(); ca.row2img = row2img; ca.aux = aux; ca.out = out;
-    ca.N = u.cin; ca.out_plain = plain_out ? 1 : 0;
-    ca.Cin = u.cout; ca.CinP = conv_cinp(u.cout); ca.NB = n; ca.H = u.Hout; ca.W = u.Wout; ca.taps = u.k == 3 ? 9 : 1;
+    ca.wpk = split ? u.w_bs.as<float>() : u.w_b.as<float>(); ca.aux = aux; ca.out_plain = plain_out ? 1 : 0;
     prof.begin(st);
     LRP_HIP_CHECK(conv_launch(EPI_MUL, ca, st, split ? PREC_BF16X3 : PREC_FP32));
-    prof.end(st, 2.0 * n * u.Hout * u.Wout * (double)(u.k == 3 ? 9 : 1) * u.cout * u.cin);
+    prof.end(st, bwd_flop(u, n));
     return LRP_OK;
   }
 
@@ -711,21 +732,29 @@ struct ResNetEncoder {
     for (int bi = (int)blocks.size() - 1; bi >= 0; --bi) {
       const RnBlock& b = blocks[bi];
       const size_t per_o = (size_t)b.H * b.W * 4 * b.f;
+      // bf16x3 mode: the convs of the main branch and of the projection in split8 form; the products that enter a chain are
+      // written split, what leaves it for the join is plain fp32
+      const bool sp = block_split(b);                    // split8 groups need channel counts % 8 == 0: exact fp32 otherwise
+      auto head = [&](const float* G, float* dst) -> int {     // a chain's head: dst = R_o * G
+        if (sp)
+          hipLaunchKernelGGL(rn_mul_gate_split_kernel, dim3(stream_grid((size_t)n * per_o / 8)), dim3(256), 0, st, Ro, G, row2img,
+                             dst, n, per_o / 8);
+        else
+          hipLaunchKernelGGL(rn_mul_gate_kernel, dim3(stream_grid((size_t)n * per_o)), dim3(256), 0, st, Ro, G, row2img,
+                             (const float*)nullptr, dst, n, per_o);
+        LRP_HIP_CHECK(hipGetLastError());
+        return LRP_OK;
+      };
+      // S3 = R_o * (fA Q3) in s3 (r1 / r5), unless the epilogue of the block walked before this one has written it already
+      // (same operand format: have_s3 is only set then); then S2 and S1.  S1 of a projection block takes the other S3 buffer,
+      // which S0 follows into
+      float* S1 = b.u0 < 0 ? r3.as<float>() : s3_other;
+      if (!have_s3) LRP_TRY(head(b.GA.as<float>(), s3));
+      LRP_TRY(unit_backward(units[b.u3], n, row2img, s3, units[b.u2].gate.as<float>(), r2.as<float>(), st, sp, !sp));              // S2
+      LRP_TRY(unit_backward(units[b.u2], n, row2img, r2.as<float>(), units[b.u1].gate.as<float>(), S1, st, sp, !sp));              // S1
       if (b.u0 < 0) {
         // identity block, 3 conv launches: S3 -> S2 -> S1 -> R_t = t*C1 + R_o*GS, the join and (when the next block
         // agrees on the operand format) the next block's S3 = R_t * GA_next written by unit 1's epilogue
-        const bool sp = block_split(b);
-        if (!have_s3) {
-          if (sp)
-            hipLaunchKernelGGL(rn_mul_gate_split_kernel, dim3(stream_grid((size_t)n * per_o / 8)), dim3(256), 0, st, Ro,
-                               b.GA.as<float>(), row2img, s3, n, per_o / 8);
-          else
-            hipLaunchKernelGGL(rn_mul_gate_kernel, dim3(stream_grid((size_t)n * per_o)), dim3(256), 0, st, Ro, b.GA.as<float>(),
-                               row2img, (const float*)nullptr, s3, n, per_o);
-          LRP_HIP_CHECK(hipGetLastError());
-        }
-        LRP_TRY(unit_backward(units[b.u3], n, row2img, s3, units[b.u2].gate.as<float>(), r2.as<float>(), st, sp, !sp));
-        LRP_TRY(unit_backward(units[b.u2], n, row2img, r2.as<float>(), units[b.u1].gate.as<float>(), r3.as<float>(), st, sp, !sp));
         BlockTail tl;
         tl.join = Ro; tl.join_gate = b.GS.as<float>();
         have_s3 = false;
@@ -733,38 +762,17 @@ struct ResNetEncoder {
           tl.gate2 = blocks[bi - 1].GA.as<float>(); tl.out2 = s3_other;
           have_s3 = true;
         }
-        LRP_TRY(unit_backward(units[b.u1], n, row2img, r3.as<float>(), b.t_in.as<float>(), cur, st, sp, true, &tl));
+        LRP_TRY(unit_backward(units[b.u1], n, row2img, S1, b.t_in.as<float>(), cur, st, sp, true, &tl));
         std::swap(s3, s3_other);
         Ro = cur;
         std::swap(cur, other);
         continue;
       }
-      // projection block (first of a stack).  bf16x3 mode: the three convs of the main branch and the projection chain in
-      // split8 form; the products that enter a chain are written split, what leaves it for the join is plain fp32
-      const bool sp = block_split(b);                    // split8 groups need channel counts % 8 == 0: exact fp32 otherwise
-      auto head = [&](const float* G, float* dst) {
-        if (sp)
-          hipLaunchKernelGGL(rn_mul_gate_split_kernel, dim3(stream_grid((size_t)n * per_o / 8)), dim3(256), 0, st, Ro, G, row2img,
-                             dst, n, per_o / 8);
-        else
-          hipLaunchKernelGGL(rn_mul_gate_kernel, dim3(stream_grid((size_t)n * per_o)), dim3(256), 0, st, Ro, G, row2img,
-                             (const float*)nullptr, dst, n, per_o);
-      };
-      // S3 = R_o * (fA Q3): already written by the epilogue of the identity block walked before this one (same operand
-      // format: have_s3 is only set then) — round 3 recomputed it here, one pass over R_o per stack for nothing
-      float* A = s3;                                     // r1 / r5: S3, later free
-      float* Bf = s3_other;                              // the other one: S1, then S0
-      if (!have_s3) {
-        head(b.GA.as<float>(), A);
-        LRP_HIP_CHECK(hipGetLastError());
-      }
-      LRP_TRY(unit_backward(units[b.u3], n, row2img, A, units[b.u2].gate.as<float>(), r2.as<float>(), st, sp, !sp));              // S2
-      LRP_TRY(unit_backward(units[b.u2], n, row2img, r2.as<float>(), units[b.u1].gate.as<float>(), Bf, st, sp, !sp));              // S1
+      // projection block (first of a stack)
       const float* taux = b.stride == 2 ? b.t_sub.as<float>() : b.t_in.as<float>();
-      LRP_TRY(unit_backward(units[b.u1], n, row2img, Bf, taux, r2.as<float>(), st, sp, true));                                    // t*C1 (coarse)
-      head(b.GS.as<float>(), Bf);                                                                                                  // S0
-      LRP_HIP_CHECK(hipGetLastError());
-      LRP_TRY(unit_backward(units[b.u0], n, row2img, Bf, taux, r3.as<float>(), st, sp, true));                                    // t*C0
+      LRP_TRY(unit_backward(units[b.u1], n, row2img, S1, taux, r2.as<float>(), st, sp, true));                                    // t*C1 (coarse)
+      LRP_TRY(head(b.GS.as<float>(), S1));                                                                                         // S0
+      LRP_TRY(unit_backward(units[b.u0], n, row2img, S1, taux, r3.as<float>(), st, sp, true));                                    // t*C0
       // join: R_t = t*C1 + t*C0 (scattered to the even positions behind a stride-2 block) and — one pass — the head of the
       // block walked next, S3' = R_t * GA' (an identity block: the last of the stack below)
       have_s3 = false;
@@ -772,14 +780,14 @@ struct ResNetEncoder {
       if (sp && !(b.cin & 7)) {
         const size_t tot8 = (size_t)n * b.Hin * b.Win * b.cin / 8;
         const float* g2 = fuse_next ? blocks[bi - 1].GA.as<float>() : (const float*)nullptr;
-        float* o2 = fuse_next ? A : (float*)nullptr;
+        float* o2 = fuse_next ? s3 : (float*)nullptr;    // (S3 of this block has been consumed)
         if (b.stride == 2)
           hipLaunchKernelGGL(rn_join_split_kernel<true>, dim3(stream_grid(tot8)), dim3(256), 0, st, r2.as<float>(), r3.as<float>(), cur,
                              g2, row2img, o2, n, b.Hin, b.Win, b.cin);
         else
           hipLaunchKernelGGL(rn_join_split_kernel<false>, dim3(stream_grid(tot8)), dim3(256), 0, st, r2.as<float>(), r3.as<float>(), cur,
                              g2, row2img, o2, n, b.Hin, b.Win, b.cin);
-        if (fuse_next) { s3 = A; s3_other = Bf; have_s3 = true; }
+        have_s3 = fuse_next;
       } else if (b.stride == 2) {
         const size_t tot = (size_t)n * b.Hin * b.Win * b.cin;
         hipLaunchKernelGGL(rn_scatter2_kernel, dim3(stream_grid(tot)), dim3(256), 0, st, r2.as<float>(), r3.as<float>(), cur, n,
@@ -806,30 +814,57 @@ struct ResNetEncoder {
       hipLaunchKernelGGL(rn_pool3_route_kernel<false>, dim3(stream_grid(tot / 4)), dim3(256), 0, st, Ro, pool_win.as<unsigned char>(),
                          q_stem.as<float>(), row2img, r1.as<float>(), n, s.Hout, s.Wout, s.cout);
     LRP_HIP_CHECK(hipGetLastError());
-    if (sw().img_fused != 0 && s.cout == 64 && (ssplit ? s.w_bs.p : s.w_b.p) && conv_npad(RN_STEM_TCOLS) >= 5 * 60 + 4 && conv_cinp(s.cout) == 64) {
-      // T = S . W and the 7x7 / stride-2 shift-and-add in ONE launch, T never leaves LDS (resnet_kernels.h rn_stem_reverse_kernel);
-      // LRP_IMG_FUSED=0 (and stems that are not 64 channels wide): the two-kernel form below
+    const StemEnd lrp_end{ssplit ? &rn_stem_reverse_kernel<true> : &rn_stem_reverse_kernel<false>, &rn_stem_stencil_kernel<0>};
+    return stem_reverse(ssplit ? s.w_bs.as<float>() : s.w_b.as<float>(), ssplit ? PREC_BF16X3 : PREC_FP32, s.cout, lrp_end, n, row2img,
+                        R_img_dev, st);
+  }
+
+  // ---- the stem conv's reverse, every walk's ----
+  // r1 holds the operand S [n][Hout][Wout][K]: K = stem_c, or 2 stem_c where it carries two chains.  T = S . W over the 49 taps x 6
+  // columns (w: w_b / w_bs, w_ab / w_abs, w_g; rp: PREC_FP32, or PREC_BF16X3 for an operand and a matrix in split8 form), then
+  // the 7x7 / stride-2 shift-and-add into the image.  (The kernels lie in the code object in the order the callers name them.)
+  // The image end is the caller's: the instantiations of one MODE (resnet_kernels.h: 0 = LRP, x+ . T+ + x- . T-;  1 = T+, a
+  // gradient;  2 = x . T+) — the stencil and the one-launch form for this operand (SPLIT = split8; nullptr: there is none)
+  struct StemEnd {
+    void (*fused)(const float*, const float*, const float*, const int*, float*, int, int, int, int);
+    void (*stencil)(const float*, const float*, const int*, float*, int, int, int);
+  };
+  // the tap GEMM alone (explain_ab's dry run asks conv_plan about it)
+  ConvArgs stem_tap_args(const float* w, int K, int n) const {
+    const RnUnit& s = units[0];
+    ConvArgs ca{};
+    ca.in = r1.as<float>(); ca.NB = n * s.Hout * s.Wout; ca.H = 1; ca.W = 1; ca.Cin = K; ca.CinP = conv_cinp(K);
+    ca.taps = 1; ca.wpk = w; ca.N = RN_STEM_TCOLS; ca.out = r2.as<float>();
+    return ca;
+  }
+  // the dynamic-LDS attribute of an rn_stem_reverse_kernel instantiation, set before its first launch
+  int stem_lds_attr(const void* kernel) {
+    for (const void*& done : stem_attr_set) {
+      if (done == kernel) return LRP_OK;
+      if (done) continue;
+      LRP_HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RN_STEM_LDS));
+      done = kernel;
+      return LRP_OK;
+    }
+    return fail(LRP_ERR_STATE, "stem_lds_attr: more instantiations of rn_stem_reverse_kernel than slots");
+  }
+  int stem_reverse(const float* w, int rp, int K, const StemEnd& end, int n, const int* row2img, float* R_img_dev, hipStream_t st) {
+    const RnUnit& s = units[0];
+    // T = S . W and the shift-and-add in ONE launch, T never leaves LDS (resnet_kernels.h rn_stem_reverse_kernel): its K is fixed
+    // at the 64 channels of one chain, so a two-chain operand (K = 2 stem_c) never takes it.  LRP_IMG_FUSED=0, and every other
+    // stem: the two-kernel form below
+    if (sw().img_fused != 0 && end.fused && w && K == s.cout && s.cout == 64 && conv_npad(RN_STEM_TCOLS) >= 5 * 60 + 4 &&
+        conv_cinp(s.cout) == 64) {
+      LRP_TRY(stem_lds_attr(reinterpret_cast<const void*>(end.fused)));
       const int txs = (s.Wout + RN_ST - 1) / RN_ST, tys = (s.Hout + RN_ST - 1) / RN_ST;
-      if (!stem_attr_set) {
-        LRP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rn_stem_reverse_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, RN_STEM_LDS));
-        LRP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rn_stem_reverse_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, RN_STEM_LDS));
-        stem_attr_set = true;
-      }
-      if (ssplit)
-        hipLaunchKernelGGL(rn_stem_reverse_kernel<true>, dim3((unsigned)(n * txs * tys)), dim3(512), RN_STEM_LDS, st, r1.as<float>(), s.w_bs.as<float>(),
-                           images.as<float>(), row2img, R_img_dev, s.Hout, s.Wout, txs, tys);
-      else
-        hipLaunchKernelGGL(rn_stem_reverse_kernel<false>, dim3((unsigned)(n * txs * tys)), dim3(512), RN_STEM_LDS, st, r1.as<float>(), s.w_b.as<float>(),
-                           images.as<float>(), row2img, R_img_dev, s.Hout, s.Wout, txs, tys);
+      hipLaunchKernelGGL(end.fused, dim3((unsigned)(n * txs * tys)), dim3(512), RN_STEM_LDS, st, r1.as<float>(), w, images.as<float>(),
+                         row2img, R_img_dev, s.Hout, s.Wout, txs, tys);
       LRP_HIP_CHECK(hipGetLastError());
       return LRP_OK;
     }
-    ConvArgs ca{};
-    ca.in = r1.as<float>(); ca.NB = n * s.Hout * s.Wout; ca.H = 1; ca.W = 1; ca.Cin = s.cout; ca.CinP = conv_cinp(s.cout);
-    ca.taps = 1; ca.wpk = ssplit ? s.w_bs.as<float>() : s.w_b.as<float>(); ca.N = RN_STEM_TCOLS; ca.out = r2.as<float>();
-    LRP_HIP_CHECK(conv_launch(EPI_STORE, ca, st, ssplit ? PREC_BF16X3 : PREC_FP32));
-    hipLaunchKernelGGL(rn_stem_stencil_kernel<0>, dim3(stream_grid((size_t)n * img_h * img_w)), dim3(256), 0, st, r2.as<float>(),
-                       images.as<float>(), row2img, R_img_dev, n, img_h, img_w);
+    LRP_HIP_CHECK(conv_launch(EPI_STORE, stem_tap_args(w, K, n), st, rp));
+    hipLaunchKernelGGL(end.stencil, dim3(stream_grid((size_t)n * img_h * img_w)), dim3(256), 0, st, r2.as<float>(), images.as<float>(),
+                       row2img, R_img_dev, n, img_h, img_w);
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   }
@@ -846,11 +881,9 @@ struct ResNetEncoder {
     const int rp = sp ? PREC_BF16X3 : PREC_FP32;
     // one transposed conv through unit u over both chains; aux_b != nullptr: dual gate, the output carries two chains
     auto conv = [&](const RnUnit& u, const float* S, const float* aux, const float* aux_b, float* out, const BlockTail* tail) -> int {
-      ConvArgs ca{};
+      ConvArgs ca = bwd_args(u, n, row2img, S, out, 2);
       if (tail) { ca.join = tail->join; ca.join_gate = tail->join_gate; }
-      ca.in = S; ca.wpk = sp ? u.w_abs.as<float>() : u.w_ab.as<float>(); ca.row2img = row2img; ca.aux = aux; ca.out = out;
-      ca.N = u.cin; ca.Cin = 2 * u.cout; ca.CinP = conv_cinp(2 * u.cout); ca.NB = n; ca.H = u.Hout; ca.W = u.Wout;
-      ca.taps = u.k == 3 ? 9 : 1;
+      ca.wpk = sp ? u.w_abs.as<float>() : u.w_ab.as<float>(); ca.aux = aux;
       if (aux_b) { ca.aux_b = aux_b; ca.out_b = out + u.cin; ca.ostride = 2 * u.cin; }
       else ca.out_plain = 1;                             // a relevance: feeds the join
       if (dry) {
@@ -861,7 +894,7 @@ struct ResNetEncoder {
       }
       prof.begin(st);
       LRP_HIP_CHECK(conv_launch(EPI_MUL, ca, st, rp));
-      prof.end(st, 4.0 * n * u.Hout * u.Wout * (double)(u.k == 3 ? 9 : 1) * u.cout * u.cin);
+      prof.end(st, 2 * bwd_flop(u, n));                  // (both chains)
       return LRP_OK;
     };
     auto head = [&](const RnBlock& bb, const float* Ro, const float* Ga, const float* Gi, float* dst) -> int {
@@ -924,11 +957,10 @@ struct ResNetEncoder {
     }
     // stem: two-gate pool routing -> T = [S_a | S_i] . [alpha (w+ | w-) ; -beta (w- | w+)] (K = 2 stem_c, N = 294) -> 7x7/2 stencil
     const RnUnit& s = units[0];
-    ConvArgs ca{};
-    ca.in = r1.as<float>(); ca.NB = n * s.Hout * s.Wout; ca.H = 1; ca.W = 1; ca.Cin = 2 * s.cout; ca.CinP = conv_cinp(2 * s.cout);
-    ca.taps = 1; ca.wpk = sp ? s.w_abs.as<float>() : s.w_ab.as<float>(); ca.N = RN_STEM_TCOLS; ca.out = r2.as<float>();
+    const float* wab = sp ? s.w_abs.as<float>() : s.w_ab.as<float>();
     if (dry) {
-      if (!conv_plan(conv_ask(EPI_STORE, rp, 7, false, ca)).ok) return fail(LRP_ERR_UNSUPPORTED, "alpha-beta walk: no conv kernel for the stem's tap GEMM");
+      if (!conv_plan(conv_ask(EPI_STORE, rp, 7, false, stem_tap_args(wab, 2 * s.cout, n))).ok)
+        return fail(LRP_ERR_UNSUPPORTED, "alpha-beta walk: no conv kernel for the stem's tap GEMM");
       return LRP_OK;
     }
     const size_t tot = (size_t)n * s.Hout * s.Wout * s.cout;
@@ -939,11 +971,7 @@ struct ResNetEncoder {
       hipLaunchKernelGGL(rn_pool3_route2_kernel<false>, dim3(stream_grid(tot / 4)), dim3(256), 0, st, Ro, pool_win.as<unsigned char>(),
                          q_stem.as<float>(), q_stem_i.as<float>(), row2img, r1.as<float>(), n, s.Hout, s.Wout, s.cout);
     LRP_HIP_CHECK(hipGetLastError());
-    LRP_HIP_CHECK(conv_launch(EPI_STORE, ca, st, rp));
-    hipLaunchKernelGGL(rn_stem_stencil_kernel<0>, dim3(stream_grid((size_t)n * img_h * img_w)), dim3(256), 0, st, r2.as<float>(),
-                       images.as<float>(), row2img, R_img_dev, n, img_h, img_w);
-    LRP_HIP_CHECK(hipGetLastError());
-    return LRP_OK;
+    return stem_reverse(wab, rp, 2 * s.cout, StemEnd{nullptr, &rn_stem_stencil_kernel<0>}, n, row2img, R_img_dev, st);
   }
 
   // ---- gradient walks (lrp_cnn_walk: LRP_WALK_GRADIENT / _INPUT_X_GRADIENT / _GUIDED_BACKPROP) -------------------------------
@@ -955,13 +983,13 @@ struct ResNetEncoder {
       if (u.k == 7) {
         const int Npb = conv_npad(RN_STEM_TCOLS), Kb = conv_cinp(u.cout);
         const size_t nb = (size_t)Npb * Kb;
-        if (!u.w_g.p) LRP_TRY(u.w_g.alloc(nb * 4, ws_total));
+        LRP_TRY(reserve(u.w_g, nb));
         hipLaunchKernelGGL(rn_pack_stem_grad_kernel, dim3(stream_grid(nb)), dim3(256), 0, st, u.w_a.as<float>(), u.gamma.as<float>(),
                            u.var.as<float>(), RN_BN_EPS, u.w_g.as<float>(), u.cout, Npb, Kb);
       } else {
         const int taps = u.k * u.k, CPi = conv_cinp(u.cin), CPo = conv_cinp(u.cout), rows = conv_npad(u.cin);
         const size_t nb = (size_t)rows * taps * CPo;
-        if (!u.w_g.p) LRP_TRY(u.w_g.alloc(nb * 4, ws_total));
+        LRP_TRY(reserve(u.w_g, nb));
         hipLaunchKernelGGL(rn_pack_grad_kernel, dim3(stream_grid(nb)), dim3(256), 0, st, u.w_a.as<float>(), u.gamma.as<float>(),
                            u.var.as<float>(), RN_BN_EPS, u.w_g.as<float>(), taps, u.cin, u.cout, CPi, CPo, rows);
       }
@@ -970,21 +998,19 @@ struct ResNetEncoder {
     }
     return LRP_OK;
   }
-  // one unit's gradient step: out = convT(S, W s) on the unit's output grid, then (mask != nullptr) the ReLU in front of it —
-  // GUIDED: clamp at 0 — and (tail != nullptr) the residual join out = rho(acc + tail) [mask], all in the conv's epilogue
-  int grad_backward(const RnUnit& u, int n, const int* row2img, const float* S, const unsigned char* mask, float* out, bool guided,
-                    hipStream_t st, const float* tail = nullptr, bool relu_nomask = false) {
-    ConvArgs ca{};
-    ca.in = S; ca.wpk = u.w_g.as<float>(); ca.row2img = row2img; ca.out = out; ca.N = u.cin; ca.out_plain = 1;
-    ca.Cin = u.cout; ca.CinP = conv_cinp(u.cout); ca.NB = n; ca.H = u.Hout; ca.W = u.Wout; ca.taps = u.k == 3 ? 9 : 1;
+  // one unit's gradient step: out = convT(S, W s) on the unit's output grid, then the ReLU in front of it — clamp: at 0 first
+  // (GUIDED, Deconvnet); mask != nullptr: its forward decision — and (tail != nullptr, with a mask) the residual join
+  // out = rho(acc + tail) [mask], all in the conv's epilogue
+  int grad_backward(const RnUnit& u, int n, const int* row2img, const float* S, const unsigned char* mask, float* out, bool clamp,
+                    hipStream_t st, const float* tail = nullptr) {
+    ConvArgs ca = bwd_args(u, n, row2img, S, out);
+    ca.wpk = u.w_g.as<float>(); ca.out_plain = 1; ca.relu_out = clamp ? 1 : 0;
     if (!mask) {
       ca.gate_none = 1;
-      ca.relu_out = relu_nomask ? 1 : 0;                 // Deconvnet: the ReLU in front clamps, and no mask follows
       LRP_HIP_CHECK(conv_launch(EPI_MUL, ca, st, PREC_FP32));
       return LRP_OK;
     }
     ca.aux = reinterpret_cast<const float*>(mask);       // (byte masks: conv_igemm_kernel GMASK)
-    ca.relu_out = guided ? 1 : 0;
     if (tail) { ca.join = tail; ca.join_gate = reinterpret_cast<const float*>(mask); }
     LRP_HIP_CHECK(conv_launch_grad_mask(ca, st));
     return LRP_OK;
@@ -998,45 +1024,64 @@ struct ResNetEncoder {
   // rho = relu for GUIDED_BACKPROP (every ReLU clamps what arrives first), identity otherwise.
   // LRP_WALK_DECONVNET (gradient_based.py:180-225) is the GUIDED walk with every mask replaced by ones: rho at each Activation,
   // the plain gradient through conv + BN, Add, pad and the stem pool.  It reads no ReLU decision — only pool_win, which every
-  // forward writes, and the BN-scaled matrices — so it runs in every precision mode (explain_deconvnet).
+  // forward writes, and the BN-scaled matrices — so it runs in every precision mode.
+  // What the four walks disagree on, decided once at the top of explain_grad:
+  struct GradMode {
+    bool masks = true;     // the fp32 forward's ReLU decisions are read (off: Deconvnet)
+    int clamp = 0;         // what a ReLU does to what arrives: 0 nothing but its mask, 1 GUIDED: clamp, then the mask,
+                           // 2 Deconvnet: the clamp alone (rn_grad_join_kernel tells 1 from 2; everywhere else it is a flag)
+    int img_mode = 1;      // the image end (rn_stem_reverse_kernel's MODE): 1 the gradient, 2 times the image
+  };
   int explain_grad(int n, const int* row2img, const float* head, float* R_img_dev, hipStream_t st, int walk) {
     if (walk != LRP_WALK_GRADIENT && walk != LRP_WALK_INPUT_X_GRADIENT && walk != LRP_WALK_GUIDED_BACKPROP && walk != LRP_WALK_DECONVNET)
       return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
-    if (walk == LRP_WALK_DECONVNET) return explain_deconvnet(n, row2img, head, R_img_dev, st);
-    if (prec != PREC_FP32)
+    GradMode m;
+    m.masks = walk != LRP_WALK_DECONVNET;
+    m.clamp = walk == LRP_WALK_DECONVNET ? 2 : walk == LRP_WALK_GUIDED_BACKPROP ? 1 : 0;
+    m.img_mode = walk == LRP_WALK_INPUT_X_GRADIENT ? 2 : 1;
+    if (m.masks && prec != PREC_FP32)
       return fail(LRP_ERR_UNSUPPORTED, "gradient walks on a ResNet encoder run in LRP_PREC_FP32 only: set it with lrp_set_precision "
                                        "and call lrp_encode_images again");
-    if (!masks_ok) return fail(LRP_ERR_STATE, "lrp_encode_images must run in LRP_PREC_FP32 mode before a ResNet gradient walk");
-    const bool guided = walk == LRP_WALK_GUIDED_BACKPROP;
+    if (m.masks && !masks_ok)
+      return fail(LRP_ERR_STATE, "lrp_encode_images must run in LRP_PREC_FP32 mode before a ResNet gradient walk");
+    auto mask_of = [&](const DevBuf& d) { return m.masks ? d.as<unsigned char>() : (const unsigned char*)nullptr; };
+    const bool clamp = m.clamp != 0;
     LRP_TRY(ensure_grad_weights(st));
     float* G = r0.as<float>();
     float* other = r4.as<float>();
     {
       const RnBlock& t = blocks.back();
       const size_t per = (size_t)t.H * t.W * 4 * t.f;
-      hipLaunchKernelGGL(rn_grad_head_kernel, dim3(stream_grid((size_t)n * per / 4)), dim3(256), 0, st, head,
-                         t.omask.as<unsigned char>(), row2img, G, n, per, guided ? 1 : 0);
+      hipLaunchKernelGGL(rn_grad_head_kernel, dim3(stream_grid((size_t)n * per / 4)), dim3(256), 0, st, head, mask_of(t.omask), row2img, G,
+                         n, per, clamp ? 1 : 0);
       LRP_HIP_CHECK(hipGetLastError());
     }
     for (int bi = (int)blocks.size() - 1; bi >= 0; --bi) {
       const RnBlock& b = blocks[bi];
       const RnUnit &u1 = units[b.u1], &u2 = units[b.u2], &u3 = units[b.u3];
-      LRP_TRY(grad_backward(u3, n, row2img, G, u2.mask.as<unsigned char>(), r2.as<float>(), guided, st));
-      LRP_TRY(grad_backward(u2, n, row2img, r2.as<float>(), u1.mask.as<unsigned char>(), r3.as<float>(), guided, st));
-      const unsigned char* in_mask = bi > 0 ? blocks[bi - 1].omask.as<unsigned char>() : (const unsigned char*)nullptr;
-      if (b.u0 < 0) {
-        // identity block (never the first): the join and the block input's ReLU in unit 1's epilogue
-        LRP_TRY(grad_backward(u1, n, row2img, r3.as<float>(), in_mask, other, guided, st, G));
+      LRP_TRY(grad_backward(u3, n, row2img, G, mask_of(u2.mask), r2.as<float>(), clamp, st));
+      LRP_TRY(grad_backward(u2, n, row2img, r2.as<float>(), mask_of(u1.mask), r3.as<float>(), clamp, st));
+      // the block input's ReLU (the first block's input is the stem pool's output: none there)
+      const unsigned char* in_mask = bi > 0 ? mask_of(blocks[bi - 1].omask) : (const unsigned char*)nullptr;
+      if (m.masks && b.u0 < 0) {
+        // identity block (never the first) with masks: the join and the block input's ReLU ride in unit 1's epilogue
+        LRP_TRY(grad_backward(u1, n, row2img, r3.as<float>(), in_mask, other, clamp, st, G));
       } else {
-        LRP_TRY(grad_backward(u1, n, row2img, r3.as<float>(), nullptr, r1.as<float>(), guided, st));
-        LRP_TRY(grad_backward(units[b.u0], n, row2img, G, nullptr, r5.as<float>(), guided, st));
+        LRP_TRY(grad_backward(u1, n, row2img, r3.as<float>(), nullptr, r1.as<float>(), false, st));
+        const float* sc = G;                             // the shortcut's term: G itself, or convT0(G) on the coarse grid
+        if (b.u0 >= 0) {
+          LRP_TRY(grad_backward(units[b.u0], n, row2img, G, nullptr, r5.as<float>(), false, st));
+          sc = r5.as<float>();
+        }
+        // the join, then the block input's ReLU
         const size_t tot = (size_t)n * b.Hin * b.Win * b.cin / 4;
-        if (b.stride == 2)
-          hipLaunchKernelGGL(rn_grad_join_kernel<true>, dim3(stream_grid(tot)), dim3(256), 0, st, r1.as<float>(), r5.as<float>(), in_mask,
-                             row2img, other, n, b.Hin, b.Win, b.cin, guided ? 1 : 0);
+        const int jclamp = m.masks || bi > 0 ? m.clamp : 0;
+        if (b.u0 >= 0 && b.stride == 2)
+          hipLaunchKernelGGL(rn_grad_join_kernel<true>, dim3(stream_grid(tot)), dim3(256), 0, st, r1.as<float>(), sc, in_mask, row2img, other,
+                             n, b.Hin, b.Win, b.cin, jclamp);
         else
-          hipLaunchKernelGGL(rn_grad_join_kernel<false>, dim3(stream_grid(tot)), dim3(256), 0, st, r1.as<float>(), r5.as<float>(), in_mask,
-                             row2img, other, n, b.Hin, b.Win, b.cin, guided ? 1 : 0);
+          hipLaunchKernelGGL(rn_grad_join_kernel<false>, dim3(stream_grid(tot)), dim3(256), 0, st, r1.as<float>(), sc, in_mask, row2img, other,
+                             n, b.Hin, b.Win, b.cin, jclamp);
         LRP_HIP_CHECK(hipGetLastError());
       }
       std::swap(G, other);
@@ -1045,91 +1090,12 @@ struct ResNetEncoder {
     const RnUnit& s = units[0];
     const size_t tot = (size_t)n * s.Hout * s.Wout * s.cout / 4;
     hipLaunchKernelGGL(rn_grad_pool_route_kernel, dim3(stream_grid(tot)), dim3(256), 0, st, G, pool_win.as<unsigned char>(),
-                       a0.as<float>(), row2img, r1.as<float>(), n, s.Hout, s.Wout, s.cout, guided ? 1 : 0);
+                       m.masks ? a0.as<float>() : (const float*)nullptr, row2img, r1.as<float>(), n, s.Hout, s.Wout, s.cout, clamp ? 1 : 0);
     LRP_HIP_CHECK(hipGetLastError());
-    return grad_stem(n, row2img, R_img_dev, st, walk == LRP_WALK_INPUT_X_GRADIENT);
+    const StemEnd end{m.img_mode == 1 ? &rn_stem_reverse_kernel<false, 1> : &rn_stem_reverse_kernel<false, 2>,
+                      m.img_mode == 2 ? &rn_stem_stencil_kernel<2> : &rn_stem_stencil_kernel<1>};
+    return stem_reverse(s.w_g.as<float>(), PREC_FP32, s.cout, end, n, row2img, R_img_dev, st);
   }
-  // the Deconvnet walk (see explain_grad): rho = relu at every Activation, no mask anywhere
-  int explain_deconvnet(int n, const int* row2img, const float* head, float* R_img_dev, hipStream_t st) {
-    LRP_TRY(ensure_grad_weights(st));
-    float* G = r0.as<float>();
-    float* other = r4.as<float>();
-    {
-      const RnBlock& t = blocks.back();
-      const size_t per = (size_t)t.H * t.W * 4 * t.f;
-      hipLaunchKernelGGL(rn_grad_head_kernel, dim3(stream_grid((size_t)n * per / 4)), dim3(256), 0, st, head, (const unsigned char*)nullptr,
-                         row2img, G, n, per, 1);
-      LRP_HIP_CHECK(hipGetLastError());
-    }
-    for (int bi = (int)blocks.size() - 1; bi >= 0; --bi) {
-      const RnBlock& b = blocks[bi];
-      const RnUnit &u1 = units[b.u1], &u2 = units[b.u2], &u3 = units[b.u3];
-      LRP_TRY(grad_backward(u3, n, row2img, G, nullptr, r2.as<float>(), false, st, nullptr, true));
-      LRP_TRY(grad_backward(u2, n, row2img, r2.as<float>(), nullptr, r3.as<float>(), false, st, nullptr, true));
-      LRP_TRY(grad_backward(u1, n, row2img, r3.as<float>(), nullptr, r1.as<float>(), false, st));
-      const float* sc = G;                               // the shortcut's term: G itself, or convT0(G) on the coarse grid
-      if (b.u0 >= 0) {
-        LRP_TRY(grad_backward(units[b.u0], n, row2img, G, nullptr, r5.as<float>(), false, st));
-        sc = r5.as<float>();
-      }
-      // the join, then the block input's Activation (the first block's input is the stem pool's output: no clamp there)
-      const size_t tot = (size_t)n * b.Hin * b.Win * b.cin / 4;
-      const int clamp = bi > 0 ? 2 : 0;
-      if (b.u0 >= 0 && b.stride == 2)
-        hipLaunchKernelGGL(rn_grad_join_kernel<true>, dim3(stream_grid(tot)), dim3(256), 0, st, r1.as<float>(), sc, (const unsigned char*)nullptr,
-                           row2img, other, n, b.Hin, b.Win, b.cin, clamp);
-      else
-        hipLaunchKernelGGL(rn_grad_join_kernel<false>, dim3(stream_grid(tot)), dim3(256), 0, st, r1.as<float>(), sc, (const unsigned char*)nullptr,
-                           row2img, other, n, b.Hin, b.Win, b.cin, clamp);
-      LRP_HIP_CHECK(hipGetLastError());
-      std::swap(G, other);
-    }
-    const RnUnit& s = units[0];
-    const size_t tot = (size_t)n * s.Hout * s.Wout * s.cout / 4;
-    hipLaunchKernelGGL(rn_grad_pool_route_kernel, dim3(stream_grid(tot)), dim3(256), 0, st, G, pool_win.as<unsigned char>(),
-                       (const float*)nullptr, row2img, r1.as<float>(), n, s.Hout, s.Wout, s.cout, 1);
-    LRP_HIP_CHECK(hipGetLastError());
-    return grad_stem(n, row2img, R_img_dev, st, false);
-  }
-  // the stem conv's backward on r1 (the gradient at its pre-activation): T GEMM + 7x7/2 stencil, ixg: times the image
-  int grad_stem(int n, const int* row2img, float* R_img_dev, hipStream_t st, bool ixg) {
-    const RnUnit& s = units[0];
-    if (sw().img_fused != 0 && s.cout == 64 && conv_npad(RN_STEM_TCOLS) >= 5 * 60 + 4 && conv_cinp(s.cout) == 64) {
-      const int txs = (s.Wout + RN_ST - 1) / RN_ST, tys = (s.Hout + RN_ST - 1) / RN_ST;
-      if (!stem_grad_attr_set) {
-        LRP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rn_stem_reverse_kernel<false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, RN_STEM_LDS));
-        LRP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&rn_stem_reverse_kernel<false, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, RN_STEM_LDS));
-        stem_grad_attr_set = true;
-      }
-      if (ixg)
-        hipLaunchKernelGGL((rn_stem_reverse_kernel<false, 2>), dim3((unsigned)(n * txs * tys)), dim3(512), RN_STEM_LDS, st, r1.as<float>(),
-                           s.w_g.as<float>(), images.as<float>(), row2img, R_img_dev, s.Hout, s.Wout, txs, tys);
-      else
-        hipLaunchKernelGGL((rn_stem_reverse_kernel<false, 1>), dim3((unsigned)(n * txs * tys)), dim3(512), RN_STEM_LDS, st, r1.as<float>(),
-                           s.w_g.as<float>(), images.as<float>(), row2img, R_img_dev, s.Hout, s.Wout, txs, tys);
-      LRP_HIP_CHECK(hipGetLastError());
-      return LRP_OK;
-    }
-    ConvArgs ca{};
-    ca.in = r1.as<float>(); ca.NB = n * s.Hout * s.Wout; ca.H = 1; ca.W = 1; ca.Cin = s.cout; ca.CinP = conv_cinp(s.cout);
-    ca.taps = 1; ca.wpk = s.w_g.as<float>(); ca.N = RN_STEM_TCOLS; ca.out = r2.as<float>();
-    LRP_HIP_CHECK(conv_launch(EPI_STORE, ca, st, PREC_FP32));
-    if (ixg)
-      hipLaunchKernelGGL(rn_stem_stencil_kernel<2>, dim3(stream_grid((size_t)n * img_h * img_w)), dim3(256), 0, st, r2.as<float>(),
-                         images.as<float>(), row2img, R_img_dev, n, img_h, img_w);
-    else
-      hipLaunchKernelGGL(rn_stem_stencil_kernel<1>, dim3(stream_grid((size_t)n * img_h * img_w)), dim3(256), 0, st, r2.as<float>(),
-                         images.as<float>(), row2img, R_img_dev, n, img_h, img_w);
-    LRP_HIP_CHECK(hipGetLastError());
-    return LRP_OK;
-  }
-  bool stem_grad_attr_set = false;
-
-  // the stem's routing needs Q alone: what arrives at a0 = relu(y) through the pool is already a relevance
-  // (t * C1 of the first block), so multiplying by the relu-unit gate a0*Q would count a0 twice
-  DevBuf q_stem;
-  DevBuf pool_win;
-  bool stem_attr_set = false;
 };
 
 }  // namespace lrp

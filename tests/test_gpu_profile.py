@@ -54,6 +54,46 @@ def test_vgg_walk_books_one_record_per_layer(name, cfg, hw, B, prec):
     assert eng.profile_query() == (0, 0.0, 0.0)
 
 
+@pytest.mark.parametrize("prec", ["bf16x3", "fp32"])
+def test_resnet_walk_books_one_record_per_conv_launch(prec):
+    """The `ident` net of test_gpu_resnet_alphabeta.py (one stack of a projection and an identity block, stem 8, 16 x 16), B = 2,
+    4 maps: one record per transposed conv through a unit — 4 for the projection block, 3 for the identity block, none for the
+    stem's tap GEMM — with 2 n Hout Wout k^2 cout cin on each; the two-chain walk of rule (2, 1) makes the same launches over both
+    chains and books twice that on each."""
+    from test_gpu_resnet_alphabeta import NETS, _engine as ab_engine
+    stacks, stem, (h, wd), _, _ = NETS["ident"]
+    assert (stacks, stem, (h, wd)) == (((8, 2),), 8, (16, 16))
+    B, n = 2, 4
+    rs = np.random.RandomState(5)
+    w = resnet_weights(rs, stacks, stem=stem, bias_std=0.2)
+    X = rs.uniform(-120, 130, size=(B, h, wd, 3)).astype(np.float32)
+    side, f = h // 4, stacks[0][0]
+    # (k, cin, cout) of the units on their side x side output grid: block 1 has the projection shortcut, block 2 has none
+    convs = [(1, stem, 4 * f), (1, stem, f), (3, f, f), (1, f, 4 * f), (1, 4 * f, f), (3, f, f), (1, f, 4 * f)]
+    want = sum(2 * n * side * side * k * k * cout * cin for k, cin, cout in convs)
+    assert want < 2 ** 53
+    eng = ab_engine("ident", w, max_images=B, max_tokens=n)
+    eng.set_precision(prec)
+    idx = [0, 1, 1, 0]
+    R = rs.standard_normal((n, side * side, 4 * f)).astype(np.float32)
+    for rule, factor in ((None, 1), ((2, 1), 2)):
+        if rule:
+            eng.set_cnn_rule(*rule)
+        eng.encode_images(X)
+        eng.profile_enable(True)
+        eng.cnn_explain(idx, R)
+        launches, ms, flop = eng.profile_query()
+        print("resnet ident", prec, rule, launches, ms, flop, factor * want)
+        assert launches == len(convs) == 7
+        assert flop == float(factor * want)
+        assert ms > 0
+        eng.cnn_explain(idx, R)
+        recs = eng.profile_records()
+        assert len(recs) == 7
+        assert sum(fl for _, fl in recs) == float(factor * want)
+        eng.profile_enable(False)
+
+
 def test_resnet_handle_reports_its_own_records():
     """lrp_profile_query on a ResNet handle reads the ResNet encoder's records, as lrp_profile_records does: the launch count
     of one walk equals the row count of an identical second walk."""
