@@ -337,6 +337,26 @@ typedef struct lrp_conv_rule {
 } lrp_conv_rule;
 int lrp_set_cnn_rules(lrp_handle* h, const lrp_conv_rule* rules, int32_t n_rules);
 
+/* Added without a version bump (purely additive).  The rule PAIR of a ResNet handle's LRP walk: `stem` for the
+ * 7x7 stem conv (the input layer), `units` for every conv above it; BatchNorm, Add, the pad and the stem pool are reversed as
+ * before whatever the pair.  Records as lrp_set_cnn_rules reads them:
+ *   units  LRP_RULE_ALPHA_BETA (bias 1 or 0) or LRP_RULE_EPSILON (bias 1 or 0; eps = 0 is ZRule)
+ *   stem   those, and LRP_RULE_FLAT, LRP_RULE_WSQUARE, LRP_RULE_BOUNDED.  The stem is a valid conv over the explicitly padded
+ *          image, so all 147 taps count at every output pixel (flat: Z = 147; w-square: the sum of w^2 per channel; bounded: pad
+ *          cells hold low / high like every other cell) and relevance sent to pad cells is cropped away.
+ * The two records are independent: every combination runs.  lrp_set_cnn_rule(alpha, beta) IS the pair with that alpha-beta-with-
+ * bias record twice: one rule state, the same code, to the bit; the pair already set changes and drops nothing.  Any other
+ * change drops the encode caches (LRP_ERR_STATE from the explain calls until lrp_encode_images ran again).  Every other pair leaves
+ * the forward as it is — the features are those of a handle that never set a rule, bit for bit — and lrp_encode_images makes the
+ * pair's gates behind it with fp32 launches of the units' convs and one streaming kernel per gate.
+ * LRP_ERR_INVALID: lrp_set_cnn_rules' value checks; an input-layer kind in `units`.  LRP_ERR_UNSUPPORTED: a VGG-style handle;
+ * beta > 0 in either record on widths that are no multiples of 8 (as lrp_set_cnn_rule); from the explain calls for a pair with an
+ * epsilon kind outside LRP_PREC_FP32, and for a launch lrp_conv_plan refuses.  Alpha-beta and the three input kinds run in
+ * LRP_PREC_BF16X3 and LRP_PREC_FP32.  Buffers and matrices appear with the first pair that needs them, are counted in
+ * lrp_workspace_bytes and idle afterwards; a handle that never sets a pair allocates nothing.  The gradient walks ignore the pair.
+ * lrp_set_cnn_rules keeps answering LRP_ERR_UNSUPPORTED on a ResNet handle: a rule per conv of the branched graph is not built. */
+int lrp_set_resnet_rules(lrp_handle* h, const lrp_conv_rule* stem, const lrp_conv_rule* units);
+
 /* Dominant-kernel timing for bench.py's roofline block: when enabled, HIP
  * events bracket every conv-LRP launch on the caller's stream; query returns
  * launches and summed milliseconds since the last reset (syncs the events). */

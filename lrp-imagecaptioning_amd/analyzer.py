@@ -280,24 +280,51 @@ def rule_table(rule, input_layer_rule, n_conv):
     return tuple(table)
 
 
+def resnet_rule_pair(rule, input_layer_rule=None):
+    """The rule pair of a ResNet encoder (LRPEngine.set_resnet_rules) from the keywords of LRP(...): -> (stem record, record of
+    every other conv).  rule: ONE rule; a list is refused — the reference pops list entries in its graph-reversal order of the
+    branched graph, which is not reproduced.  input_layer_rule: a rule, or (low, high) for BoundedRule; None: `rule` at the stem too."""
+    if rule is None:
+        raise ValueError("Need LRP rule(s).")                                              # RA:345-346
+    if isinstance(rule, list):
+        raise NotImplementedError("a list with a rule per conv on a ResNet encoder: the reference's list order over the branched graph "
+                                  "is not reproduced; give one rule and an input_layer_rule")
+    units = normalize_rule(rule)
+    if units[0] in _INPUT_ONLY:
+        raise NotImplementedError("%s above the input layer is not built: it sends relevance to units whose ReLU is off, "
+                                  "which the cached gates cannot carry" % units[0])
+    if input_layer_rule is None:
+        return units, units
+    if isinstance(input_layer_rule, tuple) and len(input_layer_rule) == 2 and not isinstance(input_layer_rule[0], str):
+        input_layer_rule = ("bounded",) + tuple(input_layer_rule)                          # RA:379-386
+    return normalize_rule(input_layer_rule), units
+
+
 class LRP(LRPSequentialPresetA):
-    """relevance_analyzer.py:300-500 for the truncated VGG-style encoders: `rule` for every conv (a name of LRP_RULES, a rule
-    class, a record of normalize_rule, or a list per conv), `input_layer_rule` for the image layer (a rule, or (low, high) for
-    BoundedRule); max-pools by gradient routing.  Same analyze([X, R]) surface; the engine runs the table walk of
-    lrp_set_cnn_rules.  Epsilon and Z rules switch the engine to exact fp32, as the gradient analyzers do."""
+    """relevance_analyzer.py:300-500 for the truncated encoders: `rule` for every conv (a name of LRP_RULES, a rule class, a record
+    of normalize_rule, or — VGG-style encoders — a list per conv), `input_layer_rule` for the image layer (a rule, or (low, high)
+    for BoundedRule); pools by gradient routing.  Same analyze([X, R]) surface; the engine runs the table walk of
+    lrp_set_cnn_rules, on a ResNet `ImageModelSpec` the rule pair of lrp_set_resnet_rules (BatchNorm, Add and the pad reversed as
+    under every other analyzer).  Epsilon and Z rules switch the engine to exact fp32, as the gradient analyzers do.
+
+    One deviation on a ResNet encoder: the reference selects the input rule by `is_input_layer` (checks.py:394-424), which is
+    false for Keras ResNet's `conv1_conv` because `conv1_pad` sits in front of it, so with a single rule it silently never
+    applies `input_layer_rule` on this model.  Here the input rule applies at the stem conv: what the caller asks for, and what
+    the reference's list form does.  A `rule=[...]` list on a ResNet spec stays NotImplementedError."""
 
     def __init__(self, model, rule=None, input_layer_rule=None, neuron_selection_mode="replace", **kwargs):
         if rule is None:
             raise ValueError("Need LRP rule(s).")                                          # RA:345-346
-        if getattr(model, "resnet", None) is not None:
-            raise NotImplementedError("the ResNet encoder's walk has no rule table: LRPAlphaBeta / LRPAlpha2Beta1 / LRPSequentialPresetB "
-                                      "run one alpha-beta rule on it")
-        table = rule_table(rule, input_layer_rule, len(model.cnn_cfg))
+        resnet = getattr(model, "resnet", None) is not None
+        table = resnet_rule_pair(rule, input_layer_rule) if resnet else rule_table(rule, input_layer_rule, len(model.cnn_cfg))
         self._rule, self._input_layer_rule, self._table = rule, input_layer_rule, table
         super(LRP, self).__init__(model, neuron_selection_mode=neuron_selection_mode, **kwargs)
         if any(r[0] == "epsilon" for r in table):
             self._engine.set_precision("fp32")
-        self._engine.set_cnn_rules(table)
+        if resnet:
+            self._engine.set_resnet_rules(table[1], table[0])
+        else:
+            self._engine.set_cnn_rules(table)
 
 
 class LRPZ(LRP):

@@ -464,41 +464,61 @@ int lrp_set_cnn_rule(lrp_handle* h, float alpha, float beta) {
   });
 }
 
+// One record of either rule entry, value-checked into `o`.  i: the conv the record is for, 0 = the input layer — flat, w-square and
+// bounded are refused above it
+static int check_conv_rule(const lrp_conv_rule& r, int i, Encoder::ConvRule& o) {
+  if (r.kind < LRP_RULE_ALPHA_BETA || r.kind > LRP_RULE_BOUNDED) return fail(LRP_ERR_INVALID, "conv %d: unknown rule kind %d", i, r.kind);
+  o.kind = r.kind;
+  if (o.input_only() && i > 0)
+    return fail(LRP_ERR_INVALID, "conv %d: flat, w-square and bounded are input-layer rules (above it they need relevance at dead units)", i);
+  o.bias = 0;
+  if (r.kind == LRP_RULE_ALPHA_BETA || r.kind == LRP_RULE_EPSILON) {
+    if (r.bias != 0 && r.bias != 1) return fail(LRP_ERR_INVALID, "conv %d: bias must be 0 or 1", i);
+    o.bias = r.bias;
+  }
+  if (r.kind == LRP_RULE_ALPHA_BETA) {               // lrp_set_cnn_rule's check
+    if (!(r.alpha >= 1.f)) return fail(LRP_ERR_INVALID, "conv %d: alpha should be >= 1 (alpha=%g)", i, (double)r.alpha);
+    if (!(r.beta >= 0.f)) return fail(LRP_ERR_INVALID, "conv %d: beta should be >= 0 (beta=%g)", i, (double)r.beta);
+    if (!(fabs((double)r.alpha - (double)r.beta - 1.0) <= 6e-8 * ((double)r.alpha + (double)r.beta)))
+      return fail(LRP_ERR_INVALID, "conv %d: alpha - beta should be 1 (alpha=%g, beta=%g)", i, (double)r.alpha, (double)r.beta);
+    o.alpha = r.alpha; o.beta = r.alpha - 1.f;
+  } else if (r.kind == LRP_RULE_EPSILON) {
+    if (!(r.eps >= 0.f) || !(r.eps < 3.0e38f)) return fail(LRP_ERR_INVALID, "conv %d: epsilon should be >= 0 (eps=%g)", i, (double)r.eps);
+    o.eps = r.eps;
+  } else if (r.kind == LRP_RULE_BOUNDED) {
+    if (!(r.low < r.high) || !(fabsf(r.low) < 3.0e38f) || !(fabsf(r.high) < 3.0e38f))
+      return fail(LRP_ERR_INVALID, "bounded rule: low < high (low=%g, high=%g)", (double)r.low, (double)r.high);
+    o.low = r.low; o.high = r.high;
+  }
+  return LRP_OK;
+}
+
 int lrp_set_cnn_rules(lrp_handle* h, const lrp_conv_rule* rules, int32_t n_rules) {
   return with_handle(h, [&]() -> int {
-    if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "the ResNet encoder's walk has no rule table");
+    if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "the ResNet encoder's walk has no rule per conv: lrp_set_resnet_rules takes a rule pair");
     if (!rules || n_rules != (int)h->enc.layers.size())
       return fail(LRP_ERR_INVALID, "one rule per conv: %d given, %d convs", rules ? n_rules : 0, (int)h->enc.layers.size());
     std::vector<Encoder::ConvRule> t((size_t)n_rules);
-    for (int i = 0; i < n_rules; ++i) {
-      const lrp_conv_rule& r = rules[i];
-      Encoder::ConvRule& o = t[(size_t)i];
-      if (r.kind < LRP_RULE_ALPHA_BETA || r.kind > LRP_RULE_BOUNDED) return fail(LRP_ERR_INVALID, "conv %d: unknown rule kind %d", i, r.kind);
-      o.kind = r.kind;
-      if (o.input_only() && i > 0)
-        return fail(LRP_ERR_INVALID, "conv %d: flat, w-square and bounded are input-layer rules (above it they need relevance at dead units)", i);
-      o.bias = 0;
-      if (r.kind == LRP_RULE_ALPHA_BETA || r.kind == LRP_RULE_EPSILON) {
-        if (r.bias != 0 && r.bias != 1) return fail(LRP_ERR_INVALID, "conv %d: bias must be 0 or 1", i);
-        o.bias = r.bias;
-      }
-      if (r.kind == LRP_RULE_ALPHA_BETA) {               // lrp_set_cnn_rule's check
-        if (!(r.alpha >= 1.f)) return fail(LRP_ERR_INVALID, "conv %d: alpha should be >= 1 (alpha=%g)", i, (double)r.alpha);
-        if (!(r.beta >= 0.f)) return fail(LRP_ERR_INVALID, "conv %d: beta should be >= 0 (beta=%g)", i, (double)r.beta);
-        if (!(fabs((double)r.alpha - (double)r.beta - 1.0) <= 6e-8 * ((double)r.alpha + (double)r.beta)))
-          return fail(LRP_ERR_INVALID, "conv %d: alpha - beta should be 1 (alpha=%g, beta=%g)", i, (double)r.alpha, (double)r.beta);
-        o.alpha = r.alpha; o.beta = r.alpha - 1.f;
-      } else if (r.kind == LRP_RULE_EPSILON) {
-        if (!(r.eps >= 0.f) || !(r.eps < 3.0e38f)) return fail(LRP_ERR_INVALID, "conv %d: epsilon should be >= 0 (eps=%g)", i, (double)r.eps);
-        o.eps = r.eps;
-      } else if (r.kind == LRP_RULE_BOUNDED) {
-        if (!(r.low < r.high) || !(fabsf(r.low) < 3.0e38f) || !(fabsf(r.high) < 3.0e38f))
-          return fail(LRP_ERR_INVALID, "bounded rule: low < high (low=%g, high=%g)", (double)r.low, (double)r.high);
-        o.low = r.low; o.high = r.high;
-      }
-    }
+    for (int i = 0; i < n_rules; ++i) LRP_TRY(check_conv_rule(rules[i], i, t[(size_t)i]));
     if (t[0].input_only() && n_rules < 2) return fail(LRP_ERR_UNSUPPORTED, "an input-layer rule needs a conv above the image layer");
     return set_vgg_table(h, std::move(t));
+  });
+}
+
+int lrp_set_resnet_rules(lrp_handle* h, const lrp_conv_rule* stem, const lrp_conv_rule* units) {
+  return with_handle(h, [&]() -> int {
+    if (!h) return fail(LRP_ERR_INVALID, "null handle");
+    if (!h->resnet) return fail(LRP_ERR_UNSUPPORTED, "a VGG-style handle takes a rule per conv: lrp_set_cnn_rules");
+    if (!stem || !units) return fail(LRP_ERR_INVALID, "lrp_set_resnet_rules: two records, the stem's and the other convs'");
+    Encoder::ConvRule cs, cu;
+    LRP_TRY(check_conv_rule(*stem, 0, cs));
+    LRP_TRY(check_conv_rule(*units, 1, cu));
+    auto rec = [](const Encoder::ConvRule& c) {
+      ResNetEncoder::Rule r;
+      r.kind = c.kind; r.bias = c.bias; r.alpha = c.alpha; r.beta = c.beta; r.eps = c.eps; r.low = c.low; r.high = c.high;
+      return r;
+    };
+    return h->rn.set_rules(rec(cs), rec(cu));                      // (refuses beta > 0 on widths that are no multiples of 8)
   });
 }
 

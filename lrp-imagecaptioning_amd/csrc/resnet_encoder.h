@@ -7,6 +7,10 @@
 // This path runs in exact fp32 (PREC_FP32) throughout.
 //   explain_ab(): the same walk under the alpha-beta rule with beta > 0 (set_rule): two relevance chains per tensor, the second
 //              gate of every unit and block made at encode time behind the unchanged forward (oracle: tests/resnet_ab_ref.py).
+//   set_rules(): the rule PAIR — one record for the stem conv, one for every conv above it (alpha-beta / epsilon with or without the
+//              bias; flat, w-square, bounded at the stem).  rule_gates() writes the pair's gates behind the unchanged forward,
+//              explain() / explain_ab() walk them by the unit record's chain count, stem_end() ends both by the stem record's
+//              (oracle: tests/resnet_rule_ref.py).
 //   explain_grad(): the gradient family, one walk driven by a GradMode.  Gradient / InputTimesGradient / GuidedBackprop in
 //              LRP_PREC_FP32 mode: the same convT launches with BN-scaled full-sign weights (w_g, packed on the first such walk)
 //              and the ReLU decisions the fp32 forward recorded as byte masks (RnUnit::mask, RnBlock::omask).  Deconvnet: the
@@ -55,6 +59,10 @@ struct RnUnit {            // conv + BN
   // w_dualn_h: interleaved [w | w-] fp16 pairs of a dual_il unit) and the backward matrix [alpha w+ ; -beta w-], plain and split8
   DevBuf gate_i, w_n, w_dualn_h, w_ab, w_abs;
   bool ab_packed = false;
+  // rule pair (ResNetEncoder::set_rules): the one-chain backward matrix of a rule that does not walk on w_b — the full w of the
+  // epsilon kinds; the stem: w, 1 or w^2 in the T+ rows, those two in split8 form as well.  Neither exists before the first such rule
+  DevBuf w_r, w_rs;
+  bool rule_packed = false;
   size_t out_elems() const { return (size_t)Hout * Wout * cout; }
   size_t in_elems() const { return (size_t)Hin * Win * cin; }
 };
@@ -79,7 +87,7 @@ struct ResNetEncoder {
   // (t * C1 of the first block), so multiplying by the relu-unit gate a0*Q would count a0 twice
   DevBuf q_stem;
   DevBuf pool_win;                 // winner of every 3x3/2 pool window (one byte)
-  const void* stem_attr_set[4] = {};   // the rn_stem_reverse_kernel instantiations whose LDS attribute is set (stem_lds_attr)
+  const void* stem_attr_set[8] = {};   // the rn_stem_reverse_kernel instantiations whose LDS attribute is set (stem_lds_attr)
   DevBuf fa, fb, fc, fz, fsc;      // forward scratch
   DevBuf fxs;                      // a unit's input as scaled fp16 pairs (fp16-pair forward)
   DevBuf f16_slots;                // scratch maxima of make_f16_operand
@@ -216,6 +224,7 @@ struct ResNetEncoder {
       u.have[s] = true;
       u.grad_ok = false;
       u.ab_packed = false;
+      u.rule_packed = false;
       norms_ready = false;
       encoded = 0;                                       // caches belong to the old weights
       return LRP_OK;
@@ -286,9 +295,29 @@ struct ResNetEncoder {
   // bias, hence two gates Bn / safe(Za) and Bn / safe(Zi); the walk carries [S_a | S_i] as one tensor and every transposed conv is
   // ONE GEMM over both chains against [alpha w+ ; -beta w-] (explain_ab).  beta = 0 (the default) is the alpha1beta0 walk:
   // nothing here is allocated, launched or read, and what the (1, 0) walk reads is written by the same launches either way.
-  float ab_alpha = 1.f, ab_beta = 0.f;
-  bool ab_on() const { return ab_beta > 0.f; }
+  // The handle's rule is a PAIR (lrp_set_resnet_rules): one record for the stem conv, one for every conv above it.
+  // lrp_set_cnn_rule(alpha, beta) is the pair with that alpha-beta-with-bias record twice (one_rule()): the walk above, made by
+  // the launches above.  Every other pair leaves the forward as it is and makes its gates behind it (rule_gates).
+  struct Rule {
+    int kind = LRP_RULE_ALPHA_BETA, bias = 1;
+    float alpha = 1.f, beta = 0.f, eps = 0.f, low = 0.f, high = 0.f;
+    int chains() const { return kind == LRP_RULE_ALPHA_BETA && beta > 0.f ? 2 : 1; }
+    bool input_only() const { return kind == LRP_RULE_FLAT || kind == LRP_RULE_WSQUARE || kind == LRP_RULE_BOUNDED; }
+    bool on_default_matrix() const { return (kind == LRP_RULE_ALPHA_BETA && beta == 0.f) || kind == LRP_RULE_BOUNDED; }   // w_b / w_bs
+    bool same(const Rule& o) const {
+      return kind == o.kind && bias == o.bias && alpha == o.alpha && beta == o.beta && eps == o.eps && low == o.low && high == o.high;
+    }
+  };
+  Rule rule_stem, rule_units;
+  const Rule& rule_of(const RnUnit& u) const { return u.k == 7 ? rule_stem : rule_units; }
+  bool one_rule() const {
+    return rule_stem.kind == LRP_RULE_ALPHA_BETA && rule_stem.bias && rule_stem.same(rule_units);
+  }
+  bool ab_on() const { return one_rule() && rule_units.beta > 0.f; }      // the second gates ride on the forward's own launches
+  bool two_chains() const { return rule_stem.chains() == 2 || rule_units.chains() == 2; }
+  bool has_eps() const { return rule_stem.kind == LRP_RULE_EPSILON || rule_units.kind == LRP_RULE_EPSILON; }
   DevBuf q_stem_i;
+  DevBuf stem_dconst;      // the stem's constant denominator per channel (flat, w-square, bounded: rn_stem_rule_consts_kernel)
   // the dual-gate epilogue works on whole split8 groups of either chain (conv_plan: Cin % 16 == 0 over both chains)
   bool ab_supported() const {
     if (stem_c & 7) return false;
@@ -296,73 +325,118 @@ struct ResNetEncoder {
       if (b.f & 7) return false;
     return true;
   }
-  int set_rule(float alpha, float beta) {
-    if (alpha == ab_alpha && beta == ab_beta) return LRP_OK;
-    if (beta > 0.f) {
-      if (!ab_supported())
-        return fail(LRP_ERR_UNSUPPORTED, "alpha-beta with beta > 0 on a ResNet encoder needs a stem width and stack widths that are multiples of 8");
-      const size_t B = max_images, NT = max_tokens;      // (every buffer below appears, or grows, with the first rule that needs it)
-      for (RnUnit& u : units) {
+  // both records are validated (engine.hip).  Every buffer appears, or grows, with the first pair that needs it, and stays (idle)
+  // under a later pair that does not
+  int set_rules(const Rule& rs, const Rule& ru) {
+    if (rs.same(rule_stem) && ru.same(rule_units)) return LRP_OK;
+    if ((rs.chains() == 2 || ru.chains() == 2) && !ab_supported())
+      return fail(LRP_ERR_UNSUPPORTED, "alpha-beta with beta > 0 on a ResNet encoder needs a stem width and stack widths that are multiples of 8");
+    const size_t B = max_images, NT = max_tokens;
+    const size_t stem_hw = (size_t)(img_h / 2) * (img_w / 2);
+    const bool on_fwd = rs.kind == LRP_RULE_ALPHA_BETA && rs.bias && rs.same(ru);      // one_rule() of the new pair
+    for (RnUnit& u : units) {
+      const Rule& r = u.k == 7 ? rs : ru;
+      const int taps = u.k * u.k;
+      if (r.chains() == 2) {
         if (u.k == 7) {                                  // (the stem's second gate is q_stem_i)
           LRP_TRY(reserve(u.w_n, (size_t)conv_npad(u.cout) * 2 * RN_STEM_K));
           const size_t nb = (size_t)conv_npad(RN_STEM_TCOLS) * conv_cinp(2 * u.cout);
           LRP_TRY(reserve(u.w_ab, nb)); LRP_TRY(reserve(u.w_abs, nb));
-          continue;
+        } else {
+          LRP_TRY(reserve(u.gate_i, B * u.out_elems()));
+          LRP_TRY(reserve(u.w_n, (size_t)conv_npad(u.cout) * taps * conv_cinp(u.cin)));
+          if (on_fwd && u.dual_il && u.w_dual_h.p) LRP_TRY(reserve(u.w_dualn_h, (size_t)conv_npad(2 * u.cout) * taps * conv_cinp(u.cin)));
+          const size_t nb = (size_t)conv_npad(u.cin) * taps * conv_cinp(2 * u.cout);
+          LRP_TRY(reserve(u.w_ab, nb)); LRP_TRY(reserve(u.w_abs, nb));
         }
-        const int taps = u.k * u.k;
-        LRP_TRY(reserve(u.gate_i, B * u.out_elems()));
-        LRP_TRY(reserve(u.w_n, (size_t)conv_npad(u.cout) * taps * conv_cinp(u.cin)));
-        if (u.dual_il && u.w_dual_h.p) LRP_TRY(reserve(u.w_dualn_h, (size_t)conv_npad(2 * u.cout) * taps * conv_cinp(u.cin)));
-        const size_t nb = (size_t)conv_npad(u.cin) * taps * conv_cinp(2 * u.cout);
-        LRP_TRY(reserve(u.w_ab, nb)); LRP_TRY(reserve(u.w_abs, nb));
+      } else if (!r.on_default_matrix()) {
+        const size_t nb = u.k == 7 ? (size_t)conv_npad(RN_STEM_TCOLS) * conv_cinp(u.cout) : (size_t)conv_npad(u.cin) * taps * conv_cinp(u.cout);
+        LRP_TRY(reserve(u.w_r, nb));
+        // (split8 serves the bf16x3 walk, which no epsilon kind takes: flat and w-square at the stem alone)
+        if (r.kind != LRP_RULE_EPSILON && !(u.cout & 7)) LRP_TRY(reserve(u.w_rs, nb));
       }
+    }
+    if (ru.chains() == 2)
       for (RnBlock& b : blocks) {
         const size_t ne = B * (size_t)b.H * b.W * 4 * b.f;
         LRP_TRY(reserve(b.GA_i, ne));
         if (b.u0 >= 0) LRP_TRY(reserve(b.GS_i, ne));
       }
-      const size_t stem_hw = (size_t)(img_h / 2) * (img_w / 2);
-      LRP_TRY(reserve(q_stem_i, B * stem_hw * stem_c));
+    if (rs.chains() == 2) LRP_TRY(reserve(q_stem_i, B * stem_hw * stem_c));
+    if (rs.input_only()) LRP_TRY(reserve(stem_dconst, (size_t)stem_c));
+    if (rs.chains() == 2 || ru.chains() == 2) {
       // the per-token scratch of the tensors that carry two chains (S3 / S0, S2, S1, the pool routing's output)
       size_t max_act = stem_hw * stem_c;
       for (const RnUnit& u : units) max_act = std::max(max_act, std::max(u.out_elems(), u.in_elems()));
       const size_t tok2 = std::max(2 * max_act, stem_hw * (size_t)RN_STEM_TCOLS);
       for (DevBuf* d : {&r1, &r2, &r3, &r5}) LRP_TRY(reserve(*d, NT * tok2));
     }
-    // (beta = 0 again: the buffers stay, idle)
-    ab_alpha = alpha; ab_beta = beta;
-    for (RnUnit& u : units) u.ab_packed = false;
-    encoded = 0;                                         // the caches belong to the old rule
+    rule_stem = rs; rule_units = ru;
+    for (RnUnit& u : units) { u.ab_packed = false; u.rule_packed = false; }
+    encoded = 0;                                         // the caches belong to the old pair
     return LRP_OK;
   }
-  // the rule's matrices of every unit whose weights or rule changed since its last packing, from the resident forward matrix w_a
+  int set_rule(float alpha, float beta) {                // lrp_set_cnn_rule: the record with the bias, twice
+    Rule r;
+    r.alpha = alpha; r.beta = beta;
+    return set_rules(r, r);
+  }
+  // the pair's matrices of every unit whose weights or rule changed since its last packing, from the resident forward matrix w_a
   int ensure_ab_weights(hipStream_t st) {
     for (RnUnit& u : units) {
-      if (u.ab_packed) continue;
+      const Rule& r = rule_of(u);
+      if (u.ab_packed || r.chains() != 2) continue;
       // a weight set after the rule may have changed which forward path the unit takes
-      if (u.k != 7 && u.dual_il && u.w_dual_h.p)
+      if (ab_on() && u.k != 7 && u.dual_il && u.w_dual_h.p)
         LRP_TRY(reserve(u.w_dualn_h, (size_t)conv_npad(2 * u.cout) * u.k * u.k * conv_cinp(u.cin)));
       if (u.k == 7) {
         const int Np = conv_npad(u.cout), Npb = conv_npad(RN_STEM_TCOLS), Kb2 = conv_cinp(2 * u.cout);
         const size_t nf = (size_t)Np * 2 * RN_STEM_K, nb = (size_t)Npb * Kb2;
         hipLaunchKernelGGL(rn_pack_stem_ab_kernel, dim3(stream_grid(nf + nb)), dim3(256), 0, st, u.w_a.as<float>(), u.w_n.as<float>(),
-                           u.w_ab.as<float>(), u.cout, Np, Npb, Kb2, ab_alpha, ab_beta);
+                           u.w_ab.as<float>(), u.cout, Np, Npb, Kb2, r.alpha, r.beta);
         split_copy(u.w_ab.as<float>(), u.w_abs.as<float>(), nb, st);
       } else {
         const int taps = u.k * u.k, CPi = conv_cinp(u.cin), CP2 = conv_cinp(2 * u.cout), rows = conv_npad(u.cin);
         const size_t nf = (size_t)conv_npad(u.cout) * taps * CPi, nb = (size_t)rows * taps * CP2;
         hipLaunchKernelGGL(rn_pack_neg_kernel, dim3(stream_grid(nf)), dim3(256), 0, st, u.w_a.as<float>(), u.w_n.as<float>(), nf);
-        if (u.w_dualn_h.p) {
+        if (ab_on() && u.w_dualn_h.p) {
           const int Nd = conv_npad(2 * u.cout);
           hipLaunchKernelGGL(rn_pack_dual_neg_h_kernel, dim3(stream_grid((size_t)Nd * taps * CPi / 8)), dim3(256), 0, st, u.w_a.as<float>(),
                              u.w_dualn_h.as<float>(), taps * CPi, Nd, u.wds.as<float>());
         }
         hipLaunchKernelGGL(rn_pack_ab_kernel, dim3(stream_grid(nb)), dim3(256), 0, st, u.w_a.as<float>(), u.w_ab.as<float>(), taps, u.cin,
-                           u.cout, CPi, CP2, rows, ab_alpha, ab_beta);
+                           u.cout, CPi, CP2, rows, r.alpha, r.beta);
         split_copy(u.w_ab.as<float>(), u.w_abs.as<float>(), nb, st);
       }
       LRP_HIP_CHECK(hipGetLastError());
       u.ab_packed = true;
+    }
+    return LRP_OK;
+  }
+  // ... and the one-chain matrices of the records that do not walk on w_b (w_r / w_rs), and the stem's constant denominator
+  int ensure_rule_weights(hipStream_t st) {
+    for (RnUnit& u : units) {
+      const Rule& r = rule_of(u);
+      if (u.rule_packed) continue;
+      if (u.k == 7 && r.input_only())
+        hipLaunchKernelGGL(rn_stem_rule_consts_kernel, dim3((u.cout + 255) / 256), dim3(256), 0, st, u.w_a.as<float>(), stem_dconst.as<float>(),
+                           u.cout, r.kind, r.low, r.high);
+      if (r.chains() == 1 && !r.on_default_matrix()) {
+        if (u.k == 7) {
+          const int Npb = conv_npad(RN_STEM_TCOLS), Kb = conv_cinp(u.cout);
+          const size_t nb = (size_t)Npb * Kb;
+          hipLaunchKernelGGL(rn_pack_stem_rule_kernel, dim3(stream_grid(nb)), dim3(256), 0, st, u.w_a.as<float>(), u.w_r.as<float>(), u.cout,
+                             Npb, Kb, r.kind);
+          if (r.kind != LRP_RULE_EPSILON && u.w_rs.p) split_copy(u.w_r.as<float>(), u.w_rs.as<float>(), nb, st);
+        } else {
+          const int taps = u.k * u.k, CPi = conv_cinp(u.cin), CPo = conv_cinp(u.cout), rows = conv_npad(u.cin);
+          const size_t nb = (size_t)rows * taps * CPo;
+          hipLaunchKernelGGL(rn_pack_pq_kernel, dim3(stream_grid(nb)), dim3(256), 0, st, u.w_a.as<float>(), u.w_r.as<float>(), taps, u.cin,
+                             u.cout, CPi, CPo, rows, 1.f, 1.f);       // (p, q) = (1, 1): the full w
+        }
+      }
+      LRP_HIP_CHECK(hipGetLastError());
+      u.rule_packed = true;
     }
     return LRP_OK;
   }
@@ -519,15 +593,20 @@ struct ResNetEncoder {
   }
   // the stem's forward up to its BatchNorm, for both paths: im2col -> two 1-tap GEMMs on the fp32 MFMA, c (exact) into fa and Z
   // (both sign branches) into fz.  cz: the Z launch, which unit_gate_inh runs once more against w_n under beta > 0
+  ConvArgs stem_fwd_args(int B) const {                  // a 1-tap GEMM over the im2col rows in stemA
+    const RnUnit& s = units[0];
+    ConvArgs cz{};
+    cz.in = stemA.as<float>(); cz.NB = B * s.Hout * s.Wout; cz.H = 1; cz.W = 1; cz.Cin = 2 * RN_STEM_K; cz.CinP = 2 * RN_STEM_K;
+    cz.taps = 1; cz.N = s.cout; cz.bias = s.bias.as<float>();
+    return cz;
+  }
   int stem_forward(int B, ConvArgs& cz, hipStream_t st) {
     const RnUnit& s = units[0];
     const size_t tot = (size_t)B * s.Hout * s.Wout * 2 * RN_STEM_K;
     hipLaunchKernelGGL(rn_stem_im2col_kernel, dim3(stream_grid(tot)), dim3(256), 0, st, images.as<float>(),
                        stemA.as<float>(), B, img_h, img_w);
     LRP_HIP_CHECK(hipGetLastError());
-    cz = ConvArgs{};
-    cz.in = stemA.as<float>(); cz.NB = B * s.Hout * s.Wout; cz.H = 1; cz.W = 1; cz.Cin = 2 * RN_STEM_K; cz.CinP = 2 * RN_STEM_K;
-    cz.taps = 1; cz.N = s.cout; cz.bias = s.bias.as<float>();
+    cz = stem_fwd_args(B);
     cz.wpk = s.w_a.as<float>(); cz.out = fa.as<float>();
     LRP_HIP_CHECK(conv_launch(EPI_BIAS, cz, st));
     cz.wpk = s.w_z.as<float>(); cz.out = fz.as<float>();
@@ -616,11 +695,13 @@ struct ResNetEncoder {
   int encode(const float* images_dev, int B, hipStream_t st) {
     if (B < 1 || B > max_images) return fail(LRP_ERR_INVALID, "B=%d outside [1,%d]", B, max_images);
     LRP_TRY(check_ready());
-    if (ab_on()) LRP_TRY(ensure_ab_weights(st));
+    if (two_chains()) LRP_TRY(ensure_ab_weights(st));
+    if (!one_rule()) LRP_TRY(ensure_rule_weights(st));
     LRP_HIP_CHECK(hipMemcpyAsync(images.p, images_dev, (size_t)B * img_h * img_w * 3 * 4, hipMemcpyDeviceToDevice, st));
     masks_ok = false;
     if (emit_ok()) LRP_TRY(encode_emit(B, st));
     else LRP_TRY(encode_fp32_acts(B, st));               // (sets masks_ok in LRP_PREC_FP32 mode)
+    if (!one_rule()) LRP_TRY(rule_gates(B, st));         // the pair's gates, behind the unchanged forward
     encoded = B;
     features_only = false;
     return LRP_OK;
@@ -681,6 +762,80 @@ struct ResNetEncoder {
     return LRP_OK;
   }
 
+  // ---- the gates of a rule pair that is not the one-rule entry's (set_rules) ----
+  // Behind the forward of either path, which is left exactly as it is (features, the default gates and every cache of the gradient
+  // walks), the gates the walk reads are brought under the pair's denominators: the units' gate (and gate_i), the blocks' GA and a
+  // projection's GS (and GA_i / GS_i), the stem's q_stem (and q_stem_i).  What the forward kept suffices as input: the stem's im2col
+  // rows and every block input t_in / t_sub in fp32.  Per unit c = conv(x, w) + b, Za and (beta > 0) Zi are fp32 launches of the
+  // unit's conv (EPI_BIAS: the dual_il units of the forward never write c or Z+), then ONE kernel per gate.
+  // Above the stem a gate is the FORWARD's gate times safe(Za) / D — the forward's denominator over the rule's, BatchNorm's factor
+  // untouched — never Bn / D made anew: the forward's gates, GA and GS are consistent with the block inputs it wrote (o = sc + y3,
+  // fA + fS = 1, y cancelling in y Bn), and where sc + y3 or y is small a y3 in another arithmetic (the fp16-pair forward against
+  // this pass's fp32) breaks that by O(y3 / o) rounding errors; the ratio of two denominators is well conditioned.  So GA takes
+  // unit 3's ratio, a projection's GS unit 0's, an identity block's GS stays.  The stem's c is the forward's own launch again, bit
+  // for bit: its gate is made directly.  The forward's scratch is free by now: fc = c, fz = Za, fxs = Zi, fa = a1, fb = a2.
+  int rule_gate(const RnUnit& u, const Rule& r, const float* Z, const float* src, float* act, float* gate, int den, int B, int relu,
+                hipStream_t st) {
+    const size_t n = (size_t)B * u.out_elems();
+    hipLaunchKernelGGL(rn_rule_gate_kernel, dim3(stream_grid(n / 4)), dim3(256), 0, st, fc.as<float>(), Z, fz.as<float>(), u.bias.as<float>(),
+                       stem_dconst.as<float>(), u.gamma.as<float>(), u.beta.as<float>(), u.mean.as<float>(), u.var.as<float>(), RN_BN_EPS, src,
+                       act, gate, n, u.cout, relu, den, r.bias ? 0 : 1, r.eps);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  }
+  // the stem: its forward's launches again (stem_fwd_args), q_stem (and q_stem_i) = Bn / D
+  int rule_stem_gates(int B, hipStream_t st) {
+    const RnUnit& s = units[0];
+    const Rule& r = rule_stem;
+    ConvArgs ca = stem_fwd_args(B);
+    ca.wpk = s.w_a.as<float>(); ca.out = fc.as<float>();
+    LRP_HIP_CHECK(conv_launch(EPI_BIAS, ca, st));
+    if (r.kind != LRP_RULE_ALPHA_BETA) {
+      const int den = r.kind == LRP_RULE_EPSILON ? 1 : r.kind == LRP_RULE_BOUNDED ? 3 : 2;
+      return rule_gate(s, r, nullptr, nullptr, nullptr, q_stem.as<float>(), den, B, 0, st);
+    }
+    ca.wpk = s.w_z.as<float>(); ca.out = fz.as<float>();
+    LRP_HIP_CHECK(conv_launch(EPI_BIAS, ca, st));
+    LRP_TRY(rule_gate(s, r, fz.as<float>(), nullptr, nullptr, q_stem.as<float>(), 0, B, 0, st));
+    if (r.beta > 0.f) {
+      ca.wpk = s.w_n.as<float>(); ca.out = fxs.as<float>();
+      LRP_HIP_CHECK(conv_launch(EPI_BIAS, ca, st));
+      LRP_TRY(rule_gate(s, r, fxs.as<float>(), nullptr, nullptr, q_stem_i.as<float>(), 0, B, 0, st));
+    }
+    return LRP_OK;
+  }
+  // one unit above the stem: `ca` is its forward launch on fp32 operands (fwd_args).  g: the forward's tensor that carries the
+  // unit's denominator (gate of a relu unit, GA / GS of a pre-Add unit), scaled in place; g_i (beta > 0): where the inhibitor's
+  // goes, made from g first.  act = relu(BN(c)), the next unit's input (nullptr: not wanted)
+  int rule_unit(const RnUnit& u, const Rule& r, ConvArgs ca, float* act, float* g, float* g_i, int B, hipStream_t st) {
+    ca.wpk = u.w_a.as<float>(); ca.out = fc.as<float>();
+    LRP_HIP_CHECK(conv_launch(EPI_BIAS, ca, st));
+    ca.wpk = u.w_z.as<float>(); ca.out = fz.as<float>();
+    LRP_HIP_CHECK(conv_launch(EPI_BIAS, ca, st));
+    if (r.chains() == 2) {
+      ca.wpk = u.w_n.as<float>(); ca.out = fxs.as<float>();
+      LRP_HIP_CHECK(conv_launch(EPI_BIAS, ca, st));
+      LRP_TRY(rule_gate(u, r, fxs.as<float>(), g, act, g_i, 0, B, 1, st));
+      act = nullptr;
+      if (r.bias) return LRP_OK;                         // (the activator's gate is the forward's)
+    }
+    return rule_gate(u, r, fz.as<float>(), g, act, g, r.kind == LRP_RULE_EPSILON ? 1 : 0, B, 1, st);
+  }
+  int rule_gates(int B, hipStream_t st) {
+    const Rule &rs = rule_stem, &ru = rule_units;
+    if (!(rs.kind == LRP_RULE_ALPHA_BETA && rs.bias && rs.beta == 0.f)) LRP_TRY(rule_stem_gates(B, st));      // (that record's q_stem is the forward's)
+    if (ru.kind == LRP_RULE_ALPHA_BETA && ru.bias && ru.beta == 0.f) return LRP_OK;      // (... and so are the units' gates)
+    for (RnBlock& b : blocks) {
+      RnUnit &u1 = units[b.u1], &u2 = units[b.u2], &u3 = units[b.u3];
+      const float* tin = b.stride == 2 ? b.t_sub.as<float>() : b.t_in.as<float>();
+      if (b.u0 >= 0) LRP_TRY(rule_unit(units[b.u0], ru, fwd_args(units[b.u0], tin, B), nullptr, b.GS.as<float>(), b.GS_i.as<float>(), B, st));
+      LRP_TRY(rule_unit(u1, ru, fwd_args(u1, tin, B), fa.as<float>(), u1.gate.as<float>(), u1.gate_i.as<float>(), B, st));            // a1
+      LRP_TRY(rule_unit(u2, ru, fwd_args(u2, fa.as<float>(), B), fb.as<float>(), u2.gate.as<float>(), u2.gate_i.as<float>(), B, st)); // a2
+      LRP_TRY(rule_unit(u3, ru, fwd_args(u3, fb.as<float>(), B), nullptr, b.GA.as<float>(), b.GA_i.as<float>(), B, st));
+    }
+    return LRP_OK;
+  }
+
   // the transposed conv through unit u, every walk's: S [n][Hout][Wout][chains * cout] -> out [n][Hout][Wout][cin].  The callers
   // add the matrix (w_b / w_bs, w_ab / w_abs over two chains, w_g), the gates and the epilogue
   static ConvArgs bwd_args(const RnUnit& u, int n, const int* row2img, const float* S, float* out, int chains = 1) {
@@ -702,7 +857,8 @@ struct ResNetEncoder {
                     bool split = false, bool plain_out = true, const BlockTail* tail = nullptr) {
     ConvArgs ca = bwd_args(u, n, row2img, S, out);
     if (tail) { ca.join = tail->join; ca.join_gate = tail->join_gate; ca.gate2 = tail->gate2; ca.out2s = tail->out2; }
-    ca.wpk = split ? u.w_bs.as<float>() : u.w_b.as<float>(); ca.aux = aux; ca.out_plain = plain_out ? 1 : 0;
+    const bool own = !rule_units.on_default_matrix();    // (an epsilon kind: the full w, exact fp32 only)
+    ca.wpk = own ? u.w_r.as<float>() : split ? u.w_bs.as<float>() : u.w_b.as<float>(); ca.aux = aux; ca.out_plain = plain_out ? 1 : 0;
     prof.begin(st);
     LRP_HIP_CHECK(conv_launch(EPI_MUL, ca, st, split ? PREC_BF16X3 : PREC_FP32));
     prof.end(st, bwd_flop(u, n));
@@ -713,10 +869,16 @@ struct ResNetEncoder {
     if (n < 1 || n > max_tokens) return fail(LRP_ERR_INVALID, "n=%d outside [1,%d]", n, max_tokens);
     if (encoded < 1 || features_only) return fail(LRP_ERR_STATE, "lrp_encode_images must run before the CNN explain");
     if (walk != LRP_WALK_LRP) return explain_grad(n, row2img, R_feat_dev, R_img_dev, st, walk);
-    if (ab_on()) {                                       // every launch is asked about before the first runs
+    // epsilon kinds are exact-fp32 only (their gate is a step in the activation for small eps, and a ReLU decision
+    // the fp16-pair forward takes differently moves the map by O(1))
+    if (has_eps() && prec != PREC_FP32)
+      return fail(LRP_ERR_UNSUPPORTED, "a rule pair with an epsilon kind runs in LRP_PREC_FP32 only: set it with lrp_set_precision "
+                                       "and call lrp_encode_images again");
+    if (rule_units.chains() == 2) {                      // every launch is asked about before the first runs
       LRP_TRY(explain_ab(n, row2img, R_feat_dev, R_img_dev, st, true));
       return explain_ab(n, row2img, R_feat_dev, R_img_dev, st, false);
     }
+    if (!one_rule()) LRP_TRY(stem_end(nullptr, n, row2img, R_img_dev, st, true));      // (the convs above are the default walk's launches)
     const float* Ro = R_feat_dev;          // relevance at the current block's output
     float* cur = r0.as<float>();           // where the next R_t is written (ping-pong r0 / r4)
     float* other = r4.as<float>();
@@ -801,33 +963,18 @@ struct ResNetEncoder {
       Ro = cur;
       std::swap(cur, other);
     }
-    // stem: pool routing * Q_stem -> T = S . W (K = stem_c, N = 294) -> 7x7/2 stencil with the x+/x- selection
-    const RnUnit& s = units[0];
-    const size_t tot = (size_t)n * s.Hout * s.Wout * s.cout;
-    // the stem's tap GEMM (K = stem channels -> 49 taps x 6 columns) as bf16x3 like the other convs of the walk: the pool
-    // routing writes its operand in split8 form (fp32 mode: plain fp32 on the fp32 MFMA)
-    const bool ssplit = prec == PREC_BF16X3 && s.w_bs.p && !(s.cout & 7);
-    if (ssplit)
-      hipLaunchKernelGGL(rn_pool3_route_kernel<true>, dim3(stream_grid(tot / 8)), dim3(256), 0, st, Ro, pool_win.as<unsigned char>(),
-                         q_stem.as<float>(), row2img, r1.as<float>(), n, s.Hout, s.Wout, s.cout);
-    else
-      hipLaunchKernelGGL(rn_pool3_route_kernel<false>, dim3(stream_grid(tot / 4)), dim3(256), 0, st, Ro, pool_win.as<unsigned char>(),
-                         q_stem.as<float>(), row2img, r1.as<float>(), n, s.Hout, s.Wout, s.cout);
-    LRP_HIP_CHECK(hipGetLastError());
-    const StemEnd lrp_end{ssplit ? &rn_stem_reverse_kernel<true> : &rn_stem_reverse_kernel<false>, &rn_stem_stencil_kernel<0>};
-    return stem_reverse(ssplit ? s.w_bs.as<float>() : s.w_b.as<float>(), ssplit ? PREC_BF16X3 : PREC_FP32, s.cout, lrp_end, n, row2img,
-                        R_img_dev, st);
+    return stem_end(Ro, n, row2img, R_img_dev, st, false);
   }
 
   // ---- the stem conv's reverse, every walk's ----
   // r1 holds the operand S [n][Hout][Wout][K]: K = stem_c, or 2 stem_c where it carries two chains.  T = S . W over the 49 taps x 6
-  // columns (w: w_b / w_bs, w_ab / w_abs, w_g; rp: PREC_FP32, or PREC_BF16X3 for an operand and a matrix in split8 form), then
+  // columns (w: w_b / w_bs, w_ab / w_abs, w_r / w_rs, w_g; rp: PREC_FP32, or PREC_BF16X3 for an operand and a matrix in split8 form), then
   // the 7x7 / stride-2 shift-and-add into the image.  (The kernels lie in the code object in the order the callers name them.)
   // The image end is the caller's: the instantiations of one MODE (resnet_kernels.h: 0 = LRP, x+ . T+ + x- . T-;  1 = T+, a
-  // gradient;  2 = x . T+) — the stencil and the one-launch form for this operand (SPLIT = split8; nullptr: there is none)
+  // gradient, flat, w-square;  2 = x . T+;  3 = (x - low) . T+ + (x - high) . T-) — the stencil and the one-launch form for this operand (SPLIT = split8; nullptr: there is none)
   struct StemEnd {
-    void (*fused)(const float*, const float*, const float*, const int*, float*, int, int, int, int);
-    void (*stencil)(const float*, const float*, const int*, float*, int, int, int);
+    void (*fused)(const float*, const float*, const float*, const int*, float*, int, int, int, int, float, float);
+    void (*stencil)(const float*, const float*, const int*, float*, int, int, int, float, float);
   };
   // the tap GEMM alone (explain_ab's dry run asks conv_plan about it)
   ConvArgs stem_tap_args(const float* w, int K, int n) const {
@@ -848,7 +995,9 @@ struct ResNetEncoder {
     }
     return fail(LRP_ERR_STATE, "stem_lds_attr: more instantiations of rn_stem_reverse_kernel than slots");
   }
-  int stem_reverse(const float* w, int rp, int K, const StemEnd& end, int n, const int* row2img, float* R_img_dev, hipStream_t st) {
+  // low, high: the BoundedRule's scalars (MODE 3 alone reads them)
+  int stem_reverse(const float* w, int rp, int K, const StemEnd& end, int n, const int* row2img, float* R_img_dev, hipStream_t st,
+                   float low = 0.f, float high = 0.f) {
     const RnUnit& s = units[0];
     // T = S . W and the shift-and-add in ONE launch, T never leaves LDS (resnet_kernels.h rn_stem_reverse_kernel): its K is fixed
     // at the 64 channels of one chain, so a two-chain operand (K = 2 stem_c) never takes it.  LRP_IMG_FUSED=0, and every other
@@ -858,13 +1007,13 @@ struct ResNetEncoder {
       LRP_TRY(stem_lds_attr(reinterpret_cast<const void*>(end.fused)));
       const int txs = (s.Wout + RN_ST - 1) / RN_ST, tys = (s.Hout + RN_ST - 1) / RN_ST;
       hipLaunchKernelGGL(end.fused, dim3((unsigned)(n * txs * tys)), dim3(512), RN_STEM_LDS, st, r1.as<float>(), w, images.as<float>(),
-                         row2img, R_img_dev, s.Hout, s.Wout, txs, tys);
+                         row2img, R_img_dev, s.Hout, s.Wout, txs, tys, low, high);
       LRP_HIP_CHECK(hipGetLastError());
       return LRP_OK;
     }
     LRP_HIP_CHECK(conv_launch(EPI_STORE, stem_tap_args(w, K, n), st, rp));
     hipLaunchKernelGGL(end.stencil, dim3(stream_grid((size_t)n * img_h * img_w)), dim3(256), 0, st, r2.as<float>(), images.as<float>(),
-                       row2img, R_img_dev, n, img_h, img_w);
+                       row2img, R_img_dev, n, img_h, img_w, low, high);
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   }
@@ -955,23 +1104,55 @@ struct ResNetEncoder {
       Ro = cur;
       std::swap(cur, other);
     }
-    // stem: two-gate pool routing -> T = [S_a | S_i] . [alpha (w+ | w-) ; -beta (w- | w+)] (K = 2 stem_c, N = 294) -> 7x7/2 stencil
+    return stem_end(Ro, n, row2img, R_img_dev, st, dry);
+  }
+
+  // ---- the stem end of both LRP walks, chosen by the stem record alone: what arrives at the pool's output is a plain relevance
+  // whatever the rule above it ----
+  //   two chains (alpha-beta, beta > 0): two-gate pool routing -> T = [S_a | S_i] . [alpha (w+ | w-) ; -beta (w- | w+)] (K = 2 stem_c,
+  //                N = 294) -> the 7x7/2 stencil with the x+ / x- selection
+  //   one chain:   pool routing * q_stem -> T = S . W (K = stem_c) -> the image end of the record's MODE, in one launch where
+  //                stem_reverse takes it.  W: w_b (alpha-beta, bounded) or w_r (epsilon, flat, w-square)
+  // the tap GEMM runs as bf16x3 like the other convs of the walk: the pool routing writes its operand in split8 form (fp32 mode, and
+  // a stem width that is no multiple of 8: plain fp32 on the fp32 MFMA).  dry: conv_plan is asked about the tap GEMM, nothing runs.
+  int stem_end(const float* Ro, int n, const int* row2img, float* R_img_dev, hipStream_t st, bool dry) {
     const RnUnit& s = units[0];
-    const float* wab = sp ? s.w_abs.as<float>() : s.w_ab.as<float>();
+    const Rule& r = rule_stem;
+    const bool two = r.chains() == 2, own = !two && !r.on_default_matrix();
+    const bool sp = prec == PREC_BF16X3 && !(s.cout & 7) && (two ? s.w_abs.p : own ? s.w_rs.p : s.w_bs.p) != nullptr;
+    const int rp = sp ? PREC_BF16X3 : PREC_FP32, K = two ? 2 * s.cout : s.cout;
+    const DevBuf& wm = two ? (sp ? s.w_abs : s.w_ab) : own ? (sp ? s.w_rs : s.w_r) : (sp ? s.w_bs : s.w_b);
     if (dry) {
-      if (!conv_plan(conv_ask(EPI_STORE, rp, 7, false, stem_tap_args(wab, 2 * s.cout, n))).ok)
-        return fail(LRP_ERR_UNSUPPORTED, "alpha-beta walk: no conv kernel for the stem's tap GEMM");
+      if (!conv_plan(conv_ask(EPI_STORE, rp, 7, false, stem_tap_args(wm.as<float>(), K, n))).ok)
+        return fail(LRP_ERR_UNSUPPORTED, "LRP walk: no conv kernel for the stem's tap GEMM (K=%d)", K);
       return LRP_OK;
     }
     const size_t tot = (size_t)n * s.Hout * s.Wout * s.cout;
-    if (sp)
-      hipLaunchKernelGGL(rn_pool3_route2_kernel<true>, dim3(stream_grid(tot / 8)), dim3(256), 0, st, Ro, pool_win.as<unsigned char>(),
-                         q_stem.as<float>(), q_stem_i.as<float>(), row2img, r1.as<float>(), n, s.Hout, s.Wout, s.cout);
+    const unsigned char* win = pool_win.as<unsigned char>();
+    const float *qa = q_stem.as<float>(), *qi = q_stem_i.as<float>();
+    float* S = r1.as<float>();
+    if (two && sp)
+      hipLaunchKernelGGL(rn_pool3_route2_kernel<true>, dim3(stream_grid(tot / 8)), dim3(256), 0, st, Ro, win, qa, qi, row2img, S, n, s.Hout,
+                         s.Wout, s.cout);
+    else if (two)
+      hipLaunchKernelGGL(rn_pool3_route2_kernel<false>, dim3(stream_grid(tot / 4)), dim3(256), 0, st, Ro, win, qa, qi, row2img, S, n, s.Hout,
+                         s.Wout, s.cout);
+    else if (sp)
+      hipLaunchKernelGGL(rn_pool3_route_kernel<true>, dim3(stream_grid(tot / 8)), dim3(256), 0, st, Ro, win, qa, row2img, S, n, s.Hout, s.Wout,
+                         s.cout);
     else
-      hipLaunchKernelGGL(rn_pool3_route2_kernel<false>, dim3(stream_grid(tot / 4)), dim3(256), 0, st, Ro, pool_win.as<unsigned char>(),
-                         q_stem.as<float>(), q_stem_i.as<float>(), row2img, r1.as<float>(), n, s.Hout, s.Wout, s.cout);
+      hipLaunchKernelGGL(rn_pool3_route_kernel<false>, dim3(stream_grid(tot / 4)), dim3(256), 0, st, Ro, win, qa, row2img, S, n, s.Hout, s.Wout,
+                         s.cout);
     LRP_HIP_CHECK(hipGetLastError());
-    return stem_reverse(wab, rp, 2 * s.cout, StemEnd{nullptr, &rn_stem_stencil_kernel<0>}, n, row2img, R_img_dev, st);
+    StemEnd end{nullptr, &rn_stem_stencil_kernel<0>};
+    switch (two ? LRP_RULE_ALPHA_BETA : r.kind) {
+      case LRP_RULE_EPSILON: end = {sp ? &rn_stem_reverse_kernel<true, 2> : &rn_stem_reverse_kernel<false, 2>, &rn_stem_stencil_kernel<2>}; break;
+      case LRP_RULE_FLAT:
+      case LRP_RULE_WSQUARE: end = {sp ? &rn_stem_reverse_kernel<true, 1> : &rn_stem_reverse_kernel<false, 1>, &rn_stem_stencil_kernel<1>}; break;
+      case LRP_RULE_BOUNDED: end = {sp ? &rn_stem_reverse_kernel<true, 3> : &rn_stem_reverse_kernel<false, 3>, &rn_stem_stencil_kernel<3>}; break;
+      default: if (!two) end.fused = sp ? &rn_stem_reverse_kernel<true> : &rn_stem_reverse_kernel<false>;
+    }
+    return stem_reverse(wm.as<float>(), rp, K, end, n, row2img, R_img_dev, st, r.low, r.high);
   }
 
   // ---- gradient walks (lrp_cnn_walk: LRP_WALK_GRADIENT / _INPUT_X_GRADIENT / _GUIDED_BACKPROP) -------------------------------

@@ -547,11 +547,13 @@ constexpr int RN_SROW = 68;                                   // LDS row pitch o
 constexpr int RN_STS = 61;                                    // ... of the T tile (60 columns used; odd: the stencil's column reads spread over the banks)
 constexpr int RN_STEM_LDS = (64 * RN_SROW + 256 * RN_STS) * 4;   // 79.9 KB: two workgroups per CU
 // MODE (the image end, like the VGG image layer's img_mode): 0 = LRP, x+ . T+ + x- . T-;  1 = T+ (a gradient: the weights are
-// packed W s into both halves, rn_pack_stem_grad_kernel);  2 = x . T+ (Input x Gradient)
+// packed W s into both halves, rn_pack_stem_grad_kernel; FlatRule / WSquareRule);  2 = x . T+ (Input x Gradient; EpsilonRule);
+// 3 = (x - low) . T+ + (x - high) . T- (BoundedRule; low / high are read by this mode alone)
 template <bool SPLIT, int MODE = 0>
 __global__ __launch_bounds__(512, 2) void rn_stem_reverse_kernel(const float* __restrict__ S, const float* __restrict__ Wb,
                                                                  const float* __restrict__ ximg, const int* __restrict__ row2img,
-                                                                 float* __restrict__ out, int Ho, int Wo, int tiles_x, int tiles_y) {
+                                                                 float* __restrict__ out, int Ho, int Wo, int tiles_x, int tiles_y,
+                                                                 float low, float high) {
   extern __shared__ __attribute__((aligned(16))) float rn_smem[];
   float* Bs = rn_smem;                                        // [64 columns of this tap group][RN_SROW]
   float* Ts = Bs + 64 * RN_SROW;                              // [256][RN_STS]
@@ -676,6 +678,7 @@ __global__ __launch_bounds__(512, 2) void rn_stem_reverse_kernel(const float* __
     for (int c = 0; c < 3; ++c) {
       if constexpr (MODE == 1) ov[c] = pos[q][c];
       else if constexpr (MODE == 2) ov[c] = xv[c] * pos[q][c];
+      else if constexpr (MODE == 3) ov[c] = (xv[c] - low) * pos[q][c] + (xv[c] - high) * neg[q][c];
       else ov[c] = xv[c] >= 0.f ? xv[c] * pos[q][c] : xv[c] * neg[q][c];
     }
   }
@@ -684,7 +687,7 @@ __global__ __launch_bounds__(512, 2) void rn_stem_reverse_kernel(const float* __
 template <int MODE>                                       // as rn_stem_reverse_kernel
 __global__ __launch_bounds__(256) void rn_stem_stencil_kernel(const float* __restrict__ T, const float* __restrict__ ximg,
                                                               const int* __restrict__ row2img, float* __restrict__ out,
-                                                              int ntok, int H, int W) {
+                                                              int ntok, int H, int W, float low, float high) {
   const int Ho = H / 2, Wo = W / 2;
   const size_t total = (size_t)ntok * H * W;
   for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
@@ -710,6 +713,7 @@ __global__ __launch_bounds__(256) void rn_stem_stencil_kernel(const float* __res
     for (int c = 0; c < 3; ++c) {
       if constexpr (MODE == 1) o[c] = pos[c];
       else if constexpr (MODE == 2) o[c] = x[c] * pos[c];
+      else if constexpr (MODE == 3) o[c] = (x[c] - low) * pos[c] + (x[c] - high) * neg[c];
       else o[c] = x[c] >= 0.f ? x[c] * pos[c] : x[c] * neg[c];
     }
   }
@@ -1095,6 +1099,105 @@ __global__ __launch_bounds__(256) void rn_pack_stem_ab_kernel(const float* __res
       }
       wb[q] = v;
     }
+  }
+}
+
+// ---- the rule pair of the ResNet walk (lrp_set_resnet_rules; resnet_encoder.h rule_gates) --------------------------
+// One record for the stem conv, one for every conv above it.  Whatever the rule, relevance R at a unit's y = BN(c) reaches the
+// unit's input as m . convT(R Bn / D, M): the rule picks the denominator D (here), the matrix M (the packers below) and, at the
+// stem, the multiplier m (rn_stem_stencil_kernel's MODE).
+
+// The gate of a conv + BN unit under a rule, from c = conv(x, w) + b, with the rule's denominator D
+//   den 0  safe(Z - [nobias] b)                 alpha-beta: Z = Za or Zi, both made with the full bias
+//   den 1  stab_eps(c - [nobias] b, eps)        EpsilonRule; eps = 0: ZRule
+//   den 2  safe(dconst[ch])                     FlatRule (147) / WSquareRule (sum of w^2) at the stem: one value per channel
+//   den 3  safe((c - b) - dconst[ch])           BoundedRule at the stem: dconst = low sum(w+) + high sum(w-)
+// src == nullptr: rn_bn_unit_kernel's Q made anew, gate = Bn / D (relu != 0: relu(y) Bn / D).
+// src != nullptr: gate = src safe(Zref) / D — a tensor of the forward that carries 1 / safe(Zref), Zref = the forward's denominator
+//   Za, moved to the rule's denominator with everything else it holds left as the forward made it (src may be gate: in place).
+// act (optional): relu(y) (relu != 0) resp. y, the next unit's input.  4 channels per thread.
+__global__ __launch_bounds__(256) void rn_rule_gate_kernel(const float* __restrict__ c, const float* __restrict__ Z,
+                                                           const float* __restrict__ Zref, const float* __restrict__ bias,
+                                                           const float* __restrict__ dconst, const float* __restrict__ gamma,
+                                                           const float* __restrict__ beta, const float* __restrict__ mean,
+                                                           const float* __restrict__ var, float bn_eps, const float* src,
+                                                           float* __restrict__ act, float* gate, size_t n, int C, int relu, int den,
+                                                           int nobias, float eps) {
+  const size_t n4 = n / 4;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const int ch = (int)((i * 4) % C);
+    const f32x4 cv = reinterpret_cast<const f32x4*>(c)[i];
+    const f32x4 ga = *reinterpret_cast<const f32x4*>(gamma + ch), be = *reinterpret_cast<const f32x4*>(beta + ch);
+    const f32x4 mu = *reinterpret_cast<const f32x4*>(mean + ch), va = *reinterpret_cast<const f32x4*>(var + ch);
+    const f32x4 bi = *reinterpret_cast<const f32x4*>(bias + ch);
+    f32x4 zv = cv, sv = cv, zr = cv;
+    if (den == 0) zv = reinterpret_cast<const f32x4*>(Z)[i];
+    if (den >= 2) zv = *reinterpret_cast<const f32x4*>(dconst + ch);
+    if (src) { sv = reinterpret_cast<const f32x4*>(src)[i]; zr = reinterpret_cast<const f32x4*>(Zref)[i]; }
+    f32x4 g, a;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const float y = ga[q] * (cv[q] - mu[q]) / sqrtf(va[q] + bn_eps) + be[q];
+      const float b0 = nobias ? bi[q] : 0.f;
+      const float d = den == 0 ? safe_den(zv[q] - b0) : den == 1 ? stab_eps(cv[q] - b0, eps) : den == 2 ? safe_den(zv[q])
+                                                                                             : safe_den((cv[q] - bi[q]) - zv[q]);
+      a[q] = relu ? fmaxf(y, 0.f) : y;
+      if (src) g[q] = sv[q] * (safe_den(zr[q]) / d);
+      else {
+        const float qq = (cv[q] * (y - be[q])) / safe_den(stab_sign((cv[q] - mu[q]) * y)) / d;
+        g[q] = relu ? a[q] * qq : qq;
+      }
+    }
+    reinterpret_cast<f32x4*>(gate)[i] = g;
+    if (act) reinterpret_cast<f32x4*>(act)[i] = a;
+  }
+}
+
+// The stem's constant denominators, one per output channel, from its forward matrix w_a [Np][2 * RN_STEM_K] (w_a[co][t*3 + c]).
+// The stem is a valid conv over the explicitly padded image, so all 147 taps count at every output pixel:
+//   LRP_RULE_FLAT 147;  LRP_RULE_WSQUARE sum of w^2;  LRP_RULE_BOUNDED low sum(w+) + high sum(w-) (pad cells hold low / high too)
+__global__ __launch_bounds__(256) void rn_stem_rule_consts_kernel(const float* __restrict__ wa, float* __restrict__ dconst, int cout,
+                                                                  int kind, float low, float high) {
+  const int co = blockIdx.x * 256 + threadIdx.x;
+  if (co >= cout) return;
+  float s2 = 0.f, sp = 0.f, sn = 0.f;
+  for (int k = 0; k < 147; ++k) {
+    const float v = wa[(size_t)co * 2 * RN_STEM_K + k];
+    s2 += v * v;
+    if (v > 0.f) sp += v; else sn += v;
+  }
+  dconst[co] = kind == 2 ? 147.f : kind == 3 ? s2 : low * sp + high * sn;
+}
+
+// Backward matrix of a unit above the stem in w_b's layout (rn_pack_grad_kernel's index map), p w+ + q w-: (1, 0) is w_b, (1, 1)
+// the full w of the epsilon kinds
+__global__ __launch_bounds__(256) void rn_pack_pq_kernel(const float* __restrict__ wa, float* __restrict__ dst, int taps, int cin, int cout,
+                                                         int CPi, int CPo, int rows, float p, float q) {
+  const int K = taps * CPo;
+  const size_t total = (size_t)rows * K;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int ci = (int)(i / K), k = (int)(i % K), t = k / CPo, co = k % CPo;
+    float v = 0.f;
+    if (ci < cin && co < cout) {
+      const float x = wa[(size_t)co * taps * CPi + (size_t)(taps - 1 - t) * CPi + ci];
+      v = x >= 0.f ? p * x : q * x;
+    }
+    dst[i] = v;
+  }
+}
+// The stem's tap matrix [Npb][Kb] (layout of its w_b) of the one-chain kinds that do not walk on w_b itself: the T+ rows t*6 + c
+// hold w (LRP_RULE_EPSILON), 1 (LRP_RULE_FLAT) or w^2 (LRP_RULE_WSQUARE), the T- rows are zero.  (BoundedRule walks on w_b: w+ ; w-.)
+__global__ __launch_bounds__(256) void rn_pack_stem_rule_kernel(const float* __restrict__ wa, float* __restrict__ wb, int cout, int Npb,
+                                                                int Kb, int kind) {
+  const size_t total = (size_t)Npb * Kb;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int row = (int)(i / Kb), co = (int)(i % Kb), t = row / 6, c6 = row % 6;
+    float v = 0.f;
+    if (t < 49 && c6 < 3 && co < cout) {
+      const float x = wa[(size_t)co * 2 * RN_STEM_K + t * 3 + c6];
+      v = kind == 1 ? x : kind == 2 ? 1.f : x * x;
+    }
+    wb[i] = v;
   }
 }
 

@@ -66,7 +66,7 @@ class LRPEngine(object):
         self.n_images = 0
         self.precision = "bf16x3"                       # library default for the reverse walk (set_precision)
         self.cnn_rule = (1, 0)                          # ... and for its conv rule (set_cnn_rule)
-        self.cnn_rules = None                           # ... or the table in its place (set_cnn_rules)
+        self.cnn_rules = None                           # ... or the table in its place (set_cnn_rules; ResNet: the pair (stem, units))
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -497,6 +497,18 @@ class LRPEngine(object):
         self.cnn_rule = (alpha, beta)
         self.cnn_rules = None                           # (the one rule replaces a table: set_cnn_rules)
 
+    @staticmethod
+    def _fill_rule(rec, r):
+        """a record of analyzer.normalize_rule -> lrp_conv_rule"""
+        if r[0] == "alphabeta":
+            rec.kind, rec.alpha, rec.beta, rec.bias = _capi.LRP_RULE_ALPHA_BETA, r[1], r[2], int(r[3])
+        elif r[0] == "epsilon":
+            rec.kind, rec.eps, rec.bias = _capi.LRP_RULE_EPSILON, r[1], int(r[2])
+        elif r[0] == "bounded":
+            rec.kind, rec.low, rec.high = _capi.LRP_RULE_BOUNDED, r[1], r[2]
+        else:
+            rec.kind = _capi.LRP_RULE_FLAT if r[0] == "flat" else _capi.LRP_RULE_WSQUARE
+
     def set_cnn_rules(self, table):
         """One rule per conv of the VGG-style encoder's LRP walk (lrp_set_cnn_rules), input layer first.  `table`: a list with one
         entry per conv — ("alphabeta", alpha, beta, bias), ("epsilon", eps, bias), ("flat",), ("wsquare",), ("bounded", low, high)
@@ -507,19 +519,32 @@ class LRPEngine(object):
         table = tuple(normalize_rule(r) for r in table)
         arr = (_capi.LrpConvRule * max(1, len(table)))()
         for rec, r in zip(arr, table):
-            if r[0] == "alphabeta":
-                rec.kind, rec.alpha, rec.beta, rec.bias = _capi.LRP_RULE_ALPHA_BETA, r[1], r[2], int(r[3])
-            elif r[0] == "epsilon":
-                rec.kind, rec.eps, rec.bias = _capi.LRP_RULE_EPSILON, r[1], int(r[2])
-            elif r[0] == "bounded":
-                rec.kind, rec.low, rec.high = _capi.LRP_RULE_BOUNDED, r[1], r[2]
-            else:
-                rec.kind = _capi.LRP_RULE_FLAT if r[0] == "flat" else _capi.LRP_RULE_WSQUARE
+            self._fill_rule(rec, r)
         _capi.check(self._lib.lrp_set_cnn_rules(self._h, C.cast(arr, C.c_void_p), len(table)))
         uniform = table[0][0] == "alphabeta" and table[0][3] and all(r == table[0] for r in table)
         new_rule, new_table = ((table[0][1], table[0][2]), None) if uniform else (None, table)
         if (new_rule, new_table) != (self.cnn_rule, getattr(self, "cnn_rules", None)):
             self.n_images = 0                            # the library dropped the caches of the other rules
+            self.captions = None
+        self.cnn_rule, self.cnn_rules = new_rule, new_table
+
+    def set_resnet_rules(self, rule, input_layer_rule=None):
+        """The rule pair of the ResNet encoder's LRP walk (lrp_set_resnet_rules): `rule` for every conv above the stem —
+        ("alphabeta", alpha, beta, bias) or ("epsilon", eps, bias) — and `input_layer_rule` for the stem conv — those, ("flat",),
+        ("wsquare",), ("bounded", low, high) or (low, high); None: `rule` there too.  Records as analyzer.normalize_rule returns
+        them, or anything it accepts.  The same alpha-beta rule with bias in both places is set_cnn_rule(alpha, beta).  A change
+        drops the encode caches: call encode_images again.  Epsilon kinds need set_precision('fp32') (the explain calls raise
+        NotImplementedError otherwise); beta > 0 needs widths that are multiples of 8, as set_cnn_rule."""
+        from .analyzer import resnet_rule_pair
+        stem, units = resnet_rule_pair(rule, input_layer_rule)
+        arr = (_capi.LrpConvRule * 2)()
+        for rec, r in zip(arr, (stem, units)):
+            self._fill_rule(rec, r)
+        _capi.check(self._lib.lrp_set_resnet_rules(self._h, C.addressof(arr[0]), C.addressof(arr[1])))
+        uniform = stem == units and stem[0] == "alphabeta" and stem[3]
+        new_rule, new_table = ((stem[1], stem[2]), None) if uniform else (None, (stem, units))
+        if (new_rule, new_table) != (self.cnn_rule, getattr(self, "cnn_rules", None)):
+            self.n_images = 0                            # the library dropped the caches of the other pair
             self.captions = None
         self.cnn_rule, self.cnn_rules = new_rule, new_table
 

@@ -49,7 +49,10 @@ class CaptionModelSpec(object):
         """cnn_rule: the (alpha, beta) of the encoder's conv rule (LRPEngine.set_cnn_rule), or 'alpha1beta0' (the default:
         LRPSequentialPresetA, E:32) / 'alpha2beta1' (LRPSequentialPresetB's conv rule), or a preset name of analyzer.PRESETS
         ('presetB', and — VGG-style encoders — 'presetAflat', 'presetBflat', 'zplus', ...) or a list with one rule per conv, input
-        layer first; a ResNet encoder takes what amounts to ONE alpha-beta rule with bias on every conv (NotImplementedError otherwise)
+        layer first, or a dict {"rule": ..., "input_layer_rule": ...} with the keywords of analyzer.LRP(...) — either encoder: a
+        VGG-style one makes analyzer.rule_table of it, a ResNet one the rule pair of LRPEngine.set_resnet_rules (self.cnn_rules is
+        then (stem record, record of the other convs)).  The preset names and lists on a ResNet encoder take what amounts to ONE
+        alpha-beta rule with bias on every conv (NotImplementedError otherwise)
         (analyzer.normalize_rule; LRPEngine.set_cnn_rules: self.cnn_rules holds the table, self.cnn_rule is then None); every explainer built on the spec
         whose CNN half is the LRP walk applies it to its engine; the gradient-baseline classes do not (their walks ignore the
         rule, and setting it would cost them its encode pass and buffers for nothing).
@@ -80,6 +83,17 @@ class CaptionModelSpec(object):
         (LRPEngine.set_cnn_rules); a table that is one alpha-beta rule with bias on every conv is that one rule"""
         names = ("alpha1beta0", "alpha2beta1")
         table = None
+        if isinstance(cnn_rule, dict):                   # the keywords of LRP(...)
+            if set(cnn_rule) - {"rule", "input_layer_rule"} or "rule" not in cnn_rule:
+                raise ValueError("cnn_rule as a dict holds 'rule' and optionally 'input_layer_rule', the keywords of LRP(...)")
+            if self.resnet is None:
+                table = (cnn_rule["rule"], cnn_rule.get("input_layer_rule"))
+            else:
+                from .analyzer import resnet_rule_pair
+                stem, units = resnet_rule_pair(cnn_rule["rule"], cnn_rule.get("input_layer_rule"))
+                if stem == units and stem[0] == "alphabeta" and stem[3]:
+                    return (stem[1], stem[2]), None
+                return None, (stem, units)
         if isinstance(cnn_rule, str) and cnn_rule not in names:
             if cnn_rule not in presets:
                 raise ValueError("cnn_rule must be (alpha, beta), 'alpha1beta0', 'alpha2beta1', one of %s or a list with a rule per conv"
@@ -136,7 +150,10 @@ class ExplainImgCaptioningAttentionModel(object):
         if self._applies_cnn_rule and getattr(model, "cnn_rules", None) is not None:
             if any(r[0] == "epsilon" for r in model.cnn_rules):
                 self._engine.set_precision("fp32")      # (epsilon kinds run in exact fp32 only)
-            self._engine.set_cnn_rules(model.cnn_rules)
+            if getattr(model, "resnet", None) is not None:
+                self._engine.set_resnet_rules(model.cnn_rules[1], model.cnn_rules[0])      # the pair (stem, units)
+            else:
+                self._engine.set_cnn_rules(model.cnn_rules)
         elif self._applies_cnn_rule and tuple(getattr(model, "cnn_rule", None) or (1, 0)) != (1, 0):
             self._engine.set_cnn_rule(*model.cnn_rule)
         self._CNN_explainer = _EngineAnalyzer(self._engine)      # LRPSequentialPresetA(image_model, EPS, 'replace'), E:32
