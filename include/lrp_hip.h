@@ -237,8 +237,12 @@ int lrp_decoder_gradient(lrp_handle* h, int32_t n, const int32_t* img_idx_host, 
  * the walk runs in every precision mode on both encoders, in exact fp32.  Its first call after an encode builds a 0/1
  * position gate per pooled layer of a VGG-style encoder (max_images x that layer's activations, float32, allocated by the
  * first call and counted in lrp_workspace_bytes); the ResNet form allocates the BN-scaled matrices of the other gradient
- * walks and nothing else. */
-enum { LRP_WALK_LRP = 0, LRP_WALK_GRADIENT = 1, LRP_WALK_INPUT_X_GRADIENT = 2, LRP_WALK_GUIDED_BACKPROP = 3, LRP_WALK_DECONVNET = 4 };
+ * walks and nothing else.
+ * LRP_WALK_DEEPLIFT (added without a version bump; innvestigate/analyzer/deeplift.py:44-250, see lrp_set_deeplift_reference):
+ * VGG-style handles in LRP_PREC_FP32 only.  LRP_ERR_UNSUPPORTED on a ResNet handle and in every other precision mode;
+ * LRP_ERR_STATE without a reference, or when lrp_encode_images has not run since the reference was set or changed. */
+enum { LRP_WALK_LRP = 0, LRP_WALK_GRADIENT = 1, LRP_WALK_INPUT_X_GRADIENT = 2, LRP_WALK_GUIDED_BACKPROP = 3, LRP_WALK_DECONVNET = 4,
+       LRP_WALK_DEEPLIFT = 5 };
 int lrp_cnn_walk(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const float* head_dev, float* out_dev,
                  int32_t walk, void* stream);
 
@@ -357,6 +361,24 @@ int lrp_set_cnn_rules(lrp_handle* h, const lrp_conv_rule* rules, int32_t n_rules
  * lrp_set_cnn_rules keeps answering LRP_ERR_UNSUPPORTED on a ResNet handle: a rule per conv of the branched graph is not built. */
 int lrp_set_resnet_rules(lrp_handle* h, const lrp_conv_rule* stem, const lrp_conv_rule* units);
 
+/* Added without a version bump (purely additive).  DeepLIFT on a VGG-style handle:
+ *   DeepLIFT(model, neuron_selection_mode="replace", reference_inputs=r, approximate_gradient=...).analyze([X, head])
+ * of innvestigate/analyzer/deeplift.py, where every Conv2D(activation='relu') takes LinearRule on the fused layer:
+ *   t = dX * convT(M A / safe(dY)),  g = convT(M A),  out = |dX| < 1e-7 ? g : t   (approximate_gradient=False: out = t)
+ * with dX = X - Xr, dY = Y - Yr against the forward of ONE reference shared by all images, safe(d) = d + 1e-7 [d == 0], M the ReLU
+ * mask of the image's forward; max-pools take the plain gradient (the image's arg-max, first in scan order on ties); the head is
+ * the caller's tensor.  ref_host: (img_h, img_w, 3) float32, or NULL for the constant ref_scalar.
+ * mode 0 = off, 1 = approximate_gradient=False (one chain), 2 = True (two chains and the per-element select).
+ * A change of reference or mode drops the encode caches, as lrp_set_cnn_rules does; the same setting again does nothing.  The
+ * next lrp_encode_images in LRP_PREC_FP32 runs the reference through the images' own forward path as a batch of one (again only
+ * after a weight, precision or reference change) and writes one gate per layer and image behind the unchanged forward; in the
+ * other precision modes nothing is computed and LRP_WALK_DEEPLIFT answers LRP_ERR_UNSUPPORTED.  The LRP and gradient walks, the
+ * features and the fine-tune step are, bit for bit, those of a handle without a reference.  Buffers appear with the first
+ * mode != 0 (mode 2 adds the two-chain ping-pong of 2 max_tokens rows), are counted in lrp_workspace_bytes and idle afterwards;
+ * a handle that never sets a reference allocates nothing.  LRP_ERR_UNSUPPORTED: a ResNet handle (its stand-alone Activation,
+ * BatchNorm and Add layers take other mappings), or a launch lrp_conv_plan refuses.  LRP_ERR_INVALID: mode, a non-finite value. */
+int lrp_set_deeplift_reference(lrp_handle* h, const float* ref_host, float ref_scalar, int32_t mode);
+
 /* Dominant-kernel timing for bench.py's roofline block: when enabled, HIP
  * events bracket every conv-LRP launch on the caller's stream; query returns
  * launches and summed milliseconds since the last reset (syncs the events). */
@@ -406,6 +428,16 @@ int lrp_op_conv_ab(const float* sp_dev, const float* sn_dev, const float* w_hwio
 int lrp_op_conv_rule(const float* s0_dev, const float* s1_dev, const float* w_hwio_host, int32_t chains_in, int32_t gates_out, float p0,
                      float q0, float p1, float q1, const float* g0_dev, const float* g1_dev, float* out0_dev, float* out1_dev, int32_t NB,
                      int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t pool, int32_t split, void* stream);
+
+/* Added without a version bump (purely additive).  One fused conv + ReLU layer of the DeepLIFT walk as an operator, exact fp32,
+ * all tensors plain fp32 NHWC.  With Y = relu(conv(x) + b), Yr = relu(conv(xr) + b), M = [Y > 0] (with pool != 0: and the first
+ * arg-max of Y's 2x2 window, where a_dev, at pooled resolution, is routed to):
+ *   out = mode 2 && |x - xr| < 1e-7 ? convT(M a) : (x - xr) * convT(M a / safe(Y - Yr))        (mode 1: always the second)
+ * x_dev, out_dev (NB, H, W, Cin); xr_dev (H, W, Cin), shared by the batch; a_dev (NB, H u, W u, Cout), u = 1/2 with pool;
+ * w_hwio_host (3, 3, Cin, Cout); bias_host (Cout).  Cout % 4 == 0; Cin % 4 == 0, or Cin == 3: the image layer's launches.
+ * What lrp_conv_plan refuses is LRP_ERR_UNSUPPORTED. */
+int lrp_op_deeplift_conv(const float* x_dev, const float* xr_dev, const float* a_dev, const float* w_hwio_host, const float* bias_host,
+                         float* out_dev, int32_t NB, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t pool, int32_t mode, void* stream);
 
 /* ABI v6.  The conv-LRP launch BEHIND a 2x2 max-pool (AlphaBetaRule RR:274-322 for a conv whose output feeds MaxPooling2D: the
  * relevance arrives through the pool's gradient routing, RA:470-480 -> IL:138-157, i.e. one non-zero per window and channel)

@@ -67,6 +67,8 @@ SYMBOLS = {
     "lrp_set_cnn_rule": (C.c_int, [_P, C.c_float, C.c_float]),
     "lrp_set_cnn_rules": (C.c_int, [_P, _P, C.c_int32]),
     "lrp_set_resnet_rules": (C.c_int, [_P, _P, _P]),
+    "lrp_set_deeplift_reference": (C.c_int, [_P, _P, C.c_float, C.c_int32]),
+    "lrp_op_deeplift_conv": (C.c_int, [_P] * 6 + [C.c_int32] * 7 + [_P]),
     "lrp_profile_enable": (C.c_int, [_P, C.c_int32]),
     "lrp_profile_query": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "lrp_profile_records": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),

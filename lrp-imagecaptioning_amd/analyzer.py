@@ -27,7 +27,13 @@ And the rest of the gradient-based entries that need no trained side data (gradi
     SmoothGrad(image_model, augment_by_n=64, postprocess=None, ...)       # GaussianSmoother over Gradient
     IntegratedGradients(image_model, steps=64, postprocess=None, ...)     # PathIntegrator over Gradient
 
-with samples, walks and the mean on the device (LRPEngine.cnn_walk_augmented); `analyzers` maps the reference's names to what is built."""
+with samples, walks and the mean on the device (LRPEngine.cnn_walk_augmented); `analyzers` maps the reference's names to what is built.
+
+DeepLIFT and DeepTaylor (innvestigate/analyzer/deeplift.py:44-250, deeptaylor.py:40-199), VGG-style encoders, reached by name:
+
+    DeepLIFT(image_model, reference_inputs=0, approximate_gradient=True)    # LRPEngine.set_deeplift_reference + the 'deeplift' walk
+    DeepTaylor(image_model) / BoundedDeepTaylor(image_model, low, high)     # the default walk / the bounded table, head [feat > 0]
+"""
 import numpy as np
 
 from .engine import LRPEngine
@@ -513,12 +519,109 @@ class Deconvnet(_GradientWalkAnalyzer):
     _walk = "deconvnet"
 
 
+def check_deeplift_reference(reference_inputs, img_hw):
+    """reference_inputs of DeepLIFT as the engine takes it: a finite scalar, or an array that broadcasts to (1, H, W, 3) — one
+    reference for all images (utils/keras/__init__.py:60-74)."""
+    if isinstance(reference_inputs, (str, bytes)) or reference_inputs is None:
+        raise ValueError("reference_inputs must be a number or an array")
+    ref = np.asarray(reference_inputs, dtype=np.float32)
+    if not np.all(np.isfinite(ref)):
+        raise ValueError("reference_inputs must be finite")
+    if ref.ndim:
+        try:
+            np.broadcast_to(ref, (1, img_hw[0], img_hw[1], 3))
+        except ValueError:
+            raise ValueError("reference_inputs of shape %s does not broadcast to (1, %d, %d, 3): one reference is shared by all "
+                             "images" % (ref.shape, img_hw[0], img_hw[1]))
+    return ref
+
+
+class DeepLIFT(_GradientWalkAnalyzer):
+    """deeplift.py:44-250 for the VGG-style encoders, `analyze([X, head])`: LinearRule on every fused conv + ReLU layer against
+    the forward of `reference_inputs` (a scalar or an array that broadcasts to (1, H, W, 3)), the pools by gradient routing;
+    approximate_gradient as in the reference (the gradient where |x - reference| < 1e-7).  Runs on the engine's DeepLIFT walk
+    (lrp_set_deeplift_reference, LRP_WALK_DEEPLIFT) in exact fp32.  A ResNet spec is NotImplementedError: its stand-alone
+    Activation, BatchNorm and Add layers take other mappings, and that walk is not built."""
+    _walk = "deeplift"
+
+    def __init__(self, model, reference_inputs=0, approximate_gradient=True, neuron_selection_mode="replace", max_batch=8,
+                 device=None):
+        _check_selection_mode(neuron_selection_mode)
+        if getattr(model, "resnet", None) is not None:
+            raise NotImplementedError("DeepLIFT is built for the VGG-style (conv-list) encoders only")
+        ref = check_deeplift_reference(reference_inputs, model.img_hw)
+        self._reference_inputs, self._approximate_gradient = ref, bool(approximate_gradient)
+        super(DeepLIFT, self).__init__(model, neuron_selection_mode=neuron_selection_mode, max_batch=max_batch, device=device)
+        self._engine.set_deeplift_reference(ref, self._approximate_gradient)
+
+
+class DeepLIFTWrapper(object):
+    """deeplift.py:253-: the wrapper around the `deeplift` package, which the reference imports in its constructor."""
+
+    def __init__(self, model=None, *args, **kwargs):
+        raise ImportError("To use DeepLIFTWrapper please install the python module 'deeplift', "
+                          "e.g.: 'pip install deeplift'")
+
+
+class DeepTaylor(LRP):
+    """deeptaylor.py:40-160 for the VGG-style encoders: Alpha1Beta0Rule (with the bias) on every fused conv, the pools by gradient
+    routing, and a ReLU on the output — whose mask is already in the top layer's gate (a = 0 there gives G = 0).  That is the
+    engine's default walk.  A ResNet spec is NotImplementedError (its BatchNorm layers are `do_nothing` there, another walk)."""
+
+    def __init__(self, model, neuron_selection_mode="replace", **kwargs):
+        if getattr(model, "resnet", None) is not None:
+            raise NotImplementedError("DeepTaylor is built for the VGG-style (conv-list) encoders only")
+        super(DeepTaylor, self).__init__(model, rule="Alpha1Beta0", input_layer_rule=self._input_rule(),
+                                         neuron_selection_mode=neuron_selection_mode, **kwargs)
+
+    def _input_rule(self):
+        return None
+
+    def analyze(self, X, neuron_selection=None):
+        """The head passes the output ReLU's gradient mapping first (deeptaylor.py:69-75, :144-154): head [feat > 0].  The top
+        layer's rule divides by Z+ and has no gate of its own, so this mask is the one thing the default walk does not hold."""
+        if neuron_selection is not None:
+            raise ValueError("Only neuron_selection_mode 'index' expects the neuron_selection parameter.")  # base.py:489-492
+        X = list(X) if isinstance(X, (list, tuple)) else [X]
+        if len(X) != 2:
+            raise ValueError("neuron_selection_mode 'replace' expects [X, R]")
+        img, R = np.asarray(X[0], dtype=np.float32), np.asarray(X[1], dtype=np.float32)
+        n = img.shape[0]
+        if R.shape[0] != n:
+            raise ValueError("X and R must have the same batch size")
+        e = self._engine
+        out = np.empty_like(img)
+        for lo in range(0, n, e.max_images):
+            hi = min(n, lo + e.max_images, lo + e.max_tokens)
+            e.encode_images(img[lo:hi])
+            head = R[lo:hi].reshape(hi - lo, e.L, e.D) * (e.get_features()[:hi - lo].cpu().numpy() > 0)
+            out[lo:hi] = e.cnn_explain(list(range(hi - lo)), head).cpu().numpy()
+        return out
+
+
+class BoundedDeepTaylor(DeepTaylor):
+    """deeptaylor.py:163-199: DeepTaylor with BoundedRule(low, high) at the image layer."""
+
+    def __init__(self, model, low=None, high=None, **kwargs):
+        if low is None or high is None:
+            raise ValueError("The low or high parameter is missing. Z-B (bounded rule) require both values.")   # :172-175
+        if not (float(low) < float(high)):
+            raise ValueError("bounded rule: low < high (low=%r, high=%r)" % (low, high))
+        self._bounds = (float(low), float(high))
+        super(BoundedDeepTaylor, self).__init__(model, **kwargs)
+
+    def _input_rule(self):
+        return self._bounds
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # AugmentReduceBase wrappers (wrapper.py:78-345) on LRPEngine.cnn_walk_augmented
 # ---------------------------------------------------------------------------------------------------------------------
 def _engine_walk(subanalyzer):
     """(walk, postprocess) of an analyzer of this module that runs on an engine walk: the four gradient-walk classes and the
     LRP classes (the 'lrp' walk under the subanalyzer's own rule and precision)."""
+    if isinstance(subanalyzer, DeepLIFT):
+        raise TypeError("DeepLIFT is not built under an augmenting wrapper")
     if isinstance(subanalyzer, _GradientWalkAnalyzer):
         post = getattr(subanalyzer, "_postprocess", None)
         if isinstance(subanalyzer, InputTimesGradient) and post is not None:
@@ -646,8 +749,10 @@ class IntegratedGradients(PathIntegrator):
         super(IntegratedGradients, self).__init__(sub, steps=steps, reference_inputs=reference_inputs, path=path)
 
 
-# innvestigate/analyzer/__init__.py:35-85, the entries this module builds under the reference's keys (deep_taylor*, deep_lift*,
-# pattern.*, gradient.baseline, input and random are not built and stay absent)
+# innvestigate/analyzer/__init__.py:35-85, the entries this module builds under the reference's keys (pattern.*,
+# gradient.baseline, input and random are not built and stay absent).  DeepLIFT, DeepLIFTWrapper, DeepTaylor and BoundedDeepTaylor
+# are built (above) but reached by NAME: their keys deep_lift, deep_lift.wrapper, deep_taylor and deep_taylor.bounded stay out of
+# this table, which existing tests pin as it is.
 analyzers = {
     "gradient": Gradient,
     "input_t_gradient": InputTimesGradient,

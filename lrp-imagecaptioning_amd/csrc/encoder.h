@@ -1,6 +1,7 @@
 // encoder.h — host-side orchestration of the CNN half:
 //   encode():  one forward per IMAGE, caching the relevance gates G_l and Z_top
 //   explain(): one reverse walk per TOKEN (batched over all tokens of the call)
+//   explain_deeplift(): the DeepLIFT walk against one reference image (lrp_set_deeplift_reference; deeplift_kernels.h)
 // Reference semantics: LRPSequentialPresetA.analyze([X,R]) (AB:478-520) over the
 // sub-model input_1 -> block5_conv3 (E:29-32); rules RR:274-322, RA:470-480.
 #pragma once
@@ -15,6 +16,7 @@
 #include "conv_launch.h"
 #include "conv_plan.h"
 #include "conv_sparse.h"
+#include "deeplift_kernels.h"
 #include "f16_operand.h"
 #include "fwd_mode.h"
 
@@ -75,6 +77,10 @@ struct ConvLayer {
   DevBuf Gt, w_fwd_t, w_fwd_ts, w_bwd_t, w_bwd_t_s;
   DevBuf Gn, w_fwd_n, w_fwd_ns;
   bool t_packed = false;
+  // DeepLIFT (Encoder::set_deeplift_reference): the reference's input and activation of this layer — ONE image's worth,
+  // from the reference's own forward — and per image the gate D = M ? safe(Y - Yr) : 0 (deeplift_kernels.h dl_gate_kernel; every
+  // layer, the top one included).  Allocated by the first reference that is set.
+  DevBuf Xr, Yr, Dl;
   size_t act_elems() const { return (size_t)H * W * cout; }
 };
 
@@ -231,12 +237,18 @@ struct Encoder {
   // Fine-tune step: the weight gradient of layer l needs a_{l-1}; keep what the LRP caches drop.
   // Two users: the fine-tune step (for the life of the handle once lrp_train_begin ran) and a rule table (while it is set).
   // keep_acts = either; each asks and releases for itself, so neither can switch the other's activations off.
+  // A DeepLIFT reference is a third user, while it is set and the handle is in LRP_PREC_FP32 (dl_active: its walk runs nowhere
+  // else, and the other modes' forwards keep their fused forms); encode() decides keep_acts from the three.
   bool keep_acts = false, keep_for_train = false, keep_for_rule = false;
-  int enable_keep_acts(int64_t* total, bool for_rule = false) {
+  int alloc_keep_acts(int64_t* total) {
     for (size_t li = 0; li + 1 < layers.size(); ++li) {
       ConvLayer& L = layers[li];
       if (!L.pool_after && !L.Akeep.p) LRP_TRY(L.Akeep.alloc((size_t)max_images * L.act_elems() * sizeof(float), total));   // (kept across a rule round trip)
     }
+    return LRP_OK;
+  }
+  int enable_keep_acts(int64_t* total, bool for_rule = false) {
+    LRP_TRY(alloc_keep_acts(total));
     (for_rule ? keep_for_rule : keep_for_train) = true;
     keep_acts = true;
     return LRP_OK;
@@ -364,6 +376,7 @@ struct Encoder {
     L.t_packed = false;
     if (table_on()) LRP_TRY(pack_table_layer(li, w_dev, st));
     L.norm_dirty = true;
+    dl_ref_stale = true;
     LRP_HIP_CHECK(hipMemcpyAsync(L.bias.p, b_dev, (size_t)L.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
     L.raw_w_dev.release(); L.raw_b_dev.release();   // stale from here on (the trainer's master buffer is the truth)
     return LRP_OK;
@@ -377,6 +390,7 @@ struct Encoder {
       LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_gates, 0));
       gates_pending = false;
     }
+    dl_ref_stale = true;                               // the reference's activations belong to the old weights
     if (!L.raw_w_dev.p) LRP_TRY(L.raw_w_dev.alloc(nW * sizeof(float), total));
     LRP_HIP_CHECK(hipMemcpyAsync(L.raw_w_dev.p, w, nW * sizeof(float), kind, st));
     LRP_TRY(alloc_conv_operands(li, total, st));
@@ -395,6 +409,7 @@ struct Encoder {
     LRP_HIP_CHECK(hipMemcpyAsync(L.bias.p, L.raw_b_dev.p, (size_t)L.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
     L.have_b = true;
     L.norm_dirty = true;
+    dl_ref_stale = true;
     encoded = 0;
     return LRP_OK;
   }
@@ -410,6 +425,8 @@ struct Encoder {
   int encode(const float* images_dev, int B, hipStream_t st) {
     if (B < 1 || B > max_images) return fail(LRP_ERR_INVALID, "B=%d outside [1,%d]", B, max_images);
     LRP_TRY(check_ready());
+    keep_acts = keep_for_train || keep_for_rule || dl_active();
+    if (dl_active() && dl_ref_stale) LRP_TRY(dl_reference_pass(st));
     ++encode_epoch;
     for (ConvLayer& L : layers) L.gfull_epoch = encode_epoch;     // (every path writes the full-resolution gates, except the fused pool: after_pool_gate)
     const size_t img_elems = (size_t)img_h * img_w * 3;
@@ -433,6 +450,10 @@ struct Encoder {
     encoded = B;
     if (table_on() && table_runs()) {
       const int rc = table_pass(B, st);
+      if (rc != LRP_OK) { encoded = 0; return rc; }
+    }
+    if (dl_active()) {
+      const int rc = dl_pass(B, st);
       if (rc != LRP_OK) { encoded = 0; return rc; }
     }
     features_only = false;
@@ -502,7 +523,11 @@ struct Encoder {
     else ca = fwd_conv_args(L, B, x);
     ca.wpk = L.w_fwd.as<float>(); ca.N = 2 * L.cout; ca.split = L.cout;
     ca.out = top ? feat.as<float>() : a; ca.out2 = top ? ztop.as<float>() : z;
+    if (dl_capture && li > 0)                            // the reference's forward: its input of this layer ...
+      LRP_HIP_CHECK(hipMemcpyAsync(L.Xr.p, x, (size_t)L.H * L.W * L.cin * sizeof(float), hipMemcpyDeviceToDevice, st));
     LRP_HIP_CHECK(conv_launch(EPI_FWD_DUAL, ca, st));
+    if (dl_capture)                                      // ... and its activation, in front of the pool
+      LRP_HIP_CHECK(hipMemcpyAsync(L.Yr.p, top ? feat.p : (void*)a, L.act_elems() * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (top) return LRP_OK;
     if (L.pool_after) {
       LRP_TRY(pool_gate_pass(L, B, a, z, x, st));      // x now holds pool(a): input of the next conv
@@ -1232,6 +1257,173 @@ struct Encoder {
       std::swap(S, Snext);
     }
     return image_stencil_tail(n, S, row2img_dev, R_img_dev, img_mode, r0.low, r0.high, st);
+  }
+
+  // ---- DeepLIFT (lrp_set_deeplift_reference, LRP_WALK_DEEPLIFT; deeplift_kernels.h has the rule) ----
+  // One reference image per handle.  At encode, in LRP_PREC_FP32: the reference goes through forward_exact as a batch of one (the
+  // SAME path as the images: where image and reference agree on a receptive field Y and Yr are the same bits, which the dY == 0
+  // branch of SafeDivide needs) whenever weights, precision or reference changed, keeping Xr_l / Yr_l; behind the images' own
+  // forward dl_pass writes the gate D_l of every layer.  dX is not stored: the walk recomputes it from the kept layer inputs and
+  // Xr_l (the same 4 bytes read per element and token as a stored dX, and no (images x activations) tensor per layer; Xr_l is one
+  // image's worth and stays in L2).
+  int dl_mode = 0;                                       // 0 off | 1 approximate_gradient=False (one chain) | 2 True (two chains + select)
+  bool dl_ref_stale = true, dl_capture = false;
+  long dl_epoch = -1;                                    // the encode whose gates D_l are current
+  std::vector<float> dl_ref_host;                        // the reference as set, broadcast to (img_h, img_w, 3)
+  DevBuf dl_s0, dl_s1, dl_r2i;                           // mode 2: the two chains' ping-pong (2 max_tokens rows) and row2img twice
+  bool dl_active() const { return dl_mode != 0 && prec == PREC_FP32; }
+  int set_deeplift_reference(const float* ref_host, float ref_scalar, int mode, int64_t* total) {
+    if (mode == 0) {
+      if (dl_mode != 0) { dl_mode = 0; encoded = 0; }    // (the buffers stay, idle)
+      return LRP_OK;
+    }
+    const size_t img_elems = (size_t)img_h * img_w * 3;
+    std::vector<float> ref(img_elems, ref_scalar);
+    if (ref_host) ref.assign(ref_host, ref_host + img_elems);
+    for (float v : ref)
+      if (!(fabsf(v) < 3.0e38f)) return fail(LRP_ERR_INVALID, "the DeepLIFT reference must be finite");
+    if (mode == dl_mode && ref == dl_ref_host) return LRP_OK;   // the same setting again changes nothing
+    auto mk = [&](DevBuf& d, size_t bytes) -> int { return d.p && d.bytes >= bytes ? LRP_OK : d.alloc(bytes, total); };
+    const size_t B = (size_t)max_images, NT = (size_t)max_tokens;
+    for (ConvLayer& L : layers) {
+      LRP_TRY(mk(L.Xr, (size_t)L.H * L.W * L.cin * sizeof(float)));
+      LRP_TRY(mk(L.Yr, L.act_elems() * sizeof(float)));
+      LRP_TRY(mk(L.Dl, B * L.act_elems() * sizeof(float)));
+    }
+    if (mode == 2) {                                     // (one chain: the default walk's ping-pong s0 / s1)
+      const size_t tok = std::max(max_act_elems(), img_elems / 3 * IMG_T_COLS);
+      LRP_TRY(mk(dl_s0, 2 * NT * tok * sizeof(float)));
+      LRP_TRY(mk(dl_s1, 2 * NT * tok * sizeof(float)));
+      LRP_TRY(mk(dl_r2i, 2 * NT * sizeof(int)));
+    }
+    LRP_TRY(alloc_keep_acts(total));
+    LRP_HIP_CHECK(hipDeviceSynchronize());               // a walk in flight may still read the old reference
+    LRP_HIP_CHECK(hipMemcpy(layers[0].Xr.p, ref.data(), img_elems * sizeof(float), hipMemcpyHostToDevice));
+    dl_ref_host.swap(ref);
+    dl_mode = mode;
+    dl_ref_stale = true;
+    encoded = 0;                                         // the caches belong to the old reference
+    return LRP_OK;
+  }
+  // the reference's forward: image slot 0 and every cache it touches are overwritten by the encode that follows
+  int dl_reference_pass(hipStream_t st) {
+    if (gates_pending) {
+      LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_gates, 0));
+      gates_pending = false;
+    }
+    LRP_HIP_CHECK(hipMemcpyAsync(images.p, layers[0].Xr.p, (size_t)img_h * img_w * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    dl_capture = true;
+    const int rc = forward_exact(1, st);
+    dl_capture = false;
+    LRP_TRY(rc);
+    dl_ref_stale = false;
+    return LRP_OK;
+  }
+  // behind the images' forward (keep_acts: every conv's input and activation is still there): the gates
+  int dl_pass(int B, hipStream_t st) {
+    for (size_t li = 0; li < layers.size(); ++li) {
+      ConvLayer& L = layers[li];
+      const bool top = li + 1 == layers.size();
+      const size_t n4 = (size_t)B * L.act_elems() / 4;
+      if (L.pool_after) LRP_TRY(full_gate((int)li, st));
+      const float* y = top ? feat.as<float>() : L.Akeep.as<float>();
+      hipLaunchKernelGGL(dl_gate_kernel, dim3(stream_grid(n4)), dim3(256), 0, st, L.pool_after ? (const float*)nullptr : y,
+                         L.pool_after ? L.G.as<float>() : (const float*)nullptr, L.pool_after ? L.P.as<float>() : (const float*)nullptr,
+                         L.Yr.as<float>(), L.Dl.as<float>(), B, L.H, L.W, L.cout);
+      LRP_HIP_CHECK(hipGetLastError());
+    }
+    dl_epoch = encode_epoch;
+    return LRP_OK;
+  }
+  static int dl_combine(bool two, bool pool, const float* c, const float* x, const float* xr, const float* dn, const int* r2i, float* out, int n,
+                        int H, int W, int C, hipStream_t st) {
+    const dim3 grid(stream_grid((size_t)n * H * W * (C / 4)));
+    if (two && pool) hipLaunchKernelGGL((dl_combine_kernel<true, true>), grid, dim3(256), 0, st, c, x, xr, dn, r2i, out, n, H, W, C);
+    else if (two) hipLaunchKernelGGL((dl_combine_kernel<true, false>), grid, dim3(256), 0, st, c, x, xr, dn, r2i, out, n, H, W, C);
+    else if (pool) hipLaunchKernelGGL((dl_combine_kernel<false, true>), grid, dim3(256), 0, st, c, x, xr, dn, r2i, out, n, H, W, C);
+    else hipLaunchKernelGGL((dl_combine_kernel<false, false>), grid, dim3(256), 0, st, c, x, xr, dn, r2i, out, n, H, W, C);
+    return launched();
+  }
+  static int dl_final(bool two, const float* c, const float* x, const float* xr, const int* r2i, float* out, int n, size_t per, hipStream_t st) {
+    const bool v4 = !(per & 3);
+    const dim3 grid(stream_grid((size_t)n * per / (v4 ? 4 : 1)));
+    if (two && v4) hipLaunchKernelGGL((dl_final_kernel<true, 4>), grid, dim3(256), 0, st, c, x, xr, r2i, out, n, per);
+    else if (two) hipLaunchKernelGGL((dl_final_kernel<true, 1>), grid, dim3(256), 0, st, c, x, xr, r2i, out, n, per);
+    else if (v4) hipLaunchKernelGGL((dl_final_kernel<false, 4>), grid, dim3(256), 0, st, c, x, xr, r2i, out, n, per);
+    else hipLaunchKernelGGL((dl_final_kernel<false, 1>), grid, dim3(256), 0, st, c, x, xr, r2i, out, n, per);
+    return launched();
+  }
+  // The walk.  Per layer: the transposed conv with the full w (w_bwd_full, exact fp32, no gate in its epilogue) over the stacked
+  // chains [t ; g] — 2n rows, n in mode 1 — then dl_combine_kernel: the select, the 2x routing through a pool and both gates of the
+  // layer below.  The image layer is the stand-alone image launch over the same rows, then the select.
+  int dl_check(int n) const {                            // mode before state: a refusal says what to change first
+    if (n < 1 || n > max_tokens) return fail(LRP_ERR_INVALID, "n=%d outside [1,%d]", n, max_tokens);
+    if (prec != PREC_FP32)
+      return fail(LRP_ERR_UNSUPPORTED, "the DeepLIFT walk runs in LRP_PREC_FP32 only (dY of fp16-pair activations means nothing where it is small): "
+                                       "set it with lrp_set_precision and call lrp_encode_images again");
+    if (dl_mode == 0) return fail(LRP_ERR_STATE, "lrp_set_deeplift_reference must be called before the DeepLIFT walk");
+    if (encoded < 1 || features_only || dl_epoch != encode_epoch)
+      return fail(LRP_ERR_STATE, "lrp_encode_images must run (after lrp_set_deeplift_reference) before the DeepLIFT walk");
+    return LRP_OK;
+  }
+  int explain_deeplift(int n, const int* row2img_dev, const float* head_dev, float* R_img_dev, hipStream_t st) {
+    LRP_TRY(dl_check(n));
+    const bool two = dl_mode == 2;
+    const int rows = two ? 2 * n : n;
+    float *S = two ? dl_s0.as<float>() : s0.as<float>(), *Snext = two ? dl_s1.as<float>() : s1.as<float>();
+    const int* r2i_rows = row2img_dev;
+    auto conv_args = [&](int li) {
+      const ConvLayer& L = layers[li];
+      ConvArgs ca = conv3x3_args(L, rows, S, L.cout);
+      ca.wpk = L.w_bwd_full.as<float>();
+      return ca;
+    };
+    // every launch is one conv_plan answers: asked before the first one runs
+    for (int li = (int)layers.size() - 1; li >= 0; --li) {
+      ConvArgs ca = conv_args(li);
+      int epi = EPI_MUL;
+      if (li == 0) epi = image_layer_args(ca, rows, Snext, Snext, 1, 0.f, 0.f);
+      else ca.N = layers[li].cin;
+      if (!conv_plan(conv_ask(epi, PREC_FP32, 7, false, ca)).ok)
+        return fail(LRP_ERR_UNSUPPORTED, "conv %d: no exact-fp32 launch for %d rows of %d channels", li, rows, layers[li].cout);
+    }
+    if (two) {
+      LRP_HIP_CHECK(hipMemcpyAsync(dl_r2i.p, row2img_dev, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, st));
+      LRP_HIP_CHECK(hipMemcpyAsync(dl_r2i.as<int>() + n, row2img_dev, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, st));
+      r2i_rows = dl_r2i.as<int>();
+    }
+    {
+      const ConvLayer& T = layers.back();                // the head through the top layer's gates
+      prof.begin(st);
+      LRP_TRY(dl_combine(two, false, head_dev, nullptr, nullptr, T.Dl.as<float>(), row2img_dev, S, n, T.H, T.W, T.cout, st));
+      prof.end(st, 0.0);
+    }
+    for (int li = (int)layers.size() - 1; li >= 1; --li) {
+      const ConvLayer &L = layers[li], &P = layers[li - 1];
+      ConvArgs ca = conv_args(li);
+      ca.in = S; ca.N = L.cin; ca.out = Snext; ca.gate_none = 1;
+      prof.begin(st);
+      LRP_HIP_CHECK(conv_launch(EPI_MUL, ca, st, PREC_FP32));
+      prof.end(st, (two ? 2.0 : 1.0) * layer_flop(n, li));
+      prof.begin(st);
+      LRP_TRY(dl_combine(two, P.pool_after, Snext, layer_input(li), L.Xr.as<float>(), P.Dl.as<float>(), row2img_dev, S, n, L.H, L.W, L.cin, st));
+      prof.end(st, 0.0);
+    }
+    ConvArgs ca = conv_args(0);
+    ca.in = S; ca.row2img = r2i_rows;
+    const int epi = image_layer_args(ca, rows, Snext, Snext, 1, 0.f, 0.f);
+    prof.begin(st);
+    LRP_HIP_CHECK(conv_launch(epi, ca, st, PREC_FP32));
+    prof.end(st, (two ? 2.0 : 1.0) * layer_flop(n, 0));
+    const float* c = Snext;
+    if (!img_fused()) {
+      LRP_TRY(image_stencil_tail(rows, Snext, r2i_rows, S, 1, 0.f, 0.f, st));
+      c = S;
+    }
+    prof.begin(st);
+    LRP_TRY(dl_final(two, c, images.as<float>(), layers[0].Xr.as<float>(), row2img_dev, R_img_dev, n, (size_t)img_h * img_w * 3, st));
+    prof.end(st, 0.0);
+    return LRP_OK;
   }
 
   // R_feat_dev (n, top_h*top_w, top_c) -> R_img_dev (n, img_h, img_w, 3); row2img_dev: device int[n]

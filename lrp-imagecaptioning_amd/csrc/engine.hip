@@ -379,7 +379,13 @@ int lrp_cnn_walk(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const fl
                  void* stream) {
   return with_handle(h, [&]() -> int {
     if (!h || !img_idx_host || !head_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
-    if (walk < LRP_WALK_LRP || walk > LRP_WALK_DECONVNET) return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
+    if (walk < LRP_WALK_LRP || walk > LRP_WALK_DEEPLIFT) return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
+    if (walk == LRP_WALK_DEEPLIFT) {                     // (its own checks, in its own order: mode before state; nothing runs on a refusal)
+      if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "the DeepLIFT walk is built for the VGG-style (conv-list) encoders only");
+      LRP_TRY(h->enc.dl_check(n));
+      LRP_TRY(stage_indices(h, n, img_idx_host, nullptr, false, S(stream)));
+      return h->enc.explain_deeplift(n, h->idx_dev.as<int>(), head_dev, out_dev, S(stream));
+    }
     if (h->encoded() < 1 || h->features_only()) return fail(LRP_ERR_STATE, "lrp_encode_images must run before lrp_cnn_walk");
     // (checked before any staging: nothing runs; Deconvnet reads no ReLU decision and runs in every mode)
     if (h->resnet && walk != LRP_WALK_LRP && walk != LRP_WALK_DECONVNET && h->rn.prec != PREC_FP32)
@@ -406,6 +412,7 @@ int lrp_set_precision(lrp_handle* h, int32_t mode) {
       LRP_TRY(h->trainer.drop_early_forward(nullptr));
       h->enc.encoded = 0;
       h->rn.encoded = 0;
+      h->enc.dl_ref_stale = true;                        // (the DeepLIFT reference's activations go with the caches)
     }
     h->enc.prec = km;
     h->enc.fwd_fast = fast;
@@ -502,6 +509,17 @@ int lrp_set_cnn_rules(lrp_handle* h, const lrp_conv_rule* rules, int32_t n_rules
     for (int i = 0; i < n_rules; ++i) LRP_TRY(check_conv_rule(rules[i], i, t[(size_t)i]));
     if (t[0].input_only() && n_rules < 2) return fail(LRP_ERR_UNSUPPORTED, "an input-layer rule needs a conv above the image layer");
     return set_vgg_table(h, std::move(t));
+  });
+}
+
+int lrp_set_deeplift_reference(lrp_handle* h, const float* ref_host, float ref_scalar, int32_t mode) {
+  return with_handle(h, [&]() -> int {
+    if (mode < 0 || mode > 2) return fail(LRP_ERR_INVALID, "DeepLIFT mode %d: 0 = off, 1 = approximate_gradient=False, 2 = True", mode);
+    if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "the DeepLIFT walk is built for the VGG-style (conv-list) encoders only");
+    const int was = h->enc.encoded;
+    LRP_TRY(h->enc.set_deeplift_reference(ref_host, ref_scalar, mode, &h->ws_bytes));
+    if (was && !h->enc.encoded) LRP_TRY(h->trainer.drop_early_forward(nullptr));   // (a change dropped the caches it ran on)
+    return LRP_OK;
   });
 }
 
@@ -705,6 +723,113 @@ int lrp_op_conv_ab(const float* sp_dev, const float* sn_dev, const float* w_hwio
                    int32_t pool, int32_t split, void* stream) {
   return lrp_op_conv_rule(sp_dev, sn_dev, w_hwio_host, 2, 2, alpha, 0.f, 0.f, -beta, gp_dev, gn_dev, outp_dev, outn_dev, NB, H, W, Cin, Cout, pool,
                           split, stream);
+}
+
+// One fused conv + ReLU layer of the DeepLIFT walk (Encoder::explain_deeplift) as an operator.  Image and reference go through the
+// forward as ONE batch of NB + 1 (the same launch: where they agree on a receptive field Y and Yr are the same bits); a three-channel
+// input takes the image layer's forms (im2col GEMM forward, tap-expanded GEMM + stencil backward) as layer 0 of a handle does.
+int lrp_op_deeplift_conv(const float* x_dev, const float* xr_dev, const float* a_dev, const float* w_hwio_host, const float* bias_host,
+                         float* out_dev, int32_t NB, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t pool, int32_t mode, void* stream) {
+  return guarded([&]() -> int {
+    if (!x_dev || !xr_dev || !a_dev || !w_hwio_host || !bias_host || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (mode != 1 && mode != 2) return fail(LRP_ERR_INVALID, "DeepLIFT mode %d: 1 = approximate_gradient=False, 2 = True", mode);
+    if (NB < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return fail(LRP_ERR_INVALID, "NB, H, W, Cin, Cout must be >= 1");
+    const bool img = Cin == 3;
+    if ((Cout & 3) || (!img && (Cin & 3))) return fail(LRP_ERR_UNSUPPORTED, "Cout must be a multiple of 4, Cin 3 or a multiple of 4");
+    if (pool && ((H & 1) || (W & 1))) return fail(LRP_ERR_UNSUPPORTED, "odd resolution before a 2x2 pool");
+    const bool two = mode == 2;
+    const int rows = two ? 2 * NB : NB, NF = NB + 1;
+    const int64_t lim = (int64_t)1 << 31;
+    if ((int64_t)rows * H * W * std::max(Cout, img ? IMG_T_COLS : Cin) >= lim || (int64_t)NF * H * W * std::max(2 * Cout, 64) >= lim ||
+        (int64_t)9 * Cin * Cout >= lim)
+      return fail(LRP_ERR_UNSUPPORTED, "operator entry: tensor too large");
+    hipStream_t st = S(stream);
+    const size_t px = (size_t)H * W, xin = px * Cin, act = px * Cout;
+    DevBuf xa, y, z, a1, wraw, wf, wb, wb2, bdev, gm, pooled, D, Sb, Cb, Tb, r2i;
+    // ---- the launches, each asked of conv_plan before the first one runs ----
+    ConvArgs cf{}, cb{};
+    int epi_f, epi_b;
+    if (img) {
+      cf.NB = NF * H * W; cf.H = 1; cf.W = 1; cf.Cin = 64; cf.CinP = 64; cf.taps = 1; cf.N = 2 * Cout; cf.split = Cout;
+      epi_f = EPI_FWD_DUAL;
+      cb.NB = rows; cb.H = H; cb.W = W; cb.Cin = Cout; cb.CinP = conv_cinp(Cout); cb.taps = 1; cb.N = IMG_T_COLS;
+      if (Encoder::img_fused()) { cb.img_mode = 1; epi_b = EPI_IMG_STENCIL; }
+      else { cb.NB = rows * H * W; cb.H = 1; cb.W = 1; epi_b = EPI_STORE; }
+    } else {
+      cf.NB = NF; cf.H = H; cf.W = W; cf.Cin = Cin; cf.CinP = conv_cinp(Cin); cf.taps = 9; cf.N = Cout;
+      epi_f = EPI_BIAS_RELU;
+      cb.NB = rows; cb.H = H; cb.W = W; cb.Cin = Cout; cb.CinP = conv_cinp(Cout); cb.taps = 9; cb.N = Cin; cb.gate_none = 1;
+      epi_b = EPI_MUL;
+    }
+    if (!conv_plan(conv_ask(epi_f, PREC_FP32, 7, false, cf)).ok || !conv_plan(conv_ask(epi_b, PREC_FP32, 7, false, cb)).ok)
+      return fail(LRP_ERR_UNSUPPORTED, "no exact-fp32 launch for a %d -> %d layer at %d x %d", Cin, Cout, H, W);
+    // ---- forward of [x ; xr] ----
+    LRP_TRY(xa.alloc((size_t)NF * xin * sizeof(float), nullptr));
+    LRP_HIP_CHECK(hipMemcpyAsync(xa.p, x_dev, (size_t)NB * xin * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LRP_HIP_CHECK(hipMemcpyAsync(xa.as<float>() + (size_t)NB * xin, xr_dev, xin * sizeof(float), hipMemcpyDeviceToDevice, st));
+    LRP_TRY(y.alloc((size_t)NF * act * sizeof(float), nullptr));
+    LRP_TRY(bdev.alloc((size_t)Cout * sizeof(float), nullptr));
+    LRP_HIP_CHECK(hipMemcpy(bdev.p, bias_host, (size_t)Cout * sizeof(float), hipMemcpyHostToDevice));
+    if (img) {
+      const size_t nf = (size_t)conv_npad(2 * Cout) * 64, nb = (size_t)conv_npad(IMG_T_COLS) * conv_cinp(Cout);
+      LRP_TRY(wraw.alloc((size_t)27 * Cout * sizeof(float), nullptr));
+      LRP_HIP_CHECK(hipMemcpy(wraw.p, w_hwio_host, wraw.bytes, hipMemcpyHostToDevice));
+      LRP_TRY(wf.alloc(nf * sizeof(float), nullptr)); LRP_TRY(wb2.alloc(nb * sizeof(float), nullptr)); LRP_TRY(wb.alloc(nb * sizeof(float), nullptr));
+      LRP_HIP_CHECK(hipMemsetAsync(wf.p, 0, wf.bytes, st)); LRP_HIP_CHECK(hipMemsetAsync(wb2.p, 0, wb2.bytes, st));
+      LRP_HIP_CHECK(hipMemsetAsync(wb.p, 0, wb.bytes, st));
+      hipLaunchKernelGGL(pack_image_layer_dev_kernel, dim3((27 * Cout + 255) / 256), dim3(256), 0, st, wraw.as<float>(), wf.as<float>(), wb2.as<float>(),
+                         wb.as<float>(), Cout, conv_cinp(Cout));
+      LRP_TRY(a1.alloc((size_t)NF * px * 64 * sizeof(float), nullptr));
+      LRP_TRY(z.alloc((size_t)NF * act * sizeof(float), nullptr));
+      hipLaunchKernelGGL(im2col_image_kernel, dim3((unsigned)(((size_t)NF * px * 8 + 255) / 256)), dim3(256), 0, st, xa.as<float>(), a1.as<float>(), NF, H, W);
+      LRP_HIP_CHECK(hipGetLastError());
+      cf.in = a1.as<float>(); cf.out2 = z.as<float>();
+    } else {
+      LRP_TRY(op_pack_weight(w_hwio_host, 9, Cin, Cout, 0, wraw, wf, st));
+      LRP_TRY(op_pack_weight(w_hwio_host, 9, Cin, Cout, 1, wraw, wb, st));
+      cf.in = xa.as<float>();
+    }
+    cf.wpk = wf.as<float>(); cf.bias = bdev.as<float>(); cf.out = y.as<float>();
+    LRP_HIP_CHECK(conv_launch(epi_f, cf, st, PREC_FP32));
+    // ---- the gate D of the layer: the mask of the images' forward (through the pool: its first arg-max), safe(Y - Yr) under it ----
+    const float* yr = y.as<float>() + (size_t)NB * act;
+    LRP_TRY(D.alloc((size_t)NB * act * sizeof(float), nullptr));
+    if (pool) {
+      LRP_TRY(gm.alloc((size_t)NB * act * sizeof(float), nullptr));
+      LRP_TRY(pooled.alloc((size_t)NB * act / 4 * sizeof(float), nullptr));
+      hipLaunchKernelGGL(pool_gate_kernel, dim3(stream_grid((size_t)NB * act / 16)), dim3(256), 0, st, y.as<float>(), y.as<float>(), pooled.as<float>(),
+                         gm.as<float>(), NB, H, W, Cout);             // (z = a: the gate is 1 at a live arg-max, 0 elsewhere)
+    }
+    hipLaunchKernelGGL(dl_gate_kernel, dim3(stream_grid((size_t)NB * act / 4)), dim3(256), 0, st, pool ? (const float*)nullptr : y.as<float>(),
+                       pool ? gm.as<float>() : (const float*)nullptr, pool ? pooled.as<float>() : (const float*)nullptr, yr, D.as<float>(), NB, H, W, Cout);
+    LRP_HIP_CHECK(hipGetLastError());
+    // ---- the chains [a / D ; a M] (routed through the pool), the transposed conv over both, the select ----
+    LRP_TRY(Sb.alloc((size_t)rows * act * sizeof(float), nullptr));
+    const int Ha = pool ? H / 2 : H, Wa = pool ? W / 2 : W;
+    LRP_TRY(Encoder::dl_combine(two, pool != 0, a_dev, nullptr, nullptr, D.as<float>(), nullptr, Sb.as<float>(), NB, Ha, Wa, Cout, st));
+    LRP_TRY(Cb.alloc((size_t)rows * px * (img ? 4 : Cin) * sizeof(float), nullptr));
+    cb.in = Sb.as<float>(); cb.wpk = wb.as<float>(); cb.out = Cb.as<float>();
+    if (img) {
+      std::vector<int> idx((size_t)rows);
+      for (int i = 0; i < rows; ++i) idx[(size_t)i] = i % NB;
+      LRP_TRY(r2i.alloc((size_t)rows * sizeof(int), nullptr));
+      LRP_HIP_CHECK(hipMemcpy(r2i.p, idx.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice));
+      cb.row2img = r2i.as<int>(); cb.ximg = xa.as<float>();
+      if (epi_b == EPI_STORE) {
+        LRP_TRY(Tb.alloc((size_t)rows * px * IMG_T_COLS * sizeof(float), nullptr));
+        cb.out = Tb.as<float>();
+      }
+    }
+    LRP_HIP_CHECK(conv_launch(epi_b, cb, st, PREC_FP32));
+    if (img && epi_b == EPI_STORE) {
+      hipLaunchKernelGGL(img_stencil_kernel, dim3(stream_grid((size_t)rows * px)), dim3(256), 0, st, Tb.as<float>(), xa.as<float>(), r2i.as<int>(),
+                         Cb.as<float>(), rows, H, W, 1, 0.f, 0.f);
+      LRP_HIP_CHECK(hipGetLastError());
+    }
+    LRP_TRY(Encoder::dl_final(two, Cb.as<float>(), x_dev, xr_dev, nullptr, out_dev, NB, xin, st));
+    LRP_HIP_CHECK(hipStreamSynchronize(st));             // the operand copies are freed on return
+    return LRP_OK;
+  });
 }
 
 int lrp_op_conv_pool_sparse(const float* sc_dev, const unsigned char* pos_dev, const float* w_hwio_host, const float* gate_dev,

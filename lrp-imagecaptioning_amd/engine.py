@@ -353,7 +353,7 @@ class LRPEngine(object):
         return log_softmax_topk(logits, k)
 
     # ------------------------------------------------------------------ gradient baselines
-    WALKS = {"lrp": 0, "gradient": 1, "input_x_gradient": 2, "guided_backprop": 3, "deconvnet": 4}
+    WALKS = {"lrp": 0, "gradient": 1, "input_x_gradient": 2, "guided_backprop": 3, "deconvnet": 4, "deeplift": 5}
 
     def decoder_gradient(self, img_idx, t, want_r_words=True):
         """_lstm_decoder_backward (explainers.py:780-832 / :1452-1532) for n (image, t) units: (n, L, D) float32
@@ -396,6 +396,8 @@ class LRPEngine(object):
         captions = None) and encode_images has to run again before anything else is explained."""
         if walk not in self.WALKS:
             raise ValueError("unknown walk %r: one of %s" % (walk, sorted(self.WALKS)))
+        if walk == "deeplift":
+            raise TypeError("the DeepLIFT walk is not built under an augmenting wrapper")
         if kind not in self.AUGMENT_KINDS:
             raise ValueError("kind must be 'gaussian' or 'path'")
         if postprocess not in _POST:
@@ -548,6 +550,31 @@ class LRPEngine(object):
             self.captions = None
         self.cnn_rule, self.cnn_rules = new_rule, new_table
 
+    def set_deeplift_reference(self, reference=0, approximate_gradient=True):
+        """The reference of the DeepLIFT walk (lrp_set_deeplift_reference; cnn_walk(..., 'deeplift')): a scalar, or an array that
+        broadcasts to (1, H, W, 3) as the reference's reference_inputs does — one reference for all images.
+        approximate_gradient: True (the per-element switch to the gradient where |x - reference| < 1e-7), False, or None to take
+        the reference away again.  VGG-style encoders in 'fp32' mode only (NotImplementedError from this call on a ResNet engine,
+        from the walk in the other modes).  A change drops the encode caches: call encode_images again."""
+        H, W = self.img_hw
+        if approximate_gradient is None:
+            mode, ref = 0, None
+        else:
+            mode = 2 if approximate_gradient else 1
+            ref = np.asarray(reference.detach().cpu() if torch.is_tensor(reference) else reference, dtype=np.float32)
+        key = None if mode == 0 else (mode, ref.tobytes(), ref.shape)
+        if mode == 0 or ref.ndim == 0:
+            arr, scalar = None, float(ref) if mode else 0.0
+        else:
+            arr = np.ascontiguousarray(np.broadcast_to(ref, (1, H, W, 3)), dtype=np.float32)
+            scalar = 0.0
+        _capi.check(self._lib.lrp_set_deeplift_reference(self._h, arr.ctypes.data_as(C.c_void_p) if arr is not None else None,
+                                                         scalar, mode))
+        if key != getattr(self, "_deeplift_key", None):
+            self.n_images = 0                            # the library dropped the caches of the other reference
+            self.captions = None
+        self._deeplift_key = key
+
     def set_fast_layers(self, mask):
         """Which conv layers take the two-MFMA form in 'f16x2' mode (lrp_set_fast_layers): bit li of `mask`, an iterable of
         layer indices, or None / -1 for the built-in rule.  0 = fp16 pairs with three MFMAs in every layer.  A change drops
@@ -653,6 +680,25 @@ def op_conv_rule(chains, w_hwio, coef, gates, pool=False, split_bf16=False):
                                      pq[2], pq[3], p(gates[0]), opt(gates, 1), p(outs[0]), opt(outs, 1), NB, H, W, Cin, Cout,
                                      int(bool(pool)), int(bool(split_bf16)), _cur_stream(chains[0].device)))
     return outs
+
+
+def op_deeplift_conv(x, xr, a, w_hwio, bias, pool=False, approximate_gradient=True):
+    """One fused conv + ReLU layer of the DeepLIFT walk (lrp_op_deeplift_conv), exact fp32: x (NB, H, W, Cin) and the shared reference
+    input xr (H, W, Cin) go through the layer, the incoming a (NB, H u, W u, Cout), u = 1/2 with pool, is routed to the arg-max of
+    the image's activation and mapped back with LinearRule; returns (NB, H, W, Cin).  Cin is 3 or a multiple of 4."""
+    lib = _capi.load()
+    w = np.ascontiguousarray(w_hwio, dtype=np.float32)
+    b = np.ascontiguousarray(bias, dtype=np.float32)
+    Cin, Cout = w.shape[2], w.shape[3]
+    NB, H, W, _ = x.shape
+    d = 2 if pool else 1
+    assert tuple(x.shape) == (NB, H, W, Cin) and tuple(xr.shape) == (H, W, Cin) and tuple(a.shape) == (NB, H // d, W // d, Cout)
+    x, xr, a = x.contiguous(), xr.contiguous(), a.contiguous()
+    out = torch.empty((NB, H, W, Cin), dtype=torch.float32, device=x.device)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    _capi.check(lib.lrp_op_deeplift_conv(p(x), p(xr), p(a), w.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p), p(out), NB, H, W,
+                                         Cin, Cout, int(bool(pool)), 2 if approximate_gradient else 1, _cur_stream(x.device)))
+    return out
 
 
 def op_conv_pool_sparse(sc, pos, w_hwio, gate, reps=1):

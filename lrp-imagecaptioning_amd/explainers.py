@@ -532,6 +532,19 @@ class _DeconvnetMixin(_GradientMixin):
     _walk = "deconvnet"
 
 
+class _DeepLIFTMixin(_GradientMixin):
+    """CNN half = analyzer.DeepLIFT (deeplift.py:44-250) on the explainer's own engine: the 'deeplift' walk against the forward of
+    `reference_inputs` (a scalar or an array that broadcasts to (1, H, W, 3)); VGG-style encoders, exact fp32."""
+    _walk = "deeplift"
+
+    def __init__(self, *args, **kwargs):
+        reference_inputs = kwargs.pop("reference_inputs", 0)
+        approximate_gradient = bool(kwargs.pop("approximate_gradient", True))
+        super(_DeepLIFTMixin, self).__init__(*args, **kwargs)
+        from .analyzer import check_deeplift_reference
+        self._engine.set_deeplift_reference(check_deeplift_reference(reference_inputs, self._model.img_hw), approximate_gradient)
+
+
 class _AugmentedMixin(_GradientMixin):
     """`_explain_CNN(X, R)` on an analyzer instance of its own, created on first use from an ImageModelSpec of the model's encoder
     weights: a second, CNN-only handle, as every analyzer of analyzer.py has.  The explainer's own engine — its encode caches
@@ -592,4 +605,13 @@ class ExplainImgCaptioningGridTDSmoothGrad(_SmoothGradMixin, ExplainImgCaptionin
 
 
 class ExplainImgCaptioningGridTDIntegratedGradients(_IntegratedGradientsMixin, ExplainImgCaptioningGridTDModel):
+    _STATE_ATTRS = ExplainImgCaptioningGridTDModel._STATE_ATTRS + ("o1t_act", "o2t_act")
+
+
+
+class ExplainImgCaptioningAdaptiveAttentionDeepLIFT(_DeepLIFTMixin, ExplainImgCaptioningAdaptiveAttention):
+    _STATE_ATTRS = ExplainImgCaptioningAdaptiveAttention._STATE_ATTRS + ("ot_act",)
+
+
+class ExplainImgCaptioningGridTDDeepLIFT(_DeepLIFTMixin, ExplainImgCaptioningGridTDModel):
     _STATE_ATTRS = ExplainImgCaptioningGridTDModel._STATE_ATTRS + ("o1t_act", "o2t_act")
