@@ -207,6 +207,32 @@ int lrp_decoder_gen_step(lrp_handle* h, int32_t B, const int32_t* parent_host, c
  * ties to the lower column; logp_dev (rows, k) float64.  1 <= k <= min(V, 32). */
 int lrp_op_log_softmax_topk(const double* logits_dev, int32_t rows, int32_t V, int32_t k, int32_t* ids_dev,
                             double* logp_dev, void* stream);
+/* The whole search on the device (added without raising the ABI version: nothing existing changed).  The bookkeeping of
+ * explainers.py:51-120 — the two bounded heaps of `Caption(log_prob, sentence)` tuples (inference.py:267-315), the completion
+ * rule, the final pick — as two kernels (csrc/beam_kernels.h): totals in float64, the k largest under the total order
+ * (log_prob, sentence) by a counting rank, bit-identical to the host bookkeeping on the same scores.
+ * lrp_decoder_beam_search: after lrp_decoder_gen_begin(h, n_images * k) on features laid out one slot per (image, beam).
+ *   Enqueues `steps` iterations (re-parent, append, decoder step, logits, ranking, selection) and the finish on the stream:
+ *   no host synchronisation and no copy.  Outputs (device): captions_dev (n_images, k, max_caption_len + 1) int32 tokenizer
+ *   ids, zero-padded, every caption with a trailing EOS — the complete ones by descending order, then the live ones; row 0 is
+ *   the reference's answer; lengths_dev (n_images, k) EOS included; logp_dev (n_images, k) float64; n_complete_dev (n_images).
+ *   Refused before anything is launched: n_images * k > max_images, k outside [1, min(V, 32)], eos outside [1, V], rows other
+ *   than the search was begun with (LRP_ERR_INVALID); steps outside [1, max_caption_len] (LRP_ERR_RANGE); no search begun
+ *   (LRP_ERR_STATE).  Leaves the handle as lrp_decoder_gen_begin does: explain calls need a new lrp_decoder_forward.
+ * lrp_op_beam_select / lrp_op_beam_finish: the same two kernels on caller-owned device buffers.  state_dev holds
+ *   lrp_op_beam_state_bytes(n_images, k, max_len) bytes (8-byte aligned; a negative value for arguments the operators refuse)
+ *   and needs no initialisation: step 0 starts a search.  Step s reads ids_dev / logp_dev (n_images * k, k) as
+ *   lrp_op_log_softmax_topk writes them (at s = 0 only row 0 of an image is live) and writes parent_dev / word_dev
+ *   (n_images * k): row r of step s + 1 continues row parent_dev[r] with tokenizer id word_dev[r].  Steps run in order
+ *   0 .. steps - 1 <= max_len - 1, then lrp_op_beam_finish(steps) writes the outputs above with max_len in place of
+ *   max_caption_len. */
+int lrp_decoder_beam_search(lrp_handle* h, int32_t n_images, int32_t k, int32_t steps, int32_t eos, int32_t* captions_dev,
+                            int32_t* lengths_dev, double* logp_dev, int32_t* n_complete_dev, void* stream);
+int64_t lrp_op_beam_state_bytes(int32_t n_images, int32_t k, int32_t max_len);
+int lrp_op_beam_select(void* state_dev, const int32_t* ids_dev, const double* logp_dev, int32_t n_images, int32_t k,
+                       int32_t max_len, int32_t step, int32_t eos, int32_t* parent_dev, int32_t* word_dev, void* stream);
+int lrp_op_beam_finish(const void* state_dev, int32_t n_images, int32_t k, int32_t max_len, int32_t steps, int32_t eos,
+                       int32_t* captions_dev, int32_t* lengths_dev, double* logp_dev, int32_t* n_complete_dev, void* stream);
 
 /* ---- gradient baselines on the same caches -------------------------------------------------
  * lrp_decoder_gradient == ExplainImgCaptioning{AdaptiveAttention,GridTD}Gradient._lstm_decoder_backward(t)

@@ -80,6 +80,10 @@ SYMBOLS = {
     "lrp_decoder_gen_begin": (C.c_int, [_P, C.c_int32, _P]),
     "lrp_decoder_gen_step": (C.c_int, [_P, C.c_int32, _P, _P, C.c_int32, _P, _P]),
     "lrp_op_log_softmax_topk": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    "lrp_decoder_beam_search": (C.c_int, [_P] + [C.c_int32] * 4 + [_P] * 5),
+    "lrp_op_beam_state_bytes": (C.c_int64, [C.c_int32] * 3),
+    "lrp_op_beam_select": (C.c_int, [_P] * 3 + [C.c_int32] * 5 + [_P] * 3),
+    "lrp_op_beam_finish": (C.c_int, [_P] + [C.c_int32] * 5 + [_P] * 5),
     "lrp_decoder_gradient": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P]),
     "lrp_cnn_walk": (C.c_int, [_P, C.c_int32, _P, _P, _P, C.c_int32, _P]),
     "lrp_op_avgpool_lrp": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "beam_kernels.h"
 #include "cnn_kernels.h"
 #include "common.h"
 #include "conv_launch.h"
@@ -16,6 +17,7 @@
 #include "decoder_batched_kernels.h"
 #include "decoder_kernels.h"
 #include "gradient_kernels.h"
+#include "score_kernels.h"
 #include "train_gemm.h"
 
 namespace lrp {
@@ -464,8 +466,9 @@ struct Decoder {
     return LRP_OK;
   }
 
-  // ---- incremental decoding for caption generation: the beam bookkeeping of E:51-120 stays on the host, each search
-  // step costs ONE decoder step for all live hypotheses (the reference re-runs the whole captioner per step)
+  // ---- incremental decoding for caption generation: each search step costs ONE decoder step for all live hypotheses (the
+  // reference re-runs the whole captioner per step).  gen_step leaves the beam bookkeeping of E:51-120 to the host;
+  // beam_search (below) keeps it on the device too
   DevBuf gen_tmp, gen_idx;
   int* gen_pinned = nullptr;
   hipEvent_t ev_gen = nullptr;
@@ -510,6 +513,12 @@ struct Decoder {
       }
       LRP_HIP_CHECK(hipMemcpyAsync(gen_idx.p, gen_pinned, (size_t)2 * B * sizeof(int), hipMemcpyHostToDevice, st));
       LRP_HIP_CHECK(hipEventRecord(ev_gen, st));
+    }
+    return gen_advance(B, s, logits_dev, st);
+  }
+  // the device half of a step: re-parent and append from gen_idx (parent | word, device memory), one decoder step, the logits
+  int gen_advance(int B, int s, double* logits_dev, hipStream_t st) {
+    if (s > 0) {
       if (kind == LRP_DEC_ADAPTIVE) {
         LRP_TRY(gen_reparent<float>("ht", B, s, st));
         LRP_TRY(gen_reparent<float>("ct", B, s, st));
@@ -522,6 +531,42 @@ struct Decoder {
     LRP_TRY(kind == LRP_DEC_ADAPTIVE ? step_adaptive(s, B, st) : step_gridtd(s, B, st));
     const double* rows = (kind == LRP_DEC_ADAPTIVE ? u.as<double>() : h2u.as<double>()) + (size_t)s * H;
     LRP_HIP_CHECK((skinny<double, double, double>(rows, Tm * H, Wout.as<float>(), V, bout.as<float>(), logits_dev, V, B, H, V, 0, st)));
+    return LRP_OK;
+  }
+
+  // ---- the whole search on the stream (beam_kernels.h): per step gen_advance from the device's own parent | word, the ranking
+  // (log_softmax_topk_kernel) and the bookkeeping (beam_select_kernel, which writes the next step's parent | word into gen_idx);
+  // then beam_finish_kernel.  No host synchronisation, no pinned buffer, no copy.  Scratch is allocated by the first call.
+  DevBuf beam_logits, beam_ids, beam_logp, beam_state;
+  int beam_search(int n_images, int k, int steps, int eos_id, int32_t* captions_dev, int32_t* lengths_dev, double* logp_dev,
+                  int32_t* n_complete_dev, hipStream_t st) {
+    if (n_images < 1 || n_images > B_max) return fail(LRP_ERR_INVALID, "n_images=%d outside [1,%d]", n_images, B_max);
+    if (k < 1 || k > BEAM_K_MAX || k > V) return fail(LRP_ERR_INVALID, "beam %d outside [1, min(V=%d, %d)]", k, V, BEAM_K_MAX);
+    if ((int64_t)n_images * k > B_max) return fail(LRP_ERR_INVALID, "%d images x beam %d need more than the handle's %d rows", n_images, k, B_max);
+    if (steps < 1 || steps > Tm) return fail(LRP_ERR_RANGE, "steps=%d outside [1,%d]", steps, Tm);
+    if (eos_id < 1 || eos_id > V) return fail(LRP_ERR_INVALID, "eos=%d outside [1,%d]", eos_id, V);
+    if (gen_rows < 1 || have_forward) return fail(LRP_ERR_STATE, "lrp_decoder_gen_begin must run first");
+    const int B = n_images * k;
+    if (B != gen_rows) return fail(LRP_ERR_INVALID, "%d images x beam %d but the search was begun with %d rows", n_images, k, gen_rows);
+    if (!beam_state.p) {
+      int64_t dummy = 0;
+      LRP_TRY(beam_logits.alloc((size_t)B_max * V * sizeof(double), &dummy));
+      LRP_TRY(beam_ids.alloc((size_t)B_max * BEAM_K_MAX * sizeof(int), &dummy));
+      LRP_TRY(beam_logp.alloc((size_t)B_max * BEAM_K_MAX * sizeof(double), &dummy));
+      // n_images * k <= B_max rows of Tm words per buffer bound every (n_images, k) the checks above admit
+      LRP_TRY(beam_state.alloc(beam_state_bytes(B_max, BEAM_K_MAX, Tm), &dummy));
+    }
+    for (int s = 0; s < steps; ++s) {
+      LRP_TRY(gen_advance(B, s, beam_logits.as<double>(), st));
+      hipLaunchKernelGGL(log_softmax_topk_kernel, dim3(B), dim3(256), 0, st, beam_logits.as<double>(), V, k, beam_ids.as<int>(),
+                         beam_logp.as<double>());
+      hipLaunchKernelGGL(beam_select_kernel, dim3(n_images), dim3(BEAM_THREADS), 0, st, beam_state.p, beam_ids.as<int>(),
+                         beam_logp.as<double>(), k, Tm, s, eos_id, gen_idx.as<int>(), gen_idx.as<int>() + B);
+      LRP_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(beam_finish_kernel, dim3(n_images), dim3(64), 0, st, beam_state.p, k, Tm, steps, eos_id, captions_dev,
+                       lengths_dev, logp_dev, n_complete_dev);
+    LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   }
 

@@ -292,6 +292,14 @@ int lrp_decoder_gen_step(lrp_handle* h, int32_t B, const int32_t* parent_host, c
   });
 }
 
+int lrp_decoder_beam_search(lrp_handle* h, int32_t n_images, int32_t k, int32_t steps, int32_t eos, int32_t* captions_dev,
+                            int32_t* lengths_dev, double* logp_dev, int32_t* n_complete_dev, void* stream) {
+  return with_handle(h, [&]() -> int {
+    if (!h || !captions_dev || !lengths_dev || !logp_dev || !n_complete_dev) return fail(LRP_ERR_INVALID, "null argument");
+    return h->dec.beam_search(n_images, k, steps, eos, captions_dev, lengths_dev, logp_dev, n_complete_dev, S(stream));
+  });
+}
+
 int lrp_read_state(lrp_handle* h, const char* name, void* out_dev, size_t out_bytes, void* stream) {
   return with_handle(h, [&]() -> int {
     if (!h || !name || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
@@ -1095,6 +1103,47 @@ int lrp_op_log_softmax_topk(const double* logits_dev, int32_t rows, int32_t V, i
     if (!logits_dev || !ids_dev || !logp_dev) return fail(LRP_ERR_INVALID, "null argument");
     if (rows < 1 || V < 1 || k < 1 || k > V || k > TOPK_MAX) return fail(LRP_ERR_INVALID, "need rows >= 1 and 1 <= k <= min(V, %d)", TOPK_MAX);
     hipLaunchKernelGGL(log_softmax_topk_kernel, dim3(rows), dim3(256), 0, S(stream), logits_dev, V, k, ids_dev, logp_dev);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+// ---- the beam bookkeeping as stand-alone operators on caller-owned buffers (csrc/beam_kernels.h)
+static int beam_op_args(int n_images, int k, int max_len) {
+  if (n_images < 1 || max_len < 1 || k < 1 || k > BEAM_K_MAX)
+    return fail(LRP_ERR_INVALID, "need n_images >= 1, max_len >= 1 and 1 <= k <= %d", BEAM_K_MAX);
+  if ((int64_t)n_images * k * k > INT32_MAX || (int64_t)n_images * k * (max_len + 1) > INT32_MAX)
+    return fail(LRP_ERR_INVALID, "n_images x k x k and n_images x k x (max_len + 1) must fit 31 bits");
+  return LRP_OK;
+}
+
+int64_t lrp_op_beam_state_bytes(int32_t n_images, int32_t k, int32_t max_len) {
+  return guarded([&]() -> int { return beam_op_args(n_images, k, max_len); }) == LRP_OK
+             ? (int64_t)beam_state_bytes(n_images, k, max_len)
+             : (int64_t)LRP_ERR_INVALID;
+}
+
+int lrp_op_beam_select(void* state_dev, const int32_t* ids_dev, const double* logp_dev, int32_t n_images, int32_t k, int32_t max_len,
+                       int32_t step, int32_t eos, int32_t* parent_dev, int32_t* word_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (!state_dev || !ids_dev || !logp_dev || !parent_dev || !word_dev) return fail(LRP_ERR_INVALID, "null argument");
+    LRP_TRY(beam_op_args(n_images, k, max_len));
+    if (step < 0 || step >= max_len) return fail(LRP_ERR_RANGE, "step %d outside [0,%d)", step, max_len);
+    hipLaunchKernelGGL(beam_select_kernel, dim3(n_images), dim3(BEAM_THREADS), 0, S(stream), state_dev, ids_dev, logp_dev, k, max_len,
+                       step, eos, parent_dev, word_dev);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_op_beam_finish(const void* state_dev, int32_t n_images, int32_t k, int32_t max_len, int32_t steps, int32_t eos,
+                       int32_t* captions_dev, int32_t* lengths_dev, double* logp_dev, int32_t* n_complete_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (!state_dev || !captions_dev || !lengths_dev || !logp_dev || !n_complete_dev) return fail(LRP_ERR_INVALID, "null argument");
+    LRP_TRY(beam_op_args(n_images, k, max_len));
+    if (steps < 1 || steps > max_len) return fail(LRP_ERR_RANGE, "steps=%d outside [1,%d]", steps, max_len);
+    hipLaunchKernelGGL(beam_finish_kernel, dim3(n_images), dim3(64), 0, S(stream), state_dev, k, max_len, steps, eos, captions_dev,
+                       lengths_dev, logp_dev, n_complete_dev);
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   });

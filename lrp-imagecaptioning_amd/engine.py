@@ -352,6 +352,32 @@ class LRPEngine(object):
         descending probability.  Only these k pairs per row have to cross PCIe."""
         return log_softmax_topk(logits, k)
 
+    def _beam_search_packed(self, n_images, k, steps, eos):
+        """lrp_decoder_beam_search into ONE device allocation: (buffer, (captions, lengths, logp, n_complete) views)."""
+        n, k = int(n_images), int(k)
+        if n < 1 or k < 1:
+            raise ValueError("n_images and k must be positive")
+        buf, views = _beam_result_views(n, k, self.Tm, self.device)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        _capi.check(self._lib.lrp_decoder_beam_search(self._h, n, k, int(steps), int(eos), p(views[0]), p(views[1]), p(views[2]),
+                                                      p(views[3]), self._stream()))
+        return buf, views
+
+    def beam_search(self, n_images, k, steps, eos):
+        """The whole caption search of explainers.py:51-120 on the stream, after `gen_begin(n_images * k)` on features laid
+        out one slot per (image, beam): `steps` decoder steps with the ranking and the beam bookkeeping on the device, no
+        host round trip in between.  Returns device tensors: captions (n_images, k, max_caption_len + 1) int32 tokenizer
+        ids with a trailing EOS, zero-padded (complete captions by descending order, then live ones: what `beam.search`
+        returns; [:, 0] is the reference's answer), lengths (n_images, k) int32, logp (n_images, k) float64,
+        n_complete (n_images,) int32."""
+        return self._beam_search_packed(n_images, k, steps, eos)[1]
+
+    def beam_search_lists(self, n_images, k, steps, eos):
+        """`beam_search`, brought to the host in one copy, in the form `beam.search` returns: per image a list of captions."""
+        buf, _ = self._beam_search_packed(n_images, k, steps, eos)
+        caps, lens, _, _ = _beam_result_views(int(n_images), int(k), self.Tm, None, buf.cpu())[1]
+        return beam_lists(caps, lens)
+
     # ------------------------------------------------------------------ gradient baselines (SURVEY 8f-3)
     WALKS = {"lrp": 0, "gradient": 1, "input_x_gradient": 2, "guided_backprop": 3, "deconvnet": 4, "deeplift": 5}
 
@@ -804,6 +830,71 @@ def log_softmax_topk(logits, k):
     _capi.check(lib.lrp_op_log_softmax_topk(C.c_void_p(x.data_ptr()), rows, V, int(k), C.c_void_p(ids.data_ptr()),
                                             C.c_void_p(lp.data_ptr()), _cur_stream(x.device)))
     return ids, lp
+
+
+def _beam_result_views(n, k, max_len, device, buf=None):
+    """The four results of a search as views of one byte buffer (so that they reach the host in one copy):
+    logp (n, k) float64 | captions (n, k, max_len + 1) int32 | lengths (n, k) int32 | n_complete (n,) int32."""
+    sizes = [n * k * 8, n * k * (max_len + 1) * 4, n * k * 4, n * 4]
+    if buf is None:
+        buf = torch.empty(sum(sizes), dtype=torch.uint8, device=device)
+    o = [0, sizes[0], sizes[0] + sizes[1], sizes[0] + sizes[1] + sizes[2], sum(sizes)]
+    logp = buf[o[0]:o[1]].view(torch.float64).view(n, k)
+    caps = buf[o[1]:o[2]].view(torch.int32).view(n, k, max_len + 1)
+    lens = buf[o[2]:o[3]].view(torch.int32).view(n, k)
+    ncomp = buf[o[3]:o[4]].view(torch.int32)
+    return buf, (caps, lens, logp, ncomp)
+
+
+def beam_lists(captions, lengths):
+    """(n, k, max_len + 1) captions and (n, k) lengths -> per image the list of captions `beam.search` returns."""
+    caps, lens = captions.cpu().numpy(), lengths.cpu().numpy()
+    return [[caps[i, q, :lens[i, q]].tolist() for q in range(caps.shape[1]) if lens[i, q] > 0] for i in range(caps.shape[0])]
+
+
+def beam_state(n_images, k, max_len, device):
+    """An (uninitialised) state buffer for `beam_select` / `beam_finish`: lrp_op_beam_state_bytes bytes on `device`."""
+    nbytes = _capi.load().lrp_op_beam_state_bytes(int(n_images), int(k), int(max_len))
+    if nbytes < 0:
+        raise ValueError("need n_images >= 1, max_len >= 1 and 1 <= k <= 32")
+    return torch.empty(nbytes // 8, dtype=torch.int64, device=device)
+
+
+def beam_select(state, ids, logp, step, eos, max_len):
+    """lrp_op_beam_select: search step `step` of the beam bookkeeping (explainers.py:51-120, as `beam.search` restates it) for
+    all images at once.  state = `beam_state(n_images, k, max_len, device)`; ids (n_images * k, k) int32 model columns and logp
+    (n_images * k, k) float64 as `log_softmax_topk` returns them.  Returns (parent, word), (n_images * k,) int32 device tensors:
+    row r of the next step continues row parent[r] with tokenizer id word[r]."""
+    lib = _capi.load()
+    ids, logp = ids.contiguous(), logp.contiguous()
+    if ids.dtype != torch.int32 or logp.dtype != torch.float64 or ids.dim() != 2 or ids.shape != logp.shape:
+        raise ValueError("expected ids int32 and logp float64 of one (n_images * k, k) shape")
+    rows, k = ids.shape
+    if k < 1 or rows % k:
+        raise ValueError("ids must have n_images * k rows of k columns")
+    n = rows // k
+    if state.numel() * state.element_size() < lib.lrp_op_beam_state_bytes(n, k, int(max_len)):
+        raise ValueError("state is smaller than lrp_op_beam_state_bytes(n_images, k, max_len)")
+    parent = torch.empty(rows, dtype=torch.int32, device=ids.device)
+    word = torch.empty(rows, dtype=torch.int32, device=ids.device)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    _capi.check(lib.lrp_op_beam_select(p(state), p(ids), p(logp), n, k, int(max_len), int(step), int(eos), p(parent), p(word),
+                                       _cur_stream(ids.device)))
+    return parent, word
+
+
+def beam_finish(state, n_images, k, max_len, steps, eos):
+    """lrp_op_beam_finish after `steps` calls of `beam_select`: (captions (n_images, k, max_len + 1) int32 with a trailing EOS,
+    lengths (n_images, k) int32, logp (n_images, k) float64, n_complete (n_images,) int32) — `LRPEngine.beam_search`'s results."""
+    lib = _capi.load()
+    n, k = int(n_images), int(k)
+    if n < 1 or k < 1 or state.numel() * state.element_size() < lib.lrp_op_beam_state_bytes(n, k, int(max_len)):
+        raise ValueError("state is smaller than lrp_op_beam_state_bytes(n_images, k, max_len)")
+    _, views = _beam_result_views(n, k, int(max_len), state.device)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    _capi.check(lib.lrp_op_beam_finish(p(state), n, k, int(max_len), int(steps), int(eos), p(views[0]), p(views[1]), p(views[2]),
+                                       p(views[3]), _cur_stream(state.device)))
+    return views
 
 
 _LUT_CACHE = {}

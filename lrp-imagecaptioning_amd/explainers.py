@@ -254,7 +254,9 @@ class ExplainImgCaptioningAttentionModel(object):
                                                       want_R_feat=return_R_feat, want_attention=True, want_r_words=True)
         return out, pairs, att, rw, R
 
-    def _beam_search(self, X, beam_size=3):
+    device_search = False      # True: `_beam_search` keeps the beam bookkeeping on the device too (`on_device=None` reads this)
+
+    def _beam_search(self, X, beam_size=3, on_device=None):
         """Caption generation (E:51-120; the batched form of inference.py:178-253).  Upstream of the LRP path (captions
         are an input to it); provided so harnesses run end to end.
           * bookkeeping = `beam.search`: the reference's two bounded heaps, EOS handling and final pick, pinned against
@@ -263,8 +265,13 @@ class ExplainImgCaptioningAttentionModel(object):
             step per search step for ALL beams of ALL images that fit the handle — max_images >= images x beam_size —
             where the reference re-runs the whole captioner on every partial caption, E:71), and so does the ranking
             (lrp_op_log_softmax_topk): per step only beam_size (id, log p) pairs per hypothesis come to the host.
+        on_device=True (default: the class attribute `device_search`) moves the bookkeeping to the device as well
+        (`LRPEngine.beam_search`: all steps of a group enqueued at once, one copy of the results per group); the captions
+        are the same lists (tests/test_gpu_beam_device.py).
         Returns, per image, up to beam_size captions, element [0] = the reference's answer (one image: that list)."""
         from . import beam
+        if on_device is None:
+            on_device = self.device_search
         _, imgs_input = X
         imgs_input = np.asarray(imgs_input, dtype=np.float32)
         EOS = self._preprocessor.EOS_TOKEN_LABEL_ENCODED
@@ -281,6 +288,9 @@ class ExplainImgCaptioningAttentionModel(object):
             feat = eng.get_features()[:G]
             eng.set_features(feat.repeat_interleave(k, dim=0).contiguous())    # one row (feature slot) per (image, beam)
             eng.gen_begin(G * k)
+            if on_device:
+                results += eng.beam_search_lists(G, k, self._max_caption_length, EOS)
+                continue
 
             def step(s, parent, word):
                 logits = eng.gen_step(s, parent, word)                          # (G * k, V) float64, stays on the device
