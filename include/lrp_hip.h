@@ -405,6 +405,40 @@ int lrp_set_resnet_rules(lrp_handle* h, const lrp_conv_rule* stem, const lrp_con
  * BatchNorm and Add layers take other mappings), or a launch lrp_conv_plan refuses.  LRP_ERR_INVALID: mode, a non-finite value. */
 int lrp_set_deeplift_reference(lrp_handle* h, const float* ref_host, float ref_scalar, int32_t mode);
 
+/* Layer trace (added without a version bump; innvestigate/analyzer/base.py:570-603, :715-802 — reverse_keep_tensors,
+ * reverse_check_min_max_values, reverse_check_finite): the LRP walk of a VGG-style handle with the relevance at the input of every
+ * layer materialised and reduced on the device.  The encoder's nodes are its convs and 2x2 max-pools in execution order,
+ * nid = 0 .. N-1; the traced tensors, in sorted-id order, are index 0 = (-1, 0), the head as the caller passed it, and index
+ * 1 + nid = (nid, 0), the relevance at the INPUT of node nid in that tensor's shape — index 1 is the image-level result.  A pool's
+ * input tensor is at full resolution: the pool's output relevance at the forward's arg-max (first in scan order), exact 0.0
+ * at the other three cells.  With LRP_MAX_CONV = 32 there are at most 64 tensors: every one has a bit in a 64-bit mask.
+ * lrp_set_layer_trace: while on, the handle keeps every conv's input at encode (as a rule table does; counted in
+ *   lrp_workspace_bytes).  A change drops the encode caches, as lrp_set_cnn_rules does; the same value again does nothing.
+ *   Features, the other walks and the fine-tune step are, bit for bit, those of a handle that never saw the switch.
+ * lrp_trace_tensor_count: N + 1.  lrp_trace_tensor_info: node id and shape of tensor `index`, and for a call with n rows and
+ *   keep_mask (bit t = tensor index t) its offset in the keep buffer in floats (-1: not selected) and the buffer's size.
+ * lrp_cnn_explain_traced: n heads (n, L, D) and img_idx_host as lrp_cnn_explain, under the rule in force (the default,
+ *   lrp_set_cnn_rule or any lrp_set_cnn_rules table, one chain or two) in LRP_PREC_FP32 and LRP_PREC_BF16X3[_FAST].  Writes
+ *   R_img_dev (n, img_h, img_w, 3); stats_dev (N + 1, n, 4) float64 — minimum, maximum, sum and count of non-finite elements of
+ *   every traced tensor per row, from the fp32 values the keep buffer would hold (min / max exact, NaN where the row holds a
+ *   NaN, -0.0 below +0.0; the sum accumulated in float64; reductions in a fixed order that depends neither on n nor on the
+ *   other rows: a row's statistics and kept tensors are the same bits at n = 1 and inside a larger call); and, keep_dev not
+ *   NULL, each tensor of keep_mask as (n, H, W, C) float32 at its offset.  Per layer it runs the rule's transposed conv with
+ *   a plain fp32 accumulator and one streaming kernel (csrc/trace_kernels.h); its reduction partials are allocated by the first
+ *   traced call (counted in lrp_workspace_bytes).
+ *   LRP_ERR_UNSUPPORTED: a ResNet handle, LRP_PREC_F16X2, an epsilon table outside LRP_PREC_FP32, a launch lrp_conv_plan refuses.
+ *   LRP_ERR_STATE: the switch is off, or lrp_encode_images has not run since it was turned on.  LRP_ERR_INVALID: n, a mask
+ *   naming no tensor, keep_floats below what lrp_trace_tensor_info reports — nothing is launched.
+ * lrp_op_tensor_stats: the same four statistics of x_dev (rows, per_row) float32 into stats_dev (rows, 4) float64; one block
+ *   per row, a fixed order. */
+int lrp_set_layer_trace(lrp_handle* h, int32_t on);
+int32_t lrp_trace_tensor_count(lrp_handle* h);
+int lrp_trace_tensor_info(lrp_handle* h, int32_t index, int32_t n, uint64_t keep_mask, int32_t* nid, int32_t* H, int32_t* W, int32_t* C,
+                          int64_t* offset, int64_t* keep_floats);
+int lrp_cnn_explain_traced(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const float* R_feat_dev, float* R_img_dev,
+                           double* stats_dev, uint64_t keep_mask, float* keep_dev, int64_t keep_floats, void* stream);
+int lrp_op_tensor_stats(const float* x_dev, int32_t rows, int64_t per_row, double* stats_dev, void* stream);
+
 /* Dominant-kernel timing for bench.py's roofline block: when enabled, HIP
  * events bracket every conv-LRP launch on the caller's stream; query returns
  * launches and summed milliseconds since the last reset (syncs the events). */

@@ -69,6 +69,11 @@ SYMBOLS = {
     "lrp_set_resnet_rules": (C.c_int, [_P, _P, _P]),
     "lrp_set_deeplift_reference": (C.c_int, [_P, _P, C.c_float, C.c_int32]),
     "lrp_op_deeplift_conv": (C.c_int, [_P] * 6 + [C.c_int32] * 7 + [_P]),
+    "lrp_set_layer_trace": (C.c_int, [_P, C.c_int32]),
+    "lrp_trace_tensor_count": (C.c_int32, [_P]),
+    "lrp_trace_tensor_info": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_uint64] + [C.POINTER(C.c_int32)] * 4 + [C.POINTER(C.c_int64)] * 2),
+    "lrp_cnn_explain_traced": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P, _P, C.c_uint64, _P, C.c_int64, _P]),
+    "lrp_op_tensor_stats": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P]),
     "lrp_profile_enable": (C.c_int, [_P, C.c_int32]),
     "lrp_profile_query": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "lrp_profile_records": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),

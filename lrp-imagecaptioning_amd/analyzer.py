@@ -79,14 +79,39 @@ class ImageModelSpec(object):
         return h, w, self.cnn_cfg[-1][2]
 
 
+def reversed_tensor_ids(cnn_cfg):
+    """The sorted ids of the reversed tensors of a VGG-style conv list (base.py:715-802; graph.py:770-816): (-1, 0) the head,
+    (nid, 0) the relevance at the input of node nid — the convs and 2x2 pools in execution order."""
+    n_nodes = sum(2 if pool else 1 for _, _, _, pool in cnn_cfg)
+    return [(nid, 0) for nid in range(-1, n_nodes)]
+
+
 class LRPSequentialPresetA(object):
-    def __init__(self, model, epsilon=0.1, neuron_selection_mode="replace", max_batch=8, device=None, **kwargs):
+    """analyze([X, R]) on the engine's LRP walk.  The reverse analyzers' inspection switches (base.py:570-603) are taken by name on
+    a VGG-style spec — reverse_keep_tensors, reverse_check_min_max_values, reverse_check_finite: with any of them set, analyze runs
+    the traced walk (LRPEngine.cnn_explain_traced), prints the reference's lines (base.py:769-802) and sets `_reversed_tensors`,
+    the sorted list of ((nid, 0), float32 ndarray (N, H, W, C)), as the reference does, and `_reversed_stats`, a dict
+    id -> {"min", "max", "sum" (per input row), "nonfinite"}.  The ids: (-1, 0) the head, (nid, 0) the relevance at the input of
+    node nid (convs and 2x2 pools in execution order).  reverse_clip_values and reverse_project_bottleneck_layers change the walk
+    itself and are not built."""
+
+    def __init__(self, model, epsilon=0.1, neuron_selection_mode="replace", max_batch=8, device=None, reverse_keep_tensors=False,
+                 reverse_check_min_max_values=False, reverse_check_finite=False, reverse_clip_values=False,
+                 reverse_project_bottleneck_layers=False, **kwargs):
         if neuron_selection_mode not in ["max_activation", "index", "all", "replace"]:
             raise ValueError("neuron_selection parameter is not valid.")             # base.py:332-333
         if neuron_selection_mode != "replace":
             raise NotImplementedError("only neuron_selection_mode='replace' is on the captioning hot path")
         if not (epsilon > 0):
             raise ValueError("epsilon must be > 0")                                   # relevance_based/utils.py:52-60
+        if reverse_clip_values or reverse_project_bottleneck_layers:
+            raise NotImplementedError("reverse_clip_values and reverse_project_bottleneck_layers change the walk itself and are not built")
+        self._reverse_keep_tensors = bool(reverse_keep_tensors)
+        self._reverse_check_min_max_values = bool(reverse_check_min_max_values)
+        self._reverse_check_finite = bool(reverse_check_finite)
+        self._trace = self._reverse_keep_tensors or self._reverse_check_min_max_values or self._reverse_check_finite
+        if self._trace and getattr(model, "resnet", None) is not None:
+            raise NotImplementedError("the reverse_* inspection switches are built for the VGG-style (conv-list) encoders only")
         self._epsilon = epsilon          # used by Dense layers only (PresetA); the truncated encoders have none
         self._neuron_selection_mode = neuron_selection_mode
         self._model = model
@@ -96,12 +121,68 @@ class LRPSequentialPresetA(object):
                                  V=4, max_images=max_batch, max_tokens=max_batch, max_caption_len=2, device=device,
                                  resnet=model.resnet)
         self._engine.set_weights(model.weights)
+        if self._trace:
+            self._engine.set_layer_trace(True)
         self._impl = _EngineAnalyzer(self._engine)
 
     def analyze(self, X, neuron_selection=None):
         if neuron_selection is not None:
             raise ValueError("Only neuron_selection_mode 'index' expects the neuron_selection parameter.")  # base.py:489-492
+        if self._trace:
+            return self._analyze_traced(X)
         return self._impl.analyze(X)
+
+    def reversed_tensor_ids(self):
+        """The ids of the reversed tensors, sorted: (-1, 0), (0, 0), ... (N - 1, 0) for the N convs and pools of the spec."""
+        return reversed_tensor_ids(self._model.cnn_cfg)
+
+    def _analyze_traced(self, X, mask_head=False):
+        """analyze through the traced walk, in chunks of max_batch; mask_head: head [feat > 0] first (DeepTaylor)."""
+        X = list(X) if isinstance(X, (list, tuple)) else [X]
+        if len(X) != 2:
+            raise ValueError("neuron_selection_mode 'replace' expects [X, R]")
+        img, R = np.asarray(X[0], dtype=np.float32), np.asarray(X[1], dtype=np.float32)
+        n = img.shape[0]
+        if R.shape[0] != n:
+            raise ValueError("X and R must have the same batch size")
+        e = self._engine
+        ids = [i for i, _ in e.trace_tensors()]
+        out = np.empty_like(img)
+        stats, parts = [], dict((i, []) for i in ids)
+        for lo in range(0, n, e.max_images):
+            hi = min(n, lo + e.max_images, lo + e.max_tokens)
+            e.encode_images(img[lo:hi])
+            head = R[lo:hi].reshape(hi - lo, e.L, e.D)
+            if mask_head:
+                head = head * (e.get_features()[:hi - lo].cpu().numpy() > 0)
+            r, st, kept = e.cnn_explain_traced(list(range(hi - lo)), head, keep=True if self._reverse_keep_tensors else ())
+            out[lo:hi] = r.cpu().numpy()
+            stats.append(st.cpu().numpy())
+            for i, t in kept.items():
+                parts[i].append(t.cpu().numpy())
+        self._handle_debug_output(ids, np.concatenate(stats, axis=1), parts)
+        return out
+
+    def _handle_debug_output(self, ids, stats, parts):
+        """base.py:769-802 from the per-row statistics (n_tensors, N, 4) and the kept chunks: the reference reduces each tensor
+        over the whole batch."""
+        mn = [np.float32(np.min(stats[k, :, 0])) for k in range(len(ids))]           # (np.min / np.max: NaN where a row's is NaN)
+        mx = [np.float32(np.max(stats[k, :, 1])) for k in range(len(ids))]
+        nonfinite = [int(stats[k, :, 3].sum()) for k in range(len(ids))]
+        self._reversed_stats = dict((i, {"min": float(mn[k]), "max": float(mx[k]), "sum": stats[k, :, 2].copy(), "nonfinite": nonfinite[k]})
+                                    for k, i in enumerate(ids))
+        if self._reverse_check_min_max_values:
+            print("Minimum values in tensors: "
+                  "((NodeID, TensorID), Value) - {}".format(sorted(zip(ids, mn), key=lambda t: t[0])))
+            print("Maximum values in tensors: "
+                  "((NodeID, TensorID), Value) - {}".format(sorted(zip(ids, mx), key=lambda t: t[0])))
+        if self._reverse_check_finite:
+            bad = sorted(i for k, i in enumerate(ids) if nonfinite[k] > 0)
+            if bad:
+                print("Not finite values found in following nodes: "
+                      "(NodeID, TensorID) - {}".format(bad))
+        if self._reverse_keep_tensors:
+            self._reversed_tensors = sorted(((i, np.concatenate(parts[i], axis=0)) for i in ids), key=lambda t: t[0])
 
 
 def infer_alpha_beta(alpha, beta, caller):
@@ -582,6 +663,8 @@ class DeepTaylor(LRP):
         layer's rule divides by Z+ and has no gate of its own, so this mask is the one thing the default walk does not hold."""
         if neuron_selection is not None:
             raise ValueError("Only neuron_selection_mode 'index' expects the neuron_selection parameter.")  # base.py:489-492
+        if self._trace:
+            return self._analyze_traced(X, mask_head=True)
         X = list(X) if isinstance(X, (list, tuple)) else [X]
         if len(X) != 2:
             raise ValueError("neuron_selection_mode 'replace' expects [X, R]")

@@ -2,6 +2,7 @@
 //   encode():  one forward per IMAGE, caching the relevance gates G_l and Z_top
 //   explain(): one reverse walk per TOKEN (batched over all tokens of the call)
 //   explain_deeplift(): the DeepLIFT walk against one reference image (lrp_set_deeplift_reference; deeplift_kernels.h)
+//   explain_traced(): the LRP walk with the relevance at every layer's input kept and reduced (lrp_set_layer_trace; trace_kernels.h)
 // Reference semantics: LRPSequentialPresetA.analyze([X,R]) (AB:478-520) over the
 // sub-model input_1 -> block5_conv3 (E:29-32); rules RR:274-322, RA:470-480.
 #pragma once
@@ -19,6 +20,7 @@
 #include "deeplift_kernels.h"
 #include "f16_operand.h"
 #include "fwd_mode.h"
+#include "trace_kernels.h"
 
 namespace lrp {
 
@@ -238,8 +240,9 @@ struct Encoder {
   // Two users: the fine-tune step (for the life of the handle once lrp_train_begin ran) and a rule table (while it is set).
   // keep_acts = either; each asks and releases for itself, so neither can switch the other's activations off.
   // A DeepLIFT reference is a third user, while it is set and the handle is in LRP_PREC_FP32 (dl_active: its walk runs nowhere
-  // else, and the other modes' forwards keep their fused forms); encode() decides keep_acts from the three.
-  bool keep_acts = false, keep_for_train = false, keep_for_rule = false;
+  // else, and the other modes' forwards keep their fused forms); the layer trace (set_layer_trace) is a fourth, while it is on.
+  // encode() decides keep_acts from the four.
+  bool keep_acts = false, keep_for_train = false, keep_for_rule = false, keep_for_trace = false;
   int alloc_keep_acts(int64_t* total) {
     for (size_t li = 0; li + 1 < layers.size(); ++li) {
       ConvLayer& L = layers[li];
@@ -425,7 +428,7 @@ struct Encoder {
   int encode(const float* images_dev, int B, hipStream_t st) {
     if (B < 1 || B > max_images) return fail(LRP_ERR_INVALID, "B=%d outside [1,%d]", B, max_images);
     LRP_TRY(check_ready());
-    keep_acts = keep_for_train || keep_for_rule || dl_active();
+    keep_acts = keep_for_train || keep_for_rule || dl_active() || keep_for_trace;
     if (dl_active() && dl_ref_stale) LRP_TRY(dl_reference_pass(st));
     ++encode_epoch;
     for (ConvLayer& L : layers) L.gfull_epoch = encode_epoch;     // (every path writes the full-resolution gates, except the fused pool: after_pool_gate)
@@ -990,7 +993,7 @@ struct Encoder {
     if (!table_on()) return;
     table.clear();
     keep_for_rule = false;                               // (the buffers stay, idle; the fine-tune step's own request stands)
-    keep_acts = keep_for_train;
+    keep_acts = keep_for_train || keep_for_trace;
     encoded = 0;                                         // the caches belong to the old rule
   }
   // does layer li of `rules` walk on the default walk's own backward matrix (w+ tap-flipped; the image layer: w+ ; w-)?
@@ -1193,6 +1196,28 @@ struct Encoder {
     }
     return LRP_OK;
   }
+  // head of a rule's walk (KG:898-900 per chain): S_top = R / safe(den_top[img]) in the form the top layer's launch reads
+  int rule_head(const ConvRule& r, bool split, int n, const int* row2img_dev, const float* R_feat_dev, float* S, hipStream_t st) {
+    const ConvLayer& T = layers.back();
+    const float* za = r.own_gate() ? zt_top.as<float>() : ztop.as<float>();
+    const size_t pixels = (size_t)n * T.H * T.W, per = T.act_elems();
+    if (r.chains() == 2) {
+      const size_t items = pixels * (T.cout / (split ? 8 : 4));
+      if (split)
+        hipLaunchKernelGGL(chain_join_kernel<true>, dim3(stream_grid(items)), dim3(256), 0, st, R_feat_dev, R_feat_dev, za, zntop.as<float>(),
+                           row2img_dev, S, pixels, T.H * T.W, T.cout);
+      else
+        hipLaunchKernelGGL(chain_join_kernel<false>, dim3(stream_grid(items)), dim3(256), 0, st, R_feat_dev, R_feat_dev, za, zntop.as<float>(),
+                           row2img_dev, S, pixels, T.H * T.W, T.cout);
+    } else if (split) {
+      hipLaunchKernelGGL(top_divide_split_kernel, dim3(stream_grid((size_t)n * per / 8)), dim3(256), 0, st, R_feat_dev, za, row2img_dev, S, n, per / 8);
+    } else {
+      hipLaunchKernelGGL(top_divide_kernel, dim3(stream_grid((size_t)n * per / 4)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(R_feat_dev),
+                         reinterpret_cast<const f32x4*>(za), row2img_dev, reinterpret_cast<f32x4*>(S), n, per / 4);
+    }
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  }
   // the table's walk
   int explain_table(int n, const int* row2img_dev, const float* R_feat_dev, float* R_img_dev, hipStream_t st) {
     if (walk_f16) return fail(LRP_ERR_UNSUPPORTED, "LRP_PREC_F16X2 has no rule-table walk (its per-token scaling is per chain)");
@@ -1211,27 +1236,7 @@ struct Encoder {
     }
     const bool two = table_chains(table) == 2;
     float *S = two ? s0ab.as<float>() : s0.as<float>(), *Snext = two ? s1ab.as<float>() : s1.as<float>();
-    {
-      const ConvLayer& T = layers.back();
-      const ConvRule& r = table.back();
-      const float* za = r.own_gate() ? zt_top.as<float>() : ztop.as<float>();
-      const size_t pixels = (size_t)n * T.H * T.W, per = T.act_elems();
-      if (r.chains() == 2) {
-        const size_t items = pixels * (T.cout / (split ? 8 : 4));
-        if (split)
-          hipLaunchKernelGGL(chain_join_kernel<true>, dim3(stream_grid(items)), dim3(256), 0, st, R_feat_dev, R_feat_dev, za, zntop.as<float>(),
-                             row2img_dev, S, pixels, T.H * T.W, T.cout);
-        else
-          hipLaunchKernelGGL(chain_join_kernel<false>, dim3(stream_grid(items)), dim3(256), 0, st, R_feat_dev, R_feat_dev, za, zntop.as<float>(),
-                             row2img_dev, S, pixels, T.H * T.W, T.cout);
-      } else if (split) {
-        hipLaunchKernelGGL(top_divide_split_kernel, dim3(stream_grid((size_t)n * per / 8)), dim3(256), 0, st, R_feat_dev, za, row2img_dev, S, n, per / 8);
-      } else {
-        hipLaunchKernelGGL(top_divide_kernel, dim3(stream_grid((size_t)n * per / 4)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(R_feat_dev),
-                           reinterpret_cast<const f32x4*>(za), row2img_dev, reinterpret_cast<f32x4*>(S), n, per / 4);
-      }
-      LRP_HIP_CHECK(hipGetLastError());
-    }
+    LRP_TRY(rule_head(table.back(), split, n, row2img_dev, R_feat_dev, S, st));
     const ConvRule& r0 = table[0];
     const int img_mode = r0.kind == LRP_RULE_ALPHA_BETA ? 0 : r0.kind == LRP_RULE_EPSILON ? 2 : r0.kind == LRP_RULE_BOUNDED ? 3 : 1;
     for (int li = (int)layers.size() - 1; li >= 0; --li) {
@@ -1424,6 +1429,158 @@ struct Encoder {
     LRP_TRY(dl_final(two, c, images.as<float>(), layers[0].Xr.as<float>(), row2img_dev, R_img_dev, n, (size_t)img_h * img_w * 3, st));
     prof.end(st, 0.0);
     return LRP_OK;
+  }
+
+  // ---- layer trace (lrp_set_layer_trace, lrp_cnn_explain_traced; trace_kernels.h has the arithmetic) ----
+  // The reversed tensors of the reference's reverse analyzers: the head, and the relevance at the input of every node (conv or 2x2
+  // pool, in execution order).  While the switch is on the handle is one more user of keep_acts; nothing else changes, and what the
+  // traced walk needs beyond the rule's own buffers (the partials of its reductions) appears with the first traced call.
+  struct TraceTensor {
+    int nid, H, W, C;
+    size_t elems() const { return (size_t)H * W * C; }
+  };
+  // in sorted-id order: (-1, 0) the head, (0, 0) the image, ...
+  std::vector<TraceTensor> trace_tensors() const {
+    std::vector<TraceTensor> v;
+    v.push_back(TraceTensor{-1, top_h, top_w, top_c});
+    int nid = 0;
+    for (const ConvLayer& L : layers) {
+      v.push_back(TraceTensor{nid++, L.H, L.W, L.cin});
+      if (L.pool_after) v.push_back(TraceTensor{nid++, L.H, L.W, L.cout});
+    }
+    return v;
+  }
+  // index (in trace_tensors) of the input tensor of conv li; the pool behind conv li follows the conv's own
+  int trace_index_of_conv(int li) const {
+    int t = 1;
+    for (int q = 0; q < li; ++q) t += layers[q].pool_after ? 2 : 1;
+    return t;
+  }
+  // where the tensors `mask` selects lie in a keep buffer for n rows (floats; every tensor starts on a multiple of 4): -1 for the
+  // others.  Returns the buffer's size.
+  int64_t trace_keep_layout(int n, uint64_t mask, std::vector<int64_t>& off) const {
+    const std::vector<TraceTensor> tt = trace_tensors();
+    off.assign(tt.size(), -1);
+    int64_t cur = 0;
+    for (size_t t = 0; t < tt.size(); ++t) {
+      if (!((mask >> t) & 1)) continue;
+      off[t] = cur;
+      cur += ((int64_t)n * (int64_t)tt[t].elems() + 3) / 4 * 4;
+    }
+    return cur;
+  }
+  int set_layer_trace(bool on, int64_t* total) {
+    if (on == keep_for_trace) return LRP_OK;             // the same setting again changes nothing
+    if (on) LRP_TRY(alloc_keep_acts(total));
+    keep_for_trace = on;
+    encoded = 0;                                         // the next encode keeps (or stops keeping) the layer inputs
+    return LRP_OK;
+  }
+  static const ConvRule& default_rule() {
+    static const ConvRule r;
+    return r;
+  }
+  const ConvRule& rule_at(int li) const { return table_on() ? table[li] : default_rule(); }
+  int trace_check(int n) const {                         // mode before state, as dl_check
+    if (n < 1 || n > max_tokens) return fail(LRP_ERR_INVALID, "n=%d outside [1,%d]", n, max_tokens);
+    if (walk_f16) return fail(LRP_ERR_UNSUPPORTED, "LRP_PREC_F16X2 has no traced walk (its chains travel under per-token scales)");
+    if (table_on() && !table_runs()) return fail(LRP_ERR_UNSUPPORTED, "epsilon rules run in LRP_PREC_FP32 only");
+    if (!keep_for_trace) return fail(LRP_ERR_STATE, "lrp_set_layer_trace(h, 1) must be called before lrp_cnn_explain_traced");
+    if (encoded < 1 || features_only) return fail(LRP_ERR_STATE, "lrp_encode_images must run (after lrp_set_layer_trace) before lrp_cnn_explain_traced");
+    return LRP_OK;
+  }
+  DevBuf tr_part;                                        // [2 tensors][max_tokens][chunks of the largest layer][TRACE_PART] doubles
+  static int trace_chunks(const ConvLayer& L, bool split) {
+    const size_t items = (size_t)L.H * L.W * (L.cin / (split ? 8 : 4));
+    return (int)((items + TRACE_ITEMS_PER_BLOCK - 1) / TRACE_ITEMS_PER_BLOCK);
+  }
+  static int tensor_stats(const float* x, int rows, size_t per_row, double* stats, hipStream_t st) {
+    hipLaunchKernelGGL(tensor_stats_kernel, dim3(rows), dim3(1024), 0, st, x, per_row, stats);
+    return launched();
+  }
+  static int trace_layer(bool pool, bool split, int k, const TraceLayerArgs& t, int nblk, hipStream_t st) {
+    const dim3 grid(nblk, t.n);
+#define LRP_TRACE_CASE(P, S, K) \
+  if (pool == P && split == S && k == K) hipLaunchKernelGGL((trace_layer_kernel<P, S, K>), grid, dim3(256), 0, st, t)
+    LRP_TRACE_CASE(false, false, 1); LRP_TRACE_CASE(false, false, 2); LRP_TRACE_CASE(false, true, 1); LRP_TRACE_CASE(false, true, 2);
+    LRP_TRACE_CASE(true, false, 1); LRP_TRACE_CASE(true, false, 2); LRP_TRACE_CASE(true, true, 1); LRP_TRACE_CASE(true, true, 2);
+#undef LRP_TRACE_CASE
+    return launched();
+  }
+  // stats_dev (n_tensors, n, 4) float64; keep_dev with `keep_off` from trace_keep_layout (nullptr: nothing is kept)
+  int explain_traced(int n, const int* row2img_dev, const float* R_feat_dev, float* R_img_dev, double* stats_dev, float* keep_dev,
+                     const std::vector<int64_t>& keep_off, hipStream_t st) {
+    LRP_TRY(trace_check(n));
+    if (gates_pending) LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_gates, 0));   // gates / Z_top come from the side stream
+    const bool split = table_on() ? table_split() : rule_split();
+    const int rp = split ? PREC_BF16X3 : PREC_FP32;
+    const int nl = (int)layers.size();
+    bool two = false;
+    for (int li = 0; li < nl; ++li) two = two || rule_at(li).chains() == 2;
+    float *S = two ? s0ab.as<float>() : s0.as<float>(), *Snext = two ? s1ab.as<float>() : s1.as<float>();
+    const ConvRule& r0 = rule_at(0);
+    const int img_mode = r0.kind == LRP_RULE_ALPHA_BETA ? 0 : r0.kind == LRP_RULE_EPSILON ? 2 : r0.kind == LRP_RULE_BOUNDED ? 3 : 1;
+    auto conv_args = [&](int li) {
+      const ConvLayer& L = layers[li];
+      ConvArgs ca = conv3x3_args(L, n, S, rule_at(li).chains() * L.cout);
+      if (rule_on_default_matrix(rule_at(li))) ca.wpk = split ? L.w_bwd_s.as<float>() : L.w_bwd.as<float>();
+      else ca.wpk = split ? L.w_bwd_t_s.as<float>() : L.w_bwd_t.as<float>();
+      ca.row2img = row2img_dev;
+      if (li > 0) { ca.N = L.cin; ca.out = Snext; ca.gate_none = 1; ca.out_plain = 1; }
+      return ca;
+    };
+    // every launch is one conv_plan answers: asked before the first one runs
+    int max_chunks = 1;
+    for (int li = nl - 1; li >= 0; --li) {
+      ConvArgs ca = conv_args(li);
+      int epi = EPI_MUL;
+      if (li == 0) epi = image_layer_args(ca, n, Snext, R_img_dev, img_mode, r0.low, r0.high);
+      else max_chunks = std::max(max_chunks, trace_chunks(layers[li], false));   // (sized for either arithmetic: it never grows)
+      if (!conv_plan(conv_ask(epi, rp, 7, false, ca)).ok)
+        return fail(LRP_ERR_UNSUPPORTED, "conv %d: no launch reads %d chain(s) of %d channels into a plain accumulator", li, rule_at(li).chains(),
+                    layers[li].cout);
+    }
+    const size_t part_row = (size_t)max_chunks * TRACE_PART, part_tensor = (size_t)max_tokens * part_row;
+    if (!tr_part.p) LRP_TRY(tr_part.alloc(2 * part_tensor * sizeof(double), ws_total));
+    const std::vector<TraceTensor> tt = trace_tensors();
+    auto keep_ptr = [&](int t) -> float* { return keep_dev && keep_off[(size_t)t] >= 0 ? keep_dev + keep_off[(size_t)t] : nullptr; };
+    auto stats_of = [&](int t) { return stats_dev + (size_t)t * n * 4; };
+    auto whole = [&](int t, const float* x) -> int {     // a tensor that exists as such: the head, the image
+      LRP_TRY(tensor_stats(x, n, tt[(size_t)t].elems(), stats_of(t), st));
+      if (float* k = keep_ptr(t)) LRP_HIP_CHECK(hipMemcpyAsync(k, x, (size_t)n * tt[(size_t)t].elems() * sizeof(float), hipMemcpyDeviceToDevice, st));
+      return LRP_OK;
+    };
+    LRP_TRY(whole(0, R_feat_dev));
+    LRP_TRY(rule_head(rule_at(nl - 1), split, n, row2img_dev, R_feat_dev, S, st));
+    for (int li = nl - 1; li >= 1; --li) {
+      const ConvLayer &L = layers[li], &P = layers[li - 1];
+      const int k = rule_at(li - 1).chains();
+      prof.begin(st);
+      LRP_HIP_CHECK(conv_launch(EPI_MUL, conv_args(li), st, rp));
+      prof.end(st, (double)rule_at(li).chains() * layer_flop(n, li));
+      if (P.pool_after) LRP_TRY(full_gate(li - 1, st));
+      const int tc = trace_index_of_conv(li), nblk = trace_chunks(L, split);
+      TraceLayerArgs t{};
+      t.acc = Snext; t.a = layer_input(li); t.gpos = P.pool_after ? P.G.as<float>() : nullptr;
+      t.g0 = table_on() ? table_gate(li - 1) : P.G.as<float>(); t.g1 = k == 2 ? P.Gn.as<float>() : nullptr;
+      t.row2img = row2img_dev; t.S = S;
+      t.keep_conv = keep_ptr(tc); t.keep_pool = P.pool_after ? keep_ptr(tc - 1) : nullptr;
+      t.part_conv = tr_part.as<double>(); t.part_pool = tr_part.as<double>() + part_tensor;
+      t.n = n; t.H = L.H; t.W = L.W; t.C = L.cin;
+      prof.begin(st);
+      LRP_TRY(trace_layer(P.pool_after, split, k, t, nblk, st));
+      prof.end(st, 0.0);
+      hipLaunchKernelGGL(trace_finish_kernel, dim3((n + 63) / 64), dim3(64), 0, st, t.part_conv, n, nblk, stats_of(tc));
+      if (P.pool_after) hipLaunchKernelGGL(trace_finish_kernel, dim3((n + 63) / 64), dim3(64), 0, st, t.part_pool, n, nblk, stats_of(tc - 1));
+      LRP_HIP_CHECK(hipGetLastError());
+    }
+    ConvArgs ca = conv_args(0);
+    const int epi = image_layer_args(ca, n, Snext, R_img_dev, img_mode, r0.low, r0.high);
+    prof.begin(st);
+    LRP_HIP_CHECK(conv_launch(epi, ca, st, rp));
+    prof.end(st, (double)r0.chains() * layer_flop(n, 0));
+    LRP_TRY(image_stencil_tail(n, Snext, row2img_dev, R_img_dev, img_mode, r0.low, r0.high, st));
+    return whole(1, R_img_dev);
   }
 
   // R_feat_dev (n, top_h*top_w, top_c) -> R_img_dev (n, img_h, img_w, 3); row2img_dev: device int[n]

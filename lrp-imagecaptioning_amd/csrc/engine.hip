@@ -351,6 +351,77 @@ int lrp_cnn_explain(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const
   });
 }
 
+// ---- layer trace (Encoder::explain_traced) ----
+int lrp_set_layer_trace(lrp_handle* h, int32_t on) {
+  return with_handle(h, [&]() -> int {
+    if (!h) return fail(LRP_ERR_INVALID, "null handle");
+    if (on != 0 && on != 1) return fail(LRP_ERR_INVALID, "on must be 0 or 1");
+    if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "the layer trace is built for the VGG-style (conv-list) encoders only");
+    if ((on != 0) == h->enc.keep_for_trace) return LRP_OK;
+    LRP_TRY(h->trainer.drop_early_forward(nullptr));      // (it ran on the caches this drops)
+    return h->enc.set_layer_trace(on != 0, &h->ws_bytes);
+  });
+}
+
+int32_t lrp_trace_tensor_count(lrp_handle* h) {
+  return with_handle(h, [&]() -> int {
+    if (!h) return fail(LRP_ERR_INVALID, "null handle");
+    if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "the layer trace is built for the VGG-style (conv-list) encoders only");
+    return (int)h->enc.trace_tensors().size();
+  });
+}
+
+int lrp_trace_tensor_info(lrp_handle* h, int32_t index, int32_t n, uint64_t keep_mask, int32_t* nid, int32_t* H, int32_t* W, int32_t* C,
+                          int64_t* offset, int64_t* keep_floats) {
+  return with_handle(h, [&]() -> int {
+    if (!h) return fail(LRP_ERR_INVALID, "null handle");
+    if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "the layer trace is built for the VGG-style (conv-list) encoders only");
+    const std::vector<Encoder::TraceTensor> tt = h->enc.trace_tensors();
+    if (index < 0 || index >= (int)tt.size()) return fail(LRP_ERR_INVALID, "tensor %d outside [0,%d)", index, (int)tt.size());
+    if (n < 1 || n > h->enc.max_tokens) return fail(LRP_ERR_INVALID, "n=%d outside [1,%d]", n, h->enc.max_tokens);
+    if (tt.size() < 64 && (keep_mask >> tt.size()) != 0) return fail(LRP_ERR_INVALID, "keep_mask names tensors beyond the %d traced", (int)tt.size());
+    std::vector<int64_t> off;
+    const int64_t total = h->enc.trace_keep_layout(n, keep_mask, off);
+    const Encoder::TraceTensor& t = tt[(size_t)index];
+    if (nid) *nid = t.nid;
+    if (H) *H = t.H;
+    if (W) *W = t.W;
+    if (C) *C = t.C;
+    if (offset) *offset = off[(size_t)index];
+    if (keep_floats) *keep_floats = total;
+    return LRP_OK;
+  });
+}
+
+int lrp_cnn_explain_traced(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const float* R_feat_dev, float* R_img_dev,
+                           double* stats_dev, uint64_t keep_mask, float* keep_dev, int64_t keep_floats, void* stream) {
+  return with_handle(h, [&]() -> int {
+    if (!h || !img_idx_host || !R_feat_dev || !R_img_dev || !stats_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (h->resnet)
+      return fail(LRP_ERR_UNSUPPORTED, "the layer trace is built for the VGG-style (conv-list) encoders only (a ResNet's reversed graph has "
+                                       "some 350 nodes of six kinds, and its walk fuses several of them)");
+    // (checked before any staging: nothing runs on a refusal)
+    LRP_TRY(h->enc.trace_check(n));
+    const size_t nt = h->enc.trace_tensors().size();
+    if (nt < 64 && (keep_mask >> nt) != 0) return fail(LRP_ERR_INVALID, "keep_mask names tensors beyond the %d traced", (int)nt);
+    std::vector<int64_t> off;
+    const int64_t need = h->enc.trace_keep_layout(n, keep_dev ? keep_mask : 0, off);
+    if (keep_dev && keep_floats < need)
+      return fail(LRP_ERR_INVALID, "the keep buffer holds %lld floats, the selected tensors need %lld (lrp_trace_tensor_info)",
+                  (long long)keep_floats, (long long)need);
+    LRP_TRY(stage_indices(h, n, img_idx_host, nullptr, false, S(stream)));
+    return h->enc.explain_traced(n, h->idx_dev.as<int>(), R_feat_dev, R_img_dev, stats_dev, keep_dev, off, S(stream));
+  });
+}
+
+int lrp_op_tensor_stats(const float* x_dev, int32_t rows, int64_t per_row, double* stats_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (!x_dev || !stats_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (rows < 1 || per_row < 1) return fail(LRP_ERR_INVALID, "rows and per_row must be positive");
+    return Encoder::tensor_stats(x_dev, rows, (size_t)per_row, stats_dev, S(stream));
+  });
+}
+
 int lrp_explain_tokens(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const int32_t* t_host, int32_t variant,
                        float* R_img_dev, float* R_feat_dev, float* att_dev, double* r_words_dev, void* stream) {
   return with_handle(h, [&]() -> int {

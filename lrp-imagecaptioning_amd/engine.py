@@ -202,6 +202,82 @@ class LRPEngine(object):
                                               self._stream()))
         return out
 
+    # ------------------------------------------------------------------ layer trace
+    def set_layer_trace(self, on):
+        """The trace switch of a VGG-style engine (lrp_set_layer_trace): while on, encode_images keeps every conv's input and
+        cnn_explain_traced runs.  A change drops the encode caches: call encode_images again.  NotImplementedError on a
+        ResNet engine."""
+        on = bool(on)
+        _capi.check(self._lib.lrp_set_layer_trace(self._h, int(on)))
+        if on != getattr(self, "layer_trace", False):
+            self.n_images = 0                            # the library dropped the caches
+            self.captions = None
+        self.layer_trace = on
+
+    def _trace_info(self, n, mask):
+        """[(nid, (H, W, C), offset)] in sorted-id order and the keep buffer's size in floats, for n rows and `mask`"""
+        cnt = int(self._lib.lrp_trace_tensor_count(self._h))
+        if cnt < 0:
+            _capi.check(cnt)
+        vals = [C.c_int32() for _ in range(4)]
+        off, tot = C.c_int64(), C.c_int64()
+        out = []
+        for i in range(cnt):
+            _capi.check(self._lib.lrp_trace_tensor_info(self._h, i, n, mask, *[C.byref(v) for v in vals], C.byref(off), C.byref(tot)))
+            out.append((vals[0].value, (vals[1].value, vals[2].value, vals[3].value), off.value))
+        return out, tot.value
+
+    def trace_tensors(self):
+        """The traced tensors in sorted-id order, as the reference names its reversed tensors: [((nid, 0), (H, W, C))] —
+        (-1, 0) the head, (nid, 0) the relevance at the input of node nid (convs and 2x2 pools in execution order), (0, 0) the
+        image-level result."""
+        return [((nid, 0), shape) for nid, shape, _ in self._trace_info(1, 0)[0]]
+
+    def cnn_explain_traced(self, img_idx, R_feat, keep=(), out=None):
+        """cnn_explain with the relevance at every layer's input (lrp_cnn_explain_traced; needs set_layer_trace(True) and an
+        encode since).  keep: ids (nid, 0) or node ids of the tensors to return, True for all (False / None / (): none).  Returns (R_img, stats, kept):
+        stats (n_tensors, n, 4) float64 — minimum, maximum, sum, non-finite count per tensor (trace_tensors() order) and row;
+        kept: dict id -> (n, H, W, C) float32 tensor (views of one buffer)."""
+        n = len(img_idx)
+        ii, pi = _i32(img_idx)
+        R = self._dev(R_feat).reshape(n, self.L, self.D)
+        ids = [nid for nid, _, _ in self._trace_info(1, 0)[0]]
+        if keep is True:
+            want = list(ids)
+        elif keep is False or keep is None:
+            want = []
+        else:
+            want = [int(k[0]) if isinstance(k, (tuple, list)) else int(k) for k in keep]
+            for k in want:
+                if k not in ids:
+                    raise ValueError("no traced tensor (%d, 0): ids are (-1, 0) .. (%d, 0)" % (k, ids[-1]))
+        mask = sum(1 << ids.index(k) for k in set(want))
+        info, total = self._trace_info(n, mask)
+        if out is None:
+            out = torch.empty((n, self.img_hw[0], self.img_hw[1], 3), dtype=torch.float32, device=self.device)
+        stats = torch.empty((len(ids), n, 4), dtype=torch.float64, device=self.device)
+        buf = torch.empty((max(total, 1),), dtype=torch.float32, device=self.device) if mask else None
+        _capi.check(self._lib.lrp_cnn_explain_traced(self._h, n, pi, C.c_void_p(R.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                     C.c_void_p(stats.data_ptr()), mask,
+                                                     C.c_void_p(buf.data_ptr()) if buf is not None else None, total, self._stream()))
+        kept = {}
+        for nid, (H, W, Cc), off in info:
+            if off >= 0:
+                kept[(nid, 0)] = buf[off:off + n * H * W * Cc].view(n, H, W, Cc)
+        return out, stats, kept
+
+    def tensor_stats(self, x):
+        """Minimum, maximum, float64 sum and non-finite count of every row of x (rows, ...) float32 on the device
+        (lrp_op_tensor_stats): (rows, 4) float64.  min / max are NaN where the row holds a NaN; -0.0 orders below +0.0."""
+        x = self._dev(x)
+        if x.dim() < 1 or x.numel() == 0:
+            raise ValueError("x must be a non-empty (rows, ...) array")
+        rows = int(x.shape[0])
+        stats = torch.empty((rows, 4), dtype=torch.float64, device=self.device)
+        _capi.check(self._lib.lrp_op_tensor_stats(C.c_void_p(x.data_ptr()), rows, x.numel() // rows, C.c_void_p(stats.data_ptr()),
+                                                  self._stream()))
+        return stats
+
     # ------------------------------------------------------------------ fine-tune step (SURVEY 8f-2)
     def train_begin(self, lr=2e-4, clipvalue=0.01, beta1=0.9, beta2=0.999, eps=1e-7):
         """Adam(lr, clipvalue) as `ImgCaptioningAdaptiveAttentionLRPInferenceModel.build` compiles it (M:1370);

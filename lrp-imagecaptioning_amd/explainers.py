@@ -127,7 +127,8 @@ class ExplainImgCaptioningAttentionModel(object):
     _applies_cnn_rule = True     # the CNN half is the LRP walk (False: the gradient baselines, whose walks ignore the rule)
 
     def __init__(self, model, weight_path=None, dataset_provider=None, max_caption_length=20, max_images=1,
-                 device=None):
+                 device=None, layer_trace=False):
+        """layer_trace=True turns the engine's trace switch on (LRPEngine.set_layer_trace): `layer_relevance` then runs."""
         if weight_path:
             with np.load(weight_path) as z:               # stands in for keras load_weights (E:27)
                 model.weights.update({k: z[k] for k in z.files})
@@ -156,6 +157,9 @@ class ExplainImgCaptioningAttentionModel(object):
                 self._engine.set_cnn_rules(model.cnn_rules)
         elif self._applies_cnn_rule and tuple(getattr(model, "cnn_rule", None) or (1, 0)) != (1, 0):
             self._engine.set_cnn_rule(*model.cnn_rule)
+        self._layer_trace = bool(layer_trace)
+        if self._layer_trace:
+            self._engine.set_layer_trace(True)
         self._CNN_explainer = _EngineAnalyzer(self._engine)      # LRPSequentialPresetA(image_model, EPS, 'replace'), E:32
         self._state_cache = {}
         self.caption = None
@@ -242,6 +246,25 @@ class ExplainImgCaptioningAttentionModel(object):
             self.r_words = self._r_words_from(rw[n - 1].cpu().numpy(), n)
         rel = [Rn[i].reshape(1, g, g, self.D) for i in range(n)]
         return rel, self.attention[1:-1]
+
+    def layer_relevance(self, ts=None, keep=()):
+        """The relevance at every layer's input of the CNN walk, for the words `ts` (default: all) of the caption last forwarded:
+        the reverse analyzers' reverse_keep_tensors / reverse_check_* output (innvestigate/analyzer/base.py:570-603) per word.
+        Returns (ids, stats, kept): ids [(nid, 0)] sorted — (-1, 0) the head R_feat, (0, 0) the image; stats
+        (n_words, n_tensors, 4) float64 numpy — minimum, maximum, sum, non-finite count; kept: dict id -> (n_words, H, W, C)
+        float32 tensor for the ids in `keep` (True: all).  Needs layer_trace=True at construction."""
+        if not self._layer_trace:
+            raise RuntimeError("layer_relevance needs the trace switch: construct the explainer with layer_trace=True")
+        if self.caption is None:
+            raise RuntimeError("_forward_beam_search must run first")
+        ts = list(range(1, len(self.caption))) if ts is None else [int(t) for t in ts]
+        for t in ts:
+            self._check_t(t)
+        n = len(ts)
+        R, _, _ = self._engine.decoder_explain([0] * n, ts, variant="sequence", want_attention=False, want_r_words=False)
+        _, stats, kept = self._engine.cnn_explain_traced([0] * n, R, keep=keep)
+        ids = [i for i, _ in self._engine.trace_tensors()]
+        return ids, stats.permute(1, 0, 2).cpu().numpy(), kept
 
     # -------------------------------------------------------------- batched entry points (new)
     def explain_batch(self, images, captions, return_R_feat=False):
@@ -452,6 +475,9 @@ class _GradientMixin(object):
         n = R.shape[0]
         out = self._engine.cnn_walk([0] * n, R.reshape(n, self.L, self.D), self._walk)
         return out if as_tensor else out.cpu().numpy()
+
+    def layer_relevance(self, ts=None, keep=()):
+        raise NotImplementedError("the layer trace is built for the LRP walk only, not for the gradient-family walks")
 
     def _explain_lstm_single_word_sequence(self, t=0):
         raise NotImplementedError("the gradient engines explain through _lstm_decoder_backward")   # E:174-177 base stub
