@@ -266,9 +266,12 @@ int lrp_decoder_gradient(lrp_handle* h, int32_t n, const int32_t* img_idx_host, 
  * walks and nothing else.
  * LRP_WALK_DEEPLIFT (added without a version bump; innvestigate/analyzer/deeplift.py:44-250, see lrp_set_deeplift_reference):
  * VGG-style handles in LRP_PREC_FP32 only.  LRP_ERR_UNSUPPORTED on a ResNet handle and in every other precision mode;
- * LRP_ERR_STATE without a reference, or when lrp_encode_images has not run since the reference was set or changed. */
+ * LRP_ERR_STATE without a reference, or when lrp_encode_images has not run since the reference was set or changed.
+ * LRP_WALK_PATTERNNET / LRP_WALK_PATTERN_ATTRIBUTION (added without a version bump; analyzer/pattern_based.py:68-281, see
+ * lrp_pattern_fit_begin): VGG-style handles in LRP_PREC_FP32 only, on the patterns the handle holds.  LRP_ERR_UNSUPPORTED on a
+ * ResNet handle and in every other precision mode; LRP_ERR_STATE while a conv has no pattern, or with no encode. */
 enum { LRP_WALK_LRP = 0, LRP_WALK_GRADIENT = 1, LRP_WALK_INPUT_X_GRADIENT = 2, LRP_WALK_GUIDED_BACKPROP = 3, LRP_WALK_DECONVNET = 4,
-       LRP_WALK_DEEPLIFT = 5 };
+       LRP_WALK_DEEPLIFT = 5, LRP_WALK_PATTERNNET = 6, LRP_WALK_PATTERN_ATTRIBUTION = 7 };
 int lrp_cnn_walk(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const float* head_dev, float* out_dev,
                  int32_t walk, void* stream);
 
@@ -438,6 +441,38 @@ int lrp_trace_tensor_info(lrp_handle* h, int32_t index, int32_t n, uint64_t keep
 int lrp_cnn_explain_traced(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const float* R_feat_dev, float* R_img_dev,
                            double* stats_dev, uint64_t keep_mask, float* keep_dev, int64_t keep_floats, void* stream);
 int lrp_op_tensor_stats(const float* x_dev, int32_t rows, int64_t per_row, double* stats_dev, void* stream);
+
+/* PatternNet / PatternAttribution (added without a version bump; innvestigate/tools/pattern.py:220-336 — the fit — and
+ * analyzer/pattern_based.py:68-281 — the walk).  VGG-style handles, LRP_PREC_FP32.  Fit and walk are independent: the walk runs on
+ * whatever patterns the handle holds, fitted or set.
+ * The fit, per conv: X = the im2col rows of the layer input (K = 9 cin, zero padded), Y = X W (no bias, no activation), mask per
+ *   position and channel = 1 (LINEAR), [Y + b > 0] (RELU_POSITIVE) or [Y + b <= 0] (RELU_NEGATIVE).  Over every position of every
+ *   image accumulated, in float64 on the device: Sx[k][c] = sum X_k mask_c, Sxy[k][c] = sum X_k Y_c mask_c, cnt[c] = sum mask_c,
+ *   Sy[c] = sum Y_c, P = positions.  The pattern is A = cov / safe(sum_k W[k][c] cov[k][c]) with cov = Sxy / safe(cnt) -
+ *   Sx / safe(cnt) * Sy / P and safe(v) = v + [v == 0]; a channel that never satisfies the mask gets zeros.
+ * lrp_pattern_fit_begin: allocates and zeroes the sums (counted in lrp_workspace_bytes, as everything the pattern entries
+ *   allocate), makes the handle keep every conv's input at encode and drops the encode caches.
+ * lrp_pattern_fit_batch: accumulates the images of the last lrp_encode_images; a second call for the same encode is LRP_ERR_STATE.
+ * lrp_pattern_fit_end: computes the patterns from the sums and installs them; the fit is closed, its sums stay readable.
+ * lrp_pattern_stats: conv's sums as one float64 array [Sx (9 cin cout, HWIO) | Sxy (the same) | cnt (cout) | Sy (cout) | P (1)];
+ *   n_doubles must be that size.
+ * lrp_set_patterns / lrp_get_patterns: one conv's pattern, (3, 3, cin, cout) float32 on the device.
+ * lrp_set_pattern_projection: reverse_project_bottleneck_layers (default 1): every reversed tensor — the head, the tensor at every
+ *   conv's input, the result — is divided per row by its absolute maximum (1 where that is 0) before it is used.
+ * The walks: per conv the ReLU's gradient, then the conv's gradient with the kernel replaced by A (PATTERNNET) or A * W
+ *   (PATTERN_ATTRIBUTION); pools route to the forward's arg-max.  A row's result is the same bits at n = 1 and inside a larger call.
+ * LRP_ERR_UNSUPPORTED: a ResNet handle; outside LRP_PREC_FP32 (fit entries and walks); a launch lrp_conv_plan refuses.
+ * LRP_ERR_STATE: fit_batch / fit_end without fit_begin, fit_batch without an encode since or twice for one, fit_end without a
+ *   batch, stats before any fit, get without a pattern, a walk while a conv has no pattern or without an encode.
+ * LRP_ERR_INVALID: a conv index or type out of range, a wrong size.  Nothing is launched on a refusal. */
+enum { LRP_PATTERN_LINEAR = 0, LRP_PATTERN_RELU_POSITIVE = 1, LRP_PATTERN_RELU_NEGATIVE = 2 };
+int lrp_pattern_fit_begin(lrp_handle* h, int32_t type);
+int lrp_pattern_fit_batch(lrp_handle* h, void* stream);
+int lrp_pattern_fit_end(lrp_handle* h, void* stream);
+int lrp_pattern_stats(lrp_handle* h, int32_t conv, double* sums_dev, int64_t n_doubles, void* stream);
+int lrp_set_patterns(lrp_handle* h, int32_t conv, const float* A_hwio_dev, void* stream);
+int lrp_get_patterns(lrp_handle* h, int32_t conv, float* A_hwio_dev, void* stream);
+int lrp_set_pattern_projection(lrp_handle* h, int32_t on);
 
 /* Dominant-kernel timing for bench.py's roofline block: when enabled, HIP
  * events bracket every conv-LRP launch on the caller's stream; query returns

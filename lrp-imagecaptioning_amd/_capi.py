@@ -13,6 +13,7 @@ LRP_DEC_ADAPTIVE, LRP_DEC_GRIDTD = 0, 1
 LRP_ENC_VGG, LRP_ENC_RESNET = 0, 1
 LRP_EXPLAIN_SEQUENCE, LRP_EXPLAIN_SINGLE_STEP = 0, 1
 LRP_PREC_FP32, LRP_PREC_BF16X3, LRP_PREC_BF16X3_FAST, LRP_PREC_F16X2 = 0, 1, 2, 3
+LRP_PATTERN_LINEAR, LRP_PATTERN_RELU_POSITIVE, LRP_PATTERN_RELU_NEGATIVE = 0, 1, 2
 LRP_MAX_CONV = 32
 LRP_TRAIN_FP32, LRP_TRAIN_BF16 = 0, 1
 # lrp_conv_plan: epilogues, operand formats, forms, flags
@@ -74,6 +75,13 @@ SYMBOLS = {
     "lrp_trace_tensor_info": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_uint64] + [C.POINTER(C.c_int32)] * 4 + [C.POINTER(C.c_int64)] * 2),
     "lrp_cnn_explain_traced": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), _P, _P, _P, C.c_uint64, _P, C.c_int64, _P]),
     "lrp_op_tensor_stats": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P]),
+    "lrp_pattern_fit_begin": (C.c_int, [_P, C.c_int32]),
+    "lrp_pattern_fit_batch": (C.c_int, [_P, _P]),
+    "lrp_pattern_fit_end": (C.c_int, [_P, _P]),
+    "lrp_pattern_stats": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
+    "lrp_set_patterns": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "lrp_get_patterns": (C.c_int, [_P, C.c_int32, _P, _P]),
+    "lrp_set_pattern_projection": (C.c_int, [_P, C.c_int32]),
     "lrp_profile_enable": (C.c_int, [_P, C.c_int32]),
     "lrp_profile_query": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "lrp_profile_records": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32)]),

@@ -33,6 +33,11 @@ DeepLIFT and DeepTaylor (innvestigate/analyzer/deeplift.py:44-250, deeptaylor.py
 
     DeepLIFT(image_model, reference_inputs=0, approximate_gradient=True)    # LRPEngine.set_deeplift_reference + the 'deeplift' walk
     DeepTaylor(image_model) / BoundedDeepTaylor(image_model, low, high)     # the default walk / the bounded table, head [feat > 0]
+
+PatternNet and PatternAttribution (pattern_based.py:128-281), VGG-style encoders, reached by name as well:
+
+    PatternNet(image_model, patterns=None, pattern_type=None)               # .fit(X) / .fit_generator(gen) or patterns from
+    PatternAttribution(image_model, patterns=None, pattern_type=None)       # pattern.PatternComputer; the 'patternnet' / 'pattern_attribution' walks
 """
 import numpy as np
 
@@ -642,6 +647,58 @@ class DeepLIFTWrapper(object):
     def __init__(self, model=None, *args, **kwargs):
         raise ImportError("To use DeepLIFTWrapper please install the python module 'deeplift', "
                           "e.g.: 'pip install deeplift'")
+
+
+class PatternNet(_GradientWalkAnalyzer):
+    """pattern_based.py:128-247 for the VGG-style encoders, `analyze([X, head])` on the engine's 'patternnet' walk
+    (LRP_WALK_PATTERNNET, exact fp32): per conv + ReLU layer the ReLU's gradient, then the conv's gradient with the kernel replaced
+    by the layer's pattern; reverse_project_bottleneck_layers (default True) divides every reversed tensor by its absolute maximum.
+    patterns: one (3, 3, cin, cout) array per conv, e.g. from pattern.PatternComputer; None: call fit / fit_generator first
+    (pattern_type, default 'relu').  The other reverse_* switches are not built for this walk.  A ResNet spec is refused as the
+    reference refuses BatchNorm and Add layers."""
+    _walk = "patternnet"
+    _REVERSE_SWITCHES = ("reverse_keep_tensors", "reverse_check_min_max_values", "reverse_check_finite", "reverse_clip_values",
+                         "reverse_verbose")
+
+    def __init__(self, model, patterns=None, pattern_type=None, **kwargs):
+        if getattr(model, "resnet", None) is not None:
+            raise NotAnalyzeableModelException("PatternNet is only well defined for conv2d/max-pooling/dense layers.")   # :161-166
+        for k in self._REVERSE_SWITCHES:
+            if kwargs.pop(k, False):
+                raise NotImplementedError("%s is not built for the pattern walks" % k)
+        self._project = bool(kwargs.pop("reverse_project_bottleneck_layers", True))
+        if not self._project:
+            import warnings
+            warnings.warn("The standard setting for 'reverse_project_bottleneck_layers' is overwritten.")       # :178-181
+        self._patterns = list(patterns) if patterns is not None else None
+        self._pattern_type = pattern_type
+        super(PatternNet, self).__init__(model, **kwargs)
+        self._engine.set_pattern_projection(self._project)
+        if self._patterns is not None:
+            self._engine.set_patterns(self._patterns)
+
+    def fit(self, X=None, batch_size=32, **kwargs):
+        """base.py:248-257: the patterns from the data X (N, H, W, 3), batch_size images at a time."""
+        X = np.asarray(X, dtype=np.float32)
+        return self.fit_generator(X[lo:lo + batch_size] for lo in range(0, len(X), batch_size))
+
+    def fit_generator(self, generator, **kwargs):
+        """pattern_based.py:209-243: one pass over the batches the generator yields (arrays, or [array] lists)."""
+        pattern_type = "relu" if self._pattern_type is None else self._pattern_type
+        if isinstance(pattern_type, (list, tuple)):
+            raise ValueError("Only one pattern type allowed. Please pass a string.")                                # :228-230
+        from .pattern import fit_engine
+        self._patterns = fit_engine(self._engine, generator, pattern_type)
+
+    def analyze(self, X, neuron_selection=None):
+        if self._patterns is None:
+            raise RuntimeError("no patterns: pass patterns= or call fit / fit_generator before analyze")
+        return super(PatternNet, self).analyze(X, neuron_selection=neuron_selection)
+
+
+class PatternAttribution(PatternNet):
+    """pattern_based.py:250-281: PatternNet with the kernel replaced by pattern * kernel ('pattern_attribution' walk)."""
+    _walk = "pattern_attribution"
 
 
 class DeepTaylor(LRP):

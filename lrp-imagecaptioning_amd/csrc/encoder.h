@@ -20,7 +20,9 @@
 #include "deeplift_kernels.h"
 #include "f16_operand.h"
 #include "fwd_mode.h"
+#include "pattern_kernels.h"
 #include "trace_kernels.h"
+#include "train_gemm.h"
 
 namespace lrp {
 
@@ -83,6 +85,12 @@ struct ConvLayer {
   // from the reference's own forward — and per image the gate D = M ? safe(Y - Yr) : 0 (deeplift_kernels.h dl_gate_kernel; every
   // layer, the top one included).  Allocated by the first reference that is set.
   DevBuf Xr, Yr, Dl;
+  // PatternNet / PatternAttribution (Encoder::pattern_*): the fit's float64 sums [Sx | Sxy | cnt | Sy | P], the pattern
+  // A (HWIO, as fitted or as set) and its packed copies for the walk's transposed conv — A and A * w in w_bwd_full's layout,
+  // rebuilt by the next pattern walk after the pattern or the weights changed.  Allocated by the first pattern call that needs them.
+  DevBuf pat_sums, pat, pat_bwd, pat_bwd_w;
+  bool have_pat = false, pat_packed = false;
+  size_t pat_sum_doubles() const { return (size_t)2 * 9 * cin * cout + 2 * (size_t)cout + 1; }
   size_t act_elems() const { return (size_t)H * W * cout; }
 };
 
@@ -241,8 +249,8 @@ struct Encoder {
   // keep_acts = either; each asks and releases for itself, so neither can switch the other's activations off.
   // A DeepLIFT reference is a third user, while it is set and the handle is in LRP_PREC_FP32 (dl_active: its walk runs nowhere
   // else, and the other modes' forwards keep their fused forms); the layer trace (set_layer_trace) is a fourth, while it is on.
-  // encode() decides keep_acts from the four.
-  bool keep_acts = false, keep_for_train = false, keep_for_rule = false, keep_for_trace = false;
+  // A pattern fit (pattern_fit_begin .. pattern_fit_end) is a fifth.  encode() decides keep_acts from the five.
+  bool keep_acts = false, keep_for_train = false, keep_for_rule = false, keep_for_trace = false, keep_for_pattern = false;
   int alloc_keep_acts(int64_t* total) {
     for (size_t li = 0; li + 1 < layers.size(); ++li) {
       ConvLayer& L = layers[li];
@@ -377,6 +385,7 @@ struct Encoder {
     if (!L.have_w || !L.have_b) return fail(LRP_ERR_STATE, "layer %d has no operand copies to rebuild", li);
     LRP_TRY(repack_conv_weight_from_device(li, w_dev, tmp, st));
     L.t_packed = false;
+    L.pat_packed = false;
     if (table_on()) LRP_TRY(pack_table_layer(li, w_dev, st));
     L.norm_dirty = true;
     dl_ref_stale = true;
@@ -401,6 +410,7 @@ struct Encoder {
     L.have_w = true;
     L.norm_dirty = true;
     L.t_packed = false;                                // (repacked by the next encode under a rule table)
+    L.pat_packed = false;                              // (A * w belongs to the old weights: repacked by the next pattern walk)
     encoded = 0;                                       // caches belong to the old weights
     return LRP_OK;
   }
@@ -428,7 +438,7 @@ struct Encoder {
   int encode(const float* images_dev, int B, hipStream_t st) {
     if (B < 1 || B > max_images) return fail(LRP_ERR_INVALID, "B=%d outside [1,%d]", B, max_images);
     LRP_TRY(check_ready());
-    keep_acts = keep_for_train || keep_for_rule || dl_active() || keep_for_trace;
+    keep_acts = keep_for_train || keep_for_rule || dl_active() || keep_for_trace || keep_for_pattern;
     if (dl_active() && dl_ref_stale) LRP_TRY(dl_reference_pass(st));
     ++encode_epoch;
     for (ConvLayer& L : layers) L.gfull_epoch = encode_epoch;     // (every path writes the full-resolution gates, except the fused pool: after_pool_gate)
@@ -1581,6 +1591,255 @@ struct Encoder {
     prof.end(st, (double)r0.chains() * layer_flop(n, 0));
     LRP_TRY(image_stencil_tail(n, Snext, row2img_dev, R_img_dev, img_mode, r0.low, r0.high, st));
     return whole(1, R_img_dev);
+  }
+
+  // ---- PatternNet / PatternAttribution (lrp_pattern_*, LRP_WALK_PATTERNNET / _PATTERN_ATTRIBUTION; pattern_kernels.h) ----
+  // The fit and the walk are independent: the walk takes whatever patterns the layers hold, fitted here or set by the caller.
+  // Everything below is allocated by the first pattern call that needs it; a handle that never makes one allocates nothing.
+  int pat_type = -1;                                     // the running fit's mask (PAT_*), -1: no fit is open
+  long pat_fit_epoch = -1, pat_batches = 0;              // the encode accumulated last; batches accumulated by this fit
+  bool pat_project = true;                               // reverse_project_bottleneck_layers (pattern_based.py:175-183)
+  DevBuf pat_prod, pat_ws, pat_part;                     // fit: the batch's two products (fp32), the K-split workspace, the mask pass' partials
+  size_t pat_ws_floats = 0;
+  DevBuf pat_div, pat_maxpart;                           // walk: a row's divisor, the partials of its maximum
+  int pattern_mode_check() const {
+    if (prec != PREC_FP32)
+      return fail(LRP_ERR_UNSUPPORTED, "the pattern fit and walks run in LRP_PREC_FP32 only (a mask taken in another arithmetic is another mask): "
+                                       "set it with lrp_set_precision and call lrp_encode_images again");
+    return LRP_OK;
+  }
+  int pattern_fit_begin(int type, int64_t* total) {
+    if (type < PAT_LINEAR || type > PAT_RELU_NEGATIVE) return fail(LRP_ERR_INVALID, "unknown pattern type %d", type);
+    LRP_TRY(pattern_mode_check());
+    size_t max_kc = 0, max_cout = 0;
+    for (const ConvLayer& L : layers) {
+      max_kc = std::max(max_kc, (size_t)9 * L.cin * L.cout);
+      max_cout = std::max(max_cout, (size_t)L.cout);
+    }
+    if ((size_t)27 * layers[0].cout * sizeof(float) > 65536)
+      return fail(LRP_ERR_UNSUPPORTED, "the image layer's fit holds 27 x cout weights in LDS: cout <= 592");
+    auto mk = [&](DevBuf& d, size_t bytes) -> int { return d.p && d.bytes >= bytes ? LRP_OK : d.alloc(bytes, total); };
+    for (ConvLayer& L : layers) LRP_TRY(mk(L.pat_sums, L.pat_sum_doubles() * sizeof(double)));
+    LRP_TRY(mk(pat_prod, 2 * max_kc * sizeof(float)));
+    pat_ws_floats = 8 * max_kc;
+    LRP_TRY(mk(pat_ws, pat_ws_floats * sizeof(float)));
+    LRP_TRY(mk(pat_part, (size_t)PAT_MAX_CHUNKS * 2 * max_cout * sizeof(double)));
+    LRP_TRY(alloc_keep_acts(total));
+    LRP_HIP_CHECK(hipDeviceSynchronize());               // (an earlier fit's launches may still add to the sums)
+    for (ConvLayer& L : layers) LRP_HIP_CHECK(hipMemset(L.pat_sums.p, 0, L.pat_sum_doubles() * sizeof(double)));
+    LRP_HIP_CHECK(hipDeviceSynchronize());
+    pat_type = type; pat_fit_epoch = -1; pat_batches = 0;
+    keep_for_pattern = true;
+    encoded = 0;                                         // the next encode keeps the layer inputs
+    return LRP_OK;
+  }
+  int pattern_fit_check() const {
+    LRP_TRY(pattern_mode_check());
+    if (pat_type < 0) return fail(LRP_ERR_STATE, "lrp_pattern_fit_begin must be called first");
+    return LRP_OK;
+  }
+  // the images of the last encode: per conv c = conv(x) + b, the mask pass, the two products, the float64 sums
+  int pattern_fit_batch(hipStream_t st) {
+    LRP_TRY(pattern_fit_check());
+    if (encoded < 1 || features_only || !keep_acts)
+      return fail(LRP_ERR_STATE, "lrp_encode_images must run (after lrp_pattern_fit_begin) before lrp_pattern_fit_batch");
+    if (pat_fit_epoch == encode_epoch) return fail(LRP_ERR_STATE, "this encode is already part of the fit: an encode is accumulated at most once");
+    const int B = encoded;
+    float *c = bufA.as<float>(), *m = bufZ.as<float>(), *ym = bufXs.as<float>();
+    auto conv_args = [&](int li) {
+      ConvArgs ca = fwd_conv_args(layers[li], B, layer_input(li));
+      ca.wpk = layers[li].w_fwd_a.as<float>(); ca.N = layers[li].cout; ca.out = c;
+      return ca;
+    };
+    // every launch is one conv_plan answers: asked before the first one runs
+    for (int li = 1; li < (int)layers.size(); ++li)
+      if (!conv_plan(conv_ask(EPI_BIAS, PREC_FP32, 7, false, conv_args(li))).ok)
+        return fail(LRP_ERR_UNSUPPORTED, "conv %d: no exact-fp32 launch for its pre-activation", li);
+    for (int li = 0; li < (int)layers.size(); ++li) {
+      const ConvLayer& L = layers[li];
+      const long P = (long)B * L.H * L.W;
+      const size_t KC = (size_t)9 * L.cin * L.cout;
+      prof.begin(st);
+      if (li == 0) {
+        hipLaunchKernelGGL(pattern_image_conv_kernel, dim3(stream_grid((size_t)P * (L.cout / 4))), dim3(256), (size_t)27 * L.cout * sizeof(float), st,
+                           images.as<float>(), L.w_fwd.as<float>(), L.bias.as<float>(), c, B, L.H, L.W, L.cout);
+        LRP_HIP_CHECK(hipGetLastError());
+      } else {
+        LRP_HIP_CHECK(conv_launch(EPI_BIAS, conv_args(li), st, PREC_FP32));
+      }
+      prof.end(st, 2.0 * (double)P * (double)KC);
+      const long rows_per = std::max(256L, (P + PAT_MAX_CHUNKS - 1) / PAT_MAX_CHUNKS);
+      const int chunks = (int)((P + rows_per - 1) / rows_per);
+      prof.begin(st);
+      hipLaunchKernelGGL(pattern_mask_kernel, dim3(chunks), dim3(256), 0, st, c, L.bias.as<float>(), m, ym, pat_part.as<double>(), P, L.cout,
+                         rows_per, pat_type);
+      LRP_HIP_CHECK(hipGetLastError());
+      prof.end(st, 0.0);
+      SgemmArgs a{};                                     // X^T . rhs, all nine taps in one launch (the weight gradient's product)
+      a.A = layer_input(li); a.lda = L.cin; a.ldb = L.cout; a.ldc = L.cout;
+      a.M = L.cin; a.N = L.cout; a.K = P; a.transA = 1; a.transB = 0;
+      a.gather = 1; a.gH = L.H; a.gW = L.W; a.taps = 9; a.tapC = (long)L.cin * L.cout;
+      prof.begin(st);
+      a.B = m; a.C = pat_prod.as<float>();
+      LRP_HIP_CHECK(sgemm(a, pat_ws.as<float>(), pat_ws_floats, st));
+      a.B = ym; a.C = pat_prod.as<float>() + KC;
+      LRP_HIP_CHECK(sgemm(a, pat_ws.as<float>(), pat_ws_floats, st));
+      prof.end(st, 4.0 * (double)P * (double)KC);
+      prof.begin(st);
+      hipLaunchKernelGGL(pattern_accumulate_kernel, dim3(stream_grid(2 * KC)), dim3(256), 0, st, pat_prod.as<float>(), pat_part.as<double>(), chunks,
+                         L.pat_sums.as<double>(), KC, L.cout, (double)P);
+      LRP_HIP_CHECK(hipGetLastError());
+      prof.end(st, 0.0);
+    }
+    pat_fit_epoch = encode_epoch;
+    ++pat_batches;
+    return LRP_OK;
+  }
+  int pattern_alloc(ConvLayer& L) {
+    if (!L.pat.p) LRP_TRY(L.pat.alloc((size_t)9 * L.cin * L.cout * sizeof(float), ws_total));
+    return LRP_OK;
+  }
+  // sums -> patterns, installed; the fit is closed (its sums stay readable until the next lrp_pattern_fit_begin)
+  int pattern_fit_end(hipStream_t st) {
+    LRP_TRY(pattern_fit_check());
+    if (pat_batches < 1) return fail(LRP_ERR_STATE, "lrp_pattern_fit_batch must run at least once before lrp_pattern_fit_end");
+    for (ConvLayer& L : layers) LRP_TRY(pattern_alloc(L));
+    for (size_t li = 0; li < layers.size(); ++li) {
+      ConvLayer& L = layers[li];
+      const int CP = li == 0 ? 0 : conv_cinp(L.cin);
+      hipLaunchKernelGGL(pattern_compute_kernel, dim3(L.cout), dim3(256), 0, st, L.pat_sums.as<double>(),
+                         li == 0 ? L.w_fwd.as<float>() : L.w_fwd_a.as<float>(), li == 0 ? 64 : 9 * CP, CP, L.cin, L.cout, L.pat.as<float>());
+      LRP_HIP_CHECK(hipGetLastError());
+      L.have_pat = true;
+      L.pat_packed = false;
+    }
+    pat_type = -1;
+    keep_for_pattern = false;                            // (the caches of the last encode stay valid: they hold more than is needed)
+    return LRP_OK;
+  }
+  int pattern_set(int li, const float* A_dev, hipStream_t st) {
+    ConvLayer& L = layers[li];
+    LRP_TRY(pattern_alloc(L));
+    LRP_HIP_CHECK(hipMemcpyAsync(L.pat.p, A_dev, (size_t)9 * L.cin * L.cout * sizeof(float), hipMemcpyDeviceToDevice, st));
+    L.have_pat = true;
+    L.pat_packed = false;
+    return LRP_OK;
+  }
+  // the walk's matrices of every layer whose pattern or weights changed: A and A * w as the gradient walk's w_bwd_full is packed
+  int pattern_pack(hipStream_t st) {
+    for (size_t li = 0; li < layers.size(); ++li) {
+      ConvLayer& L = layers[li];
+      if (L.pat_packed) continue;
+      const size_t nb = li == 0 ? (size_t)conv_npad(IMG_T_COLS) * conv_cinp(L.cout) : (size_t)conv_npad(L.cin) * 9 * conv_cinp(L.cout);
+      for (DevBuf* d : {&L.pat_bwd, &L.pat_bwd_w}) {
+        if (d->p && d->bytes == nb * sizeof(float)) continue;
+        LRP_TRY(d->alloc(nb * sizeof(float), ws_total));
+        LRP_HIP_CHECK(hipMemsetAsync(d->p, 0, d->bytes, st));          // padding rows / columns stay zero
+      }
+      if (li == 0) {
+        hipLaunchKernelGGL(pattern_pack_image_kernel, dim3((27 * L.cout + 255) / 256), dim3(256), 0, st, L.pat.as<float>(), L.pat_bwd.as<float>(),
+                           L.cout, conv_cinp(L.cout));
+      } else {
+        const int CPo = conv_cinp(L.cout), Npb = conv_npad(L.cin);
+        hipLaunchKernelGGL(pack_conv_dev_kernel, dim3(stream_grid(nb)), dim3(256), 0, st, L.pat.as<float>(), L.pat_bwd.as<float>(), 1, L.cin,
+                           L.cout, CPo, Npb, 0, 0);
+      }
+      hipLaunchKernelGGL(pattern_mul_kernel, dim3(stream_grid(nb / 4)), dim3(256), 0, st, L.pat_bwd.as<f32x4>(), L.w_bwd_full.as<f32x4>(),
+                         L.pat_bwd_w.as<f32x4>(), nb / 4);
+      LRP_HIP_CHECK(hipGetLastError());
+      L.pat_packed = true;
+    }
+    return LRP_OK;
+  }
+  int pattern_walk_check(int n) const {                  // mode before state, as dl_check
+    if (n < 1 || n > max_tokens) return fail(LRP_ERR_INVALID, "n=%d outside [1,%d]", n, max_tokens);
+    LRP_TRY(pattern_mode_check());
+    for (const ConvLayer& L : layers)
+      if (!L.have_pat) return fail(LRP_ERR_STATE, "conv '%s' has no pattern: fit them (lrp_pattern_fit_*) or set them (lrp_set_patterns)", L.name.c_str());
+    if (encoded < 1 || features_only) return fail(LRP_ERR_STATE, "lrp_encode_images must run before the pattern walk");
+    return LRP_OK;
+  }
+  // a row's divisor: max |x| of each of the n rows of x, 1 where that is 0
+  int pattern_row_div(const float* x, int n, size_t per_row, hipStream_t st) {
+    const int chunks = pattern_chunks(per_row);
+    hipLaunchKernelGGL(pattern_absmax_part_kernel, dim3(chunks, n), dim3(256), 0, st, x, per_row, pat_maxpart.as<float>());
+    hipLaunchKernelGGL(pattern_absmax_finish_kernel, dim3((n + 63) / 64), dim3(64), 0, st, pat_maxpart.as<float>(), n, chunks, pat_div.as<float>());
+    return launched();
+  }
+  // The walk (pattern_based.py:68-125): per conv + ReLU layer the ReLU's gradient, then the conv's gradient with the kernel replaced
+  // by A (PatternNet) or A * w (PatternAttribution); every reversed tensor is divided by its row's absolute maximum first
+  // (pat_project; the head, every conv's input, the result — behind a pool the routed tensor's maximum is already 1).
+  int explain_pattern(int n, const int* row2img_dev, const float* head_dev, float* R_img_dev, bool attribution, hipStream_t st) {
+    LRP_TRY(pattern_walk_check(n));
+    if (gates_pending) LRP_HIP_CHECK(hipStreamWaitEvent(st, ev_gates, 0));
+    const int nl = (int)layers.size();
+    float *S = s0.as<float>(), *Snext = s1.as<float>();
+    auto matrix = [&](int li) { return attribution ? layers[li].pat_bwd_w.as<float>() : layers[li].pat_bwd.as<float>(); };
+    auto conv_args = [&](int li) {
+      const ConvLayer& L = layers[li];
+      ConvArgs ca = conv3x3_args(L, n, S, L.cout);
+      ca.wpk = matrix(li); ca.row2img = row2img_dev;
+      if (li > 0) { ca.N = L.cin; ca.out = Snext; ca.gate_none = 1; ca.out_plain = 1; }
+      return ca;
+    };
+    // every launch is one conv_plan answers: asked before the first one runs
+    const size_t img_row = (size_t)img_h * img_w * 3;
+    int max_chunks = std::max(pattern_chunks(layers.back().act_elems()), pattern_chunks(img_row));
+    for (int li = nl - 1; li >= 0; --li) {
+      ConvArgs ca = conv_args(li);
+      int epi = EPI_MUL;
+      if (li == 0) epi = image_layer_args(ca, n, Snext, R_img_dev, 1, 0.f, 0.f);
+      else max_chunks = std::max(max_chunks, pattern_chunks((size_t)layers[li].H * layers[li].W * layers[li].cin));
+      if (!conv_plan(conv_ask(epi, PREC_FP32, 7, false, ca)).ok)
+        return fail(LRP_ERR_UNSUPPORTED, "conv %d: no exact-fp32 launch reads %d channels into a plain accumulator", li, layers[li].cout);
+    }
+    if (!pat_div.p) {
+      LRP_TRY(pat_div.alloc((size_t)max_tokens * sizeof(float), ws_total));
+      LRP_TRY(pat_maxpart.alloc((size_t)max_tokens * max_chunks * sizeof(float), ws_total));
+    }
+    LRP_TRY(pattern_pack(st));
+    const float* div = pat_project ? pat_div.as<float>() : nullptr;
+    {
+      const ConvLayer& T = layers.back();                // the head, projected, through the top ReLU
+      const size_t per4 = T.act_elems() / 4;
+      prof.begin(st);
+      if (pat_project) LRP_TRY(pattern_row_div(head_dev, n, T.act_elems(), st));
+      hipLaunchKernelGGL(pattern_head_kernel, dim3(stream_grid((size_t)n * per4)), dim3(256), 0, st, reinterpret_cast<const f32x4*>(head_dev),
+                         feat.as<f32x4>(), row2img_dev, div, reinterpret_cast<f32x4*>(S), n, per4);
+      LRP_HIP_CHECK(hipGetLastError());
+      prof.end(st, 0.0);
+    }
+    for (int li = nl - 1; li >= 1; --li) {
+      const ConvLayer &L = layers[li], &P = layers[li - 1];
+      prof.begin(st);
+      LRP_HIP_CHECK(conv_launch(EPI_MUL, conv_args(li), st, PREC_FP32));
+      prof.end(st, layer_flop(n, li));
+      if (P.pool_after) LRP_TRY(full_gate(li - 1, st));
+      PatternProjectArgs t{};
+      t.acc = Snext; t.gate = P.G.as<float>(); t.row2img = row2img_dev; t.div = div; t.S = S;
+      t.n = n; t.H = L.H; t.W = L.W; t.C = L.cin;
+      prof.begin(st);
+      if (pat_project) LRP_TRY(pattern_row_div(Snext, n, (size_t)L.H * L.W * L.cin, st));
+      const dim3 grid(stream_grid((size_t)n * L.H * L.W * (L.cin / 4)));
+      if (P.pool_after) hipLaunchKernelGGL((pattern_project_kernel<true>), grid, dim3(256), 0, st, t);
+      else hipLaunchKernelGGL((pattern_project_kernel<false>), grid, dim3(256), 0, st, t);
+      LRP_HIP_CHECK(hipGetLastError());
+      prof.end(st, 0.0);
+    }
+    ConvArgs ca = conv_args(0);
+    const int epi = image_layer_args(ca, n, Snext, R_img_dev, 1, 0.f, 0.f);
+    prof.begin(st);
+    LRP_HIP_CHECK(conv_launch(epi, ca, st, PREC_FP32));
+    prof.end(st, layer_flop(n, 0));
+    LRP_TRY(image_stencil_tail(n, Snext, row2img_dev, R_img_dev, 1, 0.f, 0.f, st));
+    if (pat_project) {
+      prof.begin(st);
+      LRP_TRY(pattern_row_div(R_img_dev, n, img_row, st));
+      hipLaunchKernelGGL(pattern_scale_kernel, dim3(stream_grid((size_t)n * img_row / 4)), dim3(256), 0, st, R_img_dev, img_row, pat_div.as<float>(), n);
+      LRP_HIP_CHECK(hipGetLastError());
+      prof.end(st, 0.0);
+    }
+    return LRP_OK;
   }
 
   // R_feat_dev (n, top_h*top_w, top_c) -> R_img_dev (n, img_h, img_w, 3); row2img_dev: device int[n]

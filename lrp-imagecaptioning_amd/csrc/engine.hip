@@ -458,7 +458,13 @@ int lrp_cnn_walk(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const fl
                  void* stream) {
   return with_handle(h, [&]() -> int {
     if (!h || !img_idx_host || !head_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
-    if (walk < LRP_WALK_LRP || walk > LRP_WALK_DEEPLIFT) return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
+    if (walk < LRP_WALK_LRP || walk > LRP_WALK_PATTERN_ATTRIBUTION) return fail(LRP_ERR_INVALID, "unknown walk %d", walk);
+    if (walk == LRP_WALK_PATTERNNET || walk == LRP_WALK_PATTERN_ATTRIBUTION) {   // (as DeepLIFT: its own checks, nothing runs on a refusal)
+      if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "the pattern walks are built for the VGG-style (conv-list) encoders only");
+      LRP_TRY(h->enc.pattern_walk_check(n));
+      LRP_TRY(stage_indices(h, n, img_idx_host, nullptr, false, S(stream)));
+      return h->enc.explain_pattern(n, h->idx_dev.as<int>(), head_dev, out_dev, walk == LRP_WALK_PATTERN_ATTRIBUTION, S(stream));
+    }
     if (walk == LRP_WALK_DEEPLIFT) {                     // (its own checks, in its own order: mode before state; nothing runs on a refusal)
       if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "the DeepLIFT walk is built for the VGG-style (conv-list) encoders only");
       LRP_TRY(h->enc.dl_check(n));
@@ -474,6 +480,85 @@ int lrp_cnn_walk(lrp_handle* h, int32_t n, const int32_t* img_idx_host, const fl
     if (h->resnet) return h->rn.explain(n, h->idx_dev.as<int>(), head_dev, out_dev, S(stream), walk);
     h->enc.row2img_host = h->idx_pinned;
     return h->enc.explain(n, h->idx_dev.as<int>(), head_dev, out_dev, S(stream), walk);
+  });
+}
+
+// ---- PatternNet / PatternAttribution (Encoder::pattern_*) ----
+static int pattern_handle(lrp_handle* h) {
+  if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "patterns are built for the VGG-style (conv-list) encoders only (the reference refuses BatchNorm and Add too)");
+  return LRP_OK;
+}
+static int pattern_conv(lrp_handle* h, int32_t conv) {
+  LRP_TRY(pattern_handle(h));
+  if (conv < 0 || conv >= (int)h->enc.layers.size()) return fail(LRP_ERR_INVALID, "conv %d outside [0,%d)", conv, (int)h->enc.layers.size());
+  return LRP_OK;
+}
+
+int lrp_pattern_fit_begin(lrp_handle* h, int32_t type) {
+  return with_handle(h, [&]() -> int {
+    LRP_TRY(pattern_handle(h));
+    static_assert(LRP_PATTERN_LINEAR == lrp::PAT_LINEAR && LRP_PATTERN_RELU_POSITIVE == lrp::PAT_RELU_POSITIVE &&
+                  LRP_PATTERN_RELU_NEGATIVE == lrp::PAT_RELU_NEGATIVE, "lrp_hip.h LRP_PATTERN_*");
+    if (type < LRP_PATTERN_LINEAR || type > LRP_PATTERN_RELU_NEGATIVE) return fail(LRP_ERR_INVALID, "unknown pattern type %d", type);
+    LRP_TRY(h->enc.pattern_mode_check());
+    LRP_TRY(h->trainer.drop_early_forward(nullptr));      // (it ran on the caches this drops)
+    return h->enc.pattern_fit_begin(type, &h->ws_bytes);
+  });
+}
+
+int lrp_pattern_fit_batch(lrp_handle* h, void* stream) {
+  return with_handle(h, [&]() -> int {
+    LRP_TRY(pattern_handle(h));
+    return h->enc.pattern_fit_batch(S(stream));
+  });
+}
+
+int lrp_pattern_fit_end(lrp_handle* h, void* stream) {
+  return with_handle(h, [&]() -> int {
+    LRP_TRY(pattern_handle(h));
+    return h->enc.pattern_fit_end(S(stream));
+  });
+}
+
+int lrp_pattern_stats(lrp_handle* h, int32_t conv, double* sums_dev, int64_t n_doubles, void* stream) {
+  return with_handle(h, [&]() -> int {
+    LRP_TRY(pattern_conv(h, conv));
+    if (!sums_dev) return fail(LRP_ERR_INVALID, "null argument");
+    const ConvLayer& L = h->enc.layers[(size_t)conv];
+    if (n_doubles != (int64_t)L.pat_sum_doubles())
+      return fail(LRP_ERR_INVALID, "conv %d: the sums are %lld doubles (2 x 9 cin cout + 2 cout + 1), %lld given", conv,
+                  (long long)L.pat_sum_doubles(), (long long)n_doubles);
+    if (!L.pat_sums.p) return fail(LRP_ERR_STATE, "no fit has run: lrp_pattern_fit_begin allocates the sums");
+    LRP_HIP_CHECK(hipMemcpyAsync(sums_dev, L.pat_sums.p, L.pat_sum_doubles() * sizeof(double), hipMemcpyDeviceToDevice, S(stream)));
+    return LRP_OK;
+  });
+}
+
+int lrp_set_patterns(lrp_handle* h, int32_t conv, const float* A_hwio_dev, void* stream) {
+  return with_handle(h, [&]() -> int {
+    LRP_TRY(pattern_conv(h, conv));
+    if (!A_hwio_dev) return fail(LRP_ERR_INVALID, "null argument");
+    return h->enc.pattern_set(conv, A_hwio_dev, S(stream));
+  });
+}
+
+int lrp_get_patterns(lrp_handle* h, int32_t conv, float* A_hwio_dev, void* stream) {
+  return with_handle(h, [&]() -> int {
+    LRP_TRY(pattern_conv(h, conv));
+    if (!A_hwio_dev) return fail(LRP_ERR_INVALID, "null argument");
+    const ConvLayer& L = h->enc.layers[(size_t)conv];
+    if (!L.have_pat) return fail(LRP_ERR_STATE, "conv %d has no pattern: fit them (lrp_pattern_fit_*) or set them (lrp_set_patterns)", conv);
+    LRP_HIP_CHECK(hipMemcpyAsync(A_hwio_dev, L.pat.p, (size_t)9 * L.cin * L.cout * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
+    return LRP_OK;
+  });
+}
+
+int lrp_set_pattern_projection(lrp_handle* h, int32_t on) {
+  return with_handle(h, [&]() -> int {
+    LRP_TRY(pattern_handle(h));
+    if (on != 0 && on != 1) return fail(LRP_ERR_INVALID, "on must be 0 or 1");
+    h->enc.pat_project = on != 0;
+    return LRP_OK;
   });
 }
 

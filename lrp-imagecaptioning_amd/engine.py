@@ -455,7 +455,8 @@ class LRPEngine(object):
         return beam_lists(caps, lens)
 
     # ------------------------------------------------------------------ gradient baselines
-    WALKS = {"lrp": 0, "gradient": 1, "input_x_gradient": 2, "guided_backprop": 3, "deconvnet": 4, "deeplift": 5}
+    WALKS = {"lrp": 0, "gradient": 1, "input_x_gradient": 2, "guided_backprop": 3, "deconvnet": 4, "deeplift": 5,
+             "patternnet": 6, "pattern_attribution": 7}
 
     def decoder_gradient(self, img_idx, t, want_r_words=True):
         """_lstm_decoder_backward (explainers.py:780-832 / :1452-1532) for n (image, t) units: (n, L, D) float32
@@ -472,7 +473,8 @@ class LRPEngine(object):
     def cnn_walk(self, img_idx, head, walk="gradient", out=None):
         """Gradient / InputTimesGradient / GuidedBackprop `.analyze([X, head])` (gradient_based.py:101-265) on the
         cached forward of `lrp_encode_images`; walk='lrp' is cnn_explain; walk='deconvnet' (gradient_based.py:180-225) reads
-        no ReLU decision of the forward and runs in every precision mode on both encoders."""
+        no ReLU decision of the forward and runs in every precision mode on both encoders; 'patternnet' / 'pattern_attribution'
+        (pattern_based.py:68-281) run on the patterns of pattern_fit / set_patterns, VGG-style engines in 'fp32' mode only."""
         n = len(img_idx)
         ii, pi = _i32(img_idx)
         Hd = self._dev(head).reshape(n, self.L, self.D)
@@ -676,6 +678,88 @@ class LRPEngine(object):
             self.n_images = 0                            # the library dropped the caches of the other reference
             self.captions = None
         self._deeplift_key = key
+
+    # ------------------------------------------------------------------ PatternNet / PatternAttribution
+    PATTERN_TYPES = {"linear": _capi.LRP_PATTERN_LINEAR, "relu": _capi.LRP_PATTERN_RELU_POSITIVE,
+                     "relu.positive": _capi.LRP_PATTERN_RELU_POSITIVE, "relu.negative": _capi.LRP_PATTERN_RELU_NEGATIVE}
+
+    def _pattern_shapes(self):
+        return [(3, 3, int(cin), int(cout)) for _, cin, cout, _ in self.cnn_cfg]
+
+    def pattern_fit(self, images, pattern_type="relu", batch=None):
+        """Fit the patterns of every conv on `images` (B, H, W, 3) (tools/pattern.py:220-336; lrp_pattern_fit_*): the images are
+        encoded in batches of at most `batch` (default max_images) and accumulated on the device, then the patterns are computed
+        and installed.  pattern_type: 'linear', 'relu' (= 'relu.positive') or 'relu.negative'.  Returns get_patterns().
+        VGG-style engines in 'fp32' mode only.  The encode caches afterwards belong to the last batch."""
+        if pattern_type not in self.PATTERN_TYPES:
+            raise ValueError("unknown pattern type %r: one of %s" % (pattern_type, sorted(self.PATTERN_TYPES)))
+        x = self._dev(images)
+        if x.dim() != 4 or tuple(x.shape[1:]) != (self.img_hw[0], self.img_hw[1], 3):
+            raise ValueError("images must be (B,%d,%d,3)" % self.img_hw)
+        step = min(self.max_images, int(batch) if batch else self.max_images)
+        if step < 1 or x.shape[0] < 1:
+            raise ValueError("pattern_fit needs at least one image and a batch of at least 1")
+        self.pattern_fit_begin(pattern_type)
+        for lo in range(0, int(x.shape[0]), step):
+            self.encode_images(x[lo:lo + step])
+            self.pattern_fit_batch()
+        self.pattern_fit_end()
+        return self.get_patterns()
+
+    def pattern_fit_begin(self, pattern_type="relu"):
+        """Open a fit (lrp_pattern_fit_begin): zeroes the sums and drops the encode caches; then encode_images +
+        pattern_fit_batch per batch, pattern_fit_end to install the patterns."""
+        if pattern_type not in self.PATTERN_TYPES:
+            raise ValueError("unknown pattern type %r: one of %s" % (pattern_type, sorted(self.PATTERN_TYPES)))
+        _capi.check(self._lib.lrp_pattern_fit_begin(self._h, self.PATTERN_TYPES[pattern_type]))
+        self.n_images = 0
+        self.captions = None
+
+    def pattern_fit_batch(self):
+        _capi.check(self._lib.lrp_pattern_fit_batch(self._h, self._stream()))
+
+    def pattern_fit_end(self):
+        _capi.check(self._lib.lrp_pattern_fit_end(self._h, self._stream()))
+
+    def pattern_stats(self):
+        """The fit's float64 sums per conv (lrp_pattern_stats): a list of dicts with Sx, Sxy (3, 3, cin, cout), cnt, Sy (cout,)
+        and P (a float), as numpy arrays."""
+        out = []
+        for li, (_, _, cin, cout) in enumerate(self._pattern_shapes()):
+            kc = 9 * cin * cout
+            buf = torch.empty((2 * kc + 2 * cout + 1,), dtype=torch.float64, device=self.device)
+            _capi.check(self._lib.lrp_pattern_stats(self._h, li, C.c_void_p(buf.data_ptr()), buf.numel(), self._stream()))
+            b = buf.cpu().numpy()
+            out.append({"Sx": b[:kc].reshape(3, 3, cin, cout), "Sxy": b[kc:2 * kc].reshape(3, 3, cin, cout),
+                        "cnt": b[2 * kc:2 * kc + cout], "Sy": b[2 * kc + cout:2 * kc + 2 * cout], "P": float(b[-1])})
+        return out
+
+    def set_patterns(self, patterns):
+        """One (3, 3, cin, cout) array per conv (lrp_set_patterns): what the 'patternnet' / 'pattern_attribution' walks run on."""
+        shapes = self._pattern_shapes()
+        patterns = list(patterns)
+        if len(patterns) != len(shapes):
+            raise ValueError("one pattern per conv: %d given, %d convs" % (len(patterns), len(shapes)))
+        for li, (p, shp) in enumerate(zip(patterns, shapes)):
+            t = self._dev(p)
+            if tuple(t.shape) != shp:
+                raise ValueError("pattern %d: expected HWIO %s, got %s" % (li, shp, tuple(t.shape)))
+            _capi.check(self._lib.lrp_set_patterns(self._h, li, C.c_void_p(t.data_ptr()), self._stream()))
+
+    def get_patterns(self):
+        """The patterns the engine holds, fitted or set: a list of (3, 3, cin, cout) float32 numpy arrays (lrp_get_patterns)."""
+        out = []
+        for li, shp in enumerate(self._pattern_shapes()):
+            t = torch.empty(shp, dtype=torch.float32, device=self.device)
+            _capi.check(self._lib.lrp_get_patterns(self._h, li, C.c_void_p(t.data_ptr()), self._stream()))
+            out.append(t.cpu().numpy())
+        return out
+
+    def set_pattern_projection(self, on):
+        """reverse_project_bottleneck_layers of the pattern walks (lrp_set_pattern_projection; default on): every reversed tensor
+        is divided per row by its absolute maximum before it is used."""
+        _capi.check(self._lib.lrp_set_pattern_projection(self._h, int(bool(on))))
+        self.pattern_projection = bool(on)
 
     def set_fast_layers(self, mask):
         """Which conv layers take the two-MFMA form in 'f16x2' mode (lrp_set_fast_layers): bit li of `mask`, an iterable of

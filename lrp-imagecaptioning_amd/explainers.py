@@ -651,3 +651,62 @@ class ExplainImgCaptioningAdaptiveAttentionDeepLIFT(_DeepLIFTMixin, ExplainImgCa
 
 class ExplainImgCaptioningGridTDDeepLIFT(_DeepLIFTMixin, ExplainImgCaptioningGridTDModel):
     _STATE_ATTRS = ExplainImgCaptioningGridTDModel._STATE_ATTRS + ("o1t_act", "o2t_act")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# PatternNet / PatternAttribution (innvestigate/analyzer/pattern_based.py:128-281) as comparison engines, as the DeepLIFT pair:
+# decoder half = `_lstm_decoder_backward`; CNN half = the 'patternnet' / 'pattern_attribution' walk of the explainer's own engine
+# on the patterns given at construction (`patterns=`, one HWIO array per conv) or fitted by `fit_patterns(images)`.
+# ---------------------------------------------------------------------------------------------------------------
+class _PatternNetMixin(_GradientMixin):
+    _walk = "patternnet"
+
+    def __init__(self, *args, **kwargs):
+        patterns = kwargs.pop("patterns", None)
+        self._pattern_type = kwargs.pop("pattern_type", None)
+        project = kwargs.pop("reverse_project_bottleneck_layers", True)
+        super(_PatternNetMixin, self).__init__(*args, **kwargs)
+        if getattr(self._model, "resnet", None) is not None:
+            raise NotImplementedError("PatternNet is built for the VGG-style (conv-list) encoders only")
+        self._engine.set_pattern_projection(project)
+        self._has_patterns = patterns is not None
+        if self._has_patterns:
+            self._engine.set_patterns(list(patterns))
+
+    def fit_patterns(self, images, batch_size=32):
+        """Fit the patterns on `images` (N, H, W, 3) with the explainer's own engine (LRPEngine.pattern_fit).  The encode caches
+        then belong to the last batch: the cached caption and image are dropped."""
+        pattern_type = "relu" if self._pattern_type is None else self._pattern_type
+        if isinstance(pattern_type, (list, tuple)):
+            raise ValueError("Only one pattern type allowed. Please pass a string.")
+        self._engine.pattern_fit(images, pattern_type, batch=batch_size)
+        self._has_patterns = True
+        self._img_input = None
+        self.caption = None
+        self._state_cache = {}
+        return self._engine.get_patterns()
+
+    def _explain_CNN(self, X, relevance_value, as_tensor=False):
+        if not self._has_patterns:
+            raise RuntimeError("no patterns: pass patterns= or call fit_patterns(images) first")
+        return super(_PatternNetMixin, self)._explain_CNN(X, relevance_value, as_tensor=as_tensor)
+
+
+class _PatternAttributionMixin(_PatternNetMixin):
+    _walk = "pattern_attribution"
+
+
+class ExplainImgCaptioningAdaptiveAttentionPatternNet(_PatternNetMixin, ExplainImgCaptioningAdaptiveAttention):
+    _STATE_ATTRS = ExplainImgCaptioningAdaptiveAttention._STATE_ATTRS + ("ot_act",)
+
+
+class ExplainImgCaptioningAdaptiveAttentionPatternAttribution(_PatternAttributionMixin, ExplainImgCaptioningAdaptiveAttention):
+    _STATE_ATTRS = ExplainImgCaptioningAdaptiveAttention._STATE_ATTRS + ("ot_act",)
+
+
+class ExplainImgCaptioningGridTDPatternNet(_PatternNetMixin, ExplainImgCaptioningGridTDModel):
+    _STATE_ATTRS = ExplainImgCaptioningGridTDModel._STATE_ATTRS + ("o1t_act", "o2t_act")
+
+
+class ExplainImgCaptioningGridTDPatternAttribution(_PatternAttributionMixin, ExplainImgCaptioningGridTDModel):
+    _STATE_ATTRS = ExplainImgCaptioningGridTDModel._STATE_ATTRS + ("o1t_act", "o2t_act")
