@@ -357,7 +357,7 @@ int lrp_set_layer_trace(lrp_handle* h, int32_t on) {
     if (!h) return fail(LRP_ERR_INVALID, "null handle");
     if (on != 0 && on != 1) return fail(LRP_ERR_INVALID, "on must be 0 or 1");
     if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "the layer trace is built for the VGG-style (conv-list) encoders only");
-    if ((on != 0) == h->enc.keep_for_trace) return LRP_OK;
+    if ((on != 0) == h->enc.tr.on) return LRP_OK;
     LRP_TRY(h->trainer.drop_early_forward(nullptr));      // (it ran on the caches this drops)
     return h->enc.set_layer_trace(on != 0, &h->ws_bytes);
   });
@@ -376,13 +376,13 @@ int lrp_trace_tensor_info(lrp_handle* h, int32_t index, int32_t n, uint64_t keep
   return with_handle(h, [&]() -> int {
     if (!h) return fail(LRP_ERR_INVALID, "null handle");
     if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "the layer trace is built for the VGG-style (conv-list) encoders only");
-    const std::vector<Encoder::TraceTensor> tt = h->enc.trace_tensors();
+    const std::vector<TraceTensor> tt = h->enc.trace_tensors();
     if (index < 0 || index >= (int)tt.size()) return fail(LRP_ERR_INVALID, "tensor %d outside [0,%d)", index, (int)tt.size());
     if (n < 1 || n > h->enc.max_tokens) return fail(LRP_ERR_INVALID, "n=%d outside [1,%d]", n, h->enc.max_tokens);
     if (tt.size() < 64 && (keep_mask >> tt.size()) != 0) return fail(LRP_ERR_INVALID, "keep_mask names tensors beyond the %d traced", (int)tt.size());
     std::vector<int64_t> off;
     const int64_t total = h->enc.trace_keep_layout(n, keep_mask, off);
-    const Encoder::TraceTensor& t = tt[(size_t)index];
+    const TraceTensor& t = tt[(size_t)index];
     if (nid) *nid = t.nid;
     if (H) *H = t.H;
     if (W) *W = t.W;
@@ -525,11 +525,13 @@ int lrp_pattern_stats(lrp_handle* h, int32_t conv, double* sums_dev, int64_t n_d
     LRP_TRY(pattern_conv(h, conv));
     if (!sums_dev) return fail(LRP_ERR_INVALID, "null argument");
     const ConvLayer& L = h->enc.layers[(size_t)conv];
-    if (n_doubles != (int64_t)L.pat_sum_doubles())
+    const DevBuf& sums = h->enc.pat.layer[(size_t)conv].sums;
+    const size_t doubles = PatternState::sum_doubles(L.cin, L.cout);
+    if (n_doubles != (int64_t)doubles)
       return fail(LRP_ERR_INVALID, "conv %d: the sums are %lld doubles (2 x 9 cin cout + 2 cout + 1), %lld given", conv,
-                  (long long)L.pat_sum_doubles(), (long long)n_doubles);
-    if (!L.pat_sums.p) return fail(LRP_ERR_STATE, "no fit has run: lrp_pattern_fit_begin allocates the sums");
-    LRP_HIP_CHECK(hipMemcpyAsync(sums_dev, L.pat_sums.p, L.pat_sum_doubles() * sizeof(double), hipMemcpyDeviceToDevice, S(stream)));
+                  (long long)doubles, (long long)n_doubles);
+    if (!sums.p) return fail(LRP_ERR_STATE, "no fit has run: lrp_pattern_fit_begin allocates the sums");
+    LRP_HIP_CHECK(hipMemcpyAsync(sums_dev, sums.p, doubles * sizeof(double), hipMemcpyDeviceToDevice, S(stream)));
     return LRP_OK;
   });
 }
@@ -547,8 +549,9 @@ int lrp_get_patterns(lrp_handle* h, int32_t conv, float* A_hwio_dev, void* strea
     LRP_TRY(pattern_conv(h, conv));
     if (!A_hwio_dev) return fail(LRP_ERR_INVALID, "null argument");
     const ConvLayer& L = h->enc.layers[(size_t)conv];
-    if (!L.have_pat) return fail(LRP_ERR_STATE, "conv %d has no pattern: fit them (lrp_pattern_fit_*) or set them (lrp_set_patterns)", conv);
-    LRP_HIP_CHECK(hipMemcpyAsync(A_hwio_dev, L.pat.p, (size_t)9 * L.cin * L.cout * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
+    const PatternState::Layer& pl = h->enc.pat.layer[(size_t)conv];
+    if (!pl.have) return fail(LRP_ERR_STATE, "conv %d has no pattern: fit them (lrp_pattern_fit_*) or set them (lrp_set_patterns)", conv);
+    LRP_HIP_CHECK(hipMemcpyAsync(A_hwio_dev, pl.A.p, (size_t)9 * L.cin * L.cout * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
     return LRP_OK;
   });
 }
@@ -557,7 +560,7 @@ int lrp_set_pattern_projection(lrp_handle* h, int32_t on) {
   return with_handle(h, [&]() -> int {
     LRP_TRY(pattern_handle(h));
     if (on != 0 && on != 1) return fail(LRP_ERR_INVALID, "on must be 0 or 1");
-    h->enc.pat_project = on != 0;
+    h->enc.pat.project = on != 0;
     return LRP_OK;
   });
 }
@@ -576,7 +579,7 @@ int lrp_set_precision(lrp_handle* h, int32_t mode) {
       LRP_TRY(h->trainer.drop_early_forward(nullptr));
       h->enc.encoded = 0;
       h->rn.encoded = 0;
-      h->enc.dl_ref_stale = true;                        // (the DeepLIFT reference's activations go with the caches)
+      h->enc.dl.ref_stale = true;                        // (the DeepLIFT reference's activations go with the caches)
     }
     h->enc.prec = km;
     h->enc.fwd_fast = fast;
@@ -588,15 +591,15 @@ int lrp_set_precision(lrp_handle* h, int32_t mode) {
 
 // The rule of a VGG handle, from either entry: `t` is validated, one record per conv.  Alpha-beta with the bias and beta == 0 on every
 // conv is the default walk, which is the empty table.
-static int set_vgg_table(lrp_handle* h, std::vector<Encoder::ConvRule> t) {
+static int set_vgg_table(lrp_handle* h, std::vector<ConvRule> t) {
   Encoder& e = h->enc;
   bool is_default = true;
-  for (const Encoder::ConvRule& r : t)
+  for (const ConvRule& r : t)
     if (r.kind != LRP_RULE_ALPHA_BETA || !r.bias || r.beta > 0.f) is_default = false;
   if (is_default) t.clear();
-  bool same = t.size() == e.table.size();                // the same rule again changes nothing
+  bool same = t.size() == e.rules.table.size();          // the same rule again changes nothing
   for (size_t i = 0; same && i < t.size(); ++i) {
-    const Encoder::ConvRule &a = e.table[i], &b = t[i];
+    const ConvRule &a = e.rules.table[i], &b = t[i];
     if (a.kind != b.kind || a.bias != b.bias || a.alpha != b.alpha || a.eps != b.eps || a.low != b.low || a.high != b.high) same = false;
   }
   if (same) return LRP_OK;
@@ -629,15 +632,15 @@ int lrp_set_cnn_rule(lrp_handle* h, float alpha, float beta) {
       return fail(LRP_ERR_INVALID, "alpha - beta should be 1 (alpha=%g, beta=%g)", (double)alpha, (double)beta);
     beta = alpha - 1.f;
     if (h->resnet) return h->rn.set_rule(alpha, beta);    // (refuses beta > 0 on widths that are no multiples of 8)
-    Encoder::ConvRule r;                                 // the one rule is a uniform table (with the bias, as RR:274-322 has it)
+    ConvRule r;                                          // the one rule is a uniform table (with the bias, as RR:274-322 has it)
     r.alpha = alpha; r.beta = beta;
-    return set_vgg_table(h, std::vector<Encoder::ConvRule>(h->enc.layers.size(), r));
+    return set_vgg_table(h, std::vector<ConvRule>(h->enc.layers.size(), r));
   });
 }
 
 // One record of either rule entry, value-checked into `o`.  i: the conv the record is for, 0 = the input layer — flat, w-square and
 // bounded are refused above it
-static int check_conv_rule(const lrp_conv_rule& r, int i, Encoder::ConvRule& o) {
+static int check_conv_rule(const lrp_conv_rule& r, int i, ConvRule& o) {
   if (r.kind < LRP_RULE_ALPHA_BETA || r.kind > LRP_RULE_BOUNDED) return fail(LRP_ERR_INVALID, "conv %d: unknown rule kind %d", i, r.kind);
   o.kind = r.kind;
   if (o.input_only() && i > 0)
@@ -669,7 +672,7 @@ int lrp_set_cnn_rules(lrp_handle* h, const lrp_conv_rule* rules, int32_t n_rules
     if (h->resnet) return fail(LRP_ERR_UNSUPPORTED, "the ResNet encoder's walk has no rule per conv: lrp_set_resnet_rules takes a rule pair");
     if (!rules || n_rules != (int)h->enc.layers.size())
       return fail(LRP_ERR_INVALID, "one rule per conv: %d given, %d convs", rules ? n_rules : 0, (int)h->enc.layers.size());
-    std::vector<Encoder::ConvRule> t((size_t)n_rules);
+    std::vector<ConvRule> t((size_t)n_rules);
     for (int i = 0; i < n_rules; ++i) LRP_TRY(check_conv_rule(rules[i], i, t[(size_t)i]));
     if (t[0].input_only() && n_rules < 2) return fail(LRP_ERR_UNSUPPORTED, "an input-layer rule needs a conv above the image layer");
     return set_vgg_table(h, std::move(t));
@@ -692,10 +695,10 @@ int lrp_set_resnet_rules(lrp_handle* h, const lrp_conv_rule* stem, const lrp_con
     if (!h) return fail(LRP_ERR_INVALID, "null handle");
     if (!h->resnet) return fail(LRP_ERR_UNSUPPORTED, "a VGG-style handle takes a rule per conv: lrp_set_cnn_rules");
     if (!stem || !units) return fail(LRP_ERR_INVALID, "lrp_set_resnet_rules: two records, the stem's and the other convs'");
-    Encoder::ConvRule cs, cu;
+    ConvRule cs, cu;
     LRP_TRY(check_conv_rule(*stem, 0, cs));
     LRP_TRY(check_conv_rule(*units, 1, cu));
-    auto rec = [](const Encoder::ConvRule& c) {
+    auto rec = [](const ConvRule& c) {
       ResNetEncoder::Rule r;
       r.kind = c.kind; r.bias = c.bias; r.alpha = c.alpha; r.beta = c.beta; r.eps = c.eps; r.low = c.low; r.high = c.high;
       return r;
