@@ -699,6 +699,51 @@ int lrp_perturb_apply(const float* x_dev, const int32_t* img_idx_dev, const int3
 int lrp_perturb_word_scores(lrp_handle* h, const int32_t* slot_dev, const int32_t* t_dev, const int32_t* k_dev, int32_t n,
                             double* logit_dev, double* logp_dev, void* stream);
 
+/* Occlusion sensitivity (Zeiler & Fergus 2014) and RISE (Petsiuk et al. 2018) word saliency: masked copies of the image go
+ * through lrp_encode_images / lrp_decoder_forward / lrp_perturb_word_scores, and the word scores are folded back into a map.
+ * Handle-free operators like lrp_op_augment_* and lrp_perturb_*: device pointers, the caller's stream, no synchronisation;
+ * additive to the ABI.  Every argument is checked before any HIP call.  A row's output is a pure function of its arguments: any
+ * cut of the rows into calls, and any position of a row in a call, gives the same bits.  (csrc/saliency_kernels.h)
+ * Occlusion geometry: window (ph, pw), stride (sh, sw) with 1 <= sh <= ph <= H and 1 <= sw <= pw <= W (else LRP_ERR_INVALID);
+ *   Hn = ceil((H - ph) / sh) + 1, Wn alike; window k = i * Wn + j covers rows [i sh, min(i sh + ph, H)) and columns
+ *   [j sw, min(j sw + pw, W)): the last window of an axis is clipped, every pixel is covered.  More than 65536 windows:
+ *   LRP_ERR_RANGE.
+ * lrp_op_occlude: out_dev (n, H, W, C) float32: row r is image img_idx_dev[r] of x_dev (B, H, W, C) with window k_dev[r] set to
+ *   fill_dev[c] (C floats on the device), every channel; k = -1 copies the image (the unoccluded score).  An image index outside
+ *   [0, B) or a k outside [-1, Hn Wn) gives a NaN row.  16-byte accesses when H W C % 4 == 0 and both tensors are 16-byte aligned.
+ * lrp_op_occlusion_map: scores_dev (n_img, 1 + Hn Wn, T) float64, row 0 the unoccluded score -> out_dev (n_img, T, H, W) float32:
+ *   S[t][y][x] = (sum over the windows k covering (y, x), ascending k, of s_0[t] - s_{1+k}[t]) / c(y, x), c the number of covering
+ *   windows, in float64, rounded once.  A gather: no atomics.
+ * lrp_op_rise_grids: mask (key, k) -> grid_dev (n, (s + 1)^2) uint8 cells in {0, 1} and shift_dev (n, 2) int32 (dy, dx).  key_dev
+ *   (n) uint32 is the caller's identity of the image, not its slot; k_dev (n) int32 the mask number.  Philox4x32-10 as in
+ *   lrp_op_augment_gaussian with key = (seed & 0xFFFFFFFF, seed >> 32): cell e = a (s + 1) + c takes lane e % 4 of counter
+ *   (e / 4, k, key, 1) (the last word 1 separates the stream from the Gaussian augment's 0); G = 1 iff (x >> 8) < floor(p 2^24)
+ *   (computed in double; p = 1: all ones).  The shifts come from counter (0xFFFFFFFF, k, key, 1): dy = x0 % ch, dx = x1 % cw;
+ *   the modulo bias (at most ch / 2^32) is accepted.  1 <= s <= 63 (else LRP_ERR_RANGE); 0 < p <= 1, ch >= ceil(H / s),
+ *   cw >= ceil(W / s), ch, cw <= 2^20 (else LRP_ERR_INVALID).
+ * lrp_op_rise_apply: out_dev (n, H, W, C) = fill + m (x - fill) in float32, each operation rounded on its own, row r from image
+ *   img_idx_dev[r] with the mask of grid_dev[r], shift_dev[r].  The mask at pixel (y, x): Y = y + dy, ny = 2 Y + 1 - ch,
+ *   a0 = floor_div(ny, 2 ch), fy = (ny - 2 ch a0) / (2 ch), rows a0 and a0 + 1 clamped into [0, s]; columns alike;
+ *   m = top + fy (bot - top) with top = G[a0][c0] + fx (G[a0][c1] - G[a0][c0]) and bot alike on row a1: the half-pixel-centre
+ *   bilinear upsample of the (s + 1)^2 grid by exactly (ch, cw), cropped at (dy, dx).  (RISE itself resizes an s x s grid by a
+ *   non-integer factor; the two agree in distribution away from the border.)  A row whose image index is outside [0, B) or whose
+ *   shift is outside [0, ch) x [0, cw) comes out as NaN.
+ * lrp_op_rise_map: scores_dev (n_img, K, T) float64, grid_dev (n_img, K, (s + 1)^2), shift_dev (n_img, K, 2) -> out_dev
+ *   (n_img, T, H, W) float32: S[t][y][x] = (sum over k ascending of s_k[t] m_k(y, x)) / (K p), masks recomputed in float64 from
+ *   the grids, one thread per pixel adding its K terms in ascending k (the order depends on K only), rounded once. */
+int lrp_op_occlude(const float* x_dev, const int32_t* img_idx_dev, const int32_t* k_dev, const float* fill_dev, float* out_dev,
+                   int32_t n, int32_t B, int32_t H, int32_t W, int32_t C, int32_t ph, int32_t pw, int32_t sh, int32_t sw,
+                   void* stream);
+int lrp_op_occlusion_map(const double* scores_dev, float* out_dev, int32_t n_img, int32_t T, int32_t H, int32_t W, int32_t ph,
+                         int32_t pw, int32_t sh, int32_t sw, void* stream);
+int lrp_op_rise_grids(const uint32_t* key_dev, const int32_t* k_dev, int32_t n, int32_t s, double p, uint64_t seed, int32_t H,
+                      int32_t W, int32_t ch, int32_t cw, uint8_t* grid_dev, int32_t* shift_dev, void* stream);
+int lrp_op_rise_apply(const float* x_dev, const int32_t* img_idx_dev, const uint8_t* grid_dev, const int32_t* shift_dev,
+                      const float* fill_dev, float* out_dev, int32_t n, int32_t B, int32_t H, int32_t W, int32_t C, int32_t s,
+                      int32_t ch, int32_t cw, void* stream);
+int lrp_op_rise_map(const double* scores_dev, const uint8_t* grid_dev, const int32_t* shift_dev, float* out_dev, int32_t n_img,
+                    int32_t K, int32_t T, int32_t H, int32_t W, int32_t s, double p, int32_t ch, int32_t cw, void* stream);
+
 /* Operator-level entries of the fine-tune step's dense products (unit tests at real layer sizes; csrc/train_gemm.h).
  * lrp_op_sgemm: C (+)= op(A) op(B) on the fp32 matrix cores, row-major with leading dimensions;
  *   op(A)[m][k] = transA ? A[k*lda + m] : A[m*lda + k], op(B)[k][n] = transB ? B[n*ldb + k] : B[k*ldb + n]

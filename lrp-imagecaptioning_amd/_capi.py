@@ -134,6 +134,11 @@ SYMBOLS = {
     "lrp_perturb_ranks": (C.c_int, [_P] + [C.c_int32] * 10 + [_P, _P, _P]),
     "lrp_perturb_apply": (C.c_int, [_P] * 6 + [C.c_int32] * 10 + [C.c_float, C.c_float, _P]),
     "lrp_perturb_word_scores": (C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, _P]),
+    "lrp_op_occlude": (C.c_int, [_P] * 5 + [C.c_int32] * 9 + [_P]),
+    "lrp_op_occlusion_map": (C.c_int, [_P, _P] + [C.c_int32] * 8 + [_P]),
+    "lrp_op_rise_grids": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_double, C.c_uint64] + [C.c_int32] * 4 + [_P, _P, _P]),
+    "lrp_op_rise_apply": (C.c_int, [_P] * 6 + [C.c_int32] * 8 + [_P]),
+    "lrp_op_rise_map": (C.c_int, [_P] * 4 + [C.c_int32] * 6 + [C.c_double, C.c_int32, C.c_int32, _P]),
     "lrp_last_error": (C.c_char_p, []),
     "lrp_abi_version": (C.c_int, []),
     "lrp_launch_count": (C.c_int64, []),

@@ -23,6 +23,7 @@
 #include "perturb_kernels.h"
 #include "resnet_encoder.h"
 #include "rules_kernels.h"
+#include "saliency_kernels.h"
 #include "score_kernels.h"
 #include "trainer.h"
 
@@ -1592,6 +1593,131 @@ int lrp_perturb_word_scores(lrp_handle* h, const int32_t* slot_dev, const int32_
     if (!h->dec.have_forward) return fail(LRP_ERR_STATE, "lrp_decoder_forward must run before lrp_perturb_word_scores");
     hipLaunchKernelGGL(perturb_word_score_kernel, dim3(n), dim3(256), 0, S(stream), h->dec.S_<double>("caption_preds"), slot_dev,
                        t_dev, k_dev, h->dec.B_cur, h->dec.Tm, h->dec.V, logit_dev, logp_dev);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+
+// ---- occlusion and RISE word saliency (csrc/saliency_kernels.h)
+static int saliency_image(int32_t H, int32_t W, int32_t C) {
+  if (H < 1 || W < 1 || C < 1) return fail(LRP_ERR_INVALID, "H, W, C must be positive");
+  if ((int64_t)H * W * C > INT32_MAX) return fail(LRP_ERR_INVALID, "one image must hold fewer than 2^31 values");
+  return LRP_OK;
+}
+
+static int occlusion_geometry(int32_t H, int32_t W, int32_t C, int32_t ph, int32_t pw, int32_t sh, int32_t sw, OccGeom* g) {
+  LRP_TRY(saliency_image(H, W, C));
+  if (sh < 1 || sh > ph || ph > H || sw < 1 || sw > pw || pw > W)
+    return fail(LRP_ERR_INVALID, "occlusion needs 1 <= stride <= window <= image on both axes: window (%d, %d), stride (%d, %d), "
+                "image (%d, %d)", ph, pw, sh, sw, H, W);
+  const int64_t Hn = (H - ph + sh - 1) / sh + 1, Wn = (W - pw + sw - 1) / sw + 1;
+  if (Hn * Wn > OCC_MAX_WINDOWS) return fail(LRP_ERR_RANGE, "%lld windows: at most %d are scored", (long long)(Hn * Wn), OCC_MAX_WINDOWS);
+  *g = OccGeom{H, W, C, ph, pw, sh, sw, (int)Hn, (int)Wn};
+  return LRP_OK;
+}
+
+static int rise_geometry(int32_t H, int32_t W, int32_t C, int32_t s, int32_t ch, int32_t cw, RiseGeom* g) {
+  LRP_TRY(saliency_image(H, W, C));
+  if (s < 1 || s > RISE_MAX_S) return fail(LRP_ERR_RANGE, "RISE grid s=%d outside [1,%d]", s, RISE_MAX_S);
+  if (ch < (H + s - 1) / s || cw < (W + s - 1) / s)
+    return fail(LRP_ERR_INVALID, "RISE cell (%d, %d) is below (ceil(H / s), ceil(W / s)) = (%d, %d): the grid would not cover the image",
+                ch, cw, (H + s - 1) / s, (W + s - 1) / s);
+  if (ch > RISE_MAX_CELL || cw > RISE_MAX_CELL) return fail(LRP_ERR_INVALID, "a RISE cell side may not exceed %d", RISE_MAX_CELL);
+  *g = RiseGeom{H, W, C, s, ch, cw};
+  return LRP_OK;
+}
+
+static int rise_probability(double p) {
+  if (!(p > 0.0) || !(p <= 1.0)) return fail(LRP_ERR_INVALID, "RISE needs 0 < p <= 1 (p=%g)", p);
+  return LRP_OK;
+}
+
+static bool aligned16(const void* a, const void* b) { return (((uintptr_t)a | (uintptr_t)b) & 15) == 0; }
+
+int lrp_op_occlude(const float* x_dev, const int32_t* img_idx_dev, const int32_t* k_dev, const float* fill_dev, float* out_dev,
+                   int32_t n, int32_t B, int32_t H, int32_t W, int32_t C, int32_t ph, int32_t pw, int32_t sh, int32_t sw,
+                   void* stream) {
+  return guarded([&]() -> int {
+    if (!x_dev || !img_idx_dev || !k_dev || !fill_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n < 1 || B < 1) return fail(LRP_ERR_INVALID, "n and B must be positive");
+    OccGeom g;
+    LRP_TRY(occlusion_geometry(H, W, C, ph, pw, sh, sw, &g));
+    const size_t per = (size_t)H * W * C, work = (size_t)n * ((per + 3) / 4);
+    if (per % 4 == 0 && aligned16(x_dev, out_dev))
+      hipLaunchKernelGGL(occlude_kernel<true>, dim3(stream_grid(work)), dim3(256), 0, S(stream), x_dev, img_idx_dev, k_dev, fill_dev,
+                         out_dev, n, B, g);
+    else
+      hipLaunchKernelGGL(occlude_kernel<false>, dim3(stream_grid(work)), dim3(256), 0, S(stream), x_dev, img_idx_dev, k_dev, fill_dev,
+                         out_dev, n, B, g);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_op_occlusion_map(const double* scores_dev, float* out_dev, int32_t n_img, int32_t T, int32_t H, int32_t W, int32_t ph,
+                         int32_t pw, int32_t sh, int32_t sw, void* stream) {
+  return guarded([&]() -> int {
+    if (!scores_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n_img < 1 || T < 1) return fail(LRP_ERR_INVALID, "n_img and T must be positive");
+    OccGeom g;
+    LRP_TRY(occlusion_geometry(H, W, 1, ph, pw, sh, sw, &g));
+    hipLaunchKernelGGL(occlusion_map_kernel, dim3(stream_grid((size_t)n_img * T * H * W)), dim3(256), 0, S(stream), scores_dev,
+                       out_dev, n_img, T, g);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_op_rise_grids(const uint32_t* key_dev, const int32_t* k_dev, int32_t n, int32_t s, double p, uint64_t seed, int32_t H,
+                      int32_t W, int32_t ch, int32_t cw, uint8_t* grid_dev, int32_t* shift_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (!key_dev || !k_dev || !grid_dev || !shift_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n < 1) return fail(LRP_ERR_INVALID, "n must be positive");
+    RiseGeom g;
+    LRP_TRY(rise_geometry(H, W, 1, s, ch, cw, &g));
+    LRP_TRY(rise_probability(p));
+    const unsigned thresh = (unsigned)std::floor(p * 16777216.0);
+    const size_t work = (size_t)n * (((size_t)(s + 1) * (s + 1) + 3) / 4 + 1);
+    hipLaunchKernelGGL(rise_grids_kernel, dim3(stream_grid(work)), dim3(256), 0, S(stream), key_dev, k_dev, n, s, thresh,
+                       (unsigned)(seed & 0xFFFFFFFFull), (unsigned)(seed >> 32), ch, cw, grid_dev, shift_dev);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_op_rise_apply(const float* x_dev, const int32_t* img_idx_dev, const uint8_t* grid_dev, const int32_t* shift_dev,
+                      const float* fill_dev, float* out_dev, int32_t n, int32_t B, int32_t H, int32_t W, int32_t C, int32_t s,
+                      int32_t ch, int32_t cw, void* stream) {
+  return guarded([&]() -> int {
+    if (!x_dev || !img_idx_dev || !grid_dev || !shift_dev || !fill_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n < 1 || B < 1) return fail(LRP_ERR_INVALID, "n and B must be positive");
+    RiseGeom g;
+    LRP_TRY(rise_geometry(H, W, C, s, ch, cw, &g));
+    const size_t per = (size_t)H * W * C, work = (size_t)n * ((per + 3) / 4);
+    if (per % 4 == 0 && aligned16(x_dev, out_dev))
+      hipLaunchKernelGGL(rise_apply_kernel<true>, dim3(stream_grid(work)), dim3(256), 0, S(stream), x_dev, img_idx_dev, grid_dev,
+                         shift_dev, fill_dev, out_dev, n, B, g);
+    else
+      hipLaunchKernelGGL(rise_apply_kernel<false>, dim3(stream_grid(work)), dim3(256), 0, S(stream), x_dev, img_idx_dev, grid_dev,
+                         shift_dev, fill_dev, out_dev, n, B, g);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_op_rise_map(const double* scores_dev, const uint8_t* grid_dev, const int32_t* shift_dev, float* out_dev, int32_t n_img,
+                    int32_t K, int32_t T, int32_t H, int32_t W, int32_t s, double p, int32_t ch, int32_t cw, void* stream) {
+  return guarded([&]() -> int {
+    if (!scores_dev || !grid_dev || !shift_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n_img < 1 || K < 1 || T < 1) return fail(LRP_ERR_INVALID, "n_img, K and T must be positive");
+    RiseGeom g;
+    LRP_TRY(rise_geometry(H, W, 1, s, ch, cw, &g));
+    LRP_TRY(rise_probability(p));
+    const int64_t blocks = (int64_t)n_img * ((T + RISE_TT - 1) / RISE_TT) * (((int64_t)H * W + 255) / 256);
+    if (blocks > INT32_MAX) return fail(LRP_ERR_INVALID, "n_img * T * H * W is too large for one launch: split the images");
+    hipLaunchKernelGGL(rise_map_kernel, dim3((unsigned)blocks), dim3(256), 0, S(stream), scores_dev, grid_dev, shift_dev, out_dev, K, T,
+                       g, (double)K * p);
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   });

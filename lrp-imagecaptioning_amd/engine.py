@@ -1473,3 +1473,155 @@ def perturb_word_scores(engine, slot, t, col):
     p = lambda x: C.c_void_p(x.data_ptr())
     _capi.check(engine._lib.lrp_perturb_word_scores(engine._h, p(s), p(tt), p(kk), n, p(logit), p(logp), engine._stream()))
     return logit, logp
+
+
+# ---- occlusion and RISE word saliency (csrc/saliency_kernels.h, lrp_op_occlude / _occlusion_map / _rise_*)
+OCC_MAX_WINDOWS = 65536
+RISE_MAX_S = 63
+
+
+def _pair(v, what):
+    try:
+        a, b = (v, v) if np.isscalar(v) else v
+        a, b = int(a), int(b)
+    except (TypeError, ValueError):
+        raise ValueError("%s must be an int or a pair of ints" % what)
+    return a, b
+
+
+def occlusion_geometry(H, W, window, stride=None):
+    """(Hn, Wn): windows per column / row (host arithmetic of include/lrp_hip.h).  stride None: the window.  ValueError unless
+    1 <= stride <= window <= image on both axes; NotImplementedError for more than OCC_MAX_WINDOWS windows."""
+    ph, pw = _pair(window, "window")
+    sh, sw = (ph, pw) if stride is None else _pair(stride, "stride")
+    if not (1 <= sh <= ph <= H and 1 <= sw <= pw <= W):
+        raise ValueError("occlusion needs 1 <= stride <= window <= image on both axes: window (%d, %d), stride (%d, %d), image "
+                         "(%d, %d)" % (ph, pw, sh, sw, H, W))
+    Hn, Wn = -(-(H - ph) // sh) + 1, -(-(W - pw) // sw) + 1
+    if Hn * Wn > OCC_MAX_WINDOWS:
+        raise NotImplementedError("%d windows: at most %d are scored" % (Hn * Wn, OCC_MAX_WINDOWS))
+    return Hn, Wn
+
+
+def rise_cell(H, W, s):
+    """(ch, cw) = (ceil(H / s), ceil(W / s)): the smallest cell whose (s + 1)^2 grid covers the image at every shift."""
+    s = int(s)
+    if not 1 <= s <= RISE_MAX_S:
+        raise NotImplementedError("RISE grid s=%d outside [1,%d]" % (s, RISE_MAX_S))
+    return -(-H // s), -(-W // s)
+
+
+def _sal_images(x):
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 4 or not x.is_cuda:
+        raise ValueError("expected a (B, H, W, C) float32 device tensor")
+    return x.contiguous()
+
+
+def _sal_ints(a, dev, n=None, dtype=torch.int32, shape=None):
+    if not torch.is_tensor(a):
+        a = torch.as_tensor(np.asarray(a, dtype=np.int64))
+    a = a.to(device=dev, dtype=dtype).contiguous()
+    want = shape if shape is not None else ((n,) if n is not None else (a.numel(),))
+    if tuple(a.shape) != tuple(want):
+        raise ValueError("expected %s entries, got %s" % (tuple(want), tuple(a.shape)))
+    return a
+
+
+def _sal_fill(fill, Cc, dev):
+    f = np.asarray(fill, dtype=np.float32).reshape(-1)
+    if f.size not in (1, Cc):
+        raise ValueError("fill must be a scalar or one value per channel (%d)" % Cc)
+    return torch.as_tensor(np.broadcast_to(f, (Cc,)).copy()).to(dev)
+
+
+def op_occlude(x, img_idx, k, window, stride=None, fill=0.0):
+    """x (B, H, W, C) float32 device tensor -> (n, H, W, C): row r is image img_idx[r] with occlusion window k[r] set to `fill`
+    (a scalar, one value per channel, or a (C,) device tensor), every channel; k = -1 copies the image.  An image index outside
+    [0, B) or a k outside [-1, Hn * Wn) gives a NaN row."""
+    x = _sal_images(x)
+    B, Hh, Ww, Cc = x.shape
+    ph, pw = _pair(window, "window")
+    sh, sw = (ph, pw) if stride is None else _pair(stride, "stride")
+    dev = x.device
+    idx = _sal_ints(img_idx, dev)
+    n = idx.shape[0]
+    kk = _sal_ints(k, dev, n)
+    f = fill.to(device=dev, dtype=torch.float32).contiguous() if torch.is_tensor(fill) else _sal_fill(fill, Cc, dev)
+    if tuple(f.shape) != (Cc,):
+        raise ValueError("fill must hold one value per channel")
+    out = torch.empty((n, Hh, Ww, Cc), dtype=torch.float32, device=dev)
+    _capi.check(_capi.load().lrp_op_occlude(_p(x), _p(idx), _p(kk), _p(f), _p(out), n, B, Hh, Ww, Cc, ph, pw, sh, sw,
+                                            _cur_stream(dev)))
+    return out
+
+
+def op_occlusion_map(scores, H, W, window, stride=None):
+    """scores (n_img, 1 + Hn * Wn, T) float64 device tensor, row 0 the unoccluded score -> (n_img, T, H, W) float32: per pixel
+    the mean over the covering windows of s_0 - s_window, summed in float64 in ascending window order."""
+    ph, pw = _pair(window, "window")
+    sh, sw = (ph, pw) if stride is None else _pair(stride, "stride")
+    Hn, Wn = occlusion_geometry(H, W, (ph, pw), (sh, sw))
+    if not torch.is_tensor(scores) or scores.dtype != torch.float64 or scores.dim() != 3 or scores.shape[1] != 1 + Hn * Wn:
+        raise ValueError("scores must be an (n_img, %d, T) float64 device tensor" % (1 + Hn * Wn))
+    scores = scores.contiguous()
+    n_img, _, T = scores.shape
+    out = torch.empty((n_img, T, H, W), dtype=torch.float32, device=scores.device)
+    _capi.check(_capi.load().lrp_op_occlusion_map(_p(scores), _p(out), n_img, T, H, W, ph, pw, sh, sw, _cur_stream(scores.device)))
+    return out
+
+
+def op_rise_grids(keys, k, s, p, seed, H, W, cell=None, device=None):
+    """Masks (key, k) -> (grid (n, (s + 1)^2) uint8, shift (n, 2) int32) device tensors: Philox4x32-10 draws that depend on
+    (seed, key, k) alone (include/lrp_hip.h).  keys: the caller's identity of each row's image (uint32); cell: (ch, cw), default
+    rise_cell(H, W, s)."""
+    ch, cw = rise_cell(H, W, s) if cell is None else _pair(cell, "cell")
+    dev = device if device is not None else (k.device if torch.is_tensor(k) else torch.device("cuda", torch.cuda.current_device()))
+    kk = _sal_ints(k, dev)
+    n = kk.shape[0]
+    ky = _sal_ints(keys, dev, n, dtype=torch.int64) & 0xFFFFFFFF            # the uint32's bits in an int32 tensor
+    ky = torch.where(ky >= 2 ** 31, ky - 2 ** 32, ky).to(torch.int32).contiguous()
+    grid = torch.empty((n, (int(s) + 1) ** 2), dtype=torch.uint8, device=dev)
+    shift = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    _capi.check(_capi.load().lrp_op_rise_grids(_p(ky), _p(kk), n, int(s), float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, H, W, ch, cw,
+                                               _p(grid), _p(shift), _cur_stream(dev)))
+    return grid, shift
+
+
+def op_rise_apply(x, img_idx, grid, shift, s, fill=0.0, cell=None):
+    """x (B, H, W, C) float32 device tensor -> (n, H, W, C): fill + m (x - fill), row r from image img_idx[r] under the mask of
+    grid[r] / shift[r] (op_rise_grids): the (s + 1)^2 grid upsampled bilinearly by `cell` pixels per cell, cropped at the shift."""
+    x = _sal_images(x)
+    B, Hh, Ww, Cc = x.shape
+    ch, cw = rise_cell(Hh, Ww, s) if cell is None else _pair(cell, "cell")
+    dev = x.device
+    idx = _sal_ints(img_idx, dev)
+    n = idx.shape[0]
+    if grid.dtype != torch.uint8 or tuple(grid.shape) != (n, (int(s) + 1) ** 2) or grid.device != dev:
+        raise ValueError("grid must be an (n, (s + 1)^2) uint8 tensor on the device of x")
+    sh = _sal_ints(shift, dev, shape=(n, 2))
+    f = fill.to(device=dev, dtype=torch.float32).contiguous() if torch.is_tensor(fill) else _sal_fill(fill, Cc, dev)
+    if tuple(f.shape) != (Cc,):
+        raise ValueError("fill must hold one value per channel")
+    out = torch.empty((n, Hh, Ww, Cc), dtype=torch.float32, device=dev)
+    _capi.check(_capi.load().lrp_op_rise_apply(_p(x), _p(idx), _p(grid.contiguous()), _p(sh), _p(f), _p(out), n, B, Hh, Ww, Cc,
+                                               int(s), ch, cw, _cur_stream(dev)))
+    return out
+
+
+def op_rise_map(scores, grid, shift, H, W, s, p, cell=None):
+    """scores (n_img, K, T) float64, grid (n_img, K, (s + 1)^2) uint8, shift (n_img, K, 2) int32 device tensors ->
+    (n_img, T, H, W) float32: sum_k s_k[t] m_k(y, x) / (K p), the masks recomputed from the grids, summed in float64 in ascending
+    k whatever else shares the launch."""
+    ch, cw = rise_cell(H, W, s) if cell is None else _pair(cell, "cell")
+    if not torch.is_tensor(scores) or scores.dtype != torch.float64 or scores.dim() != 3:
+        raise ValueError("scores must be an (n_img, K, T) float64 device tensor")
+    scores = scores.contiguous()
+    n_img, K, T = scores.shape
+    dev = scores.device
+    if grid.dtype != torch.uint8 or tuple(grid.shape) != (n_img, K, (int(s) + 1) ** 2) or grid.device != dev:
+        raise ValueError("grid must be an (n_img, K, (s + 1)^2) uint8 tensor on the device of the scores")
+    sh = _sal_ints(shift, dev, shape=(n_img, K, 2))
+    out = torch.empty((n_img, T, H, W), dtype=torch.float32, device=dev)
+    _capi.check(_capi.load().lrp_op_rise_map(_p(scores), _p(grid.contiguous()), _p(sh), _p(out), n_img, K, T, H, W, int(s), float(p),
+                                             ch, cw, _cur_stream(dev)))
+    return out

@@ -710,3 +710,57 @@ class ExplainImgCaptioningGridTDPatternNet(_PatternNetMixin, ExplainImgCaptionin
 
 class ExplainImgCaptioningGridTDPatternAttribution(_PatternAttributionMixin, ExplainImgCaptioningGridTDModel):
     _STATE_ATTRS = ExplainImgCaptioningGridTDModel._STATE_ATTRS + ("o1t_act", "o2t_act")
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Occlusion sensitivity and RISE (saliency.py): the model-agnostic controls.  Nothing is walked backwards and nothing
+# encoder-specific is read, so the classes run on VGG-style and ResNet specs alike.  The reference has no such classes; the names
+# follow its scheme.  Constructor keywords of the driver (OcclusionSaliency / RISESaliency) are forwarded to it.
+# ---------------------------------------------------------------------------------------------------------------
+class _SaliencyMixin(object):
+    _driver = None           # the driver class of saliency.py
+    _KW = ()
+    _applies_cnn_rule = False
+
+    def __init__(self, *args, **kwargs):
+        from . import saliency
+        driver = getattr(saliency, self._driver)
+        kw = {k: kwargs.pop(k) for k in self._KW if k in kwargs}
+        driver.check_arguments(**kw)                           # (before an engine is created)
+        super(_SaliencyMixin, self).__init__(*args, **kwargs)
+        self._saliency = driver(self, **kw)
+
+    def explain_images(self, images, captions=None, words=None):
+        """The driver's `explain`: {"units": [(image, t)], "maps": (n_units, H, W) float32 device tensor, "scores0": ...}."""
+        return self._saliency.explain(images, captions, words)
+
+    def _no_walk(self, *args, **kwargs):
+        raise NotImplementedError("occlusion and RISE explain whole images through explain_images: there is no decoder or CNN walk")
+
+    _explain_lstm_single_word_sequence = _explain_lstm_single_word = _explain_CNN = _explain_sentence = layer_relevance = _no_walk
+
+
+class _OcclusionMixin(_SaliencyMixin):
+    _driver = "OcclusionSaliency"
+    _KW = ("window", "stride", "fill", "score")
+
+
+class _RISEMixin(_SaliencyMixin):
+    _driver = "RISESaliency"
+    _KW = ("n_masks", "s", "p", "seed", "fill", "score", "keys")
+
+
+class ExplainImgCaptioningAdaptiveAttentionOcclusion(_OcclusionMixin, ExplainImgCaptioningAdaptiveAttention):
+    pass
+
+
+class ExplainImgCaptioningAdaptiveAttentionRISE(_RISEMixin, ExplainImgCaptioningAdaptiveAttention):
+    pass
+
+
+class ExplainImgCaptioningGridTDOcclusion(_OcclusionMixin, ExplainImgCaptioningGridTDModel):
+    pass
+
+
+class ExplainImgCaptioningGridTDRISE(_RISEMixin, ExplainImgCaptioningGridTDModel):
+    pass

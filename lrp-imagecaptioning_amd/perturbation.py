@@ -153,7 +153,7 @@ class Perturbation(object):
 class CaptionPerturbationAnalysis(object):
     """PT:194-397 for a captioning model: the perturbation curve of every (image, word) unit.
 
-    explainer: any of the explainer classes (LRP, gradient, gradient x input, Guided Grad-CAM; either decoder); its
+    explainer: any of the explainer classes (LRP, gradient, gradient x input, Guided Grad-CAM, occlusion, RISE; either decoder); its
     heat-map of a word ranks the regions.  order 'relevance' (most relevant first), 'least_relevant' (the scores negated)
     or 'random' (a host-drawn permutation per unit from `seed`: the baseline the curve is read against; nothing is
     explained).  Step 0 is the unperturbed image; step s perturbs 1 + (s - 1) * regions_per_step regions (PT:377-385;
@@ -174,11 +174,20 @@ class CaptionPerturbationAnalysis(object):
         self.order = order
         self.seed = seed
 
-    def _heatmaps(self, ii, ts):
-        """(n, H, W, 3) heat-maps of the units (slot, t) of the engine's current forward, on the device."""
-        from .explainers import _GradientMixin, _GuidedGradcamMixin
+    def _heatmaps(self, ii, ts, images=None, captions=None):
+        """(n, H, W, 3) heat-maps of the units (slot, t) of the engine's current forward, on the device.  images, captions: what
+        that forward was made from (read by the occlusion / RISE explainers only, which run forwards of their own)."""
+        from .explainers import _GradientMixin, _GuidedGradcamMixin, _SaliencyMixin
         ex = self.explainer
         eng = ex._engine
+        if isinstance(ex, _SaliencyMixin):
+            # occlusion / RISE need the chunk's images and captions, not the cached forward (which their own chunks replace:
+            # step 0 has been read by now, and the next chunk encodes again)
+            words = [[t for i, t in zip(ii, ts) if i == b] for b in range(len(captions))]
+            res = ex.explain_images(images, captions, words)
+            row = {u: j for j, u in enumerate(res["units"])}
+            sel = torch.as_tensor([row[(i, t)] for i, t in zip(ii, ts)], device=eng.device)
+            return res["maps"][sel].unsqueeze(-1).expand(-1, -1, -1, 3).contiguous()
         if isinstance(ex, _GuidedGradcamMixin):
             return eng.guided_gradcam(ii, ts)
         if isinstance(ex, _GradientMixin):
@@ -243,7 +252,7 @@ class CaptionPerturbationAnalysis(object):
             if self.order != "random":
                 for c0 in range(0, len(mine), eng.max_tokens):
                     chunk = mine[c0:c0 + eng.max_tokens]
-                    R = self._heatmaps([u[0] for u in chunk], [u[1] for u in chunk])
+                    R = self._heatmaps([u[0] for u in chunk], [u[1] for u in chunk], x_dev[lo:hi], captions[lo:hi])
                     ranks[u0 + c0:u0 + c0 + len(chunk)] = pert.ranks_device(R, negate=self.order == "least_relevant")
             u0 = u1
 
