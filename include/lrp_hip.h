@@ -744,6 +744,54 @@ int lrp_op_rise_apply(const float* x_dev, const int32_t* img_idx_dev, const uint
 int lrp_op_rise_map(const double* scores_dev, const uint8_t* grid_dev, const int32_t* shift_dev, float* out_dev, int32_t n_img,
                     int32_t K, int32_t T, int32_t H, int32_t W, int32_t s, double p, int32_t ch, int32_t cw, void* stream);
 
+/* LIME (Ribeiro et al. 2016) and KernelSHAP (Lundberg & Lee 2017) word saliency: the mask is a binary choice over d segments of
+ * the image (label_dev: an int32 label map from any segmenter), the masked copies go through the same forwards as above and the
+ * word scores are folded by a weighted linear regression.  Handle-free operators like lrp_op_rise_*: device pointers, the
+ * caller's stream, no synchronisation; additive to the ABI.  Every argument is checked before any HIP call.
+ * (csrc/segment_kernels.h)
+ * Segments: 2 <= d <= 128 (else LRP_ERR_RANGE).  A row's subset is 4 uint32 words: bit j of word j / 32 is segment j, bits at or
+ *   above d are zero.
+ * lrp_op_segment_draws: row (key, k) -> bits_dev (n, 4) uint32.  key_dev (n) uint32 is the caller's identity of the image, k_dev
+ *   (n) int32 the draw number.  Philox4x32-10 as in lrp_op_rise_grids with key = (seed & 0xFFFFFFFF, seed >> 32); the last
+ *   counter word is 2 for LRP_SEGMENT_BERNOULLI and 3 for LRP_SEGMENT_SHAPLEY (0: the Gaussian augment, 1: RISE).
+ *   Bernoulli (LIME): segment j takes lane j % 4 of counter (j / 4, k, key, 2), on iff (x >> 8) < floor(p 2^24); 0 < p <= 1.
+ *   Shapley (KernelSHAP), pair q = k >> 1: u = lane 0 of counter (0xFFFFFFFF, q, key, 3); size s = 1 + #{i : u >= thr[i]} in
+ *   [1, d - 1], thr_dev (d - 2) uint32 on the device (NULL allowed at d = 2 only): thr[i] = min(2^32 - 1, floor(C(i + 1) 2^32))
+ *   with C the cumulative of p(m) ~ (d - 1) / (m (d - m)), m = 1 .. d - 1, computed by the caller in double.  Partial
+ *   Fisher-Yates over perm = 0 .. d - 1: for i = 0 .. s - 1, r = lane i % 4 of counter (i / 4, q, key, 3),
+ *   j = i + mulhi32(r, d - i), swap perm[i], perm[j]; the subset is perm[0 .. s).  An odd k is the complement within d bits of
+ *   draw k - 1 (antithetic pairs).  p is not read in Shapley mode, thr_dev not in Bernoulli mode.  A row is a pure function of
+ *   (seed, key, k, d, p or thr): any cut or order of the rows into calls gives the same bits.  An unknown mode, a p outside
+ *   (0, 1] or a missing thr_dev: LRP_ERR_INVALID.
+ * lrp_op_segment_apply: out_dev (n, H, W, C) float32: row r is image img_idx_dev[r] of x_dev (B, H, W, C) with every pixel whose
+ *   segment label_dev[img][y][x] is off in bits_dev[r] set to fill_dev[c]: a select, no arithmetic, so all bits set reproduces
+ *   the image.  An image index outside [0, B) gives a NaN row, a label outside [0, d) a NaN pixel.  16-byte accesses when
+ *   H W C % 4 == 0 and both tensors are 16-byte aligned.
+ * lrp_op_segment_fit: bits_dev (n_img, K, 4), wtab_dev (d + 1) float64, y_dev (n_img, K, T) float64 -> phi_dev (n_img, T, d),
+ *   icpt_dev (n_img, T) float64, status_dev (n_img) int32.  Row weight w_k = wtab[popcount(z_k)]; weight 0 drops the row.
+ *   delta_dev NULL (LIME form): minimise sum_k w_k (y_k - b - z_k . phi)^2 + ridge |phi|^2, b free and unpenalised (icpt = b).
+ *   delta_dev (n_img, T) (Shapley form): phi_{d-1} = delta - sum_{j<d-1} phi_j, minimise sum_k w_k (y_k - z_{k,d-1} delta -
+ *   sum_{j<d-1} (z_kj - z_{k,d-1}) phi_j)^2 + ridge sum_{j<d-1} phi_j^2: the efficiency constraint by elimination; icpt = 0.
+ *   All in float64.  Every entry of the normal equations is a sum over k in ascending order, by one thread; the Gram matrix is
+ *   shared by the T words of an image, each word its own right-hand side; Cholesky, one workgroup per image, the packed factor
+ *   in LDS.  A pivot that is <= 0 or not finite sets status = 1 and the image's phi and icpt to NaN (else status = 0); a
+ *   near-singular system is not detected.  An image's phi has the same bits at n_img = 1 and in any batch, a word's alone and
+ *   among T others.  ridge < 0 or not finite: LRP_ERR_INVALID.
+ * lrp_op_segment_map: phi_dev (n_img, T, d) float64, label_dev (n_img, H, W) int32 -> out_dev (n_img, T, H, W) float32:
+ *   out = (float) phi[t][label], rounded once; a label outside [0, d) gives NaN. */
+#define LRP_SEGMENT_BERNOULLI 0
+#define LRP_SEGMENT_SHAPLEY 1
+int lrp_op_segment_draws(const uint32_t* key_dev, const int32_t* k_dev, int32_t n, int32_t d, int32_t mode, double p,
+                         const uint32_t* thr_dev, uint64_t seed, uint32_t* bits_dev, void* stream);
+int lrp_op_segment_apply(const float* x_dev, const int32_t* img_idx_dev, const uint32_t* bits_dev, const int32_t* label_dev,
+                         const float* fill_dev, float* out_dev, int32_t n, int32_t B, int32_t H, int32_t W, int32_t C, int32_t d,
+                         void* stream);
+int lrp_op_segment_fit(const uint32_t* bits_dev, const double* wtab_dev, const double* y_dev, const double* delta_dev, double ridge,
+                       double* phi_dev, double* icpt_dev, int32_t* status_dev, int32_t n_img, int32_t K, int32_t T, int32_t d,
+                       void* stream);
+int lrp_op_segment_map(const double* phi_dev, const int32_t* label_dev, float* out_dev, int32_t n_img, int32_t T, int32_t H,
+                       int32_t W, int32_t d, void* stream);
+
 /* Operator-level entries of the fine-tune step's dense products (unit tests at real layer sizes; csrc/train_gemm.h).
  * lrp_op_sgemm: C (+)= op(A) op(B) on the fp32 matrix cores, row-major with leading dimensions;
  *   op(A)[m][k] = transA ? A[k*lda + m] : A[m*lda + k], op(B)[k][n] = transB ? B[n*ldb + k] : B[k*ldb + n]

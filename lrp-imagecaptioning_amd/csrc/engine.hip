@@ -3,6 +3,8 @@
 // encoder (CNN half) and decoder (LSTM/attention half) orchestration.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <exception>
@@ -25,6 +27,7 @@
 #include "rules_kernels.h"
 #include "saliency_kernels.h"
 #include "score_kernels.h"
+#include "segment_kernels.h"
 #include "trainer.h"
 
 namespace lrp {
@@ -1718,6 +1721,91 @@ int lrp_op_rise_map(const double* scores_dev, const uint8_t* grid_dev, const int
     if (blocks > INT32_MAX) return fail(LRP_ERR_INVALID, "n_img * T * H * W is too large for one launch: split the images");
     hipLaunchKernelGGL(rise_map_kernel, dim3((unsigned)blocks), dim3(256), 0, S(stream), scores_dev, grid_dev, shift_dev, out_dev, K, T,
                        g, (double)K * p);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+// ---- LIME and KernelSHAP word saliency (csrc/segment_kernels.h)
+static int segment_count(int32_t d) {
+  if (d < 2 || d > SEG_MAX_D) return fail(LRP_ERR_RANGE, "segment count d=%d outside [2,%d]", d, SEG_MAX_D);
+  return LRP_OK;
+}
+
+int lrp_op_segment_draws(const uint32_t* key_dev, const int32_t* k_dev, int32_t n, int32_t d, int32_t mode, double p,
+                         const uint32_t* thr_dev, uint64_t seed, uint32_t* bits_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (!key_dev || !k_dev || !bits_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n < 1) return fail(LRP_ERR_INVALID, "n must be positive");
+    LRP_TRY(segment_count(d));
+    if (mode != LRP_SEGMENT_BERNOULLI && mode != LRP_SEGMENT_SHAPLEY) return fail(LRP_ERR_INVALID, "unknown draw mode %d", mode);
+    unsigned thresh = 0;
+    if (mode == LRP_SEGMENT_BERNOULLI) {
+      if (!(p > 0.0) || !(p <= 1.0)) return fail(LRP_ERR_INVALID, "Bernoulli draws need 0 < p <= 1 (p=%g)", p);
+      thresh = (unsigned)std::floor(p * 16777216.0);
+    } else if (d > 2 && !thr_dev) {
+      return fail(LRP_ERR_INVALID, "Shapley draws at d > 2 need the d - 2 size thresholds");
+    }
+    hipLaunchKernelGGL(segment_draws_kernel, dim3((unsigned)std::min<int64_t>(((int64_t)n + SEG_DRAW_THREADS - 1) / SEG_DRAW_THREADS, 4096)),
+                       dim3(SEG_DRAW_THREADS), 0, S(stream), key_dev, k_dev, n, d, mode == LRP_SEGMENT_SHAPLEY ? 1 : 0, thresh, thr_dev,
+                       (unsigned)(seed & 0xFFFFFFFFull), (unsigned)(seed >> 32), bits_dev);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_op_segment_apply(const float* x_dev, const int32_t* img_idx_dev, const uint32_t* bits_dev, const int32_t* label_dev,
+                         const float* fill_dev, float* out_dev, int32_t n, int32_t B, int32_t H, int32_t W, int32_t C, int32_t d,
+                         void* stream) {
+  return guarded([&]() -> int {
+    if (!x_dev || !img_idx_dev || !bits_dev || !label_dev || !fill_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n < 1 || B < 1) return fail(LRP_ERR_INVALID, "n and B must be positive");
+    LRP_TRY(saliency_image(H, W, C));
+    LRP_TRY(segment_count(d));
+    const size_t per = (size_t)H * W * C, work = (size_t)n * ((per + 3) / 4);
+    if (per % 4 == 0 && aligned16(x_dev, out_dev))
+      hipLaunchKernelGGL(segment_apply_kernel<true>, dim3(stream_grid(work)), dim3(256), 0, S(stream), x_dev, img_idx_dev, bits_dev,
+                         label_dev, fill_dev, out_dev, n, B, H, W, C, d);
+    else
+      hipLaunchKernelGGL(segment_apply_kernel<false>, dim3(stream_grid(work)), dim3(256), 0, S(stream), x_dev, img_idx_dev, bits_dev,
+                         label_dev, fill_dev, out_dev, n, B, H, W, C, d);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_op_segment_fit(const uint32_t* bits_dev, const double* wtab_dev, const double* y_dev, const double* delta_dev, double ridge,
+                       double* phi_dev, double* icpt_dev, int32_t* status_dev, int32_t n_img, int32_t K, int32_t T, int32_t d,
+                       void* stream) {
+  return guarded([&]() -> int {
+    if (!bits_dev || !wtab_dev || !y_dev || !phi_dev || !icpt_dev || !status_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n_img < 1 || K < 1 || T < 1) return fail(LRP_ERR_INVALID, "n_img, K and T must be positive");
+    LRP_TRY(segment_count(d));
+    if (!(ridge >= 0.0) || !std::isfinite(ridge)) return fail(LRP_ERR_INVALID, "ridge must be finite and >= 0 (ridge=%g)", ridge);
+    const size_t lds = segment_fit_lds(delta_dev ? d - 1 : d + 1);
+    // above the 64 KiB a kernel may take unasked, the dynamic-LDS attribute is raised once, to the largest case (d = SEG_MAX_D)
+    static std::atomic<bool> attr_set{false};
+    if (lds > 64 * 1024 && !attr_set.load()) {
+      LRP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(segment_fit_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)segment_fit_lds(SEG_MAX_D + 1)));
+      attr_set.store(true);
+    }
+    hipLaunchKernelGGL(segment_fit_kernel, dim3((unsigned)n_img), dim3(SEG_FIT_THREADS), lds, S(stream), bits_dev, wtab_dev, y_dev,
+                       delta_dev, ridge, phi_dev, icpt_dev, status_dev, K, T, d);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_op_segment_map(const double* phi_dev, const int32_t* label_dev, float* out_dev, int32_t n_img, int32_t T, int32_t H,
+                       int32_t W, int32_t d, void* stream) {
+  return guarded([&]() -> int {
+    if (!phi_dev || !label_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n_img < 1 || T < 1) return fail(LRP_ERR_INVALID, "n_img and T must be positive");
+    LRP_TRY(saliency_image(H, W, 1));
+    LRP_TRY(segment_count(d));
+    hipLaunchKernelGGL(segment_map_kernel, dim3(stream_grid((size_t)n_img * T * H * W)), dim3(256), 0, S(stream), phi_dev, label_dev,
+                       out_dev, n_img, T, H, W, d);
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   });

@@ -1625,3 +1625,130 @@ def op_rise_map(scores, grid, shift, H, W, s, p, cell=None):
     _capi.check(_capi.load().lrp_op_rise_map(_p(scores), _p(grid.contiguous()), _p(sh), _p(out), n_img, K, T, H, W, int(s), float(p),
                                              ch, cw, _cur_stream(dev)))
     return out
+
+
+# ---- LIME and KernelSHAP word saliency (csrc/segment_kernels.h, lrp_op_segment_*)
+SEG_MAX_D = 128
+SEG_MODES = {"bernoulli": 0, "shapley": 1}
+
+
+def _seg_count(d):
+    d = int(d)
+    if not 2 <= d <= SEG_MAX_D:
+        raise NotImplementedError("segment count d=%d outside [2,%d]" % (d, SEG_MAX_D))
+    return d
+
+
+def shapley_size_thresholds(d):
+    """(d - 2,) uint32: thr[i] = min(2^32 - 1, floor(C(i + 1) 2^32)) in float64, C the cumulative of the Shapley kernel's size
+    distribution p(m) ~ (d - 1) / (m (d - m)), m = 1 .. d - 1.  A uniform 32-bit u has size 1 + #{i : u >= thr[i]}: the integers
+    lrp_op_segment_draws compares against."""
+    d = _seg_count(d)
+    m = np.arange(1, d, dtype=np.float64)
+    pm = (d - 1.0) / (m * (d - m))
+    cum = np.cumsum(pm / pm.sum())[:d - 2]
+    return np.minimum(2.0 ** 32 - 1.0, np.floor(cum * 2.0 ** 32)).astype(np.uint32)
+
+
+def _seg_bits(bits, dev, shape):
+    if not torch.is_tensor(bits):
+        bits = torch.as_tensor(np.ascontiguousarray(np.asarray(bits).astype(np.uint32)).view(np.int32))
+    if bits.dtype != torch.int32 or tuple(bits.shape) != tuple(shape):
+        raise ValueError("bits must be a %s int32 tensor (the uint32 words' bits)" % (tuple(shape),))
+    return bits.to(dev).contiguous()
+
+
+def _seg_labels(label, dev, shape):
+    if not torch.is_tensor(label):
+        label = torch.as_tensor(np.asarray(label, dtype=np.int64))
+    if tuple(label.shape) != tuple(shape):
+        raise ValueError("labels must be %s ints" % (tuple(shape),))
+    return label.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def op_segment_draws(keys, k, d, mode, p=0.5, seed=0, device=None):
+    """Rows (key, k) -> (n, 4) int32 device tensor holding the uint32 words of each row's subset of d segments: bit j of word
+    j / 32 is segment j.  mode 'bernoulli' (each segment on with probability p) or 'shapley' (size from the Shapley kernel's
+    distribution, then a uniform subset of that size; an odd k the complement of k - 1).  Philox4x32-10 draws that depend on
+    (seed, key, k, d, p) alone (include/lrp_hip.h)."""
+    d = _seg_count(d)
+    if mode not in SEG_MODES:
+        raise ValueError("mode must be 'bernoulli' or 'shapley'")
+    dev = device if device is not None else (k.device if torch.is_tensor(k) else torch.device("cuda", torch.cuda.current_device()))
+    kk = _sal_ints(k, dev)
+    n = kk.shape[0]
+    ky = _sal_ints(keys, dev, n, dtype=torch.int64) & 0xFFFFFFFF            # the uint32's bits in an int32 tensor
+    ky = torch.where(ky >= 2 ** 31, ky - 2 ** 32, ky).to(torch.int32).contiguous()
+    thr = None
+    if mode == "shapley" and d > 2:
+        thr = torch.as_tensor(shapley_size_thresholds(d).view(np.int32)).to(dev)
+    bits = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    _capi.check(_capi.load().lrp_op_segment_draws(_p(ky), _p(kk), n, d, SEG_MODES[mode], float(p), None if thr is None else _p(thr),
+                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, _p(bits), _cur_stream(dev)))
+    return bits
+
+
+def op_segment_apply(x, img_idx, bits, label, d, fill=0.0):
+    """x (B, H, W, C) float32 device tensor, label (B, H, W) ints in [0, d) -> (n, H, W, C): row r is image img_idx[r] with the
+    pixels of every segment that is off in bits[r] set to `fill`; values are selected, never computed.  An image index outside
+    [0, B) gives a NaN row, a label outside [0, d) a NaN pixel."""
+    x = _sal_images(x)
+    B, Hh, Ww, Cc = x.shape
+    d = _seg_count(d)
+    dev = x.device
+    idx = _sal_ints(img_idx, dev)
+    n = idx.shape[0]
+    bits = _seg_bits(bits, dev, (n, 4))
+    label = _seg_labels(label, dev, (B, Hh, Ww))
+    f = fill.to(device=dev, dtype=torch.float32).contiguous() if torch.is_tensor(fill) else _sal_fill(fill, Cc, dev)
+    if tuple(f.shape) != (Cc,):
+        raise ValueError("fill must hold one value per channel")
+    out = torch.empty((n, Hh, Ww, Cc), dtype=torch.float32, device=dev)
+    _capi.check(_capi.load().lrp_op_segment_apply(_p(x), _p(idx), _p(bits), _p(label), _p(f), _p(out), n, B, Hh, Ww, Cc, d,
+                                                  _cur_stream(dev)))
+    return out
+
+
+def op_segment_fit(bits, wtab, y, d, ridge=0.0, delta=None):
+    """bits (n_img, K, 4) int32, wtab (d + 1,) float64 (the row weight by subset size), y (n_img, K, T) float64 device tensors ->
+    (phi (n_img, T, d), intercept (n_img, T), status (n_img,) int32).  delta None: weighted ridge regression of y on the
+    subsets with a free intercept (LIME); delta (n_img, T): the Shapley form, sum(phi) = delta by elimination, intercept 0.
+    status 1: the normal equations are singular (phi NaN)."""
+    d = _seg_count(d)
+    if not torch.is_tensor(y) or y.dtype != torch.float64 or y.dim() != 3 or not y.is_cuda:
+        raise ValueError("y must be an (n_img, K, T) float64 device tensor")
+    y = y.contiguous()
+    n_img, K, T = y.shape
+    dev = y.device
+    bits = _seg_bits(bits, dev, (n_img, K, 4))
+    wt = torch.as_tensor(np.ascontiguousarray(wtab, dtype=np.float64)) if not torch.is_tensor(wtab) else wtab
+    wt = wt.to(device=dev, dtype=torch.float64).contiguous()
+    if tuple(wt.shape) != (d + 1,):
+        raise ValueError("wtab must hold d + 1 weights")
+    if delta is not None:
+        if not torch.is_tensor(delta) or delta.dtype != torch.float64 or tuple(delta.shape) != (n_img, T) or delta.device != dev:
+            raise ValueError("delta must be an (n_img, T) float64 tensor on the device of y")
+        delta = delta.contiguous()
+    phi = torch.empty((n_img, T, d), dtype=torch.float64, device=dev)
+    icpt = torch.empty((n_img, T), dtype=torch.float64, device=dev)
+    status = torch.empty((n_img,), dtype=torch.int32, device=dev)
+    _capi.check(_capi.load().lrp_op_segment_fit(_p(bits), _p(wt), _p(y), None if delta is None else _p(delta), float(ridge), _p(phi),
+                                                _p(icpt), _p(status), n_img, K, T, d, _cur_stream(dev)))
+    return phi, icpt, status
+
+
+def op_segment_map(phi, label, d):
+    """phi (n_img, T, d) float64, label (n_img, H, W) ints -> (n_img, T, H, W) float32: phi[t][label], rounded once; NaN for a
+    label outside [0, d)."""
+    d = _seg_count(d)
+    if not torch.is_tensor(phi) or phi.dtype != torch.float64 or phi.dim() != 3 or phi.shape[2] != d or not phi.is_cuda:
+        raise ValueError("phi must be an (n_img, T, d) float64 device tensor")
+    phi = phi.contiguous()
+    n_img, T, _ = phi.shape
+    if not hasattr(label, "shape") or len(label.shape) != 3 or label.shape[0] != n_img:
+        raise ValueError("labels must be (n_img, H, W) ints")
+    H, W = int(label.shape[1]), int(label.shape[2])
+    label = _seg_labels(label, phi.device, (n_img, H, W))
+    out = torch.empty((n_img, T, H, W), dtype=torch.float32, device=phi.device)
+    _capi.check(_capi.load().lrp_op_segment_map(_p(phi), _p(label), _p(out), n_img, T, H, W, d, _cur_stream(phi.device)))
+    return out

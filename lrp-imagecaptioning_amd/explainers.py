@@ -735,7 +735,8 @@ class _SaliencyMixin(object):
         return self._saliency.explain(images, captions, words)
 
     def _no_walk(self, *args, **kwargs):
-        raise NotImplementedError("occlusion and RISE explain whole images through explain_images: there is no decoder or CNN walk")
+        raise NotImplementedError("occlusion, RISE, LIME and KernelSHAP explain whole images through explain_images: there is no "
+                                  "decoder or CNN walk")
 
     _explain_lstm_single_word_sequence = _explain_lstm_single_word = _explain_CNN = _explain_sentence = layer_relevance = _no_walk
 
@@ -763,4 +764,38 @@ class ExplainImgCaptioningGridTDOcclusion(_OcclusionMixin, ExplainImgCaptioningG
 
 
 class ExplainImgCaptioningGridTDRISE(_RISEMixin, ExplainImgCaptioningGridTDModel):
+    pass
+
+
+# LIME and KernelSHAP (saliency.py): the same scheme; `segments` is a (B, H, W) int label map from any segmenter of the caller's
+# (None: the regular grid of the `cells` keyword)
+class _SegmentMixin(_SaliencyMixin):
+    def explain_images(self, images, captions=None, words=None, segments=None):
+        """The driver's `explain`: the keys above, plus "coefficients", "intercept", "segments" and "status"."""
+        return self._saliency.explain(images, captions, words, segments)
+
+
+class _LIMEMixin(_SegmentMixin):
+    _driver = "LIMESaliency"
+    _KW = ("n_samples", "cells", "p", "kernel_width", "ridge", "seed", "fill", "score", "keys")
+
+
+class _KernelSHAPMixin(_SegmentMixin):
+    _driver = "KernelSHAPSaliency"
+    _KW = ("n_samples", "cells", "ridge", "seed", "fill", "score", "keys")
+
+
+class ExplainImgCaptioningAdaptiveAttentionLIME(_LIMEMixin, ExplainImgCaptioningAdaptiveAttention):
+    pass
+
+
+class ExplainImgCaptioningAdaptiveAttentionKernelSHAP(_KernelSHAPMixin, ExplainImgCaptioningAdaptiveAttention):
+    pass
+
+
+class ExplainImgCaptioningGridTDLIME(_LIMEMixin, ExplainImgCaptioningGridTDModel):
+    pass
+
+
+class ExplainImgCaptioningGridTDKernelSHAP(_KernelSHAPMixin, ExplainImgCaptioningGridTDModel):
     pass

@@ -6,6 +6,10 @@ compared against.
                         saliency is the mean fall over the windows that cover it
     RISESaliency        score n_masks randomly masked copies of the image; a pixel's saliency is the mean of the scores weighted
                         by the pixel's mask value, divided by p
+    LIMESaliency        (Ribeiro, Singh & Guestrin, KDD 2016) switch the segments of the image on and off at random; a pixel's
+                        saliency is its segment's coefficient in a kernel-weighted ridge regression of the score on the switches
+    KernelSHAPSaliency  (Lundberg & Lee, NeurIPS 2017) the same regression under the Shapley kernel and the efficiency constraint:
+                        the segments' Shapley values, sampled or (up to 12 segments) exact
 
 A masked image is one image slot of the engine: per chunk of max_images slots (any mix of images and masks) the apply operator
 makes the rows (lrp_op_occlude / lrp_op_rise_apply), `encode_images` and one teacher-forced `decoder_forward` with each slot's
@@ -60,8 +64,17 @@ class _WordSaliency(object):
         """S (n_img, 1 + rows, T) float64 -> (n_img, T, H, W) float32"""
         raise NotImplementedError()
 
+    def _set_segments(self, x_dev, segments):
+        """the caller's label map, before anything runs (the segment methods alone take one)"""
+        if segments is not None:
+            raise ValueError("%s takes no segments" % type(self).__name__)
+
+    def _extras(self, active, n_words, B):
+        """what a method adds to the result dict, after _maps"""
+        return {}
+
     # ---------------------------------------------------------------- the driver
-    def explain(self, images, captions=None, words=None):
+    def explain(self, images, captions=None, words=None, segments=None):
         """images (B, H, W, 3) preprocessed (numpy or device tensor); captions: one id list per image (None: beam search); words:
         per image the positions t >= 1 to explain (None: every word before EOS), as in
         CaptionPerturbationAnalysis.compute_perturbation_analysis.  Returns a dict:
@@ -69,7 +82,13 @@ class _WordSaliency(object):
             maps     (n_units, H, W) float32 device tensor
             scores0  (n_units,) float64 device tensor: the word's score on the unmasked image
             scores   per image (None without a word) the (1 + rows, n_words) float64 device score matrix the maps were folded
-                     from: row 0 the unmasked image, row 1 + k window / mask k"""
+                     from: row 0 the unmasked image, row 1 + k window / mask k
+        segments (LIME and KernelSHAP alone): a (B, H, W) int label map from any segmenter, every label of [0, d) in every image
+        (None: the regular grid of `cells`); their result also holds
+            coefficients  per image the (n_words, d) float64 device tensor of the fit
+            intercept     per image (n_words,): LIME's intercept, KernelSHAP's base score (every segment filled)
+            segments      the (B, H, W) int32 label map used
+            status        (B,) int32, 0: the fit went through (anything else raises ValueError)"""
         ex = self.explainer
         eng = ex._engine
         dev = eng.device
@@ -77,6 +96,7 @@ class _WordSaliency(object):
         if x_dev.dim() != 4:
             raise ValueError("expected (B, H, W, 3) images")
         B, H, W = int(x_dev.shape[0]), int(x_dev.shape[1]), int(x_dev.shape[2])
+        self._set_segments(x_dev, segments)
         if captions is None:
             res = ex._beam_search((None, x_dev.cpu().numpy()))
             captions = [res[0]] if B == 1 else [r[0] for r in res]
@@ -136,10 +156,12 @@ class _WordSaliency(object):
         per_image = [None] * B
         for a, b in enumerate(active):
             per_image[b] = S[a, :, :int(nw[a])]
-        return {"units": units,
-                "maps": torch.cat([maps[a, :int(nw[a])] for a in range(len(active))]),
-                "scores0": torch.cat([S[a, 0, :int(nw[a])] for a in range(len(active))]),
-                "scores": per_image}
+        res = {"units": units,
+               "maps": torch.cat([maps[a, :int(nw[a])] for a in range(len(active))]),
+               "scores0": torch.cat([S[a, 0, :int(nw[a])] for a in range(len(active))]),
+               "scores": per_image}
+        res.update(self._extras(active, nw, B))
+        return res
 
 
 class OcclusionSaliency(_WordSaliency):
@@ -219,3 +241,234 @@ class RISESaliency(_WordSaliency):
     def _maps(self, S, H, W):
         n_img, K = S.shape[0], self.n_masks
         return _eng.op_rise_map(S[:, 1:], self.grids.view(n_img, K, -1), self.shifts.view(n_img, K, 2), H, W, self.s, self.p)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# LIME and KernelSHAP: the mask is a binary choice over d segments, the scores are folded by a weighted linear regression
+# (csrc/segment_kernels.h).  The same driver: only the hooks differ.
+# ---------------------------------------------------------------------------------------------------------------
+shapley_size_thresholds = _eng.shapley_size_thresholds
+SHAP_ENUM_MAX_D = 12
+
+
+def grid_segments(H, W, cells):
+    """(H, W) int32 labels of a regular grid of `cells` (an int or (cells_y, cells_x)): cell boundaries at floor(i H / cells_y)
+    and floor(j W / cells_x), label = i cells_x + j."""
+    cy, cx = _eng._pair(cells, "cells")
+    if cy < 1 or cx < 1:
+        raise ValueError("cells must be positive")
+    row = np.searchsorted(np.arange(cy + 1, dtype=np.int64) * H // cy, np.arange(H), side="right") - 1
+    col = np.searchsorted(np.arange(cx + 1, dtype=np.int64) * W // cx, np.arange(W), side="right") - 1
+    return (row[:, None] * cx + col[None, :]).astype(np.int32)
+
+
+def _full_bits(d):
+    """the four words of the subset that holds every one of d segments, as int32"""
+    words = [(1 << min(max(d - 32 * w, 0), 32)) - 1 for w in range(4)]
+    return np.array(words, dtype=np.uint32).view(np.int32)
+
+
+def lime_weights(d, kernel_width):
+    """wtab[m], m = 0 .. d: LIME's exponential kernel sqrt(exp(-D^2 / kernel_width^2)) on the cosine distance D = 1 - sqrt(m / d)
+    of a subset of m segments to the all-ones vector (the empty subset has distance 1)."""
+    m = np.arange(d + 1, dtype=np.float64)
+    return np.sqrt(np.exp(-(1.0 - np.sqrt(m / d)) ** 2 / float(kernel_width) ** 2))
+
+
+def shapley_weights(d):
+    """wtab[m] = (d - 1) / (C(d, m) m (d - m)) on 1 <= m <= d - 1, 0 at the ends: the Shapley kernel of Lundberg & Lee, theorem 2"""
+    from math import comb
+    w = np.zeros(d + 1, dtype=np.float64)
+    for m in range(1, d):
+        w[m] = (d - 1.0) / (float(comb(d, m)) * m * (d - m))
+    return w
+
+
+def _check_segment_common(cells, ridge, seed, keys, fill, score):
+    cy, cx = _eng._pair(cells, "cells")
+    if cy < 1 or cx < 1:
+        raise ValueError("cells must be positive")
+    _eng._seg_count(cy * cx)                                   # NotImplementedError outside [2, SEG_MAX_D]
+    if not (np.isfinite(ridge) and float(ridge) >= 0.0):
+        raise ValueError("ridge must be finite and >= 0")
+    if int(seed) != seed or not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be an int in [0, 2^64)")
+    if keys is not None and any(int(k) != k or not 0 <= k < 2 ** 32 for k in keys):
+        raise ValueError("keys must be ints in [0, 2^32)")
+    _check_common(fill, score)
+    return cy * cx
+
+
+class _SegmentSaliency(_WordSaliency):
+    """what LIME and KernelSHAP share: the label map, its check, the keys of the draws and the extra keys of the result"""
+
+    def __init__(self, explainer, cells, ridge, seed, fill, score, keys):
+        super(_SegmentSaliency, self).__init__(explainer, fill, score)
+        self.cells, self.ridge, self.seed = _eng._pair(cells, "cells"), float(ridge), int(seed)
+        self.keys = None if keys is None else [int(k) for k in keys]
+
+    def _check_d(self, d):
+        _eng._seg_count(d)
+
+    def _set_segments(self, x_dev, segments):
+        B, H, W = int(x_dev.shape[0]), int(x_dev.shape[1]), int(x_dev.shape[2])
+        dev = x_dev.device
+        if segments is None:
+            lab = torch.as_tensor(grid_segments(H, W, self.cells)).to(dev).unsqueeze(0).expand(B, H, W).contiguous()
+            d = self.cells[0] * self.cells[1]
+        else:
+            lab = segments if torch.is_tensor(segments) else torch.as_tensor(np.asarray(segments))
+            if tuple(lab.shape) != (B, H, W) or lab.dtype.is_floating_point or lab.dtype == torch.bool:
+                raise ValueError("segments must be a (B, H, W) = (%d, %d, %d) int label map" % (B, H, W))
+            lab = lab.to(dev)
+            lo, hi = int(lab.min()), int(lab.max())
+            if lo < 0:
+                raise ValueError("segment labels must be >= 0")
+            d = hi + 1                                         # one d per call
+            lab = lab.to(torch.int32).contiguous()
+        self._check_d(d)
+        # every label must occur in every image: an image's regression then has the same d columns whatever its batch mates are
+        present = torch.zeros((B, d), dtype=torch.bool, device=dev).scatter_(1, lab.view(B, -1).long(), True)
+        missing = (~present).nonzero()
+        if missing.numel():
+            b, l = (int(v) for v in missing[0])
+            raise ValueError("image %d has no pixel of segment %d: every label in [0, %d) must occur in every image" % (b, l, d))
+        self.labels, self.d = lab, d
+
+    def _draw_keys(self, x_dev, image_ids):
+        if self.keys is not None and len(self.keys) != x_dev.shape[0]:
+            raise ValueError("one key per image")
+        return np.asarray([b if self.keys is None else self.keys[b] for b in image_ids], dtype=np.int64)
+
+    def _fold(self, phi, icpt, status, active):
+        """keep the fit for _extras, refuse a singular one, gather the maps"""
+        bad = status.nonzero()
+        if bad.numel():
+            raise ValueError("image %d: the regression's normal equations are singular; use more samples or a ridge"
+                             % active[int(bad[0])])
+        self._fit = (phi, icpt, status)
+        return _eng.op_segment_map(phi, self.labels[torch.as_tensor(active, device=phi.device)], self.d)
+
+    def _extras(self, active, n_words, B):
+        phi, icpt, status = self._fit
+        coef, inter = [None] * B, [None] * B
+        st = torch.zeros((B,), dtype=torch.int32, device=phi.device)
+        st[torch.as_tensor(active, device=phi.device)] = status
+        for a, b in enumerate(active):
+            coef[b], inter[b] = phi[a, :int(n_words[a])], icpt[a, :int(n_words[a])]
+        return {"coefficients": coef, "intercept": inter, "segments": self.labels, "status": st}
+
+
+class LIMESaliency(_SegmentSaliency):
+    """LIME (Ribeiro, Singh & Guestrin 2016) on image segments: row 0 is the image itself and joins the fit as the all-ones sample
+    (as LIME's first sample does), rows 1 .. n_samples switch each segment on with probability p (off: `fill`).  A weighted ridge
+    regression of the word's score on the binary vectors, free intercept, the row weight LIME's exponential kernel of width
+    kernel_width on the cosine distance to the all-ones vector; a pixel's saliency is its segment's coefficient.  cells: the
+    regular grid used when `explain` gets no label map.  LIME's feature selection is not built: every segment enters the fit."""
+
+    @staticmethod
+    def check_arguments(n_samples=None, cells=7, p=0.5, kernel_width=0.25, ridge=1.0, seed=0, fill=0.0, score="prob", keys=None):
+        if n_samples is None or int(n_samples) != n_samples or n_samples < 1:
+            raise ValueError("n_samples must be a positive int")
+        if not 0.0 < float(p) <= 1.0:
+            raise ValueError("LIME needs 0 < p <= 1")
+        if not (np.isfinite(kernel_width) and float(kernel_width) > 0.0):
+            raise ValueError("kernel_width must be finite and > 0")
+        return _check_segment_common(cells, ridge, seed, keys, fill, score)
+
+    def __init__(self, explainer, n_samples, cells=7, p=0.5, kernel_width=0.25, ridge=1.0, seed=0, fill=0.0, score="prob", keys=None):
+        self.check_arguments(n_samples, cells, p, kernel_width, ridge, seed, fill, score, keys)
+        super(LIMESaliency, self).__init__(explainer, cells, ridge, seed, fill, score, keys)
+        self.n_samples, self.p, self.kernel_width = int(n_samples), float(p), float(kernel_width)
+
+    def _rows(self):
+        return self.n_samples
+
+    def _prepare(self, x_dev, image_ids):
+        keys, K = self._draw_keys(x_dev, image_ids), self.n_samples
+        self._active = list(image_ids)
+        self.bits = _eng.op_segment_draws(np.repeat(keys, K), np.tile(np.arange(K, dtype=np.int64), len(keys)), self.d, "bernoulli",
+                                          self.p, self.seed, device=x_dev.device)
+        self._full = torch.as_tensor(_full_bits(self.d)).to(x_dev.device)
+
+    def _apply(self, x_dev, img, k, grid_row, plain):
+        bits = self.bits[grid_row]
+        if plain:                                              # every segment on: the operator returns the image's bits
+            bits[torch.as_tensor(plain, device=x_dev.device)] = self._full
+        return _eng.op_segment_apply(x_dev, img, bits, self.labels, self.d, self.fill)
+
+    def _maps(self, S, H, W):
+        n_img = S.shape[0]
+        bits = torch.cat([self._full.view(1, 1, 4).expand(n_img, 1, 4), self.bits.view(n_img, self.n_samples, 4)], dim=1)
+        phi, icpt, status = _eng.op_segment_fit(bits, lime_weights(self.d, self.kernel_width), S, self.d, self.ridge)
+        return self._fold(phi, icpt, status, self._active)
+
+
+class KernelSHAPSaliency(_SegmentSaliency):
+    """KernelSHAP (Lundberg & Lee 2017) on image segments: row 0 is the image (`total`), row 1 the image with every segment
+    filled (`base`); the regression explains score - base under the constraint sum(phi) = total - base, which is eliminated as
+    the shap package does.  n_samples an even int >= 2 d: antithetic pairs of subsets drawn from the Shapley kernel's size
+    distribution, unit weights.  n_samples None: every one of the 2^d - 2 proper subsets in ascending integer order under the
+    Shapley kernel's weights, which gives the exact Shapley values of the d segments (d <= 12).  `intercept` is the base score."""
+
+    @staticmethod
+    def _check_samples(n_samples, d):
+        if n_samples is None:
+            if d > SHAP_ENUM_MAX_D:
+                raise NotImplementedError("enumerating the subsets of d=%d segments: n_samples=None is for d <= %d" % (d, SHAP_ENUM_MAX_D))
+        elif int(n_samples) != n_samples or n_samples % 2 or n_samples < 2 * d:
+            raise ValueError("n_samples must be an even int >= 2 d = %d (antithetic pairs; fewer leave the fit singular)" % (2 * d))
+
+    @staticmethod
+    def check_arguments(n_samples=None, cells=4, ridge=0.0, seed=0, fill=0.0, score="prob", keys=None):
+        d = _check_segment_common(cells, ridge, seed, keys, fill, score)
+        KernelSHAPSaliency._check_samples(n_samples, d)
+        return d
+
+    def __init__(self, explainer, n_samples=None, cells=4, ridge=0.0, seed=0, fill=0.0, score="prob", keys=None):
+        self.check_arguments(n_samples, cells, ridge, seed, fill, score, keys)
+        super(KernelSHAPSaliency, self).__init__(explainer, cells, ridge, seed, fill, score, keys)
+        self.n_samples = None if n_samples is None else int(n_samples)
+
+    def _check_d(self, d):                                     # (again with the d of the caller's label map)
+        _eng._seg_count(d)
+        self._check_samples(self.n_samples, d)
+
+    def _n(self):
+        return 2 ** self.d - 2 if self.n_samples is None else self.n_samples
+
+    def _rows(self):
+        return 1 + self._n()
+
+    def _prepare(self, x_dev, image_ids):
+        dev, K, n_img = x_dev.device, self._n(), len(image_ids)
+        self._active = list(image_ids)
+        if self.n_samples is None:
+            draws = torch.zeros((K, 4), dtype=torch.int32, device=dev)
+            draws[:, 0] = torch.arange(1, K + 1, dtype=torch.int32, device=dev)
+            draws = draws.unsqueeze(0).expand(n_img, K, 4)
+        else:
+            keys = self._draw_keys(x_dev, image_ids)
+            draws = _eng.op_segment_draws(np.repeat(keys, K), np.tile(np.arange(K, dtype=np.int64), n_img), self.d, "shapley",
+                                          seed=self.seed, device=dev).view(n_img, K, 4)
+        # per image: the empty subset (the base row), then the samples
+        self.bits = torch.cat([torch.zeros((n_img, 1, 4), dtype=torch.int32, device=dev), draws], dim=1).contiguous()
+        self._full = torch.as_tensor(_full_bits(self.d)).to(dev)
+
+    def _apply(self, x_dev, img, k, grid_row, plain):
+        bits = self.bits.view(-1, 4)[grid_row]
+        if plain:
+            bits[torch.as_tensor(plain, device=x_dev.device)] = self._full
+        return _eng.op_segment_apply(x_dev, img, bits, self.labels, self.d, self.fill)
+
+    def _maps(self, S, H, W):
+        base = S[:, 1]
+        delta = (S[:, 0] - base).contiguous()
+        y = (S[:, 2:] - base[:, None]).contiguous()
+        if self.n_samples is None:
+            wtab = shapley_weights(self.d)
+        else:
+            wtab = np.ones(self.d + 1, dtype=np.float64)
+            wtab[0] = wtab[self.d] = 0.0
+        phi, _, status = _eng.op_segment_fit(self.bits[:, 1:].contiguous(), wtab, y, self.d, self.ridge, delta)
+        return self._fold(phi, base.contiguous(), status, self._active)
