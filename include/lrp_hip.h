@@ -744,6 +744,69 @@ int lrp_op_rise_apply(const float* x_dev, const int32_t* img_idx_dev, const uint
 int lrp_op_rise_map(const double* scores_dev, const uint8_t* grid_dev, const int32_t* shift_dev, float* out_dev, int32_t n_img,
                     int32_t K, int32_t T, int32_t H, int32_t W, int32_t s, double p, int32_t ch, int32_t cw, void* stream);
 
+/* The class-activation-map family as word saliencies: the gradient forms Grad-CAM (Selvaraju et al. 2017), Grad-CAM++
+ * (Chattopadhay et al. 2018), XGrad-CAM (Fu et al. 2020), LayerCAM (Jiang et al. 2021) and HiResCAM (Draelos & Carin 2020), and
+ * the gradient-free forms Score-CAM (Wang et al. 2020) and Ablation-CAM (Desai & Ramaswamy 2020), whose channel weights come from
+ * forwards (lrp_encode_images or lrp_set_features, lrp_decoder_forward, lrp_perturb_word_scores).  Handle-free operators like
+ * lrp_op_gradcam and lrp_op_rise_*: device pointers, the caller's stream, no synchronisation; additive to the ABI.  Every
+ * argument is checked before any HIP call.  One workgroup per unit, (image, word) or slice of a row, fixed-order fp64
+ * reductions, no float atomics: an output is a pure function of its own arguments, so any cut into calls and any neighbours
+ * in a launch give the same bits.  (csrc/cam_kernels.h)
+ * Shared: feat_dev (B, L, D) float32 (lrp_get_features), L = g * g, S = g * upscale, M_dev (S, g) float64
+ *   (lrp_eval_expand_matrix on the device); g <= 16, S <= 448, D a multiple of 8 up to 4096.
+ *   The finish, from a coarse map A (L) in fp64: cam = max(M A M^T, 0), cam /= max(cam) + 1e-6 (a cam that is nowhere positive:
+ *   exact zeros) — the finish of lrp_op_gradcam, operation for operation.
+ * lrp_op_cam: arguments as lrp_op_gradcam, plus mode.  Per unit u with F = feat[img_idx[u]] and G = grads[u], (L, D), in fp64:
+ *   mode 0 gradcam    w_c = mean_l G[l][c];                                                    A[l] = sum_c F[l][c] w_c
+ *   mode 1 gradcam++  S_c = sum_l F[l][c], den = 2 G^2 + S_c G^3, alpha = den != 0 ? G^2 / den : 0 (per l, c),
+ *                     w_c = sum_l alpha[l][c] max(G[l][c], 0);                                 A[l] = sum_c F[l][c] w_c
+ *   mode 2 xgradcam   w_c = sum_l F[l][c] G[l][c] / (sum_l F[l][c] + 1e-7);                    A[l] = sum_c F[l][c] w_c
+ *   mode 3 layercam   A[l] = sum_c max(G[l][c], 0) F[l][c]
+ *   mode 4 hirescam   A[l] = sum_c G[l][c] F[l][c]
+ *   then the finish -> cam_dev (n, S, S) float64, and the optional gate out_dev (n, S * S, C) float64 = (double)gb * cam
+ *   (gb_dev and out_dev both or neither; C <= 64), which generalises Guided Grad-CAM to every form.  Mode 0 equals
+ *   lrp_op_gradcam bit for bit.  A unit whose image index is outside [0, B) reads nothing and comes out as NaN.
+ * lrp_op_cam_weighted: scores_dev (n_img, R, T) float64: row 0 the unmasked image, row 1 + k channel k, and for mode 1 row
+ *   1 + D the fill image; R = 1 + D (modes 0, 2) or 2 + D (mode 1), else LRP_ERR_INVALID.  img_idx_dev (n_img) int32: the image's
+ *   row of feat_dev.  Per (image, word t), with s_k = scores[1 + k][t]:
+ *   mode 0 softmax    w_k = exp(s_k - max_k s) / sum_k exp(s_k - max_k s), the sum in ascending k
+ *   mode 1 linear     w_k = s_k - s_fill
+ *   mode 2 ablation   w_k = (s_0 - s_k) / |s_0|; every weight 0 where s_0 == 0
+ *   A[l] = sum_c F[l][c] w_c, then the finish -> cam_dev (n_img, T, S, S) float64 and / or map_dev (n_img, T, S, S) float32, the
+ *   cam rounded once (either may be NULL, not both).  A NaN score makes that word's map NaN and nothing else; an image index
+ *   outside [0, B) makes the image's maps NaN.
+ * lrp_op_scorecam_apply: x_dev (B, H, W, C) float32 with H = W = g * upscale, k_dev (n) int32, fill_dev (C) float32 -> out_dev
+ *   (n, H, W, C) float32.  Row r with k in [0, D): the channel map v[l] = feat[img][l][k] is min-max normalised on the g x g grid
+ *   in float32, (v - min) / (max - min) with each operation rounded on its own (all zeros where max == min), then upsampled by
+ *   exactly `upscale` pixels per cell with the half-pixel-centre bilinear rule of lrp_op_rise_apply at shift 0 (ny = 2 y + 1 -
+ *   upscale, a0 = floor_div(ny, 2 upscale), fy = (ny - 2 upscale a0) / (2 upscale)), rows and columns clamped into [0, g - 1];
+ *   out = fill + m (x - fill) in its float32 rounding order.  (Normalising before the upsample equals normalising after it: a
+ *   bilinear interpolant takes its extremes at the nodes.)  k = -1 copies the image, k = D gives the fill image.  An image index
+ *   outside [0, B) or a k outside [-1, D] gives a NaN row.  16-byte accesses when H W C % 4 == 0 and both tensors are 16-byte
+ *   aligned.  n <= 65535 rows per call; D >= 1 (any value).
+ * lrp_op_feature_ablate: out_dev (n, L, D) float32: row r is feat[img_idx_dev[r]] with channel k_dev[r] set to 0 (a copy
+ *   otherwise: bit-exact); k = -1 copies the features.  An image index outside [0, B) or a k outside [-1, D) gives a NaN row.
+ *   Any L, D >= 1. */
+#define LRP_CAM_GRADCAM 0
+#define LRP_CAM_GRADCAMPP 1
+#define LRP_CAM_XGRADCAM 2
+#define LRP_CAM_LAYERCAM 3
+#define LRP_CAM_HIRESCAM 4
+#define LRP_CAMW_SOFTMAX 0
+#define LRP_CAMW_LINEAR 1
+#define LRP_CAMW_ABLATION 2
+int lrp_op_cam(const float* feat_dev, const int32_t* img_idx_dev, const float* grads_dev, const double* M_dev, const float* gb_dev,
+               double* cam_dev, double* out_dev, int32_t n, int32_t B, int32_t g, int32_t upscale, int32_t D, int32_t C,
+               int32_t mode, void* stream);
+int lrp_op_cam_weighted(const double* scores_dev, const float* feat_dev, const int32_t* img_idx_dev, const double* M_dev,
+                        double* cam_dev, float* map_dev, int32_t n_img, int32_t R, int32_t T, int32_t B, int32_t g, int32_t upscale,
+                        int32_t D, int32_t mode, void* stream);
+int lrp_op_scorecam_apply(const float* x_dev, const float* feat_dev, const int32_t* img_idx_dev, const int32_t* k_dev,
+                          const float* fill_dev, float* out_dev, int32_t n, int32_t B, int32_t g, int32_t upscale, int32_t C,
+                          int32_t D, void* stream);
+int lrp_op_feature_ablate(const float* feat_dev, const int32_t* img_idx_dev, const int32_t* k_dev, float* out_dev, int32_t n,
+                          int32_t B, int32_t L, int32_t D, void* stream);
+
 /* LIME (Ribeiro et al. 2016) and KernelSHAP (Lundberg & Lee 2017) word saliency: the mask is a binary choice over d segments of
  * the image (label_dev: an int32 label map from any segmenter), the masked copies go through the same forwards as above and the
  * word scores are folded by a weighted linear regression.  Handle-free operators like lrp_op_rise_*: device pointers, the

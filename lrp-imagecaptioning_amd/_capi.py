@@ -139,6 +139,10 @@ SYMBOLS = {
     "lrp_op_rise_grids": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_double, C.c_uint64] + [C.c_int32] * 4 + [_P, _P, _P]),
     "lrp_op_rise_apply": (C.c_int, [_P] * 6 + [C.c_int32] * 8 + [_P]),
     "lrp_op_rise_map": (C.c_int, [_P] * 4 + [C.c_int32] * 6 + [C.c_double, C.c_int32, C.c_int32, _P]),
+    "lrp_op_cam": (C.c_int, [_P] * 7 + [C.c_int32] * 7 + [_P]),
+    "lrp_op_cam_weighted": (C.c_int, [_P] * 6 + [C.c_int32] * 8 + [_P]),
+    "lrp_op_scorecam_apply": (C.c_int, [_P] * 6 + [C.c_int32] * 6 + [_P]),
+    "lrp_op_feature_ablate": (C.c_int, [_P] * 4 + [C.c_int32] * 4 + [_P]),
     "lrp_op_segment_draws": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_double, _P, C.c_uint64, _P, _P]),
     "lrp_op_segment_apply": (C.c_int, [_P] * 6 + [C.c_int32] * 6 + [_P]),
     "lrp_op_segment_fit": (C.c_int, [_P] * 4 + [C.c_double, _P, _P, _P] + [C.c_int32] * 4 + [_P]),

@@ -22,6 +22,7 @@
 #include "encoder.h"
 #include "eval_kernels.h"
 #include "gradcam_kernels.h"
+#include "cam_kernels.h"     // (after gradcam_kernels.h: it shares that kernel's stages)
 #include "perturb_kernels.h"
 #include "resnet_encoder.h"
 #include "rules_kernels.h"
@@ -1721,6 +1722,99 @@ int lrp_op_rise_map(const double* scores_dev, const uint8_t* grid_dev, const int
     if (blocks > INT32_MAX) return fail(LRP_ERR_INVALID, "n_img * T * H * W is too large for one launch: split the images");
     hipLaunchKernelGGL(rise_map_kernel, dim3((unsigned)blocks), dim3(256), 0, S(stream), scores_dev, grid_dev, shift_dev, out_dev, K, T,
                        g, (double)K * p);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+// ---- the CAM family as word saliencies (csrc/cam_kernels.h)
+static int cam_geometry(int32_t g, int32_t upscale, int32_t D) {
+  if (g < 1 || g > EVAL_MAX_G || upscale < 1 || g * upscale > EVAL_MAX_S)
+    return fail(LRP_ERR_INVALID, "need 1 <= g <= %d and 1 <= g * upscale <= %d", EVAL_MAX_G, EVAL_MAX_S);
+  if (D < 8 || D % 8 != 0 || D > GRADCAM_MAX_D) return fail(LRP_ERR_INVALID, "D must be a multiple of 8 in [8, %d]", GRADCAM_MAX_D);
+  return LRP_OK;
+}
+
+int lrp_op_cam(const float* feat_dev, const int32_t* img_idx_dev, const float* grads_dev, const double* M_dev, const float* gb_dev,
+               double* cam_dev, double* out_dev, int32_t n, int32_t B, int32_t g, int32_t upscale, int32_t D, int32_t C,
+               int32_t mode, void* stream) {
+  return guarded([&]() -> int {
+    if (!feat_dev || !img_idx_dev || !grads_dev || !M_dev || !cam_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if ((gb_dev == nullptr) != (out_dev == nullptr)) return fail(LRP_ERR_INVALID, "gb_dev and out_dev go together: both or neither may be null");
+    if (n < 1 || B < 1) return fail(LRP_ERR_INVALID, "n and B must be positive");
+    LRP_TRY(cam_geometry(g, upscale, D));
+    if (gb_dev && (C < 1 || C > 64)) return fail(LRP_ERR_INVALID, "need 1 <= C <= 64 channels of the gated map");
+    if (mode < 0 || mode >= CAM_MODES)
+      return fail(LRP_ERR_INVALID, "mode must be 0 (gradcam), 1 (gradcam++), 2 (xgradcam), 3 (layercam) or 4 (hirescam)");
+    const int Sd = g * upscale;
+    const size_t lds = (size_t)(g * g + (D > g * Sd ? D : g * Sd)) * sizeof(double);
+    hipLaunchKernelGGL(cam_kernel, dim3(n), dim3(256), lds, S(stream), feat_dev, img_idx_dev, grads_dev, M_dev, gb_dev, cam_dev,
+                       out_dev, B, g, Sd, D, C, mode);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_op_cam_weighted(const double* scores_dev, const float* feat_dev, const int32_t* img_idx_dev, const double* M_dev,
+                        double* cam_dev, float* map_dev, int32_t n_img, int32_t R, int32_t T, int32_t B, int32_t g, int32_t upscale,
+                        int32_t D, int32_t mode, void* stream) {
+  return guarded([&]() -> int {
+    if (!scores_dev || !feat_dev || !img_idx_dev || !M_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (!cam_dev && !map_dev) return fail(LRP_ERR_INVALID, "null argument: at least one of cam_dev and map_dev is needed");
+    if (n_img < 1 || T < 1 || B < 1) return fail(LRP_ERR_INVALID, "n_img, T and B must be positive");
+    LRP_TRY(cam_geometry(g, upscale, D));
+    if (mode < 0 || mode >= CAMW_MODES) return fail(LRP_ERR_INVALID, "mode must be 0 (softmax), 1 (linear) or 2 (ablation)");
+    const int rows = 1 + D + (mode == CAMW_LINEAR ? 1 : 0);
+    if (R != rows) return fail(LRP_ERR_INVALID, "the scores need R = %d rows per image in this mode (R=%d)", rows, R);
+    if ((int64_t)n_img * T > INT32_MAX) return fail(LRP_ERR_INVALID, "n_img * T must be below 2^31");
+    const int Sd = g * upscale;
+    const size_t lds = (size_t)(g * g + (D > g * Sd ? D : g * Sd)) * sizeof(double);
+    hipLaunchKernelGGL(cam_weighted_kernel, dim3(n_img * T), dim3(256), lds, S(stream), scores_dev, feat_dev, img_idx_dev, M_dev,
+                       cam_dev, map_dev, B, R, T, g, Sd, D, mode);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_op_scorecam_apply(const float* x_dev, const float* feat_dev, const int32_t* img_idx_dev, const int32_t* k_dev,
+                          const float* fill_dev, float* out_dev, int32_t n, int32_t B, int32_t g, int32_t upscale, int32_t C,
+                          int32_t D, void* stream) {
+  return guarded([&]() -> int {
+    if (!x_dev || !feat_dev || !img_idx_dev || !k_dev || !fill_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n < 1 || n > 65535 || B < 1) return fail(LRP_ERR_INVALID, "need 1 <= n <= 65535 rows and a positive B");
+    if (g < 1 || g > EVAL_MAX_G || upscale < 1 || upscale > RISE_MAX_CELL)
+      return fail(LRP_ERR_INVALID, "need 1 <= g <= %d and 1 <= upscale <= %d", EVAL_MAX_G, RISE_MAX_CELL);
+    if (D < 1) return fail(LRP_ERR_INVALID, "D must be positive");
+    if ((int64_t)g * upscale > INT32_MAX) return fail(LRP_ERR_INVALID, "one image must hold fewer than 2^31 values");
+    const int Sd = g * upscale;
+    LRP_TRY(saliency_image(Sd, Sd, C));
+    const size_t per = (size_t)Sd * Sd * C, groups = (per + 3) / 4;
+    const dim3 grid((unsigned)((groups + CAM_SLICE - 1) / CAM_SLICE), (unsigned)n);
+    const ScoreCamGeom q{g, upscale, C, D};
+    if (per % 4 == 0 && aligned16(x_dev, out_dev))
+      hipLaunchKernelGGL(scorecam_apply_kernel<true>, grid, dim3(256), 0, S(stream), x_dev, feat_dev, img_idx_dev, k_dev, fill_dev,
+                         out_dev, B, q);
+    else
+      hipLaunchKernelGGL(scorecam_apply_kernel<false>, grid, dim3(256), 0, S(stream), x_dev, feat_dev, img_idx_dev, k_dev, fill_dev,
+                         out_dev, B, q);
+    LRP_HIP_CHECK(hipGetLastError());
+    return LRP_OK;
+  });
+}
+
+int lrp_op_feature_ablate(const float* feat_dev, const int32_t* img_idx_dev, const int32_t* k_dev, float* out_dev, int32_t n,
+                          int32_t B, int32_t L, int32_t D, void* stream) {
+  return guarded([&]() -> int {
+    if (!feat_dev || !img_idx_dev || !k_dev || !out_dev) return fail(LRP_ERR_INVALID, "null argument");
+    if (n < 1 || B < 1 || L < 1 || D < 1) return fail(LRP_ERR_INVALID, "n, B, L and D must be positive");
+    if ((int64_t)L * D > INT32_MAX) return fail(LRP_ERR_INVALID, "one feature map must hold fewer than 2^31 values");
+    const size_t per = (size_t)L * D, work = (size_t)n * ((per + 3) / 4);
+    if (per % 4 == 0 && aligned16(feat_dev, out_dev))
+      hipLaunchKernelGGL(feature_ablate_kernel<true>, dim3(stream_grid(work)), dim3(256), 0, S(stream), feat_dev, img_idx_dev, k_dev,
+                         out_dev, n, B, L, D);
+    else
+      hipLaunchKernelGGL(feature_ablate_kernel<false>, dim3(stream_grid(work)), dim3(256), 0, S(stream), feat_dev, img_idx_dev, k_dev,
+                         out_dev, n, B, L, D);
     LRP_HIP_CHECK(hipGetLastError());
     return LRP_OK;
   });

@@ -1627,6 +1627,141 @@ def op_rise_map(scores, grid, shift, H, W, s, p, cell=None):
     return out
 
 
+# ---- the CAM family as word saliencies (csrc/cam_kernels.h, lrp_op_cam / _cam_weighted / _scorecam_apply / _feature_ablate)
+CAM_MODES = {"gradcam": 0, "gradcam++": 1, "xgradcam": 2, "layercam": 3, "hirescam": 4}
+CAM_WEIGHTS = {"softmax": 0, "linear": 1, "ablation": 2}
+CAM_MAX_G, CAM_MAX_S, CAM_MAX_D = 16, 448, 4096
+
+
+def cam_geometry(L, H, W):
+    """(g, upscale) of an (H, W) image over L = g * g feature positions.  ValueError unless the image is square and its side a
+    multiple of sqrt(L); NotImplementedError beyond g = 16 or a side of 448."""
+    g = int(round(np.sqrt(L)))
+    if g < 1 or g * g != L or H != W or H < g or H % g != 0:
+        raise ValueError("the CAM family needs a square image whose side is a multiple of sqrt(L): image (%d, %d), L=%d" % (H, W, L))
+    if g > CAM_MAX_G or H > CAM_MAX_S:
+        raise NotImplementedError("the CAM kernels take g <= %d and an image side <= %d" % (CAM_MAX_G, CAM_MAX_S))
+    return g, H // g
+
+
+def _cam_channels(D):
+    if D < 8 or D % 8 != 0 or D > CAM_MAX_D:
+        raise ValueError("D must be a multiple of 8 in [8, %d] (D=%d)" % (CAM_MAX_D, D))
+
+
+def _cam_features(feat, g):
+    if not torch.is_tensor(feat) or feat.dtype != torch.float32 or feat.dim() != 3 or feat.shape[1] != g * g or not feat.is_cuda:
+        raise ValueError("expected a (B, g * g, D) float32 device tensor of features")
+    return feat.contiguous()
+
+
+def op_cam(feat, img_idx, grads, g, upscale, method="gradcam", gb=None, sigma=20.0):
+    """The gradient forms of the CAM family for n (image, word) units in fp64 on the device: feat (B, L, D) float32 device
+    tensor, img_idx n image indices, grads (n, L, D) float32, L = g * g, method one of CAM_MODES -> cam (n, S, S) float64,
+    S = g * upscale.  With gb (n, S, S, C) float32 -> (gb * cam (n, S, S, C) float64, cam).  method='gradcam' equals op_gradcam
+    bit for bit.  A unit whose image index is outside [0, B) comes out as NaN."""
+    if method not in CAM_MODES:
+        raise ValueError("unknown CAM method %r: one of %s" % (method, sorted(CAM_MODES)))
+    g, upscale = int(g), int(upscale)
+    if not (1 <= g <= CAM_MAX_G and upscale >= 1 and g * upscale <= CAM_MAX_S):
+        raise ValueError("need 1 <= g <= %d and 1 <= g * upscale <= %d" % (CAM_MAX_G, CAM_MAX_S))
+    if not torch.is_tensor(feat) or not torch.is_tensor(grads) or feat.dim() != 3 or grads.dim() != 3:
+        raise ValueError("expected feat (B, g * g, D) and grads (n, g * g, D) float32 tensors")
+    _cam_channels(int(feat.shape[2]))
+    f = _cam_features(feat, g)
+    d = grads.contiguous()
+    if d.dtype != torch.float32 or tuple(d.shape[1:]) != tuple(f.shape[1:]) or d.device != f.device:
+        raise ValueError("expected feat (B, g * g, D) and grads (n, g * g, D) float32 tensors on one device")
+    n, B, D, S = d.shape[0], f.shape[0], f.shape[2], g * upscale
+    idx = _sal_ints(img_idx, f.device, n)
+    out = None
+    if gb is not None:
+        gb = gb.contiguous()
+        if gb.dtype != torch.float32 or gb.dim() != 4 or tuple(gb.shape[:3]) != (n, S, S) or not 1 <= gb.shape[3] <= 64:
+            raise ValueError("gb must be an (n, S, S, C) float32 tensor, C <= 64")
+        out = torch.empty(gb.shape, dtype=torch.float64, device=f.device)
+    M = _expand_matrix_dev(f.device, g, upscale, sigma)
+    cam = torch.empty((n, S, S), dtype=torch.float64, device=f.device)
+    _capi.check(_capi.load().lrp_op_cam(_p(f), _p(idx), _p(d), _p(M), _p(gb), _p(cam), _p(out), n, B, g, upscale, D,
+                                        gb.shape[3] if gb is not None else 0, CAM_MODES[method], _cur_stream(f.device)))
+    return cam if gb is None else (out, cam)
+
+
+def op_cam_weighted(scores, feat, img_idx, g, upscale, weights="softmax", want_cam=False, sigma=20.0):
+    """The fold of Score-CAM and Ablation-CAM: scores (n_img, R, T) float64 device tensor (row 0 the unmasked image, row 1 + k
+    channel k, with 'linear' row 1 + D the fill image), feat (B, L, D) float32, img_idx n_img rows of feat, weights one of
+    CAM_WEIGHTS -> (n_img, T, S, S) float32 maps (want_cam: (maps, the float64 cams they were rounded from))."""
+    if weights not in CAM_WEIGHTS:
+        raise ValueError("unknown weighting %r: one of %s" % (weights, sorted(CAM_WEIGHTS)))
+    g, upscale = int(g), int(upscale)
+    if not (1 <= g <= CAM_MAX_G and upscale >= 1 and g * upscale <= CAM_MAX_S):
+        raise ValueError("need 1 <= g <= %d and 1 <= g * upscale <= %d" % (CAM_MAX_G, CAM_MAX_S))
+    if not torch.is_tensor(feat) or feat.dim() != 3:
+        raise ValueError("expected a (B, g * g, D) float32 device tensor of features")
+    D = int(feat.shape[2])
+    _cam_channels(D)
+    f = _cam_features(feat, g)
+    R = 1 + D + (weights == "linear")
+    if not torch.is_tensor(scores) or scores.dtype != torch.float64 or scores.dim() != 3 or scores.shape[1] != R \
+            or scores.device != f.device or scores.shape[2] < 1:
+        raise ValueError("scores must be an (n_img, %d, T) float64 tensor on the device of the features" % R)
+    scores = scores.contiguous()
+    n_img, _, T = scores.shape
+    idx = _sal_ints(img_idx, f.device, n_img)
+    S = g * upscale
+    M = _expand_matrix_dev(f.device, g, upscale, sigma)
+    maps = torch.empty((n_img, T, S, S), dtype=torch.float32, device=f.device)
+    cam = torch.empty((n_img, T, S, S), dtype=torch.float64, device=f.device) if want_cam else None
+    _capi.check(_capi.load().lrp_op_cam_weighted(_p(scores), _p(f), _p(idx), _p(M), _p(cam), _p(maps), n_img, R, T, f.shape[0], g,
+                                                 upscale, D, CAM_WEIGHTS[weights], _cur_stream(f.device)))
+    return (maps, cam) if want_cam else maps
+
+
+def op_scorecam_apply(x, feat, img_idx, k, g, upscale, fill=0.0):
+    """x (B, H, W, C) float32 device tensor, H = W = g * upscale, feat (B, g * g, D) -> (n, H, W, C): row r is fill + m (x - fill)
+    with m the min-max normalised, bilinearly upsampled map of channel k[r] of image img_idx[r]; k = -1 copies the image, k = D
+    gives the fill image; an image index outside [0, B) or a k outside [-1, D] gives a NaN row."""
+    x = _sal_images(x)
+    B, Hh, Ww, Cc = x.shape
+    g, upscale = int(g), int(upscale)
+    if not (1 <= g <= CAM_MAX_G and upscale >= 1) or Hh != Ww or Hh != g * upscale:
+        raise ValueError("need a square image of side g * upscale, 1 <= g <= %d: image (%d, %d), g=%d, upscale=%d"
+                         % (CAM_MAX_G, Hh, Ww, g, upscale))
+    f = _cam_features(feat, g)
+    dev = x.device
+    if f.device != dev or f.shape[0] != B:
+        raise ValueError("feat must hold the features of the B images, on their device")
+    idx = _sal_ints(img_idx, dev)
+    n = idx.shape[0]
+    if not 1 <= n <= 65535:
+        raise ValueError("between 1 and 65535 rows per call")
+    kk = _sal_ints(k, dev, n)
+    fl = fill.to(device=dev, dtype=torch.float32).contiguous() if torch.is_tensor(fill) else _sal_fill(fill, Cc, dev)
+    if tuple(fl.shape) != (Cc,):
+        raise ValueError("fill must hold one value per channel")
+    out = torch.empty((n, Hh, Ww, Cc), dtype=torch.float32, device=dev)
+    _capi.check(_capi.load().lrp_op_scorecam_apply(_p(x), _p(f), _p(idx), _p(kk), _p(fl), _p(out), n, B, g, upscale, Cc,
+                                                   int(f.shape[2]), _cur_stream(dev)))
+    return out
+
+
+def op_feature_ablate(feat, img_idx, k):
+    """feat (B, L, D) float32 device tensor -> (n, L, D): row r is feat[img_idx[r]] with channel k[r] set to 0; k = -1 copies;
+    an image index outside [0, B) or a k outside [-1, D) gives a NaN row."""
+    if not torch.is_tensor(feat) or feat.dtype != torch.float32 or feat.dim() != 3 or not feat.is_cuda:
+        raise ValueError("expected a (B, L, D) float32 device tensor of features")
+    f = feat.contiguous()
+    B, L, D = f.shape
+    idx = _sal_ints(img_idx, f.device)
+    n = idx.shape[0]
+    if n < 1:
+        raise ValueError("at least one row")
+    kk = _sal_ints(k, f.device, n)
+    out = torch.empty((n, L, D), dtype=torch.float32, device=f.device)
+    _capi.check(_capi.load().lrp_op_feature_ablate(_p(f), _p(idx), _p(kk), _p(out), n, B, L, D, _cur_stream(f.device)))
+    return out
+
+
 # ---- LIME and KernelSHAP word saliency (csrc/segment_kernels.h, lrp_op_segment_*)
 SEG_MAX_D = 128
 SEG_MODES = {"bernoulli": 0, "shapley": 1}

@@ -799,3 +799,46 @@ class ExplainImgCaptioningGridTDLIME(_LIMEMixin, ExplainImgCaptioningGridTDModel
 
 class ExplainImgCaptioningGridTDKernelSHAP(_KernelSHAPMixin, ExplainImgCaptioningGridTDModel):
     pass
+
+
+# The CAM family (saliency.py; csrc/cam_kernels.h): the same scheme.  CAM takes method= ('gradcam', 'gradcam++', 'xgradcam',
+# 'layercam', 'hirescam') and guided=; it reads the decoder gradient and is limited as the gradient baselines above are (exact
+# fp32 forward; adaptive decoder with embedding_dim == hidden_dim).  ScoreCAM and AblationCAM read forwards only.  The Guided
+# Grad-CAM classes above are the reference's and stay as they are.
+class _CAMMixin(_SaliencyMixin):
+    _driver = "GradientCAMSaliency"
+    _KW = ("method", "guided")
+
+
+class _ScoreCAMMixin(_SaliencyMixin):
+    _driver = "ScoreCAMSaliency"
+    _KW = ("weights", "fill", "score")
+
+
+class _AblationCAMMixin(_SaliencyMixin):
+    _driver = "AblationCAMSaliency"
+    _KW = ("score",)
+
+
+class ExplainImgCaptioningAdaptiveAttentionCAM(_CAMMixin, ExplainImgCaptioningAdaptiveAttention):
+    pass
+
+
+class ExplainImgCaptioningAdaptiveAttentionScoreCAM(_ScoreCAMMixin, ExplainImgCaptioningAdaptiveAttention):
+    pass
+
+
+class ExplainImgCaptioningAdaptiveAttentionAblationCAM(_AblationCAMMixin, ExplainImgCaptioningAdaptiveAttention):
+    pass
+
+
+class ExplainImgCaptioningGridTDCAM(_CAMMixin, ExplainImgCaptioningGridTDModel):
+    pass
+
+
+class ExplainImgCaptioningGridTDScoreCAM(_ScoreCAMMixin, ExplainImgCaptioningGridTDModel):
+    pass
+
+
+class ExplainImgCaptioningGridTDAblationCAM(_AblationCAMMixin, ExplainImgCaptioningGridTDModel):
+    pass

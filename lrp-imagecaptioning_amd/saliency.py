@@ -10,6 +10,12 @@ compared against.
                         saliency is its segment's coefficient in a kernel-weighted ridge regression of the score on the switches
     KernelSHAPSaliency  (Lundberg & Lee, NeurIPS 2017) the same regression under the Shapley kernel and the efficiency constraint:
                         the segments' Shapley values, sampled or (up to 12 segments) exact
+    GradientCAMSaliency (Grad-CAM, Grad-CAM++, XGrad-CAM, LayerCAM, HiResCAM) a map over the positions of the encoder output from the
+                        gradient of the word's logit there, expanded to the image; no masked forward
+    ScoreCAMSaliency    (Wang et al., CVPR-W 2020) mask the image by each feature channel's own upsampled map; a channel's weight
+                        in the CAM is the word's score under its mask
+    AblationCAMSaliency (Desai & Ramaswamy, WACV 2020) zero one channel of the encoder output at a time; a channel's weight is the
+                        relative fall of the word's score (decoder forwards only)
 
 A masked image is one image slot of the engine: per chunk of max_images slots (any mix of images and masks) the apply operator
 makes the rows (lrp_op_occlude / lrp_op_rise_apply), `encode_images` and one teacher-forced `decoder_forward` with each slot's
@@ -73,7 +79,44 @@ class _WordSaliency(object):
         """what a method adds to the result dict, after _maps"""
         return {}
 
+    def _check_images(self, x_dev):
+        """what a method demands of the (B, H, W, 3) images, before anything runs"""
+        pass
+
+    def _enter(self, eng, rows):
+        """how a chunk's rows enter the engine: masked images through the encoder (the CAM family's ablated feature rows
+        replace its output instead)"""
+        eng.encode_images(rows)
+
     # ---------------------------------------------------------------- the driver
+    def _units(self, images, captions, words, segments):
+        """the arguments of `explain`, checked -> (x_dev, B, H, W, captions, units, words_of, active)"""
+        ex = self.explainer
+        eng = ex._engine
+        x_dev = eng._dev(images)
+        if x_dev.dim() != 4:
+            raise ValueError("expected (B, H, W, 3) images")
+        B, H, W = int(x_dev.shape[0]), int(x_dev.shape[1]), int(x_dev.shape[2])
+        self._check_images(x_dev)
+        self._set_segments(x_dev, segments)
+        if captions is None:
+            res = ex._beam_search((None, x_dev.cpu().numpy()))
+            captions = [res[0]] if B == 1 else [r[0] for r in res]
+        captions = [list(map(int, c)) for c in captions]
+        if len(captions) != B or (words is not None and len(words) != B):
+            raise ValueError("one caption (and one list of word positions) per image")
+        units, words_of = [], []
+        for b in range(B):
+            ts = [int(t) for t in (range(1, len(captions[b])) if words is None else words[b])]
+            for t in ts:
+                if t < 1 or t > len(captions[b]):
+                    raise NotImplementedError("index out of range of captions")          # E:538-539
+                units.append((b, t))
+            words_of.append(ts)
+        if not units:
+            raise ValueError("no word to explain")
+        return x_dev, B, H, W, captions, units, words_of, [b for b in range(B) if words_of[b]]
+
     def explain(self, images, captions=None, words=None, segments=None):
         """images (B, H, W, 3) preprocessed (numpy or device tensor); captions: one id list per image (None: beam search); words:
         per image the positions t >= 1 to explain (None: every word before EOS), as in
@@ -92,28 +135,7 @@ class _WordSaliency(object):
         ex = self.explainer
         eng = ex._engine
         dev = eng.device
-        x_dev = eng._dev(images)
-        if x_dev.dim() != 4:
-            raise ValueError("expected (B, H, W, 3) images")
-        B, H, W = int(x_dev.shape[0]), int(x_dev.shape[1]), int(x_dev.shape[2])
-        self._set_segments(x_dev, segments)
-        if captions is None:
-            res = ex._beam_search((None, x_dev.cpu().numpy()))
-            captions = [res[0]] if B == 1 else [r[0] for r in res]
-        captions = [list(map(int, c)) for c in captions]
-        if len(captions) != B or (words is not None and len(words) != B):
-            raise ValueError("one caption (and one list of word positions) per image")
-        units, words_of = [], []
-        for b in range(B):
-            ts = [int(t) for t in (range(1, len(captions[b])) if words is None else words[b])]
-            for t in ts:
-                if t < 1 or t > len(captions[b]):
-                    raise NotImplementedError("index out of range of captions")          # E:538-539
-                units.append((b, t))
-            words_of.append(ts)
-        if not units:
-            raise ValueError("no word to explain")
-        active = [b for b in range(B) if words_of[b]]
+        x_dev, B, H, W, captions, units, words_of, active = self._units(images, captions, words, segments)
         self._prepare(x_dev, active)
         R = 1 + self._rows()                                   # row 0: the unmasked image (k = -1)
         Tp = -(-max(len(words_of[b]) for b in active) // _TILE) * _TILE
@@ -144,7 +166,7 @@ class _WordSaliency(object):
             c1 = min(len(job_ai), c0 + M)
             rows = self._apply(x_dev, job_img_d[c0:c1], job_k_d[c0:c1], job_grid_d[c0:c1],
                                [j - c0 for j in range(c0, c1) if job_row[j] == 0])
-            eng.encode_images(rows)
+            self._enter(eng, rows)
             eng.decoder_forward([captions[active[a]] for a in job_ai[c0:c1]])
             u0, u1 = int(ustart[c0]), int(ustart[c1])
             logit, logp = _eng.perturb_word_scores(eng, unit_job_d[u0:u1] - c0, unit_t_d[u0:u1], unit_col_d[u0:u1])
@@ -472,3 +494,155 @@ class KernelSHAPSaliency(_SegmentSaliency):
             wtab[0] = wtab[self.d] = 0.0
         phi, _, status = _eng.op_segment_fit(self.bits[:, 1:].contiguous(), wtab, y, self.d, self.ridge, delta)
         return self._fold(phi, base.contiguous(), status, self._active)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The CAM family (csrc/cam_kernels.h): a map over the L = g * g positions of the encoder output, expanded to the image as
+# Guided Grad-CAM's factor is.  The gradient forms read lrp_decoder_gradient and run no masked forward; Score-CAM and
+# Ablation-CAM take their channel weights from forwards and run on the driver above.
+# ---------------------------------------------------------------------------------------------------------------
+CAM_METHODS = tuple(sorted(_eng.CAM_MODES, key=_eng.CAM_MODES.get))
+SCORECAM_WEIGHTS = ("softmax", "linear")
+
+
+def _cam_model(explainer):
+    """(g, upscale) of the explainer's model; ValueError / NotImplementedError where the CAM kernels do not reach"""
+    eng = explainer._engine
+    _eng._cam_channels(eng.D)
+    return _eng.cam_geometry(eng.L, eng.img_hw[0], eng.img_hw[1])
+
+
+class GradientCAMSaliency(_WordSaliency):
+    """method: 'gradcam' (Selvaraju et al. 2017), 'gradcam++' (Chattopadhay et al. 2018), 'xgradcam' (Fu et al. 2020),
+    'layercam' (Jiang et al. 2021) or 'hirescam' (Draelos & Carin 2020), on the gradient of the word's logit at the encoder
+    output.  No masked forward: per chunk of min(max_images, max_tokens) units encode_images, one teacher-forced
+    decoder_forward, decoder_gradient and lrp_op_cam.  guided: the cam also gates the guided-backprop map of the unit (Guided
+    Grad-CAM for every form): the result gains "guided", (n_units, H, W, 3) float64.  "maps" is the cam in float32, "scores0"
+    the word's logit, "scores" per image its (1, n_words) row.  Limited as the gradient baselines are: the engine is switched
+    to the exact fp32 forward, and an adaptive decoder needs embedding_dim == hidden_dim."""
+
+    @staticmethod
+    def check_arguments(method="gradcam", guided=False):
+        if method not in CAM_METHODS:
+            raise ValueError("unknown CAM method %r: one of %s" % (method, list(CAM_METHODS)))
+        if guided not in (False, True):
+            raise ValueError("guided must be a bool")
+
+    def __init__(self, explainer, method="gradcam", guided=False):
+        self.check_arguments(method, guided)
+        super(GradientCAMSaliency, self).__init__(explainer, 0.0, "logit")
+        self.method, self.guided = method, bool(guided)
+        self._g, self._up = _cam_model(explainer)
+        eng = explainer._engine
+        if eng.decoder == "adaptive" and eng.E != eng.H:
+            raise NotImplementedError("the decoder gradient of the adaptive model needs embedding_dim == hidden_dim")
+        eng.set_precision("fp32")                              # (as _GradientMixin: the forward whose ReLU decisions are exact fp32)
+
+    def _check_images(self, x_dev):
+        _eng.cam_geometry(self.explainer._engine.L, int(x_dev.shape[1]), int(x_dev.shape[2]))
+
+    def explain(self, images, captions=None, words=None, segments=None):
+        ex = self.explainer
+        eng = ex._engine
+        dev = eng.device
+        x_dev, B, H, W, captions, units, words_of, active = self._units(images, captions, words, segments)
+        chunk = min(eng.max_images, eng.max_tokens)
+        cams, gated, s0 = [], [], []
+        for c0 in range(0, len(units), chunk):
+            part = units[c0:c0 + chunk]
+            imgs = sorted(set(b for b, _ in part))             # at most `chunk` images: the units are in image order
+            slot = dict((b, i) for i, b in enumerate(imgs))
+            eng.encode_images(x_dev[torch.as_tensor(imgs, device=dev)])
+            eng.decoder_forward([captions[b] for b in imgs])
+            ii, tt = [slot[b] for b, _ in part], [t for _, t in part]
+            d, _ = eng.decoder_gradient(ii, tt, want_r_words=False)
+            gb = eng.cnn_walk(ii, d, "guided_backprop") if self.guided else None
+            r = _eng.op_cam(eng.get_features(), ii, d, self._g, self._up, self.method, gb=gb)
+            if self.guided:
+                gated.append(r[0])
+                r = r[1]
+            cams.append(r)
+            s0.append(_eng.perturb_word_scores(eng, ii, tt, [captions[b][t - 1] - 1 for b, t in part])[0])
+        ex.caption = None                                      # the engine's caches now hold the last chunk
+        ex._state_cache = {}
+        s0 = torch.cat(s0)
+        per_image, u0 = [None] * B, 0
+        for b in active:
+            per_image[b] = s0[u0:u0 + len(words_of[b])].view(1, -1)
+            u0 += len(words_of[b])
+        res = {"units": units, "maps": torch.cat(cams).to(torch.float32), "scores0": s0, "scores": per_image}
+        if self.guided:
+            res["guided"] = torch.cat(gated)
+        return res
+
+
+class _ForwardCAMSaliency(_WordSaliency):
+    """what Score-CAM and Ablation-CAM share: the images' features kept on the device, one row per feature channel, the fold"""
+    _weights = None
+
+    def __init__(self, explainer, fill, score):
+        super(_ForwardCAMSaliency, self).__init__(explainer, fill, score)
+        self._g, self._up = _cam_model(explainer)
+
+    def _check_images(self, x_dev):
+        _eng.cam_geometry(self.explainer._engine.L, int(x_dev.shape[1]), int(x_dev.shape[2]))
+
+    def _rows(self):
+        return self.explainer._engine.D
+
+    def _prepare(self, x_dev, image_ids):
+        eng = self.explainer._engine
+        ids = torch.as_tensor(list(image_ids), device=x_dev.device)
+        self._active = ids.to(torch.int32)
+        self.feat = torch.zeros((x_dev.shape[0], eng.L, eng.D), dtype=torch.float32, device=x_dev.device)
+        for c0 in range(0, len(image_ids), eng.max_images):
+            eng.encode_images(x_dev[ids[c0:c0 + eng.max_images]])
+            self.feat[ids[c0:c0 + eng.max_images]] = eng.get_features()
+
+    def _maps(self, S, H, W):
+        return _eng.op_cam_weighted(S, self.feat, self._active, self._g, self._up, self._weights)
+
+
+class ScoreCAMSaliency(_ForwardCAMSaliency):
+    """Score-CAM (Wang et al. 2020): row k of an image is the image under the min-max normalised, bilinearly upsampled map of
+    feature channel k (`fill` where the map is 0), D rows per image; a channel's weight is the softmax over the channels of the
+    word's score under its mask ('softmax', the paper's form) or the score's rise over the all-fill image, one more row
+    ('linear', the paper's "increase of confidence" without the softmax).  The coarse map is sum_c F[l][c] w_c."""
+
+    @staticmethod
+    def check_arguments(weights="softmax", fill=0.0, score="logit"):
+        if weights not in SCORECAM_WEIGHTS:
+            raise ValueError("weights must be 'softmax' or 'linear'")
+        _check_common(fill, score)
+
+    def __init__(self, explainer, weights="softmax", fill=0.0, score="logit"):
+        self.check_arguments(weights, fill, score)
+        super(ScoreCAMSaliency, self).__init__(explainer, fill, score)
+        self.weights = self._weights = weights
+
+    def _rows(self):
+        return self.explainer._engine.D + (self.weights == "linear")
+
+    def _apply(self, x_dev, img, k, grid_row, plain):
+        return _eng.op_scorecam_apply(x_dev, self.feat, img, k, self._g, self._up, self.fill)   # (k = -1 copies, k = D: the fill image)
+
+
+class AblationCAMSaliency(_ForwardCAMSaliency):
+    """Ablation-CAM (Desai & Ramaswamy 2020): row k of an image is its encoder output with channel k set to 0, which enters the
+    engine through set_features: decoder forwards only.  A channel's weight is the relative fall of the word's score,
+    (s_0 - s_k) / |s_0|."""
+    _weights = "ablation"
+
+    @staticmethod
+    def check_arguments(score="logit"):
+        _check_common(0.0, score)
+
+    def __init__(self, explainer, score="logit"):
+        self.check_arguments(score)
+        super(AblationCAMSaliency, self).__init__(explainer, 0.0, score)
+
+    def _apply(self, x_dev, img, k, grid_row, plain):
+        return _eng.op_feature_ablate(self.feat, img, k)       # (k = -1 copies the features)
+
+    def _enter(self, eng, rows):
+        eng.set_features(rows)
