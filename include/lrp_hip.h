@@ -955,6 +955,9 @@ int lrp_reload_switches(void);
  * weights from registers (one workgroup barrier per channel chunk) — with LRP_PLAN_FRAG and N % 128 == 0, for the dense split-bf16
  * LRP_EPI_MUL launch (no JOIN, no request) and the interleaved fp16-pair LRP_EPI_FWD_DUAL (terms 7 | 23; POOL_GC gives the _POOL
  * form).  LRP_CONV_BREG4=0 gives the pipelined forms back.
+ * LRP_FORM_BREG (N <= 64, 128 x 64 tile, weights in registers) names two loops of one kernel family; which one a launch runs on is the
+ * launcher's choice and no part of this answer: the chunk loop of LRP_FORM_BREG8 / BREG4 for the dense split-bf16 LRP_EPI_MUL
+ * launch, the tile's first loop for everything else and under LRP_CONV_BREG2=0.  Every field here is the same under both settings.
  * LRP_PLAN_DUAL_MUL (added later in ABI v10): the dual-gate epilogue of the alpha-beta walk (two gates on one accumulator, two outputs; Cin counts both
  * chains).  LRP_EPI_MUL / LRP_EPI_MUL_UP2 with LRP_OPND_FP32 or LRP_OPND_BF16X3 on LRP_FORM_PLAIN, LRP_FORM_SMALL and the 128 x 128
  * LRP_FORM_HALO; never the 8-wave tile or a weights-in-registers form; refused with FRAG, JOIN, GMASK, any request, LRP_OPND_F16X2,

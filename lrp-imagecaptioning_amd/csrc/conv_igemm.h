@@ -65,13 +65,16 @@ __device__ __attribute__((aligned(16))) float lrp_zero_page[4] = {0.f, 0.f, 0.f,
 // dense launch's loop as well, and every reuse of one of them waited for the weight loads in flight [ISA: vmcnt(1) three times a chunk].
 // DG (EPI_MUL / EPI_MUL_UP2, PREC_FP32 and PREC_BF16X3, staged and pipelined resident-image tiles): the dual-gate epilogue
 // (ConvArgs::aux_b).  An axis of its own for GMASK's reason: the single-gate instantiations compile to what they were.
+// C2 (the 128 x 64 weights-in-registers tile, FORM_BREG, dense split-bf16 walk only): the chunk loop of the 8-wave tile instead of this
+// tile's first loop (BREG2 below; LRP_CONV_BREG2).  An axis of its own because both loops stay instantiated for the same tile.
 template <int WM, int WN, int TM, int TN, int EPI, int PREC, bool HALO = false, bool BREG = false, int TERMS = 7, int NS = 2,
-          bool GMASK = false, bool PW = false, bool DG = false>
+          bool GMASK = false, bool PW = false, bool DG = false, bool C2 = false>
 __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 : NS > 2 ? 2 : conv_min_waves(WM * WN, TM, TN, HALO)) void conv_igemm_kernel(ConvArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)   // the host pass only needs the launch stub (the buffer-resource builtins are device-only)
-  using T = ConvKernelTraits<WM, WN, TM, TN, EPI, PREC, HALO, BREG, TERMS, NS, GMASK, PW, DG>;
+  using T = ConvKernelTraits<WM, WN, TM, TN, EPI, PREC, HALO, BREG, TERMS, NS, GMASK, PW, DG, C2>;
   // BREG8: no B stage, so LDS is the two resident images or one 128-row C slab of the epilogue, whichever is larger (128 KB)
   // BREG4: the two resident images + a spare slot per wave (52 KB) or the epilogue's whole 128 x 128 C tile (64 KB; 80 KB pipelined)
+  // BREG2: the same 52 KB, three workgroups per CU
   __shared__ __attribute__((aligned(16))) float smem[T::SMEM];
 
   // ---- XCD-aware block remap: the n_tiles blocks that share an A tile get
@@ -295,10 +298,10 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
   typedef unsigned u32x2w __attribute__((ext_vector_type(2)));
   struct PwItem { u32x4 hi, lo; u32x2w q; };
   // (BREG4: the same items, sequenced by the chunk's steps instead — see its loop)
-  [[maybe_unused]] const bool pw = T::BREG4 ? PW : HALO && !BREG && PREC == PREC_BF16X3 && a.up2_src != nullptr;
+  [[maybe_unused]] const bool pw = T::BREG4 ? PW : T::BREG2 ? false : HALO && !BREG && PREC == PREC_BF16X3 && a.up2_src != nullptr;
   [[maybe_unused]] int pw_wx0 = 0, pw_nwx = 1, pw_items = 0, pw_ri0 = 0, pw_ri1 = 0;
   [[maybe_unused]] float pw_inv_nwx = 1.f;
-  if constexpr (HALO && (!BREG || PW) && PREC == PREC_BF16X3) {
+  if constexpr (HALO && (!BREG || (PW && T::BREG4)) && PREC == PREC_BF16X3) {
     if (pw) {
       pw_wx0 = (x0 - 1) >> 1;                           // (arithmetic shift: the window column outside the image for x0 = 0)
       pw_nwx = ((x0 + a.tw) >> 1) - pw_wx0 + 1;
@@ -361,75 +364,90 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     }
   };
   [[maybe_unused]] PwItem pwi{};
-  if constexpr (T::BREGC) {
-    if constexpr (PW) {
+  // compact pool interface into the 128 x 64 weights-in-registers tile (pairs of S_c; per-token tiles, at most 64 channels: conv_plan
+  // checks): the whole A operand — both chunks, both LDS buffers — is built up front.
+  [[maybe_unused]] auto breg_window_loader = [&]() {
+    // compact pool interface (pairs of S_c, per-token tiles: the launcher checks): item = (window of the resident image,
+    // 8-channel group)
+    const int Hp = a.H >> 1, Wp = a.W >> 1;
+    const int h0 = Y0 - img0 * a.H;                      // the tile's first image row (tiles are per token)
+    const int wy0 = (h0 - 1) >> 1, wx0 = (x0 - 1) >> 1;  // (arithmetic shifts: -1 >> 1 = -1, the window row / column outside the image)
+    const int nwx = ((x0 + a.tw) >> 1) - wx0 + 1, nwy = ((h0 + a.th) >> 1) - wy0 + 1;
+    const int items = nwy * nwx * 8;
+    const int ntok = img0 < a.NB ? img0 : a.NB - 1;
+    const int img = a.row2img ? a.row2img[ntok] : ntok;
+    const float inv_nwx = 1.0f / (float)nwx;
+    constexpr int UW = 2;                                // items in flight per thread (2 x 16 B + 8 B of loads each)
+    typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
+    for (int it0 = tid; it0 < items; it0 += T::NT * UW) {
+      f32x4 pv[UW][2];
+      u32x2_ qv[UW];
+      int wyv[UW], wxv[UW], cgv[UW];
+      bool okv[UW];
+#pragma unroll
+      for (int u = 0; u < UW; ++u) {
+        const int item = it0 + u * T::NT;
+        const int cg = item & 7, wdx = item >> 3;
+        int wr, wc;
+        conv_divmod(wdx, nwx, inv_nwx, wr, wc);
+        const int wy = wy0 + wr, wx = wx0 + wc;
+        cgv[u] = cg; wyv[u] = wy; wxv[u] = wx;
+        okv[u] = item < items && wy >= 0 && wy < Hp && wx >= 0 && wx < Wp && cg * 8 < a.Cin;
+        // unconditional loads from a clamped (always valid) window; the values of an invalid item are zeroed below
+        const int wyc = wy < 0 ? 0 : (wy >= Hp ? Hp - 1 : wy), wxc = wx < 0 ? 0 : (wx >= Wp ? Wp - 1 : wx);
+        const int cgc = cg * 8 < a.Cin ? cg : 0;
+        const size_t wo = ((size_t)wyc * Wp + wxc) * a.Cin + cgc * 8;
+        const float* pp = a.up2_src + (size_t)ntok * Hp * Wp * a.Cin + wo;
+        pv[u][0] = *reinterpret_cast<const f32x4*>(pp); pv[u][1] = *reinterpret_cast<const f32x4*>(pp + 4);
+        qv[u] = *reinterpret_cast<const u32x2_*>(a.up2_gpos + (size_t)img * Hp * Wp * a.Cin + wo);
+      }
+#pragma unroll
+      for (int u = 0; u < UW; ++u) {
+        if (it0 + u * T::NT >= items) continue;
+        const u32x4 z4u = {0u, 0u, 0u, 0u};
+        const u32x4 hiw = okv[u] ? __builtin_bit_cast(u32x4, pv[u][0]) : z4u;   // S_c as [hi8 | lo8]
+        const u32x4 low = okv[u] ? __builtin_bit_cast(u32x4, pv[u][1]) : z4u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                    // the window's four pixels: position j = 2 dy + dx
+          const int hy = 2 * wyv[u] + (j >> 1) - (h0 - 1), hx = 2 * wxv[u] + (j & 1) - (x0 - 1);
+          if (hy < 0 || hy >= a.hrows || hx < 0 || hx >= HALO_PITCH) continue;
+          // 16-bit lane c of a dword pair keeps its value iff channel c's arg-max sits at position j
+          u32x4 mh, ml;
+#pragma unroll
+          for (int d = 0; d < 4; ++d) {
+            const unsigned p0 = (qv[u][d >> 1] >> (16 * (d & 1))) & 0xFFu, p1 = (qv[u][d >> 1] >> (16 * (d & 1) + 8)) & 0xFFu;
+            const unsigned m = (p0 == (unsigned)j ? 0x0000FFFFu : 0u) | (p1 == (unsigned)j ? 0xFFFF0000u : 0u);
+            mh[d] = hiw[d] & m;
+            ml[d] = low[d] & m;
+          }
+          const int row = hy * HALO_PITCH + hx;
+          const int swzu = ((hy * a.tw + hx - 1) >> 1) & 7;
+          const int dst = (cgv[u] >> 2) * T::STAGE + row * LDS_STRIDE + (((2 * (cgv[u] & 3)) ^ swzu) << 2);
+          *reinterpret_cast<u32x4*>(smem + dst) = mh;
+          *reinterpret_cast<u32x4*>(smem + (dst ^ 4)) = ml;
+        }
+      }
+    }
+  };
+  // the chunk loop's prologue: chunk 0 of the resident image; chunk 1 follows in the loop.  (BREG2 with PW — the folded launch,
+  // at most two chunks: both, through the window loader above.  Chunk 1 by pw_load / pw_store items during chunk 0's steps, as on
+  // the BREG4 loop, was measured and lost to the first loop by 2 %; this form wins 7 %: profiles/breg2_ab.txt.)
+  [[maybe_unused]] auto bregc_chunk0 = [&]() {
+    if constexpr (PW && T::BREG2) {
+      breg_window_loader();
+    } else if constexpr (PW) {
       pw_load(pwi, tid, 0); pw_store(pwi, tid, 0, 0);
       if (tid + T::NT < pw_items) { pw_load(pwi, tid + T::NT, 0); pw_store(pwi, tid + T::NT, 0, 0); }
     } else
-    for (int p = wave_s; p < halo_np; p += T::NW) fire_halo_piece(prep_halo_piece(p, 0, true), p, 0);   // chunk 0; chunk 1 follows in the loop
+    for (int p = wave_s; p < halo_np; p += T::NW) fire_halo_piece(prep_halo_piece(p, 0, true), p, 0);
+  };
+  if constexpr (T::BREG2) {
+    // (its prologue runs behind the first weight loads, in front of the loop: see there)
+  } else if constexpr (T::BREGC) {
+    bregc_chunk0();
   } else if constexpr (BREG) {
     if (PREC == PREC_BF16X3 && a.up2_src) {
-      // compact pool interface (pairs of S_c, per-token tiles: the launcher checks): item = (window of the resident image,
-      // 8-channel group)
-      const int Hp = a.H >> 1, Wp = a.W >> 1;
-      const int h0 = Y0 - img0 * a.H;                      // the tile's first image row (tiles are per token)
-      const int wy0 = (h0 - 1) >> 1, wx0 = (x0 - 1) >> 1;  // (arithmetic shifts: -1 >> 1 = -1, the window row / column outside the image)
-      const int nwx = ((x0 + a.tw) >> 1) - wx0 + 1, nwy = ((h0 + a.th) >> 1) - wy0 + 1;
-      const int items = nwy * nwx * 8;
-      const int ntok = img0 < a.NB ? img0 : a.NB - 1;
-      const int img = a.row2img ? a.row2img[ntok] : ntok;
-      const float inv_nwx = 1.0f / (float)nwx;
-      constexpr int UW = 2;                                // items in flight per thread (2 x 16 B + 8 B of loads each)
-      typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
-      for (int it0 = tid; it0 < items; it0 += T::NT * UW) {
-        f32x4 pv[UW][2];
-        u32x2_ qv[UW];
-        int wyv[UW], wxv[UW], cgv[UW];
-        bool okv[UW];
-#pragma unroll
-        for (int u = 0; u < UW; ++u) {
-          const int item = it0 + u * T::NT;
-          const int cg = item & 7, wdx = item >> 3;
-          int wr, wc;
-          conv_divmod(wdx, nwx, inv_nwx, wr, wc);
-          const int wy = wy0 + wr, wx = wx0 + wc;
-          cgv[u] = cg; wyv[u] = wy; wxv[u] = wx;
-          okv[u] = item < items && wy >= 0 && wy < Hp && wx >= 0 && wx < Wp && cg * 8 < a.Cin;
-          // unconditional loads from a clamped (always valid) window; the values of an invalid item are zeroed below
-          const int wyc = wy < 0 ? 0 : (wy >= Hp ? Hp - 1 : wy), wxc = wx < 0 ? 0 : (wx >= Wp ? Wp - 1 : wx);
-          const int cgc = cg * 8 < a.Cin ? cg : 0;
-          const size_t wo = ((size_t)wyc * Wp + wxc) * a.Cin + cgc * 8;
-          const float* pp = a.up2_src + (size_t)ntok * Hp * Wp * a.Cin + wo;
-          pv[u][0] = *reinterpret_cast<const f32x4*>(pp); pv[u][1] = *reinterpret_cast<const f32x4*>(pp + 4);
-          qv[u] = *reinterpret_cast<const u32x2_*>(a.up2_gpos + (size_t)img * Hp * Wp * a.Cin + wo);
-        }
-#pragma unroll
-        for (int u = 0; u < UW; ++u) {
-          if (it0 + u * T::NT >= items) continue;
-          const u32x4 z4u = {0u, 0u, 0u, 0u};
-          const u32x4 hiw = okv[u] ? __builtin_bit_cast(u32x4, pv[u][0]) : z4u;   // S_c as [hi8 | lo8]
-          const u32x4 low = okv[u] ? __builtin_bit_cast(u32x4, pv[u][1]) : z4u;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {                    // the window's four pixels: position j = 2 dy + dx
-            const int hy = 2 * wyv[u] + (j >> 1) - (h0 - 1), hx = 2 * wxv[u] + (j & 1) - (x0 - 1);
-            if (hy < 0 || hy >= a.hrows || hx < 0 || hx >= HALO_PITCH) continue;
-            // 16-bit lane c of a dword pair keeps its value iff channel c's arg-max sits at position j
-            u32x4 mh, ml;
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {
-              const unsigned p0 = (qv[u][d >> 1] >> (16 * (d & 1))) & 0xFFu, p1 = (qv[u][d >> 1] >> (16 * (d & 1) + 8)) & 0xFFu;
-              const unsigned m = (p0 == (unsigned)j ? 0x0000FFFFu : 0u) | (p1 == (unsigned)j ? 0xFFFF0000u : 0u);
-              mh[d] = hiw[d] & m;
-              ml[d] = low[d] & m;
-            }
-            const int row = hy * HALO_PITCH + hx;
-            const int swzu = ((hy * a.tw + hx - 1) >> 1) & 7;
-            const int dst = (cgv[u] >> 2) * T::STAGE + row * LDS_STRIDE + (((2 * (cgv[u] & 3)) ^ swzu) << 2);
-            *reinterpret_cast<u32x4*>(smem + dst) = mh;
-            *reinterpret_cast<u32x4*>(smem + (dst ^ 4)) = ml;
-          }
-        }
-      }
+      breg_window_loader();
     } else
     for (int p = wave_s; p < halo_np; p += T::NW) {         // channel chunks 0 and 1 -> LDS buffers 0 and 1
       fire_halo_piece(prep_halo_piece(p, 0, true), p, 0);
@@ -450,7 +468,7 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
 #pragma unroll
     for (int s_ = 2; s_ < NS; ++s_) fire_chunk(prep_chunk(nk > s_), s_);
   }
-  conv_dma_oldest_landed_barrier<T>();
+  if constexpr (!T::BREG2) conv_dma_oldest_landed_barrier<T>();
 
   const int a_off = HALO ? 0 : (wm * TM * 32 + (lane & 31)) * LDS_STRIDE;
   const int b_off = T::ABUF + (wn * TN * 32 + (lane & 31)) * LDS_STRIDE;
@@ -590,6 +608,9 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     // ONE basic block — dead pieces and prefetches past the end are clamped or go to a spare LDS slot instead of being
     // branched around — so that hipcc counts every wait.  Same MFMA chain per output element as every other form: chunk-major,
     // taps innermost, two k16 steps, al*bh, ah*bl, ah*bh.
+    // BREG2 (TM x TN = 2 x 1, the N <= 64 launches): the same 24 pieces; a weight step is two loads and six MFMAs.  PW there is the
+    // folded launch (per-token tiles, at most two chunks): the window loader has built both chunks in the prologue, no piece arrives
+    // during the loop.  The first two weight steps are requested in front of the resident image (see below).
     // BREG4 (TM x TN = 2 x 2): a 12-row resident image is 24 pieces = six per wave as well, and two outstanding weight steps
     // are again 2 x 2 TN = 8 loads.  The fp16-pair dual forward rides on the same loop: TERMS 23 leaves out the lo half of the
     // odd column tiles (Z+; three loads per step, six outstanding), and the blocked accumulation folds acc into tot behind the
@@ -615,6 +636,12 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
     };
     load_b(bq[0], 0);
     load_b(bq[1], 1);
+    if constexpr (T::BREG2) {
+      // the first two weight steps depend on nothing the image barrier protects: requested in front of the resident image, their
+      // round trip runs under the image's (a tile of the N <= 64 launches is 18 or 36 steps long: every exposed round trip counts)
+      bregc_chunk0();
+      conv_dma_landed_barrier();
+    }
     set_tap(0);
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
@@ -633,7 +660,9 @@ __global__ __launch_bounds__(64 * WM * WN, BREG && WM * WN != 8 && TN == 1 ? 3 :
 #pragma unroll
       for (int s = 0; s < 18; ++s) {
         load_b(bq[(s + 2) % 3], c * 18 + s + 2);
-        if constexpr (PW) {
+        if constexpr (PW && T::BREG2) {
+          // (both chunks were built in the prologue: nothing arrives during the loop)
+        } else if constexpr (PW) {
           // compact pool interface: behind the hand-over barrier of chunk c - 1 the other buffer is free for all of chunk c.  The two
           // items of a thread go through the same ten registers one after the other: loaded early, written mid-chunk; the
           // lgkmcnt(0) in front of the next hand-over covers the writes.  (Unconditional: a dead item loads from a clamped

@@ -106,14 +106,18 @@ inline hipError_t conv_launch_img(ConvArgs a, hipStream_t st) {
 }
 
 // one arm of conv_launch_epi: entry I of CONV_FORM_TILES, compiled only where this (EPI, PREC, TERMS, GMASK, DG) has a kernel on it
+// FORM_BREG has two loops, and which one a launch runs on is decided here, not in the plan: the chunk loop where it exists (the
+// dense split-bf16 walk) unless LRP_CONV_BREG2=0; on it, a launch that reads the compact pool interface takes the PW instantiation.
 template <int I, int EPI, int PREC, int TERMS, bool GMASK, bool DG>
 inline bool conv_launch_form(const ConvPlan& p, ConvArgs& a, hipStream_t st) {
   constexpr ConvFormTile F = CONV_FORM_TILES[I];
-  if constexpr (conv_kernel_exists(F.form, F.BM, F.BN, F.pw, EPI, PREC, TERMS, GMASK, DG)) {
-    if (p.form != F.form || p.BM != F.BM || p.BN != F.BN || p.pw != F.pw) return false;
-    constexpr ConvKernelShape K = conv_kernel_shape(F.form, F.BM, F.BN, F.pw);
+  if constexpr (conv_kernel_exists(F.form, F.BM, F.BN, F.pw, EPI, PREC, TERMS, GMASK, DG, F.c2)) {
+    const bool c2 = p.form == FORM_BREG && sw().conv_breg2 && conv_kernel_exists(FORM_BREG, 128, 64, false, EPI, PREC, TERMS, GMASK, DG, true);
+    const bool pw = p.pw || (c2 && a.up2_src);
+    if (p.form != F.form || p.BM != F.BM || p.BN != F.BN || pw != F.pw || c2 != F.c2) return false;
+    constexpr ConvKernelShape K = conv_kernel_shape(F.form, F.BM, F.BN, F.pw, F.c2);
     if (K.HALO && (EPI == EPI_MUL || EPI == EPI_MUL_UP2)) a.tile_map = conv_tile_order(a, st);
-    hipLaunchKernelGGL((conv_igemm_kernel<K.WM, K.WN, K.TM, K.TN, EPI, PREC, K.HALO, K.BREG, TERMS, K.NS, GMASK, K.PW, DG>),
+    hipLaunchKernelGGL((conv_igemm_kernel<K.WM, K.WN, K.TM, K.TN, EPI, PREC, K.HALO, K.BREG, TERMS, K.NS, GMASK, K.PW, DG, K.C2>),
                        dim3(p.m_tiles * p.n_tiles), dim3(p.threads), 0, st, a);
     return true;
   }

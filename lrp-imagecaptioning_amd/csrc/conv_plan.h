@@ -32,7 +32,7 @@ enum ConvForm {
   FORM_PLAIN = 0,   // A and B staged per k-step, 128 x 128 / 128 x 64 / 128 x 32 / 8-wave 256 x 256
   FORM_SMALL = 1,   // small grids: 64 x 64 tiles, CONV_SMALL_NS-stage k pipeline
   FORM_HALO = 2,    // resident image (3x3, split operands), 128 x 128 / 128 x 64 / 8-wave 256 x 256
-  FORM_BREG = 3,    // resident image + weights in registers (N <= 64), 128 x 64
+  FORM_BREG = 3,    // resident image + weights in registers (N <= 64), 128 x 64; two loops: the launcher's choice (LRP_CONV_BREG2, conv_launch.h)
   FORM_POOL = 4,    // FORM_HALO 128 x 128 with tiles of even height and width: the 2x2 max-pool in the dual forward's epilogue
   FORM_IMG = 5,     // EPI_IMG_STENCIL: 16 x 16 pixel patches
   FORM_BREG8 = 6,   // FORM_HALO's 8-wave 256 x 256 tile with the weights in registers (dense split-bf16 EPI_MUL, N % 256 == 0)
@@ -95,15 +95,20 @@ constexpr int conv_terms(int prec, int terms, bool dual) { return prec == PREC_F
 // through the kernel's PW axis — FORM_BREG4 only; the pipelined tiles decide that at run time.
 //   FORM_PLAIN / FORM_SMALL   everything (the 8-wave tile: split operands, one gate)
 //   FORM_HALO                 split operands, the MUL and forward epilogues; dual gate: split-bf16 on the 128 x 128 tile
-//   FORM_BREG                 the MUL epilogues, both split formats
+//   FORM_BREG                 the MUL epilogues, both split formats; the dense split-bf16 walk (EPI_MUL, PREC_BF16X3) also on the
+//                             chunk loop (c2), there with the PW axis
 //   FORM_BREG8                the dense split-bf16 walk: EPI_MUL, PREC_BF16X3
 //   FORM_BREG4                the same, and the fp16-pair dual forward (TERMS 7 / 23)
 //   FORM_POOL, FORM_BREG4_POOL   the fp16-pair dual forward (the kernels of FORM_HALO 128 x 128 / FORM_BREG4)
 // Not built, and refused: a dual gate on the 8-wave tile or on a weights-in-registers form, byte masks off the staged tiles.
 // (The 8-wave tiles of the fp16-pair FORWARD epilogues are instantiated although no plan answers them — conv_plan: blocked
 // accumulation does not fit that tile.)
-constexpr bool conv_kernel_exists(int form, int BM, int BN, bool pw, int epi, int prec, int terms, bool gmask, bool dual) {
+// c2: FORM_BREG's second loop (the chunk loop of FORM_BREG8 / FORM_BREG4 on the 128 x 64 tile; LRP_CONV_BREG2) — a property of the
+// kernel the launcher picks, not of the plan: the dense split-bf16 walk only, with or without the PW axis.
+constexpr bool conv_kernel_exists(int form, int BM, int BN, bool pw, int epi, int prec, int terms, bool gmask, bool dual, bool c2 = false) {
   if (!conv_epi_exists(epi, prec, terms, gmask, dual)) return false;
+  if (c2 && !(form == FORM_BREG && epi == EPI_MUL && prec == PREC_BF16X3 && !dual && BM == 128 && BN == 64)) return false;
+  if (pw && form == FORM_BREG) return c2;
   const bool mul = epi == EPI_MUL || epi == EPI_MUL_UP2, fwd = epi == EPI_BIAS || epi == EPI_BIAS_RELU || epi == EPI_FWD_DUAL;
   const bool split = prec != PREC_FP32, walk = epi == EPI_MUL && prec == PREC_BF16X3, pairs_fwd = epi == EPI_FWD_DUAL && prec == PREC_F16X2;
   const bool t128 = BM == 128 && BN == 128, t64 = BM == 128 && BN == 64, t32 = BM == 128 && BN == 32, t256 = BM == 256 && BN == 256;
@@ -120,18 +125,19 @@ constexpr bool conv_kernel_exists(int form, int BM, int BN, bool pw, int epi, in
   }
   return false;
 }
-// every (form, tile, pw) some epilogue has a kernel for: what conv_launch_epi dispatches over
-struct ConvFormTile { int form, BM, BN; bool pw; };
+// every (form, tile, pw, c2) some epilogue has a kernel for: what conv_launch_epi dispatches over
+struct ConvFormTile { int form, BM, BN; bool pw, c2 = false; };
 constexpr ConvFormTile CONV_FORM_TILES[] = {
     {FORM_PLAIN, 128, 128, false}, {FORM_PLAIN, 128, 64, false}, {FORM_PLAIN, 128, 32, false}, {FORM_PLAIN, 256, 256, false},
     {FORM_SMALL, 64, 64, false},   {FORM_HALO, 128, 128, false}, {FORM_HALO, 128, 64, false},  {FORM_HALO, 256, 256, false},
     {FORM_BREG, 128, 64, false},   {FORM_POOL, 128, 128, false}, {FORM_IMG, 256, 64, false},   {FORM_BREG8, 256, 256, false},
-    {FORM_BREG4, 128, 128, false}, {FORM_BREG4, 128, 128, true}, {FORM_BREG4_POOL, 128, 128, false}};
+    {FORM_BREG4, 128, 128, false}, {FORM_BREG4, 128, 128, true}, {FORM_BREG4_POOL, 128, 128, false},
+    {FORM_BREG, 128, 64, false, true}, {FORM_BREG, 128, 64, true, true}};
 constexpr int CONV_FORM_TILE_COUNT = sizeof(CONV_FORM_TILES) / sizeof(CONV_FORM_TILES[0]);
 
 // the kernel's template arguments for a (form, tile, pw): BM = 32 WM TM, BN = 32 WN TN; see the tile configurations above
-struct ConvKernelShape { int WM, WN, TM, TN; bool HALO, BREG; int NS; bool PW; };
-constexpr ConvKernelShape conv_kernel_shape(int form, int BM, int BN, bool pw) {
+struct ConvKernelShape { int WM, WN, TM, TN; bool HALO, BREG; int NS; bool PW, C2 = false; };
+constexpr ConvKernelShape conv_kernel_shape(int form, int BM, int BN, bool pw, bool c2 = false) {
   const bool breg = form == FORM_BREG || form == FORM_BREG8 || form == FORM_BREG4 || form == FORM_BREG4_POOL;
   const bool halo = breg || form == FORM_HALO || form == FORM_POOL;
   const int ns = form == FORM_SMALL ? CONV_SMALL_NS : 2;
@@ -139,16 +145,16 @@ constexpr ConvKernelShape conv_kernel_shape(int form, int BM, int BN, bool pw) {
   if (BM == 256) return {2, 4, 4, 2, halo, breg, ns, pw};
   if (BM == 64) return {2, 2, 1, 1, halo, breg, ns, pw};
   if (BN == 128) return {2, 2, 2, 2, halo, breg, ns, pw};
-  if (BN == 64) return {2, 2, 2, 1, halo, breg, ns, pw};
+  if (BN == 64) return {2, 2, 2, 1, halo, breg, ns, pw, c2};
   return {4, 1, 1, 1, halo, breg, ns, pw};
 }
 // the kernel's own question: is this set of template arguments one of the above?
 constexpr bool conv_kernel_instantiated(int WM, int WN, int TM, int TN, bool HALO, bool BREG, int NS, bool PW, int epi, int prec, int terms,
-                                        bool gmask, bool dual) {
+                                        bool gmask, bool dual, bool C2 = false) {
   for (const ConvFormTile& f : CONV_FORM_TILES) {
-    const ConvKernelShape k = conv_kernel_shape(f.form, f.BM, f.BN, f.pw);
-    if (k.WM == WM && k.WN == WN && k.TM == TM && k.TN == TN && k.HALO == HALO && k.BREG == BREG && k.NS == NS && k.PW == PW &&
-        conv_kernel_exists(f.form, f.BM, f.BN, f.pw, epi, prec, terms, gmask, dual))
+    const ConvKernelShape k = conv_kernel_shape(f.form, f.BM, f.BN, f.pw, f.c2);
+    if (k.WM == WM && k.WN == WN && k.TM == TM && k.TN == TN && k.HALO == HALO && k.BREG == BREG && k.NS == NS && k.PW == PW && k.C2 == C2 &&
+        conv_kernel_exists(f.form, f.BM, f.BN, f.pw, epi, prec, terms, gmask, dual, f.c2))
       return true;
   }
   return false;

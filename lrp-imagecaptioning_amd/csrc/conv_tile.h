@@ -20,10 +20,10 @@ namespace lrp {
 // floor(160 KB / LDS per block) blocks of NW waves
 constexpr int conv_min_waves(int NW, int TM, int TN, bool halo = false) { return NW == 8 || halo ? 2 : (TM * TN >= 4 ? 2 : 3); }
 
-template <int WM_, int WN_, int TM_, int TN_, int EPI_, int PREC_, bool HALO_, bool BREG_, int TERMS_, int NS_, bool GMASK_, bool PW_, bool DG_>
+template <int WM_, int WN_, int TM_, int TN_, int EPI_, int PREC_, bool HALO_, bool BREG_, int TERMS_, int NS_, bool GMASK_, bool PW_, bool DG_, bool C2_ = false>
 struct ConvKernelTraits {
   static constexpr int WM = WM_, WN = WN_, TM = TM_, TN = TN_, EPI = EPI_, PREC = PREC_, TERMS = TERMS_, NS = NS_;
-  static constexpr bool HALO = HALO_, BREG = BREG_, GMASK = GMASK_, PW = PW_, DG = DG_;
+  static constexpr bool HALO = HALO_, BREG = BREG_, GMASK = GMASK_, PW = PW_, DG = DG_, C2 = C2_;
 
   static constexpr int NW = WM * WN, NT = 64 * NW;           // waves / threads per block (4 or 8 waves)
   static constexpr bool SPLIT = PREC != PREC_FP32;            // operands in split8 form (bf16 or fp16 pairs): 16 k per MFMA
@@ -34,11 +34,13 @@ struct ConvKernelTraits {
   static constexpr int STAGE = ABUF + (BREG ? 0 : BN) * LDS_STRIDE;
   static constexpr bool BREG8 = BREG && NW == 8;              // the 8-wave 256 x 256 tile with its weights in registers (the kernel's first loop)
   static constexpr bool BREG4 = BREG && NW == 4 && TN == 2;   // the same loop on the 4-wave 128 x 128 tile (FORM_BREG4: walk and dual forward)
-  static constexpr bool BREGC = BREG8 || BREG4;               // weights in registers, one barrier per channel CHUNK
+  static constexpr bool BREG2 = BREG && NW == 4 && TN == 1 && C2;   // the same loop on the 4-wave 128 x 64 tile (FORM_BREG under LRP_CONV_BREG2: the walk's N <= 64 launches)
+  static constexpr bool BREGC = BREG8 || BREG4 || BREG2;      // weights in registers, one barrier per channel CHUNK
+  static_assert(!C2 || BREG2, "C2: the chunk loop of the 128 x 64 weights-in-registers tile");
   static_assert(!BREG || (HALO && SPLIT && (BREGC || BM * BN <= 2 * STAGE)), "BREG needs the resident image");
-  // which tiles, forms and epilogues go together — BREG8 / BREG4: the dense split-bf16 walk (and, BREG4, the fp16-pair dual forward);
-  // PW: that walk on the BREG4 loop; DG: the MUL epilogues of the 4-wave staged / pipelined tiles — is conv_plan.h's table
-  static_assert(conv_kernel_instantiated(WM, WN, TM, TN, HALO, BREG, NS, PW, EPI, PREC, TERMS, GMASK, DG), "no such instantiation: conv_plan.h conv_kernel_exists");
+  // which tiles, forms and epilogues go together — BREG8 / BREG4 / BREG2: the dense split-bf16 walk (and, BREG4, the fp16-pair dual forward);
+  // PW: that walk on the BREG4 / BREG2 loop; DG: the MUL epilogues of the 4-wave staged / pipelined tiles — is conv_plan.h's table
+  static_assert(conv_kernel_instantiated(WM, WN, TM, TN, HALO, BREG, NS, PW, EPI, PREC, TERMS, GMASK, DG, C2), "no such instantiation: conv_plan.h conv_kernel_exists");
   static_assert((BM / 8) % NW == 0 && (BN / 8) % NW == 0, "pieces must divide over the waves");
   static_assert(!HALO || EPI != EPI_STORE, "the image layer is a 1-tap GEMM");
   static_assert(NS == 2 || (NS > 2 && !HALO && !BREG), "deeper staging exists for the plain (non-resident) A path only");
@@ -46,8 +48,9 @@ struct ConvKernelTraits {
   static_assert((NS - 2) * DPC <= 63, "vmcnt is a 6-bit counter");
   // BREG8: no B stage, so LDS is the two resident images or one 128-row C slab of the epilogue, whichever is larger (128 KB)
   // BREG4: the two resident images + a spare slot per wave (52 KB) or the epilogue's whole 128 x 128 C tile (64 KB; 80 KB pipelined)
+  // BREG2: the same 52 KB (the 128 x 64 C tile is 32 KB): three workgroups per CU
   static constexpr int SMEM = BREG8   ? (2 * STAGE > BM / 2 * BN ? 2 * STAGE : BM / 2 * BN)
-                              : BREG4 ? (2 * STAGE + NW * 8 * LDS_STRIDE > BM * BN ? 2 * STAGE + NW * 8 * LDS_STRIDE : BM * BN)
+                              : BREG4 || BREG2 ? (2 * STAGE + NW * 8 * LDS_STRIDE > BM * BN ? 2 * STAGE + NW * 8 * LDS_STRIDE : BM * BN)
                                       : NS * STAGE;
   static constexpr int CSLAB = BREGC ? SMEM : 2 * STAGE;      // floats the epilogue's C slab may take
 

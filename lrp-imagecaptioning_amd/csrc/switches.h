@@ -14,6 +14,8 @@ struct Switches {
                             //                     also read when weights are set: only then are the layers' fragment-major copies made
   int conv_breg4 = 1;       // LRP_CONV_BREG4=0    the 128 x 128 resident-image launches with N % 128 == 0 (dense split-bf16 walk, interleaved dual forward) on the
                             //                     pipelined kernel; also read when weights are set: only then are the fragment-major copies made
+  int conv_breg2 = 1;       // LRP_CONV_BREG2=0    the N <= 64 weights-in-registers launches of the dense split-bf16 walk (FORM_BREG) on their first loop
+                            //                     (whole fragment sets double-buffered, a full stop between channel groups) instead of the chunk loop; a per-launch switch only
   int conv_sparse_wreg = 1; // LRP_CONV_SPARSE_WREG=0  the large form of the 2:4-sparse pooled consumers (conv_sparse.h) on the LDS-stage loop (weights by
                             //                     LDS-DMA into four stages, a barrier every second k-step) instead of the weights-in-registers loop
   int conv_small = 1;       // LRP_CONV_SMALL=0    small grids keep the 128-row tiles (no 64 x 64 tiles)
@@ -40,6 +42,7 @@ struct Switches {
     // switch's run against the default path — operator and engine level, bit-identical — is tests/test_gpu_conv_breg8.py)
     if (const char* e = getenv("LRP_CONV_BREG8")) conv_breg8 = atoi(e);
     if (const char* e = getenv("LRP_CONV_BREG4")) conv_breg4 = atoi(e);   // (likewise: tests/test_gpu_conv_breg4.py)
+    if (const char* e = getenv("LRP_CONV_BREG2")) conv_breg2 = atoi(e);   // (likewise: tests/test_gpu_conv_breg2.py)
     if (const char* e = getenv("LRP_CONV_SPARSE_WREG")) conv_sparse_wreg = atoi(e);   // (likewise: tests/test_gpu_conv_sparse_wreg.py)
   }
 };
